@@ -16,16 +16,21 @@ this process starts the N rank processes itself, before it touches the GPU.  The
 the gathering of finished frames -- there is no data-path collective, scaling is weak.  `rccl_ranks` (ncclCommCount) and
 `per_rank` in the line show that N ranks met and what each measured.
 
+A plain run (no --full) does what the headline needs and nothing else: it sets the chunks up, warms them up, times --steps steps,
+writes what the last step computed if --dump-outputs DIR is given (benchlib/dump.py) and prints the line.  --full adds the self-checks of
+the timed frames and every leg below.
+
 Prints ONE JSON line on rank 0 with, besides the contract's fields,
   roofline       the dominant kernel ALONE on the part (solo: one chunk per launch, HIP events of its own dispatch) as algorithmic
                  bytes / time vs 8 TB/s; beside it time_shared (the launches of the timed region) and path (3.0 KB per macroblock)
   issue_roofline the resource that does bound the path: VALU issue CYCLES (per-opcode cost x PMC instruction counts)
+  self_check     one chunk of the timed region coded again on its own, every chunk against the CPU oracle's digests   (--full)
   cpu_baseline   the CPU oracle (oracle/vp8_oracle.c, OpenMP) on a bounded sample of the same workload, and the reference's own
-                 kernels compiled for x86 on one core                                                   (N = 1 only)
-  with_bitstream the same frames with finished VP8 frames delivered to host memory                     (N = 1 only)
+                 kernels compiled for x86 on one core                                           (--full, N = 1 only)
+  with_bitstream the same frames with finished VP8 frames delivered to host memory             (--full, N = 1 only)
   from_host_memory  the rate WITH the host-device link in it: every source frame copied in from page-locked host memory inside the
-                 timed loop (vp8hip_batch_upload_current), without and with the finished frames delivered back   (N = 1 only)
-The legs that are ONE or TWO videos coded frame after frame, and the other geometries, run in a child process per rank (--child-legs;
+                 timed loop (vp8hip_batch_upload_current), without and with the finished frames delivered back   (--full, N = 1 only)
+The legs that are ONE or TWO videos coded frame after frame, and the other geometries, run in a child process per rank (--full; --child-legs;
 a process keeps every hardware queue it ever used; and a leg that dies -- destroying dozens of contexts has, rarely,
 ended a process inside the runtime -- takes only itself along: the child hands every finished leg over at once, the parent keeps
 the headline's contexts until the line is out and leaves without tearing anything down):
@@ -70,13 +75,19 @@ def parse():
                     help="GOP chunks per batched launch (1 = every chunk launches its own kernels on its own stream; up to 8)")
     ap.add_argument("--refs", choices=["all", "last"], default="all", help="last = LAST only (BASELINE configs[1]: use_golden = use_altref = 0)")
     ap.add_argument("--ssim-target", type=float, default=-1.0, help="SSIM_target (reference default -1 = single LQ pass; 0.93 = the 4-pass path)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--no-side-legs", action="store_true", help="skip single_stream / other_configs / with_bitstream")
-    ap.add_argument("--only-bitstream", action="store_true", help="of the side legs only with_bitstream (same-box A/B runs)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: its self-checks, the side legs and the CPU baseline "
+                    "(off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg of --full (0 = skip)")
+    ap.add_argument("--no-side-legs", action="store_true", help="of --full: skip single_stream / other_configs / with_bitstream")
+    ap.add_argument("--only-bitstream", action="store_true", help="of --full: of the side legs only with_bitstream (same-box A/B runs)")
     ap.add_argument("--profile-all", action="store_true", help="time every kernel with hipEvents in the timed region (adds packets)")
     ap.add_argument("--spawn", action="store_true", help="start the rank processes from here even for --gpus 1 (the N > 1 launch path)")
     ap.add_argument("--child-legs", choices=["few", "other"], default=None, help=argparse.SUPPRESS)   # internal: side legs in a fresh process
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.only_bitstream and not args.full:
+        ap.error("--only-bitstream selects among the legs of --full: add --full")
+    return args
 
 
 
@@ -139,9 +150,9 @@ def main():
         os.close(json_fd)
         sys.exit(0)          # (through the ordinary teardown: every context of every leg has been destroyed by now)
     # ---- side legs in fresh processes, BEFORE this process makes a stream (benchlib/children.py says why) --------------------------
-    run_children = not args.no_side_legs and not args.only_bitstream
+    run_children = args.full and not args.no_side_legs and not args.only_bitstream
     from benchlib import children
-    child_out, child_rc = children.run_child_legs(args, dist, rdzv_key, world, os.path.abspath(__file__))
+    child_out, child_rc = children.run_child_legs(args, dist, rdzv_key, world, os.path.abspath(__file__)) if args.full else (b"", 0)
     # the product north_star names -- the reference's own main() on libvp8hip.so, .y4m to .ivf, fresh processes (benchlib/drop_in.py) -- also
     # before this process holds a queue
     drop_in = None
@@ -152,8 +163,12 @@ def main():
     from benchlib.headline import run_headline
     hl = run_headline(args, api, lib, dist, rank, world, local, nd, barrier, affinity, experiment_build)
     leg, out = hl.leg, hl.out
+    # ---- what the timed path computed in its last step, before any side leg moves the chunks on ------------------------------------
+    if args.dump_outputs and rank == 0:
+        from benchlib.dump import dump_outputs
+        dump_outputs(leg, args.dump_outputs)
     # ---- side legs on the headline's own chunks: reported next to the headline value, never as it ---------------------------------
-    if rank == 0 and world == 1 and not args.no_side_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_side_legs:
         from benchlib.legs_bitstream import frames_out_legs
         frames_out_legs(leg, args, out, experiment_build)
     host_frames = leg.host_frames
@@ -161,7 +176,7 @@ def main():
         children.merge_child_legs(out, child_out, child_rc, hl.dominant, hl.W, hl.H)
     if drop_in is not None and rank == 0:
         out["drop_in"] = drop_in
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
         os.sched_setaffinity(0, all_cpus)       # the CPU baseline gets every host core again, not the GPU's NUMA node only
         from benchlib.cpu_baseline import cpu_baseline
         out["cpu_baseline"] = cpu_baseline(args, api, host_frames, hl.W, hl.H, hl.mbs)

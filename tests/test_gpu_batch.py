@@ -268,7 +268,7 @@ def test_bench_with_the_switchable_forms_of_the_search_kernels_codes_the_same_fr
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-side-legs", "--cpu-seconds", "0",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-side-legs", "--cpu-seconds", "0",
                         "--gops-per-gpu", "12", "--batch", "6"], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][0])

@@ -156,7 +156,7 @@ def test_bench_with_two_ranks_on_one_gpu(tmp_path, standin):
     does except RCCL itself and the second GPU.  The rates mean nothing (two ranks share one GPU and a host-memory transport)."""
     env = dict(os.environ, VP8HIP_RCCL_LIBRARY=standin, VP8HIP_RENDEZVOUS_DIR=str(tmp_path), VP8_BENCH_ALL_RANKS_ON_DEVICE="0",
                VP8_BENCH_CHILD_TIMEOUT="600")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--cpu-seconds", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--cpu-seconds", "0",
                         "--gops-per-gpu", "12", "--batch", "6"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -182,7 +182,7 @@ def test_bench_with_eight_ranks_on_one_gpu_codes_configs4_per_rank(tmp_path, sta
     itself; the rates mean nothing."""
     env = dict(os.environ, VP8HIP_RCCL_LIBRARY=standin, VP8HIP_RENDEZVOUS_DIR=str(tmp_path), VP8_BENCH_ALL_RANKS_ON_DEVICE="0",
                VP8_BENCH_CHILD_TIMEOUT="1200", VP8_BENCH_REFSHARD_FRAMES="8", VP8_BENCH_RDZV_TIMEOUT="600", VP8HIP_QUIET="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "0",
                         "--gops-per-gpu", "4", "--batch", "4"], env=env, capture_output=True, text=True, timeout=2400)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]

@@ -272,8 +272,10 @@ def test_fuzz_one_seed():
 
 
 def _bench(*extra):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-side-legs",
-                        "--cpu-seconds", "0", *extra], capture_output=True, text=True, timeout=900)
+    # the hardware queues are the library's own choice (16) here, whatever the calling environment exports
+    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full",
+                        "--no-side-legs", "--cpu-seconds", "0", *extra], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, "bench.py must print exactly ONE JSON line:\n" + r.stdout[-2000:] + r.stderr[-2000:]
@@ -308,7 +310,7 @@ def test_bench_under_torchrun_runs_its_child_legs():
     PyTorch: the rank and the child process of its one- and two-video legs form the library's own RCCL groups (file rendezvous keyed by
     the launcher's pid and port) and never import torch -- one HIP runtime, the one libvp8hip.so was built for, at every N."""
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", "29557", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--cpu-seconds", "0"],
+                        "--master-port", "29557", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--cpu-seconds", "0"],
                        capture_output=True, text=True, timeout=900, env=dict(os.environ, VP8_BENCH_CHILD_TIMEOUT="300", VP8_BENCH_FORCE_DIST="1"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -323,6 +325,32 @@ def test_bench_under_torchrun_runs_its_child_legs():
 def test_bench_last_only_config():
     d = _bench("--refs", "last", "--width", "1280", "--height", "720")
     assert d["config"]["refs_per_frame"] == 1.0 and d["config"]["macroblocks_per_frame"] == 3600
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, runs no self-check and no side leg, and --dump-outputs writes what the last
+    step computed: float32 / float64 arrays, 64 MB at most, the same bytes from two runs with the same arguments."""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                            "--gops-per-gpu", "12", "--batch", "6", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["config"]["frames_per_gpu"] == 4 * 12 and d["ms_per_step"] > 0
+        assert abs(d["ms_per_step"] * 4 / 1e3 - d["timed_region_s"]) < 1e-3
+        assert not {"self_check", "single_stream", "other_configs", "with_bitstream", "cpu_baseline", "drop_in"} & set(d), sorted(d)
+        files = sorted(out.glob("*.npy"))
+        arrays = {f.stem: np.load(f) for f in files}
+        assert {"recon_crc32", "recon_y", "mb_coeffs"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        assert arrays["recon_crc32"].shape == (12, 3) and arrays["recon_y"].shape[0] == 12
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 WORKER = textwrap.dedent("""
