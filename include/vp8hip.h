@@ -191,9 +191,16 @@ int vp8hip_set_source_size(vp8hip_ctx *ctx, int src_width, int src_height);
  * recomputes them from the device copy, e.g. after vp8hip_upload_mb_data.) */
 int vp8hip_prepare_filter_mask(vp8hip_ctx *ctx, int32_t *nz_out);
 
-/* do_loop_filter(), loop_filter.h:185-190: normal loop filter on the reconstruction, in place,
- * after which that reconstruction IS the LAST reference of the next vp8hip_inter_transform. */
+/* do_loop_filter(), loop_filter.h:185-190: the loop filter of the context's type (vp8hip_set_loop_filter_type; the normal
+ * filter by default) on the reconstruction, in place, after which that reconstruction IS the LAST reference of the next
+ * vp8hip_inter_transform. */
 int vp8hip_loop_filter(vp8hip_ctx *ctx);
+/* The loop filter vp8hip_loop_filter / vp8hip_batch_loop_filter apply from the next call on: 0 = the normal filter (RFC 6386
+ * section 15.3, the default and the reference's), 1 = the simple filter (section 15.2: luma only, p0 and q0 only, no hev; a
+ * macroblock whose segment has loop_filter_level 0 is skipped and the rest of the plane is filtered).  The frame header's
+ * filter_type bit (vp8hip_header_params / vp8bs_frame.loop_filter_type) must say the same, or decoders drift from the encoder's
+ * reconstruction.  Any other value: VP8HIP_ERR_ARG. */
+int vp8hip_set_loop_filter_type(vp8hip_ctx *ctx, int type);
 /* on = 1: the context gets a second stream, and work that does not depend on the filtered frame runs beside the loop filter:
  * the entropy stage of the same frame (vp8hip_count_probs ... vp8hip_encode_frame), the next frame's upload, parameter scan
  * and GOLDEN / ALTREF searches.  The filter stays on the stream the frame was coded on and the CONTEXT moves to the other one
@@ -241,7 +248,7 @@ int vp8hip_encode_coefficients(vp8hip_ctx *ctx, const uint32_t *coeff_probs, int
 #define VP8HIP_SHARPNESS_ON_DEVICE INT32_MIN
 typedef struct {
     int32_t is_key, is_golden, is_altref;    /* frames.current_is_{key,golden,altref}_frame */
-    int32_t loop_filter_type;                /* video.loop_filter_type (0) */
+    int32_t loop_filter_type;                /* video.loop_filter_type: 0 normal, 1 simple -- the filter the context applies (vp8hip_set_loop_filter_type) */
     int32_t loop_filter_sharpness;           /* video.loop_filter_sharpness; VP8HIP_SHARPNESS_ON_DEVICE = the value vp8hip_auto_segments
                                                 computed.  (Not -1: get_loopfilter_strength's `int` accumulator overflows on large noisy
                                                 frames, vp8enc.cpp:112-126, and the sharpness it then leaves is NEGATIVE -- -1 on a 1080p
@@ -311,8 +318,8 @@ const char *vp8hip_status_string(int status);
  * -- return values and counters provisional until vp8drv_resolve -- in round 3: 3), MINOR when entry points are added.  A host
  * built against an older header checks it once after loading the library.  3001: the shard, device-memory and frame-check entry points;
  * 3002: vp8drv_encode_video_device; 3003: vp8hip_import_last, vp8hip_group_*, the load-time hardware-queue setting;
- * vp8drv_frame_check folds position in (4: its values change). */
-#define VP8HIP_ABI_VERSION 4008
+ * vp8drv_frame_check folds position in (4: its values change); 4009: vp8hip_set_loop_filter_type and vp8drv_config.loop_filter_type. */
+#define VP8HIP_ABI_VERSION 4009
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait
  * (VP8HIP_EXPERIMENT_SKIP, VP8HIP_EXPERIMENT_SKIP_ENT, VP8HIP_EXPERIMENT_NOWAIT, VP8DRV_EXPERIMENT_READY_FIRST; built with

@@ -66,9 +66,12 @@ typedef struct {
                                 runs on the device (vp8hip_set_source_size) and key frames carry this size as the display
                                 size unless display_width/height say otherwise.  0 = frames of the coded size.  Needs
                                 device_params = 1 */
+    int32_t loop_filter_type;    /* 0 (default): the normal loop filter, the reference's; 1: the simple loop filter (RFC 6386
+                                section 15.2, vp8hip_set_loop_filter_type), written into every frame header.  Other values:
+                                vp8drv_create returns VP8HIP_ERR_ARG.  Members of a batch must agree */
 } vp8drv_config;
 
-void vp8drv_default_config(vp8drv_config *cfg);   /* the reference's defaults: 150, 5, 0, 48, -1, 1, 1, 1, 0, 0, 0, 0, 3, 0, 0, 0, 0 */
+void vp8drv_default_config(vp8drv_config *cfg);   /* the reference's defaults: 150, 5, 0, 48, -1, 1, 1, 1, 0, 0, 0, 0, 3, 0, 0, 0, 0, 0 */
 
 int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const vp8drv_config *cfg);
 void vp8drv_destroy(vp8drv *d);

@@ -51,6 +51,8 @@ int vp8hip_shard_share_last(vp8hip_ctx *ctx, int root);
 int vp8hip_shard_max(vp8hip_ctx *ctx, double *value);
 
 /* ---- the process group of a GOP-sharded run: one process per GPU, no data-path collective -------------------
+ * (Not tested with the simple loop filter, vp8hip_set_loop_filter_type 1: neither this group nor the by-reference split built on it,
+ * vp8oclenc_amd/ref_shard.py.)
  * GOP chunks are independent (intra_part.h:1091-1098).  What the ranks of a node still need from each other -- starting together,
  * the slowest rank's time, the finished frames in the hands of the one writer (the reference's single output file, encIO.h:1-30,
  * vp8enc.cpp:476-481) -- is here, over RCCL on a stream of the group's own, so that a host needs no GPU framework of its own for it:
@@ -130,6 +132,8 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
  * of all of them in one launch; vp8hip_batch_loop_filter for the same members follows.  (The members' segment data: vp8hip_batch_auto_segments
  * with is_key_frame set, or vp8hip_set_segments per member.) */
 int vp8hip_batch_intra_transform(vp8hip_batch *b, const int *active);
+/* The loop filter of the active members: the simple filter's batch form when every active member has type 1
+ * (vp8hip_set_loop_filter_type), the normal filter's when every one has type 0, VP8HIP_ERR_STATE for a mix. */
 int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active);
 /* vp8hip_check_ssim_async for the active members (one launch; the verdicts ride in the following vp8hip_batch_loop_filter);
  * vp8hip_check_ssim_result per member afterwards */

@@ -16,6 +16,7 @@ ap.add_argument("--width", type=int, default=1920)
 ap.add_argument("--height", type=int, default=1080)
 ap.add_argument("--partitions", type=int, default=8)
 ap.add_argument("--check-ssim", type=int, default=0)
+ap.add_argument("--loop-filter-type", type=int, choices=(0, 1), default=0, help="0 = the normal loop filter, 1 = the simple one")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -28,7 +29,8 @@ mbs = (W // 16) * (H // 16)
 nd = 8
 dev = [tuple(api.to_device(p) for p in seq.frame(t)) for t in range(nd)]
 api.device_synchronize()
-drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim) for _ in range(a.streams)]
+drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
+                         loop_filter_type=a.loop_filter_type) for _ in range(a.streams)]
 sizes = [0] * a.streams
 
 def work(k, n, emit):
@@ -70,4 +72,8 @@ for emit in {"both": (False, True), "on": (True,), "off": (False,)}[a.only]:
     fps = a.streams * a.frames / el
     print(f"{W}x{H} {a.streams} streams x {a.frames} frames, bitstream {'on ' if emit else 'off'}: {fps:8.1f} fps, {fps * mbs / 1e6:6.2f} M MB/s, "
           f"{el / a.frames * 1e3 / 1:7.3f} ms per frame and stream" + (f", {sum(sizes) / (a.streams * a.frames) / 1024:.1f} KiB per frame" if emit else ""))
+if a.streams == 1:   # the loop filter by its own clock (the kernel of the chosen type stamps the same words)
+    ms, n, ghz = drvs[0].hip.profile_read_clock()
+    if n:
+        print(f"loop filter type {a.loop_filter_type} by its own clock: {ms / n * 1e3:.1f} us per launch over {n} launches, shader clock {ghz:.2f} GHz")
 for d in drvs: d.close()

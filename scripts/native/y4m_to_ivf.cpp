@@ -1,7 +1,7 @@
 // y4m_to_ivf.cpp -- the reference's program with the path swapped in, as a complete C++ user of the C ABI: YUV4MPEG2 in,
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
-//              [-no-check-ssim] [-conformant]
+//              [-no-check-ssim] [-conformant] [-simple-filter]
 // As in the reference, check_SSIM runs after every inter frame and scene_change() looks at every frame that would be an inter frame.
 // Everything between the two files runs behind include/vp8hip_driver.h; the frames are handed over at their source size
 // and padded on the device (cfg.src_width / src_height), key frames carry that size as the display size.
@@ -38,6 +38,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-no-scene-detect")) cfg.scene_detect = 0;
         else if (!strcmp(argv[i], "-no-check-ssim")) cfg.check_ssim = 0;
         else if (!strcmp(argv[i], "-conformant")) cfg.conformant_stream = 1;
+        else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     FILE *in = fopen(argv[1], "rb");

@@ -1,7 +1,7 @@
 // y4m_to_ivf_gops.cpp -- one YUV4MPEG2 file to one IVF file with its closed GOPs coded SIDE BY SIDE: the file-to-file form of what
 // bench.py's headline measures, as a complete C++ user of the C ABI.
 //   y4m_to_ivf_gops <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n]
-//                   [-no-check-ssim] [-conformant] [-chunks N (48)] [-batch B (6)]
+//                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)]
 // A key frame resets every reference (intra_part.h:1091-1098, inter_part.h:35-50), so the frames [k g, (k + 1) g) of a run with
 // `-g g` are a unit of their own: N such chunks are in flight at once, B of them advance together as one batch (every stage ONE
 // launch for the batch: vp8drv_batch_*), a host thread per batch; the input is streamed (two page-locked frame buffers per chunk in
@@ -46,6 +46,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-altref-range")) cfg.altref_range = atoi(val());
         else if (!strcmp(argv[i], "-no-check-ssim")) cfg.check_ssim = 0;
         else if (!strcmp(argv[i], "-conformant")) cfg.conformant_stream = 1;
+        else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-chunks")) in_flight = atoi(val());
         else if (!strcmp(argv[i], "-batch")) batch = atoi(val());
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }

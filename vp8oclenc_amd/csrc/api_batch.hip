@@ -476,10 +476,12 @@ int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active) {
     void *hand[MAX_BATCH];
     unsigned launch_no[MAX_BATCH];
     LfCheck chk[MAX_BATCH];
-    int n = 0;
+    int n = 0, type = -1;
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
         if (!b->c[i]->recon_ready || b->c[i]->recon < 0) return VP8HIP_ERR_STATE;
+        if (type >= 0 && b->c[i]->lf_type != type) return VP8HIP_ERR_STATE;   // one launch, one filter: the members' types must agree
+        type = b->c[i]->lf_type;
     }
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
@@ -489,7 +491,7 @@ int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active) {
         sds[n] = c->d_sd;
         prog[n] = c->d_progress;
         hand[n] = c->d_lf_handoff;
-        launch_no[n] = c->lf_launches++;
+        launch_no[n] = type == 1 ? c->lf_simple_launches++ : c->lf_launches++;
         lf_check(c, chk[n]);
         c->verdict_stream = b->stream;
         m[n++] = c;
@@ -501,7 +503,8 @@ int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active) {
         Timed t(c0, VP8HIP_K_LOOP_FILTER);
         // (form 3 for batches: with the part full a launch's instructions and LDS count, not its latency; VP8HIP_LF_BATCH_FORM=4 for A/B runs)
         static const bool form4 = [] { const char *v = getenv("VP8HIP_LF_BATCH_FORM"); return v && atoi(v) == 4; }();
-        if (form4) launch_loop_filter4_batch(b->stream, recon, outs, sds, prog, hand, c0->mbw, c0->mbh, launch_no, n, chk);
+        if (type == 1) launch_loop_filter_simple_batch(b->stream, recon, outs, sds, prog, c0->mbw, c0->mbh, launch_no, n, chk);
+        else if (form4) launch_loop_filter4_batch(b->stream, recon, outs, sds, prog, hand, c0->mbw, c0->mbh, launch_no, n, chk);
         else launch_loop_filter3_batch(b->stream, recon, outs, sds, prog, c0->mbw, c0->mbh, launch_no, n, chk);
     }
     b->ent_fork_fresh = b->ent != nullptr;

@@ -367,6 +367,19 @@ int vp8hip_prepare_filter_mask(vp8hip_ctx *c, int32_t *nz_out) {
     return VP8HIP_OK;
 }
 
+int vp8hip_set_loop_filter_type(vp8hip_ctx *c, int type) {
+    if (!c || (type != 0 && type != 1)) return VP8HIP_ERR_ARG;
+    if (type == 1 && !loop_filter_simple_fits(c->mbh)) return VP8HIP_ERR_ARG;
+    c->lf_type = type;
+    return VP8HIP_OK;
+}
+
+// the filter of the context's type on `s` (form 4 for the normal filter: the short chain of one video)
+static void launch_loop_filter_of_type(vp8hip_ctx *c, hipStream_t s, Frame &f, const LfCheck *chk) {
+    if (c->lf_type == 1) launch_loop_filter_simple(s, f, c->out, c->d_sd, c->d_progress, c->mbw, c->mbh, c->lf_simple_launches++, chk);
+    else launch_loop_filter4(s, f, c->out, c->d_sd, c->d_progress, c->d_lf_handoff, c->mbw, c->mbh, c->lf_launches++, c->lf_stall_test, chk);
+}
+
 int vp8hip_loop_filter(vp8hip_ctx *c) {
     USE_DEVICE(c);
     JOIN_LF(c);
@@ -379,7 +392,7 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
         hipStream_t chain = c->stream;
         const bool by_verdict = chk.on != 0;      // (see side_stream_ordered)
         if (!by_verdict) HIPCHK(c, hipEventRecord(c->ev_fork, chain));
-        launch_loop_filter4(chain, f, c->out, c->d_sd, c->d_progress, c->d_lf_handoff, c->mbw, c->mbh, c->lf_launches++, c->lf_stall_test, &chk);
+        launch_loop_filter_of_type(c, chain, f, &chk);
         c->verdict_stream = chain;
         if (!by_verdict) HIPCHK(c, hipStreamWaitEvent(c->lf_stream, c->ev_fork, 0));   // the side work starts where the filter starts
         c->fork_by_verdict = c->fork_by_verdict_at_launch = by_verdict;
@@ -389,7 +402,7 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
         c->lf_sd = c->d_sd;
     } else {
         Timed t(c, VP8HIP_K_LOOP_FILTER);
-        launch_loop_filter4(c->stream, f, c->out, c->d_sd, c->d_progress, c->d_lf_handoff, c->mbw, c->mbh, c->lf_launches++, c->lf_stall_test, &chk);
+        launch_loop_filter_of_type(c, c->stream, f, &chk);
         c->verdict_stream = c->stream;
     }
     // the filtered reconstruction is the LAST reference of the next frame (vp8enc.cpp:395-401); its replicated edges are made

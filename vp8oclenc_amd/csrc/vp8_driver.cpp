@@ -55,11 +55,13 @@ void vp8drv_default_config(vp8drv_config *c) {
     c->conformant_stream = 0;
     c->scene_detect = 0;
     c->src_width = c->src_height = 0;
+    c->loop_filter_type = 0;
 }
 
 int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const vp8drv_config *cfg) {
     if (!out || !cfg) return VP8HIP_ERR_ARG;
     *out = nullptr;
+    if (cfg->loop_filter_type != 0 && cfg->loop_filter_type != 1) return VP8HIP_ERR_ARG;
     vp8drv *d = new (std::nothrow) vp8drv();
     if (!d) return VP8HIP_ERR_ARG;
     d->cfg = *cfg;
@@ -67,6 +69,14 @@ int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const
     if (rc != VP8HIP_OK) {
         delete d;
         return rc;
+    }
+    if (cfg->loop_filter_type) {
+        const int rc = vp8hip_set_loop_filter_type(d->hip, cfg->loop_filter_type);
+        if (rc != VP8HIP_OK) {
+            vp8hip_destroy(d->hip);
+            delete d;
+            return rc;
+        }
     }
     if (cfg->overlap_filter) vp8hip_filter_overlap(d->hip, 1);
     if (cfg->conformant_stream) vp8hip_conformant_stream(d->hip, 1);
@@ -260,7 +270,7 @@ vp8hip_header_params header_params(const vp8drv *d) {
     hp.is_key = d->last_key;
     hp.is_golden = d->last_key;                 // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369)
     hp.is_altref = d->last_altref;
-    hp.loop_filter_type = 0;                    // init.h:1583
+    hp.loop_filter_type = d->cfg.loop_filter_type;   // 0 in the reference (init.h:1583)
     hp.loop_filter_sharpness = d->sharpness;    // or VP8HIP_SHARPNESS_ON_DEVICE
     hp.width = d->cfg.display_width;
     hp.height = d->cfg.display_height;
@@ -316,7 +326,7 @@ int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     f.is_key = d->last_key;
     f.is_golden = d->last_key;                  // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369)
     f.is_altref = d->last_altref;
-    f.loop_filter_type = 0;                     // init.h:1583
+    f.loop_filter_type = d->cfg.loop_filter_type;    // 0 in the reference (init.h:1583)
     f.loop_filter_sharpness = sharp;
     f.partitions_log2 = P == 8 ? 3 : (P == 4 ? 2 : (P == 2 ? 1 : 0));
     f.skip_prob = vp8host_skip_prob(d->nz.data(), d->mbs);
@@ -402,10 +412,11 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
     vp8hip_ctx *ctx[VP8HIP_MAX_BATCH];
     for (int i = 0; i < n; ++i) {
         // the batched loop is the device-parameter loop (what bench.py and a file-to-file transcode run); one launch serves all
-        // members, so what travels as ONE kernel argument must agree: quantizer range, check_SSIM on or off, partitions
+        // members, so what travels as ONE kernel argument must agree: quantizer range, check_SSIM on or off, partitions, filter type
         if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect) return VP8HIP_ERR_ARG;
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
-        if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0))
+        if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
+            a.loop_filter_type != z.loop_filter_type)
             return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
     }

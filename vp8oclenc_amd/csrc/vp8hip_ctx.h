@@ -107,6 +107,8 @@ struct vp8hip_ctx {
     int shard_rank = 0, shard_world = 1;
     void *d_lf_handoff = nullptr;   // loop filter form 4: a band's bottom rows on their way to the next band (tagged granules)
     unsigned lf_launches = 0;       // window index of the loop filter's never-reset band counters
+    int lf_type = 0;                // vp8hip_set_loop_filter_type: 0 normal, 1 simple
+    unsigned lf_simple_launches = 0;   // ... the simple filter's own window index (its counters are its own, LF_SIMPLE_WORD)
     int src_w = 0, src_h = 0;       // vp8hip_set_source_size: size of the planes handed over as current frames (0 = coded size)
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out

@@ -30,6 +30,8 @@ extern thread_local LaunchTiming tl_timing;
 constexpr int PAD = 32;        // allocated margin (pixels) around every plane
 constexpr int EXT = 8;         // replicated-edge width actually filled (max reach of any filter: 3)
 constexpr int LF_ERR_WORD = 1536;   // int index inside the loop filter's progress buffer of its time-out flag
+constexpr int LF_SIMPLE_WORD = 512;  // ... of the simple loop filter's band counters (form 3's sit at 0, the diagnostic stamps at 1024)
+constexpr int LF_SIMPLE_WORDS = 512;
 constexpr int S2_CLOCK_WORD = LF_ERR_WORD + 32;   // ... and of k_search2's launch clock (five 64-bit words, see launch_clock_end)
 constexpr int CLOCK_SAMPLE = 64;    // every 64th workgroup of a launch stamps the clock
 constexpr int SD_INTS = 11;    // ints per segment_data, src/vp8enc.h:80-92
@@ -173,6 +175,13 @@ void launch_loop_filter3(hipStream_t s, const Frame &recon, const MBOut &o, SegD
 void launch_loop_filter4(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, void *handoff,
                          int mbw, int mbh, unsigned launch_no, int stall_test = 0, const LfCheck *chk = nullptr);
 size_t loop_filter4_handoff_bytes(int mbw, int mbh);   // the HBM buffer form 4 hands a band's bottom rows to the next band through
+// The simple loop filter (frame header filter_type 1, kernels_lf_simple.hip): luma only, form 3's data movement.  launch_no counts
+// the context's simple-filter launches only (its band counters are its own, at LF_SIMPLE_WORD of the progress buffer).
+void launch_loop_filter_simple(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, int mbw, int mbh,
+                               unsigned launch_no, const LfCheck *chk = nullptr);
+void launch_loop_filter_simple_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
+                                     int32_t *const *progress, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk = nullptr);
+bool loop_filter_simple_fits(int mbh);   // its band counters fit their window of the progress buffer
 
 // per-frame parameter scans on the device copy of the current frame (kernels_rc.hip); stats = 4 uint32
 size_t rc_partial_words();   // uint32 words of per-workgroup partial sums the three launchers below need
