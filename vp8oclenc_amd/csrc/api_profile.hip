@@ -162,6 +162,23 @@ int vp8hip_debug_weight(vp8hip_ctx *c, const int32_t *d, int n, int32_t *out) {
     return VP8HIP_OK;
 }
 
+// test tap (not in the public header): the same through the matrix-core form of the search kernels (weight_mfma)
+int vp8hip_debug_weight_mfma(vp8hip_ctx *c, const int32_t *d, int n, int32_t *out) {
+    USE_DEVICE(c);
+    JOIN_LF(c);
+    if (!c || !d || !out || n <= 0) return VP8HIP_ERR_ARG;
+    int32_t *dd = nullptr, *dout = nullptr;
+    HIPCHK(c, hipMalloc(&dd, (size_t)n * 64));
+    HIPCHK(c, hipMalloc(&dout, (size_t)n * 4));
+    HIPCHK(c, hipMemcpyAsync(dd, d, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
+    launch_weight_tap_mfma(c->stream, dd, n, dout);
+    HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(dd);
+    hipFree(dout);
+    return VP8HIP_OK;
+}
+
 // test hook (not in the public header): while on, the loop filter's inter-band counters are published from a wrong
 // base, so every band but the first runs into its bounded wait -> VP8HIP_ERR_TIMEOUT at the next synchronize
 int vp8hip_debug_lf_stall(vp8hip_ctx *c, int on) {

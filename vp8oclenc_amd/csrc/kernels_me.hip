@@ -280,10 +280,21 @@ __device__ __forceinline__ void s1_subblock(const uint8_t *cp, int cstride, cons
     for (int i = 0; i < 5; ++i) acc[i] += weight_cols_pre(pre, col + i);
 }
 
-// The same with the current block's share of the metric taken from LDS (pre16: the 16 ints weight_pre_column x 4 of this sub-block, made once
-// per wave by s1_make_pre below): the five dy lanes of a block -- and every reference -- need the same 16 dot4, 8 permutes and 4 biases per
-// sub-block; as instructions of the wave they cost what they cost one lane.
-__device__ __forceinline__ void s1_subblock_pre(const int *pre16, const uint8_t *rp, int rstride, int acc[5]) {
+// The same with the current block's share of the metric taken from LDS (pre_lds[pre_off ..]: the 16 ints weight_pre_column x 4 of this sub-block,
+// made once per wave by s1_make_pre below): the five dy lanes of a block -- and every reference -- need the same 16 dot4, 8 permutes and 4 biases
+// per sub-block; as instructions of the wave they cost what they cost one lane.  The column pass of a candidate is one MFMA for the whole wave
+// (weight_mfma, vp8hip_dev.h; every lane of the wave runs this), B = its four columns, C = the current block's share, read again from LDS for each
+// candidate: held in registers next to the 16 results it would cost 16 registers, and the loop form is tuned for eight waves per SIMD.  The
+// offset passes through an empty asm per candidate so that the compiler cannot see the five reads are the same and keep one copy (it did, and
+// then copied 16 registers into the accumulator before every MFMA); hiding the pointer instead makes the reads flat loads.  An MFMA operand
+// is an even-aligned register quad, so candidates 1 and 3 (columns 1..4, 3..6) take copies: made by vcopy right before their MFMA, behind a
+// scheduling barrier.  Left to itself hipcc built all five quads up front (20 registers for the 8 columns) and spilled at 64.
+__device__ __forceinline__ int vcopy(uint32_t x) {
+    int y;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "v"(x));
+    return y;
+}
+__device__ __forceinline__ void s1_subblock_pre(v4i wa, const int *pre_lds, int pre_off, const uint8_t *rp, int rstride, int acc[5]) {
     uint32_t q0[4], q1[4];
 #pragma unroll
     for (int y = 0; y < 4; ++y) {
@@ -293,14 +304,15 @@ __device__ __forceinline__ void s1_subblock_pre(const int *pre16, const uint8_t 
     uint32_t col[8];
     transpose4x4(q0, col);
     transpose4x4(q1, col + 4);
-    int pre[16];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int4 v = *reinterpret_cast<const int4 *>(pre16 + 4 * k);
-        pre[4 * k] = v.x; pre[4 * k + 1] = v.y; pre[4 * k + 2] = v.z; pre[4 * k + 3] = v.w;
+    for (int i = 0; i < 5; ++i) {
+        int off = pre_off;
+        asm volatile("" : "+v"(off));
+        __builtin_amdgcn_sched_barrier(0);
+        const v4i b = (i & 1) ? v4i{vcopy(col[i]), vcopy(col[i + 1]), vcopy(col[i + 2]), vcopy(col[i + 3])}
+                              : v4i{(int)col[i], (int)col[i + 1], (int)col[i + 2], (int)col[i + 3]};
+        acc[i] += weight_mfma(wa, load_pre16(pre_lds + off), b);
     }
-#pragma unroll
-    for (int i = 0; i < 5; ++i) acc[i] += weight_cols_pre(pre, col + i);
 }
 // ... made by the wave for its twelve blocks: lane = (block slot, sub-block), 48 of the 64 lanes; 16 ints each into pre_lds[slot][sub-block][16]
 constexpr int S1_PRE_INTS = 12 * 4 * 16;
@@ -326,7 +338,8 @@ __device__ __forceinline__ void s1_make_pre(const Plane &cur, int cx, int cy, in
 // `live` false: the lanes take part in the shuffles on harmless in-frame data.
 template <bool SPLIT, bool PRE_LDS = false>
 __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, int cx, int cy, uint32_t pv, bool live, int sub, int lane,
-                                                  const int *pre_lds = nullptr /* PRE_LDS (loop form): this block's [sub-block][16] from s1_make_pre */) {
+                                                  const int *pre_lds = nullptr /* PRE_LDS (loop form): the workgroup's table from s1_make_pre */,
+                                                  int pre_off = 0 /* ... and where this block's [sub-block][16] start in it */) {
     const int sb0 = sub / 5, j = sub - 5 * sb0;       // SPLIT: this lane's sub-block; otherwise sb0 = 0
     // vector / pixel_rate truncates toward zero (:495-500)
     int v0x = (int16_t)(pv & 0xffffu), v0y = (int16_t)(pv >> 16);
@@ -356,10 +369,11 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
     } else {
         // one sub-block at a time (loop NOT unrolled: the register footprint decides how many waves a SIMD holds)
         if (PRE_LDS) {
+            const v4i wa = metric_a(lane);
 #pragma unroll 1
             for (int sb = 0; sb < 4; ++sb) {
                 const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;
-                s1_subblock_pre(pre_lds + 16 * sb, rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
+                s1_subblock_pre(wa, pre_lds, pre_off + 16 * sb, rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
             }
         } else {
 #pragma unroll 1
@@ -423,6 +437,7 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
     const int parent = (cy >> 4) * a.net_width + (cx >> 4);
     const bool parent_written = (cx >> 4) < a.pbw && (cy >> 4) < a.pbh;
     const int *pre_lds = nullptr;
+    int pre_off = 0;
     if (!SPLIT && PRE_LDS) {
         // the current blocks' share of the metric, once per wave into LDS: lane = (block slot, sub-block).  The stages hand over inside the wave
         // (LDS executes a wave's operations in order): no barrier, the compiler is kept from moving the reads up
@@ -433,14 +448,15 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
         const int tby = a.bw == 1 ? tb : (int)__umulhi((uint32_t)tb, a.bw_inv), tbx = tb - tby * a.bw;
         s1_make_pre(a.cur, tbx * 8, tby * 8, sb, slot < M::BLOCKS_PER_WAVE, &s_pre[wave][(slot < M::BLOCKS_PER_WAVE ? slot : 0) * 64 + sb * 16]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        pre_lds = &s_pre[wave][(grp < M::BLOCKS_PER_WAVE ? grp : 0) * 64];
+        pre_lds = &s_pre[0][0];
+        pre_off = wave * S1_PRE_INTS + (grp < M::BLOCKS_PER_WAVE ? grp : 0) * 64;
     }
     const int nr = REF_LOOP ? a.nrefs : 1;
 #pragma unroll 1
     for (int ri = 0; ri < nr; ++ri) {
         const int r = a.refmap[REF_LOOP ? ri : (int)blockIdx.y];
         const uint32_t pv = parent_written ? reinterpret_cast<const uint32_t *>(a.src[r])[parent] : 0u;
-        const uint32_t out = search1_block<SPLIT, !SPLIT && PRE_LDS>(a, r, cx, cy, pv, live, sub, lane, pre_lds);
+        const uint32_t out = search1_block<SPLIT, !SPLIT && PRE_LDS>(a, r, cx, cy, pv, live, sub, lane, pre_lds, pre_off);
         if (sub == 0 && live) {
             const int cell = (cy >> 3) * a.net_width + (cx >> 3);
             reinterpret_cast<uint32_t *>(a.dst[r])[cell] = out;
@@ -587,9 +603,11 @@ __global__ __launch_bounds__(256) void k_search1(Search1Args a) { search1_body<S
 static_assert(sizeof(BatchOf<Search1Args>) <= 4096 && sizeof(PyrArgs) <= 4096 && sizeof(BatchOf<PackItem>) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void k_search1_b(BatchOf<Search1Args> b) { search1_body<SPLIT>(b.item[blockIdx.z]); }
-__global__ __launch_bounds__(256) void k_search1_pl(Search1Args a) { search1_body<false, true>(a); }
-__global__ __launch_bounds__(256) void k_search1_pl_b(BatchOf<Search1Args> b) { search1_body<false, true>(b.item[blockIdx.z]); }
-__global__ __launch_bounds__(256) void k_search1_plr_b(BatchOf<Search1Args> b) { search1_body<false, true, true>(b.item[blockIdx.z]); }
+// (the loop form's register budgets pinned, eight waves per SIMD and seven: under a bare launch bound hipcc gives the MFMA results of the metric
+// AGPRs and pays a v_accvgpr_read per value)
+__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_search1_pl(Search1Args a) { search1_body<false, true>(a); }
+__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_search1_pl_b(BatchOf<Search1Args> b) { search1_body<false, true>(b.item[blockIdx.z]); }
+__global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search1_plr_b(BatchOf<Search1Args> b) { search1_body<false, true, true>(b.item[blockIdx.z]); }
 // VP8HIP_S1_REF_LOOP=0: a workgroup per reference in batches too (same-box A/B runs)
 static bool search1_ref_loop() {
     static const bool on = [] { const char *v = getenv("VP8HIP_S1_REF_LOOP"); return !(v && v[0] == '0'); }();
@@ -757,6 +775,37 @@ __global__ __launch_bounds__(256) void k_weight_tap(const int32_t *d, int n, int
 }
 void launch_weight_tap(hipStream_t s, const int32_t *d, int n, int32_t *out) {
     hipLaunchKernelGGL(k_weight_tap, dim3((n + 255) / 256), dim3(256), 0, s, d, n, out);
+}
+// the same through the form the search kernels run (weight_mfma): a block per lane, every lane of every wave a different one.  The
+// lanes past n take the last block again (an MFMA runs for the whole wave) and store nothing
+__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_weight_tap_mfma(const int32_t *d, int n, int32_t *out) {
+    const int i0 = blockIdx.x * 256 + threadIdx.x, i = i0 < n ? i0 : n - 1;
+    uint32_t cc[4];
+    v4i pp;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        uint32_t cw = 0, pw = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int v = d[i * 16 + 4 * r + c];
+            const uint32_t cb = (uint32_t)(v > 0 ? v : 0) ^ 0x80u, pb = (uint32_t)(v > 0 ? 0 : -v) ^ 0x80u;
+            cw |= cb << (8 * r);
+            pw |= pb << (8 * r);
+        }
+        cc[c] = cw;
+        pp[c] = (int)pw;
+    }
+    int pre[16];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) weight_pre_column(cc[c], pre + 4 * c);
+    v16i c16;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) c16[k] = pre[k];
+    const int w = weight_mfma(metric_a((int)threadIdx.x), c16, pp);
+    if (i0 < n) out[i0] = w;
+}
+void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out) {
+    hipLaunchKernelGGL(k_weight_tap_mfma, dim3((n + 255) / 256), dim3(256), 0, s, d, n, out);
 }
 
 }  // namespace vp8

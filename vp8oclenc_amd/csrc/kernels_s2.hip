@@ -15,8 +15,9 @@
 //     16 bytes, one ds_read_b128 each; a lane comes out with, per y case, one dword of the prediction [column][row half].  The
 //     whole-pel cases are copies.
 //   * Then lane k = candidate (dx, dy) of the 25 (+ the zero-vector candidate): the block-match metric on four 4x4 blocks, the
-//     current block's share of its column pass made once per block into LDS (weight_pre_column) and added by every candidate with
-//     one dot4 per quantity (weight_cols_pre, vp8hip_dev.h); the minimum over the 32 lanes by four DPP steps + row_bcast.
+//     current block's share of its column pass made once per block into LDS (weight_pre_column) and the column pass of 64 (candidate,
+//     4x4 block) tasks of a wave as ONE more MFMA, the current block's share its C input (weight_mfma, vp8hip_dev.h); the minimum over
+//     the 32 lanes by four DPP steps + row_bcast.
 // The operand and result lane maps of the MFMA are pinned by scripts/ubench/mfma_i8_layout.hip, the results by the whole parity
 // suite.  History per 1080p frame and reference: 32-bit multiply-adds 0.156 ms; both passes on v_dot4_i32_i8 0.091 (892 vector
 // instructions per wave; git history, ae32ece^); this form 681 instructions, 56 us per chunk of three references.
@@ -115,8 +116,6 @@ __device__ __forceinline__ uint32_t halfwave_min_upper(uint32_t key) {
 // Pixels travel as signed bytes p - 128 and every tap set sums to 128, so a pass computes sum((p-128) f) = sum(p f) - 128 * 128, and
 //     sat_i8((sum(p f) - 16384 + 64) >> 7) = sat_u8((sum(p f) + 64) >> 7) - 128:
 // the signed saturation of the biased sum IS the biased byte of the reference's clamped sample; the rounding 64 rides in the product (mfma_round).
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned short ashr7_pk_i8(int a, int b) { return __builtin_amdgcn_ashr_pk_i8_i32(a, b, 7); }
 __device__ __forceinline__ uint32_t pack4(unsigned short lo, unsigned short hi) {
@@ -257,6 +256,9 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
     if (k == 25) { qx = cx * 4; qy = cy * 4; }
     const bool valid = live && k < 26 && qx >= 0 && qx <= a.w * 4 - 32 && qy >= 0 && qy <= a.h * 4 - 32;
     int diff = 0;
+    const v4i wa = metric_a(wl_n);        // the metric's column pass on the matrix cores (weight_mfma, vp8hip_dev.h): every lane of the wave is here
+    // a 4x4 block's four prediction columns: every other dword of [column][row half] from its first one
+    auto cols4 = [](const uint32_t *src) { return v4i{(int)src[0], (int)src[2], (int)src[4], (int)src[6]}; };
     if (SPREAD) {
         int *q3 = &s_pre[g][64];          // [candidate]: the cost of its fourth 4x4 block, made by another lane (the H array's bytes behind the pre table)
         const bool helper = lane >= 26;
@@ -265,17 +267,7 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         const uint32_t *own = k < 25 ? &s_V[g][k * V_STRIDE] : &s_cz[g][16];
         const uint32_t *hsrc = &s_V[g][(lane - 26) * 3 * V_STRIDE + 9];     // idle lanes: candidate 3 (lane - 26) + j, 4x4 block 3 (n = m = 1)
         int *hdst = &q3[(lane - 26) * 3];
-        auto metric = [&](const uint32_t *src, const int *pre16) {
-            int pre[16];
-            uint32_t pp[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int4 v = *reinterpret_cast<const int4 *>(pre16 + 4 * j);
-                pre[4 * j] = v.x; pre[4 * j + 1] = v.y; pre[4 * j + 2] = v.z; pre[4 * j + 3] = v.w;
-                pp[j] = src[2 * j];
-            }
-            return weight_cols_pre(pre, pp);
-        };
+        auto metric = [&](const uint32_t *src, const int *pre16) { return weight_mfma(wa, load_pre16(pre16), cols4(src)); };
 #pragma unroll
         for (int j = 0; j < 3; ++j) {       // rounds 0..2: a candidate's own lane its 4x4 blocks 0..2, the idle lanes block 3 of candidates 0..17
             const int c = metric(helper ? hsrc + j * V_STRIDE : own + (8 * (j & 1) + (j >> 1)), &s_pre[g][helper ? 48 : 16 * j]);
@@ -290,31 +282,13 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         __syncthreads();
         diff += q3[k < 26 ? k : 31];
     } else {
-    uint32_t P[8][2];
-    {
-        // candidates 0..24: their prediction from the producer; lane 25 (zero MV: whole-pel, both passes are the identity)
-        // and the idle lanes read the zero-MV block
-        const uint32_t *src = k < 25 ? &s_V[g][k * V_STRIDE] : &s_cz[g][16];
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(src + 4 * c4);
-            P[2 * c4][0] = v.x; P[2 * c4][1] = v.y; P[2 * c4 + 1][0] = v.z; P[2 * c4 + 1][1] = v.w;
-        }
-    }
+    // candidates 0..24: their prediction from the producer; lane 25 (zero MV: whole-pel, both passes are the identity)
+    // and the idle lanes read the zero-MV block.  4x4 block (m, n) = columns 4n.., row half m
+    const uint32_t *src = k < 25 ? &s_V[g][k * V_STRIDE] : &s_cz[g][16];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            int pre[16];
-            uint32_t pp[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int4 v = *reinterpret_cast<const int4 *>(&s_pre[g][((m * 2 + n) * 4 + j) * 4]);
-                pre[4 * j] = v.x; pre[4 * j + 1] = v.y; pre[4 * j + 2] = v.z; pre[4 * j + 3] = v.w;
-                pp[j] = P[4 * n + j][m];
-            }
-            diff += weight_cols_pre(pre, pp);
-        }
+        for (int n = 0; n < 2; ++n) diff += weight_mfma(wa, load_pre16(&s_pre[g][(m * 2 + n) * 16]), cols4(src + 8 * n + m));
     }
     if (k < 25) diff += (iabs(dx) + iabs(dy)) * 32;  // :1176-1178
     uint32_t key = (valid && diff < 0x7fff) ? ((uint32_t)diff << 8) | (uint32_t)k : 0xffffffffu;

@@ -163,6 +163,7 @@ void launch_search1(hipStream_t s, const Frame &cur, const RefSet &refs, const N
                     int src_idx, int net_width, bool latency = false);   // latency: the short-wave mapping whatever the size
 void launch_search2(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, unsigned long long *clk = nullptr);
 void launch_weight_tap(hipStream_t s, const int32_t *d, int n, int32_t *out);
+void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out);
 void launch_mb(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, const Frame &recon,
                const MBOut &o, const SegData *d_sd, float ssim_target, int mbw, int mbh, bool conformant = false);
 void launch_filter_mask(hipStream_t s, const MBOut &o, const SegData *d_sd, int mbs);
@@ -422,7 +423,8 @@ __device__ __forceinline__ uint32_t abs_acc(s16x2 v, uint32_t acc) {
 //   * row pass on PAIRS of rows in packed 16-bit (every intermediate fits int16 for 8-bit pixel differences:
 //     |R| <= 8160, |a1|,|b1| <= 16320, |a1 +- b1 + 7| <= 32647), |a|+|b| of a pair = xor + one v_sad_u16.
 // 9 instructions per column instead of 4 byte subtractions + 13: the device metric is pinned on 200k random and on the
-// extreme difference blocks by test_block_match_metric_device_vs_oracle through k_weight_tap.
+// extreme difference blocks by test_block_match_metric_device_vs_oracle through k_weight_tap.  The search kernels' hot forms run the
+// column pass on the matrix cores instead (weight_mfma below; pinned the same way through k_weight_tap_mfma).
 constexpr uint32_t pk8s(int a, int b, int c, int d) {
     return (uint32_t)(a & 255) | ((uint32_t)(b & 255) << 8) | ((uint32_t)(c & 255) << 16) | ((uint32_t)(d & 255) << 24);
 }
@@ -498,6 +500,64 @@ __device__ __forceinline__ int weight_cols_pre(const int pre[16], const uint32_t
         B[c] = as_s16x2(__builtin_amdgcn_perm((uint32_t)t3, (uint32_t)R2, 0x07060100u));
     }
     return weight_rows(A, B);
+}
+
+// ---- the column pass on the matrix cores -------------------------------------------------------------------------
+// The 16 dot4 of weight_cols_pre are a product of a constant 16 x 16 int8 table W (row i = quantity i & 3 of column i >> 2,
+// {R0, R2, X, Y} with the negated weights K_W_*N, over the 16 prediction bytes in column-dword order) with the prediction, plus
+// the current block's share.  ONE v_mfma_i32_32x32x32_i8 (D = A.B + C) does that for the 64 lanes of a wave at once, each lane
+// on its own block (lane maps pinned by scripts/ubench/mfma_i8_layout.hip):
+//   * A and B: lane l holds k = 16 (l >> 5) + j, j = 0..15, of row l & 31 (A) or column l & 31 (B);
+//   * D: register r of lane l holds row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
+// So a lane's 16 result registers are exactly the rows whose bit 2 equals its half h = l >> 5, and its 16 B bytes are exactly the
+// k of that half.  A is made BLOCK-DIAGONAL: a row with bit 2 = h reads only k in [16h, 16h + 16), and both diagonal blocks are W,
+// with row m = (i & 3) + 8 (i >> 2) + 4h holding W's row i.  Then register i of lane l is W[i] . (its own 16 bytes) + (its own C[i]):
+// nothing crosses lanes, and C = the 16 ints of weight_pre_column x 4, [column][R0, R2, X, Y].  Every weight is an int8 and every
+// sum is the integer the dot4 form computes (|sum| < 2^15): the rotations and the row pass that follow are unchanged, and so is
+// every bit of the result.  An MFMA runs for the whole wave whatever EXEC says: call weight_mfma only where every lane is active.
+// One MFMA holds the SIMD's vector issue for 8 cycles where the 16 dot4 (VOP3P, ~4.2 each) took ~67.
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+struct MetricTable { uint32_t w[64][4]; };   // the A operand, lane l's four dwords
+constexpr MetricTable make_metric_a() {
+    MetricTable t{};
+    const uint32_t K[4] = {K_W_R0N, K_W_R2N, K_W_XN, K_W_YN};
+    for (int l = 0; l < 64; ++l) {
+        const int m = l & 31, h = l >> 5;
+        if (((m >> 2) & 1) != h) continue;                  // off the diagonal: zero
+        const int i = (m & 3) + 4 * (m >> 3);               // the result register row m lands in
+        t.w[l][i >> 2] = K[i & 3];                          // k = 16h + 4c + r: row r of column c, only column c = i >> 2 weighs
+    }
+    return t;
+}
+static __device__ __constant__ const MetricTable K_METRIC_A = make_metric_a();
+// this lane's A operand: read once per wave, kept in four registers
+__device__ __forceinline__ v4i metric_a(int wave_lane) { return *reinterpret_cast<const v4i *>(K_METRIC_A.w[wave_lane & 63]); }
+
+// weight of (current - prediction) for one 4x4 block per lane: a = metric_a, c = weight_pre_column of the four current columns
+// ([column][R0, R2, X, Y]), p = the four prediction columns as biased bytes.  The same value as weight_cols_pre.
+__device__ __forceinline__ int weight_mfma(v4i a, v16i c, v4i p) {
+    const v16i d = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, p, c, 0, 0, 0);
+    s16x2 A[4], B[4];
+#pragma unroll
+    for (int col = 0; col < 4; ++col) {
+        const uint32_t xy = pk16(d[4 * col + 2], d[4 * col + 3]);
+        const int t1 = dot2(xy, K_ROT16_A, 16 * 14500);
+        const int t3 = dot2(xy, K_ROT16_B, 16 * 7500);
+        A[col] = as_s16x2(__builtin_amdgcn_perm((uint32_t)t1, (uint32_t)d[4 * col + 0], 0x07060100u));
+        B[col] = as_s16x2(__builtin_amdgcn_perm((uint32_t)t3, (uint32_t)d[4 * col + 1], 0x07060100u));
+    }
+    return weight_rows(A, B);
+}
+// C of weight_mfma from the 16 ints at pre16 (16-byte aligned): four 16-byte loads
+__device__ __forceinline__ v16i load_pre16(const int *pre16) {
+    v16i c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const v4i v = *reinterpret_cast<const v4i *>(pre16 + 4 * j);
+        c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
+    }
+    return c;
 }
 
 // (Tried for the whole-pel search, where a reference column is the prediction column of up to four candidates: the four linear
