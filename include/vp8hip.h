@@ -201,6 +201,45 @@ int vp8hip_loop_filter(vp8hip_ctx *ctx);
  * filter_type bit (vp8hip_header_params / vp8bs_frame.loop_filter_type) must say the same, or decoders drift from the encoder's
  * reconstruction.  Any other value: VP8HIP_ERR_ARG. */
 int vp8hip_set_loop_filter_type(vp8hip_ctx *ctx, int type);
+/* ---- quality of the coded frames (opt-in) -------------------------------------------------------------------------------
+ * With stats on, every vp8hip_loop_filter / vp8hip_batch_loop_filter measures the FILTERED reconstruction against the current frame
+ * as it was handed in, on the device, on the stream the filter runs on, without a host wait: the source region only (the size of
+ * vp8hip_set_source_size, or the coded size; chroma ((w + 1) / 2) x ((h + 1) / 2)), never the padding.  Per plane Y, U, V the exact
+ * sum of squared errors, PSNR = 10 log10(samples 255^2 / sse) (100 when sse is 0, libvpx's cap), and SSIM in libvpx's integer form
+ * (8x8 windows every 4 samples, c1 = 26634, c2 = 239708; the mean over the plane's windows, 1.0 / 0.0 for a plane without a whole
+ * window and sse 0 / not 0); ssim_all = 0.8 ssim_Y + 0.1 (ssim_U + ssim_V).  Deterministic: the same bits whether a context runs alone
+ * or in a batch.  These numbers describe the encoder's reconstruction: what a decoder shows whenever the stream decodes to it (with
+ * vp8hip_conformant_stream 0 the reference's stream defects, REFERENCE_DEFECTS.md, can make a decoder's picture differ). */
+typedef struct {
+    int32_t frame_number;    /* 0-based index of the current frame measured, in the order the context received its frames */
+    int32_t is_key;          /* the reconstruction came from vp8hip_intra_transform */
+    uint64_t sse[3];         /* Y, U, V */
+    uint64_t samples[3];
+    double psnr[3];
+    double psnr_all;         /* over sse_Y + sse_U + sse_V and samples_Y + samples_U + samples_V */
+    double ssim[3];
+    double ssim_all;
+} vp8hip_quality;
+/* Over every frame made final so far.  A frame's record becomes final when the context measures a frame with ANOTHER frame_number: a
+ * second filter of the same current frame (a frame sent back by check_SSIM and coded again as a key frame) replaces the first's record. */
+typedef struct {
+    int64_t frames;
+    uint64_t sse[3], samples[3];   /* summed */
+    double psnr[3];                /* from the summed sse and samples per plane (vpxenc's "Y", "U", "V") */
+    double psnr_all;               /* from the summed sse and samples of all planes (vpxenc's "Overall") */
+    double psnr_avg;               /* mean of the frames' psnr_all (vpxenc's "Avg") */
+    double ssim[3];                /* mean of the frames' ssim[p] */
+    double ssim_all;               /* mean of the frames' ssim_all */
+    double psnr_min;               /* lowest psnr_all (0 without frames) ... */
+    int64_t psnr_min_frame;        /* ... and its frame_number (-1 without frames) */
+} vp8hip_quality_totals;
+/* on = 1: from the next filter on, every frame is measured; turning it on from off starts a new summary.  0 (default): nothing runs. */
+int vp8hip_set_quality_stats(vp8hip_ctx *ctx, int on);
+/* The record of the last frame measured.  Waits for that measurement alone (a word its launch writes last), not for the stream.
+ * VP8HIP_ERR_STATE: stats off, or nothing measured yet. */
+int vp8hip_quality_result(vp8hip_ctx *ctx, vp8hip_quality *q);
+/* The summary since stats were turned on, the last frame measured included.  Waits the same way.  VP8HIP_ERR_STATE: stats off. */
+int vp8hip_quality_summary(vp8hip_ctx *ctx, vp8hip_quality_totals *s);
 /* on = 1: the context gets a second stream, and work that does not depend on the filtered frame runs beside the loop filter:
  * the entropy stage of the same frame (vp8hip_count_probs ... vp8hip_encode_frame), the next frame's upload, parameter scan
  * and GOLDEN / ALTREF searches.  The filter stays on the stream the frame was coded on and the CONTEXT moves to the other one
@@ -318,8 +357,9 @@ const char *vp8hip_status_string(int status);
  * -- return values and counters provisional until vp8drv_resolve -- in round 3: 3), MINOR when entry points are added.  A host
  * built against an older header checks it once after loading the library.  3001: the shard, device-memory and frame-check entry points;
  * 3002: vp8drv_encode_video_device; 3003: vp8hip_import_last, vp8hip_group_*, the load-time hardware-queue setting;
- * vp8drv_frame_check folds position in (4: its values change); 4009: vp8hip_set_loop_filter_type and vp8drv_config.loop_filter_type. */
-#define VP8HIP_ABI_VERSION 4009
+ * vp8drv_frame_check folds position in (4: its values change); 4009: vp8hip_set_loop_filter_type and vp8drv_config.loop_filter_type;
+ * 4010: quality statistics (vp8hip_set_quality_stats, vp8hip_batch_quality, vp8drv_config.quality_stats, vp8drv_get_frame_quality). */
+#define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait
  * (VP8HIP_EXPERIMENT_SKIP, VP8HIP_EXPERIMENT_SKIP_ENT, VP8HIP_EXPERIMENT_NOWAIT, VP8DRV_EXPERIMENT_READY_FIRST; built with

@@ -69,9 +69,12 @@ typedef struct {
     int32_t loop_filter_type;    /* 0 (default): the normal loop filter, the reference's; 1: the simple loop filter (RFC 6386
                                 section 15.2, vp8hip_set_loop_filter_type), written into every frame header.  Other values:
                                 vp8drv_create returns VP8HIP_ERR_ARG.  Members of a batch must agree */
+    int32_t quality_stats;       /* 1: PSNR and SSIM of every coded frame, measured on the device (vp8hip_set_quality_stats):
+                                vp8drv_get_frame_quality, vp8drv_get_quality_summary.  0 (default): off.  Other values:
+                                vp8drv_create returns VP8HIP_ERR_ARG */
 } vp8drv_config;
 
-void vp8drv_default_config(vp8drv_config *cfg);   /* the reference's defaults: 150, 5, 0, 48, -1, 1, 1, 1, 0, 0, 0, 0, 3, 0, 0, 0, 0, 0 */
+void vp8drv_default_config(vp8drv_config *cfg);   /* the reference's defaults: 150, 5, 0, 48, -1, 1, 1, 1, 0, 0, 0, 0, 3, 0, 0, 0, 0, 0, 0 */
 
 int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const vp8drv_config *cfg);
 void vp8drv_destroy(vp8drv *d);
@@ -199,6 +202,13 @@ typedef struct {
     int32_t refs_searched;            /* references searched by all inter frames so far (1 + use_golden + use_altref each) */
 } vp8drv_stats;
 void vp8drv_get_stats(const vp8drv *d, vp8drv_stats *s);
+/* cfg.quality_stats = 1: the record of the frame just made final (its check_SSIM verdict is taken first, as vp8drv_get_frame does:
+ * a frame coded again as a key frame has the key frame's record, is_key 1), and the summary over every frame made final so far.
+ * Neither waits for more than the last measurement.  VP8HIP_ERR_STATE when stats are off or no frame was coded yet. */
+typedef vp8hip_quality vp8drv_quality;
+typedef vp8hip_quality_totals vp8drv_quality_summary;
+int vp8drv_get_frame_quality(vp8drv *d, vp8drv_quality *q);
+int vp8drv_get_quality_summary(vp8drv *d, vp8drv_quality_summary *s);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,10 @@ int vp8hip_batch_intra_transform(vp8hip_batch *b, const int *active);
 /* The loop filter of the active members: the simple filter's batch form when every active member has type 1
  * (vp8hip_set_loop_filter_type), the normal filter's when every one has type 0, VP8HIP_ERR_STATE for a mix. */
 int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active);
+/* The quality measurement (vp8hip_set_quality_stats) of the active members that have stats on, in ONE launch on the batch's stream:
+ * each member's last filtered frame against its current frame.  vp8hip_batch_loop_filter makes this call itself at its end, so a
+ * caller needs it only to measure again (the record is then replaced by the same numbers).  Members may differ in whether stats are on. */
+int vp8hip_batch_quality(vp8hip_batch *b, const int *active);
 /* vp8hip_check_ssim_async for the active members (one launch; the verdicts ride in the following vp8hip_batch_loop_filter);
  * vp8hip_check_ssim_result per member afterwards */
 int vp8hip_batch_check_ssim_async(vp8hip_batch *b, const int *active, const int32_t (*refqi)[4], int qi_min);

@@ -61,6 +61,12 @@ typedef enum {
     VP8HIP_DBG_CURRENT_CHROMA /* ref 0 = U, 1 = V : tight (W/2)x(H/2) plane of the current frame (after copy_with_padding) */
 } vp8hip_debug_id;
 int vp8hip_debug_download(vp8hip_ctx *ctx, int what, int ref, int level, void *dst, size_t bytes);
+/* The quality kernel (vp8hip_set_quality_stats) on caller planes in host memory: a source and a reconstruction of width x height
+ * luma samples (chroma ((width + 1) / 2) x ((height + 1) / 2)), rows stride[p] bytes apart.  Fills q as a measured frame's record
+ * (frame_number 0, is_key 0: the exact squared errors, the sample counts, PSNR and the SSIM means); blocks.  Touches nothing of the
+ * context but its stream. */
+int vp8hip_debug_quality(vp8hip_ctx *ctx, int width, int height, const uint8_t *const src[3], const int32_t src_stride[3],
+                         const uint8_t *const rec[3], const int32_t rec_stride[3], vp8hip_quality *q);
 
 
 #ifdef __cplusplus

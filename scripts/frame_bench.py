@@ -17,6 +17,7 @@ ap.add_argument("--height", type=int, default=1080)
 ap.add_argument("--partitions", type=int, default=8)
 ap.add_argument("--check-ssim", type=int, default=0)
 ap.add_argument("--loop-filter-type", type=int, choices=(0, 1), default=0, help="0 = the normal loop filter, 1 = the simple one")
+ap.add_argument("--quality-stats", type=int, choices=(0, 1), default=0, help="1 = PSNR / SSIM of every frame on the device (vp8drv_config.quality_stats): what it costs")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -30,7 +31,7 @@ nd = 8
 dev = [tuple(api.to_device(p) for p in seq.frame(t)) for t in range(nd)]
 api.device_synchronize()
 drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
-                         loop_filter_type=a.loop_filter_type) for _ in range(a.streams)]
+                         loop_filter_type=a.loop_filter_type, quality_stats=a.quality_stats) for _ in range(a.streams)]
 sizes = [0] * a.streams
 
 def work(k, n, emit):
@@ -76,4 +77,7 @@ if a.streams == 1:   # the loop filter by its own clock (the kernel of the chose
     ms, n, ghz = drvs[0].hip.profile_read_clock()
     if n:
         print(f"loop filter type {a.loop_filter_type} by its own clock: {ms / n * 1e3:.1f} us per launch over {n} launches, shader clock {ghz:.2f} GHz")
+if a.quality_stats:
+    q = drvs[0].quality_summary()
+    print(f"quality of stream 0 over {q.frames} frames: PSNR overall {q.psnr_all:.3f} dB, avg {q.psnr_avg:.3f} dB, SSIM {q.ssim_all:.5f}")
 for d in drvs: d.close()

@@ -1,7 +1,7 @@
 // y4m_to_ivf.cpp -- the reference's program with the path swapped in, as a complete C++ user of the C ABI: YUV4MPEG2 in,
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
-//              [-no-check-ssim] [-conformant] [-simple-filter]
+//              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr]
 // As in the reference, check_SSIM runs after every inter frame and scene_change() looks at every frame that would be an inter frame.
 // Everything between the two files runs behind include/vp8hip_driver.h; the frames are handed over at their source size
 // and padded on the device (cfg.src_width / src_height), key frames carry that size as the display size.
@@ -39,6 +39,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-no-check-ssim")) cfg.check_ssim = 0;
         else if (!strcmp(argv[i], "-conformant")) cfg.conformant_stream = 1;
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
+        else if (!strcmp(argv[i], "-psnr")) cfg.quality_stats = 1;               // PSNR / SSIM summary on stderr
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     FILE *in = fopen(argv[1], "rb");
@@ -176,6 +177,13 @@ int main(int argc, char **argv) {
     fclose(in);
     vp8drv_stats st;
     vp8drv_get_stats(drv, &st);
+    if (cfg.quality_stats) {   // vpxenc --psnr's summary, measured on the device (vp8drv_config.quality_stats)
+        vp8drv_quality_summary q;
+        CK(vp8drv_get_quality_summary(drv, &q));
+        fprintf(stderr, "Stream 0 PSNR (Overall/Avg/Y/U/V) %.3f %.3f %.3f %.3f %.3f  SSIM %.5f (Y %.5f)  worst frame %lld: %.3f dB  (%lld frames)\n",
+                q.psnr_all, q.psnr_avg, q.psnr[0], q.psnr[1], q.psnr[2], q.ssim_all, q.ssim[0], (long long)q.psnr_min_frame, q.psnr_min,
+                (long long)q.frames);
+    }
     vp8drv_destroy(drv);
     for (int k = 0; k < RING; ++k) vp8hip_host_free(0, buf[k]);
     printf("%s: %u frames %dx%d (coded %dx%d), %u key (%d by scene change, %d recoded), %zu bytes; %d hardware queues\n", argv[2], n, W, H, Wc, Hc, keys,

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "vp8hip_create", "vp8hip_destroy", "vp8hip_upload_current", "vp8hip_set_current_device", "vp8hip_upload_last",
     "vp8hip_set_last_device", "vp8hip_set_segments", "vp8hip_inter_transform", "vp8hip_download_results",
     "vp8hip_upload_mb_data", "vp8hip_upload_recon", "vp8hip_prepare_filter_mask", "vp8hip_loop_filter", "vp8hip_set_loop_filter_type",
+    "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
     "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
@@ -45,7 +46,7 @@ class Vp8HipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 4009  # VP8HIP_ABI_VERSION, include/vp8hip.h
+ABI_VERSION = 4010  # VP8HIP_ABI_VERSION, include/vp8hip.h
 ERR_OVERFLOW = -7   # VP8HIP_ERR_OVERFLOW, include/vp8hip.h
 ERR_FORMAT = -8     # VP8HIP_ERR_FORMAT
 SHARPNESS_ON_DEVICE = -2 ** 31   # VP8HIP_SHARPNESS_ON_DEVICE
@@ -436,7 +437,7 @@ class DrvConfig(C.Structure):
                 ("num_partitions", C.c_int32), ("display_width", C.c_int32), ("display_height", C.c_int32),
                 ("host_bitstream", C.c_int32), ("overlap_filter", C.c_int32), ("ref_mask", C.c_int32),
                 ("conformant_stream", C.c_int32), ("scene_detect", C.c_int32),
-                ("src_width", C.c_int32), ("src_height", C.c_int32), ("loop_filter_type", C.c_int32)]
+                ("src_width", C.c_int32), ("src_height", C.c_int32), ("loop_filter_type", C.c_int32), ("quality_stats", C.c_int32)]
 
 
 class DrvStats(C.Structure):
@@ -444,6 +445,19 @@ class DrvStats(C.Structure):
                                           "last_use_altref", "last_prev_is_golden", "last_prev_is_altref",
                                           "last_was_altref", "redone_as_key", "last_replaced")] + \
                [("last_new_ssim", C.c_float), ("last_min_ssim", C.c_float), ("scene_changes", C.c_int32), ("refs_searched", C.c_int32)]
+
+
+class Quality(C.Structure):
+    """vp8hip_quality = vp8drv_quality, include/vp8hip.h: one measured frame"""
+    _fields_ = [("frame_number", C.c_int32), ("is_key", C.c_int32), ("sse", C.c_uint64 * 3), ("samples", C.c_uint64 * 3),
+                ("psnr", C.c_double * 3), ("psnr_all", C.c_double), ("ssim", C.c_double * 3), ("ssim_all", C.c_double)]
+
+
+class QualitySummary(C.Structure):
+    """vp8hip_quality_totals = vp8drv_quality_summary, include/vp8hip.h: every frame made final so far"""
+    _fields_ = [("frames", C.c_int64), ("sse", C.c_uint64 * 3), ("samples", C.c_uint64 * 3), ("psnr", C.c_double * 3),
+                ("psnr_all", C.c_double), ("psnr_avg", C.c_double), ("ssim", C.c_double * 3), ("ssim_all", C.c_double),
+                ("psnr_min", C.c_double), ("psnr_min_frame", C.c_int64)]
 
 
 class NativeDriver:
@@ -594,6 +608,24 @@ class NativeDriver:
     def stats(self) -> DrvStats:
         s = DrvStats()
         self.lib.vp8drv_get_stats(self.h, C.byref(s))
+        return s
+
+    def frame_quality(self) -> Quality:
+        """vp8drv_get_frame_quality (cfg quality_stats=1): PSNR / SSIM of the frame just made final (its verdict is taken first)"""
+        q = Quality()
+        self.lib.vp8drv_get_frame_quality.argtypes = [C.c_void_p, C.POINTER(Quality)]
+        rc = self.lib.vp8drv_get_frame_quality(self.h, C.byref(q))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_frame_quality: {self.lib.vp8hip_status_string(rc).decode()} ({rc})")
+        return q
+
+    def quality_summary(self) -> QualitySummary:
+        """vp8drv_get_quality_summary: over every frame made final so far"""
+        s = QualitySummary()
+        self.lib.vp8drv_get_quality_summary.argtypes = [C.c_void_p, C.POINTER(QualitySummary)]
+        rc = self.lib.vp8drv_get_quality_summary(self.h, C.byref(s))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_quality_summary: {self.lib.vp8hip_status_string(rc).decode()} ({rc})")
         return s
 
     def close(self):
@@ -897,6 +929,37 @@ class Vp8Hip:
         from the next loop_filter on.  The frame header's filter_type must say the same."""
         self.lib.vp8hip_set_loop_filter_type.argtypes = [C.c_void_p, C.c_int]
         self._chk(self.lib.vp8hip_set_loop_filter_type(self.h, int(t)), "set_loop_filter_type")
+
+    def set_quality_stats(self, on: bool = True):
+        """vp8hip_set_quality_stats: PSNR / SSIM of every filtered frame against its source, on the device (on from off: a new summary)"""
+        self.lib.vp8hip_set_quality_stats.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.vp8hip_set_quality_stats(self.h, int(bool(on))), "set_quality_stats")
+
+    def quality_result(self) -> "Quality":
+        q = Quality()
+        self.lib.vp8hip_quality_result.argtypes = [C.c_void_p, C.POINTER(Quality)]
+        self._chk(self.lib.vp8hip_quality_result(self.h, C.byref(q)), "quality_result")
+        return q
+
+    def quality_summary(self) -> "QualitySummary":
+        s = QualitySummary()
+        self.lib.vp8hip_quality_summary.argtypes = [C.c_void_p, C.POINTER(QualitySummary)]
+        self._chk(self.lib.vp8hip_quality_summary(self.h, C.byref(s)), "quality_summary")
+        return s
+
+    def debug_quality(self, src, rec) -> "Quality":
+        """vp8hip_debug_quality (test tap): the quality kernel on caller planes; src, rec = (Y, U, V) uint8 arrays, chroma
+        ((w + 1) // 2) x ((h + 1) // 2)"""
+        src = [np.ascontiguousarray(p, np.uint8) for p in src]
+        rec = [np.ascontiguousarray(p, np.uint8) for p in rec]
+        h, w = src[0].shape
+        P3, I3 = C.c_void_p * 3, C.c_int32 * 3
+        q = Quality()
+        self.lib.vp8hip_debug_quality.argtypes = [C.c_void_p, C.c_int, C.c_int, P3, I3, P3, I3, C.POINTER(Quality)]
+        self._chk(self.lib.vp8hip_debug_quality(self.h, w, h, P3(*[p.ctypes.data for p in src]), I3(*[p.shape[1] for p in src]),
+                                                P3(*[p.ctypes.data for p in rec]), I3(*[p.shape[1] for p in rec]), C.byref(q)),
+                  "debug_quality")
+        return q
 
     def filter_overlap(self, on: bool = True):
         """vp8hip_filter_overlap: one video coded frame after frame -- the loop filter on a stream of its own, the next frame's GOLDEN /

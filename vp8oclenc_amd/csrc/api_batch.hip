@@ -459,7 +459,7 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
         Timed t(c0, VP8HIP_K_MB);
         launch_mb_batch(s, cur, refs, nets, recon, outs, sds, c0->ssim_target, c0->mbw, c0->mbh, n, c0->conformant != 0);
     }
-    for (int i = 0; i < n; ++i) m[i]->recon_ready = true;
+    for (int i = 0; i < n; ++i) m[i]->recon_ready = true, m[i]->recon_key = false;
     HIPCHK(c0, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -513,11 +513,12 @@ int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active) {
         c->frames[c->recon].pyramid_valid = false;
         c->frames[c->recon].border_valid = false;   // its replicated edges are made with its pyramid, in one launch
         c->slot[0] = c->recon;
+        c->lf_key = c->recon_key;
         c->recon = -1;
         c->recon_ready = false;
     }
     HIPCHK(c0, hipGetLastError());
-    return VP8HIP_OK;
+    return batch_quality(b, active);   // (the members with stats on: one launch behind the filter)
 }
 
 // intra_transform (intra_part.h:1089-1109) for the members whose frame is a key frame, in ONE launch (the members' wavefronts side by side:
@@ -563,7 +564,7 @@ int vp8hip_batch_intra_transform(vp8hip_batch *b, const int *active) {
         Timed t(c0, VP8HIP_K_FILTER_MASK);
         for (int i = 0; i < n; ++i) launch_filter_mask(b->stream, m[i]->out, m[i]->d_sd, m[i]->mbs);
     }
-    for (int i = 0; i < n; ++i) m[i]->recon_ready = true;
+    for (int i = 0; i < n; ++i) m[i]->recon_ready = true, m[i]->recon_key = true;
     HIPCHK(c0, hipGetLastError());
     return VP8HIP_OK;
 }

@@ -450,6 +450,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     if (c->h_frame) hipHostFree(c->h_frame);
     hipFree(c->d_frame);
     if (c->h_verdict) hipHostFree(c->h_verdict);
+    if (c->h_quality) hipHostFree(c->h_quality);
+    hipFree(c->d_quality);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -722,6 +724,7 @@ int vp8hip_upload_recon(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->recon_ready = true;
+    c->recon_key = false;
     return VP8HIP_OK;
 }
 

@@ -204,6 +204,7 @@ int vp8hip_inter_transform(vp8hip_ctx *c, int prev_is_golden, int prev_is_altref
         launch_mb(c->stream, c->cur, refs, c->nets, c->frames[c->recon].f, c->out, c->d_sd, c->ssim_target, c->mbw, c->mbh, c->conformant != 0);
     }
     c->recon_ready = true;
+    c->recon_key = false;
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -236,6 +237,7 @@ int vp8hip_inter_finish(vp8hip_ctx *c, int use_golden, int use_altref) {
                   c->mbw, c->mbh, c->conformant != 0);
     }
     c->recon_ready = true;
+    c->recon_key = false;
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -256,6 +258,7 @@ int vp8hip_intra_transform(vp8hip_ctx *c) {
                      ++c->intra_gen, c->d_progress + LF_ERR_WORD, 0.0f, 1, c->mbw, c->mbh, c->lf_stall_test);
     }
     c->recon_ready = true;
+    c->recon_key = true;
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -393,6 +396,8 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
         const bool by_verdict = chk.on != 0;      // (see side_stream_ordered)
         if (!by_verdict) HIPCHK(c, hipEventRecord(c->ev_fork, chain));
         launch_loop_filter_of_type(c, chain, f, &chk);
+        c->lf_key = c->recon_key;
+        quality_after_filter(c, f, chain);   // (behind the filter on its stream: whatever overwrites this source is ordered behind it)
         c->verdict_stream = chain;
         if (!by_verdict) HIPCHK(c, hipStreamWaitEvent(c->lf_stream, c->ev_fork, 0));   // the side work starts where the filter starts
         c->fork_by_verdict = c->fork_by_verdict_at_launch = by_verdict;
@@ -401,8 +406,12 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
         c->lf_pending = true;
         c->lf_sd = c->d_sd;
     } else {
-        Timed t(c, VP8HIP_K_LOOP_FILTER);
-        launch_loop_filter_of_type(c, c->stream, f, &chk);
+        {
+            Timed t(c, VP8HIP_K_LOOP_FILTER);
+            launch_loop_filter_of_type(c, c->stream, f, &chk);
+        }
+        c->lf_key = c->recon_key;
+        quality_after_filter(c, f, c->stream);
         c->verdict_stream = c->stream;
     }
     // the filtered reconstruction is the LAST reference of the next frame (vp8enc.cpp:395-401); its replicated edges are made

@@ -56,12 +56,14 @@ void vp8drv_default_config(vp8drv_config *c) {
     c->scene_detect = 0;
     c->src_width = c->src_height = 0;
     c->loop_filter_type = 0;
+    c->quality_stats = 0;
 }
 
 int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const vp8drv_config *cfg) {
     if (!out || !cfg) return VP8HIP_ERR_ARG;
     *out = nullptr;
     if (cfg->loop_filter_type != 0 && cfg->loop_filter_type != 1) return VP8HIP_ERR_ARG;
+    if (cfg->quality_stats != 0 && cfg->quality_stats != 1) return VP8HIP_ERR_ARG;
     vp8drv *d = new (std::nothrow) vp8drv();
     if (!d) return VP8HIP_ERR_ARG;
     d->cfg = *cfg;
@@ -72,6 +74,14 @@ int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const
     }
     if (cfg->loop_filter_type) {
         const int rc = vp8hip_set_loop_filter_type(d->hip, cfg->loop_filter_type);
+        if (rc != VP8HIP_OK) {
+            vp8hip_destroy(d->hip);
+            delete d;
+            return rc;
+        }
+    }
+    if (cfg->quality_stats) {
+        const int rc = vp8hip_set_quality_stats(d->hip, 1);
         if (rc != VP8HIP_OK) {
             vp8hip_destroy(d->hip);
             delete d;
@@ -558,6 +568,21 @@ int vp8drv_resolve(vp8drv *d) {
     if (!d) return VP8HIP_ERR_ARG;
     const int rc = resolve(d);
     return rc < 0 ? rc : (d->have_frame && d->last_key ? 1 : 0);
+}
+
+// the record of the frame just made final: its verdict first (a frame coded again as a key frame has the key frame's record)
+int vp8drv_get_frame_quality(vp8drv *d, vp8drv_quality *q) {
+    if (!d || !q) return VP8HIP_ERR_ARG;
+    if (!d->cfg.quality_stats || !d->have_frame) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    return vp8hip_quality_result(d->hip, q);
+}
+
+int vp8drv_get_quality_summary(vp8drv *d, vp8drv_quality_summary *s) {
+    if (!d || !s) return VP8HIP_ERR_ARG;
+    if (!d->cfg.quality_stats) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    return vp8hip_quality_summary(d->hip, s);
 }
 
 int vp8drv_ready(const vp8drv *d) { return !d || !d->verdict_pending || vp8hip_check_ssim_ready(d->hip); }

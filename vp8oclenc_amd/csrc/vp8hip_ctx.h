@@ -112,6 +112,14 @@ struct vp8hip_ctx {
     int src_w = 0, src_h = 0;       // vp8hip_set_source_size: size of the planes handed over as current frames (0 = coded size)
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out
+    // vp8hip_set_quality_stats: the state, the per-wave partials and the ticket of k_quality (one allocation), the state's host mirror
+    bool quality_on = false;
+    bool recon_key = false;         // the reconstruction in flight came from the intra path ...
+    bool lf_key = false;            // ... and so did the last filtered one
+    uint8_t *d_quality = nullptr;
+    vp8::QualityState *h_quality = nullptr;
+    uint32_t quality_seq = 0;       // launches so far: the last one writes this into h_quality->seq
+    hipStream_t quality_stream = nullptr;   // ... on this stream
     void *scratch = nullptr;        // device staging for debug pyramid downloads
     // coefficient entropy stage: per-block flags and third contexts, token counts per partition, probabilities
     uint8_t *ent_flags = nullptr, *ent_third = nullptr;
@@ -319,6 +327,10 @@ int receive_last_surface(const vp8hip_ctx *c);
 int adopt_last(vp8hip_ctx *c, int idx);
 // ---- api_profile.hip ----
 int prof_collect(vp8hip_ctx *c);
+// ---- api_quality.hip ----
+bool quality_item(vp8hip_ctx *c, const Frame &rec, hipStream_t s, QualityArgs &a);   // false: stats off
+void quality_after_filter(vp8hip_ctx *c, const Frame &rec, hipStream_t s);           // the measurement behind the context's filter
+int batch_quality(vp8hip_batch *b, const int *active);
 
 }  // namespace vp8
 

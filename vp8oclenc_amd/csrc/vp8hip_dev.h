@@ -12,6 +12,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/vp8hip.h"
+
 namespace vp8 {
 
 // Per-kernel timing (vp8hip_profile_enable): the launchers of the single-kernel stages go through VP8_LAUNCH, which hands
@@ -183,6 +185,43 @@ void launch_loop_filter_simple(hipStream_t s, const Frame &recon, const MBOut &o
 void launch_loop_filter_simple_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
                                      int32_t *const *progress, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk = nullptr);
 bool loop_filter_simple_fits(int mbh);   // its band counters fit their window of the progress buffer
+
+// ---- quality of the coded frames (kernels_quality.hip; vp8hip_set_quality_stats) --------------------------------------------
+// k_quality: one wave per tile of QUALITY_TILE_COLS x QUALITY_TILE_ROWS 4x4 blocks of one plane, all three planes in one launch; a
+// tile's partial sums go to `partial`, and the last wave to finish (an integer ticket) reduces them in a fixed order, folds the
+// previous record into the sums when it belongs to another frame, and writes the state (and its host mirror, then `seq`).
+constexpr int QUALITY_TILE_COLS = 63;   // block columns a wave owns (lane 63 loads the column right of them for the windows)
+constexpr int QUALITY_TILE_ROWS = 8;    // block rows a wave owns (it walks one more for the windows)
+struct QualitySums {                    // the frames made final (vp8hip_quality_totals before the means)
+    int64_t frames;
+    uint64_t sse[3], samples[3];
+    double psnr_all_sum, ssim_all_sum, ssim_sum[3], psnr_min;
+    int64_t psnr_min_frame;
+};
+struct QualityState {
+    vp8hip_quality pending;             // the last frame measured (not yet in `sums`)
+    int32_t has_pending;
+    uint32_t seq;                       // host mirror: the launch that wrote it (written last)
+    QualitySums sums;
+};
+struct QualityPartial { unsigned long long sse; double ssim; };
+struct QualityPlane { const uint8_t *s, *r; int ss, rs, w, h; };   // source, reconstruction, their strides; the region measured
+struct QualityArgs {
+    QualityPlane p[3];
+    QualityPartial *partial;            // quality_tiles() entries
+    unsigned *ticket;                   // zero at rest
+    QualityState *state;                // device copy
+    QualityState *host;                 // host mirror, or nullptr
+    uint32_t seq;
+    int32_t frame_number, is_key;
+};
+int quality_tiles(int w, int h);        // waves of one launch for a luma region of w x h (chroma ((w + 1) / 2) x ((h + 1) / 2))
+// the region of `src` (w x h luma) measured against `rec` (planes of the same layout)
+QualityArgs quality_args(const Frame &src, const Frame &rec, int w, int h);
+void launch_quality(hipStream_t s, const QualityArgs &a);
+void launch_quality_batch(hipStream_t s, const QualityArgs *a, int n);
+// the host's view of a state: the sums with the pending record folded in, as means
+void quality_totals(const QualityState &st, vp8hip_quality_totals *t);
 
 // per-frame parameter scans on the device copy of the current frame (kernels_rc.hip); stats = 4 uint32
 size_t rc_partial_words();   // uint32 words of per-workgroup partial sums the three launchers below need
