@@ -185,6 +185,23 @@ int vp8hip_conformant_stream(vp8hip_ctx *ctx, int on);
  * widths the reference never writes V's right padding (:180-183 read and write U instead) and this is what it means.
  * All members of a batch must have the same source size (vp8hip_batch_create and the batched launch check it). */
 int vp8hip_set_source_size(vp8hip_ctx *ctx, int src_width, int src_height);
+/* The other half of the reference's three sizes (video.src_* against video.dst_*; init.h:414-417 allocates "a buffer to store the
+ * resized input frame", init.h:1731-1732 sets dst = src "for now" and get_yuv420_frame's resize branch, encIO.h:228, has no body):
+ * source frames LARGER than the coded picture, scaled down on the device.  After this call the planes handed to
+ * vp8hip_upload_current / vp8hip_prefetch_current / vp8hip_set_current_device and the batched forms are tight planes of
+ * in_width x in_height (even, at most 16384, not below dst), and ONE launch (k_scale_b, in place of the pack) scales them to
+ * dst_width x dst_height and pads that to the coded size as vp8hip_set_source_size describes.  dst obeys vp8hip_set_source_size's
+ * rules for src and takes its place everywhere the source size is used (display size, the region of the quality statistics, which
+ * compare the reconstruction with the frame that was CODED, the scaled one: their PSNR is the codec's, not the scaler's).
+ * filter: 0 = area (box) filter, integers only, alias-free at any ratio; 1 = Lanczos-3 stretched by the ratio.  The arithmetic --
+ * separable, every plane on its own, chroma from (in / 2) to (dst / 2) -- is stated bit for bit in include/vp8hip_host.h
+ * (vp8host_scale_taps returns the very tables the device applies).  A size pair that needs more than 32 taps in a dimension (area
+ * beyond about 31:1, Lanczos beyond about 5:1), a bad size or filter: VP8HIP_ERR_ARG and nothing has changed.  0, 0, 0, 0 (any
+ * filter) = no scaling, frames of the coded size; in == dst = vp8hip_set_source_size(dst); vp8hip_set_source_size ends scaling.
+ * A pending vp8hip_prefetch_current made for another incoming size is dropped.  Waits for the context's streams (the tables change
+ * under them): not a per-frame call.  Reference planes (vp8hip_upload_last, vp8hip_set_last_device, downloads) keep the coded size.
+ * No upscaling: a decoder does that from the key frame header's scale bits.  All members of a batch must agree on all five values. */
+int vp8hip_set_source_scaling(vp8hip_ctx *ctx, int in_width, int in_height, int dst_width, int dst_height, int filter);
 
 /* prepare_filter_mask_and_non_zero_coeffs(), loop_filter.h:25-55.  nz_out: [MBs] or NULL.
  * (vp8hip_inter_transform already produced mask and counts for its own coefficients; this call
@@ -233,7 +250,9 @@ typedef struct {
     double psnr_min;               /* lowest psnr_all (0 without frames) ... */
     int64_t psnr_min_frame;        /* ... and its frame_number (-1 without frames) */
 } vp8hip_quality_totals;
-/* on = 1: from the next filter on, every frame is measured; turning it on from off starts a new summary.  0 (default): nothing runs. */
+/* on = 1: from the next filter on, every frame is measured; turning it on from off starts a new summary.  0 (default): nothing runs.
+ * With vp8hip_set_source_scaling the frame measured against is the one that was coded, the SCALED source, over dst_width x dst_height:
+ * the PSNR is the codec's, not the scaler's. */
 int vp8hip_set_quality_stats(vp8hip_ctx *ctx, int on);
 /* The record of the last frame measured.  Waits for that measurement alone (a word its launch writes last), not for the stream.
  * VP8HIP_ERR_STATE: stats off, or nothing measured yet. */
@@ -358,7 +377,9 @@ const char *vp8hip_status_string(int status);
  * built against an older header checks it once after loading the library.  3001: the shard, device-memory and frame-check entry points;
  * 3002: vp8drv_encode_video_device; 3003: vp8hip_import_last, vp8hip_group_*, the load-time hardware-queue setting;
  * vp8drv_frame_check folds position in (4: its values change); 4009: vp8hip_set_loop_filter_type and vp8drv_config.loop_filter_type;
- * 4010: quality statistics (vp8hip_set_quality_stats, vp8hip_batch_quality, vp8drv_config.quality_stats, vp8drv_get_frame_quality). */
+ * 4010: quality statistics (vp8hip_set_quality_stats, vp8hip_batch_quality, vp8drv_config.quality_stats, vp8drv_get_frame_quality);
+ * also under 4010: vp8hip_set_source_scaling, vp8host_scale_taps and vp8drv_config.in_width / in_height / scale_filter, in front of
+ * quality_stats, which stays the last field (a host fills the struct with vp8drv_default_config, which zeroes them: no scaling). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

@@ -69,12 +69,19 @@ typedef struct {
     int32_t loop_filter_type;    /* 0 (default): the normal loop filter, the reference's; 1: the simple loop filter (RFC 6386
                                 section 15.2, vp8hip_set_loop_filter_type), written into every frame header.  Other values:
                                 vp8drv_create returns VP8HIP_ERR_ARG.  Members of a batch must agree */
+    int32_t in_width, in_height, scale_filter;   /* in_* non-zero: the frames handed to vp8drv_encode_frame_* (and the prefetch / stage /
+                                batched forms) have THIS size and are scaled down on the device (vp8hip_set_source_scaling) to
+                                src_width x src_height, or to the coded size when those are 0; scale_filter 0 = area, 1 = Lanczos-3.
+                                Key frames carry the size scaled TO as the display size, as they carry src now.  Needs
+                                device_params = 1; vp8drv_create returns VP8HIP_ERR_ARG for whatever the setter refuses.
+                                0, 0 (default): no scaling.  Members of a batch must agree.  (They stand in front of
+                                quality_stats, which stays the struct's last field.) */
     int32_t quality_stats;       /* 1: PSNR and SSIM of every coded frame, measured on the device (vp8hip_set_quality_stats):
                                 vp8drv_get_frame_quality, vp8drv_get_quality_summary.  0 (default): off.  Other values:
                                 vp8drv_create returns VP8HIP_ERR_ARG */
 } vp8drv_config;
 
-void vp8drv_default_config(vp8drv_config *cfg);   /* the reference's defaults: 150, 5, 0, 48, -1, 1, 1, 1, 0, 0, 0, 0, 3, 0, 0, 0, 0, 0, 0 */
+void vp8drv_default_config(vp8drv_config *cfg);   /* the reference's defaults: 150, 5, 0, 48, -1, 1, 1, 1, 0, 0, 0, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 */
 
 int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const vp8drv_config *cfg);
 void vp8drv_destroy(vp8drv *d);

@@ -8,6 +8,7 @@
 #ifndef VP8HIP_HOST_H
 #define VP8HIP_HOST_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -41,6 +42,22 @@ void vp8host_prepare_segments_data(int is_key_frame, const int32_t refqi[4], int
  * (get_yuv420_frame checks bytes 0 and 4 of it, encIO.h:243-248: vp8host_y4m_frame_marker_ok). */
 int vp8host_y4m_parse_header(const uint8_t *data, size_t size, int32_t *width, int32_t *height, int32_t *framerate, size_t *first_frame_offset);
 int vp8host_y4m_frame_marker_ok(const uint8_t marker[6]);
+
+/* The tables of the device's scaler (vp8hip_set_source_scaling, include/vp8hip.h): one dimension of one plane, n_in samples to
+ * n_out <= n_in <= 16384.  For every output i: the first source sample start[i], and *n_taps (the same for every i, at most
+ * VP8HOST_SCALE_MAX_TAPS) signed coefficients coef[i * VP8HOST_SCALE_MAX_TAPS + k] whose sum is exactly 4096; the rest of a row is 0.
+ * Taps outside the plane are folded onto the edge sample, so 0 <= start[i] and start[i] + *n_taps <= n_in.  The device applies
+ *     t[y][i]   = (sum_k cx[i][k] * src[y][start_x[i] + k] + 32) >> 6                          (arithmetic shift, fits int16)
+ *     out[j][i] = clamp((sum_k cy[j][k] * t[start_y[j] + k][i] + (1 << 17)) >> 18, 0, 255).
+ * kind 0, area: in units of 1 / n_out of a source sample output i covers [i n_in, (i + 1) n_in), sample j covers
+ * [j n_out, (j + 1) n_out); with cum_j the length of output i's interval left of sample j's right end,
+ * c[i][j] = floor(4096 cum_j / n_in) - floor(4096 cum_(j-1) / n_in): integers only.  At 2:1 both passes together are
+ * (a + b + c + d + 2) >> 2.  kind 1, Lanczos-3 stretched by r = n_in / n_out: centre (i + 0.5) r - 0.5, taps ceil(centre - 3 r) ..
+ * floor(centre + 3 r), weights L(d / r), L(x) = sinc(x) sinc(x / 3) for |x| < 3, in double; each rounded to nearest of 4096 w / sum,
+ * the remainder added to the row's largest tap.  Returns 0, or -1 for bad arguments, more than VP8HOST_SCALE_MAX_TAPS taps (area
+ * beyond about 31:1, Lanczos beyond about 5:1), more taps than samples, or a row whose sum of |c| exceeds 8000. */
+#define VP8HOST_SCALE_MAX_TAPS 32
+int vp8host_scale_taps(int n_in, int n_out, int kind, int32_t *n_taps, int32_t *start /* [n_out] */, int16_t *coef /* [n_out * 32] */);
 
 /* frames.skip_prob, loop_filter.h:37-44 */
 int vp8host_skip_prob(const int32_t *MB_non_zero_coeffs, int mb_count);

@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--ssim-target", type=float, default=-1.0); ap.add_argument("--framerate", type=int, default=30)
     ap.add_argument("--simple-filter", action="store_true", help="the simple loop filter (RFC 6386 section 15.2, filter_type 1) instead of the normal one")
     ap.add_argument("--conformant", action="store_true", help="vp8hip_conformant_stream: NOT the reference byte for byte, but a stream that decodes to the encoder's own reconstruction")
+    ap.add_argument("--resize", default="", metavar="WxH", help="code the picture at this size: the frames are scaled down on the device (vp8hip_set_source_scaling)")
+    ap.add_argument("--resize-filter", choices=("area", "lanczos"), default="area")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dist = None
@@ -53,8 +55,11 @@ def main():
     else:
         seq = YuvFile(a.yuv, a.width, a.height) if a.yuv else SynthSequence(a.width, a.height, seed=1)
     frames = min(a.frames, seq.n) if (a.yuv or a.y4m) else a.frames
-    Wc, Hc = (seq.W + 15) // 16 * 16, (seq.H + 15) // 16 * 16            # the coded ("wrk") size, init.h:375-392
-    src = dict(src_width=seq.W, src_height=seq.H) if (Wc, Hc) != (seq.W, seq.H) else {}
+    Wd, Hd = (int(x) for x in a.resize.lower().split("x")) if a.resize else (seq.W, seq.H)      # the picture that is coded and displayed ("dst")
+    Wc, Hc = (Wd + 15) // 16 * 16, (Hd + 15) // 16 * 16            # the coded ("wrk") size, init.h:375-392
+    src = dict(src_width=Wd, src_height=Hd) if (Wc, Hc) != (Wd, Hd) else {}
+    if (Wd, Hd) != (seq.W, seq.H):
+        src.update(in_width=seq.W, in_height=seq.H, scale_filter=int(a.resize_filter == "lanczos"))
     t0 = time.perf_counter()
     mine = gop_shard.encode_chunks_frames(
         lambda: gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
@@ -63,9 +68,9 @@ def main():
         seq, gop_shard.chunks_of_rank(frames, a.gop, rank, world))
     allf = gop_shard.gather_frames(mine, frames, dist)
     if rank == 0:
-        n = gop_shard.write_ivf(a.out, allf, seq.W, seq.H, a.framerate)
+        n = gop_shard.write_ivf(a.out, allf, Wd, Hd, a.framerate)
         el = time.perf_counter() - t0
-        print(f"{a.out}: {frames} frames {seq.W}x{seq.H}, {n} bytes, {world} GPU(s), {frames / el:.1f} frames/s including the host-side frame source")
+        print(f"{a.out}: {frames} frames {seq.W}x{seq.H}{f' scaled to {Wd}x{Hd}' if a.resize else ''}, {n} bytes, {world} GPU(s), {frames / el:.1f} frames/s including the host-side frame source")
     if dist is not None:
         dist.close()
 

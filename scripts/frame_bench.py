@@ -18,6 +18,8 @@ ap.add_argument("--partitions", type=int, default=8)
 ap.add_argument("--check-ssim", type=int, default=0)
 ap.add_argument("--loop-filter-type", type=int, choices=(0, 1), default=0, help="0 = the normal loop filter, 1 = the simple one")
 ap.add_argument("--quality-stats", type=int, choices=(0, 1), default=0, help="1 = PSNR / SSIM of every frame on the device (vp8drv_config.quality_stats): what it costs")
+ap.add_argument("--scale-from", default="", metavar="WxH", help="the frames come in at this size and are scaled down to --width x --height on the device (vp8drv_config.in_width / in_height)")
+ap.add_argument("--scale-filter", choices=("area", "lanczos"), default="area")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -28,10 +30,19 @@ seq = SynthSequence(a.width, a.height, seed=1)
 W, H = seq.W, seq.H
 mbs = (W // 16) * (H // 16)
 nd = 8
-dev = [tuple(api.to_device(p) for p in seq.frame(t)) for t in range(nd)]
+scale = {}
+if a.scale_from:      # the same coded size, every frame through k_scale_b instead of k_pack_b
+    in_w, in_h = (int(x) for x in a.scale_from.lower().split("x"))
+    seq = SynthSequence(in_w, in_h, seed=1)
+    scale = dict(in_width=in_w, in_height=in_h, scale_filter=int(a.scale_filter == "lanczos"))
+    if (a.width, a.height) != (W, H):
+        scale.update(src_width=a.width, src_height=a.height)
+    dev = [tuple(api.to_device(np.ascontiguousarray(p[:in_h >> (i > 0), :in_w >> (i > 0)])) for i, p in enumerate(seq.frame(t))) for t in range(nd)]
+else:
+    dev = [tuple(api.to_device(p) for p in seq.frame(t)) for t in range(nd)]
 api.device_synchronize()
 drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
-                         loop_filter_type=a.loop_filter_type, quality_stats=a.quality_stats) for _ in range(a.streams)]
+                         loop_filter_type=a.loop_filter_type, quality_stats=a.quality_stats, **scale) for _ in range(a.streams)]
 sizes = [0] * a.streams
 
 def work(k, n, emit):
@@ -71,7 +82,7 @@ for emit in {"both": (False, True), "on": (True,), "off": (False,)}[a.only]:
     for k in range(a.streams): sizes[k] = 0
     el = run(a.frames, emit)
     fps = a.streams * a.frames / el
-    print(f"{W}x{H} {a.streams} streams x {a.frames} frames, bitstream {'on ' if emit else 'off'}: {fps:8.1f} fps, {fps * mbs / 1e6:6.2f} M MB/s, "
+    print(f"{W}x{H}{' scaled from ' + a.scale_from + ' (' + a.scale_filter + ')' if a.scale_from else ''} {a.streams} streams x {a.frames} frames, bitstream {'on ' if emit else 'off'}: {fps:8.1f} fps, {fps * mbs / 1e6:6.2f} M MB/s, "
           f"{el / a.frames * 1e3 / 1:7.3f} ms per frame and stream" + (f", {sum(sizes) / (a.streams * a.frames) / 1024:.1f} KiB per frame" if emit else ""))
 if a.streams == 1:   # the loop filter by its own clock (the kernel of the chosen type stamps the same words)
     ms, n, ghz = drvs[0].hip.profile_read_clock()

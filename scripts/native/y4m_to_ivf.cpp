@@ -1,7 +1,9 @@
 // y4m_to_ivf.cpp -- the reference's program with the path swapped in, as a complete C++ user of the C ABI: YUV4MPEG2 in,
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
-//              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr]
+//              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos]
+// -resize: the Y4M header gives the size of the frames that come in, WxH (even, not above it) the picture that is coded: the frames are
+// scaled down on the device (cfg.in_width / in_height, vp8hip_set_source_scaling); IVF header and key frames carry WxH.
 // As in the reference, check_SSIM runs after every inter frame and scene_change() looks at every frame that would be an inter frame.
 // Everything between the two files runs behind include/vp8hip_driver.h; the frames are handed over at their source size
 // and padded on the device (cfg.src_width / src_height), key frames carry that size as the display size.
@@ -26,6 +28,7 @@ int main(int argc, char **argv) {
     vp8drv_default_config(&cfg);
     cfg.scene_detect = 1;                       // main() calls scene_change() for every would-be inter frame (vp8enc.cpp:408)
     cfg.overlap_filter = 1;
+    int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -40,6 +43,13 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-conformant")) cfg.conformant_stream = 1;
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-psnr")) cfg.quality_stats = 1;               // PSNR / SSIM summary on stderr
+        else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
+        else if (!strcmp(argv[i], "-resize-filter")) {
+            const char *f = val();
+            if (!strcmp(f, "area")) cfg.scale_filter = 0;
+            else if (!strcmp(f, "lanczos")) cfg.scale_filter = 1;
+            else { fprintf(stderr, "-resize-filter area|lanczos\n"); return 2; }
+        }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     FILE *in = fopen(argv[1], "rb");
@@ -53,14 +63,19 @@ int main(int argc, char **argv) {
         return 1;
     }
     fseek(in, (long)first, SEEK_SET);
-    const int Wc = (W + 15) / 16 * 16, Hc = (H + 15) / 16 * 16;      // video.wrk_*, init.h:375-392
-    if (Wc != W || Hc != H) { cfg.src_width = W; cfg.src_height = H; }
+    // video.src_* is the file's size, video.dst_* the picture that is coded and displayed (-resize; the file's without it), video.wrk_* that
+    // rounded up to whole macroblocks (init.h:375-392).  The frames are handed over as the file has them: scaled and padded on the device.
+    const int Wd = rw ? rw : W, Hd = rh ? rh : H;
+    if (Wd < 2 || Hd < 2 || (Wd & 1) || (Hd & 1) || Wd > W || Hd > H) { fprintf(stderr, "-resize %dx%d: even, and not above the file's %dx%d\n", Wd, Hd, W, H); return 2; }
+    const int Wc = (Wd + 15) / 16 * 16, Hc = (Hd + 15) / 16 * 16;
+    if (Wc != Wd || Hc != Hd) { cfg.src_width = Wd; cfg.src_height = Hd; }
+    if (Wd != W || Hd != H) { cfg.in_width = W; cfg.in_height = H; }
     vp8drv *drv = nullptr;
     CK(vp8drv_create(&drv, Wc, Hc, 0, &cfg));
     FILE *out = fopen(argv[2], "wb");
     if (!out) { perror(argv[2]); return 1; }
     uint8_t fh[32];
-    fwrite(fh, 1, vp8bs_ivf_file_header(fh, W, H, (uint32_t)(fps ? fps : 30), 1, 0), out);     // frame count patched at the end (encIO.h:100-139)
+    fwrite(fh, 1, vp8bs_ivf_file_header(fh, Wd, Hd, (uint32_t)(fps ? fps : 30), 1, 0), out);     // frame count patched at the end (encIO.h:100-139)
     const size_t ysz = (size_t)W * H, csz = ysz / 4;
     std::vector<uint8_t> bytes((size_t)(Wc / 16) * (Hc / 16) * 1900 + (1 << 20));
     // A reader thread keeps a ring of page-locked frame buffers filled ahead of the coder (get_yuv420_frame's fread, encIO.h:204-254, off the
@@ -172,7 +187,7 @@ int main(int argc, char **argv) {
     // the reference's file says one frame more than it holds: write_output_header counts from a frame number that main() has
     // already advanced past the last frame (encIO.h:124-134, vp8enc.cpp:487-489; REFERENCE_DEFECTS.md #8) -- reproduced, the bar
     // being the reference's bytes
-    fwrite(fh, 1, vp8bs_ivf_file_header(fh, W, H, (uint32_t)(fps ? fps : 30), 1, n + 1), out);
+    fwrite(fh, 1, vp8bs_ivf_file_header(fh, Wd, Hd, (uint32_t)(fps ? fps : 30), 1, n + 1), out);
     fclose(out);
     fclose(in);
     vp8drv_stats st;

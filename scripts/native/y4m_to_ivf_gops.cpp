@@ -1,7 +1,8 @@
 // y4m_to_ivf_gops.cpp -- one YUV4MPEG2 file to one IVF file with its closed GOPs coded SIDE BY SIDE: the file-to-file form of what
 // bench.py's headline measures, as a complete C++ user of the C ABI.
 //   y4m_to_ivf_gops <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n]
-//                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)]
+//                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos]
+// (-resize: as in y4m_to_ivf.cpp -- frames of the file's size in, scaled down to WxH on the device, one launch per batch step)
 // A key frame resets every reference (intra_part.h:1091-1098, inter_part.h:35-50), so the frames [k g, (k + 1) g) of a run with
 // `-g g` are a unit of their own: N such chunks are in flight at once, B of them advance together as one batch (every stage ONE
 // launch for the batch: vp8drv_batch_*), a host thread per batch; the input is streamed (two page-locked frame buffers per chunk in
@@ -36,6 +37,7 @@ int main(int argc, char **argv) {
     vp8drv_config cfg;
     vp8drv_default_config(&cfg);
     int in_flight = 48, batch = 6;
+    int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -49,6 +51,13 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-chunks")) in_flight = atoi(val());
         else if (!strcmp(argv[i], "-batch")) batch = atoi(val());
+        else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
+        else if (!strcmp(argv[i], "-resize-filter")) {
+            const char *f = val();
+            if (!strcmp(f, "area")) cfg.scale_filter = 0;
+            else if (!strcmp(f, "lanczos")) cfg.scale_filter = 1;
+            else { fprintf(stderr, "-resize-filter area|lanczos\n"); return 2; }
+        }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (cfg.gop_size < 1 || batch < 1 || batch > VP8HIP_MAX_BATCH || in_flight < 1) { fprintf(stderr, "bad -g / -batch / -chunks\n"); return 2; }
@@ -76,8 +85,13 @@ int main(int argc, char **argv) {
     const int fd = open(argv[1], O_RDONLY);
     if (fd < 0) { perror(argv[1]); return 1; }
     const double t_read = now();
-    const int Wc = (W + 15) / 16 * 16, Hc = (H + 15) / 16 * 16;      // video.wrk_*, init.h:375-392
-    if (Wc != W || Hc != H) { cfg.src_width = W; cfg.src_height = H; }
+    // video.src_* is the file's size, video.dst_* the picture that is coded and displayed (-resize; the file's without it), video.wrk_* that
+    // rounded up to whole macroblocks (init.h:375-392).  The frames are handed over as the file has them: scaled and padded on the device.
+    const int Wd = rw ? rw : W, Hd = rh ? rh : H;
+    if (Wd < 2 || Hd < 2 || (Wd & 1) || (Hd & 1) || Wd > W || Hd > H) { fprintf(stderr, "-resize %dx%d: even, and not above the file's %dx%d\n", Wd, Hd, W, H); return 2; }
+    const int Wc = (Wd + 15) / 16 * 16, Hc = (Hd + 15) / 16 * 16;
+    if (Wc != Wd || Hc != Hd) { cfg.src_width = Wd; cfg.src_height = Hd; }
+    if (Wd != W || Hd != H) { cfg.in_width = W; cfg.in_height = H; }
     const int g = cfg.gop_size, nchunks = (nframes + g - 1) / g;
     if (in_flight > nchunks) in_flight = nchunks;
     const int nbatches = (in_flight + batch - 1) / batch;
@@ -104,7 +118,7 @@ int main(int argc, char **argv) {
     if (!out) { perror(argv[2]); return 1; }
     uint8_t fh[32];
     // the reference's file says one frame more than it holds (encIO.h:124-134, vp8enc.cpp:487-489; REFERENCE_DEFECTS.md #8) -- reproduced
-    fwrite(fh, 1, vp8bs_ivf_file_header(fh, W, H, (uint32_t)(fps ? fps : 30), 1, (uint32_t)nframes + 1), out);
+    fwrite(fh, 1, vp8bs_ivf_file_header(fh, Wd, Hd, (uint32_t)(fps ? fps : 30), 1, (uint32_t)nframes + 1), out);
     std::vector<std::vector<uint8_t>> out_frames((size_t)nframes);
     std::vector<char> ready((size_t)nframes, 0);
     std::mutex wm;

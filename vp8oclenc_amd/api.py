@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -430,6 +430,24 @@ class Gop:
         self.lib.vp8host_gop_frame_done(C.byref(self.s))
 
 
+SCALE_AREA, SCALE_LANCZOS = 0, 1   # filter of vp8hip_set_source_scaling / vp8drv_config.scale_filter
+SCALE_MAX_TAPS = 32                 # VP8HOST_SCALE_MAX_TAPS, include/vp8hip_host.h
+
+
+def scale_taps(n_in: int, n_out: int, kind: int = SCALE_AREA):
+    """vp8host_scale_taps: one dimension of one plane of the device's scaler -> (n_taps, start [n_out] int32, coef [n_out, n_taps] int16),
+    the very tables k_scale_b applies.  Raises ValueError when the pair is refused (more than 32 taps, bad arguments)."""
+    lib = load_library()
+    lib.vp8host_scale_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+    n = C.c_int32(0)
+    start = np.zeros(max(int(n_out), 1), np.int32)
+    coef = np.zeros((max(int(n_out), 1), SCALE_MAX_TAPS), np.int16)
+    if lib.vp8host_scale_taps(int(n_in), int(n_out), int(kind), C.byref(n), start.ctypes.data, coef.ctypes.data) != 0:
+        raise ValueError(f"vp8host_scale_taps({n_in} -> {n_out}, kind {kind}) refused")
+    assert not coef[:, n.value:].any()
+    return n.value, start, np.ascontiguousarray(coef[:, :n.value])
+
+
 class DrvConfig(C.Structure):
     """vp8drv_config, include/vp8hip_driver.h"""
     _fields_ = [("gop_size", C.c_int32), ("altref_range", C.c_int32), ("qi_min", C.c_int32), ("qi_max", C.c_int32),
@@ -437,7 +455,8 @@ class DrvConfig(C.Structure):
                 ("num_partitions", C.c_int32), ("display_width", C.c_int32), ("display_height", C.c_int32),
                 ("host_bitstream", C.c_int32), ("overlap_filter", C.c_int32), ("ref_mask", C.c_int32),
                 ("conformant_stream", C.c_int32), ("scene_detect", C.c_int32),
-                ("src_width", C.c_int32), ("src_height", C.c_int32), ("loop_filter_type", C.c_int32), ("quality_stats", C.c_int32)]
+                ("src_width", C.c_int32), ("src_height", C.c_int32), ("loop_filter_type", C.c_int32),
+                ("in_width", C.c_int32), ("in_height", C.c_int32), ("scale_filter", C.c_int32), ("quality_stats", C.c_int32)]
 
 
 class DrvStats(C.Structure):
@@ -929,6 +948,14 @@ class Vp8Hip:
         from the next loop_filter on.  The frame header's filter_type must say the same."""
         self.lib.vp8hip_set_loop_filter_type.argtypes = [C.c_void_p, C.c_int]
         self._chk(self.lib.vp8hip_set_loop_filter_type(self.h, int(t)), "set_loop_filter_type")
+
+    def set_source_scaling(self, in_width: int, in_height: int, dst_width: int, dst_height: int, filter: int = SCALE_AREA):
+        """vp8hip_set_source_scaling: current frames come in at in_width x in_height and are scaled down to dst on the device
+        (0, 0, 0, 0 = off); self.src is the size of the planes to hand over, as with set_source_size"""
+        self.lib.vp8hip_set_source_scaling.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        self._chk(self.lib.vp8hip_set_source_scaling(self.h, int(in_width), int(in_height), int(dst_width), int(dst_height), int(filter)),
+                  "set_source_scaling")
+        self.src = (int(in_width), int(in_height))
 
     def set_quality_stats(self, on: bool = True):
         """vp8hip_set_quality_stats: PSNR / SSIM of every filtered frame against its source, on the device (on from off: a new summary)"""

@@ -39,7 +39,7 @@ int vp8hip_batch_create(vp8hip_batch **out, vp8hip_ctx *const *ctxs, int n) {
     for (int i = 0; i < n; ++i) {
         if (!ctxs[i] || ctxs[i]->W != ctxs[0]->W || ctxs[i]->H != ctxs[0]->H || ctxs[i]->device != ctxs[0]->device ||
             ctxs[i]->ssim_target != ctxs[0]->ssim_target || ctxs[i]->lf_overlap || ctxs[i]->conformant != ctxs[0]->conformant ||
-            ctxs[i]->src_w != ctxs[0]->src_w || ctxs[i]->src_h != ctxs[0]->src_h)
+            !same_intake(ctxs[i], ctxs[0]))
             return VP8HIP_ERR_ARG;
         if (!ctxs[i]->own_stream) return VP8HIP_ERR_STATE;            // already a member of a batch
         for (int j = 0; j < i; ++j)
@@ -160,7 +160,8 @@ static int stage_copy(vp8hip_batch *b, uint8_t *d, const void *y, const void *u,
 // the copy stream, its events and the members' staging buffers (two each), made on first use and again when the source size has changed
 static int batch_stage_ready(vp8hip_batch *b) {
     vp8hip_ctx *c0 = b->c[0];
-    const int sw = c0->src_w ? c0->src_w : c0->W, sh = c0->src_h ? c0->src_h : c0->H;
+    int sw, sh;
+    incoming_size(c0, &sw, &sh);
     const size_t bytes = (size_t)sw * sh + 2 * (size_t)(sw / 2) * (sh / 2);
     if (!b->copy) {
         HIPCHK(c0, hipStreamCreateWithFlags(&b->copy, hipStreamNonBlocking));
@@ -197,12 +198,13 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
         if (!y[i] || !u[i] || !v[i]) return VP8HIP_ERR_ARG;
-        if (b->c[i]->src_w != c0->src_w || b->c[i]->src_h != c0->src_h) return VP8HIP_ERR_ARG;   // one launch, one source size
+        if (!same_intake(b->c[i], c0)) return VP8HIP_ERR_ARG;   // one launch, one source size (and one scaler: incoming size, dst, filter)
     }
     if (host) {
         const int rc = batch_stage_ready(b);
         if (rc) return rc;
-        const int sw = c0->src_w ? c0->src_w : c0->W, sh = c0->src_h ? c0->src_h : c0->H;
+        int sw, sh;
+        incoming_size(c0, &sw, &sh);
         const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
         slot = b->stage_idx ^= 1;
         bool waited = false;
@@ -229,12 +231,14 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     }
     const Frame *f[MAX_BATCH];
     const void *py[MAX_BATCH], *pu[MAX_BATCH], *pv[MAX_BATCH];
+    const ScalePlan *plans[MAX_BATCH];
     int n = 0;
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
         flush_scan(b->c[i]);      // (a parameter scan of the frame that is being replaced, asked for and never used: on that frame, now)
         next_current(b->c[i]);
         f[n] = &b->c[i]->cur;
+        plans[n] = &b->c[i]->scale;
         py[n] = y[i]; pu[n] = u[i]; pv[n] = v[i];
         ++n;
     }
@@ -255,7 +259,8 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     if (host) HIPCHK(c0, hipStreamWaitEvent(ps, b->ev_copied, 0));
     {
         Timed t(c0, VP8HIP_K_PACK);
-        launch_pack_batch(ps, f, py, pu, pv, n, c0->src_w, c0->src_h);
+        if (c0->scale.in_w) launch_scale_batch(ps, f, py, pu, pv, plans, n);      // a frame that is scaled is not packed as well
+        else launch_pack_batch(ps, f, py, pu, pv, n, c0->src_w, c0->src_h);
     }
     HIPCHK(c0, hipGetLastError());
     if (host) {
@@ -282,7 +287,8 @@ int vp8hip_batch_prefetch_current(vp8hip_batch *b, const uint8_t *const *y, cons
     USE_DEVICE_ONLY(c0);
     const int rc = batch_stage_ready(b);
     if (rc) return rc;
-    const int sw = c0->src_w ? c0->src_w : c0->W, sh = c0->src_h ? c0->src_h : c0->H;
+    int sw, sh;
+    incoming_size(c0, &sw, &sh);
     const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
     const int slot = b->stage_idx ^ 1;       // what the next upload will flip to
     if (b->packed_valid[slot]) HIPCHK(c0, hipStreamWaitEvent(b->copy, b->ev_packed[slot], 0));

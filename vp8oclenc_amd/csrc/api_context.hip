@@ -85,8 +85,24 @@ int copy_out(vp8hip_ctx *c, void *dst, const Plane &src) {
 }
 
 // sw, sh: size of the planes that come in (0 = the coded size): the current frames of a context with a source size
-int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw, int sh) {
+// scaled: they come in at the scaler's incoming size and k_scale_b takes k_pack_b's place (planes from the host: through scale_stage,
+// a frame larger than the surface cannot be copied into the surface first)
+int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw, int sh, bool scaled) {
     Timed t(c, VP8HIP_K_PACK);
+    if (scaled) {
+        const size_t ny = (size_t)c->scale.in_w * c->scale.in_h, nc = (size_t)(c->scale.in_w / 2) * (c->scale.in_h / 2);
+        if (kind != hipMemcpyDeviceToDevice) {
+            uint8_t *d = c->scale_stage;      // (the caller synchronises the stream before it returns: one buffer is enough)
+            HIPCHK(c, hipMemcpyAsync(d, y, ny, kind, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d + ny, u, nc, kind, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d + ny + nc, v, nc, kind, c->stream));
+            y = d; u = d + ny; v = d + ny + nc;
+        }
+        const Frame *fp = &f;
+        const ScalePlan *plan = &c->scale;
+        launch_scale_batch(c->stream, &fp, &y, &u, &v, &plan, 1);
+        return VP8HIP_OK;
+    }
     if (kind == hipMemcpyDeviceToDevice) {
         launch_pack(c->stream, f, y, u, v, sw, sh);
         return VP8HIP_OK;
@@ -441,6 +457,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
         hipFree(c->h2d_stage[1]);
     }
     if (c->ev_chroma) hipEventDestroy(c->ev_chroma);
+    hipFree(c->scale.d_blob);
+    hipFree(c->scale_stage);
     shard_release(c);
     event_pool_put(c->device, c->ev, c->ev_made);
     hipFree(c->pixel_pool);
@@ -462,7 +480,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
 int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     USE_DEVICE_ONLY(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
-    const int sw = c->src_w ? c->src_w : c->W, sh = c->src_h ? c->src_h : c->H;
+    int sw, sh;
+    incoming_size(c, &sw, &sh);
     const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
     if (!c->h2d_stream) {
         HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
@@ -501,7 +520,8 @@ int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, c
 int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     USE_DEVICE(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
-    const int sw = c->src_w ? c->src_w : c->W, sh = c->src_h ? c->src_h : c->H;
+    int sw, sh;
+    incoming_size(c, &sw, &sh);
     const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
     // a prefetch counts only for the source size it was made for: the staging buffers hold ny + 2 nc bytes of THAT size and the pack would read
     // them with this one's offsets (vp8hip_set_source_size also drops a pending prefetch; this is the second lock on the same door)
@@ -512,7 +532,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
         next_current(c);
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0));
         const uint8_t *d = c->h2d_stage[slot];
-        const int rc = set_frame_planes(c, c->cur, d, d + ny, d + ny + nc, hipMemcpyDeviceToDevice, c->src_w, c->src_h);
+        const int rc = set_frame_planes(c, c->cur, d, d + ny, d + ny + nc, hipMemcpyDeviceToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->ev_stage_read[slot], c->stream));
         c->stage_read_valid[slot] = true;
@@ -521,7 +541,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
     }
     c->h2d_pre_valid = false;
     next_current(c);
-    int rc = set_frame_planes(c, c->cur, y, u, v, hipMemcpyHostToDevice, c->src_w, c->src_h);
+    int rc = set_frame_planes(c, c->cur, y, u, v, hipMemcpyHostToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
     if (rc) return rc;
     // pageable host memory: the call must not return while the copy still reads the host buffer
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -532,23 +552,75 @@ int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const
     USE_DEVICE(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
     next_current(c);
-    return set_frame_planes(c, c->cur, y, u, v, hipMemcpyDeviceToDevice, c->src_w, c->src_h);
+    return set_frame_planes(c, c->cur, y, u, v, hipMemcpyDeviceToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
+}
+
+// dst of a scaler, or the source size: even, not above the coded size and fewer than 16 below it
+static bool source_size_ok(const vp8hip_ctx *c, int w, int h) {
+    return w > 0 && h > 0 && !(w & 1) && !(h & 1) && w <= c->W && h <= c->H && c->W - w < 16 && c->H - h < 16;
+}
+// what is still in flight may read the scaler's tables or its staging buffer: it ends first (the setters are not per-frame calls)
+static int scale_quiesce(vp8hip_ctx *c) {
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
+    if (c->h2d_stream) HIPCHK(c, hipStreamSynchronize(c->h2d_stream));
+    if (c->batch && c->batch->prep) HIPCHK(c, hipStreamSynchronize(c->batch->prep));
+    return VP8HIP_OK;
+}
+static void set_source(vp8hip_ctx *c, int w, int h, int in_w, int in_h, int kind) {
+    const bool same = w == c->W && h == c->H;
+    w = same ? 0 : w;
+    h = same ? 0 : h;
+    // planes prefetched at another incoming size are not this size's frame
+    if (w != c->src_w || h != c->src_h || in_w != c->scale.in_w || in_h != c->scale.in_h) c->h2d_pre_valid = false;
+    c->src_w = w;
+    c->src_h = h;
+    c->scale.in_w = in_w;
+    c->scale.in_h = in_h;
+    c->scale.kind = kind;
 }
 
 int vp8hip_set_source_size(vp8hip_ctx *c, int src_width, int src_height) {
     if (!c) return VP8HIP_ERR_ARG;
     if (src_width == 0 && src_height == 0) {
-        if (c->src_w || c->src_h) c->h2d_pre_valid = false;
-        c->src_w = c->src_h = 0;
+        set_source(c, 0, 0, 0, 0, 0);
         return VP8HIP_OK;
     }
-    if (src_width <= 0 || src_height <= 0 || (src_width & 1) || (src_height & 1) || src_width > c->W || src_height > c->H ||
-        c->W - src_width >= 16 || c->H - src_height >= 16)
+    if (!source_size_ok(c, src_width, src_height)) return VP8HIP_ERR_ARG;
+    set_source(c, src_width, src_height, 0, 0, 0);
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int dst_width, int dst_height, int filter) {
+    if (!c) return VP8HIP_ERR_ARG;
+    if (!in_width && !in_height && !dst_width && !dst_height) return vp8hip_set_source_size(c, 0, 0);
+    if (!source_size_ok(c, dst_width, dst_height) || (filter != 0 && filter != 1) || (in_width & 1) || (in_height & 1) ||
+        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384)
         return VP8HIP_ERR_ARG;
-    const bool same = src_width == c->W && src_height == c->H;
-    if ((same ? 0 : src_width) != c->src_w || (same ? 0 : src_height) != c->src_h) c->h2d_pre_valid = false;     // planes prefetched at the old size are not this size's frame
-    c->src_w = same ? 0 : src_width;
-    c->src_h = same ? 0 : src_height;
+    if (in_width == dst_width && in_height == dst_height) return vp8hip_set_source_size(c, dst_width, dst_height);
+    // everything that can be refused is tried before anything of the context changes
+    ScalePlan plan;
+    std::vector<uint8_t> blob;
+    if (!scale_plan_make(&plan, in_width, in_height, dst_width, dst_height, c->W, c->H, filter, blob)) return VP8HIP_ERR_ARG;
+    { const int rc = scale_quiesce(c); if (rc) return rc; }
+    const size_t stage = (size_t)in_width * in_height + 2 * (size_t)(in_width / 2) * (in_height / 2);
+    uint8_t *d_blob = nullptr;
+    HIPCHK(c, hipMalloc(&d_blob, blob.size()));
+    if (stage > c->scale_stage_bytes) {
+        uint8_t *d_stage = nullptr;
+        const hipError_t e = hipMalloc(&d_stage, stage);
+        if (e != hipSuccess) { (void)hipFree(d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
+        (void)hipFree(c->scale_stage);
+        c->scale_stage = d_stage;
+        c->scale_stage_bytes = stage;
+    }
+    const hipError_t e = hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
+    (void)hipFree(c->scale.d_blob);
+    set_source(c, dst_width, dst_height, in_width, in_height, filter);
+    plan.d_blob = d_blob;
+    c->scale = plan;
     return VP8HIP_OK;
 }
 

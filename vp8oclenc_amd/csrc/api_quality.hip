@@ -33,6 +33,8 @@ int quality_wait(vp8hip_ctx *c) {
 
 bool quality_item(vp8hip_ctx *c, const Frame &rec, hipStream_t s, QualityArgs &a) {
     if (!c->quality_on) return false;
+    // (with vp8hip_set_source_scaling the source size is what the frames are scaled TO and c->cur holds the scaled frame: the codec's
+    // error is measured, not the scaler's)
     const int w = c->src_w ? c->src_w : c->W, h = c->src_h ? c->src_h : c->H;
     a = quality_args(c->cur, rec, w, h);
     a.partial = quality_partial(c);

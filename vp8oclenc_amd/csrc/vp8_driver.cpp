@@ -56,6 +56,7 @@ void vp8drv_default_config(vp8drv_config *c) {
     c->scene_detect = 0;
     c->src_width = c->src_height = 0;
     c->loop_filter_type = 0;
+    c->in_width = c->in_height = c->scale_filter = 0;
     c->quality_stats = 0;
 }
 
@@ -90,14 +91,20 @@ int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const
     }
     if (cfg->overlap_filter) vp8hip_filter_overlap(d->hip, 1);
     if (cfg->conformant_stream) vp8hip_conformant_stream(d->hip, 1);
-    if (cfg->src_width || cfg->src_height) {
-        const int rc = cfg->device_params ? vp8hip_set_source_size(d->hip, cfg->src_width, cfg->src_height) : VP8HIP_ERR_ARG;
+    if (cfg->src_width || cfg->src_height || cfg->in_width || cfg->in_height) {
+        // the size the frames are scaled to (or come in at): video.dst_width/height
+        const int dw = cfg->src_width ? cfg->src_width : width, dh = cfg->src_height ? cfg->src_height : height;
+        int rc = VP8HIP_ERR_ARG;
+        if (cfg->device_params && (cfg->in_width || cfg->in_height) && cfg->in_width > 0 && cfg->in_height > 0)
+            rc = vp8hip_set_source_scaling(d->hip, cfg->in_width, cfg->in_height, dw, dh, cfg->scale_filter);
+        else if (cfg->device_params && !cfg->in_width && !cfg->in_height)
+            rc = vp8hip_set_source_size(d->hip, cfg->src_width, cfg->src_height);
         if (rc != VP8HIP_OK) {
             vp8hip_destroy(d->hip);
             delete d;
             return rc;
         }
-        if (!d->cfg.display_width) d->cfg.display_width = cfg->src_width;       // video.dst_width/height = the source's
+        if (!d->cfg.display_width) d->cfg.display_width = cfg->src_width;       // (0 = the coded size)
         if (!d->cfg.display_height) d->cfg.display_height = cfg->src_height;
     }
     d->W = width;
@@ -426,7 +433,8 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect) return VP8HIP_ERR_ARG;
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
-            a.loop_filter_type != z.loop_filter_type)
+            a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
+            (a.in_width && a.scale_filter != z.scale_filter))
             return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
     }

@@ -2,6 +2,8 @@
 // (include/vp8hip_host.h).  Plain C++, no HIP calls: usable (and tested) without a GPU.
 #include "../../include/vp8hip_host.h"
 
+#include <math.h>
+
 namespace {
 
 // src/vp8enc.h:17-39 (same tables as the kernels use)
@@ -252,5 +254,82 @@ void vp8host_gop_inter_flags(const vp8host_gop *g, int32_t *use_golden, int32_t 
 }
 
 void vp8host_gop_frame_done(vp8host_gop *g) { ++g->frame_number; }
+
+// The two filter tables of the device's scaler (include/vp8hip_host.h): integer-only for the area filter, `double` for Lanczos-3.
+int vp8host_scale_taps(int n_in, int n_out, int kind, int32_t *n_taps, int32_t *start, int16_t *coef) {
+    constexpr int MAXT = VP8HOST_SCALE_MAX_TAPS;
+    if (!n_taps || !start || !coef || n_in < 1 || n_out < 1 || n_out > n_in || n_in > 16384 || (kind != 0 && kind != 1)) return -1;
+    *n_taps = 0;
+    const double r = (double)n_in / n_out, pi = 3.14159265358979323846;
+    // first and last source sample output i touches
+    auto span = [&](int i, int *first, int *last) {
+        if (kind == 0) {
+            *first = (int)((int64_t)i * n_in / n_out);
+            *last = (int)((((int64_t)i + 1) * n_in - 1) / n_out);
+        } else {
+            const double c = (i + 0.5) * r - 0.5;
+            *first = (int)ceil(c - 3.0 * r);
+            *last = (int)floor(c + 3.0 * r);
+        }
+    };
+    int n = 0;
+    for (int i = 0; i < n_out; ++i) {
+        int a, b;
+        span(i, &a, &b);
+        if (b - a + 1 > n) n = b - a + 1;
+    }
+    if (n > MAXT || n > n_in) return -1;
+    for (int i = 0; i < n_out; ++i) {
+        int a, b;
+        span(i, &a, &b);
+        const int cnt = b - a + 1;
+        int32_t w[MAXT];
+        if (kind == 0) {
+            int64_t prev = 0;
+            for (int k = 0; k < cnt; ++k) {
+                int64_t cum = ((int64_t)a + k + 1) * n_out - (int64_t)i * n_in;      // of output i's interval, what lies left of this sample's right end
+                if (cum > n_in) cum = n_in;
+                const int64_t q = 4096 * cum / n_in;
+                w[k] = (int32_t)(q - prev);
+                prev = q;
+            }
+        } else {
+            const double c = (i + 0.5) * r - 0.5;
+            double f[MAXT], sum = 0.0;
+            for (int k = 0; k < cnt; ++k) {
+                const double x = (a + k - c) / r;
+                double v = 0.0;
+                if (fabs(x) < 3.0) v = x == 0.0 ? 1.0 : (sin(pi * x) / (pi * x)) * (sin(pi * x / 3.0) / (pi * x / 3.0));
+                f[k] = v;
+                sum += v;
+            }
+            for (int k = 0; k < cnt; ++k) w[k] = (int32_t)floor(4096.0 * f[k] / sum + 0.5);
+        }
+        // taps outside the plane fold onto the edge sample; the row then starts where all n taps are inside
+        int s = a < 0 ? 0 : a;
+        if (s > n_in - n) s = n_in - n;
+        int32_t row[MAXT] = {0};
+        for (int k = 0; k < cnt; ++k) {
+            int j = a + k;
+            j = j < 0 ? 0 : (j > n_in - 1 ? n_in - 1 : j);
+            row[j - s] += w[k];
+        }
+        if (kind == 1) {      // the rounding's remainder goes to the largest tap
+            int total = 0, big = 0;
+            for (int k = 0; k < n; ++k) {
+                total += row[k];
+                if (row[k] > row[big]) big = k;
+            }
+            row[big] += 4096 - total;
+        }
+        int mag = 0;
+        for (int k = 0; k < n; ++k) mag += row[k] < 0 ? -row[k] : row[k];
+        if (mag > 8000) return -1;      // 255 * 8000 / 64 = 31 875: the horizontal pass stays inside int16
+        start[i] = s;
+        for (int k = 0; k < MAXT; ++k) coef[(size_t)i * MAXT + k] = (int16_t)(k < n ? row[k] : 0);
+    }
+    *n_taps = n;
+    return 0;
+}
 
 }  // extern "C"

@@ -110,6 +110,11 @@ struct vp8hip_ctx {
     int lf_type = 0;                // vp8hip_set_loop_filter_type: 0 normal, 1 simple
     unsigned lf_simple_launches = 0;   // ... the simple filter's own window index (its counters are its own, LF_SIMPLE_WORD)
     int src_w = 0, src_h = 0;       // vp8hip_set_source_size: size of the planes handed over as current frames (0 = coded size)
+    // vp8hip_set_source_scaling: current frames come in at scale.in_w x scale.in_h (0 = no scaling) and k_scale_b makes src_w x src_h of
+    // them (the coded size when those are 0); the tables live in scale.d_blob, planes from host memory pass through scale_stage
+    vp8::ScalePlan scale;
+    uint8_t *scale_stage = nullptr;
+    size_t scale_stage_bytes = 0;
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out
     // vp8hip_set_quality_stats: the state, the per-wave partials and the ticket of k_quality (one allocation), the state's host mirror
@@ -291,7 +296,16 @@ void note_queue_oversubscription();
 int pick_free_frame(const vp8hip_ctx *c);
 int copy_in(vp8hip_ctx *c, const Plane &dst, const void *src, hipMemcpyKind kind);
 int copy_out(vp8hip_ctx *c, void *dst, const Plane &src);
-int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw = 0, int sh = 0);
+int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw = 0, int sh = 0, bool scaled = false);
+// size of the planes a context takes as current frames: the incoming size of its scaler, its source size, or the coded size
+inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) {
+    *w = c->scale.in_w ? c->scale.in_w : (c->src_w ? c->src_w : c->W);
+    *h = c->scale.in_w ? c->scale.in_h : (c->src_h ? c->src_h : c->H);
+}
+inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched pack / scale launch takes as one value
+    return a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
+           (!a->scale.in_w || a->scale.kind == b->scale.kind);
+}
 void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask = 0);
 int make_last(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
 SegData *sd_for_writing(vp8hip_ctx *c);

@@ -12,6 +12,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/vp8hip.h"
 
 namespace vp8 {
@@ -141,6 +143,14 @@ void launch_pyramid_batch(hipStream_t s, const Frame *const *f, int nframes, uin
 struct ScanRequest { uint32_t *partial, *stats; SegData *sd; int32_t *strength_out; int is_key; int32_t refqi[4]; int qi_min; };
 void launch_pack_batch(hipStream_t s, const Frame *const *f, const void *const *y, const void *const *u, const void *const *v, int n,
                        int sw = 0, int sh = 0);
+// kernels_scale.hip: a frame that comes in LARGER than the coded picture is scaled down into the surfaces instead of packed
+// (vp8hip_set_source_scaling).  A plan = the four tables (luma x, luma y, chroma x, chroma y) of include/vp8hip_host.h's
+// vp8host_scale_taps, stretched over the padded surface, in one device block.
+struct ScaleDim { int n, n_in, n_surf; size_t off_start, off_coef; int max_span[4]; };
+struct ScalePlan { int in_w = 0, in_h = 0, kind = 0; ScaleDim d[4] = {}; uint8_t *d_blob = nullptr; };
+bool scale_plan_make(ScalePlan *p, int in_w, int in_h, int dst_w, int dst_h, int W, int H, int kind, std::vector<uint8_t> &blob);   // false: refused
+void launch_scale_batch(hipStream_t s, const Frame *const *f, const void *const *y, const void *const *u, const void *const *v,
+                        const ScalePlan *const *plan, int n);
 bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int net_width, int n, bool finest, bool top_only = false);
 void launch_search1_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int level, int src_idx,
                           int net_width, int n);
