@@ -5,22 +5,28 @@
 // the kernel is built around what the vector pipe has to issue.  Pixels travel as signed bytes p - 128: every tap set sums to 128,
 // so a filter pass computes sum((p - 128) * f) = sum(p * f) - 128 * 128 and sat_i8((sum + 64) >> 7) IS the biased byte of the
 // reference's clamped sample (v_ashr_pk_i8_i32: no bias to undo).
-//   * 32 lanes per 8x8 block (2 blocks per wave, 8 per workgroup), one reference per blockIdx.y.
+//   * 32 lanes per 8x8 block (2 blocks per wave, 8 per workgroup).  In batches a workgroup takes its blocks through every enabled
+//     reference of its context, one after the other (grid y = 1): the blocks' coordinates, the current block's load and byte scatter
+//     and its share of the metric are made once for the two or three of them.  One video: one reference per blockIdx.y.
 //   * The 16 x 32-byte window around the 1x winner is staged in LDS by ONE unaligned 16-byte global load per lane (the window
 //     starts at its own first byte).
 //   * Horizontal pass = one v_mfma_i32_32x32x32_i8: A = the two blocks' window rows, B = the taps of the four fractional x cases
 //     x 8 columns (a constant operand table, make_bh below), the rounding 64 as one more product (k = 31: mfma_round).  A lane comes out with a
 //     column and four groups of four consecutive rows = four dwords of the TRANSPOSED H array, which go to LDS.
 //   * Vertical pass = three MFMAs over the wave's 2 x 5 x 8 columns: A = the taps of the four y cases (make_av), B = 32 columns of
-//     16 bytes, one ds_read_b128 each; a lane comes out with, per y case, one dword of the prediction [column][row half].  The
-//     whole-pel cases are copies.
+//     16 bytes, one ds_read_b128 each; a lane comes out with, per y case, one dword of the prediction: four rows of one column, stored
+//     [4x4 block][candidate][column] so that a (candidate, 4x4 block) task of the cost phase is 16 contiguous bytes.  The whole-pel cases
+//     are copies, and the zero-vector block is candidate 25 of the same array.
 //   * Then lane k = candidate (dx, dy) of the 25 (+ the zero-vector candidate): the block-match metric on four 4x4 blocks, the
 //     current block's share of its column pass made once per block into LDS (weight_pre_column) and the column pass of 64 (candidate,
 //     4x4 block) tasks of a wave as ONE more MFMA, the current block's share its C input (weight_mfma, vp8hip_dev.h); the minimum over
-//     the 32 lanes by four DPP steps + row_bcast.
+//     the 32 lanes by four DPP steps + row_bcast, over a key whose low byte holds the candidate's offsets as (dy + 2) * 8 + (dx + 2): the
+//     one lane that writes the block's result reads the winner's vector out of it.
 // The operand and result lane maps of the MFMA are pinned by scripts/ubench/mfma_i8_layout.hip, the results by the whole parity
 // suite.  History per 1080p frame and reference: 32-bit multiply-adds 0.156 ms; both passes on v_dot4_i32_i8 0.091 (892 vector
-// instructions per wave; git history, ae32ece^); this form 681 instructions, 56 us per chunk of three references.
+// instructions per wave; git history, ae32ece^); with the metric's column pass on the matrix cores 522 vector instructions per wave, group of
+// eight blocks and reference; with the reference loop 475 per reference + 53 per group = 493 at three references
+// (tests/test_search2_instruction_budget.py).
 #include <stdlib.h>
 #include <string.h>
 
@@ -71,7 +77,14 @@ static __device__ __constant__ const OperandTable K_BH = make_bh();
 static __device__ __constant__ const OperandTable K_AV = make_av();
 
 constexpr int HT_XC = 36;            // dwords per x case in the transposed H array: 8 columns x 16 B + 16 B bank skew
-constexpr int V_STRIDE = 20;           // dwords per candidate in the V array: 8 columns x 8 B + 16 B so that the b128 reads of 16 lanes miss each other's banks
+// The V array (vertical pass results = the predictions of the 25 candidates, + the zero-vector block as candidate 25) is ordered
+// [4x4 block][candidate][column]: a (candidate, 4x4 block) task of the cost phase is 16 contiguous bytes, one ds_read_b128, and the
+// 16 lanes such a read serves at a time take 16 consecutive candidates = 256 consecutive bytes = every bank once, with no skew.
+constexpr int V_CAND = 4;              // dwords per task: the four columns of a 4x4 block, four rows each
+constexpr int V_ROW = 26 * V_CAND;     // dwords per 4x4 block: 25 candidates (y case * 5 + x case) + the zero-vector block
+constexpr int V_SLOT = 4 * V_ROW;      // dwords per 8x8 block: 4x4 block b = 2 * (row half) + (column half)
+constexpr int V_ZERO = 25;
+constexpr int PRE_SLOT = 96;           // ints per 8x8 block in the pre table: 4x4 blocks 0, 1, 2, 3, 3, 3 x 16 (see search2_body)
 constexpr int WIN_ROW = 8;             // dwords per row of the staged window: 20 bytes loaded, 32 so that a row half is one aligned ds_read_b128
 // Every LDS array of the kernel is indexed by the block's slot g, and the two blocks of a wave sit in ITS lanes: the stages
 // hand data over inside a wave, so a wave-level "my LDS writes have landed" is all the synchronisation there is
@@ -143,203 +156,249 @@ __device__ __forceinline__ v16i mfma_round(v4i a, v4i b) {
 // same); here the idle lanes take the FOURTH 4x4 block of candidates 0..17 during the first three rounds, and the fourth 4x4 block of candidates
 // 18..25 of all eight blocks -- 64 tasks -- is one round of wave 0 alone: 3.25 rounds per wave on average instead of 4.  The costs meet in LDS
 // (in the H array's dead bytes), two workgroup barriers around wave 0's extra round.  Same integer sums in another order: the same result.
-// tn: the thread's number again, for what a workgroup that takes several groups (search2_groups) should NOT keep across its loop: every
+// ALLREFS: the workgroup takes its eight blocks through EVERY enabled reference of its context, one after the other (the batched forms, grid
+// y = 1); what does not depend on the reference is made once, ahead of the loop: the blocks' coordinates, the current block's load, its byte
+// scatter and its share of the metric (the pre table, which therefore has an array of its own: the H array's bytes are the next reference's).
+// Otherwise one reference, ref_idx (the one-video form: one reference per blockIdx.y).
+// tn: the thread's number again, for what a workgroup that takes several groups (search2_groups) should NOT keep across its loops: every
 // register of lane arithmetic kept is one a wave of the SIMD cannot have, and the cheap ones (two or three instructions to make) are made again
-template <bool SPREAD>
+template <bool SPREAD, bool ALLREFS>
 __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_idx, int tn) {
-    if (ref_idx >= a.nrefs) return;
+    if (ALLREFS ? a.nrefs == 0 : ref_idx >= a.nrefs) return;
     __shared__ __attribute__((aligned(16))) uint32_t s_HT[8][5 * HT_XC];
-    __shared__ __attribute__((aligned(16))) uint32_t s_cz[8][32];   // [0..15] current block, [16..31] zero-MV block, both as [column][row half], biased bytes
-    __shared__ __attribute__((aligned(16))) uint32_t s_V[8][25 * V_STRIDE];   // vertical pass results: [y case * 5 + x case][column][row half]
-    uint32_t(*s_win)[25 * V_STRIDE] = s_V;   // the staged window (16 rows x 32 B) is dead once the horizontal pass has read it: same bytes
-    // the current block's share of the metric, [4x4 block][column][R0,R2,X,Y]: made after the vertical pass, in the bytes of the H array
-    // (dead by then; the LDS per workgroup decides how many workgroups a CU holds: 22.8 KB = seven, with an array of its own six --
-    // 68.9-69.1 against 68.4-68.9 M MB/s on one box, scripts/ab_build.sh; eight, with the V array's bank skew given up, adds nothing)
-    int(*s_pre)[5 * HT_XC] = reinterpret_cast<int(*)[5 * HT_XC]>(s_HT);
-    const int r = a.refmap[ref_idx];
+    __shared__ __attribute__((aligned(16))) uint32_t s_V[8][V_SLOT];   // vertical pass results and the zero-MV block: [4x4 block][candidate][column], biased bytes
+    uint32_t(*s_win)[V_SLOT] = s_V;   // the staged window (16 rows x 32 B) is dead once the horizontal pass has read it: same bytes
+    // the current block's share of the metric, [4x4 block][column][R0,R2,X,Y], made once per group of blocks; 4x4 block 3 three times over
+    // (ints 48.., 64.., 80..), so that an idle lane of the cost phase, which stays on block 3, steps through the table as the others do.
+    // (LDS per workgroup decides how many workgroups a CU holds: 21.6 KB = seven.)
+    __shared__ __attribute__((aligned(16))) int s_pre[8][PRE_SLOT];
+    // [candidate]: the cost of its fourth 4x4 block, made by another lane: in the H array's bytes, dead once the vertical pass has read them
+    int(*s_q3)[5 * HT_XC] = reinterpret_cast<int(*)[5 * HT_XC]>(s_HT);
     const int g = threadIdx.x >> 5, lane = threadIdx.x & 31;
+    const int wl = threadIdx.x & 63, kh = wl >> 5, gp = g & ~1;   // lane of the wave, its k half in an MFMA operand, the wave's first slot
     const int b = imin(wg_x * 8 + g, a.nblk - 1);
     const bool live = wg_x * 8 + g < a.nblk;
     const int by = a.bw == 1 ? b : (int)__umulhi((uint32_t)b, a.bw_inv), bx = b - by * a.bw;   // b / bw: bw_inv = ceil(2^32 / bw), exact for b * bw < 2^32
     const int cx = bx * 8, cy = by * 8;
-    const uint32_t nv = reinterpret_cast<const uint32_t *>(a.net_in[r])[b];
-    const int nx = (int16_t)(nv & 0xffffu), ny = (int16_t)(nv >> 16);
-    const int v0x = (int16_t)(nx * 4), v0y = (int16_t)(ny * 4);
-    // window origin; a garbage vector (possible only when every candidate is out of frame) is clamped
-    // so that the loads stay inside the allocated margin
-    const int Lx = iclamp(cx + nx, 3 - EXT, a.w + EXT - 11), Ly = iclamp(cy + ny, 3 - EXT, a.h + EXT - 11);
-    const Plane rf = a.ref[r];
-    const int wl = threadIdx.x & 63, kh = wl >> 5, gp = g & ~1;   // lane of the wave, its k half in an MFMA operand, the wave's first slot
-    const int g_n = tn >> 5, lane_n = tn & 31, wl_n = tn & 63, kh_n = wl_n >> 5, gp_n = g_n & ~1;
-    // The window from its own first byte (Lx - 3: any alignment; the part's global loads need none): lane = (row, half) takes 16
-    // bytes, 16 rows of 32 bytes -- the six-tap passes need 14 x 19, the rest stays inside the planes' allocated margin (PAD) and
-    // meets zero taps.  One load and one ds_write_b128 per lane, no loop.
-    {
-        const int row = lane_n >> 1, half = lane_n & 1;
-        v4i v;
-        __builtin_memcpy(&v, rf.p + (ptrdiff_t)(Ly - 3 + row) * rf.stride + (Lx - 3) + 16 * half, 16);
-        *reinterpret_cast<v4i *>(&s_win[g_n][row * WIN_ROW + 4 * half]) = v ^ (int)0x80808080u;
-    }
-    {   // current block (lanes 0-15) and zero-MV block (16-31): one dword each, scattered as column bytes
-        const int sel = lane_n >> 4, row = (lane_n >> 1) & 7, half = lane_n & 1;
-        const uint8_t *base = sel ? rf.p : a.cur.p;
-        const int stride = sel ? rf.stride : a.cur.stride;
-        const uint32_t v = *reinterpret_cast<const uint32_t *>(base + (ptrdiff_t)(cy + row) * stride + cx + 4 * half) ^ 0x80808080u;
-        uint8_t *cz = reinterpret_cast<uint8_t *>(s_cz[g_n]) + sel * 64 + half * 32 + row;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cz[j * 8] = (uint8_t)(v >> (8 * j));
-    }
-    lds_fence();
-
-    // ---- horizontal pass: ONE MFMA for the wave's two blocks ------------------------------------------------------------
-    // A = the windows (row m = 16 * block + window row; rows 14, 15 and bytes 20..31 of a row hold whatever the LDS held: they
-    // meet zero taps or land in bytes nobody reads), B = the taps of the four fractional x cases (K_BH).  A lane comes out with
-    // column n = (x case, c) and four groups of four consecutive rows: each group one dword of the TRANSPOSED H array.
-    {
-        const int m = wl & 31, m_n = wl_n & 31;
-        const v4i aw = *reinterpret_cast<const v4i *>(&s_win[gp_n + (m_n >> 4)][(m_n & 15) * WIN_ROW + 4 * kh_n]);
-        const v4i bh = *reinterpret_cast<const v4i *>(K_BH.w[wl_n]);
-        const v16i acc = mfma_round(one_at_k31(aw, -kh_n), bh);
-        const int xi = m >> 3, c = m & 7, xc = xi + (xi >> 1);
-        uint32_t *ht = &s_HT[gp][xc * HT_XC + c * 4 + kh];   // rows 4 * kh .. of column c; + 2: rows 8 + 4 * kh ..; next slot: the other block
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ht[(q >> 1) * (5 * HT_XC) + 2 * (q & 1)] = round_pack4(acc, q);
-    }
-    {   // whole-pel x case: column c of the window, rows 4*rg..4*rg+3 (rows 14, 15 -- staged like the others -- only ever meet zero taps)
-        const int c = lane_n & 7, rg = lane_n >> 3;
-        const uint8_t *wb = reinterpret_cast<const uint8_t *>(s_win[g_n]) + 3 + c + rg * (16 * WIN_ROW);
-        uint32_t v = 0;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) v |= (uint32_t)wb[rr * (4 * WIN_ROW)] << (8 * rr);
-        s_HT[g_n][2 * HT_XC + c * 4 + rg] = v;
-    }
-    lds_fence();
-
-    // ---- vertical pass: three MFMAs for the wave's 2 x 5 x 8 columns ------------------------------------------------------
-    // A = the taps of the four fractional y cases (K_AV: row m = (y case, output row)), B = 32 columns of the H arrays, 16 bytes
-    // each (the lanes of the upper k half read the same column: their A entries are zero).  A lane comes out with its column and, per
-    // y case, the four rows 4 * kh .. 4 * kh + 3: one dword of the prediction [column][row half].  The whole-pel y case is a copy.
-    {
-        const v4i av = *reinterpret_cast<const v4i *>(K_AV.w[wl_n]);
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const int ng = 32 * t + (wl & 31);
-            const bool on = t < 2 || (wl & 31) < 16;
-            const int blk = ng >= 40 ? 1 : 0, rem = on ? ng - 40 * blk : 0, xc = rem >> 3, c = rem & 7;
-            const v4i hv = *reinterpret_cast<const v4i *>(&s_HT[gp + blk][xc * HT_XC + c * 4]);
-            const v16i acc = mfma_round(av, one_at_k31(hv, -kh_n));
-            if (on) {
-                uint32_t *sv = &s_V[gp + blk][xc * V_STRIDE + c * 2 + kh];
-#pragma unroll
-                for (int f = 0; f < 4; ++f) sv[(f + (f >> 1)) * 5 * V_STRIDE] = round_pack4(acc, f);
-                // whole-pel dy: rows 3..10 of the column, the lower lane half rows 3..6, the upper 7..10
-                sv[2 * 5 * V_STRIDE] = kh ? __builtin_amdgcn_alignbyte((uint32_t)hv[2], (uint32_t)hv[1], 3)
-                                          : __builtin_amdgcn_alignbyte((uint32_t)hv[1], (uint32_t)hv[0], 3);
-            }
-        }
-    }
-    lds_fence();
-    {   // the current block's share of the metric (vp8hip_dev.h, weight_pre_column): 16 columns x 4 quantities, two per lane.
+    {   // current block: lanes 0-15 one dword each, scattered as column bytes [column][row half] (16 dwords, in the table's last 64 bytes), then
+        // its share of the metric (vp8hip_dev.h, weight_pre_column): 16 columns x 4 quantities, two per lane.
         // Order = the order the cost loop below walks the 4x4 blocks: q = (m*2 + n)*4 + j  <->  column 4n+j, row half m
+        const int g_n = tn >> 5, lane_n = tn & 31;
+        uint32_t *tmp = reinterpret_cast<uint32_t *>(&s_pre[g_n][80]);
+        if (lane_n < 16) {
+            const int row = lane_n >> 1, half = lane_n & 1;
+            const uint32_t v = *reinterpret_cast<const uint32_t *>(a.cur.p + (ptrdiff_t)(cy + row) * a.cur.stride + cx + 4 * half) ^ 0x80808080u;
+            uint8_t *cz = reinterpret_cast<uint8_t *>(tmp) + half * 32 + row;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cz[j * 8] = (uint8_t)(v >> (8 * j));
+        }
+        lds_fence();
         const int q = lane_n & 15, m = q >> 3, n = (q >> 2) & 1, j = q & 3;
-        const uint32_t ccol = s_cz[g_n][(4 * n + j) * 2 + m];
+        const uint32_t ccol = tmp[(4 * n + j) * 2 + m];      // (every lane of the wave reads before any of them writes: LDS takes a wave's operations in order)
         int *pre = &s_pre[g_n][q * 4 + (lane_n >> 4) * 2];
-        pre[0] = dot4s(ccol, lane_n < 16 ? K_W_R0 : K_W_X, 0);
-        pre[1] = dot4s(ccol, lane_n < 16 ? K_W_R2 : K_W_Y, 0);
+        const int p0 = dot4s(ccol, lane_n < 16 ? K_W_R0 : K_W_X, 0), p1 = dot4s(ccol, lane_n < 16 ? K_W_R2 : K_W_Y, 0);
+        pre[0] = p0;
+        pre[1] = p1;
+        if (q >= 12) { pre[16] = p0; pre[17] = p1; pre[32] = p0; pre[33] = p1; }
     }
-    lds_fence();
-
-    // ---- cost: lane = candidate --------------------------------------------------------------------
+    // ---- lane = candidate: what of it does not depend on the reference ------------------------------
+    // its number in the key's low byte as (dy + 2) * 8 + (dx + 2), 40 for the zero vector: the same order as k, and the lane
+    // that writes the block's result takes the winner's offsets out of it with a mask and a shift
     const int k = lane;
     const int dx = k % 5 - 2, dy = k / 5 - 2;
-    int qx = (int16_t)(cx * 4 + v0x + dx), qy = (int16_t)(cy * 4 + v0y + dy);
-    if (k == 25) { qx = cx * 4; qy = cy * 4; }
-    const bool valid = live && k < 26 && qx >= 0 && qx <= a.w * 4 - 32 && qy >= 0 && qy <= a.h * 4 - 32;
-    int diff = 0;
-    const v4i wa = metric_a(wl_n);        // the metric's column pass on the matrix cores (weight_mfma, vp8hip_dev.h): every lane of the wave is here
-    // a 4x4 block's four prediction columns: every other dword of [column][row half] from its first one
-    auto cols4 = [](const uint32_t *src) { return v4i{(int)src[0], (int)src[2], (int)src[4], (int)src[6]}; };
-    if (SPREAD) {
-        int *q3 = &s_pre[g][64];          // [candidate]: the cost of its fourth 4x4 block, made by another lane (the H array's bytes behind the pre table)
-        const bool helper = lane >= 26;
-        // (branch-free: a lane's own candidate or, for the idle lanes, candidate hb + j; the idle lanes' costs go to q3, everybody else's
-        // store lands in the table's unused word 31)
-        const uint32_t *own = k < 25 ? &s_V[g][k * V_STRIDE] : &s_cz[g][16];
-        const uint32_t *hsrc = &s_V[g][(lane - 26) * 3 * V_STRIDE + 9];     // idle lanes: candidate 3 (lane - 26) + j, 4x4 block 3 (n = m = 1)
-        int *hdst = &q3[(lane - 26) * 3];
-        auto metric = [&](const uint32_t *src, const int *pre16) { return weight_mfma(wa, load_pre16(pre16), cols4(src)); };
+    // (with the candidate's vector-cost penalty, :1176-1178, above it: cost and number go into the key with one shift-and-add)
+    const uint32_t kcode = k < 25 ? (uint32_t)((iabs(dx) + iabs(dy)) * 32 * 256 + (dy + 2) * 8 + dx + 2) : 40u;
+    const v4i wa = metric_a(wl);        // the metric's column pass on the matrix cores (weight_mfma, vp8hip_dev.h): every lane of the wave is here
+
+    // ---- everything below is per reference ------------------------------------------------------------------------------
+    // From the part above it uses: b, live, cx, cy (the block), k, dx, dy, kcode, wa (the lane's candidate) and the pre table.
+    // Its LDS reuse rests on one rule -- LDS executes a wave's operations in program order, and every array slot is written only by the
+    // wave whose lanes own it (the one wave of the fourth-block round only reads other slots, between the two barriers):
+    //   * the window lives in the first 512 bytes of the block's V slot; candidate 25 of 4x4 block 0 (bytes 400..415) lies inside them, so
+    //     the zero-MV scatter comes after the last read of the window and before the vertical pass's stores;
+    //   * q3 (the fourth-block costs) lives in words 64..95 of the block's H slot, written after the vertical pass has read the H array and
+    //     read back before the next reference's horizontal pass writes it; words 29..31 of q3 take the stores nobody reads;
+    //   * the pre table is only read here.
+    auto one_reference = [&](int ri) {
+        int tr = tn;
+        if (ALLREFS) asm volatile("" : "+v"(tr));     // (the same number, as far as the compiler can tell a new one per reference)
+        const int g_n = tr >> 5, lane_n = tr & 31, wl_n = tr & 63, kh_n = wl_n >> 5, gp_n = g_n & ~1;
+        const int r = a.refmap[ri];
+        const uint32_t nv = reinterpret_cast<const uint32_t *>(a.net_in[r])[b];
+        const int nx = (int16_t)(nv & 0xffffu), ny = (int16_t)(nv >> 16);
+        const int v0x = (int16_t)(nx * 4), v0y = (int16_t)(ny * 4);
+        // window origin; a garbage vector (possible only when every candidate is out of frame) is clamped
+        // so that the loads stay inside the allocated margin
+        const int Lx = iclamp(cx + nx, 3 - EXT, a.w + EXT - 11), Ly = iclamp(cy + ny, 3 - EXT, a.h + EXT - 11);
+        const Plane rf = a.ref[r];
+        // The window from its own first byte (Lx - 3: any alignment; the part's global loads need none): lane = (row, half) takes 16
+        // bytes, 16 rows of 32 bytes -- the six-tap passes need 14 x 19, the rest stays inside the planes' allocated margin (PAD) and
+        // meets zero taps.  One load and one ds_write_b128 per lane, no loop.
+        {
+            const int row = lane_n >> 1, half = lane_n & 1;
+            v4i v;
+            __builtin_memcpy(&v, rf.p + (ptrdiff_t)(Ly - 3 + row) * rf.stride + (Lx - 3) + 16 * half, 16);
+            *reinterpret_cast<v4i *>(&s_win[g_n][row * WIN_ROW + 4 * half]) = v ^ (int)0x80808080u;
+        }
+        // zero-MV block: one dword per lane (both halves of the block's lanes load the same eight rows: no branch), scattered below, once the
+        // window -- whose bytes its place in the V array shares -- has been read
+        const uint32_t zv = *reinterpret_cast<const uint32_t *>(rf.p + (ptrdiff_t)(cy + ((lane_n >> 1) & 7)) * rf.stride + cx + 4 * (lane_n & 1)) ^ 0x80808080u;
+        lds_fence();
+
+        // ---- horizontal pass: ONE MFMA for the wave's two blocks ------------------------------------------------------------
+        // A = the windows (row m = 16 * block + window row; rows 14, 15 and bytes 20..31 of a row hold whatever the LDS held: they
+        // meet zero taps or land in bytes nobody reads), B = the taps of the four fractional x cases (K_BH).  A lane comes out with
+        // column n = (x case, c) and four groups of four consecutive rows: each group one dword of the TRANSPOSED H array.
+        {
+            const int m = wl & 31, m_n = wl_n & 31;
+            const v4i aw = *reinterpret_cast<const v4i *>(&s_win[gp_n + (m_n >> 4)][(m_n & 15) * WIN_ROW + 4 * kh_n]);
+            const v4i bh = *reinterpret_cast<const v4i *>(K_BH.w[wl_n]);
+            const v16i acc = mfma_round(one_at_k31(aw, -kh_n), bh);
+            const int xi = m >> 3, c = m & 7, xc = xi + (xi >> 1);
+            uint32_t *ht = &s_HT[gp][xc * HT_XC + c * 4 + kh];   // rows 4 * kh .. of column c; + 2: rows 8 + 4 * kh ..; next slot: the other block
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {       // rounds 0..2: a candidate's own lane its 4x4 blocks 0..2, the idle lanes block 3 of candidates 0..17
-            const int c = metric(helper ? hsrc + j * V_STRIDE : own + (8 * (j & 1) + (j >> 1)), &s_pre[g][helper ? 48 : 16 * j]);
-            *(helper ? hdst + j : &q3[31]) = c;
-            diff += helper ? 0 : c;
+            for (int q = 0; q < 4; ++q) ht[(q >> 1) * (5 * HT_XC) + 2 * (q & 1)] = round_pack4(acc, q);
         }
-        __syncthreads();                    // every wave's V / pre / zero-MV arrays (and the idle lanes' costs) are in LDS
-        if ((int)(threadIdx.x >> 6) == (wg_x & 3)) {      // ONE wave (taking turns from workgroup to workgroup: the waves of a workgroup sit on different SIMDs): block 3 of candidates 18..25 of all eight block slots
-            const int slot = wl >> 3, cand = 18 + (wl & 7);
-            s_pre[slot][64 + cand] = metric((cand < 25 ? &s_V[slot][cand * V_STRIDE] : &s_cz[slot][16]) + 9, &s_pre[slot][48]);
+        {   // whole-pel x case: column c of the window, rows 4*rg..4*rg+3 (rows 14, 15 -- staged like the others -- only ever meet zero taps)
+            const int c = lane_n & 7, rg = lane_n >> 3;
+            const uint8_t *wb = reinterpret_cast<const uint8_t *>(s_win[g_n]) + 3 + c + rg * (16 * WIN_ROW);
+            uint32_t v = 0;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) v |= (uint32_t)wb[rr * (4 * WIN_ROW)] << (8 * rr);
+            s_HT[g_n][2 * HT_XC + c * 4 + rg] = v;
         }
-        __syncthreads();
-        diff += q3[k < 26 ? k : 31];
+        {   // the zero-MV block as candidate 25 of the V array: the lane's dword = row `row`, columns 4 * half .. + 3 -> byte row & 3 of the four
+            // column dwords of 4x4 block (row >> 2, half).  (Behind the window's reads: LDS takes a wave's operations in order.)
+            const int row = (lane_n >> 1) & 7, half = lane_n & 1;
+            uint8_t *z = reinterpret_cast<uint8_t *>(&s_V[g_n][((row >> 2) * 2 + half) * V_ROW + V_ZERO * V_CAND]) + (row & 3);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j * 4] = (uint8_t)(zv >> (8 * j));
+        }
+        lds_fence();
+
+        // ---- vertical pass: three MFMAs for the wave's 2 x 5 x 8 columns ------------------------------------------------------
+        // A = the taps of the four fractional y cases (K_AV: row m = (y case, output row)), B = 32 columns of the H arrays, 16 bytes
+        // each (the lanes of the upper k half read the same column: their A entries are zero).  A lane comes out with its column and, per
+        // y case, the four rows 4 * kh .. 4 * kh + 3: one dword of the prediction, column c & 3 of 4x4 block (kh, c >> 2).  The whole-pel y case is a copy.
+        {
+            const v4i av = *reinterpret_cast<const v4i *>(K_AV.w[wl_n]);
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const int ng = 32 * t + (wl & 31);
+                const bool on = t < 2 || (wl & 31) < 16;
+                const int blk = ng >= 40 ? 1 : 0, rem = on ? ng - 40 * blk : 0, xc = rem >> 3, c = rem & 7;
+                const v4i hv = *reinterpret_cast<const v4i *>(&s_HT[gp + blk][xc * HT_XC + c * 4]);
+                const v16i acc = mfma_round(av, one_at_k31(hv, -kh_n));
+                if (on) {
+                    uint32_t *sv = &s_V[gp + blk][(kh * 2 + (c >> 2)) * V_ROW + xc * V_CAND + (c & 3)];
+#pragma unroll
+                    for (int f = 0; f < 4; ++f) sv[(f + (f >> 1)) * 5 * V_CAND] = round_pack4(acc, f);
+                    // whole-pel dy: rows 3..10 of the column, the lower lane half rows 3..6, the upper 7..10
+                    sv[2 * 5 * V_CAND] = kh ? __builtin_amdgcn_alignbyte((uint32_t)hv[2], (uint32_t)hv[1], 3)
+                                            : __builtin_amdgcn_alignbyte((uint32_t)hv[1], (uint32_t)hv[0], 3);
+                }
+            }
+        }
+        lds_fence();
+
+        // ---- cost: lane = candidate --------------------------------------------------------------------
+        int qx = (int16_t)(cx * 4 + v0x + dx), qy = (int16_t)(cy * 4 + v0y + dy);
+        if (k == 25) { qx = cx * 4; qy = cy * 4; }
+        const bool valid = live && k < 26 && qx >= 0 && qx <= a.w * 4 - 32 && qy >= 0 && qy <= a.h * 4 - 32;
+        int diff = 0;
+        // a task = 16 bytes of the V array (the B operand: one ds_read_b128) and 16 ints of the pre table (the C input)
+        auto metric = [&](const uint32_t *src, const int *pre16) { return weight_mfma(wa, load_pre16(pre16), *reinterpret_cast<const v4i *>(src)); };
+        if (SPREAD) {
+            int *q3 = &s_q3[g][64];
+            const bool helper = lane >= 26;
+            // (branch-free: a lane's own candidate, 4x4 block j in round j, or, for the idle lanes, 4x4 block 3 of candidate 3 (lane - 26) + j: one
+            // base address and one stride per lane, the table's copies of block 3 one block apart like the others; the idle lanes' costs go to q3,
+            // everybody else's to the table's unused words 29..31, and an idle lane's own sum is never looked at: `valid` is false there)
+            const uint32_t *src = helper ? &s_V[g][3 * V_ROW + (lane - 26) * 3 * V_CAND] : &s_V[g][k * V_CAND];
+            const int step = helper ? V_CAND : V_ROW;
+            const int *pre = &s_pre[g][helper ? 48 : 0];
+            int *dst = &q3[helper ? (lane - 26) * 3 : 29];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {       // rounds 0..2: a candidate's own lane its 4x4 blocks 0..2, the idle lanes block 3 of candidates 0..17
+                const int c = metric(src + j * step, pre + 16 * j);
+                dst[j] = c;
+                diff += c;
+            }
+            __syncthreads();                    // every wave's V and pre arrays (and the idle lanes' costs) are in LDS
+            if ((int)(threadIdx.x >> 6) == (wg_x & 3)) {      // ONE wave (taking turns from workgroup to workgroup: the waves of a workgroup sit on different SIMDs): block 3 of candidates 18..25 of all eight block slots
+                const int slot = wl >> 3, cand = 18 + (wl & 7);
+                s_q3[slot][64 + cand] = metric(&s_V[slot][3 * V_ROW + cand * V_CAND], &s_pre[slot][48]);
+            }
+            __syncthreads();
+            diff += q3[k < 26 ? k : 31];
+        } else {
+            // lane 25: the zero-MV block (whole-pel: both passes are the identity); the idle lanes read it too
+            const uint32_t *src = &s_V[g][imin(k, V_ZERO) * V_CAND];
+#pragma unroll
+            for (int bb = 0; bb < 4; ++bb) diff += metric(src + bb * V_ROW, &s_pre[g][bb * 16]);
+        }
+        uint32_t key = ((uint32_t)diff << 8) + kcode;     // (diff + penalty) << 8 | number
+        key = (valid && key < (0x7fffu << 8)) ? key : 0xffffffffu;
+        key = halfwave_min_upper(key);
+        if (lane == 16 && live) {   // (every lane of the block holds the block's position and vector; this one also the minimum)
+            // :1136-1137: with no candidate in the frame the result is the frame's last position; otherwise the winner's, as a vector: the
+            // block's own position drops out of (int16)((int16)(4 cx + v0x + dx) - 4 cx) = (int16)(v0x + dx)
+            int vx = (int16_t)((int16_t)(a.w * 4 - 32) - cx * 4), vy = (int16_t)((int16_t)(a.h * 4 - 32) - cy * 4), md = 0x7fff;
+            if (key != 0xffffffffu) {
+                const int kk = key & 0xff;
+                md = (int)(key >> 8);
+                vx = kk == 40 ? 0 : (int16_t)(v0x + (kk & 7) - 2);
+                vy = kk == 40 ? 0 : (int16_t)(v0y + (kk >> 3) - 2);
+            }
+            if ((vx != 0) | (vy != 0)) md -= (iabs(vx - v0x) + iabs(vy - v0y)) * 32;  // :1195-1197
+            reinterpret_cast<uint32_t *>(a.net_out[r])[b] = (uint32_t)(uint16_t)vx | ((uint32_t)(uint16_t)vy << 16);
+            a.bdiff[r][b] = md;
+        }
+    };
+    if (ALLREFS) {
+#pragma unroll 1
+        for (int ri = 0; ri < a.nrefs; ++ri) one_reference(ri);
     } else {
-    // candidates 0..24: their prediction from the producer; lane 25 (zero MV: whole-pel, both passes are the identity)
-    // and the idle lanes read the zero-MV block.  4x4 block (m, n) = columns 4n.., row half m
-    const uint32_t *src = k < 25 ? &s_V[g][k * V_STRIDE] : &s_cz[g][16];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) diff += weight_mfma(wa, load_pre16(&s_pre[g][(m * 2 + n) * 16]), cols4(src + 8 * n + m));
-    }
-    if (k < 25) diff += (iabs(dx) + iabs(dy)) * 32;  // :1176-1178
-    uint32_t key = (valid && diff < 0x7fff) ? ((uint32_t)diff << 8) | (uint32_t)k : 0xffffffffu;
-    key = halfwave_min_upper(key);
-    if (lane == 16 && live) {   // (every lane of the block holds the block's position and vector; this one also the minimum)
-        int bqx = (int16_t)(a.w * 4 - 32), bqy = (int16_t)(a.h * 4 - 32), md = 0x7fff;  // :1136-1137
-        if (key != 0xffffffffu) {
-            const int kk = key & 0xff;
-            md = (int)(key >> 8);
-            bqx = kk == 25 ? cx * 4 : (int16_t)(cx * 4 + v0x + (kk % 5 - 2));
-            bqy = kk == 25 ? cy * 4 : (int16_t)(cy * 4 + v0y + (kk / 5 - 2));
-        }
-        const int vx = (int16_t)(bqx - cx * 4), vy = (int16_t)(bqy - cy * 4);
-        if ((vx != 0) | (vy != 0)) md -= (iabs(vx - v0x) + iabs(vy - v0y)) * 32;  // :1195-1197
-        reinterpret_cast<uint32_t *>(a.net_out[r])[b] = (uint32_t)(uint16_t)vx | ((uint32_t)(uint16_t)vy << 16);
-        a.bdiff[r][b] = md;
+        one_reference(ref_idx);
     }
 }
 
 // ITER: a workgroup takes ITER consecutive groups of eight blocks, one after the other.  A third of what a wave issues for a group does not
 // depend on the group -- the lane's place in the operand tables of the two passes and the tables themselves, its LDS addresses in every stage, its
 // candidate's offset and penalty -- and the compiler keeps all of it in registers across the loop (the price: registers, i.e. waves per SIMD).
-template <bool SPREAD, int ITER>
+template <bool SPREAD, int ITER, bool ALLREFS>
 __device__ __forceinline__ void search2_groups(const S2Args &a, int grp, int ref_idx) {
-    if (ITER == 1) { search2_body<SPREAD>(a, grp, ref_idx, (int)threadIdx.x); return; }
+    if (ITER == 1 && !ALLREFS) { search2_body<SPREAD, ALLREFS>(a, grp, ref_idx, (int)threadIdx.x); return; }
 #pragma unroll 1
     for (int it = 0; it < ITER; ++it) {
         int tn = (int)threadIdx.x;
         asm volatile("" : "+v"(tn));     // (the same number, as far as the compiler can tell a new one per group)
-        search2_body<SPREAD>(a, grp * ITER + it, ref_idx, tn);
+        search2_body<SPREAD, ALLREFS>(a, grp * ITER + it, ref_idx, tn);
     }
 }
+// (waves_per_eu, here as on the batched forms: left to __launch_bounds__(256, 4) the register allocator takes 74 registers for the two-group
+// form -- six waves per SIMD -- where it fits the same code into 72 when told to; the one-group form, the default for one video, has 57
+// either way.  The MFMAs' results still land in VGPRs, no v_accvgpr_read per result: tests/test_kernel_resources.py pins zero AGPRs.)
 template <bool SPREAD, int ITER>
-__global__ __launch_bounds__(256, 4) void k_search2(S2Args a) {   // (a register budget of 128 also makes the MFMAs write VGPRs: no v_accvgpr_read per result)
+__global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2(S2Args a) {
     launch_clock_begin(a.clk);
-    search2_groups<SPREAD, ITER>(a, xcd_band(blockIdx.x, gridDim.x), blockIdx.y);
+    search2_groups<SPREAD, ITER, false>(a, xcd_band(blockIdx.x, gridDim.x), blockIdx.y);
     launch_clock_end(a.clk);
 }
 static_assert(sizeof(BatchOf<S2Args>) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+// The batched forms: grid (groups, 1, contexts), every enabled reference of the context inside the workgroup (ALLREFS)
 template <bool SPREAD, int ITER>
-__global__ __launch_bounds__(256, 4) void k_search2_b(BatchOf<S2Args> b) {
+__global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2_b(BatchOf<S2Args> b) {
     launch_clock_begin(b.item[0].clk);
-    search2_groups<SPREAD, ITER>(b.item[blockIdx.z], xcd_band(blockIdx.x, gridDim.x), blockIdx.y);
+    search2_groups<SPREAD, ITER, true>(b.item[blockIdx.z], xcd_band(blockIdx.x, gridDim.x), 0);
     launch_clock_end(b.item[0].clk);
 }
 // The same launch carrying the loop-filter strength scans of its members' NEW frames (kernels_rc_dev.h): the workgroups behind the
-// nbx block groups of reference 0.  With the part full a launch of the scan's own holds the batch's stream for 0.4-0.7 ms where its
+// nbx block groups.  With the part full a launch of the scan's own holds the batch's stream for 0.4-0.7 ms where its
 // work is 15 us (every workgroup waits for a place) -- the headline without that launch: +4 %, scripts/ab_flags_experiments.sh -- and
 // the shorter launches of the chain cannot absorb it either (in the pyramid's launch it made THAT link the long one: -2 %).  This is
-// the frame's longest launch, the scan's result is wanted by k_mb, which comes next, and the scan's 136 workgroups per frame are
-// spread through the launch's 12 000 per member.
+// the frame's longest launch, the scan's result is wanted by k_mb, which comes next, and the scan's 136 workgroups per frame ride
+// behind the launch's search workgroups.
 struct S2Scans { rc::ScanCore item[MAX_BATCH]; uint32_t mask; int nbx, wgs; };
 static_assert(sizeof(BatchOf<S2Args>) + sizeof(S2Scans) <= 4096, "the kernel-argument segment");
 // (waves_per_eu: with the scans' body in the same function the register allocator otherwise settles at 76 -- six waves per SIMD; told to, it fits the same code into 70)
@@ -347,11 +406,11 @@ template <bool SPREAD, int ITER>
 __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2_bs(BatchOf<S2Args> b, S2Scans sc) {
     if ((int)blockIdx.x >= sc.nbx) {
         const int wg = (int)blockIdx.x - sc.nbx;
-        if (blockIdx.y == 0 && ((sc.mask >> blockIdx.z) & 1) && wg < sc.wgs) rc::strength_segments_body(b.item[blockIdx.z].cur, sc.item[blockIdx.z], wg, sc.wgs);
+        if (((sc.mask >> blockIdx.z) & 1) && wg < sc.wgs) rc::strength_segments_body(b.item[blockIdx.z].cur, sc.item[blockIdx.z], wg, sc.wgs);
         return;
     }
     launch_clock_begin(b.item[0].clk);
-    search2_groups<SPREAD, ITER>(b.item[blockIdx.z], xcd_band(blockIdx.x, sc.nbx), blockIdx.y);
+    search2_groups<SPREAD, ITER, true>(b.item[blockIdx.z], xcd_band(blockIdx.x, sc.nbx), 0);
     launch_clock_end(b.item[0].clk);
 }
 // Persistent form: a grid no larger than what the part holds at once, every workgroup walking the (context, reference,
@@ -363,7 +422,7 @@ __global__ __launch_bounds__(256, 4) void k_search2_p(BatchOf<S2Args> b, int nbx
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
         const int item = w / (nbx * maxrefs), rem = w - item * (nbx * maxrefs);
         const int ref_idx = rem / nbx, wg_x = rem - ref_idx * nbx;
-        search2_body<false>(b.item[item], wg_x, ref_idx, (int)threadIdx.x);
+        search2_body<false, false>(b.item[item], wg_x, ref_idx, (int)threadIdx.x);
         lds_fence();   // the next round reuses this workgroup's LDS: every read of this round has returned
     }
 }
@@ -396,11 +455,13 @@ static bool search2_spread() {
     static const bool on = [] { const char *v = getenv("VP8HIP_S2_SPREAD"); return !(v && v[0] == '0'); }();
     return on;
 }
-// VP8HIP_S2_ITER=1/2/4: groups of eight blocks a workgroup takes one after the other (same-box A/B runs).  Batches: four.  One video: one --
-// its launch is a few rounds of workgroups long, and workgroups four times as long make its end ragged (53.0 against 54.3 us)
+// VP8HIP_S2_ITER=1/2: groups of eight blocks a workgroup takes one after the other (same-box A/B runs).  Batches: two, each through every
+// enabled reference -- up to six passes of the body per workgroup (four took the registers past seven waves per SIMD, and a workgroup of
+// twelve passes makes the launch's end ragged).  One video: one -- its launch is a few rounds of workgroups long, and longer workgroups make
+// its end ragged (53.0 against 54.3 us)
 static int search2_iter(bool batch) {
-    static const int forced = [] { const char *v = getenv("VP8HIP_S2_ITER"); const int k = v && v[0] ? atoi(v) : 0; return k == 1 || k == 2 || k == 4 ? k : 0; }();
-    return forced ? forced : (batch ? 4 : 1);
+    static const int forced = [] { const char *v = getenv("VP8HIP_S2_ITER"); const int k = v && v[0] ? atoi(v) : 0; return k == 1 || k == 2 ? k : 0; }();
+    return forced ? forced : (batch ? 2 : 1);
 }
 static bool search2_skip() {
     static const bool skip = experiment_skip("s2");
@@ -412,7 +473,6 @@ void launch_search2(hipStream_t s, const Frame &cur, const RefSet &refs, const N
     if (a.nrefs == 0 || search2_skip()) return;
     const int nbx = (a.nblk + 7) / 8;
     if (!search2_spread()) VP8_LAUNCH((k_search2<false, 1>), dim3(nbx, a.nrefs), dim3(256), 0, s, a);
-    else if (search2_iter(false) == 4) VP8_LAUNCH((k_search2<true, 4>), dim3((nbx + 3) / 4, a.nrefs), dim3(256), 0, s, a);
     else if (search2_iter(false) == 2) VP8_LAUNCH((k_search2<true, 2>), dim3((nbx + 1) / 2, a.nrefs), dim3(256), 0, s, a);
     else VP8_LAUNCH((k_search2<true, 1>), dim3(nbx, a.nrefs), dim3(256), 0, s, a);
 }
@@ -445,18 +505,16 @@ bool launch_search2_batch(hipStream_t s, const Frame *const *cur, const RefSet *
     }
     const int iter = search2_spread() ? search2_iter(true) : 1, ngrp = (nbx + iter - 1) / iter;     // workgroups that search: each takes `iter` groups of eight blocks
     if (!sc.mask) {
-        if (!search2_spread()) VP8_LAUNCH((k_search2_b<false, 1>), dim3(nbx, maxrefs, n), dim3(256), 0, s, b);
-        else if (iter == 4) VP8_LAUNCH((k_search2_b<true, 4>), dim3(ngrp, maxrefs, n), dim3(256), 0, s, b);
-        else if (iter == 2) VP8_LAUNCH((k_search2_b<true, 2>), dim3(ngrp, maxrefs, n), dim3(256), 0, s, b);
-        else VP8_LAUNCH((k_search2_b<true, 1>), dim3(nbx, maxrefs, n), dim3(256), 0, s, b);
+        if (!search2_spread()) VP8_LAUNCH((k_search2_b<false, 1>), dim3(nbx, 1, n), dim3(256), 0, s, b);
+        else if (iter == 2) VP8_LAUNCH((k_search2_b<true, 2>), dim3(ngrp, 1, n), dim3(256), 0, s, b);
+        else VP8_LAUNCH((k_search2_b<true, 1>), dim3(nbx, 1, n), dim3(256), 0, s, b);
         return false;
     }
     sc.nbx = ngrp;
     sc.wgs = (b.item[0].h + rc::ROWS_PER_BLOCK - 1) / rc::ROWS_PER_BLOCK;
-    if (!search2_spread()) VP8_LAUNCH((k_search2_bs<false, 1>), dim3(nbx + sc.wgs, maxrefs, n), dim3(256), 0, s, b, sc);
-    else if (iter == 4) VP8_LAUNCH((k_search2_bs<true, 4>), dim3(ngrp + sc.wgs, maxrefs, n), dim3(256), 0, s, b, sc);
-    else if (iter == 2) VP8_LAUNCH((k_search2_bs<true, 2>), dim3(ngrp + sc.wgs, maxrefs, n), dim3(256), 0, s, b, sc);
-    else VP8_LAUNCH((k_search2_bs<true, 1>), dim3(nbx + sc.wgs, maxrefs, n), dim3(256), 0, s, b, sc);
+    if (!search2_spread()) VP8_LAUNCH((k_search2_bs<false, 1>), dim3(nbx + sc.wgs, 1, n), dim3(256), 0, s, b, sc);
+    else if (iter == 2) VP8_LAUNCH((k_search2_bs<true, 2>), dim3(ngrp + sc.wgs, 1, n), dim3(256), 0, s, b, sc);
+    else VP8_LAUNCH((k_search2_bs<true, 1>), dim3(nbx + sc.wgs, 1, n), dim3(256), 0, s, b, sc);
     return true;
 }
 
