@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Compare the instruction streams of kernels in two gfx950 assembly files (hipcc -S --cuda-device-only).
+
+    scripts/asm_kernel_diff.py before.s after.s k_loop_filter3_b [k_other ...]
+    scripts/asm_kernel_diff.py --loop one.s k_loop_filter3_b      # static size of the kernel's largest loop
+
+A kernel is named by a fragment of its symbol that must match exactly one kernel of each file.  Its stream is what lies
+between its entry label and its s_endpgm-terminated end, without comments, directives and blank lines; labels and mangled
+symbols are renamed in order of first appearance, so streams that differ only in names compare equal.  Prints one line per
+kernel (instruction counts, identical or not) and a unified diff of the streams that differ; exit status 1 if any does."""
+import difflib
+import re
+import sys
+
+
+def streams(path):
+    """{kernel symbol: [normalised instruction or label line]}"""
+    text = open(path).read()
+    kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)
+    out = {}
+    for k in kernels:
+        m = re.search(r"^" + re.escape(k) + r":.*?\n(.*?)^\.Lfunc_end\d+:", text, re.M | re.S)
+        names = {}
+
+        def rename(mm, names=names):
+            return names.setdefault(mm.group(0), "L%d" % len(names) if mm.group(0).startswith(".L") else "SYM%d" % len(names))
+
+        lines = []
+        for ln in m.group(1).splitlines():
+            ln = ln.split(";")[0].strip()
+            if not ln or (ln.startswith(".") and not ln.endswith(":")):
+                continue
+            lines.append(re.sub(r"\.LBB\d+_\d+|_Z\w+", rename, " ".join(ln.split())))
+        out[k] = lines
+    return out
+
+
+def pick(ks, frag):
+    hit = [k for k in ks if re.search(re.escape(frag) + r"(?![a-z0-9_])", k)]   # (a mangled name goes on with an upper-case letter)
+    if len(hit) != 1:
+        sys.exit("%r matches %s" % (frag, hit or "nothing"))
+    return hit[0]
+
+
+def instructions(lines):
+    return [ln for ln in lines if not ln.endswith(":")]
+
+
+def largest_loop(lines):
+    """(first, last) line index of the largest span from a label to the last backward branch to it"""
+    at = {ln[:-1]: i for i, ln in enumerate(lines) if ln.endswith(":")}
+    best = (0, 0)
+    for i, ln in enumerate(lines):
+        m = re.match(r"s_c?branch\S*\s+(L\d+)$", ln)
+        if m and at.get(m.group(1), i) < i and i - at[m.group(1)] > best[1] - best[0]:
+            best = (at[m.group(1)], i)
+    return best
+
+
+def main(argv):
+    if argv and argv[0] == "--loop":
+        s = streams(argv[1])
+        for frag in argv[2:]:
+            k = pick(s, frag)
+            a, b = largest_loop(s[k])
+            print("%s: largest loop %d instructions (of %d)" % (k, len(instructions(s[k][a:b + 1])), len(instructions(s[k]))))
+        return 0
+    before, after = streams(argv[0]), streams(argv[1])
+    differ = 0
+    for frag in argv[2:]:
+        kb, ka = pick(before, frag), pick(after, frag)
+        same = before[kb] == after[ka]
+        print("%-28s %5d -> %5d instructions  %s" % (frag, len(instructions(before[kb])), len(instructions(after[ka])), "identical" if same else "DIFFERENT"))
+        if not same:
+            differ = 1
+            sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(before[kb], after[ka], kb, ka, lineterm="", n=2))
+    return differ
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

@@ -30,19 +30,17 @@
 // Every device-side wait is bounded (VP8HIP_ERR_TIMEOUT).
 // History (1080p, one frame): v1 one wave per row through HBM 1.9 ms; v2 banded 0.71 ms; v3 (byte tiles, worker does
 // everything) 0.31 ms; this file: see DESIGN.md section 4.
-#include <stdlib.h>
-#include <string.h>
-
-#include "vp8hip_dev.h"
+#include "lf_shared.h"
 
 namespace vp8 {
 
 namespace lf4 {
 
+using namespace lf;
+
 constexpr int WORKERS = 4;             // worker waves per band (one per SIMD)
 constexpr int ROWS = 2 * WORKERS;      // MB rows per band
 constexpr int RING = 8;                // ring length of the plane in macroblocks (a power of two)
-constexpr int BIAS = 256;
 // the plane: one stride for luma and chroma rows, so that P2's row offsets are the same immediates in every lane
 constexpr int LS = RING * 16 * 4 + 16;         // 528 B: 128 luma samples (or 64 U | 4 pad | 64 V) + padding against bank conflicts
 constexpr int VOFF = RING * 8 * 4 + 16;        // V's samples inside a chroma row
@@ -55,72 +53,7 @@ constexpr int BIG = 0x3fffffff;
 enum { W_PORTER = WORKERS, W_LOADER = 2 * WORKERS, W_PUBLISHER, NWAVES };
 enum { F_FEED = WORKERS, F_TOP = 2 * WORKERS, F_TOPDRAIN, F_PUB, F_ABORT, NFLAGS };   // flag[0..WORKERS-1] = 2*step + phase of each worker; flag[F_FEED + i] = steps porter i has fed
 
-__device__ __forceinline__ int ad(int a, int b) { return (int)__builtin_amdgcn_sad_u16((uint32_t)a, (uint32_t)b, 0u); }
-__device__ __forceinline__ int c128(int v) { return iclamp(v, -128, 127); }
-__device__ __forceinline__ int max3i(int a, int b, int c) { return imax(imax(a, b), c); }
-struct EdgeRegs { int p3, p2, p1, p0, q0, q1, q2, q3; };
-struct Limits { int mb_delta, b_delta, hev_thr; };   // *_delta = interior limit - 2*edge limit - 1, see edge_masks
-
-// 2|p0-q0| + (|p1-q1| >> 1) <= E  <=>  |p1-q1| + 4|p0-q0| <= 2E + 1  <=>  that sum + (I - 2E - 1) <= I, so the
-// edge test joins the six interior tests (each |a-b| <= I) in one max3 and one compare.  edge_delta = I-2E-1.
-// I == -1 switches the edge off: the interior differences are >= 0, so the mask can never be true.
-__device__ __forceinline__ void edge_masks(const EdgeRegs &e, int int_lim, int edge_delta, int hev_thr, bool &mask,
-                                           bool &hev) {
-    const int d10 = ad(e.p1, e.p0), dq10 = ad(e.q1, e.q0);
-    const int m1 = max3i(ad(e.p3, e.p2), ad(e.p2, e.p1), d10);
-    const int m2 = max3i(dq10, ad(e.q2, e.q1), ad(e.q3, e.q2));
-    const int edge = (int)__builtin_amdgcn_sad_u16((uint32_t)e.p1, (uint32_t)e.q1, (uint32_t)((ad(e.p0, e.q0) << 2) + edge_delta));
-    mask = max3i(m1, m2, edge) <= int_lim;
-    hev = imax(d10, dq10) > hev_thr;
-}
-__device__ __forceinline__ void filter_mb_edge(EdgeRegs &e, const Limits &L, int int_lim) {  // :829-883
-    bool mask, hev;
-    edge_masks(e, int_lim, L.mb_delta, L.hev_thr, mask, hev);
-    int w = c128(e.p1 - e.q1);
-    w = c128(w + __mul24(e.q0 - e.p0, 3));   // (|q0 - p0| < 2^11: v_mad_i32_i24, not the 64-bit multiply-add hipcc picks for `* 3`)
-    w = mask ? w : 0;
-    int a = imin(hev ? w : 0, 123);   // min(a + 4, 127) >> 3 and min(a + 3, 127) >> 3 are both 15 from 123 on: one min for the two
-    const int b = (a + 3) >> 3;
-    a = (a + 4) >> 3;
-    e.q0 -= a; e.p0 += b;
-    w = hev ? 0 : w;
-    a = (w * 27 + 63) >> 7; e.q0 -= a; e.p0 += a;
-    a = (w * 18 + 63) >> 7; e.q1 -= a; e.p1 += a;
-    a = (w * 9 + 63) >> 7;  e.q2 -= a; e.p2 += a;
-}
-__device__ __forceinline__ void filter_b_edge(EdgeRegs &e, const Limits &L, int int_lim) {  // :885-926
-    bool mask, hev;
-    edge_masks(e, int_lim, L.b_delta, L.hev_thr, mask, hev);
-    int a = c128(e.p1 - e.q1);
-    a = hev ? a : 0;
-    a = iclamp(a + __mul24(e.q0 - e.p0, 3), -128, 123);   // the clamp to 127 and the two min(.., 127) >> 3 behind it in one (see filter_mb_edge)
-    a = mask ? a : 0;
-    const int b = (a + 3) >> 3;
-    a = (a + 4) >> 3;
-    e.q0 -= a; e.p0 += b;
-    a = (a + 1) >> 1;
-    a = hev ? 0 : a;
-    e.q1 -= a; e.p1 += a;
-}
-
-// One line of biased samples t[0..19] (t[0..3] precede the macroblock edge) through the MB edge and the three
-// inner edges, each under its own interior limit (-1 = edge switched off).  t[] receives the UNSATURATED results (the reference saturates when it
-// stores); the p/q registers handed from edge to edge stay unsaturated too (:1024, :1062).  t[0], t[18], t[19] are never written.
-__device__ __forceinline__ void filter_line(int (&t)[20], const Limits &L, int il_mb, int il4, int il8) {
-    EdgeRegs e;
-    e.p3 = t[0]; e.p2 = t[1]; e.p1 = t[2]; e.p0 = t[3];
-    e.q0 = t[4]; e.q1 = t[5]; e.q2 = t[6]; e.q3 = t[7];
-    filter_mb_edge(e, L, il_mb);
-    t[1] = e.p2; t[2] = e.p1; t[3] = e.p0;
-    t[4] = e.q0; t[5] = e.q1; t[6] = e.q2;
-#pragma unroll
-    for (int k = 4; k < 16; k += 4) {
-        e.p3 = e.q0; e.p2 = e.q1; e.p1 = e.q2; e.p0 = e.q3;
-        e.q0 = t[4 + k]; e.q1 = t[5 + k]; e.q2 = t[6 + k]; e.q3 = t[7 + k];
-        filter_b_edge(e, L, k == 4 ? il4 : il8);
-        t[2 + k] = e.p1; t[3 + k] = e.p0; t[4 + k] = e.q0; t[5 + k] = e.q1;
-    }
-}
+// (the sample helpers, EdgeRegs, Limits and filter_line, the normal filter's line in one piece: lf_shared.h)
 
 // ---- the same line in two parts ------------------------------------------------------------------------------------------
 // A lone wave issues an instruction every 5.3 cycles whether or not it depends on the one before (scripts/ubench/lone_wave.hip),
@@ -228,8 +161,6 @@ __device__ __forceinline__ void line_post(int (&t)[20], const Limits &L, int il_
     t[14] = e.p1; t[15] = e.p0; t[16] = e.q0; t[17] = e.q1;
 }
 
-// biased sample -> biased saturated sample; its low byte is the pixel (BIAS = 256)
-__device__ __forceinline__ int satb(int v) { return iclamp(v, BIAS, BIAS + 255); }
 // four plane dwords (biased saturated samples) -> their four bytes
 __device__ __forceinline__ uint32_t pack4(const int4 &v) {
     const uint32_t lo = __builtin_amdgcn_perm((uint32_t)v.y, (uint32_t)v.x, 0x0c0c0400u);
@@ -273,15 +204,12 @@ typedef int v2i_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) v4i_t lds_int4;
 typedef __attribute__((address_space(3))) v2i_t lds_int2;
 typedef __attribute__((address_space(3))) int lds_int;
-typedef __attribute__((address_space(3))) volatile int lds_flag_t;
 __device__ __forceinline__ int4 ld128(uint32_t a) { const v4i_t v = *(lds_int4 *)(uintptr_t)a; return make_int4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ int2 ld64(uint32_t a) { const v2i_t v = *(lds_int2 *)(uintptr_t)a; return make_int2(v.x, v.y); }
 __device__ __forceinline__ int ld32(uint32_t a) { return *(lds_int *)(uintptr_t)a; }
 __device__ __forceinline__ void st128(uint32_t a, const int4 &v) { *(lds_int4 *)(uintptr_t)a = v4i_t{v.x, v.y, v.z, v.w}; }
 __device__ __forceinline__ void st64(uint32_t a, const int2 &v) { *(lds_int2 *)(uintptr_t)a = v2i_t{v.x, v.y}; }
 __device__ __forceinline__ void st32(uint32_t a, int v) { *(lds_int *)(uintptr_t)a = v; }
-// everything this wave has written to / read from LDS is done, and the compiler moves no memory access across this point
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 struct Args {
     Plane Y, U, V;
@@ -309,87 +237,8 @@ struct Shared {
     int4 lim[4];                                  // per segment: {interior limit, mb_delta, b_delta, hev threshold} (struct Limits)
 };
 
-// Every wait in this kernel is bounded (dispatch order and co-residency of workgroups are not architecturally
-// guaranteed): a wait that is still unsatisfied after SPIN_LIMIT polls (>= 0.3 s; a frame takes < 1 ms) raises the
-// workgroup's abort flag and the error word in HBM, and every wave that sees the flag leaves the kernel.  The
-// frame is then invalid -- reported as VP8HIP_ERR_TIMEOUT -- but nothing hangs.
-constexpr int SPIN_LIMIT = 1 << 22;
-#define LF_WAIT(cond_unsatisfied, nap)                                              \
-    {                                                                               \
-        int spins_ = 0;                                                             \
-        while ((cond_unsatisfied) && !flag[F_ABORT]) {                              \
-            __builtin_amdgcn_s_sleep(nap);                                          \
-            if (++spins_ > SPIN_LIMIT / (nap)) { flag[F_ABORT] = 1; *a.err = 1; }   \
-        }                                                                           \
-        if (flag[F_ABORT]) return;                                                  \
-        asm volatile("" ::: "memory");                                              \
-    }
-
-// The workgroup behind the last band, present when check_SSIM rides in the launch: what check_SSIM reports (vp8enc.cpp:237-258:
-// replaced count, the raster-order float sum / count, the minimum), the updated segment data back to where the entropy stage
-// reads them, and the verdict to the host.  The sum must be the reference's -- one float accumulator over the macroblocks in
-// raster order -- so the values are staged in LDS by all threads (the plane this workgroup has no other use for)
-// and one thread adds them, four per ds_read_b128.
-__device__ __forceinline__ void verdict_workgroup(const Args &a, Shared &sh, bool updated) {   // (inlined: a call would put the argument block into scratch memory)
-    constexpr int NT = NWAVES * 64, CHUNK = 8192;
-    static_assert(sizeof(sh.Y) >= CHUNK * sizeof(float), "staging area");
-    float *s_val = reinterpret_cast<float *>(&sh.Y[0]);
-    const int mbs = a.mbw * a.mbh, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (threadIdx.x == 0) sh.repl = 0;
-    int repl = 0;
-    float mn = 2.0f, sum = 0.0f;
-    for (int base = 0; base < mbs; base += CHUNK) {
-        const int n = imin(CHUNK, mbs - base);
-        __syncthreads();
-        for (int i = threadIdx.x; i < CHUNK; i += NT) {
-            float v = 0.0f;
-            if (i < n) {
-                v = a.o.ssim[base + i];
-                repl += a.chk.is_inter[base + i] == 0;
-                mn = v < mn ? v : mn;
-            }
-            s_val[i] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const float4 *q = reinterpret_cast<const float4 *>(s_val);
-            int i = 0;
-            for (; i + 32 <= n; i += 32) {   // eight reads in flight, then the 32 dependent additions
-                float4 v[8];
-#pragma unroll
-                for (int k2 = 0; k2 < 8; ++k2) v[k2] = q[(i >> 2) + k2];
-#pragma unroll
-                for (int k2 = 0; k2 < 8; ++k2) sum = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(sum, v[k2].x), v[k2].y), v[k2].z), v[k2].w);
-            }
-            for (; i + 4 <= n; i += 4) {
-                const float4 v = q[i >> 2];
-                sum = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(sum, v.x), v.y), v.z), v.w);
-            }
-            for (; i < n; ++i) sum = __fadd_rn(sum, s_val[i]);
-        }
-    }
-    // with no macroblock flagged the fallback left is_inter untouched (stale): nothing was replaced
-    const bool fallback_ran = __builtin_nontemporal_load(a.o.flags) != 0;
-    if (fallback_ran) atomicAdd(&sh.repl, repl);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const float o = __shfl_xor(mn, m, 64); mn = o < mn ? o : mn; }
-    __syncthreads();            // (sh.red was last read before this function)
-    if (lane == 0) sh.red[wave] = mn;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int w = 0; w < NWAVES; ++w) mn = sh.red[w] < mn ? sh.red[w] : mn;
-    if (updated) {
-        for (int i = 0; i < 4 * SD_INTS; ++i) a.sd->v[i] = sh.sd.v[i];
-        a.chk.strength[2] = 7;      // video.loop_filter_sharpness after prepare_segments_data(1, 7)
-    }
-    a.o.flags[0] = 0;               // the fallback has run (the launch before this one): zero at rest
-    const int32_t w[5] = {sh.repl, __float_as_int(__fdiv_rn(sum, (float)mbs)), __float_as_int(mn), *a.err, updated ? 1 : 0};
-    for (int i = 0; i < 5; ++i) {
-        a.chk.stats[i] = w[i];
-        __hip_atomic_store(&a.chk.verdict[i], w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __hip_atomic_store(&a.chk.verdict[5], (int32_t)a.chk.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // the host polls this word
-}
+// the bounded wait of lf_shared.h, with its fence: the plane accesses behind a wait carry no dependence on the flags
+#define LF_WAIT(cond_unsatisfied, nap) LF_BOUNDED_WAIT(cond_unsatisfied, nap, true)
 
 #ifdef LF_STAMPS
 #define STAMP(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
@@ -404,31 +253,12 @@ __device__ __forceinline__ void loop_filter4_body(const Args &a) {
     lds_flag_t *const flag = (lds_flag_t *)sh.flag;
     if (threadIdx.x < 16) flag[threadIdx.x] = 0;
     if (threadIdx.x == 0) sh.first_lf0 = 0x7fffffff;
-    // check_SSIM's tail in this launch (vp8enc.cpp:252-261): `if (min1 > 0.95) prepare_segments_data(1, 7)`.  Every workgroup
-    // takes the frame's minimum SSIM itself (8 160 floats at 1080p: a few microseconds) and, above 0.95, filters with the
-    // segment data that call produces -- nobody waits for a kernel that would have done it.
     const int32_t *sdv = a.sd->v;
     if (a.chk.on) {
-        float mn = 2.0f;
-        const int mbs_all = a.mbw * a.mbh;
-        for (int i = threadIdx.x; i < mbs_all; i += NWAVES * 64) { const float v = a.o.ssim[i]; mn = v < mn ? v : mn; }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { const float o = __shfl_xor(mn, m, 64); mn = o < mn ? o : mn; }
-        if (lane == 0) sh.red[wave] = mn;
-        __syncthreads();
-        mn = sh.red[0];
-#pragma unroll
-        for (int w = 1; w < NWAVES; ++w) mn = sh.red[w] < mn ? sh.red[w] : mn;
-        if (mn > 0.95f) {   // (the reference compares with the double 0.95: no float lies between 0.95f and 0.95)
-            if (threadIdx.x == 0) {
-                const int refqi[4] = {a.chk.refqi[0], a.chk.refqi[1], a.chk.refqi[2], a.chk.refqi[3]};
-                fill_segment_data(&sh.sd, 0, refqi, a.chk.qi_min, a.chk.strength[0], a.chk.strength[1], true);
-            }
-            sdv = sh.sd.v;
-            __syncthreads();
-        }
-        if (band >= a.nbands) {
-            verdict_workgroup(a, sh, sdv != a.sd->v);
+        sdv = check_ssim_segments<NWAVES>(a, sh, wave);
+        if (band >= a.nbands) {   // the workgroup behind the last band: the luma plane is its staging area
+            static_assert(sizeof(sh.Y) >= VERDICT_CHUNK * sizeof(float), "staging area");
+            verdict_workgroup<NWAVES>(a, sh, sdv != a.sd->v, reinterpret_cast<float *>(&sh.Y[0]));
             return;
         }
     } else if (band >= a.nbands) {
@@ -440,10 +270,8 @@ __device__ __forceinline__ void loop_filter4_body(const Args &a) {
         sh.lim[threadIdx.x] = make_int4(il, il - (sd[SD_MBEDGE_LIMIT] & 0xff) * 2 - 1, il - (sd[SD_SUB_BEDGE_LIMIT] & 0xff) * 2 - 1,
                                         sd[SD_HEV_THRESHOLD] & 0xff);
     }
-    // The kernel's own clock (constant 100 MHz): band 0 stamps the start, the drainer of the last band adds end - start to an
-    // accumulator the host reads with the profile (vp8hip_profile_read_clock).
-    // hipEvents around a launch also count the time its packet waits for the queue when many streams share the part.
-    unsigned long long *clk = reinterpret_cast<unsigned long long *>(a.err + 4);   // {start, sum of ticks, launches, sum of shader-clock cycles per tick x 1000, launches left out of that sum, launches whose last wave changed slots}
+    // The launch clock (lf_shared.h): band 0 stamps the start, the drainer of the last band the end.
+    unsigned long long *clk = reinterpret_cast<unsigned long long *>(a.err + 4);
     // (the start is SUBTRACTED from the sum of ticks here and the end added by the frame's last wave: no wave has to read the start back.
     // The word is meaningful when no launch is in flight, which is when the host reads it.)
     if (band == 0 && threadIdx.x == 0) {
@@ -454,7 +282,7 @@ __device__ __forceinline__ void loop_filter4_body(const Args &a) {
 #endif
     }
     const unsigned long long cyc0 = __builtin_amdgcn_s_memtime(), tick0 = __builtin_amdgcn_s_memrealtime();
-    const uint32_t hwid0 = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID
+    const uint32_t hwid0 = hw_slot();
     __syncthreads();
     const int mbw = a.mbw, mbh = a.mbh;
     const int band_row0 = band * ROWS;
@@ -613,11 +441,7 @@ __device__ __forceinline__ void loop_filter4_body(const Args &a) {
             // the shader clock this wave saw while it ran: s_memtime cycles per 100 MHz tick (MI355X_MICROARCH.md, DVFS (6)), x 1000
             const float cyc_f = (float)(__builtin_amdgcn_s_memtime() - cyc0), tick_f = (float)(t1 - tick0 + 1);
             const unsigned long long ratio = (unsigned long long)(cyc_f * 1000.0f / tick_f);
-            const uint32_t hwid1 = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
-            // a wave that was context-switched (the hardware scheduler rotating an oversubscribed set of queues) comes back on
-            // another slot, whose cycle counter is another one: such launches are counted, not averaged
-            if (ratio > 100000ull) atomicAdd(clk + 4, 1ull); else atomicAdd(clk + 3, ratio);
-            if (hwid1 != hwid0) atomicAdd(clk + 5, 1ull);
+            LF_CLOCK_RATIO(clk, ratio, hwid0)
         }
         return;
     }
@@ -891,12 +715,8 @@ static lf4::Args loop_filter4_args(hipStream_t s, const Frame &recon, const MBOu
     a.mbw = mbw;
     a.mbh = mbh;
     a.nbands = (mbh + lf4::ROWS - 1) / lf4::ROWS;
-    // the hand-off tags are never reset: every launch tags inside its own window (wraps after ~2^31/(mbw+2)
-    // launches; the host zeroes the buffer when the window index wraps)
-    const unsigned window = 0x7fffffffu / (unsigned)(mbw + 2) - 1;
-    const unsigned n = launch_no % window;
-    if (n == 0) (void)hipMemsetAsync(handoff, 0, loop_filter4_handoff_bytes(mbw, mbh), s);
-    a.gbase = (int)(n * (unsigned)(mbw + 2));
+    a.gbase = lf_window_base(launch_no, mbw);   // (the tags of the hand-off buffer count in the launch's window)
+    if (a.gbase == 0) (void)hipMemsetAsync(handoff, 0, loop_filter4_handoff_bytes(mbw, mbh), s);
     a.err = progress + LF_ERR_WORD;
     a.stall_test = stall_test;
     return a;

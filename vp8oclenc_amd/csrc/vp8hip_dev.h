@@ -179,16 +179,14 @@ void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out
 void launch_mb(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, const Frame &recon,
                const MBOut &o, const SegData *d_sd, float ssim_target, int mbw, int mbh, bool conformant = false);
 void launch_filter_mask(hipStream_t s, const MBOut &o, const SegData *d_sd, int mbs);
-// The loop filter exists in two forms with the same results.  Form 3: byte tiles and strips in 46 KB of LDS,
-// the worker wave does everything itself -- what batches of GOP chunks launch (with the part full what counts is the
+// The loop filter exists in two forms with the same results.  Form 3 (lf_banded.h): byte tiles and strips in 46 KB
+// of LDS, the worker wave does everything itself -- what batches of GOP chunks launch, and only they (with the part full what counts is the
 // instructions and the LDS a launch takes from the other kernels, not its latency).  Form 4: a band-tall plane of dwords in
 // 112 KB of LDS, the workers only filter, porter waves feed and drain -- the short dependency chain of ONE video.
-void launch_loop_filter3(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress,
-                         int mbw, int mbh, unsigned launch_no, int stall_test = 0, const LfCheck *chk = nullptr);
 void launch_loop_filter4(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, void *handoff,
                          int mbw, int mbh, unsigned launch_no, int stall_test = 0, const LfCheck *chk = nullptr);
 size_t loop_filter4_handoff_bytes(int mbw, int mbh);   // the HBM buffer form 4 hands a band's bottom rows to the next band through
-// The simple loop filter (frame header filter_type 1, kernels_lf_simple.hip): luma only, form 3's data movement.  launch_no counts
+// The simple loop filter (frame header filter_type 1, kernels_lf_simple.hip): luma only, form 3's data movement (lf_banded.h).  launch_no counts
 // the context's simple-filter launches only (its band counters are its own, at LF_SIMPLE_WORD of the progress buffer).
 void launch_loop_filter_simple(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, int mbw, int mbh,
                                unsigned launch_no, const LfCheck *chk = nullptr);
