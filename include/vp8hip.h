@@ -202,6 +202,32 @@ int vp8hip_set_source_size(vp8hip_ctx *ctx, int src_width, int src_height);
  * under them): not a per-frame call.  Reference planes (vp8hip_upload_last, vp8hip_set_last_device, downloads) keep the coded size.
  * No upscaling: a decoder does that from the key frame header's scale bits.  All members of a batch must agree on all five values. */
 int vp8hip_set_source_scaling(vp8hip_ctx *ctx, int in_width, int in_height, int dst_width, int dst_height, int filter);
+/* Temporal noise reduction of the source frames, the third stage of the input side (libvpx: --noise-sensitivity); the reference never
+ * did anything about noise.  level 1, 2, 3: every frame that becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the
+ * pack out of a vp8hip_prefetch_current staging buffer, vp8hip_batch_set_current_device, vp8hip_batch_upload_current, with or without a
+ * source size or scaling -- passes through ONE more launch (k_denoise_b) right behind its pack or scale launch, on the same stream,
+ * before anything else reads it: pyramid, edge replication, chroma scan, vp8hip_auto_segments, the searches, the quality statistics.
+ * The launch works on whole coded macroblocks of the padded frame against the context's HISTORY, the previous frame taken in as it
+ * left the denoiser; the rule -- per-sample steps towards the history, a per-macroblock decision that leaves moving blocks alone -- is
+ * stated bit for bit in include/vp8hip_host.h (vp8host_denoise_frame).  Without a history (the first frame, after
+ * vp8hip_denoise_restart, after the level changed) the frame passes through unchanged and becomes the history.  Once per frame TAKEN
+ * IN: a frame coded a second time (check_SSIM's verdict) is the same current frame and is not denoised again.  The quality statistics
+ * measure against the frame that was CODED, the denoised one, as they do with scaling: their PSNR is the codec's.
+ * level 0 (default): off -- no launch, no byte and no number changes.  Any other value: VP8HIP_ERR_ARG and nothing has changed.
+ * Turning it on or changing the level restarts the history.  Waits for the context's streams: not a per-frame call.  All members of a
+ * batch must agree on the level (vp8hip_batch_create and the batched launch check it).  Shard and group contexts: not supported. */
+int vp8hip_set_denoise(vp8hip_ctx *ctx, int level);
+/* The next frame taken in passes through unchanged and becomes the history (a host calls it where its stream restarts: a key frame of
+ * the GOP schedule, so that a closed GOP coded on its own sees the frames the serial program sees). */
+int vp8hip_denoise_restart(vp8hip_ctx *ctx);
+typedef struct {
+    int32_t frame_number;    /* 0-based index of the frame taken in, as in vp8hip_quality */
+    int32_t mbs_filtered;    /* macroblocks whose luma was filtered (0 for a frame that passed through) */
+    int32_t mbs_total;
+} vp8hip_denoise_stats;
+/* The record of the last frame taken in.  Waits for that launch's last word only, as vp8hip_quality_result does.
+ * VP8HIP_ERR_STATE: denoising off, or no frame taken in since it was turned on. */
+int vp8hip_denoise_result(vp8hip_ctx *ctx, vp8hip_denoise_stats *s);
 
 /* prepare_filter_mask_and_non_zero_coeffs(), loop_filter.h:25-55.  nz_out: [MBs] or NULL.
  * (vp8hip_inter_transform already produced mask and counts for its own coefficients; this call
@@ -379,7 +405,9 @@ const char *vp8hip_status_string(int status);
  * vp8drv_frame_check folds position in (4: its values change); 4009: vp8hip_set_loop_filter_type and vp8drv_config.loop_filter_type;
  * 4010: quality statistics (vp8hip_set_quality_stats, vp8hip_batch_quality, vp8drv_config.quality_stats, vp8drv_get_frame_quality);
  * also under 4010: vp8hip_set_source_scaling, vp8host_scale_taps and vp8drv_config.in_width / in_height / scale_filter, in front of
- * quality_stats, which stays the last field (a host fills the struct with vp8drv_default_config, which zeroes them: no scaling). */
+ * quality_stats, which stays the last field (a host fills the struct with vp8drv_default_config, which zeroes them: no scaling);
+ * also under 4010: vp8hip_set_denoise, vp8hip_denoise_restart, vp8hip_denoise_result, vp8host_denoise_frame, vp8drv_set_denoise and
+ * vp8drv_get_denoise_stats (entry points only: vp8drv_config is unchanged). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

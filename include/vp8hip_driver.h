@@ -216,6 +216,18 @@ typedef vp8hip_quality vp8drv_quality;
 typedef vp8hip_quality_totals vp8drv_quality_summary;
 int vp8drv_get_frame_quality(vp8drv *d, vp8drv_quality *q);
 int vp8drv_get_quality_summary(vp8drv *d, vp8drv_quality_summary *s);
+/* Temporal noise reduction of the source frames (vp8hip_set_denoise; the rule: include/vp8hip_host.h), an entry point and not a field
+ * because vp8drv_config keeps its size.  Call it after vp8drv_create; level 0-3, 0 (default) = off.  It takes the open check_SSIM
+ * verdict first.  VP8HIP_ERR_ARG: a bad level, or device_params = 0 (the host parameter mirror would scan the caller's luma, which
+ * is not the frame that is coded); VP8HIP_ERR_STATE: the driver is a member of a live batch (members must agree: set the level before
+ * vp8drv_batch_create, which refuses members that disagree).
+ * The history restarts when the GOP schedule makes the incoming frame a key frame (gop.current_is_key at the moment the frame is taken
+ * in, through vp8drv_encode_frame_device / _host, vp8drv_stage_frame_host, a prefetched frame, the batched calls), so a closed GOP coded
+ * as a chunk of its own sees the frames the serial program sees.  force_key, scene cuts and frames sent back by check_SSIM do not restart
+ * it -- the block decision rejects a cut by itself -- and a frame coded again as a key frame is not denoised twice. */
+int vp8drv_set_denoise(vp8drv *d, int level);
+/* the record of the last frame taken in (vp8hip_denoise_result); VP8HIP_ERR_STATE when denoising is off or no frame was taken in */
+int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,32 @@ int vp8host_y4m_frame_marker_ok(const uint8_t marker[6]);
 #define VP8HOST_SCALE_MAX_TAPS 32
 int vp8host_scale_taps(int n_in, int n_out, int kind, int32_t *n_taps, int32_t *start /* [n_out] */, int16_t *coef /* [n_out * 32] */);
 
+/* The rule of the device's temporal denoiser (vp8hip_set_denoise, include/vp8hip.h; k_denoise_b), bit for bit.  The project's own: the
+ * reference never did anything about noise.
+ * History and pass-through.  A context with denoising on keeps a history: the previous frame as it left the denoiser, Y, U and V at
+ * the coded size, padding included.  The denoiser works on the frame after pack / pad / scale, on whole coded macroblocks, before
+ * anything else reads the frame.  Without a history (first frame, after a restart, after the level changed) the frame passes through
+ * unchanged and becomes the history.
+ * Per sample, with k = level (1, 2, 3), source S and history R: d = R - S, a = |d|, and the step c is
+ *     a <= 2 + k: c = d (the output is R);   else a <= 7: c = sign(d) (2 + k);   else a <= 15: c = sign(d) (3 + k);
+ *     else: c = sign(d) (5 + k).
+ * With k = 1 these are libvpx's VP8 denoiser steps, 3 / 4 / 6 above a threshold of 3.  |c| <= a and c has d's sign, so S + c lies
+ * between S and R and needs no clamp.
+ * Per 16x16 luma macroblock: T = sum of c over its 256 samples, sad = sum of a.  The macroblock is FILTERED iff
+ * |T| <= VP8HOST_DENOISE_SUM_Y (16 * 16 * 2, libvpx's) and sad <= VP8HOST_DENOISE_SAD_Y; otherwise it is COPIED: output = source.
+ * The two 8x8 chroma blocks of a filtered macroblock are filtered by the same per-sample rule, each on its own and only if its
+ * |T_c| <= VP8HOST_DENOISE_SUM_C; a copied macroblock's chroma blocks are copied.  Output of a filtered block = S + c.  The whole
+ * output frame is the new history.
+ * vp8host_denoise_frame: the rule on tight planes of the coded size (width, height multiples of 16; chroma width / 2 x height / 2).
+ * have_history 0 or level 0: out = src, *mbs_filtered = 0.  With level != 0 the history planes are replaced by the output (in-out);
+ * with level 0 they are left alone.  out may be src or the history itself.  Returns 0, or -1 for bad arguments. */
+#define VP8HOST_DENOISE_SUM_Y 512
+#define VP8HOST_DENOISE_SAD_Y 2560
+#define VP8HOST_DENOISE_SUM_C 128
+int vp8host_denoise_frame(const uint8_t *src_y, const uint8_t *src_u, const uint8_t *src_v, uint8_t *hist_y, uint8_t *hist_u, uint8_t *hist_v,
+                          uint8_t *out_y, uint8_t *out_u, uint8_t *out_v, int width, int height, int level, int have_history,
+                          int32_t *mbs_filtered);
+
 /* frames.skip_prob, loop_filter.h:37-44 */
 int vp8host_skip_prob(const int32_t *MB_non_zero_coeffs, int mb_count);
 

@@ -42,6 +42,7 @@ def main():
     ap.add_argument("--conformant", action="store_true", help="vp8hip_conformant_stream: NOT the reference byte for byte, but a stream that decodes to the encoder's own reconstruction")
     ap.add_argument("--resize", default="", metavar="WxH", help="code the picture at this size: the frames are scaled down on the device (vp8hip_set_source_scaling)")
     ap.add_argument("--resize-filter", choices=("area", "lanczos"), default="area")
+    ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dist = None
@@ -61,11 +62,14 @@ def main():
     if (Wd, Hd) != (seq.W, seq.H):
         src.update(in_width=seq.W, in_height=seq.H, scale_filter=int(a.resize_filter == "lanczos"))
     t0 = time.perf_counter()
-    mine = gop_shard.encode_chunks_frames(
-        lambda: gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
-                                        ssim_target=a.ssim_target, check_ssim=1, conformant_stream=int(a.conformant),
-                                        loop_filter_type=int(a.simple_filter)),
-        seq, gop_shard.chunks_of_rank(frames, a.gop, rank, world))
+    def make_encoder():
+        enc = gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
+                                      ssim_target=a.ssim_target, check_ssim=1, conformant_stream=int(a.conformant),
+                                      loop_filter_type=int(a.simple_filter))
+        if a.denoise:
+            enc.drv.set_denoise(a.denoise)
+        return enc
+    mine = gop_shard.encode_chunks_frames(make_encoder, seq, gop_shard.chunks_of_rank(frames, a.gop, rank, world))
     allf = gop_shard.gather_frames(mine, frames, dist)
     if rank == 0:
         n = gop_shard.write_ivf(a.out, allf, Wd, Hd, a.framerate)

@@ -20,6 +20,7 @@ ap.add_argument("--loop-filter-type", type=int, choices=(0, 1), default=0, help=
 ap.add_argument("--quality-stats", type=int, choices=(0, 1), default=0, help="1 = PSNR / SSIM of every frame on the device (vp8drv_config.quality_stats): what it costs")
 ap.add_argument("--scale-from", default="", metavar="WxH", help="the frames come in at this size and are scaled down to --width x --height on the device (vp8drv_config.in_width / in_height)")
 ap.add_argument("--scale-filter", choices=("area", "lanczos"), default="area")
+ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of every frame taken in (vp8drv_set_denoise): what k_denoise_b costs")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -43,6 +44,9 @@ else:
 api.device_synchronize()
 drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
                          loop_filter_type=a.loop_filter_type, quality_stats=a.quality_stats, **scale) for _ in range(a.streams)]
+if a.denoise:
+    for d in drvs:
+        d.set_denoise(a.denoise)
 sizes = [0] * a.streams
 
 def work(k, n, emit):

@@ -1,7 +1,9 @@
 // y4m_to_ivf.cpp -- the reference's program with the path swapped in, as a complete C++ user of the C ABI: YUV4MPEG2 in,
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
-//              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos]
+//              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
+// -denoise N: temporal noise reduction of the source frames on the device, N = 1, 2, 3 (vp8drv_set_denoise; 0 = off); the share of
+// macroblocks it filtered is printed at the end, next to -psnr's summary.
 // -resize: the Y4M header gives the size of the frames that come in, WxH (even, not above it) the picture that is coded: the frames are
 // scaled down on the device (cfg.in_width / in_height, vp8hip_set_source_scaling); IVF header and key frames carry WxH.
 // As in the reference, check_SSIM runs after every inter frame and scene_change() looks at every frame that would be an inter frame.
@@ -29,6 +31,7 @@ int main(int argc, char **argv) {
     cfg.scene_detect = 1;                       // main() calls scene_change() for every would-be inter frame (vp8enc.cpp:408)
     cfg.overlap_filter = 1;
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
+    int denoise = 0;         // -denoise
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -43,6 +46,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-conformant")) cfg.conformant_stream = 1;
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-psnr")) cfg.quality_stats = 1;               // PSNR / SSIM summary on stderr
+        else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -72,6 +76,8 @@ int main(int argc, char **argv) {
     if (Wd != W || Hd != H) { cfg.in_width = W; cfg.in_height = H; }
     vp8drv *drv = nullptr;
     CK(vp8drv_create(&drv, Wc, Hc, 0, &cfg));
+    if (denoise) CK(vp8drv_set_denoise(drv, denoise));
+    long long dn_filtered = 0, dn_total = 0;
     FILE *out = fopen(argv[2], "wb");
     if (!out) { perror(argv[2]); return 1; }
     uint8_t fh[32];
@@ -157,6 +163,12 @@ int main(int argc, char **argv) {
             }
             cv.notify_all();
             CK(vp8drv_encode_frame_host(drv, p[0], p[1], p[2], 0));      // (uploads nothing if the frame was handed over early)
+            if (denoise) {      // the record of the frame just taken in (its launch ended long ago)
+                vp8hip_denoise_stats ds;
+                CK(vp8drv_get_denoise_stats(drv, &ds));
+                dn_filtered += ds.mbs_filtered;
+                dn_total += ds.mbs_total;
+            }
             CK(prefetch_next());
         }
         if (pending) {      // the previous frame's bytes
@@ -199,6 +211,9 @@ int main(int argc, char **argv) {
                 q.psnr_all, q.psnr_avg, q.psnr[0], q.psnr[1], q.psnr[2], q.ssim_all, q.ssim[0], (long long)q.psnr_min_frame, q.psnr_min,
                 (long long)q.frames);
     }
+    if (denoise)
+        fprintf(stderr, "Denoiser level %d: %lld of %lld macroblocks filtered (%.1f %%)\n", denoise, dn_filtered, dn_total,
+                dn_total ? 100.0 * (double)dn_filtered / (double)dn_total : 0.0);
     vp8drv_destroy(drv);
     for (int k = 0; k < RING; ++k) vp8hip_host_free(0, buf[k]);
     printf("%s: %u frames %dx%d (coded %dx%d), %u key (%d by scene change, %d recoded), %zu bytes; %d hardware queues\n", argv[2], n, W, H, Wc, Hc, keys,

@@ -1,7 +1,8 @@
 // y4m_to_ivf_gops.cpp -- one YUV4MPEG2 file to one IVF file with its closed GOPs coded SIDE BY SIDE: the file-to-file form of what
 // bench.py's headline measures, as a complete C++ user of the C ABI.
 //   y4m_to_ivf_gops <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n]
-//                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos]
+//                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
+// (-denoise N: as in y4m_to_ivf.cpp -- the history restarts at every GOP's key frame, so a chunk sees the frames the serial program sees)
 // (-resize: as in y4m_to_ivf.cpp -- frames of the file's size in, scaled down to WxH on the device, one launch per batch step)
 // A key frame resets every reference (intra_part.h:1091-1098, inter_part.h:35-50), so the frames [k g, (k + 1) g) of a run with
 // `-g g` are a unit of their own: N such chunks are in flight at once, B of them advance together as one batch (every stage ONE
@@ -38,6 +39,7 @@ int main(int argc, char **argv) {
     vp8drv_default_config(&cfg);
     int in_flight = 48, batch = 6;
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
+    int denoise = 0;         // -denoise
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -51,6 +53,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-chunks")) in_flight = atoi(val());
         else if (!strcmp(argv[i], "-batch")) batch = atoi(val());
+        else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -102,6 +105,7 @@ int main(int argc, char **argv) {
     std::vector<vp8drv_batch *> bat((size_t)nbatches, nullptr);
     for (int j = 0; j < in_flight; ++j) {
         CK(vp8drv_create(&drv[j], Wc, Hc, 0, &cfg));
+        if (denoise) CK(vp8drv_set_denoise(drv[j], denoise));      // (before the batch is made: its members must agree)
         CK(vp8hip_reserve_frame_path_dense(vp8drv_context(drv[j])));      // frame t + 1 is started before frame t's bytes are taken: no frame is ever coded twice
         if ((j + 1) % batch == 0 || j == in_flight - 1) {
             const int k = j / batch, j0 = k * batch;

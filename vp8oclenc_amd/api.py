@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -479,6 +479,34 @@ class QualitySummary(C.Structure):
                 ("psnr_min", C.c_double), ("psnr_min_frame", C.c_int64)]
 
 
+class DenoiseStats(C.Structure):
+    """vp8hip_denoise_stats, include/vp8hip.h: the last frame taken in by a context with vp8hip_set_denoise"""
+    _fields_ = [("frame_number", C.c_int32), ("mbs_filtered", C.c_int32), ("mbs_total", C.c_int32)]
+
+
+DENOISE_SUM_Y, DENOISE_SAD_Y, DENOISE_SUM_C = 512, 2560, 128   # VP8HOST_DENOISE_*, include/vp8hip_host.h
+
+
+def denoise_frame(src, hist, level: int, have_history: bool):
+    """vp8host_denoise_frame: the device's denoiser in plain C++ on tight planes of the coded size.  src = (Y, U, V); hist = (Y, U, V)
+    arrays that are updated in place when level != 0 (or None with level 0) -> ((Y, U, V) out, macroblocks filtered)"""
+    lib = load_library()
+    lib.vp8host_denoise_frame.argtypes = [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    src = [np.ascontiguousarray(p, np.uint8) for p in src]
+    h, w = src[0].shape
+    out = [np.empty_like(p) for p in src]
+    if hist is not None:
+        for a, b in zip(hist, src):
+            if a.dtype != np.uint8 or not a.flags["C_CONTIGUOUS"] or a.shape != b.shape:
+                raise ValueError("denoise_frame: the history planes are contiguous uint8 arrays of the source planes' shapes")
+    hp = [a.ctypes.data for a in hist] if hist is not None else [None] * 3
+    n = C.c_int32(0)
+    if lib.vp8host_denoise_frame(*[p.ctypes.data for p in src], *hp, *[p.ctypes.data for p in out], w, h, int(level), int(bool(have_history)),
+                                 C.byref(n)) != 0:
+        raise ValueError(f"vp8host_denoise_frame({w}x{h}, level {level}) refused")
+    return out, n.value
+
+
 class NativeDriver:
     """The reference's frame loop as native host code (vp8_driver.cpp, include/vp8hip_driver.h): one call per
     frame.  `.hip` is a view of its context for downloads and taps."""
@@ -637,6 +665,23 @@ class NativeDriver:
         if rc != 0:
             raise Vp8HipError(f"vp8drv_get_frame_quality: {self.lib.vp8hip_status_string(rc).decode()} ({rc})")
         return q
+
+    def set_denoise(self, level: int) -> None:
+        """vp8drv_set_denoise: temporal noise reduction of the source frames, level 0 (off) to 3; the history restarts at the GOP
+        schedule's key frames"""
+        self.lib.vp8drv_set_denoise.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.vp8drv_set_denoise(self.h, int(level))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_denoise({level}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def denoise_stats(self) -> DenoiseStats:
+        """vp8drv_get_denoise_stats: the last frame taken in"""
+        s = DenoiseStats()
+        self.lib.vp8drv_get_denoise_stats.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
+        rc = self.lib.vp8drv_get_denoise_stats(self.h, C.byref(s))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_denoise_stats: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return s
 
     def quality_summary(self) -> QualitySummary:
         """vp8drv_get_quality_summary: over every frame made final so far"""
@@ -956,6 +1001,23 @@ class Vp8Hip:
         self._chk(self.lib.vp8hip_set_source_scaling(self.h, int(in_width), int(in_height), int(dst_width), int(dst_height), int(filter)),
                   "set_source_scaling")
         self.src = (int(in_width), int(in_height))
+
+    def set_denoise(self, level: int):
+        """vp8hip_set_denoise: every frame that becomes current passes through the temporal denoiser (level 1-3; 0 = off); turning it
+        on or changing the level restarts the history"""
+        self.lib.vp8hip_set_denoise.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.vp8hip_set_denoise(self.h, int(level)), "set_denoise")
+
+    def denoise_restart(self):
+        """vp8hip_denoise_restart: the next frame taken in passes through and becomes the history"""
+        self.lib.vp8hip_denoise_restart.argtypes = [C.c_void_p]
+        self._chk(self.lib.vp8hip_denoise_restart(self.h), "denoise_restart")
+
+    def denoise_result(self) -> "DenoiseStats":
+        s = DenoiseStats()
+        self.lib.vp8hip_denoise_result.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
+        self._chk(self.lib.vp8hip_denoise_result(self.h, C.byref(s)), "denoise_result")
+        return s
 
     def set_quality_stats(self, on: bool = True):
         """vp8hip_set_quality_stats: PSNR / SSIM of every filtered frame against its source, on the device (on from off: a new summary)"""

@@ -262,6 +262,15 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         if (c0->scale.in_w) launch_scale_batch(ps, f, py, pu, pv, plans, n);      // a frame that is scaled is not packed as well
         else launch_pack_batch(ps, f, py, pu, pv, n, c0->src_w, c0->src_h);
     }
+    {   // vp8hip_set_denoise: the members that have a history, in one launch behind the pack (the others' frames pass through)
+        DenoiseItem dn[MAX_BATCH];
+        int nd = 0;
+        for (int i = 0; i < b->n; ++i) {
+            if (active && !active[i]) continue;
+            if (denoise_item(b->c[i], ps, dn[nd])) ++nd;
+        }
+        launch_denoise_batch(ps, dn, nd, c0->dn_level);
+    }
     HIPCHK(c0, hipGetLastError());
     if (host) {
         HIPCHK(c0, hipEventRecord(b->ev_packed[slot], ps));

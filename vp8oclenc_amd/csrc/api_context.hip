@@ -469,6 +469,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     hipFree(c->d_frame);
     if (c->h_verdict) hipHostFree(c->h_verdict);
     if (c->h_quality) hipHostFree(c->h_quality);
+    if (c->h_dn) hipHostFree(c->h_dn);
+    hipFree(c->d_dn);
     hipFree(c->d_quality);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
@@ -535,6 +537,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
         const int rc = set_frame_planes(c, c->cur, d, d + ny, d + ny + nc, hipMemcpyDeviceToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->ev_stage_read[slot], c->stream));
+        denoise_current(c);
         c->stage_read_valid[slot] = true;
         HIPCHK(c, hipEventSynchronize(c->ev_h2d));      // the host's planes are the host's again when this returns (done long ago, normally)
         return VP8HIP_OK;
@@ -543,6 +546,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
     next_current(c);
     int rc = set_frame_planes(c, c->cur, y, u, v, hipMemcpyHostToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
     if (rc) return rc;
+    denoise_current(c);
     // pageable host memory: the call must not return while the copy still reads the host buffer
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VP8HIP_OK;
@@ -552,7 +556,10 @@ int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const
     USE_DEVICE(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
     next_current(c);
-    return set_frame_planes(c, c->cur, y, u, v, hipMemcpyDeviceToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
+    const int rc = set_frame_planes(c, c->cur, y, u, v, hipMemcpyDeviceToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
+    if (rc) return rc;
+    denoise_current(c);      // (vp8hip_set_denoise: right behind the pack, before anything else reads the frame)
+    return VP8HIP_OK;
 }
 
 // dst of a scaler, or the source size: even, not above the coded size and fewer than 16 below it

@@ -29,6 +29,8 @@ struct vp8drv {
     bool verdict_pending = false;    // check_SSIM's verdict on the frame just coded is still on its way (resolve())
     const uint8_t *staged = nullptr; // vp8drv_stage_frame_host: these planes are the context's current frame already (and, with scene_detect, their scan is under way)
     bool staged_scan = false;
+    int denoise = 0;                 // vp8drv_set_denoise: the level in force
+    bool in_batch = false;           // a member of a live vp8drv_batch
     // read-back buffers of vp8drv_get_frame
     std::vector<int32_t> seg, nz, ref, parts, is_inter, modes;
     std::vector<int16_t> vectors;
@@ -295,6 +297,14 @@ vp8hip_header_params header_params(const vp8drv *d) {
     return hp;
 }
 
+// vp8drv_set_denoise: the history restarts where the GOP schedule starts a GOP -- the frame about to be taken in is a scheduled key
+// frame -- so that a closed GOP coded as a chunk of its own sees the frames the serial program sees.  force_key, scene cuts and
+// frames sent back by check_SSIM are not the schedule's.
+int denoise_intake(vp8drv *d, bool scheduled_key) {
+    if (d->denoise && scheduled_key) return vp8hip_denoise_restart(d->hip);
+    return VP8HIP_OK;
+}
+
 int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     const int P = d->cfg.num_partitions;
     const size_t n = (size_t)d->mbs;
@@ -375,6 +385,7 @@ int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const vo
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
     { const int rc = resolve(d); if (rc < 0) return rc; }                        // the previous frame's check_SSIM verdict, if still open
     vp8host_gop_next(&d->gop);
+    DRV_CHK(denoise_intake(d, d->gop.current_is_key != 0));
     DRV_CHK(vp8hip_set_current_device(d->hip, y, u, v));                          // vp8enc.cpp:386-388
     return frame_body(d, nullptr, d->gop.current_is_key || force_key);
 }
@@ -387,6 +398,7 @@ int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, cons
     d->staged = nullptr;
     if (!staged) {
         d->staged_scan = false;
+        DRV_CHK(denoise_intake(d, d->gop.current_is_key != 0));      // (a prefetched frame is packed, and denoised, in this upload)
         DRV_CHK(vp8hip_upload_current(d->hip, y, u, v));
     }
     return frame_body(d, y, d->gop.current_is_key || force_key);
@@ -401,6 +413,11 @@ int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, cons
 int vp8drv_stage_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
     { const int rc = resolve(d); if (rc < 0) return rc; }
+    if (d->denoise) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
+        vp8host_gop g = d->gop;
+        vp8host_gop_next(&g);
+        DRV_CHK(denoise_intake(d, g.current_is_key != 0));
+    }
     DRV_CHK(vp8hip_upload_current(d->hip, y, u, v));
     d->staged = y;
     d->staged_scan = false;
@@ -434,7 +451,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
-            (a.in_width && a.scale_filter != z.scale_filter))
+            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise)
             return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
     }
@@ -446,13 +463,17 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         return rc;
     }
     b->n = n;
-    for (int i = 0; i < n; ++i) b->d[i] = drv[i];
+    for (int i = 0; i < n; ++i) {
+        b->d[i] = drv[i];
+        drv[i]->in_batch = true;
+    }
     *out = b;
     return VP8HIP_OK;
 }
 
 void vp8drv_batch_destroy(vp8drv_batch *b) {
     if (!b) return;
+    for (int i = 0; i < b->n; ++i) b->d[i]->in_batch = false;
     vp8hip_batch_destroy(b->hb);
     delete b;
 }
@@ -476,6 +497,7 @@ static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *c
         key[i] = d->gop.current_is_key || (force_key && force_key[i]);
         active[i] = !key[i];
         if (was_key) was_key[i] = key[i];
+        DRV_CHK(denoise_intake(d, d->gop.current_is_key != 0));
     }
     if (host) DRV_CHK(vp8hip_batch_upload_current(b->hb, members, reinterpret_cast<const uint8_t *const *>(y), reinterpret_cast<const uint8_t *const *>(u),
                                                   reinterpret_cast<const uint8_t *const *>(v)));
@@ -591,6 +613,20 @@ int vp8drv_get_quality_summary(vp8drv *d, vp8drv_quality_summary *s) {
     if (!d->cfg.quality_stats) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     return vp8hip_quality_summary(d->hip, s);
+}
+
+int vp8drv_set_denoise(vp8drv *d, int level) {
+    if (!d || level < 0 || level > 3 || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_denoise(d->hip, level));
+    d->denoise = level;
+    return VP8HIP_OK;
+}
+
+int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s) {
+    if (!d || !s) return VP8HIP_ERR_ARG;
+    return vp8hip_denoise_result(d->hip, s);
 }
 
 int vp8drv_ready(const vp8drv *d) { return !d || !d->verdict_pending || vp8hip_check_ssim_ready(d->hip); }

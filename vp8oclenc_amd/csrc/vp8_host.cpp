@@ -3,6 +3,7 @@
 #include "../../include/vp8hip_host.h"
 
 #include <math.h>
+#include <string.h>
 
 namespace {
 
@@ -333,3 +334,74 @@ int vp8host_scale_taps(int n_in, int n_out, int kind, int32_t *n_taps, int32_t *
 }
 
 }  // extern "C"
+
+// The device's temporal denoiser in plain C++ (include/vp8hip_host.h has the rule).
+namespace {
+
+inline int denoise_step(int s, int r, int k, int *a_out) {
+    const int d = r - s, a = d < 0 ? -d : d;
+    *a_out = a;
+    if (a <= 2 + k) return d;
+    const int m = a <= 7 ? 2 + k : (a <= 15 ? 3 + k : 5 + k);
+    return d < 0 ? -m : m;
+}
+
+// one n x n block: the steps into c[], returns T; *sad gets the sum of |d|
+int denoise_block(const uint8_t *s, const uint8_t *r, int stride, int n, int k, int *c, int *sad) {
+    int T = 0;
+    *sad = 0;
+    for (int y = 0; y < n; ++y)
+        for (int x = 0; x < n; ++x) {
+            int a;
+            const int v = denoise_step(s[y * stride + x], r[y * stride + x], k, &a);
+            c[y * n + x] = v;
+            T += v;
+            *sad += a;
+        }
+    return T;
+}
+
+void denoise_put(const uint8_t *s, uint8_t *o, int stride, int n, const int *c) {
+    for (int y = 0; y < n; ++y)
+        for (int x = 0; x < n; ++x) o[y * stride + x] = (uint8_t)(s[y * stride + x] + (c ? c[y * n + x] : 0));
+}
+
+}  // namespace
+
+extern "C" int vp8host_denoise_frame(const uint8_t *src_y, const uint8_t *src_u, const uint8_t *src_v, uint8_t *hist_y, uint8_t *hist_u,
+                                     uint8_t *hist_v, uint8_t *out_y, uint8_t *out_u, uint8_t *out_v, int width, int height, int level,
+                                     int have_history, int32_t *mbs_filtered) {
+    if (!src_y || !src_u || !src_v || !out_y || !out_u || !out_v || !mbs_filtered || width < 16 || height < 16 || (width & 15) || (height & 15) ||
+        level < 0 || level > 3 || (level && (!hist_y || !hist_u || !hist_v)))
+        return -1;
+    const int cw = width / 2, ch = height / 2;
+    const size_t ny = (size_t)width * height, nc = (size_t)cw * ch;
+    *mbs_filtered = 0;
+    if (!level || !have_history) {
+        if (out_y != src_y) memmove(out_y, src_y, ny);
+        if (out_u != src_u) memmove(out_u, src_u, nc);
+        if (out_v != src_v) memmove(out_v, src_v, nc);
+    } else {
+        int c[256], cc[64], sad, unused;
+        for (int my = 0; my < height / 16; ++my)
+            for (int mx = 0; mx < width / 16; ++mx) {
+                const size_t oy = (size_t)my * 16 * width + mx * 16, oc = (size_t)my * 8 * cw + mx * 8;
+                const int T = denoise_block(src_y + oy, hist_y + oy, width, 16, level, c, &sad);
+                const bool f = (T < 0 ? -T : T) <= VP8HOST_DENOISE_SUM_Y && sad <= VP8HOST_DENOISE_SAD_Y;
+                denoise_put(src_y + oy, out_y + oy, width, 16, f ? c : nullptr);
+                *mbs_filtered += f;
+                const uint8_t *sp[2] = {src_u + oc, src_v + oc}, *hp[2] = {hist_u + oc, hist_v + oc};
+                uint8_t *op[2] = {out_u + oc, out_v + oc};
+                for (int p = 0; p < 2; ++p) {
+                    const int Tc = denoise_block(sp[p], hp[p], cw, 8, level, cc, &unused);
+                    denoise_put(sp[p], op[p], cw, 8, f && (Tc < 0 ? -Tc : Tc) <= VP8HOST_DENOISE_SUM_C ? cc : nullptr);
+                }
+            }
+    }
+    if (level) {
+        if (hist_y != out_y) memmove(hist_y, out_y, ny);
+        if (hist_u != out_u) memmove(hist_u, out_u, nc);
+        if (hist_v != out_v) memmove(hist_v, out_v, nc);
+    }
+    return 0;
+}

@@ -115,6 +115,16 @@ struct vp8hip_ctx {
     vp8::ScalePlan scale;
     uint8_t *scale_stage = nullptr;
     size_t scale_stage_bytes = 0;
+    // vp8hip_set_denoise: the level (0 = off); whether cur_prev holds a history (the previous frame taken in, as it left k_denoise_b, at
+    // this level); the count / ticket word of the launch, the record's host mirror and the launches so far (the last one writes
+    // dn_seq into the mirror's seq).  dn_host: the last frame taken in passed through and its record is the host's own.
+    int dn_level = 0;
+    bool dn_have_history = false, dn_taken = false, dn_host = false;
+    unsigned long long *d_dn = nullptr;
+    vp8::DenoiseMirror *h_dn = nullptr;
+    vp8::DenoiseMirror dn_passed{};
+    uint32_t dn_seq = 0;
+    hipStream_t dn_stream = nullptr;
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out
     // vp8hip_set_quality_stats: the state, the per-wave partials and the ticket of k_quality (one allocation), the state's host mirror
@@ -304,7 +314,7 @@ inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) {
 }
 inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched pack / scale launch takes as one value
     return a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
-           (!a->scale.in_w || a->scale.kind == b->scale.kind);
+           (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level;      // (and one denoiser level)
 }
 void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask = 0);
 int make_last(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
@@ -341,6 +351,12 @@ int receive_last_surface(const vp8hip_ctx *c);
 int adopt_last(vp8hip_ctx *c, int idx);
 // ---- api_profile.hip ----
 int prof_collect(vp8hip_ctx *c);
+// ---- api_denoise.hip ----
+// The frame just packed or scaled into c->cur passes through the denoiser (every way a frame becomes current calls one of these, right
+// behind the pack, on the pack's stream).  denoise_item: false = nothing to launch (off, or no history: the frame passes through and
+// is the history from now on); denoise_current: the launch for one context.
+bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it);
+void denoise_current(vp8hip_ctx *c);
 // ---- api_quality.hip ----
 bool quality_item(vp8hip_ctx *c, const Frame &rec, hipStream_t s, QualityArgs &a);   // false: stats off
 void quality_after_filter(vp8hip_ctx *c, const Frame &rec, hipStream_t s);           // the measurement behind the context's filter

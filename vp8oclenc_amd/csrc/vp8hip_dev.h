@@ -151,6 +151,12 @@ struct ScalePlan { int in_w = 0, in_h = 0, kind = 0; ScaleDim d[4] = {}; uint8_t
 bool scale_plan_make(ScalePlan *p, int in_w, int in_h, int dst_w, int dst_h, int W, int H, int kind, std::vector<uint8_t> &blob);   // false: refused
 void launch_scale_batch(hipStream_t s, const Frame *const *f, const void *const *y, const void *const *u, const void *const *v,
                         const ScalePlan *const *plan, int n);
+// kernels_denoise.hip: temporal noise reduction of the frame just packed or scaled (vp8hip_set_denoise), in place on `cur` against
+// `hist`, the previous current frame as it left this launch; the rule is include/vp8hip_host.h's.  `word` (zero at rest) takes the
+// count of filtered macroblocks and the waves' tickets; the wave with the last ticket writes the record into `host`, seq last.
+struct DenoiseMirror { int32_t frame_number, mbs_filtered, mbs_total; uint32_t seq; };
+struct DenoiseItem { Frame cur, hist; unsigned long long *word; DenoiseMirror *host; uint32_t seq; int32_t frame_number; };
+void launch_denoise_batch(hipStream_t s, const DenoiseItem *items, int n, int level);
 bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int net_width, int n, bool finest, bool top_only = false);
 void launch_search1_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int level, int src_idx,
                           int net_width, int n);
