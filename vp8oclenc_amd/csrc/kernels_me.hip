@@ -280,8 +280,8 @@ __device__ __forceinline__ void s1_subblock(const uint8_t *cp, int cstride, cons
     for (int i = 0; i < 5; ++i) acc[i] += weight_cols_pre(pre, col + i);
 }
 
-// The same with the current block's share of the metric taken from LDS (pre_lds[pre_off ..]: the 16 ints weight_pre_column x 4 of this sub-block,
-// made once per wave by s1_make_pre below): the five dy lanes of a block -- and every reference -- need the same 16 dot4, 8 permutes and 4 biases
+// The same with the current block's share of the metric taken from LDS (pre_lds[pre_off ..]: the 16 ints weight_pre_block of this sub-block,
+// made once per wave by s1_make_pre below): the five dy lanes of a block -- and every reference -- need the same 16 dot4, 12 adds, 8 permutes and 4 biases
 // per sub-block; as instructions of the wave they cost what they cost one lane.  The column pass of a candidate is one MFMA for the whole wave
 // (weight_mfma, vp8hip_dev.h; every lane of the wave runs this), B = its four columns, C = the current block's share, read again from LDS for each
 // candidate: held in registers next to the 16 results it would cost 16 registers, and the loop form is tuned for eight waves per SIMD.  The
@@ -324,8 +324,7 @@ __device__ __forceinline__ void s1_make_pre(const Plane &cur, int cx, int cy, in
     for (int y = 0; y < 4; ++y) c[y] = *reinterpret_cast<const uint32_t *>(cp + (ptrdiff_t)y * cur.stride) ^ 0x80808080u;
     transpose4x4(c, cc);
     int pre[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) weight_pre_column(cc[k], pre + 4 * k);
+    weight_pre_block(cc, pre);
     if (on) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) *reinterpret_cast<int4 *>(dst16 + 4 * k) = make_int4(pre[4 * k], pre[4 * k + 1], pre[4 * k + 2], pre[4 * k + 3]);
@@ -796,8 +795,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) voi
         pp[c] = (int)pw;
     }
     int pre[16];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) weight_pre_column(cc[c], pre + 4 * c);
+    weight_pre_block(cc, pre);
     v16i c16;
 #pragma unroll
     for (int k = 0; k < 16; ++k) c16[k] = pre[k];

@@ -18,7 +18,7 @@
 //     [4x4 block][candidate][column] so that a (candidate, 4x4 block) task of the cost phase is 16 contiguous bytes.  The whole-pel cases
 //     are copies, and the zero-vector block is candidate 25 of the same array.
 //   * Then lane k = candidate (dx, dy) of the 25 (+ the zero-vector candidate): the block-match metric on four 4x4 blocks, the
-//     current block's share of its column pass made once per block into LDS (weight_pre_column) and the column pass of 64 (candidate,
+//     current block's share of its column pass made once per block into LDS (weight_pre_block) and the column pass of 64 (candidate,
 //     4x4 block) tasks of a wave as ONE more MFMA, the current block's share its C input (weight_mfma, vp8hip_dev.h); the minimum over
 //     the 32 lanes by four DPP steps + row_bcast, over a key whose low byte holds the candidate's offsets as (dy + 2) * 8 + (dx + 2): the
 //     one lane that writes the block's result reads the winner's vector out of it.
@@ -26,7 +26,8 @@
 // suite.  History per 1080p frame and reference: 32-bit multiply-adds 0.156 ms; both passes on v_dot4_i32_i8 0.091 (892 vector
 // instructions per wave; git history, ae32ece^); with the metric's column pass on the matrix cores 522 vector instructions per wave, group of
 // eight blocks and reference; with the reference loop 475 per reference + 53 per group = 493 at three references
-// (tests/test_search2_instruction_budget.py).
+// (tests/test_search2_instruction_budget.py); with the row butterfly of rows 0 and 2 of the metric folded into its MFMA 443 per reference + 70 per
+// group = 466 (tests/test_metric_instruction_budget.py).
 #include <stdlib.h>
 #include <string.h>
 
@@ -168,7 +169,7 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
     __shared__ __attribute__((aligned(16))) uint32_t s_HT[8][5 * HT_XC];
     __shared__ __attribute__((aligned(16))) uint32_t s_V[8][V_SLOT];   // vertical pass results and the zero-MV block: [4x4 block][candidate][column], biased bytes
     uint32_t(*s_win)[V_SLOT] = s_V;   // the staged window (16 rows x 32 B) is dead once the horizontal pass has read it: same bytes
-    // the current block's share of the metric, [4x4 block][column][R0,R2,X,Y], made once per group of blocks; 4x4 block 3 three times over
+    // the current block's share of the metric, [4x4 block][the 16 quantities of weight_mfma], made once per group of blocks; 4x4 block 3 three times over
     // (ints 48.., 64.., 80..), so that an idle lane of the cost phase, which stays on block 3, steps through the table as the others do.
     // (LDS per workgroup decides how many workgroups a CU holds: 21.6 KB = seven.)
     __shared__ __attribute__((aligned(16))) int s_pre[8][PRE_SLOT];
@@ -180,26 +181,29 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
     const bool live = wg_x * 8 + g < a.nblk;
     const int by = a.bw == 1 ? b : (int)__umulhi((uint32_t)b, a.bw_inv), bx = b - by * a.bw;   // b / bw: bw_inv = ceil(2^32 / bw), exact for b * bw < 2^32
     const int cx = bx * 8, cy = by * 8;
-    {   // current block: lanes 0-15 one dword each, scattered as column bytes [column][row half] (16 dwords, in the table's last 64 bytes), then
-        // its share of the metric (vp8hip_dev.h, weight_pre_column): 16 columns x 4 quantities, two per lane.
-        // Order = the order the cost loop below walks the 4x4 blocks: q = (m*2 + n)*4 + j  <->  column 4n+j, row half m
+    {   // current block: lanes 0-15 one dword each, scattered as column bytes [row half][column] (16 dwords, in the table's last 64 bytes): the four
+        // columns of 4x4 block (m*2 + n) -- the order the cost loop below walks them: row half m, column half n -- are four consecutive dwords.  Then
+        // its share of the metric (vp8hip_dev.h, weight_pre_half), half a 4x4 block per lane: lane = (copy t, half): the 4x4 blocks 0, 1, 2, 3 and the two
+        // further copies of block 3 (t = 3, 4, 5), the quantities of row 0 + X or those of row 2 + Y.  No lane is masked: the lanes past the twelfth
+        // make and store the last copy's halves again.
         const int g_n = tn >> 5, lane_n = tn & 31;
         uint32_t *tmp = reinterpret_cast<uint32_t *>(&s_pre[g_n][80]);
         if (lane_n < 16) {
             const int row = lane_n >> 1, half = lane_n & 1;
             const uint32_t v = *reinterpret_cast<const uint32_t *>(a.cur.p + (ptrdiff_t)(cy + row) * a.cur.stride + cx + 4 * half) ^ 0x80808080u;
-            uint8_t *cz = reinterpret_cast<uint8_t *>(tmp) + half * 32 + row;
+            uint8_t *cz = reinterpret_cast<uint8_t *>(tmp) + (row >> 2) * 32 + half * 16 + (row & 3);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) cz[j * 8] = (uint8_t)(v >> (8 * j));
+            for (int j = 0; j < 4; ++j) cz[j * 4] = (uint8_t)(v >> (8 * j));
         }
         lds_fence();
-        const int q = lane_n & 15, m = q >> 3, n = (q >> 2) & 1, j = q & 3;
-        const uint32_t ccol = tmp[(4 * n + j) * 2 + m];      // (every lane of the wave reads before any of them writes: LDS takes a wave's operations in order)
-        int *pre = &s_pre[g_n][q * 4 + (lane_n >> 4) * 2];
-        const int p0 = dot4s(ccol, lane_n < 16 ? K_W_R0 : K_W_X, 0), p1 = dot4s(ccol, lane_n < 16 ? K_W_R2 : K_W_Y, 0);
-        pre[0] = p0;
-        pre[1] = p1;
-        if (q >= 12) { pre[16] = p0; pre[17] = p1; pre[32] = p0; pre[33] = p1; }
+        const int hf = lane_n & 1, t = imin(lane_n >> 1, 5), qb = imin(t, 3);
+        const v4i cv = *reinterpret_cast<const v4i *>(tmp + 4 * qb);   // (every lane of the wave reads before any of them writes: LDS takes a wave's operations in order)
+        const uint32_t cc[4] = {(uint32_t)cv.x, (uint32_t)cv.y, (uint32_t)cv.z, (uint32_t)cv.w};
+        int smcd[4], xy[4];
+        weight_pre_half(cc, hf ? K_W_R2 : K_W_R0, hf ? K_W_Y : K_W_X, smcd, xy);
+        int *dst = &s_pre[g_n][16 * t + 4 * hf];
+        *reinterpret_cast<v4i *>(dst) = v4i{smcd[0], smcd[1], smcd[2], smcd[3]};
+        *reinterpret_cast<v4i *>(dst + METRIC_X) = v4i{xy[0], xy[1], xy[2], xy[3]};
     }
     // ---- lane = candidate: what of it does not depend on the reference ------------------------------
     // its number in the key's low byte as (dy + 2) * 8 + (dx + 2), 40 for the zero vector: the same order as k, and the lane

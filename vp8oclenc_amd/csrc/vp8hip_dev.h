@@ -502,9 +502,33 @@ __device__ __forceinline__ void weight_pre_column(uint32_t ccol, int pre[4]) {
 // unsigned; the biases ride on work that is done anyway: +0x8000 joins the rounding 7 of a1 (then ">> 4" is a LOGICAL
 // shift and the pair comes out with +2048: floor((x + 32768) / 16) = floor(x / 16) + 2048), and +2^28 joins the rounding
 // constants of the rotations (the high half comes out with +4096; |sums| < 2^28, so nothing saturates).
+// ... the part behind the butterfly, for one pair of rows: o0, o2 = (a1 + b1 + 7 + 0x8000) >> 4 and (a1 - b1 + 7 + 0x8000) >> 4 of the pair,
+// xy_lo / xy_hi = (c1, d1) of its first / second row, d1 = the pair's d1; adds the pair's eight |coefficients| (with their biases taken off) to acc
+__device__ __forceinline__ uint32_t weight_rows_tail(uint32_t o0, uint32_t o2, uint32_t xy_lo, uint32_t xy_hi, uint32_t d1, uint32_t acc) {
+    const int t1l = dot2(xy_lo, K_ROT_A, 12000 + (1 << 28)), t1h = dot2(xy_hi, K_ROT_A, 12000 + (1 << 28));
+    const int t3l = dot2(xy_lo, K_ROT_B, 51000 + (1 << 28)), t3h = dot2(xy_hi, K_ROT_B, 51000 + (1 << 28));
+    // (x >> 16) of both rows = the high halves, packed (+4096 each)
+    const uint32_t o1 = __builtin_amdgcn_perm((uint32_t)t1h, (uint32_t)t1l, 0x07060302u);
+    const uint32_t o3 = __builtin_amdgcn_perm((uint32_t)t3h, (uint32_t)t3l, 0x07060302u);
+    // |o1 + (d1 != 0)| per half: the +1 rides in the subtrahend of the absolute difference.
+    // d1 != 0, per half: min(d1 as unsigned, 1), one v_pk_min_u16 (was sub / or / shift / and on the pair).  The 1s pass
+    // through an empty asm: min(x, 1) with a constant hipcc can see becomes x != 0, which it scalarises into two v_cmp and
+    // two v_cndmask per pair.
+    uint32_t ones = 0x00010001u;
+    asm("" : "+s"(ones));
+    const uint32_t nz = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, d1), __builtin_bit_cast(u16x2, ones)));
+    acc = __builtin_amdgcn_sad_u16(o0, 0x08000800u, acc);
+    acc = __builtin_amdgcn_sad_u16(o1, 0x10001000u - nz, acc);
+    acc = __builtin_amdgcn_sad_u16(o2, 0x08000800u, acc);
+    return __builtin_amdgcn_sad_u16(o3, 0x10001000u, acc);
+}
+// ... and the end: o00 = the DC in its low half, still carrying its +2048 (the high half may hold anything)
+__device__ __forceinline__ int weight_rows_end(uint32_t acc, uint32_t o00) {
+    const int a00 = (int)__builtin_amdgcn_sad_u16(o00 & 0xffffu, 2048u, 0u);   // |DC| (the high halves are both zero)
+    return (int)acc - (a00 - (a00 >> 2));   // DC counts a quarter (DC_UNSIGNIFICANCE, :83,:183)
+}
 __device__ __forceinline__ int weight_rows(const s16x2 A[4], const s16x2 B[4]) {
-    uint32_t acc = 0;
-    int o00 = 0;
+    uint32_t acc = 0, o00 = 0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const s16x2 *X = h == 0 ? A : B;
@@ -514,26 +538,10 @@ __device__ __forceinline__ int weight_rows(const s16x2 A[4], const s16x2 B[4]) {
         const u16x2 o2 = (a7 - __builtin_bit_cast(u16x2, b1)) >> u16x2{4, 4};
         const uint32_t xy_lo = __builtin_amdgcn_perm(as_u32(d1), as_u32(c1), 0x05040100u);   // (c1, d1) of the first row
         const uint32_t xy_hi = __builtin_amdgcn_perm(as_u32(d1), as_u32(c1), 0x07060302u);   // ... of the second row
-        const int t1l = dot2(xy_lo, K_ROT_A, 12000 + (1 << 28)), t1h = dot2(xy_hi, K_ROT_A, 12000 + (1 << 28));
-        const int t3l = dot2(xy_lo, K_ROT_B, 51000 + (1 << 28)), t3h = dot2(xy_hi, K_ROT_B, 51000 + (1 << 28));
-        // (x >> 16) of both rows = the high halves, packed (+4096 each)
-        const uint32_t o1 = __builtin_amdgcn_perm((uint32_t)t1h, (uint32_t)t1l, 0x07060302u);
-        const uint32_t o3 = __builtin_amdgcn_perm((uint32_t)t3h, (uint32_t)t3l, 0x07060302u);
-        // |o1 + (d1 != 0)| per half: the +1 rides in the subtrahend of the absolute difference.
-        // d1 != 0, per half: min(d1 as unsigned, 1), one v_pk_min_u16 (was sub / or / shift / and on the pair).  The 1s pass
-        // through an empty asm: min(x, 1) with a constant hipcc can see becomes x != 0, which it scalarises into two v_cmp and
-        // two v_cndmask per pair.
-        uint32_t ones = 0x00010001u;
-        asm("" : "+s"(ones));
-        const uint32_t nz = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, d1), __builtin_bit_cast(u16x2, ones)));
-        acc = __builtin_amdgcn_sad_u16(__builtin_bit_cast(uint32_t, o0), 0x08000800u, acc);
-        acc = __builtin_amdgcn_sad_u16(o1, 0x10001000u - nz, acc);
-        acc = __builtin_amdgcn_sad_u16(__builtin_bit_cast(uint32_t, o2), 0x08000800u, acc);
-        acc = __builtin_amdgcn_sad_u16(o3, 0x10001000u, acc);
-        if (h == 0) o00 = (int)(__builtin_bit_cast(uint32_t, o0) & 0xffffu);   // the DC, still carrying its +2048
+        acc = weight_rows_tail(__builtin_bit_cast(uint32_t, o0), __builtin_bit_cast(uint32_t, o2), xy_lo, xy_hi, as_u32(d1), acc);
+        if (h == 0) o00 = __builtin_bit_cast(uint32_t, o0);
     }
-    const int a00 = (int)__builtin_amdgcn_sad_u16((uint32_t)o00, 2048u, 0u);   // |DC| (the high halves are both zero)
-    return (int)acc - (a00 - (a00 >> 2));   // DC counts a quarter (DC_UNSIGNIFICANCE, :83,:183)
+    return weight_rows_end(acc, o00);
 }
 
 // weight of (current - prediction) for one 4x4 block: pre = weight_pre_column of the four current columns,
@@ -556,8 +564,7 @@ __device__ __forceinline__ int weight_cols_pre(const int pre[16], const uint32_t
 }
 
 // ---- the column pass on the matrix cores -------------------------------------------------------------------------
-// The 16 dot4 of weight_cols_pre are a product of a constant 16 x 16 int8 table W (row i = quantity i & 3 of column i >> 2,
-// {R0, R2, X, Y} with the negated weights K_W_*N, over the 16 prediction bytes in column-dword order) with the prediction, plus
+// The 16 dot4 of weight_cols_pre are a product of a constant 16 x 16 int8 table W with the 16 prediction bytes (column-dword order), plus
 // the current block's share.  ONE v_mfma_i32_32x32x32_i8 (D = A.B + C) does that for the 64 lanes of a wave at once, each lane
 // on its own block (lane maps pinned by scripts/ubench/mfma_i8_layout.hip):
 //   * A and B: lane l holds k = 16 (l >> 5) + j, j = 0..15, of row l & 31 (A) or column l & 31 (B);
@@ -565,21 +572,50 @@ __device__ __forceinline__ int weight_cols_pre(const int pre[16], const uint32_t
 // So a lane's 16 result registers are exactly the rows whose bit 2 equals its half h = l >> 5, and its 16 B bytes are exactly the
 // k of that half.  A is made BLOCK-DIAGONAL: a row with bit 2 = h reads only k in [16h, 16h + 16), and both diagonal blocks are W,
 // with row m = (i & 3) + 8 (i >> 2) + 4h holding W's row i.  Then register i of lane l is W[i] . (its own 16 bytes) + (its own C[i]):
-// nothing crosses lanes, and C = the 16 ints of weight_pre_column x 4, [column][R0, R2, X, Y].  Every weight is an int8 and every
-// sum is the integer the dot4 form computes (|sum| < 2^15): the rotations and the row pass that follow are unchanged, and so is
-// every bit of the result.  An MFMA runs for the whole wave whatever EXEC says: call weight_mfma only where every lane is active.
+// nothing crosses lanes.  An MFMA runs for the whole wave whatever EXEC says: call weight_mfma only where every lane is active.
 // One MFMA holds the SIMD's vector issue for 8 cycles where the 16 dot4 (VOP3P, ~4.2 each) took ~67.
+//
+// The product is free, so it also does the part of the ROW pass that is linear in the pixels.  Rows 0 and 2 of the column pass (R0[c],
+// R2[c]) are linear; rows 1 and 3 come out of the rotations with their rounding shift.  The row pass begins, for every row, with the
+// butterfly a1 = R[0] + R[3], b1 = R[1] + R[2], c1 = R[1] - R[2], d1 = R[0] - R[3], then a1 +- b1 + 7: for rows 0 and 2 that is a
+// linear function of the 16 bytes, and W delivers it directly.  The 16 quantities of a lane (METRIC_*):
+//     s0 = R0[0] + R0[1] + R0[2] + R0[3]   (a1 + b1)      m0 = R0[0] - R0[1] - R0[2] + R0[3]   (a1 - b1)
+//     c0 = R0[1] - R0[2]                                  d0 = R0[0] - R0[3]
+//     s2, m2, c2, d2: the same over R2;   X[c], Y[c] of the four columns, as in weight_cols_pre.
+// Every weight is +-8, +-16 or +-32 (an int8); a row of W has non-zero bytes in up to all four dwords of the lane.  The current
+// block's share is the C input (weight_pre_block), and the s and m of it carry the row pass's 7 + 0x8000 (see weight_rows).
+// Behind the MFMA the rows are paired (1, 3) and (0, 2): pair (1, 3) is packed from the rotations' high halves and takes the whole row
+// pass; pair (0, 2) needs no butterfly at all, only the packing of (s0, s2), (m0, m2), (c0, d0), (c2, d2) and (d0, d2).
+// The result is the integer weight_cols_pre computes:
+//   * the row pass treats every row alike and the metric is a sum of absolute values: which rows share a packed pair does not matter,
+//     and the DC is still the low half of the pair that holds row 0;
+//   * ranges, for 8-bit pixel differences: |R0[c]|, |R2[c]| <= 8 * 4 * 255 = 8160, so |c|, |d| <= 16320 fit int16 and the packing of
+//     their low halves loses nothing; |s|, |m| <= 4 * 8160 = 32640, |s + 7|, |m + 7| <= 32647 < 2^15: s + 7 + 0x8000 lies in
+//     [0, 65536) and its low 16 bits ARE the unsigned 16-bit value (a1 + 7 + 0x8000) + b1 of weight_rows (the sums agree modulo 2^16
+//     and both lie in the range), so ">> 4" on the packed low halves sees what it saw; only the low 16 bits of s and m are used.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+// the order of a lane's 16 quantities: result registers of the MFMA, ints of its C input
+enum { METRIC_S0, METRIC_M0, METRIC_C0, METRIC_D0, METRIC_S2, METRIC_M2, METRIC_C2, METRIC_D2, METRIC_X /* + c */, METRIC_Y = 12 /* + c */ };
+// W: the weights of quantity i on the four rows of prediction column c (the prediction counts negative)
+constexpr uint32_t metric_w(int i, int c) {
+    if (i >= METRIC_X) return (i & 3) != c ? 0u : i >= METRIC_Y ? K_W_YN : K_W_XN;
+    const uint32_t pos = i < METRIC_S2 ? K_W_R0N : K_W_R2N, neg = i < METRIC_S2 ? K_W_R0 : K_W_R2;   // + R[c], - R[c] of the difference
+    switch (i & 3) {
+    case METRIC_S0: return pos;
+    case METRIC_M0: return c == 0 || c == 3 ? pos : neg;
+    case METRIC_C0: return c == 1 ? pos : c == 2 ? neg : 0u;
+    default: return c == 0 ? pos : c == 3 ? neg : 0u;
+    }
+}
 struct MetricTable { uint32_t w[64][4]; };   // the A operand, lane l's four dwords
 constexpr MetricTable make_metric_a() {
     MetricTable t{};
-    const uint32_t K[4] = {K_W_R0N, K_W_R2N, K_W_XN, K_W_YN};
     for (int l = 0; l < 64; ++l) {
         const int m = l & 31, h = l >> 5;
         if (((m >> 2) & 1) != h) continue;                  // off the diagonal: zero
         const int i = (m & 3) + 4 * (m >> 3);               // the result register row m lands in
-        t.w[l][i >> 2] = K[i & 3];                          // k = 16h + 4c + r: row r of column c, only column c = i >> 2 weighs
+        for (int c = 0; c < 4; ++c) t.w[l][c] = metric_w(i, c);   // k = 16h + 4c + r: row r of column c
     }
     return t;
 }
@@ -587,20 +623,57 @@ static __device__ __constant__ const MetricTable K_METRIC_A = make_metric_a();
 // this lane's A operand: read once per wave, kept in four registers
 __device__ __forceinline__ v4i metric_a(int wave_lane) { return *reinterpret_cast<const v4i *>(K_METRIC_A.w[wave_lane & 63]); }
 
-// weight of (current - prediction) for one 4x4 block per lane: a = metric_a, c = weight_pre_column of the four current columns
-// ([column][R0, R2, X, Y]), p = the four prediction columns as biased bytes.  The same value as weight_cols_pre.
+// The current block's share of the 16 quantities (the C input of weight_mfma), from its four columns (cc[c] = the four rows of column c
+// as biased bytes), is two halves of the same shape: {s, m, c, d} of a row + one of X / Y for the four columns, with the weights k_r
+// (K_W_R0 or K_W_R2) and k_xy (K_W_X or K_W_Y).  From the per-column R with adds: 8 dot4 + 6 adds for a half, where a dot4 chain per
+// quantity would be 16 dot4.  s and m carry the 7 and the bias of the row pass (see weight_rows).
+__device__ __forceinline__ void weight_pre_half(const uint32_t cc[4], uint32_t k_r, uint32_t k_xy, int smcd[4], int xy[4]) {
+    int R[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        R[c] = dot4s(cc[c], k_r, 0);
+        xy[c] = dot4s(cc[c], k_xy, 0);
+    }
+    const int a7 = R[0] + R[3] + 0x8007, b = R[1] + R[2];
+    smcd[METRIC_S0] = a7 + b;
+    smcd[METRIC_M0] = a7 - b;
+    smcd[METRIC_C0] = R[1] - R[2];
+    smcd[METRIC_D0] = R[0] - R[3];
+}
+__device__ __forceinline__ void weight_pre_block(const uint32_t cc[4], int pre[16]) {
+    weight_pre_half(cc, K_W_R0, K_W_X, pre + METRIC_S0, pre + METRIC_X);
+    weight_pre_half(cc, K_W_R2, K_W_Y, pre + METRIC_S2, pre + METRIC_Y);
+}
+
+// weight of (current - prediction) for one 4x4 block per lane: a = metric_a, c = weight_pre_block of the current block, p = the four
+// prediction columns as biased bytes.  The same value as weight_cols_pre.
 __device__ __forceinline__ int weight_mfma(v4i a, v16i c, v4i p) {
     const v16i d = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, p, c, 0, 0, 0);
-    s16x2 A[4], B[4];
+    // rows 1 and 3: the rotations per column, their high halves packed (R1[c], R3[c]), then one h iteration of weight_rows
+    s16x2 P[4];
 #pragma unroll
     for (int col = 0; col < 4; ++col) {
-        const uint32_t xy = pk16(d[4 * col + 2], d[4 * col + 3]);
+        const uint32_t xy = pk16(d[METRIC_X + col], d[METRIC_Y + col]);
         const int t1 = dot2(xy, K_ROT16_A, 16 * 14500);
         const int t3 = dot2(xy, K_ROT16_B, 16 * 7500);
-        A[col] = as_s16x2(__builtin_amdgcn_perm((uint32_t)t1, (uint32_t)d[4 * col + 0], 0x07060100u));
-        B[col] = as_s16x2(__builtin_amdgcn_perm((uint32_t)t3, (uint32_t)d[4 * col + 1], 0x07060100u));
+        P[col] = as_s16x2(__builtin_amdgcn_perm((uint32_t)t3, (uint32_t)t1, 0x07060302u));
     }
-    return weight_rows(A, B);
+    uint32_t acc = 0;
+    {
+        const s16x2 a1 = P[0] + P[3], d1 = P[0] - P[3], b1 = P[1] + P[2], c1 = P[1] - P[2];
+        const u16x2 a7 = __builtin_bit_cast(u16x2, a1) + u16x2{0x8007, 0x8007};
+        const u16x2 o0 = (a7 + __builtin_bit_cast(u16x2, b1)) >> u16x2{4, 4};
+        const u16x2 o2 = (a7 - __builtin_bit_cast(u16x2, b1)) >> u16x2{4, 4};
+        const uint32_t xy_lo = __builtin_amdgcn_perm(as_u32(d1), as_u32(c1), 0x05040100u);
+        const uint32_t xy_hi = __builtin_amdgcn_perm(as_u32(d1), as_u32(c1), 0x07060302u);
+        acc = weight_rows_tail(__builtin_bit_cast(uint32_t, o0), __builtin_bit_cast(uint32_t, o2), xy_lo, xy_hi, as_u32(d1), acc);
+    }
+    // rows 0 and 2: the butterfly came out of the product
+    const u16x2 o0 = __builtin_bit_cast(u16x2, pk16(d[METRIC_S0], d[METRIC_S2])) >> u16x2{4, 4};
+    const u16x2 o2 = __builtin_bit_cast(u16x2, pk16(d[METRIC_M0], d[METRIC_M2])) >> u16x2{4, 4};
+    acc = weight_rows_tail(__builtin_bit_cast(uint32_t, o0), __builtin_bit_cast(uint32_t, o2), pk16(d[METRIC_C0], d[METRIC_D0]),
+                           pk16(d[METRIC_C2], d[METRIC_D2]), pk16(d[METRIC_D0], d[METRIC_D2]), acc);
+    return weight_rows_end(acc, __builtin_bit_cast(uint32_t, o0));
 }
 // C of weight_mfma from the 16 ints at pre16 (16-byte aligned): four 16-byte loads
 __device__ __forceinline__ v16i load_pre16(const int *pre16) {
