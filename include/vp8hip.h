@@ -202,6 +202,22 @@ int vp8hip_set_source_size(vp8hip_ctx *ctx, int src_width, int src_height);
  * under them): not a per-frame call.  Reference planes (vp8hip_upload_last, vp8hip_set_last_device, downloads) keep the coded size.
  * No upscaling: a decoder does that from the key frame header's scale bits.  All members of a batch must agree on all five values. */
 int vp8hip_set_source_scaling(vp8hip_ctx *ctx, int in_width, int in_height, int dst_width, int dst_height, int filter);
+/* Source frames in another format than tight 8-bit I420: NV12 (what a hardware decoder hands out), P010 (its 10-bit form), planar 4:2:2
+ * and 4:4:4, and 10-bit planar.  format: one of enum vp8host_source_format, from include/vp8hip_host.h (which states the planes of each format and the
+ * ONE integer rule that makes 8-bit I420 of them, bit for bit; vp8host_convert_frame is the rule in plain C++).  After this call the
+ * three pointers handed to vp8hip_set_current_device, vp8hip_upload_current, vp8hip_prefetch_current and the batched forms
+ * (vp8hip_batch_set_current_device, vp8hip_batch_upload_current, vp8hip_batch_prefetch_current) are that format's tight planes at the
+ * size frames come in at (the scaler's incoming size, the source size, or the coded size).  The two-plane formats never read the third
+ * pointer: pass the second one again.  ONE launch (k_convert_b) in front of the pack or scale launch, on the same stream, writes tight
+ * I420 of the incoming size into a staging buffer of the context, and the pack or scale launch reads that as if the caller had handed
+ * it in: convert, then pack or scale, then denoise.  Padding, scaling, denoising, the chroma scan and the quality statistics (which
+ * compare with the CONVERTED frame, the one that was coded) see exactly what they see for the equivalent I420 frame; it composes with
+ * vp8hip_set_source_size, vp8hip_set_source_scaling and vp8hip_set_denoise in any order of calls.
+ * 0 (I420, the default): no launch, no allocation, no byte and no number changes.  An unknown format: VP8HIP_ERR_ARG and nothing has
+ * changed.  A pending vp8hip_prefetch_current made in another format is dropped.  Waits for the context's streams: not a per-frame
+ * call.  Reference planes (vp8hip_upload_last, vp8hip_set_last_device, vp8hip_upload_recon, downloads) stay 8-bit I420 of the coded
+ * size.  All members of a batch must agree on the format (vp8hip_batch_create and the batched launch check it). */
+int vp8hip_set_source_format(vp8hip_ctx *ctx, int format);
 /* Temporal noise reduction of the source frames, the third stage of the input side (libvpx: --noise-sensitivity); the reference never
  * did anything about noise.  level 1, 2, 3: every frame that becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the
  * pack out of a vp8hip_prefetch_current staging buffer, vp8hip_batch_set_current_device, vp8hip_batch_upload_current, with or without a
@@ -407,7 +423,9 @@ const char *vp8hip_status_string(int status);
  * also under 4010: vp8hip_set_source_scaling, vp8host_scale_taps and vp8drv_config.in_width / in_height / scale_filter, in front of
  * quality_stats, which stays the last field (a host fills the struct with vp8drv_default_config, which zeroes them: no scaling);
  * also under 4010: vp8hip_set_denoise, vp8hip_denoise_restart, vp8hip_denoise_result, vp8host_denoise_frame, vp8drv_set_denoise and
- * vp8drv_get_denoise_stats (entry points only: vp8drv_config is unchanged). */
+ * vp8drv_get_denoise_stats (entry points only: vp8drv_config is unchanged);
+ * also under 4010: source formats (vp8hip_set_source_format, vp8drv_set_source_format, vp8host_source_plane_bytes, vp8host_convert_frame,
+ * vp8host_y4m_colourspace; entry points only: vp8drv_config is unchanged). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

@@ -228,6 +228,14 @@ int vp8drv_get_quality_summary(vp8drv *d, vp8drv_quality_summary *s);
 int vp8drv_set_denoise(vp8drv *d, int level);
 /* the record of the last frame taken in (vp8hip_denoise_result); VP8HIP_ERR_STATE when denoising is off or no frame was taken in */
 int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s);
+/* The format of the source frames (vp8hip_set_source_format; the formats and the rule: include/vp8hip_host.h), an entry point and not a
+ * field of vp8drv_config for the reason vp8drv_set_denoise is one.  Call it after vp8drv_create and before the first frame, or
+ * between frames.  From then on the three pointers of vp8drv_encode_frame_device / _host, vp8drv_prefetch_frame_host,
+ * vp8drv_stage_frame_host and the batched calls are that format's planes (the two-plane formats do not read the third: pass the
+ * second again).  0 = 8-bit I420, the default.  VP8HIP_ERR_ARG: an unknown format, or cfg.device_params = 0 (the host parameter
+ * mirror reads the caller's luma plane as 8-bit samples).  VP8HIP_ERR_STATE: the driver is a member of a live batch (the members
+ * must agree: set the format before vp8drv_batch_create, which refuses members that differ). */
+int vp8drv_set_source_format(vp8drv *d, int format);
 
 #ifdef __cplusplus
 }

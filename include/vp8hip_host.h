@@ -85,6 +85,41 @@ int vp8host_denoise_frame(const uint8_t *src_y, const uint8_t *src_u, const uint
                           uint8_t *out_y, uint8_t *out_u, uint8_t *out_v, int width, int height, int level, int have_history,
                           int32_t *mbs_filtered);
 
+/* The formats source frames may come in (vp8hip_set_source_format, include/vp8hip.h; k_convert_b) and the ONE integer rule that makes
+ * 8-bit I420 of the same width and height of each of them.  The project's own: the reference reads tight 8-bit I420 and nothing else.
+ * All planes are tight, width and height are even.  "16-bit" = little-endian words, two bytes per sample.
+ *     I420 (0)  Y, U, V; chroma w/2 x h/2                     8-bit        (the default: nothing is converted)
+ *     NV12 (1)  Y, interleaved UV (U first), w/2 x h/2 pairs  8-bit        (the third pointer is not read)
+ *     I422 (2)  Y, U, V; chroma w/2 x h                       8-bit
+ *     I444 (3)  Y, U, V; chroma w x h                         8-bit
+ *     P010 (4)  as NV12                                       16-bit, the value in the TOP ten bits: s = word >> 6
+ *     I010 (5)  as I420                                       16-bit, the value in the LOW ten bits: s = word & 1023
+ *     I210 (6)  as I422                                       as I010
+ *     I410 (7)  as I444                                       as I010
+ * With d the depth (8 or 10) and s a sample's value at that depth, every output sample is
+ *     out = min(255, (S + (1 << (k - 1))) >> k)        (out = S when k is 0),        k = log2(n) + d - 8,
+ * where S is the sum of the n source samples the output sample covers: n = 1 for luma and for the chroma of the 4:2:0 formats; n = 2,
+ * the two vertically adjacent samples (rows 2r and 2r + 1), for the chroma of 4:2:2; n = 4, the 2x2 block, for the chroma of 4:4:4.
+ * One rounding step, never two; chroma siting is not modelled; no colour matrix.  The clamp matters at ten bits only: 1023 gives
+ * (1023 + 2) >> 2 = 256.  The low six bits of a P010 word and the high six of the other 16-bit formats' words are ignored. */
+typedef enum {
+    VP8HOST_FORMAT_I420 = 0, VP8HOST_FORMAT_NV12 = 1, VP8HOST_FORMAT_I422 = 2, VP8HOST_FORMAT_I444 = 3,
+    VP8HOST_FORMAT_P010 = 4, VP8HOST_FORMAT_I010 = 5, VP8HOST_FORMAT_I210 = 6, VP8HOST_FORMAT_I410 = 7,
+    VP8HOST_FORMAT_COUNT = 8
+} vp8host_source_format;
+/* bytes of the planes a frame of width x height hands in (bytes[2] is 0 for the two-plane formats).  0, or -1: unknown format, a
+ * size that is odd or not positive */
+int vp8host_source_plane_bytes(int format, int width, int height, size_t bytes[3]);
+/* the rule as plain C++: p0, p1, p2 = the format's planes (p2 is not read for NV12 / P010), y, u, v = tight I420 of width x height.
+ * 0, or -1 for what vp8host_source_plane_bytes refuses or a null pointer. */
+int vp8host_convert_frame(int format, int width, int height, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2,
+                          uint8_t *y, uint8_t *u, uint8_t *v);
+/* The C tag of a YUV4MPEG2 header (which vp8host_y4m_parse_header, the reference's parser, never looks at): the header line is the
+ * bytes up to the first line feed, its tags are separated by spaces, the first tag that starts with C counts.  No C tag, C420,
+ * C420jpeg, C420mpeg2, C420paldv: I420; C422: I422; C444: I444; C420p10: I010; C422p10: I210; C444p10: I410.  Returns 0 and the
+ * format, or -1: anything else (Cmono, C444alpha, 12 and 16 bits, ...), no YUV4MPEG2 magic word, or no line feed in the buffer. */
+int vp8host_y4m_colourspace(const uint8_t *data, size_t size, int32_t *format);
+
 /* frames.skip_prob, loop_filter.h:37-44 */
 int vp8host_skip_prob(const int32_t *MB_non_zero_coeffs, int mb_count);
 

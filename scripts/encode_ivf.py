@@ -4,8 +4,10 @@
     python scripts/encode_ivf.py out.ivf [--y4m in.y4m | --yuv in.yuv --width 1920 --height 1080] [--frames 120 --gop 30 --partitions 4]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 scripts/encode_ivf.py out.ivf ...
 
---y4m: YUV4MPEG2, the reference's own input format (size and frame rate from its header, vp8oclenc_amd/y4m.py); --yuv: raw
-I420 of the given size; without either the synthetic sequence of the tests is used.  A raw I420 file has the given width/height (even numbers); when
+--y4m: YUV4MPEG2, the reference's own input format (size, frame rate and -- from the C tag -- the format of the frames from its header,
+vp8oclenc_amd/y4m.py: C422, C444, C420p10, C422p10 and C444p10 files are converted on the device, vp8drv_set_source_format; other
+colourspaces are refused); --yuv: raw frames of the given size, I420 or --source-format NAME (nv12, i422, i444, p010, i010, i210,
+i410); without either the synthetic sequence of the tests is used.  A raw I420 file has the given width/height (even numbers); when
 they are not multiples of 16 the frames are padded on the device (vp8hip_set_source_size = copy_with_padding, encIO.h:141-196)
 and the key frames carry the source size as display size."""
 import argparse, os, sys, time
@@ -18,17 +20,36 @@ from vp8oclenc_amd.synth import SynthSequence
 
 
 class YuvFile:
-    def __init__(self, path, W, H):
-        self.W, self.H = W, H
+    def __init__(self, path, W, H, fmt=0):
+        from vp8oclenc_amd import api
+        self.W, self.H, self.format = W, H, fmt
         self.m = np.memmap(path, np.uint8, "r")
-        self.fsz = W * H * 3 // 2
+        self.plane_bytes = api.source_plane_bytes(fmt, W, H)
+        self.fsz = sum(self.plane_bytes)
         self.n = len(self.m) // self.fsz
+
+    def planes(self, t):
+        b = self.m[t * self.fsz:(t + 1) * self.fsz]
+        n0, n1, n2 = self.plane_bytes
+        return [np.ascontiguousarray(p) for p in (b[:n0], b[n0:n0 + n1], b[n0 + n1:])[:3 if n2 else 2]]
 
     def frame(self, t):
         b = self.m[t * self.fsz:(t + 1) * self.fsz]
         W, H = self.W, self.H
         return (np.ascontiguousarray(b[:W * H].reshape(H, W)), np.ascontiguousarray(b[W * H:W * H * 5 // 4].reshape(H // 2, W // 2)),
                 np.ascontiguousarray(b[W * H * 5 // 4:].reshape(H // 2, W // 2)))
+
+
+class FormatPlanes:
+    """frame(t) of a file in another format than I420: the three pointers vp8drv_set_source_format expects (the second plane again for
+    the two-plane formats)"""
+
+    def __init__(self, seq):
+        self.seq, self.W, self.H, self.n = seq, seq.W, seq.H, seq.n
+
+    def frame(self, t):
+        p = self.seq.planes(t)
+        return p + [p[1]] * (3 - len(p))
 
 
 def main():
@@ -42,6 +63,7 @@ def main():
     ap.add_argument("--conformant", action="store_true", help="vp8hip_conformant_stream: NOT the reference byte for byte, but a stream that decodes to the encoder's own reconstruction")
     ap.add_argument("--resize", default="", metavar="WxH", help="code the picture at this size: the frames are scaled down on the device (vp8hip_set_source_scaling)")
     ap.add_argument("--resize-filter", choices=("area", "lanczos"), default="area")
+    ap.add_argument("--source-format", default="", metavar="NAME", help="the format of the frames of --yuv (or of --y4m, instead of its C tag: nv12 and p010 have none): i420, nv12, i422, i444, p010, i010, i210, i410; converted on the device (vp8drv_set_source_format)")
     ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -49,12 +71,20 @@ def main():
     if world > 1:      # the library's own process group (vp8hip_group_*: RCCL inside libvp8hip.so, the id through a file): no GPU framework in the host
         from vp8oclenc_amd import api
         dist = api.Group.from_env(local, f"encode_ivf-{os.getppid()}-{os.environ.get('MASTER_PORT', '0')}")
-    if a.y4m:
-        from vp8oclenc_amd.y4m import Y4mFile
-        seq = Y4mFile(a.y4m)
-        a.framerate = seq.framerate or a.framerate
-    else:
-        seq = YuvFile(a.yuv, a.width, a.height) if a.yuv else SynthSequence(a.width, a.height, seed=1)
+    from vp8oclenc_amd import api
+    try:
+        fmt = api.source_format(a.source_format) if a.source_format else None
+        if a.y4m:
+            from vp8oclenc_amd.y4m import Y4mFile
+            seq = Y4mFile(a.y4m, fmt)      # (without --source-format: the file's C tag, and ValueError for one the encoder cannot take)
+            a.framerate = seq.framerate or a.framerate
+        else:
+            seq = YuvFile(a.yuv, a.width, a.height, fmt or 0) if a.yuv else SynthSequence(a.width, a.height, seed=1)
+    except ValueError as e:
+        sys.exit(f"{a.y4m or a.yuv or '--source-format'}: {e}")
+    fmt = getattr(seq, "format", 0)
+    if fmt:
+        seq = FormatPlanes(seq)
     frames = min(a.frames, seq.n) if (a.yuv or a.y4m) else a.frames
     Wd, Hd = (int(x) for x in a.resize.lower().split("x")) if a.resize else (seq.W, seq.H)      # the picture that is coded and displayed ("dst")
     Wc, Hc = (Wd + 15) // 16 * 16, (Hd + 15) // 16 * 16            # the coded ("wrk") size, init.h:375-392
@@ -68,6 +98,8 @@ def main():
                                       loop_filter_type=int(a.simple_filter))
         if a.denoise:
             enc.drv.set_denoise(a.denoise)
+        if fmt:
+            enc.drv.set_source_format(fmt)
         return enc
     mine = gop_shard.encode_chunks_frames(make_encoder, seq, gop_shard.chunks_of_rank(frames, a.gop, rank, world))
     allf = gop_shard.gather_frames(mine, frames, dist)

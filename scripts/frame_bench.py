@@ -21,6 +21,7 @@ ap.add_argument("--quality-stats", type=int, choices=(0, 1), default=0, help="1 
 ap.add_argument("--scale-from", default="", metavar="WxH", help="the frames come in at this size and are scaled down to --width x --height on the device (vp8drv_config.in_width / in_height)")
 ap.add_argument("--scale-filter", choices=("area", "lanczos"), default="area")
 ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of every frame taken in (vp8drv_set_denoise): what k_denoise_b costs")
+ap.add_argument("--source-format", default="", metavar="NAME", help="the device-resident frames are this format's planes (nv12, p010, i444, ...: vp8drv_set_source_format): what k_convert_b costs")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -38,15 +39,23 @@ if a.scale_from:      # the same coded size, every frame through k_scale_b inste
     scale = dict(in_width=in_w, in_height=in_h, scale_filter=int(a.scale_filter == "lanczos"))
     if (a.width, a.height) != (W, H):
         scale.update(src_width=a.width, src_height=a.height)
-    dev = [tuple(api.to_device(np.ascontiguousarray(p[:in_h >> (i > 0), :in_w >> (i > 0)])) for i, p in enumerate(seq.frame(t))) for t in range(nd)]
+    host = [[np.ascontiguousarray(p[:in_h >> (i > 0), :in_w >> (i > 0)]) for i, p in enumerate(seq.frame(t))] for t in range(nd)]
 else:
-    dev = [tuple(api.to_device(p) for p in seq.frame(t)) for t in range(nd)]
+    host = [list(seq.frame(t)) for t in range(nd)]
+fmt = api.source_format(a.source_format) if a.source_format else 0
+if fmt:      # the same frames carried by the format's planes (chroma replicated, samples shifted up): the coded bytes do not change
+    host = [api.planes_from_i420(fmt, *f) for f in host]
+    host = [f + [f[1]] * (3 - len(f)) for f in host]      # (the two-plane formats: the second pointer again)
+dev = [tuple(api.to_device(p) for p in f) for f in host]
 api.device_synchronize()
 drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
                          loop_filter_type=a.loop_filter_type, quality_stats=a.quality_stats, **scale) for _ in range(a.streams)]
 if a.denoise:
     for d in drvs:
         d.set_denoise(a.denoise)
+if fmt:
+    for d in drvs:
+        d.set_source_format(fmt)
 sizes = [0] * a.streams
 
 def work(k, n, emit):
@@ -92,6 +101,14 @@ if a.streams == 1:   # the loop filter by its own clock (the kernel of the chose
     ms, n, ghz = drvs[0].hip.profile_read_clock()
     if n:
         print(f"loop filter type {a.loop_filter_type} by its own clock: {ms / n * 1e3:.1f} us per launch over {n} launches, shader clock {ghz:.2f} GHz")
+if a.streams == 1:   # the input side by HIP events: the pack launch, with k_convert_b in front of it when a source format is set
+    d = drvs[0]
+    d.hip.synchronize()
+    d.hip.profile_enable(["pack"])
+    work(0, 32, False)
+    ms, n = d.hip.profile_read().get("pack", (0.0, 0))
+    d.hip.profile_enable([])
+    print(f"input side ({a.source_format or 'i420'}), {n} timed launches over 32 frames: {ms / 32 * 1e3:.2f} us per frame")
 if a.quality_stats:
     q = drvs[0].quality_summary()
     print(f"quality of stream 0 over {q.frames} frames: PSNR overall {q.psnr_all:.3f} dB, avg {q.psnr_avg:.3f} dB, SSIM {q.ssim_all:.5f}")

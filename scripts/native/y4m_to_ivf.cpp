@@ -2,6 +2,10 @@
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
+//              [-input-format NAME]
+// The format of the frames is the header's C tag (vp8host_y4m_colourspace): C420* files are I420, C422, C444, C420p10, C422p10 and
+// C444p10 files are converted on the device (vp8drv_set_source_format), any other colourspace is refused.  -input-format NAME (i420,
+// nv12, i422, i444, p010, i010, i210, i410) says it instead of the tag: for frames the header cannot describe (NV12, P010).
 // -denoise N: temporal noise reduction of the source frames on the device, N = 1, 2, 3 (vp8drv_set_denoise; 0 = off); the share of
 // macroblocks it filtered is printed at the end, next to -psnr's summary.
 // -resize: the Y4M header gives the size of the frames that come in, WxH (even, not above it) the picture that is coded: the frames are
@@ -12,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <strings.h>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -32,6 +37,8 @@ int main(int argc, char **argv) {
     cfg.overlap_filter = 1;
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     int denoise = 0;         // -denoise
+    int32_t format = -1;     // -input-format (-1: the header's C tag)
+    static const char *const format_names[VP8HOST_FORMAT_COUNT] = {"i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"};
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -47,6 +54,12 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-psnr")) cfg.quality_stats = 1;               // PSNR / SSIM summary on stderr
         else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
+        else if (!strcmp(argv[i], "-input-format")) {
+            const char *f = val();
+            for (int k = 0; k < VP8HOST_FORMAT_COUNT; ++k)
+                if (!strcasecmp(f, format_names[k])) format = k;
+            if (format < 0) { fprintf(stderr, "-input-format %s: one of i420 nv12 i422 i444 p010 i010 i210 i410\n", f); return 2; }
+        }
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -66,6 +79,17 @@ int main(int argc, char **argv) {
         fprintf(stderr, "%s: not a YUV4MPEG2 stream the reference accepts\n", argv[1]);
         return 1;
     }
+    if (format < 0 && vp8host_y4m_colourspace(head, got, &format) != 0) {      // name the tag: what follows the first " C" of the header line
+        const uint8_t *line_end = static_cast<const uint8_t *>(memchr(head, '\n', got));
+        const size_t len = line_end ? (size_t)(line_end - head) : got;
+        size_t a = 0;
+        while (a + 1 < len && !(head[a] == ' ' && head[a + 1] == 'C')) ++a;
+        size_t b = a + 1;
+        while (b < len && head[b] != ' ') ++b;
+        fprintf(stderr, "%s: colourspace tag %.*s is not one this encoder takes (C420*, C422, C444, C420p10, C422p10, C444p10)\n", argv[1],
+                a + 1 < len ? (int)(b - a - 1) : 1, a + 1 < len ? reinterpret_cast<const char *>(head + a + 1) : "?");
+        return 1;
+    }
     fseek(in, (long)first, SEEK_SET);
     // video.src_* is the file's size, video.dst_* the picture that is coded and displayed (-resize; the file's without it), video.wrk_* that
     // rounded up to whole macroblocks (init.h:375-392).  The frames are handed over as the file has them: scaled and padded on the device.
@@ -77,18 +101,20 @@ int main(int argc, char **argv) {
     vp8drv *drv = nullptr;
     CK(vp8drv_create(&drv, Wc, Hc, 0, &cfg));
     if (denoise) CK(vp8drv_set_denoise(drv, denoise));
+    if (format) CK(vp8drv_set_source_format(drv, format));
     long long dn_filtered = 0, dn_total = 0;
     FILE *out = fopen(argv[2], "wb");
     if (!out) { perror(argv[2]); return 1; }
     uint8_t fh[32];
     fwrite(fh, 1, vp8bs_ivf_file_header(fh, Wd, Hd, (uint32_t)(fps ? fps : 30), 1, 0), out);     // frame count patched at the end (encIO.h:100-139)
-    const size_t ysz = (size_t)W * H, csz = ysz / 4;
+    size_t nb[3];            // the planes of a frame as the file has them (nb[2] == 0: two planes, the third pointer is the second again)
+    if (vp8host_source_plane_bytes(format, W, H, nb) != 0) { fprintf(stderr, "%dx%d: not a frame size of format %s\n", W, H, format_names[format]); return 1; }
     std::vector<uint8_t> bytes((size_t)(Wc / 16) * (Hc / 16) * 1900 + (1 << 20));
     // A reader thread keeps a ring of page-locked frame buffers filled ahead of the coder (get_yuv420_frame's fread, encIO.h:204-254, off the
     // frame loop's thread: 3 MB per 1080p frame is 0.4 ms of the loop's 0.5), the frame after the one under way is started on its way to the
     // device (vp8drv_prefetch_frame_host) and, once the frame just coded has its verdict and its entropy stage enqueued, handed over
     // altogether (vp8drv_stage_frame_host: the pack, scene_change()'s scan) while that frame's loop filter still has most of its time to run.
-    const size_t fsz = ysz + 2 * csz;
+    const size_t fsz = nb[0] + nb[1] + nb[2];
     enum { RING = 6 };
     uint8_t *buf[RING];
     int state[RING];                 // get_yuv420_frame's verdict on the frame in this slot: 1 = a frame, 0 = end of stream, -1 = broken
@@ -132,7 +158,7 @@ int main(int argc, char **argv) {
         if (wait) cv.wait(l, [&] { return rd_tail < rd_head; });
         return rd_tail < rd_head ? state[rd_tail % RING] : 2;
     };
-    auto planes = [&](size_t seq, const uint8_t *p[3]) { p[0] = buf[seq % RING]; p[1] = p[0] + ysz; p[2] = p[1] + csz; };
+    auto planes = [&](size_t seq, const uint8_t *p[3]) { p[0] = buf[seq % RING]; p[1] = p[0] + nb[0]; p[2] = nb[2] ? p[1] + nb[1] : p[1]; };
     uint32_t n = 0, keys = 0;
     size_t total = 32;
     // One video: the loop filter of a frame runs beside the next frame's input side (vp8hip_filter_overlap), and its entropy stage

@@ -78,6 +78,13 @@ int main(int argc, char **argv) {
     }
     fseek(in, 0, SEEK_END);
     const size_t file_size = (size_t)ftell(in);
+    {   // this tool reads tight 8-bit I420 only (y4m_to_ivf converts the other formats on the device): say so instead of coding a misread file
+        int32_t format = -1;
+        if (vp8host_y4m_colourspace(head, got, &format) != 0 || format != VP8HOST_FORMAT_I420) {
+            fprintf(stderr, "%s: the header's colourspace tag is not 8-bit 4:2:0 (C420*): y4m_to_ivf_gops does not convert formats, use y4m_to_ivf\n", argv[1]);
+            return 1;
+        }
+    }
     const size_t ysz = (size_t)W * H, csz = ysz / 4, fsz = ysz + 2 * csz, rec = fsz + 6;      // a frame and the marker behind it (get_yuv420_frame, encIO.h:203-254)
     const int nframes = (int)((file_size - first + 6) / rec);
     if (nframes < 1) { fprintf(stderr, "%s: no frame\n", argv[1]); return 1; }

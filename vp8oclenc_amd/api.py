@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -507,6 +507,66 @@ def denoise_frame(src, hist, level: int, have_history: bool):
     return out, n.value
 
 
+# vp8host_source_format, include/vp8hip_host.h: what the three pointers of a source frame are (vp8hip_set_source_format)
+FORMAT_I420, FORMAT_NV12, FORMAT_I422, FORMAT_I444, FORMAT_P010, FORMAT_I010, FORMAT_I210, FORMAT_I410 = range(8)
+FORMAT_NAMES = ["i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"]
+
+
+def source_format(name) -> int:
+    """a format's number from its name (any case) or number; ValueError for what vp8hip_set_source_format would refuse"""
+    if isinstance(name, str) and name.lower() in FORMAT_NAMES:
+        return FORMAT_NAMES.index(name.lower())
+    if isinstance(name, (int, np.integer)) and 0 <= int(name) < len(FORMAT_NAMES):
+        return int(name)
+    raise ValueError(f"unknown source format {name!r}: one of {', '.join(FORMAT_NAMES)}")
+
+
+def source_plane_bytes(fmt: int, width: int, height: int):
+    """vp8host_source_plane_bytes: bytes of the three planes a frame of this format hands in (the third is 0 for NV12 / P010)"""
+    lib = load_library()
+    lib.vp8host_source_plane_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    b = (C.c_size_t * 3)()
+    if lib.vp8host_source_plane_bytes(int(fmt), int(width), int(height), b) != 0:
+        raise ValueError(f"vp8host_source_plane_bytes(format {fmt}, {width}x{height}) refused")
+    return [int(x) for x in b]
+
+
+def convert_frame(fmt: int, width: int, height: int, planes):
+    """vp8host_convert_frame: the device's format conversion in plain C++.  planes = the format's two or three planes as contiguous
+    arrays of exactly vp8host_source_plane_bytes bytes each (uint8, or uint16 for the 16-bit formats on a little-endian host)
+    -> (Y, U, V) uint8 arrays, I420 of width x height"""
+    lib = load_library()
+    lib.vp8host_convert_frame.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+    need = source_plane_bytes(fmt, width, height)
+    planes = [np.ascontiguousarray(p) for p in planes]
+    if len(planes) == 2:
+        planes.append(planes[1])
+    for p, n in zip(planes, need):
+        if n and p.nbytes != n:
+            raise ValueError(f"convert_frame: a plane of {p.nbytes} bytes where format {fmt} at {width}x{height} has {n}")
+    out = (np.empty((height, width), np.uint8), np.empty((height // 2, width // 2), np.uint8), np.empty((height // 2, width // 2), np.uint8))
+    if lib.vp8host_convert_frame(int(fmt), int(width), int(height), *[p.ctypes.data for p in planes], *[o.ctypes.data for o in out]) != 0:
+        raise ValueError(f"vp8host_convert_frame(format {fmt}, {width}x{height}) refused")
+    return out
+
+
+def planes_from_i420(fmt: int, y, u, v):
+    """the planes of format `fmt` that carry this 8-bit I420 frame exactly -- chroma replicated, samples shifted up to the depth --
+    as flat uint8 arrays: vp8host_convert_frame returns the frame from them (for tools and benchmarks that need frames in a format)"""
+    fmt = source_format(fmt)
+    nv, tall, wide, deep = fmt in (FORMAT_NV12, FORMAT_P010), fmt in (FORMAT_I422, FORMAT_I444, FORMAT_I210, FORMAT_I410), \
+        fmt in (FORMAT_I444, FORMAT_I410), fmt >= FORMAT_P010
+    shift = 0 if not deep else (8 if fmt == FORMAT_P010 else 2)
+
+    def plane(a):
+        a = np.ascontiguousarray(a, np.uint8)
+        return (a.astype("<u2") << shift).ravel().view(np.uint8) if deep else a.ravel()
+    c = [np.repeat(np.repeat(p, 2 if tall else 1, axis=0), 2 if wide else 1, axis=1) for p in (np.asarray(u), np.asarray(v))]
+    if nv:
+        return [plane(y), plane(np.stack(c, axis=-1))]
+    return [plane(y), plane(c[0]), plane(c[1])]
+
+
 class NativeDriver:
     """The reference's frame loop as native host code (vp8_driver.cpp, include/vp8hip_driver.h): one call per
     frame.  `.hip` is a view of its context for downloads and taps."""
@@ -673,6 +733,14 @@ class NativeDriver:
         rc = self.lib.vp8drv_set_denoise(self.h, int(level))
         if rc != 0:
             raise Vp8HipError(f"vp8drv_set_denoise({level}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_source_format(self, fmt) -> None:
+        """vp8drv_set_source_format: the frames handed in from now on are this format's planes (a FORMAT_* number or its name)"""
+        self.lib.vp8drv_set_source_format.argtypes = [C.c_void_p, C.c_int]
+        fmt = source_format(fmt) if isinstance(fmt, str) else int(fmt)
+        rc = self.lib.vp8drv_set_source_format(self.h, fmt)
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_source_format({fmt}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def denoise_stats(self) -> DenoiseStats:
         """vp8drv_get_denoise_stats: the last frame taken in"""
@@ -1001,6 +1069,15 @@ class Vp8Hip:
         self._chk(self.lib.vp8hip_set_source_scaling(self.h, int(in_width), int(in_height), int(dst_width), int(dst_height), int(filter)),
                   "set_source_scaling")
         self.src = (int(in_width), int(in_height))
+
+    def set_source_format(self, fmt):
+        """vp8hip_set_source_format: current frames come in this format (a FORMAT_* number or its name) and k_convert_b makes 8-bit
+        I420 of them in front of the pack or scale launch; 0 = I420, nothing runs"""
+        self.lib.vp8hip_set_source_format.argtypes = [C.c_void_p, C.c_int]
+        fmt = source_format(fmt) if isinstance(fmt, str) else int(fmt)
+        rc = self.lib.vp8hip_set_source_format(self.h, fmt)
+        if rc != 0:
+            raise Vp8HipError(f"set_source_format({fmt}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_denoise(self, level: int):
         """vp8hip_set_denoise: every frame that becomes current passes through the temporal denoiser (level 1-3; 0 = off); turning it

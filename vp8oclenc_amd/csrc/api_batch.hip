@@ -144,33 +144,34 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
 
 // one frame's planes into a staging buffer: ONE copy when they lie end to end in the host's memory (an I420 frame as a file reader or a
 // decoder holds it), three otherwise
-static int stage_copy(vp8hip_batch *b, uint8_t *d, const void *y, const void *u, const void *v, size_t ny, size_t nc) {
+// (nb: the bytes of the three planes in the members' source format -- ny, nc, nc for I420; nb[2] == 0: two planes, v is not read)
+static int stage_copy(vp8hip_batch *b, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3]) {
     vp8hip_ctx *c0 = b->c[0];
     const uint8_t *py = static_cast<const uint8_t *>(y);
-    if (u == py + ny && v == py + ny + nc) {
-        HIPCHK(c0, hipMemcpyAsync(d, y, ny + 2 * nc, hipMemcpyHostToDevice, b->copy));
+    if (u == py + nb[0] && (!nb[2] || v == py + nb[0] + nb[1])) {
+        HIPCHK(c0, hipMemcpyAsync(d, y, nb[0] + nb[1] + nb[2], hipMemcpyHostToDevice, b->copy));
         return VP8HIP_OK;
     }
-    HIPCHK(c0, hipMemcpyAsync(d, y, ny, hipMemcpyHostToDevice, b->copy));
-    HIPCHK(c0, hipMemcpyAsync(d + ny, u, nc, hipMemcpyHostToDevice, b->copy));
-    HIPCHK(c0, hipMemcpyAsync(d + ny + nc, v, nc, hipMemcpyHostToDevice, b->copy));
+    HIPCHK(c0, hipMemcpyAsync(d, y, nb[0], hipMemcpyHostToDevice, b->copy));
+    HIPCHK(c0, hipMemcpyAsync(d + nb[0], u, nb[1], hipMemcpyHostToDevice, b->copy));
+    if (nb[2]) HIPCHK(c0, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], hipMemcpyHostToDevice, b->copy));
     return VP8HIP_OK;
 }
 
 // the copy stream, its events and the members' staging buffers (two each), made on first use and again when the source size has changed
 static int batch_stage_ready(vp8hip_batch *b) {
     vp8hip_ctx *c0 = b->c[0];
-    int sw, sh;
-    incoming_size(c0, &sw, &sh);
-    const size_t bytes = (size_t)sw * sh + 2 * (size_t)(sw / 2) * (sh / 2);
+    size_t nb[3];
+    incoming_bytes(c0, nb);
+    const size_t bytes = nb[0] + nb[1] + nb[2];
     if (!b->copy) {
         HIPCHK(c0, hipStreamCreateWithFlags(&b->copy, hipStreamNonBlocking));
         HIPCHK(c0, hipEventCreateWithFlags(&b->ev_copied, hipEventDisableTiming));
         HIPCHK(c0, hipEventCreateWithFlags(&b->ev_packed[0], hipEventDisableTiming));
         HIPCHK(c0, hipEventCreateWithFlags(&b->ev_packed[1], hipEventDisableTiming));
     }
-    if (b->stage_bytes == bytes) return VP8HIP_OK;
-    // (first call, or the source size has changed: nothing in flight reads the old buffers after this)
+    if (b->stage_bytes == bytes && b->stage_fmt == c0->src_fmt) return VP8HIP_OK;
+    // (first call, or the source size or format has changed: nothing in flight reads the old buffers after this)
     HIPCHK(c0, hipStreamSynchronize(b->copy));
     HIPCHK(c0, hipStreamSynchronize(b->stream));
     if (b->prep) HIPCHK(c0, hipStreamSynchronize(b->prep));
@@ -181,6 +182,7 @@ static int batch_stage_ready(vp8hip_batch *b) {
             HIPCHK(c0, hipMalloc(&b->stage[i][k], bytes));
         }
     b->stage_bytes = bytes;
+    b->stage_fmt = c0->src_fmt;
     b->packed_valid[0] = b->packed_valid[1] = false;
     b->pre_valid = false;
     return VP8HIP_OK;
@@ -198,14 +200,18 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
         if (!y[i] || !u[i] || !v[i]) return VP8HIP_ERR_ARG;
-        if (!same_intake(b->c[i], c0)) return VP8HIP_ERR_ARG;   // one launch, one source size (and one scaler: incoming size, dst, filter)
+        if (!same_intake(b->c[i], c0)) return VP8HIP_ERR_ARG;   // one launch, one source format and size (and one scaler: incoming size, dst, filter)
+    }
+    for (int i = 0; i < b->n && c0->src_fmt; ++i) {      // vp8hip_set_source_format: the members' I420 staging buffers (as a rule: they are there)
+        if (active && !active[i]) continue;
+        const int rc = format_stage_ready(b->c[i]);
+        if (rc) return rc;
     }
     if (host) {
         const int rc = batch_stage_ready(b);
         if (rc) return rc;
-        int sw, sh;
-        incoming_size(c0, &sw, &sh);
-        const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
+        size_t nb[3];
+        incoming_bytes(c0, nb);
         slot = b->stage_idx ^= 1;
         bool waited = false;
         for (int i = 0; i < b->n; ++i) {
@@ -215,7 +221,7 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
                 if (!waited && b->packed_valid[slot]) HIPCHK(c0, hipStreamWaitEvent(b->copy, b->ev_packed[slot], 0));   // the pack of two frames ago has read this buffer
                 waited = true;
                 {
-                    const int cr = stage_copy(b, d, y[i], u[i], v[i], ny, nc);
+                    const int cr = stage_copy(b, d, y[i], u[i], v[i], nb);
                     if (cr) {       // a failed copy: nothing of this call counts -- not the flip, not the prefetch
                         b->stage_idx ^= 1;
                         b->pre_valid = false;
@@ -223,7 +229,7 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
                     }
                 }
             }
-            sy[i] = d; su[i] = d + ny; sv[i] = d + ny + nc;
+            sy[i] = d; su[i] = d + nb[0]; sv[i] = d + nb[0] + nb[1];
         }
         b->pre_valid = false;
         HIPCHK(c0, hipEventRecord(b->ev_copied, b->copy));
@@ -232,6 +238,7 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     const Frame *f[MAX_BATCH];
     const void *py[MAX_BATCH], *pu[MAX_BATCH], *pv[MAX_BATCH];
     const ScalePlan *plans[MAX_BATCH];
+    ConvertItem cv[MAX_BATCH];
     int n = 0;
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
@@ -240,6 +247,7 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         f[n] = &b->c[i]->cur;
         plans[n] = &b->c[i]->scale;
         py[n] = y[i]; pu[n] = u[i]; pv[n] = v[i];
+        convert_item(b->c[i], cv[n], py[n], pu[n], pv[n]);      // (a source format: the pack reads the member's converted planes)
         ++n;
     }
     if (!n) return VP8HIP_OK;
@@ -257,6 +265,12 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         ps = b->prep;
     }
     if (host) HIPCHK(c0, hipStreamWaitEvent(ps, b->ev_copied, 0));
+    if (c0->src_fmt) {      // one launch for all members, in front of the pack or scale launch
+        int sw, sh;
+        incoming_size(c0, &sw, &sh);
+        Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
+        launch_convert_batch(ps, c0->src_fmt, sw, sh, cv, n);
+    }
     {
         Timed t(c0, VP8HIP_K_PACK);
         if (c0->scale.in_w) launch_scale_batch(ps, f, py, pu, pv, plans, n);      // a frame that is scaled is not packed as well
@@ -296,16 +310,15 @@ int vp8hip_batch_prefetch_current(vp8hip_batch *b, const uint8_t *const *y, cons
     USE_DEVICE_ONLY(c0);
     const int rc = batch_stage_ready(b);
     if (rc) return rc;
-    int sw, sh;
-    incoming_size(c0, &sw, &sh);
-    const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
+    size_t nb[3];
+    incoming_bytes(c0, nb);
     const int slot = b->stage_idx ^ 1;       // what the next upload will flip to
     if (b->packed_valid[slot]) HIPCHK(c0, hipStreamWaitEvent(b->copy, b->ev_packed[slot], 0));
     for (int i = 0; i < b->n; ++i) {
         b->pre[i][0] = b->pre[i][1] = b->pre[i][2] = nullptr;
         if (!y[i] || !u[i] || !v[i]) continue;
         uint8_t *d = b->stage[i][slot];
-        { const int cr = stage_copy(b, d, y[i], u[i], v[i], ny, nc); if (cr) return cr; }
+        { const int cr = stage_copy(b, d, y[i], u[i], v[i], nb); if (cr) return cr; }
         b->pre[i][0] = y[i]; b->pre[i][1] = u[i]; b->pre[i][2] = v[i];
     }
     HIPCHK(c0, hipEventRecord(b->ev_copied, b->copy));

@@ -122,6 +122,79 @@ int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, cons
     return copy_in(c, f.V, v, kind);
 }
 
+// what is still in flight may read the scaler's tables or a staging buffer: it ends first (the setters are not per-frame calls)
+static int scale_quiesce(vp8hip_ctx *c) {
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
+    if (c->h2d_stream) HIPCHK(c, hipStreamSynchronize(c->h2d_stream));
+    if (c->batch && c->batch->prep) HIPCHK(c, hipStreamSynchronize(c->batch->prep));
+    return VP8HIP_OK;
+}
+
+static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+int format_stage_ready(vp8hip_ctx *c) {
+    if (!c->src_fmt) return VP8HIP_OK;
+    int w, h;
+    incoming_size(c, &w, &h);
+    const size_t need = round256((size_t)w * h) + 2 * round256((size_t)(w / 2) * (h / 2));
+    if (need <= c->fmt_stage_bytes) return VP8HIP_OK;
+    { const int rc = scale_quiesce(c); if (rc) return rc; }      // (the incoming size has grown since the format was set: not a per-frame event)
+    uint8_t *d = nullptr;
+    HIPCHK(c, hipMalloc(&d, need));
+    (void)hipFree(c->fmt_stage);
+    c->fmt_stage = d;
+    c->fmt_stage_bytes = need;
+    return VP8HIP_OK;
+}
+
+bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u, const void *&v) {
+    if (!c->src_fmt) return false;
+    int w, h;
+    incoming_size(c, &w, &h);
+    it.src[0] = static_cast<const uint8_t *>(y);
+    it.src[1] = static_cast<const uint8_t *>(u);
+    it.src[2] = static_cast<const uint8_t *>(v);
+    it.dst[0] = c->fmt_stage;
+    it.dst[1] = it.dst[0] + round256((size_t)w * h);
+    it.dst[2] = it.dst[1] + round256((size_t)(w / 2) * (h / 2));
+    y = it.dst[0]; u = it.dst[1]; v = it.dst[2];
+    return true;
+}
+
+int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind) {
+    if (c->src_fmt) {
+        { const int rc = format_stage_ready(c); if (rc) return rc; }
+        if (kind != hipMemcpyDeviceToDevice) {      // (the caller synchronises the stream before it returns: one buffer is enough)
+            size_t nb[3];
+            incoming_bytes(c, nb);
+            const size_t need = nb[0] + nb[1] + nb[2];
+            if (need > c->fmt_raw_bytes) {
+                { const int rc = scale_quiesce(c); if (rc) return rc; }
+                uint8_t *d = nullptr;
+                HIPCHK(c, hipMalloc(&d, need));
+                (void)hipFree(c->fmt_raw);
+                c->fmt_raw = d;
+                c->fmt_raw_bytes = need;
+            }
+            uint8_t *d = c->fmt_raw;
+            HIPCHK(c, hipMemcpyAsync(d, y, nb[0], kind, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], kind, c->stream));
+            if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], kind, c->stream));
+            y = d; u = d + nb[0]; v = d + nb[0] + nb[1];
+            kind = hipMemcpyDeviceToDevice;
+        }
+        int w, h;
+        incoming_size(c, &w, &h);
+        ConvertItem it;
+        convert_item(c, it, y, u, v);
+        Timed t(c, VP8HIP_K_PACK);      // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
+        launch_convert_batch(c->stream, c->src_fmt, w, h, &it, 1);
+    }
+    return set_frame_planes(c, c->cur, y, u, v, kind, c->src_w, c->src_h, c->scale.in_w != 0);
+}
+
 void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask) {
     // cascade: every level from the rounded previous level (inter_part.h:11-33), one launch
     Timed t(c, VP8HIP_K_DOWNSAMPLE);
@@ -459,6 +532,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     if (c->ev_chroma) hipEventDestroy(c->ev_chroma);
     hipFree(c->scale.d_blob);
     hipFree(c->scale_stage);
+    hipFree(c->fmt_stage);
+    hipFree(c->fmt_raw);
     shard_release(c);
     event_pool_put(c->device, c->ev, c->ev_made);
     hipFree(c->pixel_pool);
@@ -482,36 +557,36 @@ void vp8hip_destroy(vp8hip_ctx *c) {
 int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     USE_DEVICE_ONLY(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
-    int sw, sh;
-    incoming_size(c, &sw, &sh);
-    const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
+    size_t nb[3];      // (the planes of the context's source format: ny, nc, nc for I420)
+    incoming_bytes(c, nb);
+    const size_t total = nb[0] + nb[1] + nb[2];
     if (!c->h2d_stream) {
         HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage_read[0], hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage_read[1], hipEventDisableTiming));
     }
-    if (c->h2d_stage_bytes != ny + 2 * nc) {     // first use, or the source size has changed: whatever still reads the old buffers ends first
+    if (c->h2d_stage_bytes != total) {     // first use, or the source size has changed: whatever still reads the old buffers ends first
         HIPCHK(c, hipStreamSynchronize(c->h2d_stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
         for (int k = 0; k < 2; ++k) {
             (void)hipFree(c->h2d_stage[k]);
             c->h2d_stage[k] = nullptr;
-            HIPCHK(c, hipMalloc(&c->h2d_stage[k], ny + 2 * nc));
+            HIPCHK(c, hipMalloc(&c->h2d_stage[k], total));
         }
-        c->h2d_stage_bytes = ny + 2 * nc;
+        c->h2d_stage_bytes = total;
         c->stage_read_valid[0] = c->stage_read_valid[1] = false;
     }
     const int slot = c->h2d_idx ^ 1;
     if (c->stage_read_valid[slot]) HIPCHK(c, hipStreamWaitEvent(c->h2d_stream, c->ev_stage_read[slot], 0));
     uint8_t *d = c->h2d_stage[slot];
-    if (u == y + ny && v == u + nc) {
-        HIPCHK(c, hipMemcpyAsync(d, y, ny + 2 * nc, hipMemcpyHostToDevice, c->h2d_stream));
+    if (u == y + nb[0] && (!nb[2] || v == u + nb[1])) {
+        HIPCHK(c, hipMemcpyAsync(d, y, total, hipMemcpyHostToDevice, c->h2d_stream));
     } else {
-        HIPCHK(c, hipMemcpyAsync(d, y, ny, hipMemcpyHostToDevice, c->h2d_stream));
-        HIPCHK(c, hipMemcpyAsync(d + ny, u, nc, hipMemcpyHostToDevice, c->h2d_stream));
-        HIPCHK(c, hipMemcpyAsync(d + ny + nc, v, nc, hipMemcpyHostToDevice, c->h2d_stream));
+        HIPCHK(c, hipMemcpyAsync(d, y, nb[0], hipMemcpyHostToDevice, c->h2d_stream));
+        HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], hipMemcpyHostToDevice, c->h2d_stream));
+        if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], hipMemcpyHostToDevice, c->h2d_stream));
     }
     HIPCHK(c, hipEventRecord(c->ev_h2d, c->h2d_stream));
     c->h2d_pre[0] = y; c->h2d_pre[1] = u; c->h2d_pre[2] = v;
@@ -522,19 +597,19 @@ int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, c
 int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     USE_DEVICE(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
-    int sw, sh;
-    incoming_size(c, &sw, &sh);
-    const size_t ny = (size_t)sw * sh, nc = (size_t)(sw / 2) * (sh / 2);
-    // a prefetch counts only for the source size it was made for: the staging buffers hold ny + 2 nc bytes of THAT size and the pack would read
-    // them with this one's offsets (vp8hip_set_source_size also drops a pending prefetch; this is the second lock on the same door)
-    if (c->h2d_pre_valid && c->h2d_stage_bytes == ny + 2 * nc && c->h2d_pre[0] == y && c->h2d_pre[1] == u && c->h2d_pre[2] == v) {
+    size_t nb[3];
+    incoming_bytes(c, nb);
+    // a prefetch counts only for the source size and format it was made for: the staging buffers hold the planes' bytes of THAT size and the pack
+    // would read them with this one's offsets (vp8hip_set_source_size and vp8hip_set_source_format also drop a pending prefetch; this is the
+    // second lock on the same door)
+    if (c->h2d_pre_valid && c->h2d_stage_bytes == nb[0] + nb[1] + nb[2] && c->h2d_pre[0] == y && c->h2d_pre[1] == u && c->h2d_pre[2] == v) {
         // prefetched: the planes are in (or on their way into) the staging buffer; the pack waits for the copy, nothing is copied here
         c->h2d_pre_valid = false;
         const int slot = c->h2d_idx ^= 1;
         next_current(c);
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0));
         const uint8_t *d = c->h2d_stage[slot];
-        const int rc = set_frame_planes(c, c->cur, d, d + ny, d + ny + nc, hipMemcpyDeviceToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
+        const int rc = take_current(c, d, d + nb[0], d + nb[0] + nb[1], hipMemcpyDeviceToDevice);
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->ev_stage_read[slot], c->stream));
         denoise_current(c);
@@ -544,7 +619,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
     }
     c->h2d_pre_valid = false;
     next_current(c);
-    int rc = set_frame_planes(c, c->cur, y, u, v, hipMemcpyHostToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
+    int rc = take_current(c, y, u, v, hipMemcpyHostToDevice);
     if (rc) return rc;
     denoise_current(c);
     // pageable host memory: the call must not return while the copy still reads the host buffer
@@ -556,7 +631,7 @@ int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const
     USE_DEVICE(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
     next_current(c);
-    const int rc = set_frame_planes(c, c->cur, y, u, v, hipMemcpyDeviceToDevice, c->src_w, c->src_h, c->scale.in_w != 0);
+    const int rc = take_current(c, y, u, v, hipMemcpyDeviceToDevice);
     if (rc) return rc;
     denoise_current(c);      // (vp8hip_set_denoise: right behind the pack, before anything else reads the frame)
     return VP8HIP_OK;
@@ -565,15 +640,6 @@ int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const
 // dst of a scaler, or the source size: even, not above the coded size and fewer than 16 below it
 static bool source_size_ok(const vp8hip_ctx *c, int w, int h) {
     return w > 0 && h > 0 && !(w & 1) && !(h & 1) && w <= c->W && h <= c->H && c->W - w < 16 && c->H - h < 16;
-}
-// what is still in flight may read the scaler's tables or its staging buffer: it ends first (the setters are not per-frame calls)
-static int scale_quiesce(vp8hip_ctx *c) {
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
-    if (c->h2d_stream) HIPCHK(c, hipStreamSynchronize(c->h2d_stream));
-    if (c->batch && c->batch->prep) HIPCHK(c, hipStreamSynchronize(c->batch->prep));
-    return VP8HIP_OK;
 }
 static void set_source(vp8hip_ctx *c, int w, int h, int in_w, int in_h, int kind) {
     const bool same = w == c->W && h == c->H;
@@ -628,6 +694,17 @@ int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int ds
     set_source(c, dst_width, dst_height, in_width, in_height, filter);
     plan.d_blob = d_blob;
     c->scale = plan;
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_source_format(vp8hip_ctx *c, int format) {
+    if (!c || format < 0 || format >= VP8HOST_FORMAT_COUNT) return VP8HIP_ERR_ARG;
+    if (format == c->src_fmt) return VP8HIP_OK;
+    { const int rc = scale_quiesce(c); if (rc) return rc; }
+    const int before = c->src_fmt;
+    c->src_fmt = format;
+    { const int rc = format_stage_ready(c); if (rc) { c->src_fmt = before; return rc; } }
+    c->h2d_pre_valid = false;      // planes prefetched in another format are not this format's frame
     return VP8HIP_OK;
 }
 

@@ -1,0 +1,224 @@
+// kernels_convert.hip -- source frames that are not tight 8-bit I420 (vp8hip_set_source_format): NV12, P010, 4:2:2, 4:4:4 and 10-bit
+// planar made 8-bit I420 of the same width and height, the first stage of the input side, in front of the pack (k_pack_b) or the
+// scaler (k_scale_b).  The reference reads I420 and nothing else; the rule is the project's own and is stated bit for bit in
+// include/vp8hip_host.h (vp8host_convert_frame is its plain C++ form): out = min(255, (S + (1 << (k - 1))) >> k) with S the sum of the
+// 1, 2 or 4 source samples an output sample covers and k = log2(n) + depth - 8.
+//
+// k_convert_b writes tight planes into a staging buffer of the context; the pack or scale launch behind it on the same stream reads
+// them as if the caller had handed in device I420, so padding, scaling, denoising and everything downstream see what they see today.
+//
+// Mapping (memory-bound: no LDS, 16-byte loads, 16-byte stores, everything in registers):
+//   * a lane makes 16 adjacent output samples of one row of one plane -- or, for the interleaved chroma of NV12 / P010, 16 of U and
+//     the 16 of V beside them -- and loads the 16 to 128 source bytes it needs for that itself (both rows of a vertical sum included);
+//   * samples travel as packed 16-bit pairs: bytes are widened and interleaved chroma is taken apart with v_perm_b32, 10-bit words
+//     are masked or shifted two at a time, sums (at most 4 * 1023) never carry between the halves, the clamp is v_pk_min_u16;
+//   * tight planes of any even width: rows start at any byte, so loads and stores are unaligned vector accesses; the last unit of a
+//     row that is no multiple of 16 wide is moved LEFT until it ends with the row (it rewrites a few samples of its neighbour with
+//     the same values) instead of reading past the row -- or the plane -- end;
+//   * rows of fewer than 16 outputs (pictures narrower than 16, or than 32 for chroma) have one unit that walks them sample by sample;
+//   * one launch for Y, U, V and all members of a batch: units are numbered luma first, blockIdx.z is the member.
+// The kernel is a template over (layout, depth): no format pays for another's branches.
+#include "../../include/vp8hip_host.h"
+#include "vp8hip_dev.h"
+
+namespace vp8 {
+
+namespace convert {
+
+enum Layout { PLANAR420, NV, PLANAR422, PLANAR444 };      // NV: interleaved chroma, 4:2:0 (at 10 bits: P010, the value in a word's top bits)
+
+struct Geo { int w, h, cw, ch, units_x, units_cx, luma_units, chroma_units; };      // chroma_units: per chroma job (NV: one job makes U and V)
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_u __attribute__((aligned(1)));      // at any byte: one global_load / global_store_dwordx4 all the same
+__device__ __forceinline__ uint4 load16(const uint8_t *p) {
+    const u32x4 v = *reinterpret_cast<const u32x4_u *>(p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void store16(uint8_t *p, uint4 v) { *reinterpret_cast<u32x4_u *>(p) = u32x4{v.x, v.y, v.z, v.w}; }
+
+// the two 10-bit values of a dword of two words, as a packed pair
+template <bool TOP> __device__ __forceinline__ uint32_t ten(uint32_t d) { return (TOP ? d >> 6 : d) & 0x03ff03ffu; }
+
+// Sixteen samples of one source row as eight packed pairs, added to acc.  HPAIR: every sample is the sum of two horizontally
+// adjacent source samples (4:4:4 chroma), so the row segment is twice as long.
+template <int DEPTH, bool TOP, bool HPAIR> __device__ __forceinline__ void row16(const uint8_t *p, uint32_t acc[8]) {
+    if constexpr (DEPTH == 8 && !HPAIR) {
+        const uint4 a = load16(p);
+        const uint32_t d[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            acc[2 * i] += __builtin_amdgcn_perm(0u, d[i], 0x0c010c00u);
+            acc[2 * i + 1] += __builtin_amdgcn_perm(0u, d[i], 0x0c030c02u);
+        }
+    } else if constexpr (DEPTH == 8) {
+        const uint4 a = load16(p), b = load16(p + 16);
+        const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] += (d[i] & 0x00ff00ffu) + ((d[i] >> 8) & 0x00ff00ffu);
+    } else if constexpr (!HPAIR) {
+        const uint4 a = load16(p), b = load16(p + 16);
+        const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] += ten<TOP>(d[i]);
+    } else {
+        const uint4 a = load16(p), b = load16(p + 16), c = load16(p + 32), e = load16(p + 48);
+        const uint32_t d[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e.x, e.y, e.z, e.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {      // a dword is one output sample's two words: (lo0, lo1) + (hi0, hi1)
+            const uint32_t t0 = ten<TOP>(d[2 * i]), t1 = ten<TOP>(d[2 * i + 1]);
+            acc[i] += __builtin_amdgcn_perm(t1, t0, 0x05040100u) + __builtin_amdgcn_perm(t1, t0, 0x07060302u);
+        }
+    }
+}
+
+// Sixteen interleaved (U, V) pairs of one row as eight packed pairs of U and eight of V
+template <int DEPTH> __device__ __forceinline__ void row16_uv(const uint8_t *p, uint32_t u[8], uint32_t v[8]) {
+    if constexpr (DEPTH == 8) {
+        const uint4 a = load16(p), b = load16(p + 16);
+        const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {      // U0 V0 U1 V1
+            u[i] = __builtin_amdgcn_perm(0u, d[i], 0x0c020c00u);
+            v[i] = __builtin_amdgcn_perm(0u, d[i], 0x0c030c01u);
+        }
+    } else {
+        const uint4 a = load16(p), b = load16(p + 16), c = load16(p + 32), e = load16(p + 48);
+        const uint32_t d[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e.x, e.y, e.z, e.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {      // a dword is (U word, V word)
+            const uint32_t t0 = ten<true>(d[2 * i]), t1 = ten<true>(d[2 * i + 1]);
+            u[i] = __builtin_amdgcn_perm(t1, t0, 0x05040100u);
+            v[i] = __builtin_amdgcn_perm(t1, t0, 0x07060302u);
+        }
+    }
+}
+
+// eight packed pairs of sums -> sixteen output bytes: the one rounding step, the clamp (ten bits only: eight-bit sums cannot pass 255)
+template <int K, bool CLAMP> __device__ __forceinline__ uint4 finish16(const uint32_t s[8]) {
+    uint32_t o[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        uint32_t t = s[i];
+        if (K > 0) t = ((t + (0x00010001u << (K > 0 ? K - 1 : 0))) >> K) & ((0xffffu >> K) * 0x00010001u);
+        if (CLAMP) t = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, t), u16x2{255, 255}));
+        o[i] = t;
+    }
+    return make_uint4(__builtin_amdgcn_perm(o[1], o[0], 0x06040200u), __builtin_amdgcn_perm(o[3], o[2], 0x06040200u),
+                      __builtin_amdgcn_perm(o[5], o[4], 0x06040200u), __builtin_amdgcn_perm(o[7], o[6], 0x06040200u));
+}
+
+// sample i of a plane at the format's depth, and the rule on one sum: the walk over rows too narrow for a unit of sixteen
+template <int DEPTH, bool TOP> __device__ __forceinline__ int sample(const uint8_t *p, size_t i) {
+    if (DEPTH == 8) return p[i];
+    const int word = p[2 * i] | (p[2 * i + 1] << 8);
+    return TOP ? word >> 6 : word & 1023;
+}
+template <int K> __device__ __forceinline__ uint8_t finish1(int S) {
+    const int o = K > 0 ? (S + (1 << (K > 0 ? K - 1 : 0))) >> K : S;
+    return (uint8_t)(o > 255 ? 255 : o);
+}
+
+template <int LAYOUT, int DEPTH> __device__ __forceinline__ void convert_body(const ConvertItem &it, const Geo &g) {
+    constexpr bool TOP = LAYOUT == NV;                      // (of the two-plane formats only P010 has words)
+    constexpr int B = DEPTH == 8 ? 1 : 2;                   // bytes per sample
+    constexpr int KY = DEPTH - 8;
+    constexpr int NX = LAYOUT == PLANAR444 ? 2 : 1, NY = (LAYOUT == PLANAR422 || LAYOUT == PLANAR444) ? 2 : 1;
+    constexpr int KC = DEPTH - 8 + (NX == 2) + (NY == 2);
+    int unit = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (unit < g.luma_units) {
+        const int r = unit / g.units_x, ux = unit - r * g.units_x;
+        uint8_t *out = it.dst[0] + (size_t)r * g.w;
+        const uint8_t *src = it.src[0] + (size_t)r * g.w * B;
+        if (g.w < 16) {
+            for (int x = 0; x < g.w; ++x) out[x] = finish1<KY>(sample<DEPTH, TOP>(src, x));
+            return;
+        }
+        const int x0 = min(ux * 16, g.w - 16);
+        if (DEPTH == 8) {
+            store16(out + x0, load16(src + x0));
+        } else {
+            uint32_t s[8] = {};
+            row16<DEPTH, TOP, false>(src + (size_t)x0 * B, s);
+            store16(out + x0, finish16<KY, true>(s));
+        }
+        return;
+    }
+    unit -= g.luma_units;
+    int plane = 1;
+    if (LAYOUT != NV && unit >= g.chroma_units) { unit -= g.chroma_units; plane = 2; }
+    if (unit >= g.chroma_units) return;
+    const int r = unit / g.units_cx, ux = unit - r * g.units_cx;
+    const size_t pitch = (size_t)g.cw * NX;                 // samples (NV: pairs) per source chroma row
+    if (LAYOUT == NV) {
+        const uint8_t *src = it.src[1] + (size_t)r * pitch * 2 * B;
+        uint8_t *ou = it.dst[1] + (size_t)r * g.cw, *ov = it.dst[2] + (size_t)r * g.cw;
+        if (g.cw < 16) {
+            for (int x = 0; x < g.cw; ++x) {
+                ou[x] = finish1<KC>(sample<DEPTH, TOP>(src, 2 * x));
+                ov[x] = finish1<KC>(sample<DEPTH, TOP>(src, 2 * x + 1));
+            }
+            return;
+        }
+        const int x0 = min(ux * 16, g.cw - 16);
+        uint32_t u[8], v[8];
+        row16_uv<DEPTH>(src + (size_t)x0 * 2 * B, u, v);
+        store16(ou + x0, finish16<KC, DEPTH != 8>(u));
+        store16(ov + x0, finish16<KC, DEPTH != 8>(v));
+        return;
+    }
+    const uint8_t *src = it.src[plane] + (size_t)r * NY * pitch * B;
+    uint8_t *out = it.dst[plane] + (size_t)r * g.cw;
+    if (g.cw < 16) {
+        for (int x = 0; x < g.cw; ++x) {
+            int S = 0;
+#pragma unroll
+            for (int j = 0; j < NY; ++j)
+#pragma unroll
+                for (int i = 0; i < NX; ++i) S += sample<DEPTH, TOP>(src, (size_t)j * pitch + (size_t)(x * NX + i));
+            out[x] = finish1<KC>(S);
+        }
+        return;
+    }
+    const int x0 = min(ux * 16, g.cw - 16);
+    uint32_t s[8] = {};
+#pragma unroll
+    for (int j = 0; j < NY; ++j) row16<DEPTH, TOP, NX == 2>(src + ((size_t)j * pitch + (size_t)x0 * NX) * B, s);
+    store16(out + x0, finish16<KC, DEPTH != 8>(s));
+}
+
+}  // namespace convert
+
+static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::Geo) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+template <int LAYOUT, int DEPTH> __global__ __launch_bounds__(256) void k_convert_b(BatchOf<ConvertItem> b, convert::Geo g) {
+    convert::convert_body<LAYOUT, DEPTH>(b.item[blockIdx.z], g);
+}
+
+void launch_convert_batch(hipStream_t s, int format, int w, int h, const ConvertItem *items, int n) {
+    if (n <= 0 || format == VP8HOST_FORMAT_I420) return;
+    BatchOf<ConvertItem> b;
+    b.n = n;
+    for (int i = 0; i < n; ++i) b.item[i] = items[i];
+    convert::Geo g;
+    g.w = w; g.h = h; g.cw = w / 2; g.ch = h / 2;
+    g.units_x = g.w < 16 ? 1 : (g.w + 15) / 16;
+    g.units_cx = g.cw < 16 ? 1 : (g.cw + 15) / 16;
+    g.luma_units = g.units_x * g.h;
+    g.chroma_units = g.units_cx * g.ch;
+    const bool nv = format == VP8HOST_FORMAT_NV12 || format == VP8HOST_FORMAT_P010;
+    const int units = g.luma_units + (nv ? 1 : 2) * g.chroma_units;
+    const dim3 grid((units + 255) / 256, 1, n), block(256);
+    using namespace convert;
+    switch (format) {
+        case VP8HOST_FORMAT_NV12: VP8_LAUNCH((k_convert_b<NV, 8>), grid, block, 0, s, b, g); break;
+        case VP8HOST_FORMAT_I422: VP8_LAUNCH((k_convert_b<PLANAR422, 8>), grid, block, 0, s, b, g); break;
+        case VP8HOST_FORMAT_I444: VP8_LAUNCH((k_convert_b<PLANAR444, 8>), grid, block, 0, s, b, g); break;
+        case VP8HOST_FORMAT_P010: VP8_LAUNCH((k_convert_b<NV, 10>), grid, block, 0, s, b, g); break;
+        case VP8HOST_FORMAT_I010: VP8_LAUNCH((k_convert_b<PLANAR420, 10>), grid, block, 0, s, b, g); break;
+        case VP8HOST_FORMAT_I210: VP8_LAUNCH((k_convert_b<PLANAR422, 10>), grid, block, 0, s, b, g); break;
+        case VP8HOST_FORMAT_I410: VP8_LAUNCH((k_convert_b<PLANAR444, 10>), grid, block, 0, s, b, g); break;
+        default: break;      // (vp8hip_set_source_format has refused it)
+    }
+}
+
+}  // namespace vp8

@@ -30,6 +30,7 @@ struct vp8drv {
     const uint8_t *staged = nullptr; // vp8drv_stage_frame_host: these planes are the context's current frame already (and, with scene_detect, their scan is under way)
     bool staged_scan = false;
     int denoise = 0;                 // vp8drv_set_denoise: the level in force
+    int format = 0;                  // vp8drv_set_source_format: the format in force
     bool in_batch = false;           // a member of a live vp8drv_batch
     // read-back buffers of vp8drv_get_frame
     std::vector<int32_t> seg, nz, ref, parts, is_inter, modes;
@@ -451,7 +452,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
-            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise)
+            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format)
             return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
     }
@@ -621,6 +622,17 @@ int vp8drv_set_denoise(vp8drv *d, int level) {
     { const int rc = resolve(d); if (rc < 0) return rc; }
     DRV_CHK(vp8hip_set_denoise(d->hip, level));
     d->denoise = level;
+    return VP8HIP_OK;
+}
+
+int vp8drv_set_source_format(vp8drv *d, int format) {
+    if (!d || format < 0 || format >= VP8HOST_FORMAT_COUNT || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_source_format(d->hip, format));
+    d->format = format;
+    d->staged = nullptr;             // planes staged in the other format are not this format's frame
+    d->staged_scan = false;
     return VP8HIP_OK;
 }
 

@@ -145,6 +145,104 @@ int vp8host_y4m_parse_header(const uint8_t *data, size_t size, int32_t *width, i
 
 int vp8host_y4m_frame_marker_ok(const uint8_t m[6]) { return m && m[0] == 'F' && m[4] == 'E'; }   // encIO.h:245
 
+// the header line's C tag (include/vp8hip_host.h); the reference's parser above never looks at it
+int vp8host_y4m_colourspace(const uint8_t *data, size_t size, int32_t *format) {
+    if (!data || !format) return -1;
+    static const char magic[] = "YUV4MPEG2";
+    size_t end = 0;
+    while (end < size && data[end] != 0x0A) ++end;
+    if (end == size || end < 9 || memcmp(data, magic, 9) != 0 || (end > 9 && data[9] != 0x20)) return -1;
+    static const struct { const char *tag; int format; } known[] = {
+        {"C420", VP8HOST_FORMAT_I420}, {"C420jpeg", VP8HOST_FORMAT_I420}, {"C420mpeg2", VP8HOST_FORMAT_I420}, {"C420paldv", VP8HOST_FORMAT_I420},
+        {"C422", VP8HOST_FORMAT_I422}, {"C444", VP8HOST_FORMAT_I444}, {"C420p10", VP8HOST_FORMAT_I010}, {"C422p10", VP8HOST_FORMAT_I210},
+        {"C444p10", VP8HOST_FORMAT_I410}};
+    for (size_t a = 9; a < end;) {
+        while (a < end && data[a] == 0x20) ++a;
+        size_t b = a;
+        while (b < end && data[b] != 0x20) ++b;
+        if (b > a && data[a] == 'C') {
+            for (const auto &k : known)
+                if (strlen(k.tag) == b - a && memcmp(k.tag, data + a, b - a) == 0) {
+                    *format = k.format;
+                    return 0;
+                }
+            return -1;
+        }
+        a = b;
+    }
+    *format = VP8HOST_FORMAT_I420;
+    return 0;
+}
+
+namespace {
+
+// what a format is made of: two planes (interleaved chroma) or three, chroma subsampled horizontally / vertically, depth, and
+// where a 16-bit word keeps its ten bits
+struct SourceLayout { bool nv; int sub_x, sub_y, depth; bool top; };
+bool source_layout(int format, SourceLayout *l) {
+    switch (format) {
+        case VP8HOST_FORMAT_I420: *l = {false, 1, 1, 8, false}; return true;
+        case VP8HOST_FORMAT_NV12: *l = {true, 1, 1, 8, false}; return true;
+        case VP8HOST_FORMAT_I422: *l = {false, 1, 0, 8, false}; return true;
+        case VP8HOST_FORMAT_I444: *l = {false, 0, 0, 8, false}; return true;
+        case VP8HOST_FORMAT_P010: *l = {true, 1, 1, 10, true}; return true;
+        case VP8HOST_FORMAT_I010: *l = {false, 1, 1, 10, false}; return true;
+        case VP8HOST_FORMAT_I210: *l = {false, 1, 0, 10, false}; return true;
+        case VP8HOST_FORMAT_I410: *l = {false, 0, 0, 10, false}; return true;
+        default: return false;
+    }
+}
+
+}  // namespace
+
+int vp8host_source_plane_bytes(int format, int width, int height, size_t bytes[3]) {
+    SourceLayout l;
+    if (!bytes || !source_layout(format, &l) || width <= 0 || height <= 0 || (width & 1) || (height & 1)) return -1;
+    const size_t b = l.depth > 8 ? 2 : 1;
+    const size_t chroma = (size_t)(width >> l.sub_x) * (size_t)(height >> l.sub_y) * b;
+    bytes[0] = (size_t)width * (size_t)height * b;
+    bytes[1] = l.nv ? 2 * chroma : chroma;
+    bytes[2] = l.nv ? 0 : chroma;
+    return 0;
+}
+
+int vp8host_convert_frame(int format, int width, int height, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2,
+                          uint8_t *y, uint8_t *u, uint8_t *v) {
+    SourceLayout l;
+    size_t bytes[3];
+    if (vp8host_source_plane_bytes(format, width, height, bytes) != 0 || !source_layout(format, &l)) return -1;
+    if (!p0 || !p1 || (!l.nv && !p2) || !y || !u || !v) return -1;
+    // sample i of a plane, at the format's depth
+    auto sample = [&](const uint8_t *p, size_t i) -> int {
+        if (l.depth == 8) return p[i];
+        const int word = p[2 * i] | (p[2 * i + 1] << 8);
+        return l.top ? word >> 6 : word & 1023;
+    };
+    auto round_off = [](int S, int k) -> uint8_t {
+        const int o = k ? (S + (1 << (k - 1))) >> k : S;
+        return (uint8_t)(o > 255 ? 255 : o);
+    };
+    const int ky = l.depth - 8;
+    for (size_t i = 0; i < (size_t)width * height; ++i) y[i] = round_off(sample(p0, i), ky);
+    const int cw = width / 2, ch = height / 2;
+    const int nx = 2 - l.sub_x, ny = 2 - l.sub_y;                  // source samples per output sample, across and down
+    const int kc = l.depth - 8 + (nx == 2) + (ny == 2);
+    const size_t pitch = (size_t)cw * nx;                          // samples (NV: pairs) per source chroma row
+    for (int r = 0; r < ch; ++r)
+        for (int x = 0; x < cw; ++x) {
+            int su = 0, sv = 0;
+            for (int j = 0; j < ny; ++j)
+                for (int i = 0; i < nx; ++i) {
+                    const size_t at = (size_t)(r * ny + j) * pitch + (size_t)(x * nx + i);
+                    if (l.nv) { su += sample(p1, 2 * at); sv += sample(p1, 2 * at + 1); }
+                    else { su += sample(p1, at); sv += sample(p2, at); }
+                }
+            u[(size_t)r * cw + x] = round_off(su, kc);
+            v[(size_t)r * cw + x] = round_off(sv, kc);
+        }
+    return 0;
+}
+
 int vp8host_scene_change(vp8host_scene_state *st, int Udiff, int Vdiff, int frame_number) {
     // vp8enc.cpp:285-310
     const int detect = (Udiff > 7) || (Vdiff > 7) || (Udiff + Vdiff > 10);

@@ -22,6 +22,7 @@
 #include <new>
 
 #include "../../include/vp8hip.h"
+#include "../../include/vp8hip_host.h"
 #include "vp8hip_dev.h"
 
 struct ncclComm;     // (rccl.h is included by api_shard.hip only; the library resolves RCCL when a host first asks for it)
@@ -115,6 +116,12 @@ struct vp8hip_ctx {
     vp8::ScalePlan scale;
     uint8_t *scale_stage = nullptr;
     size_t scale_stage_bytes = 0;
+    // vp8hip_set_source_format: what the three pointers of a current frame are (0 = I420: nothing below is used).  k_convert_b makes tight
+    // I420 of the incoming size of them in fmt_stage (Y, U, V at fmt_off, each plane 256-byte aligned) and the pack or scale launch
+    // reads that; planes from host memory that were not prefetched pass through fmt_raw first.
+    int src_fmt = 0;
+    uint8_t *fmt_stage = nullptr, *fmt_raw = nullptr;
+    size_t fmt_stage_bytes = 0, fmt_raw_bytes = 0;
     // vp8hip_set_denoise: the level (0 = off); whether cur_prev holds a history (the previous frame taken in, as it left k_denoise_b, at
     // this level); the count / ticket word of the launch, the record's host mirror and the launches so far (the last one writes
     // dn_seq into the mirror's seq).  dn_host: the last frame taken in passed through and its record is the host's own.
@@ -235,6 +242,7 @@ struct vp8hip_batch {
     bool packed_valid[2] = {false, false};
     uint8_t *stage[vp8::MAX_BATCH][2] = {};
     size_t stage_bytes = 0;
+    int stage_fmt = 0;                   // the source format the staging buffers' planes were laid out for
     int stage_idx = 0;
     // vp8hip_batch_prefetch_current: the NEXT frame's planes already on their way into the buffer the next upload will pack from
     const void *pre[vp8::MAX_BATCH][3] = {};
@@ -312,10 +320,22 @@ inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) {
     *w = c->scale.in_w ? c->scale.in_w : (c->src_w ? c->src_w : c->W);
     *h = c->scale.in_w ? c->scale.in_h : (c->src_h ? c->src_h : c->H);
 }
-inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched pack / scale launch takes as one value
-    return a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
+// bytes of the planes a context takes as a current frame, in its source format (I420: ny, nc, nc)
+inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) {
+    int w, h;
+    incoming_size(c, &w, &h);
+    (void)vp8host_source_plane_bytes(c->src_fmt, w, h, bytes);
+}
+inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched convert / pack / scale launch takes as one value
+    return a->src_fmt == b->src_fmt && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
            (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level;      // (and one denoiser level)
 }
+// vp8hip_set_source_format: the staging buffers at the context's incoming size (no-op for I420 or when they are large enough), and the
+// item of k_convert_b for planes in DEVICE memory: afterwards y, u, v are the I420 planes in fmt_stage.  false: I420, nothing to do.
+int format_stage_ready(vp8hip_ctx *c);
+bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u, const void *&v);
+// a context's new current frame from planes in its source format: convert, pack or scale (the caller denoises)
+int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
 void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask = 0);
 int make_last(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
 SegData *sd_for_writing(vp8hip_ctx *c);

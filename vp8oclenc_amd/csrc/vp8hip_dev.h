@@ -157,6 +157,11 @@ void launch_scale_batch(hipStream_t s, const Frame *const *f, const void *const 
 struct DenoiseMirror { int32_t frame_number, mbs_filtered, mbs_total; uint32_t seq; };
 struct DenoiseItem { Frame cur, hist; unsigned long long *word; DenoiseMirror *host; uint32_t seq; int32_t frame_number; };
 void launch_denoise_batch(hipStream_t s, const DenoiseItem *items, int n, int level);
+// kernels_convert.hip: source frames in another format than 8-bit I420 (vp8hip_set_source_format), made tight 8-bit I420 of the same
+// size IN FRONT of the pack or scale launch, which then reads dst as if the caller had handed it in; the rule is include/vp8hip_host.h's.
+// src: the format's planes (src[2] is not read for the two-plane formats).  Format 0 launches nothing.
+struct ConvertItem { const uint8_t *src[3]; uint8_t *dst[3]; };
+void launch_convert_batch(hipStream_t s, int format, int w, int h, const ConvertItem *items, int n);
 bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int net_width, int n, bool finest, bool top_only = false);
 void launch_search1_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int level, int src_idx,
                           int net_width, int n);
