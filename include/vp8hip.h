@@ -301,6 +301,44 @@ int vp8hip_set_quality_stats(vp8hip_ctx *ctx, int on);
 int vp8hip_quality_result(vp8hip_ctx *ctx, vp8hip_quality *q);
 /* The summary since stats were turned on, the last frame measured included.  Waits the same way.  VP8HIP_ERR_STATE: stats off. */
 int vp8hip_quality_summary(vp8hip_ctx *ctx, vp8hip_quality_totals *s);
+/* ---- frame analysis statistics (opt-in): what a rate controller measures -----------------------------------------------------
+ * libvpx's first-pass record cut to what this encoder knows, every field an exact integer; the two rules are stated bit for bit in
+ * include/vp8hip_host.h.  SOURCE SIDE: every frame that becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the pack
+ * out of a vp8hip_prefetch_current staging buffer, vp8hip_batch_set_current_device, vp8hip_batch_upload_current -- passes through ONE
+ * more launch (k_analyse_src_b) behind its convert / pack / scale / denoise launches on the same stream: it measures the coded luma
+ * (padding included, as the searches see it) against the context's history plane, the luma of the previous frame taken in, and
+ * writes the new luma into the history.  Once per frame TAKEN IN, never per coding attempt.  CODING SIDE: every vp8hip_loop_filter /
+ * vp8hip_batch_loop_filter is followed, on the filter's stream and without a host wait, by k_analyse_mb_b, one reduction over the
+ * per-macroblock arrays as the frame's coding attempt left them; a second filter of the same current frame (a frame sent back by
+ * check_SSIM and coded again as a key frame) replaces the first's record.
+ * on = 0 (default): no allocation, no launch, no byte and no number changes.  Turning it on allocates the history plane and the record
+ * and starts without a history.  Waits for the context's streams: not a per-frame call.  All members of a batch must agree
+ * (vp8hip_batch_create and the batched launch check it).  A context that shares a frame's searches with other devices (vp8hip_shard_init)
+ * codes only part of a frame: turning analysis on for one is refused with VP8HIP_ERR_STATE, and so is vp8hip_shard_init while it is on. */
+typedef struct {
+    int32_t frame_number;    /* 0-based index of the frame, in the order the context received its frames, as in vp8hip_quality */
+    int32_t is_key;          /* the coding attempt measured came from vp8hip_intra_transform (0 when coded is 0) */
+    int32_t have_prev;       /* 0: no history (first frame, after a restart); the three temporal fields are then 0 */
+    int32_t static_mbs;
+    uint64_t spatial, temporal_sse, temporal_sad;
+    int32_t coded;           /* 0: the frame was taken in and not coded yet; every field below is then 0 */
+    int32_t mbs_total, mbs_intra, mbs_split, mbs_zero_mv, mbs_no_coeffs;
+    int32_t mbs_ref[3];      /* LAST, GOLDEN, ALTREF */
+    int32_t segment_mbs[4];
+    int32_t reserved;        /* 0 */
+    uint64_t mv_abs_sum[2];  /* x, y; quarter pixels */
+    int64_t mv_sum[2];
+    uint64_t mv_sq_sum;
+    uint64_t nz_coeffs;
+} vp8hip_analysis;
+int vp8hip_set_analysis(vp8hip_ctx *ctx, int on);
+/* The next frame taken in has no history: have_prev = 0 (a host calls it where its stream restarts: a key frame of the GOP schedule, so
+ * that a closed GOP coded on its own gives the records the serial program gives). */
+int vp8hip_analysis_restart(vp8hip_ctx *ctx);
+/* The record of the last frame coded -- while it is the last or the last but one frame taken in (a host may hand the next frame over
+ * early) -- or else of the last frame taken in, with coded = 0.  Waits for the two measurements alone (a word each launch writes
+ * last), not for the streams.  VP8HIP_ERR_STATE: analysis off, or no frame taken in since it was turned on. */
+int vp8hip_analysis_result(vp8hip_ctx *ctx, vp8hip_analysis *a);
 /* on = 1: the context gets a second stream, and work that does not depend on the filtered frame runs beside the loop filter:
  * the entropy stage of the same frame (vp8hip_count_probs ... vp8hip_encode_frame), the next frame's upload, parameter scan
  * and GOLDEN / ALTREF searches.  The filter stays on the stream the frame was coded on and the CONTEXT moves to the other one
@@ -425,7 +463,9 @@ const char *vp8hip_status_string(int status);
  * also under 4010: vp8hip_set_denoise, vp8hip_denoise_restart, vp8hip_denoise_result, vp8host_denoise_frame, vp8drv_set_denoise and
  * vp8drv_get_denoise_stats (entry points only: vp8drv_config is unchanged);
  * also under 4010: source formats (vp8hip_set_source_format, vp8drv_set_source_format, vp8host_source_plane_bytes, vp8host_convert_frame,
- * vp8host_y4m_colourspace; entry points only: vp8drv_config is unchanged). */
+ * vp8host_y4m_colourspace; entry points only: vp8drv_config is unchanged);
+ * also under 4010: frame analysis (vp8hip_set_analysis, vp8hip_analysis_restart, vp8hip_analysis_result, vp8host_analyse_luma,
+ * vp8drv_set_analysis, vp8drv_get_frame_analysis) and vp8drv_set_quantizer / vp8drv_get_quantizer (entry points only). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

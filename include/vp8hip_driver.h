@@ -236,6 +236,26 @@ int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s);
  * mirror reads the caller's luma plane as 8-bit samples).  VP8HIP_ERR_STATE: the driver is a member of a live batch (the members
  * must agree: set the format before vp8drv_batch_create, which refuses members that differ). */
 int vp8drv_set_source_format(vp8drv *d, int format);
+/* ---- what a rate controller needs: a record to measure with and a quantizer to set -------------------------------------------
+ * Frame analysis statistics (vp8hip_set_analysis; the rules: include/vp8hip_host.h), entry points and not a field for the reason
+ * vp8drv_set_denoise is one.  on = 0 (default) or 1; it takes the open check_SSIM verdict first.  VP8HIP_ERR_ARG: another value, or
+ * cfg.device_params = 0; VP8HIP_ERR_STATE: the driver is a member of a live batch (set it before vp8drv_batch_create, which refuses
+ * members that differ).  The history restarts where the denoiser's does: when the GOP schedule makes the incoming frame a key frame, so
+ * a closed GOP coded as a chunk of its own gives the records the serial program gives (have_prev = 0 on its first frame). */
+int vp8drv_set_analysis(vp8drv *d, int on);
+typedef vp8hip_analysis vp8drv_analysis;
+/* The record of the frame just made final: its verdict first, as vp8drv_get_frame_quality (a frame coded again as a key frame has the
+ * key frame's coding side; its source side was measured once, when it was taken in).  VP8HIP_ERR_STATE: analysis off or no frame coded. */
+int vp8drv_get_frame_analysis(vp8drv *d, vp8drv_analysis *a);
+/* cfg.qi_min / qi_max from the next frame coded on: both ladders are made again with vp8host_quantizer_ladders and the driver's qi_min
+ * becomes the smaller of the two, exactly as in vp8drv_create.  It takes the open check_SSIM verdict first, so a frame sent back is coded
+ * again with the quantizers it was coded with.  References, GOP position and every other state stay: behind a key frame of the GOP
+ * schedule the frames are those of a driver created with the new pair.  VP8HIP_ERR_ARG: a value outside 0..127, the range of a VP8
+ * quantizer index (vp8drv_create does not look at its pair; the device clamps an index to this range); VP8HIP_ERR_STATE: the driver is
+ * a member of a live batch (members share the pair: set it before vp8drv_batch_create). */
+int vp8drv_set_quantizer(vp8drv *d, int qi_min, int qi_max);
+/* the pair in force, as given (not swapped) */
+int vp8drv_get_quantizer(const vp8drv *d, int32_t *qi_min, int32_t *qi_max);
 
 #ifdef __cplusplus
 }

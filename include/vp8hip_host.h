@@ -120,6 +120,53 @@ int vp8host_convert_frame(int format, int width, int height, const uint8_t *p0, 
  * format, or -1: anything else (Cmono, C444alpha, 12 and 16 bits, ...), no YUV4MPEG2 magic word, or no line feed in the buffer. */
 int vp8host_y4m_colourspace(const uint8_t *data, size_t size, int32_t *format);
 
+/* The rules of the frame analysis record (vp8hip_set_analysis, include/vp8hip.h; k_analyse_src_b, k_analyse_mb_b), bit for bit.  The
+ * project's own: libvpx's first-pass statistics cut to what this encoder knows.  Every field is an exact integer; no floats anywhere.
+ *
+ * SOURCE SIDE, once per frame taken in.  cur = the luma plane at the coded size (width and height whole 16x16 macroblocks) as the
+ * searches read it: after format conversion, padding or scaling, and denoising; the padding counts because the search sees it.
+ * prev = the same plane of the previous frame taken in (the context's history).  With x a sample of cur and p the sample of prev at
+ * the same place:
+ *     spatial       sum over the macroblocks of  256 * (sum of x * x over its 256 samples) - (sum of x over them) squared,
+ *                   i.e. 256 * 256 times the macroblock's variance; uint64
+ *     temporal_sse  sum over the plane of (x - p) * (x - p)
+ *     temporal_sad  sum over the plane of |x - p|
+ *     static_mbs    macroblocks whose sum of |x - p| is 0
+ *     have_prev     1; or 0 when there is no history -- the first frame after analysis was turned on or restarted -- and then
+ *                   temporal_sse = temporal_sad = static_mbs = 0
+ * vp8host_analyse_luma is the rule in plain C++ on tight planes (row stride = width); prev may be NULL (no history).  Returns 0, or
+ * -1: cur or out NULL, width or height below 16 or not a multiple of 16.
+ *
+ * CODING SIDE, a pure function of the per-macroblock arrays of the frame's FINAL coding attempt (a frame check_SSIM sent back and that
+ * was coded again as a key frame has the key frame's record), macroblocks in raster order:
+ *     parts[MBs]      MB_parts of vp8hip_results: 0 = 16x16, 1 = 8x8
+ *     ref[MBs]        MB_reference_frame: 0 LAST, 1 GOLDEN, 2 ALTREF
+ *     vec[MBs][4][2]  MB_vectors: the four 8x8 blocks TL, TR, BL, BR, each {x, y} in quarter pixels, int16
+ *     nz[MBs]         the non-zero-coefficient counts vp8hip_prepare_filter_mask returns (MB_non_zero_coeffs)
+ *     seg[MBs]        MB_segment_id, 0..3 (only the low two bits are looked at)
+ *     is_inter[MBs]   the flags vp8hip_download_intra returns, 0 where check_SSIM's fallback replaced the macroblock by an intra one.
+ *                     They count only for an inter frame on which check_SSIM ran AND reported replaced > 0; otherwise (no check, or
+ *                     nothing replaced: the fallback then leaves the array stale) every macroblock of an inter frame is inter.
+ * A macroblock is INTRA in a key frame, and in an inter frame where is_inter counts and is 0; otherwise it is INTER.
+ *     mbs_total       MBs
+ *     mbs_intra       intra macroblocks (all of a key frame)
+ *     mbs_ref[r]      inter macroblocks with ref == r, r = 0, 1, 2 (an inter macroblock with another value is counted in none)
+ *     mbs_split       inter macroblocks with parts == 1
+ *     mbs_zero_mv     inter macroblocks whose eight vector components are all 0
+ *     mv_abs_sum[k]   sum of |vec[mb][b][k]| over b = 0..3 of every inter macroblock, k = 0 (x), 1 (y), whatever parts says; uint64
+ *     mv_sum[k]       the same sum without the absolute value; int64
+ *     mv_sq_sum       sum of x * x + y * y over the same vectors; uint64
+ *     nz_coeffs       sum of nz over ALL macroblocks; uint64
+ *     mbs_no_coeffs   macroblocks (all of them) with nz == 0
+ *     segment_mbs[s]  macroblocks (all of them) with (seg & 3) == s
+ * so mbs_intra + mbs_ref[0] + mbs_ref[1] + mbs_ref[2] = mbs_total = the sum of segment_mbs; in a key frame the five inter fields
+ * and mbs_ref are 0. */
+typedef struct {
+    uint64_t spatial, temporal_sse, temporal_sad;
+    int32_t static_mbs, have_prev;
+} vp8host_luma_analysis;
+int vp8host_analyse_luma(const uint8_t *cur, const uint8_t *prev_or_null, int width, int height, vp8host_luma_analysis *out);
+
 /* frames.skip_prob, loop_filter.h:37-44 */
 int vp8host_skip_prob(const int32_t *MB_non_zero_coeffs, int mb_count);
 

@@ -65,6 +65,7 @@ def main():
     ap.add_argument("--resize-filter", choices=("area", "lanczos"), default="area")
     ap.add_argument("--source-format", default="", metavar="NAME", help="the format of the frames of --yuv (or of --y4m, instead of its C tag: nv12 and p010 have none): i420, nv12, i422, i444, p010, i010, i210, i410; converted on the device (vp8drv_set_source_format)")
     ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
+    ap.add_argument("--analysis", default="", metavar="FILE", help="the frame analysis record of every frame as one text line per frame (vp8drv_set_analysis; the line: scripts/native/y4m_to_ivf.cpp): a first-pass file")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dist = None
@@ -100,8 +101,23 @@ def main():
             enc.drv.set_denoise(a.denoise)
         if fmt:
             enc.drv.set_source_format(fmt)
+        if a.analysis:      # every frame's record next to its bytes (the line needs both)
+            enc.drv.set_analysis(True)
+            plain = enc.encode
+
+            def encode(y, u, v):
+                b = plain(y, u, v)
+                records.append(enc.drv.frame_analysis().text_line(len(b)).split(" ", 1)[1])      # (the frame number is the file's, not the chunk's)
+                return b
+            enc.encode = encode
         return enc
+    records = []
+    if a.analysis and world > 1:
+        sys.exit("--analysis: one process only (the records are not gathered over ranks)")
     mine = gop_shard.encode_chunks_frames(make_encoder, seq, gop_shard.chunks_of_rank(frames, a.gop, rank, world))
+    if a.analysis:
+        with open(a.analysis, "w") as f:
+            f.write("".join(f"{t} {line}\n" for t, line in enumerate(records)))
     allf = gop_shard.gather_frames(mine, frames, dist)
     if rank == 0:
         n = gop_shard.write_ivf(a.out, allf, Wd, Hd, a.framerate)

@@ -22,6 +22,7 @@ ap.add_argument("--scale-from", default="", metavar="WxH", help="the frames come
 ap.add_argument("--scale-filter", choices=("area", "lanczos"), default="area")
 ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of every frame taken in (vp8drv_set_denoise): what k_denoise_b costs")
 ap.add_argument("--source-format", default="", metavar="NAME", help="the device-resident frames are this format's planes (nv12, p010, i444, ...: vp8drv_set_source_format): what k_convert_b costs")
+ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the frame analysis record of every frame (vp8drv_set_analysis): what k_analyse_src_b and k_analyse_mb_b cost")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -56,6 +57,9 @@ if a.denoise:
 if fmt:
     for d in drvs:
         d.set_source_format(fmt)
+if a.analysis:
+    for d in drvs:
+        d.set_analysis(True)
 sizes = [0] * a.streams
 
 def work(k, n, emit):
@@ -112,4 +116,7 @@ if a.streams == 1:   # the input side by HIP events: the pack launch, with k_con
 if a.quality_stats:
     q = drvs[0].quality_summary()
     print(f"quality of stream 0 over {q.frames} frames: PSNR overall {q.psnr_all:.3f} dB, avg {q.psnr_avg:.3f} dB, SSIM {q.ssim_all:.5f}")
+if a.analysis:
+    r = drvs[0].frame_analysis().as_dict()
+    print(f"analysis of stream 0, frame {r['frame_number']}: " + ", ".join(f"{k} {v}" for k, v in r.items() if k != "frame_number"))
 for d in drvs: d.close()

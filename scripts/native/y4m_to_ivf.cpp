@@ -2,7 +2,12 @@
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
-//              [-input-format NAME]
+//              [-input-format NAME] [-analysis FILE]
+// -analysis FILE: the frame analysis record of every frame (vp8drv_set_analysis; the rules: include/vp8hip_host.h) as one text line per
+// frame, the first-pass file a caller's second pass reads.  Decimal integers separated by single spaces, in this order:
+//   frame_number is_key bytes have_prev static_mbs spatial temporal_sse temporal_sad coded mbs_total mbs_intra mbs_split mbs_zero_mv
+//   mbs_no_coeffs mbs_ref[0..2] segment_mbs[0..3] mv_abs_sum[0..1] mv_sum[0..1] mv_sq_sum nz_coeffs
+// (bytes = the size of the coded frame in the IVF file; the .ivf is the one written without the option).
 // The format of the frames is the header's C tag (vp8host_y4m_colourspace): C420* files are I420, C422, C444, C420p10, C422p10 and
 // C444p10 files are converted on the device (vp8drv_set_source_format), any other colourspace is refused.  -input-format NAME (i420,
 // nv12, i422, i444, p010, i010, i210, i410) says it instead of the tag: for frames the header cannot describe (NV12, P010).
@@ -38,6 +43,7 @@ int main(int argc, char **argv) {
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     int denoise = 0;         // -denoise
     int32_t format = -1;     // -input-format (-1: the header's C tag)
+    const char *analysis_path = nullptr;      // -analysis
     static const char *const format_names[VP8HOST_FORMAT_COUNT] = {"i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"};
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
@@ -54,6 +60,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-psnr")) cfg.quality_stats = 1;               // PSNR / SSIM summary on stderr
         else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
+        else if (!strcmp(argv[i], "-analysis")) analysis_path = val();
         else if (!strcmp(argv[i], "-input-format")) {
             const char *f = val();
             for (int k = 0; k < VP8HOST_FORMAT_COUNT; ++k)
@@ -103,6 +110,13 @@ int main(int argc, char **argv) {
     if (denoise) CK(vp8drv_set_denoise(drv, denoise));
     if (format) CK(vp8drv_set_source_format(drv, format));
     long long dn_filtered = 0, dn_total = 0;
+    FILE *analysis = nullptr;
+    vp8drv_analysis an{};      // the record of the frame whose bytes are still to be taken
+    if (analysis_path) {
+        CK(vp8drv_set_analysis(drv, 1));
+        analysis = fopen(analysis_path, "w");
+        if (!analysis) { perror(analysis_path); return 1; }
+    }
     FILE *out = fopen(argv[2], "wb");
     if (!out) { perror(argv[2]); return 1; }
     uint8_t fh[32];
@@ -204,6 +218,13 @@ int main(int argc, char **argv) {
             fwrite(ph, 1, vp8bs_ivf_frame_header(ph, (uint32_t)size, n), out);
             fwrite(bytes.data(), 1, size, out);
             total += 12 + size;
+            if (analysis)
+                fprintf(analysis, "%d %d %zu %d %d %llu %llu %llu %d %d %d %d %d %d %d %d %d %d %d %d %d %llu %llu %lld %lld %llu %llu\n", an.frame_number,
+                        an.is_key, size, an.have_prev, an.static_mbs, (unsigned long long)an.spatial, (unsigned long long)an.temporal_sse,
+                        (unsigned long long)an.temporal_sad, an.coded, an.mbs_total, an.mbs_intra, an.mbs_split, an.mbs_zero_mv, an.mbs_no_coeffs,
+                        an.mbs_ref[0], an.mbs_ref[1], an.mbs_ref[2], an.segment_mbs[0], an.segment_mbs[1], an.segment_mbs[2], an.segment_mbs[3],
+                        (unsigned long long)an.mv_abs_sum[0], (unsigned long long)an.mv_abs_sum[1], (long long)an.mv_sum[0], (long long)an.mv_sum[1],
+                        (unsigned long long)an.mv_sq_sum, (unsigned long long)an.nz_coeffs);
             ++n;
             pending = false;
         }
@@ -213,6 +234,7 @@ int main(int argc, char **argv) {
         CK(key);
         keys += key;
         pending = true;
+        if (analysis) CK(vp8drv_get_frame_analysis(drv, &an));      // (the frame's type is final; before the next frame is handed over)
         if (peek(false) == 1) {     // the next frame, early: current on the device, its scene scan under way, the one after it on its way
             const uint8_t *p[3];
             planes(rd_tail, p);
@@ -228,6 +250,7 @@ int main(int argc, char **argv) {
     fwrite(fh, 1, vp8bs_ivf_file_header(fh, Wd, Hd, (uint32_t)(fps ? fps : 30), 1, n + 1), out);
     fclose(out);
     fclose(in);
+    if (analysis) fclose(analysis);
     vp8drv_stats st;
     vp8drv_get_stats(drv, &st);
     if (cfg.quality_stats) {   // vpxenc --psnr's summary, measured on the device (vp8drv_config.quality_stats)

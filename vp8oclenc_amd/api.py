@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -484,6 +484,63 @@ class DenoiseStats(C.Structure):
     _fields_ = [("frame_number", C.c_int32), ("mbs_filtered", C.c_int32), ("mbs_total", C.c_int32)]
 
 
+class Analysis(C.Structure):
+    """vp8hip_analysis, include/vp8hip.h: the frame analysis record of a context with vp8hip_set_analysis (every field an exact integer;
+    the rules: include/vp8hip_host.h)"""
+    _fields_ = [("frame_number", C.c_int32), ("is_key", C.c_int32), ("have_prev", C.c_int32), ("static_mbs", C.c_int32),
+                ("spatial", C.c_uint64), ("temporal_sse", C.c_uint64), ("temporal_sad", C.c_uint64),
+                ("coded", C.c_int32), ("mbs_total", C.c_int32), ("mbs_intra", C.c_int32), ("mbs_split", C.c_int32),
+                ("mbs_zero_mv", C.c_int32), ("mbs_no_coeffs", C.c_int32), ("mbs_ref", C.c_int32 * 3), ("segment_mbs", C.c_int32 * 4),
+                ("reserved", C.c_int32), ("mv_abs_sum", C.c_uint64 * 2), ("mv_sum", C.c_int64 * 2), ("mv_sq_sum", C.c_uint64),
+                ("nz_coeffs", C.c_uint64)]
+
+    SOURCE_FIELDS = ("have_prev", "static_mbs", "spatial", "temporal_sse", "temporal_sad")
+    CODING_FIELDS = ("mbs_total", "mbs_intra", "mbs_split", "mbs_zero_mv", "mbs_no_coeffs", "mbs_ref", "segment_mbs", "mv_abs_sum", "mv_sum",
+                     "mv_sq_sum", "nz_coeffs")
+
+    def as_dict(self) -> dict:
+        """every field but `reserved` as Python ints (arrays as lists)"""
+        out = {}
+        for name, _ in self._fields_:
+            if name != "reserved":
+                v = getattr(self, name)
+                out[name] = int(v) if isinstance(v, int) else [int(x) for x in v]
+        return out
+
+    def text_line(self, nbytes: int) -> str:
+        """the line the tools' -analysis / --analysis files carry for this frame: frame number, key flag, bytes, then every field in
+        the struct's order, arrays element by element, separated by single spaces"""
+        d = self.as_dict()
+        vals = [d["frame_number"], d["is_key"], int(nbytes)]
+        for name, _ in self._fields_[2:]:
+            if name != "reserved":
+                v = d[name]
+                vals += v if isinstance(v, list) else [v]
+        return " ".join(str(x) for x in vals)
+
+
+class LumaAnalysis(C.Structure):
+    """vp8host_luma_analysis, include/vp8hip_host.h"""
+    _fields_ = [("spatial", C.c_uint64), ("temporal_sse", C.c_uint64), ("temporal_sad", C.c_uint64), ("static_mbs", C.c_int32),
+                ("have_prev", C.c_int32)]
+
+
+def analyse_luma(cur, prev=None) -> dict:
+    """vp8host_analyse_luma: the source side of the analysis record in plain C++ on tight luma planes of the coded size"""
+    lib = load_library()
+    lib.vp8host_analyse_luma.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(LumaAnalysis)]
+    cur = np.ascontiguousarray(cur, np.uint8)
+    h, w = cur.shape
+    if prev is not None:
+        prev = np.ascontiguousarray(prev, np.uint8)
+        if prev.shape != cur.shape:
+            raise ValueError("analyse_luma: prev has another shape than cur")
+    r = LumaAnalysis()
+    if lib.vp8host_analyse_luma(cur.ctypes.data, prev.ctypes.data if prev is not None else None, w, h, C.byref(r)) != 0:
+        raise ValueError(f"vp8host_analyse_luma({w}x{h}) refused")
+    return {k: int(getattr(r, k)) for k, _ in LumaAnalysis._fields_}
+
+
 DENOISE_SUM_Y, DENOISE_SAD_Y, DENOISE_SUM_C = 512, 2560, 128   # VP8HOST_DENOISE_*, include/vp8hip_host.h
 
 
@@ -750,6 +807,38 @@ class NativeDriver:
         if rc != 0:
             raise Vp8HipError(f"vp8drv_get_denoise_stats: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
         return s
+
+    def set_analysis(self, on: bool = True) -> None:
+        """vp8drv_set_analysis: the frame analysis record of every frame from the next one taken in on"""
+        self.lib.vp8drv_set_analysis.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.vp8drv_set_analysis(self.h, int(on))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_analysis({on}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def frame_analysis(self) -> Analysis:
+        """vp8drv_get_frame_analysis: the record of the frame just made final (its verdict is taken first)"""
+        a = Analysis()
+        self.lib.vp8drv_get_frame_analysis.argtypes = [C.c_void_p, C.POINTER(Analysis)]
+        rc = self.lib.vp8drv_get_frame_analysis(self.h, C.byref(a))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_frame_analysis: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return a
+
+    def set_quantizer(self, qi_min: int, qi_max: int) -> None:
+        """vp8drv_set_quantizer: both quantizer ladders made again from this pair, from the next frame coded on"""
+        self.lib.vp8drv_set_quantizer.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.lib.vp8drv_set_quantizer(self.h, int(qi_min), int(qi_max))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_quantizer({qi_min}, {qi_max}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def quantizer(self):
+        """vp8drv_get_quantizer: (qi_min, qi_max) in force"""
+        a, b = C.c_int32(), C.c_int32()
+        self.lib.vp8drv_get_quantizer.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        rc = self.lib.vp8drv_get_quantizer(self.h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_quantizer: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return a.value, b.value
 
     def quality_summary(self) -> QualitySummary:
         """vp8drv_get_quality_summary: over every frame made final so far"""
@@ -1095,6 +1184,23 @@ class Vp8Hip:
         self.lib.vp8hip_denoise_result.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
         self._chk(self.lib.vp8hip_denoise_result(self.h, C.byref(s)), "denoise_result")
         return s
+
+    def set_analysis(self, on: bool = True):
+        """vp8hip_set_analysis: every frame taken in and every coding attempt is measured (include/vp8hip.h); on from off starts
+        without a history"""
+        self.lib.vp8hip_set_analysis.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.vp8hip_set_analysis(self.h, int(bool(on))), "set_analysis")
+
+    def analysis_restart(self):
+        """vp8hip_analysis_restart: the next frame taken in has no history (have_prev = 0)"""
+        self.lib.vp8hip_analysis_restart.argtypes = [C.c_void_p]
+        self._chk(self.lib.vp8hip_analysis_restart(self.h), "analysis_restart")
+
+    def analysis_result(self) -> "Analysis":
+        a = Analysis()
+        self.lib.vp8hip_analysis_result.argtypes = [C.c_void_p, C.POINTER(Analysis)]
+        self._chk(self.lib.vp8hip_analysis_result(self.h, C.byref(a)), "analysis_result")
+        return a
 
     def set_quality_stats(self, on: bool = True):
         """vp8hip_set_quality_stats: PSNR / SSIM of every filtered frame against its source, on the device (on from off: a new summary)"""

@@ -285,6 +285,15 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         }
         launch_denoise_batch(ps, dn, nd, c0->dn_level);
     }
+    if (c0->an_on) {   // vp8hip_set_analysis: the members' source sides in one launch behind the denoiser
+        AnalysisSrcItem an[MAX_BATCH];
+        int na = 0;
+        for (int i = 0; i < b->n; ++i) {
+            if (active && !active[i]) continue;
+            if (analysis_src_item(b->c[i], ps, an[na])) ++na;
+        }
+        launch_analyse_src_batch(ps, an, na);
+    }
     HIPCHK(c0, hipGetLastError());
     if (host) {
         HIPCHK(c0, hipEventRecord(b->ev_packed[slot], ps));
@@ -487,7 +496,7 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
         Timed t(c0, VP8HIP_K_MB);
         launch_mb_batch(s, cur, refs, nets, recon, outs, sds, c0->ssim_target, c0->mbw, c0->mbh, n, c0->conformant != 0);
     }
-    for (int i = 0; i < n; ++i) m[i]->recon_ready = true, m[i]->recon_key = false;
+    for (int i = 0; i < n; ++i) m[i]->recon_ready = true, m[i]->recon_key = false, m[i]->an_checked = false;
     HIPCHK(c0, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -546,6 +555,7 @@ int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active) {
         c->recon_ready = false;
     }
     HIPCHK(c0, hipGetLastError());
+    batch_analysis(b, active);         // (vp8hip_set_analysis: the members' coding sides, one launch behind the filter)
     return batch_quality(b, active);   // (the members with stats on: one launch behind the filter)
 }
 

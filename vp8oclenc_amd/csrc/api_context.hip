@@ -545,6 +545,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     if (c->h_verdict) hipHostFree(c->h_verdict);
     if (c->h_quality) hipHostFree(c->h_quality);
     if (c->h_dn) hipHostFree(c->h_dn);
+    if (c->h_an) hipHostFree(c->h_an);
+    hipFree(c->d_an);
     hipFree(c->d_dn);
     hipFree(c->d_quality);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -613,6 +615,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->ev_stage_read[slot], c->stream));
         denoise_current(c);
+        analysis_current(c);
         c->stage_read_valid[slot] = true;
         HIPCHK(c, hipEventSynchronize(c->ev_h2d));      // the host's planes are the host's again when this returns (done long ago, normally)
         return VP8HIP_OK;
@@ -622,6 +625,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
     int rc = take_current(c, y, u, v, hipMemcpyHostToDevice);
     if (rc) return rc;
     denoise_current(c);
+    analysis_current(c);
     // pageable host memory: the call must not return while the copy still reads the host buffer
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VP8HIP_OK;
@@ -634,6 +638,7 @@ int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const
     const int rc = take_current(c, y, u, v, hipMemcpyDeviceToDevice);
     if (rc) return rc;
     denoise_current(c);      // (vp8hip_set_denoise: right behind the pack, before anything else reads the frame)
+    analysis_current(c);     // (vp8hip_set_analysis: the frame as the searches will read it)
     return VP8HIP_OK;
 }
 

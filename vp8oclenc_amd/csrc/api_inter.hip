@@ -117,6 +117,7 @@ void check_item(vp8hip_ctx *c, CheckItem &it, const int32_t refqi[4], int qi_min
     it.gen = ++c->intra_gen;
     c->ent_counted_partitions = 0;
     c->chk_armed = true;
+    c->an_checked = true;
     for (int k = 0; k < 4; ++k) c->chk_refqi[k] = refqi[k];
     c->chk_qi_min = qi_min;
 }
@@ -205,6 +206,7 @@ int vp8hip_inter_transform(vp8hip_ctx *c, int prev_is_golden, int prev_is_altref
     }
     c->recon_ready = true;
     c->recon_key = false;
+    c->an_checked = false;
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -238,6 +240,7 @@ int vp8hip_inter_finish(vp8hip_ctx *c, int use_golden, int use_altref) {
     }
     c->recon_ready = true;
     c->recon_key = false;
+    c->an_checked = false;
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -275,6 +278,7 @@ int vp8hip_check_ssim(vp8hip_ctx *c, int32_t *replaced, float *new_ssim, float *
                      ++c->intra_gen, c->d_progress + LF_ERR_WORD, c->ssim_target, 0, c->mbw, c->mbh, c->lf_stall_test, c->conformant);
     }
     launch_ssim_stats(c->stream, c->out, c->intra_is_inter, c->mbs, c->d_progress + LF_ERR_WORD, c->intra_stats);
+    c->an_checked = true;
     HIPCHK(c, hipGetLastError());
     int32_t st[4];
     HIPCHK(c, hipMemcpyAsync(st, c->intra_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
@@ -397,6 +401,7 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
         if (!by_verdict) HIPCHK(c, hipEventRecord(c->ev_fork, chain));
         launch_loop_filter_of_type(c, chain, f, &chk);
         c->lf_key = c->recon_key;
+        analysis_after_filter(c, chain);
         quality_after_filter(c, f, chain);   // (behind the filter on its stream: whatever overwrites this source is ordered behind it)
         c->verdict_stream = chain;
         if (!by_verdict) HIPCHK(c, hipStreamWaitEvent(c->lf_stream, c->ev_fork, 0));   // the side work starts where the filter starts
@@ -411,6 +416,7 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
             launch_loop_filter_of_type(c, c->stream, f, &chk);
         }
         c->lf_key = c->recon_key;
+        analysis_after_filter(c, c->stream);
         quality_after_filter(c, f, c->stream);
         c->verdict_stream = c->stream;
     }

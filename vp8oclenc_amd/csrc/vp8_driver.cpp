@@ -31,6 +31,7 @@ struct vp8drv {
     bool staged_scan = false;
     int denoise = 0;                 // vp8drv_set_denoise: the level in force
     int format = 0;                  // vp8drv_set_source_format: the format in force
+    bool analysis = false;           // vp8drv_set_analysis
     bool in_batch = false;           // a member of a live vp8drv_batch
     // read-back buffers of vp8drv_get_frame
     std::vector<int32_t> seg, nz, ref, parts, is_inter, modes;
@@ -301,7 +302,12 @@ vp8hip_header_params header_params(const vp8drv *d) {
 // vp8drv_set_denoise: the history restarts where the GOP schedule starts a GOP -- the frame about to be taken in is a scheduled key
 // frame -- so that a closed GOP coded as a chunk of its own sees the frames the serial program sees.  force_key, scene cuts and
 // frames sent back by check_SSIM are not the schedule's.
-int denoise_intake(vp8drv *d, bool scheduled_key) {
+// vp8drv_set_analysis: its history restarts at the same frames, for the same reason.
+int intake_restarts(vp8drv *d, bool scheduled_key) {
+    if (d->analysis && scheduled_key) {
+        const int rc = vp8hip_analysis_restart(d->hip);
+        if (rc != VP8HIP_OK) return rc;
+    }
     if (d->denoise && scheduled_key) return vp8hip_denoise_restart(d->hip);
     return VP8HIP_OK;
 }
@@ -386,7 +392,7 @@ int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const vo
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
     { const int rc = resolve(d); if (rc < 0) return rc; }                        // the previous frame's check_SSIM verdict, if still open
     vp8host_gop_next(&d->gop);
-    DRV_CHK(denoise_intake(d, d->gop.current_is_key != 0));
+    DRV_CHK(intake_restarts(d, d->gop.current_is_key != 0));
     DRV_CHK(vp8hip_set_current_device(d->hip, y, u, v));                          // vp8enc.cpp:386-388
     return frame_body(d, nullptr, d->gop.current_is_key || force_key);
 }
@@ -399,7 +405,7 @@ int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, cons
     d->staged = nullptr;
     if (!staged) {
         d->staged_scan = false;
-        DRV_CHK(denoise_intake(d, d->gop.current_is_key != 0));      // (a prefetched frame is packed, and denoised, in this upload)
+        DRV_CHK(intake_restarts(d, d->gop.current_is_key != 0));      // (a prefetched frame is packed, and denoised, in this upload)
         DRV_CHK(vp8hip_upload_current(d->hip, y, u, v));
     }
     return frame_body(d, y, d->gop.current_is_key || force_key);
@@ -414,10 +420,10 @@ int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, cons
 int vp8drv_stage_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
     { const int rc = resolve(d); if (rc < 0) return rc; }
-    if (d->denoise) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
+    if (d->denoise || d->analysis) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
         vp8host_gop g = d->gop;
         vp8host_gop_next(&g);
-        DRV_CHK(denoise_intake(d, g.current_is_key != 0));
+        DRV_CHK(intake_restarts(d, g.current_is_key != 0));
     }
     DRV_CHK(vp8hip_upload_current(d->hip, y, u, v));
     d->staged = y;
@@ -452,7 +458,8 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
-            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format)
+            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format ||
+            drv[i]->analysis != drv[0]->analysis)
             return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
     }
@@ -498,7 +505,7 @@ static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *c
         key[i] = d->gop.current_is_key || (force_key && force_key[i]);
         active[i] = !key[i];
         if (was_key) was_key[i] = key[i];
-        DRV_CHK(denoise_intake(d, d->gop.current_is_key != 0));
+        DRV_CHK(intake_restarts(d, d->gop.current_is_key != 0));
     }
     if (host) DRV_CHK(vp8hip_batch_upload_current(b->hb, members, reinterpret_cast<const uint8_t *const *>(y), reinterpret_cast<const uint8_t *const *>(u),
                                                   reinterpret_cast<const uint8_t *const *>(v)));
@@ -633,6 +640,42 @@ int vp8drv_set_source_format(vp8drv *d, int format) {
     d->format = format;
     d->staged = nullptr;             // planes staged in the other format are not this format's frame
     d->staged_scan = false;
+    return VP8HIP_OK;
+}
+
+int vp8drv_set_analysis(vp8drv *d, int on) {
+    if (!d || (on != 0 && on != 1) || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_analysis(d->hip, on));
+    d->analysis = on != 0;
+    return VP8HIP_OK;
+}
+
+// the record of the frame just made final: its verdict first (a frame coded again as a key frame has the key frame's coding side)
+int vp8drv_get_frame_analysis(vp8drv *d, vp8drv_analysis *a) {
+    if (!d || !a) return VP8HIP_ERR_ARG;
+    if (!d->analysis || !d->have_frame) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    return vp8hip_analysis_result(d->hip, a);
+}
+
+// the two ladders and qi_min as vp8drv_create makes them, from the next frame coded on (every frame takes its quantizers from them)
+int vp8drv_set_quantizer(vp8drv *d, int qi_min, int qi_max) {
+    if (!d || qi_min < 0 || qi_min > 127 || qi_max < 0 || qi_max > 127) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }      // (a frame sent back is coded again with the pair it was coded with)
+    d->cfg.qi_min = qi_min;
+    d->cfg.qi_max = qi_max;
+    vp8host_quantizer_ladders(qi_min, qi_max, d->lastqi, d->altrefqi);
+    d->qi_min = qi_min < qi_max ? qi_min : qi_max;
+    return VP8HIP_OK;
+}
+
+int vp8drv_get_quantizer(const vp8drv *d, int32_t *qi_min, int32_t *qi_max) {
+    if (!d || !qi_min || !qi_max) return VP8HIP_ERR_ARG;
+    *qi_min = d->cfg.qi_min;
+    *qi_max = d->cfg.qi_max;
     return VP8HIP_OK;
 }
 

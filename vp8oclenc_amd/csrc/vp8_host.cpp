@@ -503,3 +503,33 @@ extern "C" int vp8host_denoise_frame(const uint8_t *src_y, const uint8_t *src_u,
     }
     return 0;
 }
+
+// The source side of the frame analysis record in plain C++ (include/vp8hip_host.h has the rule).
+extern "C" int vp8host_analyse_luma(const uint8_t *cur, const uint8_t *prev, int width, int height, vp8host_luma_analysis *out) {
+    if (!cur || !out || width < 16 || height < 16 || (width & 15) || (height & 15)) return -1;
+    vp8host_luma_analysis r{};
+    r.have_prev = prev ? 1 : 0;
+    for (int my = 0; my < height / 16; ++my)
+        for (int mx = 0; mx < width / 16; ++mx) {
+            const size_t o = (size_t)my * 16 * (size_t)width + (size_t)mx * 16;
+            uint64_t s = 0, ss = 0, sad = 0, sse = 0;
+            for (int y = 0; y < 16; ++y)
+                for (int x = 0; x < 16; ++x) {
+                    const size_t i = o + (size_t)y * (size_t)width + (size_t)x;
+                    const int v = cur[i];
+                    s += (uint64_t)v;
+                    ss += (uint64_t)(v * v);
+                    if (prev) {
+                        const int d = v - (int)prev[i];
+                        sad += (uint64_t)(d < 0 ? -d : d);
+                        sse += (uint64_t)(d * d);
+                    }
+                }
+            r.spatial += 256u * ss - s * s;
+            r.temporal_sse += sse;
+            r.temporal_sad += sad;
+            if (prev && sad == 0) r.static_mbs++;
+        }
+    *out = r;
+    return 0;
+}

@@ -132,6 +132,16 @@ struct vp8hip_ctx {
     vp8::DenoiseMirror dn_passed{};
     uint32_t dn_seq = 0;
     hipStream_t dn_stream = nullptr;
+    // vp8hip_set_analysis: the history plane (the luma of the previous frame taken in, tight, coded size), the five sum / ticket words of
+    // k_analyse_src_b, the record's host mirror; the launches so far per part (each writes its number into its part's seq last) and the
+    // frame each part was last launched for.  an_checked: check_SSIM ran on the reconstruction in flight (its verdict's device copy says
+    // whether the fallback's flags count).
+    bool an_on = false, an_have_prev = false, an_checked = false;
+    uint8_t *d_an = nullptr;
+    vp8::AnalysisMirror *h_an = nullptr;
+    uint32_t an_src_seq = 0, an_mb_seq = 0, an_src_want[2] = {0, 0};
+    int an_src_frame[2] = {-1, -1}, an_mb_frame = -1;
+    hipStream_t an_src_stream[2] = {nullptr, nullptr}, an_mb_stream = nullptr;
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out
     // vp8hip_set_quality_stats: the state, the per-wave partials and the ticket of k_quality (one allocation), the state's host mirror
@@ -328,7 +338,8 @@ inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) {
 }
 inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched convert / pack / scale launch takes as one value
     return a->src_fmt == b->src_fmt && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
-           (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level;      // (and one denoiser level)
+           (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level &&     // (and one denoiser level)
+           a->an_on == b->an_on;                                                                    // (analysis on for all or for none)
 }
 // vp8hip_set_source_format: the staging buffers at the context's incoming size (no-op for I420 or when they are large enough), and the
 // item of k_convert_b for planes in DEVICE memory: afterwards y, u, v are the I420 planes in fmt_stage.  false: I420, nothing to do.
@@ -377,6 +388,15 @@ int prof_collect(vp8hip_ctx *c);
 // is the history from now on); denoise_current: the launch for one context.
 bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it);
 void denoise_current(vp8hip_ctx *c);
+// ---- api_analysis.hip ----
+// The source side: the frame just taken into c->cur, behind its pack / scale / denoise launches on stream s (every way a frame becomes
+// current calls one of these).  The coding side: the attempt whose loop filter was just launched on s (c->lf_key says which kind).
+// *_item: false = analysis off, nothing to launch.
+bool analysis_src_item(vp8hip_ctx *c, hipStream_t s, AnalysisSrcItem &it);
+void analysis_current(vp8hip_ctx *c);
+bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it);
+void analysis_after_filter(vp8hip_ctx *c, hipStream_t s);
+void batch_analysis(vp8hip_batch *b, const int *active);
 // ---- api_quality.hip ----
 bool quality_item(vp8hip_ctx *c, const Frame &rec, hipStream_t s, QualityArgs &a);   // false: stats off
 void quality_after_filter(vp8hip_ctx *c, const Frame &rec, hipStream_t s);           // the measurement behind the context's filter

@@ -157,6 +157,29 @@ void launch_scale_batch(hipStream_t s, const Frame *const *f, const void *const 
 struct DenoiseMirror { int32_t frame_number, mbs_filtered, mbs_total; uint32_t seq; };
 struct DenoiseItem { Frame cur, hist; unsigned long long *word; DenoiseMirror *host; uint32_t seq; int32_t frame_number; };
 void launch_denoise_batch(hipStream_t s, const DenoiseItem *items, int n, int level);
+// kernels_analysis.hip: the frame analysis record (vp8hip_set_analysis); both rules are include/vp8hip_host.h's.
+// k_analyse_src_b: the coded luma of the frame just taken in against `hist`, a tight plane of w x h bytes that the same launch then
+// overwrites with the luma; have_prev 0: measures `spatial` and copies only.  `acc` (five 64-bit words, zero at rest) takes the
+// workgroups' sums and tickets; the workgroup with the last ticket writes the record into `host`, seq last.
+// k_analyse_mb_b: one workgroup per frame over the per-macroblock arrays; `replaced` = the device copy of check_SSIM's verdict (word 0:
+// macroblocks replaced) when the check ran on this attempt, else nullptr (is_inter is then not read).
+struct AnalysisSrcMirror { uint64_t spatial, sse, sad; int32_t static_mbs, have_prev, frame_number; uint32_t seq; };
+struct AnalysisMbMirror {
+    int32_t frame_number, is_key, mbs_total, mbs_intra, mbs_split, mbs_zero_mv, mbs_no_coeffs, mbs_ref[3], segment_mbs[4];
+    uint64_t mv_abs_sum[2]; int64_t mv_sum[2]; uint64_t mv_sq_sum, nz_coeffs;
+    uint32_t seq;
+};
+struct AnalysisMirror { AnalysisSrcMirror src[2]; AnalysisMbMirror mb; };      // src[frame_number & 1]: a frame handed over early keeps the last one's
+struct AnalysisSrcItem { Plane cur; uint8_t *hist; unsigned long long *acc; AnalysisSrcMirror *host; uint32_t seq; int32_t frame_number, have_prev; };
+struct AnalysisMbItem {
+    const int32_t *parts, *ref, *seg, *nz, *is_inter, *replaced;
+    const int16_t *vec;
+    AnalysisMbMirror *host;
+    uint32_t seq;
+    int32_t frame_number, is_key, mbs;
+};
+void launch_analyse_src_batch(hipStream_t s, const AnalysisSrcItem *items, int n);
+void launch_analyse_mb_batch(hipStream_t s, const AnalysisMbItem *items, int n);
 // kernels_convert.hip: source frames in another format than 8-bit I420 (vp8hip_set_source_format), made tight 8-bit I420 of the same
 // size IN FRONT of the pack or scale launch, which then reads dst as if the caller had handed it in; the rule is include/vp8hip_host.h's.
 // src: the format's planes (src[2] is not read for the two-plane formats).  Format 0 launches nothing.
