@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "vp8hip_dev.h"
+#include "s1_pre_layout.h"
 
 namespace vp8 {
 
@@ -314,8 +315,12 @@ __device__ __forceinline__ void s1_subblock_pre(v4i wa, const int *pre_lds, int 
         acc[i] += weight_mfma(wa, load_pre16(pre_lds + off), b);
     }
 }
-// ... made by the wave for its twelve blocks: lane = (block slot, sub-block), 48 of the 64 lanes; 16 ints each into pre_lds[slot][sub-block][16]
-constexpr int S1_PRE_INTS = 12 * 4 * 16;
+// ... made by the wave for its twelve blocks: lane = (block slot, sub-block), 48 of the 64 lanes; 16 ints each into pre_lds[slot][sub-block][16].
+// A block slot is S1_PRE_SLOT = 68 ints apart from the next, not 64 (s1_pre_layout.h): in a C read the lanes of a wave differ only in their block slot,
+// and slots a whole bank row apart put the five or six blocks of a lane group of the ds_read_b128 on the same four banks.  Checked here with the
+// address the kernels index by: every C read of the table costs the LDS the four cycles of a conflict-free read.
+static_assert(s1_pre_c_read_worst() == 4 && s1_pre_c_read_best() == 4, "the C reads of the whole-pel search's pre table must be free of LDS bank conflicts");
+static_assert(S1_PRE_BLOCKS == S1Map<false>::BLOCKS_PER_WAVE, "s1_pre_layout.h and the loop form's lane map disagree");
 __device__ __forceinline__ void s1_make_pre(const Plane &cur, int cx, int cy, int sb, bool on, int *dst16) {
     const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;      // the order of the cost loop: (0,0), (0,+4 rows), (+4 cols,0), (+4,+4)
     const uint8_t *cp = cur.p + (ptrdiff_t)(cy + sy) * cur.stride + cx + sx;
@@ -372,7 +377,7 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
 #pragma unroll 1
             for (int sb = 0; sb < 4; ++sb) {
                 const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;
-                s1_subblock_pre(wa, pre_lds, pre_off + 16 * sb, rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
+                s1_subblock_pre(wa, pre_lds, pre_off + s1_pre_sub_at(sb), rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
             }
         } else {
 #pragma unroll 1
@@ -445,10 +450,10 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
         const int tb_raw = (xcd_band(blockIdx.x, gridDim.x) * 4 + wave) * M::BLOCKS_PER_WAVE + slot;
         const int tb = tb_raw < a.nblk ? tb_raw : a.nblk - 1;
         const int tby = a.bw == 1 ? tb : (int)__umulhi((uint32_t)tb, a.bw_inv), tbx = tb - tby * a.bw;
-        s1_make_pre(a.cur, tbx * 8, tby * 8, sb, slot < M::BLOCKS_PER_WAVE, &s_pre[wave][(slot < M::BLOCKS_PER_WAVE ? slot : 0) * 64 + sb * 16]);
+        s1_make_pre(a.cur, tbx * 8, tby * 8, sb, slot < M::BLOCKS_PER_WAVE, &s_pre[0][0] + s1_pre_slot_at(wave, slot) + s1_pre_sub_at(sb));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         pre_lds = &s_pre[0][0];
-        pre_off = wave * S1_PRE_INTS + (grp < M::BLOCKS_PER_WAVE ? grp : 0) * 64;
+        pre_off = s1_pre_c_at(wave, lane, 0, 0);     // this lane's block slot; the sub-block (s1_pre_sub_at) and the quad (load_pre16) are added per read
     }
     const int nr = REF_LOOP ? a.nrefs : 1;
 #pragma unroll 1
