@@ -218,6 +218,18 @@ int vp8hip_set_source_scaling(vp8hip_ctx *ctx, int in_width, int in_height, int 
  * call.  Reference planes (vp8hip_upload_last, vp8hip_set_last_device, vp8hip_upload_recon, downloads) stay 8-bit I420 of the coded
  * size.  All members of a batch must agree on the format (vp8hip_batch_create and the batched launch check it). */
 int vp8hip_set_source_format(vp8hip_ctx *ctx, int format);
+/* The packed family of the same enum, numbers 16 .. 19 (8 .. 15 are refused): YUY2 and UYVY, a capture card's packed 4:2:2, and BGRA
+ * and RGBA, a renderer's or a screen capture's 32-bit surface.  ONE plane: the second and third pointers of every call above are never
+ * read (they must still not be null: pass the first again).  The same single launch in front of the pack or scale launch
+ * (k_convert_packed_b), the same staging buffer, the same composition with the source size, the scaler and the denoiser; a
+ * vp8hip_prefetch_current stages the plane's 2 w h or 4 w h bytes.  YUY2 / UYVY follow the I422 rule.  BGRA / RGBA are read with the
+ * colour matrix of vp8hip_set_source_colour: matrix = one of enum vp8host_colour_matrix: BT.601 or BT.709, limited or full range (the
+ * integer tables and the rule are in include/vp8hip_host.h, vp8host_convert_frame_colour is the rule in plain C++), 0 = BT.601 limited,
+ * the default.  The matrix is stored with the context and read by the RGB formats only, so it may be set before or after the format,
+ * and with any other format it changes no byte.  Waits for the context's streams: not a per-frame call.  A pending
+ * vp8hip_prefetch_current made under another matrix is dropped.  Anything but 0 .. 3: VP8HIP_ERR_ARG and nothing has changed.  All
+ * members of a batch must agree on the matrix as on the format. */
+int vp8hip_set_source_colour(vp8hip_ctx *ctx, int matrix);
 /* Temporal noise reduction of the source frames, the third stage of the input side (libvpx: --noise-sensitivity); the reference never
  * did anything about noise.  level 1, 2, 3: every frame that becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the
  * pack out of a vp8hip_prefetch_current staging buffer, vp8hip_batch_set_current_device, vp8hip_batch_upload_current, with or without a
@@ -464,6 +476,8 @@ const char *vp8hip_status_string(int status);
  * vp8drv_get_denoise_stats (entry points only: vp8drv_config is unchanged);
  * also under 4010: source formats (vp8hip_set_source_format, vp8drv_set_source_format, vp8host_source_plane_bytes, vp8host_convert_frame,
  * vp8host_y4m_colourspace; entry points only: vp8drv_config is unchanged);
+ * also under 4010: the packed source formats YUY2, UYVY, BGRA, RGBA and their colour matrix (vp8hip_set_source_colour,
+ * vp8drv_set_source_colour, vp8host_convert_frame_colour, vp8host_colour_coefficients; entry points only);
  * also under 4010: frame analysis (vp8hip_set_analysis, vp8hip_analysis_restart, vp8hip_analysis_result, vp8host_analyse_luma,
  * vp8drv_set_analysis, vp8drv_get_frame_analysis) and vp8drv_set_quantizer / vp8drv_get_quantizer (entry points only). */
 #define VP8HIP_ABI_VERSION 4010

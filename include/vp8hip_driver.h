@@ -236,6 +236,11 @@ int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s);
  * mirror reads the caller's luma plane as 8-bit samples).  VP8HIP_ERR_STATE: the driver is a member of a live batch (the members
  * must agree: set the format before vp8drv_batch_create, which refuses members that differ). */
 int vp8drv_set_source_format(vp8drv *d, int format);
+/* The colour matrix BGRA / RGBA source frames are read with (vp8hip_set_source_colour; enum vp8host_colour_matrix and the tables:
+ * include/vp8hip_host.h), 0 = BT.601 limited range, the default.  The rules of vp8drv_set_source_format: between frames, in any order
+ * relative to the format; VP8HIP_ERR_ARG: not one of the four matrices, or cfg.device_params = 0; VP8HIP_ERR_STATE: the driver is a
+ * member of a live batch (vp8drv_batch_create refuses members that differ). */
+int vp8drv_set_source_colour(vp8drv *d, int matrix);
 /* ---- what a rate controller needs: a record to measure with and a quantizer to set -------------------------------------------
  * Frame analysis statistics (vp8hip_set_analysis; the rules: include/vp8hip_host.h), entry points and not a field for the reason
  * vp8drv_set_denoise is one.  on = 0 (default) or 1; it takes the open check_SSIM verdict first.  VP8HIP_ERR_ARG: another value, or

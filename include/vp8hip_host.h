@@ -100,20 +100,61 @@ int vp8host_denoise_frame(const uint8_t *src_y, const uint8_t *src_u, const uint
  *     out = min(255, (S + (1 << (k - 1))) >> k)        (out = S when k is 0),        k = log2(n) + d - 8,
  * where S is the sum of the n source samples the output sample covers: n = 1 for luma and for the chroma of the 4:2:0 formats; n = 2,
  * the two vertically adjacent samples (rows 2r and 2r + 1), for the chroma of 4:2:2; n = 4, the 2x2 block, for the chroma of 4:4:4.
- * One rounding step, never two; chroma siting is not modelled; no colour matrix.  The clamp matters at ten bits only: 1023 gives
- * (1023 + 2) >> 2 = 256.  The low six bits of a P010 word and the high six of the other 16-bit formats' words are ignored. */
+ * One rounding step, never two; chroma siting is not modelled; no colour matrix for these eight (the planar family, numbers below
+ * VP8HOST_FORMAT_COUNT).  The clamp matters at ten bits only: 1023 gives (1023 + 2) >> 2 = 256.  The low six bits of a P010 word and
+ * the high six of the other 16-bit formats' words are ignored.
+ *
+ * THE PACKED FAMILY, numbers VP8HOST_FORMAT_PACKED_FIRST .. VP8HOST_FORMAT_PACKED_END - 1 (8 .. 15 are no format and are refused
+ * everywhere): ONE plane, tight, 8-bit, width and height even.  The second and third pointers are never read.
+ *     YUY2 (16)  per pixel pair the four bytes Y0 U Y1 V        2 w h bytes      (k_convert_packed_b)
+ *     UYVY (17)  per pixel pair the four bytes U Y0 V Y1        2 w h bytes
+ *     BGRA (18)  per pixel the four bytes B G R A               4 w h bytes      (A never influences anything)
+ *     RGBA (19)  per pixel the four bytes R G B A               4 w h bytes
+ * YUY2 / UYVY are the I422 rule on the samples they carry: luma is copied, chroma is (c[2r][x] + c[2r + 1][x] + 1) >> 1, so a YUY2
+ * frame converts to exactly what the I422 frame holding the same samples converts to.
+ * BGRA / RGBA take a colour matrix m (enum vp8host_colour_matrix; vp8hip_set_source_colour): an offset and nine coefficients, times 256,
+ * in the order R, G, B:
+ *     m                   off    Y             U               V
+ *     0 BT601_LIMITED     16     66 129  25    -38  -74 112    112  -94 -18        (the default)
+ *     1 BT709_LIMITED     16     47 157  16    -26  -86 112    112 -102 -10
+ *     2 BT601_FULL         0     77 150  29    -43  -84 127    127 -106 -21
+ *     3 BT709_FULL         0     54 183  19    -29  -98 127    127 -116 -11
+ *     Y = off + ((cR R + cG G + cB B + 128) >> 8)                       per pixel, with the Y row
+ *     U = (S + 131072 + 512) >> 10                                      S = the sum of cR R + cG G + cB B, with the U row, over the four
+ *     V = the same with the V row                                           pixels of the 2x2 block
+ * One rounding step on the summed block, never two; >> is the arithmetic shift of a number that is never negative here.  No clamp is
+ * needed and none is applied.  What the tables guarantee (tests/test_packed_format_cpu.py asserts each): luma rows sum to 220 (limited)
+ * and 256 (full), so R = G = B = v gives Y = v at the full matrices; every chroma row sums to 0, so grey gives exactly 128; over the
+ * RGB cube limited output stays in [16, 235] / [16, 240] and full output in [0, 255] / [1, 255]; S + 131584 is never negative.  The
+ * distance from the floating-point BT.601 / BT.709 definition, measured on 100 000 random pixels, is about 1.6 (full, where 0.5 is
+ * carried as 127 / 256) and about 1.1 (limited); the test bounds it by 2.  Every chroma coefficient fits a signed byte and every luma coefficient an unsigned byte -- the device forms the sums with
+ * byte dot products -- so keep both properties and the sums if a coefficient is ever changed.  No gamma, no primaries, no siting. */
 typedef enum {
     VP8HOST_FORMAT_I420 = 0, VP8HOST_FORMAT_NV12 = 1, VP8HOST_FORMAT_I422 = 2, VP8HOST_FORMAT_I444 = 3,
     VP8HOST_FORMAT_P010 = 4, VP8HOST_FORMAT_I010 = 5, VP8HOST_FORMAT_I210 = 6, VP8HOST_FORMAT_I410 = 7,
-    VP8HOST_FORMAT_COUNT = 8
+    VP8HOST_FORMAT_COUNT = 8,      /* the planar family ends here */
+    VP8HOST_FORMAT_PACKED_FIRST = 16,
+    VP8HOST_FORMAT_YUY2 = 16, VP8HOST_FORMAT_UYVY = 17, VP8HOST_FORMAT_BGRA = 18, VP8HOST_FORMAT_RGBA = 19,
+    VP8HOST_FORMAT_PACKED_END = 20
 } vp8host_source_format;
-/* bytes of the planes a frame of width x height hands in (bytes[2] is 0 for the two-plane formats).  0, or -1: unknown format, a
- * size that is odd or not positive */
+typedef enum {
+    VP8HOST_COLOUR_BT601_LIMITED = 0, VP8HOST_COLOUR_BT709_LIMITED = 1, VP8HOST_COLOUR_BT601_FULL = 2, VP8HOST_COLOUR_BT709_FULL = 3,
+    VP8HOST_COLOUR_COUNT = 4
+} vp8host_colour_matrix;
+/* bytes of the planes a frame of width x height hands in (bytes[2] is 0 for the two-plane formats, bytes[1] and bytes[2] for the
+ * packed ones).  0, or -1: unknown format, a size that is odd or not positive */
 int vp8host_source_plane_bytes(int format, int width, int height, size_t bytes[3]);
-/* the rule as plain C++: p0, p1, p2 = the format's planes (p2 is not read for NV12 / P010), y, u, v = tight I420 of width x height.
+/* the rule as plain C++: p0, p1, p2 = the format's planes (p2 is not read for NV12 / P010, p1 and p2 are not read -- and may be null
+ * -- for the packed formats, which take matrix 0), y, u, v = tight I420 of width x height.
  * 0, or -1 for what vp8host_source_plane_bytes refuses or a null pointer. */
 int vp8host_convert_frame(int format, int width, int height, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2,
                           uint8_t *y, uint8_t *u, uint8_t *v);
+/* the same with the colour matrix BGRA / RGBA are read with (the other formats check it and do not use it).  -1 also for a matrix
+ * that is none of the four */
+int vp8host_convert_frame_colour(int format, int matrix, int width, int height, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2,
+                                 uint8_t *y, uint8_t *u, uint8_t *v);
+/* the table above: c = the Y, U and V rows one after the other, each in the order R, G, B.  0, or -1: unknown matrix, null pointer */
+int vp8host_colour_coefficients(int matrix, int32_t c[9], int32_t *y_offset);
 /* The C tag of a YUV4MPEG2 header (which vp8host_y4m_parse_header, the reference's parser, never looks at): the header line is the
  * bytes up to the first line feed, its tags are separated by spaces, the first tag that starts with C counts.  No C tag, C420,
  * C420jpeg, C420mpeg2, C420paldv: I420; C422: I422; C444: I444; C420p10: I010; C422p10: I210; C444p10: I410.  Returns 0 and the

@@ -7,7 +7,8 @@
 --y4m: YUV4MPEG2, the reference's own input format (size, frame rate and -- from the C tag -- the format of the frames from its header,
 vp8oclenc_amd/y4m.py: C422, C444, C420p10, C422p10 and C444p10 files are converted on the device, vp8drv_set_source_format; other
 colourspaces are refused); --yuv: raw frames of the given size, I420 or --source-format NAME (nv12, i422, i444, p010, i010, i210,
-i410); without either the synthetic sequence of the tests is used.  A raw I420 file has the given width/height (even numbers); when
+i410, or the packed yuy2, uyvy, bgra, rgba; the RGB ones are read with --source-matrix bt601|bt709 and --source-range limited|full,
+vp8drv_set_source_colour); without either the synthetic sequence of the tests is used.  A raw I420 file has the given width/height (even numbers); when
 they are not multiples of 16 the frames are padded on the device (vp8hip_set_source_size = copy_with_padding, encIO.h:141-196)
 and the key frames carry the source size as display size."""
 import argparse, os, sys, time
@@ -31,7 +32,7 @@ class YuvFile:
     def planes(self, t):
         b = self.m[t * self.fsz:(t + 1) * self.fsz]
         n0, n1, n2 = self.plane_bytes
-        return [np.ascontiguousarray(p) for p in (b[:n0], b[n0:n0 + n1], b[n0 + n1:])[:3 if n2 else 2]]
+        return [np.ascontiguousarray(p) for p in (b[:n0], b[n0:n0 + n1], b[n0 + n1:])[:3 if n2 else 2 if n1 else 1]]
 
     def frame(self, t):
         b = self.m[t * self.fsz:(t + 1) * self.fsz]
@@ -42,14 +43,14 @@ class YuvFile:
 
 class FormatPlanes:
     """frame(t) of a file in another format than I420: the three pointers vp8drv_set_source_format expects (the second plane again for
-    the two-plane formats)"""
+    the two-plane formats, the only plane again for the packed ones)"""
 
     def __init__(self, seq):
         self.seq, self.W, self.H, self.n = seq, seq.W, seq.H, seq.n
 
     def frame(self, t):
         p = self.seq.planes(t)
-        return p + [p[1]] * (3 - len(p))
+        return p + [p[-1]] * (3 - len(p))
 
 
 def main():
@@ -63,7 +64,9 @@ def main():
     ap.add_argument("--conformant", action="store_true", help="vp8hip_conformant_stream: NOT the reference byte for byte, but a stream that decodes to the encoder's own reconstruction")
     ap.add_argument("--resize", default="", metavar="WxH", help="code the picture at this size: the frames are scaled down on the device (vp8hip_set_source_scaling)")
     ap.add_argument("--resize-filter", choices=("area", "lanczos"), default="area")
-    ap.add_argument("--source-format", default="", metavar="NAME", help="the format of the frames of --yuv (or of --y4m, instead of its C tag: nv12 and p010 have none): i420, nv12, i422, i444, p010, i010, i210, i410; converted on the device (vp8drv_set_source_format)")
+    ap.add_argument("--source-format", default="", metavar="NAME", help="the format of the frames of --yuv (or of --y4m, instead of its C tag: nv12 and p010 have none): i420, nv12, i422, i444, p010, i010, i210, i410, and for --yuv the packed yuy2, uyvy, bgra, rgba; converted on the device (vp8drv_set_source_format)")
+    ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", help="the colour matrix bgra / rgba frames are read with (vp8drv_set_source_colour)")
+    ap.add_argument("--source-range", choices=("limited", "full"), default="limited", help="... and the range of the YUV it makes")
     ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
     ap.add_argument("--analysis", default="", metavar="FILE", help="the frame analysis record of every frame as one text line per frame (vp8drv_set_analysis; the line: scripts/native/y4m_to_ivf.cpp): a first-pass file")
     a = ap.parse_args()
@@ -75,6 +78,8 @@ def main():
     from vp8oclenc_amd import api
     try:
         fmt = api.source_format(a.source_format) if a.source_format else None
+        if a.y4m and fmt is not None and fmt >= api.FORMAT_YUY2:
+            raise ValueError(f"a YUV4MPEG2 frame is planar: {a.source_format} goes with --yuv")
         if a.y4m:
             from vp8oclenc_amd.y4m import Y4mFile
             seq = Y4mFile(a.y4m, fmt)      # (without --source-format: the file's C tag, and ValueError for one the encoder cannot take)
@@ -101,6 +106,7 @@ def main():
             enc.drv.set_denoise(a.denoise)
         if fmt:
             enc.drv.set_source_format(fmt)
+            enc.drv.set_source_colour(a.source_matrix, a.source_range)
         if a.analysis:      # every frame's record next to its bytes (the line needs both)
             enc.drv.set_analysis(True)
             plain = enc.encode

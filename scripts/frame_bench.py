@@ -21,7 +21,9 @@ ap.add_argument("--quality-stats", type=int, choices=(0, 1), default=0, help="1 
 ap.add_argument("--scale-from", default="", metavar="WxH", help="the frames come in at this size and are scaled down to --width x --height on the device (vp8drv_config.in_width / in_height)")
 ap.add_argument("--scale-filter", choices=("area", "lanczos"), default="area")
 ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of every frame taken in (vp8drv_set_denoise): what k_denoise_b costs")
-ap.add_argument("--source-format", default="", metavar="NAME", help="the device-resident frames are this format's planes (nv12, p010, i444, ...: vp8drv_set_source_format): what k_convert_b costs")
+ap.add_argument("--source-format", default="", metavar="NAME", help="the device-resident frames are this format's planes (nv12, p010, i444, ..., or the packed yuy2, uyvy, bgra, rgba: vp8drv_set_source_format): what k_convert_b / k_convert_packed_b costs")
+ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", help="the colour matrix bgra / rgba frames are read with (vp8drv_set_source_colour)")
+ap.add_argument("--source-range", choices=("limited", "full"), default="limited")
 ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the frame analysis record of every frame (vp8drv_set_analysis): what k_analyse_src_b and k_analyse_mb_b cost")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
@@ -43,10 +45,22 @@ if a.scale_from:      # the same coded size, every frame through k_scale_b inste
     host = [[np.ascontiguousarray(p[:in_h >> (i > 0), :in_w >> (i > 0)]) for i, p in enumerate(seq.frame(t))] for t in range(nd)]
 else:
     host = [list(seq.frame(t)) for t in range(nd)]
+def rgb_near_i420(fmt, y, u, v):
+    """a BGRA or RGBA frame (one flat uint8 plane, alpha 255) that looks like this I420 frame: the floating-point inverse of BT.601
+    limited range, chroma replicated, clipped.  Not exact -- no RGB frame carries an arbitrary I420 frame -- so the coded bytes change"""
+    Y = np.asarray(y, np.float32) - 16.0
+    U, V = (np.repeat(np.repeat(np.asarray(p, np.float32) - 128.0, 2, axis=0), 2, axis=1) for p in (u, v))
+    r, g, b = 1.164 * Y + 1.596 * V, 1.164 * Y - 0.392 * U - 0.813 * V, 1.164 * Y + 2.017 * U
+    chans = (b, g, r) if fmt == api.FORMAT_BGRA else (r, g, b)
+    px = np.stack([np.clip(np.rint(c), 0, 255).astype(np.uint8) for c in chans] + [np.full(Y.shape, 255, np.uint8)], axis=-1)
+    return [np.ascontiguousarray(px).ravel()]
+
+
 fmt = api.source_format(a.source_format) if a.source_format else 0
 if fmt:      # the same frames carried by the format's planes (chroma replicated, samples shifted up): the coded bytes do not change
-    host = [api.planes_from_i420(fmt, *f) for f in host]
-    host = [f + [f[1]] * (3 - len(f)) for f in host]      # (the two-plane formats: the second pointer again)
+    rgb = fmt in (api.FORMAT_BGRA, api.FORMAT_RGBA)      # (RGB: a picture close to the frame, not the frame: the coded bytes do change)
+    host = [rgb_near_i420(fmt, *f) if rgb else api.planes_from_i420(fmt, *f) for f in host]
+    host = [f + [f[-1]] * (3 - len(f)) for f in host]      # (the two-plane formats: the second pointer again; the packed ones: the first)
 dev = [tuple(api.to_device(p) for p in f) for f in host]
 api.device_synchronize()
 drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
@@ -57,6 +71,7 @@ if a.denoise:
 if fmt:
     for d in drvs:
         d.set_source_format(fmt)
+        d.set_source_colour(a.source_matrix, a.source_range)
 if a.analysis:
     for d in drvs:
         d.set_analysis(True)

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -567,15 +567,52 @@ def denoise_frame(src, hist, level: int, have_history: bool):
 # vp8host_source_format, include/vp8hip_host.h: what the three pointers of a source frame are (vp8hip_set_source_format)
 FORMAT_I420, FORMAT_NV12, FORMAT_I422, FORMAT_I444, FORMAT_P010, FORMAT_I010, FORMAT_I210, FORMAT_I410 = range(8)
 FORMAT_NAMES = ["i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"]
+# the packed family (one plane; 8 .. 15 are no format)
+FORMAT_YUY2, FORMAT_UYVY, FORMAT_BGRA, FORMAT_RGBA = range(16, 20)
+PACKED_FORMAT_NAMES = {"yuy2": FORMAT_YUY2, "uyvy": FORMAT_UYVY, "bgra": FORMAT_BGRA, "rgba": FORMAT_RGBA}
+# vp8host_colour_matrix: what BGRA / RGBA are read with (vp8hip_set_source_colour)
+COLOUR_BT601_LIMITED, COLOUR_BT709_LIMITED, COLOUR_BT601_FULL, COLOUR_BT709_FULL = range(4)
+COLOUR_MATRIX_NAMES = ["bt601", "bt709"]
+COLOUR_RANGE_NAMES = ["limited", "full"]
 
 
 def source_format(name) -> int:
     """a format's number from its name (any case) or number; ValueError for what vp8hip_set_source_format would refuse"""
     if isinstance(name, str) and name.lower() in FORMAT_NAMES:
         return FORMAT_NAMES.index(name.lower())
-    if isinstance(name, (int, np.integer)) and 0 <= int(name) < len(FORMAT_NAMES):
+    if isinstance(name, str) and name.lower() in PACKED_FORMAT_NAMES:
+        return PACKED_FORMAT_NAMES[name.lower()]
+    if isinstance(name, (int, np.integer)) and (0 <= int(name) < len(FORMAT_NAMES) or int(name) in PACKED_FORMAT_NAMES.values()):
         return int(name)
-    raise ValueError(f"unknown source format {name!r}: one of {', '.join(FORMAT_NAMES)}")
+    raise ValueError(f"unknown source format {name!r}: one of {', '.join(FORMAT_NAMES + list(PACKED_FORMAT_NAMES))}")
+
+
+def source_format_name(fmt: int) -> str:
+    fmt = source_format(fmt)
+    return FORMAT_NAMES[fmt] if fmt < len(FORMAT_NAMES) else {v: k for k, v in PACKED_FORMAT_NAMES.items()}[fmt]
+
+
+def source_colour(matrix="bt601", range_="limited") -> int:
+    """a colour matrix's number from a matrix name (bt601, bt709) and a range (limited, full), or from its number; ValueError for
+    what vp8hip_set_source_colour would refuse"""
+    if isinstance(matrix, (int, np.integer)) and not isinstance(matrix, bool):
+        if 0 <= int(matrix) < 4:
+            return int(matrix)
+        raise ValueError(f"unknown colour matrix {matrix!r}: 0 .. 3")
+    m, r = str(matrix).lower(), str(range_).lower()
+    if m not in COLOUR_MATRIX_NAMES or r not in COLOUR_RANGE_NAMES:
+        raise ValueError(f"unknown colour matrix {matrix!r} / range {range_!r}: one of {', '.join(COLOUR_MATRIX_NAMES)} and one of {', '.join(COLOUR_RANGE_NAMES)}")
+    return COLOUR_MATRIX_NAMES.index(m) + 2 * COLOUR_RANGE_NAMES.index(r)
+
+
+def colour_coefficients(matrix: int):
+    """vp8host_colour_coefficients: (the Y, U and V rows as a 3x3 int32 array, columns R, G, B; the luma offset)"""
+    lib = load_library()
+    lib.vp8host_colour_coefficients.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    c, off = (C.c_int32 * 9)(), C.c_int32(0)
+    if lib.vp8host_colour_coefficients(int(matrix), c, C.byref(off)) != 0:
+        raise ValueError(f"vp8host_colour_coefficients({matrix}) refused")
+    return np.array(list(c), np.int32).reshape(3, 3), off.value
 
 
 def source_plane_bytes(fmt: int, width: int, height: int):
@@ -588,22 +625,28 @@ def source_plane_bytes(fmt: int, width: int, height: int):
     return [int(x) for x in b]
 
 
-def convert_frame(fmt: int, width: int, height: int, planes):
-    """vp8host_convert_frame: the device's format conversion in plain C++.  planes = the format's two or three planes as contiguous
-    arrays of exactly vp8host_source_plane_bytes bytes each (uint8, or uint16 for the 16-bit formats on a little-endian host)
-    -> (Y, U, V) uint8 arrays, I420 of width x height"""
+def convert_frame(fmt: int, width: int, height: int, planes, matrix: int = 0):
+    """vp8host_convert_frame / vp8host_convert_frame_colour: the device's format conversion in plain C++.  planes = the format's
+    one, two or three planes as contiguous arrays of exactly vp8host_source_plane_bytes bytes each (uint8, or uint16 for the 16-bit
+    formats on a little-endian host); matrix = the colour matrix BGRA / RGBA are read with -> (Y, U, V) uint8 arrays, I420 of
+    width x height"""
     lib = load_library()
     lib.vp8host_convert_frame.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+    lib.vp8host_convert_frame_colour.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
     need = source_plane_bytes(fmt, width, height)
     planes = [np.ascontiguousarray(p) for p in planes]
-    if len(planes) == 2:
-        planes.append(planes[1])
+    while len(planes) < 3:
+        planes.append(planes[-1])
     for p, n in zip(planes, need):
         if n and p.nbytes != n:
             raise ValueError(f"convert_frame: a plane of {p.nbytes} bytes where format {fmt} at {width}x{height} has {n}")
     out = (np.empty((height, width), np.uint8), np.empty((height // 2, width // 2), np.uint8), np.empty((height // 2, width // 2), np.uint8))
-    if lib.vp8host_convert_frame(int(fmt), int(width), int(height), *[p.ctypes.data for p in planes], *[o.ctypes.data for o in out]) != 0:
-        raise ValueError(f"vp8host_convert_frame(format {fmt}, {width}x{height}) refused")
+    if matrix:
+        rc = lib.vp8host_convert_frame_colour(int(fmt), int(matrix), int(width), int(height), *[p.ctypes.data for p in planes], *[o.ctypes.data for o in out])
+    else:
+        rc = lib.vp8host_convert_frame(int(fmt), int(width), int(height), *[p.ctypes.data for p in planes], *[o.ctypes.data for o in out])
+    if rc != 0:
+        raise ValueError(f"vp8host_convert_frame(format {fmt}, matrix {matrix}, {width}x{height}) refused")
     return out
 
 
@@ -611,6 +654,16 @@ def planes_from_i420(fmt: int, y, u, v):
     """the planes of format `fmt` that carry this 8-bit I420 frame exactly -- chroma replicated, samples shifted up to the depth --
     as flat uint8 arrays: vp8host_convert_frame returns the frame from them (for tools and benchmarks that need frames in a format)"""
     fmt = source_format(fmt)
+    if fmt in (FORMAT_YUY2, FORMAT_UYVY):      # the I422 frame's samples, interleaved
+        yy = np.ascontiguousarray(y, np.uint8)
+        h, w = yy.shape
+        cu, cv = (np.repeat(np.asarray(p, np.uint8), 2, axis=0) for p in (u, v))
+        q = np.empty((h, w // 2, 4), np.uint8)
+        ly, lu = (0, 1) if fmt == FORMAT_YUY2 else (1, 0)
+        q[:, :, ly], q[:, :, ly + 2], q[:, :, lu], q[:, :, lu + 2] = yy[:, 0::2], yy[:, 1::2], cu, cv
+        return [q.ravel()]
+    if fmt in (FORMAT_BGRA, FORMAT_RGBA):
+        raise ValueError("planes_from_i420: no RGB frame carries an arbitrary I420 frame exactly")
     nv, tall, wide, deep = fmt in (FORMAT_NV12, FORMAT_P010), fmt in (FORMAT_I422, FORMAT_I444, FORMAT_I210, FORMAT_I410), \
         fmt in (FORMAT_I444, FORMAT_I410), fmt >= FORMAT_P010
     shift = 0 if not deep else (8 if fmt == FORMAT_P010 else 2)
@@ -790,6 +843,14 @@ class NativeDriver:
         rc = self.lib.vp8drv_set_denoise(self.h, int(level))
         if rc != 0:
             raise Vp8HipError(f"vp8drv_set_denoise({level}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_source_colour(self, matrix, range_="limited") -> None:
+        """vp8drv_set_source_colour: BGRA / RGBA frames are read with this matrix (a COLOUR_* number, or bt601 / bt709 and a range)"""
+        self.lib.vp8drv_set_source_colour.argtypes = [C.c_void_p, C.c_int]
+        m = source_colour(matrix, range_) if isinstance(matrix, str) else int(matrix)
+        rc = self.lib.vp8drv_set_source_colour(self.h, m)
+        if rc < 0:
+            raise Vp8HipError(f"vp8drv_set_source_colour({m}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_source_format(self, fmt) -> None:
         """vp8drv_set_source_format: the frames handed in from now on are this format's planes (a FORMAT_* number or its name)"""
@@ -1158,6 +1219,14 @@ class Vp8Hip:
         self._chk(self.lib.vp8hip_set_source_scaling(self.h, int(in_width), int(in_height), int(dst_width), int(dst_height), int(filter)),
                   "set_source_scaling")
         self.src = (int(in_width), int(in_height))
+
+    def set_source_colour(self, matrix, range_="limited"):
+        """vp8hip_set_source_colour: BGRA / RGBA frames are read with this matrix (a COLOUR_* number, or bt601 / bt709 and a range)"""
+        self.lib.vp8hip_set_source_colour.argtypes = [C.c_void_p, C.c_int]
+        m = source_colour(matrix, range_) if isinstance(matrix, str) else int(matrix)
+        rc = self.lib.vp8hip_set_source_colour(self.h, m)
+        if rc < 0:
+            raise Vp8HipError(f"set_source_colour({m}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_source_format(self, fmt):
         """vp8hip_set_source_format: current frames come in this format (a FORMAT_* number or its name) and k_convert_b makes 8-bit

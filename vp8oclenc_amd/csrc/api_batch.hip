@@ -148,7 +148,7 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
 static int stage_copy(vp8hip_batch *b, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3]) {
     vp8hip_ctx *c0 = b->c[0];
     const uint8_t *py = static_cast<const uint8_t *>(y);
-    if (u == py + nb[0] && (!nb[2] || v == py + nb[0] + nb[1])) {
+    if (!nb[1] || (u == py + nb[0] && (!nb[2] || v == py + nb[0] + nb[1]))) {      // (one plane, or planes end to end)
         HIPCHK(c0, hipMemcpyAsync(d, y, nb[0] + nb[1] + nb[2], hipMemcpyHostToDevice, b->copy));
         return VP8HIP_OK;
     }
@@ -269,7 +269,7 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         int sw, sh;
         incoming_size(c0, &sw, &sh);
         Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
-        launch_convert_batch(ps, c0->src_fmt, sw, sh, cv, n);
+        if (!launch_convert_batch(ps, c0->src_fmt, c0->src_colour, sw, sh, cv, n)) return VP8HIP_ERR_ARG;
     }
     {
         Timed t(c0, VP8HIP_K_PACK);

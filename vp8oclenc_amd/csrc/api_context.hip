@@ -180,7 +180,7 @@ int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hip
             }
             uint8_t *d = c->fmt_raw;
             HIPCHK(c, hipMemcpyAsync(d, y, nb[0], kind, c->stream));
-            HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], kind, c->stream));
+            if (nb[1]) HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], kind, c->stream));      // (the packed formats have one plane)
             if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], kind, c->stream));
             y = d; u = d + nb[0]; v = d + nb[0] + nb[1];
             kind = hipMemcpyDeviceToDevice;
@@ -190,7 +190,7 @@ int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hip
         ConvertItem it;
         convert_item(c, it, y, u, v);
         Timed t(c, VP8HIP_K_PACK);      // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
-        launch_convert_batch(c->stream, c->src_fmt, w, h, &it, 1);
+        if (!launch_convert_batch(c->stream, c->src_fmt, c->src_colour, w, h, &it, 1)) return VP8HIP_ERR_ARG;
     }
     return set_frame_planes(c, c->cur, y, u, v, kind, c->src_w, c->src_h, c->scale.in_w != 0);
 }
@@ -583,7 +583,7 @@ int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, c
     const int slot = c->h2d_idx ^ 1;
     if (c->stage_read_valid[slot]) HIPCHK(c, hipStreamWaitEvent(c->h2d_stream, c->ev_stage_read[slot], 0));
     uint8_t *d = c->h2d_stage[slot];
-    if (u == y + nb[0] && (!nb[2] || v == u + nb[1])) {
+    if (!nb[1] || (u == y + nb[0] && (!nb[2] || v == u + nb[1]))) {      // (one plane, or planes end to end)
         HIPCHK(c, hipMemcpyAsync(d, y, total, hipMemcpyHostToDevice, c->h2d_stream));
     } else {
         HIPCHK(c, hipMemcpyAsync(d, y, nb[0], hipMemcpyHostToDevice, c->h2d_stream));
@@ -703,13 +703,24 @@ int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int ds
 }
 
 int vp8hip_set_source_format(vp8hip_ctx *c, int format) {
-    if (!c || format < 0 || format >= VP8HOST_FORMAT_COUNT) return VP8HIP_ERR_ARG;
+    if (!c || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END)
+        return VP8HIP_ERR_ARG;
     if (format == c->src_fmt) return VP8HIP_OK;
     { const int rc = scale_quiesce(c); if (rc) return rc; }
     const int before = c->src_fmt;
     c->src_fmt = format;
     { const int rc = format_stage_ready(c); if (rc) { c->src_fmt = before; return rc; } }
     c->h2d_pre_valid = false;      // planes prefetched in another format are not this format's frame
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_source_colour(vp8hip_ctx *c, int matrix) {
+    if (!c || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT) return VP8HIP_ERR_ARG;
+    if (matrix == c->src_colour) return VP8HIP_OK;
+    { const int rc = scale_quiesce(c); if (rc) return rc; }
+    c->src_colour = matrix;
+    c->h2d_pre_valid = false;      // planes prefetched under another matrix are not this matrix's frame
+    if (c->batch) c->batch->pre_valid = false;
     return VP8HIP_OK;
 }
 

@@ -1,5 +1,6 @@
 // kernels_convert.hip -- source frames that are not tight 8-bit I420 (vp8hip_set_source_format): NV12, P010, 4:2:2, 4:4:4 and 10-bit
-// planar made 8-bit I420 of the same width and height, the first stage of the input side, in front of the pack (k_pack_b) or the
+// planar (k_convert_b, below) and the packed YUY2, UYVY, BGRA and RGBA (k_convert_packed_b, further down) made 8-bit I420 of the same
+// width and height, the first stage of the input side, in front of the pack (k_pack_b) or the
 // scaler (k_scale_b).  The reference reads I420 and nothing else; the rule is the project's own and is stated bit for bit in
 // include/vp8hip_host.h (vp8host_convert_frame is its plain C++ form): out = min(255, (S + (1 << (k - 1))) >> k) with S the sum of the
 // 1, 2 or 4 source samples an output sample covers and k = log2(n) + depth - 8.
@@ -187,18 +188,175 @@ template <int LAYOUT, int DEPTH> __device__ __forceinline__ void convert_body(co
     store16(out + x0, finish16<KC, DEPTH != 8>(s));
 }
 
+// ---- the packed family: YUY2, UYVY, BGRA, RGBA (one plane; the rule is include/vp8hip_host.h's) ---------------------------------------
+// Mapping (memory-bound again: every source byte is loaded ONCE, by the lane that needs it; no LDS):
+//   * a lane owns 16 pixels of TWO adjacent rows -- the rows of one chroma row -- loads both with 16-byte loads (4 per row for RGB, 2
+//     for 4:2:2) and stores 2 x 16 luma bytes and 8 + 8 chroma bytes;
+//   * RGB: luma is v_dot4_u32_u8 of the pixel's dword with the Y row as a dword of unsigned bytes (the alpha byte's coefficient is 0),
+//     the rounding 128 in the accumulator, the shift a byte permute (the sum fits 16 bits), the offset added to four packed bytes at
+//     once; chroma is v_dot4_i32_i8 of the pixel with its sign bits flipped (p - 128 as a signed byte) with the U or V row as signed
+//     bytes, the four pixels of a block chained through the accumulator, which starts at 131072 + 512 + 4 * 128 * (the row's sum: each
+//     of the four pixels is seen 128 too low; 0 for every table of the header).  BGRA and RGBA differ in where the host puts the coefficients in their dwords and in nothing else;
+//   * 4:2:2: luma is a byte permute, chroma the rounded-up byte average of the two rows' dwords, (a | b) - (((a ^ b) >> 1) & 0x7f7f7f7f),
+//     and two rounds of byte permutes; YUY2 and UYVY differ in the two selectors and in nothing else;
+//   * so the matrix and the byte order are kernel ARGUMENTS of a few dwords: two code objects, not sixteen;
+//   * edges as above: a row's last unit moves left, rows narrower than 16 pixels are walked pixel pair by pixel pair.
+struct PackedArgs {
+    int w, h, units_x, units;                 // units = units_x * h / 2
+    uint32_t cy, cu, cv;                      // RGB: the rows as bytes at the pixel's byte positions
+    uint32_t off4, bias_u, bias_v;            // the luma offset in all four bytes; the chroma accumulators' start
+    uint32_t sel_y, sel_c;                    // 4:2:2: the luma bytes of two dwords; (U, U, V, V) of two dwords
+    int shift_y, shift_u;                     // 4:2:2, the walk: bit positions of Y0 and U in a pair's dword (Y1 and V: 16 above)
+};
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x2 u32x2_u __attribute__((aligned(1)));
+typedef uint32_t u32_u __attribute__((aligned(1)));
+__device__ __forceinline__ void store8(uint8_t *p, uint32_t a, uint32_t b) { *reinterpret_cast<u32x2_u *>(p) = u32x2{a, b}; }
+__device__ __forceinline__ uint32_t load4(const uint8_t *p) { return *reinterpret_cast<const u32_u *>(p); }
+
+__device__ __forceinline__ uint32_t luma1(uint32_t px, const PackedArgs &g) { return __builtin_amdgcn_udot4(px, g.cy, 128u, false); }      // (Y - off) * 256 + fraction
+__device__ __forceinline__ int chroma1(uint32_t px, uint32_t c, int acc) { return __builtin_amdgcn_sdot4((int)(px ^ 0x80808080u), (int)c, acc, false); }
+
+// sixteen RGB pixels of one row -> sixteen luma bytes
+__device__ __forceinline__ uint4 rgb_luma16(const uint32_t p[16], const PackedArgs &g) {
+    uint32_t o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t lo = __builtin_amdgcn_perm(luma1(p[4 * i + 1], g), luma1(p[4 * i], g), 0x0c0c0501u);
+        const uint32_t hi = __builtin_amdgcn_perm(luma1(p[4 * i + 3], g), luma1(p[4 * i + 2], g), 0x0c0c0501u);
+        o[i] = __builtin_amdgcn_perm(hi, lo, 0x05040100u) + g.off4;      // (no byte carries: Y <= 255)
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <bool RGB> __device__ __forceinline__ void packed_body(const ConvertItem &it, const PackedArgs &g) {
+    constexpr int B = RGB ? 4 : 2;            // bytes per pixel
+    const int unit = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (unit >= g.units) return;
+    const int r = unit / g.units_x, ux = unit - r * g.units_x, cw = g.w >> 1;
+    const size_t pitch = (size_t)g.w * B;
+    const uint8_t *s0 = it.src[0] + (size_t)(2 * r) * pitch, *s1 = s0 + pitch;
+    uint8_t *y0 = it.dst[0] + (size_t)(2 * r) * g.w, *y1 = y0 + g.w;
+    uint8_t *ou = it.dst[1] + (size_t)r * cw, *ov = it.dst[2] + (size_t)r * cw;
+    if (g.w < 16) {
+        for (int x = 0; x < cw; ++x) {
+            if constexpr (RGB) {
+                const uint32_t a = load4(s0 + 8 * x), b = load4(s0 + 8 * x + 4), c = load4(s1 + 8 * x), d = load4(s1 + 8 * x + 4);
+                const uint32_t off = g.off4 & 255u;
+                y0[2 * x] = (uint8_t)((luma1(a, g) >> 8) + off);
+                y0[2 * x + 1] = (uint8_t)((luma1(b, g) >> 8) + off);
+                y1[2 * x] = (uint8_t)((luma1(c, g) >> 8) + off);
+                y1[2 * x + 1] = (uint8_t)((luma1(d, g) >> 8) + off);
+                ou[x] = (uint8_t)(chroma1(d, g.cu, chroma1(c, g.cu, chroma1(b, g.cu, chroma1(a, g.cu, (int)g.bias_u)))) >> 10);
+                ov[x] = (uint8_t)(chroma1(d, g.cv, chroma1(c, g.cv, chroma1(b, g.cv, chroma1(a, g.cv, (int)g.bias_v)))) >> 10);
+            } else {
+                const uint32_t a = load4(s0 + 4 * x), b = load4(s1 + 4 * x);
+                y0[2 * x] = (uint8_t)(a >> g.shift_y);
+                y0[2 * x + 1] = (uint8_t)(a >> (g.shift_y + 16));
+                y1[2 * x] = (uint8_t)(b >> g.shift_y);
+                y1[2 * x + 1] = (uint8_t)(b >> (g.shift_y + 16));
+                ou[x] = (uint8_t)((((a >> g.shift_u) & 255u) + ((b >> g.shift_u) & 255u) + 1u) >> 1);
+                ov[x] = (uint8_t)((((a >> (g.shift_u + 16)) & 255u) + ((b >> (g.shift_u + 16)) & 255u) + 1u) >> 1);
+            }
+        }
+        return;
+    }
+    const int x0 = min(ux * 16, g.w - 16);      // even: the widths are
+    s0 += (size_t)x0 * B;
+    s1 += (size_t)x0 * B;
+    if constexpr (RGB) {
+        uint32_t a[16], b[16];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint4 t = load16(s0 + 16 * i), q = load16(s1 + 16 * i);
+            a[4 * i] = t.x; a[4 * i + 1] = t.y; a[4 * i + 2] = t.z; a[4 * i + 3] = t.w;
+            b[4 * i] = q.x; b[4 * i + 1] = q.y; b[4 * i + 2] = q.z; b[4 * i + 3] = q.w;
+        }
+        store16(y0 + x0, rgb_luma16(a, g));
+        store16(y1 + x0, rgb_luma16(b, g));
+        uint32_t u[2] = {}, v[2] = {};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int su = chroma1(b[2 * i + 1], g.cu, chroma1(b[2 * i], g.cu, chroma1(a[2 * i + 1], g.cu, chroma1(a[2 * i], g.cu, (int)g.bias_u))));
+            const int sv = chroma1(b[2 * i + 1], g.cv, chroma1(b[2 * i], g.cv, chroma1(a[2 * i + 1], g.cv, chroma1(a[2 * i], g.cv, (int)g.bias_v))));
+            // (S + bias never negative and below 2^18: bits 10..17 are the byte)
+            u[i >> 2] |= (((uint32_t)su >> 10) & 255u) << (8 * (i & 3));
+            v[i >> 2] |= (((uint32_t)sv >> 10) & 255u) << (8 * (i & 3));
+        }
+        store8(ou + (x0 >> 1), u[0], u[1]);
+        store8(ov + (x0 >> 1), v[0], v[1]);
+    } else {
+        const uint4 t0 = load16(s0), t1 = load16(s0 + 16), q0 = load16(s1), q1 = load16(s1 + 16);
+        const uint32_t a[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w}, b[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+        store16(y0 + x0, make_uint4(__builtin_amdgcn_perm(a[1], a[0], g.sel_y), __builtin_amdgcn_perm(a[3], a[2], g.sel_y),
+                                    __builtin_amdgcn_perm(a[5], a[4], g.sel_y), __builtin_amdgcn_perm(a[7], a[6], g.sel_y)));
+        store16(y1 + x0, make_uint4(__builtin_amdgcn_perm(b[1], b[0], g.sel_y), __builtin_amdgcn_perm(b[3], b[2], g.sel_y),
+                                    __builtin_amdgcn_perm(b[5], b[4], g.sel_y), __builtin_amdgcn_perm(b[7], b[6], g.sel_y)));
+        uint32_t c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t m0 = (a[2 * i] | b[2 * i]) - (((a[2 * i] ^ b[2 * i]) >> 1) & 0x7f7f7f7fu);
+            const uint32_t m1 = (a[2 * i + 1] | b[2 * i + 1]) - (((a[2 * i + 1] ^ b[2 * i + 1]) >> 1) & 0x7f7f7f7fu);
+            c[i] = __builtin_amdgcn_perm(m1, m0, g.sel_c);      // U, U, V, V
+        }
+        store8(ou + (x0 >> 1), __builtin_amdgcn_perm(c[1], c[0], 0x05040100u), __builtin_amdgcn_perm(c[3], c[2], 0x05040100u));
+        store8(ov + (x0 >> 1), __builtin_amdgcn_perm(c[1], c[0], 0x07060302u), __builtin_amdgcn_perm(c[3], c[2], 0x07060302u));
+    }
+}
+
 }  // namespace convert
+
+static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::PackedArgs) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+template <bool RGB> __global__ __launch_bounds__(256) void k_convert_packed_b(BatchOf<ConvertItem> b, convert::PackedArgs g) {
+    convert::packed_body<RGB>(b.item[blockIdx.z], g);
+}
+
+static bool launch_convert_packed(hipStream_t s, int format, int matrix, int w, int h, const BatchOf<ConvertItem> &b) {
+    convert::PackedArgs g = {};
+    g.w = w; g.h = h;
+    g.units_x = w < 16 ? 1 : (w + 15) / 16;
+    g.units = g.units_x * (h / 2);
+    const bool rgb = format == VP8HOST_FORMAT_BGRA || format == VP8HOST_FORMAT_RGBA;
+    if (rgb) {
+        int32_t c[9], off;
+        if (vp8host_colour_coefficients(matrix, c, &off) != 0) return false;      // (vp8hip_set_source_colour refuses it: the caller fails the frame)
+        const int at[3] = {format == VP8HOST_FORMAT_BGRA ? 16 : 0, 8, format == VP8HOST_FORMAT_BGRA ? 0 : 16};      // R, G, B in a pixel's dword
+        int sum_u = 0, sum_v = 0;
+        for (int k = 0; k < 3; ++k) {
+            g.cy |= (uint32_t)(uint8_t)c[k] << at[k];
+            g.cu |= (uint32_t)(uint8_t)(int8_t)c[3 + k] << at[k];
+            g.cv |= (uint32_t)(uint8_t)(int8_t)c[6 + k] << at[k];
+            sum_u += c[3 + k];
+            sum_v += c[6 + k];
+        }
+        g.off4 = (uint32_t)off * 0x01010101u;
+        g.bias_u = (uint32_t)(131072 + 512 + 4 * 128 * sum_u);      // the dot product sees p - 128, four pixels of it
+        g.bias_v = (uint32_t)(131072 + 512 + 4 * 128 * sum_v);
+    } else {
+        const bool yuy2 = format == VP8HOST_FORMAT_YUY2;
+        g.sel_y = yuy2 ? 0x06040200u : 0x07050301u;
+        g.sel_c = yuy2 ? 0x07030501u : 0x06020400u;
+        g.shift_y = yuy2 ? 0 : 8;
+        g.shift_u = yuy2 ? 8 : 0;
+    }
+    const dim3 grid((g.units + 255) / 256, 1, b.n), block(256);
+    if (rgb) VP8_LAUNCH((k_convert_packed_b<true>), grid, block, 0, s, b, g);
+    else VP8_LAUNCH((k_convert_packed_b<false>), grid, block, 0, s, b, g);
+    return true;
+}
 
 static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::Geo) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
 template <int LAYOUT, int DEPTH> __global__ __launch_bounds__(256) void k_convert_b(BatchOf<ConvertItem> b, convert::Geo g) {
     convert::convert_body<LAYOUT, DEPTH>(b.item[blockIdx.z], g);
 }
 
-void launch_convert_batch(hipStream_t s, int format, int w, int h, const ConvertItem *items, int n) {
-    if (n <= 0 || format == VP8HOST_FORMAT_I420) return;
+bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const ConvertItem *items, int n) {
+    if (n <= 0 || format == VP8HOST_FORMAT_I420) return true;
     BatchOf<ConvertItem> b;
     b.n = n;
     for (int i = 0; i < n; ++i) b.item[i] = items[i];
+    if (format >= VP8HOST_FORMAT_PACKED_FIRST && format < VP8HOST_FORMAT_PACKED_END) return launch_convert_packed(s, format, matrix, w, h, b);
     convert::Geo g;
     g.w = w; g.h = h; g.cw = w / 2; g.ch = h / 2;
     g.units_x = g.w < 16 ? 1 : (g.w + 15) / 16;
@@ -217,8 +375,9 @@ void launch_convert_batch(hipStream_t s, int format, int w, int h, const Convert
         case VP8HOST_FORMAT_I010: VP8_LAUNCH((k_convert_b<PLANAR420, 10>), grid, block, 0, s, b, g); break;
         case VP8HOST_FORMAT_I210: VP8_LAUNCH((k_convert_b<PLANAR422, 10>), grid, block, 0, s, b, g); break;
         case VP8HOST_FORMAT_I410: VP8_LAUNCH((k_convert_b<PLANAR444, 10>), grid, block, 0, s, b, g); break;
-        default: break;      // (vp8hip_set_source_format has refused it)
+        default: return false;      // (vp8hip_set_source_format refuses it)
     }
+    return true;
 }
 
 }  // namespace vp8

@@ -31,6 +31,7 @@ struct vp8drv {
     bool staged_scan = false;
     int denoise = 0;                 // vp8drv_set_denoise: the level in force
     int format = 0;                  // vp8drv_set_source_format: the format in force
+    int colour = 0;                  // vp8drv_set_source_colour: the colour matrix in force (read by BGRA / RGBA only)
     bool analysis = false;           // vp8drv_set_analysis
     bool in_batch = false;           // a member of a live vp8drv_batch
     // read-back buffers of vp8drv_get_frame
@@ -458,7 +459,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
-            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format ||
+            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format || drv[i]->colour != drv[0]->colour ||
             drv[i]->analysis != drv[0]->analysis)
             return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
@@ -633,12 +634,25 @@ int vp8drv_set_denoise(vp8drv *d, int level) {
 }
 
 int vp8drv_set_source_format(vp8drv *d, int format) {
-    if (!d || format < 0 || format >= VP8HOST_FORMAT_COUNT || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (!d || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END ||
+        !d->cfg.device_params)
+        return VP8HIP_ERR_ARG;
     if (d->in_batch) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     DRV_CHK(vp8hip_set_source_format(d->hip, format));
     d->format = format;
     d->staged = nullptr;             // planes staged in the other format are not this format's frame
+    d->staged_scan = false;
+    return VP8HIP_OK;
+}
+
+int vp8drv_set_source_colour(vp8drv *d, int matrix) {
+    if (!d || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_source_colour(d->hip, matrix));
+    d->colour = matrix;
+    d->staged = nullptr;             // planes staged under the other matrix are not this matrix's frame
     d->staged_scan = false;
     return VP8HIP_OK;
 }

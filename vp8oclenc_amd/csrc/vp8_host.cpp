@@ -193,10 +193,32 @@ bool source_layout(int format, SourceLayout *l) {
     }
 }
 
+// the colour matrices of BGRA / RGBA, include/vp8hip_host.h: offset, then the Y, U and V rows, each R, G, B
+const int32_t colour_table[VP8HOST_COLOUR_COUNT][10] = {
+    {16, 66, 129, 25, -38, -74, 112, 112, -94, -18},
+    {16, 47, 157, 16, -26, -86, 112, 112, -102, -10},
+    {0, 77, 150, 29, -43, -84, 127, 127, -106, -21},
+    {0, 54, 183, 19, -29, -98, 127, 127, -116, -11},
+};
+bool packed_format(int format) { return format >= VP8HOST_FORMAT_PACKED_FIRST && format < VP8HOST_FORMAT_PACKED_END; }
+
 }  // namespace
+
+int vp8host_colour_coefficients(int matrix, int32_t c[9], int32_t *y_offset) {
+    if (matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT || !c || !y_offset) return -1;
+    *y_offset = colour_table[matrix][0];
+    for (int i = 0; i < 9; ++i) c[i] = colour_table[matrix][1 + i];
+    return 0;
+}
 
 int vp8host_source_plane_bytes(int format, int width, int height, size_t bytes[3]) {
     SourceLayout l;
+    if (bytes && packed_format(format) && width > 0 && height > 0 && !(width & 1) && !(height & 1)) {
+        const bool rgb = format == VP8HOST_FORMAT_BGRA || format == VP8HOST_FORMAT_RGBA;
+        bytes[0] = (size_t)width * (size_t)height * (rgb ? 4 : 2);
+        bytes[1] = bytes[2] = 0;
+        return 0;
+    }
     if (!bytes || !source_layout(format, &l) || width <= 0 || height <= 0 || (width & 1) || (height & 1)) return -1;
     const size_t b = l.depth > 8 ? 2 : 1;
     const size_t chroma = (size_t)(width >> l.sub_x) * (size_t)(height >> l.sub_y) * b;
@@ -206,8 +228,55 @@ int vp8host_source_plane_bytes(int format, int width, int height, size_t bytes[3
     return 0;
 }
 
+// the packed family: one plane; YUY2 / UYVY by the I422 rule on the samples they carry, BGRA / RGBA through the matrix
+static int convert_packed(int format, int matrix, int width, int height, const uint8_t *p, uint8_t *y, uint8_t *u, uint8_t *v) {
+    const int cw = width / 2, ch = height / 2;
+    if (format == VP8HOST_FORMAT_YUY2 || format == VP8HOST_FORMAT_UYVY) {
+        const int ly = format == VP8HOST_FORMAT_YUY2 ? 0 : 1, lu = format == VP8HOST_FORMAT_YUY2 ? 1 : 0;      // V sits two bytes behind U
+        for (int r = 0; r < height; ++r)
+            for (int x = 0; x < width; ++x) y[(size_t)r * width + x] = p[((size_t)r * width + x) * 2 + ly];
+        for (int r = 0; r < ch; ++r)
+            for (int x = 0; x < cw; ++x) {
+                const uint8_t *a = p + ((size_t)(2 * r) * cw + x) * 4, *b = a + (size_t)cw * 4;
+                u[(size_t)r * cw + x] = (uint8_t)((a[lu] + b[lu] + 1) >> 1);
+                v[(size_t)r * cw + x] = (uint8_t)((a[lu + 2] + b[lu + 2] + 1) >> 1);
+            }
+        return 0;
+    }
+    const int32_t *m = colour_table[matrix];
+    const int ir = format == VP8HOST_FORMAT_BGRA ? 2 : 0, ib = 2 - ir;
+    for (int r = 0; r < height; ++r)
+        for (int x = 0; x < width; ++x) {
+            const uint8_t *q = p + ((size_t)r * width + x) * 4;
+            y[(size_t)r * width + x] = (uint8_t)(m[0] + ((m[1] * q[ir] + m[2] * q[1] + m[3] * q[ib] + 128) >> 8));
+        }
+    for (int r = 0; r < ch; ++r)
+        for (int x = 0; x < cw; ++x) {
+            int32_t su = 0, sv = 0;
+            for (int j = 0; j < 2; ++j)
+                for (int i = 0; i < 2; ++i) {
+                    const uint8_t *q = p + ((size_t)(2 * r + j) * width + (2 * x + i)) * 4;
+                    su += m[4] * q[ir] + m[5] * q[1] + m[6] * q[ib];
+                    sv += m[7] * q[ir] + m[8] * q[1] + m[9] * q[ib];
+                }
+            u[(size_t)r * cw + x] = (uint8_t)((su + 131072 + 512) >> 10);
+            v[(size_t)r * cw + x] = (uint8_t)((sv + 131072 + 512) >> 10);
+        }
+    return 0;
+}
+
+int vp8host_convert_frame_colour(int format, int matrix, int width, int height, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2,
+                                 uint8_t *y, uint8_t *u, uint8_t *v) {
+    if (matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT) return -1;
+    if (!packed_format(format)) return vp8host_convert_frame(format, width, height, p0, p1, p2, y, u, v);
+    size_t bytes[3];
+    if (vp8host_source_plane_bytes(format, width, height, bytes) != 0 || !p0 || !y || !u || !v) return -1;
+    return convert_packed(format, matrix, width, height, p0, y, u, v);
+}
+
 int vp8host_convert_frame(int format, int width, int height, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2,
                           uint8_t *y, uint8_t *u, uint8_t *v) {
+    if (packed_format(format)) return vp8host_convert_frame_colour(format, VP8HOST_COLOUR_BT601_LIMITED, width, height, p0, p1, p2, y, u, v);
     SourceLayout l;
     size_t bytes[3];
     if (vp8host_source_plane_bytes(format, width, height, bytes) != 0 || !source_layout(format, &l)) return -1;

@@ -119,7 +119,8 @@ struct vp8hip_ctx {
     // vp8hip_set_source_format: what the three pointers of a current frame are (0 = I420: nothing below is used).  k_convert_b makes tight
     // I420 of the incoming size of them in fmt_stage (Y, U, V at fmt_off, each plane 256-byte aligned) and the pack or scale launch
     // reads that; planes from host memory that were not prefetched pass through fmt_raw first.
-    int src_fmt = 0;
+    // vp8hip_set_source_colour: the colour matrix BGRA / RGBA frames are read with (no other format looks at it).
+    int src_fmt = 0, src_colour = 0;
     uint8_t *fmt_stage = nullptr, *fmt_raw = nullptr;
     size_t fmt_stage_bytes = 0, fmt_raw_bytes = 0;
     // vp8hip_set_denoise: the level (0 = off); whether cur_prev holds a history (the previous frame taken in, as it left k_denoise_b, at
@@ -337,7 +338,7 @@ inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) {
     (void)vp8host_source_plane_bytes(c->src_fmt, w, h, bytes);
 }
 inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched convert / pack / scale launch takes as one value
-    return a->src_fmt == b->src_fmt && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
+    return a->src_fmt == b->src_fmt && a->src_colour == b->src_colour && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
            (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level &&     // (and one denoiser level)
            a->an_on == b->an_on;                                                                    // (analysis on for all or for none)
 }

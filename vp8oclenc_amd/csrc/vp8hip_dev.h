@@ -182,9 +182,11 @@ void launch_analyse_src_batch(hipStream_t s, const AnalysisSrcItem *items, int n
 void launch_analyse_mb_batch(hipStream_t s, const AnalysisMbItem *items, int n);
 // kernels_convert.hip: source frames in another format than 8-bit I420 (vp8hip_set_source_format), made tight 8-bit I420 of the same
 // size IN FRONT of the pack or scale launch, which then reads dst as if the caller had handed it in; the rule is include/vp8hip_host.h's.
-// src: the format's planes (src[2] is not read for the two-plane formats).  Format 0 launches nothing.
+// src: the format's planes (src[2] is not read for the two-plane formats, src[1] and src[2] for the packed ones, k_convert_packed_b).
+// matrix: the colour matrix BGRA / RGBA are read with (vp8hip_set_source_colour).  Format 0 launches nothing.  false: a format or
+// matrix the setters refuse -- nothing was launched and the staging buffer is NOT the frame.
 struct ConvertItem { const uint8_t *src[3]; uint8_t *dst[3]; };
-void launch_convert_batch(hipStream_t s, int format, int w, int h, const ConvertItem *items, int n);
+bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const ConvertItem *items, int n);
 bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int net_width, int n, bool finest, bool top_only = false);
 void launch_search1_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int level, int src_idx,
                           int net_width, int n);

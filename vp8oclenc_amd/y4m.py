@@ -71,7 +71,7 @@ class Y4mFile:
 
     def frame(self, t: int):
         if self.format != api.FORMAT_I420:
-            raise ValueError(f"a {api.FORMAT_NAMES[self.format]} file has no I420 frames: planes(t), and vp8drv_set_source_format")
+            raise ValueError(f"a {api.source_format_name(self.format)} file has no I420 frames: planes(t), and vp8drv_set_source_format")
         b = self._bytes(t)
         W, H = self.W, self.H
         return (np.ascontiguousarray(b[:W * H].reshape(H, W)), np.ascontiguousarray(b[W * H:W * H * 5 // 4].reshape(H // 2, W // 2)),
