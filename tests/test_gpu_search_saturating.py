@@ -113,9 +113,12 @@ def _compare(member, idx, flags, want, bad):
             if not np.array_equal(got, nets[(r, name)]):
                 bad.append((idx, r, name, int((got != nets[(r, name)]).sum())))
     a = member.download_results(recon=True)
-    for k in ("MB_parts", "MB_reference_frame", "MB_vectors", "MB_coeffs", "MB_segment_id"):
+    for k in ("MB_parts", "MB_reference_frame", "MB_vectors", "MB_coeffs", "MB_segment_id", "prefilter_Y", "prefilter_U", "prefilter_V"):
         if not np.array_equal(a[k], mb[k]):
             bad.append((idx, k, "results", int((a[k] != mb[k]).sum())))
+    x, y = np.asarray(a["MB_SSIM"], np.float32).view(np.uint32), np.asarray(mb["MB_SSIM"], np.float32).view(np.uint32)
+    if not np.array_equal(x, y):      # by bit pattern: the value gates the segment loop
+        bad.append((idx, "MB_SSIM", "results", int((x != y).sum())))
 
 
 @pytest.mark.parametrize("W,H", [(80, 48), (176, 144)])
