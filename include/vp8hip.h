@@ -257,6 +257,43 @@ typedef struct {
  * VP8HIP_ERR_STATE: denoising off, or no frame taken in since it was turned on. */
 int vp8hip_denoise_result(vp8hip_ctx *ctx, vp8hip_denoise_stats *s);
 
+/* Interlaced source frames made progressive, a stage of the input side between the format converter and the pack or scale launch.  A
+ * capture card, a broadcast archive or a decoder often hands over frames whose even and odd rows are two fields taken a field period
+ * apart (1080i, 576i, 480i); VP8 has no interlaced coding tools, and coded as they are every moving edge is a comb that the search and
+ * the transform pay for, the scaler mixes the fields and the denoiser sees motion in every second row.  mode 1 (field) or 2
+ * (adaptive), keep = the field that survives and defines the frame's instant, 0 = top (rows 0, 2, ...), 1 = bottom: every frame that
+ * becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the pack out of a vp8hip_prefetch_current staging buffer,
+ * vp8hip_batch_set_current_device, vp8hip_batch_upload_current -- passes through ONE more launch (k_deinterlace_b) on the same stream,
+ * which reads tight I420 of the incoming size (the caller's planes, the converter's output or an upload's staging buffer) and writes
+ * tight I420 into a staging buffer of the context; the pack or scale launch reads that as if the caller had handed it in.  The rule --
+ * kept rows copied, missing rows a four-tap value of the kept rows (mode 1), clamped around the sample that came in by how much the
+ * neighbourhood moved since the previous frame (mode 2: what stands still is woven at full vertical resolution) -- is stated bit for
+ * bit in include/vp8hip_host.h (vp8host_deinterlace_frame).  One frame out per frame in: no rate doubling.
+ * COMPOSITION: convert, then deinterlace, then pack or scale, then denoise, then the analysis source side.  The chroma scan, the
+ * analysis and the quality statistics see the deinterlaced frame: the one that was coded.  It composes with vp8hip_set_source_size,
+ * vp8hip_set_source_scaling, vp8hip_set_source_format and vp8hip_set_denoise in any order of calls.
+ * Mode 2's history is the previous frame taken in AS RECEIVED (both fields, unprocessed), kept in buffers of the context: nothing
+ * depends on the caller's planes after the call that took them has returned.  Without a history (the first frame, after
+ * vp8hip_deinterlace_restart, after the mode, the parity or the incoming size changed) the frame is mode 1's.  Once per frame TAKEN
+ * IN: a frame coded a second time (check_SSIM's verdict) is the same current frame and is not deinterlaced again.
+ * mode 0 (default): off -- no launch, no allocation, no byte and no number changes.  Any other mode or keep, or an incoming height
+ * below 4 (every plane needs a row of each field; the size setters refuse such a height while a mode is set): VP8HIP_ERR_ARG and
+ * nothing has changed.  Turning it on, or changing mode or parity, restarts the history and drops a pending vp8hip_prefetch_current.
+ * Waits for the context's streams: not a per-frame call.  All members of a batch must agree on mode and parity
+ * (vp8hip_batch_create and the batched launch check it).  Shard and group contexts: not supported. */
+int vp8hip_set_deinterlace(vp8hip_ctx *ctx, int mode, int keep);
+/* The next frame taken in has no history (a host calls it where its stream restarts: a key frame of the GOP schedule, so that a closed
+ * GOP coded on its own sees the frames the serial program sees). */
+int vp8hip_deinterlace_restart(vp8hip_ctx *ctx);
+typedef struct {
+    int32_t frame_number;    /* 0-based index of the frame taken in, as in vp8hip_quality */
+    int32_t woven;           /* luma samples of missing rows that left as they came (0 in mode 1 and without a history) */
+    int32_t missing;         /* luma samples of missing rows */
+} vp8hip_deinterlace_stats;
+/* The record of the last frame taken in.  Waits for that launch's last word only, as vp8hip_quality_result does.
+ * VP8HIP_ERR_STATE: deinterlacing off, or no frame taken in since it was turned on. */
+int vp8hip_deinterlace_result(vp8hip_ctx *ctx, vp8hip_deinterlace_stats *s);
+
 /* prepare_filter_mask_and_non_zero_coeffs(), loop_filter.h:25-55.  nz_out: [MBs] or NULL.
  * (vp8hip_inter_transform already produced mask and counts for its own coefficients; this call
  * recomputes them from the device copy, e.g. after vp8hip_upload_mb_data.) */
@@ -474,6 +511,9 @@ const char *vp8hip_status_string(int status);
  * quality_stats, which stays the last field (a host fills the struct with vp8drv_default_config, which zeroes them: no scaling);
  * also under 4010: vp8hip_set_denoise, vp8hip_denoise_restart, vp8hip_denoise_result, vp8host_denoise_frame, vp8drv_set_denoise and
  * vp8drv_get_denoise_stats (entry points only: vp8drv_config is unchanged);
+ * also under 4010: the deinterlacer (vp8hip_set_deinterlace, vp8hip_deinterlace_restart, vp8hip_deinterlace_result,
+ * vp8host_deinterlace_frame, vp8host_y4m_interlace, vp8drv_set_deinterlace, vp8drv_get_deinterlace_stats; entry points only:
+ * vp8drv_config is unchanged);
  * also under 4010: source formats (vp8hip_set_source_format, vp8drv_set_source_format, vp8host_source_plane_bytes, vp8host_convert_frame,
  * vp8host_y4m_colourspace; entry points only: vp8drv_config is unchanged);
  * also under 4010: the packed source formats YUY2, UYVY, BGRA, RGBA and their colour matrix (vp8hip_set_source_colour,

@@ -228,6 +228,23 @@ int vp8drv_get_quality_summary(vp8drv *d, vp8drv_quality_summary *s);
 int vp8drv_set_denoise(vp8drv *d, int level);
 /* the record of the last frame taken in (vp8hip_denoise_result); VP8HIP_ERR_STATE when denoising is off or no frame was taken in */
 int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s);
+/* Interlaced source frames made progressive (vp8hip_set_deinterlace; the rule: include/vp8hip_host.h), an entry point and not a field
+ * for the reason vp8drv_set_denoise is one, and under its rules: call it after vp8drv_create; mode 0 (default, off), 1 (field) or 2
+ * (adaptive), keep 0 (top field) or 1 (bottom field).  It takes the open check_SSIM verdict first.  VP8HIP_ERR_ARG: another mode or
+ * keep, an incoming height below 4, or cfg.device_params = 0 (the host parameter mirror would scan the caller's luma, which is not the
+ * frame that is coded); VP8HIP_ERR_STATE: the driver is a member of a live batch (members must agree on mode and parity: set them
+ * before vp8drv_batch_create, which refuses members that differ).  Every way a frame is taken in passes through it:
+ * vp8drv_encode_frame_device / _host, vp8drv_prefetch_frame_host, vp8drv_stage_frame_host and the batched calls.
+ * The order is convert, then deinterlace, then pack or scale, then denoise, then the analysis source side; the chroma scan, the
+ * analysis and the quality statistics see the deinterlaced frame, the one that was coded.
+ * The history of mode 2 restarts where the denoiser's does: when the GOP schedule makes the incoming frame a key frame, so a closed GOP
+ * coded as a chunk of its own sees what the serial program sees.  force_key, scene cuts and frames sent back by check_SSIM do not
+ * restart it, and a frame coded again as a key frame is not deinterlaced twice.  KNOWN COST: a GOP's first frame is therefore
+ * field-interpolated in mode 2.  Handing the frame BEFORE a chunk's first frame in as a primer would lift that, and it would be exact
+ * because the history is unprocessed input; it is not done here. */
+int vp8drv_set_deinterlace(vp8drv *d, int mode, int keep);
+/* the record of the last frame taken in (vp8hip_deinterlace_result); VP8HIP_ERR_STATE when deinterlacing is off or no frame was taken in */
+int vp8drv_get_deinterlace_stats(vp8drv *d, vp8hip_deinterlace_stats *s);
 /* The format of the source frames (vp8hip_set_source_format; the formats and the rule: include/vp8hip_host.h), an entry point and not a
  * field of vp8drv_config for the reason vp8drv_set_denoise is one.  Call it after vp8drv_create and before the first frame, or
  * between frames.  From then on the three pointers of vp8drv_encode_frame_device / _host, vp8drv_prefetch_frame_host,

@@ -160,6 +160,39 @@ int vp8host_colour_coefficients(int matrix, int32_t c[9], int32_t *y_offset);
  * C420jpeg, C420mpeg2, C420paldv: I420; C422: I422; C444: I444; C420p10: I010; C422p10: I210; C444p10: I410.  Returns 0 and the
  * format, or -1: anything else (Cmono, C444alpha, 12 and 16 bits, ...), no YUV4MPEG2 magic word, or no line feed in the buffer. */
 int vp8host_y4m_colourspace(const uint8_t *data, size_t size, int32_t *format);
+/* The I tag of the same header line, read the same way (the first tag that starts with I counts).  No I tag, Ip, I?: progressive;
+ * It: top field first; Ib: bottom field first.  Returns 0 and one of enum vp8host_field_order, or -1: Im (mixed: the field order is
+ * a per-frame parameter this reader does not follow) and any other I tag, no YUV4MPEG2 magic word, or no line feed in the buffer. */
+typedef enum { VP8HOST_FIELDS_PROGRESSIVE = 0, VP8HOST_FIELDS_TOP_FIRST = 1, VP8HOST_FIELDS_BOTTOM_FIRST = 2 } vp8host_field_order;
+int vp8host_y4m_interlace(const uint8_t *data, size_t size, int32_t *field_order);
+
+/* The rule of the device's deinterlacer (vp8hip_set_deinterlace, include/vp8hip.h; k_deinterlace_b), bit for bit, integers only.  The
+ * project's own: VP8 has no interlaced coding tools and the reference does not know what a field is.
+ * It applies to each of the three tight I420 planes of the INCOMING size (the scaler's incoming size, else the source size, else the
+ * coded size) on its own, after format conversion and before padding, scaling and denoising.  One output frame per input frame: no
+ * rate doubling.  keep = the field that survives and defines the output frame's instant: 0 = the top field (rows 0, 2, 4, ...),
+ * 1 = the bottom field (rows 1, 3, 5, ...); the same parity in the chroma planes' rows.  With h the plane's rows:
+ * KEPT ROWS, y = keep (mod 2), are copied unchanged.
+ * SPATIAL VALUE s of a sample of a MISSING row y: the kept rows are K[j] = row 2 j + keep, j = 0 .. n - 1; with
+ *     j0 = floor((y - 1 - keep) / 2)          (-1 for y = 0 when keep = 1)
+ * the taps are a0 .. a3 = K[j0 - 1], K[j0], K[j0 + 1], K[j0 + 2] in the sample's column, every index clamped to 0 .. n - 1, and
+ *     s = clamp(0, 255, (-a0 + 9 a1 + 9 a2 - a3 + 8) >> 4)          (arithmetic shift).
+ * MODE 1, field: output = s.  No history.
+ * MODE 2, adaptive: a history P is kept, the previous frame taken in as the deinterlacer RECEIVED it (both fields, unprocessed).
+ * With cur the frame received, wv = cur[y][x], d(r) = |cur[r][x] - P[r][x]| and m = max(d(y), d(max(y - 1, 0)), d(min(y + 1, h - 1))):
+ *     output = min(max(s, wv - m), wv + m).
+ * It lies between s and wv: no clamp.  A static sample (m = 0) is woven at full vertical resolution, a moving one gets the field
+ * interpolation; there is no threshold.  Without a history -- the first frame, after a restart, after the mode or the parity changed,
+ * after the incoming size changed -- output = s, the frame equals mode 1's, and the frame as received becomes the history.
+ * The record of a frame: woven = the LUMA samples of missing rows whose output equals wv (0 in mode 1 and without a history),
+ * missing = the luma samples of missing rows.  A height below 4 is refused: every plane then has a row of each field.
+ * vp8host_deinterlace_frame: the rule on tight planes of width x height (both even, height >= 4; chroma width / 2 x height / 2).
+ * mode 0: out = src, *woven = 0, the history is left alone.  mode 1: the history is not read, not written and may be null.  mode 2:
+ * the history planes are read when have_history != 0 and are replaced by src (in-out).  out must not overlap src or the history.
+ * Returns 0, or -1 for bad arguments. */
+int vp8host_deinterlace_frame(const uint8_t *src_y, const uint8_t *src_u, const uint8_t *src_v, uint8_t *hist_y, uint8_t *hist_u,
+                              uint8_t *hist_v, uint8_t *out_y, uint8_t *out_u, uint8_t *out_v, int width, int height, int mode, int keep,
+                              int have_history, int32_t *woven);
 
 /* The rules of the frame analysis record (vp8hip_set_analysis, include/vp8hip.h; k_analyse_src_b, k_analyse_mb_b), bit for bit.  The
  * project's own: libvpx's first-pass statistics cut to what this encoder knows.  Every field is an exact integer; no floats anywhere.

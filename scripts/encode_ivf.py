@@ -68,6 +68,8 @@ def main():
     ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", help="the colour matrix bgra / rgba frames are read with (vp8drv_set_source_colour)")
     ap.add_argument("--source-range", choices=("limited", "full"), default="limited", help="... and the range of the YUV it makes")
     ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
+    ap.add_argument("--deinterlace", choices=("off", "field", "adaptive"), default="off", metavar="MODE", help="interlaced source frames made progressive on the device (vp8drv_set_deinterlace): field = every missing row interpolated, adaptive = what stands still is woven; the history restarts with every GOP")
+    ap.add_argument("--field", choices=("top", "bottom"), default="top", help="... the field that is kept")
     ap.add_argument("--analysis", default="", metavar="FILE", help="the frame analysis record of every frame as one text line per frame (vp8drv_set_analysis; the line: scripts/native/y4m_to_ivf.cpp): a first-pass file")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -104,6 +106,8 @@ def main():
                                       loop_filter_type=int(a.simple_filter))
         if a.denoise:
             enc.drv.set_denoise(a.denoise)
+        if a.deinterlace != "off":
+            enc.drv.set_deinterlace(a.deinterlace, a.field)
         if fmt:
             enc.drv.set_source_format(fmt)
             enc.drv.set_source_colour(a.source_matrix, a.source_range)

@@ -21,6 +21,8 @@ ap.add_argument("--quality-stats", type=int, choices=(0, 1), default=0, help="1 
 ap.add_argument("--scale-from", default="", metavar="WxH", help="the frames come in at this size and are scaled down to --width x --height on the device (vp8drv_config.in_width / in_height)")
 ap.add_argument("--scale-filter", choices=("area", "lanczos"), default="area")
 ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of every frame taken in (vp8drv_set_denoise): what k_denoise_b costs")
+ap.add_argument("--deinterlace", choices=("off", "field", "adaptive"), default="off", metavar="MODE", help="every frame taken in passes through the deinterlacer (vp8drv_set_deinterlace): what k_deinterlace_b costs")
+ap.add_argument("--field", choices=("top", "bottom"), default="top", help="... the field that is kept")
 ap.add_argument("--source-format", default="", metavar="NAME", help="the device-resident frames are this format's planes (nv12, p010, i444, ..., or the packed yuy2, uyvy, bgra, rgba: vp8drv_set_source_format): what k_convert_b / k_convert_packed_b costs")
 ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", help="the colour matrix bgra / rgba frames are read with (vp8drv_set_source_colour)")
 ap.add_argument("--source-range", choices=("limited", "full"), default="limited")
@@ -68,6 +70,9 @@ drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, ch
 if a.denoise:
     for d in drvs:
         d.set_denoise(a.denoise)
+if a.deinterlace != "off":
+    for d in drvs:
+        d.set_deinterlace(a.deinterlace, a.field)
 if fmt:
     for d in drvs:
         d.set_source_format(fmt)

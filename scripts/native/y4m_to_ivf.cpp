@@ -2,7 +2,12 @@
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
-//              [-input-format NAME] [-analysis FILE]
+//              [-input-format NAME] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]]
+// -deinterlace: interlaced frames are made progressive on the device (vp8drv_set_deinterlace; the rule: include/vp8hip_host.h), field =
+// every missing row interpolated, adaptive = what stands still is woven.  :top / :bottom names the field that is kept; without it that
+// is the FIRST field of the header's I tag (It: top, Ib: bottom; vp8host_y4m_interlace), and top, with a line on stderr, for a file
+// that says it is progressive or says nothing.  An Im (mixed) file is refused.  Without the option nothing changes, whatever the tag
+// says.  The share of missing samples that were woven is printed at the end, next to -psnr's summary.
 // -analysis FILE: the frame analysis record of every frame (vp8drv_set_analysis; the rules: include/vp8hip_host.h) as one text line per
 // frame, the first-pass file a caller's second pass reads.  Decimal integers separated by single spaces, in this order:
 //   frame_number is_key bytes have_prev static_mbs spatial temporal_sse temporal_sad coded mbs_total mbs_intra mbs_split mbs_zero_mv
@@ -42,6 +47,7 @@ int main(int argc, char **argv) {
     cfg.overlap_filter = 1;
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     int denoise = 0;         // -denoise
+    int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     int32_t format = -1;     // -input-format (-1: the header's C tag)
     const char *analysis_path = nullptr;      // -analysis
     static const char *const format_names[VP8HOST_FORMAT_COUNT] = {"i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"};
@@ -61,6 +67,15 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-psnr")) cfg.quality_stats = 1;               // PSNR / SSIM summary on stderr
         else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
         else if (!strcmp(argv[i], "-analysis")) analysis_path = val();
+        else if (!strcmp(argv[i], "-deinterlace")) {
+            const char *f = val(), *colon = strchr(f, ':');
+            const size_t len = colon ? (size_t)(colon - f) : strlen(f);
+            if (len == 5 && !strncmp(f, "field", 5)) deint = 1;
+            else if (len == 8 && !strncmp(f, "adaptive", 8)) deint = 2;
+            if (colon && !strcmp(colon + 1, "top")) field = 0;
+            else if (colon && !strcmp(colon + 1, "bottom")) field = 1;
+            if (!deint || (colon && field < 0)) { fprintf(stderr, "-deinterlace field|adaptive[:top|bottom]\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "-input-format")) {
             const char *f = val();
             for (int k = 0; k < VP8HOST_FORMAT_COUNT; ++k)
@@ -97,6 +112,17 @@ int main(int argc, char **argv) {
                 a + 1 < len ? (int)(b - a - 1) : 1, a + 1 < len ? reinterpret_cast<const char *>(head + a + 1) : "?");
         return 1;
     }
+    if (deint) {
+        int32_t order = 0;
+        if (vp8host_y4m_interlace(head, got, &order) != 0) {
+            fprintf(stderr, "%s: interlace tag Im (mixed) or unknown: not a field order -deinterlace can follow (Ip, I?, It, Ib)\n", argv[1]);
+            return 1;
+        }
+        if (field < 0) {
+            if (order == VP8HOST_FIELDS_PROGRESSIVE) fprintf(stderr, "%s: no field order in the header: -deinterlace keeps the top field\n", argv[1]);
+            field = order == VP8HOST_FIELDS_BOTTOM_FIRST ? 1 : 0;
+        }
+    }
     fseek(in, (long)first, SEEK_SET);
     // video.src_* is the file's size, video.dst_* the picture that is coded and displayed (-resize; the file's without it), video.wrk_* that
     // rounded up to whole macroblocks (init.h:375-392).  The frames are handed over as the file has them: scaled and padded on the device.
@@ -109,7 +135,8 @@ int main(int argc, char **argv) {
     CK(vp8drv_create(&drv, Wc, Hc, 0, &cfg));
     if (denoise) CK(vp8drv_set_denoise(drv, denoise));
     if (format) CK(vp8drv_set_source_format(drv, format));
-    long long dn_filtered = 0, dn_total = 0;
+    if (deint) CK(vp8drv_set_deinterlace(drv, deint, field));
+    long long dn_filtered = 0, dn_total = 0, di_woven = 0, di_missing = 0;
     FILE *analysis = nullptr;
     vp8drv_analysis an{};      // the record of the frame whose bytes are still to be taken
     if (analysis_path) {
@@ -209,6 +236,12 @@ int main(int argc, char **argv) {
                 dn_filtered += ds.mbs_filtered;
                 dn_total += ds.mbs_total;
             }
+            if (deint) {
+                vp8hip_deinterlace_stats is;
+                CK(vp8drv_get_deinterlace_stats(drv, &is));
+                di_woven += is.woven;
+                di_missing += is.missing;
+            }
             CK(prefetch_next());
         }
         if (pending) {      // the previous frame's bytes
@@ -263,6 +296,9 @@ int main(int argc, char **argv) {
     if (denoise)
         fprintf(stderr, "Denoiser level %d: %lld of %lld macroblocks filtered (%.1f %%)\n", denoise, dn_filtered, dn_total,
                 dn_total ? 100.0 * (double)dn_filtered / (double)dn_total : 0.0);
+    if (deint)
+        fprintf(stderr, "Deinterlacer %s, %s field kept: %lld of %lld missing luma samples woven (%.1f %%)\n", deint == 1 ? "field" : "adaptive",
+                field ? "bottom" : "top", di_woven, di_missing, di_missing ? 100.0 * (double)di_woven / (double)di_missing : 0.0);
     vp8drv_destroy(drv);
     for (int k = 0; k < RING; ++k) vp8hip_host_free(0, buf[k]);
     printf("%s: %u frames %dx%d (coded %dx%d), %u key (%d by scene change, %d recoded), %zu bytes; %d hardware queues\n", argv[2], n, W, H, Wc, Hc, keys,

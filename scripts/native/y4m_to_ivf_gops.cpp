@@ -2,6 +2,8 @@
 // bench.py's headline measures, as a complete C++ user of the C ABI.
 //   y4m_to_ivf_gops <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n]
 //                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
+//                   [-deinterlace field|adaptive[:top|bottom]]
+// (-deinterlace: as in y4m_to_ivf.cpp -- the history of adaptive restarts at every GOP's key frame, so a chunk sees what the serial program sees)
 // (-denoise N: as in y4m_to_ivf.cpp -- the history restarts at every GOP's key frame, so a chunk sees the frames the serial program sees)
 // (-resize: as in y4m_to_ivf.cpp -- frames of the file's size in, scaled down to WxH on the device, one launch per batch step)
 // A key frame resets every reference (intra_part.h:1091-1098, inter_part.h:35-50), so the frames [k g, (k + 1) g) of a run with
@@ -40,6 +42,7 @@ int main(int argc, char **argv) {
     int in_flight = 48, batch = 6;
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     int denoise = 0;         // -denoise
+    int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -54,6 +57,15 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-chunks")) in_flight = atoi(val());
         else if (!strcmp(argv[i], "-batch")) batch = atoi(val());
         else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
+        else if (!strcmp(argv[i], "-deinterlace")) {
+            const char *f = val(), *colon = strchr(f, ':');
+            const size_t len = colon ? (size_t)(colon - f) : strlen(f);
+            if (len == 5 && !strncmp(f, "field", 5)) deint = 1;
+            else if (len == 8 && !strncmp(f, "adaptive", 8)) deint = 2;
+            if (colon && !strcmp(colon + 1, "top")) field = 0;
+            else if (colon && !strcmp(colon + 1, "bottom")) field = 1;
+            if (!deint || (colon && field < 0)) { fprintf(stderr, "-deinterlace field|adaptive[:top|bottom]\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -85,6 +97,17 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (deint) {
+        int32_t order = 0;
+        if (vp8host_y4m_interlace(head, got, &order) != 0) {
+            fprintf(stderr, "%s: interlace tag Im (mixed) or unknown: not a field order -deinterlace can follow (Ip, I?, It, Ib)\n", argv[1]);
+            return 1;
+        }
+        if (field < 0) {
+            if (order == VP8HOST_FIELDS_PROGRESSIVE) fprintf(stderr, "%s: no field order in the header: -deinterlace keeps the top field\n", argv[1]);
+            field = order == VP8HOST_FIELDS_BOTTOM_FIRST ? 1 : 0;
+        }
+    }
     const size_t ysz = (size_t)W * H, csz = ysz / 4, fsz = ysz + 2 * csz, rec = fsz + 6;      // a frame and the marker behind it (get_yuv420_frame, encIO.h:203-254)
     const int nframes = (int)((file_size - first + 6) / rec);
     if (nframes < 1) { fprintf(stderr, "%s: no frame\n", argv[1]); return 1; }
@@ -113,6 +136,7 @@ int main(int argc, char **argv) {
     for (int j = 0; j < in_flight; ++j) {
         CK(vp8drv_create(&drv[j], Wc, Hc, 0, &cfg));
         if (denoise) CK(vp8drv_set_denoise(drv[j], denoise));      // (before the batch is made: its members must agree)
+        if (deint) CK(vp8drv_set_deinterlace(drv[j], deint, field));
         CK(vp8hip_reserve_frame_path_dense(vp8drv_context(drv[j])));      // frame t + 1 is started before frame t's bytes are taken: no frame is ever coded twice
         if ((j + 1) % batch == 0 || j == in_flight - 1) {
             const int k = j / batch, j0 = k * batch;

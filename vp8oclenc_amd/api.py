@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_deinterlace", "vp8hip_deinterlace_restart", "vp8hip_deinterlace_result", "vp8host_deinterlace_frame", "vp8host_y4m_interlace", "vp8drv_set_deinterlace", "vp8drv_get_deinterlace_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -484,6 +484,11 @@ class DenoiseStats(C.Structure):
     _fields_ = [("frame_number", C.c_int32), ("mbs_filtered", C.c_int32), ("mbs_total", C.c_int32)]
 
 
+class DeinterlaceStats(C.Structure):
+    """vp8hip_deinterlace_stats, include/vp8hip.h: the last frame taken in by a context with vp8hip_set_deinterlace"""
+    _fields_ = [("frame_number", C.c_int32), ("woven", C.c_int32), ("missing", C.c_int32)]
+
+
 class Analysis(C.Structure):
     """vp8hip_analysis, include/vp8hip.h: the frame analysis record of a context with vp8hip_set_analysis (every field an exact integer;
     the rules: include/vp8hip_host.h)"""
@@ -561,6 +566,43 @@ def denoise_frame(src, hist, level: int, have_history: bool):
     if lib.vp8host_denoise_frame(*[p.ctypes.data for p in src], *hp, *[p.ctypes.data for p in out], w, h, int(level), int(bool(have_history)),
                                  C.byref(n)) != 0:
         raise ValueError(f"vp8host_denoise_frame({w}x{h}, level {level}) refused")
+    return out, n.value
+
+
+DEINTERLACE_OFF, DEINTERLACE_FIELD, DEINTERLACE_ADAPTIVE = range(3)      # the modes of vp8hip_set_deinterlace
+FIELD_TOP, FIELD_BOTTOM = 0, 1                                            # ... and its keep
+FIELDS_PROGRESSIVE, FIELDS_TOP_FIRST, FIELDS_BOTTOM_FIRST = range(3)      # vp8host_field_order, include/vp8hip_host.h
+_DEINTERLACE_MODES = {"off": 0, "field": 1, "adaptive": 2}
+_FIELDS = {"top": 0, "bottom": 1}
+
+
+def deinterlace_mode(name) -> int:
+    """off / field / adaptive (or the number) -> the mode of vp8hip_set_deinterlace"""
+    return _DEINTERLACE_MODES[name] if isinstance(name, str) else int(name)
+
+
+def deinterlace_field(name) -> int:
+    """top / bottom (or the number) -> the keep of vp8hip_set_deinterlace"""
+    return _FIELDS[name] if isinstance(name, str) else int(name)
+
+
+def deinterlace_frame(src, hist, mode: int, keep: int, have_history: bool):
+    """vp8host_deinterlace_frame: the device's deinterlacer in plain C++ on tight planes.  src = (Y, U, V); hist = (Y, U, V) arrays that
+    mode 2 reads (with have_history) and replaces by src, or None in modes 0 and 1 -> ((Y, U, V) out, woven luma samples)"""
+    lib = load_library()
+    lib.vp8host_deinterlace_frame.argtypes = [C.c_void_p] * 9 + [C.c_int] * 5 + [C.POINTER(C.c_int32)]
+    src = [np.ascontiguousarray(p, np.uint8) for p in src]
+    h, w = src[0].shape
+    out = [np.empty_like(p) for p in src]
+    if hist is not None:
+        for a, b in zip(hist, src):
+            if a.dtype != np.uint8 or not a.flags["C_CONTIGUOUS"] or a.shape != b.shape:
+                raise ValueError("deinterlace_frame: the history planes are contiguous uint8 arrays of the source planes' shapes")
+    hp = [a.ctypes.data for a in hist] if hist is not None else [None] * 3
+    n = C.c_int32(0)
+    if lib.vp8host_deinterlace_frame(*[p.ctypes.data for p in src], *hp, *[p.ctypes.data for p in out], w, h, int(mode), int(keep),
+                                     int(bool(have_history)), C.byref(n)) != 0:
+        raise ValueError(f"vp8host_deinterlace_frame({w}x{h}, mode {mode}, keep {keep}) refused")
     return out, n.value
 
 
@@ -859,6 +901,23 @@ class NativeDriver:
         rc = self.lib.vp8drv_set_source_format(self.h, fmt)
         if rc != 0:
             raise Vp8HipError(f"vp8drv_set_source_format({fmt}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_deinterlace(self, mode, keep=0) -> None:
+        """vp8drv_set_deinterlace: interlaced source frames made progressive; mode off / field / adaptive (0, 1, 2), keep top / bottom
+        (0, 1); the history of adaptive restarts at the GOP schedule's key frames"""
+        self.lib.vp8drv_set_deinterlace.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.lib.vp8drv_set_deinterlace(self.h, deinterlace_mode(mode), deinterlace_field(keep))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_deinterlace({mode}, {keep}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def deinterlace_stats(self) -> DeinterlaceStats:
+        """vp8drv_get_deinterlace_stats: the last frame taken in"""
+        s = DeinterlaceStats()
+        self.lib.vp8drv_get_deinterlace_stats.argtypes = [C.c_void_p, C.POINTER(DeinterlaceStats)]
+        rc = self.lib.vp8drv_get_deinterlace_stats(self.h, C.byref(s))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_deinterlace_stats: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return s
 
     def denoise_stats(self) -> DenoiseStats:
         """vp8drv_get_denoise_stats: the last frame taken in"""
@@ -1252,6 +1311,23 @@ class Vp8Hip:
         s = DenoiseStats()
         self.lib.vp8hip_denoise_result.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
         self._chk(self.lib.vp8hip_denoise_result(self.h, C.byref(s)), "denoise_result")
+        return s
+
+    def set_deinterlace(self, mode, keep=0):
+        """vp8hip_set_deinterlace: every frame that becomes current passes through the deinterlacer (mode off / field / adaptive or
+        0, 1, 2; keep top / bottom or 0, 1); turning it on or changing mode or parity restarts the history"""
+        self.lib.vp8hip_set_deinterlace.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.vp8hip_set_deinterlace(self.h, deinterlace_mode(mode), deinterlace_field(keep)), "set_deinterlace")
+
+    def deinterlace_restart(self):
+        """vp8hip_deinterlace_restart: the next frame taken in has no history"""
+        self.lib.vp8hip_deinterlace_restart.argtypes = [C.c_void_p]
+        self._chk(self.lib.vp8hip_deinterlace_restart(self.h), "deinterlace_restart")
+
+    def deinterlace_result(self) -> "DeinterlaceStats":
+        s = DeinterlaceStats()
+        self.lib.vp8hip_deinterlace_result.argtypes = [C.c_void_p, C.POINTER(DeinterlaceStats)]
+        self._chk(self.lib.vp8hip_deinterlace_result(self.h, C.byref(s)), "deinterlace_result")
         return s
 
     def set_analysis(self, on: bool = True):

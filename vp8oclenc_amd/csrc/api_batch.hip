@@ -207,6 +207,11 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         const int rc = format_stage_ready(b->c[i]);
         if (rc) return rc;
     }
+    for (int i = 0; i < b->n && c0->di_mode; ++i) {      // vp8hip_set_deinterlace: the members' staging and history buffers (as a rule: they are there)
+        if (active && !active[i]) continue;
+        const int rc = deinterlace_ready(b->c[i]);
+        if (rc) return rc;
+    }
     if (host) {
         const int rc = batch_stage_ready(b);
         if (rc) return rc;
@@ -239,6 +244,8 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     const void *py[MAX_BATCH], *pu[MAX_BATCH], *pv[MAX_BATCH];
     const ScalePlan *plans[MAX_BATCH];
     ConvertItem cv[MAX_BATCH];
+    DeinterlaceItem di[MAX_BATCH];
+    hipStream_t ps = b->prep ? b->prep : b->stream;      // the stream the members' frames are taken in on
     int n = 0;
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
@@ -248,10 +255,10 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         plans[n] = &b->c[i]->scale;
         py[n] = y[i]; pu[n] = u[i]; pv[n] = v[i];
         convert_item(b->c[i], cv[n], py[n], pu[n], pv[n]);      // (a source format: the pack reads the member's converted planes)
+        (void)deinterlace_item(b->c[i], ps, di[n], py[n], pu[n], pv[n]);      // (a deinterlacer: ... the member's deinterlaced planes; same_intake: all or none)
         ++n;
     }
     if (!n) return VP8HIP_OK;
-    hipStream_t ps = b->stream;
     if (b->prep) {
         // A new frame goes into the surface (and its parameters into the blocks) of the frame before the previous one: all
         // of that frame's work -- enqueued on `stream` before the PREVIOUS frame call began, which is where ev_gate was last
@@ -262,7 +269,6 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         b->ev_gate = b->ev_gate2;
         b->ev_gate2 = t_;
         b->prep_pending = true;
-        ps = b->prep;
     }
     if (host) HIPCHK(c0, hipStreamWaitEvent(ps, b->ev_copied, 0));
     if (c0->src_fmt) {      // one launch for all members, in front of the pack or scale launch
@@ -270,6 +276,12 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         incoming_size(c0, &sw, &sh);
         Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
         if (!launch_convert_batch(ps, c0->src_fmt, c0->src_colour, sw, sh, cv, n)) return VP8HIP_ERR_ARG;
+    }
+    if (c0->di_mode) {      // one launch for all members, behind the converter and in front of the pack or scale launch
+        int sw, sh;
+        incoming_size(c0, &sw, &sh);
+        Timed t(c0, VP8HIP_K_PACK);
+        launch_deinterlace_batch(ps, sw, sh, c0->di_keep, di, n);
     }
     {
         Timed t(c0, VP8HIP_K_PACK);

@@ -123,7 +123,7 @@ int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, cons
 }
 
 // what is still in flight may read the scaler's tables or a staging buffer: it ends first (the setters are not per-frame calls)
-static int scale_quiesce(vp8hip_ctx *c) {
+int scale_quiesce(vp8hip_ctx *c) {
     (void)hipSetDevice(c->device);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
@@ -164,33 +164,39 @@ bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u
 }
 
 int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind) {
-    if (c->src_fmt) {
-        { const int rc = format_stage_ready(c); if (rc) return rc; }
-        if (kind != hipMemcpyDeviceToDevice) {      // (the caller synchronises the stream before it returns: one buffer is enough)
-            size_t nb[3];
-            incoming_bytes(c, nb);
-            const size_t need = nb[0] + nb[1] + nb[2];
-            if (need > c->fmt_raw_bytes) {
-                { const int rc = scale_quiesce(c); if (rc) return rc; }
-                uint8_t *d = nullptr;
-                HIPCHK(c, hipMalloc(&d, need));
-                (void)hipFree(c->fmt_raw);
-                c->fmt_raw = d;
-                c->fmt_raw_bytes = need;
-            }
-            uint8_t *d = c->fmt_raw;
-            HIPCHK(c, hipMemcpyAsync(d, y, nb[0], kind, c->stream));
-            if (nb[1]) HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], kind, c->stream));      // (the packed formats have one plane)
-            if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], kind, c->stream));
-            y = d; u = d + nb[0]; v = d + nb[0] + nb[1];
-            kind = hipMemcpyDeviceToDevice;
+    if (c->src_fmt) { const int rc = format_stage_ready(c); if (rc) return rc; }
+    if (c->di_mode) { const int rc = deinterlace_ready(c); if (rc) return rc; }
+    if ((c->src_fmt || c->di_mode) && kind != hipMemcpyDeviceToDevice) {      // (the caller synchronises the stream before it returns: one buffer is enough)
+        size_t nb[3];
+        incoming_bytes(c, nb);
+        const size_t need = nb[0] + nb[1] + nb[2];
+        if (need > c->fmt_raw_bytes) {
+            { const int rc = scale_quiesce(c); if (rc) return rc; }
+            uint8_t *d = nullptr;
+            HIPCHK(c, hipMalloc(&d, need));
+            (void)hipFree(c->fmt_raw);
+            c->fmt_raw = d;
+            c->fmt_raw_bytes = need;
         }
-        int w, h;
-        incoming_size(c, &w, &h);
+        uint8_t *d = c->fmt_raw;
+        HIPCHK(c, hipMemcpyAsync(d, y, nb[0], kind, c->stream));
+        if (nb[1]) HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], kind, c->stream));      // (the packed formats have one plane)
+        if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], kind, c->stream));
+        y = d; u = d + nb[0]; v = d + nb[0] + nb[1];
+        kind = hipMemcpyDeviceToDevice;
+    }
+    int w, h;
+    incoming_size(c, &w, &h);
+    if (c->src_fmt) {
         ConvertItem it;
         convert_item(c, it, y, u, v);
         Timed t(c, VP8HIP_K_PACK);      // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
         if (!launch_convert_batch(c->stream, c->src_fmt, c->src_colour, w, h, &it, 1)) return VP8HIP_ERR_ARG;
+    }
+    DeinterlaceItem di;
+    if (deinterlace_item(c, c->stream, di, y, u, v)) {      // (vp8hip_set_deinterlace: behind the converter, in front of the pack or scale launch)
+        Timed t(c, VP8HIP_K_PACK);
+        launch_deinterlace_batch(c->stream, w, h, c->di_keep, &di, 1);
     }
     return set_frame_planes(c, c->cur, y, u, v, kind, c->src_w, c->src_h, c->scale.in_w != 0);
 }
@@ -534,6 +540,9 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     hipFree(c->scale_stage);
     hipFree(c->fmt_stage);
     hipFree(c->fmt_raw);
+    hipFree(c->di_stage);
+    hipFree(c->di_hist[0]);
+    hipFree(c->di_hist[1]);
     shard_release(c);
     event_pool_put(c->device, c->ev, c->ev_made);
     hipFree(c->pixel_pool);
@@ -545,9 +554,11 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     if (c->h_verdict) hipHostFree(c->h_verdict);
     if (c->h_quality) hipHostFree(c->h_quality);
     if (c->h_dn) hipHostFree(c->h_dn);
+    if (c->h_di) hipHostFree(c->h_di);
     if (c->h_an) hipHostFree(c->h_an);
     hipFree(c->d_an);
     hipFree(c->d_dn);
+    hipFree(c->d_di);
     hipFree(c->d_quality);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
@@ -665,7 +676,7 @@ int vp8hip_set_source_size(vp8hip_ctx *c, int src_width, int src_height) {
         set_source(c, 0, 0, 0, 0, 0);
         return VP8HIP_OK;
     }
-    if (!source_size_ok(c, src_width, src_height)) return VP8HIP_ERR_ARG;
+    if (!source_size_ok(c, src_width, src_height) || (c->di_mode && src_height < 4)) return VP8HIP_ERR_ARG;      // (the deinterlacer needs a row of each field in every plane)
     set_source(c, src_width, src_height, 0, 0, 0);
     return VP8HIP_OK;
 }
@@ -674,7 +685,7 @@ int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int ds
     if (!c) return VP8HIP_ERR_ARG;
     if (!in_width && !in_height && !dst_width && !dst_height) return vp8hip_set_source_size(c, 0, 0);
     if (!source_size_ok(c, dst_width, dst_height) || (filter != 0 && filter != 1) || (in_width & 1) || (in_height & 1) ||
-        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384)
+        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384 || (c->di_mode && in_height < 4))
         return VP8HIP_ERR_ARG;
     if (in_width == dst_width && in_height == dst_height) return vp8hip_set_source_size(c, dst_width, dst_height);
     // everything that can be refused is tried before anything of the context changes

@@ -30,6 +30,7 @@ struct vp8drv {
     const uint8_t *staged = nullptr; // vp8drv_stage_frame_host: these planes are the context's current frame already (and, with scene_detect, their scan is under way)
     bool staged_scan = false;
     int denoise = 0;                 // vp8drv_set_denoise: the level in force
+    int deinterlace = 0, field = 0;  // vp8drv_set_deinterlace: the mode and the field kept
     int format = 0;                  // vp8drv_set_source_format: the format in force
     int colour = 0;                  // vp8drv_set_source_colour: the colour matrix in force (read by BGRA / RGBA only)
     bool analysis = false;           // vp8drv_set_analysis
@@ -309,6 +310,10 @@ int intake_restarts(vp8drv *d, bool scheduled_key) {
         const int rc = vp8hip_analysis_restart(d->hip);
         if (rc != VP8HIP_OK) return rc;
     }
+    if (d->deinterlace && scheduled_key) {      // vp8drv_set_deinterlace: and so does its history
+        const int rc = vp8hip_deinterlace_restart(d->hip);
+        if (rc != VP8HIP_OK) return rc;
+    }
     if (d->denoise && scheduled_key) return vp8hip_denoise_restart(d->hip);
     return VP8HIP_OK;
 }
@@ -421,7 +426,7 @@ int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, cons
 int vp8drv_stage_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
     { const int rc = resolve(d); if (rc < 0) return rc; }
-    if (d->denoise || d->analysis) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
+    if (d->denoise || d->analysis || d->deinterlace) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
         vp8host_gop g = d->gop;
         vp8host_gop_next(&g);
         DRV_CHK(intake_restarts(d, g.current_is_key != 0));
@@ -460,7 +465,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
             (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format || drv[i]->colour != drv[0]->colour ||
-            drv[i]->analysis != drv[0]->analysis)
+            drv[i]->analysis != drv[0]->analysis || drv[i]->deinterlace != drv[0]->deinterlace || drv[i]->field != drv[0]->field)
             return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
     }
@@ -633,6 +638,16 @@ int vp8drv_set_denoise(vp8drv *d, int level) {
     return VP8HIP_OK;
 }
 
+int vp8drv_set_deinterlace(vp8drv *d, int mode, int keep) {
+    if (!d || mode < 0 || mode > 2 || (keep != 0 && keep != 1) || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_deinterlace(d->hip, mode, keep));
+    d->deinterlace = mode;
+    d->field = mode ? keep : 0;
+    return VP8HIP_OK;
+}
+
 int vp8drv_set_source_format(vp8drv *d, int format) {
     if (!d || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END ||
         !d->cfg.device_params)
@@ -696,6 +711,11 @@ int vp8drv_get_quantizer(const vp8drv *d, int32_t *qi_min, int32_t *qi_max) {
 int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s) {
     if (!d || !s) return VP8HIP_ERR_ARG;
     return vp8hip_denoise_result(d->hip, s);
+}
+
+int vp8drv_get_deinterlace_stats(vp8drv *d, vp8hip_deinterlace_stats *s) {
+    if (!d || !s) return VP8HIP_ERR_ARG;
+    return vp8hip_deinterlace_result(d->hip, s);
 }
 
 int vp8drv_ready(const vp8drv *d) { return !d || !d->verdict_pending || vp8hip_check_ssim_ready(d->hip); }

@@ -174,6 +174,32 @@ int vp8host_y4m_colourspace(const uint8_t *data, size_t size, int32_t *format) {
     return 0;
 }
 
+// the header line's I tag, read as the C tag is
+int vp8host_y4m_interlace(const uint8_t *data, size_t size, int32_t *field_order) {
+    if (!data || !field_order) return -1;
+    static const char magic[] = "YUV4MPEG2";
+    size_t end = 0;
+    while (end < size && data[end] != 0x0A) ++end;
+    if (end == size || end < 9 || memcmp(data, magic, 9) != 0 || (end > 9 && data[9] != 0x20)) return -1;
+    for (size_t a = 9; a < end;) {
+        while (a < end && data[a] == 0x20) ++a;
+        size_t b = a;
+        while (b < end && data[b] != 0x20) ++b;
+        if (b > a && data[a] == 'I') {
+            if (b - a != 2) return -1;
+            switch (data[a + 1]) {
+                case 'p': case '?': *field_order = VP8HOST_FIELDS_PROGRESSIVE; return 0;
+                case 't': *field_order = VP8HOST_FIELDS_TOP_FIRST; return 0;
+                case 'b': *field_order = VP8HOST_FIELDS_BOTTOM_FIRST; return 0;
+                default: return -1;      // Im: mixed
+            }
+        }
+        a = b;
+    }
+    *field_order = VP8HOST_FIELDS_PROGRESSIVE;
+    return 0;
+}
+
 namespace {
 
 // what a format is made of: two planes (interleaved chroma) or three, chroma subsampled horizontally / vertically, depth, and
@@ -569,6 +595,75 @@ extern "C" int vp8host_denoise_frame(const uint8_t *src_y, const uint8_t *src_u,
         if (hist_y != out_y) memmove(hist_y, out_y, ny);
         if (hist_u != out_u) memmove(hist_u, out_u, nc);
         if (hist_v != out_v) memmove(hist_v, out_v, nc);
+    }
+    return 0;
+}
+
+// The device's deinterlacer in plain C++ (include/vp8hip_host.h has the rule).
+namespace {
+
+// one tight plane of w x h; hist = nullptr: no history (output = the spatial value).  Returns the samples of missing rows left as they came.
+int deinterlace_plane(const uint8_t *src, const uint8_t *hist, uint8_t *out, int w, int h, int keep) {
+    const int n = (h - keep + 1) / 2;      // kept rows: 2 j + keep < h
+    int woven = 0;
+    for (int y = 0; y < h; ++y) {
+        const uint8_t *row = src + (size_t)y * w;
+        uint8_t *o = out + (size_t)y * w;
+        if ((y & 1) == keep) {
+            memcpy(o, row, (size_t)w);
+            continue;
+        }
+        const int j0 = (y - 1 - keep) >> 1;      // (arithmetic: -1 for y = 0, keep = 1)
+        const uint8_t *tap[4];
+        for (int k = 0; k < 4; ++k) {
+            int j = j0 - 1 + k;
+            j = j < 0 ? 0 : (j > n - 1 ? n - 1 : j);
+            tap[k] = src + (size_t)(2 * j + keep) * w;
+        }
+        const int ya = y > 0 ? y - 1 : 0, yb = y < h - 1 ? y + 1 : h - 1;
+        for (int x = 0; x < w; ++x) {
+            int s = (-tap[0][x] + 9 * tap[1][x] + 9 * tap[2][x] - tap[3][x] + 8) >> 4;
+            s = s < 0 ? 0 : (s > 255 ? 255 : s);
+            if (hist) {
+                auto d = [&](int r) { const int v = (int)src[(size_t)r * w + x] - (int)hist[(size_t)r * w + x]; return v < 0 ? -v : v; };
+                int m = d(y);
+                if (d(ya) > m) m = d(ya);
+                if (d(yb) > m) m = d(yb);
+                const int wv = row[x], lo = wv - m, hi = wv + m;
+                s = s < lo ? lo : (s > hi ? hi : s);
+                woven += s == wv;
+            }
+            o[x] = (uint8_t)s;
+        }
+    }
+    return woven;
+}
+
+}  // namespace
+
+extern "C" int vp8host_deinterlace_frame(const uint8_t *src_y, const uint8_t *src_u, const uint8_t *src_v, uint8_t *hist_y, uint8_t *hist_u,
+                                         uint8_t *hist_v, uint8_t *out_y, uint8_t *out_u, uint8_t *out_v, int width, int height, int mode,
+                                         int keep, int have_history, int32_t *woven) {
+    if (!src_y || !src_u || !src_v || !out_y || !out_u || !out_v || !woven || width < 2 || height < 4 || (width & 1) || (height & 1) ||
+        mode < 0 || mode > 2 || (keep != 0 && keep != 1) || (mode == 2 && (!hist_y || !hist_u || !hist_v)))
+        return -1;
+    const int cw = width / 2, ch = height / 2;
+    const size_t ny = (size_t)width * height, nc = (size_t)cw * ch;
+    *woven = 0;
+    if (!mode) {
+        if (out_y != src_y) memmove(out_y, src_y, ny);
+        if (out_u != src_u) memmove(out_u, src_u, nc);
+        if (out_v != src_v) memmove(out_v, src_v, nc);
+        return 0;
+    }
+    const bool h = mode == 2 && have_history;
+    *woven = deinterlace_plane(src_y, h ? hist_y : nullptr, out_y, width, height, keep);
+    (void)deinterlace_plane(src_u, h ? hist_u : nullptr, out_u, cw, ch, keep);
+    (void)deinterlace_plane(src_v, h ? hist_v : nullptr, out_v, cw, ch, keep);
+    if (mode == 2) {
+        memmove(hist_y, src_y, ny);
+        memmove(hist_u, src_u, nc);
+        memmove(hist_v, src_v, nc);
     }
     return 0;
 }

@@ -133,6 +133,20 @@ struct vp8hip_ctx {
     vp8::DenoiseMirror dn_passed{};
     uint32_t dn_seq = 0;
     hipStream_t dn_stream = nullptr;
+    // vp8hip_set_deinterlace: the mode (0 = off) and the field kept.  k_deinterlace_b writes tight I420 of the incoming size into di_stage
+    // (planes laid out as in fmt_stage) and the pack or scale launch reads that.  Mode 2's history, the previous frame AS RECEIVED, is
+    // di_hist[di_idx]; the launch that reads it copies the new frame into the other one and the two trade places.  di_hist_w x di_hist_h:
+    // the incoming size the history was taken at (another size: no history).  Planes from host memory pass through fmt_raw first.  The
+    // record: as the denoiser's (d_di the count / ticket word, h_di the host mirror, di_seq the launches so far).
+    int di_mode = 0, di_keep = 0;
+    bool di_have_history = false, di_taken = false;
+    uint8_t *di_stage = nullptr, *di_hist[2] = {nullptr, nullptr};
+    size_t di_stage_bytes = 0, di_hist_bytes = 0;
+    int di_idx = 0, di_hist_w = 0, di_hist_h = 0;
+    unsigned long long *d_di = nullptr;
+    vp8::DeinterlaceMirror *h_di = nullptr;
+    uint32_t di_seq = 0;
+    hipStream_t di_stream = nullptr;
     // vp8hip_set_analysis: the history plane (the luma of the previous frame taken in, tight, coded size), the five sum / ticket words of
     // k_analyse_src_b, the record's host mirror; the launches so far per part (each writes its number into its part's seq last) and the
     // frame each part was last launched for.  an_checked: check_SSIM ran on the reconstruction in flight (its verdict's device copy says
@@ -340,11 +354,13 @@ inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) {
 inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched convert / pack / scale launch takes as one value
     return a->src_fmt == b->src_fmt && a->src_colour == b->src_colour && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
            (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level &&     // (and one denoiser level)
+           a->di_mode == b->di_mode && a->di_keep == b->di_keep &&                                  // (one deinterlacer mode and parity)
            a->an_on == b->an_on;                                                                    // (analysis on for all or for none)
 }
 // vp8hip_set_source_format: the staging buffers at the context's incoming size (no-op for I420 or when they are large enough), and the
 // item of k_convert_b for planes in DEVICE memory: afterwards y, u, v are the I420 planes in fmt_stage.  false: I420, nothing to do.
 int format_stage_ready(vp8hip_ctx *c);
+int scale_quiesce(vp8hip_ctx *c);      // whatever is in flight on the context's streams (and its batch's head-of-frame stream) ends
 bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u, const void *&v);
 // a context's new current frame from planes in its source format: convert, pack or scale (the caller denoises)
 int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
@@ -389,6 +405,13 @@ int prof_collect(vp8hip_ctx *c);
 // is the history from now on); denoise_current: the launch for one context.
 bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it);
 void denoise_current(vp8hip_ctx *c);
+// ---- api_deinterlace.hip ----
+// The frame about to be packed or scaled passes through the deinterlacer (every way a frame becomes current calls these, behind its
+// convert launch and in front of its pack or scale launch, on the same stream).  deinterlace_ready: the staging and history buffers at
+// the context's incoming size, before anything of the call has changed state (VP8HIP_ERR_ARG: an incoming height below 4).
+// deinterlace_item: y, u, v = tight I420 in DEVICE memory; afterwards they are the planes in di_stage.  false: off, nothing to launch.
+int deinterlace_ready(vp8hip_ctx *c);
+bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const void *&y, const void *&u, const void *&v);
 // ---- api_analysis.hip ----
 // The source side: the frame just taken into c->cur, behind its pack / scale / denoise launches on stream s (every way a frame becomes
 // current calls one of these).  The coding side: the attempt whose loop filter was just launched on s (c->lf_key says which kind).

@@ -187,6 +187,21 @@ void launch_analyse_mb_batch(hipStream_t s, const AnalysisMbItem *items, int n);
 // matrix the setters refuse -- nothing was launched and the staging buffer is NOT the frame.
 struct ConvertItem { const uint8_t *src[3]; uint8_t *dst[3]; };
 bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const ConvertItem *items, int n);
+// kernels_deinterlace.hip: interlaced source frames made progressive (vp8hip_set_deinterlace) BEHIND the convert launch and IN FRONT of
+// the pack or scale launch, which then reads dst as it reads a converted frame; the rule is include/vp8hip_host.h's.  src: tight I420
+// of w x h; hist: the previous frame as received (all nullptr: no history -- the spatial value everywhere); keep_hist: where this
+// frame goes verbatim, the next frame's history (all nullptr in mode 1); none of the four overlap.  `word` (zero at rest) takes the
+// count of woven luma samples and the waves' tickets; the wave with the last ticket writes the record into `host`, seq last.
+struct DeinterlaceMirror { int32_t frame_number, woven, missing; uint32_t seq; };
+struct DeinterlaceItem {
+    const uint8_t *src[3], *hist[3];
+    uint8_t *dst[3], *keep_hist[3];
+    unsigned long long *word;
+    DeinterlaceMirror *host;
+    uint32_t seq;
+    int32_t frame_number;
+};
+void launch_deinterlace_batch(hipStream_t s, int w, int h, int keep, const DeinterlaceItem *items, int n);
 bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int net_width, int n, bool finest, bool top_only = false);
 void launch_search1_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int level, int src_idx,
                           int net_width, int n);

@@ -37,6 +37,19 @@ def colourspace(data: bytes) -> int:
     return fmt.value
 
 
+def interlace(data: bytes) -> int:
+    """the field order (api.FIELDS_*) the header's I tag names: progressive without one, for Ip and for I?; raises ValueError, naming
+    the tag, for Im (mixed) and anything else"""
+    lib = api.load_library()
+    lib.vp8host_y4m_interlace.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
+    order = C.c_int32()
+    if lib.vp8host_y4m_interlace(data, len(data), C.byref(order)) != 0:
+        line = bytes(data).split(b"\n", 1)[0].split(b" ")
+        tag = next((t.decode("latin-1") for t in line[1:] if t.startswith(b"I")), None)
+        raise ValueError(f"interlace tag {tag}: not one of Ip, I?, It, Ib" if tag else "not a YUV4MPEG2 header line")
+    return order.value
+
+
 class Y4mFile:
     """frames of a .y4m file: .W, .H (the SOURCE size: hand them to an encoder created for the padded size with
     src_width / src_height), .framerate, .n, .format (api.FORMAT_*, from the C tag, or `fmt` for a file whose frames are NV12 /
