@@ -2,8 +2,9 @@
 // (k_analyse_src_b behind every intake, k_analyse_mb_b behind every loop filter; kernels_analysis.hip) and the record for the host.
 //
 // One device allocation: the five sum / ticket words of the source-side launch (256 bytes), then the history plane.  The host mirror
-// keeps TWO source-side records, by the frame number's parity: a host may hand frame n + 1 over while frame n's record is still to
-// be read (vp8drv_stage_frame_host), and frame n's coding side names the frame it belongs to.
+// (one allocation too; each of its three parts has a seq and a view of its own, vp8hip_ctx.h) keeps TWO source-side records, by the
+// frame number's parity: a host may hand frame n + 1 over while frame n's record is still to be read (vp8drv_stage_frame_host), and
+// frame n's coding side names the frame it belongs to.
 #include "vp8hip_ctx.h"
 
 using namespace vp8;
@@ -12,23 +13,8 @@ namespace vp8 {
 
 namespace {
 
-unsigned long long *analysis_acc(const vp8hip_ctx *c) { return reinterpret_cast<unsigned long long *>(c->d_an); }
-uint8_t *analysis_history(const vp8hip_ctx *c) { return c->d_an + 256; }
-
-// a launch's record is complete (its seq is there); polled like the quality record, with the stream's liveness looked at now and then
-int analysis_wait(vp8hip_ctx *c, const uint32_t *word, uint32_t want, hipStream_t s) {
-    for (unsigned spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != want; ++spins) {
-        if ((spins & 0xfff) == 0xfff) {
-            const hipError_t q = hipStreamQuery(s);
-            if (q != hipErrorNotReady && __atomic_load_n(word, __ATOMIC_ACQUIRE) != want) {
-                if (q != hipSuccess) { c->last_hip_error = (int)q; return VP8HIP_ERR_HIP; }
-                return VP8HIP_ERR_TIMEOUT;   // the stream is idle and the word never came
-            }
-        }
-        __builtin_ia32_pause();
-    }
-    return VP8HIP_OK;
-}
+unsigned long long *analysis_acc(const vp8hip_ctx *c) { return reinterpret_cast<unsigned long long *>(c->an.d); }
+uint8_t *analysis_history(const vp8hip_ctx *c) { return c->an.d + 256; }
 
 }  // namespace
 
@@ -38,20 +24,14 @@ bool analysis_src_item(vp8hip_ctx *c, hipStream_t s, AnalysisSrcItem &it) {
     it.cur = c->cur.Y[0];
     it.hist = analysis_history(c);
     it.acc = analysis_acc(c);
-    it.host = &c->h_an->src[k];
-    it.seq = ++c->an_src_seq;
+    it.host = c->an_src[k].h;
+    it.seq = c->an_src[k].seq = ++c->an_src_launches;
     it.frame_number = frame;
     it.have_prev = c->an_have_prev ? 1 : 0;
     c->an_have_prev = true;
-    c->an_src_want[k] = it.seq;
     c->an_src_frame[k] = frame;
-    c->an_src_stream[k] = s;
+    c->an_src[k].stream = s;
     return true;
-}
-
-void analysis_current(vp8hip_ctx *c) {
-    AnalysisSrcItem it;
-    if (analysis_src_item(c, c->stream, it)) launch_analyse_src_batch(c->stream, &it, 1);
 }
 
 bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it) {
@@ -66,13 +46,13 @@ bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it) {
     it.vec = c->out.vec;
     it.is_inter = c->intra_is_inter;
     it.replaced = (checked && !c->lf_key) ? c->intra_stats : nullptr;
-    it.host = &c->h_an->mb;
-    it.seq = ++c->an_mb_seq;
+    it.host = c->an_mb.h;
+    it.seq = ++c->an_mb.seq;
     it.frame_number = frame;
     it.is_key = c->lf_key ? 1 : 0;
     it.mbs = c->mbs;
     c->an_mb_frame = frame;
-    c->an_mb_stream = s;
+    c->an_mb.stream = s;
     return true;
 }
 
@@ -102,19 +82,13 @@ int vp8hip_set_analysis(vp8hip_ctx *c, int on) {
     if (on && c->shard_comm) return VP8HIP_ERR_STATE;      // (a context whose frames are split over devices codes only part of a frame)
     // a launch still in flight reads and writes the history and the record: it ends first (not a per-frame call)
     JOIN_LF(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
-    if (c->batch && c->batch->prep) HIPCHK(c, hipStreamSynchronize(c->batch->prep));
-    if (on && !c->d_an) {
-        uint8_t *d = nullptr;
-        AnalysisMirror *h = nullptr;
-        HIPCHK(c, hipMalloc(&d, 256 + (size_t)c->mbs * 256));
-        hipError_t e = hipMemset(d, 0, 256);
-        if (e == hipSuccess) e = hipHostMalloc(&h, sizeof(AnalysisMirror), hipHostMallocCoherent);
-        if (e != hipSuccess) { (void)hipFree(d); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
-        memset(h, 0, sizeof(*h));
-        c->d_an = d;
-        c->h_an = h;
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    if (on) {
+        const int rc = c->an.make(c, 256 + (size_t)c->mbs * 256, 256);
+        if (rc) return rc;
+        c->an_src[0].h = &c->an.h->src[0];
+        c->an_src[1].h = &c->an.h->src[1];
+        c->an_mb.h = &c->an.h->mb;
     }
     c->an_on = on != 0;
     c->an_have_prev = false;
@@ -135,13 +109,10 @@ int vp8hip_analysis_result(vp8hip_ctx *c, vp8hip_analysis *a) {
     if (!c->an_on || last < 0 || c->an_src_frame[last & 1] != last) return VP8HIP_ERR_STATE;
     const bool coded = c->an_mb_frame >= 0 && c->an_mb_frame >= last - 1 && c->an_src_frame[c->an_mb_frame & 1] == c->an_mb_frame;
     const int frame = coded ? c->an_mb_frame : last, k = frame & 1;
-    int rc = analysis_wait(c, &c->h_an->src[k].seq, c->an_src_want[k], c->an_src_stream[k]);
+    int rc = c->an_src[k].wait(c);
+    if (!rc && coded) rc = c->an_mb.wait(c);
     if (rc) return rc;
-    if (coded) {
-        rc = analysis_wait(c, &c->h_an->mb.seq, c->an_mb_seq, c->an_mb_stream);
-        if (rc) return rc;
-    }
-    const AnalysisSrcMirror s = c->h_an->src[k];
+    const AnalysisSrcMirror s = *c->an_src[k].h;
     memset(a, 0, sizeof(*a));
     a->frame_number = frame;
     a->have_prev = s.have_prev;
@@ -150,7 +121,7 @@ int vp8hip_analysis_result(vp8hip_ctx *c, vp8hip_analysis *a) {
     a->temporal_sse = s.sse;
     a->temporal_sad = s.sad;
     if (!coded) return VP8HIP_OK;
-    const AnalysisMbMirror m = c->h_an->mb;
+    const AnalysisMbMirror m = *c->an_mb.h;
     a->coded = 1;
     a->is_key = m.is_key;
     a->mbs_total = m.mbs_total;

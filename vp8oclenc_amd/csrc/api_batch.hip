@@ -126,7 +126,7 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
         hipEventDestroy(b->ev_copied);
         hipEventDestroy(b->ev_packed[0]);
         hipEventDestroy(b->ev_packed[1]);
-        for (int i = 0; i < b->n; ++i) { hipFree(b->stage[i][0]); hipFree(b->stage[i][1]); }
+        for (int i = 0; i < b->n; ++i) { b->stage[i][0].release(); b->stage[i][1].release(); }
     }
     if (b->ev_ent_fork) hipEventDestroy(b->ev_ent_fork);
     if (b->ev_ent) hipEventDestroy(b->ev_ent);
@@ -140,22 +140,6 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
         b->c[i]->counted = true;
     }
     delete b;
-}
-
-// one frame's planes into a staging buffer: ONE copy when they lie end to end in the host's memory (an I420 frame as a file reader or a
-// decoder holds it), three otherwise
-// (nb: the bytes of the three planes in the members' source format -- ny, nc, nc for I420; nb[2] == 0: two planes, v is not read)
-static int stage_copy(vp8hip_batch *b, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3]) {
-    vp8hip_ctx *c0 = b->c[0];
-    const uint8_t *py = static_cast<const uint8_t *>(y);
-    if (!nb[1] || (u == py + nb[0] && (!nb[2] || v == py + nb[0] + nb[1]))) {      // (one plane, or planes end to end)
-        HIPCHK(c0, hipMemcpyAsync(d, y, nb[0] + nb[1] + nb[2], hipMemcpyHostToDevice, b->copy));
-        return VP8HIP_OK;
-    }
-    HIPCHK(c0, hipMemcpyAsync(d, y, nb[0], hipMemcpyHostToDevice, b->copy));
-    HIPCHK(c0, hipMemcpyAsync(d + nb[0], u, nb[1], hipMemcpyHostToDevice, b->copy));
-    if (nb[2]) HIPCHK(c0, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], hipMemcpyHostToDevice, b->copy));
-    return VP8HIP_OK;
 }
 
 // the copy stream, its events and the members' staging buffers (two each), made on first use and again when the source size has changed
@@ -172,14 +156,13 @@ static int batch_stage_ready(vp8hip_batch *b) {
     }
     if (b->stage_bytes == bytes && b->stage_fmt == c0->src_fmt) return VP8HIP_OK;
     // (first call, or the source size or format has changed: nothing in flight reads the old buffers after this)
-    HIPCHK(c0, hipStreamSynchronize(b->copy));
-    HIPCHK(c0, hipStreamSynchronize(b->stream));
-    if (b->prep) HIPCHK(c0, hipStreamSynchronize(b->prep));
+    { const int rc = quiesce_intake(c0); if (rc) return rc; }
+    b->stage_bytes = 0;
     for (int i = 0; i < b->n; ++i)
         for (int k = 0; k < 2; ++k) {
-            (void)hipFree(b->stage[i][k]);
-            b->stage[i][k] = nullptr;
-            HIPCHK(c0, hipMalloc(&b->stage[i][k], bytes));
+            b->stage[i][k].release();
+            const int rc = b->stage[i][k].grow(c0, bytes);      // (quiesces once more, on idle streams: not a per-frame path)
+            if (rc) return rc;
         }
     b->stage_bytes = bytes;
     b->stage_fmt = c0->src_fmt;
@@ -193,25 +176,20 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     if (!b || !y || !u || !v) return VP8HIP_ERR_ARG;
     vp8hip_ctx *c0 = b->c[0];
     USE_DEVICE_ONLY(c0);
-    const void *sy[MAX_BATCH], *su[MAX_BATCH], *sv[MAX_BATCH];
-    int slot = -1;
+    vp8hip_ctx *m[MAX_BATCH];
+    const void *my[MAX_BATCH], *mu[MAX_BATCH], *mv[MAX_BATCH];      // the active members and their planes
+    int n = 0, slot = -1;
     // every member's pointers are looked at BEFORE anything changes: an error return must leave the staging slots, the prefetch record and
     // the members' current frames as they were (a retry that flipped stage_idx once more would pack an older frame from the other slot)
     for (int i = 0; i < b->n; ++i) {
         if (active && !active[i]) continue;
         if (!y[i] || !u[i] || !v[i]) return VP8HIP_ERR_ARG;
         if (!same_intake(b->c[i], c0)) return VP8HIP_ERR_ARG;   // one launch, one source format and size (and one scaler: incoming size, dst, filter)
+        m[n] = b->c[i];
+        my[n] = y[i]; mu[n] = u[i]; mv[n] = v[i];
+        ++n;
     }
-    for (int i = 0; i < b->n && c0->src_fmt; ++i) {      // vp8hip_set_source_format: the members' I420 staging buffers (as a rule: they are there)
-        if (active && !active[i]) continue;
-        const int rc = format_stage_ready(b->c[i]);
-        if (rc) return rc;
-    }
-    for (int i = 0; i < b->n && c0->di_mode; ++i) {      // vp8hip_set_deinterlace: the members' staging and history buffers (as a rule: they are there)
-        if (active && !active[i]) continue;
-        const int rc = deinterlace_ready(b->c[i]);
-        if (rc) return rc;
-    }
+    { const int rc = intake_ready(m, n); if (rc) return rc; }      // (take_frames would ask too -- behind the staging flip, which is too late to refuse)
     if (host) {
         const int rc = batch_stage_ready(b);
         if (rc) return rc;
@@ -219,14 +197,14 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         incoming_bytes(c0, nb);
         slot = b->stage_idx ^= 1;
         bool waited = false;
-        for (int i = 0; i < b->n; ++i) {
+        for (int i = 0, k = 0; i < b->n; ++i) {
             if (active && !active[i]) continue;
-            uint8_t *d = b->stage[i][slot];
+            uint8_t *d = b->stage[i][slot].p;
             if (!(b->pre_valid && b->pre[i][0] == y[i] && b->pre[i][1] == u[i] && b->pre[i][2] == v[i])) {   // not prefetched: copied now
                 if (!waited && b->packed_valid[slot]) HIPCHK(c0, hipStreamWaitEvent(b->copy, b->ev_packed[slot], 0));   // the pack of two frames ago has read this buffer
                 waited = true;
                 {
-                    const int cr = stage_copy(b, d, y[i], u[i], v[i], nb);
+                    const int cr = copy_planes(c0, d, y[i], u[i], v[i], nb, hipMemcpyHostToDevice, b->copy);
                     if (cr) {       // a failed copy: nothing of this call counts -- not the flip, not the prefetch
                         b->stage_idx ^= 1;
                         b->pre_valid = false;
@@ -234,31 +212,17 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
                     }
                 }
             }
-            sy[i] = d; su[i] = d + nb[0]; sv[i] = d + nb[0] + nb[1];
+            my[k] = d; mu[k] = d + nb[0]; mv[k] = d + nb[0] + nb[1];
+            ++k;
         }
         b->pre_valid = false;
         HIPCHK(c0, hipEventRecord(b->ev_copied, b->copy));
-        y = sy; u = su; v = sv;
     }
-    const Frame *f[MAX_BATCH];
-    const void *py[MAX_BATCH], *pu[MAX_BATCH], *pv[MAX_BATCH];
-    const ScalePlan *plans[MAX_BATCH];
-    ConvertItem cv[MAX_BATCH];
-    DeinterlaceItem di[MAX_BATCH];
-    hipStream_t ps = b->prep ? b->prep : b->stream;      // the stream the members' frames are taken in on
-    int n = 0;
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        flush_scan(b->c[i]);      // (a parameter scan of the frame that is being replaced, asked for and never used: on that frame, now)
-        next_current(b->c[i]);
-        f[n] = &b->c[i]->cur;
-        plans[n] = &b->c[i]->scale;
-        py[n] = y[i]; pu[n] = u[i]; pv[n] = v[i];
-        convert_item(b->c[i], cv[n], py[n], pu[n], pv[n]);      // (a source format: the pack reads the member's converted planes)
-        (void)deinterlace_item(b->c[i], ps, di[n], py[n], pu[n], pv[n]);      // (a deinterlacer: ... the member's deinterlaced planes; same_intake: all or none)
-        ++n;
-    }
+    // (a parameter scan of the frame that is being replaced, asked for and never used: on that frame, now -- on `stream`, in front of the
+    // gate below, so that the next call's head-of-frame work, which overwrites that frame's surface, waits for it)
+    for (int i = 0; i < n; ++i) flush_scan(m[i]);
     if (!n) return VP8HIP_OK;
+    hipStream_t ps = b->prep ? b->prep : b->stream;      // the stream the members' frames are taken in on
     if (b->prep) {
         // A new frame goes into the surface (and its parameters into the blocks) of the frame before the previous one: all
         // of that frame's work -- enqueued on `stream` before the PREVIOUS frame call began, which is where ev_gate was last
@@ -271,41 +235,7 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         b->prep_pending = true;
     }
     if (host) HIPCHK(c0, hipStreamWaitEvent(ps, b->ev_copied, 0));
-    if (c0->src_fmt) {      // one launch for all members, in front of the pack or scale launch
-        int sw, sh;
-        incoming_size(c0, &sw, &sh);
-        Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
-        if (!launch_convert_batch(ps, c0->src_fmt, c0->src_colour, sw, sh, cv, n)) return VP8HIP_ERR_ARG;
-    }
-    if (c0->di_mode) {      // one launch for all members, behind the converter and in front of the pack or scale launch
-        int sw, sh;
-        incoming_size(c0, &sw, &sh);
-        Timed t(c0, VP8HIP_K_PACK);
-        launch_deinterlace_batch(ps, sw, sh, c0->di_keep, di, n);
-    }
-    {
-        Timed t(c0, VP8HIP_K_PACK);
-        if (c0->scale.in_w) launch_scale_batch(ps, f, py, pu, pv, plans, n);      // a frame that is scaled is not packed as well
-        else launch_pack_batch(ps, f, py, pu, pv, n, c0->src_w, c0->src_h);
-    }
-    {   // vp8hip_set_denoise: the members that have a history, in one launch behind the pack (the others' frames pass through)
-        DenoiseItem dn[MAX_BATCH];
-        int nd = 0;
-        for (int i = 0; i < b->n; ++i) {
-            if (active && !active[i]) continue;
-            if (denoise_item(b->c[i], ps, dn[nd])) ++nd;
-        }
-        launch_denoise_batch(ps, dn, nd, c0->dn_level);
-    }
-    if (c0->an_on) {   // vp8hip_set_analysis: the members' source sides in one launch behind the denoiser
-        AnalysisSrcItem an[MAX_BATCH];
-        int na = 0;
-        for (int i = 0; i < b->n; ++i) {
-            if (active && !active[i]) continue;
-            if (analysis_src_item(b->c[i], ps, an[na])) ++na;
-        }
-        launch_analyse_src_batch(ps, an, na);
-    }
+    { const int rc = take_frames(m, my, mu, mv, n, ps); if (rc) return rc; }
     HIPCHK(c0, hipGetLastError());
     if (host) {
         HIPCHK(c0, hipEventRecord(b->ev_packed[slot], ps));
@@ -338,8 +268,7 @@ int vp8hip_batch_prefetch_current(vp8hip_batch *b, const uint8_t *const *y, cons
     for (int i = 0; i < b->n; ++i) {
         b->pre[i][0] = b->pre[i][1] = b->pre[i][2] = nullptr;
         if (!y[i] || !u[i] || !v[i]) continue;
-        uint8_t *d = b->stage[i][slot];
-        { const int cr = stage_copy(b, d, y[i], u[i], v[i], nb); if (cr) return cr; }
+        { const int cr = copy_planes(c0, b->stage[i][slot].p, y[i], u[i], v[i], nb, hipMemcpyHostToDevice, b->copy); if (cr) return cr; }
         b->pre[i][0] = y[i]; b->pre[i][1] = u[i]; b->pre[i][2] = v[i];
     }
     HIPCHK(c0, hipEventRecord(b->ev_copied, b->copy));

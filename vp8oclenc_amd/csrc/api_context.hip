@@ -1,5 +1,6 @@
-// api_context.hip -- the context: HBM surfaces, per-frame parameters, stream ordering, downloads, device memory for hosts that have none.
-// Replaces init_all()'s GPU half (init.h:133-312, 430-582, 595-1166), the uploads of vp8enc.cpp:386-401 and the read-backs of inter_part.h:263-265.
+// api_context.hip -- the context: HBM surfaces, per-frame parameters, stream ordering, the record wait, downloads, device memory for hosts that
+// have none.  Replaces init_all()'s GPU half (init.h:133-312, 430-582, 595-1166) and the read-backs of inter_part.h:263-265 (the uploads of
+// vp8enc.cpp:386-401: api_intake.hip).
 #include <dirent.h>
 #include <unistd.h>
 
@@ -24,14 +25,14 @@ uint8_t *carve(uint8_t *cursor, int w, int h, Plane *pl) {
     pl->stride = stride;
     pl->w = w;
     pl->h = h;
-    return cursor + (bytes + 255) / 256 * 256;
+    return cursor + round256(bytes);
 }
 
 size_t frame_bytes(int W, int H) {
     size_t n = 0;
     int s;
-    for (int l = 0; l < 5; ++l) n += (plane_bytes(W >> l, H >> l, &s) + 255) / 256 * 256;
-    n += 2 * ((plane_bytes(W / 2, H / 2, &s) + 255) / 256 * 256);
+    for (int l = 0; l < 5; ++l) n += round256(plane_bytes(W >> l, H >> l, &s));
+    n += 2 * round256(plane_bytes(W / 2, H / 2, &s));
     return n;
 }
 
@@ -82,123 +83,6 @@ int copy_in(vp8hip_ctx *c, const Plane &dst, const void *src, hipMemcpyKind kind
 int copy_out(vp8hip_ctx *c, void *dst, const Plane &src) {
     HIPCHK(c, hipMemcpy2DAsync(dst, src.w, src.p, src.stride, src.w, src.h, hipMemcpyDeviceToHost, c->stream));
     return VP8HIP_OK;
-}
-
-// sw, sh: size of the planes that come in (0 = the coded size): the current frames of a context with a source size
-// scaled: they come in at the scaler's incoming size and k_scale_b takes k_pack_b's place (planes from the host: through scale_stage,
-// a frame larger than the surface cannot be copied into the surface first)
-int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw, int sh, bool scaled) {
-    Timed t(c, VP8HIP_K_PACK);
-    if (scaled) {
-        const size_t ny = (size_t)c->scale.in_w * c->scale.in_h, nc = (size_t)(c->scale.in_w / 2) * (c->scale.in_h / 2);
-        if (kind != hipMemcpyDeviceToDevice) {
-            uint8_t *d = c->scale_stage;      // (the caller synchronises the stream before it returns: one buffer is enough)
-            HIPCHK(c, hipMemcpyAsync(d, y, ny, kind, c->stream));
-            HIPCHK(c, hipMemcpyAsync(d + ny, u, nc, kind, c->stream));
-            HIPCHK(c, hipMemcpyAsync(d + ny + nc, v, nc, kind, c->stream));
-            y = d; u = d + ny; v = d + ny + nc;
-        }
-        const Frame *fp = &f;
-        const ScalePlan *plan = &c->scale;
-        launch_scale_batch(c->stream, &fp, &y, &u, &v, &plan, 1);
-        return VP8HIP_OK;
-    }
-    if (kind == hipMemcpyDeviceToDevice) {
-        launch_pack(c->stream, f, y, u, v, sw, sh);
-        return VP8HIP_OK;
-    }
-    if (sw > 0) {
-        // the source rectangle into the surface, then copy_with_padding in place: the pack kernel with the surface as its own
-        // source (samples inside the rectangle are rewritten with themselves, the rest repeats the rectangle's edge)
-        HIPCHK(c, hipMemcpy2DAsync(f.Y[0].p, f.Y[0].stride, y, sw, sw, sh, kind, c->stream));
-        HIPCHK(c, hipMemcpy2DAsync(f.U.p, f.U.stride, u, sw / 2, sw / 2, sh / 2, kind, c->stream));
-        HIPCHK(c, hipMemcpy2DAsync(f.V.p, f.V.stride, v, sw / 2, sw / 2, sh / 2, kind, c->stream));
-        launch_pack(c->stream, f, f.Y[0].p, f.U.p, f.V.p, sw, sh, f.Y[0].stride, f.U.stride);
-        return VP8HIP_OK;
-    }
-    int rc;
-    if ((rc = copy_in(c, f.Y[0], y, kind))) return rc;
-    if ((rc = copy_in(c, f.U, u, kind))) return rc;
-    return copy_in(c, f.V, v, kind);
-}
-
-// what is still in flight may read the scaler's tables or a staging buffer: it ends first (the setters are not per-frame calls)
-int scale_quiesce(vp8hip_ctx *c) {
-    (void)hipSetDevice(c->device);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
-    if (c->h2d_stream) HIPCHK(c, hipStreamSynchronize(c->h2d_stream));
-    if (c->batch && c->batch->prep) HIPCHK(c, hipStreamSynchronize(c->batch->prep));
-    return VP8HIP_OK;
-}
-
-static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-int format_stage_ready(vp8hip_ctx *c) {
-    if (!c->src_fmt) return VP8HIP_OK;
-    int w, h;
-    incoming_size(c, &w, &h);
-    const size_t need = round256((size_t)w * h) + 2 * round256((size_t)(w / 2) * (h / 2));
-    if (need <= c->fmt_stage_bytes) return VP8HIP_OK;
-    { const int rc = scale_quiesce(c); if (rc) return rc; }      // (the incoming size has grown since the format was set: not a per-frame event)
-    uint8_t *d = nullptr;
-    HIPCHK(c, hipMalloc(&d, need));
-    (void)hipFree(c->fmt_stage);
-    c->fmt_stage = d;
-    c->fmt_stage_bytes = need;
-    return VP8HIP_OK;
-}
-
-bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u, const void *&v) {
-    if (!c->src_fmt) return false;
-    int w, h;
-    incoming_size(c, &w, &h);
-    it.src[0] = static_cast<const uint8_t *>(y);
-    it.src[1] = static_cast<const uint8_t *>(u);
-    it.src[2] = static_cast<const uint8_t *>(v);
-    it.dst[0] = c->fmt_stage;
-    it.dst[1] = it.dst[0] + round256((size_t)w * h);
-    it.dst[2] = it.dst[1] + round256((size_t)(w / 2) * (h / 2));
-    y = it.dst[0]; u = it.dst[1]; v = it.dst[2];
-    return true;
-}
-
-int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind) {
-    if (c->src_fmt) { const int rc = format_stage_ready(c); if (rc) return rc; }
-    if (c->di_mode) { const int rc = deinterlace_ready(c); if (rc) return rc; }
-    if ((c->src_fmt || c->di_mode) && kind != hipMemcpyDeviceToDevice) {      // (the caller synchronises the stream before it returns: one buffer is enough)
-        size_t nb[3];
-        incoming_bytes(c, nb);
-        const size_t need = nb[0] + nb[1] + nb[2];
-        if (need > c->fmt_raw_bytes) {
-            { const int rc = scale_quiesce(c); if (rc) return rc; }
-            uint8_t *d = nullptr;
-            HIPCHK(c, hipMalloc(&d, need));
-            (void)hipFree(c->fmt_raw);
-            c->fmt_raw = d;
-            c->fmt_raw_bytes = need;
-        }
-        uint8_t *d = c->fmt_raw;
-        HIPCHK(c, hipMemcpyAsync(d, y, nb[0], kind, c->stream));
-        if (nb[1]) HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], kind, c->stream));      // (the packed formats have one plane)
-        if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], kind, c->stream));
-        y = d; u = d + nb[0]; v = d + nb[0] + nb[1];
-        kind = hipMemcpyDeviceToDevice;
-    }
-    int w, h;
-    incoming_size(c, &w, &h);
-    if (c->src_fmt) {
-        ConvertItem it;
-        convert_item(c, it, y, u, v);
-        Timed t(c, VP8HIP_K_PACK);      // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
-        if (!launch_convert_batch(c->stream, c->src_fmt, c->src_colour, w, h, &it, 1)) return VP8HIP_ERR_ARG;
-    }
-    DeinterlaceItem di;
-    if (deinterlace_item(c, c->stream, di, y, u, v)) {      // (vp8hip_set_deinterlace: behind the converter, in front of the pack or scale launch)
-        Timed t(c, VP8HIP_K_PACK);
-        launch_deinterlace_batch(c->stream, w, h, c->di_keep, &di, 1);
-    }
-    return set_frame_planes(c, c->cur, y, u, v, kind, c->src_w, c->src_h, c->scale.in_w != 0);
 }
 
 void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask) {
@@ -355,6 +239,8 @@ void batch_join_prep(vp8hip_batch *b) {
     (void)hipEventRecord(b->ev_prep, b->prep);
     (void)hipStreamWaitEvent(b->stream, b->ev_prep, 0);
 }
+// (NOT wait_for_seq: this is no result somebody asked for -- it gives up silently as soon as the filter's stream is idle and sets no
+// error; the entry point that follows reports a stream that failed)
 void side_stream_ordered(vp8hip_ctx *c) {
     if (!c->lf_pending || !c->fork_by_verdict) return;
     const uint32_t want = c->verdict_seq;
@@ -391,6 +277,23 @@ int check_device_timeout(vp8hip_ctx *c) {
 }
 
 }  // namespace vp8
+
+// A launch writes its record into host memory the device sees and the sequence number last, at system scope: the host polls that word
+// and needs no event.  Every few thousand polls it looks whether the stream is still alive: a stream that is idle (or has failed)
+// while the word -- looked at once more -- is still not there never ran the launch's last workgroup.
+int wait_for_seq(vp8hip_ctx *c, const uint32_t *word, uint32_t want, hipStream_t s) {
+    for (unsigned spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != want; ++spins) {
+        if ((spins & 0xfff) == 0xfff) {
+            const hipError_t q = hipStreamQuery(s);
+            if (q != hipErrorNotReady && __atomic_load_n(word, __ATOMIC_ACQUIRE) != want) {
+                if (q != hipSuccess) { c->last_hip_error = (int)q; return VP8HIP_ERR_HIP; }
+                return VP8HIP_ERR_TIMEOUT;   // the stream is idle and the word never came
+            }
+        }
+        __builtin_ia32_pause();
+    }
+    return VP8HIP_OK;
+}
 
 extern "C" {
 
@@ -532,17 +435,16 @@ void vp8hip_destroy(vp8hip_ctx *c) {
         hipEventDestroy(c->ev_h2d);
         hipEventDestroy(c->ev_stage_read[0]);
         hipEventDestroy(c->ev_stage_read[1]);
-        hipFree(c->h2d_stage[0]);
-        hipFree(c->h2d_stage[1]);
+        c->h2d_stage[0].release();
+        c->h2d_stage[1].release();
     }
     if (c->ev_chroma) hipEventDestroy(c->ev_chroma);
     hipFree(c->scale.d_blob);
-    hipFree(c->scale_stage);
-    hipFree(c->fmt_stage);
-    hipFree(c->fmt_raw);
-    hipFree(c->di_stage);
-    hipFree(c->di_hist[0]);
-    hipFree(c->di_hist[1]);
+    c->fmt_stage.release();
+    c->raw_stage.release();
+    c->di_stage.release();
+    c->di_hist[0].release();
+    c->di_hist[1].release();
     shard_release(c);
     event_pool_put(c->device, c->ev, c->ev_made);
     hipFree(c->pixel_pool);
@@ -552,187 +454,12 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     if (c->h_frame) hipHostFree(c->h_frame);
     hipFree(c->d_frame);
     if (c->h_verdict) hipHostFree(c->h_verdict);
-    if (c->h_quality) hipHostFree(c->h_quality);
-    if (c->h_dn) hipHostFree(c->h_dn);
-    if (c->h_di) hipHostFree(c->h_di);
-    if (c->h_an) hipHostFree(c->h_an);
-    hipFree(c->d_an);
-    hipFree(c->d_dn);
-    hipFree(c->d_di);
-    hipFree(c->d_quality);
+    c->quality.release();
+    c->dn.release();
+    c->di.release();
+    c->an.release();      // (an_src and an_mb are parts of it)
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
-}
-
-// The next frame's planes started on their way while the current frame is coded (vp8hip_ctx.h): tight planes of the source size, one
-// copy when they lie end to end (an I420 frame as a file reader holds it), on a stream of their own into the staging buffer the pack
-// of two frames ago has finished with.  Touches nothing of the frame under way.
-int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
-    USE_DEVICE_ONLY(c);
-    if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
-    size_t nb[3];      // (the planes of the context's source format: ny, nc, nc for I420)
-    incoming_bytes(c, nb);
-    const size_t total = nb[0] + nb[1] + nb[2];
-    if (!c->h2d_stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage_read[0], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage_read[1], hipEventDisableTiming));
-    }
-    if (c->h2d_stage_bytes != total) {     // first use, or the source size has changed: whatever still reads the old buffers ends first
-        HIPCHK(c, hipStreamSynchronize(c->h2d_stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
-        for (int k = 0; k < 2; ++k) {
-            (void)hipFree(c->h2d_stage[k]);
-            c->h2d_stage[k] = nullptr;
-            HIPCHK(c, hipMalloc(&c->h2d_stage[k], total));
-        }
-        c->h2d_stage_bytes = total;
-        c->stage_read_valid[0] = c->stage_read_valid[1] = false;
-    }
-    const int slot = c->h2d_idx ^ 1;
-    if (c->stage_read_valid[slot]) HIPCHK(c, hipStreamWaitEvent(c->h2d_stream, c->ev_stage_read[slot], 0));
-    uint8_t *d = c->h2d_stage[slot];
-    if (!nb[1] || (u == y + nb[0] && (!nb[2] || v == u + nb[1]))) {      // (one plane, or planes end to end)
-        HIPCHK(c, hipMemcpyAsync(d, y, total, hipMemcpyHostToDevice, c->h2d_stream));
-    } else {
-        HIPCHK(c, hipMemcpyAsync(d, y, nb[0], hipMemcpyHostToDevice, c->h2d_stream));
-        HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], hipMemcpyHostToDevice, c->h2d_stream));
-        if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], hipMemcpyHostToDevice, c->h2d_stream));
-    }
-    HIPCHK(c, hipEventRecord(c->ev_h2d, c->h2d_stream));
-    c->h2d_pre[0] = y; c->h2d_pre[1] = u; c->h2d_pre[2] = v;
-    c->h2d_pre_valid = true;
-    return VP8HIP_OK;
-}
-
-int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
-    USE_DEVICE(c);
-    if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
-    size_t nb[3];
-    incoming_bytes(c, nb);
-    // a prefetch counts only for the source size and format it was made for: the staging buffers hold the planes' bytes of THAT size and the pack
-    // would read them with this one's offsets (vp8hip_set_source_size and vp8hip_set_source_format also drop a pending prefetch; this is the
-    // second lock on the same door)
-    if (c->h2d_pre_valid && c->h2d_stage_bytes == nb[0] + nb[1] + nb[2] && c->h2d_pre[0] == y && c->h2d_pre[1] == u && c->h2d_pre[2] == v) {
-        // prefetched: the planes are in (or on their way into) the staging buffer; the pack waits for the copy, nothing is copied here
-        c->h2d_pre_valid = false;
-        const int slot = c->h2d_idx ^= 1;
-        next_current(c);
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0));
-        const uint8_t *d = c->h2d_stage[slot];
-        const int rc = take_current(c, d, d + nb[0], d + nb[0] + nb[1], hipMemcpyDeviceToDevice);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->ev_stage_read[slot], c->stream));
-        denoise_current(c);
-        analysis_current(c);
-        c->stage_read_valid[slot] = true;
-        HIPCHK(c, hipEventSynchronize(c->ev_h2d));      // the host's planes are the host's again when this returns (done long ago, normally)
-        return VP8HIP_OK;
-    }
-    c->h2d_pre_valid = false;
-    next_current(c);
-    int rc = take_current(c, y, u, v, hipMemcpyHostToDevice);
-    if (rc) return rc;
-    denoise_current(c);
-    analysis_current(c);
-    // pageable host memory: the call must not return while the copy still reads the host buffer
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VP8HIP_OK;
-}
-
-int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const void *v) {
-    USE_DEVICE(c);
-    if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
-    next_current(c);
-    const int rc = take_current(c, y, u, v, hipMemcpyDeviceToDevice);
-    if (rc) return rc;
-    denoise_current(c);      // (vp8hip_set_denoise: right behind the pack, before anything else reads the frame)
-    analysis_current(c);     // (vp8hip_set_analysis: the frame as the searches will read it)
-    return VP8HIP_OK;
-}
-
-// dst of a scaler, or the source size: even, not above the coded size and fewer than 16 below it
-static bool source_size_ok(const vp8hip_ctx *c, int w, int h) {
-    return w > 0 && h > 0 && !(w & 1) && !(h & 1) && w <= c->W && h <= c->H && c->W - w < 16 && c->H - h < 16;
-}
-static void set_source(vp8hip_ctx *c, int w, int h, int in_w, int in_h, int kind) {
-    const bool same = w == c->W && h == c->H;
-    w = same ? 0 : w;
-    h = same ? 0 : h;
-    // planes prefetched at another incoming size are not this size's frame
-    if (w != c->src_w || h != c->src_h || in_w != c->scale.in_w || in_h != c->scale.in_h) c->h2d_pre_valid = false;
-    c->src_w = w;
-    c->src_h = h;
-    c->scale.in_w = in_w;
-    c->scale.in_h = in_h;
-    c->scale.kind = kind;
-}
-
-int vp8hip_set_source_size(vp8hip_ctx *c, int src_width, int src_height) {
-    if (!c) return VP8HIP_ERR_ARG;
-    if (src_width == 0 && src_height == 0) {
-        set_source(c, 0, 0, 0, 0, 0);
-        return VP8HIP_OK;
-    }
-    if (!source_size_ok(c, src_width, src_height) || (c->di_mode && src_height < 4)) return VP8HIP_ERR_ARG;      // (the deinterlacer needs a row of each field in every plane)
-    set_source(c, src_width, src_height, 0, 0, 0);
-    return VP8HIP_OK;
-}
-
-int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int dst_width, int dst_height, int filter) {
-    if (!c) return VP8HIP_ERR_ARG;
-    if (!in_width && !in_height && !dst_width && !dst_height) return vp8hip_set_source_size(c, 0, 0);
-    if (!source_size_ok(c, dst_width, dst_height) || (filter != 0 && filter != 1) || (in_width & 1) || (in_height & 1) ||
-        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384 || (c->di_mode && in_height < 4))
-        return VP8HIP_ERR_ARG;
-    if (in_width == dst_width && in_height == dst_height) return vp8hip_set_source_size(c, dst_width, dst_height);
-    // everything that can be refused is tried before anything of the context changes
-    ScalePlan plan;
-    std::vector<uint8_t> blob;
-    if (!scale_plan_make(&plan, in_width, in_height, dst_width, dst_height, c->W, c->H, filter, blob)) return VP8HIP_ERR_ARG;
-    { const int rc = scale_quiesce(c); if (rc) return rc; }
-    const size_t stage = (size_t)in_width * in_height + 2 * (size_t)(in_width / 2) * (in_height / 2);
-    uint8_t *d_blob = nullptr;
-    HIPCHK(c, hipMalloc(&d_blob, blob.size()));
-    if (stage > c->scale_stage_bytes) {
-        uint8_t *d_stage = nullptr;
-        const hipError_t e = hipMalloc(&d_stage, stage);
-        if (e != hipSuccess) { (void)hipFree(d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
-        (void)hipFree(c->scale_stage);
-        c->scale_stage = d_stage;
-        c->scale_stage_bytes = stage;
-    }
-    const hipError_t e = hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
-    (void)hipFree(c->scale.d_blob);
-    set_source(c, dst_width, dst_height, in_width, in_height, filter);
-    plan.d_blob = d_blob;
-    c->scale = plan;
-    return VP8HIP_OK;
-}
-
-int vp8hip_set_source_format(vp8hip_ctx *c, int format) {
-    if (!c || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END)
-        return VP8HIP_ERR_ARG;
-    if (format == c->src_fmt) return VP8HIP_OK;
-    { const int rc = scale_quiesce(c); if (rc) return rc; }
-    const int before = c->src_fmt;
-    c->src_fmt = format;
-    { const int rc = format_stage_ready(c); if (rc) { c->src_fmt = before; return rc; } }
-    c->h2d_pre_valid = false;      // planes prefetched in another format are not this format's frame
-    return VP8HIP_OK;
-}
-
-int vp8hip_set_source_colour(vp8hip_ctx *c, int matrix) {
-    if (!c || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT) return VP8HIP_ERR_ARG;
-    if (matrix == c->src_colour) return VP8HIP_OK;
-    { const int rc = scale_quiesce(c); if (rc) return rc; }
-    c->src_colour = matrix;
-    c->h2d_pre_valid = false;      // planes prefetched under another matrix are not this matrix's frame
-    if (c->batch) c->batch->pre_valid = false;
-    return VP8HIP_OK;
 }
 
 int vp8hip_loopfilter_strength(vp8hip_ctx *c, int32_t *reductor, int32_t *sharpness) {

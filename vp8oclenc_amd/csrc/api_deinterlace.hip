@@ -10,34 +10,22 @@ using namespace vp8;
 
 namespace vp8 {
 
-static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 int deinterlace_ready(vp8hip_ctx *c) {
     if (!c->di_mode) return VP8HIP_OK;
     int w, h;
     incoming_size(c, &w, &h);
     if (h < 4) return VP8HIP_ERR_ARG;
-    const size_t need = round256((size_t)w * h) + 2 * round256((size_t)(w / 2) * (h / 2));
-    const bool hist = c->di_mode == 2;
-    if (need <= c->di_stage_bytes && (!hist || need <= c->di_hist_bytes)) return VP8HIP_OK;
-    { const int rc = scale_quiesce(c); if (rc) return rc; }      // (first use, or the incoming size has grown: not a per-frame event)
-    if (need > c->di_stage_bytes) {
-        uint8_t *d = nullptr;
-        HIPCHK(c, hipMalloc(&d, need));
-        (void)hipFree(c->di_stage);
-        c->di_stage = d;
-        c->di_stage_bytes = need;
-    }
-    if (hist && need > c->di_hist_bytes) {
-        uint8_t *d[2] = {nullptr, nullptr};
-        HIPCHK(c, hipMalloc(&d[0], need));
-        const hipError_t e = hipMalloc(&d[1], need);
-        if (e != hipSuccess) { (void)hipFree(d[0]); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
-        (void)hipFree(c->di_hist[0]);
-        (void)hipFree(c->di_hist[1]);
-        c->di_hist[0] = d[0];
-        c->di_hist[1] = d[1];
-        c->di_hist_bytes = need;
+    const size_t need = tight_i420(w, h).bytes;      // (first use, or the incoming size has grown: not a per-frame event)
+    { const int rc = c->di_stage.grow(c, need); if (rc) return rc; }
+    if (c->di_mode == 2 && need > c->di_hist[0].bytes) {      // the two histories: both or neither
+        DeviceBuf d[2];
+        int rc = d[0].grow(c, need);
+        if (!rc) rc = d[1].grow(c, need);
+        if (rc) { d[0].release(); return rc; }
+        for (int k = 0; k < 2; ++k) {
+            c->di_hist[k].release();
+            c->di_hist[k] = d[k];
+        }
         c->di_have_history = false;
     }
     return VP8HIP_OK;
@@ -47,16 +35,15 @@ bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const v
     if (!c->di_mode) return false;
     int w, h;
     incoming_size(c, &w, &h);
-    const size_t oy = round256((size_t)w * h), oc = round256((size_t)(w / 2) * (h / 2));
-    const size_t off[3] = {0, oy, oy + oc};
+    const TightI420 t = tight_i420(w, h);
     const uint8_t *src[3] = {static_cast<const uint8_t *>(y), static_cast<const uint8_t *>(u), static_cast<const uint8_t *>(v)};
     const bool adaptive = c->di_mode == 2;
     const bool have = adaptive && c->di_have_history && c->di_hist_w == w && c->di_hist_h == h;
     for (int p = 0; p < 3; ++p) {
         it.src[p] = src[p];
-        it.dst[p] = c->di_stage + off[p];
-        it.hist[p] = have ? c->di_hist[c->di_idx] + off[p] : nullptr;
-        it.keep_hist[p] = adaptive ? c->di_hist[c->di_idx ^ 1] + off[p] : nullptr;
+        it.dst[p] = c->di_stage.p + t.off[p];
+        it.hist[p] = have ? c->di_hist[c->di_idx].p + t.off[p] : nullptr;
+        it.keep_hist[p] = adaptive ? c->di_hist[c->di_idx ^ 1].p + t.off[p] : nullptr;
     }
     if (adaptive) {      // the frame as received is the history from now on
         c->di_idx ^= 1;
@@ -64,35 +51,15 @@ bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const v
         c->di_hist_w = w;
         c->di_hist_h = h;
     }
-    it.word = c->d_di;
-    it.host = c->h_di;
-    it.seq = ++c->di_seq;
+    it.word = reinterpret_cast<unsigned long long *>(c->di.d);
+    it.host = c->di.h;
+    it.seq = ++c->di.seq;
     it.frame_number = c->cur_count - 1;
-    c->di_stream = s;
+    c->di.stream = s;
     c->di_taken = true;
     y = it.dst[0]; u = it.dst[1]; v = it.dst[2];
     return true;
 }
-
-namespace {
-
-// the last launch's record is complete (its seq is there); polled like the denoiser's record
-int deinterlace_wait(vp8hip_ctx *c) {
-    const uint32_t want = c->di_seq;
-    for (unsigned spins = 0; __atomic_load_n(&c->h_di->seq, __ATOMIC_ACQUIRE) != want; ++spins) {
-        if ((spins & 0xfff) == 0xfff) {
-            const hipError_t q = hipStreamQuery(c->di_stream);
-            if (q != hipErrorNotReady && __atomic_load_n(&c->h_di->seq, __ATOMIC_ACQUIRE) != want) {
-                if (q != hipSuccess) { c->last_hip_error = (int)q; return VP8HIP_ERR_HIP; }
-                return VP8HIP_ERR_TIMEOUT;   // the stream is idle and the word never came
-            }
-        }
-        __builtin_ia32_pause();
-    }
-    return VP8HIP_OK;
-}
-
-}  // namespace
 
 }  // namespace vp8
 
@@ -108,18 +75,8 @@ int vp8hip_set_deinterlace(vp8hip_ctx *c, int mode, int keep) {
     USE_DEVICE(c);
     if (mode == c->di_mode && (!mode || keep == c->di_keep)) return VP8HIP_OK;
     // a launch still in flight reads the history and writes the record: it ends first (not a per-frame call)
-    { const int rc = scale_quiesce(c); if (rc) return rc; }
-    if (mode && !c->d_di) {
-        unsigned long long *d = nullptr;
-        DeinterlaceMirror *h = nullptr;
-        HIPCHK(c, hipMalloc(&d, 256));
-        hipError_t e = hipMemset(d, 0, 256);
-        if (e == hipSuccess) e = hipHostMalloc(&h, sizeof(DeinterlaceMirror), hipHostMallocCoherent);
-        if (e != hipSuccess) { (void)hipFree(d); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
-        memset(h, 0, sizeof(*h));
-        c->d_di = d;
-        c->h_di = h;
-    }
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    if (mode) { const int rc = c->di.make(c, 256, 256); if (rc) return rc; }
     const int mode_before = c->di_mode, keep_before = c->di_keep;
     c->di_mode = mode;
     c->di_keep = keep;
@@ -141,9 +98,9 @@ int vp8hip_deinterlace_result(vp8hip_ctx *c, vp8hip_deinterlace_stats *s) {
     USE_DEVICE_ONLY(c);
     if (!c || !s) return VP8HIP_ERR_ARG;
     if (!c->di_mode || !c->di_taken) return VP8HIP_ERR_STATE;
-    const int rc = deinterlace_wait(c);
+    const int rc = c->di.wait(c);
     if (rc) return rc;
-    const DeinterlaceMirror m = *c->h_di;
+    const DeinterlaceMirror m = *c->di.h;
     s->frame_number = m.frame_number;
     s->woven = m.woven;
     s->missing = m.missing;

@@ -1,0 +1,317 @@
+// api_intake.hip -- how a frame becomes a context's current frame: the source size, scaling, format and colour setters, the staging
+// buffers, the stage order (take_frames: convert, deinterlace, scale or pack, denoise, analysis -- the one place that knows it), and the
+// single-context ways in (vp8hip_set_current_device, vp8hip_upload_current, vp8hip_prefetch_current).  A batch's ways in are api_batch.hip's;
+// they end in take_frames too.  Replaces the uploads of vp8enc.cpp:386-401.
+#include "vp8hip_ctx.h"
+
+using namespace vp8;
+
+// what is still in flight may read the scaler's tables, a staging buffer or a stage's history, or write a record: it ends first
+int vp8::quiesce_intake(vp8hip_ctx *c) {
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->lf_stream) HIPCHK(c, hipStreamSynchronize(c->lf_stream));
+    if (c->h2d_stream) HIPCHK(c, hipStreamSynchronize(c->h2d_stream));
+    if (c->batch && c->batch->prep) HIPCHK(c, hipStreamSynchronize(c->batch->prep));
+    if (c->batch && c->batch->copy) HIPCHK(c, hipStreamSynchronize(c->batch->copy));
+    return VP8HIP_OK;
+}
+
+int DeviceBuf::grow(vp8hip_ctx *c, size_t need) {
+    if (need <= bytes) return VP8HIP_OK;
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    uint8_t *d = nullptr;
+    HIPCHK(c, hipMalloc(&d, need));
+    (void)hipFree(p);
+    p = d;
+    bytes = need;
+    return VP8HIP_OK;
+}
+
+namespace vp8 {
+
+// sw, sh: size of the planes that come in (0 = the coded size): the current frames of a context with a source size
+int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw, int sh) {
+    Timed t(c, VP8HIP_K_PACK);
+    if (kind == hipMemcpyDeviceToDevice) {
+        launch_pack(c->stream, f, y, u, v, sw, sh);
+        return VP8HIP_OK;
+    }
+    if (sw > 0) {
+        // the source rectangle into the surface, then copy_with_padding in place: the pack kernel with the surface as its own
+        // source (samples inside the rectangle are rewritten with themselves, the rest repeats the rectangle's edge)
+        HIPCHK(c, hipMemcpy2DAsync(f.Y[0].p, f.Y[0].stride, y, sw, sw, sh, kind, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(f.U.p, f.U.stride, u, sw / 2, sw / 2, sh / 2, kind, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(f.V.p, f.V.stride, v, sw / 2, sw / 2, sh / 2, kind, c->stream));
+        launch_pack(c->stream, f, f.Y[0].p, f.U.p, f.V.p, sw, sh, f.Y[0].stride, f.U.stride);
+        return VP8HIP_OK;
+    }
+    int rc;
+    if ((rc = copy_in(c, f.Y[0], y, kind))) return rc;
+    if ((rc = copy_in(c, f.U, u, kind))) return rc;
+    return copy_in(c, f.V, v, kind);
+}
+
+int copy_planes(vp8hip_ctx *c, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3], hipMemcpyKind kind, hipStream_t s) {
+    const uint8_t *py = static_cast<const uint8_t *>(y);
+    if (!nb[1] || (u == py + nb[0] && (!nb[2] || v == py + nb[0] + nb[1]))) {      // (one plane, or planes end to end)
+        HIPCHK(c, hipMemcpyAsync(d, y, nb[0] + nb[1] + nb[2], kind, s));
+        return VP8HIP_OK;
+    }
+    HIPCHK(c, hipMemcpyAsync(d, y, nb[0], kind, s));
+    HIPCHK(c, hipMemcpyAsync(d + nb[0], u, nb[1], kind, s));
+    if (nb[2]) HIPCHK(c, hipMemcpyAsync(d + nb[0] + nb[1], v, nb[2], kind, s));
+    return VP8HIP_OK;
+}
+
+// vp8hip_set_source_format: the converter's output buffer at the context's incoming size (no-op for I420 or when it is large enough)
+static int format_stage_ready(vp8hip_ctx *c) {
+    if (!c->src_fmt) return VP8HIP_OK;
+    int w, h;
+    incoming_size(c, &w, &h);
+    return c->fmt_stage.grow(c, tight_i420(w, h).bytes);
+}
+
+// the item of k_convert_b for planes in DEVICE memory: afterwards y, u, v are the I420 planes in fmt_stage.  false: I420, nothing to do.
+static bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u, const void *&v) {
+    if (!c->src_fmt) return false;
+    int w, h;
+    incoming_size(c, &w, &h);
+    const TightI420 t = tight_i420(w, h);
+    const void *src[3] = {y, u, v};
+    for (int p = 0; p < 3; ++p) {
+        it.src[p] = static_cast<const uint8_t *>(src[p]);
+        it.dst[p] = c->fmt_stage.p + t.off[p];
+    }
+    y = it.dst[0]; u = it.dst[1]; v = it.dst[2];
+    return true;
+}
+
+int intake_ready(vp8hip_ctx *const *m, int n) {
+    for (int i = 0; i < n; ++i) {
+        int rc = format_stage_ready(m[i]);
+        if (!rc) rc = deinterlace_ready(m[i]);
+        if (rc) return rc;
+    }
+    return VP8HIP_OK;
+}
+
+int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u, const void *const *v, int n, hipStream_t s,
+                const hipMemcpyKind *alone, hipEvent_t planes_read) {
+    vp8hip_ctx *c0 = m[0];
+    { const int rc = intake_ready(m, n); if (rc) return rc; }
+    const Frame *f[MAX_BATCH];
+    const void *py[MAX_BATCH], *pu[MAX_BATCH], *pv[MAX_BATCH];
+    const ScalePlan *plans[MAX_BATCH];
+    ConvertItem cv[MAX_BATCH];
+    DeinterlaceItem di[MAX_BATCH];
+    for (int i = 0; i < n; ++i) {
+        next_current(m[i]);
+        f[i] = &m[i]->cur;
+        plans[i] = &m[i]->scale;
+        py[i] = y[i]; pu[i] = u[i]; pv[i] = v[i];
+        convert_item(m[i], cv[i], py[i], pu[i], pv[i]);      // (a source format: what follows reads the member's converted planes)
+        (void)deinterlace_item(m[i], s, di[i], py[i], pu[i], pv[i]);      // (a deinterlacer: ... the member's deinterlaced planes; same_intake: all or none)
+    }
+    int w, h;
+    incoming_size(c0, &w, &h);
+    if (c0->src_fmt) {      // one launch for all members, in front of the pack or scale launch
+        Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
+        if (!launch_convert_batch(s, c0->src_fmt, c0->src_colour, w, h, cv, n)) return VP8HIP_ERR_ARG;
+    }
+    if (c0->di_mode) {      // ... behind the converter and in front of the pack or scale launch
+        Timed t(c0, VP8HIP_K_PACK);
+        launch_deinterlace_batch(s, w, h, c0->di_keep, di, n);
+    }
+    if (c0->scale.in_w) {      // a frame that is scaled is not packed as well
+        Timed t(c0, VP8HIP_K_PACK);
+        launch_scale_batch(s, f, py, pu, pv, plans, n);
+    } else if (alone) {        // (s is the context's stream: the launch of one, or planes from the host straight into the surface)
+        const int rc = set_frame_planes(c0, c0->cur, py[0], pu[0], pv[0], *alone, c0->src_w, c0->src_h);
+        if (rc) return rc;
+    } else {
+        Timed t(c0, VP8HIP_K_PACK);
+        launch_pack_batch(s, f, py, pu, pv, n, c0->src_w, c0->src_h);
+    }
+    if (planes_read) HIPCHK(c0, hipEventRecord(planes_read, s));
+    {   // vp8hip_set_denoise: the members that have a history, in one launch behind the pack (the others' frames pass through)
+        DenoiseItem dn[MAX_BATCH];
+        int nd = 0;
+        for (int i = 0; i < n; ++i)
+            if (denoise_item(m[i], s, dn[nd])) ++nd;
+        launch_denoise_batch(s, dn, nd, c0->dn_level);
+    }
+    {   // vp8hip_set_analysis: the members' source sides in one launch behind the denoiser (the frame as the searches will read it)
+        AnalysisSrcItem an[MAX_BATCH];
+        int na = 0;
+        for (int i = 0; i < n; ++i)
+            if (analysis_src_item(m[i], s, an[na])) ++na;
+        launch_analyse_src_batch(s, an, na);
+    }
+    return VP8HIP_OK;
+}
+
+// one context's new current frame on its own stream; planes from the host that a convert, deinterlace or scale launch is to read pass
+// through raw_stage first (a frame larger than the surface cannot be copied into the surface)
+static int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind, hipEvent_t planes_read = nullptr) {
+    if (kind != hipMemcpyDeviceToDevice && (c->src_fmt || c->di_mode || c->scale.in_w)) {
+        size_t nb[3];
+        incoming_bytes(c, nb);
+        int rc = c->raw_stage.grow(c, nb[0] + nb[1] + nb[2]);
+        if (!rc) rc = copy_planes(c, c->raw_stage.p, y, u, v, nb, kind, c->stream);
+        if (rc) return rc;
+        y = c->raw_stage.p;
+        u = c->raw_stage.p + nb[0];
+        v = c->raw_stage.p + nb[0] + nb[1];
+        kind = hipMemcpyDeviceToDevice;
+    }
+    // (&kind: a context on its own, and where its planes are by now -- the host's only without a format, deinterlacer or scaler)
+    return take_frames(&c, &y, &u, &v, 1, c->stream, &kind, planes_read);
+}
+
+}  // namespace vp8
+
+extern "C" {
+
+// The next frame's planes started on their way while the current frame is coded (vp8hip_ctx.h): tight planes of the source size, one
+// copy when they lie end to end (an I420 frame as a file reader holds it), on a stream of their own into the staging buffer the pack
+// of two frames ago has finished with.  Touches nothing of the frame under way.
+int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
+    USE_DEVICE_ONLY(c);
+    if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
+    size_t nb[3];      // (the planes of the context's source format: ny, nc, nc for I420)
+    incoming_bytes(c, nb);
+    const size_t total = nb[0] + nb[1] + nb[2];
+    if (!c->h2d_stream) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage_read[0], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage_read[1], hipEventDisableTiming));
+    }
+    if (c->h2d_stage[0].bytes != total || c->h2d_stage[1].bytes != total) {     // first use, or the source size has changed: whatever still reads the old buffers ends first
+        { const int rc = quiesce_intake(c); if (rc) return rc; }
+        for (int k = 0; k < 2; ++k) {
+            c->h2d_stage[k].release();
+            const int rc = c->h2d_stage[k].grow(c, total);
+            if (rc) return rc;
+        }
+        c->stage_read_valid[0] = c->stage_read_valid[1] = false;
+    }
+    const int slot = c->h2d_idx ^ 1;
+    if (c->stage_read_valid[slot]) HIPCHK(c, hipStreamWaitEvent(c->h2d_stream, c->ev_stage_read[slot], 0));
+    { const int rc = copy_planes(c, c->h2d_stage[slot].p, y, u, v, nb, hipMemcpyHostToDevice, c->h2d_stream); if (rc) return rc; }
+    HIPCHK(c, hipEventRecord(c->ev_h2d, c->h2d_stream));
+    c->h2d_pre[0] = y; c->h2d_pre[1] = u; c->h2d_pre[2] = v;
+    c->h2d_pre_valid = true;
+    return VP8HIP_OK;
+}
+
+int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
+    USE_DEVICE(c);
+    if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
+    size_t nb[3];
+    incoming_bytes(c, nb);
+    // a prefetch counts only for the source size and format it was made for: the staging buffers hold the planes' bytes of THAT size and the pack
+    // would read them with this one's offsets (vp8hip_set_source_size and vp8hip_set_source_format also drop a pending prefetch; this is the
+    // second lock on the same door)
+    const int next = c->h2d_idx ^ 1;
+    if (c->h2d_pre_valid && c->h2d_stage[next].bytes == nb[0] + nb[1] + nb[2] && c->h2d_pre[0] == y && c->h2d_pre[1] == u && c->h2d_pre[2] == v) {
+        // prefetched: the planes are in (or on their way into) the staging buffer; the pack waits for the copy, nothing is copied here
+        c->h2d_pre_valid = false;
+        const int slot = c->h2d_idx = next;
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0));
+        const uint8_t *d = c->h2d_stage[slot].p;
+        const int rc = take_current(c, d, d + nb[0], d + nb[0] + nb[1], hipMemcpyDeviceToDevice, c->ev_stage_read[slot]);
+        if (rc) return rc;
+        c->stage_read_valid[slot] = true;
+        HIPCHK(c, hipEventSynchronize(c->ev_h2d));      // the host's planes are the host's again when this returns (done long ago, normally)
+        return VP8HIP_OK;
+    }
+    c->h2d_pre_valid = false;
+    const int rc = take_current(c, y, u, v, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    // pageable host memory: the call must not return while the copy still reads the host buffer
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const void *v) {
+    USE_DEVICE(c);
+    if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
+    return take_current(c, y, u, v, hipMemcpyDeviceToDevice);
+}
+
+// dst of a scaler, or the source size: even, not above the coded size and fewer than 16 below it
+static bool source_size_ok(const vp8hip_ctx *c, int w, int h) {
+    return w > 0 && h > 0 && !(w & 1) && !(h & 1) && w <= c->W && h <= c->H && c->W - w < 16 && c->H - h < 16;
+}
+static void set_source(vp8hip_ctx *c, int w, int h, int in_w, int in_h, int kind) {
+    const bool same = w == c->W && h == c->H;
+    w = same ? 0 : w;
+    h = same ? 0 : h;
+    // planes prefetched at another incoming size are not this size's frame
+    if (w != c->src_w || h != c->src_h || in_w != c->scale.in_w || in_h != c->scale.in_h) c->h2d_pre_valid = false;
+    c->src_w = w;
+    c->src_h = h;
+    c->scale.in_w = in_w;
+    c->scale.in_h = in_h;
+    c->scale.kind = kind;
+}
+
+int vp8hip_set_source_size(vp8hip_ctx *c, int src_width, int src_height) {
+    if (!c) return VP8HIP_ERR_ARG;
+    if (src_width == 0 && src_height == 0) {
+        set_source(c, 0, 0, 0, 0, 0);
+        return VP8HIP_OK;
+    }
+    if (!source_size_ok(c, src_width, src_height) || (c->di_mode && src_height < 4)) return VP8HIP_ERR_ARG;      // (the deinterlacer needs a row of each field in every plane)
+    set_source(c, src_width, src_height, 0, 0, 0);
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int dst_width, int dst_height, int filter) {
+    if (!c) return VP8HIP_ERR_ARG;
+    if (!in_width && !in_height && !dst_width && !dst_height) return vp8hip_set_source_size(c, 0, 0);
+    if (!source_size_ok(c, dst_width, dst_height) || (filter != 0 && filter != 1) || (in_width & 1) || (in_height & 1) ||
+        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384 || (c->di_mode && in_height < 4))
+        return VP8HIP_ERR_ARG;
+    if (in_width == dst_width && in_height == dst_height) return vp8hip_set_source_size(c, dst_width, dst_height);
+    // everything that can be refused is tried before anything of the context changes
+    ScalePlan plan;
+    std::vector<uint8_t> blob;
+    if (!scale_plan_make(&plan, in_width, in_height, dst_width, dst_height, c->W, c->H, filter, blob)) return VP8HIP_ERR_ARG;
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    uint8_t *d_blob = nullptr;
+    HIPCHK(c, hipMalloc(&d_blob, blob.size()));
+    const hipError_t e = hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
+    (void)hipFree(c->scale.d_blob);
+    set_source(c, dst_width, dst_height, in_width, in_height, filter);
+    plan.d_blob = d_blob;
+    c->scale = plan;
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_source_format(vp8hip_ctx *c, int format) {
+    if (!c || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END)
+        return VP8HIP_ERR_ARG;
+    if (format == c->src_fmt) return VP8HIP_OK;
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    const int before = c->src_fmt;
+    c->src_fmt = format;
+    { const int rc = format_stage_ready(c); if (rc) { c->src_fmt = before; return rc; } }
+    c->h2d_pre_valid = false;      // planes prefetched in another format are not this format's frame
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_source_colour(vp8hip_ctx *c, int matrix) {
+    if (!c || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT) return VP8HIP_ERR_ARG;
+    if (matrix == c->src_colour) return VP8HIP_OK;
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    c->src_colour = matrix;
+    c->h2d_pre_valid = false;      // planes prefetched under another matrix are not this matrix's frame
+    if (c->batch) c->batch->pre_valid = false;
+    return VP8HIP_OK;
+}
+
+}  // extern "C"

@@ -322,19 +322,10 @@ int vp8hip_check_ssim_result(vp8hip_ctx *c, int32_t *replaced, float *new_ssim, 
     volatile int32_t *v = c->h_verdict;
     const uint32_t want = c->verdict_seq;
     static const bool nowait = experiment_env("VP8HIP_EXPERIMENT_NOWAIT") != nullptr;   // timing experiment only: what the waiting costs
-    for (unsigned spins = 0; !nowait && (uint32_t)__atomic_load_n(&c->h_verdict[5], __ATOMIC_ACQUIRE) != want; ++spins) {
-        if ((spins & 0xfff) == 0xfff) {   // every few thousand polls: is the stream still alive?
-            const hipError_t q = hipStreamQuery(c->verdict_stream);
-            if (q != hipErrorNotReady && (uint32_t)__atomic_load_n(&c->h_verdict[5], __ATOMIC_ACQUIRE) != want) {
-                // the stream is idle (or failed) and the word never came: the launch did not run its verdict workgroup
-                c->verdict_pending = false;
-                if (q != hipSuccess) { c->last_hip_error = (int)q; return VP8HIP_ERR_HIP; }
-                return VP8HIP_ERR_TIMEOUT;
-            }
-        }
-        __builtin_ia32_pause();
-    }
+    // (an error: the stream is idle or failed and the word never came -- the launch did not run its verdict workgroup)
+    const int wr = nowait ? VP8HIP_OK : wait_for_seq(c, reinterpret_cast<const uint32_t *>(&c->h_verdict[5]), want, c->verdict_stream);
     c->verdict_pending = false;
+    if (wr) return wr;
     int32_t st[5];
     for (int i = 0; i < 5; ++i) st[i] = v[i];
     if (replaced) *replaced = st[0];

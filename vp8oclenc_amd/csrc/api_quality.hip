@@ -8,26 +8,10 @@ namespace vp8 {
 
 namespace {
 
-size_t quality_state_room() { return (sizeof(QualityState) + 255) & ~(size_t)255; }
-QualityState *quality_state(const vp8hip_ctx *c) { return reinterpret_cast<QualityState *>(c->d_quality); }
-unsigned *quality_ticket(const vp8hip_ctx *c) { return reinterpret_cast<unsigned *>(c->d_quality + quality_state_room()); }
-QualityPartial *quality_partial(const vp8hip_ctx *c) { return reinterpret_cast<QualityPartial *>(c->d_quality + quality_state_room() + 256); }
-
-// the last launch's mirror is complete (its seq is there); polled like check_SSIM's verdict, with the stream's liveness looked at now and then
-int quality_wait(vp8hip_ctx *c) {
-    const uint32_t want = c->quality_seq;
-    for (unsigned spins = 0; __atomic_load_n(&c->h_quality->seq, __ATOMIC_ACQUIRE) != want; ++spins) {
-        if ((spins & 0xfff) == 0xfff) {
-            const hipError_t q = hipStreamQuery(c->quality_stream);
-            if (q != hipErrorNotReady && __atomic_load_n(&c->h_quality->seq, __ATOMIC_ACQUIRE) != want) {
-                if (q != hipSuccess) { c->last_hip_error = (int)q; return VP8HIP_ERR_HIP; }
-                return VP8HIP_ERR_TIMEOUT;   // the stream is idle and the word never came
-            }
-        }
-        __builtin_ia32_pause();
-    }
-    return VP8HIP_OK;
-}
+size_t quality_state_room() { return round256(sizeof(QualityState)); }
+QualityState *quality_state(const vp8hip_ctx *c) { return reinterpret_cast<QualityState *>(c->quality.d); }
+unsigned *quality_ticket(const vp8hip_ctx *c) { return reinterpret_cast<unsigned *>(c->quality.d + quality_state_room()); }
+QualityPartial *quality_partial(const vp8hip_ctx *c) { return reinterpret_cast<QualityPartial *>(c->quality.d + quality_state_room() + 256); }
 
 }  // namespace
 
@@ -40,11 +24,11 @@ bool quality_item(vp8hip_ctx *c, const Frame &rec, hipStream_t s, QualityArgs &a
     a.partial = quality_partial(c);
     a.ticket = quality_ticket(c);
     a.state = quality_state(c);
-    a.host = c->h_quality;
-    a.seq = ++c->quality_seq;
+    a.host = c->quality.h;
+    a.seq = ++c->quality.seq;
     a.frame_number = c->cur_count - 1;
     a.is_key = c->lf_key ? 1 : 0;
-    c->quality_stream = s;
+    c->quality.stream = s;
     return true;
 }
 
@@ -79,17 +63,14 @@ int vp8hip_set_quality_stats(vp8hip_ctx *c, int on) {
         c->quality_on = on != 0;
         return VP8HIP_OK;
     }
-    if (!c->d_quality) {
-        HIPCHK(c, hipMalloc(&c->d_quality, quality_state_room() + 256 + sizeof(QualityPartial) * (size_t)quality_tiles(c->W, c->H)));
-        HIPCHK(c, hipHostMalloc(&c->h_quality, sizeof(QualityState), hipHostMallocCoherent));
-    }
+    { const int rc = c->quality.make(c, quality_state_room() + 256 + sizeof(QualityPartial) * (size_t)quality_tiles(c->W, c->H), 0); if (rc) return rc; }      // (zeroed below, with every new summary)
     // a new summary: nothing of an earlier measurement may still be on its way into the state or its mirror
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->quality_stream) HIPCHK(c, hipStreamSynchronize(c->quality_stream));
-    HIPCHK(c, hipMemsetAsync(c->d_quality, 0, quality_state_room() + 256, c->stream));
+    if (c->quality.stream) HIPCHK(c, hipStreamSynchronize(c->quality.stream));
+    HIPCHK(c, hipMemsetAsync(c->quality.d, 0, quality_state_room() + 256, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    memset(c->h_quality, 0, sizeof(QualityState));
-    c->quality_seq = 0;
+    memset(c->quality.h, 0, sizeof(QualityState));
+    c->quality.seq = 0;
     c->quality_on = true;
     return VP8HIP_OK;
 }
@@ -97,10 +78,10 @@ int vp8hip_set_quality_stats(vp8hip_ctx *c, int on) {
 int vp8hip_quality_result(vp8hip_ctx *c, vp8hip_quality *q) {
     USE_DEVICE_ONLY(c);
     if (!c || !q) return VP8HIP_ERR_ARG;
-    if (!c->quality_on || c->quality_seq == 0) return VP8HIP_ERR_STATE;
-    const int rc = quality_wait(c);
+    if (!c->quality_on || c->quality.seq == 0) return VP8HIP_ERR_STATE;
+    const int rc = c->quality.wait(c);
     if (rc) return rc;
-    *q = c->h_quality->pending;
+    *q = c->quality.h->pending;
     return VP8HIP_OK;
 }
 
@@ -108,11 +89,11 @@ int vp8hip_quality_summary(vp8hip_ctx *c, vp8hip_quality_totals *s) {
     USE_DEVICE_ONLY(c);
     if (!c || !s) return VP8HIP_ERR_ARG;
     if (!c->quality_on) return VP8HIP_ERR_STATE;
-    if (c->quality_seq) {
-        const int rc = quality_wait(c);
+    if (c->quality.seq) {
+        const int rc = c->quality.wait(c);
         if (rc) return rc;
     }
-    quality_totals(*c->h_quality, s);
+    quality_totals(*c->quality.h, s);
     return VP8HIP_OK;
 }
 
@@ -141,7 +122,7 @@ int vp8hip_debug_quality(vp8hip_ctx *c, int width, int height, const uint8_t *co
         }
     }
     const int tiles = quality_tiles(width, height);
-    const size_t room = (sizeof(QualityState) + 255) & ~(size_t)255;
+    const size_t room = quality_state_room();
     uint8_t *d = nullptr;
     HIPCHK(c, hipMalloc(&d, total + room + 256 + sizeof(QualityPartial) * (size_t)tiles));
     hipStream_t s = c->stream;

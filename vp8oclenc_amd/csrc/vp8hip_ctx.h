@@ -6,7 +6,9 @@
 // clEnqueueCopyBuffer + three clEnqueueCopyImage of inter_part.h:35-50,72-83), the vector nets,
 // the per-macroblock outputs, and one in-order HIP stream.
 //
-// Units: api_context.hip (create / destroy, surfaces, parameters, stream ordering, downloads, device memory),
+// Units: api_context.hip (create / destroy, surfaces, parameters, stream ordering, the record wait, downloads, device memory),
+// api_intake.hip (how a frame becomes current: source size / scaling / format / colour, staging, the stage order; upload, prefetch, set_current_device),
+// api_deinterlace.hip, api_denoise.hip, api_analysis.hip, api_quality.hip (a stage each: its items, its setters, its results),
 // api_inter.hip (inter path, check_SSIM, key frames, loop filter), api_entropy.hip (coefficient + header entropy stage, frames out),
 // api_batch.hip (vp8hip_batch_*), api_shard.hip (export / import, RCCL: vp8hip_shard_*, vp8hip_group_*), api_profile.hip (timers, debug taps).
 #ifndef VP8HIP_CTX_H
@@ -41,6 +43,8 @@ struct FrameSurf {
 }  // namespace vp8
 
 struct vp8hip_batch;
+struct vp8hip_ctx;
+inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
 // Device buffers that are made and freed together come out of ONE allocation: a context has forty of them, and forty hipMalloc + forty
 // hipFree -- each a trip through the driver, the frees synchronising -- were 11 ms to make a context and 15 ms to destroy it (48 chunks:
 // 1.2 s).  Every buffer starts 256-byte aligned and has a page of slack behind it.
@@ -50,7 +54,7 @@ struct DeviceArena {
     struct Want { void **p; size_t bytes; };
     std::vector<Want> wants;
     template <class T> void want(T **p, size_t n) { wants.push_back(Want{reinterpret_cast<void **>(p), n}); }
-    static size_t room(size_t n) { return ((n + 255) & ~(size_t)255) + 4096; }
+    static size_t room(size_t n) { return round256(n) + 4096; }
     hipError_t commit() {      // one hipMalloc; the pointers handed to want() are set
         size_t total = 0;
         for (const Want &w : wants) total += room(w.bytes);
@@ -64,6 +68,38 @@ struct DeviceArena {
     }
     void release() { if (base) (void)hipFree(base); base = nullptr; bytes = 0; }
 };
+
+// What a launch leaves for the host: a mirror in host memory the device writes, the mirror's seq last.  seq: the launches so far (the
+// last one writes this into h->seq); stream: the stream that one is on.  A view owns nothing: it is waited for, never released.
+template <class Mirror> struct RecordView {
+    Mirror *h = nullptr;
+    uint32_t seq = 0;
+    hipStream_t stream = nullptr;
+    int wait(vp8hip_ctx *c) const;     // the last launch's mirror is complete
+};
+// ... with what it owns: the mirror's allocation and the launch's device words (counts, tickets, state: zero at rest).
+template <class Mirror> struct Record : RecordView<Mirror> {
+    uint8_t *d = nullptr;
+    // (no-op once made; of a pair half made nothing is kept; zeroed_bytes 0: the caller zeroes the words itself)
+    int make(vp8hip_ctx *c, size_t device_bytes, size_t zeroed_bytes);
+    void release();
+};
+
+// A device buffer that grows when a setter or a larger incoming size asks for more (never per frame): whatever is in flight ends, the
+// new one is allocated, the old one freed.  On failure the old buffer and size stay.
+struct DeviceBuf {
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    int grow(vp8hip_ctx *c, size_t need);
+    void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
+// Tight I420 of w x h in one buffer, each plane 256-byte aligned: how fmt_stage, di_stage and di_hist hold a frame.
+struct TightI420 { size_t off[3], bytes; };
+inline TightI420 tight_i420(int w, int h) {
+    const size_t ny = round256((size_t)w * h), nc = round256((size_t)(w / 2) * (h / 2));
+    return TightI420{{0, ny, ny + nc}, ny + 2 * nc};
+}
 
 struct vp8hip_ctx {
     int W = 0, H = 0, mbw = 0, mbh = 0, mbs = 0, b8 = 0;
@@ -112,61 +148,52 @@ struct vp8hip_ctx {
     unsigned lf_simple_launches = 0;   // ... the simple filter's own window index (its counters are its own, LF_SIMPLE_WORD)
     int src_w = 0, src_h = 0;       // vp8hip_set_source_size: size of the planes handed over as current frames (0 = coded size)
     // vp8hip_set_source_scaling: current frames come in at scale.in_w x scale.in_h (0 = no scaling) and k_scale_b makes src_w x src_h of
-    // them (the coded size when those are 0); the tables live in scale.d_blob, planes from host memory pass through scale_stage
+    // them (the coded size when those are 0); the tables live in scale.d_blob
     vp8::ScalePlan scale;
-    uint8_t *scale_stage = nullptr;
-    size_t scale_stage_bytes = 0;
-    // vp8hip_set_source_format: what the three pointers of a current frame are (0 = I420: nothing below is used).  k_convert_b makes tight
-    // I420 of the incoming size of them in fmt_stage (Y, U, V at fmt_off, each plane 256-byte aligned) and the pack or scale launch
-    // reads that; planes from host memory that were not prefetched pass through fmt_raw first.
+    // vp8hip_set_source_format: what the three pointers of a current frame are (0 = I420: fmt_stage is not used).  k_convert_b makes tight
+    // I420 of the incoming size of them in fmt_stage (tight_i420) and the pack or scale launch reads that.
     // vp8hip_set_source_colour: the colour matrix BGRA / RGBA frames are read with (no other format looks at it).
     int src_fmt = 0, src_colour = 0;
-    uint8_t *fmt_stage = nullptr, *fmt_raw = nullptr;
-    size_t fmt_stage_bytes = 0, fmt_raw_bytes = 0;
+    DeviceBuf fmt_stage;
+    // planes from host memory that were not prefetched, on their way to a convert, deinterlace or scale launch, pass through here: the
+    // planes in the source format end to end (incoming_bytes; the call synchronises before it returns: one buffer is enough)
+    DeviceBuf raw_stage;
     // vp8hip_set_denoise: the level (0 = off); whether cur_prev holds a history (the previous frame taken in, as it left k_denoise_b, at
-    // this level); the count / ticket word of the launch, the record's host mirror and the launches so far (the last one writes
-    // dn_seq into the mirror's seq).  dn_host: the last frame taken in passed through and its record is the host's own.
+    // this level); the record (dn.d: the count / ticket word of the launch).  dn_host: the last frame taken in passed through and its
+    // record is the host's own.
     int dn_level = 0;
     bool dn_have_history = false, dn_taken = false, dn_host = false;
-    unsigned long long *d_dn = nullptr;
-    vp8::DenoiseMirror *h_dn = nullptr;
+    Record<vp8::DenoiseMirror> dn;
     vp8::DenoiseMirror dn_passed{};
-    uint32_t dn_seq = 0;
-    hipStream_t dn_stream = nullptr;
     // vp8hip_set_deinterlace: the mode (0 = off) and the field kept.  k_deinterlace_b writes tight I420 of the incoming size into di_stage
     // (planes laid out as in fmt_stage) and the pack or scale launch reads that.  Mode 2's history, the previous frame AS RECEIVED, is
-    // di_hist[di_idx]; the launch that reads it copies the new frame into the other one and the two trade places.  di_hist_w x di_hist_h:
-    // the incoming size the history was taken at (another size: no history).  Planes from host memory pass through fmt_raw first.  The
-    // record: as the denoiser's (d_di the count / ticket word, h_di the host mirror, di_seq the launches so far).
+    // di_hist[di_idx]; the launch that reads it copies the new frame into the other one and the two trade places (both of one size).
+    // di_hist_w x di_hist_h: the incoming size the history was taken at (another size: no history).  The record: as the denoiser's
+    // (di.d: the count / ticket word).
     int di_mode = 0, di_keep = 0;
     bool di_have_history = false, di_taken = false;
-    uint8_t *di_stage = nullptr, *di_hist[2] = {nullptr, nullptr};
-    size_t di_stage_bytes = 0, di_hist_bytes = 0;
+    DeviceBuf di_stage, di_hist[2];
     int di_idx = 0, di_hist_w = 0, di_hist_h = 0;
-    unsigned long long *d_di = nullptr;
-    vp8::DeinterlaceMirror *h_di = nullptr;
-    uint32_t di_seq = 0;
-    hipStream_t di_stream = nullptr;
-    // vp8hip_set_analysis: the history plane (the luma of the previous frame taken in, tight, coded size), the five sum / ticket words of
-    // k_analyse_src_b, the record's host mirror; the launches so far per part (each writes its number into its part's seq last) and the
-    // frame each part was last launched for.  an_checked: check_SSIM ran on the reconstruction in flight (its verdict's device copy says
-    // whether the fallback's flags count).
+    Record<vp8::DeinterlaceMirror> di;
+    // vp8hip_set_analysis: one allocation (an.d: the five sum / ticket words of k_analyse_src_b, then at +256 the history plane -- the luma
+    // of the previous frame taken in, tight, coded size) and one mirror (an.h) of three parts, each with a seq of its own: the views
+    // an_src[frame & 1] and an_mb point into an.h and hold the seq their part's last launch writes and its stream (`an` itself is never waited for).
+    // an_src_launches: source-side launches so far (the two an_src share the count).  an_src_frame, an_mb_frame: the frame each part was
+    // last launched for.  an_checked: check_SSIM ran on the reconstruction in flight (its verdict's device copy says whether the
+    // fallback's flags count).
     bool an_on = false, an_have_prev = false, an_checked = false;
-    uint8_t *d_an = nullptr;
-    vp8::AnalysisMirror *h_an = nullptr;
-    uint32_t an_src_seq = 0, an_mb_seq = 0, an_src_want[2] = {0, 0};
+    Record<vp8::AnalysisMirror> an;
+    RecordView<vp8::AnalysisSrcMirror> an_src[2];
+    RecordView<vp8::AnalysisMbMirror> an_mb;
+    uint32_t an_src_launches = 0;
     int an_src_frame[2] = {-1, -1}, an_mb_frame = -1;
-    hipStream_t an_src_stream[2] = {nullptr, nullptr}, an_mb_stream = nullptr;
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out
-    // vp8hip_set_quality_stats: the state, the per-wave partials and the ticket of k_quality (one allocation), the state's host mirror
+    // vp8hip_set_quality_stats: the record (quality.d: the state, the ticket and the per-wave partials of k_quality)
     bool quality_on = false;
     bool recon_key = false;         // the reconstruction in flight came from the intra path ...
     bool lf_key = false;            // ... and so did the last filtered one
-    uint8_t *d_quality = nullptr;
-    vp8::QualityState *h_quality = nullptr;
-    uint32_t quality_seq = 0;       // launches so far: the last one writes this into h_quality->seq
-    hipStream_t quality_stream = nullptr;   // ... on this stream
+    Record<vp8::QualityState> quality;
     void *scratch = nullptr;        // device staging for debug pyramid downloads
     // coefficient entropy stage: per-block flags and third contexts, token counts per partition, probabilities
     uint8_t *ent_flags = nullptr, *ent_third = nullptr;
@@ -206,8 +233,7 @@ struct vp8hip_ctx {
     hipEvent_t ev_chroma = nullptr;    // behind the fold of vp8hip_chroma_change_async
     bool chroma_pending = false, chroma_none = false;
     bool stage_read_valid[2] = {false, false};
-    uint8_t *h2d_stage[2] = {nullptr, nullptr};
-    size_t h2d_stage_bytes = 0;
+    DeviceBuf h2d_stage[2];            // (both of the planes' exact size: a prefetch counts only for the size it was made for)
     int h2d_idx = 0;
     const void *h2d_pre[3] = {nullptr, nullptr, nullptr};
     bool h2d_pre_valid = false;
@@ -265,8 +291,8 @@ struct vp8hip_batch {
     hipStream_t copy = nullptr;
     hipEvent_t ev_copied = nullptr, ev_packed[2] = {nullptr, nullptr};
     bool packed_valid[2] = {false, false};
-    uint8_t *stage[vp8::MAX_BATCH][2] = {};
-    size_t stage_bytes = 0;
+    DeviceBuf stage[vp8::MAX_BATCH][2];
+    size_t stage_bytes = 0;              // the planes' exact size all of them were made for (0: not all made)
     int stage_fmt = 0;                   // the source format the staging buffers' planes were laid out for
     int stage_idx = 0;
     // vp8hip_batch_prefetch_current: the NEXT frame's planes already on their way into the buffer the next upload will pack from
@@ -282,6 +308,30 @@ struct vp8hip_batch {
             return VP8HIP_ERR_HIP;                       \
         }                                                \
     } while (0)
+
+// The one wait for a word a launch writes last into host memory (api_context.hip): VP8HIP_OK once *word == want.
+int wait_for_seq(vp8hip_ctx *c, const uint32_t *word, uint32_t want, hipStream_t s);
+
+template <class Mirror> int Record<Mirror>::make(vp8hip_ctx *c, size_t device_bytes, size_t zeroed_bytes) {
+    if (d) return VP8HIP_OK;
+    uint8_t *nd = nullptr;
+    Mirror *nh = nullptr;
+    HIPCHK(c, hipMalloc(&nd, device_bytes));
+    hipError_t e = zeroed_bytes ? hipMemset(nd, 0, zeroed_bytes) : hipSuccess;
+    if (e == hipSuccess) e = hipHostMalloc(&nh, sizeof(Mirror), hipHostMallocCoherent);
+    if (e != hipSuccess) { (void)hipFree(nd); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
+    memset(nh, 0, sizeof(Mirror));
+    d = nd;
+    this->h = nh;
+    return VP8HIP_OK;
+}
+template <class Mirror> int RecordView<Mirror>::wait(vp8hip_ctx *c) const { return wait_for_seq(c, &h->seq, seq, stream); }
+template <class Mirror> void Record<Mirror>::release() {
+    if (this->h) (void)hipHostFree(this->h);
+    (void)hipFree(d);
+    this->h = nullptr;
+    d = nullptr;
+}
 
 namespace vp8 {
 
@@ -339,7 +389,22 @@ void note_queue_oversubscription();
 int pick_free_frame(const vp8hip_ctx *c);
 int copy_in(vp8hip_ctx *c, const Plane &dst, const void *src, hipMemcpyKind kind);
 int copy_out(vp8hip_ctx *c, void *dst, const Plane &src);
-int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw = 0, int sh = 0, bool scaled = false);
+void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask = 0);
+int make_last(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
+SegData *sd_for_writing(vp8hip_ctx *c);
+void next_params(vp8hip_ctx *c);
+void next_current(vp8hip_ctx *c);
+int join_ent(vp8hip_ctx *c);
+hipStream_t join_lf_swap(vp8hip_ctx *c);
+int join_lf_wait(vp8hip_ctx *c, hipStream_t side);
+bool side_sources_done(vp8hip_ctx *c);
+int join_lf(vp8hip_ctx *c, bool defer_ent = false);
+void flush_scan(vp8hip_ctx *c);
+void batch_join_prep(vp8hip_batch *b);
+void side_stream_ordered(vp8hip_ctx *c);
+int check_device_timeout(vp8hip_ctx *c);
+// ---- api_intake.hip: how a frame becomes current ----
+int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw = 0, int sh = 0);
 // size of the planes a context takes as current frames: the incoming size of its scaler, its source size, or the coded size
 inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) {
     *w = c->scale.in_w ? c->scale.in_w : (c->src_w ? c->src_w : c->W);
@@ -357,27 +422,21 @@ inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what
            a->di_mode == b->di_mode && a->di_keep == b->di_keep &&                                  // (one deinterlacer mode and parity)
            a->an_on == b->an_on;                                                                    // (analysis on for all or for none)
 }
-// vp8hip_set_source_format: the staging buffers at the context's incoming size (no-op for I420 or when they are large enough), and the
-// item of k_convert_b for planes in DEVICE memory: afterwards y, u, v are the I420 planes in fmt_stage.  false: I420, nothing to do.
-int format_stage_ready(vp8hip_ctx *c);
-int scale_quiesce(vp8hip_ctx *c);      // whatever is in flight on the context's streams (and its batch's head-of-frame stream) ends
-bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u, const void *&v);
-// a context's new current frame from planes in its source format: convert, pack or scale (the caller denoises)
-int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
-void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask = 0);
-int make_last(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
-SegData *sd_for_writing(vp8hip_ctx *c);
-void next_params(vp8hip_ctx *c);
-void next_current(vp8hip_ctx *c);
-int join_ent(vp8hip_ctx *c);
-hipStream_t join_lf_swap(vp8hip_ctx *c);
-int join_lf_wait(vp8hip_ctx *c, hipStream_t side);
-bool side_sources_done(vp8hip_ctx *c);
-int join_lf(vp8hip_ctx *c, bool defer_ent = false);
-void flush_scan(vp8hip_ctx *c);
-void batch_join_prep(vp8hip_batch *b);
-void side_stream_ordered(vp8hip_ctx *c);
-int check_device_timeout(vp8hip_ctx *c);
+// whatever is in flight on the context's streams (and its batch's) ends: setters and growing buffers, never per frame
+int quiesce_intake(vp8hip_ctx *c);
+// a frame's planes (nb: their bytes in the source format; a format of two planes or one never reads the later pointers) end to end into d,
+// on stream s: ONE copy when they lie end to end already (an I420 frame as a file reader or a decoder holds it)
+int copy_planes(vp8hip_ctx *c, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3], hipMemcpyKind kind, hipStream_t s);
+// the buffers the members' next frames need, at their incoming size (as a rule: they are there); changes nothing else
+int intake_ready(vp8hip_ctx *const *m, int n);
+// THE ORDER, once: n contexts of one intake (same_intake) take their new current frames in on stream s -- convert, deinterlace,
+// scale or pack, denoise, analysis.  y, u, v: the members' planes in DEVICE memory in their source format.
+// alone: nullptr for a batch's members.  For a context on its own (n == 1, s its stream) it points at where the planes are: such a
+// context keeps the pack launch of one, and without a format, deinterlacer or scaler its planes may be the host's, copied straight
+// into the surface.
+// planes_read (or nullptr) is recorded behind the pack or scale launch: nothing behind it reads the caller's planes.
+int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u, const void *const *v, int n, hipStream_t s,
+                const hipMemcpyKind *alone = nullptr, hipEvent_t planes_read = nullptr);
 // ---- api_inter.hip ----
 void drop_overflowed_frame(vp8hip_ctx *c);
 int inter_check(const vp8hip_ctx *c, int prev_is_golden, int prev_is_altref, int use_golden, int use_altref);
@@ -400,24 +459,20 @@ int adopt_last(vp8hip_ctx *c, int idx);
 // ---- api_profile.hip ----
 int prof_collect(vp8hip_ctx *c);
 // ---- api_denoise.hip ----
-// The frame just packed or scaled into c->cur passes through the denoiser (every way a frame becomes current calls one of these, right
-// behind the pack, on the pack's stream).  denoise_item: false = nothing to launch (off, or no history: the frame passes through and
-// is the history from now on); denoise_current: the launch for one context.
+// The frame just packed or scaled into c->cur passes through the denoiser (take_frames: right behind the pack, on the pack's stream).  denoise_item: false = nothing to launch (off, or no history: the frame passes through and
+// is the history from now on).
 bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it);
-void denoise_current(vp8hip_ctx *c);
 // ---- api_deinterlace.hip ----
-// The frame about to be packed or scaled passes through the deinterlacer (every way a frame becomes current calls these, behind its
-// convert launch and in front of its pack or scale launch, on the same stream).  deinterlace_ready: the staging and history buffers at
+// The frame about to be packed or scaled passes through the deinterlacer (take_frames: behind the convert launch and in front of the
+// pack or scale launch, on the same stream).  deinterlace_ready: the staging and history buffers at
 // the context's incoming size, before anything of the call has changed state (VP8HIP_ERR_ARG: an incoming height below 4).
 // deinterlace_item: y, u, v = tight I420 in DEVICE memory; afterwards they are the planes in di_stage.  false: off, nothing to launch.
 int deinterlace_ready(vp8hip_ctx *c);
 bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const void *&y, const void *&u, const void *&v);
 // ---- api_analysis.hip ----
-// The source side: the frame just taken into c->cur, behind its pack / scale / denoise launches on stream s (every way a frame becomes
-// current calls one of these).  The coding side: the attempt whose loop filter was just launched on s (c->lf_key says which kind).
+// The source side: the frame just taken into c->cur, behind its pack / scale / denoise launches on stream s (take_frames).  The coding side: the attempt whose loop filter was just launched on s (c->lf_key says which kind).
 // *_item: false = analysis off, nothing to launch.
 bool analysis_src_item(vp8hip_ctx *c, hipStream_t s, AnalysisSrcItem &it);
-void analysis_current(vp8hip_ctx *c);
 bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it);
 void analysis_after_filter(vp8hip_ctx *c, hipStream_t s);
 void batch_analysis(vp8hip_batch *b, const int *active);
