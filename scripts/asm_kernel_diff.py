@@ -2,9 +2,11 @@
 """Compare the instruction streams of kernels in two gfx950 assembly files (hipcc -S --cuda-device-only).
 
     scripts/asm_kernel_diff.py before.s after.s k_loop_filter3_b [k_other ...]
+    scripts/asm_kernel_diff.py --all before.s after.s            # every kernel of both files, by its full symbol
     scripts/asm_kernel_diff.py --loop one.s k_loop_filter3_b      # static size of the kernel's largest loop
 
-A kernel is named by a fragment of its symbol that must match exactly one kernel of each file.  Its stream is what lies
+A kernel is named by a fragment of its symbol that must match exactly one kernel of each file (--all needs no names: it pairs
+the kernels by their mangled symbols, template instantiations included, and fails if the two files' sets differ).  Its stream is what lies
 between its entry label and its s_endpgm-terminated end, without comments, directives and blank lines; labels and mangled
 symbols are renamed in order of first appearance, so streams that differ only in names compare equal.  Prints one line per
 kernel (instruction counts, identical or not) and a unified diff of the streams that differ; exit status 1 if any does."""
@@ -57,7 +59,27 @@ def largest_loop(lines):
     return best
 
 
+def report(name, b, a):
+    """one line for a pair of streams, and their diff if they differ; 1 if they do"""
+    same = b == a
+    print("%-28s %5d -> %5d instructions  %s" % (name, len(instructions(b)), len(instructions(a)), "identical" if same else "DIFFERENT"))
+    if not same:
+        sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(b, a, "before " + name, "after " + name, lineterm="", n=2))
+    return 0 if same else 1
+
+
 def main(argv):
+    if argv and argv[0] == "--all":
+        before, after = streams(argv[1]), streams(argv[2])
+        differ = 0
+        for k in sorted(set(before) | set(after)):
+            if k in before and k in after:
+                differ |= report(k, before[k], after[k])
+            else:
+                differ = 1
+                print("%-28s only in %s" % (k, argv[1] if k in before else argv[2]))
+        print("%d kernels in %s, %d in %s: %s" % (len(before), argv[1], len(after), argv[2], "DIFFERENT" if differ else "all identical"))
+        return differ
     if argv and argv[0] == "--loop":
         s = streams(argv[1])
         for frag in argv[2:]:
@@ -69,11 +91,7 @@ def main(argv):
     differ = 0
     for frag in argv[2:]:
         kb, ka = pick(before, frag), pick(after, frag)
-        same = before[kb] == after[ka]
-        print("%-28s %5d -> %5d instructions  %s" % (frag, len(instructions(before[kb])), len(instructions(after[ka])), "identical" if same else "DIFFERENT"))
-        if not same:
-            differ = 1
-            sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(before[kb], after[ka], kb, ka, lineterm="", n=2))
+        differ |= report(frag, before[kb], after[ka])
     return differ
 
 

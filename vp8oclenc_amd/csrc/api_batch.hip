@@ -24,6 +24,25 @@ bool batch_ent_stream(vp8hip_batch *b) {
     return b->ent != nullptr;
 }
 
+// The members a batched call is for: `active[i] == 0` leaves member i out of it (a chunk whose frame is a key frame goes through the
+// intra path), active == NULL means all.  m[k] is member pos[k] of the batch: what the caller passes per member (prev_is_golden[i],
+// refqi[i], params[i], the planes) is indexed by position.  Every entry point starts here, and every one keeps THE RULE: every
+// member is checked before any member's state changes -- a call that refuses leaves the batch as it found it.
+struct Members {
+    int n = 0;
+    vp8hip_ctx *m[MAX_BATCH];
+    int pos[MAX_BATCH];
+};
+static Members active_members(const vp8hip_batch *b, const int *active) {
+    Members a;
+    for (int i = 0; i < b->n; ++i) {
+        if (active && !active[i]) continue;
+        a.m[a.n] = b->c[i];
+        a.pos[a.n++] = i;
+    }
+    return a;
+}
+
 }  // namespace vp8
 
 extern "C" {
@@ -176,18 +195,18 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
     if (!b || !y || !u || !v) return VP8HIP_ERR_ARG;
     vp8hip_ctx *c0 = b->c[0];
     USE_DEVICE_ONLY(c0);
-    vp8hip_ctx *m[MAX_BATCH];
-    const void *my[MAX_BATCH], *mu[MAX_BATCH], *mv[MAX_BATCH];      // the active members and their planes
-    int n = 0, slot = -1;
-    // every member's pointers are looked at BEFORE anything changes: an error return must leave the staging slots, the prefetch record and
-    // the members' current frames as they were (a retry that flipped stage_idx once more would pack an older frame from the other slot)
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
+    const Members a = active_members(b, active);
+    vp8hip_ctx *const *m = a.m;
+    const int n = a.n;
+    const void *my[MAX_BATCH], *mu[MAX_BATCH], *mv[MAX_BATCH];      // the members' planes
+    int slot = -1;
+    // an error return must leave the staging slots, the prefetch record and the members' current frames as they were (a retry that
+    // flipped stage_idx once more would pack an older frame from the other slot)
+    for (int k = 0; k < n; ++k) {
+        const int i = a.pos[k];
         if (!y[i] || !u[i] || !v[i]) return VP8HIP_ERR_ARG;
-        if (!same_intake(b->c[i], c0)) return VP8HIP_ERR_ARG;   // one launch, one source format and size (and one scaler: incoming size, dst, filter)
-        m[n] = b->c[i];
-        my[n] = y[i]; mu[n] = u[i]; mv[n] = v[i];
-        ++n;
+        if (!same_intake(m[k], c0)) return VP8HIP_ERR_ARG;   // one launch, one source format and size (and one scaler: incoming size, dst, filter)
+        my[k] = y[i]; mu[k] = u[i]; mv[k] = v[i];
     }
     { const int rc = intake_ready(m, n); if (rc) return rc; }      // (take_frames would ask too -- behind the staging flip, which is too late to refuse)
     if (host) {
@@ -197,8 +216,8 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         incoming_bytes(c0, nb);
         slot = b->stage_idx ^= 1;
         bool waited = false;
-        for (int i = 0, k = 0; i < b->n; ++i) {
-            if (active && !active[i]) continue;
+        for (int k = 0; k < n; ++k) {
+            const int i = a.pos[k];
             uint8_t *d = b->stage[i][slot].p;
             if (!(b->pre_valid && b->pre[i][0] == y[i] && b->pre[i][1] == u[i] && b->pre[i][2] == v[i])) {   // not prefetched: copied now
                 if (!waited && b->packed_valid[slot]) HIPCHK(c0, hipStreamWaitEvent(b->copy, b->ev_packed[slot], 0));   // the pack of two frames ago has read this buffer
@@ -213,7 +232,6 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
                 }
             }
             my[k] = d; mu[k] = d + nb[0]; mv[k] = d + nb[0] + nb[1];
-            ++k;
         }
         b->pre_valid = false;
         HIPCHK(c0, hipEventRecord(b->ev_copied, b->copy));
@@ -286,49 +304,30 @@ int vp8hip_batch_upload_current(vp8hip_batch *b, const int *active, const uint8_
                              reinterpret_cast<const void *const *>(v), true);
 }
 
-// `active[i] == 0` leaves context i out of the stage (a chunk whose frame is a key frame goes through its own
-// vp8hip_intra_transform); active == NULL means all
 int vp8hip_batch_auto_segments(vp8hip_batch *b, const int *active, const int *is_key_frame, const int32_t (*refqi)[4], int qi_min) {
     if (!b || !is_key_frame || !refqi) return VP8HIP_ERR_ARG;
     vp8hip_ctx *c0 = b->c[0];
     USE_DEVICE_ONLY(c0);
-    const Frame *cur[MAX_BATCH];
-    uint32_t *partial[MAX_BATCH], *stats[MAX_BATCH];
-    SegData *sd[MAX_BATCH];
-    int32_t *strength[MAX_BATCH];
-    int key[MAX_BATCH];
-    int32_t qi[MAX_BATCH][4];
-    int n = 0;
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        vp8hip_ctx *c = b->c[i];
-        if (c->cur_count == 0) return VP8HIP_ERR_STATE;
-        next_params(c);
-        cur[n] = &c->cur;
-        partial[n] = c->d_stats + 8;
-        stats[n] = c->d_stats;
-        sd[n] = c->d_sd;
-        strength[n] = reinterpret_cast<int32_t *>(c->d_stats + 4);
-        key[n] = is_key_frame[i] ? 1 : 0;
-        for (int k = 0; k < 4; ++k) qi[n][k] = refqi[i][k];
-        ++n;
+    const Members a = active_members(b, active);
+    for (int k = 0; k < a.n; ++k)
+        if (a.m[k]->cur_count == 0) return VP8HIP_ERR_STATE;
+    ScanRequest q[MAX_BATCH];
+    for (int k = 0; k < a.n; ++k) {
+        next_params(a.m[k]);
+        q[k] = scan_request(a.m[k], is_key_frame[a.pos[k]], refqi[a.pos[k]], qi_min);
     }
     // The scan rides in k_search2's launch of the same frame (vp8hip_batch_inter_transform, next; kernels_s2.hip says why): with the part
     // full a launch of its own holds the batch's stream for half a millisecond where its work is 15 us (VP8HIP_BATCH_SCAN_LAUNCH=1: as it was)
     static const bool own_launch = [] { const char *v = getenv("VP8HIP_BATCH_SCAN_LAUNCH"); return v && v[0] == '1'; }();
-    if (n && !b->prep && !own_launch) {
-        int k = 0;
-        for (int i = 0; i < b->n; ++i) {
-            if (active && !active[i]) continue;
-            vp8hip_ctx *c = b->c[i];
-            c->scan_req = ScanRequest{partial[k], stats[k], sd[k], strength[k], key[k], {qi[k][0], qi[k][1], qi[k][2], qi[k][3]}, qi_min};
-            c->scan_deferred = true;
-            ++k;
+    if (a.n && !b->prep && !own_launch) {
+        for (int k = 0; k < a.n; ++k) {
+            a.m[k]->scan_req = q[k];
+            a.m[k]->scan_deferred = true;
         }
         return VP8HIP_OK;
     }
-    if (n && b->prep) b->prep_pending = true;
-    if (n) launch_auto_segments_batch(b->prep ? b->prep : b->stream, cur, partial, stats, sd, strength, key, qi, qi_min, n);
+    if (a.n && b->prep) b->prep_pending = true;
+    if (a.n) launch_auto_segments_batch(b->prep ? b->prep : b->stream, q, a.n);
     HIPCHK(c0, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -338,29 +337,26 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
     if (!b || !prev_is_golden || !prev_is_altref || !use_golden || !use_altref) return VP8HIP_ERR_ARG;
     vp8hip_ctx *c0 = b->c[0];
     USE_DEVICE_ONLY(c0);
-    vp8hip_ctx *m[MAX_BATCH];
-    RefSet refs[MAX_BATCH];
-    const Frame *cur[MAX_BATCH], *recon[MAX_BATCH], *pyr[2 * MAX_BATCH], *pyr_cur[MAX_BATCH];
-    const ScanRequest *scans[MAX_BATCH] = {};   // the members' parameter scans still waiting for a launch to ride in (vp8hip_batch_auto_segments)
-    int npyr_cur = 0;
-    const NetSet *nets[MAX_BATCH];
-    const MBOut *outs[MAX_BATCH];
-    const SegData *sds[MAX_BATCH];
-    int n = 0, npyr = 0;
-    uint32_t pyr_border = 0;
-    for (int i = 0; i < b->n; ++i) {   // every member is checked before any member's state changes
-        if (active && !active[i]) continue;
-        if (b->c[i]->conformant != c0->conformant) return VP8HIP_ERR_ARG;   // one launch, one predictor
-        const int rc = inter_check(b->c[i], prev_is_golden[i], prev_is_altref[i], use_golden[i], use_altref[i]);
+    const Members a = active_members(b, active);
+    vp8hip_ctx *const *m = a.m;
+    const int n = a.n;
+    for (int k = 0; k < n; ++k) {
+        const int i = a.pos[k];
+        if (m[k]->conformant != c0->conformant) return VP8HIP_ERR_ARG;   // one launch, one predictor
+        const int rc = inter_check(m[k], prev_is_golden[i], prev_is_altref[i], use_golden[i], use_altref[i]);
         if (rc) return rc;
     }
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        vp8hip_ctx *c = b->c[i];
+    CodingItem it[MAX_BATCH];      // (it[k].scan: the member's parameter scan still waiting for a launch to ride in, vp8hip_batch_auto_segments)
+    const Frame *pyr[2 * MAX_BATCH], *pyr_cur[MAX_BATCH];
+    int npyr = 0, npyr_cur = 0;
+    uint32_t pyr_border = 0;
+    for (int k = 0; k < n; ++k) {
+        const int i = a.pos[k];
+        vp8hip_ctx *c = m[k];
         const int rc = inter_begin(c, prev_is_golden[i], prev_is_altref[i], use_golden[i], use_altref[i]);
         if (rc) {   // (inter_check above has passed: not expected.)  The scans collected so far have not been launched: they wait again
-            for (int k = 0; k < n; ++k)
-                if (scans[k]) m[k]->scan_deferred = true;
+            for (int j = 0; j < k; ++j)
+                if (it[j].scan) m[j]->scan_deferred = true;
             return rc;
         }
         FrameSurf &last = c->frames[c->slot[0]];
@@ -382,17 +378,8 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
         last.pyramid_valid = true;
         last.border_valid = true;
         c->cur_pyramid_valid = true;
-        refs[n] = ref_set(c, 1, use_golden[i], use_altref[i]);
-        cur[n] = &c->cur;
-        recon[n] = &c->frames[c->recon].f;
-        nets[n] = &c->nets;
-        outs[n] = &c->out;
-        sds[n] = c->d_sd;
-        if (c->scan_deferred) {
-            scans[n] = &c->scan_req;
-            c->scan_deferred = false;      // (this call launches it: in k_search2's launch, or on its own right behind it)
-        }
-        m[n++] = c;
+        it[k] = coding_item(c, use_golden[i], use_altref[i]);
+        c->scan_deferred = false;      // (this call launches it: in k_search2's launch, or on its own right behind it)
     }
     if (!n) return VP8HIP_OK;
     hipStream_t s = b->stream;
@@ -415,29 +402,28 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
     int first_level = 4, src = 0;
     if (coarse_mode > 0 && c0->mbw >= 2 && c0->mbh >= 2) {
         Timed t(c0, VP8HIP_K_SEARCH1_L2);
-        if (launch_search1_coarse_batch(s, cur, refs, nets, net_width, n, coarse_mode == 2, coarse_mode == 3)) {
+        if (launch_search1_coarse_batch(s, it, n, net_width, coarse_mode == 2, coarse_mode == 3)) {
             first_level = coarse_mode == 2 ? -1 : (coarse_mode == 3 ? 1 : 0);
             src = first_level == 1 ? 1 : 0;      // level 1 reads net 1 (level 2's), level 0 reads net 0 (level 1's)
         }
     }
     for (int l = first_level; l >= 0; --l) {
         Timed t(c0, VP8HIP_K_SEARCH1_L4 + (4 - l));
-        launch_search1_batch(s, cur, refs, nets, l, src, net_width, n);
+        launch_search1_batch(s, it, n, l, src, net_width);
         src ^= 1;
     }
     bool carried;
     {
         Timed t(c0, VP8HIP_K_SEARCH2);
-        carried = launch_search2_batch(s, cur, refs, nets, n, s2_clock(c0), scans);
+        carried = launch_search2_batch(s, it, n, s2_clock(c0));
     }
-    for (int i = 0; i < n && !carried; ++i)
-        if (scans[i]) launch_auto_segments(s, m[i]->cur, scans[i]->partial, scans[i]->stats, scans[i]->sd, scans[i]->strength_out, scans[i]->is_key,
-                                           scans[i]->refqi, scans[i]->qi_min);
+    for (int k = 0; k < n && !carried; ++k)
+        if (it[k].scan) launch_auto_segments(s, *it[k].scan);
     {
         Timed t(c0, VP8HIP_K_MB);
-        launch_mb_batch(s, cur, refs, nets, recon, outs, sds, c0->ssim_target, c0->mbw, c0->mbh, n, c0->conformant != 0);
+        launch_mb_batch(s, it, n, c0->ssim_target, c0->mbw, c0->mbh, c0->conformant != 0);
     }
-    for (int i = 0; i < n; ++i) m[i]->recon_ready = true, m[i]->recon_key = false, m[i]->an_checked = false;
+    for (int k = 0; k < n; ++k) recon_made(m[k], false);
     HIPCHK(c0, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -446,55 +432,31 @@ int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active) {
     if (!b) return VP8HIP_ERR_ARG;
     vp8hip_ctx *c0 = b->c[0];
     USE_DEVICE(c0);   // (joins the head-of-frame stream)
-    vp8hip_ctx *m[MAX_BATCH];
-    const Frame *recon[MAX_BATCH];
-    const MBOut *outs[MAX_BATCH];
-    SegData *sds[MAX_BATCH];
-    int32_t *prog[MAX_BATCH];
-    void *hand[MAX_BATCH];
-    unsigned launch_no[MAX_BATCH];
-    LfCheck chk[MAX_BATCH];
-    int n = 0, type = -1;
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        if (!b->c[i]->recon_ready || b->c[i]->recon < 0) return VP8HIP_ERR_STATE;
-        if (type >= 0 && b->c[i]->lf_type != type) return VP8HIP_ERR_STATE;   // one launch, one filter: the members' types must agree
-        type = b->c[i]->lf_type;
-    }
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        vp8hip_ctx *c = b->c[i];
-        recon[n] = &c->frames[c->recon].f;
-        outs[n] = &c->out;
-        sds[n] = c->d_sd;
-        prog[n] = c->d_progress;
-        hand[n] = c->d_lf_handoff;
-        launch_no[n] = type == 1 ? c->lf_simple_launches++ : c->lf_launches++;
-        lf_check(c, chk[n]);
-        c->verdict_stream = b->stream;
-        m[n++] = c;
+    const Members a = active_members(b, active);
+    vp8hip_ctx *const *m = a.m;
+    const int n = a.n;
+    for (int k = 0; k < n; ++k) {
+        if (!m[k]->recon_ready || m[k]->recon < 0) return VP8HIP_ERR_STATE;
+        if (m[k]->lf_type != m[0]->lf_type) return VP8HIP_ERR_STATE;   // one launch, one filter: the members' types must agree
     }
     if (!n) return VP8HIP_OK;
+    FilterItem it[MAX_BATCH];
+    for (int k = 0; k < n; ++k) {
+        it[k] = filter_item(m[k]);
+        m[k]->verdict_stream = b->stream;
+    }
     // the entropy stage of these frames may start here (everything it reads has been enqueued), beside the filter
     if (b->ent) HIPCHK(c0, hipEventRecord(b->ev_ent_fork, b->stream));
     {
         Timed t(c0, VP8HIP_K_LOOP_FILTER);
         // (form 3 for batches: with the part full a launch's instructions and LDS count, not its latency; VP8HIP_LF_BATCH_FORM=4 for A/B runs)
         static const bool form4 = [] { const char *v = getenv("VP8HIP_LF_BATCH_FORM"); return v && atoi(v) == 4; }();
-        if (type == 1) launch_loop_filter_simple_batch(b->stream, recon, outs, sds, prog, c0->mbw, c0->mbh, launch_no, n, chk);
-        else if (form4) launch_loop_filter4_batch(b->stream, recon, outs, sds, prog, hand, c0->mbw, c0->mbh, launch_no, n, chk);
-        else launch_loop_filter3_batch(b->stream, recon, outs, sds, prog, c0->mbw, c0->mbh, launch_no, n, chk);
+        if (m[0]->lf_type == 1) launch_loop_filter_simple_batch(b->stream, it, n, c0->mbw, c0->mbh);
+        else if (form4) launch_loop_filter4_batch(b->stream, it, n, c0->mbw, c0->mbh);
+        else launch_loop_filter3_batch(b->stream, it, n, c0->mbw, c0->mbh);
     }
     b->ent_fork_fresh = b->ent != nullptr;
-    for (int i = 0; i < n; ++i) {   // the filtered reconstruction is the LAST reference of the next frame (vp8enc.cpp:395-401)
-        vp8hip_ctx *c = m[i];
-        c->frames[c->recon].pyramid_valid = false;
-        c->frames[c->recon].border_valid = false;   // its replicated edges are made with its pyramid, in one launch
-        c->slot[0] = c->recon;
-        c->lf_key = c->recon_key;
-        c->recon = -1;
-        c->recon_ready = false;
-    }
+    for (int k = 0; k < n; ++k) recon_filtered(m[k]);
     HIPCHK(c0, hipGetLastError());
     batch_analysis(b, active);         // (vp8hip_set_analysis: the members' coding sides, one launch behind the filter)
     return batch_quality(b, active);   // (the members with stats on: one launch behind the filter)
@@ -507,22 +469,20 @@ int vp8hip_batch_intra_transform(vp8hip_batch *b, const int *active) {
     if (!b) return VP8HIP_ERR_ARG;
     vp8hip_ctx *c0 = b->c[0];
     USE_DEVICE(c0);
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        if (b->c[i]->cur_count == 0) return VP8HIP_ERR_STATE;
-    }
+    const Members a = active_members(b, active);
+    vp8hip_ctx *const *m = a.m;
+    const int n = a.n;
+    for (int k = 0; k < n; ++k)
+        if (m[k]->cur_count == 0) return VP8HIP_ERR_STATE;
     CheckItem it[MAX_BATCH];
-    vp8hip_ctx *m[MAX_BATCH];
-    int n = 0;
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        vp8hip_ctx *c = b->c[i];
+    for (int j = 0; j < n; ++j) {
+        vp8hip_ctx *c = m[j];
         const int rc = claim_recon(c);
         if (rc) return rc;
         c->ent_counted_partitions = 0;
         drop_overflowed_frame(c);
         ++c->out_gen;
-        CheckItem &k = it[n];
+        CheckItem &k = it[j];
         k.cur = &c->cur;
         k.recon = &c->frames[c->recon].f;
         k.o = &c->out;
@@ -532,7 +492,6 @@ int vp8hip_batch_intra_transform(vp8hip_batch *b, const int *active) {
         k.prog = c->intra_prog;
         k.err = c->d_progress + LF_ERR_WORD;
         k.gen = ++c->intra_gen;
-        m[n++] = c;
     }
     if (!n) return VP8HIP_OK;
     {
@@ -543,7 +502,7 @@ int vp8hip_batch_intra_transform(vp8hip_batch *b, const int *active) {
         Timed t(c0, VP8HIP_K_FILTER_MASK);
         for (int i = 0; i < n; ++i) launch_filter_mask(b->stream, m[i]->out, m[i]->d_sd, m[i]->mbs);
     }
-    for (int i = 0; i < n; ++i) m[i]->recon_ready = true, m[i]->recon_key = true;
+    for (int k = 0; k < n; ++k) recon_made(m[k], true);
     HIPCHK(c0, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -552,17 +511,14 @@ int vp8hip_batch_check_ssim_async(vp8hip_batch *b, const int *active, const int3
     if (!b || !refqi) return VP8HIP_ERR_ARG;
     vp8hip_ctx *c0 = b->c[0];
     USE_DEVICE(c0);
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        const vp8hip_ctx *c = b->c[i];
+    const Members a = active_members(b, active);
+    const int n = a.n;
+    for (int k = 0; k < n; ++k) {
+        const vp8hip_ctx *c = a.m[k];
         if (!c->recon_ready || c->recon < 0 || c->cur_count == 0 || c->verdict_pending || c->chk_armed) return VP8HIP_ERR_STATE;
     }
     CheckItem it[MAX_BATCH];
-    int n = 0;
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        check_item(b->c[i], it[n++], refqi[i], qi_min);
-    }
+    for (int k = 0; k < n; ++k) check_item(a.m[k], it[k], refqi[a.pos[k]], qi_min);
     if (!n) return VP8HIP_OK;
     if (fallback_possible(c0->ssim_target)) {
         Timed t(c0, VP8HIP_K_INTRA);
@@ -585,20 +541,17 @@ int vp8hip_batch_encode_frame_begin(vp8hip_batch *b, const int *active, int num_
     USE_DEVICE(c0);
     FrameEntropy e[MAX_BATCH];
     FrameOut fo[MAX_BATCH];
-    vp8hip_ctx *m[MAX_BATCH];
-    int n = 0;
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        if (b->c[i]->frame_pending) return VP8HIP_ERR_STATE;
-    }
-    for (int i = 0; i < b->n; ++i) {
-        if (active && !active[i]) continue;
-        vp8hip_ctx *c = b->c[i];
-        const int rc = frame_prepare(c, P, &params[i], e[n], fo[n]);
+    const Members a = active_members(b, active);
+    vp8hip_ctx *const *m = a.m;
+    const int n = a.n;
+    for (int k = 0; k < n; ++k)
+        if (m[k]->frame_pending) return VP8HIP_ERR_STATE;
+    for (int k = 0; k < n; ++k) {
+        vp8hip_ctx *c = m[k];
+        const int rc = frame_prepare(c, P, &params[a.pos[k]], e[k], fo[k]);
         if (rc) return rc;
-        c->frame_params = params[i];
+        c->frame_params = params[a.pos[k]];
         c->frame_partitions = P;
-        m[n++] = c;
     }
     if (!n) return VP8HIP_OK;
     // Beside the loop filter, on the batch's second stream: the stage reads the frame's coefficients, modes and vectors (final

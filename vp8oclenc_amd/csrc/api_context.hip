@@ -178,6 +178,11 @@ void next_params(vp8hip_ctx *c) {
     c->d_sd = c->d_sd == c->d_sd2[0] ? c->d_sd2[1] : c->d_sd2[0];
     c->d_stats = c->d_stats == c->d_stats2[0] ? c->d_stats2[1] : c->d_stats2[0];
 }
+// the parameter scan of the current frame into the blocks in force (behind next_params)
+ScanRequest scan_request(const vp8hip_ctx *c, int is_key, const int32_t refqi[4], int qi_min) {
+    return ScanRequest{c->cur.Y[0], c->d_stats + 8, c->d_stats, c->d_sd, reinterpret_cast<int32_t *>(c->d_stats + 4), is_key ? 1 : 0,
+                       {refqi[0], refqi[1], refqi[2], refqi[3]}, qi_min};
+}
 
 // work enqueued on the context's stream from here on sees the filtered reconstruction
 // work enqueued on the context's stream from here on may overwrite what the previous frame's entropy stage (on its own stream) reads
@@ -253,8 +258,7 @@ void side_stream_ordered(vp8hip_ctx *c) {
 void flush_scan(vp8hip_ctx *c) {
     if (!c->scan_deferred) return;
     c->scan_deferred = false;
-    const ScanRequest &q = c->scan_req;
-    launch_auto_segments(c->stream, c->cur, q.partial, q.stats, q.sd, q.strength_out, q.is_key, q.refqi, q.qi_min);
+    launch_auto_segments(c->stream, c->scan_req);
 }
 
 // a new current frame goes into the other of the two surfaces: the previous one stays intact for
@@ -568,8 +572,7 @@ int vp8hip_auto_segments(vp8hip_ctx *c, int is_key_frame, const int32_t refqi[4]
     if (!c || !refqi) return VP8HIP_ERR_ARG;
     if (c->cur_count == 0) return VP8HIP_ERR_STATE;
     next_params(c);
-    launch_auto_segments(c->stream, c->cur, c->d_stats + 8, c->d_stats, c->d_sd, reinterpret_cast<int32_t *>(c->d_stats + 4),
-                         is_key_frame ? 1 : 0, refqi, qi_min);
+    launch_auto_segments(c->stream, scan_request(c, is_key_frame, refqi, qi_min));
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }

@@ -34,7 +34,8 @@ namespace vp8 {
 int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw, int sh) {
     Timed t(c, VP8HIP_K_PACK);
     if (kind == hipMemcpyDeviceToDevice) {
-        launch_pack(c->stream, f, y, u, v, sw, sh);
+        const SourceItem it{&f, y, u, v, nullptr};
+        launch_pack_batch(c->stream, &it, 1, sw, sh);
         return VP8HIP_OK;
     }
     if (sw > 0) {
@@ -43,7 +44,8 @@ int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, cons
         HIPCHK(c, hipMemcpy2DAsync(f.Y[0].p, f.Y[0].stride, y, sw, sw, sh, kind, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(f.U.p, f.U.stride, u, sw / 2, sw / 2, sh / 2, kind, c->stream));
         HIPCHK(c, hipMemcpy2DAsync(f.V.p, f.V.stride, v, sw / 2, sw / 2, sh / 2, kind, c->stream));
-        launch_pack(c->stream, f, f.Y[0].p, f.U.p, f.V.p, sw, sh, f.Y[0].stride, f.U.stride);
+        const SourceItem it{&f, f.Y[0].p, f.U.p, f.V.p, nullptr};
+        launch_pack_batch(c->stream, &it, 1, sw, sh, f.Y[0].stride, f.U.stride);
         return VP8HIP_OK;
     }
     int rc;
@@ -100,18 +102,14 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
                 const hipMemcpyKind *alone, hipEvent_t planes_read) {
     vp8hip_ctx *c0 = m[0];
     { const int rc = intake_ready(m, n); if (rc) return rc; }
-    const Frame *f[MAX_BATCH];
-    const void *py[MAX_BATCH], *pu[MAX_BATCH], *pv[MAX_BATCH];
-    const ScalePlan *plans[MAX_BATCH];
+    SourceItem src[MAX_BATCH];
     ConvertItem cv[MAX_BATCH];
     DeinterlaceItem di[MAX_BATCH];
     for (int i = 0; i < n; ++i) {
         next_current(m[i]);
-        f[i] = &m[i]->cur;
-        plans[i] = &m[i]->scale;
-        py[i] = y[i]; pu[i] = u[i]; pv[i] = v[i];
-        convert_item(m[i], cv[i], py[i], pu[i], pv[i]);      // (a source format: what follows reads the member's converted planes)
-        (void)deinterlace_item(m[i], s, di[i], py[i], pu[i], pv[i]);      // (a deinterlacer: ... the member's deinterlaced planes; same_intake: all or none)
+        src[i] = SourceItem{&m[i]->cur, y[i], u[i], v[i], &m[i]->scale};
+        convert_item(m[i], cv[i], src[i].y, src[i].u, src[i].v);      // (a source format: what follows reads the member's converted planes)
+        (void)deinterlace_item(m[i], s, di[i], src[i].y, src[i].u, src[i].v);      // (a deinterlacer: ... the member's deinterlaced planes; same_intake: all or none)
     }
     int w, h;
     incoming_size(c0, &w, &h);
@@ -125,13 +123,14 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
     }
     if (c0->scale.in_w) {      // a frame that is scaled is not packed as well
         Timed t(c0, VP8HIP_K_PACK);
-        launch_scale_batch(s, f, py, pu, pv, plans, n);
+        launch_scale_batch(s, src, n);
     } else if (alone) {        // (s is the context's stream: the launch of one, or planes from the host straight into the surface)
-        const int rc = set_frame_planes(c0, c0->cur, py[0], pu[0], pv[0], *alone, c0->src_w, c0->src_h);
+        const int rc = set_frame_planes(c0, c0->cur, src[0].y, src[0].u, src[0].v, *alone, c0->src_w, c0->src_h);
         if (rc) return rc;
     } else {
         Timed t(c0, VP8HIP_K_PACK);
-        launch_pack_batch(s, f, py, pu, pv, n, c0->src_w, c0->src_h);
+        static const bool skip = experiment_skip("pack");      // timing experiment only: the batches' pack
+        if (!skip) launch_pack_batch(s, src, n, c0->src_w, c0->src_h);
     }
     if (planes_read) HIPCHK(c0, hipEventRecord(planes_read, s));
     {   // vp8hip_set_denoise: the members that have a history, in one launch behind the pack (the others' frames pass through)

@@ -31,12 +31,7 @@ int inter_begin(vp8hip_ctx *c, int prev_is_golden, int prev_is_altref, int use_g
     if (prev_is_golden) c->slot[1] = c->slot[0];
     if (prev_is_altref) c->slot[2] = c->slot[0];
     if ((use_golden && c->slot[1] < 0) || (use_altref && c->slot[2] < 0)) return VP8HIP_ERR_STATE;
-    if (c->recon < 0 || c->recon == c->slot[0] || c->recon == c->slot[1] || c->recon == c->slot[2]) {
-        c->recon = -1;
-        c->recon = pick_free_frame(c);
-        if (c->recon < 0) return VP8HIP_ERR_STATE;
-    }
-    return VP8HIP_OK;
+    return claim_recon(c);
 }
 
 RefSet ref_set(const vp8hip_ctx *c, int use_last, int use_golden, int use_altref) {
@@ -48,6 +43,13 @@ RefSet ref_set(const vp8hip_ctx *c, int use_last, int use_golden, int use_altref
     return refs;
 }
 
+// a context's frame as the searches and k_mb take it (behind inter_begin: the reconstruction's surface is claimed); the context's
+// parameter scan rides along if it is still waiting -- the caller that launches with it clears scan_deferred
+CodingItem coding_item(const vp8hip_ctx *c, int use_golden, int use_altref) {
+    return CodingItem{&c->cur, ref_set(c, 1, use_golden, use_altref), &c->nets, c->recon >= 0 ? &c->frames[c->recon].f : nullptr,
+                      &c->out, c->d_sd, c->scan_deferred ? &c->scan_req : nullptr};
+}
+
 unsigned long long *s2_clock_words(const vp8hip_ctx *c) { return reinterpret_cast<unsigned long long *>(c->d_progress + S2_CLOCK_WORD); }
 // what the launches get: the stamping costs 1.1 % of the headline (same-box A/B, 57.1 against 57.8 M MB/s), so it is on only
 // while a host asks for it (vp8hip_profile_search2_clock; bench.py: during its warm-up steps)
@@ -57,6 +59,8 @@ unsigned long long *s2_clock(const vp8hip_ctx *c) { return c->s2_clock_on ? s2_c
 // references in `which` (the reference runs the three references on three queues, inter_part.h:122-135)
 void search_refs(vp8hip_ctx *c, const RefSet &which) {
     hipStream_t s = c->stream;
+    CodingItem it = coding_item(c, 0, 0);
+    it.refs = which;
     const int net_width = c->mbw * 2;
     int src = 0;
     // one video coded frame after frame (filter on its own stream): nothing else fills the chip and every launch is a link of the
@@ -65,18 +69,18 @@ void search_refs(vp8hip_ctx *c, const RefSet &which) {
     int first = 4;
     if (c->lf_overlap && fuse) {
         Timed t(c, fuse == 2 ? VP8HIP_K_SEARCH1_L0 : VP8HIP_K_SEARCH1_L1);
-        launch_search1_coarse(s, c->cur, which, c->nets, net_width, fuse == 2);
+        launch_search1_coarse(s, it, net_width, fuse == 2);
         first = fuse == 2 ? -1 : 0;      // (level 0 reads the level-1 net: src index 0)
     }
     for (int l = first; l >= 0; --l) {
         Timed t(c, VP8HIP_K_SEARCH1_L4 + (4 - l));
         // (short waves on the coarse levels of a lone video when the fused launch is switched off: VP8HIP_S1_COARSE=0)
-        launch_search1(s, c->cur, which, c->nets, l, src, net_width, c->lf_overlap && l > 0);
+        launch_search1(s, it, l, src, net_width, c->lf_overlap && l > 0);
         src ^= 1;
     }
     Timed t(c, VP8HIP_K_SEARCH2);
     // (the launch clock only where launches of this context cannot overlap: the one that searches LAST)
-    launch_search2(s, c->cur, which, c->nets, which.use[0] ? s2_clock(c) : nullptr);
+    launch_search2(s, it, which.use[0] ? s2_clock(c) : nullptr);
 }
 
 // prepare_GPU_buffers, inter_part.h:1-33 (reset_vectors is folded into k_search1's parent read)
@@ -104,6 +108,24 @@ int claim_recon(vp8hip_ctx *c) {
     return VP8HIP_OK;
 }
 
+// The two transitions of the reconstruction's surface.  An unfiltered reconstruction now exists (k_mb's: key false; the intra path's:
+// key true); a check of the previous attempt does not count for it (an_checked is read for inter reconstructions only).
+void recon_made(vp8hip_ctx *c, bool key) {
+    c->recon_ready = true;
+    c->recon_key = key;
+    c->an_checked = false;
+}
+// ... and its filter has been launched: it is the LAST reference of the next frame (vp8enc.cpp:395-401); its replicated edges are made
+// with its pyramid, in one launch, when that frame begins (pyramids())
+void recon_filtered(vp8hip_ctx *c) {
+    c->frames[c->recon].pyramid_valid = false;
+    c->frames[c->recon].border_valid = false;
+    c->slot[0] = c->recon;
+    c->lf_key = c->recon_key;
+    c->recon = -1;
+    c->recon_ready = false;
+}
+
 // ---- check_SSIM without the host round trip ---------------------------------------------------------------------------------
 void check_item(vp8hip_ctx *c, CheckItem &it, const int32_t refqi[4], int qi_min) {
     it.cur = &c->cur;
@@ -122,7 +144,7 @@ void check_item(vp8hip_ctx *c, CheckItem &it, const int32_t refqi[4], int qi_min
     c->chk_qi_min = qi_min;
 }
 // what the loop filter launch needs to carry an armed check's verdict (on = 0 otherwise)
-void lf_check(vp8hip_ctx *c, LfCheck &k) {
+static void lf_check(vp8hip_ctx *c, LfCheck &k) {
     k.on = c->chk_armed ? 1 : 0;
     if (!k.on) return;
     c->chk_armed = false;
@@ -134,6 +156,13 @@ void lf_check(vp8hip_ctx *c, LfCheck &k) {
     k.verdict = c->h_verdict;
     k.seq = ++c->verdict_seq;
     c->verdict_pending = true;
+}
+// a context's reconstruction as the loop filter of its type takes it: the next launch number of that filter, and the armed check
+FilterItem filter_item(vp8hip_ctx *c) {
+    FilterItem it{&c->frames[c->recon].f, &c->out, c->d_sd, c->d_progress, c->d_lf_handoff,
+                  c->lf_type == 1 ? c->lf_simple_launches++ : c->lf_launches++, LfCheck{}};
+    lf_check(c, it.chk);
+    return it;
 }
 
 // With the reference's default target of -1 no macroblock can lie below it -- a macroblock's SSIM is a product of a factor in (0, 1]
@@ -202,11 +231,10 @@ int vp8hip_inter_transform(vp8hip_ctx *c, int prev_is_golden, int prev_is_altref
     }
     {
         Timed t(c, VP8HIP_K_MB);   // select_reference + pack_8x8_into_16x16 run inside
-        launch_mb(c->stream, c->cur, refs, c->nets, c->frames[c->recon].f, c->out, c->d_sd, c->ssim_target, c->mbw, c->mbh, c->conformant != 0);
+        const CodingItem it = coding_item(c, use_golden, use_altref);
+        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0);
     }
-    c->recon_ready = true;
-    c->recon_key = false;
-    c->an_checked = false;
+    recon_made(c, false);
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -235,12 +263,10 @@ int vp8hip_inter_finish(vp8hip_ctx *c, int use_golden, int use_altref) {
     JOIN_LF(c);
     {
         Timed t(c, VP8HIP_K_MB);
-        launch_mb(c->stream, c->cur, ref_set(c, 1, use_golden, use_altref), c->nets, c->frames[c->recon].f, c->out, c->d_sd, c->ssim_target,
-                  c->mbw, c->mbh, c->conformant != 0);
+        const CodingItem it = coding_item(c, use_golden, use_altref);
+        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0);
     }
-    c->recon_ready = true;
-    c->recon_key = false;
-    c->an_checked = false;
+    recon_made(c, false);
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -260,8 +286,7 @@ int vp8hip_intra_transform(vp8hip_ctx *c) {
         launch_intra(c->stream, c->cur, c->frames[c->recon].f, c->out, c->d_sd, c->intra_modes, c->intra_is_inter, c->intra_prog,
                      ++c->intra_gen, c->d_progress + LF_ERR_WORD, 0.0f, 1, c->mbw, c->mbh, c->lf_stall_test);
     }
-    c->recon_ready = true;
-    c->recon_key = true;
+    recon_made(c, true);
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }
@@ -373,9 +398,9 @@ int vp8hip_set_loop_filter_type(vp8hip_ctx *c, int type) {
 }
 
 // the filter of the context's type on `s` (form 4 for the normal filter: the short chain of one video)
-static void launch_loop_filter_of_type(vp8hip_ctx *c, hipStream_t s, Frame &f, const LfCheck *chk) {
-    if (c->lf_type == 1) launch_loop_filter_simple(s, f, c->out, c->d_sd, c->d_progress, c->mbw, c->mbh, c->lf_simple_launches++, chk);
-    else launch_loop_filter4(s, f, c->out, c->d_sd, c->d_progress, c->d_lf_handoff, c->mbw, c->mbh, c->lf_launches++, c->lf_stall_test, chk);
+static void launch_loop_filter_of_type(vp8hip_ctx *c, hipStream_t s, const FilterItem &it) {
+    if (c->lf_type == 1) launch_loop_filter_simple(s, it, c->mbw, c->mbh);
+    else launch_loop_filter4(s, it, c->mbw, c->mbh, c->lf_stall_test);
 }
 
 int vp8hip_loop_filter(vp8hip_ctx *c) {
@@ -384,14 +409,13 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
     if (!c) return VP8HIP_ERR_ARG;
     if (!c->recon_ready || c->recon < 0) return VP8HIP_ERR_STATE;
     Frame &f = c->frames[c->recon].f;
-    LfCheck chk;
-    lf_check(c, chk);
+    const FilterItem it = filter_item(c);
     if (c->lf_overlap && !c->prof_mask) {   // (the per-kernel timers bracket launches on the context's stream only)
         hipStream_t chain = c->stream;
-        const bool by_verdict = chk.on != 0;      // (see side_stream_ordered)
+        const bool by_verdict = it.chk.on != 0;      // (see side_stream_ordered)
         if (!by_verdict) HIPCHK(c, hipEventRecord(c->ev_fork, chain));
-        launch_loop_filter_of_type(c, chain, f, &chk);
-        c->lf_key = c->recon_key;
+        launch_loop_filter_of_type(c, chain, it);
+        recon_filtered(c);
         analysis_after_filter(c, chain);
         quality_after_filter(c, f, chain);   // (behind the filter on its stream: whatever overwrites this source is ordered behind it)
         c->verdict_stream = chain;
@@ -404,20 +428,13 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
     } else {
         {
             Timed t(c, VP8HIP_K_LOOP_FILTER);
-            launch_loop_filter_of_type(c, c->stream, f, &chk);
+            launch_loop_filter_of_type(c, c->stream, it);
         }
-        c->lf_key = c->recon_key;
+        recon_filtered(c);
         analysis_after_filter(c, c->stream);
         quality_after_filter(c, f, c->stream);
         c->verdict_stream = c->stream;
     }
-    // the filtered reconstruction is the LAST reference of the next frame (vp8enc.cpp:395-401); its replicated edges are made
-    // with its pyramid, in one launch, when that frame begins (pyramids())
-    c->frames[c->recon].pyramid_valid = false;
-    c->frames[c->recon].border_valid = false;
-    c->slot[0] = c->recon;
-    c->recon = -1;
-    c->recon_ready = false;
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }

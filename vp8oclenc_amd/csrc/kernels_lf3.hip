@@ -47,9 +47,8 @@ static bool lf_skip() {
     return skip;   // timing experiment only
 }
 
-void launch_loop_filter3_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
-                               int32_t *const *progress, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk) {
-    lfb::launch_batch(lf3::k_loop_filter3_b, s, recon, o, d_sd, progress, 0, mbw, mbh, launch_no, n, chk, lf_skip());
+void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh) {
+    lfb::launch_batch(lf3::k_loop_filter3_b, s, items, n, 0, mbw, mbh, lf_skip());
 }
 
 }  // namespace vp8

@@ -700,24 +700,22 @@ __global__ __launch_bounds__(NWAVES * 64) void k_loop_filter4_b(BatchOf<Args> b)
 
 size_t loop_filter4_handoff_bytes(int mbw, int mbh) { return (size_t)((mbh + lf4::ROWS - 1) / lf4::ROWS) * mbw * 32 * sizeof(uint2); }
 
-static lf4::Args loop_filter4_args(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, void *handoff, int mbw, int mbh,
-                                   unsigned launch_no, int stall_test, const LfCheck *chk) {
+static lf4::Args loop_filter4_args(hipStream_t s, const FilterItem &it, int mbw, int mbh, int stall_test) {
     lf4::Args a;
-    if (chk) a.chk = *chk;
-    else a.chk.on = 0;
-    a.Y = recon.Y[0];
-    a.U = recon.U;
-    a.V = recon.V;
-    a.o = o;
-    a.sd = d_sd;
-    a.gprog = progress;
-    a.handoff = static_cast<uint2 *>(handoff);
+    a.chk = it.chk;      // (only `on` is read when it is 0)
+    a.Y = it.recon->Y[0];
+    a.U = it.recon->U;
+    a.V = it.recon->V;
+    a.o = *it.out;
+    a.sd = it.sd;
+    a.gprog = it.progress;
+    a.handoff = static_cast<uint2 *>(it.handoff);
     a.mbw = mbw;
     a.mbh = mbh;
     a.nbands = (mbh + lf4::ROWS - 1) / lf4::ROWS;
-    a.gbase = lf_window_base(launch_no, mbw);   // (the tags of the hand-off buffer count in the launch's window)
-    if (a.gbase == 0) (void)hipMemsetAsync(handoff, 0, loop_filter4_handoff_bytes(mbw, mbh), s);
-    a.err = progress + LF_ERR_WORD;
+    a.gbase = lf_window_base(it.launch_no, mbw);   // (the tags of the hand-off buffer count in the launch's window)
+    if (a.gbase == 0) (void)hipMemsetAsync(it.handoff, 0, loop_filter4_handoff_bytes(mbw, mbh), s);
+    a.err = it.progress + LF_ERR_WORD;
     a.stall_test = stall_test;
     return a;
 }
@@ -726,20 +724,18 @@ static bool lf_skip() {
     return skip;   // timing experiment only
 }
 
-void launch_loop_filter4(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, void *handoff,
-                         int mbw, int mbh, unsigned launch_no, int stall_test, const LfCheck *chk) {
-    const lf4::Args a = loop_filter4_args(s, recon, o, d_sd, progress, handoff, mbw, mbh, launch_no, stall_test, chk);
+void launch_loop_filter4(hipStream_t s, const FilterItem &it, int mbw, int mbh, int stall_test) {
+    const lf4::Args a = loop_filter4_args(s, it, mbw, mbh, stall_test);
     if (lf_skip()) return;
     VP8_LAUNCH(lf4::k_loop_filter4, dim3(a.nbands + (a.chk.on ? 1 : 0)), dim3(lf4::NWAVES * 64), 0, s, a);   // + the verdict workgroup
 }
 
-void launch_loop_filter4_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
-                               int32_t *const *progress, void *const *handoff, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk) {
+void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh) {
     BatchOf<lf4::Args> b;
     b.n = n;
     bool any = false;
     for (int i = 0; i < n; ++i) {
-        b.item[i] = loop_filter4_args(s, *recon[i], *o[i], d_sd[i], progress[i], handoff[i], mbw, mbh, launch_no[i], 0, chk ? &chk[i] : nullptr);
+        b.item[i] = loop_filter4_args(s, items[i], mbw, mbh, 0);
         any = any || b.item[i].chk.on;
     }
     if (lf_skip()) return;

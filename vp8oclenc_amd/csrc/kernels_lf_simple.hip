@@ -62,15 +62,13 @@ __global__ __launch_bounds__(NWAVES * 64) void k_loop_filter_simple_b(BatchOf<Ar
 
 bool loop_filter_simple_fits(int mbh) { return (mbh + 1 + lfb::ROWS - 1) / lfb::ROWS + 1 <= LF_SIMPLE_WORDS; }
 
-void launch_loop_filter_simple(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, int mbw, int mbh,
-                               unsigned launch_no, const LfCheck *chk) {
-    const lfb::Args a = lfb::make_args(s, recon, o, d_sd, progress, LF_SIMPLE_WORD, mbw, mbh, launch_no, chk);
+void launch_loop_filter_simple(hipStream_t s, const FilterItem &it, int mbw, int mbh) {
+    const lfb::Args a = lfb::make_args(s, it, LF_SIMPLE_WORD, mbw, mbh);
     VP8_LAUNCH(lfs::k_loop_filter_simple, dim3(a.nbands + (a.chk.on ? 1 : 0)), dim3(lfb::NWAVES * 64), 0, s, a);   // + the verdict workgroup
 }
 
-void launch_loop_filter_simple_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
-                                     int32_t *const *progress, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk) {
-    lfb::launch_batch(lfs::k_loop_filter_simple_b, s, recon, o, d_sd, progress, LF_SIMPLE_WORD, mbw, mbh, launch_no, n, chk);
+void launch_loop_filter_simple_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh) {
+    lfb::launch_batch(lfs::k_loop_filter_simple_b, s, items, n, LF_SIMPLE_WORD, mbw, mbh);
 }
 
 }  // namespace vp8

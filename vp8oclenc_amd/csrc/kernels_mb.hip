@@ -841,8 +841,11 @@ static bool mb_packed() {
     return on;
 }
 
-static MBArgs mb_args(const Frame &cur, const RefSet &refs, const NetSet &nets, const Frame &recon, const MBOut &o, const SegData *d_sd,
-                      float ssim_target, int mbw, int mbh) {
+static MBArgs mb_args(const CodingItem &it, float ssim_target, int mbw, int mbh) {
+    const Frame &cur = *it.cur, &recon = *it.recon;
+    const RefSet &refs = it.refs;
+    const NetSet &nets = *it.nets;
+    const MBOut &o = *it.out;
     MBArgs a;
     auto planes = [](const Frame &f) { return MBPlanes{f.Y[0].p, f.U.p, f.V.p}; };
     a.cur = planes(cur);
@@ -852,7 +855,7 @@ static MBArgs mb_args(const Frame &cur, const RefSet &refs, const NetSet &nets, 
     a.cstride = cur.U.stride; a.cw = cur.U.w; a.ch = cur.U.h;
     a.o_parts = o.parts; a.o_ref = o.ref; a.o_seg = o.seg; a.o_nz = o.nz; a.o_mask = o.mask;
     a.o_vec = o.vec; a.o_coeffs = o.coeffs; a.o_ssim = o.ssim; a.o_flag = o.flags;
-    a.sd = d_sd;
+    a.sd = it.sd;
     a.bdiff0 = nets.bdiff[0]; a.bdiff1 = nets.bdiff[1]; a.bdiff2 = nets.bdiff[2];
     a.vnet0 = nets.net[0][0]; a.vnet1 = nets.net[1][0]; a.vnet2 = nets.net[2][0];
     a.ssim_target = ssim_target;
@@ -867,36 +870,20 @@ static bool mb_skip() {
     return skip;   // timing experiment only (what the frame costs without this kernel); never set in production
 }
 
-void launch_mb(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, const Frame &recon,
-               const MBOut &o, const SegData *d_sd, float ssim_target, int mbw, int mbh, bool conformant) {
-    const MBArgs a = mb_args(cur, refs, nets, recon, o, d_sd, ssim_target, mbw, mbh);
-    if (mb_skip()) return;
-    BatchOf<MBArgs> b;
-    b.n = 1;
-    b.item[0] = a;
-    if (mb_packed()) {
-        if (conformant) VP8_LAUNCH(k_mb_p_conformant, dim3((a.mbs + 7) / 8, 1, 1), dim3(192), 0, s, b);
-        else VP8_LAUNCH(k_mb_p, dim3((a.mbs + 7) / 8, 1, 1), dim3(192), 0, s, b);
-        return;
-    }
-    if (conformant) VP8_LAUNCH(k_mb_b_conformant, dim3((a.mbs + 7) / 8, 1, 1), dim3(256), 0, s, b);
-    else VP8_LAUNCH(k_mb_b, dim3((a.mbs + 7) / 8, 1, 1), dim3(256), 0, s, b);
-}
-
-void launch_mb_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, const Frame *const *recon,
-                     const MBOut *const *o, const SegData *const *d_sd, float ssim_target, int mbw, int mbh, int n, bool conformant) {
+void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant) {
     static_assert(sizeof(BatchOf<MBArgs>) <= 4096, "the batch travels in the kernel arguments");
     BatchOf<MBArgs> b;
     b.n = n;
-    for (int i = 0; i < n; ++i) b.item[i] = mb_args(*cur[i], refs[i], *nets[i], *recon[i], *o[i], d_sd[i], ssim_target, mbw, mbh);
+    for (int i = 0; i < n; ++i) b.item[i] = mb_args(items[i], ssim_target, mbw, mbh);
     if (mb_skip()) return;
+    const dim3 grid((b.item[0].mbs + 7) / 8, 1, n);
     if (mb_packed()) {
-        if (conformant) VP8_LAUNCH(k_mb_p_conformant, dim3((b.item[0].mbs + 7) / 8, 1, n), dim3(192), 0, s, b);
-        else VP8_LAUNCH(k_mb_p, dim3((b.item[0].mbs + 7) / 8, 1, n), dim3(192), 0, s, b);
+        if (conformant) VP8_LAUNCH(k_mb_p_conformant, grid, dim3(192), 0, s, b);
+        else VP8_LAUNCH(k_mb_p, grid, dim3(192), 0, s, b);
         return;
     }
-    if (conformant) VP8_LAUNCH(k_mb_b_conformant, dim3((b.item[0].mbs + 7) / 8, 1, n), dim3(256), 0, s, b);
-    else VP8_LAUNCH(k_mb_b, dim3((b.item[0].mbs + 7) / 8, 1, n), dim3(256), 0, s, b);
+    if (conformant) VP8_LAUNCH(k_mb_b_conformant, grid, dim3(256), 0, s, b);
+    else VP8_LAUNCH(k_mb_b, grid, dim3(256), 0, s, b);
 }
 
 // ------------------------------------------------------------------------------------------------

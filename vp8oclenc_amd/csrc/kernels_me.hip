@@ -200,24 +200,14 @@ static PackItem pack_item(const Frame &f, const void *y, const void *u, const vo
     if (ssy <= 0) { ssy = sw; ssc = sw >> 1; }
     return PackItem{f.Y[0], f.U, f.V, (const uint8_t *)y, (const uint8_t *)u, (const uint8_t *)v, sw, sh, ssy, ssc};
 }
-void launch_pack(hipStream_t s, const Frame &f, const void *y, const void *u, const void *v, int sw, int sh, int ssy, int ssc) {
-    const int n = (f.Y[0].w >> 3) * f.Y[0].h + 2 * ((f.U.w >> 3) * f.U.h);
-    // (a batch of one: the by-value form of the kernel picks the plane through a pointer into its argument block, which hipcc
-    // answers by copying the block to scratch memory)
-    BatchOf<PackItem> b;
-    b.n = 1;
-    b.item[0] = pack_item(f, y, u, v, sw, sh, ssy, ssc);
-    const int per = pack_units_per_thread();
-    VP8_LAUNCH(k_pack_b, dim3((n + 256 * per - 1) / (256 * per), 1, 1), dim3(256), 0, s, b, per);
-}
-void launch_pack_batch(hipStream_t s, const Frame *const *f, const void *const *y, const void *const *u, const void *const *v, int n,
-                       int sw, int sh) {
+// (one context launches a batch of one: the by-value form of the kernel picks the plane through a pointer into its argument block,
+// which hipcc answers by copying the block to scratch memory)
+void launch_pack_batch(hipStream_t s, const SourceItem *items, int n, int sw, int sh, int ssy, int ssc) {
     BatchOf<PackItem> b;
     b.n = n;
-    for (int i = 0; i < n; ++i) b.item[i] = pack_item(*f[i], y[i], u[i], v[i], sw, sh, 0, 0);
-    const int units = (f[0]->Y[0].w >> 3) * f[0]->Y[0].h + 2 * ((f[0]->U.w >> 3) * f[0]->U.h);
-    static const bool skip = experiment_skip("pack");
-    if (skip) return;   // timing experiment only
+    for (int i = 0; i < n; ++i) b.item[i] = pack_item(*items[i].f, items[i].y, items[i].u, items[i].v, sw, sh, ssy, ssc);
+    const Frame &f = *items[0].f;
+    const int units = (f.Y[0].w >> 3) * f.Y[0].h + 2 * ((f.U.w >> 3) * f.U.h);
     const int per = pack_units_per_thread();
     VP8_LAUNCH(k_pack_b, dim3((units + 256 * per - 1) / (256 * per), 1, n), dim3(256), 0, s, b, per);
 }
@@ -623,7 +613,10 @@ static bool search1_pre_lds() {
     return on;
 }
 
-static Search1Args search1_args(const Frame &cur, const RefSet &refs, const NetSet &nets, int level, int src_idx, int net_width) {
+static Search1Args search1_args(const CodingItem &it, int level, int src_idx, int net_width) {
+    const Frame &cur = *it.cur;
+    const RefSet &refs = it.refs;
+    const NetSet &nets = *it.nets;
     Search1Args a;
     a.cur = cur.Y[level];
     int n = 0;
@@ -664,9 +657,8 @@ static bool search1_split(size_t blocks_times_refs, bool latency) {
     return forced >= 0 ? forced == 1 : (latency || blocks_times_refs < (size_t)12 * 1024);
 }
 
-void launch_search1(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, int level, int src_idx,
-                    int net_width, bool latency) {
-    const Search1Args a = search1_args(cur, refs, nets, level, src_idx, net_width);
+void launch_search1(hipStream_t s, const CodingItem &it, int level, int src_idx, int net_width, bool latency) {
+    const Search1Args a = search1_args(it, level, src_idx, net_width);
     const int n = a.nrefs;
     if (a.nblk <= 0 || n == 0 || search1_skip()) return;
     if (search1_split((size_t)a.nblk * n, latency))
@@ -678,9 +670,9 @@ void launch_search1(hipStream_t s, const Frame &cur, const RefSet &refs, const N
 }
 
 // levels 4..1 (finest = false) or 4..0 in one launch (k_search1_coarse); the level-1 and level-0 nets land where launch_search1 leaves them
-void launch_search1_coarse(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, int net_width, bool finest) {
+void launch_search1_coarse(hipStream_t s, const CodingItem &it, int net_width, bool finest) {
     CoarseArgs a;
-    for (int l = 0; l <= 4; ++l) a.lv[l] = search1_args(cur, refs, nets, l, l & 1, net_width);   // src of level l: 0 for 4, 2 and 0; 1 for 3 and 1
+    for (int l = 0; l <= 4; ++l) a.lv[l] = search1_args(it, l, l & 1, net_width);   // src of level l: 0 for 4, 2 and 0; 1 for 3 and 1
     const Search1Args &L0 = a.lv[0], &L1 = a.lv[1];
     if (L0.nblk <= 0 || L0.nrefs == 0 || search1_skip()) return;
     // tiles of 4 x 4 level-1 blocks = 8 x 8 level-0 blocks; a frame of one macroblock row or column has level-0 blocks without a level-1 block above them
@@ -692,28 +684,30 @@ void launch_search1_coarse(hipStream_t s, const Frame &cur, const RefSet &refs, 
 
 // levels 4..1 (finest = false) or 4..0 of every member of a batch in ONE launch; false = the members' surfaces are not laid out alike
 // (never so for contexts of one size: the caller then launches level by level)
-bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int net_width, int n, bool finest, bool top_only) {
+bool launch_search1_coarse_batch(hipStream_t s, const CodingItem *items, int n, int net_width, bool finest, bool top_only) {
     CoarseBatchArgs a;
     a.net_width = net_width;
     a.n = n;
     int maxrefs = 0;
     for (int l = 0; l <= 4; ++l) {
-        const Plane &c = cur[0]->Y[l];
-        a.g[l] = CoarseGeom{c.w, c.h, c.stride, refs[0].ref[0].Y[l].stride};
+        const Plane &c = items[0].cur->Y[l];
+        a.g[l] = CoarseGeom{c.w, c.h, c.stride, items[0].refs.ref[0].Y[l].stride};
     }
     for (int i = 0; i < n; ++i) {
         CoarseMember &m = a.m[i];
+        const RefSet &refs = items[i].refs;
+        const NetSet &nets = *items[i].nets;
         int k = 0;
         for (int r = 0; r < 3; ++r) {
             for (int l = 0; l <= 4; ++l) {
-                const Plane &rp = refs[i].ref[r].Y[l], &cp = cur[i]->Y[l];
+                const Plane &rp = refs.ref[r].Y[l], &cp = items[i].cur->Y[l];
                 if (rp.stride != a.g[l].ref_stride || cp.stride != a.g[l].cur_stride || cp.w != a.g[l].w || cp.h != a.g[l].h || rp.w != cp.w || rp.h != cp.h) return false;
                 m.ref[r][l] = rp.p;
                 if (r == 0) m.cur[l] = cp.p;
             }
-            m.dst1[r] = nets[i]->net[r][0];       // launch_search1_batch's ping-pong: level 4 reads net 0 ... level 1 writes net 0, level 0 writes net 1
-            m.dst0[r] = nets[i]->net[r][1];
-            if (refs[i].use[r]) m.refmap[k++] = r;
+            m.dst1[r] = nets.net[r][0];       // launch_search1_batch's ping-pong: level 4 reads net 0 ... level 1 writes net 0, level 0 writes net 1
+            m.dst0[r] = nets.net[r][1];
+            if (refs.use[r]) m.refmap[k++] = r;
         }
         m.nrefs = k;
         for (int j = k; j < 3; ++j) m.refmap[j] = 0;
@@ -732,13 +726,12 @@ bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const R
     return true;
 }
 
-void launch_search1_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int level, int src_idx,
-                          int net_width, int n) {
+void launch_search1_batch(hipStream_t s, const CodingItem *items, int n, int level, int src_idx, int net_width) {
     BatchOf<Search1Args> b;
     b.n = n;
     int maxrefs = 0, totrefs = 0;
     for (int i = 0; i < n; ++i) {
-        b.item[i] = search1_args(*cur[i], refs[i], *nets[i], level, src_idx, net_width);
+        b.item[i] = search1_args(items[i], level, src_idx, net_width);
         maxrefs = b.item[i].nrefs > maxrefs ? b.item[i].nrefs : maxrefs;
         totrefs += b.item[i].nrefs;
     }

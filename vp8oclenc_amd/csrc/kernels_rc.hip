@@ -53,31 +53,23 @@ __global__ __launch_bounds__(256) void k_strength_segments_b(BatchOf<StrengthIte
 
 size_t rc_partial_words() { return 2 * MAX_PARTIALS + 4; }   // + the completion counter of k_strength_segments (zero at rest)
 
-void launch_auto_segments(hipStream_t s, const Frame &cur, uint32_t *partial, uint32_t *stats, SegData *sd, int32_t *strength_out,
-                          int is_key, const int32_t refqi[4], int qi_min) {
+void launch_auto_segments(hipStream_t s, const ScanRequest &q) {
     static const bool split = [] { const char *v = getenv("VP8HIP_SPLIT_SEGMENTS"); return v && v[0] && v[0] != '0'; }();   // A/B
-    const Plane &y = cur.Y[0];
-    const int nb = (y.h + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    const SegArgs g{y.w * y.h, (y.h - 1) * (y.w - 1), is_key, refqi[0], refqi[1], refqi[2], refqi[3], qi_min};
+    const int nb = (q.y.h + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+    const ScanCore c = scan_core(q);
     if (!split) {
-        hipLaunchKernelGGL(k_strength_segments, dim3(nb), dim3(256), 0, s, StrengthItem{y, ScanCore{partial, partial + 2 * MAX_PARTIALS, stats, sd, strength_out, g}});
+        hipLaunchKernelGGL(k_strength_segments, dim3(nb), dim3(256), 0, s, StrengthItem{q.y, c});
     } else {
-        hipLaunchKernelGGL(k_lf_strength, dim3(nb), dim3(256), 0, s, y, partial);
-        hipLaunchKernelGGL(k_auto_segments, dim3(1), dim3(256), 0, s, partial, nb, stats, sd, strength_out, g);
+        hipLaunchKernelGGL(k_lf_strength, dim3(nb), dim3(256), 0, s, q.y, c.partial);
+        hipLaunchKernelGGL(k_auto_segments, dim3(1), dim3(256), 0, s, c.partial, nb, c.stats, c.sd, c.strength_out, c.g);
     }
 }
 
-void launch_auto_segments_batch(hipStream_t s, const Frame *const *cur, uint32_t *const *partial, uint32_t *const *stats, SegData *const *sd,
-                                int32_t *const *strength_out, const int *is_key, const int32_t (*refqi)[4], int qi_min, int n) {
+void launch_auto_segments_batch(hipStream_t s, const ScanRequest *q, int n) {
     BatchOf<StrengthItem> b;
     b.n = n;
-    const Plane &y0 = cur[0]->Y[0];
-    const int nb = (y0.h + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    for (int i = 0; i < n; ++i) {
-        const Plane &y = cur[i]->Y[0];
-        const SegArgs g{y.w * y.h, (y.h - 1) * (y.w - 1), is_key[i], refqi[i][0], refqi[i][1], refqi[i][2], refqi[i][3], qi_min};
-        b.item[i] = StrengthItem{y, ScanCore{partial[i], partial[i] + 2 * MAX_PARTIALS, stats[i], sd[i], strength_out[i], g}};
-    }
+    const int nb = (q[0].y.h + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+    for (int i = 0; i < n; ++i) b.item[i] = StrengthItem{q[i].y, scan_core(q[i])};
     static const bool skip = experiment_skip("scan");
     if (skip) return;   // timing experiment only
     hipLaunchKernelGGL(k_strength_segments_b, dim3(nb, 1, n), dim3(256), 0, s, b);

@@ -96,6 +96,12 @@ __device__ __forceinline__ void auto_segments_body(const uint32_t *partial, int 
 // the partial sums of all of them
 struct ScanCore { uint32_t *partial, *done, *stats; SegData *sd; int32_t *strength_out; SegArgs g; };
 struct StrengthItem { Plane y; ScanCore c; };
+// a request as the kernels take it (host side; the plane travels beside it: StrengthItem, or the search's own copy of it)
+inline ScanCore scan_core(const ScanRequest &q) {
+    const Plane &y = q.y;
+    return ScanCore{q.partial, q.partial + 2 * MAX_PARTIALS, q.stats, q.sd, q.strength_out,
+                    SegArgs{y.w * y.h, (y.h - 1) * (y.w - 1), q.is_key, q.refqi[0], q.refqi[1], q.refqi[2], q.refqi[3], q.qi_min}};
+}
 // wg of nwg workgroups of 256 threads, whatever launch they are part of
 __device__ __forceinline__ void strength_segments_body(const Plane &y, const ScanCore &a, int wg, int nwg) {
     uint32_t *partial = a.partial, *done = a.done, *stats = a.stats;

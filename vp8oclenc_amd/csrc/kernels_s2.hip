@@ -433,7 +433,10 @@ __global__ __launch_bounds__(256, 4) void k_search2_p(BatchOf<S2Args> b, int nbx
 
 }  // namespace
 
-static S2Args search2_args(const Frame &cur, const RefSet &refs, const NetSet &nets, unsigned long long *clk) {
+static S2Args search2_args(const CodingItem &it, unsigned long long *clk) {
+    const Frame &cur = *it.cur;
+    const RefSet &refs = it.refs;
+    const NetSet &nets = *it.nets;
     S2Args a;
     a.clk = clk;
     a.cur = cur.Y[0];
@@ -472,8 +475,8 @@ static bool search2_skip() {
     return skip;   // timing experiment only
 }
 
-void launch_search2(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, unsigned long long *clk) {
-    const S2Args a = search2_args(cur, refs, nets, clk);
+void launch_search2(hipStream_t s, const CodingItem &it, unsigned long long *clk) {
+    const S2Args a = search2_args(it, clk);
     if (a.nrefs == 0 || search2_skip()) return;
     const int nbx = (a.nblk + 7) / 8;
     if (!search2_spread()) VP8_LAUNCH((k_search2<false, 1>), dim3(nbx, a.nrefs), dim3(256), 0, s, a);
@@ -481,13 +484,12 @@ void launch_search2(hipStream_t s, const Frame &cur, const RefSet &refs, const N
     else VP8_LAUNCH((k_search2<true, 1>), dim3(nbx, a.nrefs), dim3(256), 0, s, a);
 }
 
-bool launch_search2_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int n, unsigned long long *clk,
-                          const ScanRequest *const *scan) {
+bool launch_search2_batch(hipStream_t s, const CodingItem *items, int n, unsigned long long *clk) {
     BatchOf<S2Args> b;
     b.n = n;
     int maxrefs = 0;
     for (int i = 0; i < n; ++i) {
-        b.item[i] = search2_args(*cur[i], refs[i], *nets[i], clk);
+        b.item[i] = search2_args(items[i], clk);
         maxrefs = b.item[i].nrefs > maxrefs ? b.item[i].nrefs : maxrefs;
     }
     if (maxrefs == 0 || search2_skip()) return false;
@@ -499,13 +501,10 @@ bool launch_search2_batch(hipStream_t s, const Frame *const *cur, const RefSet *
     }
     S2Scans sc;
     sc.mask = 0;
-    for (int i = 0; scan && i < n; ++i) {
-        if (!scan[i]) continue;
-        const ScanRequest &q = *scan[i];
-        const Plane &y = b.item[i].cur;
+    for (int i = 0; i < n; ++i) {      // (a request's plane is the member's current luma: what the kernel reads as b.item[i].cur)
+        if (!items[i].scan) continue;
         sc.mask |= 1u << i;
-        sc.item[i] = rc::ScanCore{q.partial, q.partial + 2 * rc::MAX_PARTIALS, q.stats, q.sd, q.strength_out,
-                                  rc::SegArgs{y.w * y.h, (y.h - 1) * (y.w - 1), q.is_key, q.refqi[0], q.refqi[1], q.refqi[2], q.refqi[3], q.qi_min}};
+        sc.item[i] = rc::scan_core(*items[i].scan);
     }
     const int iter = search2_spread() ? search2_iter(true) : 1, ngrp = (nbx + iter - 1) / iter;     // workgroups that search: each takes `iter` groups of eight blocks
     if (!sc.mask) {

@@ -183,17 +183,17 @@ static scale::Geo scale_geo(const ScalePlan &p) {
     }
 }
 
-void launch_scale_batch(hipStream_t s, const Frame *const *f, const void *const *y, const void *const *u, const void *const *v,
-                        const ScalePlan *const *plan, int n) {
+void launch_scale_batch(hipStream_t s, const SourceItem *items, int n) {
     if (n <= 0) return;
-    const scale::Geo g = scale_geo(*plan[0]);
+    const scale::Geo g = scale_geo(*items[0].plan);
     BatchOf<scale::Item> b;
     b.n = n;
     int tiles = 0;
     for (int i = 0; i < n; ++i) {
-        const ScalePlan &p = *plan[i];
-        const Plane *out[3] = {&f[i]->Y[0], &f[i]->U, &f[i]->V};
-        const void *src[3] = {y[i], u[i], v[i]};
+        const ScalePlan &p = *items[i].plan;
+        const Frame &f = *items[i].f;
+        const Plane *out[3] = {&f.Y[0], &f.U, &f.V};
+        const void *src[3] = {items[i].y, items[i].u, items[i].v};
         tiles = 0;
         for (int k = 0; k < 3; ++k) {
             scale::PlaneJob &j = b.item[i].p[k];

@@ -390,36 +390,33 @@ template <typename Filter> __device__ __forceinline__ void loop_filter_body(cons
 
 // The argument block of one launch.  counter_word: where in the progress buffer this filter's band counters sit; they and
 // launch_no are a filter's own, so launches of the other forms in between leave its windows valid.
-inline Args make_args(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, int counter_word, int mbw, int mbh,
-                      unsigned launch_no, const LfCheck *chk) {
+inline Args make_args(hipStream_t s, const FilterItem &it, int counter_word, int mbw, int mbh) {
     Args a;
-    if (chk) a.chk = *chk;
-    else a.chk.on = 0;
-    a.Y = recon.Y[0];
-    a.U = recon.U;
-    a.V = recon.V;
-    a.o = o;
-    a.sd = d_sd;
-    a.gprog = progress + counter_word;
+    a.chk = it.chk;      // (only `on` is read when it is 0)
+    a.Y = it.recon->Y[0];
+    a.U = it.recon->U;
+    a.V = it.recon->V;
+    a.o = *it.out;
+    a.sd = it.sd;
+    a.gprog = it.progress + counter_word;
     a.mbw = mbw;
     a.mbh = mbh;
     a.nbands = (mbh + 1 + ROWS - 1) / ROWS;   // + the virtual flush row
-    a.gbase = lf_window_base(launch_no, mbw);
+    a.gbase = lf_window_base(it.launch_no, mbw);
     if (a.gbase == 0) (void)hipMemsetAsync(a.gprog, 0, sizeof(int32_t) * (a.nbands + 1), s);
-    a.err = progress + LF_ERR_WORD;
+    a.err = it.progress + LF_ERR_WORD;
     return a;
 }
 
 // One launch for a batch: blockIdx.z = the batch's item; + the verdict workgroup if check_SSIM rides with any of them.
 // skip: everything but the launch itself (a timing experiment).
 template <typename Kernel>
-inline void launch_batch(Kernel kernel, hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd, int32_t *const *progress,
-                         int counter_word, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk, bool skip = false) {
+inline void launch_batch(Kernel kernel, hipStream_t s, const FilterItem *items, int n, int counter_word, int mbw, int mbh, bool skip = false) {
     BatchOf<Args> b;
     b.n = n;
     bool any = false;
     for (int i = 0; i < n; ++i) {
-        b.item[i] = make_args(s, *recon[i], *o[i], d_sd[i], progress[i], counter_word, mbw, mbh, launch_no[i], chk ? &chk[i] : nullptr);
+        b.item[i] = make_args(s, items[i], counter_word, mbw, mbh);
         any = any || b.item[i].chk.on;
     }
     if (skip) return;

@@ -393,6 +393,7 @@ void build_pyramid(vp8hip_ctx *c, Frame *a, Frame *b, uint32_t border_mask = 0);
 int make_last(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind);
 SegData *sd_for_writing(vp8hip_ctx *c);
 void next_params(vp8hip_ctx *c);
+ScanRequest scan_request(const vp8hip_ctx *c, int is_key, const int32_t refqi[4], int qi_min);
 void next_current(vp8hip_ctx *c);
 int join_ent(vp8hip_ctx *c);
 hipStream_t join_lf_swap(vp8hip_ctx *c);
@@ -444,9 +445,12 @@ int inter_begin(vp8hip_ctx *c, int prev_is_golden, int prev_is_altref, int use_g
 RefSet ref_set(const vp8hip_ctx *c, int use_last, int use_golden, int use_altref);
 unsigned long long *s2_clock_words(const vp8hip_ctx *c);
 unsigned long long *s2_clock(const vp8hip_ctx *c);
+CodingItem coding_item(const vp8hip_ctx *c, int use_golden, int use_altref);
 int claim_recon(vp8hip_ctx *c);
+void recon_made(vp8hip_ctx *c, bool key);
+void recon_filtered(vp8hip_ctx *c);
 void check_item(vp8hip_ctx *c, CheckItem &it, const int32_t refqi[4], int qi_min);
-void lf_check(vp8hip_ctx *c, LfCheck &k);
+FilterItem filter_item(vp8hip_ctx *c);
 bool fallback_possible(float ssim_target);
 // ---- api_entropy.hip ----
 constexpr size_t FRAME_FIRST_COPY = 192 * 1024;

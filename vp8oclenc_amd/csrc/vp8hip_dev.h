@@ -84,6 +84,14 @@ struct SegData { int32_t v[4 * SD_INTS]; };
 // the argument blocks of the single form travel as an array in the kernel arguments, and a few streams carry what sixteen did.
 constexpr int MAX_BATCH = 8;
 template <typename A> struct BatchOf { int n; A item[MAX_BATCH]; };
+// What a batched launcher takes is ONE array of member records and what all members share: (stream, const Item *, n, ...).  A context
+// on its own is a batch of one.  The intake stages have a record each (ConvertItem, DeinterlaceItem, DenoiseItem, AnalysisSrcItem);
+// the coding chain has three, each filled by one function of the API layer from a context (the pointers are the context's own and
+// outlive the launch call), and the launchers make the kernels' argument blocks of them:
+//   SourceItem  -- pack / scale: where a member's new frame comes from and the surface it goes into (take_frames);
+//   CodingItem  -- searches and k_mb: the frame, its references, the nets and where the results go (coding_item);
+//   FilterItem  -- the three loop filters: the reconstruction, its results and the filter's own counters (filter_item);
+// and ScanRequest, the parameter scan of one frame (scan_request).
 
 // A launch's duration by the kernel's own clock (s_memrealtime, 100 MHz), for kernels of many workgroups: every CLOCK_SAMPLE-th
 // workgroup (in dispatch order, the first one included) stamps w = {earliest start, latest end, sampled workgroups done,
@@ -135,22 +143,25 @@ int persistent_workgroups();
 void launch_border(hipStream_t s, const Frame &f);
 // all four levels of one or two frames; bit z of border_mask: also the replicated edges of surface z (launch_border's work, same launch)
 void launch_pyramid(hipStream_t s, const Frame *a, const Frame *b, uint32_t border_mask = 0);
-// sw, sh: luma size of the source planes (0 = the coded size); ssy, ssc: their row strides (0 = tight)
-void launch_pack(hipStream_t s, const Frame &f, const void *y, const void *u, const void *v, int sw = 0, int sh = 0, int ssy = 0, int ssc = 0);
-// batched forms: n <= MAX_BATCH contexts (pyramid: nframes <= 2 * MAX_BATCH surfaces)
+// batched form: nframes <= 2 * MAX_BATCH surfaces
 void launch_pyramid_batch(hipStream_t s, const Frame *const *f, int nframes, uint32_t border_mask = 0);
-// launch_auto_segments' work (same arguments) for a launch that lets it ride along (launch_search2_batch)
-struct ScanRequest { uint32_t *partial, *stats; SegData *sd; int32_t *strength_out; int is_key; int32_t refqi[4]; int qi_min; };
-void launch_pack_batch(hipStream_t s, const Frame *const *f, const void *const *y, const void *const *u, const void *const *v, int n,
-                       int sw = 0, int sh = 0);
+// The parameter scan of one frame: loop-filter strength of the luma plane y + prepare_segments_data, all on the device.  What
+// launch_auto_segments launches on its own and what launch_search2_batch lets ride along.
+struct ScanRequest { Plane y; uint32_t *partial, *stats; SegData *sd; int32_t *strength_out; int is_key; int32_t refqi[4]; int qi_min; };
 // kernels_scale.hip: a frame that comes in LARGER than the coded picture is scaled down into the surfaces instead of packed
 // (vp8hip_set_source_scaling).  A plan = the four tables (luma x, luma y, chroma x, chroma y) of include/vp8hip_host.h's
 // vp8host_scale_taps, stretched over the padded surface, in one device block.
 struct ScaleDim { int n, n_in, n_surf; size_t off_start, off_coef; int max_span[4]; };
 struct ScalePlan { int in_w = 0, in_h = 0, kind = 0; ScaleDim d[4] = {}; uint8_t *d_blob = nullptr; };
 bool scale_plan_make(ScalePlan *p, int in_w, int in_h, int dst_w, int dst_h, int W, int H, int kind, std::vector<uint8_t> &blob);   // false: refused
-void launch_scale_batch(hipStream_t s, const Frame *const *f, const void *const *y, const void *const *u, const void *const *v,
-                        const ScalePlan *const *plan, int n);
+// A member's new frame: planes y, u, v (tight I420 in device memory by now) on their way into the surface f, packed or, through the
+// member's plan, scaled down.
+struct SourceItem { const Frame *f; const void *y, *u, *v; const ScalePlan *plan; };
+// sw, sh: luma size of the source planes (0 = the coded size); ssy, ssc: their row strides (0 = tight).  NOTE: the timing-experiment
+// switch that leaves the BATCHES' pack out (VP8HIP_EXPERIMENT_SKIP=pack) is take_frames' (api_intake.hip), not this launcher's, where
+// the other skip switches sit: the launch of one context, which comes through here too, has never been skipped by it.
+void launch_pack_batch(hipStream_t s, const SourceItem *items, int n, int sw = 0, int sh = 0, int ssy = 0, int ssc = 0);
+void launch_scale_batch(hipStream_t s, const SourceItem *items, int n);
 // kernels_denoise.hip: temporal noise reduction of the frame just packed or scaled (vp8hip_set_denoise), in place on `cur` against
 // `hist`, the previous current frame as it left this launch; the rule is include/vp8hip_host.h's.  `word` (zero at rest) takes the
 // count of filtered macroblocks and the waves' tickets; the wave with the last ticket writes the record into `host`, seq last.
@@ -202,47 +213,66 @@ struct DeinterlaceItem {
     int32_t frame_number;
 };
 void launch_deinterlace_batch(hipStream_t s, int w, int h, int keep, const DeinterlaceItem *items, int n);
-bool launch_search1_coarse_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int net_width, int n, bool finest, bool top_only = false);
-void launch_search1_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int level, int src_idx,
-                          int net_width, int n);
-// scan[i] (may be nullptr, as may scan): member i's new frame gets its loop-filter strength scan + segment data in this launch.
-// Returns false if the scans were NOT carried (nothing to search, or the persistent form): the caller launches them on their own.
-bool launch_search2_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, int n,
-                          unsigned long long *clk = nullptr, const ScanRequest *const *scan = nullptr);   // clk: launch clock words (launch_clock_end) or nullptr
-void launch_mb_batch(hipStream_t s, const Frame *const *cur, const RefSet *refs, const NetSet *const *nets, const Frame *const *recon,
-                     const MBOut *const *o, const SegData *const *d_sd, float ssim_target, int mbw, int mbh, int n,
-                     bool conformant = false);
-struct LfCheck;
-void launch_loop_filter3_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
-                               int32_t *const *progress, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk = nullptr);
-void launch_loop_filter4_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
-                               int32_t *const *progress, void *const *handoff, int mbw, int mbh, const unsigned *launch_no, int n,
-                               const LfCheck *chk = nullptr);
-void launch_auto_segments_batch(hipStream_t s, const Frame *const *cur, uint32_t *const *partial, uint32_t *const *stats, SegData *const *sd,
-                                int32_t *const *strength_out, const int *is_key, const int32_t (*refqi)[4], int qi_min, int n);
-// levels 4, 3, 2, 1 (and, finest, 0) in ONE launch (a single video: kernels_me.hip, k_search1_coarse); leaves the level-1 / level-0 nets where the per-level launches leave them
-void launch_search1_coarse(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, int net_width, bool finest);
-void launch_search1(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, int level,
-                    int src_idx, int net_width, bool latency = false);   // latency: the short-wave mapping whatever the size
-void launch_search2(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, unsigned long long *clk = nullptr);
+// check_SSIM's verdict riding in a loop filter launch (see CheckItem below)
+struct LfCheck {
+    int on, qi_min;
+    int32_t refqi[4];
+    const int32_t *is_inter;
+    int32_t *strength;       // {reductor, sharpness, sharpness in force}
+    int32_t *stats;          // device copy of the verdict (vp8hip_check_ssim's read-back buffer)
+    int32_t *verdict;        // host memory the device writes: the five words, then seq
+    uint32_t seq;
+};
+// One member's frame in the searches and k_mb.  recon, out, sd: k_mb's (a launch of the searches alone does not read them).
+// scan (or nullptr): the member's parameter scan still waiting for a launch to ride in (launch_search2_batch).
+struct CodingItem {
+    const Frame *cur;
+    RefSet refs;
+    const NetSet *nets;
+    const Frame *recon;
+    const MBOut *out;
+    const SegData *sd;
+    const ScanRequest *scan;
+};
+// One member's reconstruction in a loop filter launch.  launch_no counts the member's launches of THAT filter (the normal forms share
+// one count, the simple filter has its own); handoff: form 4's buffer; chk.on = 0: no check rides along.
+struct FilterItem {
+    const Frame *recon;
+    const MBOut *out;
+    SegData *sd;
+    int32_t *progress;
+    void *handoff;
+    unsigned launch_no;
+    LfCheck chk;
+};
+bool launch_search1_coarse_batch(hipStream_t s, const CodingItem *items, int n, int net_width, bool finest, bool top_only = false);
+void launch_search1_batch(hipStream_t s, const CodingItem *items, int n, int level, int src_idx, int net_width);
+// Members with a scan get their loop-filter strength scan + segment data in this launch.  Returns false if the scans were NOT
+// carried (nothing to search, or the persistent form): the caller launches them on their own.
+bool launch_search2_batch(hipStream_t s, const CodingItem *items, int n, unsigned long long *clk = nullptr);   // clk: launch clock words (launch_clock_end) or nullptr
+// (one context: a batch of one -- the kernel is the same)
+void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant = false);
+void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh);
+void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh);
+void launch_auto_segments_batch(hipStream_t s, const ScanRequest *q, int n);
+// The forms of ONE video (kernels of their own; the argument blocks are made as the batched forms make them).
+// levels 4, 3, 2, 1 (and, finest, 0) in ONE launch (kernels_me.hip, k_search1_coarse); leaves the level-1 / level-0 nets where the per-level launches leave them
+void launch_search1_coarse(hipStream_t s, const CodingItem &it, int net_width, bool finest);
+void launch_search1(hipStream_t s, const CodingItem &it, int level, int src_idx, int net_width, bool latency = false);   // latency: the short-wave mapping whatever the size
+void launch_search2(hipStream_t s, const CodingItem &it, unsigned long long *clk = nullptr);
 void launch_weight_tap(hipStream_t s, const int32_t *d, int n, int32_t *out);
 void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out);
-void launch_mb(hipStream_t s, const Frame &cur, const RefSet &refs, const NetSet &nets, const Frame &recon,
-               const MBOut &o, const SegData *d_sd, float ssim_target, int mbw, int mbh, bool conformant = false);
 void launch_filter_mask(hipStream_t s, const MBOut &o, const SegData *d_sd, int mbs);
 // The loop filter exists in two forms with the same results.  Form 3 (lf_banded.h): byte tiles and strips in 46 KB
 // of LDS, the worker wave does everything itself -- what batches of GOP chunks launch, and only they (with the part full what counts is the
 // instructions and the LDS a launch takes from the other kernels, not its latency).  Form 4: a band-tall plane of dwords in
 // 112 KB of LDS, the workers only filter, porter waves feed and drain -- the short dependency chain of ONE video.
-void launch_loop_filter4(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, void *handoff,
-                         int mbw, int mbh, unsigned launch_no, int stall_test = 0, const LfCheck *chk = nullptr);
+void launch_loop_filter4(hipStream_t s, const FilterItem &it, int mbw, int mbh, int stall_test = 0);
 size_t loop_filter4_handoff_bytes(int mbw, int mbh);   // the HBM buffer form 4 hands a band's bottom rows to the next band through
 // The simple loop filter (frame header filter_type 1, kernels_lf_simple.hip): luma only, form 3's data movement (lf_banded.h).  launch_no counts
 // the context's simple-filter launches only (its band counters are its own, at LF_SIMPLE_WORD of the progress buffer).
-void launch_loop_filter_simple(hipStream_t s, const Frame &recon, const MBOut &o, SegData *d_sd, int32_t *progress, int mbw, int mbh,
-                               unsigned launch_no, const LfCheck *chk = nullptr);
-void launch_loop_filter_simple_batch(hipStream_t s, const Frame *const *recon, const MBOut *const *o, SegData *const *d_sd,
-                                     int32_t *const *progress, int mbw, int mbh, const unsigned *launch_no, int n, const LfCheck *chk = nullptr);
+void launch_loop_filter_simple(hipStream_t s, const FilterItem &it, int mbw, int mbh);
+void launch_loop_filter_simple_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh);
 bool loop_filter_simple_fits(int mbh);   // its band counters fit their window of the progress buffer
 
 // ---- quality of the coded frames (kernels_quality.hip; vp8hip_set_quality_stats) --------------------------------------------
@@ -286,8 +316,7 @@ void quality_totals(const QualityState &st, vp8hip_quality_totals *t);
 size_t rc_partial_words();   // uint32 words of per-workgroup partial sums the three launchers below need
 void launch_lf_strength(hipStream_t s, const Frame &cur, uint32_t *partial, uint32_t *stats);    // [0] sum Y, [1] sum of squared deviations
 void launch_chroma_sad(hipStream_t s, const Frame &cur, const Frame &prev, uint32_t *partial, uint32_t *stats);   // [2] sum |dU|, [3] sum |dV|
-void launch_auto_segments(hipStream_t s, const Frame &cur, uint32_t *partial, uint32_t *stats, SegData *sd, int32_t *strength_out,
-                          int is_key, const int32_t refqi[4], int qi_min);   // strength + prepare_segments_data, all on the device
+void launch_auto_segments(hipStream_t s, const ScanRequest &q);   // strength + prepare_segments_data, all on the device
 
 // coefficient entropy stage (kernels_ent.hip): flags + third context + token histogram + probabilities
 constexpr int ENT_NCTX = 4 * 8 * 3 * 11;
@@ -380,15 +409,6 @@ struct CheckItem {
     const SegData *sd;
     int32_t *modes, *is_inter, *prog, *err;
     unsigned gen;
-};
-struct LfCheck {
-    int on, qi_min;
-    int32_t refqi[4];
-    const int32_t *is_inter;
-    int32_t *strength;       // {reductor, sharpness, sharpness in force}
-    int32_t *stats;          // device copy of the verdict (vp8hip_check_ssim's read-back buffer)
-    int32_t *verdict;        // host memory the device writes: the five words, then seq
-    uint32_t seq;
 };
 void launch_check_fallback(hipStream_t s, const CheckItem *items, int n, float target, int mbw, int mbh, int modes_of_kept);
 void launch_intra_key_batch(hipStream_t s, const CheckItem *items, int n, int mbw, int mbh);   // the key frames of n members of a batch, one launch
