@@ -294,6 +294,40 @@ typedef struct {
  * VP8HIP_ERR_STATE: deinterlacing off, or no frame taken in since it was turned on. */
 int vp8hip_deinterlace_result(vp8hip_ctx *ctx, vp8hip_deinterlace_stats *s);
 
+/* The two geometric stages of the input side, each opt-in, each ONE more launch; pure data movement whose rule is stated bit for bit
+ * in include/vp8hip_host.h.  After them the order of the input side is
+ *     window -> convert -> deinterlace -> orient -> scale or pack -> denoise -> analysis.
+ * THE WINDOW.  A hardware decoder, a capture API or a renderer hands out SURFACES: rows a pitch apart (2048 bytes for a 1920-wide NV12
+ * frame) and the picture a window inside (1920x1080 in 1920x1088, a letterboxed 1920x800 in 1920x1080).  pitch = the bytes between the
+ * rows of each of the three planes (entries of planes the source format lacks are ignored), (x, y) = the window's top-left luma
+ * sample: from now on the three pointers of every call that makes a frame current -- vp8hip_set_current_device,
+ * vp8hip_upload_current, vp8hip_prefetch_current, the three batched forms -- are the plane bases of a surface in the context's source
+ * format, and the frame is the window of the INCOMING SIZE (below) at (x, y): vp8host_source_window has the table and
+ * vp8host_window_frame is the rule in plain C++.  No byte outside the window is ever read; the surface's own size is no parameter;
+ * neither pitch nor base needs any alignment.  Planes in DEVICE memory: one launch (k_window_b) for all members of a batch, in front of
+ * everything else, writes the window's tight planes into a staging buffer of the context, and the next stage reads that as if the
+ * caller had handed it in.  Planes in HOST memory: only the window's bytes travel, as 2-D copies into the staging buffers the uploads
+ * already use; no launch.
+ * pitch NULL (default): off.  VP8HIP_ERR_ARG and nothing has changed: x or y negative or odd, or for a plane the format has
+ * pitch[p] < ((x + width) >> hs) * bpe.  Checked against the format and incoming size in force at the call; the format, size, scaling
+ * and orientation setters refuse a change that would make the window in force invalid.
+ * THE ORIENTATION.  Phone and action-camera video is stored sideways or upside down; VP8 in IVF or WebM carries no rotation tag, so a
+ * transcoder bakes the rotation in.  turns = 0..3 clockwise quarter turns, mirror = 0 or 1: a left-right flip of the incoming frame
+ * FIRST, then the rotation (vp8host_orient_frame).  Every size the library knows describes the UPRIGHT frame: the coded size,
+ * vp8hip_set_source_size, the scaler's in_width x in_height, the quality statistics' region.  With an odd `turns` the planes handed
+ * in -- the INCOMING SIZE, which is also the window's -- are in_height wide and in_width high; the window, the converter and the
+ * deinterlacer (fields are rows of the source) work at that raw size, the scaler or the pack sees the upright one.  One launch
+ * (k_orient_b) behind the deinterlacer and in front of the pack or scale launch reads tight I420 and writes tight I420 into a staging
+ * buffer of its own.  (0, 0), the default: off.  Anything else out of range, a raw height below 4 while a deinterlacer mode is set, or
+ * a window in force that the raw size would make invalid: VP8HIP_ERR_ARG and nothing has changed.
+ * BOTH: once per frame TAKEN IN, never per coding attempt.  Off is off: no launch, no allocation, no byte and no number changes.
+ * They compose with the size, scaling, format, colour, deinterlace, denoise and analysis setters in any order of calls.  A setter
+ * waits for the context's streams (not a per-frame call) and drops a pending prefetch of the context and of its batch.  All members of
+ * a batch must agree on pitches, origin, turns and mirror (vp8hip_batch_create and the batched launch check it).  Reconstructions
+ * (vp8hip_upload_last, vp8hip_set_last_device, vp8hip_upload_recon) stay tight, upright and of the coded size. */
+int vp8hip_set_source_window(vp8hip_ctx *ctx, const int32_t *pitch /* [3], NULL = off */, int x, int y);
+int vp8hip_set_source_orientation(vp8hip_ctx *ctx, int turns, int mirror);
+
 /* prepare_filter_mask_and_non_zero_coeffs(), loop_filter.h:25-55.  nz_out: [MBs] or NULL.
  * (vp8hip_inter_transform already produced mask and counts for its own coefficients; this call
  * recomputes them from the device copy, e.g. after vp8hip_upload_mb_data.) */
@@ -519,7 +553,10 @@ const char *vp8hip_status_string(int status);
  * also under 4010: the packed source formats YUY2, UYVY, BGRA, RGBA and their colour matrix (vp8hip_set_source_colour,
  * vp8drv_set_source_colour, vp8host_convert_frame_colour, vp8host_colour_coefficients; entry points only);
  * also under 4010: frame analysis (vp8hip_set_analysis, vp8hip_analysis_restart, vp8hip_analysis_result, vp8host_analyse_luma,
- * vp8drv_set_analysis, vp8drv_get_frame_analysis) and vp8drv_set_quantizer / vp8drv_get_quantizer (entry points only). */
+ * vp8drv_set_analysis, vp8drv_get_frame_analysis) and vp8drv_set_quantizer / vp8drv_get_quantizer (entry points only);
+ * also under 4010: source windows and orientation (vp8hip_set_source_window, vp8hip_set_source_orientation, vp8host_source_window,
+ * vp8host_window_frame, vp8host_orient_frame, vp8drv_set_source_window, vp8drv_set_source_orientation; entry points only:
+ * vp8drv_config is unchanged). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

@@ -258,6 +258,18 @@ int vp8drv_set_source_format(vp8drv *d, int format);
  * relative to the format; VP8HIP_ERR_ARG: not one of the four matrices, or cfg.device_params = 0; VP8HIP_ERR_STATE: the driver is a
  * member of a live batch (vp8drv_batch_create refuses members that differ). */
 int vp8drv_set_source_colour(vp8drv *d, int matrix);
+/* Source frames that are the window of a pitched surface, and source frames stored sideways or upside down
+ * (vp8hip_set_source_window, vp8hip_set_source_orientation; the rules: include/vp8hip_host.h).  Entry points, not fields of
+ * vp8drv_config, for the reason vp8drv_set_denoise is one; call them after vp8drv_create and before the first frame, or between
+ * frames, in any order relative to each other and to the other setters.  With a window the three pointers of
+ * vp8drv_encode_frame_device / _host, vp8drv_prefetch_frame_host, vp8drv_stage_frame_host and the batched calls are the plane bases
+ * of a surface (pitch = bytes between the rows of each plane, NULL = off; (x, y) = the window's top-left luma sample, both even); with
+ * an odd number of turns the planes handed in are cfg's incoming height wide and its incoming width high, and every size of
+ * vp8drv_config keeps describing the upright frame.  VP8HIP_ERR_ARG: what the library refuses, or cfg.device_params = 0 (the host
+ * parameter mirror reads the caller's luma plane as the tight upright frame).  VP8HIP_ERR_STATE: the driver is a member of a live
+ * batch (the members must agree: set them before vp8drv_batch_create, which refuses members that differ). */
+int vp8drv_set_source_window(vp8drv *d, const int32_t *pitch /* [3], NULL = off */, int x, int y);
+int vp8drv_set_source_orientation(vp8drv *d, int turns, int mirror);
 /* ---- what a rate controller needs: a record to measure with and a quantizer to set -------------------------------------------
  * Frame analysis statistics (vp8hip_set_analysis; the rules: include/vp8hip_host.h), entry points and not a field for the reason
  * vp8drv_set_denoise is one.  on = 0 (default) or 1; it takes the open check_SSIM verdict first.  VP8HIP_ERR_ARG: another value, or

@@ -194,6 +194,41 @@ int vp8host_deinterlace_frame(const uint8_t *src_y, const uint8_t *src_u, const 
                               uint8_t *hist_v, uint8_t *out_y, uint8_t *out_u, uint8_t *out_v, int width, int height, int mode, int keep,
                               int have_history, int32_t *woven);
 
+/* The geometry of the input side (vp8hip_set_source_window, vp8hip_set_source_orientation, include/vp8hip.h; k_window_b, k_orient_b),
+ * bit for bit: pure data movement.  The project's own: the reference reads tight upright I420.
+ * THE WINDOW.  The three pointers of a frame are the plane bases of a SURFACE in the source format whose rows are pitch[p] bytes
+ * apart; the frame is the window of width x height luma samples whose top-left luma sample is (x, y).  Plane p of a format has a
+ * horizontal shift hs, a vertical shift vs and bytes per element bpe:
+ *     I420  0,0,1  1,1,1  1,1,1        P010  0,0,2  1,1,4  -            YUY2, UYVY  1,0,4  -  -
+ *     NV12  0,0,1  1,1,2  -            I010  0,0,2  1,1,2  1,1,2        BGRA, RGBA  0,0,4  -  -
+ *     I422  0,0,1  1,0,1  1,0,1        I210  0,0,2  1,0,2  1,0,2
+ *     I444  0,0,1  0,0,1  0,0,1        I410  0,0,2  0,0,2  0,0,2
+ * and of the window it holds rows[p] = height >> vs rows of row_bytes[p] = (width >> hs) * bpe bytes; row r starts at byte
+ *     offset[p] + r * pitch[p],   offset[p] = (y >> vs) * pitch[p] + (x >> hs) * bpe
+ * of the plane.  The rows end to end are the tight planes vp8host_source_plane_bytes describes (rows * row_bytes is its entry).  No
+ * byte outside the window is read; the surface's own size is no parameter; pitch and base need no alignment.
+ * vp8host_source_window: the table and the validation.  -1: an unknown format, width or height odd or not positive, x or y negative
+ * or odd (even values keep 4:2:0 chroma, YUY2 pairs and field parity whole), a null pointer, or for a plane the format has
+ * pitch[p] < ((x + width) >> hs) * bpe.  pitch entries of planes the format lacks are ignored; their offset, row_bytes and rows are 0.
+ * vp8host_window_frame: the rule on planes in host memory; out0..out2 = the tight planes (pointers of planes the format lacks are
+ * not looked at). */
+int vp8host_source_window(int format, int width, int height, int x, int y, const int32_t pitch[3], size_t offset[3],
+                          int32_t row_bytes[3], int32_t rows[3]);
+int vp8host_window_frame(int format, int width, int height, int x, int y, const int32_t pitch[3], const uint8_t *p0, const uint8_t *p1,
+                         const uint8_t *p2, uint8_t *out0, uint8_t *out1, uint8_t *out2);
+/* THE ORIENTATION.  turns = 0..3 clockwise quarter turns, mirror = 0 or 1: a left-right flip of the incoming frame FIRST, then the
+ * rotation.  For each of the three tight 8-bit I420 planes, `in` the plane as it comes in, rw samples wide and rh high, and
+ * s(x, y) = in(mirror ? rw - 1 - x : x, y):
+ *     turns 0:  out(x, y) = s(x, y)                      out is rw x rh
+ *     turns 1:  out(x, y) = s(y, rh - 1 - x)             out is rh x rw
+ *     turns 2:  out(x, y) = s(rw - 1 - x, rh - 1 - y)    out is rw x rh
+ *     turns 3:  out(x, y) = s(rw - 1 - y, x)             out is rh x rw
+ * The chroma planes take the same rule at their own size (raw_width / 2 x raw_height / 2); both dimensions are even, so 4:2:0 stays
+ * exact.  Siting is not modelled.  raw_width x raw_height: the luma size of the planes that come in.  out must not overlap in.
+ * Returns 0, or -1: turns or mirror out of range, a size odd or below 2, a null pointer. */
+int vp8host_orient_frame(int turns, int mirror, int raw_width, int raw_height, const uint8_t *in_y, const uint8_t *in_u,
+                         const uint8_t *in_v, uint8_t *out_y, uint8_t *out_u, uint8_t *out_v);
+
 /* The rules of the frame analysis record (vp8hip_set_analysis, include/vp8hip.h; k_analyse_src_b, k_analyse_mb_b), bit for bit.  The
  * project's own: libvpx's first-pass statistics cut to what this encoder knows.  Every field is an exact integer; no floats anywhere.
  *

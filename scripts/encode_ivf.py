@@ -10,7 +10,11 @@ colourspaces are refused); --yuv: raw frames of the given size, I420 or --source
 i410, or the packed yuy2, uyvy, bgra, rgba; the RGB ones are read with --source-matrix bt601|bt709 and --source-range limited|full,
 vp8drv_set_source_colour); without either the synthetic sequence of the tests is used.  A raw I420 file has the given width/height (even numbers); when
 they are not multiples of 16 the frames are padded on the device (vp8hip_set_source_size = copy_with_padding, encIO.h:141-196)
-and the key frames carry the source size as display size."""
+and the key frames carry the source size as display size.
+--surface WxH --crop X:Y (with --yuv): the file's frames are surfaces of WxH and the frame is the window of --width x --height whose
+top-left luma sample is (X, Y) (vp8drv_set_source_window with the surface's tight pitch; everything even); --rotate 90|180|270 and
+--mirror: the frames are stored sideways, upside down or flipped and are turned clockwise (behind the flip) on the device
+(vp8drv_set_source_orientation); behind 90 or 270 degrees the picture that is coded is as wide as the frames that come in are high."""
 import argparse, os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,6 +74,10 @@ def main():
     ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
     ap.add_argument("--deinterlace", choices=("off", "field", "adaptive"), default="off", metavar="MODE", help="interlaced source frames made progressive on the device (vp8drv_set_deinterlace): field = every missing row interpolated, adaptive = what stands still is woven; the history restarts with every GOP")
     ap.add_argument("--field", choices=("top", "bottom"), default="top", help="... the field that is kept")
+    ap.add_argument("--surface", default="", metavar="WxH", help="with --yuv: the file's frames are surfaces of this size and the frame is the window of --width x --height at --crop (vp8drv_set_source_window)")
+    ap.add_argument("--crop", default="0:0", metavar="X:Y", help="... the window's top-left luma sample (even numbers)")
+    ap.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=0, help="turn the frames clockwise by this many degrees on the device (vp8drv_set_source_orientation)")
+    ap.add_argument("--mirror", action="store_true", help="... behind a left-right flip")
     ap.add_argument("--analysis", default="", metavar="FILE", help="the frame analysis record of every frame as one text line per frame (vp8drv_set_analysis; the line: scripts/native/y4m_to_ivf.cpp): a first-pass file")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -78,6 +86,9 @@ def main():
         from vp8oclenc_amd import api
         dist = api.Group.from_env(local, f"encode_ivf-{os.getppid()}-{os.environ.get('MASTER_PORT', '0')}")
     from vp8oclenc_amd import api
+    if a.surface and not a.yuv:
+        sys.exit("--surface goes with --yuv")
+    surface = tuple(int(x) for x in a.surface.lower().split("x")) if a.surface else None
     try:
         fmt = api.source_format(a.source_format) if a.source_format else None
         if a.y4m and fmt is not None and fmt >= api.FORMAT_YUY2:
@@ -87,18 +98,31 @@ def main():
             seq = Y4mFile(a.y4m, fmt)      # (without --source-format: the file's C tag, and ValueError for one the encoder cannot take)
             a.framerate = seq.framerate or a.framerate
         else:
-            seq = YuvFile(a.yuv, a.width, a.height, fmt or 0) if a.yuv else SynthSequence(a.width, a.height, seed=1)
+            seq = YuvFile(a.yuv, *(surface or (a.width, a.height)), fmt or 0) if a.yuv else SynthSequence(a.width, a.height, seed=1)
     except ValueError as e:
         sys.exit(f"{a.y4m or a.yuv or '--source-format'}: {e}")
     fmt = getattr(seq, "format", 0)
     if fmt:
         seq = FormatPlanes(seq)
     frames = min(a.frames, seq.n) if (a.yuv or a.y4m) else a.frames
-    Wd, Hd = (int(x) for x in a.resize.lower().split("x")) if a.resize else (seq.W, seq.H)      # the picture that is coded and displayed ("dst")
+    turns = a.rotate // 90
+    raw = (a.width, a.height) if surface else (seq.W, seq.H)      # the frames as they come in: the window of a surface, or the file's
+    Win, Hin = raw[::-1] if turns & 1 else raw                    # ... and upright
+    window = None
+    if surface:
+        try:
+            x, y = (int(v) for v in a.crop.split(":"))
+            window = (api.source_window(fmt, *surface, 0, 0, [2 ** 31 - 1] * 3)[1], x, y)      # (the surface's tight pitch)
+            api.source_window(fmt, *raw, x, y, window[0])
+            if y + raw[1] > surface[1]:
+                raise ValueError("the window ends below the surface")
+        except ValueError as e:
+            sys.exit(f"--surface {a.surface} --crop {a.crop}: {e}")
+    Wd, Hd = (int(x) for x in a.resize.lower().split("x")) if a.resize else (Win, Hin)      # the picture that is coded and displayed ("dst")
     Wc, Hc = (Wd + 15) // 16 * 16, (Hd + 15) // 16 * 16            # the coded ("wrk") size, init.h:375-392
     src = dict(src_width=Wd, src_height=Hd) if (Wc, Hc) != (Wd, Hd) else {}
-    if (Wd, Hd) != (seq.W, seq.H):
-        src.update(in_width=seq.W, in_height=seq.H, scale_filter=int(a.resize_filter == "lanczos"))
+    if (Wd, Hd) != (Win, Hin):
+        src.update(in_width=Win, in_height=Hin, scale_filter=int(a.resize_filter == "lanczos"))
     t0 = time.perf_counter()
     def make_encoder():
         enc = gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
@@ -111,6 +135,10 @@ def main():
         if fmt:
             enc.drv.set_source_format(fmt)
             enc.drv.set_source_colour(a.source_matrix, a.source_range)
+        if turns or a.mirror:
+            enc.drv.set_source_orientation(turns, int(a.mirror))
+        if window:
+            enc.drv.set_source_window(*window)
         if a.analysis:      # every frame's record next to its bytes (the line needs both)
             enc.drv.set_analysis(True)
             plain = enc.encode
@@ -132,7 +160,7 @@ def main():
     if rank == 0:
         n = gop_shard.write_ivf(a.out, allf, Wd, Hd, a.framerate)
         el = time.perf_counter() - t0
-        print(f"{a.out}: {frames} frames {seq.W}x{seq.H}{f' scaled to {Wd}x{Hd}' if a.resize else ''}, {n} bytes, {world} GPU(s), {frames / el:.1f} frames/s including the host-side frame source")
+        print(f"{a.out}: {frames} frames {Win}x{Hin}{f' scaled to {Wd}x{Hd}' if a.resize else ''}, {n} bytes, {world} GPU(s), {frames / el:.1f} frames/s including the host-side frame source")
     if dist is not None:
         dist.close()
 

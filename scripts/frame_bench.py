@@ -26,6 +26,9 @@ ap.add_argument("--field", choices=("top", "bottom"), default="top", help="... t
 ap.add_argument("--source-format", default="", metavar="NAME", help="the device-resident frames are this format's planes (nv12, p010, i444, ..., or the packed yuy2, uyvy, bgra, rgba: vp8drv_set_source_format): what k_convert_b / k_convert_packed_b costs")
 ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", help="the colour matrix bgra / rgba frames are read with (vp8drv_set_source_colour)")
 ap.add_argument("--source-range", choices=("limited", "full"), default="limited")
+ap.add_argument("--window-pitch", type=int, default=0, metavar="P", help="the device-resident frames are surfaces whose luma rows are P bytes apart (the other planes' in proportion) and the frame is the window at (0, 0) (vp8drv_set_source_window): what k_window_b costs")
+ap.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=0, help="the device-resident frames are stored turned back by this many degrees and are turned clockwise on the device (vp8drv_set_source_orientation): what k_orient_b costs; the coded bytes do not change")
+ap.add_argument("--mirror", action="store_true", help="... behind a left-right flip")
 ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the frame analysis record of every frame (vp8drv_set_analysis): what k_analyse_src_b and k_analyse_mb_b cost")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
@@ -58,11 +61,32 @@ def rgb_near_i420(fmt, y, u, v):
     return [np.ascontiguousarray(px).ravel()]
 
 
+turns = a.rotate // 90
+if turns or a.mirror:      # the frames as a sideways camera stored them: the orientation undone (a mirrored turn undoes itself)
+    host = [api.orient_frame(turns if a.mirror else (4 - turns) & 3, int(a.mirror), f) for f in host]
 fmt = api.source_format(a.source_format) if a.source_format else 0
 if fmt:      # the same frames carried by the format's planes (chroma replicated, samples shifted up): the coded bytes do not change
     rgb = fmt in (api.FORMAT_BGRA, api.FORMAT_RGBA)      # (RGB: a picture close to the frame, not the frame: the coded bytes do change)
     host = [rgb_near_i420(fmt, *f) if rgb else api.planes_from_i420(fmt, *f) for f in host]
     host = [f + [f[-1]] * (3 - len(f)) for f in host]      # (the two-plane formats: the second pointer again; the packed ones: the first)
+pitch = None
+if a.window_pitch:      # every plane's rows a pitch apart: the tight rows at the front of rows of `pitch` bytes
+    rh, rw = np.asarray(host[0][0]).shape if not fmt else ((seq.W, seq.H) if turns & 1 else (seq.H, seq.W))
+    _, tight, rows = api.source_window(fmt, rw, rh, 0, 0, [2 ** 31 - 1] * 3)
+    if a.window_pitch < tight[0]:
+        sys.exit(f"--window-pitch {a.window_pitch}: a luma row of these frames has {tight[0]} bytes")
+    pitch = [t * a.window_pitch // tight[0] for t in tight]
+    def pitched(f):
+        out = []
+        for p in range(3):
+            if not rows[p]:
+                out.append(out[-1])
+                continue
+            s = np.zeros((rows[p], pitch[p]), np.uint8)
+            s[:, :tight[p]] = np.ascontiguousarray(f[p]).view(np.uint8).reshape(rows[p], tight[p])
+            out.append(s)
+        return out
+    host = [pitched(f) for f in host]
 dev = [tuple(api.to_device(p) for p in f) for f in host]
 api.device_synchronize()
 drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
@@ -77,6 +101,12 @@ if fmt:
     for d in drvs:
         d.set_source_format(fmt)
         d.set_source_colour(a.source_matrix, a.source_range)
+if turns or a.mirror:
+    for d in drvs:
+        d.set_source_orientation(turns, int(a.mirror))
+if pitch:
+    for d in drvs:
+        d.set_source_window(pitch, 0, 0)
 if a.analysis:
     for d in drvs:
         d.set_analysis(True)

@@ -2,7 +2,13 @@
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
-//              [-input-format NAME] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]]
+//              [-input-format NAME] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
+// -crop W:H:X:Y (ffmpeg's order): the Y4M header gives the SURFACE, the crop the window of it that is the frame (vp8drv_set_source_window:
+// W, H, X, Y even; the pitch is the surface's tight pitch) and so the size that comes in; the whole surface is read from the file, only
+// the window travels to the device.  -rotate N: the frames are stored sideways or upside down and are turned clockwise by N degrees on
+// the device; -mirror: flipped left-right first (vp8drv_set_source_orientation).  Behind 90 or 270 degrees the picture that is coded,
+// and that -resize scales, is as wide as the frames that come in are high.  They compose with -resize, -deinterlace (fields are rows of
+// the frames as stored), -denoise and -input-format.
 // -deinterlace: interlaced frames are made progressive on the device (vp8drv_set_deinterlace; the rule: include/vp8hip_host.h), field =
 // every missing row interpolated, adaptive = what stands still is woven.  :top / :bottom names the field that is kept; without it that
 // is the FIRST field of the header's I tag (It: top, Ib: bottom; vp8host_y4m_interlace), and top, with a line on stderr, for a file
@@ -23,6 +29,8 @@
 // As in the reference, check_SSIM runs after every inter frame and scene_change() looks at every frame that would be an inter frame.
 // Everything between the two files runs behind include/vp8hip_driver.h; the frames are handed over at their source size
 // and padded on the device (cfg.src_width / src_height), key frames carry that size as the display size.
+#include <climits>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,6 +57,8 @@ int main(int argc, char **argv) {
     int denoise = 0;         // -denoise
     int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     int32_t format = -1;     // -input-format (-1: the header's C tag)
+    int crop[4] = {0, 0, 0, 0};     // -crop: W, H, X, Y (W == 0: the whole surface)
+    int turns = 0, mirror = 0;      // -rotate, -mirror
     const char *analysis_path = nullptr;      // -analysis
     static const char *const format_names[VP8HOST_FORMAT_COUNT] = {"i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"};
     for (int i = 3; i < argc; ++i) {
@@ -82,6 +92,15 @@ int main(int argc, char **argv) {
                 if (!strcasecmp(f, format_names[k])) format = k;
             if (format < 0) { fprintf(stderr, "-input-format %s: one of i420 nv12 i422 i444 p010 i010 i210 i410\n", f); return 2; }
         }
+        else if (!strcmp(argv[i], "-crop")) {
+            if (sscanf(val(), "%d:%d:%d:%d", &crop[0], &crop[1], &crop[2], &crop[3]) != 4 || crop[0] <= 0 || crop[1] <= 0) { fprintf(stderr, "-crop W:H:X:Y\n"); return 2; }
+        }
+        else if (!strcmp(argv[i], "-rotate")) {
+            const int deg = atoi(val());
+            if (deg != 0 && deg != 90 && deg != 180 && deg != 270) { fprintf(stderr, "-rotate 0|90|180|270\n"); return 2; }
+            turns = deg / 90;
+        }
+        else if (!strcmp(argv[i], "-mirror")) mirror = 1;
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -126,15 +145,31 @@ int main(int argc, char **argv) {
     fseek(in, (long)first, SEEK_SET);
     // video.src_* is the file's size, video.dst_* the picture that is coded and displayed (-resize; the file's without it), video.wrk_* that
     // rounded up to whole macroblocks (init.h:375-392).  The frames are handed over as the file has them: scaled and padded on the device.
-    const int Wd = rw ? rw : W, Hd = rh ? rh : H;
-    if (Wd < 2 || Hd < 2 || (Wd & 1) || (Hd & 1) || Wd > W || Hd > H) { fprintf(stderr, "-resize %dx%d: even, and not above the file's %dx%d\n", Wd, Hd, W, H); return 2; }
+    // -crop: the file's frames are surfaces and the window is what comes in; -rotate: the upright picture trades its sides
+    int32_t pitch[3] = {0, 0, 0};
+    if (crop[0]) {
+        const int32_t any[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
+        size_t off[3];
+        int32_t rows[3];
+        if (vp8host_source_window(format, W, H, 0, 0, any, off, pitch, rows) != 0 ||      // (row_bytes of the whole surface: its tight pitch)
+            vp8host_source_window(format, crop[0], crop[1], crop[2], crop[3], pitch, off, rows, rows) != 0 || crop[3] + crop[1] > H) {
+            fprintf(stderr, "-crop %d:%d:%d:%d: even numbers, and a window inside the file's %dx%d\n", crop[0], crop[1], crop[2], crop[3], W, H);
+            return 2;
+        }
+    }
+    const int Wraw = crop[0] ? crop[0] : W, Hraw = crop[0] ? crop[1] : H;
+    const int Win = (turns & 1) ? Hraw : Wraw, Hin = (turns & 1) ? Wraw : Hraw;      // the upright frame that comes in
+    const int Wd = rw ? rw : Win, Hd = rh ? rh : Hin;
+    if (Wd < 2 || Hd < 2 || (Wd & 1) || (Hd & 1) || Wd > Win || Hd > Hin) { fprintf(stderr, "-resize %dx%d: even, and not above the incoming %dx%d\n", Wd, Hd, Win, Hin); return 2; }
     const int Wc = (Wd + 15) / 16 * 16, Hc = (Hd + 15) / 16 * 16;
     if (Wc != Wd || Hc != Hd) { cfg.src_width = Wd; cfg.src_height = Hd; }
-    if (Wd != W || Hd != H) { cfg.in_width = W; cfg.in_height = H; }
+    if (Wd != Win || Hd != Hin) { cfg.in_width = Win; cfg.in_height = Hin; }
     vp8drv *drv = nullptr;
     CK(vp8drv_create(&drv, Wc, Hc, 0, &cfg));
     if (denoise) CK(vp8drv_set_denoise(drv, denoise));
     if (format) CK(vp8drv_set_source_format(drv, format));
+    if (turns || mirror) CK(vp8drv_set_source_orientation(drv, turns, mirror));
+    if (crop[0]) CK(vp8drv_set_source_window(drv, pitch, crop[2], crop[3]));
     if (deint) CK(vp8drv_set_deinterlace(drv, deint, field));
     long long dn_filtered = 0, dn_total = 0, di_woven = 0, di_missing = 0;
     FILE *analysis = nullptr;

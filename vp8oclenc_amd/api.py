@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_deinterlace", "vp8hip_deinterlace_restart", "vp8hip_deinterlace_result", "vp8host_deinterlace_frame", "vp8host_y4m_interlace", "vp8drv_set_deinterlace", "vp8drv_get_deinterlace_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_deinterlace", "vp8hip_deinterlace_restart", "vp8hip_deinterlace_result", "vp8host_deinterlace_frame", "vp8host_y4m_interlace", "vp8drv_set_deinterlace", "vp8drv_get_deinterlace_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_set_source_window", "vp8hip_set_source_orientation", "vp8host_source_window", "vp8host_window_frame", "vp8host_orient_frame", "vp8drv_set_source_window", "vp8drv_set_source_orientation", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -692,6 +692,54 @@ def convert_frame(fmt: int, width: int, height: int, planes, matrix: int = 0):
     return out
 
 
+def _pitch3(pitch):
+    p = [int(x) for x in pitch] + [0, 0, 0]
+    return (C.c_int32 * 3)(*p[:3])
+
+
+def source_window(fmt, width: int, height: int, x: int, y: int, pitch):
+    """vp8host_source_window: the window of width x height at (x, y) in a surface of format `fmt` whose planes' rows are pitch[p] bytes
+    apart -> (offset[3], row_bytes[3], rows[3]); ValueError for what the rule refuses"""
+    lib = load_library()
+    lib.vp8host_source_window.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    fmt = source_format(fmt) if isinstance(fmt, str) else int(fmt)
+    off, rb, rows = (C.c_size_t * 3)(), (C.c_int32 * 3)(), (C.c_int32 * 3)()
+    if lib.vp8host_source_window(fmt, int(width), int(height), int(x), int(y), _pitch3(pitch), off, rb, rows) != 0:
+        raise ValueError(f"vp8host_source_window(format {fmt}, {width}x{height} at ({x}, {y}), pitch {list(pitch)}) refused")
+    return [int(v) for v in off], [int(v) for v in rb], [int(v) for v in rows]
+
+
+def window_frame(fmt, width: int, height: int, x: int, y: int, pitch, planes):
+    """vp8host_window_frame: the window of a surface in plain C++.  planes = the surface's planes as contiguous uint8 arrays (as many
+    as the format has) -> the window's tight planes as flat uint8 arrays"""
+    lib = load_library()
+    lib.vp8host_window_frame.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int32)] + [C.c_void_p] * 6
+    fmt = source_format(fmt) if isinstance(fmt, str) else int(fmt)
+    _, rb, rows = source_window(fmt, width, height, x, y, pitch)
+    planes = [np.ascontiguousarray(p).view(np.uint8).reshape(-1) for p in planes]
+    out = [np.empty(rb[p] * rows[p], np.uint8) for p in range(3) if rows[p]]
+    if len(planes) < len(out):
+        raise ValueError(f"window_frame: format {fmt} has {len(out)} planes")
+    src = [planes[p].ctypes.data if p < len(out) else None for p in range(3)]
+    dst = [out[p].ctypes.data if p < len(out) else None for p in range(3)]
+    if lib.vp8host_window_frame(fmt, int(width), int(height), int(x), int(y), _pitch3(pitch), *src, *dst) != 0:
+        raise ValueError("vp8host_window_frame refused")
+    return out
+
+
+def orient_frame(turns: int, mirror: int, planes):
+    """vp8host_orient_frame: `turns` clockwise quarter turns behind a left-right flip (mirror) in plain C++.  planes = (Y, U, V), tight
+    I420 as it comes in -> the upright (Y, U, V)"""
+    lib = load_library()
+    lib.vp8host_orient_frame.argtypes = [C.c_int] * 4 + [C.c_void_p] * 6
+    src = [np.ascontiguousarray(p, np.uint8) for p in planes]
+    h, w = src[0].shape
+    out = [np.empty(p.shape[::-1] if int(turns) & 1 else p.shape, np.uint8) for p in src]
+    if lib.vp8host_orient_frame(int(turns), int(mirror), w, h, *[p.ctypes.data for p in src], *[p.ctypes.data for p in out]) != 0:
+        raise ValueError(f"vp8host_orient_frame(turns {turns}, mirror {mirror}, {w}x{h}) refused")
+    return out
+
+
 def planes_from_i420(fmt: int, y, u, v):
     """the planes of format `fmt` that carry this 8-bit I420 frame exactly -- chroma replicated, samples shifted up to the depth --
     as flat uint8 arrays: vp8host_convert_frame returns the frame from them (for tools and benchmarks that need frames in a format)"""
@@ -901,6 +949,22 @@ class NativeDriver:
         rc = self.lib.vp8drv_set_source_format(self.h, fmt)
         if rc != 0:
             raise Vp8HipError(f"vp8drv_set_source_format({fmt}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_source_window(self, pitch, x: int = 0, y: int = 0) -> None:
+        """vp8drv_set_source_window: the planes handed in are the plane bases of a surface whose rows are pitch[p] bytes apart, and the
+        frame is the window of the incoming size at (x, y); pitch None = off"""
+        self.lib.vp8drv_set_source_window.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int]
+        rc = self.lib.vp8drv_set_source_window(self.h, None if pitch is None else _pitch3(pitch), int(x), int(y))
+        if rc < 0:
+            raise Vp8HipError(f"vp8drv_set_source_window({pitch}, {x}, {y}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_source_orientation(self, turns: int, mirror: int = 0) -> None:
+        """vp8drv_set_source_orientation: source frames are turned by `turns` clockwise quarter turns behind a left-right flip
+        (mirror) on the device; with an odd `turns` the planes handed in are the incoming height wide and the incoming width high"""
+        self.lib.vp8drv_set_source_orientation.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.lib.vp8drv_set_source_orientation(self.h, int(turns), int(mirror))
+        if rc < 0:
+            raise Vp8HipError(f"vp8drv_set_source_orientation({turns}, {mirror}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_deinterlace(self, mode, keep=0) -> None:
         """vp8drv_set_deinterlace: interlaced source frames made progressive; mode off / field / adaptive (0, 1, 2), keep top / bottom
@@ -1312,6 +1376,18 @@ class Vp8Hip:
         self.lib.vp8hip_denoise_result.argtypes = [C.c_void_p, C.POINTER(DenoiseStats)]
         self._chk(self.lib.vp8hip_denoise_result(self.h, C.byref(s)), "denoise_result")
         return s
+
+    def set_source_window(self, pitch, x: int = 0, y: int = 0):
+        """vp8hip_set_source_window: the three pointers of a current frame are the plane bases of a surface whose rows are pitch[p]
+        bytes apart, and the frame is the window of the incoming size at (x, y); pitch None = off"""
+        self.lib.vp8hip_set_source_window.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int]
+        self._chk(self.lib.vp8hip_set_source_window(self.h, None if pitch is None else _pitch3(pitch), int(x), int(y)), "set_source_window")
+
+    def set_source_orientation(self, turns: int, mirror: int = 0):
+        """vp8hip_set_source_orientation: every frame that becomes current is turned by `turns` clockwise quarter turns behind a
+        left-right flip (mirror); sizes keep describing the upright frame, the planes handed in are the raw one's"""
+        self.lib.vp8hip_set_source_orientation.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.vp8hip_set_source_orientation(self.h, int(turns), int(mirror)), "set_source_orientation")
 
     def set_deinterlace(self, mode, keep=0):
         """vp8hip_set_deinterlace: every frame that becomes current passes through the deinterlacer (mode off / field / adaptive or

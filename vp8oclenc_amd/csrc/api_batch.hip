@@ -253,7 +253,7 @@ static int batch_set_current(vp8hip_batch *b, const int *active, const void *con
         b->prep_pending = true;
     }
     if (host) HIPCHK(c0, hipStreamWaitEvent(ps, b->ev_copied, 0));
-    { const int rc = take_frames(m, my, mu, mv, n, ps); if (rc) return rc; }
+    { const int rc = take_frames(m, my, mu, mv, n, ps, nullptr, nullptr, host); if (rc) return rc; }
     HIPCHK(c0, hipGetLastError());
     if (host) {
         HIPCHK(c0, hipEventRecord(b->ev_packed[slot], ps));

@@ -447,6 +447,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     c->fmt_stage.release();
     c->raw_stage.release();
     c->di_stage.release();
+    c->win_stage.release();
+    c->or_stage.release();
     c->di_hist[0].release();
     c->di_hist[1].release();
     shard_release(c);

@@ -1,5 +1,5 @@
 // api_intake.hip -- how a frame becomes a context's current frame: the source size, scaling, format and colour setters, the staging
-// buffers, the stage order (take_frames: convert, deinterlace, scale or pack, denoise, analysis -- the one place that knows it), and the
+// buffers, the stage order (take_frames: window, convert, deinterlace, orient, scale or pack, denoise, analysis -- the one place that knows it), and the
 // single-context ways in (vp8hip_set_current_device, vp8hip_upload_current, vp8hip_prefetch_current).  A batch's ways in are api_batch.hip's;
 // they end in take_frames too.  Replaces the uploads of vp8enc.cpp:386-401.
 #include "vp8hip_ctx.h"
@@ -56,6 +56,17 @@ int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, cons
 
 int copy_planes(vp8hip_ctx *c, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3], hipMemcpyKind kind, hipStream_t s) {
     const uint8_t *py = static_cast<const uint8_t *>(y);
+    if (c->win_on) {      // y, u, v: the plane bases of a surface; the window's rows, tight, and nothing else
+        size_t off[3];
+        int32_t rb[3], rows[3];
+        if (window_rule(c, off, rb, rows) != 0) return VP8HIP_ERR_ARG;
+        const uint8_t *src[3] = {py, static_cast<const uint8_t *>(u), static_cast<const uint8_t *>(v)};
+        for (int p = 0; p < 3; ++p) {
+            if (rows[p]) HIPCHK(c, hipMemcpy2DAsync(d, (size_t)rb[p], src[p] + off[p], (size_t)c->win_pitch[p], (size_t)rb[p], (size_t)rows[p], kind, s));
+            d += nb[p];
+        }
+        return VP8HIP_OK;
+    }
     if (!nb[1] || (u == py + nb[0] && (!nb[2] || v == py + nb[0] + nb[1]))) {      // (one plane, or planes end to end)
         HIPCHK(c, hipMemcpyAsync(d, y, nb[0] + nb[1] + nb[2], kind, s));
         return VP8HIP_OK;
@@ -93,26 +104,38 @@ int intake_ready(vp8hip_ctx *const *m, int n) {
     for (int i = 0; i < n; ++i) {
         int rc = format_stage_ready(m[i]);
         if (!rc) rc = deinterlace_ready(m[i]);
+        if (!rc) rc = geometry_ready(m[i]);
         if (rc) return rc;
     }
     return VP8HIP_OK;
 }
 
 int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u, const void *const *v, int n, hipStream_t s,
-                const hipMemcpyKind *alone, hipEvent_t planes_read) {
+                const hipMemcpyKind *alone, hipEvent_t planes_read, bool tight) {
     vp8hip_ctx *c0 = m[0];
     { const int rc = intake_ready(m, n); if (rc) return rc; }
     SourceItem src[MAX_BATCH];
     ConvertItem cv[MAX_BATCH];
     DeinterlaceItem di[MAX_BATCH];
+    GeometryItem wn[MAX_BATCH], orn[MAX_BATCH];
+    const bool window = c0->win_on && !tight;      // (planes that came from the host are the window already: copy_planes)
     for (int i = 0; i < n; ++i) {
         next_current(m[i]);
         src[i] = SourceItem{&m[i]->cur, y[i], u[i], v[i], &m[i]->scale};
+        if (window) (void)window_item(m[i], wn[i], src[i].y, src[i].u, src[i].v);      // (a window: what follows reads the member's tight planes)
         convert_item(m[i], cv[i], src[i].y, src[i].u, src[i].v);      // (a source format: what follows reads the member's converted planes)
         (void)deinterlace_item(m[i], s, di[i], src[i].y, src[i].u, src[i].v);      // (a deinterlacer: ... the member's deinterlaced planes; same_intake: all or none)
+        (void)orient_item(m[i], orn[i], src[i].y, src[i].u, src[i].v);      // (an orientation: ... the member's upright planes)
     }
     int w, h;
-    incoming_size(c0, &w, &h);
+    incoming_size(c0, &w, &h);      // (the raw size: what the window, the converter and the deinterlacer work at)
+    if (window) {      // one launch for all members, in front of everything else
+        Timed t(c0, VP8HIP_K_PACK);
+        size_t off[3];
+        int32_t rb[3], rows[3];
+        if (window_rule(c0, off, rb, rows) != 0) return VP8HIP_ERR_ARG;
+        launch_window_batch(s, off, c0->win_pitch, rb, rows, wn, n);
+    }
     if (c0->src_fmt) {      // one launch for all members, in front of the pack or scale launch
         Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
         if (!launch_convert_batch(s, c0->src_fmt, c0->src_colour, w, h, cv, n)) return VP8HIP_ERR_ARG;
@@ -120,6 +143,10 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
     if (c0->di_mode) {      // ... behind the converter and in front of the pack or scale launch
         Timed t(c0, VP8HIP_K_PACK);
         launch_deinterlace_batch(s, w, h, c0->di_keep, di, n);
+    }
+    if (c0->or_turns || c0->or_mirror) {      // ... behind the deinterlacer (fields are rows of the source) and in front of the pack or scale launch
+        Timed t(c0, VP8HIP_K_PACK);
+        launch_orient_batch(s, c0->or_turns, c0->or_mirror, w, h, orn, n);
     }
     if (c0->scale.in_w) {      // a frame that is scaled is not packed as well
         Timed t(c0, VP8HIP_K_PACK);
@@ -150,10 +177,11 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
     return VP8HIP_OK;
 }
 
-// one context's new current frame on its own stream; planes from the host that a convert, deinterlace or scale launch is to read pass
-// through raw_stage first (a frame larger than the surface cannot be copied into the surface)
-static int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind, hipEvent_t planes_read = nullptr) {
-    if (kind != hipMemcpyDeviceToDevice && (c->src_fmt || c->di_mode || c->scale.in_w)) {
+// one context's new current frame on its own stream; planes from the host that a convert, deinterlace, orient or scale launch is to read,
+// and the window of a surface in host memory, pass through raw_stage first (a frame larger than the surface cannot be copied into the
+// surface).  tight: planes in device memory that are the window already (a prefetch's).
+static int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind, hipEvent_t planes_read = nullptr, bool tight = false) {
+    if (kind != hipMemcpyDeviceToDevice && (c->src_fmt || c->di_mode || c->scale.in_w || c->win_on || c->or_turns || c->or_mirror)) {
         size_t nb[3];
         incoming_bytes(c, nb);
         int rc = c->raw_stage.grow(c, nb[0] + nb[1] + nb[2]);
@@ -163,9 +191,10 @@ static int take_current(vp8hip_ctx *c, const void *y, const void *u, const void 
         u = c->raw_stage.p + nb[0];
         v = c->raw_stage.p + nb[0] + nb[1];
         kind = hipMemcpyDeviceToDevice;
+        tight = true;
     }
     // (&kind: a context on its own, and where its planes are by now -- the host's only without a format, deinterlacer or scaler)
-    return take_frames(&c, &y, &u, &v, 1, c->stream, &kind, planes_read);
+    return take_frames(&c, &y, &u, &v, 1, c->stream, &kind, planes_read, tight);
 }
 
 }  // namespace vp8
@@ -220,7 +249,7 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
         const int slot = c->h2d_idx = next;
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_h2d, 0));
         const uint8_t *d = c->h2d_stage[slot].p;
-        const int rc = take_current(c, d, d + nb[0], d + nb[0] + nb[1], hipMemcpyDeviceToDevice, c->ev_stage_read[slot]);
+        const int rc = take_current(c, d, d + nb[0], d + nb[0] + nb[1], hipMemcpyDeviceToDevice, c->ev_stage_read[slot], true);
         if (rc) return rc;
         c->stage_read_valid[slot] = true;
         HIPCHK(c, hipEventSynchronize(c->ev_h2d));      // the host's planes are the host's again when this returns (done long ago, normally)
@@ -260,10 +289,12 @@ static void set_source(vp8hip_ctx *c, int w, int h, int in_w, int in_h, int kind
 int vp8hip_set_source_size(vp8hip_ctx *c, int src_width, int src_height) {
     if (!c) return VP8HIP_ERR_ARG;
     if (src_width == 0 && src_height == 0) {
+        if (!geometry_allows(c, c->src_fmt, c->W, c->H, c->or_turns)) return VP8HIP_ERR_ARG;
         set_source(c, 0, 0, 0, 0, 0);
         return VP8HIP_OK;
     }
-    if (!source_size_ok(c, src_width, src_height) || (c->di_mode && src_height < 4)) return VP8HIP_ERR_ARG;      // (the deinterlacer needs a row of each field in every plane)
+    // (the deinterlacer needs a row of each field in every plane, and a window in force must fit its pitch at the new size)
+    if (!source_size_ok(c, src_width, src_height) || !geometry_allows(c, c->src_fmt, src_width, src_height, c->or_turns)) return VP8HIP_ERR_ARG;
     set_source(c, src_width, src_height, 0, 0, 0);
     return VP8HIP_OK;
 }
@@ -272,7 +303,7 @@ int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int ds
     if (!c) return VP8HIP_ERR_ARG;
     if (!in_width && !in_height && !dst_width && !dst_height) return vp8hip_set_source_size(c, 0, 0);
     if (!source_size_ok(c, dst_width, dst_height) || (filter != 0 && filter != 1) || (in_width & 1) || (in_height & 1) ||
-        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384 || (c->di_mode && in_height < 4))
+        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384 || !geometry_allows(c, c->src_fmt, in_width, in_height, c->or_turns))
         return VP8HIP_ERR_ARG;
     if (in_width == dst_width && in_height == dst_height) return vp8hip_set_source_size(c, dst_width, dst_height);
     // everything that can be refused is tried before anything of the context changes
@@ -295,6 +326,7 @@ int vp8hip_set_source_format(vp8hip_ctx *c, int format) {
     if (!c || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END)
         return VP8HIP_ERR_ARG;
     if (format == c->src_fmt) return VP8HIP_OK;
+    { int w, h; upright_size(c, &w, &h); if (!geometry_allows(c, format, w, h, c->or_turns)) return VP8HIP_ERR_ARG; }      // (a window in force: its pitches under the new format)
     { const int rc = quiesce_intake(c); if (rc) return rc; }
     const int before = c->src_fmt;
     c->src_fmt = format;

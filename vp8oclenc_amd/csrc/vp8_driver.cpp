@@ -672,6 +672,26 @@ int vp8drv_set_source_colour(vp8drv *d, int matrix) {
     return VP8HIP_OK;
 }
 
+int vp8drv_set_source_window(vp8drv *d, const int32_t *pitch, int x, int y) {
+    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_source_window(d->hip, pitch, x, y));
+    d->staged = nullptr;             // planes staged through another window are not this window's frame
+    d->staged_scan = false;
+    return VP8HIP_OK;
+}
+
+int vp8drv_set_source_orientation(vp8drv *d, int turns, int mirror) {
+    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_source_orientation(d->hip, turns, mirror));
+    d->staged = nullptr;             // planes staged under another orientation are not this one's frame
+    d->staged_scan = false;
+    return VP8HIP_OK;
+}
+
 int vp8drv_set_analysis(vp8drv *d, int on) {
     if (!d || (on != 0 && on != 1) || !d->cfg.device_params) return VP8HIP_ERR_ARG;
     if (d->in_batch) return VP8HIP_ERR_STATE;

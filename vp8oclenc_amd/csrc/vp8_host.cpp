@@ -697,3 +697,80 @@ extern "C" int vp8host_analyse_luma(const uint8_t *cur, const uint8_t *prev, int
     *out = r;
     return 0;
 }
+
+// The geometry of the input side in plain C++ (include/vp8hip_host.h has the rule): the window of a surface, and quarter turns.
+extern "C" int vp8host_source_window(int format, int width, int height, int x, int y, const int32_t pitch[3], size_t offset[3],
+                                     int32_t row_bytes[3], int32_t rows[3]) {
+    // per plane: horizontal shift, vertical shift, bytes per element (0: the format has no such plane)
+    struct PlaneRule { int hs, vs, bpe; };
+    PlaneRule r[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    SourceLayout l;
+    if (format == VP8HOST_FORMAT_YUY2 || format == VP8HOST_FORMAT_UYVY) r[0] = {1, 0, 4};
+    else if (format == VP8HOST_FORMAT_BGRA || format == VP8HOST_FORMAT_RGBA) r[0] = {0, 0, 4};
+    else if (source_layout(format, &l)) {
+        const int b = l.depth > 8 ? 2 : 1;
+        r[0] = {0, 0, b};
+        r[1] = {l.sub_x, l.sub_y, l.nv ? 2 * b : b};
+        if (!l.nv) r[2] = r[1];
+    } else return -1;
+    if (!pitch || !offset || !row_bytes || !rows || width <= 0 || height <= 0 || (width & 1) || (height & 1) || x < 0 || y < 0 || (x & 1) || (y & 1))
+        return -1;
+    for (int p = 0; p < 3; ++p)
+        if (r[p].bpe && (int64_t)pitch[p] < (int64_t)((x + width) >> r[p].hs) * r[p].bpe) return -1;
+    for (int p = 0; p < 3; ++p) {
+        offset[p] = 0;
+        row_bytes[p] = rows[p] = 0;
+        if (!r[p].bpe) continue;
+        rows[p] = height >> r[p].vs;
+        row_bytes[p] = (width >> r[p].hs) * r[p].bpe;
+        offset[p] = (size_t)(y >> r[p].vs) * (size_t)pitch[p] + (size_t)(x >> r[p].hs) * (size_t)r[p].bpe;
+    }
+    return 0;
+}
+
+extern "C" int vp8host_window_frame(int format, int width, int height, int x, int y, const int32_t pitch[3], const uint8_t *p0,
+                                    const uint8_t *p1, const uint8_t *p2, uint8_t *out0, uint8_t *out1, uint8_t *out2) {
+    size_t off[3];
+    int32_t rb[3], rows[3];
+    if (vp8host_source_window(format, width, height, x, y, pitch, off, rb, rows) != 0) return -1;
+    const uint8_t *src[3] = {p0, p1, p2};
+    uint8_t *dst[3] = {out0, out1, out2};
+    for (int p = 0; p < 3; ++p)
+        if (rows[p] && (!src[p] || !dst[p])) return -1;
+    for (int p = 0; p < 3; ++p)
+        for (int r = 0; r < rows[p]; ++r)
+            memcpy(dst[p] + (size_t)r * (size_t)rb[p], src[p] + off[p] + (size_t)r * (size_t)pitch[p], (size_t)rb[p]);
+    return 0;
+}
+
+namespace {
+
+void orient_plane(const uint8_t *in, uint8_t *out, int rw, int rh, int turns, int mirror) {
+    const bool odd = turns & 1;
+    const int ow = odd ? rh : rw, oh = odd ? rw : rh;
+    for (int y = 0; y < oh; ++y)
+        for (int x = 0; x < ow; ++x) {
+            int sx, sy;      // where out(x, y) sits in s, the mirrored frame
+            switch (turns) {
+                case 0: sx = x; sy = y; break;
+                case 1: sx = y; sy = rh - 1 - x; break;
+                case 2: sx = rw - 1 - x; sy = rh - 1 - y; break;
+                default: sx = rw - 1 - y; sy = x; break;
+            }
+            if (mirror) sx = rw - 1 - sx;
+            out[(size_t)y * (size_t)ow + (size_t)x] = in[(size_t)sy * (size_t)rw + (size_t)sx];
+        }
+}
+
+}  // namespace
+
+extern "C" int vp8host_orient_frame(int turns, int mirror, int raw_width, int raw_height, const uint8_t *in_y, const uint8_t *in_u,
+                                    const uint8_t *in_v, uint8_t *out_y, uint8_t *out_u, uint8_t *out_v) {
+    if (turns < 0 || turns > 3 || (mirror != 0 && mirror != 1) || raw_width < 2 || raw_height < 2 || (raw_width & 1) || (raw_height & 1) ||
+        !in_y || !in_u || !in_v || !out_y || !out_u || !out_v)
+        return -1;
+    orient_plane(in_y, out_y, raw_width, raw_height, turns, mirror);
+    orient_plane(in_u, out_u, raw_width / 2, raw_height / 2, turns, mirror);
+    orient_plane(in_v, out_v, raw_width / 2, raw_height / 2, turns, mirror);
+    return 0;
+}

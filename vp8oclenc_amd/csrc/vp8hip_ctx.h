@@ -8,7 +8,7 @@
 //
 // Units: api_context.hip (create / destroy, surfaces, parameters, stream ordering, the record wait, downloads, device memory),
 // api_intake.hip (how a frame becomes current: source size / scaling / format / colour, staging, the stage order; upload, prefetch, set_current_device),
-// api_deinterlace.hip, api_denoise.hip, api_analysis.hip, api_quality.hip (a stage each: its items, its setters, its results),
+// api_geometry.hip, api_deinterlace.hip, api_denoise.hip, api_analysis.hip, api_quality.hip (a stage each: its items, its setters, its results),
 // api_inter.hip (inter path, check_SSIM, key frames, loop filter), api_entropy.hip (coefficient + header entropy stage, frames out),
 // api_batch.hip (vp8hip_batch_*), api_shard.hip (export / import, RCCL: vp8hip_shard_*, vp8hip_group_*), api_profile.hip (timers, debug taps).
 #ifndef VP8HIP_CTX_H
@@ -175,6 +175,20 @@ struct vp8hip_ctx {
     DeviceBuf di_stage, di_hist[2];
     int di_idx = 0, di_hist_w = 0, di_hist_h = 0;
     Record<vp8::DeinterlaceMirror> di;
+    // vp8hip_set_source_window: the three pointers of a current frame are the plane bases of a surface whose rows are win_pitch[p] bytes
+    // apart, and the frame is the window of the incoming size at (win_x, win_y).  k_window_b, in front of everything, writes the tight
+    // planes end to end into win_stage (laid out as raw_stage) and the next stage reads that; planes from the HOST arrive windowed
+    // (copy_planes: 2-D copies) and skip the launch.
+    // vp8hip_set_source_orientation: or_turns clockwise quarter turns behind a left-right flip (or_mirror).  Every size of the context
+    // describes the UPRIGHT frame; the planes handed in, the window, the converter and the deinterlacer are of the raw size
+    // (incoming_size), which is the upright incoming size with width and height traded when or_turns is odd.  k_orient_b, behind the
+    // deinterlacer, writes tight I420 of the upright size into or_stage (tight_i420) and the pack or scale launch reads that.
+    bool win_on = false;
+    int32_t win_pitch[3] = {0, 0, 0};
+    int win_x = 0, win_y = 0;
+    DeviceBuf win_stage;
+    int or_turns = 0, or_mirror = 0;
+    DeviceBuf or_stage;
     // vp8hip_set_analysis: one allocation (an.d: the five sum / ticket words of k_analyse_src_b, then at +256 the history plane -- the luma
     // of the previous frame taken in, tight, coded size) and one mirror (an.h) of three parts, each with a seq of its own: the views
     // an_src[frame & 1] and an_mb point into an.h and hold the seq their part's last launch writes and its stream (`an` itself is never waited for).
@@ -406,10 +420,16 @@ void side_stream_ordered(vp8hip_ctx *c);
 int check_device_timeout(vp8hip_ctx *c);
 // ---- api_intake.hip: how a frame becomes current ----
 int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw = 0, int sh = 0);
-// size of the planes a context takes as current frames: the incoming size of its scaler, its source size, or the coded size
-inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) {
+// size of the UPRIGHT frame a context takes in: the incoming size of its scaler, its source size, or the coded size
+inline void upright_size(const vp8hip_ctx *c, int *w, int *h) {
     *w = c->scale.in_w ? c->scale.in_w : (c->src_w ? c->src_w : c->W);
     *h = c->scale.in_w ? c->scale.in_h : (c->src_h ? c->src_h : c->H);
+}
+// size of the planes a context takes as current frames (what the window, the converter and the deinterlacer work at): the upright
+// size, width and height traded under an odd number of quarter turns
+inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) {
+    if (c->or_turns & 1) upright_size(c, h, w);
+    else upright_size(c, w, h);
 }
 // bytes of the planes a context takes as a current frame, in its source format (I420: ny, nc, nc)
 inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) {
@@ -421,23 +441,28 @@ inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what
     return a->src_fmt == b->src_fmt && a->src_colour == b->src_colour && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
            (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level &&     // (and one denoiser level)
            a->di_mode == b->di_mode && a->di_keep == b->di_keep &&                                  // (one deinterlacer mode and parity)
-           a->an_on == b->an_on;                                                                    // (analysis on for all or for none)
+           a->an_on == b->an_on &&                                                                  // (analysis on for all or for none)
+           a->win_on == b->win_on && (!a->win_on || (a->win_pitch[0] == b->win_pitch[0] && a->win_pitch[1] == b->win_pitch[1] && a->win_pitch[2] == b->win_pitch[2] &&
+                                                     a->win_x == b->win_x && a->win_y == b->win_y)) &&      // (one window)
+           a->or_turns == b->or_turns && a->or_mirror == b->or_mirror;                              // (one orientation)
 }
 // whatever is in flight on the context's streams (and its batch's) ends: setters and growing buffers, never per frame
 int quiesce_intake(vp8hip_ctx *c);
 // a frame's planes (nb: their bytes in the source format; a format of two planes or one never reads the later pointers) end to end into d,
-// on stream s: ONE copy when they lie end to end already (an I420 frame as a file reader or a decoder holds it)
+// on stream s: ONE copy when they lie end to end already (an I420 frame as a file reader or a decoder holds it).  A context with a
+// window: y, u, v are the plane bases of a surface and only the window's bytes travel, one 2-D copy per plane.
 int copy_planes(vp8hip_ctx *c, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3], hipMemcpyKind kind, hipStream_t s);
 // the buffers the members' next frames need, at their incoming size (as a rule: they are there); changes nothing else
 int intake_ready(vp8hip_ctx *const *m, int n);
-// THE ORDER, once: n contexts of one intake (same_intake) take their new current frames in on stream s -- convert, deinterlace,
-// scale or pack, denoise, analysis.  y, u, v: the members' planes in DEVICE memory in their source format.
+// THE ORDER, once: n contexts of one intake (same_intake) take their new current frames in on stream s -- window, convert, deinterlace,
+// orient, scale or pack, denoise, analysis.  y, u, v: the members' planes in DEVICE memory in their source format: the plane bases of
+// their surfaces when the contexts have a window, unless `tight` (planes that came from the host through copy_planes are the window already).
 // alone: nullptr for a batch's members.  For a context on its own (n == 1, s its stream) it points at where the planes are: such a
 // context keeps the pack launch of one, and without a format, deinterlacer or scaler its planes may be the host's, copied straight
 // into the surface.
 // planes_read (or nullptr) is recorded behind the pack or scale launch: nothing behind it reads the caller's planes.
 int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u, const void *const *v, int n, hipStream_t s,
-                const hipMemcpyKind *alone = nullptr, hipEvent_t planes_read = nullptr);
+                const hipMemcpyKind *alone = nullptr, hipEvent_t planes_read = nullptr, bool tight = false);
 // ---- api_inter.hip ----
 void drop_overflowed_frame(vp8hip_ctx *c);
 int inter_check(const vp8hip_ctx *c, int prev_is_golden, int prev_is_altref, int use_golden, int use_altref);
@@ -473,6 +498,16 @@ bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it);
 // deinterlace_item: y, u, v = tight I420 in DEVICE memory; afterwards they are the planes in di_stage.  false: off, nothing to launch.
 int deinterlace_ready(vp8hip_ctx *c);
 bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const void *&y, const void *&u, const void *&v);
+// ---- api_geometry.hip ----
+// The window in front of everything and the orientation behind the deinterlacer (take_frames).  geometry_ready: their staging buffers
+// at the context's incoming size.  *_item: false = off, nothing to launch; otherwise y, u, v are the stage's output afterwards.
+// window_rule: vp8host_source_window for the context's window, format and incoming size.
+// geometry_allows: would the window and the deinterlacer in force still be valid with this format, upright incoming size and turns?
+int geometry_ready(vp8hip_ctx *c);
+bool window_item(vp8hip_ctx *c, GeometryItem &it, const void *&y, const void *&u, const void *&v);
+bool orient_item(vp8hip_ctx *c, GeometryItem &it, const void *&y, const void *&u, const void *&v);
+int window_rule(const vp8hip_ctx *c, size_t off[3], int32_t row_bytes[3], int32_t rows[3]);
+bool geometry_allows(const vp8hip_ctx *c, int format, int upright_w, int upright_h, int turns);
 // ---- api_analysis.hip ----
 // The source side: the frame just taken into c->cur, behind its pack / scale / denoise launches on stream s (take_frames).  The coding side: the attempt whose loop filter was just launched on s (c->lf_key says which kind).
 // *_item: false = analysis off, nothing to launch.

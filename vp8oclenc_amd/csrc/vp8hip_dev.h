@@ -213,6 +213,16 @@ struct DeinterlaceItem {
     int32_t frame_number;
 };
 void launch_deinterlace_batch(hipStream_t s, int w, int h, int keep, const DeinterlaceItem *items, int n);
+// kernels_geometry.hip: the two geometric stages of the input side; the rules are include/vp8hip_host.h's.  Both move bytes from a
+// member's src planes to its dst planes (a staging buffer of the context), which do not overlap.
+// k_window_b (vp8hip_set_source_window) IN FRONT of everything: src = the plane bases of a surface, dst = the tight planes of the
+// window end to end; offset, pitch, row_bytes, rows: vp8host_source_window's (rows[p] == 0: the format has no plane p).
+// k_orient_b (vp8hip_set_source_orientation) BEHIND the deinterlacer and IN FRONT of the pack or scale launch: tight I420 of
+// raw_w x raw_h in, tight I420 of the upright size out (raw_h x raw_w for an odd number of turns).
+struct GeometryItem { const uint8_t *src[3]; uint8_t *dst[3]; };
+void launch_window_batch(hipStream_t s, const size_t offset[3], const int32_t pitch[3], const int32_t row_bytes[3], const int32_t rows[3],
+                         const GeometryItem *items, int n);
+void launch_orient_batch(hipStream_t s, int turns, int mirror, int raw_w, int raw_h, const GeometryItem *items, int n);
 // check_SSIM's verdict riding in a loop filter launch (see CheckItem below)
 struct LfCheck {
     int on, qi_min;
