@@ -179,6 +179,63 @@ int vp8hip_debug_weight_mfma(vp8hip_ctx *c, const int32_t *d, int n, int32_t *ou
     return VP8HIP_OK;
 }
 
+// test tap (not in the public header): the same through the row-order operand of the whole-pel search's loop form (metric_a_rows)
+int vp8hip_debug_weight_mfma_rows(vp8hip_ctx *c, const int32_t *d, int n, int32_t *out) {
+    USE_DEVICE(c);
+    JOIN_LF(c);
+    if (!c || !d || !out || n <= 0) return VP8HIP_ERR_ARG;
+    int32_t *dd = nullptr, *dout = nullptr;
+    HIPCHK(c, hipMalloc(&dd, (size_t)n * 64));
+    HIPCHK(c, hipMalloc(&dout, (size_t)n * 4));
+    HIPCHK(c, hipMemcpyAsync(dd, d, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
+    launch_weight_tap_mfma_rows(c->stream, dd, n, dout);
+    HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(dd);
+    hipFree(dout);
+    return VP8HIP_OK;
+}
+
+// test tap (not in the public header): ONE level of the batched whole-pel search (launch_search1_batch, in the form the switches pick) over
+// caller-written source nets.  The members' pyramids must stand (a batched inter_transform has run on them and every stream is idle).  src[3 i + r] /
+// dst[3 i + r]: member i's net of reference r going in (the coarser level's vectors, b8 x short2) and coming out; null where the reference is not enabled.
+int vp8hip_debug_search1_batch(vp8hip_ctx *const *ctxs, int n, const int *use_golden, const int *use_altref, int level,
+                               const int16_t *const *src, int16_t *const *dst) {
+    if (!ctxs || n <= 0 || n > MAX_BATCH || !use_golden || !use_altref || level < 0 || level > 4 || !src || !dst) return VP8HIP_ERR_ARG;
+    vp8hip_ctx *c0 = ctxs[0];
+    USE_DEVICE(c0);
+    CodingItem it[MAX_BATCH];
+    for (int i = 0; i < n; ++i) {
+        vp8hip_ctx *c = ctxs[i];
+        if (!c || c->b8 != c0->b8 || c->mbw != c0->mbw) return VP8HIP_ERR_ARG;
+        JOIN_LF(c);
+        it[i] = coding_item(c, use_golden[i], use_altref[i]);
+        for (int r = 0; r < 3; ++r) {
+            if (!it[i].refs.use[r]) continue;
+            if (!src[3 * i + r] || !dst[3 * i + r]) return VP8HIP_ERR_ARG;
+            HIPCHK(c0, hipMemcpyAsync(c->nets.net[r][0], src[3 * i + r], (size_t)c->b8 * 4, hipMemcpyHostToDevice, c0->stream));
+            HIPCHK(c0, hipMemsetAsync(c->nets.net[r][1], 0, (size_t)c->b8 * 4, c0->stream));
+        }
+    }
+    launch_search1_batch(c0->stream, it, n, level, 0, c0->mbw * 2);
+    for (int i = 0; i < n; ++i)
+        for (int r = 0; r < 3; ++r)
+            if (it[i].refs.use[r]) HIPCHK(c0, hipMemcpyAsync(dst[3 * i + r], ctxs[i]->nets.net[r][1], (size_t)ctxs[i]->b8 * 4, hipMemcpyDeviceToHost, c0->stream));
+    HIPCHK(c0, hipStreamSynchronize(c0->stream));
+    HIPCHK(c0, hipGetLastError());
+    return VP8HIP_OK;
+}
+
+// test tap (not in the public header, no device needed): the metric's two A operands as the kernels hold them, 64 lanes x 4 dwords each --
+// column order (K_METRIC_A) and row order (K_METRIC_A_ROWS)
+int vp8hip_debug_metric_tables(uint32_t *a_cols, uint32_t *a_rows) {
+    if (!a_cols || !a_rows) return VP8HIP_ERR_ARG;
+    static constexpr MetricTable cols = make_metric_a(), rows = make_metric_a_rows();
+    memcpy(a_cols, cols.w, sizeof(cols.w));
+    memcpy(a_rows, rows.w, sizeof(rows.w));
+    return VP8HIP_OK;
+}
+
 // test hook (not in the public header): while on, the loop filter's inter-band counters are published from a wrong
 // base, so every band but the first runs into its bounded wait -> VP8HIP_ERR_TIMEOUT at the next synchronize
 int vp8hip_debug_lf_stall(vp8hip_ctx *c, int on) {

@@ -2,14 +2,17 @@
 //   packing of a new frame into its padded surface, edge replication, pyramid, hierarchical full-pel search
 //   (the quarter-pel search is kernels_s2.hip, the reference choice is inside k_mb).
 // Behaviour follows the reference kernels cited at each kernel (paths under the reference's src/); the parallel
-// decomposition is new (k_search1: a lane per candidate row of an 8x8 block walking five candidates over
-// transposed columns, the winner by a shuffle minimum of packed (cost, index) keys).  Every kernel has a single
-// and a batched form (blockIdx.z = context, vp8hip_dev.h).
+// decomposition is new (k_search1: a lane per candidate row of an 8x8 block walking five candidates over the
+// row's eight bytes -- transposed columns in the dot4 forms, the rows as loaded in the loop forms, whose metric
+// is one MFMA per candidate with a row-order A table --, the winner by a minimum of packed (cost, index) keys:
+// a shuffle tree, or through LDS in the batched loop form, which packs 51 blocks into a workgroup's 256 lanes,
+// s1_fill_layout.h).  Every kernel has a single and a batched form (blockIdx.z = context, vp8hip_dev.h).
 #include <stdlib.h>
 #include <string.h>
 
 #include "vp8hip_dev.h"
 #include "s1_pre_layout.h"
+#include "s1_fill_layout.h"
 
 namespace vp8 {
 
@@ -277,31 +280,27 @@ __device__ __forceinline__ void s1_subblock(const uint8_t *cp, int cstride, cons
 // (weight_mfma, vp8hip_dev.h; every lane of the wave runs this), B = its four columns, C = the current block's share, read again from LDS for each
 // candidate: held in registers next to the 16 results it would cost 16 registers, and the loop form is tuned for eight waves per SIMD.  The
 // offset passes through an empty asm per candidate so that the compiler cannot see the five reads are the same and keep one copy (it did, and
-// then copied 16 registers into the accumulator before every MFMA); hiding the pointer instead makes the reads flat loads.  An MFMA operand
-// is an even-aligned register quad, so candidates 1 and 3 (columns 1..4, 3..6) take copies: made by vcopy right before their MFMA, behind a
-// scheduling barrier.  Left to itself hipcc built all five quads up front (20 registers for the 8 columns) and spilled at 64.
-__device__ __forceinline__ int vcopy(uint32_t x) {
-    int y;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "v"(x));
-    return y;
-}
+// then copied 16 registers into the accumulator before every MFMA); hiding the pointer instead makes the reads flat loads.  The B operand of
+// a candidate is made right before its MFMA, behind a scheduling barrier: left to itself hipcc built all five quads up front and spilled at 64.
+// History: the operand used to be in column order (K_METRIC_A), which cost two 4x4 byte transposes of the window (16 v_perm) and, an MFMA
+// operand being an even-aligned register quad, eight v_mov for candidates 1 and 3.  With the A table in row order (wa = metric_a_rows,
+// vp8hip_dev.h) candidate dx = i is bytes i..i+3 of the four rows: the low dwords as loaded (i = 0), the high dwords (i = 4), and one
+// v_alignbyte per row, written straight into an aligned quad, for the three between -- 12 instructions where 24 stood.
 __device__ __forceinline__ void s1_subblock_pre(v4i wa, const int *pre_lds, int pre_off, const uint8_t *rp, int rstride, int acc[5]) {
-    uint32_t q0[4], q1[4];
+    uint32_t q0[4], q1[4];      // bytes 0..3 and 4..7 of the window's four rows, pixels biased
 #pragma unroll
     for (int y = 0; y < 4; ++y) {
-        const uint2 q = ld_u64(rp + (ptrdiff_t)y * rstride);
-        q0[y] = q.x ^ 0x80808080u; q1[y] = q.y ^ 0x80808080u;
+        q0[y] = ld_u32(rp + (ptrdiff_t)y * rstride) ^ 0x80808080u;
+        q1[y] = ld_u32(rp + (ptrdiff_t)y * rstride + 4) ^ 0x80808080u;
     }
-    uint32_t col[8];
-    transpose4x4(q0, col);
-    transpose4x4(q1, col + 4);
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         int off = pre_off;
         asm volatile("" : "+v"(off));
         __builtin_amdgcn_sched_barrier(0);
-        const v4i b = (i & 1) ? v4i{vcopy(col[i]), vcopy(col[i + 1]), vcopy(col[i + 2]), vcopy(col[i + 3])}
-                              : v4i{(int)col[i], (int)col[i + 1], (int)col[i + 2], (int)col[i + 3]};
+        v4i b;
+#pragma unroll
+        for (int y = 0; y < 4; ++y) b[y] = i == 0 ? (int)q0[y] : i == 4 ? (int)q1[y] : (int)__builtin_amdgcn_alignbyte(q1[y], q0[y], (uint32_t)i);
         acc[i] += weight_mfma(wa, load_pre16(pre_lds + off), b);
     }
 }
@@ -330,10 +329,14 @@ __device__ __forceinline__ void s1_make_pre(const Plane &cur, int cx, int cy, in
 // the block, `lane` its number in the wave) search the 25 candidates around the scaled parent vector `pv` (packed short2, 0 = none).
 // Returns the block's vector as the net holds it (packed short2, already multiplied by pixel_rate); valid in the lane with sub == 0.
 // `live` false: the lanes take part in the shuffles on harmless in-frame data.
-template <bool SPLIT, bool PRE_LDS = false>
+// LDS_MIN (the filled loop form, where a block's five lanes may lie in two waves): the minimum over the block's lanes goes through min_lds, one word per
+// lane of the workgroup, this lane's at min_lds[sub] -- one store, a barrier, five reads (so EVERY lane of the workgroup must come here), four v_min_u32
+// where the shuffle tree is three steps of six instructions.  The caller keeps the next call from overwriting words still being read.
+template <bool SPLIT, bool PRE_LDS = false, bool LDS_MIN = false>
 __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, int cx, int cy, uint32_t pv, bool live, int sub, int lane,
                                                   const int *pre_lds = nullptr /* PRE_LDS (loop form): the workgroup's table from s1_make_pre */,
-                                                  int pre_off = 0 /* ... and where this block's [sub-block][16] start in it */) {
+                                                  int pre_off = 0 /* ... and where this block's [sub-block][16] start in it */,
+                                                  uint32_t *min_lds = nullptr /* LDS_MIN: the word of this block's first lane */) {
     const int sb0 = sub / 5, j = sub - 5 * sb0;       // SPLIT: this lane's sub-block; otherwise sb0 = 0
     // vector / pixel_rate truncates toward zero (:495-500)
     int v0x = (int16_t)(pv & 0xffffu), v0y = (int16_t)(pv >> 16);
@@ -363,7 +366,7 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
     } else {
         // one sub-block at a time (loop NOT unrolled: the register footprint decides how many waves a SIMD holds)
         if (PRE_LDS) {
-            const v4i wa = metric_a(lane);
+            const v4i wa = metric_a_rows(lane);
 #pragma unroll 1
             for (int sb = 0; sb < 4; ++sb) {
                 const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;
@@ -391,10 +394,20 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
     }
     // minimum over the five dy lanes of the block (its sb = 0 lanes hold the full sums): (cost << 8 | dxy) = the
     // reference's first strict minimum
+    if (LDS_MIN) {      // (the keys of a block differ in their low byte: the minimum is the same integer whatever the order)
+        min_lds[sub] = best;
+        __syncthreads();
 #pragma unroll
-    for (int off = 1; off <= 4; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl((int)best, lane + off, 64);
-        if (j + off < 5 && o < best) best = o;
+        for (int k = 0; k < 5; ++k) {
+            const uint32_t o = min_lds[k];
+            best = o < best ? o : best;
+        }
+    } else {
+#pragma unroll
+        for (int off = 1; off <= 4; off <<= 1) {
+            const uint32_t o = (uint32_t)__shfl((int)best, lane + off, 64);
+            if (j + off < 5 && o < best) best = o;
+        }
     }
     int bx, by;  // best position minus block position
     if (best != 0xffffffffu) {
@@ -414,14 +427,22 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
 // REF_LOOP: a workgroup searches its blocks in EVERY enabled reference, one after the other (grid y = 1), instead of a workgroup per reference:
 // the block arithmetic and the current blocks' share of the metric are made once for the two or three of them (batches; one video keeps a
 // workgroup per reference: there a launch is as long as one wave)
-template <bool SPLIT, bool PRE_LDS = false, bool REF_LOOP = false>
+// FILL (with PRE_LDS and REF_LOOP: k_search1_plr_b): blocks numbered across the workgroup, 51 of them in its 256 lanes instead of 4 x 12
+// (s1_fill_layout.h): the table is made by the whole workgroup behind one barrier, and the minimum over a block's lanes, three of which blocks lie in
+// two waves, goes through LDS (search1_block, LDS_MIN).  Every lane of the workgroup runs every MFMA and meets every barrier: nrefs is the workgroup's.
+static_assert(s1_fill_c_read_worst() == 4 && s1_fill_c_read_best() == 4, "the C reads of the filled loop form's pre table must be free of LDS bank conflicts: all four waves, every sub-block and quad");
+static_assert(s1_fill_c_read_worst(64) > 4, "the bank model sees the conflicts of unskewed slots");
+template <bool SPLIT, bool PRE_LDS = false, bool REF_LOOP = false, bool FILL = false>
 __device__ __forceinline__ void search1_body(const Search1Args &a) {
     using M = S1Map<SPLIT>;
+    static_assert(!FILL || (!SPLIT && PRE_LDS && REF_LOOP), "the filled map is the loop form's, with the table in LDS and the reference loop");
     if (!REF_LOOP && (int)blockIdx.y >= a.nrefs) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int grp = lane / M::LANES_PER_BLOCK, sub = lane - M::LANES_PER_BLOCK * grp;
-    const int b_raw = (xcd_band(blockIdx.x, gridDim.x) * 4 + wave) * M::BLOCKS_PER_WAVE + grp;
-    const bool live = grp < M::BLOCKS_PER_WAVE && b_raw < a.nblk;
+    const int grp = FILL ? s1_fill_slot_of((int)threadIdx.x) : lane / M::LANES_PER_BLOCK;
+    const int sub = FILL ? (int)threadIdx.x - S1_FILL_LANES * grp : lane - M::LANES_PER_BLOCK * grp;
+    // (FILL: the block of (workgroup, slot) as s1_fill_layout.h states it, < 0 where the slot has none -- lane 255 and the last workgroup's spare slots)
+    const int b_raw = FILL ? s1_fill_block_of(xcd_band(blockIdx.x, gridDim.x), grp, a.nblk) : (xcd_band(blockIdx.x, gridDim.x) * 4 + wave) * M::BLOCKS_PER_WAVE + grp;
+    const bool live = FILL ? b_raw >= 0 : grp < M::BLOCKS_PER_WAVE && b_raw < a.nblk;
     const int b = live ? b_raw : a.nblk - 1;
     const int by = a.bw == 1 ? b : (int)__umulhi((uint32_t)b, a.bw_inv), bx = b - by * a.bw;   // b / bw: bw_inv = ceil(2^32 / bw), exact for b * bw < 2^32
     const int cx = bx * 8, cy = by * 8;
@@ -432,7 +453,23 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
     const bool parent_written = (cx >> 4) < a.pbw && (cy >> 4) < a.pbh;
     const int *pre_lds = nullptr;
     int pre_off = 0;
-    if (!SPLIT && PRE_LDS) {
+    uint32_t *min_lds = nullptr;
+    if (FILL) {
+        // lane t = (block slot, sub-block) of the 204 tasks; the slots are read by other waves than made them: one barrier
+        __shared__ __attribute__((aligned(16))) int s_fill[S1_FILL_INTS];
+        __shared__ uint32_t s_min[2][S1_FILL_MIN_WORDS];
+        const int t = threadIdx.x, slot = s1_fill_task_slot(t), sb = s1_fill_task_sub(t);
+        const int tb_raw = xcd_band(blockIdx.x, gridDim.x) * S1_FILL_BLOCKS + slot;
+        const int tb = tb_raw < a.nblk ? tb_raw : a.nblk - 1;
+        const int tby = a.bw == 1 ? tb : (int)__umulhi((uint32_t)tb, a.bw_inv), tbx = tb - tby * a.bw;
+        s1_make_pre(a.cur, tbx * 8, tby * 8, sb, slot < S1_FILL_BLOCKS, s_fill + s1_fill_slot_at(slot) + s1_pre_sub_at(sb));
+        __syncthreads();
+        pre_lds = s_fill;
+        pre_off = s1_fill_c_at(t, 0, 0);
+        // (lane 255 has no block: never live, it searches the frame's last block with slot 50's C input, and of the five words of the minimum it
+        // reads, 256..259 are never written -- uninitialised on purpose, its result is never used)
+        min_lds = &s_min[0][s1_fill_min_at(t)];
+    } else if (!SPLIT && PRE_LDS) {
         // the current blocks' share of the metric, once per wave into LDS: lane = (block slot, sub-block).  The stages hand over inside the wave
         // (LDS executes a wave's operations in order): no barrier, the compiler is kept from moving the reads up
         __shared__ __attribute__((aligned(16))) int s_pre[4][S1_PRE_INTS];
@@ -450,7 +487,10 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
     for (int ri = 0; ri < nr; ++ri) {
         const int r = a.refmap[REF_LOOP ? ri : (int)blockIdx.y];
         const uint32_t pv = parent_written ? reinterpret_cast<const uint32_t *>(a.src[r])[parent] : 0u;
-        const uint32_t out = search1_block<SPLIT, !SPLIT && PRE_LDS>(a, r, cx, cy, pv, live, sub, lane, pre_lds, pre_off);
+        // (FILL: the minimum's words alternate between two buffers: a wave writes reference ri + 2's only behind the barrier of ri + 1, which every wave
+        // passes with its reads of ri done)
+        const uint32_t out = search1_block<SPLIT, !SPLIT && PRE_LDS, FILL>(a, r, cx, cy, pv, live, sub, lane, pre_lds, pre_off,
+                                                                            FILL ? min_lds + (ri & 1) * S1_FILL_MIN_WORDS : nullptr);
         if (sub == 0 && live) {
             const int cell = (cy >> 3) * a.net_width + (cx >> 3);
             reinterpret_cast<uint32_t *>(a.dst[r])[cell] = out;
@@ -601,7 +641,10 @@ __global__ __launch_bounds__(256) void k_search1_b(BatchOf<Search1Args> b) { sea
 // AGPRs and pays a v_accvgpr_read per value)
 __global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_search1_pl(Search1Args a) { search1_body<false, true>(a); }
 __global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_search1_pl_b(BatchOf<Search1Args> b) { search1_body<false, true>(b.item[blockIdx.z]); }
-__global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search1_plr_b(BatchOf<Search1Args> b) { search1_body<false, true, true>(b.item[blockIdx.z]); }
+__global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search1_plr_b(BatchOf<Search1Args> b) { search1_body<false, true, true, true>(b.item[blockIdx.z]); }
+// (the filled map pays where the part is full, the headline's regime.  Alone on the part -- a batch of one 1080p member, three references -- a launch is
+// as long as one wave and the barrier per reference costs more than the lanes save: 28.4 us a launch where the twelve-slot map took 27.3, -0.8 % of
+// that one-chunk rate; profiles/s1_fill_parent_vs_this.txt, section 4.  Not branched on: a launch cannot see what else runs on the part.)
 // VP8HIP_S1_REF_LOOP=0: a workgroup per reference in batches too (same-box A/B runs)
 static bool search1_ref_loop() {
     static const bool on = [] { const char *v = getenv("VP8HIP_S1_REF_LOOP"); return !(v && v[0] == '0'); }();
@@ -739,8 +782,8 @@ void launch_search1_batch(hipStream_t s, const CodingItem *items, int n, int lev
     if (nblk <= 0 || maxrefs == 0 || search1_skip()) return;
     if (search1_split((size_t)nblk * totrefs, false))
         VP8_LAUNCH(k_search1_b<true>, dim3((nblk + S1Map<true>::BLOCKS_PER_WG - 1) / S1Map<true>::BLOCKS_PER_WG, maxrefs, n), dim3(256), 0, s, b);
-    else if (search1_pre_lds() && search1_ref_loop())     // (70 registers, seven waves per SIMD; held to 64 it spills six and is no faster: 73.4-73.6 either way)
-        VP8_LAUNCH(k_search1_plr_b, dim3((nblk + S1Map<false>::BLOCKS_PER_WG - 1) / S1Map<false>::BLOCKS_PER_WG, 1, n), dim3(256), 0, s, b);
+    else if (search1_pre_lds() && search1_ref_loop())     // (68 registers, seven waves per SIMD.  Its twelve-slot predecessor, 70 registers, held to 64 spilled six and was no faster: 73.4-73.6 either way)
+        VP8_LAUNCH(k_search1_plr_b, dim3(s1_fill_grid(nblk), 1, n), dim3(256), 0, s, b);      // the filled map: 51 blocks per workgroup (s1_fill_layout.h)
     else if (search1_pre_lds())
         VP8_LAUNCH(k_search1_pl_b, dim3((nblk + S1Map<false>::BLOCKS_PER_WG - 1) / S1Map<false>::BLOCKS_PER_WG, maxrefs, n), dim3(256), 0, s, b);
     else
@@ -802,6 +845,35 @@ __global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) voi
 }
 void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out) {
     hipLaunchKernelGGL(k_weight_tap_mfma, dim3((n + 255) / 256), dim3(256), 0, s, d, n, out);
+}
+// ... and through the row-order operand of the whole-pel search's loop form (metric_a_rows): the same blocks, the prediction given as four ROW
+// dwords (byte c = column c), the current block's share as before
+__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_weight_tap_mfma_rows(const int32_t *d, int n, int32_t *out) {
+    const int i0 = blockIdx.x * 256 + threadIdx.x, i = i0 < n ? i0 : n - 1;
+    uint32_t cc[4] = {0, 0, 0, 0};
+    v4i pp = {0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        uint32_t pw = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int v = d[i * 16 + 4 * r + c];
+            const uint32_t cb = (uint32_t)(v > 0 ? v : 0) ^ 0x80u, pb = (uint32_t)(v > 0 ? 0 : -v) ^ 0x80u;
+            cc[c] |= cb << (8 * r);
+            pw |= pb << (8 * c);
+        }
+        pp[r] = (int)pw;
+    }
+    int pre[16];
+    weight_pre_block(cc, pre);
+    v16i c16;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) c16[k] = pre[k];
+    const int w = weight_mfma(metric_a_rows((int)threadIdx.x), c16, pp);
+    if (i0 < n) out[i0] = w;
+}
+void launch_weight_tap_mfma_rows(hipStream_t s, const int32_t *d, int n, int32_t *out) {
+    hipLaunchKernelGGL(k_weight_tap_mfma_rows, dim3((n + 255) / 256), dim3(256), 0, s, d, n, out);
 }
 
 }  // namespace vp8

@@ -272,6 +272,7 @@ void launch_search1(hipStream_t s, const CodingItem &it, int level, int src_idx,
 void launch_search2(hipStream_t s, const CodingItem &it, unsigned long long *clk = nullptr);
 void launch_weight_tap(hipStream_t s, const int32_t *d, int n, int32_t *out);
 void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out);
+void launch_weight_tap_mfma_rows(hipStream_t s, const int32_t *d, int n, int32_t *out);
 void launch_filter_mask(hipStream_t s, const MBOut &o, const SegData *d_sd, int mbs);
 // The loop filter exists in two forms with the same results.  Form 3 (lf_banded.h): byte tiles and strips in 46 KB
 // of LDS, the worker wave does everything itself -- what batches of GOP chunks launch, and only they (with the part full what counts is the
@@ -697,6 +698,23 @@ constexpr MetricTable make_metric_a() {
 static __device__ __constant__ const MetricTable K_METRIC_A = make_metric_a();
 // this lane's A operand: read once per wave, kept in four registers
 __device__ __forceinline__ v4i metric_a(int wave_lane) { return *reinterpret_cast<const v4i *>(K_METRIC_A.w[wave_lane & 63]); }
+// The order of k inside a half is free in an int8 product as long as A and B agree.  The same operand for a prediction that arrives as four ROW
+// dwords (byte c = column c): k = 16h + 4r + c, so byte c of dword r is the weight on row r of column c -- the per-lane 4x4 byte transpose of
+// K_METRIC_A.  The whole-pel search's loop form takes it: a candidate's B operand is then four bytes of each reference row as loaded, no transpose.
+// The C input (weight_pre_block) and everything behind the product do not depend on the order of k.
+constexpr MetricTable make_metric_a_rows() {
+    MetricTable t{};
+    for (int l = 0; l < 64; ++l) {
+        const int m = l & 31, h = l >> 5;
+        if (((m >> 2) & 1) != h) continue;
+        const int i = (m & 3) + 4 * (m >> 3);
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) t.w[l][r] |= ((metric_w(i, c) >> (8 * r)) & 255u) << (8 * c);
+    }
+    return t;
+}
+static __device__ __constant__ const MetricTable K_METRIC_A_ROWS = make_metric_a_rows();
+__device__ __forceinline__ v4i metric_a_rows(int wave_lane) { return *reinterpret_cast<const v4i *>(K_METRIC_A_ROWS.w[wave_lane & 63]); }
 
 // The current block's share of the 16 quantities (the C input of weight_mfma), from its four columns (cc[c] = the four rows of column c
 // as biased bytes), is two halves of the same shape: {s, m, c, d} of a row + one of X / Y for the four columns, with the weights k_r
