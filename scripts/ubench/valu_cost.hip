@@ -98,7 +98,9 @@
     X(80, "v_mad_u16", "v_mad_u16 %0, %0, %1, %0\n v_mad_u16 %2, %2, %3, %2\n v_mad_u16 %4, %4, %5, %4\n v_mad_u16 %6, %6, %7, %6") \
     X(81, "v_msad_u8", "v_msad_u8 %0, %0, %1, %0\n v_msad_u8 %2, %2, %3, %2\n v_msad_u8 %4, %4, %5, %4\n v_msad_u8 %6, %6, %7, %6") \
     X(82, "v_lerp_u8", "v_lerp_u8 %0, %0, %1, %0\n v_lerp_u8 %2, %2, %3, %2\n v_lerp_u8 %4, %4, %5, %4\n v_lerp_u8 %6, %6, %7, %6") \
-    X(83, "v_cvt_pk_u8_f32", "v_cvt_pk_u8_f32 %0, %0, %1, %0\n v_cvt_pk_u8_f32 %2, %2, %3, %2\n v_cvt_pk_u8_f32 %4, %4, %5, %4\n v_cvt_pk_u8_f32 %6, %6, %7, %6")
+    X(83, "v_cvt_pk_u8_f32", "v_cvt_pk_u8_f32 %0, %0, %1, %0\n v_cvt_pk_u8_f32 %2, %2, %3, %2\n v_cvt_pk_u8_f32 %4, %4, %5, %4\n v_cvt_pk_u8_f32 %6, %6, %7, %6") \
+    X(84, "v_ashr_pk_i8_i32", "v_ashr_pk_i8_i32 %0, %0, %1, 7\n v_ashr_pk_i8_i32 %2, %2, %3, 7\n v_ashr_pk_i8_i32 %4, %4, %5, 7\n v_ashr_pk_i8_i32 %6, %6, %7, 7") \
+    X(85, "v_ashr_pk_i8_i32 op_sel hi", "v_ashr_pk_i8_i32 %0, %0, %1, 7 op_sel:[0,0,0,1]\n v_ashr_pk_i8_i32 %2, %2, %3, 7 op_sel:[0,0,0,1]\n v_ashr_pk_i8_i32 %4, %4, %5, 7 op_sel:[0,0,0,1]\n v_ashr_pk_i8_i32 %6, %6, %7, 7 op_sel:[0,0,0,1]")
 
 constexpr int ITERS = 2000;   // long enough that the ramp of dispatching 8192 waves does not show
 
@@ -160,7 +162,7 @@ int main() {
     printf("{\n \"device\": \"%s\", \"cus\": %d, \"regime\": \"8 waves per SIMD on every CU, %d x 64 independent instructions per wave; simd_cycles = 1024 SIMDs x "
            "in-kernel clock x hipEvent wall / wave64 instructions; simd_cycles_in_wave = one wave's s_memtime ticks per instruction / 8\",\n \"ops\": {\n",
            p.gcnArchName, p.multiProcessorCount, ITERS);
-#define X(N, NAME, ASM) run<N>(NAME, N == 83);
+#define X(N, NAME, ASM) run<N>(NAME, N == 85);
     OPS(X)
 #undef X
     printf(" }\n}\n");

@@ -226,6 +226,61 @@ int vp8hip_debug_search1_batch(vp8hip_ctx *const *ctxs, int n, const int *use_go
     return VP8HIP_OK;
 }
 
+// test tap (not in the public header): n quadruples of int32 through the quarter-pel search's own round_pack4 (kernels_s2.hip): out[i] = the four
+// biased bytes sat_i8(v[4 i + j] >> 7), j = 0 in the lowest byte
+int vp8hip_debug_round_pack4(vp8hip_ctx *c, const int32_t *v, int n, uint32_t *out) {
+    USE_DEVICE(c);
+    JOIN_LF(c);
+    if (!c || !v || !out || n <= 0) return VP8HIP_ERR_ARG;
+    int32_t *dv = nullptr;
+    uint32_t *dout = nullptr;
+    HIPCHK(c, hipMalloc(&dv, (size_t)n * 16));
+    HIPCHK(c, hipMalloc(&dout, (size_t)n * 4));
+    HIPCHK(c, hipMemcpyAsync(dv, v, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    launch_round_pack4_tap(c->stream, dv, n, dout);
+    HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(dv);
+    hipFree(dout);
+    return VP8HIP_OK;
+}
+
+// test tap (not in the public header): the batched quarter-pel search (launch_search2_batch, in the form the switches pick) over caller-written
+// whole-pel nets.  The members' current frames and references must stand and every stream be idle (as for vp8hip_debug_search1_batch).  src[3 i + r]:
+// member i's whole-pel net of reference r (b8 x short2) going in; dst[3 i + r] / bdiff[3 i + r]: its quarter-pel net and costs coming out; null where
+// the reference is not enabled.  No parameter scan rides along.
+int vp8hip_debug_search2_batch(vp8hip_ctx *const *ctxs, int n, const int *use_golden, const int *use_altref, const int16_t *const *src,
+                               int16_t *const *dst, int32_t *const *bdiff) {
+    if (!ctxs || n <= 0 || n > MAX_BATCH || !use_golden || !use_altref || !src || !dst || !bdiff) return VP8HIP_ERR_ARG;
+    vp8hip_ctx *c0 = ctxs[0];
+    USE_DEVICE(c0);
+    CodingItem it[MAX_BATCH];
+    for (int i = 0; i < n; ++i) {
+        vp8hip_ctx *c = ctxs[i];
+        if (!c || c->b8 != c0->b8 || c->mbw != c0->mbw) return VP8HIP_ERR_ARG;
+        JOIN_LF(c);
+        it[i] = coding_item(c, use_golden[i], use_altref[i]);
+        it[i].scan = nullptr;
+        for (int r = 0; r < 3; ++r) {
+            if (!it[i].refs.use[r]) continue;
+            if (!src[3 * i + r] || !dst[3 * i + r] || !bdiff[3 * i + r]) return VP8HIP_ERR_ARG;
+            HIPCHK(c0, hipMemcpyAsync(c->nets.net[r][1], src[3 * i + r], (size_t)c->b8 * 4, hipMemcpyHostToDevice, c0->stream));
+            HIPCHK(c0, hipMemsetAsync(c->nets.net[r][0], 0x55, (size_t)c->b8 * 4, c0->stream));
+            HIPCHK(c0, hipMemsetAsync(c->nets.bdiff[r], 0x55, (size_t)c->b8 * 4, c0->stream));
+        }
+    }
+    launch_search2_batch(c0->stream, it, n);
+    for (int i = 0; i < n; ++i)
+        for (int r = 0; r < 3; ++r) {
+            if (!it[i].refs.use[r]) continue;
+            HIPCHK(c0, hipMemcpyAsync(dst[3 * i + r], ctxs[i]->nets.net[r][0], (size_t)ctxs[i]->b8 * 4, hipMemcpyDeviceToHost, c0->stream));
+            HIPCHK(c0, hipMemcpyAsync(bdiff[3 * i + r], ctxs[i]->nets.bdiff[r], (size_t)ctxs[i]->b8 * 4, hipMemcpyDeviceToHost, c0->stream));
+        }
+    HIPCHK(c0, hipStreamSynchronize(c0->stream));
+    HIPCHK(c0, hipGetLastError());
+    return VP8HIP_OK;
+}
+
 // test tap (not in the public header, no device needed): the metric's two A operands as the kernels hold them, 64 lanes x 4 dwords each --
 // column order (K_METRIC_A) and row order (K_METRIC_A_ROWS)
 int vp8hip_debug_metric_tables(uint32_t *a_cols, uint32_t *a_rows) {

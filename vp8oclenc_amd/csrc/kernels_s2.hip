@@ -20,14 +20,15 @@
 //   * Then lane k = candidate (dx, dy) of the 25 (+ the zero-vector candidate): the block-match metric on four 4x4 blocks, the
 //     current block's share of its column pass made once per block into LDS (weight_pre_block) and the column pass of 64 (candidate,
 //     4x4 block) tasks of a wave as ONE more MFMA, the current block's share its C input (weight_mfma, vp8hip_dev.h); the minimum over
-//     the 32 lanes by four DPP steps + row_bcast, over a key whose low byte holds the candidate's offsets as (dy + 2) * 8 + (dx + 2): the
-//     one lane that writes the block's result reads the winner's vector out of it.
+//     the 32 lanes by four DPP steps + one ds_swizzle, in every lane, over a key whose low byte holds the candidate's number as
+//     (dy + 2) * 8 + (dx + 2): keys are unique in a block, and the lane whose own key is the minimum writes the block's result from what it holds.
 // The operand and result lane maps of the MFMA are pinned by scripts/ubench/mfma_i8_layout.hip, the results by the whole parity
 // suite.  History per 1080p frame and reference: 32-bit multiply-adds 0.156 ms; both passes on v_dot4_i32_i8 0.091 (892 vector
 // instructions per wave; git history, ae32ece^); with the metric's column pass on the matrix cores 522 vector instructions per wave, group of
 // eight blocks and reference; with the reference loop 475 per reference + 53 per group = 493 at three references
 // (tests/test_search2_instruction_budget.py); with the row butterfly of rows 0 and 2 of the metric folded into its MFMA 443 per reference + 70 per
-// group = 466 (tests/test_metric_instruction_budget.py).
+// group = 466 (tests/test_metric_instruction_budget.py); with the filter bytes packed without permutes (round_pack4) and the result written by the
+// winning lane 411 per reference (392 issued: the rest is a branch waves skip) + 69 per group = 434 (tests/test_search2_pack_tail_budget.py).
 #include <stdlib.h>
 #include <string.h>
 
@@ -104,8 +105,9 @@ struct S2Args {
     unsigned long long *clk;   // launch clock (launch_clock_end, vp8hip_dev.h) or nullptr; a batched launch uses its first member's
 };
 
-// minimum over the 32 lanes of a block, valid in its lanes 16..31: four DPP steps inside the 16-lane rows (the lanes a step
-// pairs hold, after it, the same value: mirrors do as well as butterflies), then lane 15 of the lower row into the upper one.
+// minimum over the 32 lanes of a block, in every one of them: four DPP steps inside the 16-lane rows (the lanes a step pairs hold, after
+// it, the same value: mirrors do as well as butterflies), then the two rows of the block trade their minima through ds_swizzle_b32 (lane ^ 16
+// inside each group of 32: the LDS crossbar, no memory and no vector instruction -- DPP has no step that reaches the LOWER row).
 // (__shfl_xor is a ds_bpermute_b32 with five instructions of address arithmetic around it, per step.)
 __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 template <int CTRL, int ROW_MASK = 0xf>
@@ -118,12 +120,12 @@ template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ uint32_t dpp_or_max(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROW_MASK, 0xf, false);
 }
-__device__ __forceinline__ uint32_t halfwave_min_upper(uint32_t key) {
+__device__ __forceinline__ uint32_t block_min(uint32_t key) {
     key = umin(key, dpp_or_max<0xb1>(key));         // quad_perm [1,0,3,2]
     key = umin(key, dpp_or_max<0x4e>(key));         // quad_perm [2,3,0,1]
     key = umin(key, dpp_or_max<0x141>(key));        // row_half_mirror
     key = umin(key, dpp_or_max<0x140>(key));        // row_mirror
-    return umin(key, dpp_or_max<0x142, 0xa>(key));  // row_bcast:15 into rows 1 and 3
+    return umin(key, (uint32_t)__builtin_amdgcn_ds_swizzle((int)key, 0x401f));   // bit mode: and 0x1f, or 0, xor 0x10
 }
 
 // sat_i8(a >> 7) in byte 0, sat_i8(b >> 7) in byte 1 (v_ashr_pk_i8_i32; as a 16-bit value the undefined bits 31:16 stay explicit).
@@ -131,14 +133,19 @@ __device__ __forceinline__ uint32_t halfwave_min_upper(uint32_t key) {
 //     sat_i8((sum(p f) - 16384 + 64) >> 7) = sat_u8((sum(p f) + 64) >> 7) - 128:
 // the signed saturation of the biased sum IS the biased byte of the reference's clamped sample; the rounding 64 rides in the product (mfma_round).
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+typedef short ss2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned short ashr7_pk_i8(int a, int b) { return __builtin_amdgcn_ashr_pk_i8_i32(a, b, 7); }
-__device__ __forceinline__ uint32_t pack4(unsigned short lo, unsigned short hi) {
-    const us2 v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
-// four consecutive results of one lane (rows 4q .. 4q + 3 of its column) as four biased bytes
+// four consecutive results of one lane (rows 4q .. 4q + 3 of its column) as four biased bytes: row 4q in byte 0 .. row 4q + 3 in byte 3.
+// The second v_ashr_pk_i8_i32 writes the UPPER half of the first one's register (its destination-half select, op_sel[3]; bits 15:0 stay): no
+// v_perm_b32 to join two halves.  The lower half's upper bits are left undefined to the compiler (a zero-extension would cost a v_and_b32).
+// Order, for the hazards: the lower half comes from the builtin and the inline instruction is tied to its result ("+v"), so that the compiler's own
+// MFMA-to-VALU wait stands in front of the builtin and the inline instruction reads its registers of the same MFMA result strictly later.  An
+// MFMA result must never be read FIRST from inline assembly: the compiler's hazard pass does not look into it.
 __device__ __forceinline__ uint32_t round_pack4(const v16i &acc, int q) {
-    return pack4(ashr7_pk_i8(acc[4 * q], acc[4 * q + 1]), ashr7_pk_i8(acc[4 * q + 2], acc[4 * q + 3]));
+    const us2 lo = __builtin_shufflevector(us2{ashr7_pk_i8(acc[4 * q], acc[4 * q + 1]), 0}, us2{0, 0}, 0, -1);
+    uint32_t r = __builtin_bit_cast(uint32_t, lo);
+    asm("v_ashr_pk_i8_i32 %0, %1, %2, 7 op_sel:[0,0,0,1]" : "+v"(r) : "v"(acc[4 * q + 2]), "v"(acc[4 * q + 3]));
+    return r;
 }
 // The rounding 64 of a pass rides in the product: k = 31 of the tap operand is 64 (make_bh, make_av; no tap reaches that far) and k = 31 of
 // the data operand is made 1 here -- byte 15 of the lanes of the upper k half, which otherwise meets a zero tap.  (As the C input the
@@ -212,10 +219,11 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
     const int dx = k % 5 - 2, dy = k / 5 - 2;
     // (with the candidate's vector-cost penalty, :1176-1178, above it: cost and number go into the key with one shift-and-add)
     const uint32_t kcode = k < 25 ? (uint32_t)((iabs(dx) + iabs(dy)) * 32 * 256 + (dy + 2) * 8 + dx + 2) : 40u;
+    const us2 dxy = {(unsigned short)dx, (unsigned short)dy};     // its offsets as a 16-bit pair
     const v4i wa = metric_a(wl);        // the metric's column pass on the matrix cores (weight_mfma, vp8hip_dev.h): every lane of the wave is here
 
     // ---- everything below is per reference ------------------------------------------------------------------------------
-    // From the part above it uses: b, live, cx, cy (the block), k, dx, dy, kcode, wa (the lane's candidate) and the pre table.
+    // From the part above it uses: b, live, cx, cy (the block), k, dxy, kcode, wa (the lane's candidate) and the pre table.
     // Its LDS reuse rests on one rule -- LDS executes a wave's operations in program order, and every array slot is written only by the
     // wave whose lanes own it (the one wave of the fourth-block round only reads other slots, between the two barriers):
     //   * the window lives in the first 512 bytes of the block's V slot; candidate 25 of 4x4 block 0 (bytes 400..415) lies inside them, so
@@ -229,8 +237,11 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         const int g_n = tr >> 5, lane_n = tr & 31, wl_n = tr & 63, kh_n = wl_n >> 5, gp_n = g_n & ~1;
         const int r = a.refmap[ri];
         const uint32_t nv = reinterpret_cast<const uint32_t *>(a.net_in[r])[b];
-        const int nx = (int16_t)(nv & 0xffffu), ny = (int16_t)(nv >> 16);
-        const int v0x = (int16_t)(nx * 4), v0y = (int16_t)(ny * 4);
+        const us2 v0 = __builtin_bit_cast(us2, nv) * (unsigned short)4;      // the whole-pel vector in quarter pels, (int16)(n * 4) per half
+        // (the vector the window is placed by is the one the candidates are placed by, (int16)(4 n) / 4: n itself for every vector a search hands
+        // down, and for a written net whose 4 n passes int16 the place the reference's wrap lands on)
+        const ss2 nw = __builtin_bit_cast(ss2, v0) >> 2;
+        const int nx = nw.x, ny = nw.y;
         // window origin; a garbage vector (possible only when every candidate is out of frame) is clamped
         // so that the loads stay inside the allocated margin
         const int Lx = iclamp(cx + nx, 3 - EXT, a.w + EXT - 11), Ly = iclamp(cy + ny, 3 - EXT, a.h + EXT - 11);
@@ -306,8 +317,11 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         lds_fence();
 
         // ---- cost: lane = candidate --------------------------------------------------------------------
-        int qx = (int16_t)(cx * 4 + v0x + dx), qy = (int16_t)(cy * 4 + v0y + dy);
-        if (k == 25) { qx = cx * 4; qy = cy * 4; }
+        // The candidate's vector as a 16-bit pair, (int16)(v0x + dx) per half ((0, 0) for the zero candidate), and its position, the block's own
+        // added to it.  (int16)(4 cx + v0x + dx), as :1143 has it, differs from this sum only where it passes 32767: negative there, past the
+        // frame's last position here -- out of the frame either way (a frame is narrower than 8192 pixels: 4 w - 32 fits an int16).
+        const uint32_t vq = k == 25 ? 0u : __builtin_bit_cast(uint32_t, (us2)(v0 + dxy));
+        const int qx = cx * 4 + (int16_t)(vq & 0xffffu), qy = cy * 4 + ((int)vq >> 16);
         const bool valid = live && k < 26 && qx >= 0 && qx <= a.w * 4 - 32 && qy >= 0 && qy <= a.h * 4 - 32;
         int diff = 0;
         // a task = 16 bytes of the V array (the B operand: one ds_read_b128) and 16 ints of the pre table (the C input)
@@ -342,21 +356,35 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
             for (int bb = 0; bb < 4; ++bb) diff += metric(src + bb * V_ROW, &s_pre[g][bb * 16]);
         }
         uint32_t key = ((uint32_t)diff << 8) + kcode;     // (diff + penalty) << 8 | number
-        key = (valid && key < (0x7fffu << 8)) ? key : 0xffffffffu;
-        key = halfwave_min_upper(key);
-        if (lane == 16 && live) {   // (every lane of the block holds the block's position and vector; this one also the minimum)
-            // :1136-1137: with no candidate in the frame the result is the frame's last position; otherwise the winner's, as a vector: the
-            // block's own position drops out of (int16)((int16)(4 cx + v0x + dx) - 4 cx) = (int16)(v0x + dx)
-            int vx = (int16_t)((int16_t)(a.w * 4 - 32) - cx * 4), vy = (int16_t)((int16_t)(a.h * 4 - 32) - cy * 4), md = 0x7fff;
-            if (key != 0xffffffffu) {
-                const int kk = key & 0xff;
-                md = (int)(key >> 8);
-                vx = kk == 40 ? 0 : (int16_t)(v0x + (kk & 7) - 2);
-                vy = kk == 40 ? 0 : (int16_t)(v0y + (kk >> 3) - 2);
-            }
+        const bool ok = valid && key < (0x7fffu << 8);
+        key = ok ? key : 0xffffffffu;
+        const uint32_t kmin = block_min(key);
+        // (results by base + 32-bit byte offset, made where it is used: a uniform base and a lane's unsigned offset are one store each, no 64-bit
+        // address per lane -- and none kept across the loop)
+        auto result_write = [&](uint32_t v, int md) {
+            uint32_t bo = (uint32_t)b;
+            asm("" : "+v"(bo));
+            const uint32_t off = bo * 4u;
+            *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(a.net_out[r]) + off) = v;
+            *reinterpret_cast<int *>(reinterpret_cast<char *>(a.bdiff[r]) + off) = md;
+        };
+        // The winning lane writes: keys are unique in a block (the candidate's number is the low byte), so exactly one lane holds the minimum, and
+        // it holds all the result is made of.  A candidate in the frame has not wrapped: its vector is (v0x + dx, v0y + dy) as 16-bit sums -- one
+        // packed add -- or (0, 0) for the zero candidate; its penalty, (|dx| + |dy|) * 32, sits in the key and not in `diff`, and :1195-1197 take it
+        // back unless the vector is (0, 0): diff for a vector that is not, key >> 8 -- what the reference keeps -- for one that is (the zero candidate,
+        // or the zero offset on a zero vector: v0 is a multiple of 4, so no other offset leads there, and both carry a penalty of 0).
+        if (ok && key == kmin) {
+            result_write(vq, vq != 0 ? diff : (int)(key >> 8));
+        }
+        // :1136-1137: with no candidate accepted the result is the frame's last position, as a vector: (int16)((int16)(4 w - 32) - 4 cx), cost 0x7fff
+        // less the penalty of THAT vector.  Kept as the reference has it, behind a branch that waves skip: the zero candidate is in the frame for every
+        // block and costs less than 0x7fff whatever the pixels (tests/test_gpu_search2_pack_tail.py, test_no_block_can_cost_0x7fff), so nothing gets here.
+        if (kmin == 0xffffffffu && lane == 16 && live) {
+            const int vx = (int16_t)((int16_t)(a.w * 4 - 32) - cx * 4), vy = (int16_t)((int16_t)(a.h * 4 - 32) - cy * 4);
+            const int v0x = (int16_t)v0.x, v0y = (int16_t)v0.y;
+            int md = 0x7fff;
             if ((vx != 0) | (vy != 0)) md -= (iabs(vx - v0x) + iabs(vy - v0y)) * 32;  // :1195-1197
-            reinterpret_cast<uint32_t *>(a.net_out[r])[b] = (uint32_t)(uint16_t)vx | ((uint32_t)(uint16_t)vy << 16);
-            a.bdiff[r][b] = md;
+            result_write((uint32_t)(uint16_t)vx | ((uint32_t)(uint16_t)vy << 16), md);
         }
     };
     if (ALLREFS) {
@@ -385,17 +413,19 @@ __device__ __forceinline__ void search2_groups(const S2Args &a, int grp, int ref
 // either way.  The MFMAs' results still land in VGPRs, no v_accvgpr_read per result: tests/test_kernel_resources.py pins zero AGPRs.)
 template <bool SPREAD, int ITER>
 __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2(S2Args a) {
+    const unsigned long long first = launch_clock_first_thread();
     launch_clock_begin(a.clk);
     search2_groups<SPREAD, ITER, false>(a, xcd_band(blockIdx.x, gridDim.x), blockIdx.y);
-    launch_clock_end(a.clk);
+    launch_clock_end(a.clk, first);
 }
 static_assert(sizeof(BatchOf<S2Args>) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
 // The batched forms: grid (groups, 1, contexts), every enabled reference of the context inside the workgroup (ALLREFS)
 template <bool SPREAD, int ITER>
 __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2_b(BatchOf<S2Args> b) {
+    const unsigned long long first = launch_clock_first_thread();
     launch_clock_begin(b.item[0].clk);
     search2_groups<SPREAD, ITER, true>(b.item[blockIdx.z], xcd_band(blockIdx.x, gridDim.x), 0);
-    launch_clock_end(b.item[0].clk);
+    launch_clock_end(b.item[0].clk, first);
 }
 // The same launch carrying the loop-filter strength scans of its members' NEW frames (kernels_rc_dev.h): the workgroups behind the
 // nbx block groups.  With the part full a launch of the scan's own holds the batch's stream for 0.4-0.7 ms where its
@@ -413,9 +443,10 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) voi
         if (((sc.mask >> blockIdx.z) & 1) && wg < sc.wgs) rc::strength_segments_body(b.item[blockIdx.z].cur, sc.item[blockIdx.z], wg, sc.wgs);
         return;
     }
+    const unsigned long long first = launch_clock_first_thread();
     launch_clock_begin(b.item[0].clk);
     search2_groups<SPREAD, ITER, true>(b.item[blockIdx.z], xcd_band(blockIdx.x, sc.nbx), 0);
-    launch_clock_end(b.item[0].clk);
+    launch_clock_end(b.item[0].clk, first);
 }
 // Persistent form: a grid no larger than what the part holds at once, every workgroup walking the (context, reference,
 // block group) space with a stride.  A command-processor pipe stays busy with a launch until its last workgroup is
@@ -431,7 +462,25 @@ __global__ __launch_bounds__(256, 4) void k_search2_p(BatchOf<S2Args> b, int nbx
     }
 }
 
+// test tap: round_pack4 over caller-supplied values, a lane four quadruples (its "sixteen results" of an MFMA: q = 0..3 as the passes call it)
+__global__ __launch_bounds__(256) void k_round_pack4_tap(const int32_t *v, int n, uint32_t *out) {
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (4 * t + (j >> 2) < n) acc[j] = v[16 * t + j];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t r = round_pack4(acc, q);
+        if (4 * t + q < n) out[4 * t + q] = r;
+    }
+}
+
 }  // namespace
+
+void launch_round_pack4_tap(hipStream_t s, const int32_t *v, int n, uint32_t *out) {
+    VP8_LAUNCH(k_round_pack4_tap, dim3((n + 1023) / 1024), dim3(256), 0, s, v, n, out);
+}
 
 static S2Args search2_args(const CodingItem &it, unsigned long long *clk) {
     const Frame &cur = *it.cur;

@@ -110,10 +110,17 @@ __device__ __forceinline__ void launch_clock_begin(unsigned long long *w) {
     if (w && launch_clock_sampled() && __builtin_amdgcn_readfirstlane((int)threadIdx.x) == 0)
         atomicMin(&w[0], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
-__device__ __forceinline__ void launch_clock_end(unsigned long long *w) {   // every thread of the workgroup gets here
+// The lanes of the workgroup's first thread as a wave mask (1 in the first wave, 0 in the others), taken at the kernel's start and held in
+// scalar registers: launch_clock_end then asks for no thread number behind the kernel's body, i.e. no vector register kept across it.
+__device__ __forceinline__ unsigned long long launch_clock_first_thread() {
+    unsigned long long m = __builtin_amdgcn_ballot_w64(threadIdx.x == 0);
+    asm volatile("" : "+s"(m));      // (made here, not where it is used)
+    return m;
+}
+__device__ __forceinline__ void launch_clock_end(unsigned long long *w, unsigned long long first_thread) {   // every thread of the workgroup gets here
     if (!w || !launch_clock_sampled()) return;
     __syncthreads();
-    if (threadIdx.x != 0) return;
+    if (first_thread == 0 || __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) != 0) return;      // the mask's one bit is lane 0's
     atomicMax(&w[1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
     __threadfence();
     const unsigned total = gridDim.x * gridDim.y * gridDim.z, sampled = (total + CLOCK_SAMPLE - 1) / CLOCK_SAMPLE;
@@ -273,6 +280,7 @@ void launch_search2(hipStream_t s, const CodingItem &it, unsigned long long *clk
 void launch_weight_tap(hipStream_t s, const int32_t *d, int n, int32_t *out);
 void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out);
 void launch_weight_tap_mfma_rows(hipStream_t s, const int32_t *d, int n, int32_t *out);
+void launch_round_pack4_tap(hipStream_t s, const int32_t *v, int n, uint32_t *out);   // kernels_s2.hip: n quadruples through round_pack4
 void launch_filter_mask(hipStream_t s, const MBOut &o, const SegData *d_sd, int mbs);
 // The loop filter exists in two forms with the same results.  Form 3 (lf_banded.h): byte tiles and strips in 46 KB
 // of LDS, the worker wave does everything itself -- what batches of GOP chunks launch, and only they (with the part full what counts is the
