@@ -18,27 +18,28 @@ namespace vp8 {
 // (quantiser tables k_dc_q / k_ac_q and qi(): vp8hip_dev.h)
 
 // C division x / q (truncating toward zero, GPU_kernels.cl:1478-1481) by a quantiser that is the same for a
-// whole pass: floor(n/q) = (n*M) >> 24 with M = floor(2^24/q) + 1 is exact for n < 2^15 and 2 <= q < 512
+// whole pass: floor(n/q) = (n*M) >> 24 with M = floor(2^24/q) + 1 is exact for 0 <= n < 2^15 and 2 <= q < 512
 // (error term n*(M*q - 2^24)/(q*2^24) < 2^-9 < 1/q).  Every |coefficient| here is below 2^15 (fdct <= 2040,
-// WHT <= 16320) and every quantiser below 512 (y2ac <= 440).  (n*M) >> 24 = the HIGH half of n * (M << 8): one
-// v_mul_hi_u32 (M < 2^23 for q >= 2, so M << 8 fits; the 64-bit product by two 24-bit multiplies and a funnel shift was
-// seven instructions per coefficient).  q == 1 (the DC of a 16x16 macroblock) is passed through.  M << 8 comes from a
-// table: the quantisers are table entries and small functions of them, all below 512.
-struct TDiv { uint32_t M8; bool one; };
+// WHT <= 16320) and every quantiser below 512 (y2ac <= 440).  (n*M) >> 24 = the HIGH half of n * (M << 8).
+// On the SIGNED numerator: v_mul_hi_i32 gives floor(x*M/2^24), which for x < 0 is -(floor(|x|/q) + 1) as long as |x|*M is
+// no multiple of 2^24, and subtracting the sign (x >> 31 = -1) takes the 1 off again: x/q = mul_hi(x, M << 8) - (x >> 31),
+// three instructions (|x| through v_mul_hi_u32 and its sign put back were six).  It needs M << 8 as a POSITIVE int32:
+// true for q >= 3 (q = 2 has M << 8 = 2^31 + 256, and no multiplier at all serves x = 1 and x = 2 there).  The quantisers
+// are table entries and small functions of them: 1, or 4 .. 440 (tests/test_quantiser_division_signed_cpu.py scans them).
+// Quantiser 1 is the luma DC of an unsplit macroblock and nothing else; mb_dc_div passes that one coefficient through.
+// M << 8 comes from a table.
 struct Recip24 { uint32_t m8[512]; };
 static constexpr Recip24 make_recip24() {
     Recip24 t{};
-    for (uint32_t q = 0; q < 512; ++q) t.m8[q] = q < 2 ? 0u : (((1u << 24) / q + 1u) << 8);
+    for (uint32_t q = 0; q < 512; ++q) t.m8[q] = q < 3 ? 0u : (((1u << 24) / q + 1u) << 8);
     return t;
 }
 static __device__ __constant__ const Recip24 k_recip24 = make_recip24();
-__device__ __forceinline__ TDiv tdiv_make(int q) { return TDiv{k_recip24.m8[q & 511], q == 1}; }
-__device__ __forceinline__ int tdiv(int x, const TDiv &d) {
-    const int s = x >> 31;
-    const uint32_t n = (uint32_t)((x ^ s) - s);
-    const uint32_t r = d.one ? n : __umulhi(n, d.M8);
-    return ((int)r ^ s) - s;
-}
+typedef int TDiv;   // M << 8 of the quantiser
+__device__ __forceinline__ TDiv tdiv_make(int q) { return (int)k_recip24.m8[q & 511]; }
+__device__ __forceinline__ int tdiv(int x, TDiv m8) { return __mulhi(x, m8) - (x >> 31); }
+// the DC of a block: its quantiser may be 1
+__device__ __forceinline__ int mb_dc_div(int x, int q) { return q == 1 ? x : tdiv(x, tdiv_make(q)); }
 
 // `construct`, GPU_kernels.cl:574-774: separable six-tap on a 4x4 block at integer position (ix,iy)
 // with 1/8-pel phases (fx,fy).  Of the nine horizontally filtered lines the first six are saturated
@@ -61,17 +62,31 @@ static __device__ __constant__ const uint32_t K_P6[8][12] = {   // 1/8-pel phase
     P6(0, 0, 0, 0, 0, 0),       P6(0, -6, 123, 12, -1, 0), P6(2, -11, 108, 36, -8, 1), P6(0, -9, 93, 50, -6, 0),
     P6(3, -16, 77, 77, -16, 3), P6(0, -6, 50, 93, -9, 0),  P6(1, -8, 36, 108, -11, 2), P6(0, -1, 12, 123, -6, 0)};
 constexpr int KB6 = 128 * 128 + 64;   // undo the -128 pixel bias + rounding
+constexpr int KR6 = 64;               // rounding alone: the sum stays biased (pack_sat4)
 __device__ __forceinline__ int d4k(uint32_t a, uint32_t b, int c) { return __builtin_amdgcn_sdot4((int)a, (int)b, c, true); }
 __device__ __forceinline__ int d4(uint32_t a, uint32_t b, int c) { return __builtin_amdgcn_sdot4((int)a, (int)b, c, false); }
-// four 6-tap sums of a 12-byte line (three dwords of biased bytes), outputs c = 0..3 start at byte c
-__device__ __forceinline__ void six_tap4(uint32_t w0, uint32_t w1, uint32_t w2, const uint32_t t[9], int s[4]) {
-    s[0] = d4(w1, t[1], d4k(w0, t[0], KB6));
-    s[1] = d4(w1, t[3], d4k(w0, t[2], KB6));
-    s[2] = d4(w1, t[5], d4k(w0, t[4], KB6));
-    s[3] = d4(w2, t[8], d4(w1, t[7], d4k(w0, t[6], KB6)));
+// four 6-tap sums of a 12-byte line (three dwords of biased bytes), outputs c = 0..3 start at byte c; k0: KB6 or KR6
+__device__ __forceinline__ void six_tap4(uint32_t w0, uint32_t w1, uint32_t w2, const uint32_t t[9], int s[4], int k0) {
+    s[0] = d4(w1, t[1], d4k(w0, t[0], k0));
+    s[1] = d4(w1, t[3], d4k(w0, t[2], k0));
+    s[2] = d4(w1, t[5], d4k(w0, t[4], k0));
+    s[3] = d4(w2, t[8], d4(w1, t[7], d4k(w0, t[6], k0)));
 }
-__device__ __forceinline__ uint32_t pack_sat4(const int s[4]) {   // sat8(s >> 7) of four sums, byte c = sum c
-    const uint32_t lo = __builtin_amdgcn_ashr_pk_u8_i32(s[0], s[1], 7), hi = __builtin_amdgcn_ashr_pk_u8_i32(s[2], s[3], 7);
+// sat8(sum >> 7) of four sums as BIASED bytes (p - 128), byte c = sum c, from the sums made with KR6: the signed saturation of the
+// biased sum is the biased byte of the clamped sample, sat_i8((S + 64) >> 7) = sat_u8((S + 16384 + 64) >> 7) - 128 (16384 = 128 * 128; the
+// quarter-pel search packs its filter bytes the same way, kernels_s2.hip).  The upper halves of the two v_ashr_pk_i8_i32 results are left
+// undefined to the compiler: the permute takes the lower ones, and a zero-extension would cost a v_and_b32 each.
+typedef unsigned short mb_us2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t low_half(unsigned short v) {
+    return __builtin_bit_cast(uint32_t, __builtin_shufflevector(mb_us2{v, 0}, mb_us2{0, 0}, 0, -1));
+}
+__device__ __forceinline__ uint32_t pack_sat4(const int s[4]) {
+    const uint32_t lo = low_half(__builtin_amdgcn_ashr_pk_i8_i32(s[0], s[1], 7)), hi = low_half(__builtin_amdgcn_ashr_pk_i8_i32(s[2], s[3], 7));
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+// sat8 of four values, byte c = value c: v_ashr_pk_u8_i32 by zero saturates a pair (a v_med3_i32 each and the shifts and ors that pack them before)
+__device__ __forceinline__ uint32_t pack_satu4(const int s[4]) {
+    const uint32_t lo = low_half(__builtin_amdgcn_ashr_pk_u8_i32(s[0], s[1], 0)), hi = low_half(__builtin_amdgcn_ashr_pk_u8_i32(s[2], s[3], 0));
     return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 // rows out[r] (byte c = column c) of the 4x4 predictor.  CONFORMANT (vp8hip_conformant_stream, NOT the reference): all nine
@@ -82,21 +97,23 @@ __device__ __forceinline__ void predict4x4(const Plane &rf, int ix, int iy, int 
 #pragma unroll
     for (int i = 0; i < 9; ++i) { tx[i] = K_P6[fx][i]; ty[i] = K_P6[fy][i]; }
     uint32_t Hb[9];   // horizontally filtered lines, four biased bytes each
+    const uint8_t *line = rf.p + (ptrdiff_t)(iy - 2) * rf.stride + (ix - 2);   // (one 64-bit multiply; the lines below it are additions)
 #pragma unroll
     for (int L = 0; L < 9; ++L) {
-        const uint8_t *p = rf.p + (ptrdiff_t)(iy - 2 + L) * rf.stride + (ix - 2);
+        const uint8_t *p = line + (ptrdiff_t)L * rf.stride;
         const uint32_t w0 = ld_u32(p) ^ 0x80808080u, w1 = ld_u32(p + 4) ^ 0x80808080u, w2 = ld_u32(p + 8) ^ 0x80808080u;
         int sm[4];
-        six_tap4(w0, w1, w2, tx, sm);
         uint32_t h;
         if (L < 6 || CONFORMANT) {
+            six_tap4(w0, w1, w2, tx, sm, KR6);
             h = pack_sat4(sm);                    // saturated lines, :600-680
         } else {                                  // the last three: C division toward zero, then a plain (uchar) cast, :702-758
+            six_tap4(w0, w1, w2, tx, sm, KB6);
             h = 0;
 #pragma unroll
             for (int c = 0; c < 4; ++c) h |= (uint32_t)(div128(sm[c]) & 0xff) << (8 * c);
+            h ^= 0x80808080u;
         }
-        h ^= 0x80808080u;
         Hb[L] = fx == 0 ? __builtin_amdgcn_alignbyte(w1, w0, 2) : h;   // whole-pel x: bytes 2..5 of the line as they are
     }
     uint32_t ca[4], cb[4], oc[4];   // columns: rows 0-3, rows 4-7 (row 8 comes from Hb[8])
@@ -105,36 +122,54 @@ __device__ __forceinline__ void predict4x4(const Plane &rf, int ix, int iy, int 
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         int sm[4];
-        six_tap4(ca[c], cb[c], Hb[8] >> (8 * c), ty, sm);   // only byte 0 of the third dword meets a non-zero tap
+        six_tap4(ca[c], cb[c], Hb[8] >> (8 * c), ty, sm, KR6);   // only byte 0 of the third dword meets a non-zero tap
         const uint32_t v = pack_sat4(sm);
-        oc[c] = fy == 0 ? (__builtin_amdgcn_alignbyte(cb[c], ca[c], 2) ^ 0x80808080u) : v;   // whole-pel y: rows 2..5 of the column
+        oc[c] = fy == 0 ? __builtin_amdgcn_alignbyte(cb[c], ca[c], 2) : v;   // whole-pel y: rows 2..5 of the column (biased, as v is)
     }
     transpose4x4(oc, out);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[r] ^= 0x80808080u;
 }
 
-// dct4x4, GPU_kernels.cl:1417-1476: libvpx fdct constants, vertical pass first
+// dct4x4, GPU_kernels.cl:1417-1476: libvpx fdct constants, vertical pass first.
+// The reference scales the vertical pass's butterfly by 8.  No shift is issued for it here:
+//   * its rotations (c1*2217 + d1*5352 + 14500) >> 12 on c1 = 8c, d1 = 8d are (c*8868 + d*21408 + 7250) >> 11: a factor 4 in the
+//     constants (they fit int16), the last factor 2 taken out of the rounding constant and the shift (14500 and 7500 are even);
+//   * rows 0 and 2 of its output, 8(a +- b), stay unscaled (s = 1/8 of the reference's) through the horizontal pass, which is linear
+//     up to its rounding shifts: (8s + 7) >> 4 = s >> 1 for every integer s, and (8x + 12000) >> 16 = (x + 1500) >> 13,
+//     (8x + 51000) >> 16 = (x + 6375) >> 13 (x the rotation's sum: 12000 and 51000 are multiples of 8); d1 != 0 is d != 0.
+// |c|,|d| <= 510 in the vertical pass and <= 2040 / 16320 (unscaled / scaled rows) in the horizontal one: every rotation is one
+// v_dot2_i32_i16.
+constexpr uint32_t K_ROT4_A = 8868u | (21408u << 16);                       // (x, y) . ( 8868, 21408)
+constexpr uint32_t K_ROT4_B = (uint32_t)(-21408 & 0xffff) | (8868u << 16);  // (x, y) . (-21408, 8868)
 __device__ __forceinline__ void fdct4x4(const int in[16], int out[16]) {
     int L[16];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int r0 = in[c], r1 = in[4 + c], r2 = in[8 + c], r3 = in[12 + c];
-        const int a1 = (r0 + r3) * 8, d1 = (r0 - r3) * 8, b1 = (r1 + r2) * 8, c1 = (r1 - r2) * 8;
+        const int a1 = r0 + r3, d1 = r0 - r3, b1 = r1 + r2, c1 = r1 - r2;   // 1/8 of the reference's
         L[c] = a1 + b1;
         L[8 + c] = a1 - b1;
-        // |c1|,|d1| <= 4080 here and <= 16320 in the row pass: both rotations are one v_dot2_i32_i16 each
         const uint32_t xy = pk16(c1, d1);
-        L[4 + c] = dot2(xy, K_ROT_A, 14500) >> 12;     // c1*2217 + d1*5352 + 14500
-        L[12 + c] = dot2(xy, K_ROT_B, 7500) >> 12;     // d1*2217 - c1*5352 + 7500
+        L[4 + c] = dot2(xy, K_ROT4_A, 7250) >> 11;     // (8c1*2217 + 8d1*5352 + 14500) >> 12
+        L[12 + c] = dot2(xy, K_ROT4_B, 3750) >> 11;    // (8d1*2217 - 8c1*5352 + 7500) >> 12
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int e0 = L[4 * i], e1 = L[4 * i + 1], e2 = L[4 * i + 2], e3 = L[4 * i + 3];
         const int a1 = e0 + e3, d1 = e0 - e3, b1 = e1 + e2, c1 = e1 - e2;
-        out[4 * i] = (a1 + b1 + 7) >> 4;
-        out[4 * i + 2] = (a1 - b1 + 7) >> 4;
         const uint32_t xy = pk16(c1, d1);
-        out[4 * i + 1] = (dot2(xy, K_ROT_A, 12000) >> 16) + (d1 != 0);
-        out[4 * i + 3] = dot2(xy, K_ROT_B, 51000) >> 16;
+        if (i & 1) {                                   // rows 1 and 3: the rotations' outputs, at the reference's scale
+            out[4 * i] = (a1 + b1 + 7) >> 4;
+            out[4 * i + 2] = (a1 - b1 + 7) >> 4;
+            out[4 * i + 1] = (dot2(xy, K_ROT_A, 12000) >> 16) + (d1 != 0);
+            out[4 * i + 3] = dot2(xy, K_ROT_B, 51000) >> 16;
+        } else {                                       // rows 0 and 2: 1/8 of the reference's
+            out[4 * i] = (a1 + b1) >> 1;
+            out[4 * i + 2] = (a1 - b1) >> 1;
+            out[4 * i + 1] = (dot2(xy, K_ROT_A, 1500) >> 13) + (d1 != 0);
+            out[4 * i + 3] = dot2(xy, K_ROT_B, 6375) >> 13;
+        }
     }
 }
 
@@ -180,7 +215,7 @@ __device__ __forceinline__ int had4(int v0, int v1, int v2, int v3, int i) {
 }
 // (gathers by ds_bpermute with the eight byte addresses made once: __shfl recomputes its lane arithmetic, four instructions,
 // at each of the sixteen calls)
-__device__ __forceinline__ int wht_roundtrip_lane(int x, int lane, int dc_q, int ac_q, const TDiv &ddc, const TDiv &dac, int &q) {
+__device__ __forceinline__ int wht_roundtrip_lane(int x, int lane, int dc_q, int ac_q, TDiv ddc, TDiv dac, int &q) {
     const int L = lane & 15, r = L >> 2, c = L & 3;
     const int base = (int)(threadIdx.x & 32u) * 4;             // byte address (in the wave) of the macroblock's lane 0
     const int col = base + 4 * c, row = base + 4 * (L & 12);   // ... of lane c (top of this lane's column), of lane 4r (head of its row)
@@ -205,16 +240,27 @@ __device__ __forceinline__ constexpr int inv_zigzag(int k) {
 }
 // the same for an index known only at run time: sixteen nibbles
 __device__ __forceinline__ int inv_zigzag_rt(int k) { return (int)((0xfea9db83c7426510ull >> (4 * k)) & 15); }
-__device__ __forceinline__ void store_zigzag(int16_t *dst, const int L[16]) {
+// the sixteen coefficients of a block as the eight dwords of its zig-zag row: w[k] = (z[2k], z[2k + 1]) as int16
+__device__ __forceinline__ void pack_zigzag(const int L[16], uint32_t w[8]) {
     int z[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) z[inv_zigzag(k)] = L[k];
-    uint32_t w[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = (uint32_t)(uint16_t)z[2 * k] | ((uint32_t)(uint16_t)z[2 * k + 1] << 16);
+    for (int k = 0; k < 8; ++k) w[k] = pk16(z[2 * k], z[2 * k + 1]);
+}
+__device__ __forceinline__ void store_zigzag(int16_t *dst, const uint32_t w[8]) {
     uint4 *d4 = reinterpret_cast<uint4 *>(dst);
     d4[0] = make_uint4(w[0], w[1], w[2], w[3]);
     d4[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+// prepare_filter_mask's count of a block (CPU_kernels.cl:800-819), the sum of |coefficient| as int16, taken on the packed words: a
+// word's two halves in one xor + one v_sad_u16 (abs_acc, vp8hip_dev.h).  dc_mask: 0xffff0000 where the block's DC (the low half of
+// word 0) does not count -- the luma blocks of an unsplit macroblock, whose DCs travel in block 24 -- else all ones.
+__device__ __forceinline__ int nz_zigzag(const uint32_t w[8], uint32_t dc_mask, int acc) {
+    uint32_t s = abs_acc(as_s16x2(w[0] & dc_mask), (uint32_t)acc);
+#pragma unroll
+    for (int k = 1; k < 8; ++k) s = abs_acc(as_s16x2(w[k]), s);
+    return (int)s;
 }
 
 // Pointers only where a Frame would do: every surface of a context has the same layout (carve_frame), so one stride / size
@@ -325,6 +371,9 @@ __device__ __forceinline__ void mb_body(const MBArgs &a, MBTile *s_t) {
     uint8_t *const rpu = ref == 0 ? a.ref0.u : (ref == 1 ? a.ref1.u : a.ref2.u);
     uint8_t *const rpv = ref == 0 ? a.ref0.v : (ref == 1 ? a.ref1.v : a.ref2.v);
     const int pstride = plane == 0 ? a.ystride : a.cstride, pw = plane == 0 ? a.yw : a.cw, ph = plane == 0 ? a.yh : a.ch;
+    // the block's first pixel in its plane, in bytes from pixel (0, 0): below 2^31 for any surface, so the rows of the current frame and of the
+    // reconstruction are a plane pointer plus a 32-bit offset (64-bit row products per access were a multiply each)
+    const uint32_t pix0 = (uint32_t)(posy * pstride + posx);
     const Plane cp{plane == 0 ? a.cur.y : (plane == 1 ? a.cur.u : a.cur.v), pstride, pw, ph};
     const Plane rc{plane == 0 ? a.recon.y : (plane == 1 ? a.recon.u : a.recon.v), pstride, pw, ph};
     const Plane rp{plane == 0 ? rpy : (plane == 1 ? rpu : rpv), pstride, pw, ph};
@@ -347,7 +396,7 @@ __device__ __forceinline__ void mb_body(const MBArgs &a, MBTile *s_t) {
         predict4x4<CONFORMANT>(rp, ix, iy, dx, dy, predw);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const uint32_t cw = *reinterpret_cast<const uint32_t *>(cp.p + (ptrdiff_t)(posy + r) * cp.stride + posx);
+            const uint32_t cw = *reinterpret_cast<const uint32_t *>(cp.p + (size_t)(pix0 + (uint32_t)(r * pstride)));
             *reinterpret_cast<uint32_t *>(&s_t[g].cur[tile_off + (by * 4 + r) * msz + bx * 4]) = cw;
         }
     }
@@ -388,6 +437,7 @@ __device__ __forceinline__ void mb_body(const MBArgs &a, MBTile *s_t) {
     float ssim = -2.0f;  // pack_8x8_into_16x16, :1352
     int seg_final = a.o_seg[mb];
     int nz_blk = 0;            // this lane's share of prepare_filter_mask's count, from the last pass that ran
+    const uint32_t dc_mask = (plane == 0 && parts == 0) ? 0xffff0000u : 0xffffffffu;   // nz_zigzag
     bool any_pass = false;
 
     for (int seg = 3; seg >= 0; --seg) {        // inter_part.h:329
@@ -418,8 +468,8 @@ __device__ __forceinline__ void mb_body(const MBArgs &a, MBTile *s_t) {
                 for (int c = 0; c < 4; ++c) res[4 * r + c] = byte_of(cw, c) - byte_of(predw[r], c);
             }
             fdct4x4(res, coef);
-            const TDiv ddc = tdiv_make(dc_q), dac = tdiv_make(ac_q);
-            coef[0] = tdiv(coef[0], ddc);        // truncating, :1478-1481
+            const TDiv dac = tdiv_make(ac_q);
+            coef[0] = mb_dc_div(coef[0], dc_q);  // truncating, :1478-1481
 #pragma unroll
             for (int k = 1; k < 16; ++k) coef[k] = tdiv(coef[k], dac);
         }
@@ -437,23 +487,23 @@ __device__ __forceinline__ void mb_body(const MBArgs &a, MBTile *s_t) {
             }
         }
         if (blk) {                               // idct4x4, :1545-1608
-            if (live) store_zigzag(a.o_coeffs + ((size_t)mb * 25 + lane) * 16, coef);
-            // prepare_filter_mask, CPU_kernels.cl:800-819
-#pragma unroll
-            for (int k = 1; k < 16; ++k) nz_blk += iabs((int16_t)coef[k]);
-            if (plane != 0 || parts != 0) nz_blk += iabs((int16_t)coef[0]);
+            uint32_t zw[8];
+            pack_zigzag(coef, zw);
+            if (live) store_zigzag(a.o_coeffs + ((size_t)mb * 25 + lane) * 16, zw);
+            nz_blk = nz_zigzag(zw, dc_mask, nz_blk);
             int L[16];
             L[0] = __mul24((int16_t)coef[0], dc_q);
 #pragma unroll
-            for (int k = 1; k < 16; ++k) L[k] = __mul24((int16_t)coef[k], ac_q);
+            for (int k = 1; k < 16; ++k) L[k] = __mul24(coef[k], ac_q);   // (|quotient| <= 2040: an int16 as it stands)
             idct4x4(L);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                uint32_t w = 0;
+                int px[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) w |= (uint32_t)sat8(L[4 * r + c] + byte_of(predw[r], c)) << (8 * c);
+                for (int c = 0; c < 4; ++c) px[c] = L[4 * r + c] + byte_of(predw[r], c);
+                const uint32_t w = pack_satu4(px);
                 *reinterpret_cast<uint32_t *>(&s_t[g].rec[tile_off + (by * 4 + r) * msz + bx * 4]) = w;
-                if (live) *reinterpret_cast<uint32_t *>(rc.p + (ptrdiff_t)(posy + r) * rc.stride + posx) = w;
+                if (live) *reinterpret_cast<uint32_t *>(rc.p + (size_t)(pix0 + (uint32_t)(r * pstride))) = w;
             }
         }
         }
@@ -560,7 +610,7 @@ __device__ __forceinline__ float chain_n(const float *p) {
     return acc;
 }
 // wht_roundtrip_lane for a macroblock whose sixteen luma lanes are lanes base16 .. base16 + 15 of the wave
-__device__ __forceinline__ int wht_roundtrip_row(int x, int L, int base_bytes, int dc_q, int ac_q, const TDiv &ddc, const TDiv &dac, int &q) {
+__device__ __forceinline__ int wht_roundtrip_row(int x, int L, int base_bytes, int dc_q, int ac_q, TDiv ddc, TDiv dac, int &q) {
     const int r = L >> 2, c = L & 3;
     const int col = base_bytes + 4 * c, row = base_bytes + 4 * (L & 12);
     auto gather_col = [&](int v, int i) { return had4(__builtin_amdgcn_ds_bpermute(col, v), __builtin_amdgcn_ds_bpermute(col + 16, v),
@@ -622,6 +672,7 @@ __device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MB
     uint8_t *const rpu = ref == 0 ? a.ref0.u : (ref == 1 ? a.ref1.u : a.ref2.u);
     uint8_t *const rpv = ref == 0 ? a.ref0.v : (ref == 1 ? a.ref1.v : a.ref2.v);
     const int pstride = luma ? a.ystride : a.cstride, pw = luma ? a.yw : a.cw, ph = luma ? a.yh : a.ch;
+    const uint32_t pix0 = (uint32_t)(posy * pstride + posx);   // as in mb_body
     const Plane cp{plane == 0 ? a.cur.y : (plane == 1 ? a.cur.u : a.cur.v), pstride, pw, ph};
     const Plane rc{plane == 0 ? a.recon.y : (plane == 1 ? a.recon.u : a.recon.v), pstride, pw, ph};
     const Plane rp{plane == 0 ? rpy : (plane == 1 ? rpu : rpv), pstride, pw, ph};
@@ -640,7 +691,7 @@ __device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MB
         predict4x4<CONFORMANT>(rp, ix, iy, dx, dy, predw);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const uint32_t cw = *reinterpret_cast<const uint32_t *>(cp.p + (ptrdiff_t)(posy + r) * cp.stride + posx);
+            const uint32_t cw = *reinterpret_cast<const uint32_t *>(cp.p + (size_t)(pix0 + (uint32_t)(r * pstride)));
             *reinterpret_cast<uint32_t *>(&T.cur[tile_off + (by * 4 + r) * msz + bx * 4]) = cw;
         }
     }
@@ -684,6 +735,7 @@ __device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MB
     float ssim = -2.0f;  // pack_8x8_into_16x16, :1352
     int seg_final = a.o_seg[mb];
     int nz_y = 0, nz_c = 0;    // prepare_filter_mask's count, luma and chroma blocks, from the last pass this macroblock ran
+    const uint32_t dc_mask = (luma && parts == 0) ? 0xffff0000u : 0xffffffffu;   // nz_zigzag
     bool any_pass = false;
     for (int seg = 3, round = 0; seg >= 0; --seg, ++round) {        // inter_part.h:329
         const bool act = !(ssim > a.ssim_target);                   // dct4x4 gate, :1391
@@ -709,8 +761,8 @@ __device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MB
                     for (int c = 0; c < 4; ++c) res[4 * r + c] = byte_of(cw, c) - byte_of(predw[r], c);
                 }
                 fdct4x4(res, coef);
-                const TDiv ddc = tdiv_make(dc_q), dac = tdiv_make(ac_q);
-                coef[0] = tdiv(coef[0], ddc);        // truncating, :1478-1481
+                const TDiv dac = tdiv_make(ac_q);
+                coef[0] = mb_dc_div(coef[0], dc_q);  // truncating, :1478-1481
 #pragma unroll
                 for (int k = 1; k < 16; ++k) coef[k] = tdiv(coef[k], dac);
             }
@@ -725,22 +777,23 @@ __device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MB
                 nz_blk += iabs((int16_t)q24);
             }
             {                                        // idct4x4, :1545-1608
-                if (live) store_zigzag(a.o_coeffs + ((size_t)mb * 25 + blkidx) * 16, coef);
-#pragma unroll
-                for (int k = 1; k < 16; ++k) nz_blk += iabs((int16_t)coef[k]);
-                if (!luma || parts != 0) nz_blk += iabs((int16_t)coef[0]);
+                uint32_t zw[8];
+                pack_zigzag(coef, zw);
+                if (live) store_zigzag(a.o_coeffs + ((size_t)mb * 25 + blkidx) * 16, zw);
+                nz_blk = nz_zigzag(zw, dc_mask, nz_blk);
                 int L[16];
                 L[0] = __mul24((int16_t)coef[0], dc_q);
 #pragma unroll
-                for (int k = 1; k < 16; ++k) L[k] = __mul24((int16_t)coef[k], ac_q);
+                for (int k = 1; k < 16; ++k) L[k] = __mul24(coef[k], ac_q);   // (|quotient| <= 2040: an int16 as it stands)
                 idct4x4(L);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    uint32_t wd = 0;
+                    int px[4];
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) wd |= (uint32_t)sat8(L[4 * r + c] + byte_of(predw[r], c)) << (8 * c);
+                    for (int c = 0; c < 4; ++c) px[c] = L[4 * r + c] + byte_of(predw[r], c);
+                    const uint32_t wd = pack_satu4(px);
                     *reinterpret_cast<uint32_t *>(&T.rec[tile_off + (by * 4 + r) * msz + bx * 4]) = wd;
-                    if (live) *reinterpret_cast<uint32_t *>(rc.p + (ptrdiff_t)(posy + r) * rc.stride + posx) = wd;
+                    if (live) *reinterpret_cast<uint32_t *>(rc.p + (size_t)(pix0 + (uint32_t)(r * pstride))) = wd;
                 }
             }
             if (luma) nz_y = row_sum(nz_blk);

@@ -62,8 +62,8 @@ struct PyrArgs { Frame f[2 * MAX_BATCH]; uint32_t border_mask; };   // blockIdx.
 static int border_jobs(const Frame &f) { return (f.Y[0].h + 2 * EXT) + 2 * (f.U.h + 2 * EXT); }
 
 __global__ __launch_bounds__(256) void k_pyramid(PyrArgs a) {
-    __shared__ uint8_t s2[16][16];
-    __shared__ uint8_t s3[8][8];
+    __shared__ __attribute__((aligned(4))) uint8_t s2[16][16];
+    __shared__ __attribute__((aligned(4))) uint8_t s3[8][8];
     const Frame &f = a.f[blockIdx.z];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     const Plane &P0 = f.Y[0];
@@ -82,48 +82,64 @@ __global__ __launch_bounds__(256) void k_pyramid(PyrArgs a) {
         else if (job < ny + 2 * nc) border_row(f.V, job - ny - nc - EXT, t & 63);
         return;
     }
-    // 4x4 source pixels -> 2x2 of level 1 -> 1 of level 2
-    const int sx = imin(bx * 64 + 4 * tx, P0.w - 4), sy0 = by * 64 + 4 * ty;
+    // 4x4 source pixels -> 2x2 of level 1 -> 1 of level 2.  Every address is a plane pointer (uniform: scalar registers) plus a 32-bit
+    // offset (a surface is far below 2^31 bytes), and a 2x2 sum is two v_dot4_u32_u8 on the rows as loaded (a byte mask of ones picks the
+    // pair, the rounding 2 rides in as the accumulator) -- per-sample byte extraction and 64-bit row products were most of the 216 vector
+    // instructions a thread issued.
+    // Frame sizes are multiples of 16 (vp8hip_create), so level l is exactly w >> l by h >> l and the thread's 4x4 source pixels lie in
+    // the plane all together or not at all: ONE test covers its two rows of level 1 and its sample of level 2 (and a level-3 / level-4
+    // sample lies in its plane exactly when all the samples under it do: what a thread outside the plane computes is never stored).
+    static_assert(PAD >= 4, "a clamped row is read from its first byte");
+    const int x0 = bx * 64 + 4 * tx, sy0 = by * 64 + 4 * ty;
+    const bool in = x0 < P0.w && sy0 < P0.h;
+    const uint32_t last = (uint32_t)((P0.h - 1) * P0.stride + (P0.w - 4));               // (uniform)
+    // (rows and strides are below 2^24 and their products below 2^31: v_mad_u32_u24, where the 32-bit product is a 64-bit multiply-add)
+    const uint32_t o0 = __umul24((uint32_t)imin(sy0, P0.h - 1), (uint32_t)P0.stride) + (uint32_t)imin(x0, P0.w - 4);   // <= last
+    uint32_t lim = in ? 0xffffffffu : last;   // rows below the plane end at its last dword; they are only met by threads that store nothing
+    asm("" : "+v"(lim));                      // (one select, not one per row)
     uint32_t r[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-        r[k] = *reinterpret_cast<const uint32_t *>(P0.p + (ptrdiff_t)imin(sy0 + k, P0.h - 1) * P0.stride + sx);
-    int l1[2][2];
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t o = o0 + (uint32_t)(k * P0.stride);
+        r[k] = *reinterpret_cast<const uint32_t *>(P0.p + (size_t)(k == 0 ? o : __builtin_elementwise_min(o, lim)));
+    }
+    uint32_t l1[2][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-            l1[j][i] = (byte_of(r[2 * j], 2 * i) + byte_of(r[2 * j], 2 * i + 1) + byte_of(r[2 * j + 1], 2 * i) +
-                        byte_of(r[2 * j + 1], 2 * i + 1) + 2) >> 2;
-    const Plane &P1 = f.Y[1];
-    const int x1 = bx * 32 + 2 * tx, y1 = by * 32 + 2 * ty;
-    if (x1 < P1.w) {
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t pick = i == 0 ? 0x00000101u : 0x01010000u;
+            l1[j][i] = __builtin_amdgcn_udot4(r[2 * j], pick, __builtin_amdgcn_udot4(r[2 * j + 1], pick, 2u, false), false) >> 2;
+        }
+    const uint32_t l2 = (l1[0][0] + l1[0][1] + l1[1][0] + l1[1][1] + 2) >> 2;
+    if (in) {
+        const Plane &P1 = f.Y[1];
+        const uint32_t o1 = __umul24((uint32_t)(by * 32 + 2 * ty), (uint32_t)P1.stride) + (uint32_t)(bx * 32 + 2 * tx);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            if (y1 + j < P1.h)
-                *reinterpret_cast<uint16_t *>(P1.p + (ptrdiff_t)(y1 + j) * P1.stride + x1) = (uint16_t)(l1[j][0] | (l1[j][1] << 8));
+            *reinterpret_cast<uint16_t *>(P1.p + (size_t)(o1 + (uint32_t)(j * P1.stride))) = (uint16_t)(l1[j][0] | (l1[j][1] << 8));
+        const Plane &P2 = f.Y[2];
+        P2.p[(size_t)(__umul24((uint32_t)(by * 16 + ty), (uint32_t)P2.stride) + (uint32_t)(bx * 16 + tx))] = (uint8_t)l2;
     }
-    const int l2 = (l1[0][0] + l1[0][1] + l1[1][0] + l1[1][1] + 2) >> 2;
-    const Plane &P2 = f.Y[2];
-    const int x2 = bx * 16 + tx, y2 = by * 16 + ty;
-    if (x2 < P2.w && y2 < P2.h) P2.p[(ptrdiff_t)y2 * P2.stride + x2] = (uint8_t)l2;
     s2[ty][tx] = (uint8_t)l2;
     __syncthreads();
-    if (t < 64) {
+    if (t < 64) {     // (a 2x2 of bytes in LDS: two 16-bit reads, summed by v_sad_u8 against zero)
         const int ux = t & 7, uy = t >> 3;
-        const int l3 = (s2[2 * uy][2 * ux] + s2[2 * uy][2 * ux + 1] + s2[2 * uy + 1][2 * ux] + s2[2 * uy + 1][2 * ux + 1] + 2) >> 2;
+        const uint32_t a0 = *reinterpret_cast<const uint16_t *>(&s2[2 * uy][2 * ux]), a1 = *reinterpret_cast<const uint16_t *>(&s2[2 * uy + 1][2 * ux]);
+        const uint32_t l3 = __builtin_amdgcn_sad_u8(a0, 0u, __builtin_amdgcn_sad_u8(a1, 0u, 2u)) >> 2;
         const Plane &P3 = f.Y[3];
         const int x3 = bx * 8 + ux, y3 = by * 8 + uy;
-        if (x3 < P3.w && y3 < P3.h) P3.p[(ptrdiff_t)y3 * P3.stride + x3] = (uint8_t)l3;
+        if (x3 < P3.w && y3 < P3.h) P3.p[(size_t)(__umul24((uint32_t)y3, (uint32_t)P3.stride) + (uint32_t)x3)] = (uint8_t)l3;
         s3[uy][ux] = (uint8_t)l3;
     }
     __syncthreads();
     if (t < 16) {
         const int ux = t & 3, uy = t >> 2;
-        const int l4 = (s3[2 * uy][2 * ux] + s3[2 * uy][2 * ux + 1] + s3[2 * uy + 1][2 * ux] + s3[2 * uy + 1][2 * ux + 1] + 2) >> 2;
+        const uint32_t a0 = *reinterpret_cast<const uint16_t *>(&s3[2 * uy][2 * ux]), a1 = *reinterpret_cast<const uint16_t *>(&s3[2 * uy + 1][2 * ux]);
+        const uint32_t l4 = __builtin_amdgcn_sad_u8(a0, 0u, __builtin_amdgcn_sad_u8(a1, 0u, 2u)) >> 2;
         const Plane &P4 = f.Y[4];
         const int x4 = bx * 4 + ux, y4 = by * 4 + uy;
-        if (x4 < P4.w && y4 < P4.h) P4.p[(ptrdiff_t)y4 * P4.stride + x4] = (uint8_t)l4;
+        if (x4 < P4.w && y4 < P4.h) P4.p[(size_t)(__umul24((uint32_t)y4, (uint32_t)P4.stride) + (uint32_t)x4)] = (uint8_t)l4;
     }
 }
 
@@ -148,9 +164,12 @@ void launch_pyramid_batch(hipStream_t s, const Frame *const *f, int nframes, uin
 }
 
 // ------------------------------------------------------------------------------------------------
-// Tight HBM-resident Y,U,V planes -> the padded surfaces of a frame, one launch.  A thread copies `per` units of 8 bytes,
-// 256 units apart (a workgroup = per x 2 KB): with one unit per thread a 1080p frame is 1530 workgroups of next to no work,
-// and under load it is the dispatch of workgroups, not the copying, that such a launch waits for (same box, headline with 1 / 8 /
+// Tight HBM-resident Y,U,V planes -> the padded surfaces of a frame, one launch.  A workgroup owns a run of rows of ONE plane, a
+// wave takes every fourth of them and a lane 16 bytes of a row: which plane and which row are scalar values, and an address is a
+// scalar row base plus the lane's 32-bit byte offset.  (A thread used to copy `per` units of 8 bytes that it found by dividing a flat
+// unit index by the row's unit count and by a three-way plane select per unit: 41 vector instructions per 8 bytes.)
+// A workgroup copies about per x 2 KB, as it always did: with one unit per thread a 1080p frame was 1530 workgroups of next to no
+// work, and under load it is the dispatch of workgroups, not the copying, that such a launch waits for (same box, headline with 1 / 8 /
 // 16 / 32 units per thread: 62.0 / 62.4 / 62.5 / 62.5 M MB/s).
 // ------------------------------------------------------------------------------------------------
 // The source may be smaller than the coded ("wrk") size -- 1920x1080 in, 1920x1088 coded: copy_with_padding, encIO.h:141-196,
@@ -159,40 +178,55 @@ void launch_pyramid_batch(hipStream_t s, const Frame *const *f, int nframes, uin
 // written -- which bites only when the width is not a multiple of 16, none of BASELINE's configs; there this is the
 // intended result, not the reference's undefined one; tests/test_padding.py shows both).  sw, sh: luma size of the source; ssy, ssc: its row strides.
 struct PackItem { Plane py, pu, pv; const uint8_t *sy, *su, *sv; int sw, sh, ssy, ssc; };
-__device__ __forceinline__ void pack_body(const PackItem &a, int per) {
-    const Plane &py = a.py, &pu = a.pu, &pv = a.pv;
-    const uint8_t *sy = a.sy, *su = a.su, *sv = a.sv;
-    const int ny = (py.w >> 3) * py.h, nc = (pu.w >> 3) * pu.h;
-    for (int k = 0; k < per; ++k) {
-        int i = ((int)blockIdx.x * per + k) * 256 + (int)threadIdx.x;
-        const Plane *pl = &py;
-        const uint8_t *src = sy;
-        int sw = a.sw, sh = a.sh, ss = a.ssy;
-        if (i >= ny) {
-            i -= ny;
-            pl = &pu;
-            src = su;
-            sw >>= 1; sh >>= 1; ss = a.ssc;
-            if (i >= nc) { i -= nc; pl = &pv; src = sv; }
-            if (i >= nc) return;
-        }
-        const int upr = pl->w >> 3;     // 8-byte units per row
-        const int y = i / upr, x = (i % upr) * 8;
+// rows_y: luma rows per workgroup (a chroma workgroup takes twice as many, the same bytes); wg_y, wg_c: workgroups per luma / chroma plane
+struct PackGrid { int rows_y, wg_y, wg_c; };
+__device__ __forceinline__ void pack_body(const PackItem &a, const PackGrid &g) {
+    int wg = (int)blockIdx.x;
+    const int pi = wg < g.wg_y ? 0 : (wg < g.wg_y + g.wg_c ? 1 : 2);
+    wg -= pi == 0 ? 0 : (pi == 1 ? g.wg_y : g.wg_y + g.wg_c);
+    // (member by member: a pointer into the argument block picked by an index sends the block to scratch memory)
+    uint8_t *const dp = pi == 0 ? a.py.p : (pi == 1 ? a.pu.p : a.pv.p);
+    const uint8_t *const src = pi == 0 ? a.sy : (pi == 1 ? a.su : a.sv);
+    const int dstride = pi == 0 ? a.py.stride : a.pu.stride, dw = pi == 0 ? a.py.w : a.pu.w, dh = pi == 0 ? a.py.h : a.pu.h;
+    const int sw = pi == 0 ? a.sw : a.sw >> 1, sh = pi == 0 ? a.sh : a.sh >> 1, ss = pi == 0 ? a.ssy : a.ssc;
+    const int rows = pi == 0 ? g.rows_y : 2 * g.rows_y;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+    const int y_end = imin((wg + 1) * rows, dh);
+    const bool aligned = ((ss | (int)(reinterpret_cast<uintptr_t>(src) & 7)) & 7) == 0;   // the source rows are 8-byte aligned
+    for (int y = wg * rows + wave; y < y_end; y += 4) {
         const uint8_t *row = src + (size_t)(y < sh ? y : sh - 1) * ss;
-        uint2 v;
-        if (x + 8 <= sw && ((ss | (int)(reinterpret_cast<uintptr_t>(src) & 7)) & 7) == 0) {
-            v = *reinterpret_cast<const uint2 *>(row + x);
-        } else {          // the unit hangs over the source's right edge, or the source rows are not 8-byte aligned
-            uint32_t w[2] = {0, 0};
+        uint8_t *drow = dp + (ptrdiff_t)y * dstride;
+        for (int x = lane * 16; x + 16 <= dw; x += 1024) {
+            uint4 v;
+            if (x + 16 <= sw && aligned) {
+                const uint2 v0 = *reinterpret_cast<const uint2 *>(row + (uint32_t)x), v1 = *reinterpret_cast<const uint2 *>(row + (uint32_t)x + 8);
+                v = make_uint4(v0.x, v0.y, v1.x, v1.y);
+            } else {      // the lane's bytes hang over the source's right edge, or the source rows are not 8-byte aligned
+                uint32_t w[4] = {0, 0, 0, 0};
 #pragma unroll
-            for (int j = 0; j < 8; ++j) w[j >> 2] |= (uint32_t)row[x + j < sw ? x + j : sw - 1] << (8 * (j & 3));
-            v = make_uint2(w[0], w[1]);
+                for (int j = 0; j < 16; ++j) w[j >> 2] |= (uint32_t)row[x + j < sw ? x + j : sw - 1] << (8 * (j & 3));
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            *reinterpret_cast<uint4 *>(drow + (uint32_t)x) = v;
         }
-        *reinterpret_cast<uint2 *>(pl->p + (ptrdiff_t)y * pl->stride + x) = v;
+        // plane widths are multiples of 8 (and rows start 32-byte aligned): a row may end in one 8-byte unit, which one lane copies
+        if ((dw & 8) && lane == ((dw >> 4) & 63)) {
+            const int x = dw & ~15;
+            uint2 v;
+            if (x + 8 <= sw && aligned) {
+                v = *reinterpret_cast<const uint2 *>(row + (uint32_t)x);
+            } else {
+                uint32_t w[2] = {0, 0};
+#pragma unroll
+                for (int j = 0; j < 8; ++j) w[j >> 2] |= (uint32_t)row[x + j < sw ? x + j : sw - 1] << (8 * (j & 3));
+                v = make_uint2(w[0], w[1]);
+            }
+            *reinterpret_cast<uint2 *>(drow + (uint32_t)x) = v;
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void k_pack_b(BatchOf<PackItem> b, int per) { pack_body(b.item[blockIdx.z], per); }
+__global__ __launch_bounds__(256) void k_pack_b(BatchOf<PackItem> b, PackGrid g) { pack_body(b.item[blockIdx.z], g); }
 static int pack_units_per_thread() {
     static const int per = [] { const char *e = getenv("VP8HIP_PACK_UNITS"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
     return per;
@@ -210,9 +244,12 @@ void launch_pack_batch(hipStream_t s, const SourceItem *items, int n, int sw, in
     b.n = n;
     for (int i = 0; i < n; ++i) b.item[i] = pack_item(*items[i].f, items[i].y, items[i].u, items[i].v, sw, sh, ssy, ssc);
     const Frame &f = *items[0].f;
-    const int units = (f.Y[0].w >> 3) * f.Y[0].h + 2 * ((f.U.w >> 3) * f.U.h);
-    const int per = pack_units_per_thread();
-    VP8_LAUNCH(k_pack_b, dim3((units + 256 * per - 1) / (256 * per), 1, n), dim3(256), 0, s, b, per);
+    PackGrid g;
+    g.rows_y = pack_units_per_thread() * 2048 / f.Y[0].w;      // rows of about `per` x 2 KB
+    if (g.rows_y < 1) g.rows_y = 1;
+    g.wg_y = (f.Y[0].h + g.rows_y - 1) / g.rows_y;
+    g.wg_c = (f.U.h + 2 * g.rows_y - 1) / (2 * g.rows_y);
+    VP8_LAUNCH(k_pack_b, dim3(g.wg_y + 2 * g.wg_c, 1, n), dim3(256), 0, s, b, g);
 }
 
 // ------------------------------------------------------------------------------------------------
