@@ -422,6 +422,38 @@ int vp8hip_analysis_restart(vp8hip_ctx *ctx);
  * early) -- or else of the last frame taken in, with coded = 0.  Waits for the two measurements alone (a word each launch writes
  * last), not for the streams.  VP8HIP_ERR_STATE: analysis off, or no frame taken in since it was turned on. */
 int vp8hip_analysis_result(vp8hip_ctx *ctx, vp8hip_analysis *a);
+/* ---- a quantiser per macroblock: the caller's segment map, or variance-adaptive quantisation ----------------------------
+ * Every inter frame carries the four-segment map with the four quantiser indices of the ladder (vp8hip_auto_segments); by default
+ * the reference's SSIM loop picks a macroblock's segment, and with ssim_target = -1 that is segment 3 for every macroblock.  Here
+ * something else picks it; the rule is stated bit for bit in include/vp8hip_host.h.
+ *   mode 0 (default): off -- no launch, no allocation, no byte and no number changes.
+ *   mode 1: the caller's map (libvpx's VP8E_SET_ROI_MAP): MBs bytes, raster order, each 0..3, handed over with
+ *           vp8hip_set_segment_map_device or vp8hip_upload_segment_map and in force until replaced.  Without a map: segment 3
+ *           everywhere, which is exactly the default's frames.
+ *   mode 2: variance-adaptive, strength 1..3 (mode 0 and 1 ignore strength).  Every frame that becomes current passes through two more launches at the end
+ *           of its intake (k_aq_map_b, k_aq_seg_b) that make the map from the coded luma as the searches read it: flat macroblocks
+ *           take the finer segments, busy ones the coarser.  Once per frame TAKEN IN, never per coding attempt.  A frame taken in
+ *           before mode 2 was set has no map and is coded in segment 3.
+ * In mode 1 or 2 vp8hip_inter_transform, vp8hip_inter_finish and vp8hip_batch_inter_transform launch the mapped form of the
+ * macroblock kernel (k_mb_p_map; VP8HIP_MB_PACKED=0 has none, the packed one is launched): each macroblock runs ONE transform pass,
+ * in segment map[mb] & 3, and MB_segment_id is that value; MB_SSIM is still computed.  Key frames stay as they are: segment 0, no
+ * segmentation in the header.  Everything behind the transform (loop filters, entropy stage, analysis record) reads MB_segment_id.
+ * VP8HIP_ERR_ARG and nothing has changed: mode outside 0..2, strength outside 1..3 in mode 2.  VP8HIP_ERR_STATE and nothing has
+ * changed (mode 1 or 2, or a map): a context created with ssim_target >= 0 (the SSIM ladder and the map both own the segment id), or one
+ * that shares a frame's searches with other devices (vp8hip_shard_init, which in turn refuses a context with a mode).  Turning a mode
+ * on allocates the maps; the setter waits for the context's streams: not a per-frame call.  All members of a batch must agree on
+ * mode and strength (vp8hip_batch_create and the batched launches check it); the maps are the members' own. */
+int vp8hip_set_segment_mode(vp8hip_ctx *ctx, int mode, int strength);
+int vp8hip_segment_mode(const vp8hip_ctx *ctx, int *mode, int *strength);      /* what is in force (either pointer may be NULL) */
+/* The caller's map, MBs bytes: copied into the context on its stream (from device memory: values are taken & 3, and the map may be
+ * reused when the call returns only after the stream has got there; from host memory: a value above 3 is refused with VP8HIP_ERR_ARG,
+ * and the call returns when the copy is done).  A map may be set in any mode; mode 1 reads it. */
+int vp8hip_set_segment_map_device(vp8hip_ctx *ctx, const uint8_t *map);
+int vp8hip_upload_segment_map(vp8hip_ctx *ctx, const uint8_t *host_map);
+/* The map in force for the current frame, MBs bytes (mode 1 without a map: all 3), and in mode 2 the e of the rule for every
+ * macroblock (e_out may be NULL; not NULL outside mode 2: VP8HIP_ERR_STATE).  Blocks.  VP8HIP_ERR_STATE: mode 0, or mode 2 and no
+ * frame taken in since it was set. */
+int vp8hip_download_segment_map(vp8hip_ctx *ctx, uint8_t *map_out, uint8_t *e_out);
 /* on = 1: the context gets a second stream, and work that does not depend on the filtered frame runs beside the loop filter:
  * the entropy stage of the same frame (vp8hip_count_probs ... vp8hip_encode_frame), the next frame's upload, parameter scan
  * and GOLDEN / ALTREF searches.  The filter stays on the stream the frame was coded on and the CONTEXT moves to the other one
@@ -556,7 +588,10 @@ const char *vp8hip_status_string(int status);
  * vp8drv_set_analysis, vp8drv_get_frame_analysis) and vp8drv_set_quantizer / vp8drv_get_quantizer (entry points only);
  * also under 4010: source windows and orientation (vp8hip_set_source_window, vp8hip_set_source_orientation, vp8host_source_window,
  * vp8host_window_frame, vp8host_orient_frame, vp8drv_set_source_window, vp8drv_set_source_orientation; entry points only:
- * vp8drv_config is unchanged). */
+ * vp8drv_config is unchanged);
+ * also under 4010: the per-macroblock quantiser (vp8hip_set_segment_mode, vp8hip_segment_mode, vp8hip_set_segment_map_device,
+ * vp8hip_upload_segment_map, vp8hip_download_segment_map, vp8host_aq_segment_map, vp8host_aq_segment, vp8drv_set_segment_mode, vp8drv_set_segment_map;
+ * entry points only: vp8drv_config is unchanged). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

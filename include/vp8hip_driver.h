@@ -281,6 +281,17 @@ typedef vp8hip_analysis vp8drv_analysis;
 /* The record of the frame just made final: its verdict first, as vp8drv_get_frame_quality (a frame coded again as a key frame has the
  * key frame's coding side; its source side was measured once, when it was taken in).  VP8HIP_ERR_STATE: analysis off or no frame coded. */
 int vp8drv_get_frame_analysis(vp8drv *d, vp8drv_analysis *a);
+/* A quantiser per macroblock (vp8hip_set_segment_mode; the rule: include/vp8hip_host.h), entry points and not a field for the reason
+ * vp8drv_set_denoise is one.  mode 0 (default) off, 1 the caller's map, 2 variance-adaptive at strength 1..3.  Inter frames are coded in
+ * the mode from the next frame taken in on (a frame already handed over with vp8drv_stage_frame_host has no variance map: segment 3);
+ * key frames, scheduled or not, stay as they are.  GOP chunks give the serial program's bytes: mode 2's map depends on the current
+ * frame alone.  With vp8drv_set_analysis, segment_mbs of vp8drv_get_frame_analysis is the map's histogram on inter frames.  It takes
+ * the open check_SSIM verdict first.  VP8HIP_ERR_ARG: a bad mode or strength; VP8HIP_ERR_STATE: cfg.ssim_target >= 0, or the driver is
+ * a member of a live batch (members must agree on mode and strength: set them before vp8drv_batch_create, which refuses a mix). */
+int vp8drv_set_segment_mode(vp8drv *d, int mode, int strength);
+/* The map of mode 1: MBs bytes in host memory, raster order, each 0..3 (a larger value: VP8HIP_ERR_ARG), copied before the call returns
+ * and in force until replaced; a member of a batch may get a new one between frames.  Without one mode 1 codes segment 3 everywhere. */
+int vp8drv_set_segment_map(vp8drv *d, const uint8_t *host_map);
 /* cfg.qi_min / qi_max from the next frame coded on: both ladders are made again with vp8host_quantizer_ladders and the driver's qi_min
  * becomes the smaller of the two, exactly as in vp8drv_create.  It takes the open check_SSIM verdict first, so a frame sent back is coded
  * again with the quantizers it was coded with.  References, GOP position and every other state stay: behind a key frame of the GOP

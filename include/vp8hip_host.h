@@ -276,6 +276,30 @@ typedef struct {
 } vp8host_luma_analysis;
 int vp8host_analyse_luma(const uint8_t *cur, const uint8_t *prev_or_null, int width, int height, vp8host_luma_analysis *out);
 
+/* The rule of the per-macroblock quantiser (vp8hip_set_segment_mode, include/vp8hip.h; k_aq_map_b, k_aq_seg_b, k_mb_p_map), bit for
+ * bit.  The project's own.  Mode 0 is off, mode 1 the caller's map, mode 2 variance-adaptive with strength 1..3.
+ *
+ * In mode 1 or 2 a macroblock of an INTER frame is coded once, in segment map[mb] & 3, with that segment's row of the segment data in
+ * force: the arithmetic of the default's pass with the segment given instead of found.  MB_segment_id[mb] is that value; MB_SSIM is
+ * still computed.  Key frames stay as they are (segment 0, no segmentation in the header).
+ *
+ * Mode 2 makes the map from the coded luma of the current frame as the searches read it (behind window, convert, deinterlace, orient,
+ * scale or pack, and denoise; the padded area counts).  All integers:
+ *     v(mb)  = 256 * (sum of x * x over the macroblock's 256 samples) - (sum of x over them) squared: the analysis record's
+ *              "256 * 256 times the variance", at most 1 065 369 600
+ *     n      = v + 1, p = the position of its leading one (n >> p == 1)
+ *     frac   = p >= 3 ? (n >> (p - 3)) & 7 : (n << (3 - p)) & 7
+ *     e(mb)  = 8 * p + frac: log2 in eighths, piecewise linear, 0 for a flat macroblock, 239 at the largest v
+ *     E      = floor(sum of e(mb) over the frame's macroblocks / their number)
+ *     W      = 24, 16, 12 for strength 1, 2, 3
+ *     seg    = clamp(2 + floor((e - E) / W), 0, 3), the division rounding towards minus infinity
+ * so a macroblock of mean activity takes segment 2, flatter ones 1 and then 0 (finer), busier ones 3.
+ * vp8host_aq_segment is the last line; vp8host_aq_segment_map is the whole rule in plain C++ on a luma plane of `stride` bytes per row
+ * (width and height whole macroblocks): map_out[MBs], e_out[MBs] (may be NULL), raster order.  Returns 0, or -1: luma or map_out
+ * NULL, width or height below 16 or not a multiple of 16, stride below width, strength outside 1..3. */
+int vp8host_aq_segment(int e, int E, int W);
+int vp8host_aq_segment_map(const uint8_t *luma, int stride, int width, int height, int strength, uint8_t *map_out, uint8_t *e_out);
+
 /* frames.skip_prob, loop_filter.h:37-44 */
 int vp8host_skip_prob(const int32_t *MB_non_zero_coeffs, int mb_count);
 

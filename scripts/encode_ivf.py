@@ -79,7 +79,11 @@ def main():
     ap.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=0, help="turn the frames clockwise by this many degrees on the device (vp8drv_set_source_orientation)")
     ap.add_argument("--mirror", action="store_true", help="... behind a left-right flip")
     ap.add_argument("--analysis", default="", metavar="FILE", help="the frame analysis record of every frame as one text line per frame (vp8drv_set_analysis; the line: scripts/native/y4m_to_ivf.cpp): a first-pass file")
+    ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation of the inter frames at strength N: flat macroblocks take the finer segments of the quantiser ladder, busy ones the coarser (vp8drv_set_segment_mode, mode 2)")
+    ap.add_argument("--segment-map", default="", metavar="FILE", help="the caller's segment map for every inter frame: one byte 0..3 per macroblock of the coded picture, raster order (vp8drv_set_segment_mode, mode 1)")
     a = ap.parse_args()
+    if a.aq and a.segment_map:
+        sys.exit("--aq and --segment-map: one of them picks the segments")
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dist = None
     if world > 1:      # the library's own process group (vp8hip_group_*: RCCL inside libvp8hip.so, the id through a file): no GPU framework in the host
@@ -123,6 +127,11 @@ def main():
     src = dict(src_width=Wd, src_height=Hd) if (Wc, Hc) != (Wd, Hd) else {}
     if (Wd, Hd) != (Win, Hin):
         src.update(in_width=Win, in_height=Hin, scale_filter=int(a.resize_filter == "lanczos"))
+    seg_map = None
+    if a.segment_map:
+        seg_map = np.fromfile(a.segment_map, np.uint8)
+        if seg_map.size != (Wc // 16) * (Hc // 16) or (seg_map.size and seg_map.max() > 3):
+            sys.exit(f"--segment-map {a.segment_map}: {(Wc // 16) * (Hc // 16)} bytes of 0..3 are one map of {Wc}x{Hc}")
     t0 = time.perf_counter()
     def make_encoder():
         enc = gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
@@ -130,6 +139,11 @@ def main():
                                       loop_filter_type=int(a.simple_filter))
         if a.denoise:
             enc.drv.set_denoise(a.denoise)
+        if a.aq:
+            enc.drv.set_segment_mode(2, a.aq)
+        if seg_map is not None:
+            enc.drv.set_segment_mode(1)
+            enc.drv.set_segment_map(seg_map)
         if a.deinterlace != "off":
             enc.drv.set_deinterlace(a.deinterlace, a.field)
         if fmt:

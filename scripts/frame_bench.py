@@ -30,6 +30,7 @@ ap.add_argument("--window-pitch", type=int, default=0, metavar="P", help="the de
 ap.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=0, help="the device-resident frames are stored turned back by this many degrees and are turned clockwise on the device (vp8drv_set_source_orientation): what k_orient_b costs; the coded bytes do not change")
 ap.add_argument("--mirror", action="store_true", help="... behind a left-right flip")
 ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the frame analysis record of every frame (vp8drv_set_analysis): what k_analyse_src_b and k_analyse_mb_b cost")
+ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation at strength N (vp8drv_set_segment_mode, mode 2): what k_aq_map_b + k_aq_seg_b cost, and with one stream the mapped macroblock kernel next to the default's in the same run")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -110,6 +111,9 @@ if pitch:
 if a.analysis:
     for d in drvs:
         d.set_analysis(True)
+if a.aq:
+    for d in drvs:
+        d.set_segment_mode(2, a.aq)
 sizes = [0] * a.streams
 
 def work(k, n, emit):
@@ -163,6 +167,23 @@ if a.streams == 1:   # the input side by HIP events: the pack launch, with k_con
     ms, n = d.hip.profile_read().get("pack", (0.0, 0))
     d.hip.profile_enable([])
     print(f"input side ({a.source_format or 'i420'}), {n} timed launches over 32 frames: {ms / 32 * 1e3:.2f} us per frame")
+if a.aq and a.streams == 1:   # k_mb_p_map next to k_mb_p, and the input side without the map's launches: the same process, HIP events
+    d = drvs[0]
+
+    def stage_us(name):
+        d.hip.synchronize()
+        d.hip.profile_enable([name])
+        work(0, 32, False)
+        ms, n = d.hip.profile_read().get(name, (0.0, 0))
+        d.hip.profile_enable([])
+        return ms / max(n, 1) * 1e3, n
+    mapped, n_on = stage_us("mb")
+    d.set_segment_mode(0)
+    plain, n_off = stage_us("mb")
+    pack_off, _ = stage_us("pack")
+    d.set_segment_mode(2, a.aq)
+    print(f"macroblock kernel, mapped (--aq {a.aq}) {mapped:.2f} us per launch over {n_on} launches, default {plain:.2f} us over {n_off}; "
+          f"input side without the map {pack_off:.2f} us per launch")
 if a.quality_stats:
     q = drvs[0].quality_summary()
     print(f"quality of stream 0 over {q.frames} frames: PSNR overall {q.psnr_all:.3f} dB, avg {q.psnr_avg:.3f} dB, SSIM {q.ssim_all:.5f}")

@@ -1,7 +1,7 @@
 // y4m_to_ivf.cpp -- the reference's program with the path swapped in, as a complete C++ user of the C ABI: YUV4MPEG2 in,
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
-//              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
+//              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
 //              [-input-format NAME] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
 // -crop W:H:X:Y (ffmpeg's order): the Y4M header gives the SURFACE, the crop the window of it that is the frame (vp8drv_set_source_window:
 // W, H, X, Y even; the pitch is the surface's tight pitch) and so the size that comes in; the whole surface is read from the file, only
@@ -22,6 +22,8 @@
 // The format of the frames is the header's C tag (vp8host_y4m_colourspace): C420* files are I420, C422, C444, C420p10, C422p10 and
 // C444p10 files are converted on the device (vp8drv_set_source_format), any other colourspace is refused.  -input-format NAME (i420,
 // nv12, i422, i444, p010, i010, i210, i410) says it instead of the tag: for frames the header cannot describe (NV12, P010).
+// -aq N: variance-adaptive quantisation of the inter frames at strength N = 1, 2, 3 (vp8drv_set_segment_mode, mode 2; 0 = off): flat
+// macroblocks take the finer segments of the quantiser ladder, busy ones the coarser.
 // -denoise N: temporal noise reduction of the source frames on the device, N = 1, 2, 3 (vp8drv_set_denoise; 0 = off); the share of
 // macroblocks it filtered is printed at the end, next to -psnr's summary.
 // -resize: the Y4M header gives the size of the frames that come in, WxH (even, not above it) the picture that is coded: the frames are
@@ -55,6 +57,7 @@ int main(int argc, char **argv) {
     cfg.overlap_filter = 1;
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     int denoise = 0;         // -denoise
+    int aq = 0;              // -aq
     int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     int32_t format = -1;     // -input-format (-1: the header's C tag)
     int crop[4] = {0, 0, 0, 0};     // -crop: W, H, X, Y (W == 0: the whole surface)
@@ -76,6 +79,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-simple-filter")) cfg.loop_filter_type = 1;   // RFC 6386 section 15.2
         else if (!strcmp(argv[i], "-psnr")) cfg.quality_stats = 1;               // PSNR / SSIM summary on stderr
         else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
+        else if (!strcmp(argv[i], "-aq")) aq = atoi(val());
         else if (!strcmp(argv[i], "-analysis")) analysis_path = val();
         else if (!strcmp(argv[i], "-deinterlace")) {
             const char *f = val(), *colon = strchr(f, ':');
@@ -167,6 +171,7 @@ int main(int argc, char **argv) {
     vp8drv *drv = nullptr;
     CK(vp8drv_create(&drv, Wc, Hc, 0, &cfg));
     if (denoise) CK(vp8drv_set_denoise(drv, denoise));
+    if (aq) CK(vp8drv_set_segment_mode(drv, 2, aq));
     if (format) CK(vp8drv_set_source_format(drv, format));
     if (turns || mirror) CK(vp8drv_set_source_orientation(drv, turns, mirror));
     if (crop[0]) CK(vp8drv_set_source_window(drv, pitch, crop[2], crop[3]));

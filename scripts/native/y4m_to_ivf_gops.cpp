@@ -1,9 +1,10 @@
 // y4m_to_ivf_gops.cpp -- one YUV4MPEG2 file to one IVF file with its closed GOPs coded SIDE BY SIDE: the file-to-file form of what
 // bench.py's headline measures, as a complete C++ user of the C ABI.
 //   y4m_to_ivf_gops <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n]
-//                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos] [-denoise N]
+//                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
 //                   [-deinterlace field|adaptive[:top|bottom]]
 // (-deinterlace: as in y4m_to_ivf.cpp -- the history of adaptive restarts at every GOP's key frame, so a chunk sees what the serial program sees)
+// (-aq N: as in y4m_to_ivf.cpp -- the map depends on the current frame alone, so a chunk codes the frames the serial program codes)
 // (-denoise N: as in y4m_to_ivf.cpp -- the history restarts at every GOP's key frame, so a chunk sees the frames the serial program sees)
 // (-resize: as in y4m_to_ivf.cpp -- frames of the file's size in, scaled down to WxH on the device, one launch per batch step)
 // A key frame resets every reference (intra_part.h:1091-1098, inter_part.h:35-50), so the frames [k g, (k + 1) g) of a run with
@@ -42,6 +43,7 @@ int main(int argc, char **argv) {
     int in_flight = 48, batch = 6;
     int rw = 0, rh = 0;      // -resize: the size of the coded picture (0 = the file's)
     int denoise = 0;         // -denoise
+    int aq = 0;              // -aq
     int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
@@ -57,6 +59,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-chunks")) in_flight = atoi(val());
         else if (!strcmp(argv[i], "-batch")) batch = atoi(val());
         else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
+        else if (!strcmp(argv[i], "-aq")) aq = atoi(val());
         else if (!strcmp(argv[i], "-deinterlace")) {
             const char *f = val(), *colon = strchr(f, ':');
             const size_t len = colon ? (size_t)(colon - f) : strlen(f);
@@ -135,6 +138,7 @@ int main(int argc, char **argv) {
     std::vector<vp8drv_batch *> bat((size_t)nbatches, nullptr);
     for (int j = 0; j < in_flight; ++j) {
         CK(vp8drv_create(&drv[j], Wc, Hc, 0, &cfg));
+        if (aq) CK(vp8drv_set_segment_mode(drv[j], 2, aq));      // (before the batch is made too)
         if (denoise) CK(vp8drv_set_denoise(drv[j], denoise));      // (before the batch is made: its members must agree)
         if (deint) CK(vp8drv_set_deinterlace(drv[j], deint, field));
         CK(vp8hip_reserve_frame_path_dense(vp8drv_context(drv[j])));      // frame t + 1 is started before frame t's bytes are taken: no frame is ever coded twice

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
-    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_deinterlace", "vp8hip_deinterlace_restart", "vp8hip_deinterlace_result", "vp8host_deinterlace_frame", "vp8host_y4m_interlace", "vp8drv_set_deinterlace", "vp8drv_get_deinterlace_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_set_source_window", "vp8hip_set_source_orientation", "vp8host_source_window", "vp8host_window_frame", "vp8host_orient_frame", "vp8drv_set_source_window", "vp8drv_set_source_orientation", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
+    "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_deinterlace", "vp8hip_deinterlace_restart", "vp8hip_deinterlace_result", "vp8host_deinterlace_frame", "vp8host_y4m_interlace", "vp8drv_set_deinterlace", "vp8drv_get_deinterlace_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_segment_mode", "vp8hip_segment_mode", "vp8hip_set_segment_map_device", "vp8hip_upload_segment_map", "vp8hip_download_segment_map", "vp8host_aq_segment_map", "vp8host_aq_segment", "vp8drv_set_segment_mode", "vp8drv_set_segment_map", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_set_source_window", "vp8hip_set_source_orientation", "vp8host_source_window", "vp8host_window_frame", "vp8host_orient_frame", "vp8drv_set_source_window", "vp8drv_set_source_orientation", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
@@ -530,6 +530,22 @@ class LumaAnalysis(C.Structure):
                 ("have_prev", C.c_int32)]
 
 
+def aq_segment_map(luma, strength: int, width: int | None = None):
+    """vp8host_aq_segment_map: the variance-adaptive segment map in plain C++ (include/vp8hip_host.h) on a luma plane whose rows are
+    luma.shape[1] bytes apart; width (default: the row length) is the coded width.  Returns (map, e), uint8 per macroblock."""
+    lib = load_library()
+    lib.vp8host_aq_segment_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    luma = np.ascontiguousarray(luma, np.uint8)
+    h, stride = luma.shape
+    w = stride if width is None else int(width)
+    mbs = max(w // 16, 0) * max(h // 16, 0)
+    m, e = np.zeros(max(mbs, 1), np.uint8), np.zeros(max(mbs, 1), np.uint8)
+    rc = lib.vp8host_aq_segment_map(luma.ctypes.data, stride, w, h, int(strength), m.ctypes.data, e.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"vp8host_aq_segment_map({w}x{h}, stride {stride}, strength {strength}) refused")
+    return m[:mbs], e[:mbs]
+
+
 def analyse_luma(cur, prev=None) -> dict:
     """vp8host_analyse_luma: the source side of the analysis record in plain C++ on tight luma planes of the coded size"""
     lib = load_library()
@@ -1008,6 +1024,23 @@ class NativeDriver:
             raise Vp8HipError(f"vp8drv_get_frame_analysis: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
         return a
 
+    def set_segment_mode(self, mode: int, strength: int = 0) -> None:
+        """vp8drv_set_segment_mode: 0 off, 1 the caller's segment map, 2 variance-adaptive at strength 1..3 (inter frames only)"""
+        self.lib.vp8drv_set_segment_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.lib.vp8drv_set_segment_mode(self.h, int(mode), int(strength))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_segment_mode({mode}, {strength}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_segment_map(self, seg_map) -> None:
+        """vp8drv_set_segment_map: mode 1's map, one byte 0..3 per macroblock in raster order, in force until replaced"""
+        m = np.ascontiguousarray(seg_map, np.uint8).reshape(-1)
+        if m.size != self.hip.mbs:
+            raise ValueError(f"a segment map has one byte per macroblock: {self.hip.mbs}, not {m.size}")
+        self.lib.vp8drv_set_segment_map.argtypes = [C.c_void_p, C.c_void_p]
+        rc = self.lib.vp8drv_set_segment_map(self.h, m.ctypes.data)
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_segment_map: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
     def set_quantizer(self, qi_min: int, qi_max: int) -> None:
         """vp8drv_set_quantizer: both quantizer ladders made again from this pair, from the next frame coded on"""
         self.lib.vp8drv_set_quantizer.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1411,6 +1444,47 @@ class Vp8Hip:
         without a history"""
         self.lib.vp8hip_set_analysis.argtypes = [C.c_void_p, C.c_int]
         self._chk(self.lib.vp8hip_set_analysis(self.h, int(bool(on))), "set_analysis")
+
+    def set_segment_mode(self, mode: int, strength: int = 0):
+        """vp8hip_set_segment_mode: 0 off, 1 the caller's segment map, 2 variance-adaptive at strength 1..3 (include/vp8hip.h)"""
+        self.lib.vp8hip_set_segment_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.lib.vp8hip_set_segment_mode(self.h, int(mode), int(strength))
+        if rc != 0:
+            raise Vp8HipError(f"set_segment_mode({mode}, {strength}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def segment_mode(self):
+        """vp8hip_segment_mode: (mode, strength) in force"""
+        a, b = C.c_int(), C.c_int()
+        self.lib.vp8hip_segment_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self._chk(self.lib.vp8hip_segment_mode(self.h, C.byref(a), C.byref(b)), "segment_mode")
+        return a.value, b.value
+
+    def upload_segment_map(self, seg_map):
+        """vp8hip_upload_segment_map: mode 1's map from host memory, one byte 0..3 per macroblock, in force until replaced"""
+        m = np.ascontiguousarray(seg_map, np.uint8).reshape(-1)
+        if m.size != self.mbs:
+            raise ValueError(f"a segment map has one byte per macroblock: {self.mbs}, not {m.size}")
+        self.lib.vp8hip_upload_segment_map.argtypes = [C.c_void_p, C.c_void_p]
+        rc = self.lib.vp8hip_upload_segment_map(self.h, m.ctypes.data)
+        if rc != 0:
+            raise Vp8HipError(f"upload_segment_map: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_segment_map_device(self, d_map):
+        """vp8hip_set_segment_map_device: the same from device memory (a pointer as vp8hip_device_alloc returns it)"""
+        self.lib.vp8hip_set_segment_map_device.argtypes = [C.c_void_p, C.c_void_p]
+        rc = self.lib.vp8hip_set_segment_map_device(self.h, _ptr(d_map))
+        if rc != 0:
+            raise Vp8HipError(f"set_segment_map_device: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def download_segment_map(self, with_e: bool = False):
+        """vp8hip_download_segment_map: the map in force for the current frame (and, with_e in mode 2, e of the rule): uint8 per macroblock"""
+        m = np.zeros(self.mbs, np.uint8)
+        e = np.zeros(self.mbs, np.uint8) if with_e else None
+        self.lib.vp8hip_download_segment_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = self.lib.vp8hip_download_segment_map(self.h, m.ctypes.data, e.ctypes.data if with_e else None)
+        if rc != 0:
+            raise Vp8HipError(f"download_segment_map: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return (m, e) if with_e else m
 
     def analysis_restart(self):
         """vp8hip_analysis_restart: the next frame taken in has no history (have_prev = 0)"""

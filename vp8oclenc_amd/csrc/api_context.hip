@@ -464,6 +464,7 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     c->dn.release();
     c->di.release();
     c->an.release();      // (an_src and an_mb are parts of it)
+    c->seg_buf.release();
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
 }

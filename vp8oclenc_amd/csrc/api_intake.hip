@@ -1,5 +1,5 @@
 // api_intake.hip -- how a frame becomes a context's current frame: the source size, scaling, format and colour setters, the staging
-// buffers, the stage order (take_frames: window, convert, deinterlace, orient, scale or pack, denoise, analysis -- the one place that knows it), and the
+// buffers, the stage order (take_frames: window, convert, deinterlace, orient, scale or pack, denoise, analysis, segment map -- the one place that knows it), and the
 // single-context ways in (vp8hip_set_current_device, vp8hip_upload_current, vp8hip_prefetch_current).  A batch's ways in are api_batch.hip's;
 // they end in take_frames too.  Replaces the uploads of vp8enc.cpp:386-401.
 #include "vp8hip_ctx.h"
@@ -173,6 +173,16 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
         for (int i = 0; i < n; ++i)
             if (analysis_src_item(m[i], s, an[na])) ++na;
         launch_analyse_src_batch(s, an, na);
+    }
+    {   // vp8hip_set_segment_mode, mode 2: the members' variance-adaptive maps, last (same_intake: all members or none)
+        AqItem aq[MAX_BATCH];
+        int nq = 0;
+        for (int i = 0; i < n; ++i)
+            if (aq_item(m[i], aq[nq])) ++nq;
+        if (nq) {      // (two launches of the input side's stage, each with its own pair of events)
+            { Timed t(c0, VP8HIP_K_PACK); launch_aq_map_batch(s, aq, nq); }
+            { Timed t(c0, VP8HIP_K_PACK); launch_aq_seg_batch(s, aq, nq, c0->seg_strength); }
+        }
     }
     return VP8HIP_OK;
 }

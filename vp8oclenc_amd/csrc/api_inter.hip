@@ -47,7 +47,7 @@ RefSet ref_set(const vp8hip_ctx *c, int use_last, int use_golden, int use_altref
 // parameter scan rides along if it is still waiting -- the caller that launches with it clears scan_deferred
 CodingItem coding_item(const vp8hip_ctx *c, int use_golden, int use_altref) {
     return CodingItem{&c->cur, ref_set(c, 1, use_golden, use_altref), &c->nets, c->recon >= 0 ? &c->frames[c->recon].f : nullptr,
-                      &c->out, c->d_sd, c->scan_deferred ? &c->scan_req : nullptr};
+                      &c->out, c->d_sd, c->scan_deferred ? &c->scan_req : nullptr, segment_map_in_force(c)};
 }
 
 unsigned long long *s2_clock_words(const vp8hip_ctx *c) { return reinterpret_cast<unsigned long long *>(c->d_progress + S2_CLOCK_WORD); }
@@ -232,7 +232,7 @@ int vp8hip_inter_transform(vp8hip_ctx *c, int prev_is_golden, int prev_is_altref
     {
         Timed t(c, VP8HIP_K_MB);   // select_reference + pack_8x8_into_16x16 run inside
         const CodingItem it = coding_item(c, use_golden, use_altref);
-        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0);
+        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0, c->seg_mode != 0);
     }
     recon_made(c, false);
     HIPCHK(c, hipGetLastError());
@@ -264,7 +264,7 @@ int vp8hip_inter_finish(vp8hip_ctx *c, int use_golden, int use_altref) {
     {
         Timed t(c, VP8HIP_K_MB);
         const CodingItem it = coding_item(c, use_golden, use_altref);
-        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0);
+        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0, c->seg_mode != 0);
     }
     recon_made(c, false);
     HIPCHK(c, hipGetLastError());

@@ -625,8 +625,12 @@ __device__ __forceinline__ int wht_roundtrip_row(int x, int L, int base_bytes, i
     return (gather_col(gather_row(xq, c), r) + 3) >> 3;
 }
 
-template <bool CONFORMANT>
-__device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MBShare *s_x) {
+// MAPPED (vp8hip_set_segment_mode): ONE pass, in the segment the macroblock's byte of a.seg_map names (no map: 3) -- the default's first
+// pass with `seg` given instead of 3.  The eight macroblocks of a workgroup may hold eight different segments: seg is a per-lane value
+// here and nothing about it is workgroup-uniform.  The unmapped instantiations take MBArgs and compile to what they compiled to.
+struct MBArgsMapped : MBArgs { const uint8_t *seg_map; };
+template <bool CONFORMANT, bool MAPPED = false, class Args = MBArgs>
+__device__ __forceinline__ void mb_body_packed(const Args &a, MBTileP *s_t, MBShare *s_x) {
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), wl = threadIdx.x & 63;
     const bool luma = w < 2;
     const int g = luma ? w * 4 + (wl >> 4) : wl >> 3;          // the macroblock's slot in the workgroup
@@ -733,11 +737,13 @@ __device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MB
     __syncthreads();
 
     float ssim = -2.0f;  // pack_8x8_into_16x16, :1352
-    int seg_final = a.o_seg[mb];
+    int seg_first = 3;
+    if constexpr (MAPPED) seg_first = a.seg_map ? a.seg_map[mb] & 3 : 3;
+    int seg_final = MAPPED ? seg_first : a.o_seg[mb];
     int nz_y = 0, nz_c = 0;    // prepare_filter_mask's count, luma and chroma blocks, from the last pass this macroblock ran
     const uint32_t dc_mask = (luma && parts == 0) ? 0xffff0000u : 0xffffffffu;   // nz_zigzag
     bool any_pass = false;
-    for (int seg = 3, round = 0; seg >= 0; --seg, ++round) {        // inter_part.h:329
+    for (int seg = seg_first, round = 0; seg >= 0; --seg, ++round) {        // inter_part.h:329
         const bool act = !(ssim > a.ssim_target);                   // dct4x4 gate, :1391
         if (act) {
             any_pass = true;
@@ -847,6 +853,7 @@ __device__ __forceinline__ void mb_body_packed(const MBArgs &a, MBTileP *s_t, MB
         __syncthreads();
         const float4 mt = *reinterpret_cast<const float4 *>(s_x->metric[g]);
         ssim = __fdiv_rn(__fadd_rn(__fadd_rn(mt.x, mt.y), mt.z), 3.0f);
+        if constexpr (MAPPED) break;                 // the one pass
     }
 
     // ---- results -------------------------------------------------------------------------------
@@ -889,6 +896,17 @@ __global__ __launch_bounds__(192, 2) void k_mb_p_conformant(BatchOf<MBArgs> b) {
     __shared__ __attribute__((aligned(16))) MBShare s_x;
     mb_body_packed<true>(b.item[blockIdx.z], s_t, &s_x);
 }
+// the mapped forms (vp8hip_set_segment_mode): the packed form only
+__global__ __launch_bounds__(192, 2) void k_mb_p_map(BatchOf<MBArgsMapped> b) {
+    __shared__ __attribute__((aligned(16))) MBTileP s_t[8];
+    __shared__ __attribute__((aligned(16))) MBShare s_x;
+    mb_body_packed<false, true>(b.item[blockIdx.z], s_t, &s_x);
+}
+__global__ __launch_bounds__(192, 2) void k_mb_p_map_conformant(BatchOf<MBArgsMapped> b) {
+    __shared__ __attribute__((aligned(16))) MBTileP s_t[8];
+    __shared__ __attribute__((aligned(16))) MBShare s_x;
+    mb_body_packed<true, true>(b.item[blockIdx.z], s_t, &s_x);
+}
 static bool mb_packed() {
     static const bool on = [] { const char *v = getenv("VP8HIP_MB_PACKED"); return !(v && v[0] == '0'); }();
     return on;
@@ -923,8 +941,21 @@ static bool mb_skip() {
     return skip;   // timing experiment only (what the frame costs without this kernel); never set in production
 }
 
-void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant) {
-    static_assert(sizeof(BatchOf<MBArgs>) <= 4096, "the batch travels in the kernel arguments");
+void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant, bool mapped) {
+    static_assert(sizeof(BatchOf<MBArgs>) <= 4096 && sizeof(BatchOf<MBArgsMapped>) <= 4096, "the batch travels in the kernel arguments");
+    if (mapped) {      // (VP8HIP_MB_PACKED=0 has no mapped form: the packed one)
+        BatchOf<MBArgsMapped> b;
+        b.n = n;
+        for (int i = 0; i < n; ++i) {
+            static_cast<MBArgs &>(b.item[i]) = mb_args(items[i], ssim_target, mbw, mbh);
+            b.item[i].seg_map = items[i].seg_map;
+        }
+        if (mb_skip()) return;
+        const dim3 grid((b.item[0].mbs + 7) / 8, 1, n);
+        if (conformant) VP8_LAUNCH(k_mb_p_map_conformant, grid, dim3(192), 0, s, b);
+        else VP8_LAUNCH(k_mb_p_map, grid, dim3(192), 0, s, b);
+        return;
+    }
     BatchOf<MBArgs> b;
     b.n = n;
     for (int i = 0; i < n; ++i) b.item[i] = mb_args(items[i], ssim_target, mbw, mbh);

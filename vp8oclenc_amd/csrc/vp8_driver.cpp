@@ -467,6 +467,12 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
             (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format || drv[i]->colour != drv[0]->colour ||
             drv[i]->analysis != drv[0]->analysis || drv[i]->deinterlace != drv[0]->deinterlace || drv[i]->field != drv[0]->field)
             return VP8HIP_ERR_ARG;
+        {   // vp8drv_set_segment_mode: one mode and strength (the maps are the members' own)
+            int m0 = 0, s0 = 0, mi = 0, si = 0;
+            vp8hip_segment_mode(drv[0]->hip, &m0, &s0);
+            vp8hip_segment_mode(drv[i]->hip, &mi, &si);
+            if (mi != m0 || si != s0) return VP8HIP_ERR_ARG;
+        }
         ctx[i] = drv[i]->hip;
     }
     vp8drv_batch *b = new (std::nothrow) vp8drv_batch();
@@ -699,6 +705,21 @@ int vp8drv_set_analysis(vp8drv *d, int on) {
     DRV_CHK(vp8hip_set_analysis(d->hip, on));
     d->analysis = on != 0;
     return VP8HIP_OK;
+}
+
+// vp8hip_set_segment_mode for the frame loop: inter frames are coded in the mode from the next frame taken in on, key frames as ever
+int vp8drv_set_segment_mode(vp8drv *d, int mode, int strength) {
+    if (!d || mode < 0 || mode > 2 || (mode == 2 && (strength < 1 || strength > 3))) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    return vp8hip_set_segment_mode(d->hip, mode, strength);
+}
+
+// the caller's map of mode 1, in force until replaced (the members of a batch each have their own)
+int vp8drv_set_segment_map(vp8drv *d, const uint8_t *host_map) {
+    if (!d || !host_map) return VP8HIP_ERR_ARG;
+    { const int rc = resolve(d); if (rc < 0) return rc; }      // (a frame sent back is coded again under the map it was coded under)
+    return vp8hip_upload_segment_map(d->hip, host_map);
 }
 
 // the record of the frame just made final: its verdict first (a frame coded again as a key frame has the key frame's coding side)

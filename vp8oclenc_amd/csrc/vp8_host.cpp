@@ -698,6 +698,45 @@ extern "C" int vp8host_analyse_luma(const uint8_t *cur, const uint8_t *prev, int
     return 0;
 }
 
+// The variance-adaptive segment map in plain C++ (include/vp8hip_host.h has the rule; k_aq_map_b and k_aq_seg_b are the device's form).
+extern "C" int vp8host_aq_segment(int e, int E, int W) {
+    if (W <= 0) return 2;
+    const int d = e - E;
+    const int q = d >= 0 ? d / W : -((-d + W - 1) / W);
+    const int s = 2 + q;
+    return s < 0 ? 0 : (s > 3 ? 3 : s);
+}
+
+extern "C" int vp8host_aq_segment_map(const uint8_t *luma, int stride, int width, int height, int strength, uint8_t *map_out, uint8_t *e_out) {
+    if (!luma || !map_out || width < 16 || height < 16 || (width & 15) || (height & 15) || stride < width || strength < 1 || strength > 3) return -1;
+    const int mbw = width / 16, mbs = mbw * (height / 16);
+    const int W = strength == 1 ? 24 : (strength == 2 ? 16 : 12);
+    int64_t total = 0;      // (e waits in map_out for the frame's mean: no allocation)
+    for (int mb = 0; mb < mbs; ++mb) {
+        const uint8_t *o = luma + (size_t)(mb / mbw) * 16 * (size_t)stride + (size_t)(mb % mbw) * 16;
+        uint32_t s = 0, ss = 0;
+        for (int y = 0; y < 16; ++y)
+            for (int x = 0; x < 16; ++x) {
+                const uint32_t v = o[(size_t)y * (size_t)stride + (size_t)x];
+                s += v;
+                ss += v * v;
+            }
+        const uint32_t n = 256u * ss - s * s + 1u;
+        int p = 0;
+        while ((n >> p) > 1u) ++p;
+        const uint32_t frac = p >= 3 ? (n >> (p - 3)) & 7u : (n << (3 - p)) & 7u;
+        map_out[mb] = (uint8_t)(8 * p + (int)frac);
+        total += map_out[mb];
+    }
+    const int E = (int)(total / mbs);
+    for (int mb = 0; mb < mbs; ++mb) {
+        const uint8_t e = map_out[mb];
+        if (e_out) e_out[mb] = e;
+        map_out[mb] = (uint8_t)vp8host_aq_segment(e, E, W);
+    }
+    return 0;
+}
+
 // The geometry of the input side in plain C++ (include/vp8hip_host.h has the rule): the window of a surface, and quarter turns.
 extern "C" int vp8host_source_window(int format, int width, int height, int x, int y, const int32_t pitch[3], size_t offset[3],
                                      int32_t row_bytes[3], int32_t rows[3]) {

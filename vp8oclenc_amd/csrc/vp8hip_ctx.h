@@ -8,7 +8,7 @@
 //
 // Units: api_context.hip (create / destroy, surfaces, parameters, stream ordering, the record wait, downloads, device memory),
 // api_intake.hip (how a frame becomes current: source size / scaling / format / colour, staging, the stage order; upload, prefetch, set_current_device),
-// api_geometry.hip, api_deinterlace.hip, api_denoise.hip, api_analysis.hip, api_quality.hip (a stage each: its items, its setters, its results),
+// api_geometry.hip, api_deinterlace.hip, api_denoise.hip, api_analysis.hip, api_segment.hip, api_quality.hip (a stage each: its items, its setters, its results),
 // api_inter.hip (inter path, check_SSIM, key frames, loop filter), api_entropy.hip (coefficient + header entropy stage, frames out),
 // api_batch.hip (vp8hip_batch_*), api_shard.hip (export / import, RCCL: vp8hip_shard_*, vp8hip_group_*), api_profile.hip (timers, debug taps).
 #ifndef VP8HIP_CTX_H
@@ -201,6 +201,15 @@ struct vp8hip_ctx {
     RecordView<vp8::AnalysisMbMirror> an_mb;
     uint32_t an_src_launches = 0;
     int an_src_frame[2] = {-1, -1}, an_mb_frame = -1;
+    // vp8hip_set_segment_mode: 0 off, 1 the caller's map, 2 variance-adaptive at seg_strength.  seg_buf, made when the mode first leaves 0
+    // (segment_buffers): the two sum words of k_aq_map_b (at 0 and 128: zero at rest), then five arrays of round256(mbs) bytes -- e and
+    // the map of mode 2 for each of the two current-frame slots (cur_count & 1, as the analysis records: a frame may be taken in while
+    // the one before it is coded), and the caller's map.  aq_frame: the frame each slot's map was made for; seg_map_set: a caller's map
+    // is in force.
+    int seg_mode = 0, seg_strength = 0;
+    bool seg_map_set = false;
+    int aq_frame[2] = {-1, -1};
+    DeviceBuf seg_buf;
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out
     // vp8hip_set_quality_stats: the record (quality.d: the state, the ticket and the per-wave partials of k_quality)
@@ -442,6 +451,7 @@ inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what
            (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level &&     // (and one denoiser level)
            a->di_mode == b->di_mode && a->di_keep == b->di_keep &&                                  // (one deinterlacer mode and parity)
            a->an_on == b->an_on &&                                                                  // (analysis on for all or for none)
+           a->seg_mode == b->seg_mode && a->seg_strength == b->seg_strength &&                      // (one segment mode and strength)
            a->win_on == b->win_on && (!a->win_on || (a->win_pitch[0] == b->win_pitch[0] && a->win_pitch[1] == b->win_pitch[1] && a->win_pitch[2] == b->win_pitch[2] &&
                                                      a->win_x == b->win_x && a->win_y == b->win_y)) &&      // (one window)
            a->or_turns == b->or_turns && a->or_mirror == b->or_mirror;                              // (one orientation)
@@ -515,6 +525,12 @@ bool analysis_src_item(vp8hip_ctx *c, hipStream_t s, AnalysisSrcItem &it);
 bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it);
 void analysis_after_filter(vp8hip_ctx *c, hipStream_t s);
 void batch_analysis(vp8hip_batch *b, const int *active);
+// ---- api_segment.hip ----
+// The variance-adaptive map of the frame just taken into c->cur, at the end of the intake chain (take_frames).  false: not mode 2,
+// nothing to launch.  segment_map_in_force: what the mapped k_mb reads for the current frame -- the caller's map in mode 1, the
+// current slot's map in mode 2, nullptr (segment 3 everywhere) without one, and in mode 0.
+bool aq_item(vp8hip_ctx *c, AqItem &it);
+const uint8_t *segment_map_in_force(const vp8hip_ctx *c);
 // ---- api_quality.hip ----
 bool quality_item(vp8hip_ctx *c, const Frame &rec, hipStream_t s, QualityArgs &a);   // false: stats off
 void quality_after_filter(vp8hip_ctx *c, const Frame &rec, hipStream_t s);           // the measurement behind the context's filter

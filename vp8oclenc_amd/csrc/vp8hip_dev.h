@@ -198,6 +198,12 @@ struct AnalysisMbItem {
 };
 void launch_analyse_src_batch(hipStream_t s, const AnalysisSrcItem *items, int n);
 void launch_analyse_mb_batch(hipStream_t s, const AnalysisMbItem *items, int n);
+// kernels_aq.hip: the variance-adaptive segment map (vp8hip_set_segment_mode, mode 2); the rule is include/vp8hip_host.h's.
+// k_aq_map_b: e of every macroblock of the coded luma just taken in, a byte each, and their sum added into `sum` (zero at rest);
+// k_aq_seg_b behind it turns them into `map`, a byte per macroblock, and leaves the word zero.  e and map are 256-byte aligned and whole multiples of 256 bytes long.
+struct AqItem { Plane cur; uint8_t *e, *map; uint32_t *sum; };
+void launch_aq_map_batch(hipStream_t s, const AqItem *items, int n);
+void launch_aq_seg_batch(hipStream_t s, const AqItem *items, int n, int strength);      // right behind it, on the same stream
 // kernels_convert.hip: source frames in another format than 8-bit I420 (vp8hip_set_source_format), made tight 8-bit I420 of the same
 // size IN FRONT of the pack or scale launch, which then reads dst as if the caller had handed it in; the rule is include/vp8hip_host.h's.
 // src: the format's planes (src[2] is not read for the two-plane formats, src[1] and src[2] for the packed ones, k_convert_packed_b).
@@ -242,6 +248,7 @@ struct LfCheck {
 };
 // One member's frame in the searches and k_mb.  recon, out, sd: k_mb's (a launch of the searches alone does not read them).
 // scan (or nullptr): the member's parameter scan still waiting for a launch to ride in (launch_search2_batch).
+// seg_map: the member's segment map, a byte per macroblock, for the mapped form of k_mb (nullptr there: segment 3 everywhere).
 struct CodingItem {
     const Frame *cur;
     RefSet refs;
@@ -250,6 +257,7 @@ struct CodingItem {
     const MBOut *out;
     const SegData *sd;
     const ScanRequest *scan;
+    const uint8_t *seg_map;
 };
 // One member's reconstruction in a loop filter launch.  launch_no counts the member's launches of THAT filter (the normal forms share
 // one count, the simple filter has its own); handoff: form 4's buffer; chk.on = 0: no check rides along.
@@ -268,7 +276,8 @@ void launch_search1_batch(hipStream_t s, const CodingItem *items, int n, int lev
 // carried (nothing to search, or the persistent form): the caller launches them on their own.
 bool launch_search2_batch(hipStream_t s, const CodingItem *items, int n, unsigned long long *clk = nullptr);   // clk: launch clock words (launch_clock_end) or nullptr
 // (one context: a batch of one -- the kernel is the same)
-void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant = false);
+// mapped: every macroblock is coded once, in the segment its member's seg_map names (vp8hip_set_segment_mode; the packed form only)
+void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant = false, bool mapped = false);
 void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh);
 void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh);
 void launch_auto_segments_batch(hipStream_t s, const ScanRequest *q, int n);

@@ -18,7 +18,8 @@ from . import api
 class InterPathDriver:
     def __init__(self, backend, width: int, height: int, gop_size: int = 150, altref_range: int = 5,
                  qi_min: int = 0, qi_max: int = 48, ssim_target: float = -1.0, download: bool = True,
-                 check_ssim: bool = True, device_intra: bool = True, ref_mask: int = 3):
+                 check_ssim: bool = True, device_intra: bool = True, ref_mask: int = 3,
+                 segment_mode: int = 0, segment_strength: int = 0, segment_map=None):
         self.be = backend
         self.W, self.H = width, height
         self.mbs = (width // 16) * (height // 16)
@@ -34,6 +35,12 @@ class InterPathDriver:
         self.key_frames = 0
         self.redone_as_key = 0
         self.last_key = None
+        # vp8hip_set_segment_mode (include/vp8hip.h): inter frames coded once per macroblock in the segment a map names.  The device
+        # backend only: the CPU oracle has no mapped pass (tests/segment_map_ref.py assembles its result from the oracle's stages)
+        if segment_mode:
+            self.be.set_segment_mode(segment_mode, segment_strength)
+        if segment_map is not None:
+            self.be.upload_segment_map(segment_map)
 
     def segments_for(self, y: np.ndarray, is_key: bool, is_altref: bool, update_filter: bool = False) -> np.ndarray:
         reductor, sharp = api.loopfilter_strength(y)
