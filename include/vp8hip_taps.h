@@ -68,6 +68,15 @@ int vp8hip_debug_download(vp8hip_ctx *ctx, int what, int ref, int level, void *d
 int vp8hip_debug_quality(vp8hip_ctx *ctx, int width, int height, const uint8_t *const src[3], const int32_t src_stride[3],
                          const uint8_t *const rec[3], const int32_t rec_stride[3], vp8hip_quality *q);
 
+/* The boolean coder proper (the four launches every partition, first partition and frame goes through) on the caller's bool strings:
+ * bools holds the strings of num_partitions (1..8) partitions one after another, nbools[p] entries each, an entry being
+ * probability | bit << 8 (probability 1..255; anything else is VP8HIP_ERR_ARG).  Partition p comes out at out + p * partition_step,
+ * sizes[p] bytes of it (bytes behind them are left alone; a partition longer than partition_step is VP8HIP_ERR_OVERFLOW); blocks.
+ * Runs in the coefficient scratch under the layout the product's own planning kernel gives the strings, enlarging the scratch as
+ * vp8hip_encode_coefficients does; touches nothing of the context but its stream and that scratch. */
+int vp8hip_debug_bool_code(vp8hip_ctx *ctx, const uint16_t *bools, const uint32_t *nbools, int num_partitions, int partition_step,
+                           uint8_t *out, int32_t *sizes);
+
 
 #ifdef __cplusplus
 }

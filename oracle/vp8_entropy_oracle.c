@@ -260,3 +260,12 @@ void vp8o_encode_coefficients(const int16_t *MB, const int32_t *MB_non_zero_coef
         partition_sizes[part] = (int32_t)e.count;
     }
 }
+
+/* ---- the boolean coder alone: one partition from a string of (probability | bit << 8) entries, through the put_bool / flush
+ * above.  out takes at most n * 7 / 8 + 5 bytes (a bool shifts at most seven bits out; the flush writes four bytes). ---- */
+int32_t vp8o_bool_code(const uint16_t *bools, uint32_t n, uint8_t *out) {
+    boolenc e = {out, 255, 0, 24, 0};
+    for (uint32_t i = 0; i < n; ++i) put_bool(&e, bools[i] & 255, bools[i] >> 8);
+    flush(&e);
+    return (int32_t)e.count;
+}

@@ -100,6 +100,9 @@ void vp8o_encode_coefficients(const int16_t *MB, const int32_t *MB_non_zero_coef
                               uint8_t *output, int32_t *partition_sizes, const uint8_t *third_context,
                               const uint32_t *coeff_probs, int mb_height, int mb_width, int num_partitions,
                               int partition_step);
+/* The boolean coder of encode_coefficients (:63-146) alone on one partition's string of n bools, each probability | bit << 8
+ * (probability 1..255); returns the partition's size.  out: n * 7 / 8 + 5 bytes at least. */
+int32_t vp8o_bool_code(const uint16_t *bools, uint32_t n, uint8_t *out);
 
 /* Host intra path (vp8_intra_oracle.c): src/intra_part.h and check_SSIM of src/vp8enc.cpp:231-263.  Planes have
  * stride = width; coeffs [MBs][25][16] (blocks 0..23 written, zigzag order); modes [MBs][16]; sd = 4 x 11 ints. */

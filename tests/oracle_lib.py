@@ -251,6 +251,17 @@ class Oracle:
         return np.ctypeslib.as_array(p, shape=(self.H >> level, self.W >> level)).copy()
 
 
+def oracle_bool_code(bools) -> bytes:
+    """One partition through the oracle's serial boolean coder (vp8o_bool_code): bools = uint16 sequence of probability | bit << 8."""
+    lib = Oracle.lib()
+    lib.vp8o_bool_code.argtypes = [np.ctypeslib.ndpointer(np.uint16, flags="C_CONTIGUOUS"), C.c_uint32, u8p]
+    lib.vp8o_bool_code.restype = C.c_int32
+    b = np.ascontiguousarray(bools, np.uint16).reshape(-1)
+    out = np.zeros(len(b) * 7 // 8 + 16, np.uint8)
+    n = lib.vp8o_bool_code(b if len(b) else np.zeros(1, np.uint16), len(b), out)
+    return out[:n].tobytes()
+
+
 def ref_stages() -> Stages | None:
     """The reference's own kernels (x86 build) or None when oracle/_ref was not built."""
     if not os.path.exists(REF_SO):

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "vp8hip_create", "vp8hip_destroy", "vp8hip_upload_current", "vp8hip_set_current_device", "vp8hip_upload_last",
     "vp8hip_set_last_device", "vp8hip_set_segments", "vp8hip_inter_transform", "vp8hip_download_results",
     "vp8hip_upload_mb_data", "vp8hip_upload_recon", "vp8hip_prepare_filter_mask", "vp8hip_loop_filter", "vp8hip_set_loop_filter_type",
-    "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality",
+    "vp8hip_set_quality_stats", "vp8hip_quality_result", "vp8hip_quality_summary", "vp8hip_batch_quality", "vp8drv_get_frame_quality", "vp8drv_get_quality_summary", "vp8hip_debug_quality", "vp8hip_debug_bool_code",
     "vp8hip_download_last", "vp8hip_synchronize", "vp8hip_stream", "vp8hip_last_hip_error", "vp8hip_status_string",
     "vp8hip_profile_enable", "vp8hip_profile_read", "vp8hip_debug_download", "vp8hip_count_probs", "vp8hip_encode_coefficients", "vp8hip_loopfilter_strength", "vp8hip_chroma_change", "vp8hip_chroma_change_async", "vp8hip_chroma_change_result", "vp8hip_auto_segments", "vp8hip_get_segments",
     "vp8hip_intra_transform", "vp8hip_check_ssim", "vp8hip_download_intra", "vp8hip_conformant_stream", "vp8hip_set_source_size", "vp8hip_set_source_scaling", "vp8host_scale_taps", "vp8hip_set_denoise", "vp8hip_denoise_restart", "vp8hip_denoise_result", "vp8host_denoise_frame", "vp8drv_set_denoise", "vp8drv_get_denoise_stats", "vp8hip_set_deinterlace", "vp8hip_deinterlace_restart", "vp8hip_deinterlace_result", "vp8host_deinterlace_frame", "vp8host_y4m_interlace", "vp8drv_set_deinterlace", "vp8drv_get_deinterlace_stats", "vp8hip_set_analysis", "vp8hip_analysis_restart", "vp8hip_analysis_result", "vp8host_analyse_luma", "vp8drv_set_analysis", "vp8drv_get_frame_analysis", "vp8drv_set_quantizer", "vp8drv_get_quantizer", "vp8hip_set_segment_mode", "vp8hip_segment_mode", "vp8hip_set_segment_map_device", "vp8hip_upload_segment_map", "vp8hip_download_segment_map", "vp8host_aq_segment_map", "vp8host_aq_segment", "vp8drv_set_segment_mode", "vp8drv_set_segment_map", "vp8hip_set_source_format", "vp8drv_set_source_format", "vp8host_source_plane_bytes", "vp8host_convert_frame", "vp8host_y4m_colourspace", "vp8hip_set_source_colour", "vp8drv_set_source_colour", "vp8host_convert_frame_colour", "vp8host_colour_coefficients", "vp8hip_set_source_window", "vp8hip_set_source_orientation", "vp8host_source_window", "vp8host_window_frame", "vp8host_orient_frame", "vp8drv_set_source_window", "vp8drv_set_source_orientation", "vp8hip_abi_version", "vp8hip_experiments_compiled_in", "vp8hip_batch_prep_mode", "vp8hip_device_count", "vp8hip_device_alloc", "vp8hip_device_free", "vp8hip_device_upload", "vp8hip_device_download", "vp8hip_device_synchronize", "vp8hip_device_mem_info", "vp8hip_device_pci_bus_id", "vp8hip_runtime_version", "vp8hip_shard_unique_id", "vp8hip_shard_init", "vp8hip_shard_rank", "vp8hip_shard_world", "vp8hip_shard_share_search", "vp8hip_shard_share_last", "vp8hip_shard_max", "vp8hip_encode_header", "vp8hip_encode_frame",
@@ -1581,6 +1581,24 @@ class Vp8Hip:
         self._chk(self.lib.vp8hip_encode_coefficients(self.h, probs.ctypes.data, num_partitions, step, out.ctypes.data,
                                                       sizes.ctypes.data), "encode_coefficients")
         return [out[p * step: p * step + sizes[p]].copy() for p in range(num_partitions)]
+
+    def debug_bool_code(self, strings, partition_step: int = 0, out=None):
+        """vp8hip_debug_bool_code (test tap): the boolean coder on bool strings, one per partition, each a uint16 sequence of
+        probability | bit << 8: list of partition byte strings.  out (uint8[len(strings) * partition_step]), where given, is the
+        buffer the partitions are written into."""
+        strings = [np.ascontiguousarray(b, np.uint16).reshape(-1) for b in strings]
+        P = len(strings)
+        n = np.array([len(b) for b in strings], np.uint32)
+        flat = np.ascontiguousarray(np.concatenate(strings + [np.zeros(1, np.uint16)]))
+        step = partition_step or (int(n.max(initial=0)) * 7 // 8 + 16)
+        if out is None:
+            out = np.zeros(P * step, np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= P * step
+        sizes = np.zeros(max(P, 1), np.int32)
+        self.lib.vp8hip_debug_bool_code.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.vp8hip_debug_bool_code(self.h, flat.ctypes.data, n.ctypes.data, P, step, out.ctypes.data, sizes.ctypes.data),
+                  "debug_bool_code")
+        return [out[p * step: p * step + sizes[p]].tobytes() for p in range(P)]
 
     def download_last(self):
         W, H = self.W, self.H

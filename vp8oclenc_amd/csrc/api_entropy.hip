@@ -250,6 +250,56 @@ int vp8hip_encode_coefficients(vp8hip_ctx *c, const uint32_t *coeff_probs, int n
     return VP8HIP_OK;
 }
 
+// test tap (vp8hip_taps.h): the boolean coder proper on the caller's bool strings, laid into the coefficient scratch as k_ent_emit
+// leaves them (string after string), under the plan k_ent_plan itself makes of them
+int vp8hip_debug_bool_code(vp8hip_ctx *c, const uint16_t *bools, const uint32_t *nbools, int num_partitions, int partition_step,
+                           uint8_t *out, int32_t *sizes) {
+    USE_DEVICE(c);
+    if (!c || !nbools || !out || !sizes || partition_step < 4) return VP8HIP_ERR_ARG;
+    const int P = num_partitions;
+    if (P < 1 || P > ENT_MAX_PARTITIONS) return VP8HIP_ERR_ARG;
+    if (c->frame_pending || c->ent_pending) return VP8HIP_ERR_STATE;   // a frame's stage owns the scratch
+    uint32_t offs[ENT_MAX_PARTITIONS + 1];
+    uint64_t total = 0;
+    for (int p = 0; p < P; ++p) {
+        offs[p] = (uint32_t)total;
+        total += nbools[p];
+        if (total > (1u << 28)) return VP8HIP_ERR_ARG;
+    }
+    offs[P] = (uint32_t)total;
+    if (total && !bools) return VP8HIP_ERR_ARG;
+    for (uint64_t i = 0; i < total; ++i)
+        if ((bools[i] & 255u) == 0 || (bools[i] >> 8) > 1u) return VP8HIP_ERR_ARG;   // a probability is 1..255, a bit 0 or 1
+    int rc = ent_alloc(c);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    EntPlan plan;
+    for (;;) {
+        HIPCHK(c, hipMemcpyAsync(c->ent.offs, offs, sizeof(uint32_t) * (P + 1), hipMemcpyHostToDevice, s));
+        launch_bool_plan(s, c->ent, P);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&plan, c->ent.plan, sizeof(plan), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (!plan.overflow) break;
+        if ((rc = ent_grow(c)) != VP8HIP_OK) return rc;   // longer than the scratch: enlarge it (VP8HIP_ERR_OVERFLOW at its maximum)
+    }
+    if (total) HIPCHK(c, hipMemcpyAsync(c->ent.bools, bools, sizeof(uint16_t) * total, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->ent.acc, 0, sizeof(uint64_t) * plan.word_base[P], s));   // (k_ent_emit's other job)
+    launch_bool_code(s, c->ent, P);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&plan, c->ent.plan, sizeof(plan), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int p = 0; p < P; ++p)
+        if (plan.nbytes[p] > (uint32_t)partition_step) return VP8HIP_ERR_OVERFLOW;
+    for (int p = 0; p < P; ++p) {
+        sizes[p] = (int32_t)plan.nbytes[p];
+        HIPCHK(c, hipMemcpyAsync(out + (size_t)p * partition_step, c->ent.bytes + (size_t)plan.word_base[p] * 4, plan.nbytes[p],
+                                 hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    return VP8HIP_OK;
+}
+
 int vp8hip_encode_header(vp8hip_ctx *c, const vp8hip_header_params *p, uint8_t *out, size_t capacity, size_t *size) {
     USE_DEVICE(c);
     if (!c || !p || !out || !size) return VP8HIP_ERR_ARG;

@@ -1037,6 +1037,17 @@ void launch_bool_code(hipStream_t s, const EntBuffers &eb, int P) {
     jobs.j[0] = jobs.j[1] = code_job(eb, P);
     bool_code(s, jobs, 1);
 }
+// the plan of P bool strings that lie end to end in eb.bools, eb.offs[0..P] holding their prefix sums: string p is "slot" p of
+// partition p, so k_ent_plan lays them out by the rules it applies to a frame (the bool-coder tap, vp8hip_debug_bool_code)
+void launch_bool_plan(hipStream_t s, const EntBuffers &eb, int P) {
+    ent::Geom g{};
+    g.P = P;
+    for (int p = 0; p <= ENT_MAX_PARTITIONS; ++p) g.slot_base[p] = (uint32_t)(p < P ? p : P);
+    g.cap_bools = eb.cap_bools;
+    g.cap_chunks = eb.cap_chunks;
+    g.cap_words = eb.cap_words;
+    hipLaunchKernelGGL(ent::k_ent_plan, dim3(1), dim3(64), 0, s, eb.offs, g, eb.plan);
+}
 void launch_frame_code(hipStream_t s, const EntBuffers &coef, int P, const EntBuffers &hdr, uint32_t head, uint32_t capacity, uint8_t *frame) {
     ent::CodeJobs jobs{};
     jobs.j[0] = code_job(coef, P);

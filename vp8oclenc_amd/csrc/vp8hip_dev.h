@@ -379,6 +379,8 @@ void launch_scan_exclusive(hipStream_t s, uint32_t *v, uint32_t *tile_sum, int n
 // the coder on bool strings laid out per eb.plan (accumulators cleared by the emit kernel); eb.maps holds
 // cap_chunks chunk maps followed by the super-chunk maps (ent_maps_entries)
 void launch_bool_code(hipStream_t s, const EntBuffers &eb, int P);
+// the plan (k_ent_plan) of P bool strings laid end to end, eb.offs[0..P] = their prefix sums (vp8hip_debug_bool_code)
+void launch_bool_plan(hipStream_t s, const EntBuffers &eb, int P);
 // the coder on the coefficient partitions and the first partition at once, its last kernel laying the finished frame
 // out (gather_frame): frame[0] = frame size (0 = overflow), frame[1] = first-partition size, frame bytes from frame + 16
 void launch_frame_code(hipStream_t s, const EntBuffers &coef, int P, const EntBuffers &hdr, uint32_t head, uint32_t capacity, uint8_t *frame);
