@@ -454,6 +454,38 @@ int vp8hip_upload_segment_map(vp8hip_ctx *ctx, const uint8_t *host_map);
  * macroblock (e_out may be NULL; not NULL outside mode 2: VP8HIP_ERR_STATE).  Blocks.  VP8HIP_ERR_STATE: mode 0, or mode 2 and no
  * frame taken in since it was set. */
 int vp8hip_download_segment_map(vp8hip_ctx *ctx, uint8_t *map_out, uint8_t *e_out);
+/* ---- hidden alternate reference frames (opt-in; NOT the reference, which never codes a frame it does not show) -------------------
+ * libvpx's --auto-alt-ref with its ARNR filter, the placement left to the caller: a frame made by motion-compensated temporal
+ * filtering of up to VP8HOST_ARF_MAX_FRAMES source frames around a centre frame is coded as an inter frame that is NOT shown
+ * (show_frame = 0), refreshes ALTREF only (refresh_last = 0) and so gives the frames behind it a reference cleaner than their
+ * neighbours.  A context that never calls these entry points launches nothing, allocates nothing and changes no byte or number.
+ * vp8hip_arf_filter_device: frames[k][0..2] = the Y, U, V planes of frame k, tight 8-bit I420 of the context's INCOMING size (its
+ * scaler's incoming size, else its source size, else the coded size) in this device's memory; centre in 0 .. n - 1; strength 0 .. 6.
+ * ONE launch (k_arf_filter_b; the rule is stated bit for bit in include/vp8hip_host.h, vp8host_arf_filter_frame) writes the filtered
+ * frame into a staging buffer the context owns (allocated on first use), and that frame becomes the CURRENT frame through the
+ * ordinary intake, exactly as if vp8hip_set_current_device had been given it: padding, scaling, orientation and the segment map of
+ * mode 2 see it as they see a source frame.  The planes may be reused once the context's stream has got there.
+ * vp8hip_arf_filter_host: the same for planes in host memory (uploaded into a buffer of the context's; returns when they were read).
+ * vp8hip_arf_result: the (tile, frame k != centre) pairs of the last filter launch by block weight 0, 1, 2; blocks.
+ * vp8hip_arf_release: frees the two buffers (whatever reads them ends first: not a per-frame call); the next filter call makes them again.
+ * The frame is then coded like any inter frame -- vp8hip_auto_segments or vp8hip_set_segments, vp8hip_inter_transform with the
+ * rotation owed by the previous shown frame -- and ENDS with vp8hip_loop_filter_hidden in the place of vp8hip_loop_filter: the
+ * filtered reconstruction becomes ALTREF, a slot assignment, with its replicated edges and its pyramid made behind the filter; LAST
+ * stays the surface it is, and the intake is left as the hidden frame found it: the current frame is the last shown frame again, so
+ * the next frame taken in is compared with it (vp8hip_chroma_change) and numbered behind it.  The rotation is consumed by the hidden frame's transform: the next shown frame's takes prev_is_golden =
+ * prev_is_altref = 0, or LAST overwrites the new ALTREF.  Its bytes: vp8hip_header_params.is_altref = VP8HIP_ALTREF_HIDDEN.
+ * VP8HIP_ERR_ARG and nothing has changed: n, centre or strength out of range, a null plane, a context with a source format other than
+ * I420, a source window, a deinterlacer, a denoiser or analysis (the last three keep a history of the frames taken in that a frame
+ * out of order would disturb).  VP8HIP_ERR_STATE: a member of a batch, a context that shares a frame's searches with other devices
+ * (vp8hip_shard_init), a context with vp8hip_filter_overlap (the next frame's ALTREF search would start beside the filter that
+ * writes ALTREF; the combination is refused rather than ordered), vp8hip_arf_result before any filter launch, and
+ * vp8hip_loop_filter_hidden without an inter reconstruction, or with an armed check_SSIM (a hidden frame has no fallback). */
+#define VP8HIP_ALTREF_HIDDEN 2
+int vp8hip_arf_filter_device(vp8hip_ctx *ctx, const void *const (*frames)[3], int n, int centre, int strength);
+int vp8hip_arf_filter_host(vp8hip_ctx *ctx, const uint8_t *const (*frames)[3], int n, int centre, int strength);
+int vp8hip_arf_result(vp8hip_ctx *ctx, int32_t weights[3]);
+int vp8hip_arf_release(vp8hip_ctx *ctx);
+int vp8hip_loop_filter_hidden(vp8hip_ctx *ctx);
 /* on = 1: the context gets a second stream, and work that does not depend on the filtered frame runs beside the loop filter:
  * the entropy stage of the same frame (vp8hip_count_probs ... vp8hip_encode_frame), the next frame's upload, parameter scan
  * and GOLDEN / ALTREF searches.  The filter stays on the stream the frame was coded on and the CONTEXT moves to the other one
@@ -500,7 +532,8 @@ int vp8hip_encode_coefficients(vp8hip_ctx *ctx, const uint32_t *coeff_probs, int
  * vp8bs_encode_header (include/vp8hip_bitstream.h); vp8bs_gather_frame appends the coefficient partitions. */
 #define VP8HIP_SHARPNESS_ON_DEVICE INT32_MIN
 typedef struct {
-    int32_t is_key, is_golden, is_altref;    /* frames.current_is_{key,golden,altref}_frame */
+    int32_t is_key, is_golden, is_altref;    /* frames.current_is_{key,golden,altref}_frame; is_altref = VP8HIP_ALTREF_HIDDEN (inter frames): a
+                                                hidden frame -- show_frame = 0 in the frame tag, refresh_alternate = 1, refresh_last = 0 */
     int32_t loop_filter_type;                /* video.loop_filter_type: 0 normal, 1 simple -- the filter the context applies (vp8hip_set_loop_filter_type) */
     int32_t loop_filter_sharpness;           /* video.loop_filter_sharpness; VP8HIP_SHARPNESS_ON_DEVICE = the value vp8hip_auto_segments
                                                 computed.  (Not -1: get_loopfilter_strength's `int` accumulator overflows on large noisy
@@ -591,7 +624,11 @@ const char *vp8hip_status_string(int status);
  * vp8drv_config is unchanged);
  * also under 4010: the per-macroblock quantiser (vp8hip_set_segment_mode, vp8hip_segment_mode, vp8hip_set_segment_map_device,
  * vp8hip_upload_segment_map, vp8hip_download_segment_map, vp8host_aq_segment_map, vp8host_aq_segment, vp8drv_set_segment_mode, vp8drv_set_segment_map;
- * entry points only: vp8drv_config is unchanged). */
+ * entry points only: vp8drv_config is unchanged);
+ * also under 4010: hidden alternate reference frames (vp8hip_arf_filter_device, vp8hip_arf_filter_host, vp8hip_arf_result,
+ * vp8hip_arf_release, vp8hip_loop_filter_hidden, vp8host_arf_filter_frame, vp8host_arf_round_divide, vp8drv_set_arf,
+ * vp8drv_encode_arf_device, vp8drv_encode_arf_host, vp8drv_get_arf_stats; entry points only, and the value VP8HIP_ALTREF_HIDDEN of
+ * the existing is_altref fields: vp8drv_config, vp8drv_stats, vp8hip_header_params and vp8bs_frame keep their layout). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

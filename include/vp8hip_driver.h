@@ -301,6 +301,47 @@ int vp8drv_set_segment_map(vp8drv *d, const uint8_t *host_map);
 int vp8drv_set_quantizer(vp8drv *d, int qi_min, int qi_max);
 /* the pair in force, as given (not swapped) */
 int vp8drv_get_quantizer(const vp8drv *d, int32_t *qi_min, int32_t *qi_max);
+/* ---- hidden alternate reference frames (vp8hip_arf_filter_device, include/vp8hip.h; the rule: include/vp8hip_host.h) -----------------
+ * libvpx's --auto-alt-ref=1 --arnr-maxframes --arnr-strength with the placement left to the caller: the caller owns the lookahead and
+ * hands the window in whenever it wants a hidden frame; the driver keeps no queue.  Entry points and not fields of vp8drv_config for
+ * the reason vp8drv_set_denoise is one.
+ * vp8drv_set_arf: 0 (default) = off, 1 .. 7 = on at strength 0 .. 6.  Takes the open check_SSIM verdict first.  Turning it off
+ * frees the filter's staging buffers and nothing else: the current frame and the references stay.
+ * vp8drv_encode_arf_device: frames[k][0..2] = the planes of frame k of the window, tight 8-bit I420 of the incoming size in device
+ * memory, 1 <= n <= 7, centre in 0 .. n - 1.  It takes the open check_SSIM verdict first, filters the window on the device and codes
+ * the filtered frame as an INTER frame that is not shown: on the altrefqi ladder, with the references the next shown frame would be
+ * allowed (cfg.scene_detect keeps working: the hidden frame steps out of the intake when it is coded, so the next frame's chroma
+ * comparison is with the last SHOWN frame; GOLDEN unless the last shown frame was a key frame; ALTREF unless that frame was a key frame or a scheduled alt-ref, and
+ * only where it differs from GOLDEN; both subject to cfg.ref_mask), WITHOUT check_SSIM (no fallback, no filter update, no redo as key
+ * frame), and with the reconstruction into ALTREF while LAST stays.  frame_number, the GOP counters, the scene history, vp8drv_stats
+ * and the quality summary are left alone: they count shown frames.  Returns 0; vp8drv_get_frame / _begin / _end then deliver its bytes
+ * like any frame's (show_frame = 0, refresh_alternate = 1, refresh_last = 0 in them).  A container gives it a record of its own with
+ * the timestamp of the next shown frame.
+ * AFTERWARDS shown inter frames search ALTREF, subject to cfg.ref_mask, until a key frame or a scheduled shown alt-ref replaces it;
+ * use_golden keeps following the real history of shown frames.  A caller that wants hidden alt-refs only sets cfg.altref_range above
+ * cfg.gop_size.  Hidden frames of a GOP depend on that GOP's frames only when the caller clips its windows to the GOP.
+ * vp8drv_encode_arf_host: the simple form -- uploads the window, blocks, and does the same.
+ * THE VERDICT IT TAKES: when the open verdict sends the last shown frame back, that frame is coded again as a key frame inside this
+ * call, before the hidden frame (which then follows a key frame), and the call still returns 0: its return value speaks of the hidden
+ * frame only.  A caller that has to know -- one that has not taken that frame's bytes yet, or that clips its windows to the GOP --
+ * calls vp8drv_resolve or vp8drv_get_frame for the shown frame first, as the tools do; vp8drv_stats.redone_as_key counts it either way.
+ * VP8HIP_ERR_STATE: hidden frames off, no frame coded yet (no reference), the driver is a member of a live batch (vp8drv_batch_create
+ * in turn refuses a driver with hidden frames on: they are not batched), a frame handed over early with vp8drv_stage_frame_host is
+ * waiting, or the context shares a frame's searches with other devices.  VP8HIP_ERR_ARG: a bad n, centre or strength, a null plane,
+ * cfg.device_params = 0, cfg.overlap_filter (the next frame's ALTREF search would start beside the filter that writes ALTREF),
+ * a source format other than 0, a source window,
+ * deinterlacing, denoising or analysis switched on (the last three keep a history that a hidden frame would disturb).
+ * vp8drv_get_arf_stats: hidden frames coded so far, and of the last one its window, its reference flags and the (tile, frame) pairs by
+ * block weight 0, 1, 2; blocks.  VP8HIP_ERR_STATE: none coded. */
+typedef struct {
+    int32_t hidden_frames;
+    int32_t last_frames, last_use_golden, last_use_altref;
+    int32_t last_weight[3];
+} vp8drv_arf_stats;
+int vp8drv_set_arf(vp8drv *d, int strength_plus_one);
+int vp8drv_encode_arf_device(vp8drv *d, const void *const (*frames)[3], int n, int centre);
+int vp8drv_encode_arf_host(vp8drv *d, const uint8_t *const (*frames)[3], int n, int centre);
+int vp8drv_get_arf_stats(vp8drv *d, vp8drv_arf_stats *s);
 
 #ifdef __cplusplus
 }

@@ -300,6 +300,43 @@ int vp8host_analyse_luma(const uint8_t *cur, const uint8_t *prev_or_null, int wi
 int vp8host_aq_segment(int e, int E, int W);
 int vp8host_aq_segment_map(const uint8_t *luma, int stride, int width, int height, int strength, uint8_t *map_out, uint8_t *e_out);
 
+/* The rule of the temporal filter that makes a hidden alternate reference frame (vp8hip_arf_filter_device, include/vp8hip.h;
+ * k_arf_filter_b), bit for bit, integers only.  The project's own, after libvpx's --auto-alt-ref / --arnr-maxframes / --arnr-strength:
+ * the reference never codes a frame it does not show.
+ * IN: n frames (1 <= n <= VP8HOST_ARF_MAX_FRAMES) of tight 8-bit I420 of one size w x h, both even; a centre index c in 0 .. n - 1; a
+ * strength s in 0 .. 6.  OUT: one tight I420 frame of w x h.
+ * EXTENSION: every plane is read as if extended to We x He = 16 ceil(w / 16) x 16 ceil(h / 16) luma samples (chroma: half of that) by
+ * repeating its last column and its last row.  Only the w x h samples are written; there are no partial-tile special cases.
+ * PER 16x16 LUMA TILE of the centre frame (top-left (x0, y0), both multiples of 16) AND PER FRAME k != c: a full-pel search over
+ * dx, dy in [-8, 7].  A candidate counts only if its block lies inside the extended picture: 0 <= x0 + dx, x0 + dx + 16 <= We,
+ * 0 <= y0 + dy, y0 + dy + 16 <= He.  SAD = the sum of |centre - frame k| over the 256 samples.  The winner is the lexicographic minimum
+ * of (SAD, |dx| + |dy|, dy, dx), i.e. the minimum of the 29-bit key
+ *     SAD << 13 | (|dx| + |dy|) << 8 | (dy + 8) << 4 | (dx + 8).
+ * SSE = the sum of squared differences of the winning block against the centre tile, and the BLOCK WEIGHT
+ *     bw = 2 if SSE < 10000, 1 if SSE < 20000, else 0          (libvpx's THRESH_LOW and THRESH_HIGH).
+ * The centre frame itself has bw = 2 and the zero vector.  The tile's two 8x8 chroma blocks take the full-pel vector
+ * (dx >> 1, dy >> 1), arithmetic shifts.
+ * PER SAMPLE of every plane, with o the centre frame's sample and, for each frame with bw > 0, p its predicted sample:
+ *     d = o - p,   m = (3 d d + r) >> s with r = s ? 1 << (s - 1) : 0,   m = 16 - min(m, 16),   count += m bw,   acc += m bw p
+ * and the output sample is (acc + count / 2) / count, integer divisions.  count is at least 32 (the centre gives 16 * 2) and at most
+ * 224; acc is at most 255 count, below 65536.  n = 1 returns the centre frame unchanged.
+ * THE DIVISION is exact and made by a reciprocal multiply, the same two macros on the host and on the device:
+ * VP8HOST_ARF_DIVIDE(acc + count / 2, VP8HOST_ARF_RECIPROCAL(count)).  With R = floor((2^32 - 1) / count) + 1 the error
+ * R count - 2^32 lies in [0, count), so floor(x R / 2^32) = floor(x / count) while x count < 2^32: x < 65536 + 112, count <= 224.
+ * vp8host_arf_round_divide applies the pair to arrays (for a test that walks every pair that can occur).
+ * vp8host_arf_filter_frame: the rule in plain C++.  frames[3 k + p] = plane p of frame k.  weights (may be NULL) receives, for
+ * b = 0, 1, 2, the number of (tile, frame k != c) pairs with bw = b; vectors (may be NULL) receives for tile t in raster order and
+ * frame k the winner as vectors[(t n + k) 2 + 0] = dx, [.. + 1] = dy (0, 0 for k = c).  out must not overlap a source frame.  Returns 0,
+ * or -1: a null pointer, n, centre or strength out of range, w or h odd or below 2. */
+#define VP8HOST_ARF_MAX_FRAMES 7
+#define VP8HOST_ARF_THRESH_LOW 10000
+#define VP8HOST_ARF_THRESH_HIGH 20000
+#define VP8HOST_ARF_RECIPROCAL(count) (0xFFFFFFFFu / (uint32_t)(count) + 1u)
+#define VP8HOST_ARF_DIVIDE(x, recip) ((uint32_t)(((uint64_t)(uint32_t)(x) * (uint32_t)(recip)) >> 32))
+int vp8host_arf_filter_frame(const uint8_t *const *frames, int n, int centre, int strength, int width, int height, uint8_t *out_y,
+                             uint8_t *out_u, uint8_t *out_v, int32_t weights[3], int8_t *vectors);
+void vp8host_arf_round_divide(const uint32_t *acc, const uint32_t *count, size_t n, uint32_t *out);
+
 /* frames.skip_prob, loop_filter.h:37-44 */
 int vp8host_skip_prob(const int32_t *MB_non_zero_coeffs, int mb_count);
 

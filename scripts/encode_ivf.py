@@ -14,7 +14,10 @@ and the key frames carry the source size as display size.
 --surface WxH --crop X:Y (with --yuv): the file's frames are surfaces of WxH and the frame is the window of --width x --height whose
 top-left luma sample is (X, Y) (vp8drv_set_source_window with the surface's tight pitch; everything even); --rotate 90|180|270 and
 --mirror: the frames are stored sideways, upside down or flipped and are turned clockwise (behind the flip) on the device
-(vp8drv_set_source_orientation); behind 90 or 270 degrees the picture that is coded is as wide as the frames that come in are high."""
+(vp8drv_set_source_orientation); behind 90 or 270 degrees the picture that is coded is as wide as the frames that come in are high.
+--arf PERIOD[:FRAMES[:STRENGTH]] (FRAMES 1..7, default 7; STRENGTH 0..6, default 3): hidden alternate reference frames (vp8drv_set_arf,
+vp8drv_encode_arf_host), placed as scripts/native/y4m_to_ivf -arf places them (gop_shard.hidden_frame_events): the file is the one that
+tool writes with -no-scene-detect (this script never detects scenes).  One process; 8-bit I420 frames without --denoise, --deinterlace, --analysis or --surface."""
 import argparse, os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -81,7 +84,16 @@ def main():
     ap.add_argument("--analysis", default="", metavar="FILE", help="the frame analysis record of every frame as one text line per frame (vp8drv_set_analysis; the line: scripts/native/y4m_to_ivf.cpp): a first-pass file")
     ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation of the inter frames at strength N: flat macroblocks take the finer segments of the quantiser ladder, busy ones the coarser (vp8drv_set_segment_mode, mode 2)")
     ap.add_argument("--segment-map", default="", metavar="FILE", help="the caller's segment map for every inter frame: one byte 0..3 per macroblock of the coded picture, raster order (vp8drv_set_segment_mode, mode 1)")
+    ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames made by temporal filtering on the device (vp8drv_set_arf, vp8drv_encode_arf_host): one in front of every group of PERIOD frames of a GOP, centred on the group's last frame, FRAMES frames wide (default 7) at STRENGTH 0..6 (default 3)")
     a = ap.parse_args()
+    arf = None
+    if a.arf:
+        try:
+            arf = gop_shard.parse_arf(a.arf)
+        except ValueError as e:
+            sys.exit(f"--arf {a.arf}: {e}")
+        if a.denoise or a.deinterlace != "off" or a.analysis or a.surface:
+            sys.exit("--arf does not go with --denoise, --deinterlace, --analysis or --surface")
     if a.aq and a.segment_map:
         sys.exit("--aq and --segment-map: one of them picks the segments")
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -136,7 +148,9 @@ def main():
     def make_encoder():
         enc = gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
                                       ssim_target=a.ssim_target, check_ssim=1, conformant_stream=int(a.conformant),
-                                      loop_filter_type=int(a.simple_filter))
+                                      loop_filter_type=int(a.simple_filter), **(dict(overlap_filter=0) if arf else {}))
+        if arf:      # (the driver refuses the filter's own stream beside hidden frames)
+            enc.drv.set_arf(arf[2] + 1)
         if a.denoise:
             enc.drv.set_denoise(a.denoise)
         if a.aq:
@@ -166,6 +180,25 @@ def main():
     records = []
     if a.analysis and world > 1:
         sys.exit("--analysis: one process only (the records are not gathered over ranks)")
+    if arf:      # the plain loop with the lookahead the frame source gives: a hidden frame is a record of its own
+        if world > 1 or fmt:
+            sys.exit("--arf: one process, 8-bit I420 frames")
+        recs, hidden = [], 0
+        for start, length in gop_shard.gop_chunks(frames, a.gop):
+            enc = make_encoder()
+            for ev in gop_shard.hidden_frame_events(length, arf[0], arf[1]):
+                if ev[0] == "shown":
+                    recs.append((start + ev[1], enc.encode(*seq.frame(start + ev[1]))))
+                else:
+                    _, lo, n, centre, ts = ev
+                    enc.drv.encode_arf_host([seq.frame(start + lo + k) for k in range(n)], centre)
+                    recs.append((start + ts, enc.drv.get_frame()))
+                    hidden += 1
+            enc.close()
+        n = gop_shard.write_ivf_records(a.out, recs, Wd, Hd, a.framerate)
+        el = time.perf_counter() - t0
+        print(f"{a.out}: {frames} shown + {hidden} hidden frames {Win}x{Hin}{f' scaled to {Wd}x{Hd}' if a.resize else ''}, {n} bytes, {frames / el:.1f} frames/s including the host-side frame source")
+        return
     mine = gop_shard.encode_chunks_frames(make_encoder, seq, gop_shard.chunks_of_rank(frames, a.gop, rank, world))
     if a.analysis:
         with open(a.analysis, "w") as f:

@@ -6,7 +6,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
-from vp8oclenc_amd import api
+from vp8oclenc_amd import api, gop_shard
 from vp8oclenc_amd.synth import SynthSequence
 
 ap = argparse.ArgumentParser()
@@ -31,6 +31,7 @@ ap.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=0, help
 ap.add_argument("--mirror", action="store_true", help="... behind a left-right flip")
 ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the frame analysis record of every frame (vp8drv_set_analysis): what k_analyse_src_b and k_analyse_mb_b cost")
 ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation at strength N (vp8drv_set_segment_mode, mode 2): what k_aq_map_b + k_aq_seg_b cost, and with one stream the mapped macroblock kernel next to the default's in the same run")
+ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames (vp8drv_set_arf, vp8drv_encode_arf_device): every stream codes one in front of every PERIOD-th frame from a window of FRAMES device-resident frames (default 7) at STRENGTH (default 3); with one stream also what k_arf_filter_b costs by HIP events")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
@@ -114,12 +115,30 @@ if a.analysis:
 if a.aq:
     for d in drvs:
         d.set_segment_mode(2, a.aq)
+arf = gop_shard.parse_arf(a.arf) if a.arf else None
+if arf:
+    for d in drvs:
+        d.set_arf(arf[2] + 1)
 sizes = [0] * a.streams
+hidden_coded = [0] * a.streams
+
+
+def hidden_frame(d, k, t, emit):
+    """in front of frame t: a hidden frame centred on the last frame of the group of PERIOD frames that starts there"""
+    c = t + arf[0] - 1
+    lo, hi = max(0, c - arf[1] // 2), c + arf[1] // 2
+    d.encode_arf_device([tuple(p.data_ptr() for p in dev[(j + 3 * k) % nd]) for j in range(lo, hi + 1)], c - lo)
+    hidden_coded[k] += 1
+    if emit:
+        sizes[k] += len(d.get_frame())
+
 
 def work(k, n, emit):
     d = drvs[k]
     for t in range(n):
         y, u, v = dev[(t + 3 * k) % nd]
+        if arf and t and t % arf[0] == 0:
+            hidden_frame(d, k, t, emit)
         d.encode_frame_device(y.data_ptr(), u.data_ptr(), v.data_ptr())
         if emit:
             sizes[k] += len(d.get_frame())
@@ -130,6 +149,8 @@ def run_pipeline(n, emit):
     for t in range(n):
         for k, d in enumerate(drvs):
             y, u, v = dev[(t + 3 * k) % nd]
+            if arf and t and t % arf[0] == 0:
+                hidden_frame(d, k, t, emit)
             d.encode_frame_device(y.data_ptr(), u.data_ptr(), v.data_ptr())
             if emit:
                 d.get_frame_begin()
@@ -184,6 +205,20 @@ if a.aq and a.streams == 1:   # k_mb_p_map next to k_mb_p, and the input side wi
     d.set_segment_mode(2, a.aq)
     print(f"macroblock kernel, mapped (--aq {a.aq}) {mapped:.2f} us per launch over {n_on} launches, default {plain:.2f} us over {n_off}; "
           f"input side without the map {pack_off:.2f} us per launch")
+if arf:
+    st = drvs[0].arf_stats()
+    print(f"hidden alt-refs (--arf {a.arf}): {sum(hidden_coded)} coded over all runs and streams; stream 0's last: {st.last_frames} frames, tiles by block weight 0 / 1 / 2: {list(st.last_weight)}")
+    if a.streams == 1:      # the filter launch by HIP events: the input side's stage of a hidden frame (filter + pack) minus a shown frame's (pack)
+        d = drvs[0]
+        d.hip.synchronize()
+        d.hip.profile_enable(["pack"])
+        work(0, 1, False)
+        pack_ms, _ = d.hip.profile_read().get("pack", (0.0, 0))
+        for _ in range(8):
+            hidden_frame(d, 0, 8, False)
+        ms, n = d.hip.profile_read().get("pack", (0.0, 0))
+        d.hip.profile_enable([])
+        print(f"k_arf_filter_b, window of {st.last_frames}: {(ms / 8 - pack_ms) * 1e3:.1f} us per launch (the stage's {n} launches over 8 hidden frames minus the pack launch's {pack_ms * 1e3:.1f} us)")
 if a.quality_stats:
     q = drvs[0].quality_summary()
     print(f"quality of stream 0 over {q.frames} frames: PSNR overall {q.psnr_all:.3f} dB, avg {q.psnr_avg:.3f} dB, SSIM {q.ssim_all:.5f}")

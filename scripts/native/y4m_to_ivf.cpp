@@ -3,6 +3,16 @@
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
 //              [-input-format NAME] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
+//              [-arf PERIOD[:FRAMES[:STRENGTH]]]
+// -arf PERIOD[:FRAMES[:STRENGTH]] (FRAMES 1..7, default 7; STRENGTH 0..6, default 3): hidden alternate reference frames
+// (vp8drv_set_arf, vp8drv_encode_arf_host; libvpx's --auto-alt-ref=1 --arnr-maxframes --arnr-strength).  In front of the first frame of
+// every group of PERIOD frames of a GOP -- behind the key frame for the GOP's first group -- a hidden frame is coded, made by temporal
+// filtering of FRAMES frames centred on the group's last frame, the window clipped to the GOP and the file.  It is an IVF record of its own
+// with the timestamp of the next shown frame, and the file header's frame count includes it.  The option reads ahead, so this mode is a
+// plain loop (no reader thread, no frame handed over early, the filter on the frame's own stream); scene detection works as without
+// the option, and a key frame it or check_SSIM makes starts the GOP the windows are clipped to; it composes with
+// -resize, -rotate, -mirror, -aq, -psnr and the quantiser options and refuses -denoise, -deinterlace, -analysis, -crop and any format
+// but 8-bit I420.
 // -crop W:H:X:Y (ffmpeg's order): the Y4M header gives the SURFACE, the crop the window of it that is the frame (vp8drv_set_source_window:
 // W, H, X, Y even; the pitch is the surface's tight pitch) and so the size that comes in; the whole surface is read from the file, only
 // the window travels to the device.  -rotate N: the frames are stored sideways or upside down and are turned clockwise by N degrees on
@@ -63,6 +73,7 @@ int main(int argc, char **argv) {
     int crop[4] = {0, 0, 0, 0};     // -crop: W, H, X, Y (W == 0: the whole surface)
     int turns = 0, mirror = 0;      // -rotate, -mirror
     const char *analysis_path = nullptr;      // -analysis
+    int arf_period = 0, arf_frames = 7, arf_strength = 3;      // -arf
     static const char *const format_names[VP8HOST_FORMAT_COUNT] = {"i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"};
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
@@ -105,6 +116,13 @@ int main(int argc, char **argv) {
             turns = deg / 90;
         }
         else if (!strcmp(argv[i], "-mirror")) mirror = 1;
+        else if (!strcmp(argv[i], "-arf")) {
+            const int k = sscanf(val(), "%d:%d:%d", &arf_period, &arf_frames, &arf_strength);
+            if (k < 1 || arf_period < 1 || arf_frames < 1 || arf_frames > VP8HOST_ARF_MAX_FRAMES || arf_strength < 0 || arf_strength > 6) {
+                fprintf(stderr, "-arf PERIOD[:FRAMES[:STRENGTH]]: PERIOD >= 1, FRAMES 1..7, STRENGTH 0..6\n");
+                return 2;
+            }
+        }
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -113,6 +131,11 @@ int main(int argc, char **argv) {
             else { fprintf(stderr, "-resize-filter area|lanczos\n"); return 2; }
         }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+    }
+    if (arf_period) {
+        if (denoise || deint || analysis_path || crop[0]) { fprintf(stderr, "-arf does not go with -denoise, -deinterlace, -analysis or -crop\n"); return 2; }
+        cfg.overlap_filter = 0;    // (the next frame's ALTREF search would start beside the filter that writes ALTREF; the key frames stay where they are without the option)
+        fprintf(stderr, "-arf: the loop filter runs on the frame's own stream in this mode (no frame is handed over early)\n");
     }
     FILE *in = fopen(argv[1], "rb");
     if (!in) { perror(argv[1]); return 1; }
@@ -191,6 +214,97 @@ int main(int argc, char **argv) {
     size_t nb[3];            // the planes of a frame as the file has them (nb[2] == 0: two planes, the third pointer is the second again)
     if (vp8host_source_plane_bytes(format, W, H, nb) != 0) { fprintf(stderr, "%dx%d: not a frame size of format %s\n", W, H, format_names[format]); return 1; }
     std::vector<uint8_t> bytes((size_t)(Wc / 16) * (Hc / 16) * 1900 + (1 << 20));
+    if (arf_period) {      // the plain loop with a lookahead
+        if (format) { fprintf(stderr, "-arf takes 8-bit I420 frames only\n"); return 2; }
+        CK(vp8drv_set_arf(drv, arf_strength + 1));
+        const size_t fsz = nb[0] + nb[1] + nb[2];
+        std::vector<std::vector<uint8_t>> ahead;      // frames first .. first + ahead.size() - 1 of the file
+        long first_held = 0;
+        bool eof = false;
+        auto have = [&](long idx) -> bool {           // frame idx is in memory (reads up to it); false: the file ends before it
+            while (!eof && first_held + (long)ahead.size() <= idx) {
+                std::vector<uint8_t> f(fsz);
+                uint8_t marker[6];
+                if (fread(f.data(), 1, fsz, in) != fsz) { eof = true; break; }
+                const size_t k = fread(marker, 1, 6, in);
+                if (k > 0 && !vp8host_y4m_frame_marker_ok(marker)) { fprintf(stderr, "broken stream!\n"); eof = true; break; }
+                ahead.push_back(std::move(f));
+            }
+            return idx < first_held + (long)ahead.size();
+        };
+        auto frame = [&](long idx) { return ahead[(size_t)(idx - first_held)].data(); };
+        uint32_t records = 0, shown = 0, hidden = 0, keys = 0;
+        size_t total = 32;
+        auto write_record = [&](uint64_t timestamp) -> int {
+            size_t size = 0;
+            const int rc = vp8drv_get_frame(drv, bytes.data(), bytes.size(), &size);
+            if (rc < 0) return rc;
+            uint8_t ph[12];
+            fwrite(ph, 1, vp8bs_ivf_frame_header(ph, (uint32_t)size, timestamp), out);
+            fwrite(bytes.data(), 1, size, out);
+            total += 12 + size;
+            ++records;
+            return 0;
+        };
+        long gop_start = 0;
+        // the hidden frame of the group that starts at `group_first`, centred on the group's last frame; timestamp: the next shown frame's
+        auto hidden_frame = [&](long group_first, uint64_t timestamp) -> int {
+            const long gop_end = gop_start + cfg.gop_size;
+            long last = group_first + arf_period - 1;
+            if (last > gop_end - 1) last = gop_end - 1;
+            while (last > group_first && !have(last)) --last;
+            if (last == gop_start || !have(last)) return 0;      // (a group that is the key frame alone)
+            long lo = last - arf_frames / 2, hi = last + arf_frames / 2;
+            if (lo < gop_start) lo = gop_start;
+            if (lo < first_held) lo = first_held;
+            if (hi > gop_end - 1) hi = gop_end - 1;
+            while (hi > last && !have(hi)) --hi;
+            const uint8_t *win[VP8HOST_ARF_MAX_FRAMES][3];
+            for (long k = lo; k <= hi; ++k) { win[k - lo][0] = frame(k); win[k - lo][1] = win[k - lo][0] + nb[0]; win[k - lo][2] = win[k - lo][1] + nb[1]; }
+            const int rc = vp8drv_encode_arf_host(drv, win, (int)(hi - lo + 1), (int)(last - lo));
+            if (rc < 0) return rc;
+            ++hidden;
+            return write_record(timestamp);
+        };
+        const auto t_loop = std::chrono::steady_clock::now();
+        for (long t = 0; have(t); ++t) {
+            if (t - gop_start >= cfg.gop_size) gop_start = t;      // (the schedule makes this frame a key frame)
+            const long pos = t - gop_start;
+            if (pos && pos % arf_period == 0) CK(hidden_frame(t, (uint64_t)t));
+            const uint8_t *y = frame(t);
+            CK(vp8drv_encode_frame_host(drv, y, y + nb[0], y + nb[0] + nb[1], 0));
+            CK(write_record((uint64_t)t));
+            const int key = vp8drv_resolve(drv);
+            CK(key);
+            keys += key;
+            ++shown;
+            if (key) {      // a GOP starts here, by the schedule or because check_SSIM sent the frame back
+                gop_start = t;
+                CK(hidden_frame(t, (uint64_t)t + 1));
+            }
+            while (first_held < t - arf_frames) { ahead.erase(ahead.begin()); ++first_held; }      // (no window reaches further back than FRAMES / 2)
+        }
+        const double loop_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
+        fseek(out, 0, SEEK_SET);
+        fwrite(fh, 1, vp8bs_ivf_file_header(fh, Wd, Hd, (uint32_t)(fps ? fps : 30), 1, records + 1), out);      // (one more than it holds, as without the option)
+        fclose(out);
+        fclose(in);
+        if (cfg.quality_stats) {
+            vp8drv_quality_summary q;
+            CK(vp8drv_get_quality_summary(drv, &q));
+            fprintf(stderr, "Stream 0 PSNR (Overall/Avg/Y/U/V) %.3f %.3f %.3f %.3f %.3f  SSIM %.5f (Y %.5f)  worst frame %lld: %.3f dB  (%lld frames)\n",
+                    q.psnr_all, q.psnr_avg, q.psnr[0], q.psnr[1], q.psnr[2], q.ssim_all, q.ssim[0], (long long)q.psnr_min_frame, q.psnr_min,
+                    (long long)q.frames);
+        }
+        vp8drv_arf_stats as{};
+        if (hidden) CK(vp8drv_get_arf_stats(drv, &as));
+        fprintf(stderr, "Hidden alt-refs: %u, period %d, %d frames, strength %d; the last one's tiles by block weight 0 / 1 / 2: %d / %d / %d\n", hidden, arf_period,
+                arf_frames, arf_strength, as.last_weight[0], as.last_weight[1], as.last_weight[2]);
+        vp8drv_destroy(drv);
+        printf("%s: %u shown + %u hidden frames %dx%d (coded %dx%d), %u key, %zu bytes\n", argv[2], shown, hidden, W, H, Wc, Hc, keys, total);
+        printf("%.6f s of reading + coding + writing (%.1f frames/s)\n", loop_s, shown / (loop_s > 0 ? loop_s : 1));
+        return 0;
+    }
     // A reader thread keeps a ring of page-locked frame buffers filled ahead of the coder (get_yuv420_frame's fread, encIO.h:204-254, off the
     // frame loop's thread: 3 MB per 1080p frame is 0.4 ms of the loop's 0.5), the frame after the one under way is started on its way to the
     // device (vp8drv_prefetch_frame_host) and, once the frame just coded has its verdict and its entropy stage enqueued, handed over

@@ -17,7 +17,7 @@ K_NAMES = ["pack", "downsample", "search1_l4", "search1_l3", "search1_l2", "sear
            "select", "mb", "filter_mask", "loop_filter", "border", "ent_count", "ent_encode", "intra", "hdr_encode"]
 K_COUNT = len(K_NAMES)
 
-DBG_NET1, DBG_NET2, DBG_BDIFF, DBG_PYRAMID, DBG_MB_MASK, DBG_MB_NZ, DBG_THIRD_CONTEXT, DBG_CURRENT_CHROMA = range(8)
+DBG_NET1, DBG_NET2, DBG_BDIFF, DBG_PYRAMID, DBG_MB_MASK, DBG_MB_NZ, DBG_THIRD_CONTEXT, DBG_CURRENT_CHROMA, DBG_ARF_FRAME = range(9)
 
 # every symbol include/vp8hip.h and include/vp8hip_host.h declare
 ABI_SYMBOLS = [
@@ -39,6 +39,9 @@ ABI_SYMBOLS = [
     "vp8drv_default_config", "vp8drv_create", "vp8drv_destroy", "vp8drv_context", "vp8drv_encode_frame_device",
     "vp8drv_encode_frame_host", "vp8drv_get_stats", "vp8hip_reserve_frame_path", "vp8hip_reserve_frame_path_dense", "vp8drv_resolve", "vp8drv_ready", "vp8drv_batch_ready", "vp8drv_batches_encode_frame_device", "vp8drv_batches_encode_frames_device", "vp8drv_batches_encode_frames_host", "vp8drv_batch_encode_frame_host", "vp8hip_batch_upload_current", "vp8hip_batch_intra_transform", "vp8hip_batch_prefetch_current", "vp8hip_prefetch_current", "vp8drv_prefetch_frame_host", "vp8drv_stage_frame_host", "vp8drv_batch_prefetch_frame_host", "vp8hip_host_alloc", "vp8hip_host_free", "vp8drv_frame_check", "vp8drv_encode_video_device", "vp8hip_check_ssim_ready", "vp8hip_check_ssim_async", "vp8hip_check_ssim_result", "vp8hip_batch_check_ssim_async", "vp8drv_get_frame", "vp8drv_get_frame_begin", "vp8drv_get_frame_end",
     "vp8bs_default_probs", "vp8bs_encode_header", "vp8bs_gather_frame", "vp8bs_ivf_file_header", "vp8bs_ivf_frame_header",
+    "vp8hip_arf_filter_device", "vp8hip_arf_filter_host", "vp8hip_arf_result", "vp8hip_arf_release", "vp8hip_loop_filter_hidden",
+    "vp8host_arf_filter_frame", "vp8host_arf_round_divide", "vp8drv_set_arf", "vp8drv_encode_arf_device", "vp8drv_encode_arf_host",
+    "vp8drv_get_arf_stats",
 ]
 
 
@@ -47,6 +50,8 @@ class Vp8HipError(RuntimeError):
 
 
 ABI_VERSION = 4010  # VP8HIP_ABI_VERSION, include/vp8hip.h
+ALTREF_HIDDEN = 2   # VP8HIP_ALTREF_HIDDEN: is_altref of a hidden alternate reference frame (header params, bitstream.Frame)
+ARF_MAX_FRAMES = 7  # VP8HOST_ARF_MAX_FRAMES, include/vp8hip_host.h
 ERR_OVERFLOW = -7   # VP8HIP_ERR_OVERFLOW, include/vp8hip.h
 ERR_FORMAT = -8     # VP8HIP_ERR_FORMAT
 SHARPNESS_ON_DEVICE = -2 ** 31   # VP8HIP_SHARPNESS_ON_DEVICE
@@ -565,6 +570,53 @@ def analyse_luma(cur, prev=None) -> dict:
 DENOISE_SUM_Y, DENOISE_SAD_Y, DENOISE_SUM_C = 512, 2560, 128   # VP8HOST_DENOISE_*, include/vp8hip_host.h
 
 
+class ArfStats(C.Structure):
+    """vp8drv_arf_stats, include/vp8hip_driver.h"""
+    _fields_ = [("hidden_frames", C.c_int32), ("last_frames", C.c_int32), ("last_use_golden", C.c_int32), ("last_use_altref", C.c_int32),
+                ("last_weight", C.c_int32 * 3)]
+
+
+def _plane_table(frames):
+    """[(Y, U, V), ...] -> (contiguous uint8 copies that must stay alive, a C array of n x 3 addresses)"""
+    keep = [tuple(np.ascontiguousarray(p, np.uint8) for p in f) for f in frames]
+    h, w = keep[0][0].shape
+    for y, u, v in keep:
+        if y.shape != (h, w) or u.shape != (h // 2, w // 2) or v.shape != (h // 2, w // 2):
+            raise ValueError("the frames of a window are tight I420 planes of one even size")
+    table = (C.c_void_p * (3 * len(keep)))(*[p.ctypes.data for f in keep for p in f])
+    return keep, table
+
+
+def arf_filter_frame(frames, centre: int, strength: int):
+    """vp8host_arf_filter_frame: the device's temporal filter in plain C++ (the rule: include/vp8hip_host.h).  frames = [(Y, U, V), ...]
+    -> ((Y, U, V) filtered, weights[3], vectors[tiles][n][2])"""
+    lib = load_library()
+    lib.vp8host_arf_filter_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
+    keep, table = _plane_table(frames)
+    h, w = keep[0][0].shape
+    n = len(keep)
+    out = (np.zeros((h, w), np.uint8), np.zeros((h // 2, w // 2), np.uint8), np.zeros((h // 2, w // 2), np.uint8))
+    weights = np.zeros(3, np.int32)
+    vectors = np.zeros((((w + 15) // 16) * ((h + 15) // 16), n, 2), np.int8)
+    if lib.vp8host_arf_filter_frame(table, n, int(centre), int(strength), w, h, *[p.ctypes.data for p in out], weights.ctypes.data,
+                                    vectors.ctypes.data) != 0:
+        raise ValueError(f"vp8host_arf_filter_frame({w}x{h}, n {n}, centre {centre}, strength {strength}) refused")
+    return out, [int(x) for x in weights], vectors
+
+
+def arf_round_divide(acc, count) -> np.ndarray:
+    """vp8host_arf_round_divide: (acc + count / 2) / count by the reciprocal multiply the host function and the kernel share"""
+    lib = load_library()
+    lib.vp8host_arf_round_divide.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.vp8host_arf_round_divide.restype = None
+    a, c = np.ascontiguousarray(acc, np.uint32).reshape(-1), np.ascontiguousarray(count, np.uint32).reshape(-1)
+    assert a.shape == c.shape
+    out = np.zeros(a.shape, np.uint32)
+    lib.vp8host_arf_round_divide(a.ctypes.data, c.ctypes.data, a.size, out.ctypes.data)
+    return out
+
+
 def denoise_frame(src, hist, level: int, have_history: bool):
     """vp8host_denoise_frame: the device's denoiser in plain C++ on tight planes of the coded size.  src = (Y, U, V); hist = (Y, U, V)
     arrays that are updated in place when level != 0 (or None with level 0) -> ((Y, U, V) out, macroblocks filtered)"""
@@ -1024,6 +1076,39 @@ class NativeDriver:
             raise Vp8HipError(f"vp8drv_get_frame_analysis: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
         return a
 
+    def set_arf(self, strength_plus_one: int) -> None:
+        """vp8drv_set_arf: hidden alternate reference frames, 0 = off, 1..7 = on at strength 0..6 (include/vp8hip_driver.h)"""
+        self.lib.vp8drv_set_arf.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.vp8drv_set_arf(self.h, int(strength_plus_one))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_arf({strength_plus_one}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def encode_arf_host(self, frames, centre: int) -> None:
+        """vp8drv_encode_arf_host: a hidden frame from the window frames = [(Y, U, V), ...] in host memory, centred on frames[centre];
+        get_frame() then delivers its bytes"""
+        self.lib.vp8drv_encode_arf_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        keep, table = _plane_table(frames)
+        rc = self.lib.vp8drv_encode_arf_host(self.h, table, len(keep), int(centre))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_encode_arf_host: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def encode_arf_device(self, ptrs, centre: int) -> None:
+        """vp8drv_encode_arf_device: the same for ptrs = [(d_y, d_u, d_v), ...] device addresses of tight planes of the incoming size"""
+        self.lib.vp8drv_encode_arf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        table = (C.c_void_p * (3 * len(ptrs)))(*[a for f in ptrs for a in f])
+        rc = self.lib.vp8drv_encode_arf_device(self.h, table, len(ptrs), int(centre))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_encode_arf_device: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def arf_stats(self) -> ArfStats:
+        """vp8drv_get_arf_stats: hidden frames coded, and the last one's window, reference flags and tiles by block weight"""
+        st = ArfStats()
+        self.lib.vp8drv_get_arf_stats.argtypes = [C.c_void_p, C.POINTER(ArfStats)]
+        rc = self.lib.vp8drv_get_arf_stats(self.h, C.byref(st))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_arf_stats: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return st
+
     def set_segment_mode(self, mode: int, strength: int = 0) -> None:
         """vp8drv_set_segment_mode: 0 off, 1 the caller's segment map, 2 variance-adaptive at strength 1..3 (inter frames only)"""
         self.lib.vp8drv_set_segment_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1362,6 +1447,47 @@ class Vp8Hip:
     def loop_filter(self):
         self._chk(self.lib.vp8hip_loop_filter(self.h), "loop_filter")
 
+    def loop_filter_hidden(self):
+        """vp8hip_loop_filter_hidden: the end of a hidden frame -- the filtered reconstruction becomes ALTREF, LAST stays"""
+        self.lib.vp8hip_loop_filter_hidden.argtypes = [C.c_void_p]
+        self._chk(self.lib.vp8hip_loop_filter_hidden(self.h), "loop_filter_hidden")
+        self.hidden_recon = tuple(self.debug(DBG_ARF_FRAME, r) for r in (3, 4, 5))
+
+    def arf_filter(self, frames, centre: int, strength: int):
+        """vp8hip_arf_filter_host: the window frames = [(Y, U, V), ...] (host memory, the incoming size) through the temporal filter;
+        the filtered frame becomes the current frame.  Returns it as it left the filter."""
+        self.lib.vp8hip_arf_filter_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        keep, table = _plane_table(frames)
+        self._chk(self.lib.vp8hip_arf_filter_host(self.h, table, len(keep), int(centre), int(strength)), "arf_filter_host")
+        return self.arf_frame()
+
+    def arf_filter_device(self, ptrs, centre: int, strength: int):
+        """vp8hip_arf_filter_device: the same for ptrs = [(d_y, d_u, d_v), ...] device addresses"""
+        self.lib.vp8hip_arf_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        table = (C.c_void_p * (3 * len(ptrs)))(*[a for f in ptrs for a in f])
+        self._chk(self.lib.vp8hip_arf_filter_device(self.h, table, len(ptrs), int(centre), int(strength)), "arf_filter_device")
+
+    def incoming_size(self):
+        """size of the planes this view believes the context takes as current frames: what set_source_size / set_source_scaling of
+        THIS object said last (a borrowed view of a driver's context sets .src itself), else the coded size"""
+        w, h = getattr(self, "src", (0, 0))
+        return (w, h) if w and h else (self.W, self.H)
+
+    def arf_frame(self):
+        """the frame as it left the last temporal filter launch: (Y, U, V), tight, the incoming size (the debug tap)"""
+        return tuple(self.debug(DBG_ARF_FRAME, r) for r in (0, 1, 2))
+
+    def arf_result(self):
+        """vp8hip_arf_result: the (tile, frame) pairs of the last filter launch by block weight 0, 1, 2"""
+        wgt = (C.c_int32 * 3)()
+        self.lib.vp8hip_arf_result.argtypes = [C.c_void_p, C.c_void_p]
+        self._chk(self.lib.vp8hip_arf_result(self.h, wgt), "arf_result")
+        return [int(x) for x in wgt]
+
+    def arf_release(self):
+        self.lib.vp8hip_arf_release.argtypes = [C.c_void_p]
+        self._chk(self.lib.vp8hip_arf_release(self.h), "arf_release")
+
     def set_loop_filter_type(self, t: int):
         """vp8hip_set_loop_filter_type: 0 = the normal loop filter (default), 1 = the simple filter (RFC 6386 section 15.2),
         from the next loop_filter on.  The frame header's filter_type must say the same."""
@@ -1661,6 +1787,9 @@ class Vp8Hip:
             a = np.zeros((self.mbs, 25), np.uint8)
         elif what == DBG_CURRENT_CHROMA:
             a = np.zeros((self.H // 2, self.W // 2), np.uint8)
+        elif what == DBG_ARF_FRAME:      # ref 0..2: the filtered frame at the incoming size; 3..5: the ALTREF surface at the coded size
+            w, h = (self.W, self.H) if ref >= 3 else self.incoming_size()
+            a = np.zeros((h, w) if ref in (0, 3) else (h // 2, w // 2), np.uint8)
         else:
             a = np.zeros(self.mbs, np.int32)
         self._chk(self.lib.vp8hip_debug_download(self.h, what, ref, level, a.ctypes.data, a.nbytes), "debug_download")

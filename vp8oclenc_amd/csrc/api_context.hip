@@ -465,6 +465,8 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     c->di.release();
     c->an.release();      // (an_src and an_mb are parts of it)
     c->seg_buf.release();
+    c->arf_stage.release();
+    c->arf_in.release();
     if (c->own_stream) hipStreamDestroy(c->own_stream);
     delete c;
 }

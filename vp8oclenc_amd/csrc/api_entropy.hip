@@ -6,6 +6,9 @@ using namespace vp8;
 
 namespace vp8 {
 
+// the frame tag's show_frame bit: every frame but a hidden alternate reference frame
+static inline bool frame_shown(const vp8hip_header_params *p) { return p->is_key || p->is_altref != VP8HIP_ALTREF_HIDDEN; }
+
 // scratch of the boolean coder, allocated the first time the stage is used (a context that only runs the
 // inter path never pays for it): 64 bools per 4x4 block on average (of at most 304)
 void ent_free(vp8hip_ctx *c) {
@@ -116,7 +119,7 @@ int frame_prepare(vp8hip_ctx *c, int P, const vp8hip_header_params *p, FrameEntr
     e.modes = intra_info ? c->intra_modes : nullptr;
     e.f.is_key = p->is_key ? 1 : 0;
     e.f.is_golden = p->is_golden ? 1 : 0;
-    e.f.is_altref = p->is_altref ? 1 : 0;
+    e.f.is_altref = p->is_altref == VP8HIP_ALTREF_HIDDEN ? 2 : (p->is_altref ? 1 : 0);
     e.f.loop_filter_type = p->loop_filter_type;
     e.f.sharpness = p->loop_filter_sharpness;
     e.f.partitions_log2 = P == 8 ? 3 : (P == 4 ? 2 : (P == 2 ? 1 : 0));
@@ -312,7 +315,7 @@ int vp8hip_encode_header(vp8hip_ctx *c, const vp8hip_header_params *p, uint8_t *
     HdrFrame f;
     f.is_key = p->is_key ? 1 : 0;
     f.is_golden = p->is_golden ? 1 : 0;
-    f.is_altref = p->is_altref ? 1 : 0;
+    f.is_altref = p->is_altref == VP8HIP_ALTREF_HIDDEN ? 2 : (p->is_altref ? 1 : 0);
     f.loop_filter_type = p->loop_filter_type;
     f.sharpness = p->loop_filter_sharpness;
     f.partitions_log2 = p->partitions_log2;
@@ -332,7 +335,7 @@ int vp8hip_encode_header(vp8hip_ctx *c, const vp8hip_header_params *p, uint8_t *
     HIPCHK(c, hipMemcpyAsync(out + head, c->hdr.bytes, plan.nbytes[0], hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     // frame tag (entropy_host.cpp:1214-1247): key/inter bit, version 0, show_frame, size of the first partition
-    const uint32_t tag = (p->is_key ? 0u : 1u) | 0x10u | (plan.nbytes[0] << 5);
+    const uint32_t tag = (p->is_key ? 0u : 1u) | (frame_shown(p) ? 0x10u : 0u) | (plan.nbytes[0] << 5);
     out[0] = (uint8_t)tag;
     out[1] = (uint8_t)(tag >> 8);
     out[2] = (uint8_t)(tag >> 16);
@@ -423,7 +426,7 @@ int vp8hip_encode_frame_end(vp8hip_ctx *c, uint8_t *out, size_t capacity, size_t
     }
     memcpy(out + head, c->h_frame + 16 + head, n - head);
     const uint32_t first_part = reinterpret_cast<const uint32_t *>(c->h_frame)[1];   // size of the first partition, for the frame tag
-    const uint32_t tag = (p->is_key ? 0u : 1u) | 0x10u | (first_part << 5);
+    const uint32_t tag = (p->is_key ? 0u : 1u) | (frame_shown(p) ? 0x10u : 0u) | (first_part << 5);
     out[0] = (uint8_t)tag;
     out[1] = (uint8_t)(tag >> 8);
     out[2] = (uint8_t)(tag >> 16);

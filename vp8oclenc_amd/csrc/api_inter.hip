@@ -439,4 +439,40 @@ int vp8hip_loop_filter(vp8hip_ctx *c) {
     return VP8HIP_OK;
 }
 
+// The end of a HIDDEN inter frame (vp8hip_arf_filter_device): the filtered reconstruction becomes ALTREF -- a slot assignment -- and LAST
+// stays what it is, with the pyramid and border it has; lf_key, which speaks of LAST, is left alone.  Nobody rotates this surface
+// through LAST, where references get their replicated edges and their pyramid (pyramids()): both are made here, right behind the filter
+// on its stream.  No quality measurement and no analysis record: those count shown frames.
+int vp8hip_loop_filter_hidden(vp8hip_ctx *c) {
+    USE_DEVICE(c);
+    JOIN_LF(c);
+    if (!c) return VP8HIP_ERR_ARG;
+    // with vp8hip_filter_overlap the next frame's ALTREF search starts beside the filter in flight, and this filter writes ALTREF: refused
+    if (!c->recon_ready || c->recon < 0 || c->recon_key || c->lf_overlap || c->chk_armed || c->batch || c->shard_comm) return VP8HIP_ERR_STATE;
+    FrameSurf &fs = c->frames[c->recon];
+    const FilterItem it = filter_item(c);
+    {
+        Timed t(c, VP8HIP_K_LOOP_FILTER);
+        launch_loop_filter_of_type(c, c->stream, it);
+    }
+    build_pyramid(c, &fs.f, nullptr, 1u);
+    fs.pyramid_valid = fs.border_valid = true;
+    c->slot[2] = c->recon;
+    c->recon = -1;
+    c->recon_ready = false;
+    // The hidden frame leaves the intake as it found it: the two current surfaces trade places again and the count of frames taken in
+    // steps back, so the current frame is the last SHOWN frame once more and the next frame taken in finds it as its predecessor (what
+    // vp8hip_chroma_change compares with, what numbers the quality records, which slot holds whose segment map).  Everything that read
+    // the filtered frame is enqueued on this stream in front of whatever writes that surface next.
+    if (c->cur_count > 0) {
+        const Frame t = c->cur;
+        c->cur = c->cur_prev;
+        c->cur_prev = t;
+        c->cur_count--;
+        c->cur_pyramid_valid = false;
+    }
+    HIPCHK(c, hipGetLastError());
+    return VP8HIP_OK;
+}
+
 }  // extern "C"

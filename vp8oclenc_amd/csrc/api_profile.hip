@@ -132,6 +132,24 @@ int vp8hip_debug_download(vp8hip_ctx *c, int what, int ref, int level, void *dst
             if (rc) return rc;
             break;
         }
+        case VP8HIP_DBG_ARF_FRAME: {
+            if (ref < 0 || ref > 5) return VP8HIP_ERR_ARG;
+            if (ref < 3) {      // the frame as it left k_arf_filter_b: tight, the incoming size it was made at
+                if (!c->arf_w) return VP8HIP_ERR_STATE;
+                const TightI420 t = tight_i420(c->arf_w, c->arf_h);
+                const size_t n = ref ? (size_t)(c->arf_w / 2) * (c->arf_h / 2) : (size_t)c->arf_w * c->arf_h;
+                if (bytes != n) return VP8HIP_ERR_ARG;
+                HIPCHK(c, hipMemcpyAsync(dst, c->arf_stage.p + 256 + t.off[ref], n, hipMemcpyDeviceToHost, s));
+                break;
+            }
+            if (c->slot[2] < 0) return VP8HIP_ERR_STATE;
+            const Frame &f = c->frames[c->slot[2]].f;      // ALTREF: behind a hidden frame, its filtered reconstruction
+            const Plane &p = ref == 3 ? f.Y[0] : (ref == 4 ? f.U : f.V);
+            if (bytes != (size_t)p.w * p.h) return VP8HIP_ERR_ARG;
+            int rc = copy_out(c, dst, p);
+            if (rc) return rc;
+            break;
+        }
         case 100:  // diagnostic build only (-DLF2_STAMPS): cycle sums written by the loop filter
             if (bytes != 512) return VP8HIP_ERR_ARG;
             HIPCHK(c, hipMemcpyAsync(dst, (const char *)c->d_progress + 4096, 512, hipMemcpyDeviceToHost, s));

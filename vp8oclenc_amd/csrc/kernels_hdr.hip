@@ -220,10 +220,10 @@ __device__ __forceinline__ void hdr_frame_body(const Params &a, uint32_t *partia
             w.flag(0);
         } else {
             w.flag(a.is_golden);
-            w.flag(a.is_altref);
+            w.flag(a.is_altref != 0);
             if (!a.is_golden) w.literal(0, 2);
             if (!a.is_altref) w.literal(0, 2);
-            w.flag(0); w.flag(0); w.flag(0); w.flag(1);
+            w.flag(0); w.flag(0); w.flag(0); w.flag(a.is_altref != 2);      // refresh_last: not by a hidden frame (VP8HIP_ALTREF_HIDDEN)
         }
         s_n1 = w.n;
     }

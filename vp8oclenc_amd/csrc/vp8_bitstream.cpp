@@ -139,6 +139,7 @@ size_t vp8bs_encode_header(const vp8bs_frame *f, uint8_t *out, size_t capacity, 
     const bool key = f->is_key != 0;
     if (!key && (!f->MB_reference_frame || !f->MB_parts || !f->MB_vectors)) return 0;
     if (key && !f->modes) return 0;
+    const bool hidden = !key && f->is_altref == 2;   // a hidden alternate reference frame (VP8HIP_ALTREF_HIDDEN): not shown, LAST stays
     const size_t head = key ? 10 : 3;
     if (capacity < head + 8) return 0;
     const View v{f};
@@ -186,13 +187,13 @@ size_t vp8bs_encode_header(const vp8bs_frame *f, uint8_t *out, size_t capacity, 
         w.flag(0);                              // refresh_entropy_probs
     } else {
         w.flag(f->is_golden);                   // refresh_golden_frame, refresh_alternate_frame
-        w.flag(f->is_altref);
+        w.flag(f->is_altref != 0);
         if (!f->is_golden) w.literal(0, 2);     // no buffer copies
         if (!f->is_altref) w.literal(0, 2);
         w.flag(0);                              // sign biases
         w.flag(0);
         w.flag(0);                              // refresh_entropy_probs
-        w.flag(1);                              // refresh_last
+        w.flag(!hidden);                        // refresh_last
     }
     {   // token_prob_update(): every context that occurred gets its probability
         const uint8_t *upd = &k_coeff_update_probs[0][0][0][0];
@@ -266,7 +267,7 @@ size_t vp8bs_encode_header(const vp8bs_frame *f, uint8_t *out, size_t capacity, 
     if (first_part >= ((size_t)1 << 19)) return (size_t)-1;   // does not fit the frame tag's 19-bit size field: not a decodable frame
 
     // frame tag: key/inter bit, version 0, show_frame, 19 bits of first-partition size (section 9.1)
-    const uint32_t tag = (key ? 0u : 1u) | 0x10u | ((uint32_t)first_part << 5);
+    const uint32_t tag = (key ? 0u : 1u) | (hidden ? 0u : 0x10u) | ((uint32_t)first_part << 5);
     out[0] = (uint8_t)tag;
     out[1] = (uint8_t)(tag >> 8);
     out[2] = (uint8_t)(tag >> 16);

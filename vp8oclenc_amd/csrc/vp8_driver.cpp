@@ -35,6 +35,13 @@ struct vp8drv {
     int colour = 0;                  // vp8drv_set_source_colour: the colour matrix in force (read by BGRA / RGBA only)
     bool analysis = false;           // vp8drv_set_analysis
     bool in_batch = false;           // a member of a live vp8drv_batch
+    bool window = false;             // vp8drv_set_source_window: a window is in force
+    // vp8drv_set_arf: strength + 1 (0 = off).  last_hidden: the frame just coded is a hidden one.  rotation_consumed: a hidden frame's
+    // transform has applied the reference rotation the last shown frame owed; the next shown frame's must not apply it again.
+    // hidden_altref: ALTREF holds a hidden frame's reconstruction (until a key frame or a scheduled shown alt-ref rotates LAST into it).
+    int arf = 0;
+    bool last_hidden = false, rotation_consumed = false, hidden_altref = false;
+    vp8drv_arf_stats arf_st{};
     // read-back buffers of vp8drv_get_frame
     std::vector<int32_t> seg, nz, ref, parts, is_inter, modes;
     std::vector<int16_t> vectors;
@@ -170,6 +177,7 @@ int key_frame(vp8drv *d, const uint8_t *host_y) {
     d->st.frame_number = d->gop.frame_number;
     d->have_frame = true;
     d->last_key = d->last_altref = true;
+    d->last_hidden = d->rotation_consumed = d->hidden_altref = false;      // (LAST = GOLDEN = ALTREF = this frame, by the rotation it owes)
     d->checked = false;
     d->replaced = 0;
     return 1;
@@ -227,14 +235,21 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     DRV_CHK(segments(d, host_y, false, refqi));
     int32_t use_golden = 0, use_altref = 0;
     vp8host_gop_inter_flags(&d->gop, &use_golden, &use_altref);                  // inter_part.h:103-104
+    // vp8drv_encode_arf_*: a hidden frame's transform has applied the rotation already (again, and LAST would overwrite the new
+    // ALTREF); and while ALTREF holds a hidden frame's reconstruction it differs from GOLDEN whatever the frame numbers say
+    const int32_t prev_is_golden = d->rotation_consumed ? 0 : d->gop.prev_is_golden, prev_is_altref = d->rotation_consumed ? 0 : d->gop.prev_is_altref;
+    if (prev_is_altref) d->hidden_altref = false;
+    if (d->hidden_altref) use_altref = 1;
+    d->rotation_consumed = false;
+    d->last_hidden = false;
     use_golden &= d->cfg.ref_mask & 1;
     use_altref &= (d->cfg.ref_mask >> 1) & 1;
-    DRV_CHK(vp8hip_inter_transform(d->hip, d->gop.prev_is_golden, d->gop.prev_is_altref, use_golden, use_altref));
+    DRV_CHK(vp8hip_inter_transform(d->hip, prev_is_golden, prev_is_altref, use_golden, use_altref));
     d->st.last_use_golden = use_golden;
     d->st.last_use_altref = use_altref;
     d->st.refs_searched += 1 + use_golden + use_altref;
-    d->st.last_prev_is_golden = d->gop.prev_is_golden;
-    d->st.last_prev_is_altref = d->gop.prev_is_altref;
+    d->st.last_prev_is_golden = prev_is_golden;
+    d->st.last_prev_is_altref = prev_is_altref;
     d->st.last_was_altref = d->gop.current_is_altref;
     d->checked = false;
     d->replaced = 0;
@@ -292,7 +307,7 @@ vp8hip_header_params header_params(const vp8drv *d) {
     vp8hip_header_params hp{};
     hp.is_key = d->last_key;
     hp.is_golden = d->last_key;                 // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369)
-    hp.is_altref = d->last_altref;
+    hp.is_altref = d->last_hidden ? VP8HIP_ALTREF_HIDDEN : d->last_altref;
     hp.loop_filter_type = d->cfg.loop_filter_type;   // 0 in the reference (init.h:1583)
     hp.loop_filter_sharpness = d->sharpness;    // or VP8HIP_SHARPNESS_ON_DEVICE
     hp.width = d->cfg.display_width;
@@ -365,7 +380,7 @@ int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     f.mb_height = d->H / 16;
     f.is_key = d->last_key;
     f.is_golden = d->last_key;                  // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369)
-    f.is_altref = d->last_altref;
+    f.is_altref = d->last_hidden ? VP8HIP_ALTREF_HIDDEN : d->last_altref;
     f.loop_filter_type = d->cfg.loop_filter_type;    // 0 in the reference (init.h:1583)
     f.loop_filter_sharpness = sharp;
     f.partitions_log2 = P == 8 ? 3 : (P == 4 ? 2 : (P == 2 ? 1 : 0));
@@ -460,7 +475,8 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
     for (int i = 0; i < n; ++i) {
         // the batched loop is the device-parameter loop (what bench.py and a file-to-file transcode run); one launch serves all
         // members, so what travels as ONE kernel argument must agree: quantizer range, check_SSIM on or off, partitions, filter type
-        if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect) return VP8HIP_ERR_ARG;
+        if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect || drv[i]->arf || drv[i]->rotation_consumed || drv[i]->hidden_altref)
+            return VP8HIP_ERR_ARG;      // (hidden frames are not batched, nor is a driver whose references a hidden frame still shapes)
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
@@ -683,6 +699,7 @@ int vp8drv_set_source_window(vp8drv *d, const int32_t *pitch, int x, int y) {
     if (d->in_batch) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     DRV_CHK(vp8hip_set_source_window(d->hip, pitch, x, y));
+    d->window = pitch != nullptr;
     d->staged = nullptr;             // planes staged through another window are not this window's frame
     d->staged_scan = false;
     return VP8HIP_OK;
@@ -757,6 +774,79 @@ int vp8drv_get_denoise_stats(vp8drv *d, vp8hip_denoise_stats *s) {
 int vp8drv_get_deinterlace_stats(vp8drv *d, vp8hip_deinterlace_stats *s) {
     if (!d || !s) return VP8HIP_ERR_ARG;
     return vp8hip_deinterlace_result(d->hip, s);
+}
+
+// ---- hidden alternate reference frames ------------------------------------------------------------------------------------------------
+int vp8drv_set_arf(vp8drv *d, int strength_plus_one) {
+    if (!d || strength_plus_one < 0 || strength_plus_one > 7) return VP8HIP_ERR_ARG;
+    if (strength_plus_one && (!d->cfg.device_params || d->cfg.overlap_filter || d->format || d->window || d->deinterlace ||
+                              d->denoise || d->analysis))
+        return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    d->arf = strength_plus_one;
+    if (!strength_plus_one && d->arf_st.hidden_frames) (void)vp8hip_arf_result(d->hip, d->arf_st.last_weight);
+    if (!strength_plus_one) return vp8hip_arf_release(d->hip);      // (the staging buffers only: the current frame and ALTREF are surfaces)
+    return VP8HIP_OK;
+}
+
+// The filtered frame is the context's current frame: code it as an inter frame on the finer ladder, with the references the next
+// shown frame would be allowed, no check_SSIM, and the reconstruction into ALTREF.  The GOP state, the frame counters, the scene
+// history and the quality summary are not touched: they count shown frames.
+static int hidden_frame(vp8drv *d) {
+    DRV_CHK(segments(d, nullptr, false, d->altrefqi));
+    // the rotation the last shown frame owes (vp8host_gop_next would name it prev_is_*), unless a hidden frame has applied it already
+    const int32_t owed_golden = d->rotation_consumed ? 0 : d->gop.current_is_golden, owed_altref = d->rotation_consumed ? 0 : d->gop.current_is_altref;
+    if (owed_altref) d->hidden_altref = false;
+    int32_t use_golden = !d->gop.current_is_golden;
+    int32_t use_altref = !owed_altref && (d->hidden_altref || d->gop.altref_frame_number != d->gop.golden_frame_number);
+    use_golden &= d->cfg.ref_mask & 1;
+    use_altref &= (d->cfg.ref_mask >> 1) & 1;
+    DRV_CHK(vp8hip_inter_transform(d->hip, owed_golden, owed_altref, use_golden, use_altref));
+    d->rotation_consumed = true;
+    DRV_CHK(vp8hip_loop_filter_hidden(d->hip));
+    d->hidden_altref = true;
+    d->have_frame = true;
+    d->last_key = false;
+    d->last_altref = true;
+    d->last_hidden = true;
+    d->checked = false;
+    d->replaced = 0;
+    d->arf_st.hidden_frames++;
+    d->arf_st.last_use_golden = use_golden;
+    d->arf_st.last_use_altref = use_altref;
+    return VP8HIP_OK;
+}
+
+static int arf_check(vp8drv *d, const void *frames, int n, int centre) {
+    if (!d || !frames || n < 1 || n > VP8HOST_ARF_MAX_FRAMES || centre < 0 || centre >= n) return VP8HIP_ERR_ARG;
+    if (d->format || d->window || d->deinterlace || d->denoise || d->analysis || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (!d->arf || d->in_batch || !d->have_frame || d->staged) return VP8HIP_ERR_STATE;      // (off; batched; no reference yet; a frame handed over early is the current frame)
+    const int rc = resolve(d);                                                                // the open check_SSIM verdict first
+    return rc < 0 ? rc : VP8HIP_OK;
+}
+
+int vp8drv_encode_arf_device(vp8drv *d, const void *const (*frames)[3], int n, int centre) {
+    DRV_CHK(arf_check(d, frames, n, centre));
+    DRV_CHK(vp8hip_arf_filter_device(d->hip, frames, n, centre, d->arf - 1));
+    d->arf_st.last_frames = n;
+    return hidden_frame(d);
+}
+
+int vp8drv_encode_arf_host(vp8drv *d, const uint8_t *const (*frames)[3], int n, int centre) {
+    DRV_CHK(arf_check(d, frames, n, centre));
+    DRV_CHK(vp8hip_arf_filter_host(d->hip, frames, n, centre, d->arf - 1));
+    d->arf_st.last_frames = n;
+    return hidden_frame(d);
+}
+
+int vp8drv_get_arf_stats(vp8drv *d, vp8drv_arf_stats *s) {
+    if (!d || !s) return VP8HIP_ERR_ARG;
+    if (!d->arf_st.hidden_frames) return VP8HIP_ERR_STATE;
+    const int rc = vp8hip_arf_result(d->hip, d->arf_st.last_weight);      // (VP8HIP_ERR_STATE: released by vp8drv_set_arf(d, 0), which kept them)
+    if (rc != VP8HIP_OK && rc != VP8HIP_ERR_STATE) return rc;
+    *s = d->arf_st;
+    return VP8HIP_OK;
 }
 
 int vp8drv_ready(const vp8drv *d) { return !d || !d->verdict_pending || vp8hip_check_ssim_ready(d->hip); }

@@ -813,3 +813,103 @@ extern "C" int vp8host_orient_frame(int turns, int mirror, int raw_width, int ra
     orient_plane(in_v, out_v, raw_width / 2, raw_height / 2, turns, mirror);
     return 0;
 }
+
+// The temporal filter of the hidden alternate reference frame in plain C++ (include/vp8hip_host.h has the rule).
+namespace {
+
+// sample (x, y) of a tight plane of w x h extended by its last column and row (coordinates below 0 never count, they are clamped too)
+inline int arf_at(const uint8_t *p, int w, int h, int x, int y) {
+    x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x);
+    y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
+    return p[(size_t)y * w + x];
+}
+
+// one block of bs x bs samples at (bx, by) of plane `o` (centre) against `p` displaced by (dx, dy), block weight bw: into acc / count
+void arf_accumulate(const uint8_t *o, const uint8_t *p, int w, int h, int bx, int by, int bs, int dx, int dy, int bw, int strength,
+                    uint32_t *acc, uint32_t *count) {
+    const int r = strength ? 1 << (strength - 1) : 0;
+    for (int y = 0; y < bs; ++y)
+        for (int x = 0; x < bs; ++x) {
+            const int ov = arf_at(o, w, h, bx + x, by + y), pv = arf_at(p, w, h, bx + x + dx, by + y + dy);
+            const int d = ov - pv;
+            int m = (3 * d * d + r) >> strength;
+            m = 16 - (m < 16 ? m : 16);
+            count[y * bs + x] += (uint32_t)(m * bw);
+            acc[y * bs + x] += (uint32_t)(m * bw * pv);
+        }
+}
+
+void arf_put(uint8_t *out, int w, int h, int bx, int by, int bs, const uint32_t *acc, const uint32_t *count) {
+    for (int y = 0; y < bs && by + y < h; ++y)
+        for (int x = 0; x < bs && bx + x < w; ++x) {
+            const uint32_t n = count[y * bs + x];
+            out[(size_t)(by + y) * w + bx + x] = (uint8_t)VP8HOST_ARF_DIVIDE(acc[y * bs + x] + n / 2, VP8HOST_ARF_RECIPROCAL(n));
+        }
+}
+
+}  // namespace
+
+extern "C" void vp8host_arf_round_divide(const uint32_t *acc, const uint32_t *count, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; ++i) out[i] = VP8HOST_ARF_DIVIDE(acc[i] + count[i] / 2, VP8HOST_ARF_RECIPROCAL(count[i]));
+}
+
+extern "C" int vp8host_arf_filter_frame(const uint8_t *const *frames, int n, int centre, int strength, int width, int height, uint8_t *out_y,
+                                        uint8_t *out_u, uint8_t *out_v, int32_t weights[3], int8_t *vectors) {
+    if (!frames || !out_y || !out_u || !out_v || n < 1 || n > VP8HOST_ARF_MAX_FRAMES || centre < 0 || centre >= n || strength < 0 || strength > 6 ||
+        width < 2 || height < 2 || (width & 1) || (height & 1))
+        return -1;
+    for (int i = 0; i < 3 * n; ++i)
+        if (!frames[i]) return -1;
+    const int cw = width / 2, ch = height / 2, tw = (width + 15) / 16, th = (height + 15) / 16, We = tw * 16, He = th * 16;
+    if (weights) weights[0] = weights[1] = weights[2] = 0;
+    const uint8_t *const *C = frames + 3 * centre;
+    uint32_t acc[3][256], count[3][256];
+    for (int ty = 0; ty < th; ++ty)
+        for (int tx = 0; tx < tw; ++tx) {
+            const int x0 = tx * 16, y0 = ty * 16;
+            memset(acc, 0, sizeof acc);
+            memset(count, 0, sizeof count);
+            for (int k = 0; k < n; ++k) {
+                const uint8_t *const *F = frames + 3 * k;
+                int dx = 0, dy = 0, bw = 2;
+                if (k != centre) {
+                    uint32_t best = 0xFFFFFFFFu;
+                    for (int cy = -8; cy <= 7; ++cy)
+                        for (int cx = -8; cx <= 7; ++cx) {
+                            if (x0 + cx < 0 || x0 + cx + 16 > We || y0 + cy < 0 || y0 + cy + 16 > He) continue;
+                            uint32_t sad = 0;
+                            for (int y = 0; y < 16; ++y)
+                                for (int x = 0; x < 16; ++x) {
+                                    const int d = arf_at(C[0], width, height, x0 + x, y0 + y) - arf_at(F[0], width, height, x0 + x + cx, y0 + y + cy);
+                                    sad += (uint32_t)(d < 0 ? -d : d);
+                                }
+                            const uint32_t key = sad << 13 | (uint32_t)((cx < 0 ? -cx : cx) + (cy < 0 ? -cy : cy)) << 8 | (uint32_t)(cy + 8) << 4 | (uint32_t)(cx + 8);
+                            if (key < best) best = key;
+                        }
+                    dx = (int)(best & 15u) - 8;
+                    dy = (int)((best >> 4) & 15u) - 8;
+                    uint32_t sse = 0;
+                    for (int y = 0; y < 16; ++y)
+                        for (int x = 0; x < 16; ++x) {
+                            const int d = arf_at(C[0], width, height, x0 + x, y0 + y) - arf_at(F[0], width, height, x0 + x + dx, y0 + y + dy);
+                            sse += (uint32_t)(d * d);
+                        }
+                    bw = sse < VP8HOST_ARF_THRESH_LOW ? 2 : (sse < VP8HOST_ARF_THRESH_HIGH ? 1 : 0);
+                    if (weights) ++weights[bw];
+                }
+                if (vectors) {
+                    int8_t *v = vectors + ((size_t)(ty * tw + tx) * n + k) * 2;
+                    v[0] = (int8_t)dx;
+                    v[1] = (int8_t)dy;
+                }
+                if (!bw) continue;
+                arf_accumulate(C[0], F[0], width, height, x0, y0, 16, dx, dy, bw, strength, acc[0], count[0]);
+                arf_accumulate(C[1], F[1], cw, ch, x0 / 2, y0 / 2, 8, dx >> 1, dy >> 1, bw, strength, acc[1], count[1]);
+                arf_accumulate(C[2], F[2], cw, ch, x0 / 2, y0 / 2, 8, dx >> 1, dy >> 1, bw, strength, acc[2], count[2]);
+            }
+            arf_put(out_y, width, height, x0, y0, 16, acc[0], count[0]);
+            arf_put(out_u, cw, ch, x0 / 2, y0 / 2, 8, acc[1], count[1]);
+            arf_put(out_v, cw, ch, x0 / 2, y0 / 2, 8, acc[2], count[2]);
+        }
+    return 0;
+}

@@ -210,6 +210,11 @@ struct vp8hip_ctx {
     bool seg_map_set = false;
     int aq_frame[2] = {-1, -1};
     DeviceBuf seg_buf;
+    // vp8hip_arf_filter_device: arf_stage, made on first use and grown with the incoming size: the weight words of k_arf_filter_b
+    // at 0, the filtered frame (tight_i420 of the incoming size) at 256.  arf_w x arf_h: the size the frame in it was made at (0: none).
+    // arf_in: the window of vp8hip_arf_filter_host on its way to the device.
+    DeviceBuf arf_stage, arf_in;
+    int arf_w = 0, arf_h = 0;
     int conformant = 0;             // vp8hip_conformant_stream (NOT the reference; off by default)
     int lf_stall_test = 0;          // test hook (vp8hip_debug_lf_stall): make the next loop filters / intra wavefronts time out
     // vp8hip_set_quality_stats: the record (quality.d: the state, the ticket and the per-wave partials of k_quality)

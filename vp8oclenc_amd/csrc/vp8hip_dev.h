@@ -236,6 +236,13 @@ struct GeometryItem { const uint8_t *src[3]; uint8_t *dst[3]; };
 void launch_window_batch(hipStream_t s, const size_t offset[3], const int32_t pitch[3], const int32_t row_bytes[3], const int32_t rows[3],
                          const GeometryItem *items, int n);
 void launch_orient_batch(hipStream_t s, int turns, int mirror, int raw_w, int raw_h, const GeometryItem *items, int n);
+// kernels_arf.hip: the temporal filter of a hidden alternate reference frame (vp8hip_arf_filter_device); the rule is
+// include/vp8hip_host.h's.  src: n frames of tight I420 of w x h in device memory; dst: the filtered frame, tight, which overlaps none
+// of them; weights: ARF_WEIGHT_SLOTS 64-bit words (the caller zeroes them in front of the launch) whose SUM holds the (tile, frame) pairs
+// by block weight 0, 1, 2 in three fields of 21 bits (at most 6 pairs a tile: room for 349 000 tiles).
+constexpr int ARF_WEIGHT_SLOTS = 32;
+struct ArfItem { const uint8_t *src[7][3]; uint8_t *dst[3]; unsigned long long *weights; int w, h, n, centre, strength; };
+void launch_arf_filter(hipStream_t s, const ArfItem &item);
 // check_SSIM's verdict riding in a loop filter launch (see CheckItem below)
 struct LfCheck {
     int on, qi_min;

@@ -35,6 +35,10 @@ class InterPathDriver:
         self.key_frames = 0
         self.redone_as_key = 0
         self.last_key = None
+        # hidden alternate reference frames (encode_hidden; the native loop: vp8drv_encode_arf_*, include/vp8hip_driver.h)
+        self.hidden_frames = 0
+        self.rotation_consumed = False       # a hidden frame's transform has applied the rotation the last shown frame owed
+        self.hidden_altref = False           # ALTREF holds a hidden frame's reconstruction
         # vp8hip_set_segment_mode (include/vp8hip.h): inter frames coded once per macroblock in the segment a map names.  The device
         # backend only: the CPU oracle has no mapped pass (tests/segment_map_ref.py assembles its result from the oracle's stages)
         if segment_mode:
@@ -60,6 +64,7 @@ class InterPathDriver:
         self.be.set_segments(sd)
         self.be.intra_transform()
         self.gop.key_coded()                                                    # intra_part.h:1091-1098
+        self.rotation_consumed = self.hidden_altref = False                     # LAST = GOLDEN = ALTREF = this frame, by the rotation it owes
         if self.download:
             self.last_key = self.be.download_results(recon=True)
             self.last_key["segments"] = sd
@@ -80,8 +85,14 @@ class InterPathDriver:
         sd = self.segments_for(y, False, bool(g.current_is_altref))             # vp8enc.cpp:419
         self.be.set_segments(sd)
         use_golden, use_altref = self.gop.inter_flags()                         # inter_part.h:103-104
+        prev_is_golden, prev_is_altref = (0, 0) if self.rotation_consumed else (g.prev_is_golden, g.prev_is_altref)
+        if prev_is_altref:
+            self.hidden_altref = False
+        if self.hidden_altref:                                                  # it differs from GOLDEN whatever the frame numbers say
+            use_altref = 1
+        self.rotation_consumed = False
         use_golden, use_altref = use_golden & (self.ref_mask & 1), use_altref & ((self.ref_mask >> 1) & 1)
-        self.be.inter_transform(g.prev_is_golden, g.prev_is_altref, use_golden, use_altref)
+        self.be.inter_transform(prev_is_golden, prev_is_altref, use_golden, use_altref)
         out = {"segments": sd, "use_golden": use_golden, "use_altref": use_altref, "is_altref": int(g.current_is_altref)}
         if self.check:
             replaced, new_ssim, min1 = self.be.check_ssim()                     # vp8enc.cpp:442, 231-263
@@ -102,4 +113,32 @@ class InterPathDriver:
         self.be.loop_filter()                                                   # vp8enc.cpp:473
         self.gop.frame_done()
         self.inter_frames += 1
+        return out
+
+    def encode_hidden(self, frames, centre: int, strength: int):
+        """A hidden alternate reference frame (vp8drv_encode_arf_host): the window frames = [(Y, U, V), ...] through the temporal filter
+        (backend.arf_filter), the filtered frame coded as an inter frame on the altrefqi ladder with the references the next shown frame
+        would be allowed, no check_SSIM, the reconstruction into ALTREF while LAST stays (backend.loop_filter_hidden).  The GOP state
+        and the frame counters are left alone.  Returns the frame's outputs; out["is_altref"] = api.ALTREF_HIDDEN."""
+        s = self.gop.s                                                          # the last shown frame's flags: what gop.next() will call prev_is_*
+        if s.frame_number == 0 and not (self.key_frames or self.inter_frames):
+            raise api.Vp8HipError("encode_hidden: no reference yet")
+        y, u, v = self.be.arf_filter(frames, centre, strength)                  # ... and it is the backend's current frame
+        sd = self.segments_for(y, False, True)
+        self.be.set_segments(sd)
+        owed_golden, owed_altref = (0, 0) if self.rotation_consumed else (int(s.current_is_golden), int(s.current_is_altref))
+        if owed_altref:
+            self.hidden_altref = False
+        use_golden = int(not s.current_is_golden) & (self.ref_mask & 1)
+        use_altref = int((not owed_altref) and (self.hidden_altref or s.altref_frame_number != s.golden_frame_number)) & ((self.ref_mask >> 1) & 1)
+        self.be.inter_transform(owed_golden, owed_altref, use_golden, use_altref)
+        self.rotation_consumed = True
+        out = {"segments": sd, "use_golden": use_golden, "use_altref": use_altref, "is_altref": api.ALTREF_HIDDEN, "filtered": (y, u, v)}
+        if self.download:
+            out.update(self.be.download_results(recon=True))
+        out["sharpness"] = self.sharpness
+        self.be.prepare_filter_mask(want_nz=False)
+        self.be.loop_filter_hidden()
+        self.hidden_altref = True
+        self.hidden_frames += 1
         return out

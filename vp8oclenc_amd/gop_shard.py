@@ -142,3 +142,47 @@ def write_ivf(path: str, frames: list[bytes], width: int, height: int, framerate
             f.write(bitstream.ivf_frame_header(len(b), t))
             f.write(b)
     return 32 + sum(12 + len(b) for b in frames)
+
+
+# ---- hidden alternate reference frames: where the tools put them (vp8drv_encode_arf_*, include/vp8hip_driver.h) ----
+def parse_arf(text: str) -> tuple[int, int, int]:
+    """PERIOD[:FRAMES[:STRENGTH]] -> (period, frames, strength); FRAMES 1..7 (default 7), STRENGTH 0..6 (default 3)"""
+    v = [int(x) for x in text.split(":")]
+    if not 1 <= len(v) <= 3:
+        raise ValueError("PERIOD[:FRAMES[:STRENGTH]]")
+    period, frames, strength = v + [7, 3][len(v) - 1:]
+    if period < 1 or not 1 <= frames <= 7 or not 0 <= strength <= 6:
+        raise ValueError("PERIOD >= 1, FRAMES 1..7, STRENGTH 0..6")
+    return period, frames, strength
+
+
+def hidden_frame_events(length: int, period: int, max_frames: int = 7):
+    """The calls that code one closed GOP of `length` frames with hidden frames, in stream order (what scripts/native/y4m_to_ivf -arf
+    does): ('shown', t) and ('hidden', first frame of the window, frames in it, the centre's index in it, timestamp).  In front of the
+    first frame of every group of `period` frames -- behind the key frame for the first group -- a hidden frame centred on the group's
+    last frame, its window of max_frames frames clipped to the GOP; its timestamp is the next shown frame's."""
+    out = []
+    for t in range(length):
+        hidden = None
+        if t % period == 0:
+            last = min(t + period, length) - 1
+            if last != 0:      # (a group that is the key frame alone has none)
+                lo, hi = max(0, last - max_frames // 2), min(length - 1, last + max_frames // 2)
+                hidden = ("hidden", lo, hi - lo + 1, last - lo, t + 1 if t == 0 else t)
+        if hidden and t:
+            out.append(hidden)
+        out.append(("shown", t))
+        if hidden and not t:
+            out.append(hidden)
+    return out
+
+
+def write_ivf_records(path: str, records, width: int, height: int, framerate: int = 30, timescale: int = 1) -> int:
+    """write_ivf for (timestamp, bytes) records: a hidden frame is a record of its own and the header's count includes it"""
+    from . import bitstream
+    with open(path, "wb") as f:
+        f.write(bitstream.ivf_file_header(width, height, framerate, timescale, len(records) + 1))
+        for ts, b in records:
+            f.write(bitstream.ivf_frame_header(len(b), ts))
+            f.write(b)
+    return 32 + sum(12 + len(b) for _, b in records)
