@@ -316,14 +316,18 @@ __device__ __forceinline__ void s1_subblock(const uint8_t *cp, int cstride, cons
 // per sub-block; as instructions of the wave they cost what they cost one lane.  The column pass of a candidate is one MFMA for the whole wave
 // (weight_mfma, vp8hip_dev.h; every lane of the wave runs this), B = its four columns, C = the current block's share, read again from LDS for each
 // candidate: held in registers next to the 16 results it would cost 16 registers, and the loop form is tuned for eight waves per SIMD.  The
-// offset passes through an empty asm per candidate so that the compiler cannot see the five reads are the same and keep one copy (it did, and
-// then copied 16 registers into the accumulator before every MFMA); hiding the pointer instead makes the reads flat loads.  The B operand of
+// address passes through an empty asm per candidate so that the compiler cannot see the five reads are the same and keep one copy (it did, and
+// then copied 16 registers into the accumulator before every MFMA); hiding the pointer instead makes the reads flat loads.  What passes is the
+// lane's BYTE address in the table (pre_addr: s1_pre_c_bytes / s1_fill_c_bytes), in the ONE register that carries it through the sub-block loop:
+// each asm hands on what the one before it left and the caller steps it from sub-block to sub-block, so the four ds_read_b128 of a candidate take
+// the register as it stands, the quad in their offset field -- no copy and no shift per candidate (an int index hidden afresh from a value kept
+// beside it cost a v_mov_b32 and a v_lshlrev_b32 for each of the five).  The B operand of
 // a candidate is made right before its MFMA, behind a scheduling barrier: left to itself hipcc built all five quads up front and spilled at 64.
 // History: the operand used to be in column order (K_METRIC_A), which cost two 4x4 byte transposes of the window (16 v_perm) and, an MFMA
 // operand being an even-aligned register quad, eight v_mov for candidates 1 and 3.  With the A table in row order (wa = metric_a_rows,
 // vp8hip_dev.h) candidate dx = i is bytes i..i+3 of the four rows: the low dwords as loaded (i = 0), the high dwords (i = 4), and one
 // v_alignbyte per row, written straight into an aligned quad, for the three between -- 12 instructions where 24 stood.
-__device__ __forceinline__ void s1_subblock_pre(v4i wa, const int *pre_lds, int pre_off, const uint8_t *rp, int rstride, int acc[5]) {
+__device__ __forceinline__ void s1_subblock_pre(v4i wa, const int *pre_lds, int &pre_addr, const uint8_t *rp, int rstride, int acc[5]) {
     uint32_t q0[4], q1[4];      // bytes 0..3 and 4..7 of the window's four rows, pixels biased
 #pragma unroll
     for (int y = 0; y < 4; ++y) {
@@ -332,13 +336,12 @@ __device__ __forceinline__ void s1_subblock_pre(v4i wa, const int *pre_lds, int 
     }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-        int off = pre_off;
-        asm volatile("" : "+v"(off));
+        asm volatile("" : "+v"(pre_addr));
         __builtin_amdgcn_sched_barrier(0);
         v4i b;
 #pragma unroll
         for (int y = 0; y < 4; ++y) b[y] = i == 0 ? (int)q0[y] : i == 4 ? (int)q1[y] : (int)__builtin_amdgcn_alignbyte(q1[y], q0[y], (uint32_t)i);
-        acc[i] += weight_mfma(wa, load_pre16(pre_lds + off), b);
+        acc[i] += weight_mfma(wa, load_pre16(reinterpret_cast<const int *>(reinterpret_cast<const char *>(pre_lds) + pre_addr)), b);
     }
 }
 // ... made by the wave for its twelve blocks: lane = (block slot, sub-block), 48 of the 64 lanes; 16 ints each into pre_lds[slot][sub-block][16].
@@ -372,7 +375,7 @@ __device__ __forceinline__ void s1_make_pre(const Plane &cur, int cx, int cy, in
 template <bool SPLIT, bool PRE_LDS = false, bool LDS_MIN = false>
 __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, int cx, int cy, uint32_t pv, bool live, int sub, int lane,
                                                   const int *pre_lds = nullptr /* PRE_LDS (loop form): the workgroup's table from s1_make_pre */,
-                                                  int pre_off = 0 /* ... and where this block's [sub-block][16] start in it */,
+                                                  int pre_off = 0 /* ... and where this block's [sub-block][16] start in it, in BYTES */,
                                                   uint32_t *min_lds = nullptr /* LDS_MIN: the word of this block's first lane */) {
     const int sb0 = sub / 5, j = sub - 5 * sb0;       // SPLIT: this lane's sub-block; otherwise sb0 = 0
     // vector / pixel_rate truncates toward zero (:495-500)
@@ -404,10 +407,12 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
         // one sub-block at a time (loop NOT unrolled: the register footprint decides how many waves a SIMD holds)
         if (PRE_LDS) {
             const v4i wa = metric_a_rows(lane);
+            int pre_addr = pre_off;     // sub-block 0 of this lane's block; stepped by the loop, in the register the reads take it from
 #pragma unroll 1
             for (int sb = 0; sb < 4; ++sb) {
                 const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;
-                s1_subblock_pre(wa, pre_lds, pre_off + s1_pre_sub_at(sb), rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
+                s1_subblock_pre(wa, pre_lds, pre_addr, rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
+                pre_addr += s1_pre_sub_bytes(1);
             }
         } else {
 #pragma unroll 1
@@ -419,15 +424,51 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
     }
     const int pen_mask = a.pixel_rate < 4 ? -1 : 0;     // x 32 on the two finest levels, x 0 above (a shift and a mask: `* pen_scale' with a scale the compiler cannot see compiles to a 64-bit multiply-add per candidate)
     const int pen_y = iabs(iabs(py - cy) - v0y);
+    // The five candidates' keys, two candidates to a register (candidates (0, 1), (2, 3) and 4).  The ranges that make 16 bits enough:
+    //   * A candidate that is valid has not wrapped: px = cx + v0x - 2 + i lies in [0, w - 8], so px - cx = v0x + i - 2 as integers, and with
+    //     cx, px < 8192 (a frame is at most 8192 wide) |px - cx| < 8192 and |v0x| < 8194: v0x + (i - 2), its negation, |px - cx| - v0x (within
+    //     +-16386) and the absolute value of that all fit int16 -- v_pk_add_u16, v_pk_sub_i16, v_pk_max_i16 give what the 32-bit forms gave.
+    //     pen_y is the same quantity along y for the lane's row, made in 32 bits as before: at most 16386 for a valid row.
+    //   * The accumulator is a ushort by definition (& 0xffff), the penalty is added into it modulo 2^16, and x 32 modulo 2^16 is what (<< 5) &
+    //     0xffff was: (penalty x scale + acc) in one v_pk_mad_u16, scale = 32 on the two finest levels and 0 above (what pen_mask did).
+    //   * An invalid candidate's diff is never looked at, so what its lanes of the arithmetic hold (wrapped, anything) does not matter: its
+    //     half gets 0x8000 added behind the clamp to 0x7fff -- its column tested as (uint16)px > w - 8, which is px < 0 || px > w - 8 for the
+    //     wrapped 16-bit px = (int16)(xb + i) since w - 8 < 32768 -- and a row that cannot hold a valid candidate loses its whole lane (loadable).
+    //   * diff < 0x7fff becomes a clamp: min(diff, 0x7fff), and every key from 0x7fff00 up means "not accepted".  Such keys lose against every
+    //     accepted one in the minimum (over the candidates, then over the block's lanes), and when the minimum itself is one of them nothing was
+    //     accepted: the test behind the minimum is best < 0x7fff00 where it was best != 0xffffffff.  The same integer wins as before.
+    // Only the key (diff << 8 | j * 5 + i: one v_perm_b32 from the pair and a register of the lane's five numbers) and the minimum take 32 bits.
     uint32_t best = 0xffffffffu;
+    {
+        const u16x2 v0xp = {(unsigned short)v0x, (unsigned short)v0x}, cxp = {(unsigned short)cx, (unsigned short)cx};
+        const u16x2 penyp = {(unsigned short)pen_y, (unsigned short)pen_y}, wlim = {(unsigned short)(a.w - 8), (unsigned short)(a.w - 8)};
+        const unsigned short sc = (unsigned short)(32 & pen_mask);
+        const u16x2 scale = {sc, sc};
+        const uint32_t codes03 = (uint32_t)(j * 5) * 0x01010101u + 0x03020100u, code4 = (uint32_t)(j * 5 + 4);
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int px = (int16_t)(xb + i);
-        const bool valid = loadable && px >= 0 && px <= a.w - 8;
-        // :542-543 (sic): |displacement| minus the signed parent vector, only on the two finest levels
-        const int diff = (acc[i] + (((iabs(iabs(px - cx) - v0x) + pen_y) << 5) & pen_mask)) & 0xffff;   // ushort accumulator
-        const uint32_t key = (valid && diff < 0x7fff) ? ((uint32_t)diff << 8) | (uint32_t)(j * 5 + i) : 0xffffffffu;
-        best = key < best ? key : best;
+        for (int p = 0; p < 3; ++p) {
+            const int i0 = 2 * p;
+            const s16x2 off = {(short)(i0 - 2), (short)(i0 - 1)};
+            const s16x2 rel = __builtin_bit_cast(s16x2, v0xp) + off;
+            const s16x2 nrel = -rel, arel = __builtin_elementwise_max(rel, nrel);
+            const s16x2 dd = arel - __builtin_bit_cast(s16x2, v0xp), ndd = -dd, e = __builtin_elementwise_max(dd, ndd);
+            const u16x2 accp = __builtin_bit_cast(u16x2, pk16(acc[i0], p < 2 ? acc[i0 + 1] : 0));
+            u16x2 diff = __builtin_elementwise_min((u16x2)((__builtin_bit_cast(u16x2, e) + penyp) * scale + accp), (u16x2){0x7fff, 0x7fff});
+            const u16x2 pxu = cxp + __builtin_bit_cast(u16x2, rel);
+            // px - (w - 8) saturating at 0, at most 1, times 0x8000, added: a half whose column is out of the frame comes out >= 0x8000, the
+            // others unchanged.  (Inline: written in C the compiler turns the three packed instructions into two compares, two selects, a
+            // permute and an or per pair.  Plain vector instructions on plain vector results: no hazard the compiler would have to see.)
+            uint32_t d = __builtin_bit_cast(uint32_t, diff), over;
+            asm("v_pk_sub_u16 %1, %2, %3 clamp\n\tv_pk_min_u16 %1, %1, 1 op_sel_hi:[1,0]\n\tv_pk_mad_u16 %0, %1, %4, %0"
+                : "+v"(d), "=&v"(over) : "v"(__builtin_bit_cast(uint32_t, pxu)), "v"(__builtin_bit_cast(uint32_t, wlim)), "s"(0x80008000u));
+            const uint32_t k0 = __builtin_amdgcn_perm(d, p < 2 ? codes03 : code4, p == 1 ? 0x0c050402u : 0x0c050400u);
+            best = k0 < best ? k0 : best;
+            if (p < 2) {
+                const uint32_t k1 = __builtin_amdgcn_perm(d, codes03, p == 1 ? 0x0c070603u : 0x0c070601u);
+                best = k1 < best ? k1 : best;
+            }
+        }
+        best = loadable ? best : 0xffffffffu;
     }
     // minimum over the five dy lanes of the block (its sb = 0 lanes hold the full sums): (cost << 8 | dxy) = the
     // reference's first strict minimum
@@ -447,8 +488,8 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
         }
     }
     int bx, by;  // best position minus block position
-    if (best != 0xffffffffu) {
-        const int k = best & 0xff;
+    if (best < (0x7fffu << 8)) {
+        const int k = best & 0xff;      // (an accepted key: see the ranges above)
         bx = v0x + (k % 5 - 2);
         by = v0y + (k / 5 - 2);
     } else {  // nothing accepted: "vector" still holds the scaled parent, :501,:551-556
@@ -502,7 +543,7 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
         s1_make_pre(a.cur, tbx * 8, tby * 8, sb, slot < S1_FILL_BLOCKS, s_fill + s1_fill_slot_at(slot) + s1_pre_sub_at(sb));
         __syncthreads();
         pre_lds = s_fill;
-        pre_off = s1_fill_c_at(t, 0, 0);
+        pre_off = s1_fill_c_bytes(t, 0, 0);
         // (lane 255 has no block: never live, it searches the frame's last block with slot 50's C input, and of the five words of the minimum it
         // reads, 256..259 are never written -- uninitialised on purpose, its result is never used)
         min_lds = &s_min[0][s1_fill_min_at(t)];
@@ -517,7 +558,7 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
         s1_make_pre(a.cur, tbx * 8, tby * 8, sb, slot < M::BLOCKS_PER_WAVE, &s_pre[0][0] + s1_pre_slot_at(wave, slot) + s1_pre_sub_at(sb));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         pre_lds = &s_pre[0][0];
-        pre_off = s1_pre_c_at(wave, lane, 0, 0);     // this lane's block slot; the sub-block (s1_pre_sub_at) and the quad (load_pre16) are added per read
+        pre_off = s1_pre_c_bytes(wave, lane, 0, 0);  // this lane's block slot, in bytes; the sub-block (s1_pre_sub_bytes) is stepped by the loop, the quad (load_pre16) sits in the read
     }
     const int nr = REF_LOOP ? a.nrefs : 1;
 #pragma unroll 1

@@ -28,12 +28,15 @@
 // eight blocks and reference; with the reference loop 475 per reference + 53 per group = 493 at three references
 // (tests/test_search2_instruction_budget.py); with the row butterfly of rows 0 and 2 of the metric folded into its MFMA 443 per reference + 70 per
 // group = 466 (tests/test_metric_instruction_budget.py); with the filter bytes packed without permutes (round_pack4) and the result written by the
-// winning lane 411 per reference (392 issued: the rest is a branch waves skip) + 69 per group = 434 (tests/test_search2_pack_tail_budget.py).
+// winning lane 411 per reference (392 issued: the rest is a branch waves skip) + 69 per group = 434 (tests/test_search2_pack_tail_budget.py); with
+// the lane addresses of a reference's head read from a table (s2_lane_layout.h) and its global loads addressed by a uniform base and a 32-bit lane
+// offset 371 per reference + 75 per group = 396 (tests/test_search_lane_budget.py).
 #include <stdlib.h>
 #include <string.h>
 
 #include "vp8hip_dev.h"
 #include "kernels_rc_dev.h"
+#include "s2_lane_layout.h"
 
 namespace vp8 {
 
@@ -78,16 +81,12 @@ constexpr OperandTable make_av() {   // A of the vertical pass: lane l -> row m 
 static __device__ __constant__ const OperandTable K_BH = make_bh();
 static __device__ __constant__ const OperandTable K_AV = make_av();
 
-constexpr int HT_XC = 36;            // dwords per x case in the transposed H array: 8 columns x 16 B + 16 B bank skew
-// The V array (vertical pass results = the predictions of the 25 candidates, + the zero-vector block as candidate 25) is ordered
-// [4x4 block][candidate][column]: a (candidate, 4x4 block) task of the cost phase is 16 contiguous bytes, one ds_read_b128, and the
-// 16 lanes such a read serves at a time take 16 consecutive candidates = 256 consecutive bytes = every bank once, with no skew.
-constexpr int V_CAND = 4;              // dwords per task: the four columns of a 4x4 block, four rows each
-constexpr int V_ROW = 26 * V_CAND;     // dwords per 4x4 block: 25 candidates (y case * 5 + x case) + the zero-vector block
-constexpr int V_SLOT = 4 * V_ROW;      // dwords per 8x8 block: 4x4 block b = 2 * (row half) + (column half)
-constexpr int V_ZERO = 25;
-constexpr int PRE_SLOT = 96;           // ints per 8x8 block in the pre table: 4x4 blocks 0, 1, 2, 3, 3, 3 x 16 (see search2_body)
-constexpr int WIN_ROW = 8;             // dwords per row of the staged window: 20 bytes loaded, 32 so that a row half is one aligned ds_read_b128
+// The layout constants of the three LDS arrays (HT_XC, V_CAND, V_ROW, V_SLOT, V_ZERO, PRE_SLOT, WIN_ROW) and every lane's place in them: s2_lane_layout.h.
+// What of it a wave would compute again for every reference, it reads from this table instead: lane t's row, the fields 16 bits each.
+static __device__ __constant__ const S2LaneTable K_S2_LANE = make_s2_lane();
+typedef int v2i __attribute__((ext_vector_type(2)));
+template <class T>
+__device__ __forceinline__ T *lds_at(uint32_t *array, uint32_t bytes) { return reinterpret_cast<T *>(reinterpret_cast<char *>(array) + bytes); }
 // Every LDS array of the kernel is indexed by the block's slot g, and the two blocks of a wave sit in ITS lanes: the stages
 // hand data over inside a wave, so a wave-level "my LDS writes have landed" is all the synchronisation there is
 __device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -149,9 +148,10 @@ __device__ __forceinline__ uint32_t round_pack4(const v16i &acc, int q) {
 }
 // The rounding 64 of a pass rides in the product: k = 31 of the tap operand is 64 (make_bh, make_av; no tap reaches that far) and k = 31 of
 // the data operand is made 1 here -- byte 15 of the lanes of the upper k half, which otherwise meets a zero tap.  (As the C input the
-// constant cost sixteen registers: hipcc does not fold a splat into the instruction's inline-constant field.)  `upper`: 0 or -1.
-__device__ __forceinline__ v4i one_at_k31(v4i d, int upper) {
-    d.w = (int)(((uint32_t)d.w & (0xffffffffu >> (8 & upper))) | (0x01000000u & (uint32_t)upper));
+// constant cost sixteen registers: hipcc does not fold a splat into the instruction's inline-constant field.)  `keep`: s2_k31_keep of the lane,
+// all ones or all but the last byte; the one goes where nothing is kept (s2_k31_one).
+__device__ __forceinline__ v4i one_at_k31(v4i d, uint32_t keep) {
+    d.w = (int)(((uint32_t)d.w & keep) | (~keep & 0x01000000u));
     return d;
 }
 __device__ __forceinline__ v16i mfma_round(v4i a, v4i b) {
@@ -168,47 +168,64 @@ __device__ __forceinline__ v16i mfma_round(v4i a, v4i b) {
 // y = 1); what does not depend on the reference is made once, ahead of the loop: the blocks' coordinates, the current block's load, its byte
 // scatter and its share of the metric (the pre table, which therefore has an array of its own: the H array's bytes are the next reference's).
 // Otherwise one reference, ref_idx (the one-video form: one reference per blockIdx.y).
-// tn: the thread's number again, for what a workgroup that takes several groups (search2_groups) should NOT keep across its loops: every
-// register of lane arithmetic kept is one a wave of the SIMD cannot have, and the cheap ones (two or three instructions to make) are made again
-template <bool SPREAD, bool ALLREFS>
+// Lane arithmetic: every LDS address and every small integer of a global address is a function of the thread's number alone, stated once in
+// s2_lane_layout.h.  A register of it kept across the loops is one a wave of the SIMD cannot have, so only what the later stages use is kept (the H
+// store, the vertical pass and the cost phase: made from threadIdx.x, the compiler holds them); what the head of a reference uses -- the window,
+// the zero-vector block, the operands' rows and the whole-pel column -- used to be computed again per reference (37 vector instructions) and is
+// now READ: the lane's row of K_S2_LANE -- its first two dwords, which the window's load and store hang on, once per group and kept where the
+// registers allow (KEEP), the rest per reference in one load beside the net vector's -- a field taken out where it is used.
+// tn: the thread's number again, as a value the compiler cannot follow (search2_groups), for the once-per-group part, which is made again per group.
+// READ false: the fields are computed from tn by the functions the table was made from, not read -- the one-group, one-reference form, whose
+// workgroup comes here once: nothing is made twice there, and the row's registers would only add to its count.
+// KEEP: the first two dwords of the lane's row are read once per group and kept across the reference loop; otherwise per reference with the rest
+// (the one-group batched forms, which have no register to spare: kept there, the two dwords cost 8 bytes of scratch).
+template <bool SPREAD, bool ALLREFS, bool READ = true, bool KEEP = false>
 __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_idx, int tn) {
     if (ALLREFS ? a.nrefs == 0 : ref_idx >= a.nrefs) return;
     __shared__ __attribute__((aligned(16))) uint32_t s_HT[8][5 * HT_XC];
     __shared__ __attribute__((aligned(16))) uint32_t s_V[8][V_SLOT];   // vertical pass results and the zero-MV block: [4x4 block][candidate][column], biased bytes
-    uint32_t(*s_win)[V_SLOT] = s_V;   // the staged window (16 rows x 32 B) is dead once the horizontal pass has read it: same bytes
+    // (the staged window, 16 rows x 32 B, is the first 512 bytes of the block's V slot: dead once the horizontal pass has read it)
     // the current block's share of the metric, [4x4 block][the 16 quantities of weight_mfma], made once per group of blocks; 4x4 block 3 three times over
     // (ints 48.., 64.., 80..), so that an idle lane of the cost phase, which stays on block 3, steps through the table as the others do.
     // (LDS per workgroup decides how many workgroups a CU holds: 21.6 KB = seven.)
-    __shared__ __attribute__((aligned(16))) int s_pre[8][PRE_SLOT];
-    // [candidate]: the cost of its fourth 4x4 block, made by another lane: in the H array's bytes, dead once the vertical pass has read them
-    int(*s_q3)[5 * HT_XC] = reinterpret_cast<int(*)[5 * HT_XC]>(s_HT);
-    const int g = threadIdx.x >> 5, lane = threadIdx.x & 31;
-    const int wl = threadIdx.x & 63, kh = wl >> 5, gp = g & ~1;   // lane of the wave, its k half in an MFMA operand, the wave's first slot
+    __shared__ __attribute__((aligned(16))) uint32_t s_pre[8][PRE_SLOT];
+    // (q3, [candidate]: the cost of its fourth 4x4 block, made by another lane, lives in the H array's bytes, dead once the vertical pass has read them)
+    static_assert(S2_EXT == EXT, "s2_lane_layout.h restates the planes' edge width");
+    static_assert(sizeof(s_HT) == S2_HT_BYTES && sizeof(s_V) == S2_V_BYTES && sizeof(s_pre) == S2_PRE_BYTES, "s2_lane_layout.h states these arrays");
+    uint32_t *const HT = &s_HT[0][0], *const V = &s_V[0][0], *const PRE = &s_pre[0][0];
+    const int t = (int)threadIdx.x, g = s2_slot(t), lane = s2_lane(t);
     const int b = imin(wg_x * 8 + g, a.nblk - 1);
     const bool live = wg_x * 8 + g < a.nblk;
     const int by = a.bw == 1 ? b : (int)__umulhi((uint32_t)b, a.bw_inv), bx = b - by * a.bw;   // b / bw: bw_inv = ceil(2^32 / bw), exact for b * bw < 2^32
     const int cx = bx * 8, cy = by * 8;
+    // the block's cell in the nets and in the cost array as a byte offset: read and written through it.  (Through an empty asm per reference, in
+    // place: seen as a loop invariant it is widened to a 64-bit pair once and every access pays a 64-bit add.)
+    uint32_t boff = (uint32_t)b * 4u;
+    // the lane's row of K_S2_LANE as a byte offset, a new value per reference as far as the compiler can tell (in place, too: no copy) -- its loads
+    // would otherwise leave the loop and their eight registers stay
+    uint32_t trow = (uint32_t)tn * (uint32_t)(S2_LANE_DWORDS * 4);
+    // the first two dwords of that row, what the head of a reference needs first: read here, once per group, and kept across the reference loop
+    v2i lk = {0, 0};
+    if (READ && KEEP) lk = *reinterpret_cast<const v2i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow);
     {   // current block: lanes 0-15 one dword each, scattered as column bytes [row half][column] (16 dwords, in the table's last 64 bytes): the four
         // columns of 4x4 block (m*2 + n) -- the order the cost loop below walks them: row half m, column half n -- are four consecutive dwords.  Then
-        // its share of the metric (vp8hip_dev.h, weight_pre_half), half a 4x4 block per lane: lane = (copy t, half): the 4x4 blocks 0, 1, 2, 3 and the two
-        // further copies of block 3 (t = 3, 4, 5), the quantities of row 0 + X or those of row 2 + Y.  No lane is masked: the lanes past the twelfth
+        // its share of the metric (vp8hip_dev.h, weight_pre_half), half a 4x4 block per lane: lane = (copy, half): the 4x4 blocks 0, 1, 2, 3 and the two
+        // further copies of block 3 (copies 3, 4, 5), the quantities of row 0 + X or those of row 2 + Y.  No lane is masked: the lanes past the twelfth
         // make and store the last copy's halves again.
-        const int g_n = tn >> 5, lane_n = tn & 31;
-        uint32_t *tmp = reinterpret_cast<uint32_t *>(&s_pre[g_n][80]);
-        if (lane_n < 16) {
-            const int row = lane_n >> 1, half = lane_n & 1;
-            const uint32_t v = *reinterpret_cast<const uint32_t *>(a.cur.p + (ptrdiff_t)(cy + row) * a.cur.stride + cx + 4 * half) ^ 0x80808080u;
-            uint8_t *cz = reinterpret_cast<uint8_t *>(tmp) + (row >> 2) * 32 + half * 16 + (row & 3);
+        if (s2_lane(tn) < 16) {
+            const uint32_t coff = __umul24((uint32_t)(cy + s2_cur_row(tn)), (uint32_t)a.cur.stride) + (uint32_t)(cx + s2_cur_half_bytes(tn));
+            const uint32_t v = *reinterpret_cast<const uint32_t *>(a.cur.p + coff) ^ 0x80808080u;
+            uint8_t *cz = lds_at<uint8_t>(PRE, s2_cur_scatter(tn));
 #pragma unroll
             for (int j = 0; j < 4; ++j) cz[j * 4] = (uint8_t)(v >> (8 * j));
         }
         lds_fence();
-        const int hf = lane_n & 1, t = imin(lane_n >> 1, 5), qb = imin(t, 3);
-        const v4i cv = *reinterpret_cast<const v4i *>(tmp + 4 * qb);   // (every lane of the wave reads before any of them writes: LDS takes a wave's operations in order)
+        const int hf = s2_pre_half(tn);
+        const v4i cv = *lds_at<const v4i>(PRE, s2_pre_cols(tn));   // (every lane of the wave reads before any of them writes: LDS takes a wave's operations in order)
         const uint32_t cc[4] = {(uint32_t)cv.x, (uint32_t)cv.y, (uint32_t)cv.z, (uint32_t)cv.w};
         int smcd[4], xy[4];
         weight_pre_half(cc, hf ? K_W_R2 : K_W_R0, hf ? K_W_Y : K_W_X, smcd, xy);
-        int *dst = &s_pre[g_n][16 * t + 4 * hf];
+        int *dst = lds_at<int>(PRE, s2_pre_store(tn));
         *reinterpret_cast<v4i *>(dst) = v4i{smcd[0], smcd[1], smcd[2], smcd[3]};
         *reinterpret_cast<v4i *>(dst + METRIC_X) = v4i{xy[0], xy[1], xy[2], xy[3]};
     }
@@ -220,23 +237,35 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
     // (with the candidate's vector-cost penalty, :1176-1178, above it: cost and number go into the key with one shift-and-add)
     const uint32_t kcode = k < 25 ? (uint32_t)((iabs(dx) + iabs(dy)) * 32 * 256 + (dy + 2) * 8 + dx + 2) : 40u;
     const us2 dxy = {(unsigned short)dx, (unsigned short)dy};     // its offsets as a 16-bit pair
-    const v4i wa = metric_a(wl);        // the metric's column pass on the matrix cores (weight_mfma, vp8hip_dev.h): every lane of the wave is here
+    const v4i wa = metric_a(s2_wave_lane(t));        // the metric's column pass on the matrix cores (weight_mfma, vp8hip_dev.h): every lane of the wave is here
 
     // ---- everything below is per reference ------------------------------------------------------------------------------
-    // From the part above it uses: b, live, cx, cy (the block), k, dxy, kcode, wa (the lane's candidate) and the pre table.
+    // From the part above it uses: live, cx, cy, boff (the block), k, dxy, kcode, wa (the lane's candidate) and the pre table.
     // Its LDS reuse rests on one rule -- LDS executes a wave's operations in program order, and every array slot is written only by the
-    // wave whose lanes own it (the one wave of the fourth-block round only reads other slots, between the two barriers):
+    // wave whose lanes own it (the one wave of the fourth-block round only reads other slots, between the two barriers; s2_lane_layout_check.cpp
+    // walks every address of s2_lane_layout.h for it):
     //   * the window lives in the first 512 bytes of the block's V slot; candidate 25 of 4x4 block 0 (bytes 400..415) lies inside them, so
     //     the zero-MV scatter comes after the last read of the window and before the vertical pass's stores;
     //   * q3 (the fourth-block costs) lives in words 64..95 of the block's H slot, written after the vertical pass has read the H array and
     //     read back before the next reference's horizontal pass writes it; words 29..31 of q3 take the stores nobody reads;
     //   * the pre table is only read here.
     auto one_reference = [&](int ri) {
-        int tr = tn;
-        if (ALLREFS) asm volatile("" : "+v"(tr));     // (the same number, as far as the compiler can tell a new one per reference)
-        const int g_n = tr >> 5, lane_n = tr & 31, wl_n = tr & 63, kh_n = wl_n >> 5, gp_n = g_n & ~1;
+        asm volatile("" : "+v"(trow), "+v"(boff));
         const int r = a.refmap[ri];
-        const uint32_t nv = reinterpret_cast<const uint32_t *>(a.net_in[r])[b];
+        // The rest of the lane's row, at the top with the net vector's load; its first two dwords were read once per group (lk, above) and are
+        // kept: nothing the window's load and store hang on is waited for, and the zero-vector block's load comes behind the window's.
+        v4i lb = {0, 0, 0, 0};
+        if (READ && !KEEP) lk = *reinterpret_cast<const v2i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow);
+        if (READ) lb = *reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow + 4 * S2_LANE_KEPT_DWORDS);
+        auto fld = [&](int f) -> uint32_t {      // (f is a constant wherever this is called: a register and one v_and_b32 or v_lshrrev_b32)
+            if (!READ) return s2_field(tn, f);
+            const uint32_t w = (uint32_t)(f < 2 * S2_LANE_KEPT_DWORDS ? lk[(f >> 1) & 1] : lb[((f >> 1) - S2_LANE_KEPT_DWORDS) & 3]);
+            return (f & 1) ? w >> 16 : w & 0xffffu;
+        };
+        // The three global loads of a reference -- the net vector, the window, the zero-vector block -- go by a uniform base and the lane's unsigned
+        // 32-bit byte offset, as the result write does: one load each, no 64-bit address per lane.  The products are v_mad_u32_u24: a row and a stride
+        // are below 2^24 (a plane is a few thousand pixels each way), and an offset below 2^32.
+        const uint32_t nv = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(a.net_in[r]) + boff);
         const us2 v0 = __builtin_bit_cast(us2, nv) * (unsigned short)4;      // the whole-pel vector in quarter pels, (int16)(n * 4) per half
         // (the vector the window is placed by is the one the candidates are placed by, (int16)(4 n) / 4: n itself for every vector a search hands
         // down, and for a written net whose 4 n passes int16 the place the reference's wrap lands on)
@@ -249,43 +278,46 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         // The window from its own first byte (Lx - 3: any alignment; the part's global loads need none): lane = (row, half) takes 16
         // bytes, 16 rows of 32 bytes -- the six-tap passes need 14 x 19, the rest stays inside the planes' allocated margin (PAD) and
         // meets zero taps.  One load and one ds_write_b128 per lane, no loop.
+        // The window starts up to EXT - 3 rows and columns outside the frame (Lx - 3, Ly - 3 >= -EXT): the scalar base moves back by EXT rows and
+        // EXT columns, once per reference, and the lane's row and column move forward by as much (in the table's fields: s2_win_row_biased,
+        // s2_win_half_biased), so that its offset is never negative.
         {
-            const int row = lane_n >> 1, half = lane_n & 1;
+            const uint8_t *const wbase = rf.p - (ptrdiff_t)EXT * rf.stride - EXT;
+            const uint32_t woff = __umul24((uint32_t)Ly + fld(S2F_WIN_ROW), (uint32_t)rf.stride) + ((uint32_t)Lx + fld(S2F_WIN_HALF));
             v4i v;
-            __builtin_memcpy(&v, rf.p + (ptrdiff_t)(Ly - 3 + row) * rf.stride + (Lx - 3) + 16 * half, 16);
-            *reinterpret_cast<v4i *>(&s_win[g_n][row * WIN_ROW + 4 * half]) = v ^ (int)0x80808080u;
+            __builtin_memcpy(&v, wbase + woff, 16);
+            *lds_at<v4i>(V, fld(S2F_WIN_STORE)) = v ^ (int)0x80808080u;
         }
         // zero-MV block: one dword per lane (both halves of the block's lanes load the same eight rows: no branch), scattered below, once the
         // window -- whose bytes its place in the V array shares -- has been read
-        const uint32_t zv = *reinterpret_cast<const uint32_t *>(rf.p + (ptrdiff_t)(cy + ((lane_n >> 1) & 7)) * rf.stride + cx + 4 * (lane_n & 1)) ^ 0x80808080u;
+        const uint32_t zoff = __umul24((uint32_t)cy + fld(S2F_ZERO_ROW), (uint32_t)rf.stride) + ((uint32_t)cx + fld(S2F_ZERO_HALF));
+        const uint32_t zv = *reinterpret_cast<const uint32_t *>(rf.p + zoff) ^ 0x80808080u;
         lds_fence();
+        const uint32_t k_row = !READ ? (uint32_t)s2_k_row(tn) : (uint32_t)lb[(S2F_K_ROW >> 1) - S2_LANE_KEPT_DWORDS];                     // the lane's row of K_BH and of K_AV: S2F_K_ROW, alone in its dword
+        const uint32_t k31_keep = !READ ? s2_k31_keep(tn) : (uint32_t)lk[S2F_K31_KEEP_HI >> 1] | 0xffffu;        // one_at_k31's mask, all of the operand's last dword or all but its last byte: S2F_K31_KEEP_HI above 0xffff
 
         // ---- horizontal pass: ONE MFMA for the wave's two blocks ------------------------------------------------------------
         // A = the windows (row m = 16 * block + window row; rows 14, 15 and bytes 20..31 of a row hold whatever the LDS held: they
         // meet zero taps or land in bytes nobody reads), B = the taps of the four fractional x cases (K_BH).  A lane comes out with
         // column n = (x case, c) and four groups of four consecutive rows: each group one dword of the TRANSPOSED H array.
         {
-            const int m = wl & 31, m_n = wl_n & 31;
-            const v4i aw = *reinterpret_cast<const v4i *>(&s_win[gp_n + (m_n >> 4)][(m_n & 15) * WIN_ROW + 4 * kh_n]);
-            const v4i bh = *reinterpret_cast<const v4i *>(K_BH.w[wl_n]);
-            const v16i acc = mfma_round(one_at_k31(aw, -kh_n), bh);
-            const int xi = m >> 3, c = m & 7, xc = xi + (xi >> 1);
-            uint32_t *ht = &s_HT[gp][xc * HT_XC + c * 4 + kh];   // rows 4 * kh .. of column c; + 2: rows 8 + 4 * kh ..; next slot: the other block
+            const v4i aw = *lds_at<const v4i>(V, fld(S2F_AW_READ));
+            const v4i bh = *reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(K_BH.w) + k_row);
+            const v16i acc = mfma_round(one_at_k31(aw, k31_keep), bh);
+            const int ht = s2_ht_store(t);   // rows 4 * kh .. of column c; + 8 bytes: rows 8 + 4 * kh ..; next slot: the other block
 #pragma unroll
-            for (int q = 0; q < 4; ++q) ht[(q >> 1) * (5 * HT_XC) + 2 * (q & 1)] = round_pack4(acc, q);
+            for (int q = 0; q < 4; ++q) *lds_at<uint32_t>(HT, ht + s2_ht_store_step(q)) = round_pack4(acc, q);
         }
         {   // whole-pel x case: column c of the window, rows 4*rg..4*rg+3 (rows 14, 15 -- staged like the others -- only ever meet zero taps)
-            const int c = lane_n & 7, rg = lane_n >> 3;
-            const uint8_t *wb = reinterpret_cast<const uint8_t *>(s_win[g_n]) + 3 + c + rg * (16 * WIN_ROW);
+            const uint8_t *wb = lds_at<const uint8_t>(V, fld(S2F_WP_READ));
             uint32_t v = 0;
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) v |= (uint32_t)wb[rr * (4 * WIN_ROW)] << (8 * rr);
-            s_HT[g_n][2 * HT_XC + c * 4 + rg] = v;
+            *lds_at<uint32_t>(HT, fld(S2F_WP_STORE)) = v;
         }
         {   // the zero-MV block as candidate 25 of the V array: the lane's dword = row `row`, columns 4 * half .. + 3 -> byte row & 3 of the four
             // column dwords of 4x4 block (row >> 2, half).  (Behind the window's reads: LDS takes a wave's operations in order.)
-            const int row = (lane_n >> 1) & 7, half = lane_n & 1;
-            uint8_t *z = reinterpret_cast<uint8_t *>(&s_V[g_n][((row >> 2) * 2 + half) * V_ROW + V_ZERO * V_CAND]) + (row & 3);
+            uint8_t *z = lds_at<uint8_t>(V, fld(S2F_ZERO_SCATTER));
 #pragma unroll
             for (int j = 0; j < 4; ++j) z[j * 4] = (uint8_t)(zv >> (8 * j));
         }
@@ -296,21 +328,19 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         // each (the lanes of the upper k half read the same column: their A entries are zero).  A lane comes out with its column and, per
         // y case, the four rows 4 * kh .. 4 * kh + 3: one dword of the prediction, column c & 3 of 4x4 block (kh, c >> 2).  The whole-pel y case is a copy.
         {
-            const v4i av = *reinterpret_cast<const v4i *>(K_AV.w[wl_n]);
+            const v4i av = *reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(K_AV.w) + k_row);
+            const int kh = s2_k_half(t);
 #pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                const int ng = 32 * t + (wl & 31);
-                const bool on = t < 2 || (wl & 31) < 16;
-                const int blk = ng >= 40 ? 1 : 0, rem = on ? ng - 40 * blk : 0, xc = rem >> 3, c = rem & 7;
-                const v4i hv = *reinterpret_cast<const v4i *>(&s_HT[gp + blk][xc * HT_XC + c * 4]);
-                const v16i acc = mfma_round(av, one_at_k31(hv, -kh_n));
-                if (on) {
-                    uint32_t *sv = &s_V[gp + blk][(kh * 2 + (c >> 2)) * V_ROW + xc * V_CAND + (c & 3)];
+            for (int i = 0; i < 3; ++i) {
+                const v4i hv = *lds_at<const v4i>(HT, s2_hv_read(t, i));
+                const v16i acc = mfma_round(av, one_at_k31(hv, k31_keep));
+                if (s2_v_on(t, i)) {
+                    const int sv = s2_sv_store(t, i);
 #pragma unroll
-                    for (int f = 0; f < 4; ++f) sv[(f + (f >> 1)) * 5 * V_CAND] = round_pack4(acc, f);
+                    for (int f = 0; f < 4; ++f) *lds_at<uint32_t>(V, sv + s2_sv_store_step(f + (f >> 1))) = round_pack4(acc, f);
                     // whole-pel dy: rows 3..10 of the column, the lower lane half rows 3..6, the upper 7..10
-                    sv[2 * 5 * V_CAND] = kh ? __builtin_amdgcn_alignbyte((uint32_t)hv[2], (uint32_t)hv[1], 3)
-                                            : __builtin_amdgcn_alignbyte((uint32_t)hv[1], (uint32_t)hv[0], 3);
+                    *lds_at<uint32_t>(V, sv + s2_sv_store_step(2)) = kh ? __builtin_amdgcn_alignbyte((uint32_t)hv[2], (uint32_t)hv[1], 3)
+                                                                        : __builtin_amdgcn_alignbyte((uint32_t)hv[1], (uint32_t)hv[0], 3);
                 }
             }
         }
@@ -325,48 +355,42 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         const bool valid = live && k < 26 && qx >= 0 && qx <= a.w * 4 - 32 && qy >= 0 && qy <= a.h * 4 - 32;
         int diff = 0;
         // a task = 16 bytes of the V array (the B operand: one ds_read_b128) and 16 ints of the pre table (the C input)
-        auto metric = [&](const uint32_t *src, const int *pre16) { return weight_mfma(wa, load_pre16(pre16), *reinterpret_cast<const v4i *>(src)); };
+        auto metric = [&](int src, int pre16) { return weight_mfma(wa, load_pre16(lds_at<const int>(PRE, pre16)), *lds_at<const v4i>(V, src)); };
         if (SPREAD) {
-            int *q3 = &s_q3[g][64];
-            const bool helper = lane >= 26;
             // (branch-free: a lane's own candidate, 4x4 block j in round j, or, for the idle lanes, 4x4 block 3 of candidate 3 (lane - 26) + j: one
             // base address and one stride per lane, the table's copies of block 3 one block apart like the others; the idle lanes' costs go to q3,
             // everybody else's to the table's unused words 29..31, and an idle lane's own sum is never looked at: `valid` is false there)
-            const uint32_t *src = helper ? &s_V[g][3 * V_ROW + (lane - 26) * 3 * V_CAND] : &s_V[g][k * V_CAND];
-            const int step = helper ? V_CAND : V_ROW;
-            const int *pre = &s_pre[g][helper ? 48 : 0];
-            int *dst = &q3[helper ? (lane - 26) * 3 : 29];
+            const int src = s2_cost_src(t), step = s2_cost_step(t), pre = s2_cost_pre(t);
+            int *dst = lds_at<int>(HT, s2_cost_dst(t));
 #pragma unroll
             for (int j = 0; j < 3; ++j) {       // rounds 0..2: a candidate's own lane its 4x4 blocks 0..2, the idle lanes block 3 of candidates 0..17
-                const int c = metric(src + j * step, pre + 16 * j);
+                const int c = metric(src + j * step, pre + 64 * j);
                 dst[j] = c;
                 diff += c;
             }
             __syncthreads();                    // every wave's V and pre arrays (and the idle lanes' costs) are in LDS
-            if ((int)(threadIdx.x >> 6) == (wg_x & 3)) {      // ONE wave (taking turns from workgroup to workgroup: the waves of a workgroup sit on different SIMDs): block 3 of candidates 18..25 of all eight block slots
-                const int slot = wl >> 3, cand = 18 + (wl & 7);
-                s_q3[slot][64 + cand] = metric(&s_V[slot][3 * V_ROW + cand * V_CAND], &s_pre[slot][48]);
+            if (s2_wave(t) == (wg_x & 3)) {      // ONE wave (taking turns from workgroup to workgroup: the waves of a workgroup sit on different SIMDs): block 3 of candidates 18..25 of all eight block slots
+                *lds_at<int>(HT, s2_extra_dst(t)) = metric(s2_extra_src(t), s2_extra_pre(t));
             }
             __syncthreads();
-            diff += q3[k < 26 ? k : 31];
+            diff += *lds_at<const int>(HT, s2_cost_q3_read(t));
         } else {
             // lane 25: the zero-MV block (whole-pel: both passes are the identity); the idle lanes read it too
-            const uint32_t *src = &s_V[g][imin(k, V_ZERO) * V_CAND];
+            const int src = s2_cost_src_plain(t), pre = s2_cost_pre_plain(t);
 #pragma unroll
-            for (int bb = 0; bb < 4; ++bb) diff += metric(src + bb * V_ROW, &s_pre[g][bb * 16]);
+            for (int bb = 0; bb < 4; ++bb) diff += metric(src + bb * V_ROW * 4, pre + bb * 64);
         }
         uint32_t key = ((uint32_t)diff << 8) + kcode;     // (diff + penalty) << 8 | number
         const bool ok = valid && key < (0x7fffu << 8);
         key = ok ? key : 0xffffffffu;
         const uint32_t kmin = block_min(key);
-        // (results by base + 32-bit byte offset, made where it is used: a uniform base and a lane's unsigned offset are one store each, no 64-bit
-        // address per lane -- and none kept across the loop)
+        // (results by base + 32-bit byte offset: a uniform base and a lane's unsigned offset are one store each, no 64-bit address per lane.  The
+        // offset is the one the net vector was read by: one register across the loop, where the block's number as a 64-bit index took two.  Through
+        // the empty asm again, in place: the stores sit in a block of their own, where the compiler otherwise meets the offset already widened)
         auto result_write = [&](uint32_t v, int md) {
-            uint32_t bo = (uint32_t)b;
-            asm("" : "+v"(bo));
-            const uint32_t off = bo * 4u;
-            *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(a.net_out[r]) + off) = v;
-            *reinterpret_cast<int *>(reinterpret_cast<char *>(a.bdiff[r]) + off) = md;
+            asm volatile("" : "+v"(boff));
+            *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(a.net_out[r]) + boff) = v;
+            *reinterpret_cast<int *>(reinterpret_cast<char *>(a.bdiff[r]) + boff) = md;
         };
         // The winning lane writes: keys are unique in a block (the candidate's number is the low byte), so exactly one lane holds the minimum, and
         // it holds all the result is made of.  A candidate in the frame has not wrapped: its vector is (v0x + dx, v0y + dy) as 16-bit sums -- one
@@ -397,15 +421,18 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
 
 // ITER: a workgroup takes ITER consecutive groups of eight blocks, one after the other.  A third of what a wave issues for a group does not
 // depend on the group -- the lane's place in the operand tables of the two passes and the tables themselves, its LDS addresses in every stage, its
-// candidate's offset and penalty -- and the compiler keeps all of it in registers across the loop (the price: registers, i.e. waves per SIMD).
+// candidate's offset and penalty -- and the compiler keeps in registers across the loop what search2_body makes from threadIdx.x (the price:
+// registers, i.e. waves per SIMD).  What it makes from tn -- the once-per-group part's addresses, and the byte offset of the lane's row of
+// K_S2_LANE -- starts anew with every group: the empty asm below is the one place the thread's number is hidden at; per reference the body hides
+// the row's offset again, in place.  (The form that comes here once, ITER = 1 with one reference per workgroup, computes the fields: READ = false.)
 template <bool SPREAD, int ITER, bool ALLREFS>
 __device__ __forceinline__ void search2_groups(const S2Args &a, int grp, int ref_idx) {
-    if (ITER == 1 && !ALLREFS) { search2_body<SPREAD, ALLREFS>(a, grp, ref_idx, (int)threadIdx.x); return; }
+    if (ITER == 1 && !ALLREFS) { search2_body<SPREAD, ALLREFS, false>(a, grp, ref_idx, (int)threadIdx.x); return; }
 #pragma unroll 1
     for (int it = 0; it < ITER; ++it) {
         int tn = (int)threadIdx.x;
         asm volatile("" : "+v"(tn));     // (the same number, as far as the compiler can tell a new one per group)
-        search2_body<SPREAD, ALLREFS>(a, grp * ITER + it, ref_idx, tn);
+        search2_body<SPREAD, ALLREFS, true, (ITER > 1 && ALLREFS)>(a, grp * ITER + it, ref_idx, tn);
     }
 }
 // (waves_per_eu, here as on the batched forms: left to __launch_bounds__(256, 4) the register allocator takes 74 registers for the two-group
@@ -457,6 +484,8 @@ __global__ __launch_bounds__(256, 4) void k_search2_p(BatchOf<S2Args> b, int nbx
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
         const int item = w / (nbx * maxrefs), rem = w - item * (nbx * maxrefs);
         const int ref_idx = rem / nbx, wg_x = rem - ref_idx * nbx;
+        // (the table form, READ: this loop is the group loop and the reference loop in one, and with the fields read the form takes 66 registers
+        // where computing them across the loop took 79)
         search2_body<false, false>(b.item[item], wg_x, ref_idx, (int)threadIdx.x);
         lds_fence();   // the next round reuses this workgroup's LDS: every read of this round has returned
     }

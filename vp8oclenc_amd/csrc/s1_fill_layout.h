@@ -38,11 +38,15 @@ LDS_MODEL_HD constexpr int s1_fill_task_sub(int t) { return t & 3; }
 LDS_MODEL_HD constexpr int s1_fill_c_at(int t, int sb, int j, int slot_ints = S1_PRE_SLOT) {
     return s1_fill_slot_at(s1_fill_slot_of(t), slot_ints) + s1_pre_sub_at(sb, j);
 }
+// ... and its byte offset, which is what the kernel carries (s1_pre_sub_bytes: s1_pre_layout.h)
+LDS_MODEL_HD constexpr int s1_fill_c_bytes(int t, int sb, int j, int slot_ints = S1_PRE_SLOT) {
+    return 4 * s1_fill_slot_at(s1_fill_slot_of(t), slot_ints) + s1_pre_sub_bytes(sb, j);
+}
 
 // LDS cycles of that read for wave `wave` of the workgroup
 LDS_MODEL_HD constexpr int s1_fill_c_read_cycles(int wave, int sb, int j, int slot_ints = S1_PRE_SLOT, unsigned long long exec = ~0ull) {
     lds_model::WaveAddrs w{};
-    for (int l = 0; l < 64; ++l) w.a[l] = 4u * (unsigned)s1_fill_c_at(64 * wave + l, sb, j, slot_ints);
+    for (int l = 0; l < 64; ++l) w.a[l] = (unsigned)s1_fill_c_bytes(64 * wave + l, sb, j, slot_ints);
     return lds_model::ds_read_b128_cycles(w, exec);
 }
 // the most and the least any C read of the table costs: every wave, sub-block and quad

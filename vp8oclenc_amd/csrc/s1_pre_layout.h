@@ -24,11 +24,17 @@ LDS_MODEL_HD constexpr int s1_pre_sub_at(int sb, int j = 0) { return 16 * sb + 4
 LDS_MODEL_HD constexpr int s1_pre_c_at(int wave, int lane, int sb, int j, int slot_ints = S1_PRE_SLOT) {
     return s1_pre_slot_at(wave, lane / 5, slot_ints) + s1_pre_sub_at(sb, j);
 }
+// The same two as BYTE offsets, the form the kernels carry: a lane's address goes to the ds_read_b128 as it stands, the quad in the instruction's
+// offset field, with no shift per read
+LDS_MODEL_HD constexpr int s1_pre_sub_bytes(int sb, int j = 0) { return 4 * s1_pre_sub_at(sb, j); }
+LDS_MODEL_HD constexpr int s1_pre_c_bytes(int wave, int lane, int sb, int j, int slot_ints = S1_PRE_SLOT) {
+    return 4 * s1_pre_slot_at(wave, lane / 5, slot_ints) + s1_pre_sub_bytes(sb, j);
+}
 
 // LDS cycles of that read for the whole wave
 LDS_MODEL_HD constexpr int s1_pre_c_read_cycles(int wave, int sb, int j, int slot_ints = S1_PRE_SLOT, unsigned long long exec = ~0ull) {
     lds_model::WaveAddrs w{};
-    for (int l = 0; l < 64; ++l) w.a[l] = 4u * (unsigned)s1_pre_c_at(wave, l, sb, j, slot_ints);
+    for (int l = 0; l < 64; ++l) w.a[l] = (unsigned)s1_pre_c_bytes(wave, l, sb, j, slot_ints);
     return lds_model::ds_read_b128_cycles(w, exec);
 }
 // the most any C read of the table costs: every wave, sub-block and quad
