@@ -145,6 +145,19 @@ int vp8drv_batch_encode_frame_host(vp8drv_batch *b, const int *members, const vo
 /* the members' NEXT frames started on their way (vp8hip_batch_prefetch_current; y[i] NULL: nothing for member i): hand the same pointers
  * to the next vp8drv_batch_encode_frame_host */
 int vp8drv_batch_prefetch_frame_host(vp8drv_batch *b, const uint8_t *const *y, const uint8_t *const *u, const uint8_t *const *v);
+/* Scene cuts in GOP-parallel coding.  The serial loop's key-frame schedule with scene_detect on is a function of the chroma differences
+ * of consecutive frames as taken in and of the GOP length (vp8host_scene_plan, include/vp8hip_host.h), so a host scans the file first
+ * -- members of a batch each walking a segment of it, the frame before the segment first -- plans, and then codes the chunks between
+ * the planned key frames side by side, each started with force_key.
+ * vp8drv_batch_scan_frame_*: the members' frames are taken in (as vp8drv_batch_encode_frame_* takes them in, prefetch included) and the
+ * differences against each member's previous frame started, ONE launch for all (vp8hip_batch_chroma_change_async).  Nothing is coded;
+ * the GOP state, the scene history and the statistics do not move.  vp8drv_batch_scan_result: udiff[i], vdiff[i] of the members of the
+ * last scan call (zeros for a member's first frame).  A batch that has scanned codes afterwards what a fresh batch codes, byte for byte.
+ * VP8HIP_ERR_STATE, and nothing changed, when a member of the call has the denoiser on, deinterlace mode 2, analysis or quality
+ * statistics: each keeps a history of the frames taken in or numbers them, and frames taken in without being coded would change it. */
+int vp8drv_batch_scan_frame_device(vp8drv_batch *b, const int *members, const void *const *y, const void *const *u, const void *const *v);
+int vp8drv_batch_scan_frame_host(vp8drv_batch *b, const int *members, const void *const *y, const void *const *u, const void *const *v);
+int vp8drv_batch_scan_result(vp8drv_batch *b, const int *members, int32_t *udiff, int32_t *vdiff);
 /* vp8drv_get_frame_begin for the members' frames in one set of launches (src/vp8enc.cpp:48-94 for up to four chunks at
  * once); then vp8drv_get_frame_end on every member */
 int vp8drv_batch_get_frame_begin(vp8drv_batch *b, const int *members);

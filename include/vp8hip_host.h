@@ -359,6 +359,19 @@ void vp8host_gop_inter_flags(const vp8host_gop *g, int32_t *use_golden, int32_t 
 /* ++frames.frame_number at the end of the loop body, vp8enc.cpp:487 */
 void vp8host_gop_frame_done(vp8host_gop *g);
 
+/* The key-frame schedule of a whole file with scene detection on, from the chroma differences of its frames alone: nothing but the
+ * frame loop's own steps (vp8enc.cpp:364-416, 487), for t = 0 .. nframes - 1:
+ *     vp8host_gop_next;
+ *     key = current_is_key; a frame that is NOT a scheduled key frame is shown to vp8host_scene_change(udiff[t], vdiff[t], t), and is
+ *           a key frame when that says so (a scheduled key frame is never shown to it: its differences are not looked at);
+ *     on a key frame: last_key_detect = t, vp8host_gop_key_coded;
+ *     vp8host_gop_frame_done.
+ * udiff[t], vdiff[t]: vp8hip_chroma_change of frame t against frame t - 1 as taken in; entry 0 is unused.  is_key[t] = 1 for a key frame,
+ * by_scene[t] = 1 for one scene_change asked for (by_scene may be NULL).  Returns the number of key frames, or -1: udiff, vdiff or is_key
+ * NULL, nframes < 0 or gop_size < 1.  Plain C++, no allocation.  Frames that check_SSIM sends back as key frames are not the schedule's:
+ * with an SSIM target the serial program may code more key frames than this plan has. */
+int vp8host_scene_plan(const int32_t *udiff, const int32_t *vdiff, int nframes, int gop_size, uint8_t *is_key, uint8_t *by_scene);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,12 @@ int vp8hip_batch_quality(vp8hip_batch *b, const int *active);
 /* vp8hip_check_ssim_async for the active members (one launch; the verdicts ride in the following vp8hip_batch_loop_filter);
  * vp8hip_check_ssim_result per member afterwards */
 int vp8hip_batch_check_ssim_async(vp8hip_batch *b, const int *active, const int32_t (*refqi)[4], int qi_min);
+/* vp8hip_chroma_change_async for the active members in ONE launch (k_chroma_sad_b: the fold rides in it), behind the members' intake on
+ * the batch's stream, and one event for all of them; vp8hip_chroma_change_result per member afterwards, as after the per-context call:
+ * sum |cur - previous| / ((W/2)*(H/2)) for U and V on the two current surfaces as the batched intake left them (padded, scaled and
+ * converted).  A member with fewer than two frames taken in gets zeros and no work of its own is launched.  VP8HIP_ERR_STATE, and
+ * nothing changed, when an active member has no current frame. */
+int vp8hip_batch_chroma_change_async(vp8hip_batch *b, const int *active);
 /* vp8hip_encode_frame_begin for the active members in the same nine launches (params[i] = member i's header parameters;
  * every member is then between _begin and _end: take each frame with vp8hip_encode_frame_end) */
 int vp8hip_batch_encode_frame_begin(vp8hip_batch *b, const int *active, int num_partitions, const vp8hip_header_params *params);

@@ -17,7 +17,11 @@ top-left luma sample is (X, Y) (vp8drv_set_source_window with the surface's tigh
 (vp8drv_set_source_orientation); behind 90 or 270 degrees the picture that is coded is as wide as the frames that come in are high.
 --arf PERIOD[:FRAMES[:STRENGTH]] (FRAMES 1..7, default 7; STRENGTH 0..6, default 3): hidden alternate reference frames (vp8drv_set_arf,
 vp8drv_encode_arf_host), placed as scripts/native/y4m_to_ivf -arf places them (gop_shard.hidden_frame_events): the file is the one that
-tool writes with -no-scene-detect (this script never detects scenes).  One process; 8-bit I420 frames without --denoise, --deinterlace, --analysis or --surface."""
+tool writes with -no-scene-detect (with --arf this script does not detect scenes).  One process; 8-bit I420 frames without --denoise, --deinterlace, --analysis or --surface.
+--scene-detect: the file scripts/native/y4m_to_ivf writes with its default, scene detection on.  A cut is a key frame and restarts the GOP
+counter, so rank 0 first scans the chroma differences of the whole sequence in batches on the device (gop_shard.scan_differences),
+api.scene_plan makes the serial loop's own key-frame schedule of them, gop_shard.chunks_from_keys the chunks, and the ranks shard those as
+they shard the fixed ones.  Not with --denoise, --deinterlace adaptive, --analysis or --arf: their histories follow the frames taken in."""
 import argparse, os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,7 +89,13 @@ def main():
     ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation of the inter frames at strength N: flat macroblocks take the finer segments of the quantiser ladder, busy ones the coarser (vp8drv_set_segment_mode, mode 2)")
     ap.add_argument("--segment-map", default="", metavar="FILE", help="the caller's segment map for every inter frame: one byte 0..3 per macroblock of the coded picture, raster order (vp8drv_set_segment_mode, mode 1)")
     ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames made by temporal filtering on the device (vp8drv_set_arf, vp8drv_encode_arf_host): one in front of every group of PERIOD frames of a GOP, centred on the group's last frame, FRAMES frames wide (default 7) at STRENGTH 0..6 (default 3)")
+    ap.add_argument("--scene-detect", action="store_true", help="key frames where the serial program with scene detection puts them: the sequence is scanned first (gop_shard.scan_differences), api.scene_plan gives the chunks")
+    ap.add_argument("--scan-batch", type=int, default=8, metavar="N", help="... members of the scanning batch (1..8)")
     a = ap.parse_args()
+    if a.scene_detect and (a.denoise or a.deinterlace == "adaptive" or a.analysis or a.arf):
+        sys.exit("--scene-detect does not go with --denoise, --deinterlace adaptive, --analysis or --arf: their histories follow the frames taken in, the scan would disturb them")
+    if not 1 <= a.scan_batch <= 8:
+        sys.exit("--scan-batch: 1..8")
     arf = None
     if a.arf:
         try:
@@ -145,10 +155,10 @@ def main():
         if seg_map.size != (Wc // 16) * (Hc // 16) or (seg_map.size and seg_map.max() > 3):
             sys.exit(f"--segment-map {a.segment_map}: {(Wc // 16) * (Hc // 16)} bytes of 0..3 are one map of {Wc}x{Hc}")
     t0 = time.perf_counter()
-    def make_encoder():
+    def make_encoder(scan=False):
         enc = gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
                                       ssim_target=a.ssim_target, check_ssim=1, conformant_stream=int(a.conformant),
-                                      loop_filter_type=int(a.simple_filter), **(dict(overlap_filter=0) if arf else {}))
+                                      loop_filter_type=int(a.simple_filter), **(dict(overlap_filter=0) if arf or scan else {}))      # (nor are members of a batch)
         if arf:      # (the driver refuses the filter's own stream beside hidden frames)
             enc.drv.set_arf(arf[2] + 1)
         if a.denoise:
@@ -199,7 +209,24 @@ def main():
         el = time.perf_counter() - t0
         print(f"{a.out}: {frames} shown + {hidden} hidden frames {Win}x{Hin}{f' scaled to {Wd}x{Hd}' if a.resize else ''}, {n} bytes, {frames / el:.1f} frames/s including the host-side frame source")
         return
-    mine = gop_shard.encode_chunks_frames(make_encoder, seq, gop_shard.chunks_of_rank(frames, a.gop, rank, world))
+    chunks, plan = gop_shard.chunks_of_rank(frames, a.gop, rank, world), ""
+    if a.scene_detect:
+        is_key = b""
+        if rank == 0:      # one process scans: the frames as the encoders take them in (format, window, orientation, scaling), a batch of scanning members
+            t1 = time.perf_counter()
+            encs = [make_encoder(scan=True) for _ in range(max(1, min(a.scan_batch, frames)))]
+            batch = api.NativeBatch([e.drv for e in encs])
+            ud, vd = gop_shard.scan_differences(batch, seq, frames)
+            batch.close()
+            for e in encs:
+                e.close()
+            key, by_scene = api.scene_plan(ud, vd, a.gop)
+            is_key = key.astype(np.uint8).tobytes()
+            plan = f"; scene plan: {int(key.sum())} key ({int(by_scene.sum())} by scene change), scanning {time.perf_counter() - t1:.3f} s"
+        if dist is not None:
+            is_key = dist.broadcast_bytes(is_key, frames, 0)
+        chunks = gop_shard.chunks_from_keys(np.frombuffer(is_key, np.uint8))[rank::world]
+    mine = gop_shard.encode_chunks_frames(make_encoder, seq, chunks)
     if a.analysis:
         with open(a.analysis, "w") as f:
             f.write("".join(f"{t} {line}\n" for t, line in enumerate(records)))
@@ -207,7 +234,7 @@ def main():
     if rank == 0:
         n = gop_shard.write_ivf(a.out, allf, Wd, Hd, a.framerate)
         el = time.perf_counter() - t0
-        print(f"{a.out}: {frames} frames {Win}x{Hin}{f' scaled to {Wd}x{Hd}' if a.resize else ''}, {n} bytes, {world} GPU(s), {frames / el:.1f} frames/s including the host-side frame source")
+        print(f"{a.out}: {frames} frames {Win}x{Hin}{f' scaled to {Wd}x{Hd}' if a.resize else ''}, {n} bytes, {world} GPU(s), {frames / el:.1f} frames/s including the host-side frame source{plan}")
     if dist is not None:
         dist.close()
 

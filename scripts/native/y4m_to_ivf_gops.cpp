@@ -2,7 +2,14 @@
 // bench.py's headline measures, as a complete C++ user of the C ABI.
 //   y4m_to_ivf_gops <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n]
 //                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
-//                   [-deinterlace field|adaptive[:top|bottom]]
+//                   [-deinterlace field|adaptive[:top|bottom]] [-scene-detect]
+// (-scene-detect: the file `y4m_to_ivf -g g` writes with ITS default, scene detection on.  A cut makes a key frame and restarts the GOP
+//  counter, so the chunks are not known up front -- but the whole schedule is a function of the chroma differences of consecutive frames
+//  and of g (vp8host_scene_plan).  So the file is SCANNED first: cut into as many contiguous segments as chunks are in flight, member i
+//  takes in the frame before its segment and then its segment, one scan launch per batch step (vp8drv_batch_scan_frame_host), with the
+//  read-ahead of the coding loop.  The plan gives the chunks, of any length up to g, and they are coded side by side: a member whose
+//  chunk ends takes the next one from a shared queue and starts it with force_key while the others carry on.  Refused with -denoise and
+//  -deinterlace adaptive: their histories follow the frames taken in, and the schedule would depend on itself.)
 // (-deinterlace: as in y4m_to_ivf.cpp -- the history of adaptive restarts at every GOP's key frame, so a chunk sees what the serial program sees)
 // (-aq N: as in y4m_to_ivf.cpp -- the map depends on the current frame alone, so a chunk codes the frames the serial program codes)
 // (-denoise N: as in y4m_to_ivf.cpp -- the history restarts at every GOP's key frame, so a chunk sees the frames the serial program sees)
@@ -16,8 +23,9 @@
 // check_SSIM sends back is reported (the file is then not the serial program's: see below).
 // The file is, byte for byte, what `y4m_to_ivf -no-scene-detect -g g` (one video, frame after frame: the reference's loop) writes --
 // as long as no frame is sent back by check_SSIM to be a key frame (the reference then restarts its GOP counter, vp8enc.cpp:443-453,
-// intra_part.h:1091, and the serial run's later key frames move; with the default -SSIM-target -1 none is) and no scene detection
-// is asked for (a cut moves the key frames the same way).  tests/test_gpu_file_roundtrip.py holds the two programs against each other.
+// intra_part.h:1091, and the serial run's later key frames move; with the default -SSIM-target -1 none is).  Without -scene-detect
+// the serial program must be run without it too (a cut moves the key frames the same way).  tests/test_gpu_file_roundtrip.py and
+// tests/test_gpu_scene_tools.py hold the two programs against each other.
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -45,6 +53,7 @@ int main(int argc, char **argv) {
     int denoise = 0;         // -denoise
     int aq = 0;              // -aq
     int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
+    bool scene = false;      // -scene-detect
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -60,6 +69,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-batch")) batch = atoi(val());
         else if (!strcmp(argv[i], "-denoise")) denoise = atoi(val());
         else if (!strcmp(argv[i], "-aq")) aq = atoi(val());
+        else if (!strcmp(argv[i], "-scene-detect")) scene = true;
         else if (!strcmp(argv[i], "-deinterlace")) {
             const char *f = val(), *colon = strchr(f, ':');
             const size_t len = colon ? (size_t)(colon - f) : strlen(f);
@@ -80,6 +90,8 @@ int main(int argc, char **argv) {
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (cfg.gop_size < 1 || batch < 1 || batch > VP8HIP_MAX_BATCH || in_flight < 1) { fprintf(stderr, "bad -g / -batch / -chunks\n"); return 2; }
+    if (scene && denoise) { fprintf(stderr, "-scene-detect with -denoise: the denoiser's history follows the frames taken in, the scan would disturb it (y4m_to_ivf codes this)\n"); return 2; }
+    if (scene && deint == 2) { fprintf(stderr, "-scene-detect with -deinterlace adaptive: its history follows the frames taken in, the scan would disturb it (y4m_to_ivf codes this)\n"); return 2; }
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = now();
     FILE *in = fopen(argv[1], "rb");
@@ -151,6 +163,80 @@ int main(int argc, char **argv) {
     uint8_t *pinned = nullptr;
     CK(vp8hip_host_alloc(0, (size_t)in_flight * 2 * rec, reinterpret_cast<void **>(&pinned)));
     const double t_made = now();
+    // frame f of the file into buffer `parity` of the chunk in flight j (get_yuv420_frame, encIO.h:203-254), with the next frame's marker if there is one
+    auto slot_of = [&](int j, int parity) { return pinned + ((size_t)j * 2 + (size_t)(parity & 1)) * rec; };
+    auto read_frame = [&](int j, int parity, int f) {
+        const size_t want = f + 1 < nframes ? rec : fsz;
+        if (pread(fd, slot_of(j, parity), want, (off_t)(first + (size_t)f * rec)) != (ssize_t)want) return (int)VP8HIP_ERR_ARG;
+        if (want == rec && !vp8host_y4m_frame_marker_ok(slot_of(j, parity) + fsz)) return (int)VP8HIP_ERR_FORMAT;
+        return (int)VP8HIP_OK;
+    };
+    // -scene-detect: the scan phase, then the plan.  chunk c = frames [cstart[c], cstart[c + 1])
+    std::vector<int> cstart;
+    int plan_keys = 0, plan_scene = 0;
+    if (scene) {
+        std::vector<int32_t> ud((size_t)nframes, 0), vd((size_t)nframes, 0);
+        std::vector<int> src((size_t)nbatches, VP8HIP_OK);
+        std::atomic<bool> scan_failed{false};      // one batch's scan failed: the others stop at their next step
+        std::vector<std::thread> sth;
+        for (int k = 0; k < nbatches; ++k)
+            sth.emplace_back([&, k] {
+                const int j0 = k * batch, n = (k == nbatches - 1 ? in_flight - j0 : batch);
+                // member i walks segment j0 + i of the file, the frame before it first: step t takes in frame lo[i] + t
+                int lo[VP8HIP_MAX_BATCH], hi[VP8HIP_MAX_BATCH], steps = 0;
+                for (int i = 0; i < n; ++i) {
+                    const int s = (int)((long)(j0 + i) * nframes / in_flight);
+                    hi[i] = (int)((long)(j0 + i + 1) * nframes / in_flight);
+                    lo[i] = s > 0 ? s - 1 : 0;
+                    if (hi[i] - lo[i] > steps) steps = hi[i] - lo[i];
+                }
+                const void *y[VP8HIP_MAX_BATCH], *u[VP8HIP_MAX_BATCH], *v[VP8HIP_MAX_BATCH];
+                const uint8_t *py[VP8HIP_MAX_BATCH], *pu[VP8HIP_MAX_BATCH], *pv[VP8HIP_MAX_BATCH];
+                int on[VP8HIP_MAX_BATCH], on_next[VP8HIP_MAX_BATCH];
+                int32_t du[VP8HIP_MAX_BATCH], dv[VP8HIP_MAX_BATCH];
+                int &r = src[k];
+                auto step = [&](int t, int *members, bool load) {      // the members' planes of step t (read from the file first: load)
+                    int any = 0;
+                    for (int i = 0; i < n; ++i) {
+                        members[i] = lo[i] + t < hi[i];
+                        const uint8_t *p = nullptr;
+                        if (members[i]) {
+                            if (load && r == VP8HIP_OK) r = read_frame(j0 + i, t, lo[i] + t);
+                            p = slot_of(j0 + i, t);
+                            any = 1;
+                        }
+                        y[i] = py[i] = p; u[i] = pu[i] = p ? p + ysz : nullptr; v[i] = pv[i] = p ? p + ysz + csz : nullptr;
+                    }
+                    return any && r == VP8HIP_OK;
+                };
+                step(0, on, true);
+                for (int t = 0; t < steps && r == VP8HIP_OK && !scan_failed.load(); ++t) {
+                    step(t, on, false);
+                    r = vp8drv_batch_scan_frame_host(bat[k], on, y, u, v);
+                    if (r == VP8HIP_OK && t + 1 < steps && step(t + 1, on_next, true))      // the next frame read and on its way while this one is scanned
+                        r = vp8drv_batch_prefetch_frame_host(bat[k], py, pu, pv);
+                    if (r == VP8HIP_OK) r = vp8drv_batch_scan_result(bat[k], on, du, dv);
+                    for (int i = 0; i < n && r == VP8HIP_OK; ++i)
+                        if (on[i] && (t > 0 || lo[i] == 0)) { ud[(size_t)(lo[i] + t)] = du[i]; vd[(size_t)(lo[i] + t)] = dv[i]; }      // (a segment's step 0 is the frame before it)
+                }
+                if (r != VP8HIP_OK) scan_failed = true;
+            });
+        for (auto &t : sth) t.join();
+        for (int k = 0; k < nbatches; ++k)
+            if (src[k] != VP8HIP_OK) {
+                fprintf(stderr, "y4m_to_ivf_gops: the scan failed: %d (%s)\n", src[k], vp8hip_status_string(src[k]));
+                return 1;
+            }
+        std::vector<uint8_t> is_key((size_t)nframes), by_scene((size_t)nframes);
+        plan_keys = vp8host_scene_plan(ud.data(), vd.data(), nframes, g, is_key.data(), by_scene.data());
+        for (int t = 0; t < nframes; ++t) {
+            if (is_key[(size_t)t]) cstart.push_back(t);
+            plan_scene += by_scene[(size_t)t];
+        }
+        cstart.push_back(nframes);
+    }
+    const double t_scanned = now();
+    std::atomic<int> next_chunk{0};
     if (cfg.ssim_target > 0.0f)
         fprintf(stderr, "y4m_to_ivf_gops: -SSIM-target %.2f: a frame that check_SSIM sends back to be a key frame restarts the serial program's GOP counter "
                         "(vp8enc.cpp:443-453); if that happens this file is a valid stream but NOT byte for byte `y4m_to_ivf -g %d`'s (reported below)\n", cfg.ssim_target, g);
@@ -192,7 +278,81 @@ int main(int argc, char **argv) {
             const void *y[VP8HIP_MAX_BATCH], *u[VP8HIP_MAX_BATCH], *v[VP8HIP_MAX_BATCH];
             const uint8_t *py[VP8HIP_MAX_BATCH], *pu[VP8HIP_MAX_BATCH], *pv[VP8HIP_MAX_BATCH];
             int on[VP8HIP_MAX_BATCH], on_next[VP8HIP_MAX_BATCH], force[VP8HIP_MAX_BATCH], was_key[VP8HIP_MAX_BATCH];
-            for (int round = 0; rc[k] == VP8HIP_OK && !failed.load() && (size_t)round * in_flight + j0 < (size_t)nchunks; ++round) {
+            if (scene) {
+                // The planned chunks, the members advancing independently: cur[i] = the file frame member i has coded and not yet handed
+                // out, nxt[i] = the one it takes in next (-1: none), end[i] = where its chunk ends, cnt[i] = frames it has taken in (the
+                // parity of its two buffers).  The order of calls per step is that of the loop below.
+                int cur[VP8HIP_MAX_BATCH], nxt[VP8HIP_MAX_BATCH], end[VP8HIP_MAX_BATCH], cnt[VP8HIP_MAX_BATCH], first_of_chunk[VP8HIP_MAX_BATCH];
+                const int planned = (int)cstart.size() - 1;
+                auto advance = [&](int i) {      // what member i takes in after cur[i]: its chunk's next frame, or the first of the next chunk in the queue
+                    force[i] = 0;
+                    if (cur[i] >= 0 && cur[i] + 1 < end[i]) { nxt[i] = cur[i] + 1; return; }
+                    const int c = next_chunk.fetch_add(1);
+                    if (c >= planned) { nxt[i] = -1; return; }
+                    nxt[i] = cstart[(size_t)c];
+                    end[i] = cstart[(size_t)c + 1];
+                    force[i] = 1;
+                };
+                auto stage = [&](int *members, bool load) {      // the members' next frames: read into their free buffers (load), and the planes
+                    int any = 0;
+                    for (int i = 0; i < n; ++i) {
+                        members[i] = nxt[i] >= 0;
+                        const uint8_t *p = nullptr;
+                        if (members[i]) {
+                            if (load && rc[k] == VP8HIP_OK) rc[k] = read_frame(j0 + i, cnt[i], nxt[i]);
+                            p = slot_of(j0 + i, cnt[i]);
+                            any = 1;
+                        }
+                        y[i] = py[i] = p; u[i] = pu[i] = p ? p + ysz : nullptr; v[i] = pv[i] = p ? p + ysz + csz : nullptr;
+                    }
+                    return any && rc[k] == VP8HIP_OK;
+                };
+                auto encode = [&] {      // nxt becomes cur; the frames after them are read and started on their way
+                    int fk[VP8HIP_MAX_BATCH];
+                    stage(on_next, false);
+                    for (int i = 0; i < n; ++i) fk[i] = force[i];
+                    rc[k] = vp8drv_batch_encode_frame_host(bat[k], on_next, y, u, v, fk, was_key);
+                    if (rc[k] != VP8HIP_OK) return;
+                    for (int i = 0; i < n; ++i) {
+                        if (!on_next[i]) { cur[i] = -1; continue; }
+                        cur[i] = nxt[i];
+                        first_of_chunk[i] = fk[i];
+                        ++cnt[i];
+                        advance(i);
+                    }
+                    if (stage(on, true)) rc[k] = vp8drv_batch_prefetch_frame_host(bat[k], py, pu, pv);
+                };
+                for (int i = 0; i < n; ++i) { cur[i] = -1; cnt[i] = 0; end[i] = 0; advance(i); }
+                if (stage(on, true)) encode();
+                while (rc[k] == VP8HIP_OK && !failed.load()) {
+                    int cur_on[VP8HIP_MAX_BATCH], cur_f[VP8HIP_MAX_BATCH], any = 0, more = 0;
+                    for (int i = 0; i < n; ++i) { cur_f[i] = cur[i]; cur_on[i] = cur[i] >= 0; any |= cur_on[i]; more |= nxt[i] >= 0; }
+                    if (!any) break;
+                    rc[k] = vp8drv_batch_get_frame_begin(bat[k], cur_on);        // the frames' types are final here (their verdicts are in)
+                    if (rc[k] != VP8HIP_OK) break;
+                    for (int i = 0; i < n; ++i)
+                        if (cur_on[i]) {
+                            const int key = vp8drv_resolve(drv[j0 + i]) == 1;
+                            keys[k] += key;
+                            if (key && !first_of_chunk[i]) ++resent;      // a frame inside a chunk ended as a key frame: check_SSIM sent it back
+                        }
+                    if (more) encode();
+                    else for (int i = 0; i < n; ++i) cur[i] = -1;
+                    if (rc[k] != VP8HIP_OK) break;
+                    for (int i = 0; i < n && rc[k] == VP8HIP_OK; ++i) {
+                        if (!cur_on[i]) continue;
+                        size_t size = 0;
+                        rc[k] = vp8drv_get_frame_end(drv[j0 + i], buf.data(), buf.size(), &size);
+                        if (rc[k] == VP8HIP_OK) {
+                            std::lock_guard<std::mutex> l(wm);
+                            out_frames[(size_t)cur_f[i]].assign(buf.begin(), buf.begin() + (long)size);
+                            ready[(size_t)cur_f[i]] = 1;
+                        }
+                    }
+                    wcv.notify_all();
+                }
+            }
+            for (int round = 0; !scene && rc[k] == VP8HIP_OK && !failed.load() && (size_t)round * in_flight + j0 < (size_t)nchunks; ++round) {
                 // member i codes chunk c_i = round * in_flight + j0 + i: frames c_i g + t, t < g
                 auto frame_of = [&](int i, int t) { const long c = (long)round * in_flight + j0 + i; return c < nchunks && c * g + t < nframes ? (int)(c * g + t) : -1; };
                 auto slot = [&](int i, int t) { return pinned + ((size_t)(j0 + i) * 2 + (size_t)(t & 1)) * rec; };
@@ -285,8 +445,11 @@ int main(int argc, char **argv) {
                         "valid stream but NOT byte for byte `y4m_to_ivf -g %d`'s\n", resent.load(), g);
     printf("%s: %d frames %dx%d (coded %dx%d) in %d closed GOPs of %d, %d in flight in %d batches, %d key frames, %zu bytes; %d hardware queues\n", argv[2], nframes, W, H, Wc,
            Hc, nchunks, g, in_flight, nbatches, nkeys, total, vp8hip_hw_queues());
+    if (scene)
+        printf("  scene plan: %d key (%d by scene change), %d chunks of at most %d frames; scanning %.3f s (every frame from the file and over the link once more), "
+               "%.0f frames/s from the scan's start to the last frame coded\n", plan_keys, plan_scene, (int)cstart.size() - 1, g, t_scanned - t_made, nframes / (t_coded - t_made));
     printf("  seconds: opening %.3f, %d contexts, their scratch and frame buffers %.3f, reading + coding %.3f (%.0f frames/s, %.2f M macroblocks/s, every frame from the file and over the "
-           "host-device link both ways), writing %.3f, tearing down %.3f\n", t_read - t_start, in_flight, t_made - t_read, t_coded - t_made, nframes / (t_coded - t_made),
-           (double)nframes * (Wc / 16) * (Hc / 16) / (t_coded - t_made) / 1e6, t_written - t_coded, now() - t_written);
+           "host-device link both ways), writing %.3f, tearing down %.3f\n", t_read - t_start, in_flight, t_made - t_read, t_coded - t_scanned, nframes / (t_coded - t_scanned),
+           (double)nframes * (Wc / 16) * (Hc / 16) / (t_coded - t_scanned) / 1e6, t_written - t_coded, now() - t_written);
     return 0;
 }

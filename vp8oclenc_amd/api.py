@@ -35,7 +35,8 @@ ABI_SYMBOLS = [
     "vp8hip_encode_frame_begin", "vp8hip_encode_frame_end", "vp8hip_filter_overlap",
     "vp8host_quantizer_ladders", "vp8host_loopfilter_strength", "vp8host_prepare_segments_data", "vp8host_skip_prob",
     "vp8host_gop_init", "vp8host_gop_next", "vp8host_gop_key_coded", "vp8host_gop_inter_flags",
-    "vp8host_gop_frame_done", "vp8host_scene_change", "vp8host_y4m_parse_header", "vp8host_y4m_frame_marker_ok",
+    "vp8host_gop_frame_done", "vp8host_scene_change", "vp8host_scene_plan", "vp8hip_batch_chroma_change_async",
+    "vp8drv_batch_scan_frame_device", "vp8drv_batch_scan_frame_host", "vp8drv_batch_scan_result", "vp8host_y4m_parse_header", "vp8host_y4m_frame_marker_ok",
     "vp8drv_default_config", "vp8drv_create", "vp8drv_destroy", "vp8drv_context", "vp8drv_encode_frame_device",
     "vp8drv_encode_frame_host", "vp8drv_get_stats", "vp8hip_reserve_frame_path", "vp8hip_reserve_frame_path_dense", "vp8drv_resolve", "vp8drv_ready", "vp8drv_batch_ready", "vp8drv_batches_encode_frame_device", "vp8drv_batches_encode_frames_device", "vp8drv_batches_encode_frames_host", "vp8drv_batch_encode_frame_host", "vp8hip_batch_upload_current", "vp8hip_batch_intra_transform", "vp8hip_batch_prefetch_current", "vp8hip_prefetch_current", "vp8drv_prefetch_frame_host", "vp8drv_stage_frame_host", "vp8drv_batch_prefetch_frame_host", "vp8hip_host_alloc", "vp8hip_host_free", "vp8drv_frame_check", "vp8drv_encode_video_device", "vp8hip_check_ssim_ready", "vp8hip_check_ssim_async", "vp8hip_check_ssim_result", "vp8hip_batch_check_ssim_async", "vp8drv_get_frame", "vp8drv_get_frame_begin", "vp8drv_get_frame_end",
     "vp8bs_default_probs", "vp8bs_encode_header", "vp8bs_gather_frame", "vp8bs_ivf_file_header", "vp8bs_ivf_frame_header",
@@ -395,6 +396,20 @@ def scene_change(state: SceneState, Udiff: int, Vdiff: int, frame_number: int) -
     lib = load_library()
     lib.vp8host_scene_change.argtypes = [C.POINTER(SceneState), C.c_int, C.c_int, C.c_int]
     return bool(lib.vp8host_scene_change(C.byref(state), int(Udiff), int(Vdiff), int(frame_number)))
+
+
+def scene_plan(udiff, vdiff, gop_size: int):
+    """vp8host_scene_plan: the serial loop's key-frame schedule with scene detection on, from the chroma differences of a file's frames
+    (entry 0 unused) and the GOP length -> (is_key, by_scene), two bool arrays of len(udiff)."""
+    lib = load_library()
+    ud, vd = np.ascontiguousarray(udiff, np.int32), np.ascontiguousarray(vdiff, np.int32)
+    if ud.ndim != 1 or ud.shape != vd.shape:
+        raise ValueError("scene_plan: udiff and vdiff must be two 1-D arrays of one length")
+    key, scene = np.zeros(ud.size, np.uint8), np.zeros(ud.size, np.uint8)
+    lib.vp8host_scene_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    if lib.vp8host_scene_plan(ud.ctypes.data, vd.ctypes.data, ud.size, int(gop_size), key.ctypes.data, scene.ctypes.data) < 0:
+        raise ValueError(f"scene_plan: refused (gop_size {gop_size})")
+    return key.astype(bool), scene.astype(bool)
 
 
 def prepare_segments_data(is_key: bool, refqi, qi_min: int, reductor: int, sharpness: int, update_filter: bool = False,
@@ -1187,10 +1202,12 @@ class NativeBatch:
         self._key = (C.c_int * n)()
         self._members = (C.c_int * n)()
 
-    def encode_frame_device(self, planes, members=None, host=False):
+    def encode_frame_device(self, planes, members=None, host=False, force_key=None):
         """planes[i] = (d_y, d_u, d_v) device pointers of member i's frame (None for a member that sits this call out, or
         members[i] false); returns the list of "was a key frame" flags.  host=True: the pointers are HOST addresses
-        (vp8drv_batch_encode_frame_host; the planes stay unchanged until the next call has returned)."""
+        (vp8drv_batch_encode_frame_host; the planes stay unchanged until the next call has returned).  force_key[i] true: member i's
+        frame is a key frame whatever its schedule says (a chunk that starts at a planned key frame)."""
+        fk = None if force_key is None else (C.c_int * self.n)(*[1 if k else 0 for k in force_key])
         for i, p in enumerate(planes):
             on = p is not None and (members is None or members[i])
             self._members[i] = 1 if on else 0
@@ -1198,13 +1215,39 @@ class NativeBatch:
                 self._ptrs[0][i], self._ptrs[1][i], self._ptrs[2][i] = p
         fn = self.lib.vp8drv_batch_encode_frame_host if host else self.lib.vp8drv_batch_encode_frame_device
         fn.argtypes = self.lib.vp8drv_batch_encode_frame_device.argtypes
-        rc = fn(self.h, self._members, self._ptrs[0], self._ptrs[1], self._ptrs[2], None, self._key)
+        rc = fn(self.h, self._members, self._ptrs[0], self._ptrs[1], self._ptrs[2], fk, self._key)
         if rc < 0:
             raise Vp8HipError(f"vp8drv_batch_encode_frame_{'host' if host else 'device'}: {self.lib.vp8hip_status_string(rc).decode()} ({rc})")
         return [bool(k) for k in self._key]
 
-    def encode_frame_host(self, planes, members=None):
-        return self.encode_frame_device(planes, members, host=True)
+    def encode_frame_host(self, planes, members=None, force_key=None):
+        return self.encode_frame_device(planes, members, host=True, force_key=force_key)
+
+    def scan_frame_device(self, planes, members=None, host=False):
+        """The members' frames taken in and their chroma differences against each member's previous frame started, one launch for all
+        (vp8drv_batch_scan_frame_device / _host); nothing is coded.  planes and members as in encode_frame_device; scan_result() follows."""
+        for i, p in enumerate(planes):
+            on = p is not None and (members is None or members[i])
+            self._members[i] = 1 if on else 0
+            if on:
+                self._ptrs[0][i], self._ptrs[1][i], self._ptrs[2][i] = p
+        fn = self.lib.vp8drv_batch_scan_frame_host if host else self.lib.vp8drv_batch_scan_frame_device
+        fn.argtypes = self.lib.vp8drv_batch_encode_frame_device.argtypes[:5]
+        rc = fn(self.h, self._members, self._ptrs[0], self._ptrs[1], self._ptrs[2])
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_batch_scan_frame_{'host' if host else 'device'}: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def scan_frame_host(self, planes, members=None):
+        self.scan_frame_device(planes, members, host=True)
+
+    def scan_result(self):
+        """[(Udiff, Vdiff)] of the members of the last scan call, None for those that sat it out (vp8drv_batch_scan_result)"""
+        ud, vd = (C.c_int32 * self.n)(), (C.c_int32 * self.n)()
+        self.lib.vp8drv_batch_scan_result.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        rc = self.lib.vp8drv_batch_scan_result(self.h, self._members, ud, vd)
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_batch_scan_result: {self.lib.vp8hip_status_string(rc).decode()} ({rc})")
+        return [(ud[i], vd[i]) if self._members[i] else None for i in range(self.n)]
 
     def ready(self) -> bool:
         """no member's check_SSIM verdict is still on its way: the next encode_frame_device would not wait (vp8drv_batch_ready)"""

@@ -149,6 +149,7 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
     }
     if (b->ev_ent_fork) hipEventDestroy(b->ev_ent_fork);
     if (b->ev_ent) hipEventDestroy(b->ev_ent);
+    if (b->ev_chroma) hipEventDestroy(b->ev_chroma);      // (the stream has been synchronised: a member's pending scan has its sums)
     for (int i = 0; i < b->n; ++i) b->c[i]->frame_event = nullptr;
     --g_live_contexts;
     for (int i = 0; i < b->n; ++i) {
@@ -526,6 +527,36 @@ int vp8hip_batch_check_ssim_async(vp8hip_batch *b, const int *active, const int3
         launch_check_fallback(b->stream, it, n, c0->ssim_target, c0->mbw, c0->mbh, c0->conformant);
     }
     HIPCHK(c0, hipGetLastError());
+    return VP8HIP_OK;
+}
+
+// scene_change()'s two sums (vp8enc.cpp:265-284) for the active members in ONE launch with its fold, nobody waiting: the members' words are
+// those of vp8hip_chroma_change_async, the event is the batch's, and vp8hip_chroma_change_result per member takes the answer.
+int vp8hip_batch_chroma_change_async(vp8hip_batch *b, const int *active) {
+    if (!b) return VP8HIP_ERR_ARG;
+    vp8hip_ctx *c0 = b->c[0];
+    USE_DEVICE(c0);   // (joins the head-of-frame stream: the members' intake is in front of what follows)
+    const Members a = active_members(b, active);
+    for (int k = 0; k < a.n; ++k)
+        if (a.m[k]->cur_count == 0) return VP8HIP_ERR_STATE;
+    if (!b->ev_chroma) HIPCHK(c0, hipEventCreateWithFlags(&b->ev_chroma, FRAME_EVENT_FLAGS));
+    ChromaScan q[MAX_BATCH];
+    int nq = 0;
+    for (int k = 0; k < a.n; ++k) {
+        vp8hip_ctx *c = a.m[k];
+        flush_scan(c);      // (a parameter scan still waiting for a launch uses the same partial sums)
+        c->chroma_pending = true;
+        c->chroma_none = c->cur_count < 2;
+        c->chroma_by_batch = true;
+        if (c->chroma_none) continue;
+        q[nq++] = ChromaScan{&c->cur, &c->cur_prev, c->d_stats + 8, reinterpret_cast<uint32_t *>(c->h_verdict) + 32};
+    }
+    if (!nq) return VP8HIP_OK;
+    launch_chroma_sad_batch(b->stream, q, nq);
+    HIPCHK(c0, hipGetLastError());
+    HIPCHK(c0, hipEventRecord(b->ev_chroma, b->stream));
+    // (the next frame's intake overwrites the older of the two surfaces the scan reads: on a head-of-frame stream it waits for the scan)
+    if (b->prep) HIPCHK(c0, hipStreamWaitEvent(b->prep, b->ev_chroma, 0));
     return VP8HIP_OK;
 }
 

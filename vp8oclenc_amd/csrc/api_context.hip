@@ -520,6 +520,7 @@ int vp8hip_chroma_change_async(vp8hip_ctx *c) {
     if (c->cur_count == 0) return VP8HIP_ERR_STATE;
     c->chroma_pending = true;
     c->chroma_none = c->cur_count < 2;
+    c->chroma_by_batch = false;
     if (c->chroma_none) return VP8HIP_OK;
     if (!c->ev_chroma) HIPCHK(c, hipEventCreateWithFlags(&c->ev_chroma, hipEventDisableTiming));
     uint32_t *words = reinterpret_cast<uint32_t *>(c->h_verdict) + 32;      // (the verdict block's second half: coherent page-locked memory)
@@ -536,7 +537,9 @@ int vp8hip_chroma_change_result(vp8hip_ctx *c, int32_t *Udiff, int32_t *Vdiff) {
     *Udiff = *Vdiff = 0;
     if (c->chroma_none) return VP8HIP_OK;
     (void)hipSetDevice(c->device);
-    HIPCHK(c, hipEventSynchronize(c->ev_chroma));
+    // (a batch's scan: the batch's event; a batch destroyed since then has synchronised its stream)
+    if (!c->chroma_by_batch) HIPCHK(c, hipEventSynchronize(c->ev_chroma));
+    else if (c->batch && c->batch->ev_chroma) HIPCHK(c, hipEventSynchronize(c->batch->ev_chroma));
     const volatile uint32_t *words = reinterpret_cast<const volatile uint32_t *>(c->h_verdict) + 32;
     const int nc = (c->W / 2) * (c->H / 2);
     *Udiff = (int32_t)words[0] / nc;      // vp8enc.cpp:277, 284

@@ -630,6 +630,49 @@ int vp8drv_batch_prefetch_frame_host(vp8drv_batch *b, const uint8_t *const *y, c
     return vp8hip_batch_prefetch_current(b->hb, y, u, v);
 }
 
+// ---- the scan of a file's chroma differences, batched: what vp8host_scene_plan makes the key-frame schedule of ---------------------
+// The members' frames are taken in and scene_change()'s two sums started (one launch for all of them); nothing is coded and neither the
+// GOP state nor the scene history moves.  Whatever keeps a history of the frames taken in, or numbers them, would be disturbed by frames
+// that are never coded -- and the schedule would then depend on itself: such members are refused, before anything changes.
+//   denoiser:            the previous frame taken in is its history (and a scanned frame would be filtered against it)
+//   deinterlace mode 2:  the previous frame as received is its history
+//   analysis:            numbers the frames taken in and keeps the previous luma
+//   quality statistics:  number their records by the frames taken in
+// (deinterlace mode 1, a source format, scaling, a window, an orientation and a segment mode are functions of the one frame: allowed.)
+static int batch_scan_frame(vp8drv_batch *b, const int *members, const void *const *y, const void *const *u, const void *const *v, bool host) {
+    if (!b || !y || !u || !v) return VP8HIP_ERR_ARG;
+    for (int i = 0; i < b->n; ++i) {
+        const vp8drv *d = b->d[i];
+        if (members && !members[i]) continue;
+        if (d->denoise || d->deinterlace == 2 || d->analysis || d->cfg.quality_stats) return VP8HIP_ERR_STATE;
+    }
+    for (int i = 0; i < b->n; ++i) {   // an open check_SSIM verdict needs the member's current frame: taken before the frame is replaced
+        if (members && !members[i]) continue;
+        const int rc = resolve(b->d[i]);
+        if (rc < 0) return rc;
+    }
+    if (host) DRV_CHK(vp8hip_batch_upload_current(b->hb, members, reinterpret_cast<const uint8_t *const *>(y), reinterpret_cast<const uint8_t *const *>(u),
+                                                  reinterpret_cast<const uint8_t *const *>(v)));
+    else DRV_CHK(vp8hip_batch_set_current_device(b->hb, members, y, u, v));
+    return vp8hip_batch_chroma_change_async(b->hb, members);
+}
+
+int vp8drv_batch_scan_frame_device(vp8drv_batch *b, const int *members, const void *const *y, const void *const *u, const void *const *v) {
+    return batch_scan_frame(b, members, y, u, v, false);
+}
+int vp8drv_batch_scan_frame_host(vp8drv_batch *b, const int *members, const void *const *y, const void *const *u, const void *const *v) {
+    return batch_scan_frame(b, members, y, u, v, true);
+}
+
+int vp8drv_batch_scan_result(vp8drv_batch *b, const int *members, int32_t *udiff, int32_t *vdiff) {
+    if (!b || !udiff || !vdiff) return VP8HIP_ERR_ARG;
+    for (int i = 0; i < b->n; ++i) {
+        if (members && !members[i]) continue;
+        DRV_CHK(vp8hip_chroma_change_result(b->d[i]->hip, &udiff[i], &vdiff[i]));
+    }
+    return VP8HIP_OK;
+}
+
 int vp8drv_resolve(vp8drv *d) {
     if (!d) return VP8HIP_ERR_ARG;
     const int rc = resolve(d);

@@ -449,6 +449,28 @@ void vp8host_gop_inter_flags(const vp8host_gop *g, int32_t *use_golden, int32_t 
 
 void vp8host_gop_frame_done(vp8host_gop *g) { ++g->frame_number; }
 
+int vp8host_scene_plan(const int32_t *udiff, const int32_t *vdiff, int nframes, int gop_size, uint8_t *is_key, uint8_t *by_scene) {
+    if (!udiff || !vdiff || !is_key || nframes < 0 || gop_size < 1) return -1;
+    vp8host_gop g;
+    vp8host_scene_state sc{};
+    vp8host_gop_init(&g, gop_size, 1);      // (the alt-ref period does not reach the key-frame counters)
+    int keys = 0;
+    for (int t = 0; t < nframes; ++t) {
+        vp8host_gop_next(&g);
+        bool key = g.current_is_key != 0, scene = false;
+        if (!key && vp8host_scene_change(&sc, udiff[t], vdiff[t], g.frame_number)) key = scene = true;
+        if (key) {
+            sc.last_key_detect = g.frame_number;
+            vp8host_gop_key_coded(&g);
+            ++keys;
+        }
+        vp8host_gop_frame_done(&g);
+        is_key[t] = key ? 1 : 0;
+        if (by_scene) by_scene[t] = scene ? 1 : 0;
+    }
+    return keys;
+}
+
 // The two filter tables of the device's scaler (include/vp8hip_host.h): integer-only for the area filter, `double` for Lanczos-3.
 int vp8host_scale_taps(int n_in, int n_out, int kind, int32_t *n_taps, int32_t *start, int16_t *coef) {
     constexpr int MAXT = VP8HOST_SCALE_MAX_TAPS;

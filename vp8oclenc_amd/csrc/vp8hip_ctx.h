@@ -260,6 +260,7 @@ struct vp8hip_ctx {
     hipEvent_t ev_h2d = nullptr, ev_stage_read[2] = {nullptr, nullptr};
     hipEvent_t ev_chroma = nullptr;    // behind the fold of vp8hip_chroma_change_async
     bool chroma_pending = false, chroma_none = false;
+    bool chroma_by_batch = false;      // the pending scan is vp8hip_batch_chroma_change_async's: its event is the batch's
     bool stage_read_valid[2] = {false, false};
     DeviceBuf h2d_stage[2];            // (both of the planes' exact size: a prefetch counts only for the size it was made for)
     int h2d_idx = 0;
@@ -313,6 +314,7 @@ struct vp8hip_batch {
     hipStream_t ent = nullptr;           // nullptr: the stage stays in the chain (VP8HIP_BATCH_ENT_STREAM=0)
     hipEvent_t ev_ent_fork = nullptr, ev_ent = nullptr;
     bool ent_fork_fresh = false;         // nothing was enqueued for a member since ev_ent_fork was recorded
+    hipEvent_t ev_chroma = nullptr;      // behind the launch of vp8hip_batch_chroma_change_async (made on first use)
     // vp8hip_batch_upload_current: the members' new frames from HOST memory.  The copies run on a stream of their own (the copy engines,
     // beside whatever the batch's stream still has: the previous frame's loop filter) into one of two staging buffers per member; the
     // launch that packs them waits for the copies, the copies for the pack that last read their buffer.

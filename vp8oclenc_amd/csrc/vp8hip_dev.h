@@ -352,6 +352,9 @@ size_t rc_partial_words();   // uint32 words of per-workgroup partial sums the t
 void launch_lf_strength(hipStream_t s, const Frame &cur, uint32_t *partial, uint32_t *stats);    // [0] sum Y, [1] sum of squared deviations
 void launch_chroma_sad(hipStream_t s, const Frame &cur, const Frame &prev, uint32_t *partial, uint32_t *stats);   // [2] sum |dU|, [3] sum |dV|
 void launch_auto_segments(hipStream_t s, const ScanRequest &q);   // strength + prepare_segments_data, all on the device
+// the chroma scan of n <= MAX_BATCH contexts of one geometry in ONE launch, fold included: words[0] = sum |dU|, words[1] = sum |dV| (host memory the device writes)
+struct ChromaScan { const Frame *cur, *prev; uint32_t *partial, *words; };
+void launch_chroma_sad_batch(hipStream_t s, const ChromaScan *q, int n);
 
 // coefficient entropy stage (kernels_ent.hip): flags + third context + token histogram + probabilities
 constexpr int ENT_NCTX = 4 * 8 * 3 * 11;

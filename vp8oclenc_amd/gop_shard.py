@@ -18,6 +18,33 @@ def gop_chunks(total_frames: int, gop_size: int) -> list[tuple[int, int]]:
     return [(s, min(gop_size, total_frames - s)) for s in range(0, total_frames, gop_size)]
 
 
+def chunks_from_keys(is_key) -> list[tuple[int, int]]:
+    """(first frame, length) of every closed GOP of a planned key-frame schedule (api.scene_plan: the serial loop's own key frames with
+    scene detection on): a chunk starts at every key frame and runs up to the next.  Frame 0 must be one."""
+    keys = [t for t, k in enumerate(is_key) if k]
+    if len(is_key) and (not keys or keys[0] != 0):
+        raise ValueError("chunks_from_keys: frame 0 must be a key frame")
+    return [(s, e - s) for s, e in zip(keys, keys[1:] + [len(is_key)])]
+
+
+def scan_differences(batch, sequence, frames: int):
+    """(udiff, vdiff) of a sequence's first `frames` frames, entry 0 unused: the chroma differences of consecutive frames as the members
+    of `batch` (api.NativeBatch) take them in, what api.scene_plan makes the key-frame schedule of.  The sequence is cut into as many
+    contiguous segments as the batch has members; member i takes in the frame before its segment and then its segment, one scan launch
+    per step (NativeBatch.scan_frame_host).  Nothing is coded: the batch codes afterwards what a fresh one codes."""
+    n = batch.n
+    lo = [max(i * frames // n - 1, 0) for i in range(n)]
+    hi = [(i + 1) * frames // n for i in range(n)]
+    ud, vd = np.zeros(frames, np.int32), np.zeros(frames, np.int32)
+    for t in range(max(h - l for l, h in zip(lo, hi))):
+        held = [[np.ascontiguousarray(p) for p in sequence.frame(lo[i] + t)] if lo[i] + t < hi[i] else None for i in range(n)]
+        batch.scan_frame_host([None if h is None else tuple(p.ctypes.data for p in h) for h in held])
+        for i, r in enumerate(batch.scan_result()):      # (waits for the scan, which is behind the copies out of `held`)
+            if r is not None and (t > 0 or lo[i] == 0):      # (a segment's step 0 is the frame before it)
+                ud[lo[i] + t], vd[lo[i] + t] = r
+    return ud, vd
+
+
 def chunks_of_rank(total_frames: int, gop_size: int, rank: int, world: int) -> list[tuple[int, int]]:
     return gop_chunks(total_frames, gop_size)[rank::world]
 
