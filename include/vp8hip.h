@@ -225,11 +225,31 @@ int vp8hip_set_source_format(vp8hip_ctx *ctx, int format);
  * vp8hip_prefetch_current stages the plane's 2 w h or 4 w h bytes.  YUY2 / UYVY follow the I422 rule.  BGRA / RGBA are read with the
  * colour matrix of vp8hip_set_source_colour: matrix = one of enum vp8host_colour_matrix: BT.601 or BT.709, limited or full range (the
  * integer tables and the rule are in include/vp8hip_host.h, vp8host_convert_frame_colour is the rule in plain C++), 0 = BT.601 limited,
- * the default.  The matrix is stored with the context and read by the RGB formats only, so it may be set before or after the format,
+ * the default.  The matrix is stored with the context and read by the RGB formats and by a tone-mapped source
+ * (vp8hip_set_source_transfer) only, so it may be set before or after the format,
  * and with any other format it changes no byte.  Waits for the context's streams: not a per-frame call.  A pending
  * vp8hip_prefetch_current made under another matrix is dropped.  Anything but 0 .. 3: VP8HIP_ERR_ARG and nothing has changed.  All
  * members of a batch must agree on the matrix as on the format. */
 int vp8hip_set_source_colour(vp8hip_ctx *ctx, int matrix);
+/* HDR ten-bit sources made SDR.  P010 and I010 are what a hardware decoder or a phone delivers for HDR video -- HLG from phones, PQ
+ * from HDR10 sources, both BT.2020 -- and the format rule alone keeps the PQ or HLG signal and the BT.2020 primaries, which every VP8
+ * player then shows as BT.601 / BT.709 SDR: grey and flat, or dim and desaturated.  transfer: one of enum vp8host_transfer
+ * (include/vp8hip_host.h, which states the rule bit for bit: inverse transfer, BT.2020 -> BT.709 primaries, a tone curve from `peak`
+ * nits to SDR white, the SDR transfer, and the colour matrix of vp8hip_set_source_colour on the way back to Y'CbCr;
+ * vp8host_tonemap_frame is the rule in plain C++); peak: the peak luminance the source was graded for, 400 .. 10000 nits.  With a
+ * transfer in force ONE launch (k_tonemap_b) stands where k_convert_b stands and writes the same staging buffer, so every way a frame
+ * becomes current takes it -- vp8hip_set_current_device, vp8hip_upload_current, vp8hip_prefetch_current and the batched forms -- and
+ * the window in front of it and the deinterlacer, the orientation, the scaler, the pack and the denoiser behind it see what they see
+ * for the equivalent SDR I420 frame.  The setter makes the rule's four tables (40 KiB) and uploads them into a buffer of the context.
+ * VP8HOST_TRANSFER_SDR (0, the default; peak is not looked at): no launch, no allocation -- the table buffer is released -- and no
+ * byte changes: P010 / I010 frames are converted by k_convert_b again.
+ * The rule covers P010 and I010 only.  Like the colour matrix the transfer may be set before or after the format: with I420 in force
+ * it is held and nothing reads it, and whichever of the two setters would complete another combination -- this one with NV12, 4:2:2,
+ * 4:4:4 or a packed format in force, vp8hip_set_source_format to one of those with a transfer in force -- returns VP8HIP_ERR_ARG and
+ * changes nothing, as does a peak out of range or an unknown transfer.  Waits for the context's streams: not a per-frame call.  A
+ * pending vp8hip_prefetch_current made under another transfer or peak is dropped.  All members of a batch must agree on transfer and
+ * peak as on the format.  (A context with hidden alt-refs refuses every source format but I420, so it never tone-maps.) */
+int vp8hip_set_source_transfer(vp8hip_ctx *ctx, int transfer, int peak);
 /* Temporal noise reduction of the source frames, the third stage of the input side (libvpx: --noise-sensitivity); the reference never
  * did anything about noise.  level 1, 2, 3: every frame that becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the
  * pack out of a vp8hip_prefetch_current staging buffer, vp8hip_batch_set_current_device, vp8hip_batch_upload_current, with or without a
@@ -628,7 +648,9 @@ const char *vp8hip_status_string(int status);
  * also under 4010: hidden alternate reference frames (vp8hip_arf_filter_device, vp8hip_arf_filter_host, vp8hip_arf_result,
  * vp8hip_arf_release, vp8hip_loop_filter_hidden, vp8host_arf_filter_frame, vp8host_arf_round_divide, vp8drv_set_arf,
  * vp8drv_encode_arf_device, vp8drv_encode_arf_host, vp8drv_get_arf_stats; entry points only, and the value VP8HIP_ALTREF_HIDDEN of
- * the existing is_altref fields: vp8drv_config, vp8drv_stats, vp8hip_header_params and vp8bs_frame keep their layout). */
+ * the existing is_altref fields: vp8drv_config, vp8drv_stats, vp8hip_header_params and vp8bs_frame keep their layout);
+ * also under 4010: HDR tone mapping (vp8hip_set_source_transfer, vp8drv_set_source_transfer, vp8host_tonemap_tables,
+ * vp8host_tonemap_frame; entry points only: vp8drv_config is unchanged). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

@@ -271,6 +271,13 @@ int vp8drv_set_source_format(vp8drv *d, int format);
  * relative to the format; VP8HIP_ERR_ARG: not one of the four matrices, or cfg.device_params = 0; VP8HIP_ERR_STATE: the driver is a
  * member of a live batch (vp8drv_batch_create refuses members that differ). */
 int vp8drv_set_source_colour(vp8drv *d, int matrix);
+/* The transfer function and peak P010 / I010 source frames carry (vp8hip_set_source_transfer; enum vp8host_transfer and the rule:
+ * include/vp8hip_host.h): PQ or HLG frames are tone-mapped to SDR on the device, 0 = off, the default.  The rules of
+ * vp8drv_set_source_format: an entry point, between frames, in any order relative to the format (whichever of the two completes a
+ * combination the rule does not cover is refused); VP8HIP_ERR_ARG: an unknown transfer, a peak outside 400 .. 10000, a format in
+ * force other than I420, P010 or I010, or cfg.device_params = 0; VP8HIP_ERR_STATE: the driver is a member of a live batch
+ * (vp8drv_batch_create refuses members that differ in transfer or peak). */
+int vp8drv_set_source_transfer(vp8drv *d, int transfer, int peak);
 /* Source frames that are the window of a pitched surface, and source frames stored sideways or upside down
  * (vp8hip_set_source_window, vp8hip_set_source_orientation; the rules: include/vp8hip_host.h).  Entry points, not fields of
  * vp8drv_config, for the reason vp8drv_set_denoise is one; call them after vp8drv_create and before the first frame, or between

@@ -155,6 +155,61 @@ int vp8host_convert_frame_colour(int format, int matrix, int width, int height, 
                                  uint8_t *y, uint8_t *u, uint8_t *v);
 /* the table above: c = the Y, U and V rows one after the other, each in the order R, G, B.  0, or -1: unknown matrix, null pointer */
 int vp8host_colour_coefficients(int matrix, int32_t c[9], int32_t *y_offset);
+
+/* HDR SOURCES MADE SDR (vp8hip_set_source_transfer, include/vp8hip.h; k_tonemap_b): the ONE integer rule that makes 8-bit SDR I420 of
+ * a ten-bit PQ (SMPTE ST 2084, HDR10) or HLG (BT.2100) frame.  The project's own: without it the planar rule above keeps the PQ or HLG
+ * signal and the BT.2020 primaries, and a VP8 player, which shows BT.601 / BT.709 SDR, shows PQ grey and flat and HLG dim and
+ * desaturated.  It applies to formats P010 (4) and I010 (5) ONLY; with I420 (0) in force a transfer is held and nothing reads it;
+ * every other format refuses it.  transfer = one of enum vp8host_transfer; peak P = the display peak the source was graded for, an
+ * integer number of nits, 400 .. 10000 (the tools default to 1000).  The source is BT.2020 non-constant-luminance, limited range, ten
+ * bits; chroma is the 2x2 block's one (Cb, Cr) pair for all four pixels (no siting, as everywhere here).
+ *
+ * Per pixel, with y = Y' - 64, cb = Cb - 512, cr = Cr - 512 (every ten-bit code is accepted, those outside 64 .. 940 included; the
+ * low six bits of a P010 word and the high six of an I010 word are ignored); >> is the arithmetic shift:
+ *     R' = clamp((38295 y            + 55209 cr + 4096) >> 13, 0, 4095)       12-bit full-range BT.2020 R'G'B'
+ *     G' = clamp((38295 y -  6161 cb - 21391 cr + 4096) >> 13, 0, 4095)       (every term and sum fits int32)
+ *     B' = clamp((38295 y + 70440 cb            + 4096) >> 13, 0, 4095)
+ *     m  = max(R', G', B');  g = gain[m];  aR = lin[R'], aG = lin[G'], aB = lin[B']       20-bit linear light, 2^20 = peak
+ *     tR = max(0, ( 1701 aR -  602 aG -   75 aB + 512) >> 10)      BT.2020 -> BT.709 primaries, times 1024; every row sums to 1024,
+ *     tG = max(0, ( -128 aR + 1161 aG -    9 aB + 512) >> 10)      so grey stays grey exactly; every sum fits int32
+ *     tB = max(0, (  -19 aR -  103 aG + 1146 aB + 512) >> 10)
+ *     o  = min(65535, (t * g + 2^19) >> 20)       per component; a 64-bit product (at most 21 + 23 bits); 65535 = SDR white, linear
+ *     c8 = o < 4096 ? lo[o] : hi[o >> 4]          8-bit full-range R, G, B
+ * The I420 output is exactly the BGRA rule above applied to the pixel (B, G, R) = the three c8: Y = off + ((cR R + cG G + cB B + 128)
+ * >> 8), U and V from the 2x2 sums, with the colour matrix of vp8hip_set_source_colour (default BT.601 limited).  So a tone-mapped
+ * frame EQUALS vp8host_convert_frame_colour(BGRA, matrix, ...) of the c8 picture, byte for byte (tests/test_tonemap_cpu.py holds it
+ * to that).
+ *
+ * The four tables are computed on the host in double, once per (transfer, peak), with e = i / 4095, i = 0 .. 4095:
+ *     PQ   p = e^(1/m2),  N = 10000 (max(p - c1, 0) / (c2 - c3 p))^(1/m1) nits  (m1 = 2610/16384, m2 = 128 * 2523/4096, c1 = 3424/4096,
+ *          c2 = 32 * 2413/4096, c3 = 32 * 2392/4096);  D = min(N, P) nits;  s = D / P
+ *     HLG  s = e^2 / 3 for e <= 1/2, else (exp((e - c) / a) + b) / 12  (a = 0.17883277, b = 0.28466892, c = 0.55991073: BT.2100's inverse
+ *          OETF);  D = P s^gamma,  gamma = 1.2 + 0.42 log10(P / 1000).  HERE THE RULE DEPARTS FROM BT.2100: its OOTF takes the
+ *          luminance term on Ys = 0.2627 R + 0.6780 G + 0.0593 B, this one takes it on the LARGEST component, m above.  That lets one
+ *          gain table, indexed by one scalar, serve both transfers (PQ's tone curve is applied on the largest component too, which
+ *          keeps hue and never clips a component the curve has not seen); on grey the two agree exactly, on saturated colours this
+ *          one is somewhat darker.
+ *     tone curve   x = D / 203 (BT.2408's reference white), w = P / 203,  T = x (1 + x / w^2) / (1 + x): slope 1 at black, T(w) = 1
+ *     lin[i]  = min(2^20 - 1, rint(2^20 s))
+ *     gain[i] = rint(65535 * 2^20 * T / lin[i]) where lin[i] > 0; the entries below the first non-zero lin take that entry's gain
+ *     lo[j]   = rint(255 (j / 65535)^(1/2.4))                          j = 0 .. 4095
+ *     hi[j]   = rint(255 (min(16 j + 8, 65535) / 65535)^(1/2.4))       j = 0 .. 4095
+ * What the rule guarantees for PQ at 1000, 4000 and 10000 nits and HLG at 400 and 1000 (tests/test_tonemap_cpu.py asserts each): lin,
+ * the grey ramp's o and its c8 never decrease; lin[0] = 0 and code 4095 gives c8 = 255; lin stays below 2^20 and gain below 2^23, so t is
+ * below 2^21 and t * g below 2^44, far inside 64 bits; grey in (Cb = Cr = 512) gives U = V = 128 exactly.  Measured when the rule was written: 254 of the 256 c8 values
+ * occur on the grey ramp, the largest step between neighbouring 12-bit codes is 3, at the very bottom; PQ 203 nits gives c8 191 .. 194
+ * and HLG 75 % gives 194; on 100 000 random pixels the matrix sums lie in -0.71e9 .. 1.78e9.  Keep these if a constant is ever
+ * changed. */
+typedef enum { VP8HOST_TRANSFER_SDR = 0, VP8HOST_TRANSFER_PQ = 1, VP8HOST_TRANSFER_HLG = 2 } vp8host_transfer;
+#define VP8HOST_PEAK_MIN 400
+#define VP8HOST_PEAK_MAX 10000
+/* the four tables of (transfer, peak).  0, or -1: a transfer other than PQ or HLG, a peak outside 400 .. 10000, a null pointer */
+int vp8host_tonemap_tables(int transfer, int peak, uint32_t lin[4096], uint32_t gain[4096], uint8_t lo[4096], uint8_t hi[4096]);
+/* the rule as plain C++ on those tables: p0, p1, p2 = the planes of a P010 or I010 frame (p2 is not read for P010), y, u, v = tight
+ * I420 of width x height.  0, or -1: a format other than P010 or I010, what vp8host_tonemap_tables refuses, an unknown matrix, a size
+ * vp8host_source_plane_bytes refuses, a null pointer */
+int vp8host_tonemap_frame(int format, int transfer, int peak, int matrix, int width, int height, const uint8_t *p0, const uint8_t *p1,
+                          const uint8_t *p2, uint8_t *y, uint8_t *u, uint8_t *v);
 /* The C tag of a YUV4MPEG2 header (which vp8host_y4m_parse_header, the reference's parser, never looks at): the header line is the
  * bytes up to the first line feed, its tags are separated by spaces, the first tag that starts with C counts.  No C tag, C420,
  * C420jpeg, C420mpeg2, C420paldv: I420; C422: I422; C444: I444; C420p10: I010; C422p10: I210; C444p10: I410.  Returns 0 and the

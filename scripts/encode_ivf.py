@@ -78,6 +78,8 @@ def main():
     ap.add_argument("--source-format", default="", metavar="NAME", help="the format of the frames of --yuv (or of --y4m, instead of its C tag: nv12 and p010 have none): i420, nv12, i422, i444, p010, i010, i210, i410, and for --yuv the packed yuy2, uyvy, bgra, rgba; converted on the device (vp8drv_set_source_format)")
     ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", help="the colour matrix bgra / rgba frames are read with (vp8drv_set_source_colour)")
     ap.add_argument("--source-range", choices=("limited", "full"), default="limited", help="... and the range of the YUV it makes")
+    ap.add_argument("--source-transfer", choices=("pq", "hlg"), default="", help="the ten-bit frames (--source-format p010 or i010, or a C420p10 file) carry a PQ or HLG signal in BT.2020 and are tone-mapped to SDR on the device, written with --source-matrix / --source-range (vp8drv_set_source_transfer)")
+    ap.add_argument("--source-peak", type=int, default=1000, metavar="N", help="... the peak luminance they were graded for, 400..10000 nits")
     ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
     ap.add_argument("--deinterlace", choices=("off", "field", "adaptive"), default="off", metavar="MODE", help="interlaced source frames made progressive on the device (vp8drv_set_deinterlace): field = every missing row interpolated, adaptive = what stands still is woven; the history restarts with every GOP")
     ap.add_argument("--field", choices=("top", "bottom"), default="top", help="... the field that is kept")
@@ -128,6 +130,9 @@ def main():
     except ValueError as e:
         sys.exit(f"{a.y4m or a.yuv or '--source-format'}: {e}")
     fmt = getattr(seq, "format", 0)
+    if a.source_transfer and (fmt not in (api.FORMAT_P010, api.FORMAT_I010) or not api.PEAK_MIN <= a.source_peak <= api.PEAK_MAX):
+        sys.exit(f"--source-transfer {a.source_transfer} --source-peak {a.source_peak}: ten-bit 4:2:0 frames only (--source-format p010 or i010, or a C420p10 file; "
+                 f"these are {api.source_format_name(fmt)}) and a peak of {api.PEAK_MIN}..{api.PEAK_MAX} nits")
     if fmt:
         seq = FormatPlanes(seq)
     frames = min(a.frames, seq.n) if (a.yuv or a.y4m) else a.frames
@@ -173,6 +178,8 @@ def main():
         if fmt:
             enc.drv.set_source_format(fmt)
             enc.drv.set_source_colour(a.source_matrix, a.source_range)
+        if a.source_transfer:
+            enc.drv.set_source_transfer(a.source_transfer, a.source_peak)
         if turns or a.mirror:
             enc.drv.set_source_orientation(turns, int(a.mirror))
         if window:

@@ -26,6 +26,8 @@ ap.add_argument("--field", choices=("top", "bottom"), default="top", help="... t
 ap.add_argument("--source-format", default="", metavar="NAME", help="the device-resident frames are this format's planes (nv12, p010, i444, ..., or the packed yuy2, uyvy, bgra, rgba: vp8drv_set_source_format): what k_convert_b / k_convert_packed_b costs")
 ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", help="the colour matrix bgra / rgba frames are read with (vp8drv_set_source_colour)")
 ap.add_argument("--source-range", choices=("limited", "full"), default="limited")
+ap.add_argument("--source-transfer", choices=("pq", "hlg"), default="", help="with --source-format p010 or i010: the frames are tone-mapped to SDR on the device (vp8drv_set_source_transfer): what k_tonemap_b costs in k_convert_b's place")
+ap.add_argument("--source-peak", type=int, default=1000, metavar="N", help="... the peak luminance in nits, 400..10000")
 ap.add_argument("--window-pitch", type=int, default=0, metavar="P", help="the device-resident frames are surfaces whose luma rows are P bytes apart (the other planes' in proportion) and the frame is the window at (0, 0) (vp8drv_set_source_window): what k_window_b costs")
 ap.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=0, help="the device-resident frames are stored turned back by this many degrees and are turned clockwise on the device (vp8drv_set_source_orientation): what k_orient_b costs; the coded bytes do not change")
 ap.add_argument("--mirror", action="store_true", help="... behind a left-right flip")
@@ -103,6 +105,11 @@ if fmt:
     for d in drvs:
         d.set_source_format(fmt)
         d.set_source_colour(a.source_matrix, a.source_range)
+if a.source_transfer:      # (the frames carry an SDR picture's codes: the mapped picture means nothing, the kernel's work is the same)
+    if fmt not in (api.FORMAT_P010, api.FORMAT_I010):
+        sys.exit("--source-transfer goes with --source-format p010 or i010")
+    for d in drvs:
+        d.set_source_transfer(a.source_transfer, a.source_peak)
 if turns or a.mirror:
     for d in drvs:
         d.set_source_orientation(turns, int(a.mirror))
@@ -187,7 +194,7 @@ if a.streams == 1:   # the input side by HIP events: the pack launch, with k_con
     work(0, 32, False)
     ms, n = d.hip.profile_read().get("pack", (0.0, 0))
     d.hip.profile_enable([])
-    print(f"input side ({a.source_format or 'i420'}), {n} timed launches over 32 frames: {ms / 32 * 1e3:.2f} us per frame")
+    print(f"input side ({a.source_format or 'i420'}{' ' + a.source_transfer + ' ' + str(a.source_peak) if a.source_transfer else ''}), {n} timed launches over 32 frames: {ms / 32 * 1e3:.2f} us per frame")
 if a.aq and a.streams == 1:   # k_mb_p_map next to k_mb_p, and the input side without the map's launches: the same process, HIP events
     d = drvs[0]
 

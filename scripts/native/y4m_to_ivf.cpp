@@ -2,7 +2,7 @@
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
-//              [-input-format NAME] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
+//              [-input-format NAME] [-input-transfer pq|hlg[:PEAK]] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
 //              [-arf PERIOD[:FRAMES[:STRENGTH]]]
 // -arf PERIOD[:FRAMES[:STRENGTH]] (FRAMES 1..7, default 7; STRENGTH 0..6, default 3): hidden alternate reference frames
 // (vp8drv_set_arf, vp8drv_encode_arf_host; libvpx's --auto-alt-ref=1 --arnr-maxframes --arnr-strength).  In front of the first frame of
@@ -32,6 +32,10 @@
 // The format of the frames is the header's C tag (vp8host_y4m_colourspace): C420* files are I420, C422, C444, C420p10, C422p10 and
 // C444p10 files are converted on the device (vp8drv_set_source_format), any other colourspace is refused.  -input-format NAME (i420,
 // nv12, i422, i444, p010, i010, i210, i410) says it instead of the tag: for frames the header cannot describe (NV12, P010).
+// -input-transfer pq|hlg[:PEAK]: the ten-bit frames carry a PQ (HDR10) or HLG signal in BT.2020, graded for PEAK nits (400..10000,
+// default 1000), and are tone-mapped to SDR on the device (vp8drv_set_source_transfer; the rule: include/vp8hip_host.h).  A Y4M header
+// carries neither transfer nor primaries, so the option says it.  It goes with C420p10 files only (their frames read as i010, or as
+// p010 with -input-format); any other file is refused with its tag named.
 // -aq N: variance-adaptive quantisation of the inter frames at strength N = 1, 2, 3 (vp8drv_set_segment_mode, mode 2; 0 = off): flat
 // macroblocks take the finer segments of the quantiser ladder, busy ones the coarser.
 // -denoise N: temporal noise reduction of the source frames on the device, N = 1, 2, 3 (vp8drv_set_denoise; 0 = off); the share of
@@ -70,6 +74,7 @@ int main(int argc, char **argv) {
     int aq = 0;              // -aq
     int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     int32_t format = -1;     // -input-format (-1: the header's C tag)
+    int transfer = 0, peak = 1000;  // -input-transfer: PQ or HLG ten-bit frames are tone-mapped to SDR on the device
     int crop[4] = {0, 0, 0, 0};     // -crop: W, H, X, Y (W == 0: the whole surface)
     int turns = 0, mirror = 0;      // -rotate, -mirror
     const char *analysis_path = nullptr;      // -analysis
@@ -106,6 +111,14 @@ int main(int argc, char **argv) {
             for (int k = 0; k < VP8HOST_FORMAT_COUNT; ++k)
                 if (!strcasecmp(f, format_names[k])) format = k;
             if (format < 0) { fprintf(stderr, "-input-format %s: one of i420 nv12 i422 i444 p010 i010 i210 i410\n", f); return 2; }
+        }
+        else if (!strcmp(argv[i], "-input-transfer")) {
+            const char *f = val(), *colon = strchr(f, ':');
+            const size_t len = colon ? (size_t)(colon - f) : strlen(f);
+            if (len == 2 && !strncasecmp(f, "pq", 2)) transfer = VP8HOST_TRANSFER_PQ;
+            else if (len == 3 && !strncasecmp(f, "hlg", 3)) transfer = VP8HOST_TRANSFER_HLG;
+            if (colon) peak = atoi(colon + 1);
+            if (!transfer || peak < VP8HOST_PEAK_MIN || peak > VP8HOST_PEAK_MAX) { fprintf(stderr, "-input-transfer pq|hlg[:PEAK], PEAK 400..10000 nits\n"); return 2; }
         }
         else if (!strcmp(argv[i], "-crop")) {
             if (sscanf(val(), "%d:%d:%d:%d", &crop[0], &crop[1], &crop[2], &crop[3]) != 4 || crop[0] <= 0 || crop[1] <= 0) { fprintf(stderr, "-crop W:H:X:Y\n"); return 2; }
@@ -147,15 +160,28 @@ int main(int argc, char **argv) {
         fprintf(stderr, "%s: not a YUV4MPEG2 stream the reference accepts\n", argv[1]);
         return 1;
     }
-    if (format < 0 && vp8host_y4m_colourspace(head, got, &format) != 0) {      // name the tag: what follows the first " C" of the header line
-        const uint8_t *line_end = static_cast<const uint8_t *>(memchr(head, '\n', got));
-        const size_t len = line_end ? (size_t)(line_end - head) : got;
-        size_t a = 0;
-        while (a + 1 < len && !(head[a] == ' ' && head[a + 1] == 'C')) ++a;
-        size_t b = a + 1;
-        while (b < len && head[b] != ' ') ++b;
+    // the header's C tag by name: what follows the first " C" of the header line
+    const uint8_t *line_end = static_cast<const uint8_t *>(memchr(head, '\n', got));
+    const size_t line_len = line_end ? (size_t)(line_end - head) : got;
+    size_t tag_a = 0;
+    while (tag_a + 1 < line_len && !(head[tag_a] == ' ' && head[tag_a + 1] == 'C')) ++tag_a;
+    size_t tag_b = tag_a + 1;
+    while (tag_b < line_len && head[tag_b] != ' ') ++tag_b;
+    const bool has_tag = tag_a + 1 < line_len;
+    const int tag_len = has_tag ? (int)(tag_b - tag_a - 1) : 7;
+    const char *tag = has_tag ? reinterpret_cast<const char *>(head + tag_a + 1) : "(no C)";
+    if (transfer) {      // ten-bit 4:2:0 and nothing else carries a PQ or HLG signal this encoder maps
+        int32_t tagged = -1;
+        if (vp8host_y4m_colourspace(head, got, &tagged) != 0 || tagged != VP8HOST_FORMAT_I010 || !has_tag ||
+            (format >= 0 && format != VP8HOST_FORMAT_I010 && format != VP8HOST_FORMAT_P010)) {
+            fprintf(stderr, "%s: -input-transfer goes with C420p10 files only (frames as i010 or p010), not with colourspace tag %.*s%s%s\n", argv[1], tag_len, tag,
+                    format >= 0 ? " read as " : "", format >= 0 ? format_names[format] : "");
+            return 2;
+        }
+    }
+    if (format < 0 && vp8host_y4m_colourspace(head, got, &format) != 0) {
         fprintf(stderr, "%s: colourspace tag %.*s is not one this encoder takes (C420*, C422, C444, C420p10, C422p10, C444p10)\n", argv[1],
-                a + 1 < len ? (int)(b - a - 1) : 1, a + 1 < len ? reinterpret_cast<const char *>(head + a + 1) : "?");
+                has_tag ? tag_len : 1, has_tag ? tag : "?");
         return 1;
     }
     if (deint) {
@@ -196,6 +222,7 @@ int main(int argc, char **argv) {
     if (denoise) CK(vp8drv_set_denoise(drv, denoise));
     if (aq) CK(vp8drv_set_segment_mode(drv, 2, aq));
     if (format) CK(vp8drv_set_source_format(drv, format));
+    if (transfer) CK(vp8drv_set_source_transfer(drv, transfer, peak));
     if (turns || mirror) CK(vp8drv_set_source_orientation(drv, turns, mirror));
     if (crop[0]) CK(vp8drv_set_source_window(drv, pitch, crop[2], crop[3]));
     if (deint) CK(vp8drv_set_deinterlace(drv, deint, field));

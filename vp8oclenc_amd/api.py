@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "vp8hip_arf_filter_device", "vp8hip_arf_filter_host", "vp8hip_arf_result", "vp8hip_arf_release", "vp8hip_loop_filter_hidden",
     "vp8host_arf_filter_frame", "vp8host_arf_round_divide", "vp8drv_set_arf", "vp8drv_encode_arf_device", "vp8drv_encode_arf_host",
     "vp8drv_get_arf_stats",
+    "vp8hip_set_source_transfer", "vp8drv_set_source_transfer", "vp8host_tonemap_tables", "vp8host_tonemap_frame",
 ]
 
 
@@ -775,6 +776,54 @@ def convert_frame(fmt: int, width: int, height: int, planes, matrix: int = 0):
     return out
 
 
+# vp8host_transfer, include/vp8hip_host.h: the transfer function P010 / I010 frames carry (vp8hip_set_source_transfer)
+TRANSFER_SDR, TRANSFER_PQ, TRANSFER_HLG = range(3)
+TRANSFER_NAMES = ["sdr", "pq", "hlg"]
+PEAK_MIN, PEAK_MAX, PEAK_DEFAULT = 400, 10000, 1000      # VP8HOST_PEAK_MIN, VP8HOST_PEAK_MAX; the tools' default
+
+
+def source_transfer(name) -> int:
+    """a transfer's number from its name (sdr, pq, hlg; any case) or number; ValueError for what vp8hip_set_source_transfer would refuse"""
+    if isinstance(name, str) and name.lower() in TRANSFER_NAMES:
+        return TRANSFER_NAMES.index(name.lower())
+    if isinstance(name, (int, np.integer)) and not isinstance(name, bool) and 0 <= int(name) < len(TRANSFER_NAMES):
+        return int(name)
+    raise ValueError(f"unknown source transfer {name!r}: one of {', '.join(TRANSFER_NAMES)}")
+
+
+def tonemap_tables(transfer, peak: int = PEAK_DEFAULT):
+    """vp8host_tonemap_tables: the four tables of the tone-mapping rule for (transfer, peak) -> (lin, gain) uint32 and (lo, hi) uint8
+    arrays of 4096 entries each"""
+    lib = load_library()
+    lib.vp8host_tonemap_tables.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4
+    t = source_transfer(transfer) if isinstance(transfer, str) else int(transfer)
+    out = (np.empty(4096, np.uint32), np.empty(4096, np.uint32), np.empty(4096, np.uint8), np.empty(4096, np.uint8))
+    if lib.vp8host_tonemap_tables(t, int(peak), *[o.ctypes.data for o in out]) != 0:
+        raise ValueError(f"vp8host_tonemap_tables(transfer {transfer}, peak {peak}) refused")
+    return out
+
+
+def tonemap_frame(fmt, transfer, peak: int, width: int, height: int, planes, matrix: int = 0):
+    """vp8host_tonemap_frame: the device's tone mapping in plain C++.  planes = the two (P010) or three (I010) planes as contiguous
+    arrays of exactly vp8host_source_plane_bytes bytes each; matrix = the colour matrix the SDR picture is written with -> (Y, U, V)
+    uint8 arrays, I420 of width x height"""
+    lib = load_library()
+    lib.vp8host_tonemap_frame.argtypes = [C.c_int] * 6 + [C.c_void_p] * 6
+    fmt = source_format(fmt) if isinstance(fmt, str) else int(fmt)
+    t = source_transfer(transfer) if isinstance(transfer, str) else int(transfer)
+    need = source_plane_bytes(fmt, width, height)
+    planes = [np.ascontiguousarray(p) for p in planes]
+    while len(planes) < 3:
+        planes.append(planes[-1])
+    for p, n in zip(planes, need):
+        if n and p.nbytes != n:
+            raise ValueError(f"tonemap_frame: a plane of {p.nbytes} bytes where format {fmt} at {width}x{height} has {n}")
+    out = (np.empty((height, width), np.uint8), np.empty((height // 2, width // 2), np.uint8), np.empty((height // 2, width // 2), np.uint8))
+    if lib.vp8host_tonemap_frame(fmt, t, int(peak), int(matrix), int(width), int(height), *[p.ctypes.data for p in planes], *[o.ctypes.data for o in out]) != 0:
+        raise ValueError(f"vp8host_tonemap_frame(format {fmt}, transfer {transfer}, peak {peak}, matrix {matrix}, {width}x{height}) refused")
+    return out
+
+
 def _pitch3(pitch):
     p = [int(x) for x in pitch] + [0, 0, 0]
     return (C.c_int32 * 3)(*p[:3])
@@ -1024,6 +1073,15 @@ class NativeDriver:
         rc = self.lib.vp8drv_set_source_colour(self.h, m)
         if rc < 0:
             raise Vp8HipError(f"vp8drv_set_source_colour({m}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_source_transfer(self, transfer, peak: int = PEAK_DEFAULT) -> None:
+        """vp8drv_set_source_transfer: P010 / I010 frames carry this transfer (a TRANSFER_* number, or sdr / pq / hlg) graded for `peak`
+        nits and are tone-mapped to SDR on the device; sdr (0) = off"""
+        self.lib.vp8drv_set_source_transfer.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        t = source_transfer(transfer) if isinstance(transfer, str) else int(transfer)
+        rc = self.lib.vp8drv_set_source_transfer(self.h, t, int(peak))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_source_transfer({t}, {peak}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_source_format(self, fmt) -> None:
         """vp8drv_set_source_format: the frames handed in from now on are this format's planes (a FORMAT_* number or its name)"""
@@ -1561,6 +1619,15 @@ class Vp8Hip:
         rc = self.lib.vp8hip_set_source_format(self.h, fmt)
         if rc != 0:
             raise Vp8HipError(f"set_source_format({fmt}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_source_transfer(self, transfer, peak: int = PEAK_DEFAULT):
+        """vp8hip_set_source_transfer: P010 / I010 current frames carry this transfer (a TRANSFER_* number, or sdr / pq / hlg) graded
+        for `peak` nits, and k_tonemap_b makes SDR I420 of them where k_convert_b would stand; sdr (0) = off"""
+        self.lib.vp8hip_set_source_transfer.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        t = source_transfer(transfer) if isinstance(transfer, str) else int(transfer)
+        rc = self.lib.vp8hip_set_source_transfer(self.h, t, int(peak))
+        if rc != 0:
+            raise Vp8HipError(f"set_source_transfer({t}, {peak}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_denoise(self, level: int):
         """vp8hip_set_denoise: every frame that becomes current passes through the temporal denoiser (level 1-3; 0 = off); turning it

@@ -445,6 +445,7 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     if (c->ev_chroma) hipEventDestroy(c->ev_chroma);
     hipFree(c->scale.d_blob);
     c->fmt_stage.release();
+    c->tm_tables.release();
     c->raw_stage.release();
     c->di_stage.release();
     c->win_stage.release();

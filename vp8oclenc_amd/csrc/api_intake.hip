@@ -138,7 +138,9 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
     }
     if (c0->src_fmt) {      // one launch for all members, in front of the pack or scale launch
         Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
-        if (!launch_convert_batch(s, c0->src_fmt, c0->src_colour, w, h, cv, n)) return VP8HIP_ERR_ARG;
+        if (c0->src_transfer) {     // (same_intake: one transfer and peak, so the first member's tables are every member's)
+            if (!launch_tonemap_batch(s, c0->src_fmt, c0->src_colour, w, h, reinterpret_cast<const uint32_t *>(c0->tm_tables.p), cv, n)) return VP8HIP_ERR_ARG;
+        } else if (!launch_convert_batch(s, c0->src_fmt, c0->src_colour, w, h, cv, n)) return VP8HIP_ERR_ARG;
     }
     if (c0->di_mode) {      // ... behind the converter and in front of the pack or scale launch
         Timed t(c0, VP8HIP_K_PACK);
@@ -332,10 +334,38 @@ int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int ds
     return VP8HIP_OK;
 }
 
+// the combinations of a transfer and a format the tone-mapping rule covers: it reads P010 and I010, and I420 frames pass it by
+static bool transfer_allows(int transfer, int format) {
+    return !transfer || format == VP8HOST_FORMAT_I420 || format == VP8HOST_FORMAT_P010 || format == VP8HOST_FORMAT_I010;
+}
+
+int vp8hip_set_source_transfer(vp8hip_ctx *c, int transfer, int peak) {
+    if (!c || (transfer != VP8HOST_TRANSFER_SDR && transfer != VP8HOST_TRANSFER_PQ && transfer != VP8HOST_TRANSFER_HLG)) return VP8HIP_ERR_ARG;
+    if (transfer == VP8HOST_TRANSFER_SDR) peak = 0;      // (off has no peak)
+    else if (peak < VP8HOST_PEAK_MIN || peak > VP8HOST_PEAK_MAX || !transfer_allows(transfer, c->src_fmt)) return VP8HIP_ERR_ARG;
+    if (transfer == c->src_transfer && peak == c->src_peak) return VP8HIP_OK;
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    if (transfer) {      // everything that can fail before anything of the context changes
+        std::vector<uint8_t> t(TONEMAP_TABLE_BYTES);
+        uint32_t *lin = reinterpret_cast<uint32_t *>(t.data());
+        if (vp8host_tonemap_tables(transfer, peak, lin, lin + 4096, t.data() + 32768, t.data() + 36864) != 0) return VP8HIP_ERR_ARG;
+        { const int rc = c->tm_tables.grow(c, t.size()); if (rc) return rc; }
+        HIPCHK(c, hipMemcpy(c->tm_tables.p, t.data(), t.size(), hipMemcpyHostToDevice));
+    } else {
+        c->tm_tables.release();
+    }
+    c->src_transfer = transfer;
+    c->src_peak = peak;
+    c->h2d_pre_valid = false;      // planes prefetched under another transfer are not this transfer's frame
+    if (c->batch) c->batch->pre_valid = false;
+    return VP8HIP_OK;
+}
+
 int vp8hip_set_source_format(vp8hip_ctx *c, int format) {
     if (!c || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END)
         return VP8HIP_ERR_ARG;
     if (format == c->src_fmt) return VP8HIP_OK;
+    if (!transfer_allows(c->src_transfer, format)) return VP8HIP_ERR_ARG;      // (a transfer in force: P010, I010, or back to I420)
     { int w, h; upright_size(c, &w, &h); if (!geometry_allows(c, format, w, h, c->or_turns)) return VP8HIP_ERR_ARG; }      // (a window in force: its pitches under the new format)
     { const int rc = quiesce_intake(c); if (rc) return rc; }
     const int before = c->src_fmt;

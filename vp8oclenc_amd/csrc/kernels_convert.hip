@@ -230,6 +230,36 @@ __device__ __forceinline__ uint4 rgb_luma16(const uint32_t p[16], const PackedAr
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+// the RGB pixels of one 2x2 block (a, b: the upper row's; c, d: the lower row's) -> four luma bytes, one U, one V: the walk's step
+__device__ __forceinline__ void rgb_store_block(uint32_t a, uint32_t b, uint32_t c, uint32_t d, const PackedArgs &g, uint8_t *y0, uint8_t *y1,
+                                                uint8_t *ou, uint8_t *ov) {
+    const uint32_t off = g.off4 & 255u;
+    y0[0] = (uint8_t)((luma1(a, g) >> 8) + off);
+    y0[1] = (uint8_t)((luma1(b, g) >> 8) + off);
+    y1[0] = (uint8_t)((luma1(c, g) >> 8) + off);
+    y1[1] = (uint8_t)((luma1(d, g) >> 8) + off);
+    *ou = (uint8_t)(chroma1(d, g.cu, chroma1(c, g.cu, chroma1(b, g.cu, chroma1(a, g.cu, (int)g.bias_u)))) >> 10);
+    *ov = (uint8_t)(chroma1(d, g.cv, chroma1(c, g.cv, chroma1(b, g.cv, chroma1(a, g.cv, (int)g.bias_v)))) >> 10);
+}
+
+// sixteen RGB pixels of each of two rows (a: the upper, b: the lower) -> 2 x 16 luma bytes and 8 + 8 chroma bytes, stored
+__device__ __forceinline__ void rgb_store16(const uint32_t a[16], const uint32_t b[16], const PackedArgs &g, uint8_t *y0, uint8_t *y1, uint8_t *ou,
+                                            uint8_t *ov) {
+    store16(y0, rgb_luma16(a, g));
+    store16(y1, rgb_luma16(b, g));
+    uint32_t u[2] = {}, v[2] = {};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int su = chroma1(b[2 * i + 1], g.cu, chroma1(b[2 * i], g.cu, chroma1(a[2 * i + 1], g.cu, chroma1(a[2 * i], g.cu, (int)g.bias_u))));
+        const int sv = chroma1(b[2 * i + 1], g.cv, chroma1(b[2 * i], g.cv, chroma1(a[2 * i + 1], g.cv, chroma1(a[2 * i], g.cv, (int)g.bias_v))));
+        // (S + bias never negative and below 2^18: bits 10..17 are the byte)
+        u[i >> 2] |= (((uint32_t)su >> 10) & 255u) << (8 * (i & 3));
+        v[i >> 2] |= (((uint32_t)sv >> 10) & 255u) << (8 * (i & 3));
+    }
+    store8(ou, u[0], u[1]);
+    store8(ov, v[0], v[1]);
+}
+
 template <bool RGB> __device__ __forceinline__ void packed_body(const ConvertItem &it, const PackedArgs &g) {
     constexpr int B = RGB ? 4 : 2;            // bytes per pixel
     const int unit = (int)blockIdx.x * 256 + (int)threadIdx.x;
@@ -242,14 +272,7 @@ template <bool RGB> __device__ __forceinline__ void packed_body(const ConvertIte
     if (g.w < 16) {
         for (int x = 0; x < cw; ++x) {
             if constexpr (RGB) {
-                const uint32_t a = load4(s0 + 8 * x), b = load4(s0 + 8 * x + 4), c = load4(s1 + 8 * x), d = load4(s1 + 8 * x + 4);
-                const uint32_t off = g.off4 & 255u;
-                y0[2 * x] = (uint8_t)((luma1(a, g) >> 8) + off);
-                y0[2 * x + 1] = (uint8_t)((luma1(b, g) >> 8) + off);
-                y1[2 * x] = (uint8_t)((luma1(c, g) >> 8) + off);
-                y1[2 * x + 1] = (uint8_t)((luma1(d, g) >> 8) + off);
-                ou[x] = (uint8_t)(chroma1(d, g.cu, chroma1(c, g.cu, chroma1(b, g.cu, chroma1(a, g.cu, (int)g.bias_u)))) >> 10);
-                ov[x] = (uint8_t)(chroma1(d, g.cv, chroma1(c, g.cv, chroma1(b, g.cv, chroma1(a, g.cv, (int)g.bias_v)))) >> 10);
+                rgb_store_block(load4(s0 + 8 * x), load4(s0 + 8 * x + 4), load4(s1 + 8 * x), load4(s1 + 8 * x + 4), g, y0 + 2 * x, y1 + 2 * x, ou + x, ov + x);
             } else {
                 const uint32_t a = load4(s0 + 4 * x), b = load4(s1 + 4 * x);
                 y0[2 * x] = (uint8_t)(a >> g.shift_y);
@@ -273,19 +296,7 @@ template <bool RGB> __device__ __forceinline__ void packed_body(const ConvertIte
             a[4 * i] = t.x; a[4 * i + 1] = t.y; a[4 * i + 2] = t.z; a[4 * i + 3] = t.w;
             b[4 * i] = q.x; b[4 * i + 1] = q.y; b[4 * i + 2] = q.z; b[4 * i + 3] = q.w;
         }
-        store16(y0 + x0, rgb_luma16(a, g));
-        store16(y1 + x0, rgb_luma16(b, g));
-        uint32_t u[2] = {}, v[2] = {};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int su = chroma1(b[2 * i + 1], g.cu, chroma1(b[2 * i], g.cu, chroma1(a[2 * i + 1], g.cu, chroma1(a[2 * i], g.cu, (int)g.bias_u))));
-            const int sv = chroma1(b[2 * i + 1], g.cv, chroma1(b[2 * i], g.cv, chroma1(a[2 * i + 1], g.cv, chroma1(a[2 * i], g.cv, (int)g.bias_v))));
-            // (S + bias never negative and below 2^18: bits 10..17 are the byte)
-            u[i >> 2] |= (((uint32_t)su >> 10) & 255u) << (8 * (i & 3));
-            v[i >> 2] |= (((uint32_t)sv >> 10) & 255u) << (8 * (i & 3));
-        }
-        store8(ou + (x0 >> 1), u[0], u[1]);
-        store8(ov + (x0 >> 1), v[0], v[1]);
+        rgb_store16(a, b, g, y0 + x0, y1 + x0, ou + (x0 >> 1), ov + (x0 >> 1));
     } else {
         const uint4 t0 = load16(s0), t1 = load16(s0 + 16), q0 = load16(s1), q1 = load16(s1 + 16);
         const uint32_t a[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w}, b[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
@@ -305,7 +316,149 @@ template <bool RGB> __device__ __forceinline__ void packed_body(const ConvertIte
     }
 }
 
+// ---- HDR sources made SDR: P010 / I010 with a transfer in force (vp8hip_set_source_transfer; the rule is include/vp8hip_host.h's) -------
+// k_tonemap_b stands where k_convert_b stands and writes the same tight I420.  The first kernel of the input side that is not data
+// movement: about 70 vector instructions and 7 table lookups per pixel.
+// Mapping:
+//   * a lane owns 16 pixels of TWO adjacent rows, as packed_body does: it loads its 2 x 16 Y' words (2 x 2 loads of 16 bytes) and its 8
+//     (Cb, Cr) pairs (P010: 2 loads of interleaved words, the value in the top ten bits; I010: one load per plane, the low ten bits)
+//     once, forms the three chroma terms of R'G'B' once per 2x2 block, and stores 2 x 16 luma bytes and 8 + 8 chroma bytes;
+//   * the four tables (TM_TABLE_BYTES, 40 KiB: lin and gain as dwords, lo and hi as bytes behind them, in the layout the setter uploads)
+//     are copied into LDS at kernel start, 10 loads of 16 bytes per lane, and looked up there: a lookup's index is a pixel value, so
+//     neighbouring lanes mostly hit neighbouring dwords (other banks) or the same one (a broadcast).  Dword entries for lin and gain:
+//     16-bit entries could not hold 20 and 23 bits; lo and hi are one byte table of 8192 (the index picks the half), read with
+//     ds_read_u8;
+//   * a workgroup of 256 lanes makes 8192 pixels, about 2300 vector instructions per lane against the 20 of the copy; it reads 24 KiB of
+//     frame and writes 12 KiB beside the 40 KiB of tables, which come from L2.  Four workgroups' tables fit a CU's 160 KiB, and 124
+//     VGPRs allow the same four waves per SIMD.  No larger workgroup share: a 1920x1080 frame is 254 workgroups, one per CU;
+//   * t * g is one 64-bit multiply-add (v_mad_u64_u32); the closing RGB -> YUV step is rgb_store16 on the (B, G, R, 0) dwords built in
+//     registers: the byte dot products of the BGRA kernel, so the matrix is the same few argument dwords;
+//   * edges as above: a row's last unit moves left, rows narrower than 16 pixels are walked 2x2 block by 2x2 block.
+constexpr int TM_TABLE_BYTES = TONEMAP_TABLE_BYTES, TM_GAIN_AT = 4096, TM_C8_AT = 8192;      // dwords from the start: lin at 0, gain, then lo | hi as bytes
+
+struct TmChroma { int r, g, b; };      // what (Cb, Cr) adds to 38295 y + 4096 for R', G' and B'
+__device__ __forceinline__ TmChroma tm_chroma(int cb, int cr) {
+    cb -= 512;
+    cr -= 512;
+    return TmChroma{55209 * cr, -6161 * cb - 21391 * cr, 70440 * cb};
+}
+__device__ __forceinline__ int tm_clamp12(int a) { return min(max(a, 0), 4095); }
+__device__ __forceinline__ uint32_t tm_out8(int sum, uint32_t gain, const uint8_t *c8) {      // one component: a row of the primaries -> c8
+    const uint32_t t = (uint32_t)max(sum >> 10, 0);
+    const uint32_t o = min((uint32_t)(((uint64_t)t * gain + 524288u) >> 20), 65535u);      // (the product is below 2^44: 24 bits are left)
+    return c8[o < 4096u ? o : 4096u + (o >> 4)];
+}
+// one pixel -> the dword of a BGRA pixel (alpha 0).  tab: the tables in LDS
+__device__ __forceinline__ uint32_t tm_pixel(int y10, const TmChroma &c, const uint32_t *tab) {
+    const uint8_t *c8 = reinterpret_cast<const uint8_t *>(tab + TM_C8_AT);
+    const int yy = 38295 * (y10 - 64) + 4096;
+    const int R1 = tm_clamp12((yy + c.r) >> 13), G1 = tm_clamp12((yy + c.g) >> 13), B1 = tm_clamp12((yy + c.b) >> 13);
+    const uint32_t gain = tab[TM_GAIN_AT + max(R1, max(G1, B1))];
+    // (lin is below 2^20: the mask changes no value and lets the nine products be full-rate 24-bit multiplies)
+    const int aR = (int)(tab[R1] & 0xfffffu), aG = (int)(tab[G1] & 0xfffffu), aB = (int)(tab[B1] & 0xfffffu);
+    const uint32_t R = tm_out8(1701 * aR - 602 * aG - 75 * aB + 512, gain, c8), G = tm_out8(-128 * aR + 1161 * aG - 9 * aB + 512, gain, c8),
+                   B = tm_out8(-19 * aR - 103 * aG + 1146 * aB + 512, gain, c8);
+    return B | (G << 8) | (R << 16);
+}
+
+template <bool TOP> __device__ __forceinline__ void tonemap_body(const ConvertItem &it, const PackedArgs &g, const uint32_t *tab) {
+    const int unit = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (unit >= g.units) return;
+    const int r = unit / g.units_x, ux = unit - r * g.units_x, cw = g.w >> 1;
+    const size_t pitch = (size_t)g.w * 2;       // bytes of a luma row, and of P010's chroma row
+    const uint8_t *s0 = it.src[0] + (size_t)(2 * r) * pitch, *s1 = s0 + pitch;
+    const uint8_t *sc = it.src[1] + (size_t)r * (TOP ? pitch : (size_t)cw * 2);
+    const uint8_t *sv = TOP ? sc : it.src[2] + (size_t)r * cw * 2;
+    uint8_t *y0 = it.dst[0] + (size_t)(2 * r) * g.w, *y1 = y0 + g.w;
+    uint8_t *ou = it.dst[1] + (size_t)r * cw, *ov = it.dst[2] + (size_t)r * cw;
+    if (g.w < 16) {
+        for (int x = 0; x < cw; ++x) {
+            const TmChroma c = TOP ? tm_chroma(sample<10, true>(sc, 2 * x), sample<10, true>(sc, 2 * x + 1))
+                                   : tm_chroma(sample<10, false>(sc, x), sample<10, false>(sv, x));
+            rgb_store_block(tm_pixel(sample<10, TOP>(s0, 2 * x), c, tab), tm_pixel(sample<10, TOP>(s0, 2 * x + 1), c, tab),
+                            tm_pixel(sample<10, TOP>(s1, 2 * x), c, tab), tm_pixel(sample<10, TOP>(s1, 2 * x + 1), c, tab), g, y0 + 2 * x, y1 + 2 * x,
+                            ou + x, ov + x);
+        }
+        return;
+    }
+    const int x0 = min(ux * 16, g.w - 16);      // even: the widths are
+    const uint4 t0 = load16(s0 + 2 * x0), t1 = load16(s0 + 2 * x0 + 16), q0 = load16(s1 + 2 * x0), q1 = load16(s1 + 2 * x0 + 16);
+    const uint32_t ya[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w}, yb[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    uint32_t cc[8];      // the block's pair: Cb in the low half, Cr in the high half
+    if constexpr (TOP) {
+        const uint4 c0 = load16(sc + 2 * x0), c1 = load16(sc + 2 * x0 + 16);
+        const uint32_t d[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) cc[i] = ten<true>(d[i]);
+    } else {
+        const uint4 c0 = load16(sc + x0), c1 = load16(sv + x0);      // eight words of each plane, at sample x0 / 2
+        const uint32_t du[4] = {c0.x, c0.y, c0.z, c0.w}, dv[4] = {c1.x, c1.y, c1.z, c1.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t u2 = ten<false>(du[i]), v2 = ten<false>(dv[i]);
+            cc[2 * i] = __builtin_amdgcn_perm(v2, u2, 0x05040100u);
+            cc[2 * i + 1] = __builtin_amdgcn_perm(v2, u2, 0x07060302u);
+        }
+    }
+    uint32_t a[16], b[16];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const TmChroma c = tm_chroma((int)(cc[i] & 0xffffu), (int)(cc[i] >> 16));
+        const uint32_t p = ten<TOP>(ya[i]), q = ten<TOP>(yb[i]);
+        a[2 * i] = tm_pixel((int)(p & 0xffffu), c, tab);
+        a[2 * i + 1] = tm_pixel((int)(p >> 16), c, tab);
+        b[2 * i] = tm_pixel((int)(q & 0xffffu), c, tab);
+        b[2 * i + 1] = tm_pixel((int)(q >> 16), c, tab);
+    }
+    rgb_store16(a, b, g, y0 + x0, y1 + x0, ou + (x0 >> 1), ov + (x0 >> 1));
+}
+
 }  // namespace convert
+
+static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::PackedArgs) + sizeof(void *) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+// tables: convert::TM_TABLE_BYTES of the context's device buffer (lin, gain, lo, hi end to end), 16-byte aligned
+template <bool TOP> __global__ __launch_bounds__(256) void k_tonemap_b(BatchOf<ConvertItem> b, convert::PackedArgs g, const uint32_t *tables) {
+    __shared__ convert::u32x4 tab[convert::TM_TABLE_BYTES / 16];
+    for (int i = (int)threadIdx.x; i < convert::TM_TABLE_BYTES / 16; i += 256) tab[i] = reinterpret_cast<const convert::u32x4 *>(tables)[i];
+    __syncthreads();      // (in front of every return: all 256 lanes arrive)
+    convert::tonemap_body<TOP>(b.item[blockIdx.z], g, reinterpret_cast<const uint32_t *>(tab));
+}
+
+// the matrix of an RGB pixel's dword as the byte rows and accumulator starts of luma1 / chroma1 (format: BGRA or RGBA, where R and B sit)
+static bool rgb_matrix_args(int format, int matrix, convert::PackedArgs &g) {
+    int32_t c[9], off;
+    if (vp8host_colour_coefficients(matrix, c, &off) != 0) return false;      // (vp8hip_set_source_colour refuses it: the caller fails the frame)
+    const int at[3] = {format == VP8HOST_FORMAT_BGRA ? 16 : 0, 8, format == VP8HOST_FORMAT_BGRA ? 0 : 16};      // R, G, B in a pixel's dword
+    int sum_u = 0, sum_v = 0;
+    for (int k = 0; k < 3; ++k) {
+        g.cy |= (uint32_t)(uint8_t)c[k] << at[k];
+        g.cu |= (uint32_t)(uint8_t)(int8_t)c[3 + k] << at[k];
+        g.cv |= (uint32_t)(uint8_t)(int8_t)c[6 + k] << at[k];
+        sum_u += c[3 + k];
+        sum_v += c[6 + k];
+    }
+    g.off4 = (uint32_t)off * 0x01010101u;
+    g.bias_u = (uint32_t)(131072 + 512 + 4 * 128 * sum_u);      // the dot product sees p - 128, four pixels of it
+    g.bias_v = (uint32_t)(131072 + 512 + 4 * 128 * sum_v);
+    return true;
+}
+
+bool launch_tonemap_batch(hipStream_t s, int format, int matrix, int w, int h, const uint32_t *tables, const ConvertItem *items, int n) {
+    if (n <= 0) return true;
+    if ((format != VP8HOST_FORMAT_P010 && format != VP8HOST_FORMAT_I010) || !tables) return false;      // (the setters refuse it: the caller fails the frame)
+    BatchOf<ConvertItem> b;
+    b.n = n;
+    for (int i = 0; i < n; ++i) b.item[i] = items[i];
+    convert::PackedArgs g = {};
+    g.w = w; g.h = h;
+    g.units_x = w < 16 ? 1 : (w + 15) / 16;
+    g.units = g.units_x * (h / 2);
+    if (!rgb_matrix_args(VP8HOST_FORMAT_BGRA, matrix, g)) return false;      // (the pixel's dword is built as BGRA's)
+    const dim3 grid((g.units + 255) / 256, 1, n), block(256);
+    if (format == VP8HOST_FORMAT_P010) VP8_LAUNCH((k_tonemap_b<true>), grid, block, 0, s, b, g, tables);
+    else VP8_LAUNCH((k_tonemap_b<false>), grid, block, 0, s, b, g, tables);
+    return true;
+}
 
 static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::PackedArgs) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
 template <bool RGB> __global__ __launch_bounds__(256) void k_convert_packed_b(BatchOf<ConvertItem> b, convert::PackedArgs g) {
@@ -319,20 +472,7 @@ static bool launch_convert_packed(hipStream_t s, int format, int matrix, int w, 
     g.units = g.units_x * (h / 2);
     const bool rgb = format == VP8HOST_FORMAT_BGRA || format == VP8HOST_FORMAT_RGBA;
     if (rgb) {
-        int32_t c[9], off;
-        if (vp8host_colour_coefficients(matrix, c, &off) != 0) return false;      // (vp8hip_set_source_colour refuses it: the caller fails the frame)
-        const int at[3] = {format == VP8HOST_FORMAT_BGRA ? 16 : 0, 8, format == VP8HOST_FORMAT_BGRA ? 0 : 16};      // R, G, B in a pixel's dword
-        int sum_u = 0, sum_v = 0;
-        for (int k = 0; k < 3; ++k) {
-            g.cy |= (uint32_t)(uint8_t)c[k] << at[k];
-            g.cu |= (uint32_t)(uint8_t)(int8_t)c[3 + k] << at[k];
-            g.cv |= (uint32_t)(uint8_t)(int8_t)c[6 + k] << at[k];
-            sum_u += c[3 + k];
-            sum_v += c[6 + k];
-        }
-        g.off4 = (uint32_t)off * 0x01010101u;
-        g.bias_u = (uint32_t)(131072 + 512 + 4 * 128 * sum_u);      // the dot product sees p - 128, four pixels of it
-        g.bias_v = (uint32_t)(131072 + 512 + 4 * 128 * sum_v);
+        if (!rgb_matrix_args(format, matrix, g)) return false;
     } else {
         const bool yuy2 = format == VP8HOST_FORMAT_YUY2;
         g.sel_y = yuy2 ? 0x06040200u : 0x07050301u;

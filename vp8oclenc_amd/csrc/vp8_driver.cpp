@@ -32,7 +32,8 @@ struct vp8drv {
     int denoise = 0;                 // vp8drv_set_denoise: the level in force
     int deinterlace = 0, field = 0;  // vp8drv_set_deinterlace: the mode and the field kept
     int format = 0;                  // vp8drv_set_source_format: the format in force
-    int colour = 0;                  // vp8drv_set_source_colour: the colour matrix in force (read by BGRA / RGBA only)
+    int colour = 0;                  // vp8drv_set_source_colour: the colour matrix in force (read by BGRA / RGBA and a tone-mapped source only)
+    int transfer = 0, peak = 0;      // vp8drv_set_source_transfer: the transfer and peak in force (0, 0: off)
     bool analysis = false;           // vp8drv_set_analysis
     bool in_batch = false;           // a member of a live vp8drv_batch
     bool window = false;             // vp8drv_set_source_window: a window is in force
@@ -481,7 +482,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
             (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format || drv[i]->colour != drv[0]->colour ||
-            drv[i]->analysis != drv[0]->analysis || drv[i]->deinterlace != drv[0]->deinterlace || drv[i]->field != drv[0]->field)
+            drv[i]->transfer != drv[0]->transfer || drv[i]->peak != drv[0]->peak || drv[i]->analysis != drv[0]->analysis || drv[i]->deinterlace != drv[0]->deinterlace || drv[i]->field != drv[0]->field)
             return VP8HIP_ERR_ARG;
         {   // vp8drv_set_segment_mode: one mode and strength (the maps are the members' own)
             int m0 = 0, s0 = 0, mi = 0, si = 0;
@@ -733,6 +734,18 @@ int vp8drv_set_source_colour(vp8drv *d, int matrix) {
     DRV_CHK(vp8hip_set_source_colour(d->hip, matrix));
     d->colour = matrix;
     d->staged = nullptr;             // planes staged under the other matrix are not this matrix's frame
+    d->staged_scan = false;
+    return VP8HIP_OK;
+}
+
+int vp8drv_set_source_transfer(vp8drv *d, int transfer, int peak) {
+    if (!d || transfer < VP8HOST_TRANSFER_SDR || transfer > VP8HOST_TRANSFER_HLG || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (d->in_batch) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_source_transfer(d->hip, transfer, peak));
+    d->transfer = transfer;
+    d->peak = transfer ? peak : 0;
+    d->staged = nullptr;             // planes staged under the other transfer are not this transfer's frame
     d->staged_scan = false;
     return VP8HIP_OK;
 }

@@ -5,6 +5,10 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
 namespace {
 
 // src/vp8enc.h:17-39 (same tables as the kernels use)
@@ -334,6 +338,89 @@ int vp8host_convert_frame(int format, int width, int height, const uint8_t *p0, 
                 }
             u[(size_t)r * cw + x] = round_off(su, kc);
             v[(size_t)r * cw + x] = round_off(sv, kc);
+        }
+    return 0;
+}
+
+// ---- HDR sources made SDR: the tables and the rule of include/vp8hip_host.h ------------------------------------------------------------
+int vp8host_tonemap_tables(int transfer, int peak, uint32_t lin[4096], uint32_t gain[4096], uint8_t lo[4096], uint8_t hi[4096]) {
+    if ((transfer != VP8HOST_TRANSFER_PQ && transfer != VP8HOST_TRANSFER_HLG) || peak < VP8HOST_PEAK_MIN || peak > VP8HOST_PEAK_MAX ||
+        !lin || !gain || !lo || !hi)
+        return -1;
+    const double P = peak, w = P / 203.0;
+    const double m1 = 2610.0 / 16384.0, m2 = 128.0 * 2523.0 / 4096.0, c1 = 3424.0 / 4096.0, c2 = 32.0 * 2413.0 / 4096.0, c3 = 32.0 * 2392.0 / 4096.0;
+    const double ha = 0.17883277, hb = 0.28466892, hc = 0.55991073, gamma = 1.2 + 0.42 * std::log10(P / 1000.0);
+    int first = -1;
+    for (int i = 0; i < 4096; ++i) {
+        const double e = i / 4095.0;
+        double s, D;
+        if (transfer == VP8HOST_TRANSFER_PQ) {
+            const double p = std::pow(e, 1.0 / m2);
+            const double N = 10000.0 * std::pow(std::max(p - c1, 0.0) / (c2 - c3 * p), 1.0 / m1);
+            D = std::min(N, P);
+            s = D / P;
+        } else {
+            s = e <= 0.5 ? e * e / 3.0 : (std::exp((e - hc) / ha) + hb) / 12.0;
+            D = P * std::pow(s, gamma);
+        }
+        const double x = D / 203.0, T = x * (1.0 + x / (w * w)) / (1.0 + x);
+        lin[i] = (uint32_t)std::min(1048575.0, std::rint(1048576.0 * s));
+        gain[i] = 0;
+        if (lin[i] > 0) {
+            gain[i] = (uint32_t)std::rint(65535.0 * 1048576.0 * T / (double)lin[i]);
+            if (first < 0) first = i;
+        }
+    }
+    for (int i = 0; i < first; ++i) gain[i] = gain[first];      // (black: lin is 0 there, the product too)
+    for (int j = 0; j < 4096; ++j) {
+        lo[j] = (uint8_t)std::rint(255.0 * std::pow(j / 65535.0, 1.0 / 2.4));
+        hi[j] = (uint8_t)std::rint(255.0 * std::pow(std::min(16 * j + 8, 65535) / 65535.0, 1.0 / 2.4));
+    }
+    return 0;
+}
+
+int vp8host_tonemap_frame(int format, int transfer, int peak, int matrix, int width, int height, const uint8_t *p0, const uint8_t *p1,
+                          const uint8_t *p2, uint8_t *y, uint8_t *u, uint8_t *v) {
+    const bool nv = format == VP8HOST_FORMAT_P010;
+    size_t bytes[3];
+    if ((!nv && format != VP8HOST_FORMAT_I010) || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT ||
+        vp8host_source_plane_bytes(format, width, height, bytes) != 0 || !p0 || !p1 || (!nv && !p2) || !y || !u || !v)
+        return -1;
+    std::vector<uint32_t> lin(4096), gain(4096);
+    std::vector<uint8_t> lo(4096), hi(4096);
+    if (vp8host_tonemap_tables(transfer, peak, lin.data(), gain.data(), lo.data(), hi.data()) != 0) return -1;
+    auto sample = [&](const uint8_t *p, size_t i) -> int32_t {
+        const int word = p[2 * i] | (p[2 * i + 1] << 8);
+        return nv ? word >> 6 : word & 1023;
+    };
+    auto clamp12 = [](int32_t a) -> int32_t { return a < 0 ? 0 : (a > 4095 ? 4095 : a); };
+    auto out8 = [&](int32_t sum, uint32_t g) -> int32_t {      // one component: primaries' row sum -> tone curve -> SDR transfer
+        const int64_t t = sum >> 10 < 0 ? 0 : sum >> 10;
+        const int64_t o = std::min<int64_t>(65535, (t * (int64_t)g + 524288) >> 20);
+        return o < 4096 ? lo[(size_t)o] : hi[(size_t)(o >> 4)];
+    };
+    const int32_t *m = colour_table[matrix];
+    const int cw = width / 2, ch = height / 2;
+    for (int r = 0; r < ch; ++r)
+        for (int x = 0; x < cw; ++x) {
+            const size_t at = (size_t)r * cw + x;
+            const int32_t cb = (nv ? sample(p1, 2 * at) : sample(p1, at)) - 512, cr = (nv ? sample(p1, 2 * at + 1) : sample(p2, at)) - 512;
+            int32_t su = 0, sv = 0;
+            for (int j = 0; j < 2; ++j)
+                for (int i = 0; i < 2; ++i) {
+                    const size_t px = (size_t)(2 * r + j) * width + (2 * x + i);
+                    const int32_t yy = 38295 * (sample(p0, px) - 64) + 4096;
+                    const int32_t R1 = clamp12((yy + 55209 * cr) >> 13), G1 = clamp12((yy - 6161 * cb - 21391 * cr) >> 13), B1 = clamp12((yy + 70440 * cb) >> 13);
+                    const uint32_t g = gain[std::max(R1, std::max(G1, B1))];
+                    const int32_t aR = (int32_t)lin[R1], aG = (int32_t)lin[G1], aB = (int32_t)lin[B1];
+                    const int32_t R = out8(1701 * aR - 602 * aG - 75 * aB + 512, g), G = out8(-128 * aR + 1161 * aG - 9 * aB + 512, g),
+                                  B = out8(-19 * aR - 103 * aG + 1146 * aB + 512, g);
+                    y[px] = (uint8_t)(m[0] + ((m[1] * R + m[2] * G + m[3] * B + 128) >> 8));
+                    su += m[4] * R + m[5] * G + m[6] * B;
+                    sv += m[7] * R + m[8] * G + m[9] * B;
+                }
+            u[at] = (uint8_t)((su + 131072 + 512) >> 10);
+            v[at] = (uint8_t)((sv + 131072 + 512) >> 10);
         }
     return 0;
 }

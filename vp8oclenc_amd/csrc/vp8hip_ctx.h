@@ -152,9 +152,11 @@ struct vp8hip_ctx {
     vp8::ScalePlan scale;
     // vp8hip_set_source_format: what the three pointers of a current frame are (0 = I420: fmt_stage is not used).  k_convert_b makes tight
     // I420 of the incoming size of them in fmt_stage (tight_i420) and the pack or scale launch reads that.
-    // vp8hip_set_source_colour: the colour matrix BGRA / RGBA frames are read with (no other format looks at it).
-    int src_fmt = 0, src_colour = 0;
-    DeviceBuf fmt_stage;
+    // vp8hip_set_source_colour: the colour matrix BGRA / RGBA frames are read with, and a tone-mapped frame is written with.
+    // vp8hip_set_source_transfer: the transfer (0 = off) and peak P010 / I010 frames carry: k_tonemap_b in k_convert_b's place, with the
+    // four tables of (src_transfer, src_peak) in tm_tables (made by the setter, released when the transfer goes back to 0).
+    int src_fmt = 0, src_colour = 0, src_transfer = 0, src_peak = 0;
+    DeviceBuf fmt_stage, tm_tables;
     // planes from host memory that were not prefetched, on their way to a convert, deinterlace or scale launch, pass through here: the
     // planes in the source format end to end (incoming_bytes; the call synchronises before it returns: one buffer is enough)
     DeviceBuf raw_stage;
@@ -454,7 +456,7 @@ inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) {
     (void)vp8host_source_plane_bytes(c->src_fmt, w, h, bytes);
 }
 inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched convert / pack / scale launch takes as one value
-    return a->src_fmt == b->src_fmt && a->src_colour == b->src_colour && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
+    return a->src_fmt == b->src_fmt && a->src_colour == b->src_colour && a->src_transfer == b->src_transfer && a->src_peak == b->src_peak && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
            (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level &&     // (and one denoiser level)
            a->di_mode == b->di_mode && a->di_keep == b->di_keep &&                                  // (one deinterlacer mode and parity)
            a->an_on == b->an_on &&                                                                  // (analysis on for all or for none)

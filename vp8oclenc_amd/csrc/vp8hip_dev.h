@@ -211,6 +211,11 @@ void launch_aq_seg_batch(hipStream_t s, const AqItem *items, int n, int strength
 // matrix the setters refuse -- nothing was launched and the staging buffer is NOT the frame.
 struct ConvertItem { const uint8_t *src[3]; uint8_t *dst[3]; };
 bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const ConvertItem *items, int n);
+// ... and with a transfer in force (vp8hip_set_source_transfer; P010 / I010 only): k_tonemap_b in k_convert_b's place, the same items,
+// the same tight I420 out.  tables: the four tables of vp8host_tonemap_tables end to end in device memory (lin, gain, lo, hi: 40 KiB);
+// matrix: the colour matrix the SDR picture is written with.  false: a format or matrix the rule does not cover (nothing was launched)
+constexpr int TONEMAP_TABLE_BYTES = 4096 * (4 + 4 + 1 + 1);
+bool launch_tonemap_batch(hipStream_t s, int format, int matrix, int w, int h, const uint32_t *tables, const ConvertItem *items, int n);
 // kernels_deinterlace.hip: interlaced source frames made progressive (vp8hip_set_deinterlace) BEHIND the convert launch and IN FRONT of
 // the pack or scale launch, which then reads dst as it reads a converted frame; the rule is include/vp8hip_host.h's.  src: tight I420
 // of w x h; hist: the previous frame as received (all nullptr: no history -- the spatial value everywhere); keep_hist: where this

@@ -46,6 +46,11 @@ class InterPathDriver:
         if segment_map is not None:
             self.be.upload_segment_map(segment_map)
 
+    def set_source_transfer(self, transfer, peak: int = api.PEAK_DEFAULT) -> None:
+        """vp8hip_set_source_transfer on the backend (the device backend only: the CPU oracle reads I420): the P010 / I010 planes it is
+        handed as current frames from now on are tone-mapped to SDR"""
+        self.be.set_source_transfer(transfer, peak)
+
     def segments_for(self, y: np.ndarray, is_key: bool, is_altref: bool, update_filter: bool = False) -> np.ndarray:
         reductor, sharp = api.loopfilter_strength(y)
         refqi = self.altrefqi if is_altref else self.lastqi
