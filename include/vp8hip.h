@@ -250,6 +250,37 @@ int vp8hip_set_source_colour(vp8hip_ctx *ctx, int matrix);
  * pending vp8hip_prefetch_current made under another transfer or peak is dropped.  All members of a batch must agree on transfer and
  * peak as on the format.  (A context with hidden alt-refs refuses every source format but I420, so it never tone-maps.) */
 int vp8hip_set_source_transfer(vp8hip_ctx *ctx, int transfer, int peak);
+/* Layers burnt into the source frames: station logos, watermarks, subtitles, timecode.  A LAYER is a plane of lw x lh pixels of four
+ * bytes, BGRA or RGBA (VP8HOST_FORMAT_BGRA / _RGBA, no other format) with straight alpha, rows `pitch` bytes apart, placed with its
+ * top-left pixel at (x, y) of the PICTURE -- the upright frame the pack or scale launch writes: the source size or the scaler's
+ * destination -- with an opacity 0 .. 255 and a colour matrix of its own (enum vp8host_colour_matrix; vp8hip_set_source_colour has no
+ * say).  The rule -- effective alpha, luma and chroma, rounding, several layers, the padding -- is stated bit for bit in
+ * include/vp8hip_host.h (vp8host_overlay_frame is its plain C++ form).  Slots 0 .. VP8HIP_MAX_OVERLAYS - 1 are applied in slot order.
+ * The layer's pixels are copied before the call returns (only the layer's bytes: a 2-D copy), so the caller's buffer is free
+ * afterwards (_device: once what the context's intake stream holds has run, as with vp8hip_set_current_device); k_overlay_prepare
+ * then makes the layer's prepared planes, once per layer set or moved, never per frame.
+ * A layer is in force FROM THE NEXT FRAME MADE CURRENT, by any route: vp8hip_set_current_device, vp8hip_upload_current (a prefetched
+ * frame is composed when it is made current, with the layers in force then), the batched forms, the driver's calls.  ONE launch
+ * (k_overlay_b) for all members of a batch stands behind the pack or scale launch and in front of the denoiser, so everything
+ * downstream -- denoiser, chroma scan, analysis, AQ map, searches, quality statistics -- sees the composed frame, the one that is
+ * coded.  Once per frame TAKEN IN, never per coding attempt.  Members of a batch may have different layers, or none; setting a layer
+ * on a member of a live batch is allowed between frames: the copy and the prepare launch go on the stream the member's frames are
+ * taken in on, and the host waits only where a buffer has to grow, where the pixels come from host memory, or where the context has a
+ * loop filter stream of its own (vp8hip_filter_overlap).
+ * A context that never sets a layer launches nothing, allocates nothing and gives the bytes it gave.
+ * vp8hip_set_overlay_placement: move or fade a layer (the planes are prepared again from the retained copy).
+ * vp8hip_clear_overlay: slot, or -1 = all; frees the slot's buffers; waits for the context's streams.
+ * VP8HIP_ERR_ARG: a bad slot, format, matrix, size (1 .. 16384), pitch (< 4 lw), position (outside -16384 .. 16384) or opacity, a null
+ * pointer, placement or clear of an empty slot (slot -1 on a context without a layer is VP8HIP_OK); VP8HIP_ERR_STATE: a context in a
+ * by-reference split (vp8hip_shard_join, which in turn refuses a context with a layer).  Everything that can be refused is checked
+ * before anything of the context changes.  Out of scope: premultiplied alpha, 24-bit RGB and YUVA layers, scaling or rotating a
+ * layer, text rendering, reading PNG, hidden alt-ref frames (vp8hip_arf_filter_*: the window frames bypass the intake). */
+#define VP8HIP_MAX_OVERLAYS 4
+int vp8hip_set_overlay_host(vp8hip_ctx *ctx, int slot, int format, int matrix, const uint8_t *pixels, int lw, int lh, int pitch, int x, int y, int opacity);
+int vp8hip_set_overlay_device(vp8hip_ctx *ctx, int slot, int format, int matrix, const void *pixels, int lw, int lh, int pitch, int x, int y, int opacity);
+int vp8hip_set_overlay_placement(vp8hip_ctx *ctx, int slot, int x, int y, int opacity);
+int vp8hip_clear_overlay(vp8hip_ctx *ctx, int slot);
+int vp8hip_overlay_count(const vp8hip_ctx *ctx);      /* slots that hold a layer */
 /* Temporal noise reduction of the source frames, the third stage of the input side (libvpx: --noise-sensitivity); the reference never
  * did anything about noise.  level 1, 2, 3: every frame that becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the
  * pack out of a vp8hip_prefetch_current staging buffer, vp8hip_batch_set_current_device, vp8hip_batch_upload_current, with or without a
@@ -650,7 +681,10 @@ const char *vp8hip_status_string(int status);
  * vp8drv_encode_arf_device, vp8drv_encode_arf_host, vp8drv_get_arf_stats; entry points only, and the value VP8HIP_ALTREF_HIDDEN of
  * the existing is_altref fields: vp8drv_config, vp8drv_stats, vp8hip_header_params and vp8bs_frame keep their layout);
  * also under 4010: HDR tone mapping (vp8hip_set_source_transfer, vp8drv_set_source_transfer, vp8host_tonemap_tables,
- * vp8host_tonemap_frame; entry points only: vp8drv_config is unchanged). */
+ * vp8host_tonemap_frame; entry points only: vp8drv_config is unchanged);
+ * also under 4010: overlays (vp8hip_set_overlay_host, vp8hip_set_overlay_device, vp8hip_set_overlay_placement, vp8hip_clear_overlay,
+ * vp8hip_overlay_count, vp8host_overlay_frame, vp8drv_set_overlay_host, vp8drv_set_overlay_device, vp8drv_set_overlay_placement,
+ * vp8drv_clear_overlay; entry points only: vp8drv_config is unchanged). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

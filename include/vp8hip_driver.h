@@ -278,6 +278,18 @@ int vp8drv_set_source_colour(vp8drv *d, int matrix);
  * force other than I420, P010 or I010, or cfg.device_params = 0; VP8HIP_ERR_STATE: the driver is a member of a live batch
  * (vp8drv_batch_create refuses members that differ in transfer or peak). */
 int vp8drv_set_source_transfer(vp8drv *d, int transfer, int peak);
+/* Layers burnt into the source frames (vp8hip_set_overlay_host / _device, vp8hip_set_overlay_placement, vp8hip_clear_overlay, which say
+ * what a layer is; the rule: include/vp8hip_host.h).  Entry points, not fields of vp8drv_config, for the reason vp8drv_set_denoise is
+ * one.  A layer is in force from the next frame the driver takes in, whichever call hands it over (vp8drv_stage_frame_host and the
+ * batch scan included); the scene scan and the coder see the same composed frame, so scene_detect keeps working.  Unlike the other
+ * intake setters they are allowed on a member of a live batch between frames, as vp8drv_set_segment_map is: a subtitle may change from
+ * frame to frame.  They take the open check_SSIM verdict first.  VP8HIP_ERR_ARG: what the context's entry point refuses, or
+ * cfg.device_params = 0 (the host mirror scans the caller's luma, which is not the frame coded).  While any layer is set
+ * vp8drv_encode_arf_device / _host refuse with VP8HIP_ERR_ARG: the window frames bypass the intake. */
+int vp8drv_set_overlay_host(vp8drv *d, int slot, int format, int matrix, const uint8_t *pixels, int lw, int lh, int pitch, int x, int y, int opacity);
+int vp8drv_set_overlay_device(vp8drv *d, int slot, int format, int matrix, const void *pixels, int lw, int lh, int pitch, int x, int y, int opacity);
+int vp8drv_set_overlay_placement(vp8drv *d, int slot, int x, int y, int opacity);
+int vp8drv_clear_overlay(vp8drv *d, int slot);
 /* Source frames that are the window of a pitched surface, and source frames stored sideways or upside down
  * (vp8hip_set_source_window, vp8hip_set_source_orientation; the rules: include/vp8hip_host.h).  Entry points, not fields of
  * vp8drv_config, for the reason vp8drv_set_denoise is one; call them after vp8drv_create and before the first frame, or between

@@ -156,6 +156,42 @@ int vp8host_convert_frame_colour(int format, int matrix, int width, int height, 
 /* the table above: c = the Y, U and V rows one after the other, each in the order R, G, B.  0, or -1: unknown matrix, null pointer */
 int vp8host_colour_coefficients(int matrix, int32_t c[9], int32_t *y_offset);
 
+/* OVERLAYS (vp8hip_set_overlay_host / _device, include/vp8hip.h; k_overlay_prepare, k_overlay_b): the ONE integer rule that burns a
+ * layer -- a station logo, a watermark, a subtitle, a timecode -- into a frame on its way in.  The project's own.  A LAYER is a plane of
+ * lw x lh pixels (1 .. 16384 each) of four bytes, format BGRA (18) or RGBA (19) and no other, STRAIGHT (not premultiplied) alpha, rows
+ * `pitch` bytes apart (pitch >= 4 lw; the bytes between the rows are never read), with the position (x, y) of its top-left pixel in
+ * PICTURE coordinates (any integers in -16384 .. 16384, odd ones included), an opacity 0 .. 255 and a colour matrix of its own (enum
+ * vp8host_colour_matrix; vp8hip_set_source_colour has no say).  The PICTURE is the upright frame the pack or scale launch writes, pw x ph,
+ * both even: the source size or the scaler's destination.  Layer pixels outside [0, pw) x [0, ph) are dropped.  Every division below
+ * truncates and every operand is non-negative.
+ *     e   = (a * opacity + 127) / 255                              the effective alpha of a layer pixel; a picture pixel that no layer
+ *                                                                  pixel covers has e = 0
+ *     Yo  = off + ((cR R + cG G + cB B + 128) >> 8)                the BGRA rule above, the Y row of the LAYER's matrix
+ *     Y   = (src * (255 - e) + Yo * e + 127) / 255                 per picture pixel
+ *     c_i = cR R_i + cG G_i + cB B_i + 32768                       per layer pixel, with the U row
+ *     E   = sum of e_i (0 .. 1020),  T = sum of e_i c_i            over the four picture pixels (2cx .. 2cx + 1, 2cy .. 2cy + 1) of a
+ *                                                                  chroma sample, whatever the parity of x and y
+ *     N   = src * 256 * (1020 - E) + T                             below 2^31
+ *     U   = ((N + 130560) >> 10) / 255                             V the same with the V row
+ * One rounding step per plane and layer; no clamp is needed and none is applied.  Several layers: slots 0 .. VP8HIP_MAX_OVERLAYS - 1 are
+ * applied in slot order, each on the result of the one before.  PADDING: the composed coded frame is the composed picture padded as
+ * copy_with_padding pads it -- sample (x, y) of the coded surface is composed sample (min(x, pw - 1), min(y, ph - 1)) -- so a layer
+ * that touches the picture's last column or row changes the padding samples behind it.
+ * What the rule guarantees (tests/test_overlay_cpu.py asserts each): (n + 127) / 255 equals t = n + 128; (t + (t >> 8)) >> 8 for every
+ * n in 0 .. 65025, and q / 255 equals (q * 0x8081) >> 23 for every q below 66299 (the chroma q never exceeds 65408), so the device
+ * never divides; for an opaque layer (a = 255, opacity = 255) at even x, y with even size the chroma rule is exactly the BGRA rule's
+ * (S + 131584) >> 10 and luma is Yo, so such a layer replaces its rectangle with vp8host_convert_frame_colour(BGRA, matrix, ...) of
+ * itself, byte for byte; e = 0 changes nothing; over the RGB cube chroma stays in [16, 240] (limited) and [1, 255] (full).
+ * Out of scope: premultiplied alpha, 24-bit RGB and YUVA layers, scaling or rotating a layer, text rendering, reading PNG, hidden
+ * alt-ref frames (the window frames bypass the intake) and by-reference splits. */
+#define VP8HOST_OVERLAY_MAX_SIZE 16384
+#define VP8HOST_OVERLAY_MAX_POS 16384
+/* the rule as plain C++: ONE layer composed in place onto tight I420 of the picture size pw x ph.  0, or -1 for anything refused: a
+ * format other than BGRA / RGBA, an unknown matrix, a size, pitch, position or opacity out of range, a picture size that is odd or not
+ * positive, a null pointer */
+int vp8host_overlay_frame(int format, int matrix, int lw, int lh, int pitch, const uint8_t *pixels, int x, int y, int opacity, int pw, int ph,
+                          uint8_t *yp, uint8_t *up, uint8_t *vp);
+
 /* HDR SOURCES MADE SDR (vp8hip_set_source_transfer, include/vp8hip.h; k_tonemap_b): the ONE integer rule that makes 8-bit SDR I420 of
  * a ten-bit PQ (SMPTE ST 2084, HDR10) or HLG (BT.2100) frame.  The project's own: without it the planar rule above keeps the PQ or HLG
  * signal and the BT.2020 primaries, and a VP8 player, which shows BT.601 / BT.709 SDR, shows PQ grey and flat and HLG dim and

@@ -80,6 +80,7 @@ def main():
     ap.add_argument("--source-range", choices=("limited", "full"), default="limited", help="... and the range of the YUV it makes")
     ap.add_argument("--source-transfer", choices=("pq", "hlg"), default="", help="the ten-bit frames (--source-format p010 or i010, or a C420p10 file) carry a PQ or HLG signal in BT.2020 and are tone-mapped to SDR on the device, written with --source-matrix / --source-range (vp8drv_set_source_transfer)")
     ap.add_argument("--source-peak", type=int, default=1000, metavar="N", help="... the peak luminance they were graded for, 400..10000 nits")
+    ap.add_argument("--overlay", action="append", default=[], metavar="FILE:WxH:X:Y[:OPACITY]", help="FILE holds W x H pixels of raw BGRA, tight, straight alpha: the layer is burnt into every frame on the device with its top-left pixel at (X, Y) of the coded picture, at OPACITY 0..255 (default 255), read with BT.601 limited range (vp8drv_set_overlay_host); up to four times, applied in order")
     ap.add_argument("--denoise", type=int, choices=(0, 1, 2, 3), default=0, help="temporal noise reduction of the source frames on the device (vp8drv_set_denoise); the history restarts with every GOP")
     ap.add_argument("--deinterlace", choices=("off", "field", "adaptive"), default="off", metavar="MODE", help="interlaced source frames made progressive on the device (vp8drv_set_deinterlace): field = every missing row interpolated, adaptive = what stands still is woven; the history restarts with every GOP")
     ap.add_argument("--field", choices=("top", "bottom"), default="top", help="... the field that is kept")
@@ -159,6 +160,12 @@ def main():
         seg_map = np.fromfile(a.segment_map, np.uint8)
         if seg_map.size != (Wc // 16) * (Hc // 16) or (seg_map.size and seg_map.max() > 3):
             sys.exit(f"--segment-map {a.segment_map}: {(Wc // 16) * (Hc // 16)} bytes of 0..3 are one map of {Wc}x{Hc}")
+    try:
+        overlays = [api.parse_overlay(o) for o in a.overlay]
+    except (ValueError, OSError) as e:
+        sys.exit(f"--overlay: {e}")
+    if len(overlays) > api.MAX_OVERLAYS or (overlays and arf):
+        sys.exit(f"--overlay: at most {api.MAX_OVERLAYS} layers, and not with --arf (the window frames bypass the intake)")
     t0 = time.perf_counter()
     def make_encoder(scan=False):
         enc = gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
@@ -180,6 +187,8 @@ def main():
             enc.drv.set_source_colour(a.source_matrix, a.source_range)
         if a.source_transfer:
             enc.drv.set_source_transfer(a.source_transfer, a.source_peak)
+        for k, (px, ox, oy, opacity) in enumerate(overlays):
+            enc.drv.set_overlay(k, px, ox, oy, opacity)
         if turns or a.mirror:
             enc.drv.set_source_orientation(turns, int(a.mirror))
         if window:

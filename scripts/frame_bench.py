@@ -28,6 +28,7 @@ ap.add_argument("--source-matrix", choices=("bt601", "bt709"), default="bt601", 
 ap.add_argument("--source-range", choices=("limited", "full"), default="limited")
 ap.add_argument("--source-transfer", choices=("pq", "hlg"), default="", help="with --source-format p010 or i010: the frames are tone-mapped to SDR on the device (vp8drv_set_source_transfer): what k_tonemap_b costs in k_convert_b's place")
 ap.add_argument("--source-peak", type=int, default=1000, metavar="N", help="... the peak luminance in nits, 400..10000")
+ap.add_argument("--overlay", action="append", default=[], metavar="FILE:WxH:X:Y[:OPACITY]", help="a layer of raw BGRA bytes burnt into every frame taken in (vp8drv_set_overlay_host), up to four times: what k_overlay_b costs")
 ap.add_argument("--window-pitch", type=int, default=0, metavar="P", help="the device-resident frames are surfaces whose luma rows are P bytes apart (the other planes' in proportion) and the frame is the window at (0, 0) (vp8drv_set_source_window): what k_window_b costs")
 ap.add_argument("--rotate", type=int, choices=(0, 90, 180, 270), default=0, help="the device-resident frames are stored turned back by this many degrees and are turned clockwise on the device (vp8drv_set_source_orientation): what k_orient_b costs; the coded bytes do not change")
 ap.add_argument("--mirror", action="store_true", help="... behind a left-right flip")
@@ -110,6 +111,9 @@ if a.source_transfer:      # (the frames carry an SDR picture's codes: the mappe
         sys.exit("--source-transfer goes with --source-format p010 or i010")
     for d in drvs:
         d.set_source_transfer(a.source_transfer, a.source_peak)
+for k, (px, ox, oy, opacity) in enumerate(api.parse_overlay(o) for o in a.overlay):
+    for d in drvs:
+        d.set_overlay(k, px, ox, oy, opacity)
 if turns or a.mirror:
     for d in drvs:
         d.set_source_orientation(turns, int(a.mirror))

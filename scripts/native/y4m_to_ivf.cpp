@@ -2,7 +2,7 @@
 // IVF out (main() of src/vp8enc.cpp reduced to: parse the header, per frame read / code / write, patch the frame count).
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
-//              [-input-format NAME] [-input-transfer pq|hlg[:PEAK]] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
+//              [-input-format NAME] [-input-transfer pq|hlg[:PEAK]] [-overlay FILE:WxH:X:Y[:OPACITY]] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
 //              [-arf PERIOD[:FRAMES[:STRENGTH]]]
 // -arf PERIOD[:FRAMES[:STRENGTH]] (FRAMES 1..7, default 7; STRENGTH 0..6, default 3): hidden alternate reference frames
 // (vp8drv_set_arf, vp8drv_encode_arf_host; libvpx's --auto-alt-ref=1 --arnr-maxframes --arnr-strength).  In front of the first frame of
@@ -36,6 +36,10 @@
 // default 1000), and are tone-mapped to SDR on the device (vp8drv_set_source_transfer; the rule: include/vp8hip_host.h).  A Y4M header
 // carries neither transfer nor primaries, so the option says it.  It goes with C420p10 files only (their frames read as i010, or as
 // p010 with -input-format); any other file is refused with its tag named.
+// -overlay FILE:WxH:X:Y[:OPACITY]: FILE holds W x H pixels of raw BGRA, tight, straight alpha; the layer is burnt into every frame on the
+// device with its top-left pixel at (X, Y) of the coded picture (any integers, odd and negative ones included) at OPACITY 0..255
+// (default 255), read with BT.601 limited range (vp8drv_set_overlay_host; the rule: include/vp8hip_host.h).  Up to four times: the
+// layers are applied in the order they appear.
 // -aq N: variance-adaptive quantisation of the inter frames at strength N = 1, 2, 3 (vp8drv_set_segment_mode, mode 2; 0 = off): flat
 // macroblocks take the finer segments of the quantiser ladder, busy ones the coarser.
 // -denoise N: temporal noise reduction of the source frames on the device, N = 1, 2, 3 (vp8drv_set_denoise; 0 = off); the share of
@@ -54,6 +58,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -74,6 +79,9 @@ int main(int argc, char **argv) {
     int aq = 0;              // -aq
     int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     int32_t format = -1;     // -input-format (-1: the header's C tag)
+    // -overlay FILE:WxH:X:Y[:OPACITY]: raw BGRA bytes, tight, burnt into every frame; slots in order of appearance, matrix 0
+    struct Overlay { int w = 0, h = 0, x = 0, y = 0, opacity = 255; std::vector<uint8_t> pixels; };
+    std::vector<Overlay> overlays;
     int transfer = 0, peak = 1000;  // -input-transfer: PQ or HLG ten-bit frames are tone-mapped to SDR on the device
     int crop[4] = {0, 0, 0, 0};     // -crop: W, H, X, Y (W == 0: the whole surface)
     int turns = 0, mirror = 0;      // -rotate, -mirror
@@ -120,6 +128,21 @@ int main(int argc, char **argv) {
             if (colon) peak = atoi(colon + 1);
             if (!transfer || peak < VP8HOST_PEAK_MIN || peak > VP8HOST_PEAK_MAX) { fprintf(stderr, "-input-transfer pq|hlg[:PEAK], PEAK 400..10000 nits\n"); return 2; }
         }
+        else if (!strcmp(argv[i], "-overlay")) {
+            Overlay o;
+            const char *f = val(), *colon = strchr(f, ':');
+            if (!colon || sscanf(colon + 1, "%dx%d:%d:%d:%d", &o.w, &o.h, &o.x, &o.y, &o.opacity) < 4 || o.w < 1 || o.h < 1 || o.w > VP8HOST_OVERLAY_MAX_SIZE ||
+                o.h > VP8HOST_OVERLAY_MAX_SIZE || o.opacity < 0 || o.opacity > 255 || overlays.size() == VP8HIP_MAX_OVERLAYS) {
+                fprintf(stderr, "-overlay FILE:WxH:X:Y[:OPACITY], OPACITY 0..255, at most %d times\n", VP8HIP_MAX_OVERLAYS);
+                return 2;
+            }
+            const std::string path(f, (size_t)(colon - f));
+            FILE *lf = fopen(path.c_str(), "rb");
+            o.pixels.resize((size_t)o.w * o.h * 4);
+            if (!lf || fread(o.pixels.data(), 1, o.pixels.size(), lf) != o.pixels.size()) { fprintf(stderr, "-overlay %s: not %d x %d x 4 bytes of BGRA\n", path.c_str(), o.w, o.h); return 2; }
+            fclose(lf);
+            overlays.push_back(std::move(o));
+        }
         else if (!strcmp(argv[i], "-crop")) {
             if (sscanf(val(), "%d:%d:%d:%d", &crop[0], &crop[1], &crop[2], &crop[3]) != 4 || crop[0] <= 0 || crop[1] <= 0) { fprintf(stderr, "-crop W:H:X:Y\n"); return 2; }
         }
@@ -146,7 +169,7 @@ int main(int argc, char **argv) {
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (arf_period) {
-        if (denoise || deint || analysis_path || crop[0]) { fprintf(stderr, "-arf does not go with -denoise, -deinterlace, -analysis or -crop\n"); return 2; }
+        if (denoise || deint || analysis_path || crop[0] || !overlays.empty()) { fprintf(stderr, "-arf does not go with -denoise, -deinterlace, -analysis, -crop or -overlay\n"); return 2; }
         cfg.overlap_filter = 0;    // (the next frame's ALTREF search would start beside the filter that writes ALTREF; the key frames stay where they are without the option)
         fprintf(stderr, "-arf: the loop filter runs on the frame's own stream in this mode (no frame is handed over early)\n");
     }
@@ -223,6 +246,8 @@ int main(int argc, char **argv) {
     if (aq) CK(vp8drv_set_segment_mode(drv, 2, aq));
     if (format) CK(vp8drv_set_source_format(drv, format));
     if (transfer) CK(vp8drv_set_source_transfer(drv, transfer, peak));
+    for (size_t k = 0; k < overlays.size(); ++k)
+        CK(vp8drv_set_overlay_host(drv, (int)k, VP8HOST_FORMAT_BGRA, 0, overlays[k].pixels.data(), overlays[k].w, overlays[k].h, 4 * overlays[k].w, overlays[k].x, overlays[k].y, overlays[k].opacity));
     if (turns || mirror) CK(vp8drv_set_source_orientation(drv, turns, mirror));
     if (crop[0]) CK(vp8drv_set_source_window(drv, pitch, crop[2], crop[3]));
     if (deint) CK(vp8drv_set_deinterlace(drv, deint, field));

@@ -2,7 +2,9 @@
 // bench.py's headline measures, as a complete C++ user of the C ABI.
 //   y4m_to_ivf_gops <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n]
 //                   [-no-check-ssim] [-conformant] [-simple-filter] [-chunks N (48)] [-batch B (6)] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
-//                   [-deinterlace field|adaptive[:top|bottom]] [-scene-detect]
+//                   [-deinterlace field|adaptive[:top|bottom]] [-scene-detect] [-overlay FILE:WxH:X:Y[:OPACITY]]
+// (-overlay: as in y4m_to_ivf.cpp, up to four times -- every context gets the layers before its batch is made; layers have no history, so
+//  a chunk codes the frames the serial program codes, and the option goes with -scene-detect: the scan and the coder see the same composed frame)
 // (-scene-detect: the file `y4m_to_ivf -g g` writes with ITS default, scene detection on.  A cut makes a key frame and restarts the GOP
 //  counter, so the chunks are not known up front -- but the whole schedule is a function of the chroma differences of consecutive frames
 //  and of g (vp8host_scene_plan).  So the file is SCANNED first: cut into as many contiguous segments as chunks are in flight, member i
@@ -35,6 +37,7 @@
 #include <unistd.h>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -54,6 +57,9 @@ int main(int argc, char **argv) {
     int aq = 0;              // -aq
     int deint = 0, field = -1;      // -deinterlace: the mode, and the field kept (-1: the first field of the header's I tag)
     bool scene = false;      // -scene-detect
+    // -overlay FILE:WxH:X:Y[:OPACITY]: raw BGRA bytes, tight, burnt into every frame; slots in order of appearance, matrix 0
+    struct Overlay { int w = 0, h = 0, x = 0, y = 0, opacity = 255; std::vector<uint8_t> pixels; };
+    std::vector<Overlay> overlays;
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
         if (!strcmp(argv[i], "-g")) cfg.gop_size = atoi(val());
@@ -78,6 +84,21 @@ int main(int argc, char **argv) {
             if (colon && !strcmp(colon + 1, "top")) field = 0;
             else if (colon && !strcmp(colon + 1, "bottom")) field = 1;
             if (!deint || (colon && field < 0)) { fprintf(stderr, "-deinterlace field|adaptive[:top|bottom]\n"); return 2; }
+        }
+        else if (!strcmp(argv[i], "-overlay")) {
+            Overlay o;
+            const char *f = val(), *colon = strchr(f, ':');
+            if (!colon || sscanf(colon + 1, "%dx%d:%d:%d:%d", &o.w, &o.h, &o.x, &o.y, &o.opacity) < 4 || o.w < 1 || o.h < 1 || o.w > VP8HOST_OVERLAY_MAX_SIZE ||
+                o.h > VP8HOST_OVERLAY_MAX_SIZE || o.opacity < 0 || o.opacity > 255 || overlays.size() == VP8HIP_MAX_OVERLAYS) {
+                fprintf(stderr, "-overlay FILE:WxH:X:Y[:OPACITY], OPACITY 0..255, at most %d times\n", VP8HIP_MAX_OVERLAYS);
+                return 2;
+            }
+            const std::string path(f, (size_t)(colon - f));
+            FILE *lf = fopen(path.c_str(), "rb");
+            o.pixels.resize((size_t)o.w * o.h * 4);
+            if (!lf || fread(o.pixels.data(), 1, o.pixels.size(), lf) != o.pixels.size()) { fprintf(stderr, "-overlay %s: not %d x %d x 4 bytes of BGRA\n", path.c_str(), o.w, o.h); return 2; }
+            fclose(lf);
+            overlays.push_back(std::move(o));
         }
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
@@ -154,6 +175,8 @@ int main(int argc, char **argv) {
         if (aq) CK(vp8drv_set_segment_mode(drv[j], 2, aq));      // (before the batch is made too)
         if (denoise) CK(vp8drv_set_denoise(drv[j], denoise));      // (before the batch is made: its members must agree)
         if (deint) CK(vp8drv_set_deinterlace(drv[j], deint, field));
+        for (size_t k = 0; k < overlays.size(); ++k)
+            CK(vp8drv_set_overlay_host(drv[j], (int)k, VP8HOST_FORMAT_BGRA, 0, overlays[k].pixels.data(), overlays[k].w, overlays[k].h, 4 * overlays[k].w, overlays[k].x, overlays[k].y, overlays[k].opacity));
         CK(vp8hip_reserve_frame_path_dense(vp8drv_context(drv[j])));      // frame t + 1 is started before frame t's bytes are taken: no frame is ever coded twice
         if ((j + 1) % batch == 0 || j == in_flight - 1) {
             const int k = j / batch, j0 = k * batch;

@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "vp8host_arf_filter_frame", "vp8host_arf_round_divide", "vp8drv_set_arf", "vp8drv_encode_arf_device", "vp8drv_encode_arf_host",
     "vp8drv_get_arf_stats",
     "vp8hip_set_source_transfer", "vp8drv_set_source_transfer", "vp8host_tonemap_tables", "vp8host_tonemap_frame",
+    "vp8hip_set_overlay_host", "vp8hip_set_overlay_device", "vp8hip_set_overlay_placement", "vp8hip_clear_overlay", "vp8hip_overlay_count",
+    "vp8host_overlay_frame", "vp8drv_set_overlay_host", "vp8drv_set_overlay_device", "vp8drv_set_overlay_placement", "vp8drv_clear_overlay",
 ]
 
 
@@ -824,6 +826,63 @@ def tonemap_frame(fmt, transfer, peak: int, width: int, height: int, planes, mat
     return out
 
 
+MAX_OVERLAYS = 4      # VP8HIP_MAX_OVERLAYS, include/vp8hip.h
+
+
+def _layer_args(pixels, lw, lh, pitch):
+    """a layer as the C entry points take it: a uint8 array of shape (lh, lw, 4), whose rows may be further apart than 4 lw bytes, or
+    device memory (anything with data_ptr()) with lw, lh and, unless the rows are tight, pitch -> (keep-alive, pointer, lw, lh, pitch, on_device)"""
+    if hasattr(pixels, "data_ptr"):
+        if lw is None or lh is None:
+            raise ValueError("a layer in device memory needs lw and lh")
+        return pixels, pixels.data_ptr(), int(lw), int(lh), int(pitch if pitch is not None else 4 * lw), True
+    a = np.asarray(pixels)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("a layer is a uint8 array of shape (lh, lw, 4)")
+    if a.strides[2] != 1 or a.strides[1] != 4 or a.strides[0] < 4 * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a, a.ctypes.data, int(a.shape[1]), int(a.shape[0]), int(a.strides[0]) if a.shape[0] > 1 else max(int(a.strides[0]), 4 * int(a.shape[1])), False
+
+
+def parse_overlay(spec: str):
+    """FILE:WxH:X:Y[:OPACITY], the tools' -overlay / --overlay option: FILE holds W x H pixels of raw BGRA, tight -> (pixels as a uint8
+    array of shape (H, W, 4), x, y, opacity); ValueError for anything else"""
+    parts = spec.rsplit(":", 4)      # (FILE may hold colons of its own: the fields are counted from the right)
+    if len(parts) < 5 or "x" not in parts[1].lower():
+        parts = spec.rsplit(":", 3) + ["255"]
+    try:
+        path, size, x, y, opacity = parts
+        w, h = (int(v) for v in size.lower().split("x"))
+        x, y, opacity = int(x), int(y), int(opacity)
+    except ValueError:
+        raise ValueError(f"overlay {spec!r}: FILE:WxH:X:Y[:OPACITY]") from None
+    if not (1 <= w <= 16384 and 1 <= h <= 16384 and 0 <= opacity <= 255):
+        raise ValueError(f"overlay {spec!r}: a size of 1..16384 and an opacity of 0..255")
+    px = np.fromfile(path, np.uint8)
+    if px.size != w * h * 4:
+        raise ValueError(f"overlay {path}: {px.size} bytes, not {w} x {h} x 4 of BGRA")
+    return px.reshape(h, w, 4), x, y, opacity
+
+
+_OVERLAY_SET_ARGS = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6
+
+
+def overlay_frame(pixels, x: int, y: int, opacity: int, planes, fmt=None, matrix: int = 0):
+    """vp8host_overlay_frame: the device's overlay rule in plain C++.  pixels = the layer, a uint8 array of shape (lh, lw, 4), BGRA
+    unless fmt says RGBA; planes = (Y, U, V), I420 of the picture size -> new (Y, U, V) with the layer composed at (x, y)"""
+    lib = load_library()
+    lib.vp8host_overlay_frame.argtypes = [C.c_int] * 5 + [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3
+    fmt = FORMAT_BGRA if fmt is None else (source_format(fmt) if isinstance(fmt, str) else int(fmt))
+    keep, ptr, lw, lh, pitch, dev = _layer_args(pixels, None, None, None)
+    out = [np.array(p, np.uint8, order="C") for p in planes]
+    ph, pw = out[0].shape
+    if out[1].shape != (ph // 2, pw // 2) or out[2].shape != (ph // 2, pw // 2):
+        raise ValueError("overlay_frame: planes are not I420 of one size")
+    if lib.vp8host_overlay_frame(fmt, int(matrix), lw, lh, pitch, ptr, int(x), int(y), int(opacity), pw, ph, *[o.ctypes.data for o in out]) != 0:
+        raise ValueError(f"vp8host_overlay_frame(format {fmt}, matrix {matrix}, {lw}x{lh} pitch {pitch} at ({x}, {y}), opacity {opacity}, picture {pw}x{ph}) refused")
+    return tuple(out)
+
+
 def _pitch3(pitch):
     p = [int(x) for x in pitch] + [0, 0, 0]
     return (C.c_int32 * 3)(*p[:3])
@@ -1073,6 +1132,31 @@ class NativeDriver:
         rc = self.lib.vp8drv_set_source_colour(self.h, m)
         if rc < 0:
             raise Vp8HipError(f"vp8drv_set_source_colour({m}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_overlay(self, slot: int, pixels, x: int, y: int, opacity: int = 255, fmt=None, matrix: int = 0, lw=None, lh=None, pitch=None) -> None:
+        """vp8drv_set_overlay_host / _device: the layer `pixels` (a uint8 array of shape (lh, lw, 4), or device memory with lw, lh and
+        pitch; BGRA unless fmt says RGBA) is burnt into every frame taken in from now on, its top-left pixel at (x, y) of the picture"""
+        fmt = FORMAT_BGRA if fmt is None else (source_format(fmt) if isinstance(fmt, str) else int(fmt))
+        keep, ptr, lw, lh, pitch, dev = _layer_args(pixels, lw, lh, pitch)
+        f = self.lib.vp8drv_set_overlay_device if dev else self.lib.vp8drv_set_overlay_host
+        f.argtypes = _OVERLAY_SET_ARGS
+        rc = f(self.h, int(slot), fmt, int(matrix), ptr, lw, lh, pitch, int(x), int(y), int(opacity))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_overlay({slot}, {lw}x{lh} at ({x}, {y})): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_overlay_placement(self, slot: int, x: int, y: int, opacity: int = 255) -> None:
+        """vp8drv_set_overlay_placement: move or fade the slot's layer"""
+        self.lib.vp8drv_set_overlay_placement.argtypes = [C.c_void_p] + [C.c_int] * 4
+        rc = self.lib.vp8drv_set_overlay_placement(self.h, int(slot), int(x), int(y), int(opacity))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_overlay_placement({slot}, {x}, {y}, {opacity}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def clear_overlay(self, slot: int = -1) -> None:
+        """vp8drv_clear_overlay: the slot's layer, or with -1 every layer, is gone from the next frame on"""
+        self.lib.vp8drv_clear_overlay.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.vp8drv_clear_overlay(self.h, int(slot))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_clear_overlay({slot}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_source_transfer(self, transfer, peak: int = PEAK_DEFAULT) -> None:
         """vp8drv_set_source_transfer: P010 / I010 frames carry this transfer (a TRANSFER_* number, or sdr / pq / hlg) graded for `peak`
@@ -1628,6 +1712,31 @@ class Vp8Hip:
         rc = self.lib.vp8hip_set_source_transfer(self.h, t, int(peak))
         if rc != 0:
             raise Vp8HipError(f"set_source_transfer({t}, {peak}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_overlay(self, slot: int, pixels, x: int, y: int, opacity: int = 255, fmt=None, matrix: int = 0, lw=None, lh=None, pitch=None):
+        """vp8hip_set_overlay_host / _device: the layer `pixels` (a uint8 array of shape (lh, lw, 4), or device memory with lw, lh and
+        pitch; BGRA unless fmt says RGBA) is burnt into every frame taken in from now on, its top-left pixel at (x, y) of the picture"""
+        fmt = FORMAT_BGRA if fmt is None else (source_format(fmt) if isinstance(fmt, str) else int(fmt))
+        keep, ptr, lw, lh, pitch, dev = _layer_args(pixels, lw, lh, pitch)
+        f = self.lib.vp8hip_set_overlay_device if dev else self.lib.vp8hip_set_overlay_host
+        f.argtypes = _OVERLAY_SET_ARGS
+        rc = f(self.h, int(slot), fmt, int(matrix), ptr, lw, lh, pitch, int(x), int(y), int(opacity))
+        if rc != 0:
+            raise Vp8HipError(f"vp8hip_set_overlay({slot}, {lw}x{lh} at ({x}, {y})): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_overlay_placement(self, slot: int, x: int, y: int, opacity: int = 255):
+        """vp8hip_set_overlay_placement: move or fade the slot's layer"""
+        self.lib.vp8hip_set_overlay_placement.argtypes = [C.c_void_p] + [C.c_int] * 4
+        rc = self.lib.vp8hip_set_overlay_placement(self.h, int(slot), int(x), int(y), int(opacity))
+        if rc != 0:
+            raise Vp8HipError(f"vp8hip_set_overlay_placement({slot}, {x}, {y}, {opacity}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def clear_overlay(self, slot: int = -1):
+        """vp8hip_clear_overlay: the slot's layer, or with -1 every layer, is gone from the next frame on"""
+        self.lib.vp8hip_clear_overlay.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.vp8hip_clear_overlay(self.h, int(slot))
+        if rc != 0:
+            raise Vp8HipError(f"vp8hip_clear_overlay({slot}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_denoise(self, level: int):
         """vp8hip_set_denoise: every frame that becomes current passes through the temporal denoiser (level 1-3; 0 = off); turning it

@@ -446,6 +446,7 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     hipFree(c->scale.d_blob);
     c->fmt_stage.release();
     c->tm_tables.release();
+    overlay_release(c);
     c->raw_stage.release();
     c->di_stage.release();
     c->win_stage.release();

@@ -1,5 +1,5 @@
 // api_intake.hip -- how a frame becomes a context's current frame: the source size, scaling, format and colour setters, the staging
-// buffers, the stage order (take_frames: window, convert, deinterlace, orient, scale or pack, denoise, analysis, segment map -- the one place that knows it), and the
+// buffers, the stage order (take_frames: window, convert, deinterlace, orient, scale or pack, overlay, denoise, analysis, segment map -- the one place that knows it), and the
 // single-context ways in (vp8hip_set_current_device, vp8hip_upload_current, vp8hip_prefetch_current).  A batch's ways in are api_batch.hip's;
 // they end in take_frames too.  Replaces the uploads of vp8enc.cpp:386-401.
 #include "vp8hip_ctx.h"
@@ -162,6 +162,19 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
         if (!skip) launch_pack_batch(s, src, n, c0->src_w, c0->src_h);
     }
     if (planes_read) HIPCHK(c0, hipEventRecord(planes_read, s));
+    {   // vp8hip_set_overlay_*: the members that have layers, in one launch behind the pack or scale launch and IN FRONT of the denoiser,
+        // whose history is the previous current surface: everything downstream sees the composed frame, the one that is coded
+        OverlayItem ov[MAX_BATCH];
+        int no = 0;
+        for (int i = 0; i < n; ++i)
+            if (overlay_item(m[i], s, ov[no])) ++no;
+        if (no) {
+            int pw, ph;
+            picture_size(c0, &pw, &ph);      // (same_intake: one picture size)
+            Timed t(c0, VP8HIP_K_PACK);
+            launch_overlay_batch(s, ov, no, pw, ph);
+        }
+    }
     {   // vp8hip_set_denoise: the members that have a history, in one launch behind the pack (the others' frames pass through)
         DenoiseItem dn[MAX_BATCH];
         int nd = 0;

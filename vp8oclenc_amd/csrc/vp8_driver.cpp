@@ -750,6 +750,32 @@ int vp8drv_set_source_transfer(vp8drv *d, int transfer, int peak) {
     return VP8HIP_OK;
 }
 
+// vp8drv_set_overlay_*: layers burnt into the frames taken in from now on.  Allowed on a member of a live batch between frames, as
+// vp8drv_set_segment_map is; with cfg.device_params = 0 the host mirror scans the caller's luma, which is not the frame coded.
+int vp8drv_set_overlay_host(vp8drv *d, int slot, int format, int matrix, const uint8_t *pixels, int lw, int lh, int pitch, int x, int y, int opacity) {
+    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    { const int rc = resolve(d); if (rc < 0) return rc; }      // the open check_SSIM verdict first
+    return vp8hip_set_overlay_host(d->hip, slot, format, matrix, pixels, lw, lh, pitch, x, y, opacity);
+}
+
+int vp8drv_set_overlay_device(vp8drv *d, int slot, int format, int matrix, const void *pixels, int lw, int lh, int pitch, int x, int y, int opacity) {
+    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    return vp8hip_set_overlay_device(d->hip, slot, format, matrix, pixels, lw, lh, pitch, x, y, opacity);
+}
+
+int vp8drv_set_overlay_placement(vp8drv *d, int slot, int x, int y, int opacity) {
+    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    return vp8hip_set_overlay_placement(d->hip, slot, x, y, opacity);
+}
+
+int vp8drv_clear_overlay(vp8drv *d, int slot) {
+    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    return vp8hip_clear_overlay(d->hip, slot);
+}
+
 int vp8drv_set_source_window(vp8drv *d, const int32_t *pitch, int x, int y) {
     if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
     if (d->in_batch) return VP8HIP_ERR_STATE;
@@ -877,6 +903,7 @@ static int hidden_frame(vp8drv *d) {
 static int arf_check(vp8drv *d, const void *frames, int n, int centre) {
     if (!d || !frames || n < 1 || n > VP8HOST_ARF_MAX_FRAMES || centre < 0 || centre >= n) return VP8HIP_ERR_ARG;
     if (d->format || d->window || d->deinterlace || d->denoise || d->analysis || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (vp8hip_overlay_count(d->hip)) return VP8HIP_ERR_ARG;      // (the window frames bypass the intake: a layer would miss them)
     if (!d->arf || d->in_batch || !d->have_frame || d->staged) return VP8HIP_ERR_STATE;      // (off; batched; no reference yet; a frame handed over early is the current frame)
     const int rc = resolve(d);                                                                // the open check_SSIM verdict first
     return rc < 0 ? rc : VP8HIP_OK;

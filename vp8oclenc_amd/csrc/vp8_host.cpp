@@ -304,9 +304,53 @@ int vp8host_convert_frame_colour(int format, int matrix, int width, int height, 
     return convert_packed(format, matrix, width, height, p0, y, u, v);
 }
 
+// OVERLAYS, include/vp8hip_host.h: one layer composed onto tight I420 of the picture size, in place
+int vp8host_overlay_frame(int format, int matrix, int lw, int lh, int pitch, const uint8_t *pixels, int x, int y, int opacity, int pw, int ph,
+                          uint8_t *yp, uint8_t *up, uint8_t *vp) {
+    if ((format != VP8HOST_FORMAT_BGRA && format != VP8HOST_FORMAT_RGBA) || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT || lw < 1 || lh < 1 ||
+        lw > VP8HOST_OVERLAY_MAX_SIZE || lh > VP8HOST_OVERLAY_MAX_SIZE || pitch < 4 * lw || x < -VP8HOST_OVERLAY_MAX_POS || x > VP8HOST_OVERLAY_MAX_POS ||
+        y < -VP8HOST_OVERLAY_MAX_POS || y > VP8HOST_OVERLAY_MAX_POS || opacity < 0 || opacity > 255 || pw <= 0 || ph <= 0 || (pw & 1) || (ph & 1) || !pixels ||
+        !yp || !up || !vp)
+        return -1;
+    const int32_t *m = colour_table[matrix];
+    const int ir = format == VP8HOST_FORMAT_BGRA ? 2 : 0, ib = 2 - ir;
+    // the layer pixel at picture position (px, py), or nullptr where the layer has none
+    auto at = [&](int px, int py) -> const uint8_t * {
+        const int lx = px - x, ly = py - y;
+        return lx >= 0 && lx < lw && ly >= 0 && ly < lh ? pixels + (size_t)ly * (size_t)pitch + (size_t)lx * 4 : nullptr;
+    };
+    const int x0 = x > 0 ? x : 0, y0 = y > 0 ? y : 0, x1 = x + lw < pw ? x + lw : pw, y1 = y + lh < ph ? y + lh : ph;
+    for (int py = y0; py < y1; ++py)
+        for (int px = x0; px < x1; ++px) {
+            const uint8_t *q = at(px, py);
+            const int32_t e = (q[3] * opacity + 127) / 255;
+            const int32_t yo = m[0] + ((m[1] * q[ir] + m[2] * q[1] + m[3] * q[ib] + 128) >> 8);
+            uint8_t *d = yp + (size_t)py * pw + px;
+            *d = (uint8_t)((*d * (255 - e) + yo * e + 127) / 255);
+        }
+    const int cw = pw / 2;
+    for (int cy = y0 >> 1; cy < (y1 + 1) >> 1; ++cy)
+        for (int cx = x0 >> 1; cx < (x1 + 1) >> 1; ++cx) {
+            int32_t E = 0, tu = 0, tv = 0;
+            for (int j = 0; j < 2; ++j)
+                for (int i = 0; i < 2; ++i) {
+                    const uint8_t *q = at(2 * cx + i, 2 * cy + j);
+                    if (!q) continue;
+                    const int32_t e = (q[3] * opacity + 127) / 255;
+                    E += e;
+                    tu += e * (m[4] * q[ir] + m[5] * q[1] + m[6] * q[ib] + 32768);
+                    tv += e * (m[7] * q[ir] + m[8] * q[1] + m[9] * q[ib] + 32768);
+                }
+            uint8_t *du = up + (size_t)cy * cw + cx, *dv = vp + (size_t)cy * cw + cx;
+            *du = (uint8_t)(((*du * 256 * (1020 - E) + tu + 130560) >> 10) / 255);
+            *dv = (uint8_t)(((*dv * 256 * (1020 - E) + tv + 130560) >> 10) / 255);
+        }
+    return 0;
+}
+
 int vp8host_convert_frame(int format, int width, int height, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2,
                           uint8_t *y, uint8_t *u, uint8_t *v) {
-    if (packed_format(format)) return vp8host_convert_frame_colour(format, VP8HOST_COLOUR_BT601_LIMITED, width, height, p0, p1, p2, y, u, v);
+    if (packed_format(format))return vp8host_convert_frame_colour(format, VP8HOST_COLOUR_BT601_LIMITED, width, height, p0, p1, p2, y, u, v);
     SourceLayout l;
     size_t bytes[3];
     if (vp8host_source_plane_bytes(format, width, height, bytes) != 0 || !source_layout(format, &l)) return -1;

@@ -157,6 +157,17 @@ struct vp8hip_ctx {
     // four tables of (src_transfer, src_peak) in tm_tables (made by the setter, released when the transfer goes back to 0).
     int src_fmt = 0, src_colour = 0, src_transfer = 0, src_peak = 0;
     DeviceBuf fmt_stage, tm_tables;
+    // vp8hip_set_overlay_host / _device: the layers burnt into every frame taken in, in slot order (ov_count of them are set; 0: no
+    // launch, no buffer).  A slot keeps the layer's pixels (tight rows) and its prepared planes (overlay_planes; sized for any
+    // placement); `stale`: the planes are not those of the placement in force -- the next intake launches k_overlay_prepare in front
+    // of k_overlay_b, on its own stream.
+    struct OverlaySlot {
+        bool set = false, stale = false;
+        int format = 0, matrix = 0, lw = 0, lh = 0, x = 0, y = 0, opacity = 0;
+        DeviceBuf pixels, planes;
+    };
+    OverlaySlot ov[VP8HIP_MAX_OVERLAYS];
+    int ov_count = 0;
     // planes from host memory that were not prefetched, on their way to a convert, deinterlace or scale launch, pass through here: the
     // planes in the source format end to end (incoming_bytes; the call synchronises before it returns: one buffer is enough)
     DeviceBuf raw_stage;
@@ -474,7 +485,7 @@ int copy_planes(vp8hip_ctx *c, uint8_t *d, const void *y, const void *u, const v
 // the buffers the members' next frames need, at their incoming size (as a rule: they are there); changes nothing else
 int intake_ready(vp8hip_ctx *const *m, int n);
 // THE ORDER, once: n contexts of one intake (same_intake) take their new current frames in on stream s -- window, convert, deinterlace,
-// orient, scale or pack, denoise, analysis.  y, u, v: the members' planes in DEVICE memory in their source format: the plane bases of
+// orient, scale or pack, overlay, denoise, analysis.  y, u, v: the members' planes in DEVICE memory in their source format: the plane bases of
 // their surfaces when the contexts have a window, unless `tight` (planes that came from the host through copy_planes are the window already).
 // alone: nullptr for a batch's members.  For a context on its own (n == 1, s its stream) it points at where the planes are: such a
 // context keeps the pack launch of one, and without a format, deinterlacer or scaler its planes may be the host's, copied straight
@@ -510,6 +521,13 @@ int prof_collect(vp8hip_ctx *c);
 // The frame just packed or scaled into c->cur passes through the denoiser (take_frames: right behind the pack, on the pack's stream).  denoise_item: false = nothing to launch (off, or no history: the frame passes through and
 // is the history from now on).
 bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it);
+// ---- api_overlay.hip ----
+// The frame just packed or scaled into c->cur takes the context's layers (take_frames: behind the pack or scale launch and in front of
+// the denoiser, on the same stream s).  overlay_item: launches k_overlay_prepare on s for the slots whose planes are stale; false = no
+// layer covers the picture, nothing to launch.  overlay_release: every slot's buffers (vp8hip_destroy).
+bool overlay_item(vp8hip_ctx *c, hipStream_t s, OverlayItem &it);
+void overlay_release(vp8hip_ctx *c);
+inline void picture_size(const vp8hip_ctx *c, int *w, int *h) { *w = c->src_w ? c->src_w : c->W; *h = c->src_h ? c->src_h : c->H; }
 // ---- api_deinterlace.hip ----
 // The frame about to be packed or scaled passes through the deinterlacer (take_frames: behind the convert launch and in front of the
 // pack or scale launch, on the same stream).  deinterlace_ready: the staging and history buffers at

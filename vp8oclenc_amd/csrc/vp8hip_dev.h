@@ -241,6 +241,20 @@ struct GeometryItem { const uint8_t *src[3]; uint8_t *dst[3]; };
 void launch_window_batch(hipStream_t s, const size_t offset[3], const int32_t pitch[3], const int32_t row_bytes[3], const int32_t rows[3],
                          const GeometryItem *items, int n);
 void launch_orient_batch(hipStream_t s, int turns, int mirror, int raw_w, int raw_h, const GeometryItem *items, int n);
+// kernels_overlay.hip: layers burnt into the frame just packed or scaled (vp8hip_set_overlay_host / _device), in place on the current
+// surface IN FRONT of the denoiser; the rule is include/vp8hip_host.h's.  A layer's PREPARED PLANES (k_overlay_prepare, when the layer
+// is set or moved) lie in one device buffer: Yo at 0 and e at off_e, lh rows of lstride bytes whose column 0 is picture column X0 =
+// x & ~3; E (16 bits) at off_E, T_u and T_v (32 bits) at off_tu and off_tv, crows rows of cstride samples whose sample (0, 0) is chroma
+// sample (CX0, cy0) of the picture; both strides are multiples of 4 and every plane starts on a multiple of 256 bytes.
+struct OverlayPlanes { int X0, lstride, CX0, cy0, cstride, crows; size_t off_e, off_E, off_tu, off_tv, bytes; };
+OverlayPlanes overlay_planes(int lw, int lh, int x, int y);
+struct OverlayLayer { const uint8_t *base; size_t off_e, off_E, off_tu, off_tv; int X0, y, lstride, lh, CX0, cy0, cstride, crows; };
+// a member's frame and its layers in slot order; ux0 .. ux1, uy0 .. uy1: the box of the layers in units of 8 luma columns and 2 luma
+// rows, inside the coded surface
+struct OverlayItem { Plane y, u, v; int n, ux0, ux1, uy0, uy1; OverlayLayer layer[VP8HIP_MAX_OVERLAYS]; };
+// false: a format or matrix the setters refuse (nothing was launched)
+bool launch_overlay_prepare(hipStream_t s, int format, int matrix, const uint8_t *pixels, int lw, int lh, int x, int y, int opacity, uint8_t *planes);
+void launch_overlay_batch(hipStream_t s, const OverlayItem *items, int n, int pw, int ph);      // pw x ph: the picture inside the coded surface
 // kernels_arf.hip: the temporal filter of a hidden alternate reference frame (vp8hip_arf_filter_device); the rule is
 // include/vp8hip_host.h's.  src: n frames of tight I420 of w x h in device memory; dst: the filtered frame, tight, which overlaps none
 // of them; weights: ARF_WEIGHT_SLOTS 64-bit words (the caller zeroes them in front of the launch) whose SUM holds the (tile, frame) pairs

@@ -51,6 +51,17 @@ class InterPathDriver:
         handed as current frames from now on are tone-mapped to SDR"""
         self.be.set_source_transfer(transfer, peak)
 
+    def set_overlay(self, slot: int, pixels, x: int, y: int, opacity: int = 255, **kw) -> None:
+        """vp8hip_set_overlay_host / _device on the backend (the device backend only): the layer is burnt into the frames handed over
+        as current frames from now on"""
+        self.be.set_overlay(slot, pixels, x, y, opacity, **kw)
+
+    def set_overlay_placement(self, slot: int, x: int, y: int, opacity: int = 255) -> None:
+        self.be.set_overlay_placement(slot, x, y, opacity)
+
+    def clear_overlay(self, slot: int = -1) -> None:
+        self.be.clear_overlay(slot)
+
     def segments_for(self, y: np.ndarray, is_key: bool, is_altref: bool, update_filter: bool = False) -> np.ndarray:
         reductor, sharp = api.loopfilter_strength(y)
         refqi = self.altrefqi if is_altref else self.lastqi
