@@ -95,7 +95,7 @@ static int check_window() {
                     for (int p = 0; p < 3; ++p) pitch[p] = rows[p] ? rb[p] + (int32_t)(off[p] % (1 << 20)) + e : 0;
                     if (vp8host_source_window(format, w, h, x, y, pitch, off, rb, rows) != 0) { fprintf(stderr, "the rule refused format %d pitch\n", format); return 1; }
                     std::vector<Block> src, dst, want;
-                    GeometryItem it[2];
+                    PlanesItem it[2];
                     for (int m = 0; m < n; ++m)
                         for (int p = 0; p < 3; ++p) {
                             // from the window's first byte to its last: base = block - off
@@ -134,7 +134,7 @@ static int check_orient() {
                 const int w = s[0], h = s[1], n = 2;
                 const size_t nb[3] = {(size_t)w * h, (size_t)(w / 2) * (h / 2), (size_t)(w / 2) * (h / 2)};
                 std::vector<Block> src, dst, want;
-                GeometryItem it[2];
+                PlanesItem it[2];
                 for (int m = 0; m < n; ++m)
                     for (int p = 0; p < 3; ++p) {
                         src.emplace_back(nb[p]); dst.emplace_back(nb[p]); want.emplace_back(nb[p]);

@@ -373,6 +373,40 @@ def test_members_that_differ_in_mode_or_parity_make_no_batch(a, b):
         c.close()
 
 
+def test_a_member_whose_deinterlacer_was_on_and_is_off_again_batches_with_one_that_never_had_it():
+    """off is off whatever parity the call that turned it off named: set_deinterlace(1, 0) and then (0, 1) leaves nothing behind"""
+    from vp8oclenc_amd import api
+    W, H = 64, 48
+    ctxs, alone = [api.Vp8Hip(W, H), api.Vp8Hip(W, H)], [api.Vp8Hip(W, H), api.Vp8Hip(W, H)]
+    for group in (ctxs, alone):
+        group[0].set_deinterlace(1, 0)
+        group[0].set_deinterlace(0, 1)
+    lib = ctxs[0].lib
+    arr = C.POINTER(C.c_void_p)
+    lib.vp8hip_batch_create.argtypes = [C.POINTER(C.c_void_p), arr, C.c_int]
+    lib.vp8hip_batch_destroy.argtypes = [C.c_void_p]
+    lib.vp8hip_batch_destroy.restype = None
+    lib.vp8hip_batch_upload_current.argtypes = [C.c_void_p, C.POINTER(C.c_int), arr, arr, arr]
+    hb = C.c_void_p()
+    assert lib.vp8hip_batch_create(C.byref(hb), (C.c_void_p * 2)(ctxs[0].h, ctxs[1].h), 2) == 0
+    videos = [ref.interlaced_video(W, H, 2, seed=51), ref.interlaced_video(W, H, 2, seed=52)]
+    for t in range(2):
+        bufs = [[api.HostBuffer(p) for p in v[t]] for v in videos]
+        planes = [(C.c_void_p * 2)(bufs[0][k].data_ptr(), bufs[1][k].data_ptr()) for k in range(3)]
+        assert lib.vp8hip_batch_upload_current(hb, None, *planes) == 0
+        for i in range(2):
+            ctxs[i].synchronize()
+            alone[i].upload_current(*videos[i][t])
+            assert_surfaces(current_surfaces(ctxs[i]), current_surfaces(alone[i]), f"member {i} frame {t}")
+            assert_surfaces(current_surfaces(ctxs[i]), videos[i][t], f"member {i} frame {t}: passed through")
+        for v in bufs:
+            for b in v:
+                b.free()
+    lib.vp8hip_batch_destroy(hb)
+    for c in ctxs + alone:
+        c.close()
+
+
 # ---- 6. beside the denoiser and the analysis ------------------------------------------------------------------------------------------
 def test_the_order_is_deinterlace_then_denoise_then_analysis():
     from vp8oclenc_amd import api

@@ -433,8 +433,9 @@ def test_setters_on_a_member_of_a_live_batch_are_refused():
     mirror.close()
 
 
-@pytest.mark.parametrize("setter", ["window", "orientation"])
+@pytest.mark.parametrize("setter", ["window", "orientation", "deinterlace", "source size"])
 def test_a_pending_prefetch_is_dropped_by_either_setter(setter):
+    """one rule for every setter that changes what the raw planes mean: planes staged under the old settings are handed over again"""
     from vp8oclenc_amd import api
     w, h = WINDOW
     hip, plain = api.Vp8Hip(w, h), api.Vp8Hip(w, h)
@@ -443,17 +444,29 @@ def test_a_pending_prefetch_is_dropped_by_either_setter(setter):
     lib.vp8hip_upload_current.argtypes = [C.c_void_p] * 4
     pitch = ref.tight_pitch(ref.I420, 80)
     hip.set_source_window(pitch, 0, 0)
-    first, second = ref.raw_frame(w, h, seed=80), ref.raw_frame(w, h, seed=81)
+    first = ref.raw_frame(w, h, seed=80)
+    if setter == "source size":     # 34x18 inside 48x32 while the planes are staged, 36x18 when they are taken (fewer than 16 below the coded width, both)
+        hip.set_source_size(34, 18)
+        first, (w, h) = ref.raw_frame(34, 18, seed=80), (36, 18)
+        plain.set_source_size(w, h)
+    second = ref.raw_frame(w, h, seed=81)
     s = Surface(ref.I420, first, 80, 48, 0, 0, pitch, 82, "pinned")
     assert lib.vp8hip_prefetch_current(hip.h, *s.ptrs) == 0
     if setter == "window":      # the same planes through another window: the bytes staged through the first one are not this frame
         hip.set_source_window(pitch, 14, 2)
         want = ref.window(ref.I420, s.planes, w, h, 14, 2)
     else:                       # the setter has waited for the copy: planes rewritten afterwards are read again, or the stale frame shows
-        hip.set_source_orientation(2, 0)
+        if setter == "orientation":
+            hip.set_source_orientation(2, 0)
+            want = ref.orient(second, 2, 0)
+        elif setter == "deinterlace":
+            hip.set_deinterlace(1, 0)
+            want = deinterlace_ref.Deinterlacer(1, 0).take(second)[0]
+        else:
+            hip.set_source_size(w, h)
+            want = second
         t = Surface(ref.I420, second, 80, 48, 0, 0, pitch, 83, "host")
         C.memmove(s.buf.data_ptr(), t.buf.ctypes.data, t.buf.nbytes)
-        want = ref.orient(second, 2, 0)
     assert lib.vp8hip_upload_current(hip.h, *s.ptrs) == 0
     plain.upload_current(*want)
     assert_surfaces(current_surfaces(hip), current_surfaces(plain), setter)

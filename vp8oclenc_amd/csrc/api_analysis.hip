@@ -19,7 +19,7 @@ uint8_t *analysis_history(const vp8hip_ctx *c) { return c->an.d + 256; }
 }  // namespace
 
 bool analysis_src_item(vp8hip_ctx *c, hipStream_t s, AnalysisSrcItem &it) {
-    if (!c->an_on) return false;
+    if (!c->in.an_on) return false;
     const int frame = c->cur_count - 1, k = frame & 1;
     it.cur = c->cur.Y[0];
     it.hist = analysis_history(c);
@@ -38,7 +38,7 @@ bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it) {
     const bool checked = c->an_checked;
     c->an_checked = false;
     const int frame = c->cur_count - 1;
-    if (!c->an_on || frame < 0 || c->an_src_frame[frame & 1] != frame) return false;   // (a frame taken in before analysis was turned on has no record)
+    if (!c->in.an_on || frame < 0 || c->an_src_frame[frame & 1] != frame) return false;   // (a frame taken in before analysis was turned on has no record)
     it.parts = c->out.parts;
     it.ref = c->out.ref;
     it.seg = c->out.seg;
@@ -78,11 +78,10 @@ extern "C" {
 int vp8hip_set_analysis(vp8hip_ctx *c, int on) {
     if (!c || (on != 0 && on != 1)) return VP8HIP_ERR_ARG;
     USE_DEVICE(c);
-    if ((on != 0) == c->an_on) return VP8HIP_OK;
+    if ((on != 0) == c->in.an_on) return VP8HIP_OK;
     if (on && c->shard_comm) return VP8HIP_ERR_STATE;      // (a context whose frames are split over devices codes only part of a frame)
     // a launch still in flight reads and writes the history and the record: it ends first (not a per-frame call)
     JOIN_LF(c);
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
     if (on) {
         const int rc = c->an.make(c, 256 + (size_t)c->mbs * 256, 256);
         if (rc) return rc;
@@ -90,7 +89,9 @@ int vp8hip_set_analysis(vp8hip_ctx *c, int on) {
         c->an_src[1].h = &c->an.h->src[1];
         c->an_mb.h = &c->an.h->mb;
     }
-    c->an_on = on != 0;
+    IntakeSettings next = c->in;
+    next.an_on = on != 0;
+    { const int rc = intake_apply(c, next); if (rc) return rc; }
     c->an_have_prev = false;
     c->an_src_frame[0] = c->an_src_frame[1] = c->an_mb_frame = -1;
     return VP8HIP_OK;
@@ -106,7 +107,7 @@ int vp8hip_analysis_result(vp8hip_ctx *c, vp8hip_analysis *a) {
     USE_DEVICE_ONLY(c);
     if (!c || !a) return VP8HIP_ERR_ARG;
     const int last = c->cur_count - 1;
-    if (!c->an_on || last < 0 || c->an_src_frame[last & 1] != last) return VP8HIP_ERR_STATE;
+    if (!c->in.an_on || last < 0 || c->an_src_frame[last & 1] != last) return VP8HIP_ERR_STATE;
     const bool coded = c->an_mb_frame >= 0 && c->an_mb_frame >= last - 1 && c->an_src_frame[c->an_mb_frame & 1] == c->an_mb_frame;
     const int frame = coded ? c->an_mb_frame : last, k = frame & 1;
     int rc = c->an_src[k].wait(c);

@@ -12,7 +12,7 @@ namespace {
 // what a context must not be or have for a hidden frame (include/vp8hip.h says why); the window's parameters
 int arf_check(const vp8hip_ctx *c, const void *frames, int n, int centre, int strength) {
     if (!c || !frames || n < 1 || n > VP8HOST_ARF_MAX_FRAMES || centre < 0 || centre >= n || strength < 0 || strength > 6) return VP8HIP_ERR_ARG;
-    if (c->src_fmt || c->win_on || c->di_mode || c->dn_level || c->an_on) return VP8HIP_ERR_ARG;
+    if (excludes_arf(c->in)) return VP8HIP_ERR_ARG;
     if (c->batch || c->shard_comm || c->lf_overlap) return VP8HIP_ERR_STATE;
     return VP8HIP_OK;
 }

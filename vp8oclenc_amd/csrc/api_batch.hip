@@ -174,7 +174,7 @@ static int batch_stage_ready(vp8hip_batch *b) {
         HIPCHK(c0, hipEventCreateWithFlags(&b->ev_packed[0], hipEventDisableTiming));
         HIPCHK(c0, hipEventCreateWithFlags(&b->ev_packed[1], hipEventDisableTiming));
     }
-    if (b->stage_bytes == bytes && b->stage_fmt == c0->src_fmt) return VP8HIP_OK;
+    if (b->stage_bytes == bytes && b->stage_fmt == c0->in.src_fmt) return VP8HIP_OK;
     // (first call, or the source size or format has changed: nothing in flight reads the old buffers after this)
     { const int rc = quiesce_intake(c0); if (rc) return rc; }
     b->stage_bytes = 0;
@@ -185,7 +185,7 @@ static int batch_stage_ready(vp8hip_batch *b) {
             if (rc) return rc;
         }
     b->stage_bytes = bytes;
-    b->stage_fmt = c0->src_fmt;
+    b->stage_fmt = c0->in.src_fmt;
     b->packed_valid[0] = b->packed_valid[1] = false;
     b->pre_valid = false;
     return VP8HIP_OK;
@@ -344,7 +344,7 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
     for (int k = 0; k < n; ++k) {
         const int i = a.pos[k];
         if (m[k]->conformant != c0->conformant) return VP8HIP_ERR_ARG;   // one launch, one predictor
-        if (m[k]->seg_mode != c0->seg_mode || m[k]->seg_strength != c0->seg_strength) return VP8HIP_ERR_ARG;   // ... and one segment mode (the maps are the members' own)
+        if (m[k]->in.seg_mode != c0->in.seg_mode || m[k]->in.seg_strength != c0->in.seg_strength) return VP8HIP_ERR_ARG;   // ... and one segment mode (the maps are the members' own)
         const int rc = inter_check(m[k], prev_is_golden[i], prev_is_altref[i], use_golden[i], use_altref[i]);
         if (rc) return rc;
     }
@@ -423,7 +423,7 @@ int vp8hip_batch_inter_transform(vp8hip_batch *b, const int *active, const int *
         if (it[k].scan) launch_auto_segments(s, *it[k].scan);
     {
         Timed t(c0, VP8HIP_K_MB);
-        launch_mb_batch(s, it, n, c0->ssim_target, c0->mbw, c0->mbh, c0->conformant != 0, c0->seg_mode != 0);
+        launch_mb_batch(s, it, n, c0->ssim_target, c0->mbw, c0->mbh, c0->conformant != 0, c0->in.seg_mode != 0);
     }
     for (int k = 0; k < n; ++k) recon_made(m[k], false);
     HIPCHK(c0, hipGetLastError());

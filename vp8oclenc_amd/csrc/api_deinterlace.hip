@@ -11,13 +11,12 @@ using namespace vp8;
 namespace vp8 {
 
 int deinterlace_ready(vp8hip_ctx *c) {
-    if (!c->di_mode) return VP8HIP_OK;
+    if (!c->in.di_mode) return VP8HIP_OK;
     int w, h;
     incoming_size(c, &w, &h);
-    if (h < 4) return VP8HIP_ERR_ARG;
     const size_t need = tight_i420(w, h).bytes;      // (first use, or the incoming size has grown: not a per-frame event)
     { const int rc = c->di_stage.grow(c, need); if (rc) return rc; }
-    if (c->di_mode == 2 && need > c->di_hist[0].bytes) {      // the two histories: both or neither
+    if (c->in.di_mode == 2 && need > c->di_hist[0].bytes) {      // the two histories: both or neither
         DeviceBuf d[2];
         int rc = d[0].grow(c, need);
         if (!rc) rc = d[1].grow(c, need);
@@ -32,12 +31,12 @@ int deinterlace_ready(vp8hip_ctx *c) {
 }
 
 bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const void *&y, const void *&u, const void *&v) {
-    if (!c->di_mode) return false;
+    if (!c->in.di_mode) return false;
     int w, h;
     incoming_size(c, &w, &h);
     const TightI420 t = tight_i420(w, h);
     const uint8_t *src[3] = {static_cast<const uint8_t *>(y), static_cast<const uint8_t *>(u), static_cast<const uint8_t *>(v)};
-    const bool adaptive = c->di_mode == 2;
+    const bool adaptive = c->in.di_mode == 2;
     const bool have = adaptive && c->di_have_history && c->di_hist_w == w && c->di_hist_h == h;
     for (int p = 0; p < 3; ++p) {
         it.src[p] = src[p];
@@ -66,25 +65,18 @@ bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const v
 extern "C" {
 
 int vp8hip_set_deinterlace(vp8hip_ctx *c, int mode, int keep) {
-    if (!c || mode < 0 || mode > 2 || (keep != 0 && keep != 1)) return VP8HIP_ERR_ARG;
-    if (mode) {
-        int w, h;
-        incoming_size(c, &w, &h);
-        if (h < 4) return VP8HIP_ERR_ARG;      // every plane needs a row of each field
-    }
+    if (!c) return VP8HIP_ERR_ARG;
+    IntakeSettings next = c->in;
+    next.di_mode = mode;
+    next.di_keep = keep;      // (off has no parity: canonical; the parity itself is judged as given)
+    if (intake_valid(c->W, c->H, next) != VP8HIP_OK) return VP8HIP_ERR_ARG;      // (here, not only in intake_apply: before canonical drops the parity of "off")
+    next = canonical(next, c->W, c->H);
     USE_DEVICE(c);
-    if (mode == c->di_mode && (!mode || keep == c->di_keep)) return VP8HIP_OK;
-    // a launch still in flight reads the history and writes the record: it ends first (not a per-frame call)
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    if (next == c->in) return VP8HIP_OK;
     if (mode) { const int rc = c->di.make(c, 256, 256); if (rc) return rc; }
-    const int mode_before = c->di_mode, keep_before = c->di_keep;
-    c->di_mode = mode;
-    c->di_keep = keep;
-    { const int rc = deinterlace_ready(c); if (rc) { c->di_mode = mode_before; c->di_keep = keep_before; return rc; } }
+    { const int rc = intake_apply(c, next); if (rc) return rc; }
     c->di_have_history = false;
     c->di_taken = false;
-    c->h2d_pre_valid = false;      // planes prefetched under other settings are handed over again
-    if (c->batch) c->batch->pre_valid = false;
     return VP8HIP_OK;
 }
 
@@ -97,7 +89,7 @@ int vp8hip_deinterlace_restart(vp8hip_ctx *c) {
 int vp8hip_deinterlace_result(vp8hip_ctx *c, vp8hip_deinterlace_stats *s) {
     USE_DEVICE_ONLY(c);
     if (!c || !s) return VP8HIP_ERR_ARG;
-    if (!c->di_mode || !c->di_taken) return VP8HIP_ERR_STATE;
+    if (!c->in.di_mode || !c->di_taken) return VP8HIP_ERR_STATE;
     const int rc = c->di.wait(c);
     if (rc) return rc;
     const DeinterlaceMirror m = *c->di.h;

@@ -10,7 +10,7 @@ using namespace vp8;
 namespace vp8 {
 
 bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it) {
-    if (!c->dn_level) return false;
+    if (!c->in.dn_level) return false;
     c->dn_taken = true;
     if (!c->dn_have_history) {      // first frame, after a restart or a level change: unchanged, and the history from now on
         c->dn_have_history = true;
@@ -36,11 +36,11 @@ extern "C" {
 int vp8hip_set_denoise(vp8hip_ctx *c, int level) {
     if (!c || level < 0 || level > 3) return VP8HIP_ERR_ARG;
     USE_DEVICE(c);
-    if (level == c->dn_level) return VP8HIP_OK;
-    // a launch still in flight reads the level's history and writes the record: it ends first (not a per-frame call)
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    if (level == c->in.dn_level) return VP8HIP_OK;
     if (level) { const int rc = c->dn.make(c, 256, 256); if (rc) return rc; }
-    c->dn_level = level;
+    IntakeSettings next = c->in;
+    next.dn_level = level;
+    { const int rc = intake_apply(c, next); if (rc) return rc; }
     c->dn_have_history = false;
     c->dn_taken = false;
     return VP8HIP_OK;
@@ -55,7 +55,7 @@ int vp8hip_denoise_restart(vp8hip_ctx *c) {
 int vp8hip_denoise_result(vp8hip_ctx *c, vp8hip_denoise_stats *s) {
     USE_DEVICE_ONLY(c);
     if (!c || !s) return VP8HIP_ERR_ARG;
-    if (!c->dn_level || !c->dn_taken) return VP8HIP_ERR_STATE;
+    if (!c->in.dn_level || !c->dn_taken) return VP8HIP_ERR_STATE;
     DenoiseMirror m = c->dn_passed;
     if (!c->dn_host) {
         const int rc = c->dn.wait(c);

@@ -56,13 +56,13 @@ int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, cons
 
 int copy_planes(vp8hip_ctx *c, uint8_t *d, const void *y, const void *u, const void *v, const size_t nb[3], hipMemcpyKind kind, hipStream_t s) {
     const uint8_t *py = static_cast<const uint8_t *>(y);
-    if (c->win_on) {      // y, u, v: the plane bases of a surface; the window's rows, tight, and nothing else
+    if (c->in.win_on) {      // y, u, v: the plane bases of a surface; the window's rows, tight, and nothing else
         size_t off[3];
         int32_t rb[3], rows[3];
         if (window_rule(c, off, rb, rows) != 0) return VP8HIP_ERR_ARG;
         const uint8_t *src[3] = {py, static_cast<const uint8_t *>(u), static_cast<const uint8_t *>(v)};
         for (int p = 0; p < 3; ++p) {
-            if (rows[p]) HIPCHK(c, hipMemcpy2DAsync(d, (size_t)rb[p], src[p] + off[p], (size_t)c->win_pitch[p], (size_t)rb[p], (size_t)rows[p], kind, s));
+            if (rows[p]) HIPCHK(c, hipMemcpy2DAsync(d, (size_t)rb[p], src[p] + off[p], (size_t)c->in.win_pitch[p], (size_t)rb[p], (size_t)rows[p], kind, s));
             d += nb[p];
         }
         return VP8HIP_OK;
@@ -77,35 +77,46 @@ int copy_planes(vp8hip_ctx *c, uint8_t *d, const void *y, const void *u, const v
     return VP8HIP_OK;
 }
 
-// vp8hip_set_source_format: the converter's output buffer at the context's incoming size (no-op for I420 or when it is large enough)
-static int format_stage_ready(vp8hip_ctx *c) {
-    if (!c->src_fmt) return VP8HIP_OK;
-    int w, h;
-    incoming_size(c, &w, &h);
-    return c->fmt_stage.grow(c, tight_i420(w, h).bytes);
-}
-
-// the item of k_convert_b for planes in DEVICE memory: afterwards y, u, v are the I420 planes in fmt_stage.  false: I420, nothing to do.
-static bool convert_item(vp8hip_ctx *c, ConvertItem &it, const void *&y, const void *&u, const void *&v) {
-    if (!c->src_fmt) return false;
-    int w, h;
-    incoming_size(c, &w, &h);
-    const TightI420 t = tight_i420(w, h);
+// the item of a stage that writes a member's three planes into a staging buffer of its own, plane p at stage + at[p] (k_window_b,
+// k_convert_b / k_tonemap_b, k_orient_b): afterwards y, u, v are the planes there, and what follows reads those
+static void planes_item(PlanesItem &it, uint8_t *stage, const size_t at[3], const void *&y, const void *&u, const void *&v) {
     const void *src[3] = {y, u, v};
     for (int p = 0; p < 3; ++p) {
         it.src[p] = static_cast<const uint8_t *>(src[p]);
-        it.dst[p] = c->fmt_stage.p + t.off[p];
+        it.dst[p] = stage + at[p];
     }
     y = it.dst[0]; u = it.dst[1]; v = it.dst[2];
-    return true;
 }
 
 int intake_ready(vp8hip_ctx *const *m, int n) {
-    for (int i = 0; i < n; ++i) {
-        int rc = format_stage_ready(m[i]);
-        if (!rc) rc = deinterlace_ready(m[i]);
-        if (!rc) rc = geometry_ready(m[i]);
+    for (int i = 0; i < n; ++i) {      // (first use, or the incoming size has grown: not a per-frame event)
+        vp8hip_ctx *c = m[i];
+        if (!needs_device_planes(c->in)) continue;      // (no stage in front of the pack: no staging buffer)
+        int w, h;
+        size_t nb[3];
+        incoming_size(c, &w, &h);
+        incoming_bytes(c, nb);
+        const size_t tight = tight_i420(w, h).bytes;
+        int rc = c->in.src_fmt ? c->fmt_stage.grow(c, tight) : VP8HIP_OK;      // the converter's output
+        if (!rc) rc = deinterlace_ready(c);
+        if (!rc && c->in.win_on) rc = c->win_stage.grow(c, nb[0] + nb[1] + nb[2]);      // the window's tight planes, laid out as raw_stage
+        if (!rc && (c->in.or_turns || c->in.or_mirror)) rc = c->or_stage.grow(c, tight);      // the upright frame (the same bytes for w x h and h x w)
         if (rc) return rc;
+    }
+    return VP8HIP_OK;
+}
+
+int intake_apply(vp8hip_ctx *c, const IntakeSettings &next) {
+    if (next == c->in) return VP8HIP_OK;
+    if (intake_valid(c->W, c->H, next) != VP8HIP_OK) return VP8HIP_ERR_ARG;
+    // a launch still in flight reads the staging buffers, the tables and the histories and writes the records: it ends first
+    { const int rc = quiesce_intake(c); if (rc) return rc; }
+    const IntakeSettings before = c->in;
+    c->in = next;
+    { const int rc = intake_ready(&c, 1); if (rc) { c->in = before; return rc; } }
+    if (!(static_cast<const SourceShape &>(next) == before)) {      // planes prefetched under another shape are not this shape's frame
+        c->h2d_pre_valid = false;
+        if (c->batch) c->batch->pre_valid = false;
     }
     return VP8HIP_OK;
 }
@@ -113,53 +124,58 @@ int intake_ready(vp8hip_ctx *const *m, int n) {
 int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u, const void *const *v, int n, hipStream_t s,
                 const hipMemcpyKind *alone, hipEvent_t planes_read, bool tight) {
     vp8hip_ctx *c0 = m[0];
+    const IntakeSettings &in = c0->in;      // (same_intake: every member's)
     { const int rc = intake_ready(m, n); if (rc) return rc; }
     SourceItem src[MAX_BATCH];
-    ConvertItem cv[MAX_BATCH];
+    PlanesItem wn[MAX_BATCH], cv[MAX_BATCH], orn[MAX_BATCH];
     DeinterlaceItem di[MAX_BATCH];
-    GeometryItem wn[MAX_BATCH], orn[MAX_BATCH];
-    const bool window = c0->win_on && !tight;      // (planes that came from the host are the window already: copy_planes)
+    const bool window = in.win_on && !tight;      // (planes that came from the host are the window already: copy_planes)
+    const bool orient = in.or_turns || in.or_mirror;
+    int w, h;
+    size_t nb[3];
+    incoming_size(c0, &w, &h);      // (the raw size: what the window, the converter and the deinterlacer work at)
+    incoming_bytes(c0, nb);
+    const size_t raw_at[3] = {0, nb[0], nb[0] + nb[1]};      // the raw planes end to end
+    const TightI420 t = tight_i420(w, h);                    // tight I420 of the raw size (the same offsets for w x h and h x w)
     for (int i = 0; i < n; ++i) {
         next_current(m[i]);
         src[i] = SourceItem{&m[i]->cur, y[i], u[i], v[i], &m[i]->scale};
-        if (window) (void)window_item(m[i], wn[i], src[i].y, src[i].u, src[i].v);      // (a window: what follows reads the member's tight planes)
-        convert_item(m[i], cv[i], src[i].y, src[i].u, src[i].v);      // (a source format: what follows reads the member's converted planes)
-        (void)deinterlace_item(m[i], s, di[i], src[i].y, src[i].u, src[i].v);      // (a deinterlacer: ... the member's deinterlaced planes; same_intake: all or none)
-        (void)orient_item(m[i], orn[i], src[i].y, src[i].u, src[i].v);      // (an orientation: ... the member's upright planes)
+        if (window) planes_item(wn[i], m[i]->win_stage.p, raw_at, src[i].y, src[i].u, src[i].v);      // (a window: what follows reads the member's tight planes)
+        if (in.src_fmt) planes_item(cv[i], m[i]->fmt_stage.p, t.off, src[i].y, src[i].u, src[i].v);      // (a source format: ... the member's converted planes)
+        (void)deinterlace_item(m[i], s, di[i], src[i].y, src[i].u, src[i].v);      // (a deinterlacer: ... the member's deinterlaced planes)
+        if (orient) planes_item(orn[i], m[i]->or_stage.p, t.off, src[i].y, src[i].u, src[i].v);      // (an orientation: ... the member's upright planes)
     }
-    int w, h;
-    incoming_size(c0, &w, &h);      // (the raw size: what the window, the converter and the deinterlacer work at)
     if (window) {      // one launch for all members, in front of everything else
         Timed t(c0, VP8HIP_K_PACK);
         size_t off[3];
         int32_t rb[3], rows[3];
         if (window_rule(c0, off, rb, rows) != 0) return VP8HIP_ERR_ARG;
-        launch_window_batch(s, off, c0->win_pitch, rb, rows, wn, n);
+        launch_window_batch(s, off, in.win_pitch, rb, rows, wn, n);
     }
-    if (c0->src_fmt) {      // one launch for all members, in front of the pack or scale launch
+    if (in.src_fmt) {      // one launch for all members, in front of the pack or scale launch
         Timed t(c0, VP8HIP_K_PACK);     // (the input side's stage: a profile counts this launch and the pack or scale launch behind it)
-        if (c0->src_transfer) {     // (same_intake: one transfer and peak, so the first member's tables are every member's)
-            if (!launch_tonemap_batch(s, c0->src_fmt, c0->src_colour, w, h, reinterpret_cast<const uint32_t *>(c0->tm_tables.p), cv, n)) return VP8HIP_ERR_ARG;
-        } else if (!launch_convert_batch(s, c0->src_fmt, c0->src_colour, w, h, cv, n)) return VP8HIP_ERR_ARG;
+        if (in.src_transfer) {     // (same_intake: one transfer and peak, so the first member's tables are every member's)
+            if (!launch_tonemap_batch(s, in.src_fmt, in.src_colour, w, h, reinterpret_cast<const uint32_t *>(c0->tm_tables.p), cv, n)) return VP8HIP_ERR_ARG;
+        } else if (!launch_convert_batch(s, in.src_fmt, in.src_colour, w, h, cv, n)) return VP8HIP_ERR_ARG;
     }
-    if (c0->di_mode) {      // ... behind the converter and in front of the pack or scale launch
+    if (in.di_mode) {      // ... behind the converter and in front of the pack or scale launch
         Timed t(c0, VP8HIP_K_PACK);
-        launch_deinterlace_batch(s, w, h, c0->di_keep, di, n);
+        launch_deinterlace_batch(s, w, h, in.di_keep, di, n);
     }
-    if (c0->or_turns || c0->or_mirror) {      // ... behind the deinterlacer (fields are rows of the source) and in front of the pack or scale launch
+    if (orient) {      // ... behind the deinterlacer (fields are rows of the source) and in front of the pack or scale launch
         Timed t(c0, VP8HIP_K_PACK);
-        launch_orient_batch(s, c0->or_turns, c0->or_mirror, w, h, orn, n);
+        launch_orient_batch(s, in.or_turns, in.or_mirror, w, h, orn, n);
     }
-    if (c0->scale.in_w) {      // a frame that is scaled is not packed as well
+    if (in.in_w) {      // a frame that is scaled is not packed as well
         Timed t(c0, VP8HIP_K_PACK);
         launch_scale_batch(s, src, n);
     } else if (alone) {        // (s is the context's stream: the launch of one, or planes from the host straight into the surface)
-        const int rc = set_frame_planes(c0, c0->cur, src[0].y, src[0].u, src[0].v, *alone, c0->src_w, c0->src_h);
+        const int rc = set_frame_planes(c0, c0->cur, src[0].y, src[0].u, src[0].v, *alone, in.src_w, in.src_h);
         if (rc) return rc;
     } else {
         Timed t(c0, VP8HIP_K_PACK);
         static const bool skip = experiment_skip("pack");      // timing experiment only: the batches' pack
-        if (!skip) launch_pack_batch(s, src, n, c0->src_w, c0->src_h);
+        if (!skip) launch_pack_batch(s, src, n, in.src_w, in.src_h);
     }
     if (planes_read) HIPCHK(c0, hipEventRecord(planes_read, s));
     {   // vp8hip_set_overlay_*: the members that have layers, in one launch behind the pack or scale launch and IN FRONT of the denoiser,
@@ -180,7 +196,7 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
         int nd = 0;
         for (int i = 0; i < n; ++i)
             if (denoise_item(m[i], s, dn[nd])) ++nd;
-        launch_denoise_batch(s, dn, nd, c0->dn_level);
+        launch_denoise_batch(s, dn, nd, in.dn_level);
     }
     {   // vp8hip_set_analysis: the members' source sides in one launch behind the denoiser (the frame as the searches will read it)
         AnalysisSrcItem an[MAX_BATCH];
@@ -196,7 +212,7 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
             if (aq_item(m[i], aq[nq])) ++nq;
         if (nq) {      // (two launches of the input side's stage, each with its own pair of events)
             { Timed t(c0, VP8HIP_K_PACK); launch_aq_map_batch(s, aq, nq); }
-            { Timed t(c0, VP8HIP_K_PACK); launch_aq_seg_batch(s, aq, nq, c0->seg_strength); }
+            { Timed t(c0, VP8HIP_K_PACK); launch_aq_seg_batch(s, aq, nq, in.seg_strength); }
         }
     }
     return VP8HIP_OK;
@@ -206,7 +222,7 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
 // and the window of a surface in host memory, pass through raw_stage first (a frame larger than the surface cannot be copied into the
 // surface).  tight: planes in device memory that are the window already (a prefetch's).
 static int take_current(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMemcpyKind kind, hipEvent_t planes_read = nullptr, bool tight = false) {
-    if (kind != hipMemcpyDeviceToDevice && (c->src_fmt || c->di_mode || c->scale.in_w || c->win_on || c->or_turns || c->or_mirror)) {
+    if (kind != hipMemcpyDeviceToDevice && needs_device_planes(c->in)) {
         size_t nb[3];
         incoming_bytes(c, nb);
         int rc = c->raw_stage.grow(c, nb[0] + nb[1] + nb[2]);
@@ -294,108 +310,84 @@ int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const
     return take_current(c, y, u, v, hipMemcpyDeviceToDevice);
 }
 
-// dst of a scaler, or the source size: even, not above the coded size and fewer than 16 below it
-static bool source_size_ok(const vp8hip_ctx *c, int w, int h) {
-    return w > 0 && h > 0 && !(w & 1) && !(h & 1) && w <= c->W && h <= c->H && c->W - w < 16 && c->H - h < 16;
-}
-static void set_source(vp8hip_ctx *c, int w, int h, int in_w, int in_h, int kind) {
-    const bool same = w == c->W && h == c->H;
-    w = same ? 0 : w;
-    h = same ? 0 : h;
-    // planes prefetched at another incoming size are not this size's frame
-    if (w != c->src_w || h != c->src_h || in_w != c->scale.in_w || in_h != c->scale.in_h) c->h2d_pre_valid = false;
-    c->src_w = w;
-    c->src_h = h;
-    c->scale.in_w = in_w;
-    c->scale.in_h = in_h;
-    c->scale.kind = kind;
-}
-
 int vp8hip_set_source_size(vp8hip_ctx *c, int src_width, int src_height) {
     if (!c) return VP8HIP_ERR_ARG;
-    if (src_width == 0 && src_height == 0) {
-        if (!geometry_allows(c, c->src_fmt, c->W, c->H, c->or_turns)) return VP8HIP_ERR_ARG;
-        set_source(c, 0, 0, 0, 0, 0);
-        return VP8HIP_OK;
+    IntakeSettings next = c->in;      // (a source size takes the scaler out)
+    next.src_w = src_width;
+    next.src_h = src_height;
+    next.in_w = next.in_h = 0;
+    const int rc = intake_apply(c, canonical(next, c->W, c->H));
+    if (!rc && c->scale.d_blob) {      // (nothing in flight reads the tables: intake_apply has waited) the plan goes with the scaler
+        (void)hipFree(c->scale.d_blob);
+        c->scale = ScalePlan{};
     }
-    // (the deinterlacer needs a row of each field in every plane, and a window in force must fit its pitch at the new size)
-    if (!source_size_ok(c, src_width, src_height) || !geometry_allows(c, c->src_fmt, src_width, src_height, c->or_turns)) return VP8HIP_ERR_ARG;
-    set_source(c, src_width, src_height, 0, 0, 0);
-    return VP8HIP_OK;
+    return rc;
 }
 
 int vp8hip_set_source_scaling(vp8hip_ctx *c, int in_width, int in_height, int dst_width, int dst_height, int filter) {
     if (!c) return VP8HIP_ERR_ARG;
     if (!in_width && !in_height && !dst_width && !dst_height) return vp8hip_set_source_size(c, 0, 0);
-    if (!source_size_ok(c, dst_width, dst_height) || (filter != 0 && filter != 1) || (in_width & 1) || (in_height & 1) ||
-        in_width < dst_width || in_height < dst_height || in_width > 16384 || in_height > 16384 || !geometry_allows(c, c->src_fmt, in_width, in_height, c->or_turns))
-        return VP8HIP_ERR_ARG;
+    if (in_width <= 0 || in_height <= 0 || !source_size_ok(c->W, c->H, dst_width, dst_height)) return VP8HIP_ERR_ARG;
+    IntakeSettings next = c->in;
+    next.src_w = dst_width;
+    next.src_h = dst_height;
+    next.in_w = in_width;
+    next.in_h = in_height;
+    next.scale_kind = filter;
+    next = canonical(next, c->W, c->H);
+    if (intake_valid(c->W, c->H, next) != VP8HIP_OK) return VP8HIP_ERR_ARG;      // (here too: the plan below is made of arguments that passed)
     if (in_width == dst_width && in_height == dst_height) return vp8hip_set_source_size(c, dst_width, dst_height);
+    if (next == c->in) return VP8HIP_OK;
     // everything that can be refused is tried before anything of the context changes
     ScalePlan plan;
     std::vector<uint8_t> blob;
     if (!scale_plan_make(&plan, in_width, in_height, dst_width, dst_height, c->W, c->H, filter, blob)) return VP8HIP_ERR_ARG;
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
-    uint8_t *d_blob = nullptr;
-    HIPCHK(c, hipMalloc(&d_blob, blob.size()));
-    const hipError_t e = hipMemcpy(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
-    (void)hipFree(c->scale.d_blob);
-    set_source(c, dst_width, dst_height, in_width, in_height, filter);
-    plan.d_blob = d_blob;
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, hipMalloc(&plan.d_blob, blob.size()));
+    const hipError_t e = hipMemcpy(plan.d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(plan.d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
+    const int rc = intake_apply(c, next);
+    if (rc) { (void)hipFree(plan.d_blob); return rc; }
+    (void)hipFree(c->scale.d_blob);      // (nothing in flight reads the old tables: intake_apply has waited)
     c->scale = plan;
     return VP8HIP_OK;
 }
 
-// the combinations of a transfer and a format the tone-mapping rule covers: it reads P010 and I010, and I420 frames pass it by
-static bool transfer_allows(int transfer, int format) {
-    return !transfer || format == VP8HOST_FORMAT_I420 || format == VP8HOST_FORMAT_P010 || format == VP8HOST_FORMAT_I010;
-}
-
 int vp8hip_set_source_transfer(vp8hip_ctx *c, int transfer, int peak) {
-    if (!c || (transfer != VP8HOST_TRANSFER_SDR && transfer != VP8HOST_TRANSFER_PQ && transfer != VP8HOST_TRANSFER_HLG)) return VP8HIP_ERR_ARG;
-    if (transfer == VP8HOST_TRANSFER_SDR) peak = 0;      // (off has no peak)
-    else if (peak < VP8HOST_PEAK_MIN || peak > VP8HOST_PEAK_MAX || !transfer_allows(transfer, c->src_fmt)) return VP8HIP_ERR_ARG;
-    if (transfer == c->src_transfer && peak == c->src_peak) return VP8HIP_OK;
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
-    if (transfer) {      // everything that can fail before anything of the context changes
+    if (!c) return VP8HIP_ERR_ARG;
+    IntakeSettings next = c->in;
+    next.src_transfer = transfer;
+    next.src_peak = peak;      // (off has no peak: canonical)
+    next = canonical(next, c->W, c->H);
+    if (next == c->in) return VP8HIP_OK;
+    DeviceBuf tables;      // the new transfer's, in a buffer of their own: a launch in flight reads the old ones, and a refusal keeps them
+    if (next.src_transfer) {
         std::vector<uint8_t> t(TONEMAP_TABLE_BYTES);
         uint32_t *lin = reinterpret_cast<uint32_t *>(t.data());
         if (vp8host_tonemap_tables(transfer, peak, lin, lin + 4096, t.data() + 32768, t.data() + 36864) != 0) return VP8HIP_ERR_ARG;
-        { const int rc = c->tm_tables.grow(c, t.size()); if (rc) return rc; }
-        HIPCHK(c, hipMemcpy(c->tm_tables.p, t.data(), t.size(), hipMemcpyHostToDevice));
-    } else {
-        c->tm_tables.release();
+        { const int rc = tables.grow(c, t.size()); if (rc) return rc; }
+        const hipError_t e = hipMemcpy(tables.p, t.data(), t.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { tables.release(); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
     }
-    c->src_transfer = transfer;
-    c->src_peak = peak;
-    c->h2d_pre_valid = false;      // planes prefetched under another transfer are not this transfer's frame
-    if (c->batch) c->batch->pre_valid = false;
+    const int rc = intake_apply(c, next);
+    if (rc) { tables.release(); return rc; }
+    c->tm_tables.release();      // (nothing in flight reads them: intake_apply has waited)
+    c->tm_tables = tables;
     return VP8HIP_OK;
 }
 
 int vp8hip_set_source_format(vp8hip_ctx *c, int format) {
-    if (!c || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END)
-        return VP8HIP_ERR_ARG;
-    if (format == c->src_fmt) return VP8HIP_OK;
-    if (!transfer_allows(c->src_transfer, format)) return VP8HIP_ERR_ARG;      // (a transfer in force: P010, I010, or back to I420)
-    { int w, h; upright_size(c, &w, &h); if (!geometry_allows(c, format, w, h, c->or_turns)) return VP8HIP_ERR_ARG; }      // (a window in force: its pitches under the new format)
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
-    const int before = c->src_fmt;
-    c->src_fmt = format;
-    { const int rc = format_stage_ready(c); if (rc) { c->src_fmt = before; return rc; } }
-    c->h2d_pre_valid = false;      // planes prefetched in another format are not this format's frame
-    return VP8HIP_OK;
+    if (!c) return VP8HIP_ERR_ARG;
+    IntakeSettings next = c->in;      // (a transfer in force: P010, I010, or back to I420; a window in force: its pitches under the new format)
+    next.src_fmt = format;
+    return intake_apply(c, next);
 }
 
 int vp8hip_set_source_colour(vp8hip_ctx *c, int matrix) {
-    if (!c || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT) return VP8HIP_ERR_ARG;
-    if (matrix == c->src_colour) return VP8HIP_OK;
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
-    c->src_colour = matrix;
-    c->h2d_pre_valid = false;      // planes prefetched under another matrix are not this matrix's frame
-    if (c->batch) c->batch->pre_valid = false;
-    return VP8HIP_OK;
+    if (!c) return VP8HIP_ERR_ARG;
+    IntakeSettings next = c->in;
+    next.src_colour = matrix;
+    return intake_apply(c, next);
 }
 
 }  // extern "C"

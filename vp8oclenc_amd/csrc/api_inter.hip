@@ -232,7 +232,7 @@ int vp8hip_inter_transform(vp8hip_ctx *c, int prev_is_golden, int prev_is_altref
     {
         Timed t(c, VP8HIP_K_MB);   // select_reference + pack_8x8_into_16x16 run inside
         const CodingItem it = coding_item(c, use_golden, use_altref);
-        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0, c->seg_mode != 0);
+        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0, c->in.seg_mode != 0);
     }
     recon_made(c, false);
     HIPCHK(c, hipGetLastError());
@@ -264,7 +264,7 @@ int vp8hip_inter_finish(vp8hip_ctx *c, int use_golden, int use_altref) {
     {
         Timed t(c, VP8HIP_K_MB);
         const CodingItem it = coding_item(c, use_golden, use_altref);
-        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0, c->seg_mode != 0);
+        launch_mb_batch(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant != 0, c->in.seg_mode != 0);
     }
     recon_made(c, false);
     HIPCHK(c, hipGetLastError());

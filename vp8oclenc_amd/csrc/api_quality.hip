@@ -19,7 +19,8 @@ bool quality_item(vp8hip_ctx *c, const Frame &rec, hipStream_t s, QualityArgs &a
     if (!c->quality_on) return false;
     // (with vp8hip_set_source_scaling the source size is what the frames are scaled TO and c->cur holds the scaled frame: the codec's
     // error is measured, not the scaler's)
-    const int w = c->src_w ? c->src_w : c->W, h = c->src_h ? c->src_h : c->H;
+    int w, h;
+    picture_size(c, &w, &h);
     a = quality_args(c->cur, rec, w, h);
     a.partial = quality_partial(c);
     a.ticket = quality_ticket(c);

@@ -43,7 +43,7 @@ int set_map(vp8hip_ctx *c, const uint8_t *map, hipMemcpyKind kind) {
 }  // namespace
 
 bool aq_item(vp8hip_ctx *c, AqItem &it) {
-    if (c->seg_mode != 2) return false;
+    if (c->in.seg_mode != 2) return false;
     const int frame = c->cur_count - 1, k = frame & 1;
     it.cur = c->cur.Y[0];
     it.e = aq_e(c, k);
@@ -54,8 +54,8 @@ bool aq_item(vp8hip_ctx *c, AqItem &it) {
 }
 
 const uint8_t *segment_map_in_force(const vp8hip_ctx *c) {
-    if (c->seg_mode == 1) return c->seg_map_set ? caller_map(c) : nullptr;
-    if (c->seg_mode != 2) return nullptr;
+    if (c->in.seg_mode == 1) return c->seg_map_set ? caller_map(c) : nullptr;
+    if (c->in.seg_mode != 2) return nullptr;
     const int frame = c->cur_count - 1;
     return frame >= 0 && c->aq_frame[frame & 1] == frame ? aq_map(c, frame & 1) : nullptr;   // (a frame taken in before mode 2 was set has no map)
 }
@@ -68,14 +68,15 @@ int vp8hip_set_segment_mode(vp8hip_ctx *c, int mode, int strength) {
     if (!c || mode < 0 || mode > 2 || (mode == 2 && (strength < 1 || strength > 3))) return VP8HIP_ERR_ARG;
     USE_DEVICE(c);
     if (mode) { const int rc = segment_refusal(c); if (rc) return rc; }
-    strength = mode == 2 ? strength : 0;
-    if (mode == c->seg_mode && strength == c->seg_strength) return VP8HIP_OK;
+    IntakeSettings next = c->in;
+    next.seg_mode = mode;
+    next.seg_strength = strength;      // (mode 2's: canonical)
+    next = canonical(next, c->W, c->H);
+    if (next == c->in) return VP8HIP_OK;
     // a launch still in flight writes the maps and the sum words: it ends first (not a per-frame call)
     JOIN_LF(c);
-    { const int rc = quiesce_intake(c); if (rc) return rc; }
     if (mode) { const int rc = segment_buffers(c); if (rc) return rc; }
-    c->seg_mode = mode;
-    c->seg_strength = strength;
+    { const int rc = intake_apply(c, next); if (rc) return rc; }
     c->aq_frame[0] = c->aq_frame[1] = -1;
     return VP8HIP_OK;
 }
@@ -99,17 +100,17 @@ int vp8hip_upload_segment_map(vp8hip_ctx *c, const uint8_t *host_map) {
 
 int vp8hip_segment_mode(const vp8hip_ctx *c, int *mode, int *strength) {
     if (!c) return VP8HIP_ERR_ARG;
-    if (mode) *mode = c->seg_mode;
-    if (strength) *strength = c->seg_strength;
+    if (mode) *mode = c->in.seg_mode;
+    if (strength) *strength = c->in.seg_strength;
     return VP8HIP_OK;
 }
 
 int vp8hip_download_segment_map(vp8hip_ctx *c, uint8_t *map_out, uint8_t *e_out) {
     if (!c || !map_out) return VP8HIP_ERR_ARG;
     USE_DEVICE(c);
-    if (!c->seg_mode || (e_out && c->seg_mode != 2)) return VP8HIP_ERR_STATE;
+    if (!c->in.seg_mode || (e_out && c->in.seg_mode != 2)) return VP8HIP_ERR_STATE;
     const uint8_t *map = segment_map_in_force(c);
-    if (c->seg_mode == 2 && !map) return VP8HIP_ERR_STATE;
+    if (c->in.seg_mode == 2 && !map) return VP8HIP_ERR_STATE;
     // (the intake of a batch's member may be on the batch's head-of-frame stream: USE_DEVICE has joined it)
     if (map) HIPCHK(c, hipMemcpyAsync(map_out, map, (size_t)c->mbs, hipMemcpyDeviceToHost, c->stream));
     else memset(map_out, 3, (size_t)c->mbs);

@@ -175,7 +175,7 @@ int vp8hip_shard_unique_id(uint8_t id[VP8HIP_SHARD_ID_BYTES]) {
 int vp8hip_shard_init(vp8hip_ctx *c, const uint8_t id[VP8HIP_SHARD_ID_BYTES], int rank, int world) {
     USE_DEVICE(c);
     if (!c || !id || world < 1 || world > 3 || rank < 0 || rank >= world) return VP8HIP_ERR_ARG;
-    if (c->shard_comm || c->batch || c->an_on || c->seg_mode || c->ov_count) return VP8HIP_ERR_STATE;      // (vp8hip_set_analysis, vp8hip_set_segment_mode, vp8hip_set_overlay_*: not for shard contexts)
+    if (c->shard_comm || c->batch || excludes_shard(c->in) || c->ov_count) return VP8HIP_ERR_STATE;      // (vp8hip_set_analysis, vp8hip_set_segment_mode, vp8hip_set_overlay_*: not for shard contexts)
     const Rccl *r = rccl();
     if (!r) return VP8HIP_ERR_HIP;
     ncclUniqueId u;

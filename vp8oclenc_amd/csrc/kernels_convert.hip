@@ -120,7 +120,7 @@ template <int K> __device__ __forceinline__ uint8_t finish1(int S) {
     return (uint8_t)(o > 255 ? 255 : o);
 }
 
-template <int LAYOUT, int DEPTH> __device__ __forceinline__ void convert_body(const ConvertItem &it, const Geo &g) {
+template <int LAYOUT, int DEPTH> __device__ __forceinline__ void convert_body(const PlanesItem &it, const Geo &g) {
     constexpr bool TOP = LAYOUT == NV;                      // (of the two-plane formats only P010 has words)
     constexpr int B = DEPTH == 8 ? 1 : 2;                   // bytes per sample
     constexpr int KY = DEPTH - 8;
@@ -260,7 +260,7 @@ __device__ __forceinline__ void rgb_store16(const uint32_t a[16], const uint32_t
     store8(ov, v[0], v[1]);
 }
 
-template <bool RGB> __device__ __forceinline__ void packed_body(const ConvertItem &it, const PackedArgs &g) {
+template <bool RGB> __device__ __forceinline__ void packed_body(const PlanesItem &it, const PackedArgs &g) {
     constexpr int B = RGB ? 4 : 2;            // bytes per pixel
     const int unit = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (unit >= g.units) return;
@@ -361,7 +361,7 @@ __device__ __forceinline__ uint32_t tm_pixel(int y10, const TmChroma &c, const u
     return B | (G << 8) | (R << 16);
 }
 
-template <bool TOP> __device__ __forceinline__ void tonemap_body(const ConvertItem &it, const PackedArgs &g, const uint32_t *tab) {
+template <bool TOP> __device__ __forceinline__ void tonemap_body(const PlanesItem &it, const PackedArgs &g, const uint32_t *tab) {
     const int unit = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (unit >= g.units) return;
     const int r = unit / g.units_x, ux = unit - r * g.units_x, cw = g.w >> 1;
@@ -415,9 +415,9 @@ template <bool TOP> __device__ __forceinline__ void tonemap_body(const ConvertIt
 
 }  // namespace convert
 
-static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::PackedArgs) + sizeof(void *) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+static_assert(sizeof(BatchOf<PlanesItem>) + sizeof(convert::PackedArgs) + sizeof(void *) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
 // tables: convert::TM_TABLE_BYTES of the context's device buffer (lin, gain, lo, hi end to end), 16-byte aligned
-template <bool TOP> __global__ __launch_bounds__(256) void k_tonemap_b(BatchOf<ConvertItem> b, convert::PackedArgs g, const uint32_t *tables) {
+template <bool TOP> __global__ __launch_bounds__(256) void k_tonemap_b(BatchOf<PlanesItem> b, convert::PackedArgs g, const uint32_t *tables) {
     __shared__ convert::u32x4 tab[convert::TM_TABLE_BYTES / 16];
     for (int i = (int)threadIdx.x; i < convert::TM_TABLE_BYTES / 16; i += 256) tab[i] = reinterpret_cast<const convert::u32x4 *>(tables)[i];
     __syncthreads();      // (in front of every return: all 256 lanes arrive)
@@ -443,10 +443,10 @@ static bool rgb_matrix_args(int format, int matrix, convert::PackedArgs &g) {
     return true;
 }
 
-bool launch_tonemap_batch(hipStream_t s, int format, int matrix, int w, int h, const uint32_t *tables, const ConvertItem *items, int n) {
+bool launch_tonemap_batch(hipStream_t s, int format, int matrix, int w, int h, const uint32_t *tables, const PlanesItem *items, int n) {
     if (n <= 0) return true;
     if ((format != VP8HOST_FORMAT_P010 && format != VP8HOST_FORMAT_I010) || !tables) return false;      // (the setters refuse it: the caller fails the frame)
-    BatchOf<ConvertItem> b;
+    BatchOf<PlanesItem> b;
     b.n = n;
     for (int i = 0; i < n; ++i) b.item[i] = items[i];
     convert::PackedArgs g = {};
@@ -460,12 +460,12 @@ bool launch_tonemap_batch(hipStream_t s, int format, int matrix, int w, int h, c
     return true;
 }
 
-static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::PackedArgs) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
-template <bool RGB> __global__ __launch_bounds__(256) void k_convert_packed_b(BatchOf<ConvertItem> b, convert::PackedArgs g) {
+static_assert(sizeof(BatchOf<PlanesItem>) + sizeof(convert::PackedArgs) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+template <bool RGB> __global__ __launch_bounds__(256) void k_convert_packed_b(BatchOf<PlanesItem> b, convert::PackedArgs g) {
     convert::packed_body<RGB>(b.item[blockIdx.z], g);
 }
 
-static bool launch_convert_packed(hipStream_t s, int format, int matrix, int w, int h, const BatchOf<ConvertItem> &b) {
+static bool launch_convert_packed(hipStream_t s, int format, int matrix, int w, int h, const BatchOf<PlanesItem> &b) {
     convert::PackedArgs g = {};
     g.w = w; g.h = h;
     g.units_x = w < 16 ? 1 : (w + 15) / 16;
@@ -486,14 +486,14 @@ static bool launch_convert_packed(hipStream_t s, int format, int matrix, int w, 
     return true;
 }
 
-static_assert(sizeof(BatchOf<ConvertItem>) + sizeof(convert::Geo) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
-template <int LAYOUT, int DEPTH> __global__ __launch_bounds__(256) void k_convert_b(BatchOf<ConvertItem> b, convert::Geo g) {
+static_assert(sizeof(BatchOf<PlanesItem>) + sizeof(convert::Geo) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+template <int LAYOUT, int DEPTH> __global__ __launch_bounds__(256) void k_convert_b(BatchOf<PlanesItem> b, convert::Geo g) {
     convert::convert_body<LAYOUT, DEPTH>(b.item[blockIdx.z], g);
 }
 
-bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const ConvertItem *items, int n) {
+bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const PlanesItem *items, int n) {
     if (n <= 0 || format == VP8HOST_FORMAT_I420) return true;
-    BatchOf<ConvertItem> b;
+    BatchOf<PlanesItem> b;
     b.n = n;
     for (int i = 0; i < n; ++i) b.item[i] = items[i];
     if (format >= VP8HOST_FORMAT_PACKED_FIRST && format < VP8HOST_FORMAT_PACKED_END) return launch_convert_packed(s, format, matrix, w, h, b);

@@ -55,7 +55,7 @@ struct WindowGeo {
     int pitch[3], row_bytes[3], rows[3], sx[3], units[3];      // sx: strips of 16 bytes per row; units = sx * rows
 };
 
-__device__ __forceinline__ void window_body(const GeometryItem &it, const WindowGeo &g) {
+__device__ __forceinline__ void window_body(const PlanesItem &it, const WindowGeo &g) {
     int unit = (int)blockIdx.x * 256 + (int)threadIdx.x, p = 0;
     if (unit >= g.units[0]) {
         unit -= g.units[0];
@@ -142,7 +142,7 @@ __device__ __forceinline__ void transpose_tile(const uint8_t *src, uint8_t *dst,
     }
 }
 
-__device__ __forceinline__ void orient_body(const GeometryItem &it, const OrientGeo &g, uint32_t *tile) {
+__device__ __forceinline__ void orient_body(const PlanesItem &it, const OrientGeo &g, uint32_t *tile) {
     int block = (int)blockIdx.x, plane = 0;      // (uniform in the workgroup: every lane reaches the barrier or none does)
     if (block >= g.y.blocks) {
         block -= g.y.blocks;
@@ -156,18 +156,18 @@ __device__ __forceinline__ void orient_body(const GeometryItem &it, const Orient
 
 }  // namespace geometry
 
-static_assert(sizeof(BatchOf<GeometryItem>) + sizeof(geometry::WindowGeo) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
-__global__ __launch_bounds__(256) void k_window_b(BatchOf<GeometryItem> b, geometry::WindowGeo g) { geometry::window_body(b.item[blockIdx.z], g); }
+static_assert(sizeof(BatchOf<PlanesItem>) + sizeof(geometry::WindowGeo) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
+__global__ __launch_bounds__(256) void k_window_b(BatchOf<PlanesItem> b, geometry::WindowGeo g) { geometry::window_body(b.item[blockIdx.z], g); }
 
-__global__ __launch_bounds__(256) void k_orient_b(BatchOf<GeometryItem> b, geometry::OrientGeo g) {
+__global__ __launch_bounds__(256) void k_orient_b(BatchOf<PlanesItem> b, geometry::OrientGeo g) {
     __shared__ uint32_t tile[geometry::TILE * geometry::TILE_PITCH];
     geometry::orient_body(b.item[blockIdx.z], g, tile);
 }
 
 void launch_window_batch(hipStream_t s, const size_t offset[3], const int32_t pitch[3], const int32_t row_bytes[3], const int32_t rows[3],
-                         const GeometryItem *items, int n) {
+                         const PlanesItem *items, int n) {
     if (n <= 0) return;
-    BatchOf<GeometryItem> b;
+    BatchOf<PlanesItem> b;
     b.n = n;
     for (int i = 0; i < n; ++i) b.item[i] = items[i];
     geometry::WindowGeo g;
@@ -185,9 +185,9 @@ void launch_window_batch(hipStream_t s, const size_t offset[3], const int32_t pi
     VP8_LAUNCH(k_window_b, dim3((unsigned)((units + 255) / 256), 1, n), dim3(256), 0, s, b, g);
 }
 
-void launch_orient_batch(hipStream_t s, int turns, int mirror, int raw_w, int raw_h, const GeometryItem *items, int n) {
+void launch_orient_batch(hipStream_t s, int turns, int mirror, int raw_w, int raw_h, const PlanesItem *items, int n) {
     if (n <= 0 || (!turns && !mirror)) return;
-    BatchOf<GeometryItem> b;
+    BatchOf<PlanesItem> b;
     b.n = n;
     for (int i = 0; i < n; ++i) b.item[i] = items[i];
     geometry::OrientGeo g;

@@ -7,8 +7,11 @@
 // the per-macroblock outputs, and one in-order HIP stream.
 //
 // Units: api_context.hip (create / destroy, surfaces, parameters, stream ordering, the record wait, downloads, device memory),
-// api_intake.hip (how a frame becomes current: source size / scaling / format / colour, staging, the stage order; upload, prefetch, set_current_device),
-// api_geometry.hip, api_deinterlace.hip, api_denoise.hip, api_analysis.hip, api_segment.hip, api_quality.hip (a stage each: its items, its setters, its results),
+// intake_settings.h (pure host code: the intake's settings in one struct, their one validity rule, their equality, the sizes that follow),
+// api_intake.hip (how a frame becomes current: intake_apply, the one way a setting changes; the source size / scaling / format / colour / transfer
+// setters, staging, the stage order; upload, prefetch, set_current_device),
+// api_geometry.hip (the window and orientation setters), api_deinterlace.hip, api_denoise.hip, api_analysis.hip, api_segment.hip, api_quality.hip
+// (a stage each: its setter -- which edits a copy of the settings and hands it to intake_apply --, its item, its results),
 // api_inter.hip (inter path, check_SSIM, key frames, loop filter), api_entropy.hip (coefficient + header entropy stage, frames out),
 // api_batch.hip (vp8hip_batch_*), api_shard.hip (export / import, RCCL: vp8hip_shard_*, vp8hip_group_*), api_profile.hip (timers, debug taps).
 #ifndef VP8HIP_CTX_H
@@ -26,6 +29,7 @@
 #include "../../include/vp8hip.h"
 #include "../../include/vp8hip_host.h"
 #include "vp8hip_dev.h"
+#include "intake_settings.h"
 
 struct ncclComm;     // (rccl.h is included by api_shard.hip only; the library resolves RCCL when a host first asks for it)
 
@@ -146,16 +150,17 @@ struct vp8hip_ctx {
     unsigned lf_launches = 0;       // window index of the loop filter's never-reset band counters
     int lf_type = 0;                // vp8hip_set_loop_filter_type: 0 normal, 1 simple
     unsigned lf_simple_launches = 0;   // ... the simple filter's own window index (its counters are its own, LF_SIMPLE_WORD)
-    int src_w = 0, src_h = 0;       // vp8hip_set_source_size: size of the planes handed over as current frames (0 = coded size)
-    // vp8hip_set_source_scaling: current frames come in at scale.in_w x scale.in_h (0 = no scaling) and k_scale_b makes src_w x src_h of
-    // them (the coded size when those are 0); the tables live in scale.d_blob
+    // THE INTAKE SETTINGS (intake_settings.h): every switch of the way a source frame becomes the current frame, changed by intake_apply
+    // alone.  What follows down to seg_buf is what the stages own besides: buffers, histories, records.
+    vp8::IntakeSettings in;
+    // vp8hip_set_source_scaling: current frames come in at in.in_w x in.in_h (0 = no scaling) and k_scale_b makes in.src_w x in.src_h of
+    // them (the coded size when those are 0); `scale` is what the launch reads, the tables live in scale.d_blob (an empty plan while in.in_w is 0)
     vp8::ScalePlan scale;
     // vp8hip_set_source_format: what the three pointers of a current frame are (0 = I420: fmt_stage is not used).  k_convert_b makes tight
     // I420 of the incoming size of them in fmt_stage (tight_i420) and the pack or scale launch reads that.
     // vp8hip_set_source_colour: the colour matrix BGRA / RGBA frames are read with, and a tone-mapped frame is written with.
     // vp8hip_set_source_transfer: the transfer (0 = off) and peak P010 / I010 frames carry: k_tonemap_b in k_convert_b's place, with the
-    // four tables of (src_transfer, src_peak) in tm_tables (made by the setter, released when the transfer goes back to 0).
-    int src_fmt = 0, src_colour = 0, src_transfer = 0, src_peak = 0;
+    // four tables of (in.src_transfer, in.src_peak) in tm_tables (made by the setter, released when the transfer goes back to 0).
     DeviceBuf fmt_stage, tm_tables;
     // vp8hip_set_overlay_host / _device: the layers burnt into every frame taken in, in slot order (ov_count of them are set; 0: no
     // launch, no buffer).  A slot keeps the layer's pixels (tight rows) and its prepared planes (overlay_planes; sized for any
@@ -171,24 +176,22 @@ struct vp8hip_ctx {
     // planes from host memory that were not prefetched, on their way to a convert, deinterlace or scale launch, pass through here: the
     // planes in the source format end to end (incoming_bytes; the call synchronises before it returns: one buffer is enough)
     DeviceBuf raw_stage;
-    // vp8hip_set_denoise: the level (0 = off); whether cur_prev holds a history (the previous frame taken in, as it left k_denoise_b, at
+    // vp8hip_set_denoise: whether cur_prev holds a history (the previous frame taken in, as it left k_denoise_b, at
     // this level); the record (dn.d: the count / ticket word of the launch).  dn_host: the last frame taken in passed through and its
     // record is the host's own.
-    int dn_level = 0;
     bool dn_have_history = false, dn_taken = false, dn_host = false;
     Record<vp8::DenoiseMirror> dn;
     vp8::DenoiseMirror dn_passed{};
-    // vp8hip_set_deinterlace: the mode (0 = off) and the field kept.  k_deinterlace_b writes tight I420 of the incoming size into di_stage
+    // vp8hip_set_deinterlace: k_deinterlace_b writes tight I420 of the incoming size into di_stage
     // (planes laid out as in fmt_stage) and the pack or scale launch reads that.  Mode 2's history, the previous frame AS RECEIVED, is
     // di_hist[di_idx]; the launch that reads it copies the new frame into the other one and the two trade places (both of one size).
     // di_hist_w x di_hist_h: the incoming size the history was taken at (another size: no history).  The record: as the denoiser's
     // (di.d: the count / ticket word).
-    int di_mode = 0, di_keep = 0;
     bool di_have_history = false, di_taken = false;
     DeviceBuf di_stage, di_hist[2];
     int di_idx = 0, di_hist_w = 0, di_hist_h = 0;
     Record<vp8::DeinterlaceMirror> di;
-    // vp8hip_set_source_window: the three pointers of a current frame are the plane bases of a surface whose rows are win_pitch[p] bytes
+    // vp8hip_set_source_window: the three pointers of a current frame are the plane bases of a surface whose rows are in.win_pitch[p] bytes
     // apart, and the frame is the window of the incoming size at (win_x, win_y).  k_window_b, in front of everything, writes the tight
     // planes end to end into win_stage (laid out as raw_stage) and the next stage reads that; planes from the HOST arrive windowed
     // (copy_planes: 2-D copies) and skip the launch.
@@ -196,30 +199,24 @@ struct vp8hip_ctx {
     // describes the UPRIGHT frame; the planes handed in, the window, the converter and the deinterlacer are of the raw size
     // (incoming_size), which is the upright incoming size with width and height traded when or_turns is odd.  k_orient_b, behind the
     // deinterlacer, writes tight I420 of the upright size into or_stage (tight_i420) and the pack or scale launch reads that.
-    bool win_on = false;
-    int32_t win_pitch[3] = {0, 0, 0};
-    int win_x = 0, win_y = 0;
-    DeviceBuf win_stage;
-    int or_turns = 0, or_mirror = 0;
-    DeviceBuf or_stage;
+    DeviceBuf win_stage, or_stage;
     // vp8hip_set_analysis: one allocation (an.d: the five sum / ticket words of k_analyse_src_b, then at +256 the history plane -- the luma
     // of the previous frame taken in, tight, coded size) and one mirror (an.h) of three parts, each with a seq of its own: the views
     // an_src[frame & 1] and an_mb point into an.h and hold the seq their part's last launch writes and its stream (`an` itself is never waited for).
     // an_src_launches: source-side launches so far (the two an_src share the count).  an_src_frame, an_mb_frame: the frame each part was
     // last launched for.  an_checked: check_SSIM ran on the reconstruction in flight (its verdict's device copy says whether the
     // fallback's flags count).
-    bool an_on = false, an_have_prev = false, an_checked = false;
+    bool an_have_prev = false, an_checked = false;
     Record<vp8::AnalysisMirror> an;
     RecordView<vp8::AnalysisSrcMirror> an_src[2];
     RecordView<vp8::AnalysisMbMirror> an_mb;
     uint32_t an_src_launches = 0;
     int an_src_frame[2] = {-1, -1}, an_mb_frame = -1;
-    // vp8hip_set_segment_mode: 0 off, 1 the caller's map, 2 variance-adaptive at seg_strength.  seg_buf, made when the mode first leaves 0
+    // vp8hip_set_segment_mode: 0 off, 1 the caller's map, 2 variance-adaptive at in.seg_strength.  seg_buf, made when the mode first leaves 0
     // (segment_buffers): the two sum words of k_aq_map_b (at 0 and 128: zero at rest), then five arrays of round256(mbs) bytes -- e and
     // the map of mode 2 for each of the two current-frame slots (cur_count & 1, as the analysis records: a frame may be taken in while
     // the one before it is coded), and the caller's map.  aq_frame: the frame each slot's map was made for; seg_map_set: a caller's map
     // is in force.
-    int seg_mode = 0, seg_strength = 0;
     bool seg_map_set = false;
     int aq_frame[2] = {-1, -1};
     DeviceBuf seg_buf;
@@ -449,33 +446,19 @@ void side_stream_ordered(vp8hip_ctx *c);
 int check_device_timeout(vp8hip_ctx *c);
 // ---- api_intake.hip: how a frame becomes current ----
 int set_frame_planes(vp8hip_ctx *c, Frame &f, const void *y, const void *u, const void *v, hipMemcpyKind kind, int sw = 0, int sh = 0);
-// size of the UPRIGHT frame a context takes in: the incoming size of its scaler, its source size, or the coded size
-inline void upright_size(const vp8hip_ctx *c, int *w, int *h) {
-    *w = c->scale.in_w ? c->scale.in_w : (c->src_w ? c->src_w : c->W);
-    *h = c->scale.in_w ? c->scale.in_h : (c->src_h ? c->src_h : c->H);
-}
-// size of the planes a context takes as current frames (what the window, the converter and the deinterlacer work at): the upright
-// size, width and height traded under an odd number of quarter turns
-inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) {
-    if (c->or_turns & 1) upright_size(c, h, w);
-    else upright_size(c, w, h);
-}
-// bytes of the planes a context takes as a current frame, in its source format (I420: ny, nc, nc)
-inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) {
-    int w, h;
-    incoming_size(c, &w, &h);
-    (void)vp8host_source_plane_bytes(c->src_fmt, w, h, bytes);
-}
-inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) {      // what one batched convert / pack / scale launch takes as one value
-    return a->src_fmt == b->src_fmt && a->src_colour == b->src_colour && a->src_transfer == b->src_transfer && a->src_peak == b->src_peak && a->src_w == b->src_w && a->src_h == b->src_h && a->scale.in_w == b->scale.in_w && a->scale.in_h == b->scale.in_h &&
-           (!a->scale.in_w || a->scale.kind == b->scale.kind) && a->dn_level == b->dn_level &&     // (and one denoiser level)
-           a->di_mode == b->di_mode && a->di_keep == b->di_keep &&                                  // (one deinterlacer mode and parity)
-           a->an_on == b->an_on &&                                                                  // (analysis on for all or for none)
-           a->seg_mode == b->seg_mode && a->seg_strength == b->seg_strength &&                      // (one segment mode and strength)
-           a->win_on == b->win_on && (!a->win_on || (a->win_pitch[0] == b->win_pitch[0] && a->win_pitch[1] == b->win_pitch[1] && a->win_pitch[2] == b->win_pitch[2] &&
-                                                     a->win_x == b->win_x && a->win_y == b->win_y)) &&      // (one window)
-           a->or_turns == b->or_turns && a->or_mirror == b->or_mirror;                              // (one orientation)
-}
+// the sizes of intake_settings.h for a context's settings in force
+inline void upright_size(const vp8hip_ctx *c, int *w, int *h) { upright_size(c->in, c->W, c->H, w, h); }
+inline void incoming_size(const vp8hip_ctx *c, int *w, int *h) { incoming_size(c->in, c->W, c->H, w, h); }
+inline void incoming_bytes(const vp8hip_ctx *c, size_t bytes[3]) { incoming_bytes(c->in, c->W, c->H, bytes); }
+inline void picture_size(const vp8hip_ctx *c, int *w, int *h) { picture_size(c->in, c->W, c->H, w, h); }
+inline int window_rule(const vp8hip_ctx *c, size_t off[3], int32_t row_bytes[3], int32_t rows[3]) { return window_rule(c->in, c->W, c->H, off, row_bytes, rows); }
+// what one batched convert / pack / scale launch takes as one value: the members' settings are equal
+inline bool same_intake(const vp8hip_ctx *a, const vp8hip_ctx *b) { return a->in == b->in; }
+static_assert(INTAKE_OK == VP8HIP_OK && INTAKE_REFUSED == VP8HIP_ERR_ARG, "intake_valid returns the library's codes");
+// THE ONE WAY a setting changes: nothing to do when `next` (canonical) is what is in force; refused (intake_valid) with nothing
+// changed; otherwise whatever is in flight ends, the stages' buffers are made for the new settings (on failure the old ones stay in
+// force), and planes prefetched under another SourceShape are dropped, the context's and its batch's: they are handed over again.
+int intake_apply(vp8hip_ctx *c, const IntakeSettings &next);
 // whatever is in flight on the context's streams (and its batch's) ends: setters and growing buffers, never per frame
 int quiesce_intake(vp8hip_ctx *c);
 // a frame's planes (nb: their bytes in the source format; a format of two planes or one never reads the later pointers) end to end into d,
@@ -527,24 +510,12 @@ bool denoise_item(vp8hip_ctx *c, hipStream_t s, DenoiseItem &it);
 // layer covers the picture, nothing to launch.  overlay_release: every slot's buffers (vp8hip_destroy).
 bool overlay_item(vp8hip_ctx *c, hipStream_t s, OverlayItem &it);
 void overlay_release(vp8hip_ctx *c);
-inline void picture_size(const vp8hip_ctx *c, int *w, int *h) { *w = c->src_w ? c->src_w : c->W; *h = c->src_h ? c->src_h : c->H; }
 // ---- api_deinterlace.hip ----
 // The frame about to be packed or scaled passes through the deinterlacer (take_frames: behind the convert launch and in front of the
-// pack or scale launch, on the same stream).  deinterlace_ready: the staging and history buffers at
-// the context's incoming size, before anything of the call has changed state (VP8HIP_ERR_ARG: an incoming height below 4).
+// pack or scale launch, on the same stream).  deinterlace_ready: the staging and history buffers at the context's incoming size.
 // deinterlace_item: y, u, v = tight I420 in DEVICE memory; afterwards they are the planes in di_stage.  false: off, nothing to launch.
 int deinterlace_ready(vp8hip_ctx *c);
 bool deinterlace_item(vp8hip_ctx *c, hipStream_t s, DeinterlaceItem &it, const void *&y, const void *&u, const void *&v);
-// ---- api_geometry.hip ----
-// The window in front of everything and the orientation behind the deinterlacer (take_frames).  geometry_ready: their staging buffers
-// at the context's incoming size.  *_item: false = off, nothing to launch; otherwise y, u, v are the stage's output afterwards.
-// window_rule: vp8host_source_window for the context's window, format and incoming size.
-// geometry_allows: would the window and the deinterlacer in force still be valid with this format, upright incoming size and turns?
-int geometry_ready(vp8hip_ctx *c);
-bool window_item(vp8hip_ctx *c, GeometryItem &it, const void *&y, const void *&u, const void *&v);
-bool orient_item(vp8hip_ctx *c, GeometryItem &it, const void *&y, const void *&u, const void *&v);
-int window_rule(const vp8hip_ctx *c, size_t off[3], int32_t row_bytes[3], int32_t rows[3]);
-bool geometry_allows(const vp8hip_ctx *c, int format, int upright_w, int upright_h, int turns);
 // ---- api_analysis.hip ----
 // The source side: the frame just taken into c->cur, behind its pack / scale / denoise launches on stream s (take_frames).  The coding side: the attempt whose loop filter was just launched on s (c->lf_key says which kind).
 // *_item: false = analysis off, nothing to launch.

@@ -85,7 +85,7 @@ struct SegData { int32_t v[4 * SD_INTS]; };
 constexpr int MAX_BATCH = 8;
 template <typename A> struct BatchOf { int n; A item[MAX_BATCH]; };
 // What a batched launcher takes is ONE array of member records and what all members share: (stream, const Item *, n, ...).  A context
-// on its own is a batch of one.  The intake stages have a record each (ConvertItem, DeinterlaceItem, DenoiseItem, AnalysisSrcItem);
+// on its own is a batch of one.  The intake stages have a record each (PlanesItem, DeinterlaceItem, DenoiseItem, AnalysisSrcItem);
 // the coding chain has three, each filled by one function of the API layer from a context (the pointers are the context's own and
 // outlive the launch call), and the launchers make the kernels' argument blocks of them:
 //   SourceItem  -- pack / scale: where a member's new frame comes from and the surface it goes into (take_frames);
@@ -209,13 +209,15 @@ void launch_aq_seg_batch(hipStream_t s, const AqItem *items, int n, int strength
 // src: the format's planes (src[2] is not read for the two-plane formats, src[1] and src[2] for the packed ones, k_convert_packed_b).
 // matrix: the colour matrix BGRA / RGBA are read with (vp8hip_set_source_colour).  Format 0 launches nothing.  false: a format or
 // matrix the setters refuse -- nothing was launched and the staging buffer is NOT the frame.
-struct ConvertItem { const uint8_t *src[3]; uint8_t *dst[3]; };
-bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const ConvertItem *items, int n);
+// PlanesItem, the record of every stage in front of the pack or scale launch that has no history: a member's three planes in, its three
+// planes (in a staging buffer of the context) out.
+struct PlanesItem { const uint8_t *src[3]; uint8_t *dst[3]; };
+bool launch_convert_batch(hipStream_t s, int format, int matrix, int w, int h, const PlanesItem *items, int n);
 // ... and with a transfer in force (vp8hip_set_source_transfer; P010 / I010 only): k_tonemap_b in k_convert_b's place, the same items,
 // the same tight I420 out.  tables: the four tables of vp8host_tonemap_tables end to end in device memory (lin, gain, lo, hi: 40 KiB);
 // matrix: the colour matrix the SDR picture is written with.  false: a format or matrix the rule does not cover (nothing was launched)
 constexpr int TONEMAP_TABLE_BYTES = 4096 * (4 + 4 + 1 + 1);
-bool launch_tonemap_batch(hipStream_t s, int format, int matrix, int w, int h, const uint32_t *tables, const ConvertItem *items, int n);
+bool launch_tonemap_batch(hipStream_t s, int format, int matrix, int w, int h, const uint32_t *tables, const PlanesItem *items, int n);
 // kernels_deinterlace.hip: interlaced source frames made progressive (vp8hip_set_deinterlace) BEHIND the convert launch and IN FRONT of
 // the pack or scale launch, which then reads dst as it reads a converted frame; the rule is include/vp8hip_host.h's.  src: tight I420
 // of w x h; hist: the previous frame as received (all nullptr: no history -- the spatial value everywhere); keep_hist: where this
@@ -237,10 +239,9 @@ void launch_deinterlace_batch(hipStream_t s, int w, int h, int keep, const Deint
 // window end to end; offset, pitch, row_bytes, rows: vp8host_source_window's (rows[p] == 0: the format has no plane p).
 // k_orient_b (vp8hip_set_source_orientation) BEHIND the deinterlacer and IN FRONT of the pack or scale launch: tight I420 of
 // raw_w x raw_h in, tight I420 of the upright size out (raw_h x raw_w for an odd number of turns).
-struct GeometryItem { const uint8_t *src[3]; uint8_t *dst[3]; };
 void launch_window_batch(hipStream_t s, const size_t offset[3], const int32_t pitch[3], const int32_t row_bytes[3], const int32_t rows[3],
-                         const GeometryItem *items, int n);
-void launch_orient_batch(hipStream_t s, int turns, int mirror, int raw_w, int raw_h, const GeometryItem *items, int n);
+                         const PlanesItem *items, int n);
+void launch_orient_batch(hipStream_t s, int turns, int mirror, int raw_w, int raw_h, const PlanesItem *items, int n);
 // kernels_overlay.hip: layers burnt into the frame just packed or scaled (vp8hip_set_overlay_host / _device), in place on the current
 // surface IN FRONT of the denoiser; the rule is include/vp8hip_host.h's.  A layer's PREPARED PLANES (k_overlay_prepare, when the layer
 // is set or moved) lie in one device buffer: Yo at 0 and e at off_e, lh rows of lstride bytes whose column 0 is picture column X0 =
