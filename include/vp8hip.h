@@ -18,6 +18,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "vp8hip_host.h"      /* vp8hip_tile, vp8hip_tile_planes, VP8HIP_MAX_TILES (vp8hip_set_canvas) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -281,6 +283,34 @@ int vp8hip_set_overlay_device(vp8hip_ctx *ctx, int slot, int format, int matrix,
 int vp8hip_set_overlay_placement(vp8hip_ctx *ctx, int slot, int x, int y, int opacity);
 int vp8hip_clear_overlay(vp8hip_ctx *ctx, int slot);
 int vp8hip_overlay_count(const vp8hip_ctx *ctx);      /* slots that hold a layer */
+/* A CANVAS: frames composed of scaled video tiles -- a film with bars, a pillarboxed 4:3 source, the grid of a conference, a speaker
+ * with thumbnails, a screen share with a camera in a corner.  The canvas is the picture (the size of vp8hip_set_source_size, or the
+ * coded size); up to VP8HIP_MAX_TILES tiles {in_w, in_h, x, y, w, h, filter} say which rectangle of it takes frames of which size,
+ * scaled down with which filter (0 area, 1 Lanczos-3; no upscaling, equal sizes are the identity); what no tile covers is the
+ * background.  The rule -- what a valid tile is, the composition, overlaps (later tiles lie on top), the padding -- is stated bit for
+ * bit in include/vp8hip_host.h ("CANVAS"; vp8host_compose_frame is its plain C++ form).
+ * vp8hip_set_canvas is a setter like the others: it waits for the context's streams, builds the tiles' tables once, and is not a
+ * per-frame call; n = 0 ends the canvas.  VP8HIP_ERR_ARG and nothing has changed: an invalid tile, n outside 0 .. VP8HIP_MAX_TILES, a
+ * background value outside 0 .. 255, or a context with something a canvas excludes -- the scaler's incoming size
+ * (vp8hip_set_source_scaling), a source format other than I420, a window, an orientation, the deinterlacer; each of those setters in
+ * turn refuses while a canvas is in force.  VP8HIP_ERR_STATE: a member of a batch (vp8hip_batch_create in turn refuses a context with
+ * a canvas) or a context that shares a frame's searches with other devices (and vp8hip_shard_init refuses a canvas).
+ * With a canvas a frame becomes current through vp8hip_compose_current_device or vp8hip_compose_current_host: src[k] holds tile k's
+ * three planes of this frame, 8-bit I420 of in_w x in_h, a pointer and a pitch each (0 = tight; no alignment is asked of either);
+ * src[k].y == NULL: the tile is absent this frame (a participant without video) and leaves what is under it.  ONE launch
+ * (k_compose_b) stands in the place of the pack or scale launch; everything behind it -- overlays, denoiser, analysis, AQ map, chroma
+ * scan, quality statistics, searches -- runs unchanged on the composed frame, the one that is coded.  The host form brings only the
+ * tiles' bytes over and returns when the host's planes are the host's again; the device form reads the planes on the context's
+ * stream, as vp8hip_set_current_device does.  VP8HIP_ERR_ARG: a null pointer, a present tile with a null u or v or a pitch below its
+ * plane's width.  VP8HIP_ERR_STATE: no canvas -- and with a canvas vp8hip_set_current_device, vp8hip_upload_current and
+ * vp8hip_prefetch_current return VP8HIP_ERR_STATE, as vp8hip_arf_filter_* return VP8HIP_ERR_ARG; nothing has changed then.
+ * A context that never sets a canvas launches nothing, allocates nothing and gives the bytes it gave.
+ * Out of scope: upscaling, NV12 or ten-bit tiles, alpha between tiles, rotating a tile, borders and labels (the overlay layers do
+ * those), batches, hidden alt-ref frames, a per-frame change of geometry without the setter's wait. */
+int vp8hip_set_canvas(vp8hip_ctx *ctx, const vp8hip_tile *tiles, int n, int bg_y, int bg_u, int bg_v);
+int vp8hip_canvas_tiles(const vp8hip_ctx *ctx);      /* tiles of the canvas in force, 0 = none */
+int vp8hip_compose_current_device(vp8hip_ctx *ctx, const vp8hip_tile_planes *src /* [n] */);
+int vp8hip_compose_current_host(vp8hip_ctx *ctx, const vp8hip_tile_planes *src /* [n] */);
 /* Temporal noise reduction of the source frames, the third stage of the input side (libvpx: --noise-sensitivity); the reference never
  * did anything about noise.  level 1, 2, 3: every frame that becomes current -- vp8hip_upload_current, vp8hip_set_current_device, the
  * pack out of a vp8hip_prefetch_current staging buffer, vp8hip_batch_set_current_device, vp8hip_batch_upload_current, with or without a
@@ -684,7 +714,10 @@ const char *vp8hip_status_string(int status);
  * vp8host_tonemap_frame; entry points only: vp8drv_config is unchanged);
  * also under 4010: overlays (vp8hip_set_overlay_host, vp8hip_set_overlay_device, vp8hip_set_overlay_placement, vp8hip_clear_overlay,
  * vp8hip_overlay_count, vp8host_overlay_frame, vp8drv_set_overlay_host, vp8drv_set_overlay_device, vp8drv_set_overlay_placement,
- * vp8drv_clear_overlay; entry points only: vp8drv_config is unchanged). */
+ * vp8drv_clear_overlay; entry points only: vp8drv_config is unchanged);
+ * also under 4010: canvases (vp8hip_set_canvas, vp8hip_canvas_tiles, vp8hip_compose_current_device, vp8hip_compose_current_host,
+ * vp8host_tile_valid, vp8host_compose_frame, vp8drv_set_canvas, vp8drv_encode_frame_tiles_device, vp8drv_encode_frame_tiles_host;
+ * entry points and the types vp8hip_tile and vp8hip_tile_planes only: vp8drv_config is unchanged). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

@@ -290,6 +290,19 @@ int vp8drv_set_overlay_host(vp8drv *d, int slot, int format, int matrix, const u
 int vp8drv_set_overlay_device(vp8drv *d, int slot, int format, int matrix, const void *pixels, int lw, int lh, int pitch, int x, int y, int opacity);
 int vp8drv_set_overlay_placement(vp8drv *d, int slot, int x, int y, int opacity);
 int vp8drv_clear_overlay(vp8drv *d, int slot);
+/* Frames composed of scaled video tiles (vp8hip_set_canvas, vp8hip_compose_current_device / _host, which say what a canvas is; the
+ * rule: include/vp8hip_host.h, "CANVAS").  Entry points, not fields of vp8drv_config, for the reason vp8drv_set_denoise is one; call
+ * vp8drv_set_canvas after vp8drv_create and before the first frame, or between frames (it takes the open check_SSIM verdict first and
+ * waits for the context's streams; n = 0 ends the canvas).  With a canvas the driver's frames come in through
+ * vp8drv_encode_frame_tiles_device / _host -- src[k]: tile k's planes of this frame, y == NULL for a tile that is absent -- which
+ * return what vp8drv_encode_frame_device / _host return; scene detection, check_SSIM, the GOP schedule, key frames, overlays, the
+ * denoiser and the quality statistics work as for any frame, on the composed frame.  The host form returns when the host's planes are
+ * the host's again.  VP8HIP_ERR_ARG: what the context's entry point refuses, or cfg.device_params = 0.  VP8HIP_ERR_STATE: a member of a
+ * live batch (vp8drv_batch_create in turn refuses a driver with a canvas), the tile calls without a canvas, and with a canvas
+ * vp8drv_encode_frame_device / _host, vp8drv_prefetch_frame_host, vp8drv_stage_frame_host and vp8drv_set_arf; nothing has changed then. */
+int vp8drv_set_canvas(vp8drv *d, const vp8hip_tile *tiles, int n, int bg_y, int bg_u, int bg_v);
+int vp8drv_encode_frame_tiles_device(vp8drv *d, const vp8hip_tile_planes *src /* [n] */, int force_key);
+int vp8drv_encode_frame_tiles_host(vp8drv *d, const vp8hip_tile_planes *src /* [n] */, int force_key);
 /* Source frames that are the window of a pitched surface, and source frames stored sideways or upside down
  * (vp8hip_set_source_window, vp8hip_set_source_orientation; the rules: include/vp8hip_host.h).  Entry points, not fields of
  * vp8drv_config, for the reason vp8drv_set_denoise is one; call them after vp8drv_create and before the first frame, or between

@@ -59,6 +59,33 @@ int vp8host_y4m_frame_marker_ok(const uint8_t marker[6]);
 #define VP8HOST_SCALE_MAX_TAPS 32
 int vp8host_scale_taps(int n_in, int n_out, int kind, int32_t *n_taps, int32_t *start /* [n_out] */, int16_t *coef /* [n_out * 32] */);
 
+/* CANVAS: a frame composed of scaled video tiles (vp8hip_set_canvas, vp8hip_compose_current_*, include/vp8hip.h; k_compose_b), bit for
+ * bit.  The project's own: the reference takes one source per frame.
+ * The canvas is the PICTURE pw x ph, both even: the size given to vp8hip_set_source_size, or the coded size.
+ * Tiles.  Up to VP8HIP_MAX_TILES tiles {in_w, in_h, x, y, w, h, filter}: frames of in_w x in_h are scaled to w x h and placed with
+ * their top-left sample at (x, y) of the picture.  A tile is valid when all six sizes and positions are even, w, h >= 2, 0 <= x,
+ * x + w <= pw, 0 <= y, y + h <= ph, w <= in_w <= 16384, h <= in_h <= 16384, filter is 0 (area) or 1 (Lanczos-3), and
+ * vp8host_scale_taps accepts in_w -> w, in_h -> h, in_w / 2 -> w / 2 and in_h / 2 -> h / 2 with that filter.  No upscaling; equal
+ * sizes are the identity.  The background (bg_y, bg_u, bg_v) is three values 0 .. 255.
+ * Per frame a tile has three planes, 8-bit I420 of in_w x in_h: a pointer and a pitch each (0 = tight, otherwise at least the plane's
+ * width; neither pointer nor pitch needs any alignment; nothing behind the last sample of the last row is read).  y == NULL: the tile
+ * is absent this frame and leaves what is under it.
+ * Composition.  (1) Every sample of the three planes is the background.  (2) For each tile in index order that is present, each of
+ * its three planes is scaled on its own by the two passes written next to vp8host_scale_taps above, with vp8host_scale_taps' own
+ * tables for the plane's two pairs (luma: in_w -> w, in_h -> h; chroma: in_w / 2 -> w / 2, in_h / 2 -> h / 2).  (3) The scaled plane
+ * REPLACES the rectangle: luma (x, y, w, h), chroma (x / 2, y / 2, w / 2, h / 2).  Later tiles lie on top of earlier ones; overlaps
+ * are allowed.  No blending, no alpha, no rounding beyond the scaler's.  (4) On the device the padding behind the picture's last
+ * column and row repeats the composed picture's edge: copy_with_padding of the result.
+ * vp8host_compose_frame writes the picture, tight planes of pw x ph and (pw / 2) x (ph / 2).  Returns 0, or -1 with nothing written
+ * for a null pointer, an odd or non-positive picture size, n outside 0 .. VP8HIP_MAX_TILES, a background value outside 0 .. 255, an
+ * invalid tile, or a pitch below its plane's width. */
+#define VP8HIP_MAX_TILES 16
+typedef struct { int32_t in_w, in_h, x, y, w, h, filter; } vp8hip_tile;
+typedef struct { const uint8_t *y, *u, *v; int32_t pitch_y, pitch_u, pitch_v; } vp8hip_tile_planes;
+int vp8host_tile_valid(int pw, int ph, const vp8hip_tile *tile);      /* 1: valid inside a picture of pw x ph */
+int vp8host_compose_frame(int pw, int ph, const vp8hip_tile *tiles, int n, int bg_y, int bg_u, int bg_v,
+                          const vp8hip_tile_planes *src /* [n] */, uint8_t *out_y, uint8_t *out_u, uint8_t *out_v);
+
 /* The rule of the device's temporal denoiser (vp8hip_set_denoise, include/vp8hip.h; k_denoise_b), bit for bit.  The project's own: the
  * reference never did anything about noise.
  * History and pass-through.  A context with denoising on keeps a history: the previous frame as it left the denoiser, Y, U and V at

@@ -21,7 +21,12 @@ tool writes with -no-scene-detect (with --arf this script does not detect scenes
 --scene-detect: the file scripts/native/y4m_to_ivf writes with its default, scene detection on.  A cut is a key frame and restarts the GOP
 counter, so rank 0 first scans the chroma differences of the whole sequence in batches on the device (gop_shard.scan_differences),
 api.scene_plan makes the serial loop's own key-frame schedule of them, gop_shard.chunks_from_keys the chunks, and the ranks shard those as
-they shard the fixed ones.  Not with --denoise, --deinterlace adaptive, --analysis or --arf: their histories follow the frames taken in."""
+they shard the fixed ones.  Not with --denoise, --deinterlace adaptive, --analysis or --arf: their histories follow the frames taken in.
+--canvas with --tile FILE.yuv:INWxINH:X:Y:W:H[:area|lanczos] (repeatable, in tile order; up to 16): the picture of --width x --height is
+composed on the device of the tiles' frames (vp8drv_set_canvas, vp8drv_encode_frame_tiles_host) -- every FILE holds tight I420 frames of
+INW x INH, scaled to W x H and placed at (X, Y); a file that ends makes its tile absent from then on; --canvas-bg Y,U,V is what no tile
+covers (default 16,128,128).  One process, one driver over the whole sequence with a key frame every --gop frames; goes with
+--overlay, --denoise, --aq, --scene-detect (the driver's own), --partitions, --qmin / --qmax, --conformant and --simple-filter only."""
 import argparse, os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,6 +69,49 @@ class FormatPlanes:
         return p + [p[-1]] * (3 - len(p))
 
 
+def canvas_main(a):
+    """--canvas: one driver over the whole sequence, every frame composed of the tiles' files"""
+    from vp8oclenc_amd import api
+    if not (a.canvas and a.tile) or a.yuv or a.y4m or a.resize or a.source_format or a.source_transfer or a.deinterlace != "off" or a.surface or a.rotate or a.mirror or \
+            a.analysis or a.segment_map or a.arf or int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        sys.exit("--canvas goes with --tile (and --tile with --canvas), one process, and none of --yuv, --y4m, --resize, --source-format, --source-transfer, "
+                 "--deinterlace, --surface, --rotate, --mirror, --analysis, --segment-map, --arf")
+    try:
+        tiles = [api.parse_tile(t) for t in a.tile]
+        bg = tuple(int(x) for x in a.canvas_bg.split(","))
+        overlays = [api.parse_overlay(o) for o in a.overlay]
+        if len(bg) != 3 or len(tiles) > api.MAX_TILES or len(overlays) > api.MAX_OVERLAYS:
+            raise ValueError(f"three background values, at most {api.MAX_TILES} tiles and {api.MAX_OVERLAYS} layers")
+        files = [YuvFile(path, t.in_w, t.in_h) for path, t in tiles]
+    except (ValueError, OSError) as e:
+        sys.exit(f"--canvas: {e}")
+    Wd, Hd = a.width, a.height
+    Wc, Hc = (Wd + 15) // 16 * 16, (Hd + 15) // 16 * 16
+    src = dict(src_width=Wd, src_height=Hd) if (Wc, Hc) != (Wd, Hd) else {}
+    t0 = time.perf_counter()
+    try:
+        drv = api.NativeDriver(Wc, Hc, device=int(os.environ.get("LOCAL_RANK", 0)), **src, gop_size=a.gop, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
+                               ssim_target=a.ssim_target, check_ssim=1, conformant_stream=int(a.conformant), loop_filter_type=int(a.simple_filter),
+                               scene_detect=int(a.scene_detect))
+        drv.set_canvas([t for _, t in tiles], bg)
+    except api.Vp8HipError as e:
+        sys.exit(f"--canvas: {e}")
+    if a.denoise:
+        drv.set_denoise(a.denoise)
+    if a.aq:
+        drv.set_segment_mode(2, a.aq)
+    for k, (px, ox, oy, opacity) in enumerate(overlays):
+        drv.set_overlay(k, px, ox, oy, opacity)
+    out = []
+    for t in range(a.frames):
+        drv.encode_tiles([f.frame(t) if t < f.n else None for f in files])
+        out.append(drv.get_frame())
+    drv.close()
+    n = gop_shard.write_ivf(a.out, out, Wd, Hd, a.framerate)
+    el = time.perf_counter() - t0
+    print(f"{a.out}: {a.frames} frames {Wd}x{Hd} composed of {len(tiles)} tiles, {n} bytes, {a.frames / el:.1f} frames/s including the host-side frame sources")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out"); ap.add_argument("--yuv"); ap.add_argument("--y4m")
@@ -94,7 +142,12 @@ def main():
     ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames made by temporal filtering on the device (vp8drv_set_arf, vp8drv_encode_arf_host): one in front of every group of PERIOD frames of a GOP, centred on the group's last frame, FRAMES frames wide (default 7) at STRENGTH 0..6 (default 3)")
     ap.add_argument("--scene-detect", action="store_true", help="key frames where the serial program with scene detection puts them: the sequence is scanned first (gop_shard.scan_differences), api.scene_plan gives the chunks")
     ap.add_argument("--scan-batch", type=int, default=8, metavar="N", help="... members of the scanning batch (1..8)")
+    ap.add_argument("--canvas", action="store_true", help="compose the picture of --width x --height of the --tile sources on the device (vp8drv_set_canvas)")
+    ap.add_argument("--tile", action="append", default=[], metavar="FILE.yuv:INWxINH:X:Y:W:H[:area|lanczos]", help="with --canvas, repeatable, in tile order: FILE holds tight I420 frames of INW x INH, scaled to W x H and placed at (X, Y) of the picture; a file that ends makes its tile absent")
+    ap.add_argument("--canvas-bg", default="16,128,128", metavar="Y,U,V", help="... the background: what no tile covers")
     a = ap.parse_args()
+    if a.canvas or a.tile:
+        return canvas_main(a)
     if a.scene_detect and (a.denoise or a.deinterlace == "adaptive" or a.analysis or a.arf):
         sys.exit("--scene-detect does not go with --denoise, --deinterlace adaptive, --analysis or --arf: their histories follow the frames taken in, the scan would disturb them")
     if not 1 <= a.scan_batch <= 8:

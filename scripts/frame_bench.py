@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Whole-encoder timing: native frame loop + vp8drv_get_frame (complete VP8 frames out), one thread per GOP stream.
-    python scripts/frame_bench.py [--streams N] [--frames K] [--width W --height H] [--partitions P]"""
+    python scripts/frame_bench.py [--streams N] [--frames K] [--width W --height H] [--partitions P]
+--tiles LAYOUT: every frame is composed on the device of device-resident tiles (vp8drv_set_canvas, vp8drv_encode_frame_tiles_device):
+letterbox = one source of the picture's size scaled to 20/27 of its height between bars (1920x1080 -> 1920x800), grid4 = four sources
+of 2/3 of the picture's size scaled to its quarters (1280x720 -> 960x540), pip = a 1:1 full frame and a source of 2/3 of the picture's
+size scaled to a quarter of its width and height in the bottom right corner (1280x720 -> 480x270).  --tiles-precomposed: the same
+pictures composed on the host beforehand (vp8host_compose_frame) and handed over as plain frames: what the composition costs."""
 import argparse, os, sys, threading, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,10 +40,14 @@ ap.add_argument("--mirror", action="store_true", help="... behind a left-right f
 ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the frame analysis record of every frame (vp8drv_set_analysis): what k_analyse_src_b and k_analyse_mb_b cost")
 ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation at strength N (vp8drv_set_segment_mode, mode 2): what k_aq_map_b + k_aq_seg_b cost, and with one stream the mapped macroblock kernel next to the default's in the same run")
 ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames (vp8drv_set_arf, vp8drv_encode_arf_device): every stream codes one in front of every PERIOD-th frame from a window of FRAMES device-resident frames (default 7) at STRENGTH (default 3); with one stream also what k_arf_filter_b costs by HIP events")
+ap.add_argument("--tiles", choices=("", "letterbox", "grid4", "pip"), default="", metavar="LAYOUT", help="compose every frame of device-resident tiles (vp8drv_set_canvas): letterbox, grid4 or pip; with one stream also what k_compose_b costs by HIP events")
+ap.add_argument("--tiles-precomposed", action="store_true", help="with --tiles: the same pictures composed on the host beforehand and handed over as plain frames")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
 ap.add_argument("--only", choices=("both", "on", "off"), default="both", help="which of the two legs to time")
 ap.add_argument("--pipeline", action="store_true", help="one host thread: encode + get_frame_begin on every stream, then get_frame_end on every stream")
 a = ap.parse_args()
+if a.tiles and a.pipeline:
+    sys.exit("--tiles: not with --pipeline")
 if a.switch_interval > 0:
     sys.setswitchinterval(a.switch_interval)
 seq = SynthSequence(a.width, a.height, seed=1)
@@ -92,10 +101,35 @@ if a.window_pitch:      # every plane's rows a pitch apart: the tight rows at th
             out.append(s)
         return out
     host = [pitched(f) for f in host]
+tiles, tile_dev = [], []
+if a.tiles:      # the sources: a synthetic sequence per tile, device-resident, tight
+    if a.scale_from or fmt or pitch or turns or a.mirror or a.deinterlace != "off" or a.arf or a.width % 24 or a.height % 108:
+        sys.exit("--tiles goes with none of --scale-from, --source-format, --window-pitch, --rotate, --mirror, --deinterlace, --arf, and a picture whose width is a multiple of 24 and whose height one of 108")
+    w, h = a.width, a.height
+    tiles = {"letterbox": [(w, h, 0, (h - h * 20 // 27) // 2, w, h * 20 // 27, 0)],
+             "grid4": [(w * 2 // 3, h * 2 // 3, x, y, w // 2, h // 2, 0) for y in (0, h // 2) for x in (0, w // 2)],
+             "pip": [(w, h, 0, 0, w, h, 0), (w * 2 // 3, h * 2 // 3, w - w // 4 - 32, h - h // 4 - 32 - (h // 4 & 1), w // 4, h // 4 + (h // 4 & 1), 0)]}[a.tiles]
+    tile_host = []
+    for k, t in enumerate(tiles):
+        s = SynthSequence(t[0], t[1], seed=1 + k)
+        tile_host.append([tuple(np.ascontiguousarray(p[:t[1] >> (i > 0), :t[0] >> (i > 0)]) for i, p in enumerate(s.frame(j))) for j in range(nd)])
+    if a.tiles_precomposed:
+        host = [list(api.compose_frame(w, h, tiles, [th[j] for th in tile_host])) for j in range(nd)]
+        if (w, h) != (W, H):
+            scale = dict(src_width=w, src_height=h)
+    else:
+        tile_dev = [[tuple(api.to_device(p) for p in th[j]) for th in tile_host] for j in range(nd)]
+        tile_src = [[(f[0].data_ptr(), f[1].data_ptr(), f[2].data_ptr(), (0, 0, 0)) for f in frame] for frame in tile_dev]
+        if (w, h) != (W, H):
+            scale = dict(src_width=w, src_height=h)
+    print(f"--tiles {a.tiles}{' (composed on the host beforehand)' if a.tiles_precomposed else ''}: " + ", ".join(f"{t[0]}x{t[1]} -> {t[4]}x{t[5]} at ({t[2]}, {t[3]})" for t in tiles))
 dev = [tuple(api.to_device(p) for p in f) for f in host]
 api.device_synchronize()
 drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
                          loop_filter_type=a.loop_filter_type, quality_stats=a.quality_stats, **scale) for _ in range(a.streams)]
+if tile_dev:
+    for d in drvs:
+        d.set_canvas(tiles)
 if a.denoise:
     for d in drvs:
         d.set_denoise(a.denoise)
@@ -150,7 +184,10 @@ def work(k, n, emit):
         y, u, v = dev[(t + 3 * k) % nd]
         if arf and t and t % arf[0] == 0:
             hidden_frame(d, k, t, emit)
-        d.encode_frame_device(y.data_ptr(), u.data_ptr(), v.data_ptr())
+        if tile_dev:
+            d.encode_tiles(tile_src[(t + 3 * k) % nd], device=True)
+        else:
+            d.encode_frame_device(y.data_ptr(), u.data_ptr(), v.data_ptr())
         if emit:
             sizes[k] += len(d.get_frame())
     d.hip.synchronize()
@@ -198,7 +235,7 @@ if a.streams == 1:   # the input side by HIP events: the pack launch, with k_con
     work(0, 32, False)
     ms, n = d.hip.profile_read().get("pack", (0.0, 0))
     d.hip.profile_enable([])
-    print(f"input side ({a.source_format or 'i420'}{' ' + a.source_transfer + ' ' + str(a.source_peak) if a.source_transfer else ''}), {n} timed launches over 32 frames: {ms / 32 * 1e3:.2f} us per frame")
+    print(f"input side ({'tiles ' + a.tiles if tile_dev else a.source_format or 'i420'}{' ' + a.source_transfer + ' ' + str(a.source_peak) if a.source_transfer else ''}), {n} timed launches over 32 frames: {ms / 32 * 1e3:.2f} us per frame")
 if a.aq and a.streams == 1:   # k_mb_p_map next to k_mb_p, and the input side without the map's launches: the same process, HIP events
     d = drvs[0]
 

@@ -112,7 +112,12 @@ std::vector<std::function<void(IntakeSettings &)>> edits() {
             [](IntakeSettings &s) { s.win_pitch[0] += 1; }, [](IntakeSettings &s) { s.win_pitch[1] += 1; }, [](IntakeSettings &s) { s.win_pitch[2] += 1; },
             [](IntakeSettings &s) { s.win_x += 2; }, [](IntakeSettings &s) { s.win_y += 2; }, [](IntakeSettings &s) { s.or_turns ^= 2; }, [](IntakeSettings &s) { s.or_mirror ^= 1; },
             [](IntakeSettings &s) { s.di_mode ^= 3; }, [](IntakeSettings &s) { s.di_keep ^= 1; }, [](IntakeSettings &s) { s.dn_level ^= 1; }, [](IntakeSettings &s) { s.an_on = false; },
-            [](IntakeSettings &s) { s.seg_mode = 1; }, [](IntakeSettings &s) { s.seg_strength ^= 1; }};
+            [](IntakeSettings &s) { s.seg_mode = 1; }, [](IntakeSettings &s) { s.seg_strength ^= 1; },
+            // the canvas (tests/test_compose_cpu.py has its verdicts): the count, the background, a tile's seven fields, the last tile
+            [](IntakeSettings &s) { s.n_tiles += 1; }, [](IntakeSettings &s) { s.bg[0] += 1; }, [](IntakeSettings &s) { s.bg[1] += 1; }, [](IntakeSettings &s) { s.bg[2] += 1; },
+            [](IntakeSettings &s) { s.tile[0].in_w += 2; }, [](IntakeSettings &s) { s.tile[0].in_h += 2; }, [](IntakeSettings &s) { s.tile[0].x += 2; },
+            [](IntakeSettings &s) { s.tile[0].y += 2; }, [](IntakeSettings &s) { s.tile[0].w += 2; }, [](IntakeSettings &s) { s.tile[0].h += 2; },
+            [](IntakeSettings &s) { s.tile[0].filter ^= 1; }, [](IntakeSettings &s) { s.tile[VP8HIP_MAX_TILES - 1].filter ^= 1; }};
 }
 
 IntakeSettings all_on() {      // 64x48: everything on at once
@@ -130,10 +135,11 @@ IntakeSettings all_on() {      // 64x48: everything on at once
 void equality() {
     const IntakeSettings a = all_on();
     expect(intake_valid(64, 48, a) == INTAKE_OK && a == canonical(a, 64, 48) && a == all_on(), "the all-on setting is valid, canonical and equal to itself");
-    // 18 ints, three pitches of 32 bits and two bools: a field added to the struct and not to edits() changes the size
-    static_assert(sizeof(IntakeSettings) == 23 * 4, "a new field: add it to operator== and to edits()");
+    // 18 ints, three pitches of 32 bits and two bools, then the canvas: a count, three background values and VP8HIP_MAX_TILES tiles of
+    // seven ints -- a field added to the struct and not to edits() changes the size
+    static_assert(sizeof(IntakeSettings) == (23 + 4 + 7 * VP8HIP_MAX_TILES) * 4, "a new field: add it to operator== and to edits()");
     const auto e = edits();
-    expect(e.size() == 23, "one edit per field");
+    expect(e.size() == 23 + 4 + 7 + 1, "one edit per field (of the tiles: the first one's seven and the last one's last)");
     for (size_t k = 0; k < e.size(); ++k) {
         IntakeSettings b = a;
         e[k](b);

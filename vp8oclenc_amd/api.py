@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "vp8hip_set_source_transfer", "vp8drv_set_source_transfer", "vp8host_tonemap_tables", "vp8host_tonemap_frame",
     "vp8hip_set_overlay_host", "vp8hip_set_overlay_device", "vp8hip_set_overlay_placement", "vp8hip_clear_overlay", "vp8hip_overlay_count",
     "vp8host_overlay_frame", "vp8drv_set_overlay_host", "vp8drv_set_overlay_device", "vp8drv_set_overlay_placement", "vp8drv_clear_overlay",
+    "vp8hip_set_canvas", "vp8hip_canvas_tiles", "vp8hip_compose_current_device", "vp8hip_compose_current_host", "vp8host_tile_valid",
+    "vp8host_compose_frame", "vp8drv_set_canvas", "vp8drv_encode_frame_tiles_device", "vp8drv_encode_frame_tiles_host",
 ]
 
 
@@ -867,6 +869,79 @@ def parse_overlay(spec: str):
 _OVERLAY_SET_ARGS = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6
 
 
+MAX_TILES = 16   # VP8HIP_MAX_TILES, include/vp8hip_host.h
+
+
+class Tile(C.Structure):
+    """vp8hip_tile: frames of in_w x in_h scaled to w x h at (x, y) of the picture; filter SCALE_AREA or SCALE_LANCZOS"""
+    _fields_ = [(n, C.c_int32) for n in ("in_w", "in_h", "x", "y", "w", "h", "filter")]
+
+
+class TilePlanes(C.Structure):
+    """vp8hip_tile_planes: a tile's three planes of one frame, a pointer and a pitch each (0 = tight); y NULL = absent"""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("pitch_y", C.c_int32), ("pitch_u", C.c_int32), ("pitch_v", C.c_int32)]
+
+
+def tiles_array(tiles):
+    """[(in_w, in_h, x, y, w, h[, filter]), ...] or Tile objects -> a ctypes array of vp8hip_tile"""
+    tiles = list(tiles)
+    arr = (Tile * max(len(tiles), 1))()
+    for k, t in enumerate(tiles):
+        arr[k] = t if isinstance(t, Tile) else Tile(*[int(x) for x in t])
+    return arr
+
+
+def parse_tile(spec: str):
+    """FILE.yuv:INWxINH:X:Y:W:H[:area|lanczos], the tools' --tile option -> (path, Tile)"""
+    try:
+        parts = spec.rsplit(":", 6) if spec.rsplit(":", 1)[-1].lower() in ("area", "lanczos") else spec.rsplit(":", 5) + ["area"]
+        path, size, x, y, w, h, kind = parts
+        iw, ih = (int(v) for v in size.lower().split("x"))
+        return path, Tile(iw, ih, int(x), int(y), int(w), int(h), SCALE_LANCZOS if kind.lower() == "lanczos" else SCALE_AREA)
+    except (ValueError, TypeError):
+        raise ValueError(f"tile {spec!r}: FILE.yuv:INWxINH:X:Y:W:H[:area|lanczos]") from None
+
+
+def tile_planes_array(frames, n=None):
+    """One frame's sources, frames[k] for tile k: None (absent), three uint8 arrays of two dimensions whose rows may be strided (the
+    pitch is the row stride), or (y, u, v, (pitch_y, pitch_u, pitch_v)) of addresses in host or device memory -> (a ctypes array of
+    vp8hip_tile_planes, what must stay alive while it is used)"""
+    frames = list(frames)
+    arr = (TilePlanes * max(n or len(frames), 1))()
+    keep = []
+    for k, f in enumerate(frames):
+        if f is None:
+            continue
+        if len(f) == 4:
+            ptrs, pitches = [_ptr(p) for p in f[:3]], [int(p) for p in f[3]]
+        else:
+            ptrs, pitches = [], []
+            for p in f:
+                if p.dtype != np.uint8 or p.ndim != 2 or p.strides[1] != 1:
+                    raise ValueError("tile planes: uint8 arrays of two dimensions with contiguous rows")
+                keep.append(p)
+                ptrs.append(p.ctypes.data)
+                pitches.append(0 if p.strides[0] == p.shape[1] else int(p.strides[0]))
+        arr[k] = TilePlanes(ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pitches[2])
+    return arr, keep
+
+
+def compose_frame(pw: int, ph: int, tiles, frames, bg=(16, 128, 128)):
+    """vp8host_compose_frame: the device's canvas rule in plain C++ -> the picture's planes (y, u, v), tight, pw x ph.  tiles as for
+    tiles_array, frames as for tile_planes_array (host memory).  ValueError for what the rule refuses."""
+    lib = load_library()
+    tiles = list(tiles)
+    ta = tiles_array(tiles)
+    pa, keep = tile_planes_array(frames, len(tiles))
+    lib.vp8host_compose_frame.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    out = (np.zeros((max(ph, 0), max(pw, 0)), np.uint8), np.zeros((max(ph, 0) // 2, max(pw, 0) // 2), np.uint8), np.zeros((max(ph, 0) // 2, max(pw, 0) // 2), np.uint8))
+    if lib.vp8host_compose_frame(int(pw), int(ph), C.addressof(ta), len(tiles), int(bg[0]), int(bg[1]), int(bg[2]), C.addressof(pa),
+                                 *[o.ctypes.data for o in out]) != 0:
+        raise ValueError(f"vp8host_compose_frame({pw}x{ph}, {len(tiles)} tiles) refused")
+    del keep
+    return out
+
+
 def overlay_frame(pixels, x: int, y: int, opacity: int, planes, fmt=None, matrix: int = 0):
     """vp8host_overlay_frame: the device's overlay rule in plain C++.  pixels = the layer, a uint8 array of shape (lh, lw, 4), BGRA
     unless fmt says RGBA; planes = (Y, U, V), I420 of the picture size -> new (Y, U, V) with the layer composed at (x, y)"""
@@ -1143,6 +1218,26 @@ class NativeDriver:
         rc = f(self.h, int(slot), fmt, int(matrix), ptr, lw, lh, pitch, int(x), int(y), int(opacity))
         if rc != 0:
             raise Vp8HipError(f"vp8drv_set_overlay({slot}, {lw}x{lh} at ({x}, {y})): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_canvas(self, tiles, bg=(16, 128, 128)) -> None:
+        """vp8drv_set_canvas: frames are composed of these tiles (tiles_array's forms) over the background from now on; [] ends it"""
+        tiles = list(tiles)
+        ta = tiles_array(tiles)
+        self.lib.vp8drv_set_canvas.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4
+        rc = self.lib.vp8drv_set_canvas(self.h, C.addressof(ta), len(tiles), int(bg[0]), int(bg[1]), int(bg[2]))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_canvas({len(tiles)} tiles): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        self._canvas_tiles = len(tiles)
+
+    def encode_tiles(self, frames, force_key: bool = False, device: bool = False) -> bool:
+        """vp8drv_encode_frame_tiles_host / _device: one frame from the tiles' sources (tile_planes_array's forms; None = absent).
+        True if the frame was coded as a key frame."""
+        pa, keep = tile_planes_array(frames, getattr(self, "_canvas_tiles", 0))
+        f = self.lib.vp8drv_encode_frame_tiles_device if device else self.lib.vp8drv_encode_frame_tiles_host
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        rc = f(self.h, C.addressof(pa), int(force_key))
+        del keep
+        return self._ret(rc)
 
     def set_overlay_placement(self, slot: int, x: int, y: int, opacity: int = 255) -> None:
         """vp8drv_set_overlay_placement: move or fade the slot's layer"""
@@ -1723,6 +1818,26 @@ class Vp8Hip:
         rc = f(self.h, int(slot), fmt, int(matrix), ptr, lw, lh, pitch, int(x), int(y), int(opacity))
         if rc != 0:
             raise Vp8HipError(f"vp8hip_set_overlay({slot}, {lw}x{lh} at ({x}, {y})): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def set_canvas(self, tiles, bg=(16, 128, 128)):
+        """vp8hip_set_canvas: current frames are composed of these tiles (tiles_array's forms) over the background; [] ends it"""
+        tiles = list(tiles)
+        ta = tiles_array(tiles)
+        self.lib.vp8hip_set_canvas.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4
+        rc = self.lib.vp8hip_set_canvas(self.h, C.addressof(ta), len(tiles), int(bg[0]), int(bg[1]), int(bg[2]))
+        if rc != 0:
+            raise Vp8HipError(f"vp8hip_set_canvas({len(tiles)} tiles): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        self._canvas_tiles = len(tiles)
+
+    def compose_current(self, frames, device: bool = False):
+        """vp8hip_compose_current_host / _device: the current frame from the tiles' sources (tile_planes_array's forms; None = absent)"""
+        pa, keep = tile_planes_array(frames, getattr(self, "_canvas_tiles", 0))
+        f = self.lib.vp8hip_compose_current_device if device else self.lib.vp8hip_compose_current_host
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        rc = f(self.h, C.addressof(pa))
+        del keep
+        if rc != 0:
+            raise Vp8HipError(f"vp8hip_compose_current: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
     def set_overlay_placement(self, slot: int, x: int, y: int, opacity: int = 255):
         """vp8hip_set_overlay_placement: move or fade the slot's layer"""

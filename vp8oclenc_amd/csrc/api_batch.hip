@@ -58,7 +58,7 @@ int vp8hip_batch_create(vp8hip_batch **out, vp8hip_ctx *const *ctxs, int n) {
     for (int i = 0; i < n; ++i) {
         if (!ctxs[i] || ctxs[i]->W != ctxs[0]->W || ctxs[i]->H != ctxs[0]->H || ctxs[i]->device != ctxs[0]->device ||
             ctxs[i]->ssim_target != ctxs[0]->ssim_target || ctxs[i]->lf_overlap || ctxs[i]->conformant != ctxs[0]->conformant ||
-            !same_intake(ctxs[i], ctxs[0]))
+            !same_intake(ctxs[i], ctxs[0]) || excludes_batch(ctxs[i]->in))
             return VP8HIP_ERR_ARG;
         if (!ctxs[i]->own_stream) return VP8HIP_ERR_STATE;            // already a member of a batch
         for (int j = 0; j < i; ++j)

@@ -444,6 +444,7 @@ void vp8hip_destroy(vp8hip_ctx *c) {
     }
     if (c->ev_chroma) hipEventDestroy(c->ev_chroma);
     hipFree(c->scale.d_blob);
+    hipFree(c->canvas.d_blob);
     c->fmt_stage.release();
     c->tm_tables.release();
     overlay_release(c);

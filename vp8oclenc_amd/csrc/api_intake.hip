@@ -1,7 +1,8 @@
 // api_intake.hip -- how a frame becomes a context's current frame: the source size, scaling, format and colour setters, the staging
 // buffers, the stage order (take_frames: window, convert, deinterlace, orient, scale or pack, overlay, denoise, analysis, segment map -- the one place that knows it), and the
 // single-context ways in (vp8hip_set_current_device, vp8hip_upload_current, vp8hip_prefetch_current).  A batch's ways in are api_batch.hip's;
-// they end in take_frames too.  Replaces the uploads of vp8enc.cpp:386-401.
+// they end in take_frames too.  A context with a canvas (vp8hip_set_canvas) takes several sources per frame: vp8hip_compose_current_device / _host
+// launch k_compose_b in the place of the pack or scale launch and share everything behind it (finish_frames).  Replaces the uploads of vp8enc.cpp:386-401.
 #include "vp8hip_ctx.h"
 
 using namespace vp8;
@@ -177,6 +178,12 @@ int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u
         static const bool skip = experiment_skip("pack");      // timing experiment only: the batches' pack
         if (!skip) launch_pack_batch(s, src, n, in.src_w, in.src_h);
     }
+    return finish_frames(m, n, s, planes_read);
+}
+
+int finish_frames(vp8hip_ctx *const *m, int n, hipStream_t s, hipEvent_t planes_read) {
+    vp8hip_ctx *c0 = m[0];
+    const IntakeSettings &in = c0->in;      // (same_intake: every member's)
     if (planes_read) HIPCHK(c0, hipEventRecord(planes_read, s));
     {   // vp8hip_set_overlay_*: the members that have layers, in one launch behind the pack or scale launch and IN FRONT of the denoiser,
         // whose history is the previous current surface: everything downstream sees the composed frame, the one that is coded
@@ -238,6 +245,62 @@ static int take_current(vp8hip_ctx *c, const void *y, const void *u, const void 
     return take_frames(&c, &y, &u, &v, 1, c->stream, &kind, planes_read, tight);
 }
 
+// a tile's three planes of this frame: their widths, rows and pitches in bytes (0 = tight)
+static void tile_planes(const vp8hip_tile &t, const vp8hip_tile_planes &p, const uint8_t *ptr[3], int32_t width[3], int32_t rows[3], int32_t pitch[3]) {
+    ptr[0] = p.y; ptr[1] = p.u; ptr[2] = p.v;
+    const int32_t given[3] = {p.pitch_y, p.pitch_u, p.pitch_v};
+    for (int k = 0; k < 3; ++k) {
+        width[k] = k ? t.in_w / 2 : t.in_w;
+        rows[k] = k ? t.in_h / 2 : t.in_h;
+        pitch[k] = given[k] ? given[k] : width[k];
+    }
+}
+
+// one context's new current frame composed of its canvas' tiles (vp8hip_compose_current_*), on its own stream.  Tiles in host memory
+// pass through raw_stage first, only their bytes, tight and end to end: one 2-D copy per plane.
+static int take_composed(vp8hip_ctx *c, const vp8hip_tile_planes *src, hipMemcpyKind kind) {
+    const IntakeSettings &in = c->in;
+    if (!in.n_tiles) return VP8HIP_ERR_STATE;
+    ComposeSource cs[VP8HIP_MAX_TILES] = {};
+    size_t total = 0;
+    for (int k = 0; k < in.n_tiles; ++k) {      // everything that can be refused, before anything of the context changes
+        if (!src[k].y) continue;
+        if (!src[k].u || !src[k].v) return VP8HIP_ERR_ARG;
+        const uint8_t *ptr[3];
+        int32_t width[3], rows[3];
+        tile_planes(in.tile[k], src[k], ptr, width, rows, cs[k].pitch);
+        for (int p = 0; p < 3; ++p) {
+            if (cs[k].pitch[p] < width[p]) return VP8HIP_ERR_ARG;
+            cs[k].p[p] = ptr[p];
+            total += round256((size_t)width[p] * rows[p]);
+        }
+    }
+    if (kind != hipMemcpyDeviceToDevice) {
+        { const int rc = c->raw_stage.grow(c, total); if (rc) return rc; }
+        uint8_t *d = c->raw_stage.p;
+        for (int k = 0; k < in.n_tiles; ++k) {
+            if (!src[k].y) continue;
+            const uint8_t *ptr[3];
+            int32_t width[3], rows[3], pitch[3];
+            tile_planes(in.tile[k], src[k], ptr, width, rows, pitch);
+            for (int p = 0; p < 3; ++p) {
+                HIPCHK(c, hipMemcpy2DAsync(d, (size_t)width[p], ptr[p], (size_t)pitch[p], (size_t)width[p], (size_t)rows[p], kind, c->stream));
+                cs[k].p[p] = d;
+                cs[k].pitch[p] = width[p];
+                d += round256((size_t)width[p] * rows[p]);
+            }
+        }
+    }
+    next_current(c);
+    {
+        int pw, ph;
+        picture_size(c, &pw, &ph);
+        Timed t(c, VP8HIP_K_PACK);
+        launch_compose(c->stream, c->cur, c->canvas, pw, ph, cs);
+    }
+    return finish_frames(&c, 1, c->stream, nullptr);
+}
+
 }  // namespace vp8
 
 extern "C" {
@@ -248,6 +311,7 @@ extern "C" {
 int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     USE_DEVICE_ONLY(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
+    if (c->in.n_tiles) return VP8HIP_ERR_STATE;      // (a canvas: frames come in through vp8hip_compose_current_*)
     size_t nb[3];      // (the planes of the context's source format: ny, nc, nc for I420)
     incoming_bytes(c, nb);
     const size_t total = nb[0] + nb[1] + nb[2];
@@ -278,6 +342,7 @@ int vp8hip_prefetch_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, c
 int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     USE_DEVICE(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
+    if (c->in.n_tiles) return VP8HIP_ERR_STATE;
     size_t nb[3];
     incoming_bytes(c, nb);
     // a prefetch counts only for the source size and format it was made for: the staging buffers hold the planes' bytes of THAT size and the pack
@@ -307,7 +372,54 @@ int vp8hip_upload_current(vp8hip_ctx *c, const uint8_t *y, const uint8_t *u, con
 int vp8hip_set_current_device(vp8hip_ctx *c, const void *y, const void *u, const void *v) {
     USE_DEVICE(c);
     if (!c || !y || !u || !v) return VP8HIP_ERR_ARG;
+    if (c->in.n_tiles) return VP8HIP_ERR_STATE;
     return take_current(c, y, u, v, hipMemcpyDeviceToDevice);
+}
+
+int vp8hip_canvas_tiles(const vp8hip_ctx *c) { return c ? c->in.n_tiles : 0; }
+
+int vp8hip_compose_current_device(vp8hip_ctx *c, const vp8hip_tile_planes *src) {
+    USE_DEVICE(c);
+    if (!c || !src) return VP8HIP_ERR_ARG;
+    return take_composed(c, src, hipMemcpyDeviceToDevice);
+}
+
+int vp8hip_compose_current_host(vp8hip_ctx *c, const vp8hip_tile_planes *src) {
+    USE_DEVICE(c);
+    if (!c || !src) return VP8HIP_ERR_ARG;
+    const int rc = take_composed(c, src, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    // pageable host memory: the call must not return while a copy still reads the host's planes
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VP8HIP_OK;
+}
+
+int vp8hip_set_canvas(vp8hip_ctx *c, const vp8hip_tile *tiles, int n, int bg_y, int bg_u, int bg_v) {
+    if (!c || n < 0 || n > VP8HIP_MAX_TILES || (n && !tiles)) return VP8HIP_ERR_ARG;
+    IntakeSettings next = c->in;
+    next.n_tiles = n;
+    next.bg[0] = bg_y; next.bg[1] = bg_u; next.bg[2] = bg_v;
+    for (int k = 0; k < n; ++k) next.tile[k] = tiles[k];
+    next = canonical(next, c->W, c->H);
+    if (intake_valid(c->W, c->H, next) != VP8HIP_OK) return VP8HIP_ERR_ARG;      // (here too: the plan below is made of arguments that passed)
+    // a batch's ways in and a by-reference split take one source per frame
+    if (n && (c->batch || c->shard_comm)) return VP8HIP_ERR_STATE;
+    if (next == c->in) return VP8HIP_OK;
+    // everything that can be refused is tried before anything of the context changes
+    ComposePlan plan;
+    if (n) {
+        std::vector<uint8_t> blob;
+        if (!compose_plan_make(&plan, next.tile, n, next.bg, blob)) return VP8HIP_ERR_ARG;
+        (void)hipSetDevice(c->device);
+        HIPCHK(c, hipMalloc(&plan.d_blob, blob.size()));
+        const hipError_t e = hipMemcpy(plan.d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(plan.d_blob); c->last_hip_error = (int)e; return VP8HIP_ERR_HIP; }
+    }
+    const int rc = intake_apply(c, next);
+    if (rc) { (void)hipFree(plan.d_blob); return rc; }
+    (void)hipFree(c->canvas.d_blob);      // (nothing in flight reads the old blob: intake_apply has waited)
+    c->canvas = plan;
+    return VP8HIP_OK;
 }
 
 int vp8hip_set_source_size(vp8hip_ctx *c, int src_width, int src_height) {

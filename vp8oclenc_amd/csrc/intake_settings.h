@@ -21,13 +21,25 @@ struct SourceShape {
     int win_x = 0, win_y = 0;
     int or_turns = 0, or_mirror = 0;          // vp8hip_set_source_orientation
     int di_mode = 0, di_keep = 0;             // vp8hip_set_deinterlace (0 = off, and no parity)
+    // vp8hip_set_canvas: the frame is composed of n_tiles scaled sources (0 = no canvas) over the background bg (Y, U, V)
+    int n_tiles = 0, bg[3] = {0, 0, 0};
+    vp8hip_tile tile[VP8HIP_MAX_TILES] = {};
 };
+inline bool operator==(const vp8hip_tile &a, const vp8hip_tile &b) {
+    return a.in_w == b.in_w && a.in_h == b.in_h && a.x == b.x && a.y == b.y && a.w == b.w && a.h == b.h && a.filter == b.filter;
+}
+inline bool same_canvas(const SourceShape &a, const SourceShape &b) {
+    if (a.n_tiles != b.n_tiles || a.bg[0] != b.bg[0] || a.bg[1] != b.bg[1] || a.bg[2] != b.bg[2]) return false;
+    for (int k = 0; k < VP8HIP_MAX_TILES; ++k)
+        if (!(a.tile[k] == b.tile[k])) return false;
+    return true;
+}
 inline bool operator==(const SourceShape &a, const SourceShape &b) {
     return a.src_w == b.src_w && a.src_h == b.src_h && a.in_w == b.in_w && a.in_h == b.in_h && a.scale_kind == b.scale_kind &&
            a.src_fmt == b.src_fmt && a.src_colour == b.src_colour && a.src_transfer == b.src_transfer && a.src_peak == b.src_peak &&
            a.win_on == b.win_on && a.win_pitch[0] == b.win_pitch[0] && a.win_pitch[1] == b.win_pitch[1] && a.win_pitch[2] == b.win_pitch[2] &&
            a.win_x == b.win_x && a.win_y == b.win_y && a.or_turns == b.or_turns && a.or_mirror == b.or_mirror &&
-           a.di_mode == b.di_mode && a.di_keep == b.di_keep;
+           a.di_mode == b.di_mode && a.di_keep == b.di_keep && same_canvas(a, b);
 }
 // ... and the switches behind it, which work on the coded surface.
 struct IntakeSettings : SourceShape {
@@ -47,6 +59,8 @@ inline IntakeSettings canonical(IntakeSettings s, int W, int H) {
     if (!s.src_transfer) s.src_peak = 0;
     if (!s.win_on) s.win_pitch[0] = s.win_pitch[1] = s.win_pitch[2] = s.win_x = s.win_y = 0;
     if (!s.di_mode) s.di_keep = 0;
+    if (s.n_tiles <= 0) s.n_tiles = s.bg[0] = s.bg[1] = s.bg[2] = 0;
+    for (int k = s.n_tiles < VP8HIP_MAX_TILES ? s.n_tiles : VP8HIP_MAX_TILES; k < VP8HIP_MAX_TILES; ++k) s.tile[k] = vp8hip_tile{};
     if (s.seg_mode != 2) s.seg_strength = 0;
     return s;
 }
@@ -80,8 +94,10 @@ inline int window_rule(const SourceShape &s, int W, int H, size_t off[3], int32_
 // a stage in front of the pack or scale launch reads the planes: they must be in device memory by then
 inline bool needs_device_planes(const SourceShape &s) { return s.src_fmt || s.di_mode || s.in_w || s.win_on || s.or_turns || s.or_mirror; }
 // what a context must not have for a hidden alt-ref frame (vp8hip_arf_filter_*), and to split its frames over devices (vp8hip_shard_init)
-inline bool excludes_arf(const IntakeSettings &s) { return s.src_fmt || s.win_on || s.di_mode || s.dn_level || s.an_on; }
-inline bool excludes_shard(const IntakeSettings &s) { return s.an_on || s.seg_mode; }
+inline bool excludes_arf(const IntakeSettings &s) { return s.src_fmt || s.win_on || s.di_mode || s.dn_level || s.an_on || s.n_tiles; }
+inline bool excludes_shard(const IntakeSettings &s) { return s.an_on || s.seg_mode || s.n_tiles; }
+// ... and to be a member of a batch (vp8hip_batch_create): a canvas takes several sources per frame, a batch's ways in take one
+inline bool excludes_batch(const IntakeSettings &s) { return s.n_tiles != 0; }
 
 // dst of a scaler, or the source size: even, not above the coded size and fewer than 16 below it
 inline bool source_size_ok(int W, int H, int w, int h) {
@@ -110,6 +126,15 @@ inline int intake_valid(int W, int H, const IntakeSettings &s) {
     int32_t rb[3], rows[3];
     if (s.win_on && window_rule(s, W, H, off, rb, rows) != 0) return INTAKE_REFUSED;      // (the window fits its pitches at the raw size, in this format)
     if (s.di_mode < 0 || s.di_mode > 2 || (s.di_keep != 0 && s.di_keep != 1) || (s.di_mode && h < 4)) return INTAKE_REFUSED;   // (every plane needs a row of each field)
+    // a canvas: the frame is composed of its tiles, 8-bit I420 each, scaled and placed by k_compose_b in the place of the pack or scale
+    // launch -- so nothing else stands in front of that launch, both ways round
+    if (s.n_tiles < 0 || s.n_tiles > VP8HIP_MAX_TILES) return INTAKE_REFUSED;
+    if (s.n_tiles) {
+        if (s.in_w || s.in_h || s.src_fmt || s.win_on || s.or_turns || s.or_mirror || s.di_mode) return INTAKE_REFUSED;
+        if (((s.bg[0] | s.bg[1] | s.bg[2]) & ~255) != 0) return INTAKE_REFUSED;
+        for (int k = 0; k < s.n_tiles; ++k)
+            if (!vp8host_tile_valid(pw, ph, &s.tile[k])) return INTAKE_REFUSED;
+    }
     if (s.dn_level < 0 || s.dn_level > 3 || s.seg_mode < 0 || s.seg_mode > 2 || (s.seg_mode == 2 && (s.seg_strength < 1 || s.seg_strength > 3))) return INTAKE_REFUSED;
     return INTAKE_OK;
 }

@@ -26,7 +26,7 @@ struct Tab { const int32_t *start; const int16_t *coef; int n; };      // coef: 
 struct PlaneJob { Plane out; const uint8_t *src; int in_w, in_h; Tab x, y; int tiles_x, tiles; };
 struct Item { PlaneJob p[3]; };
 // the launch's geometry, the same for every member: tile size, LDS layout (byte offsets), source rows per chunk
-struct Geo { int tw, th, pitch, rows, span_y, off_t, off_cx, off_cy, off_sx, off_sy; };
+using Geo = ScaleGeo;
 
 __device__ __forceinline__ void scale_body(const Item &a, const Geo &g, uint8_t *lds) {
     int tile = (int)blockIdx.x;
@@ -153,7 +153,7 @@ static scale::Tab scale_tab(const ScalePlan &p, int k) {
 
 // Tile and LDS layout for a plan: 64 x 32 outputs, halved (height first) until the int16 tile and the tables fit 24 KB; the source
 // rectangle gets what is left of 40 KB, in whole rows.  Luma decides (the chroma planes' spans are never larger).
-static scale::Geo scale_geo(const ScalePlan &p) {
+ScaleGeo scale_geo(const ScalePlan &p) {
     int kx = 3, ky = 2;      // tile = (8 << kx) x (8 << ky)
     scale::Geo g{};
     for (;;) {

@@ -37,6 +37,7 @@ struct vp8drv {
     bool analysis = false;           // vp8drv_set_analysis
     bool in_batch = false;           // a member of a live vp8drv_batch
     bool window = false;             // vp8drv_set_source_window: a window is in force
+    int canvas = 0;                  // vp8drv_set_canvas: tiles of the canvas in force (0 = none)
     // vp8drv_set_arf: strength + 1 (0 = off).  last_hidden: the frame just coded is a hidden one.  rotation_consumed: a hidden frame's
     // transform has applied the reference rotation the last shown frame owed; the next shown frame's must not apply it again.
     // hidden_altref: ALTREF holds a hidden frame's reconstruction (until a key frame or a scheduled shown alt-ref rotates LAST into it).
@@ -412,6 +413,7 @@ extern "C" {
 
 int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const void *v, int force_key) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
+    if (d->canvas) return VP8HIP_ERR_STATE;      // (frames come in through vp8drv_encode_frame_tiles_*)
     { const int rc = resolve(d); if (rc < 0) return rc; }                        // the previous frame's check_SSIM verdict, if still open
     vp8host_gop_next(&d->gop);
     DRV_CHK(intake_restarts(d, d->gop.current_is_key != 0));
@@ -421,6 +423,7 @@ int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const vo
 
 int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v, int force_key) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
+    if (d->canvas) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     vp8host_gop_next(&d->gop);
     const bool staged = d->staged == y;
@@ -441,6 +444,7 @@ int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, cons
 // vp8drv_encode_frame_host that names them has returned.
 int vp8drv_stage_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
+    if (d->canvas) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     if (d->denoise || d->analysis || d->deinterlace) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
         vp8host_gop g = d->gop;
@@ -459,8 +463,36 @@ int vp8drv_stage_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const
 
 int vp8drv_prefetch_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
+    if (d->canvas) return VP8HIP_ERR_STATE;
     return vp8hip_prefetch_current(d->hip, y, u, v);
 }
+
+// vp8drv_set_canvas: frames composed of scaled video tiles from now on (n = 0: one source per frame again)
+int vp8drv_set_canvas(vp8drv *d, const vp8hip_tile *tiles, int n, int bg_y, int bg_u, int bg_v) {
+    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
+    if (n && (d->in_batch || d->arf)) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    DRV_CHK(vp8hip_set_canvas(d->hip, tiles, n, bg_y, bg_u, bg_v));
+    d->canvas = n;
+    d->staged = nullptr;
+    d->staged_scan = false;
+    return VP8HIP_OK;
+}
+
+static int encode_frame_tiles(vp8drv *d, const vp8hip_tile_planes *src, int force_key, bool host) {
+    if (!d || !src) return VP8HIP_ERR_ARG;
+    if (!d->canvas) return VP8HIP_ERR_STATE;
+    for (int k = 0; k < d->canvas; ++k)      // (what the context would refuse, before the schedule moves)
+        if (src[k].y && (!src[k].u || !src[k].v || src[k].pitch_y < 0 || src[k].pitch_u < 0 || src[k].pitch_v < 0)) return VP8HIP_ERR_ARG;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    vp8host_gop_next(&d->gop);
+    DRV_CHK(intake_restarts(d, d->gop.current_is_key != 0));
+    DRV_CHK(host ? vp8hip_compose_current_host(d->hip, src) : vp8hip_compose_current_device(d->hip, src));
+    return frame_body(d, nullptr, d->gop.current_is_key || force_key);
+}
+
+int vp8drv_encode_frame_tiles_device(vp8drv *d, const vp8hip_tile_planes *src, int force_key) { return encode_frame_tiles(d, src, force_key, false); }
+int vp8drv_encode_frame_tiles_host(vp8drv *d, const vp8hip_tile_planes *src, int force_key) { return encode_frame_tiles(d, src, force_key, true); }
 
 // ---- several GOP chunks one frame at a time, every stage one launch for all of them (vp8hip_batch_*) -----------------------
 struct vp8drv_batch {
@@ -476,7 +508,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
     for (int i = 0; i < n; ++i) {
         // the batched loop is the device-parameter loop (what bench.py and a file-to-file transcode run); one launch serves all
         // members, so what travels as ONE kernel argument must agree: quantizer range, check_SSIM on or off, partitions, filter type
-        if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect || drv[i]->arf || drv[i]->rotation_consumed || drv[i]->hidden_altref)
+        if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect || drv[i]->arf || drv[i]->canvas || drv[i]->rotation_consumed || drv[i]->hidden_altref)
             return VP8HIP_ERR_ARG;      // (hidden frames are not batched, nor is a driver whose references a hidden frame still shapes)
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
@@ -864,7 +896,7 @@ int vp8drv_set_arf(vp8drv *d, int strength_plus_one) {
     if (strength_plus_one && (!d->cfg.device_params || d->cfg.overlap_filter || d->format || d->window || d->deinterlace ||
                               d->denoise || d->analysis))
         return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
+    if (d->in_batch || (strength_plus_one && d->canvas)) return VP8HIP_ERR_STATE;      // (a canvas: the window frames bypass the compose launch)
     { const int rc = resolve(d); if (rc < 0) return rc; }
     d->arf = strength_plus_one;
     if (!strength_plus_one && d->arf_st.hidden_frames) (void)vp8hip_arf_result(d->hip, d->arf_st.last_weight);

@@ -681,6 +681,85 @@ int vp8host_scale_taps(int n_in, int n_out, int kind, int32_t *n_taps, int32_t *
 
 }  // extern "C"
 
+// A canvas of scaled video tiles in plain C++ (include/vp8hip_host.h, "CANVAS").
+namespace {
+
+struct TapTable { int32_t n = 0; std::vector<int32_t> start; std::vector<int16_t> coef; };
+
+bool tap_table(int n_in, int n_out, int kind, TapTable *t) {
+    if (n_out < 1) return false;
+    t->start.resize((size_t)n_out);
+    t->coef.resize((size_t)n_out * VP8HOST_SCALE_MAX_TAPS);
+    return vp8host_scale_taps(n_in, n_out, kind, &t->n, t->start.data(), t->coef.data()) == 0;
+}
+
+// one plane of one tile through the two passes, into the rectangle of `out` (rows `stride` apart) whose first sample is `out`
+void compose_plane(const uint8_t *src, int pitch, int in_h, const TapTable &tx, const TapTable &ty, int w, int h, uint8_t *out, int stride) {
+    std::vector<int16_t> t((size_t)in_h * w);
+    for (int r = 0; r < in_h; ++r)
+        for (int i = 0; i < w; ++i) {
+            const uint8_t *s = src + (size_t)r * pitch + tx.start[i];
+            const int16_t *c = &tx.coef[(size_t)i * VP8HOST_SCALE_MAX_TAPS];
+            int acc = 32;
+            for (int k = 0; k < tx.n; ++k) acc += (int)c[k] * (int)s[k];
+            t[(size_t)r * w + i] = (int16_t)(acc >> 6);
+        }
+    for (int j = 0; j < h; ++j)
+        for (int i = 0; i < w; ++i) {
+            const int16_t *c = &ty.coef[(size_t)j * VP8HOST_SCALE_MAX_TAPS];
+            int acc = 1 << 17;
+            for (int k = 0; k < ty.n; ++k) acc += (int)c[k] * (int)t[(size_t)(ty.start[j] + k) * w + i];
+            acc >>= 18;
+            out[(size_t)j * stride + i] = (uint8_t)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp8host_tile_valid(int pw, int ph, const vp8hip_tile *t) {
+    if (!t || pw < 2 || ph < 2 || ((pw | ph) & 1)) return 0;
+    if ((t->in_w | t->in_h | t->x | t->y | t->w | t->h) & 1) return 0;
+    if (t->w < 2 || t->h < 2 || t->x < 0 || t->y < 0 || t->w > pw || t->h > ph || t->x > pw - t->w || t->y > ph - t->h) return 0;
+    if (t->in_w < t->w || t->in_h < t->h || t->in_w > 16384 || t->in_h > 16384 || (t->filter != 0 && t->filter != 1)) return 0;
+    TapTable tab;
+    return tap_table(t->in_w, t->w, t->filter, &tab) && tap_table(t->in_h, t->h, t->filter, &tab) &&
+           tap_table(t->in_w / 2, t->w / 2, t->filter, &tab) && tap_table(t->in_h / 2, t->h / 2, t->filter, &tab);
+}
+
+int vp8host_compose_frame(int pw, int ph, const vp8hip_tile *tiles, int n, int bg_y, int bg_u, int bg_v, const vp8hip_tile_planes *src,
+                          uint8_t *out_y, uint8_t *out_u, uint8_t *out_v) {
+    if (!out_y || !out_u || !out_v || pw < 2 || ph < 2 || ((pw | ph) & 1) || n < 0 || n > VP8HIP_MAX_TILES || (n && (!tiles || !src))) return -1;
+    if (((bg_y | bg_u | bg_v) & ~255) != 0) return -1;
+    for (int k = 0; k < n; ++k) {      // everything that can be refused, before anything is written
+        if (!vp8host_tile_valid(pw, ph, &tiles[k])) return -1;
+        const vp8hip_tile_planes &p = src[k];
+        if (!p.y) continue;
+        if (!p.u || !p.v) return -1;
+        if ((p.pitch_y && p.pitch_y < tiles[k].in_w) || (p.pitch_u && p.pitch_u < tiles[k].in_w / 2) || (p.pitch_v && p.pitch_v < tiles[k].in_w / 2)) return -1;
+    }
+    const int cw = pw / 2, ch = ph / 2;
+    memset(out_y, bg_y, (size_t)pw * ph);
+    memset(out_u, bg_u, (size_t)cw * ch);
+    memset(out_v, bg_v, (size_t)cw * ch);
+    for (int k = 0; k < n; ++k) {
+        const vp8hip_tile &t = tiles[k];
+        const vp8hip_tile_planes &p = src[k];
+        if (!p.y) continue;
+        TapTable x, y, xc, yc;
+        if (!tap_table(t.in_w, t.w, t.filter, &x) || !tap_table(t.in_h, t.h, t.filter, &y) || !tap_table(t.in_w / 2, t.w / 2, t.filter, &xc) ||
+            !tap_table(t.in_h / 2, t.h / 2, t.filter, &yc))
+            return -1;      // (vp8host_tile_valid has said otherwise)
+        compose_plane(p.y, p.pitch_y ? p.pitch_y : t.in_w, t.in_h, x, y, t.w, t.h, out_y + (size_t)t.y * pw + t.x, pw);
+        compose_plane(p.u, p.pitch_u ? p.pitch_u : t.in_w / 2, t.in_h / 2, xc, yc, t.w / 2, t.h / 2, out_u + (size_t)(t.y / 2) * cw + t.x / 2, cw);
+        compose_plane(p.v, p.pitch_v ? p.pitch_v : t.in_w / 2, t.in_h / 2, xc, yc, t.w / 2, t.h / 2, out_v + (size_t)(t.y / 2) * cw + t.x / 2, cw);
+    }
+    return 0;
+}
+
+}  // extern "C"
+
 // The device's temporal denoiser in plain C++ (include/vp8hip_host.h has the rule).
 namespace {
 

@@ -156,6 +156,10 @@ struct vp8hip_ctx {
     // vp8hip_set_source_scaling: current frames come in at in.in_w x in.in_h (0 = no scaling) and k_scale_b makes in.src_w x in.src_h of
     // them (the coded size when those are 0); `scale` is what the launch reads, the tables live in scale.d_blob (an empty plan while in.in_w is 0)
     vp8::ScalePlan scale;
+    // vp8hip_set_canvas: current frames are composed of in.n_tiles scaled sources (0 = no canvas) by k_compose_b, in the place of the
+    // pack or scale launch; `canvas` is what the launch reads (the tiles' geometry and tables live in canvas.d_blob; an empty plan
+    // without a canvas).  Tiles from the host pass through raw_stage, end to end.
+    vp8::ComposePlan canvas;
     // vp8hip_set_source_format: what the three pointers of a current frame are (0 = I420: fmt_stage is not used).  k_convert_b makes tight
     // I420 of the incoming size of them in fmt_stage (tight_i420) and the pack or scale launch reads that.
     // vp8hip_set_source_colour: the colour matrix BGRA / RGBA frames are read with, and a tone-mapped frame is written with.
@@ -476,6 +480,9 @@ int intake_ready(vp8hip_ctx *const *m, int n);
 // planes_read (or nullptr) is recorded behind the pack or scale launch: nothing behind it reads the caller's planes.
 int take_frames(vp8hip_ctx *const *m, const void *const *y, const void *const *u, const void *const *v, int n, hipStream_t s,
                 const hipMemcpyKind *alone = nullptr, hipEvent_t planes_read = nullptr, bool tight = false);
+// ... and what stands behind the pack, scale or compose launch, shared by every way in: planes_read is recorded, then overlay, denoise,
+// analysis, segment map on the members' new current frames.
+int finish_frames(vp8hip_ctx *const *m, int n, hipStream_t s, hipEvent_t planes_read);
 // ---- api_inter.hip ----
 void drop_overflowed_frame(vp8hip_ctx *c);
 int inter_check(const vp8hip_ctx *c, int prev_is_golden, int prev_is_altref, int use_golden, int use_altref);

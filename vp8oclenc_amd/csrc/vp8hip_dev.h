@@ -161,6 +161,10 @@ struct ScanRequest { Plane y; uint32_t *partial, *stats; SegData *sd; int32_t *s
 struct ScaleDim { int n, n_in, n_surf; size_t off_start, off_coef; int max_span[4]; };
 struct ScalePlan { int in_w = 0, in_h = 0, kind = 0; ScaleDim d[4] = {}; uint8_t *d_blob = nullptr; };
 bool scale_plan_make(ScalePlan *p, int in_w, int in_h, int dst_w, int dst_h, int W, int H, int kind, std::vector<uint8_t> &blob);   // false: refused
+// Tile and LDS layout of a plan: tw x th outputs per workgroup (64 x 32 unless the ratio is large), the LDS offsets in bytes, the source
+// rows per chunk (kernels_scale.hip, scale_geo).  k_compose_b walks a tile's rectangle in blocks of this shape.
+struct ScaleGeo { int tw, th, pitch, rows, span_y, off_t, off_cx, off_cy, off_sx, off_sy; };
+ScaleGeo scale_geo(const ScalePlan &p);
 // A member's new frame: planes y, u, v (tight I420 in device memory by now) on their way into the surface f, packed or, through the
 // member's plan, scaled down.
 struct SourceItem { const Frame *f; const void *y, *u, *v; const ScalePlan *plan; };
@@ -169,6 +173,14 @@ struct SourceItem { const Frame *f; const void *y, *u, *v; const ScalePlan *plan
 // the other skip switches sit: the launch of one context, which comes through here too, has never been skipped by it.
 void launch_pack_batch(hipStream_t s, const SourceItem *items, int n, int sw = 0, int sh = 0, int ssy = 0, int ssc = 0);
 void launch_scale_batch(hipStream_t s, const SourceItem *items, int n);
+// kernels_compose.hip: a frame composed of scaled video tiles (vp8hip_set_canvas), ONE launch in the place of the pack or scale launch;
+// the rule is include/vp8hip_host.h's ("CANVAS").  A plan = the tiles' geometry, block shapes and tables in one device block, made by
+// the setter; a launch passes only the frame's pointers and pitches (pitch > 0; y == nullptr: the tile is absent).
+struct ComposePlan { uint8_t *d_blob = nullptr; int n = 0; size_t lds = 0; };
+struct ComposeSource { const uint8_t *p[3]; int32_t pitch[3]; };
+bool compose_plan_make(ComposePlan *p, const vp8hip_tile *tiles, int n, const int bg[3], std::vector<uint8_t> &blob);   // false: refused
+// pw x ph: the picture (the surface beyond it repeats its edge)
+void launch_compose(hipStream_t s, const Frame &f, const ComposePlan &plan, int pw, int ph, const ComposeSource *src);
 // kernels_denoise.hip: temporal noise reduction of the frame just packed or scaled (vp8hip_set_denoise), in place on `cur` against
 // `hist`, the previous current frame as it left this launch; the rule is include/vp8hip_host.h's.  `word` (zero at rest) takes the
 // count of filtered macroblocks and the waves' tickets; the wave with the last ticket writes the record into `host`, seq last.
