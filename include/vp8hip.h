@@ -567,6 +567,33 @@ int vp8hip_arf_filter_host(vp8hip_ctx *ctx, const uint8_t *const (*frames)[3], i
 int vp8hip_arf_result(vp8hip_ctx *ctx, int32_t weights[3]);
 int vp8hip_arf_release(vp8hip_ctx *ctx);
 int vp8hip_loop_filter_hidden(vp8hip_ctx *ctx);
+/* ---- temporal layers (opt-in): the end of a SHOWN inter frame whose reconstruction refreshes the buffer the caller names --------------
+ * The rule that names it -- which references a frame of a two- or three-layer stream searches, what it refreshes and which layer it
+ * belongs to -- is vp8host_temporal_step (include/vp8hip_host.h).  The frame is coded like any inter frame (vp8hip_inter_transform
+ * with the rule's use_golden and use_altref = 0, check_SSIM if wanted) and ENDS with vp8hip_loop_filter_refresh in the place of
+ * vp8hip_loop_filter:
+ *   refresh = VP8HIP_REFRESH_LAST, filter = 1:    vp8hip_loop_filter, exactly.
+ *   refresh = VP8HIP_REFRESH_GOLDEN, filter = 1:  the filter runs and the reconstruction becomes GOLDEN -- a slot assignment, as the
+ *       hidden ending's -- with its replicated edges and its pyramid made behind the filter.  LAST, and what the context knows
+ *       about LAST, stay.
+ *   refresh = VP8HIP_REFRESH_NONE:  the reconstruction is dropped: no frame will read it.  With filter = 0 NOTHING is launched: no
+ *       filter, no edges, no pyramid.  With filter = 1 the filter runs for what rides behind or in its launch.
+ * The frame is shown, so unlike the hidden ending the intake is not stepped back, and the quality measurement, the analysis record and
+ * an armed check_SSIM's verdict follow the filter as they follow vp8hip_loop_filter.  Its bytes: vp8hip_header_params.is_golden =
+ * VP8HIP_GOLDEN_ONLY (refresh_golden_frame = 1, refresh_alternate_frame = 0 with its copy field 0, sign biases 0,
+ * refresh_entropy_probs = 0, refresh_last = 0, show_frame = 1) or VP8HIP_REFRESH_NOTHING (both refresh flags 0, both copy fields 0,
+ * the rest alike); is_altref is not read for either.  No entropy state passes from frame to frame (every frame sends every
+ * probability and the whole segment map), so a stream without the dropped frames decodes.
+ * VP8HIP_ERR_ARG: refresh or filter out of range, filter = 0 with a refresh other than NONE.  VP8HIP_ERR_STATE, for GOLDEN and NONE:
+ * no inter reconstruction, a member of a batch, a context that shares a frame's searches with other devices, a context with
+ * vp8hip_filter_overlap (the next frame's GOLDEN search would start beside the filter that writes GOLDEN), and filter = 0 with an
+ * armed check_SSIM (the verdict rides in the filter's launch). */
+#define VP8HIP_REFRESH_LAST 0
+#define VP8HIP_REFRESH_GOLDEN 1
+#define VP8HIP_REFRESH_NONE 2
+#define VP8HIP_GOLDEN_ONLY 2
+#define VP8HIP_REFRESH_NOTHING 3
+int vp8hip_loop_filter_refresh(vp8hip_ctx *ctx, int refresh, int filter);
 /* on = 1: the context gets a second stream, and work that does not depend on the filtered frame runs beside the loop filter:
  * the entropy stage of the same frame (vp8hip_count_probs ... vp8hip_encode_frame), the next frame's upload, parameter scan
  * and GOLDEN / ALTREF searches.  The filter stays on the stream the frame was coded on and the CONTEXT moves to the other one
@@ -614,7 +641,9 @@ int vp8hip_encode_coefficients(vp8hip_ctx *ctx, const uint32_t *coeff_probs, int
 #define VP8HIP_SHARPNESS_ON_DEVICE INT32_MIN
 typedef struct {
     int32_t is_key, is_golden, is_altref;    /* frames.current_is_{key,golden,altref}_frame; is_altref = VP8HIP_ALTREF_HIDDEN (inter frames): a
-                                                hidden frame -- show_frame = 0 in the frame tag, refresh_alternate = 1, refresh_last = 0 */
+                                                hidden frame -- show_frame = 0 in the frame tag, refresh_alternate = 1, refresh_last = 0;
+                                                is_golden = VP8HIP_GOLDEN_ONLY / VP8HIP_REFRESH_NOTHING (inter frames): a shown frame of a
+                                                temporal layer that refreshes GOLDEN only / no buffer (vp8hip_loop_filter_refresh) */
     int32_t loop_filter_type;                /* video.loop_filter_type: 0 normal, 1 simple -- the filter the context applies (vp8hip_set_loop_filter_type) */
     int32_t loop_filter_sharpness;           /* video.loop_filter_sharpness; VP8HIP_SHARPNESS_ON_DEVICE = the value vp8hip_auto_segments
                                                 computed.  (Not -1: get_loopfilter_strength's `int` accumulator overflows on large noisy
@@ -717,7 +746,10 @@ const char *vp8hip_status_string(int status);
  * vp8drv_clear_overlay; entry points only: vp8drv_config is unchanged);
  * also under 4010: canvases (vp8hip_set_canvas, vp8hip_canvas_tiles, vp8hip_compose_current_device, vp8hip_compose_current_host,
  * vp8host_tile_valid, vp8host_compose_frame, vp8drv_set_canvas, vp8drv_encode_frame_tiles_device, vp8drv_encode_frame_tiles_host;
- * entry points and the types vp8hip_tile and vp8hip_tile_planes only: vp8drv_config is unchanged). */
+ * entry points and the types vp8hip_tile and vp8hip_tile_planes only: vp8drv_config is unchanged);
+ * also under 4010: temporal layers (vp8host_temporal_step, vp8hip_loop_filter_refresh, vp8drv_set_temporal_layers,
+ * vp8drv_get_frame_layer; entry points, the type vp8drv_layer_info and the values VP8HIP_GOLDEN_ONLY and VP8HIP_REFRESH_NOTHING of
+ * the existing is_golden fields only: vp8drv_config, vp8drv_stats, vp8hip_header_params and vp8bs_frame keep their layout). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

@@ -30,7 +30,9 @@ typedef struct {
     int32_t width, height;            /* video.dst_width / dst_height: written into key frames (:1244-1247) */
     int32_t mb_width, mb_height;
     int32_t is_key, is_golden, is_altref;          /* frames.current_is_{key,golden,altref}_frame; is_altref = 2 (VP8HIP_ALTREF_HIDDEN, inter
-                                                      frames): a hidden frame -- show_frame = 0, refresh_alternate = 1, refresh_last = 0 */
+                                                      frames): a hidden frame -- show_frame = 0, refresh_alternate = 1, refresh_last = 0; is_golden = 2 /
+                                                      3 (VP8HIP_GOLDEN_ONLY / VP8HIP_REFRESH_NOTHING, inter frames): a shown frame of a temporal
+                                                      layer -- refresh_golden = 1 / 0, refresh_alternate = 0, no buffer copies, refresh_last = 0 */
     int32_t loop_filter_type;         /* video.loop_filter_type (0 in the reference, init.h:1583; 1 = simple filter, vp8hip_set_loop_filter_type) */
     int32_t loop_filter_sharpness;    /* video.loop_filter_sharpness as left by prepare_segments_data */
     int32_t partitions_log2;          /* video.number_of_partitions_ind: 0..3 */

@@ -387,6 +387,42 @@ int vp8drv_set_arf(vp8drv *d, int strength_plus_one);
 int vp8drv_encode_arf_device(vp8drv *d, const void *const (*frames)[3], int n, int centre);
 int vp8drv_encode_arf_host(vp8drv *d, const uint8_t *const (*frames)[3], int n, int centre);
 int vp8drv_get_arf_stats(vp8drv *d, vp8drv_arf_stats *s);
+/* ---- temporal layers (the rule: vp8host_temporal_step, include/vp8hip_host.h; the ending: vp8hip_loop_filter_refresh, include/vp8hip.h) ----
+ * A stream of two or three temporal layers, the patterns WebRTC runs VP8 with: a forwarding unit may drop every frame above a layer
+ * and what is left still decodes.  Entry points and not fields of vp8drv_config for the reason vp8drv_set_denoise is one.
+ * vp8drv_set_temporal_layers: layers 1 (default, off) to 3; flags: VP8DRV_TL_KEEP_RECON or 0.  It takes the open check_SSIM verdict first.
+ * The layer count is IN FORCE FROM THE NEXT KEY FRAME ON, whoever asks for that key frame (the GOP schedule, force_key, a scene cut, a
+ * frame sent back by check_SSIM) -- before the first frame that is the first frame; until then the frames are coded as they were, so
+ * turning layers on or off in the middle of a GOP never leaves a receiver with a half pattern.  The flags are in force at once.
+ * With layers in force an inter frame takes its references and its ending from the rule in the place of the GOP state's flags: p counts
+ * the shown frames since the last key frame as finally coded, ALTREF is never searched, every frame is quantised on the lastqi ladder,
+ * vp8drv_stats.refs_searched advances by 1 + use_golden.  The rotation a key frame owes is applied by the next frame's transform as ever.
+ * A closed GOP coded as a chunk of its own (a fresh driver, force_key) gives the bytes the serial program gives.  Everything on the input
+ * side -- canvas, overlays, formats, scaler, denoiser, deinterlacer, the per-macroblock quantiser, analysis, scene detection --
+ * composes unchanged: it follows the frames taken in, not the references.
+ * A frame that refreshes nothing is FILTERED only if something reads the filter's output or rides in its launch: cfg.check_ssim,
+ * cfg.quality_stats, vp8drv_set_analysis or VP8DRV_TL_KEEP_RECON (for a caller that reads the reconstruction back).  Otherwise no
+ * filter, no edge and no pyramid launch is made for it; its bytes are the same either way.
+ * VP8HIP_ERR_ARG, for layers > 1: cfg.device_params = 0, cfg.overlap_filter, cfg.altref_range <= cfg.gop_size (scheduled alt-refs must
+ * be off, by the convention of vp8drv_encode_arf_device); and layers or flags out of range.  VP8HIP_ERR_STATE, for layers > 1: a member
+ * of a live batch (vp8drv_batch_create in turn refuses such a driver: layers are not batched), vp8drv_set_arf on (which in turn refuses
+ * while layers are on or asked for), a context that shares a frame's searches with other devices -- and if the context joins such a
+ * split later, the calls that take a frame in.  Nothing has changed after a refusal.
+ * vp8drv_get_frame_layer: the frame just made final, valid after vp8drv_resolve or vp8drv_get_frame (it takes the open verdict itself:
+ * a frame coded again as a key frame has the key frame's record); for any driver, layers or not.  VP8HIP_ERR_STATE: no frame coded yet,
+ * or the frame just coded is a hidden one.  What an RTP VP8 payload descriptor carries: INTEGRATION.md, section 6.6. */
+#define VP8DRV_TL_KEEP_RECON 1
+typedef struct {
+    int32_t temporal_id;      /* 0 = the base layer; key frames are 0 */
+    int32_t tl0_pic_idx;      /* a running index of the temporal_id 0 frames, key frames included, modulo 256: the first frame's is 0, a
+                                 frame of a higher layer carries the index of the base frame before it */
+    int32_t layer_sync;       /* 1: the frame reads temporal layer 0 only (a receiver may start taking this layer here) */
+    int32_t refresh;          /* VP8HOST_REFRESH_LAST, _GOLDEN, _NONE; _ALL for a key frame */
+    int32_t use_golden;       /* GOLDEN was searched beside LAST */
+    int32_t filtered;         /* the loop filter ran on its reconstruction */
+} vp8drv_layer_info;
+int vp8drv_set_temporal_layers(vp8drv *d, int layers, int flags);
+int vp8drv_get_frame_layer(vp8drv *d, vp8drv_layer_info *info);
 
 #ifdef __cplusplus
 }

@@ -477,6 +477,35 @@ void vp8host_gop_inter_flags(const vp8host_gop *g, int32_t *use_golden, int32_t 
 /* ++frames.frame_number at the end of the loop body, vp8enc.cpp:487 */
 void vp8host_gop_frame_done(vp8host_gop *g);
 
+/* TEMPORAL LAYERS: which references a shown frame searches, which buffer its reconstruction refreshes and which temporal layer it
+ * belongs to, so that a forwarding unit can drop every frame above a layer and what is left still decodes (the patterns WebRTC runs
+ * VP8 with).  p = the number of shown frames coded since the last key frame AS FINALLY CODED: the key frame itself is p = 0, and a
+ * frame that is forced to be a key frame, or sent back and coded again as one, restarts p -- so the pattern restarts at every key
+ * frame, and a closed GOP coded as a chunk of its own gives the bytes the serial program gives.  ref_mask bit 0: GOLDEN may be searched
+ * (vp8drv_config.ref_mask).
+ *   layers = 1:  every frame temporal_id 0, searches LAST, refreshes LAST.
+ *   layers = 2 (period 2):
+ *     p % 2 == 0:  temporal_id 0, searches LAST, refreshes LAST
+ *     p % 2 == 1:  temporal_id 1, searches LAST, refreshes NONE, layer_sync 1
+ *   layers = 3 (period 4):
+ *     p % 4 == 0:  temporal_id 0, searches LAST, refreshes LAST
+ *     p % 4 == 1:  temporal_id 2, searches LAST, refreshes NONE, layer_sync 1
+ *     p % 4 == 2:  temporal_id 1, searches LAST, refreshes GOLDEN only, layer_sync 1
+ *     p % 4 == 3:  temporal_id 2, searches LAST and (with ref_mask & 1) GOLDEN, refreshes NONE, layer_sync = !use_golden
+ *   p = 0, the key frame:  temporal_id 0, searches nothing, refresh = VP8HOST_REFRESH_ALL, layer_sync 0, whatever `layers`.
+ * ALTREF is never searched, and every layer takes its quantisers from the lastqi ladder (vp8host_quantizer_ladders).  layer_sync = 1:
+ * the frame depends on temporal layer 0 only, so a receiver may start taking its layer at it.  LAST always holds a temporal_id 0 frame
+ * and GOLDEN a frame of temporal_id <= 1 that is newer than LAST when it is searched: a frame never reads a frame of a higher layer.
+ * Returns 0, or -1 and leaves *out alone: layers outside 1 .. 3, p < 0, out NULL.  Plain C, no state. */
+#define VP8HOST_REFRESH_LAST 0
+#define VP8HOST_REFRESH_GOLDEN 1
+#define VP8HOST_REFRESH_NONE 2
+#define VP8HOST_REFRESH_ALL 3
+typedef struct {
+    int32_t temporal_id, use_golden, refresh, layer_sync;
+} vp8host_temporal;
+int vp8host_temporal_step(int layers, int p, int ref_mask, vp8host_temporal *out);
+
 /* The key-frame schedule of a whole file with scene detection on, from the chroma differences of its frames alone: nothing but the
  * frame loop's own steps (vp8enc.cpp:364-416, 487), for t = 0 .. nframes - 1:
  *     vp8host_gop_next;

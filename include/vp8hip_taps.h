@@ -59,9 +59,12 @@ typedef enum {
     VP8HIP_DBG_MB_NZ,      /* -           : int[MBs]                                              */
     VP8HIP_DBG_THIRD_CONTEXT, /* -        : uchar[MBs][25] (entries of coded macroblocks, after vp8hip_count_probs) */
     VP8HIP_DBG_CURRENT_CHROMA, /* ref 0 = U, 1 = V : tight (W/2)x(H/2) plane of the current frame (after copy_with_padding) */
-    VP8HIP_DBG_ARF_FRAME      /* ref 0, 1, 2 = Y, U, V of the frame as it left the temporal filter (vp8hip_arf_filter_device): tight planes of
+    VP8HIP_DBG_ARF_FRAME,     /* ref 0, 1, 2 = Y, U, V of the frame as it left the temporal filter (vp8hip_arf_filter_device): tight planes of
                                  the incoming size, before the intake; ref 3, 4, 5 = Y, U, V of the ALTREF surface at the coded size (behind
                                  vp8hip_loop_filter_hidden: the hidden frame's filtered reconstruction) */
+    VP8HIP_DBG_REFRESH_FRAME   /* ref 0, 1, 2 = Y, U, V of the surface the last vp8hip_loop_filter_refresh with GOLDEN or NONE ended: the frame's
+                                 reconstruction at the coded size (filtered if the call filtered).  A dropped reconstruction's surface is free: read
+                                 it before the next frame is coded */
 } vp8hip_debug_id;
 int vp8hip_debug_download(vp8hip_ctx *ctx, int what, int ref, int level, void *dst, size_t bytes);
 /* The quality kernel (vp8hip_set_quality_stats) on caller planes in host memory: a source and a reconstruction of width x height

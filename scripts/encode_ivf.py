@@ -22,6 +22,12 @@ tool writes with -no-scene-detect (with --arf this script does not detect scenes
 counter, so rank 0 first scans the chroma differences of the whole sequence in batches on the device (gop_shard.scan_differences),
 api.scene_plan makes the serial loop's own key-frame schedule of them, gop_shard.chunks_from_keys the chunks, and the ranks shard those as
 they shard the fixed ones.  Not with --denoise, --deinterlace adaptive, --analysis or --arf: their histories follow the frames taken in.
+--temporal-layers N [--keep-layers K]: a stream of N = 1..3 temporal layers (vp8drv_set_temporal_layers; the rule: vp8host_temporal_step,
+include/vp8hip_host.h): the file scripts/native/y4m_to_ivf -temporal-layers N writes with the matching settings.  The script sets
+altref_range to the GOP size + 1 itself (scheduled alt-refs off) and turns the overlapped filter off.  --keep-layers K writes only the
+frames of temporal_id <= K -- what a forwarding unit sends a slow receiver -- each with its own timestamp; the header's frame count is then
+the number of frames written (a thinned file is not one the reference's program writes: its off-by-one is not reproduced).  One
+process; not with --arf.
 --canvas with --tile FILE.yuv:INWxINH:X:Y:W:H[:area|lanczos] (repeatable, in tile order; up to 16): the picture of --width x --height is
 composed on the device of the tiles' frames (vp8drv_set_canvas, vp8drv_encode_frame_tiles_host) -- every FILE holds tight I420 frames of
 INW x INH, scaled to W x H and placed at (X, Y); a file that ends makes its tile absent from then on; --canvas-bg Y,U,V is what no tile
@@ -140,6 +146,9 @@ def main():
     ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation of the inter frames at strength N: flat macroblocks take the finer segments of the quantiser ladder, busy ones the coarser (vp8drv_set_segment_mode, mode 2)")
     ap.add_argument("--segment-map", default="", metavar="FILE", help="the caller's segment map for every inter frame: one byte 0..3 per macroblock of the coded picture, raster order (vp8drv_set_segment_mode, mode 1)")
     ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames made by temporal filtering on the device (vp8drv_set_arf, vp8drv_encode_arf_host): one in front of every group of PERIOD frames of a GOP, centred on the group's last frame, FRAMES frames wide (default 7) at STRENGTH 0..6 (default 3)")
+    ap.add_argument("--no-check-ssim", action="store_true", help="cfg.check_ssim = 0, scripts/native/y4m_to_ivf's -no-check-ssim: no check_SSIM behind the inter frames (with --temporal-layers the unreferenced frames are then not loop-filtered)")
+    ap.add_argument("--temporal-layers", type=int, choices=(1, 2, 3), default=0, metavar="N", help="a stream of N temporal layers (vp8drv_set_temporal_layers): it still decodes when the frames above a layer are dropped")
+    ap.add_argument("--keep-layers", type=int, choices=(0, 1, 2), default=None, metavar="K", help="with --temporal-layers: write only the frames of temporal_id <= K, with their own timestamps")
     ap.add_argument("--scene-detect", action="store_true", help="key frames where the serial program with scene detection puts them: the sequence is scanned first (gop_shard.scan_differences), api.scene_plan gives the chunks")
     ap.add_argument("--scan-batch", type=int, default=8, metavar="N", help="... members of the scanning batch (1..8)")
     ap.add_argument("--canvas", action="store_true", help="compose the picture of --width x --height of the --tile sources on the device (vp8drv_set_canvas)")
@@ -160,6 +169,10 @@ def main():
             sys.exit(f"--arf {a.arf}: {e}")
         if a.denoise or a.deinterlace != "off" or a.analysis or a.surface:
             sys.exit("--arf does not go with --denoise, --deinterlace, --analysis or --surface")
+    if a.keep_layers is not None and not a.temporal_layers:
+        sys.exit("--keep-layers goes with --temporal-layers")
+    if a.temporal_layers and (arf or int(os.environ.get("WORLD_SIZE", 1)) > 1):
+        sys.exit("--temporal-layers: one process, and not with --arf (layers never search ALTREF)")
     if a.aq and a.segment_map:
         sys.exit("--aq and --segment-map: one of them picks the segments")
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -222,8 +235,18 @@ def main():
     t0 = time.perf_counter()
     def make_encoder(scan=False):
         enc = gop_shard.NativeEncoder(Wc, Hc, device=local, **src, num_partitions=a.partitions, qi_min=a.qmin, qi_max=a.qmax,
-                                      ssim_target=a.ssim_target, check_ssim=1, conformant_stream=int(a.conformant),
-                                      loop_filter_type=int(a.simple_filter), **(dict(overlap_filter=0) if arf or scan else {}))      # (nor are members of a batch)
+                                      ssim_target=a.ssim_target, check_ssim=int(not a.no_check_ssim), conformant_stream=int(a.conformant),
+                                      loop_filter_type=int(a.simple_filter), **(dict(overlap_filter=0) if arf or scan or a.temporal_layers else {}),      # (nor are members of a batch)
+                                      **(dict(gop_size=1 << 30, altref_range=(1 << 30) + 1) if a.temporal_layers else {}))      # (a chunk is one GOP; scheduled alt-refs off)
+        if a.temporal_layers and not scan:      # every frame's layer next to its bytes
+            enc.drv.set_temporal_layers(a.temporal_layers)
+            plain_encode = enc.encode
+
+            def encode_layered(y, u, v):
+                b = plain_encode(y, u, v)
+                tids.append(enc.drv.frame_layer().temporal_id)
+                return b
+            enc.encode = encode_layered
         if arf:      # (the driver refuses the filter's own stream beside hidden frames)
             enc.drv.set_arf(arf[2] + 1)
         if a.denoise:
@@ -256,7 +279,7 @@ def main():
                 return b
             enc.encode = encode
         return enc
-    records = []
+    records, tids = [], []
     if a.analysis and world > 1:
         sys.exit("--analysis: one process only (the records are not gathered over ranks)")
     if arf:      # the plain loop with the lookahead the frame source gives: a hidden frame is a record of its own
@@ -300,6 +323,17 @@ def main():
         with open(a.analysis, "w") as f:
             f.write("".join(f"{t} {line}\n" for t, line in enumerate(records)))
     allf = gop_shard.gather_frames(mine, frames, dist)
+    if a.temporal_layers:      # (one process: tids[t] is frame t's layer)
+        kept = [(t, b) for t, b in enumerate(allf) if a.keep_layers is None or tids[t] <= a.keep_layers]
+        if a.keep_layers is None:
+            n = gop_shard.write_ivf(a.out, allf, Wd, Hd, a.framerate)
+        else:
+            n = gop_shard.write_ivf_records(a.out, kept, Wd, Hd, a.framerate, count=len(kept))
+        el = time.perf_counter() - t0
+        print(f"{a.out}: {len(kept)} of {frames} frames {Win}x{Hin}, {a.temporal_layers} temporal layers (frames in layer 0 / 1 / 2: "
+              f"{' / '.join(str(tids.count(k)) for k in range(3))}){'' if a.keep_layers is None else f', layers <= {a.keep_layers} kept'}, {n} bytes, "
+              f"{frames / el:.1f} frames/s including the host-side frame source{plan}")
+        return
     if rank == 0:
         n = gop_shard.write_ivf(a.out, allf, Wd, Hd, a.framerate)
         el = time.perf_counter() - t0

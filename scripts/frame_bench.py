@@ -40,6 +40,8 @@ ap.add_argument("--mirror", action="store_true", help="... behind a left-right f
 ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the frame analysis record of every frame (vp8drv_set_analysis): what k_analyse_src_b and k_analyse_mb_b cost")
 ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation at strength N (vp8drv_set_segment_mode, mode 2): what k_aq_map_b + k_aq_seg_b cost, and with one stream the mapped macroblock kernel next to the default's in the same run")
 ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames (vp8drv_set_arf, vp8drv_encode_arf_device): every stream codes one in front of every PERIOD-th frame from a window of FRAMES device-resident frames (default 7) at STRENGTH (default 3); with one stream also what k_arf_filter_b costs by HIP events")
+ap.add_argument("--temporal-layers", type=int, choices=(1, 2, 3), default=1, metavar="N", help="a stream of N temporal layers (vp8drv_set_temporal_layers): with N > 1 scheduled alt-refs are off (--altref-range above the GOP) and the unreferenced frames are loop-filtered only if --check-ssim, --quality-stats or --analysis reads the filter's launch")
+ap.add_argument("--altref-range", type=int, default=5, metavar="N", help="vp8drv_config.altref_range (default 5, the driver's); above the GOP size = no scheduled alt-refs, what --temporal-layers 2 and 3 run with: the base to compare them with")
 ap.add_argument("--tiles", choices=("", "letterbox", "grid4", "pip"), default="", metavar="LAYOUT", help="compose every frame of device-resident tiles (vp8drv_set_canvas): letterbox, grid4 or pip; with one stream also what k_compose_b costs by HIP events")
 ap.add_argument("--tiles-precomposed", action="store_true", help="with --tiles: the same pictures composed on the host beforehand and handed over as plain frames")
 ap.add_argument("--switch-interval", type=float, default=0.0, help="sys.setswitchinterval (0 = Python's default 5 ms)")
@@ -125,7 +127,11 @@ if a.tiles:      # the sources: a synthetic sequence per tile, device-resident, 
     print(f"--tiles {a.tiles}{' (composed on the host beforehand)' if a.tiles_precomposed else ''}: " + ", ".join(f"{t[0]}x{t[1]} -> {t[4]}x{t[5]} at ({t[2]}, {t[3]})" for t in tiles))
 dev = [tuple(api.to_device(p) for p in f) for f in host]
 api.device_synchronize()
-drvs = [api.NativeDriver(W, H, gop_size=1 << 30, num_partitions=a.partitions, check_ssim=a.check_ssim,
+GOP = 1 << 30
+if a.temporal_layers > 1 and a.arf:
+    sys.exit("--temporal-layers does not go with --arf")
+altref = dict(altref_range=GOP + 1) if a.temporal_layers > 1 else dict(altref_range=a.altref_range) if a.altref_range != 5 else {}
+drvs = [api.NativeDriver(W, H, gop_size=GOP, num_partitions=a.partitions, check_ssim=a.check_ssim, **altref,
                          loop_filter_type=a.loop_filter_type, quality_stats=a.quality_stats, **scale) for _ in range(a.streams)]
 if tile_dev:
     for d in drvs:
@@ -164,6 +170,9 @@ arf = gop_shard.parse_arf(a.arf) if a.arf else None
 if arf:
     for d in drvs:
         d.set_arf(arf[2] + 1)
+if a.temporal_layers > 1:
+    for d in drvs:
+        d.set_temporal_layers(a.temporal_layers)
 sizes = [0] * a.streams
 hidden_coded = [0] * a.streams
 
@@ -267,6 +276,13 @@ if arf:
         ms, n = d.hip.profile_read().get("pack", (0.0, 0))
         d.hip.profile_enable([])
         print(f"k_arf_filter_b, window of {st.last_frames}: {(ms / 8 - pack_ms) * 1e3:.1f} us per launch (the stage's {n} launches over 8 hidden frames minus the pack launch's {pack_ms * 1e3:.1f} us)")
+if a.temporal_layers > 1:
+    period = 2 * (a.temporal_layers - 1)
+    steps = [api.temporal_step(a.temporal_layers, p) for p in range(1, period + 1)]
+    info = drvs[0].frame_layer()
+    print(f"temporal layers {a.temporal_layers}: of every {period} inter frames {sum(s['refresh'] == api.REFRESH_NONE for s in steps)} refresh no buffer and "
+          f"{sum(s['use_golden'] for s in steps)} search GOLDEN beside LAST; stream 0's last frame: temporal_id {info.temporal_id}, tl0_pic_idx {info.tl0_pic_idx}, "
+          f"{'loop-filtered' if info.filtered else 'not loop-filtered'}")
 if a.quality_stats:
     q = drvs[0].quality_summary()
     print(f"quality of stream 0 over {q.frames} frames: PSNR overall {q.psnr_all:.3f} dB, avg {q.psnr_avg:.3f} dB, SSIM {q.ssim_all:.5f}")

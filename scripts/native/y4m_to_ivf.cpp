@@ -3,7 +3,11 @@
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
 //              [-input-format NAME] [-input-transfer pq|hlg[:PEAK]] [-overlay FILE:WxH:X:Y[:OPACITY]] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
-//              [-arf PERIOD[:FRAMES[:STRENGTH]]]
+//              [-arf PERIOD[:FRAMES[:STRENGTH]]] [-temporal-layers N]
+// -temporal-layers N (1..3): a stream of N temporal layers (vp8drv_set_temporal_layers; the rule: include/vp8hip_host.h,
+// vp8host_temporal_step), which still decodes when every frame above a layer is dropped.  The option sets -altref-range to the GOP
+// size + 1 (scheduled alt-refs off), turns the overlapped loop filter off and with it the early hand-over of the next frame: this mode
+// is a plain loop too (read, code, take the bytes, write).  The frames per layer are printed next to the summary.  Not with -arf.
 // -arf PERIOD[:FRAMES[:STRENGTH]] (FRAMES 1..7, default 7; STRENGTH 0..6, default 3): hidden alternate reference frames
 // (vp8drv_set_arf, vp8drv_encode_arf_host; libvpx's --auto-alt-ref=1 --arnr-maxframes --arnr-strength).  In front of the first frame of
 // every group of PERIOD frames of a GOP -- behind the key frame for the GOP's first group -- a hidden frame is coded, made by temporal
@@ -87,6 +91,7 @@ int main(int argc, char **argv) {
     int turns = 0, mirror = 0;      // -rotate, -mirror
     const char *analysis_path = nullptr;      // -analysis
     int arf_period = 0, arf_frames = 7, arf_strength = 3;      // -arf
+    int layers = 0;          // -temporal-layers (0: the option was not given)
     static const char *const format_names[VP8HOST_FORMAT_COUNT] = {"i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"};
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
@@ -159,6 +164,10 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (!strcmp(argv[i], "-temporal-layers")) {
+            layers = atoi(val());
+            if (layers < 1 || layers > 3) { fprintf(stderr, "-temporal-layers 1..3\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -172,6 +181,12 @@ int main(int argc, char **argv) {
         if (denoise || deint || analysis_path || crop[0] || !overlays.empty()) { fprintf(stderr, "-arf does not go with -denoise, -deinterlace, -analysis, -crop or -overlay\n"); return 2; }
         cfg.overlap_filter = 0;    // (the next frame's ALTREF search would start beside the filter that writes ALTREF; the key frames stay where they are without the option)
         fprintf(stderr, "-arf: the loop filter runs on the frame's own stream in this mode (no frame is handed over early)\n");
+    }
+    if (layers) {
+        if (arf_period) { fprintf(stderr, "-temporal-layers does not go with -arf (layers never search ALTREF)\n"); return 2; }
+        cfg.altref_range = cfg.gop_size + 1;      // scheduled alt-refs off
+        cfg.overlap_filter = 0;                   // (the next frame's GOLDEN search would start beside the filter that writes GOLDEN)
+        fprintf(stderr, "-temporal-layers: the loop filter runs on the frame's own stream in this mode (no frame is handed over early)\n");
     }
     FILE *in = fopen(argv[1], "rb");
     if (!in) { perror(argv[1]); return 1; }
@@ -251,6 +266,8 @@ int main(int argc, char **argv) {
     if (turns || mirror) CK(vp8drv_set_source_orientation(drv, turns, mirror));
     if (crop[0]) CK(vp8drv_set_source_window(drv, pitch, crop[2], crop[3]));
     if (deint) CK(vp8drv_set_deinterlace(drv, deint, field));
+    if (layers) CK(vp8drv_set_temporal_layers(drv, layers, 0));
+    uint32_t per_layer[3] = {0, 0, 0}, unfiltered = 0;
     long long dn_filtered = 0, dn_total = 0, di_woven = 0, di_missing = 0;
     FILE *analysis = nullptr;
     vp8drv_analysis an{};      // the record of the frame whose bytes are still to be taken
@@ -421,6 +438,20 @@ int main(int argc, char **argv) {
         prefetched = rd_tail;
         return vp8drv_prefetch_frame_host(drv, p[0], p[1], p[2]);
     };
+    auto write_frame = [&](size_t size) {      // a frame's bytes as an IVF record, and its analysis line
+        uint8_t ph[12];
+        fwrite(ph, 1, vp8bs_ivf_frame_header(ph, (uint32_t)size, n), out);
+        fwrite(bytes.data(), 1, size, out);
+        total += 12 + size;
+        if (analysis)
+            fprintf(analysis, "%d %d %zu %d %d %llu %llu %llu %d %d %d %d %d %d %d %d %d %d %d %d %d %llu %llu %lld %lld %llu %llu\n", an.frame_number,
+                    an.is_key, size, an.have_prev, an.static_mbs, (unsigned long long)an.spatial, (unsigned long long)an.temporal_sse,
+                    (unsigned long long)an.temporal_sad, an.coded, an.mbs_total, an.mbs_intra, an.mbs_split, an.mbs_zero_mv, an.mbs_no_coeffs,
+                    an.mbs_ref[0], an.mbs_ref[1], an.mbs_ref[2], an.segment_mbs[0], an.segment_mbs[1], an.segment_mbs[2], an.segment_mbs[3],
+                    (unsigned long long)an.mv_abs_sum[0], (unsigned long long)an.mv_abs_sum[1], (long long)an.mv_sum[0], (long long)an.mv_sum[1],
+                    (unsigned long long)an.mv_sq_sum, (unsigned long long)an.nz_coeffs);
+        ++n;
+    };
     const auto t_loop = std::chrono::steady_clock::now();      // (the frame loop by the host's clock: what scripts/drop_in_bench.py quotes as fps_loop)
     for (;;) {
         const int have = peek(true);
@@ -448,23 +479,26 @@ int main(int argc, char **argv) {
                 di_woven += is.woven;
                 di_missing += is.missing;
             }
-            CK(prefetch_next());
+            if (!layers) CK(prefetch_next());
+        }
+        if (layers && got) {      // the plain loop: this frame's bytes now, its type final behind them
+            size_t size = 0;
+            CK(vp8drv_get_frame(drv, bytes.data(), bytes.size(), &size));
+            const int key = vp8drv_resolve(drv);
+            CK(key);
+            keys += key;
+            if (analysis) CK(vp8drv_get_frame_analysis(drv, &an));
+            vp8drv_layer_info li;
+            CK(vp8drv_get_frame_layer(drv, &li));
+            per_layer[li.temporal_id]++;
+            unfiltered += !li.filtered;
+            write_frame(size);
+            continue;
         }
         if (pending) {      // the previous frame's bytes
             size_t size = 0;
             CK(vp8drv_get_frame_end(drv, bytes.data(), bytes.size(), &size));
-            uint8_t ph[12];
-            fwrite(ph, 1, vp8bs_ivf_frame_header(ph, (uint32_t)size, n), out);
-            fwrite(bytes.data(), 1, size, out);
-            total += 12 + size;
-            if (analysis)
-                fprintf(analysis, "%d %d %zu %d %d %llu %llu %llu %d %d %d %d %d %d %d %d %d %d %d %d %d %llu %llu %lld %lld %llu %llu\n", an.frame_number,
-                        an.is_key, size, an.have_prev, an.static_mbs, (unsigned long long)an.spatial, (unsigned long long)an.temporal_sse,
-                        (unsigned long long)an.temporal_sad, an.coded, an.mbs_total, an.mbs_intra, an.mbs_split, an.mbs_zero_mv, an.mbs_no_coeffs,
-                        an.mbs_ref[0], an.mbs_ref[1], an.mbs_ref[2], an.segment_mbs[0], an.segment_mbs[1], an.segment_mbs[2], an.segment_mbs[3],
-                        (unsigned long long)an.mv_abs_sum[0], (unsigned long long)an.mv_abs_sum[1], (long long)an.mv_sum[0], (long long)an.mv_sum[1],
-                        (unsigned long long)an.mv_sq_sum, (unsigned long long)an.nz_coeffs);
-            ++n;
+            write_frame(size);
             pending = false;
         }
         if (!got) break;
@@ -509,6 +543,9 @@ int main(int argc, char **argv) {
     for (int k = 0; k < RING; ++k) vp8hip_host_free(0, buf[k]);
     printf("%s: %u frames %dx%d (coded %dx%d), %u key (%d by scene change, %d recoded), %zu bytes; %d hardware queues\n", argv[2], n, W, H, Wc, Hc, keys,
            st.scene_changes, st.redone_as_key, total, vp8hip_hw_queues());
+    if (layers)
+        printf("Temporal layers: %d; frames in layer 0 / 1 / 2: %u / %u / %u; %u unreferenced frames not loop-filtered\n", layers, per_layer[0], per_layer[1],
+               per_layer[2], unfiltered);
     printf("%.6f s of reading + coding + writing (%.1f frames/s)\n", loop_s, n / (loop_s > 0 ? loop_s : 1));
     return 0;
 }

@@ -17,7 +17,7 @@ K_NAMES = ["pack", "downsample", "search1_l4", "search1_l3", "search1_l2", "sear
            "select", "mb", "filter_mask", "loop_filter", "border", "ent_count", "ent_encode", "intra", "hdr_encode"]
 K_COUNT = len(K_NAMES)
 
-DBG_NET1, DBG_NET2, DBG_BDIFF, DBG_PYRAMID, DBG_MB_MASK, DBG_MB_NZ, DBG_THIRD_CONTEXT, DBG_CURRENT_CHROMA, DBG_ARF_FRAME = range(9)
+DBG_NET1, DBG_NET2, DBG_BDIFF, DBG_PYRAMID, DBG_MB_MASK, DBG_MB_NZ, DBG_THIRD_CONTEXT, DBG_CURRENT_CHROMA, DBG_ARF_FRAME, DBG_REFRESH_FRAME = range(10)
 
 # every symbol include/vp8hip.h and include/vp8hip_host.h declare
 ABI_SYMBOLS = [
@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "vp8host_overlay_frame", "vp8drv_set_overlay_host", "vp8drv_set_overlay_device", "vp8drv_set_overlay_placement", "vp8drv_clear_overlay",
     "vp8hip_set_canvas", "vp8hip_canvas_tiles", "vp8hip_compose_current_device", "vp8hip_compose_current_host", "vp8host_tile_valid",
     "vp8host_compose_frame", "vp8drv_set_canvas", "vp8drv_encode_frame_tiles_device", "vp8drv_encode_frame_tiles_host",
+    "vp8host_temporal_step", "vp8hip_loop_filter_refresh", "vp8drv_set_temporal_layers", "vp8drv_get_frame_layer",
 ]
 
 
@@ -58,6 +59,9 @@ class Vp8HipError(RuntimeError):
 ABI_VERSION = 4010  # VP8HIP_ABI_VERSION, include/vp8hip.h
 ALTREF_HIDDEN = 2   # VP8HIP_ALTREF_HIDDEN: is_altref of a hidden alternate reference frame (header params, bitstream.Frame)
 ARF_MAX_FRAMES = 7  # VP8HOST_ARF_MAX_FRAMES, include/vp8hip_host.h
+REFRESH_LAST, REFRESH_GOLDEN, REFRESH_NONE, REFRESH_ALL = range(4)   # VP8HOST_REFRESH_* (the first three also VP8HIP_REFRESH_*)
+GOLDEN_ONLY, REFRESH_NOTHING = 2, 3   # VP8HIP_GOLDEN_ONLY / VP8HIP_REFRESH_NOTHING: is_golden of a temporal layer's inter frame (header params, bitstream.Frame)
+TL_KEEP_RECON = 1   # VP8DRV_TL_KEEP_RECON, include/vp8hip_driver.h
 ERR_OVERFLOW = -7   # VP8HIP_ERR_OVERFLOW, include/vp8hip.h
 ERR_FORMAT = -8     # VP8HIP_ERR_FORMAT
 SHARPNESS_ON_DEVICE = -2 ** 31   # VP8HIP_SHARPNESS_ON_DEVICE
@@ -588,6 +592,27 @@ def analyse_luma(cur, prev=None) -> dict:
 
 
 DENOISE_SUM_Y, DENOISE_SAD_Y, DENOISE_SUM_C = 512, 2560, 128   # VP8HOST_DENOISE_*, include/vp8hip_host.h
+
+
+class Temporal(C.Structure):
+    """vp8host_temporal, include/vp8hip_host.h"""
+    _fields_ = [(n, C.c_int32) for n in ("temporal_id", "use_golden", "refresh", "layer_sync")]
+
+
+class LayerInfo(C.Structure):
+    """vp8drv_layer_info, include/vp8hip_driver.h"""
+    _fields_ = [(n, C.c_int32) for n in ("temporal_id", "tl0_pic_idx", "layer_sync", "refresh", "use_golden", "filtered")]
+
+
+def temporal_step(layers: int, p: int, ref_mask: int = 3):
+    """vp8host_temporal_step: the temporal-layer rule for the frame p shown frames behind the last key frame (the key frame: p = 0) ->
+    dict(temporal_id, use_golden, refresh, layer_sync); ValueError where the rule refuses"""
+    lib = load_library()
+    lib.vp8host_temporal_step.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(Temporal)]
+    t = Temporal()
+    if lib.vp8host_temporal_step(int(layers), int(p), int(ref_mask), C.byref(t)) != 0:
+        raise ValueError(f"vp8host_temporal_step({layers}, {p}) refused")
+    return {k: int(getattr(t, k)) for k, _ in Temporal._fields_}
 
 
 class ArfStats(C.Structure):
@@ -1361,6 +1386,22 @@ class NativeDriver:
             raise Vp8HipError(f"vp8drv_get_arf_stats: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
         return st
 
+    def set_temporal_layers(self, layers: int, flags: int = 0) -> None:
+        """vp8drv_set_temporal_layers: 1 (off) to 3 temporal layers from the next key frame on; flags: TL_KEEP_RECON (include/vp8hip_driver.h)"""
+        self.lib.vp8drv_set_temporal_layers.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.lib.vp8drv_set_temporal_layers(self.h, int(layers), int(flags))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_temporal_layers({layers}, {flags}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def frame_layer(self) -> LayerInfo:
+        """vp8drv_get_frame_layer: temporal_id, tl0_pic_idx, layer_sync, refresh, use_golden and filtered of the frame just made final"""
+        info = LayerInfo()
+        self.lib.vp8drv_get_frame_layer.argtypes = [C.c_void_p, C.POINTER(LayerInfo)]
+        rc = self.lib.vp8drv_get_frame_layer(self.h, C.byref(info))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_frame_layer: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return info
+
     def set_segment_mode(self, mode: int, strength: int = 0) -> None:
         """vp8drv_set_segment_mode: 0 off, 1 the caller's segment map, 2 variance-adaptive at strength 1..3 (inter frames only)"""
         self.lib.vp8drv_set_segment_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1732,6 +1773,16 @@ class Vp8Hip:
         self.lib.vp8hip_loop_filter_hidden.argtypes = [C.c_void_p]
         self._chk(self.lib.vp8hip_loop_filter_hidden(self.h), "loop_filter_hidden")
         self.hidden_recon = tuple(self.debug(DBG_ARF_FRAME, r) for r in (3, 4, 5))
+
+    def loop_filter_refresh(self, refresh: int, filter: bool = True):
+        """vp8hip_loop_filter_refresh: the end of a shown frame of a temporal layer -- REFRESH_LAST: loop_filter(); REFRESH_GOLDEN: the
+        filtered reconstruction becomes GOLDEN and LAST stays; REFRESH_NONE: it is dropped (unfiltered with filter = False)"""
+        self.lib.vp8hip_loop_filter_refresh.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.vp8hip_loop_filter_refresh(self.h, int(refresh), int(filter)), "loop_filter_refresh")
+
+    def refresh_frame(self):
+        """(Y, U, V) of the surface the last loop_filter_refresh with REFRESH_GOLDEN or REFRESH_NONE ended (VP8HIP_DBG_REFRESH_FRAME)"""
+        return tuple(self.debug(DBG_REFRESH_FRAME, r) for r in (0, 1, 2))
 
     def arf_filter(self, frames, centre: int, strength: int):
         """vp8hip_arf_filter_host: the window frames = [(Y, U, V), ...] (host memory, the incoming size) through the temporal filter;
@@ -2124,6 +2175,8 @@ class Vp8Hip:
         elif what == DBG_ARF_FRAME:      # ref 0..2: the filtered frame at the incoming size; 3..5: the ALTREF surface at the coded size
             w, h = (self.W, self.H) if ref >= 3 else self.incoming_size()
             a = np.zeros((h, w) if ref in (0, 3) else (h // 2, w // 2), np.uint8)
+        elif what == DBG_REFRESH_FRAME:  # ref 0..2: Y, U, V at the coded size
+            a = np.zeros((self.H, self.W) if ref == 0 else (self.H // 2, self.W // 2), np.uint8)
         else:
             a = np.zeros(self.mbs, np.int32)
         self._chk(self.lib.vp8hip_debug_download(self.h, what, ref, level, a.ctypes.data, a.nbytes), "debug_download")

@@ -6,8 +6,14 @@ using namespace vp8;
 
 namespace vp8 {
 
+// is_golden as the header coders take it: 0, 1, or -- inter frames only -- VP8HIP_GOLDEN_ONLY / VP8HIP_REFRESH_NOTHING (a shown frame of a
+// temporal layer, vp8hip_loop_filter_refresh)
+static inline int frame_is_golden(const vp8hip_header_params *p) {
+    if (!p->is_key && (p->is_golden == VP8HIP_GOLDEN_ONLY || p->is_golden == VP8HIP_REFRESH_NOTHING)) return p->is_golden;
+    return p->is_golden ? 1 : 0;
+}
 // the frame tag's show_frame bit: every frame but a hidden alternate reference frame
-static inline bool frame_shown(const vp8hip_header_params *p) { return p->is_key || p->is_altref != VP8HIP_ALTREF_HIDDEN; }
+static inline bool frame_shown(const vp8hip_header_params *p) { return p->is_key || p->is_altref != VP8HIP_ALTREF_HIDDEN || frame_is_golden(p) >= 2; }
 
 // scratch of the boolean coder, allocated the first time the stage is used (a context that only runs the
 // inter path never pays for it): 64 bools per 4x4 block on average (of at most 304)
@@ -118,7 +124,7 @@ int frame_prepare(vp8hip_ctx *c, int P, const vp8hip_header_params *p, FrameEntr
     e.is_inter = (!p->is_key && p->use_intra_info) ? c->intra_is_inter : nullptr;
     e.modes = intra_info ? c->intra_modes : nullptr;
     e.f.is_key = p->is_key ? 1 : 0;
-    e.f.is_golden = p->is_golden ? 1 : 0;
+    e.f.is_golden = frame_is_golden(p);
     e.f.is_altref = p->is_altref == VP8HIP_ALTREF_HIDDEN ? 2 : (p->is_altref ? 1 : 0);
     e.f.loop_filter_type = p->loop_filter_type;
     e.f.sharpness = p->loop_filter_sharpness;
@@ -314,7 +320,7 @@ int vp8hip_encode_header(vp8hip_ctx *c, const vp8hip_header_params *p, uint8_t *
     hipStream_t s = c->stream;
     HdrFrame f;
     f.is_key = p->is_key ? 1 : 0;
-    f.is_golden = p->is_golden ? 1 : 0;
+    f.is_golden = frame_is_golden(p);
     f.is_altref = p->is_altref == VP8HIP_ALTREF_HIDDEN ? 2 : (p->is_altref ? 1 : 0);
     f.loop_filter_type = p->loop_filter_type;
     f.sharpness = p->loop_filter_sharpness;

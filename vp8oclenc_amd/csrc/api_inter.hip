@@ -475,4 +475,48 @@ int vp8hip_loop_filter_hidden(vp8hip_ctx *c) {
     return VP8HIP_OK;
 }
 
+// The end of a SHOWN inter frame of a temporal layer (vp8host_temporal_step): which buffer the reconstruction refreshes is the caller's.
+//   (VP8HIP_REFRESH_LAST, 1):   vp8hip_loop_filter.
+//   (VP8HIP_REFRESH_GOLDEN, 1): the filter, then GOLDEN = the reconstruction -- a slot assignment, as the hidden ending's -- with its
+//                               replicated edges and pyramid made behind the filter; LAST and lf_key stay.
+//   (VP8HIP_REFRESH_NONE, f):   the reconstruction is dropped; with f = 0 nothing is launched at all.
+// The frame is shown: the intake is not stepped back, and the quality measurement, the analysis record and an armed check_SSIM's
+// verdict ride behind / in the filter's launch as behind vp8hip_loop_filter -- which is why (NONE, 0) refuses an armed check.
+int vp8hip_loop_filter_refresh(vp8hip_ctx *c, int refresh, int filter) {
+    if (!c || (refresh != VP8HIP_REFRESH_LAST && refresh != VP8HIP_REFRESH_GOLDEN && refresh != VP8HIP_REFRESH_NONE) || (filter != 0 && filter != 1) ||
+        (!filter && refresh != VP8HIP_REFRESH_NONE))
+        return VP8HIP_ERR_ARG;
+    if (refresh == VP8HIP_REFRESH_LAST) return vp8hip_loop_filter(c);
+    USE_DEVICE(c);
+    JOIN_LF(c);
+    if (!c->recon_ready || c->recon < 0 || c->recon_key || c->lf_overlap || c->batch || c->shard_comm) return VP8HIP_ERR_STATE;
+    if (!filter && c->chk_armed) return VP8HIP_ERR_STATE;      // (the verdict rides in the filter's launch)
+    FrameSurf &fs = c->frames[c->recon];
+    if (filter) {
+        const FilterItem it = filter_item(c);
+        {
+            Timed t(c, VP8HIP_K_LOOP_FILTER);
+            launch_loop_filter_of_type(c, c->stream, it);
+        }
+        const bool last_key = c->lf_key;      // (the two records name the frame's type by lf_key, which speaks of LAST: this frame is an inter frame)
+        c->lf_key = false;
+        analysis_after_filter(c, c->stream);
+        quality_after_filter(c, fs.f, c->stream);
+        c->lf_key = last_key;
+        c->verdict_stream = c->stream;
+    }
+    if (refresh == VP8HIP_REFRESH_GOLDEN) {
+        build_pyramid(c, &fs.f, nullptr, 1u);
+        fs.pyramid_valid = fs.border_valid = true;
+        c->slot[1] = c->recon;
+    } else {
+        fs.pyramid_valid = fs.border_valid = false;
+    }
+    c->refreshed = c->recon;      // (VP8HIP_DBG_REFRESH_FRAME; a dropped surface is free: the next frame's reconstruction may take it)
+    c->recon = -1;
+    c->recon_ready = false;
+    HIPCHK(c, hipGetLastError());
+    return VP8HIP_OK;
+}
+
 }  // extern "C"

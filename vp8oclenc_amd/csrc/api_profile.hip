@@ -150,6 +150,16 @@ int vp8hip_debug_download(vp8hip_ctx *c, int what, int ref, int level, void *dst
             if (rc) return rc;
             break;
         }
+        case VP8HIP_DBG_REFRESH_FRAME: {
+            if (ref < 0 || ref > 2) return VP8HIP_ERR_ARG;
+            if (c->refreshed < 0) return VP8HIP_ERR_STATE;
+            const Frame &f = c->frames[c->refreshed].f;      // GOLDEN, or the surface of a reconstruction that was dropped
+            const Plane &p = ref == 0 ? f.Y[0] : (ref == 1 ? f.U : f.V);
+            if (bytes != (size_t)p.w * p.h) return VP8HIP_ERR_ARG;
+            int rc = copy_out(c, dst, p);
+            if (rc) return rc;
+            break;
+        }
         case 100:  // diagnostic build only (-DLF2_STAMPS): cycle sums written by the loop filter
             if (bytes != 512) return VP8HIP_ERR_ARG;
             HIPCHK(c, hipMemcpyAsync(dst, (const char *)c->d_progress + 4096, 512, hipMemcpyDeviceToHost, s));

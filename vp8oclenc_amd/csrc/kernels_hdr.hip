@@ -219,11 +219,14 @@ __device__ __forceinline__ void hdr_frame_body(const Params &a, uint32_t *partia
         if (key) {
             w.flag(0);
         } else {
-            w.flag(a.is_golden);
-            w.flag(a.is_altref != 0);
-            if (!a.is_golden) w.literal(0, 2);
-            if (!a.is_altref) w.literal(0, 2);
-            w.flag(0); w.flag(0); w.flag(0); w.flag(a.is_altref != 2);      // refresh_last: not by a hidden frame (VP8HIP_ALTREF_HIDDEN)
+            // is_golden = 2 / 3: a shown frame of a temporal layer that refreshes GOLDEN only / no buffer at all (is_altref is not read)
+            const bool layered = a.is_golden >= 2;
+            const bool refresh_golden = layered ? a.is_golden == 2 : a.is_golden != 0, refresh_altref = !layered && a.is_altref != 0;
+            w.flag(refresh_golden);
+            w.flag(refresh_altref);
+            if (!refresh_golden) w.literal(0, 2);
+            if (!refresh_altref) w.literal(0, 2);
+            w.flag(0); w.flag(0); w.flag(0); w.flag(!layered && a.is_altref != 2);      // refresh_last: not by a hidden frame (VP8HIP_ALTREF_HIDDEN)
         }
         s_n1 = w.n;
     }

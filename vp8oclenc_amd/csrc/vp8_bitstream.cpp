@@ -139,7 +139,9 @@ size_t vp8bs_encode_header(const vp8bs_frame *f, uint8_t *out, size_t capacity, 
     const bool key = f->is_key != 0;
     if (!key && (!f->MB_reference_frame || !f->MB_parts || !f->MB_vectors)) return 0;
     if (key && !f->modes) return 0;
-    const bool hidden = !key && f->is_altref == 2;   // a hidden alternate reference frame (VP8HIP_ALTREF_HIDDEN): not shown, LAST stays
+    // is_golden = 2 / 3 (inter frames): a shown frame of a temporal layer that refreshes GOLDEN only / no buffer at all; is_altref is not read
+    const bool golden_only = !key && f->is_golden == 2, no_refresh = !key && f->is_golden == 3, layered = golden_only || no_refresh;
+    const bool hidden = !key && !layered && f->is_altref == 2;   // a hidden alternate reference frame (VP8HIP_ALTREF_HIDDEN): not shown, LAST stays
     const size_t head = key ? 10 : 3;
     if (capacity < head + 8) return 0;
     const View v{f};
@@ -186,14 +188,15 @@ size_t vp8bs_encode_header(const vp8bs_frame *f, uint8_t *out, size_t capacity, 
     if (key) {
         w.flag(0);                              // refresh_entropy_probs
     } else {
-        w.flag(f->is_golden);                   // refresh_golden_frame, refresh_alternate_frame
-        w.flag(f->is_altref != 0);
-        if (!f->is_golden) w.literal(0, 2);     // no buffer copies
-        if (!f->is_altref) w.literal(0, 2);
+        const bool refresh_golden = layered ? golden_only : f->is_golden != 0, refresh_altref = !layered && f->is_altref != 0;
+        w.flag(refresh_golden);                 // refresh_golden_frame, refresh_alternate_frame
+        w.flag(refresh_altref);
+        if (!refresh_golden) w.literal(0, 2);   // no buffer copies
+        if (!refresh_altref) w.literal(0, 2);
         w.flag(0);                              // sign biases
         w.flag(0);
         w.flag(0);                              // refresh_entropy_probs
-        w.flag(!hidden);                        // refresh_last
+        w.flag(!hidden && !layered);            // refresh_last
     }
     {   // token_prob_update(): every context that occurred gets its probability
         const uint8_t *upd = &k_coeff_update_probs[0][0][0][0];

@@ -44,6 +44,10 @@ struct vp8drv {
     int arf = 0;
     bool last_hidden = false, rotation_consumed = false, hidden_altref = false;
     vp8drv_arf_stats arf_st{};
+    // vp8drv_set_temporal_layers: layers in force (1 = off) and asked for (in force from the next key frame on), the flags, the rule's p
+    // of the next frame (shown frames since the last key frame as finally coded), tid-0 frames made final, the frame just coded
+    int tl_layers = 1, tl_next = 1, tl_flags = 0, tl_p = 0, tl0_count = 0;
+    vp8drv_layer_info layer{};
     // read-back buffers of vp8drv_get_frame
     std::vector<int32_t> seg, nz, ref, parts, is_inter, modes;
     std::vector<int16_t> vectors;
@@ -165,6 +169,20 @@ int segments(vp8drv *d, const uint8_t *host_y, bool key, const int32_t *refqi) {
     return vp8hip_set_segments(d->hip, sd);
 }
 
+// vp8drv_get_frame_layer's record once the frame is final: a tid-0 frame takes the next index, the others carry their base frame's
+void layer_final(vp8drv *d) {
+    if (d->layer.temporal_id == 0) ++d->tl0_count;
+    d->layer.tl0_pic_idx = (d->tl0_count - 1) & 255;
+}
+
+// a key frame is p = 0 of the temporal pattern, whoever asked for it: the pattern restarts, and a layer count asked for takes force
+void key_layer_record(vp8drv *d) {
+    d->tl_layers = d->tl_next;
+    d->tl_p = 1;
+    d->layer = vp8drv_layer_info{0, 0, 0, VP8HOST_REFRESH_ALL, 0, 1};
+    layer_final(d);
+}
+
 // prepare_segments_data() + intra_transform() (vp8enc.cpp:379-383, :411-414, :446-450) and the common tail
 // (:472-473): filter mask, loop filter.  The filtered key frame is LAST = GOLDEN = ALTREF (intra_part.h:1091-1098).
 int key_frame(vp8drv *d, const uint8_t *host_y) {
@@ -182,6 +200,7 @@ int key_frame(vp8drv *d, const uint8_t *host_y) {
     d->last_hidden = d->rotation_consumed = d->hidden_altref = false;      // (LAST = GOLDEN = ALTREF = this frame, by the rotation it owes)
     d->checked = false;
     d->replaced = 0;
+    key_layer_record(d);
     return 1;
 }
 
@@ -190,6 +209,8 @@ void inter_frame_done(vp8drv *d) {
     vp8host_gop_frame_done(&d->gop);
     d->st.inter_frames++;
     d->st.frame_number = d->gop.frame_number;
+    d->tl_p++;
+    layer_final(d);
 }
 
 // The verdict of the asynchronous check_SSIM on the frame just coded (vp8enc.cpp:442-453): statistics, and -- when more than a
@@ -233,10 +254,18 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     }
     if (key) return key_frame(d, host_y);
     // vp8enc.cpp:390, 419: loop-filter strength of the current frame -> segment data
-    const int32_t *refqi = d->gop.current_is_altref ? d->altrefqi : d->lastqi;   // vp8enc.cpp:149-151
+    // vp8drv_set_temporal_layers: references, ending and quantiser ladder from the rule in the place of the GOP state's flags
+    const bool layered = d->tl_layers > 1;
+    vp8host_temporal tl{0, 0, VP8HOST_REFRESH_LAST, 0};
+    if (layered && vp8host_temporal_step(d->tl_layers, d->tl_p, d->cfg.ref_mask, &tl)) return VP8HIP_ERR_STATE;
+    const int32_t *refqi = (d->gop.current_is_altref && !layered) ? d->altrefqi : d->lastqi;   // vp8enc.cpp:149-151
     DRV_CHK(segments(d, host_y, false, refqi));
     int32_t use_golden = 0, use_altref = 0;
     vp8host_gop_inter_flags(&d->gop, &use_golden, &use_altref);                  // inter_part.h:103-104
+    if (layered) {
+        use_golden = tl.use_golden;
+        use_altref = 0;
+    }
     // vp8drv_encode_arf_*: a hidden frame's transform has applied the rotation already (again, and LAST would overwrite the new
     // ALTREF); and while ALTREF holds a hidden frame's reconstruction it differs from GOLDEN whatever the frame numbers say
     const int32_t prev_is_golden = d->rotation_consumed ? 0 : d->gop.prev_is_golden, prev_is_altref = d->rotation_consumed ? 0 : d->gop.prev_is_altref;
@@ -252,15 +281,18 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     d->st.refs_searched += 1 + use_golden + use_altref;
     d->st.last_prev_is_golden = prev_is_golden;
     d->st.last_prev_is_altref = prev_is_altref;
-    d->st.last_was_altref = d->gop.current_is_altref;
+    d->st.last_was_altref = layered ? 0 : d->gop.current_is_altref;
     d->checked = false;
     d->replaced = 0;
+    // an unreferenced frame is filtered only if something reads the filter's output or rides in its launch
+    const bool filter = tl.refresh != VP8HOST_REFRESH_NONE || d->cfg.check_ssim || d->cfg.quality_stats || d->analysis || (d->tl_flags & VP8DRV_TL_KEEP_RECON);
+    d->layer = vp8drv_layer_info{tl.temporal_id, 0, tl.layer_sync, tl.refresh, use_golden, filter ? 1 : 0};
     if (d->cfg.check_ssim && (d->cfg.device_params || !host_y)) {
         // check_SSIM (vp8enc.cpp:231-263) with nobody waiting for it: fallback, statistics and the filter update on the device,
         // the loop filter right behind them.  What the host has to decide -- "redo as key frame", :443-453 -- it decides when it
         // next needs to know: at the start of the next call or in vp8drv_get_frame (resolve()).
         DRV_CHK(vp8hip_check_ssim_async(d->hip, refqi, d->qi_min));
-        DRV_CHK(vp8hip_loop_filter(d->hip));
+        DRV_CHK(vp8hip_loop_filter_refresh(d->hip, tl.refresh, 1));
         d->verdict_pending = true;
         d->have_frame = true;
         d->last_key = false;
@@ -295,7 +327,7 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     }
     // otherwise prepare_filter_mask was produced by vp8hip_inter_transform for its own coefficients;
     // do_loop_filter (loop_filter.h:185-190) follows directly
-    DRV_CHK(vp8hip_loop_filter(d->hip));
+    DRV_CHK(vp8hip_loop_filter_refresh(d->hip, tl.refresh, filter ? 1 : 0));
     inter_frame_done(d);
     d->have_frame = true;
     d->last_key = false;
@@ -305,10 +337,15 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
 
 // entropy_encode() + gather_frame() (vp8enc.cpp:48-94, 476-481; encIO.h:1-30) for the frame just coded:
 // coefficient statistics and partitions on the device, first partition on the host
+int layer_is_golden(const vp8drv *d) {
+    if (d->last_key || d->last_hidden) return d->last_key;
+    return d->layer.refresh == VP8HOST_REFRESH_GOLDEN ? VP8HIP_GOLDEN_ONLY : (d->layer.refresh == VP8HOST_REFRESH_NONE ? VP8HIP_REFRESH_NOTHING : 0);
+}
+
 vp8hip_header_params header_params(const vp8drv *d) {
     vp8hip_header_params hp{};
     hp.is_key = d->last_key;
-    hp.is_golden = d->last_key;                 // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369)
+    hp.is_golden = layer_is_golden(d);          // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369), or a temporal layer's refresh
     hp.is_altref = d->last_hidden ? VP8HIP_ALTREF_HIDDEN : d->last_altref;
     hp.loop_filter_type = d->cfg.loop_filter_type;   // 0 in the reference (init.h:1583)
     hp.loop_filter_sharpness = d->sharpness;    // or VP8HIP_SHARPNESS_ON_DEVICE
@@ -334,6 +371,10 @@ int intake_restarts(vp8drv *d, bool scheduled_key) {
     if (d->denoise && scheduled_key) return vp8hip_denoise_restart(d->hip);
     return VP8HIP_OK;
 }
+
+// a driver with temporal layers whose context has since joined a by-reference split (the context's refresh ending would refuse it in
+// the middle of the frame): refused before the frame is taken in
+bool layers_refused(const vp8drv *d) { return (d->tl_layers > 1 || d->tl_next > 1) && vp8hip_shard_world(d->hip) > 0; }
 
 int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     const int P = d->cfg.num_partitions;
@@ -381,7 +422,7 @@ int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     f.mb_width = d->W / 16;
     f.mb_height = d->H / 16;
     f.is_key = d->last_key;
-    f.is_golden = d->last_key;                  // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369)
+    f.is_golden = layer_is_golden(d);           // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369), or a temporal layer's refresh
     f.is_altref = d->last_hidden ? VP8HIP_ALTREF_HIDDEN : d->last_altref;
     f.loop_filter_type = d->cfg.loop_filter_type;    // 0 in the reference (init.h:1583)
     f.loop_filter_sharpness = sharp;
@@ -414,6 +455,7 @@ extern "C" {
 int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const void *v, int force_key) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
     if (d->canvas) return VP8HIP_ERR_STATE;      // (frames come in through vp8drv_encode_frame_tiles_*)
+    if (layers_refused(d)) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }                        // the previous frame's check_SSIM verdict, if still open
     vp8host_gop_next(&d->gop);
     DRV_CHK(intake_restarts(d, d->gop.current_is_key != 0));
@@ -423,7 +465,7 @@ int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const vo
 
 int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v, int force_key) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
-    if (d->canvas) return VP8HIP_ERR_STATE;
+    if (d->canvas || layers_refused(d)) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     vp8host_gop_next(&d->gop);
     const bool staged = d->staged == y;
@@ -484,6 +526,7 @@ static int encode_frame_tiles(vp8drv *d, const vp8hip_tile_planes *src, int forc
     if (!d->canvas) return VP8HIP_ERR_STATE;
     for (int k = 0; k < d->canvas; ++k)      // (what the context would refuse, before the schedule moves)
         if (src[k].y && (!src[k].u || !src[k].v || src[k].pitch_y < 0 || src[k].pitch_u < 0 || src[k].pitch_v < 0)) return VP8HIP_ERR_ARG;
+    if (layers_refused(d)) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     vp8host_gop_next(&d->gop);
     DRV_CHK(intake_restarts(d, d->gop.current_is_key != 0));
@@ -508,8 +551,9 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
     for (int i = 0; i < n; ++i) {
         // the batched loop is the device-parameter loop (what bench.py and a file-to-file transcode run); one launch serves all
         // members, so what travels as ONE kernel argument must agree: quantizer range, check_SSIM on or off, partitions, filter type
-        if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect || drv[i]->arf || drv[i]->canvas || drv[i]->rotation_consumed || drv[i]->hidden_altref)
-            return VP8HIP_ERR_ARG;      // (hidden frames are not batched, nor is a driver whose references a hidden frame still shapes)
+        if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect || drv[i]->arf || drv[i]->canvas || drv[i]->rotation_consumed || drv[i]->hidden_altref ||
+            drv[i]->tl_layers > 1 || drv[i]->tl_next > 1)
+            return VP8HIP_ERR_ARG;      // (hidden frames are not batched, nor is a driver whose references a hidden frame still shapes; nor are temporal layers)
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
@@ -601,6 +645,7 @@ static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *c
             d->checked = false;
             d->replaced = 0;
             d->sharpness = VP8HIP_SHARPNESS_ON_DEVICE;
+            key_layer_record(d);
         }
     }
     for (int i = 0; i < b->n; ++i) {
@@ -640,6 +685,7 @@ static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *c
         d->st.last_was_altref = d->gop.current_is_altref;
         d->checked = false;
         d->replaced = 0;
+        d->layer = vp8drv_layer_info{0, 0, 0, VP8HOST_REFRESH_LAST, ug[i], 1};
         if (check) d->verdict_pending = true;   // counted when the verdict is in (resolve())
         else inter_frame_done(d);
         d->have_frame = true;
@@ -896,7 +942,7 @@ int vp8drv_set_arf(vp8drv *d, int strength_plus_one) {
     if (strength_plus_one && (!d->cfg.device_params || d->cfg.overlap_filter || d->format || d->window || d->deinterlace ||
                               d->denoise || d->analysis))
         return VP8HIP_ERR_ARG;
-    if (d->in_batch || (strength_plus_one && d->canvas)) return VP8HIP_ERR_STATE;      // (a canvas: the window frames bypass the compose launch)
+    if (d->in_batch || (strength_plus_one && (d->canvas || d->tl_layers > 1 || d->tl_next > 1))) return VP8HIP_ERR_STATE;      // (a canvas: the window frames bypass the compose launch; temporal layers never search ALTREF)
     { const int rc = resolve(d); if (rc < 0) return rc; }
     d->arf = strength_plus_one;
     if (!strength_plus_one && d->arf_st.hidden_frames) (void)vp8hip_arf_result(d->hip, d->arf_st.last_weight);
@@ -961,6 +1007,25 @@ int vp8drv_get_arf_stats(vp8drv *d, vp8drv_arf_stats *s) {
     const int rc = vp8hip_arf_result(d->hip, d->arf_st.last_weight);      // (VP8HIP_ERR_STATE: released by vp8drv_set_arf(d, 0), which kept them)
     if (rc != VP8HIP_OK && rc != VP8HIP_ERR_STATE) return rc;
     *s = d->arf_st;
+    return VP8HIP_OK;
+}
+
+// ---- temporal layers --------------------------------------------------------------------------------------------------------------------
+int vp8drv_set_temporal_layers(vp8drv *d, int layers, int flags) {
+    if (!d || layers < 1 || layers > 3 || (flags & ~VP8DRV_TL_KEEP_RECON)) return VP8HIP_ERR_ARG;
+    if (layers > 1 && (!d->cfg.device_params || d->cfg.overlap_filter || d->cfg.altref_range <= d->cfg.gop_size)) return VP8HIP_ERR_ARG;
+    if (layers > 1 && (d->in_batch || d->arf || vp8hip_shard_world(d->hip) > 0)) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    d->tl_next = layers;
+    d->tl_flags = layers > 1 ? flags : 0;
+    return VP8HIP_OK;
+}
+
+int vp8drv_get_frame_layer(vp8drv *d, vp8drv_layer_info *info) {
+    if (!d || !info) return VP8HIP_ERR_ARG;
+    if (!d->have_frame || d->last_hidden) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    *info = d->layer;
     return VP8HIP_OK;
 }
 

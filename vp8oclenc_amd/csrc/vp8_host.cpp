@@ -580,6 +580,25 @@ void vp8host_gop_inter_flags(const vp8host_gop *g, int32_t *use_golden, int32_t 
 
 void vp8host_gop_frame_done(vp8host_gop *g) { ++g->frame_number; }
 
+int vp8host_temporal_step(int layers, int p, int ref_mask, vp8host_temporal *out) {  // the rule: include/vp8hip_host.h
+    if (!out || layers < 1 || layers > 3 || p < 0) return -1;
+    vp8host_temporal t{0, 0, VP8HOST_REFRESH_LAST, 0};
+    if (p == 0) {
+        t.refresh = VP8HOST_REFRESH_ALL;
+    } else if (layers == 2) {
+        if (p % 2 == 1) t = vp8host_temporal{1, 0, VP8HOST_REFRESH_NONE, 1};
+    } else if (layers == 3) {
+        switch (p % 4) {
+            case 1: t = vp8host_temporal{2, 0, VP8HOST_REFRESH_NONE, 1}; break;
+            case 2: t = vp8host_temporal{1, 0, VP8HOST_REFRESH_GOLDEN, 1}; break;
+            case 3: t = vp8host_temporal{2, ref_mask & 1, VP8HOST_REFRESH_NONE, !(ref_mask & 1)}; break;
+            default: break;
+        }
+    }
+    *out = t;
+    return 0;
+}
+
 int vp8host_scene_plan(const int32_t *udiff, const int32_t *vdiff, int nframes, int gop_size, uint8_t *is_key, uint8_t *by_scene) {
     if (!udiff || !vdiff || !is_key || nframes < 0 || gop_size < 1) return -1;
     vp8host_gop g;

@@ -119,6 +119,7 @@ struct vp8hip_ctx {
     int slot[3] = {-1, -1, -1};     // pool index of LAST / GOLDEN / ALTREF
     int recon = -1;                 // pool index of the reconstruction being produced
     bool recon_ready = false;       // holds an unfiltered reconstruction
+    int refreshed = -1;             // pool index of the surface the last vp8hip_loop_filter_refresh(GOLDEN / NONE) ended (VP8HIP_DBG_REFRESH_FRAME)
     bool cur_pyramid_valid = false;
     vp8::Frame cur_prev;                 // the previous current frame (the two surfaces swap on every upload)
     int cur_count = 0;              // current frames received so far

@@ -204,11 +204,12 @@ def hidden_frame_events(length: int, period: int, max_frames: int = 7):
     return out
 
 
-def write_ivf_records(path: str, records, width: int, height: int, framerate: int = 30, timescale: int = 1) -> int:
-    """write_ivf for (timestamp, bytes) records: a hidden frame is a record of its own and the header's count includes it"""
+def write_ivf_records(path: str, records, width: int, height: int, framerate: int = 30, timescale: int = 1, count: int | None = None) -> int:
+    """write_ivf for (timestamp, bytes) records: a hidden frame is a record of its own and the header's count includes it (count: the
+    header's frame count, where it is not the reference's -- one more than the file holds)"""
     from . import bitstream
     with open(path, "wb") as f:
-        f.write(bitstream.ivf_file_header(width, height, framerate, timescale, len(records) + 1))
+        f.write(bitstream.ivf_file_header(width, height, framerate, timescale, len(records) + 1 if count is None else count))
         for ts, b in records:
             f.write(bitstream.ivf_frame_header(len(b), ts))
             f.write(b)
