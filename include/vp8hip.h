@@ -166,17 +166,27 @@ int vp8hip_check_ssim_ready(const vp8hip_ctx *ctx);
  * header coder is not to read them: use_intra_info = 0 gives the reference's bits). */
 int vp8hip_download_intra(vp8hip_ctx *ctx, int32_t *modes, int32_t *is_inter_mb);
 /* NOT the reference's behaviour, off by default: with on = 1 the emitted stream decodes, in any VP8 decoder, to exactly the
- * reconstruction the encoder keeps as its references.  The reference's does not, in two places (found by decoding the frames
+ * reconstruction the encoder keeps as its references.  The reference's does not, in three places (1, 2 found by decoding the frames
  * with a decoder written from RFC 6386, tests/vp8_decode.py, tests/test_decode_roundtrip.py):
  *  1. `construct` (GPU_kernels.cl:702-758) wraps the last three of the nine first-pass lines of a 4x4 predictor to 8 bits
  *     where the format saturates them (RFC 6386 section 18.3): wherever the six-tap filter overshoots on one of those lines --
  *     hard edges, text, graphics -- the encoder predicts from other samples than every decoder will;
  *  2. check_SSIM writes e_data.mode on every attempt (intra_part.h:964) but coefficients and reconstruction only when the
  *     attempt is kept (:1058-1086): a macroblock whose AQ attempt was kept and whose HQ / UQ attempts then failed goes out with
- *     sub-block modes that do not belong to its coefficients.
- * Either error lives on through inter prediction until the next key frame.  on = 1 saturates all nine lines and keeps the
- * modes of the attempt that was KEPT; the output is then no longer the reference's byte for byte wherever one of the two
- * cases occurs (and identical where none does).  All members of a batch must agree. */
+ *     sub-block modes that do not belong to its coefficients;
+ *  3. the normal loop filter (CPU_kernels.cl:970-1075) hands the q registers of one edge to the next edge of the macroblock as
+ *     its p registers without the saturation its stores apply (:1024, :1062), where a decoder filters the stored samples: on
+ *     content the filter moves past 0 or 255 a few samples of the filtered reconstruction differ (found by tests/lf_ref.py;
+ *     REFERENCE_DEFECTS.md has the measured rarity).
+ * Each error lives on through inter prediction until the next key frame.  on = 1 saturates all nine lines, keeps the
+ * modes of the attempt that was KEPT and saturates the loop filter's registers where they are handed on (vp8hip_loop_filter and
+ * vp8hip_batch_loop_filter then launch the _conformant instantiations of their kernels); the output is then no longer the
+ * reference's byte for byte wherever one of the three cases occurs (and identical where none does).  All members of a batch
+ * must agree.
+ * Outside this promise: a macroblock whose segment has loop_filter_level 0 ends the whole plane's filtering in either mode
+ * (:990), where a decoder skips that macroblock alone.  Segment data made by vp8hip_auto_segments / prepare_segments_data never
+ * hold a level 0 (the level is dc_q(qi + 15) / reductor with dc_q >= 17 and the reductor at most 16); a caller who sets one
+ * with vp8hip_set_segments beside non-zero levels gets the reference's behaviour, not a decoder's. */
 int vp8hip_conformant_stream(vp8hip_ctx *ctx, int on);
 /* copy_with_padding(), encIO.h:141-196, on the device: after this call the planes handed to vp8hip_upload_current /
  * vp8hip_set_current_device / vp8hip_batch_set_current_device are tight planes of src_width x src_height (both even, less than

@@ -705,6 +705,8 @@ void vp8o_loop_filter_frame(uint8_t *frame, const int32_t *MB_segment_ids, const
                     memcpy(p2, q1, sizeof p2);
                     memcpy(p1, q2, sizeof p1);
                     memcpy(p0, q3, sizeof p0);
+                    if (vp8o_conformant) /* NOT the reference: what a decoder reads back is what the stores saturated */
+                        for (int k = 0; k < 8; ++k) { p3[k] = c128(p3[k]); p2[k] = c128(p2[k]); p1[k] = c128(p1[k]); }
                     const int eb = base + e * along;
                     rd8(frame, eb, lane, q0);
                     rd8(frame, eb + along, lane, q1);

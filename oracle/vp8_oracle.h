@@ -164,10 +164,11 @@ void vp8o_copy_with_padding(const uint8_t *sy, const uint8_t *su, const uint8_t 
                             uint8_t *dv, int w, int h);
 int vp8o_num_threads(void);
 void vp8o_set_num_threads(int n);
-/* NOT the reference, default 0.  1 = the two places where the reference's encoder and a decoder of its stream part ways
- * are closed: check_SSIM keeps the sub-block modes of the attempt it kept (vp8_intra_oracle.c), and the predictor saturates
- * all nine first-pass lines as the format says instead of wrapping the last three (vp8_oracle.c, interp4x4_construct).
- * Exists to prove that these two are the whole difference (tests/test_decode_roundtrip.py) and to check the product's
+/* NOT the reference, default 0.  1 = the three places where the reference's encoder and a decoder of its stream part ways
+ * are closed: check_SSIM keeps the sub-block modes of the attempt it kept (vp8_intra_oracle.c), the predictor saturates
+ * all nine first-pass lines as the format says instead of wrapping the last three (vp8_oracle.c, interp4x4_construct), and
+ * the loop filter clamps the registers it carries from edge to edge (vp8o_loop_filter_frame).
+ * Exists to prove that these are the whole difference (tests/test_decode_roundtrip.py) and to check the product's
  * opt-in of the same meaning, vp8hip_conformant_stream. */
 extern int vp8o_conformant;
 void vp8o_set_conformant_stream(int on);

@@ -21,8 +21,8 @@ def load_meta(z) -> dict:
         return ast.literal_eval(text)
 
 
-def default_segments(qi=(12, 24, 36, 48), lf_levels=(6, 10, 14, 20), sharp=0, inter=True) -> np.ndarray:
-    """A plausible segment_data[4] (the real one comes from the host mirror, vp8oclenc_amd.host)."""
+def default_segments(qi=(12, 24, 36, 48), lf_levels=(6, 10, 14, 20), sharp=0, inter=True, key=False) -> np.ndarray:
+    """A plausible segment_data[4] (the real one comes from the host mirror, vp8oclenc_amd.host).  key: the key-frame table of hev thresholds."""
     sd = np.zeros((4, 11), np.int32)
     for i in range(4):
         sd[i, 0] = qi[i]
@@ -36,7 +36,10 @@ def default_segments(qi=(12, 24, 36, 48), lf_levels=(6, 10, 14, 20), sharp=0, in
         sd[i, 9] = il
         sd[i, 7] = (lvl + 2) * 2 + il
         sd[i, 8] = lvl * 2 + il
-        sd[i, 10] = 3 if lvl >= 40 else (2 if lvl >= 20 else (1 if lvl >= 15 else 0))
+        if key:
+            sd[i, 10] = 2 if lvl >= 40 else (1 if lvl >= 15 else 0)
+        else:
+            sd[i, 10] = 3 if lvl >= 40 else (2 if lvl >= 20 else (1 if lvl >= 15 else 0))
     sd[0, 1] = 15
     sd[0, 4] = -15 if inter else 0
     sd[0, 5] = -15 if inter else 0

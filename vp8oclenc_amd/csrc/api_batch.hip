@@ -454,8 +454,8 @@ int vp8hip_batch_loop_filter(vp8hip_batch *b, const int *active) {
         // (form 3 for batches: with the part full a launch's instructions and LDS count, not its latency; VP8HIP_LF_BATCH_FORM=4 for A/B runs)
         static const bool form4 = [] { const char *v = getenv("VP8HIP_LF_BATCH_FORM"); return v && atoi(v) == 4; }();
         if (m[0]->lf_type == 1) launch_loop_filter_simple_batch(b->stream, it, n, c0->mbw, c0->mbh);
-        else if (form4) launch_loop_filter4_batch(b->stream, it, n, c0->mbw, c0->mbh);
-        else launch_loop_filter3_batch(b->stream, it, n, c0->mbw, c0->mbh);
+        else if (form4) launch_loop_filter4_batch(b->stream, it, n, c0->mbw, c0->mbh, c0->conformant != 0);
+        else launch_loop_filter3_batch(b->stream, it, n, c0->mbw, c0->mbh, c0->conformant != 0);
     }
     b->ent_fork_fresh = b->ent != nullptr;
     for (int k = 0; k < n; ++k) recon_filtered(m[k]);

@@ -400,7 +400,7 @@ int vp8hip_set_loop_filter_type(vp8hip_ctx *c, int type) {
 // the filter of the context's type on `s` (form 4 for the normal filter: the short chain of one video)
 static void launch_loop_filter_of_type(vp8hip_ctx *c, hipStream_t s, const FilterItem &it) {
     if (c->lf_type == 1) launch_loop_filter_simple(s, it, c->mbw, c->mbh);
-    else launch_loop_filter4(s, it, c->mbw, c->mbh, c->lf_stall_test);
+    else launch_loop_filter4(s, it, c->mbw, c->mbh, c->lf_stall_test, c->conformant != 0);
 }
 
 int vp8hip_loop_filter(vp8hip_ctx *c) {

@@ -15,7 +15,8 @@ namespace lf3 {
 
 using namespace lfb;
 
-struct NormalFilter {
+// SAT: vp8hip_conformant_stream -- the registers handed from edge to edge saturate (lf_shared.h, filter_line)
+template <bool SAT> struct NormalFilterT {
     static constexpr bool CHROMA = true;
     static constexpr bool LEVEL0_ENDS_PLANE = true;
     typedef int4 Lim;   // {interior limit, mb_delta, b_delta, hev threshold} (struct Limits)
@@ -35,10 +36,12 @@ struct NormalFilter {
         s.il8 = inner && luma ? s.int_lim : -1;
         return s;
     }
-    static __device__ __forceinline__ void line(int (&t)[20], const Step &s, bool mb_edge) { filter_line(t, s.L, mb_edge ? s.int_lim : -1, s.il4, s.il8); }
+    static __device__ __forceinline__ void line(int (&t)[20], const Step &s, bool mb_edge) { filter_line<SAT>(t, s.L, mb_edge ? s.int_lim : -1, s.il4, s.il8); }
 };
+typedef NormalFilterT<false> NormalFilter;
 
 __global__ __launch_bounds__(NWAVES * 64) void k_loop_filter3_b(BatchOf<Args> b) { loop_filter_body<NormalFilter>(b.item[blockIdx.z]); }
+__global__ __launch_bounds__(NWAVES * 64) void k_loop_filter3_b_conformant(BatchOf<Args> b) { loop_filter_body<NormalFilterT<true>>(b.item[blockIdx.z]); }
 
 }  // namespace lf3
 
@@ -47,8 +50,8 @@ static bool lf_skip() {
     return skip;   // timing experiment only
 }
 
-void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh) {
-    lfb::launch_batch(lf3::k_loop_filter3_b, s, items, n, 0, mbw, mbh, lf_skip());
+void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh, bool conformant) {
+    lfb::launch_batch(conformant ? lf3::k_loop_filter3_b_conformant : lf3::k_loop_filter3_b, s, items, n, 0, mbw, mbh, lf_skip());
 }
 
 }  // namespace vp8

@@ -106,7 +106,8 @@ __device__ __forceinline__ void line_pre(const int (&t)[20], const Limits &L, Li
     LF_KEEP(pre.mb_dq10); LF_KEEP(pre.mb_m2); LF_KEEP(pre.e4_dq10); LF_KEEP(pre.e4_m2); LF_KEEP(pre.e4_e0); LF_KEEP(pre.e4_qp3);
     LF_KEEP(pre.e8.pre_max); LF_KEEP(pre.e8.a); LF_KEEP(pre.e8.hv); LF_KEEP(pre.e12.pre_max); LF_KEEP(pre.e12.a); LF_KEEP(pre.e12.hv);
 }
-// t[0..3] have arrived.  Writes t[1..17] (unsaturated, like filter_line).
+// t[0..3] have arrived.  Writes t[1..17] (unsaturated, like filter_line).  SAT: filter_line's.
+template <bool SAT>
 __device__ __forceinline__ void line_post(int (&t)[20], const Limits &L, int il_mb, int il4, int il8, const LinePre &pre) {
     EdgeRegs e;
     e.p3 = t[0]; e.p2 = t[1]; e.p1 = t[2]; e.p0 = t[3];
@@ -133,6 +134,7 @@ __device__ __forceinline__ void line_post(int (&t)[20], const Limits &L, int il_
     t[4] = e.q0; t[5] = e.q1; t[6] = e.q2;
     {   // the edge at 4: p3, p2, p1 are the macroblock edge's q0, q1, q2
         e.p3 = e.q0; e.p2 = e.q1; e.p1 = e.q2; e.p0 = e.q3;
+        if (SAT) { e.p3 = satb(e.p3); e.p2 = satb(e.p2); e.p1 = satb(e.p1); }
         e.q0 = t[8]; e.q1 = t[9]; e.q2 = t[10]; e.q3 = t[11];
         const int d10 = ad(e.p1, e.p0);
         const int m1 = max3i(ad(e.p3, e.p2), ad(e.p2, e.p1), d10);
@@ -152,10 +154,12 @@ __device__ __forceinline__ void line_post(int (&t)[20], const Limits &L, int il_
         t[6] = e.p1; t[7] = e.p0; t[8] = e.q0; t[9] = e.q1;
     }
     e.p3 = e.q0; e.p2 = e.q1; e.p1 = t[10]; e.p0 = t[11];
+    if (SAT) { e.p3 = satb(e.p3); e.p2 = satb(e.p2); }
     e.q0 = t[12]; e.q1 = t[13]; e.q2 = t[14]; e.q3 = t[15];
     b_edge_post(e, pre.e8, il8, L.hev_thr);
     t[10] = e.p1; t[11] = e.p0; t[12] = e.q0; t[13] = e.q1;
     e.p3 = e.q0; e.p2 = e.q1; e.p1 = t[14]; e.p0 = t[15];
+    if (SAT) { e.p3 = satb(e.p3); e.p2 = satb(e.p2); }
     e.q0 = t[16]; e.q1 = t[17]; e.q2 = t[18]; e.q3 = t[19];
     b_edge_post(e, pre.e12, il8, L.hev_thr);
     t[14] = e.p1; t[15] = e.p0; t[16] = e.q0; t[17] = e.q1;
@@ -246,6 +250,7 @@ struct Shared {
 #define STAMP(v)
 #endif
 
+template <bool SAT>
 __device__ __forceinline__ void loop_filter4_body(const Args &a) {
     __shared__ __attribute__((aligned(16))) Shared sh;
     const int band = blockIdx.x;
@@ -587,7 +592,7 @@ __device__ __forceinline__ void loop_filter4_body(const Args &a) {
             line_pre(t, L, pre);
             const int4 v0 = n_v0;
             t[0] = v0.x; t[1] = v0.y; t[2] = v0.z; t[3] = v0.w;
-            line_post(t, L, il_p1, il_in, il_in | chroma_m1, pre);
+            line_post<SAT>(t, L, il_p1, il_in, il_in | chroma_m1, pre);
 #pragma unroll
             for (int k = 1; k < 18; ++k) t[k] = satb(t[k]);
             // macroblock 0 has nothing to its left (the slot belongs to a macroblock the porter may be bringing in); chroma
@@ -660,7 +665,7 @@ __device__ __forceinline__ void loop_filter4_body(const Args &a) {
 #endif
         // ---- P2: horizontal edges, lane = pixel column ---------------------------------------------
         if (on) {
-            line_post(t2, L, il_p2, il_in, il_in | chroma_m1, pre2);
+            line_post<SAT>(t2, L, il_p2, il_in, il_in | chroma_m1, pre2);
 #pragma unroll
             for (int k = 1; k < 18; ++k) t2[k] = satb(t2[k]);
 #pragma unroll
@@ -692,9 +697,12 @@ __device__ __forceinline__ void loop_filter4_body(const Args &a) {
 #endif
 }
 
-__global__ __launch_bounds__(NWAVES * 64) void k_loop_filter4(Args a) { loop_filter4_body(a); }
+__global__ __launch_bounds__(NWAVES * 64) void k_loop_filter4(Args a) { loop_filter4_body<false>(a); }
 static_assert(sizeof(BatchOf<Args>) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
-__global__ __launch_bounds__(NWAVES * 64) void k_loop_filter4_b(BatchOf<Args> b) { loop_filter4_body(b.item[blockIdx.z]); }
+__global__ __launch_bounds__(NWAVES * 64) void k_loop_filter4_b(BatchOf<Args> b) { loop_filter4_body<false>(b.item[blockIdx.z]); }
+// vp8hip_conformant_stream: the carried registers saturate at the hand-over (lf_shared.h, filter_line)
+__global__ __launch_bounds__(NWAVES * 64) void k_loop_filter4_conformant(Args a) { loop_filter4_body<true>(a); }
+__global__ __launch_bounds__(NWAVES * 64) void k_loop_filter4_b_conformant(BatchOf<Args> b) { loop_filter4_body<true>(b.item[blockIdx.z]); }
 
 }  // namespace lf4
 
@@ -724,13 +732,13 @@ static bool lf_skip() {
     return skip;   // timing experiment only
 }
 
-void launch_loop_filter4(hipStream_t s, const FilterItem &it, int mbw, int mbh, int stall_test) {
+void launch_loop_filter4(hipStream_t s, const FilterItem &it, int mbw, int mbh, int stall_test, bool conformant) {
     const lf4::Args a = loop_filter4_args(s, it, mbw, mbh, stall_test);
     if (lf_skip()) return;
-    VP8_LAUNCH(lf4::k_loop_filter4, dim3(a.nbands + (a.chk.on ? 1 : 0)), dim3(lf4::NWAVES * 64), 0, s, a);   // + the verdict workgroup
+    VP8_LAUNCH(conformant ? lf4::k_loop_filter4_conformant : lf4::k_loop_filter4, dim3(a.nbands + (a.chk.on ? 1 : 0)), dim3(lf4::NWAVES * 64), 0, s, a);   // + the verdict workgroup
 }
 
-void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh) {
+void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh, bool conformant) {
     BatchOf<lf4::Args> b;
     b.n = n;
     bool any = false;
@@ -739,7 +747,7 @@ void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, in
         any = any || b.item[i].chk.on;
     }
     if (lf_skip()) return;
-    VP8_LAUNCH(lf4::k_loop_filter4_b, dim3(b.item[0].nbands + (any ? 1 : 0), 1, n), dim3(lf4::NWAVES * 64), 0, s, b);
+    VP8_LAUNCH(conformant ? lf4::k_loop_filter4_b_conformant : lf4::k_loop_filter4_b, dim3(b.item[0].nbands + (any ? 1 : 0), 1, n), dim3(lf4::NWAVES * 64), 0, s, b);
 }
 
 }  // namespace vp8

@@ -67,6 +67,9 @@ __device__ __forceinline__ void filter_b_edge(EdgeRegs &e, const Limits &L, int 
 // inner edges, each under its own interior limit (-1 = edge switched off).  t[] receives the UNSATURATED results (the reference saturates when it
 // stores); the p/q registers handed from edge to edge stay unsaturated too (:1024, :1062).  t[0], t[18], t[19] are never written.
 // (Form 4 runs the same line in two parts, line_pre / line_post in kernels_lf4.hip.)
+// SAT (vp8hip_conformant_stream, NOT the reference): the registers an edge hands to the next one -- three from the macroblock edge, two
+// from an inner edge -- are saturated at the hand-over, as a decoder finds them in the plane.  t[] still receives unsaturated results.
+template <bool SAT = false>
 __device__ __forceinline__ void filter_line(int (&t)[20], const Limits &L, int il_mb, int il4, int il8) {
     EdgeRegs e;
     e.p3 = t[0]; e.p2 = t[1]; e.p1 = t[2]; e.p0 = t[3];
@@ -77,6 +80,7 @@ __device__ __forceinline__ void filter_line(int (&t)[20], const Limits &L, int i
 #pragma unroll
     for (int k = 4; k < 16; k += 4) {
         e.p3 = e.q0; e.p2 = e.q1; e.p1 = e.q2; e.p0 = e.q3;
+        if (SAT) { e.p3 = satb(e.p3); e.p2 = satb(e.p2); if (k == 4) e.p1 = satb(e.p1); }
         e.q0 = t[4 + k]; e.q1 = t[5 + k]; e.q2 = t[6 + k]; e.q3 = t[7 + k];
         filter_b_edge(e, L, k == 4 ? il4 : il8);
         t[2 + k] = e.p1; t[3 + k] = e.p0; t[4 + k] = e.q0; t[5 + k] = e.q1;

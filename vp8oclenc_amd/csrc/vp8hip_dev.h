@@ -317,8 +317,8 @@ bool launch_search2_batch(hipStream_t s, const CodingItem *items, int n, unsigne
 // (one context: a batch of one -- the kernel is the same)
 // mapped: every macroblock is coded once, in the segment its member's seg_map names (vp8hip_set_segment_mode; the packed form only)
 void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant = false, bool mapped = false);
-void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh);
-void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh);
+void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh, bool conformant = false);   // conformant: vp8hip_conformant_stream, the carried registers saturate
+void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh, bool conformant = false);
 void launch_auto_segments_batch(hipStream_t s, const ScanRequest *q, int n);
 // The forms of ONE video (kernels of their own; the argument blocks are made as the batched forms make them).
 // levels 4, 3, 2, 1 (and, finest, 0) in ONE launch (kernels_me.hip, k_search1_coarse); leaves the level-1 / level-0 nets where the per-level launches leave them
@@ -334,7 +334,7 @@ void launch_filter_mask(hipStream_t s, const MBOut &o, const SegData *d_sd, int 
 // of LDS, the worker wave does everything itself -- what batches of GOP chunks launch, and only they (with the part full what counts is the
 // instructions and the LDS a launch takes from the other kernels, not its latency).  Form 4: a band-tall plane of dwords in
 // 112 KB of LDS, the workers only filter, porter waves feed and drain -- the short dependency chain of ONE video.
-void launch_loop_filter4(hipStream_t s, const FilterItem &it, int mbw, int mbh, int stall_test = 0);
+void launch_loop_filter4(hipStream_t s, const FilterItem &it, int mbw, int mbh, int stall_test = 0, bool conformant = false);
 size_t loop_filter4_handoff_bytes(int mbw, int mbh);   // the HBM buffer form 4 hands a band's bottom rows to the next band through
 // The simple loop filter (frame header filter_type 1, kernels_lf_simple.hip): luma only, form 3's data movement (lf_banded.h).  launch_no counts
 // the context's simple-filter launches only (its band counters are its own, at LF_SIMPLE_WORD of the progress buffer).
