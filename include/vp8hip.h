@@ -604,6 +604,22 @@ int vp8hip_loop_filter_hidden(vp8hip_ctx *ctx);
 #define VP8HIP_GOLDEN_ONLY 2
 #define VP8HIP_REFRESH_NOTHING 3
 int vp8hip_loop_filter_refresh(vp8hip_ctx *ctx, int refresh, int filter);
+/* ---- cyclic intra refresh (opt-in): forced intra macroblocks in the inter reconstruction in flight -----------------------------------
+ * The rule -- which macroblocks at phase q of period P, what a forced macroblock becomes, why they are independent of each other -- is
+ * vp8host_intra_refresh_forced (include/vp8hip_host.h).  Call it between vp8hip_inter_transform (or vp8hip_inter_finish) and the loop
+ * filter: ONE launch (k_intra_refresh, one workgroup per forced macroblock, no waits), asynchronous, nobody waiting.  It writes the
+ * forced macroblocks' coefficients, unfiltered reconstruction, MB_parts, MB_SSIM, non-zero counts and filter masks -- no
+ * vp8hip_prepare_filter_mask is needed behind it -- and EVERY macroblock's is_inter and modes, so vp8hip_download_intra and the header
+ * coders with use_intra_info = 1 read defined arrays; MB_segment_id stays.  The analysis record counts the forced macroblocks as
+ * intra; an armed check_SSIM (vp8hip_check_ssim_async, before or behind this call) still reports replaced = 0: a refresh is not a
+ * replacement that sends a frame back as a key frame.  The SYNCHRONOUS vp8hip_check_ssim initialises is_inter and modes itself and
+ * is refused (VP8HIP_ERR_STATE, nothing changed) on a reconstruction that carries forced macroblocks.
+ * The caller owns q (vp8drv_set_intra_refresh keeps it for the native frame loop) and decides which frames are refreshed: by the
+ * rule, shown frames that refresh LAST.
+ * VP8HIP_ERR_ARG: period outside 4 .. 1024, q < 0.  VP8HIP_ERR_STATE: a context created with ssim_target > -1 (the SSIM ladder owns
+ * the segment id, and its fallback the intra arrays), a context that shares a frame's searches with other devices, no inter
+ * reconstruction in flight.  Nothing has changed after a refusal. */
+int vp8hip_intra_refresh(vp8hip_ctx *ctx, int period, int q);
 /* on = 1: the context gets a second stream, and work that does not depend on the filtered frame runs beside the loop filter:
  * the entropy stage of the same frame (vp8hip_count_probs ... vp8hip_encode_frame), the next frame's upload, parameter scan
  * and GOLDEN / ALTREF searches.  The filter stays on the stream the frame was coded on and the CONTEXT moves to the other one
@@ -759,7 +775,10 @@ const char *vp8hip_status_string(int status);
  * entry points and the types vp8hip_tile and vp8hip_tile_planes only: vp8drv_config is unchanged);
  * also under 4010: temporal layers (vp8host_temporal_step, vp8hip_loop_filter_refresh, vp8drv_set_temporal_layers,
  * vp8drv_get_frame_layer; entry points, the type vp8drv_layer_info and the values VP8HIP_GOLDEN_ONLY and VP8HIP_REFRESH_NOTHING of
- * the existing is_golden fields only: vp8drv_config, vp8drv_stats, vp8hip_header_params and vp8bs_frame keep their layout). */
+ * the existing is_golden fields only: vp8drv_config, vp8drv_stats, vp8hip_header_params and vp8bs_frame keep their layout);
+ * also under 4010: cyclic intra refresh (vp8host_intra_refresh_forced, vp8host_intra_refresh_count, vp8hip_intra_refresh,
+ * vp8drv_set_intra_refresh, vp8drv_get_intra_refresh; entry points and the type vp8drv_intra_refresh_info only: vp8drv_config and
+ * vp8drv_stats keep their layout). */
 #define VP8HIP_ABI_VERSION 4010
 int vp8hip_abi_version(void);
 /* 1 if this build of the library honours the timing-experiment switches that leave work out of a launch or a wait

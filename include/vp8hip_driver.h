@@ -423,6 +423,33 @@ typedef struct {
 } vp8drv_layer_info;
 int vp8drv_set_temporal_layers(vp8drv *d, int layers, int flags);
 int vp8drv_get_frame_layer(vp8drv *d, vp8drv_layer_info *info);
+/* ---- cyclic intra refresh (the rule: vp8host_intra_refresh_forced, include/vp8hip_host.h; the launch: vp8hip_intra_refresh, include/vp8hip.h) ----
+ * A few macroblocks of every inter frame coded as intra, in a pattern that covers the picture every `period` frames: a receiver that
+ * lost a frame can heal within a period without a key frame (libvpx's error-resilient cyclic refresh; what to do with a PLI:
+ * INTEGRATION.md, section 6.7).  Entry points and not fields of vp8drv_config for the reason vp8drv_set_denoise is one.
+ * vp8drv_set_intra_refresh: period 0 (default, off) or 4 .. 1024, IN FORCE AT THE NEXT FRAME, no key frame needed: the phase q -- the
+ * inter frames since the last key frame as finally coded that refreshed LAST -- advances whether or not refresh is on, so a closed GOP
+ * coded as a chunk of its own (a fresh driver, force_key, the same period) gives the bytes the serial program gives.  It takes the
+ * open check_SSIM verdict first.  With a period in force every shown inter frame that refreshes LAST and has a forced macroblock at
+ * its phase gets vp8hip_intra_refresh behind its transform, and its header carries the intra information, from either first-partition
+ * coder.  Frames of a temporal layer that refresh GOLDEN only or nothing, hidden frames (vp8drv_encode_arf_*) and key frames force
+ * nothing and do not advance q; any key frame restarts it.  Temporal layers, segment modes 1 and 2, vp8drv_set_quantizer, quality
+ * statistics, analysis (mbs_intra counts the forced macroblocks) and everything on the input side compose unchanged.  With period 0:
+ * no launch, no allocation, no byte changes.
+ * VP8HIP_ERR_ARG: a period outside 0 and 4 .. 1024; for a period other than 0: cfg.device_params = 0 or cfg.ssim_target > -1.
+ * VP8HIP_ERR_STATE, for a period other than 0: a member of a live batch (vp8drv_batch_create in turn refuses a driver with a period:
+ * refresh is not batched), a context that shares a frame's searches with other devices -- and if the context joins such a split
+ * later, the calls that take a frame in.  Nothing has changed after a refusal.
+ * vp8drv_get_intra_refresh: for any driver; forced counts are those of the frame just coded as first coded (a frame sent back as a
+ * key frame has forced 0 once its verdict is taken: the call takes it). */
+typedef struct {
+    int32_t period;           /* in force (0 = off) */
+    int32_t last_q;           /* the phase of the frame just coded (0 for a key frame; of a frame that does not refresh LAST: the phase it would have had) */
+    int32_t last_forced;      /* forced macroblocks of the frame just coded */
+    int64_t total_forced;     /* ... of all frames so far */
+} vp8drv_intra_refresh_info;
+int vp8drv_set_intra_refresh(vp8drv *d, int period);
+int vp8drv_get_intra_refresh(vp8drv *d, vp8drv_intra_refresh_info *info);
 
 #ifdef __cplusplus
 }

@@ -506,6 +506,36 @@ typedef struct {
 } vp8host_temporal;
 int vp8host_temporal_step(int layers, int p, int ref_mask, vp8host_temporal *out);
 
+/* CYCLIC INTRA REFRESH: which macroblocks of an inter frame are coded as intra whatever the inter pass made of them, so that a receiver
+ * that lost a frame has the whole picture back within one period without a key frame (vp8hip_intra_refresh, include/vp8hip.h;
+ * vp8drv_set_intra_refresh, include/vp8hip_driver.h; k_intra_refresh).  The project's own; the reference has no such mode.
+ *   P = the period, 4 .. 1024 (VP8HOST_INTRA_REFRESH_MIN / _MAX).
+ *   q = the phase of the frame: the number of inter frames since the last key frame AS FINALLY CODED that refreshed LAST, counted
+ *       before this frame -- the first inter frame behind a key frame has q = 0, and any key frame (scheduled, forced, a scene cut, a
+ *       frame sent back and coded again as one) restarts it.  Frames that refresh GOLDEN only or nothing, and hidden frames, neither
+ *       count nor force anything.
+ *   Macroblock (r, c) -- row r, column c -- of a shown inter frame that refreshes LAST is FORCED iff (c + 2 r) mod P == q mod P.
+ * A forced macroblock is coded as an inter macroblock first, as ever, and then replaced unconditionally by ONE intra attempt, the one
+ * check_SSIM's fallback makes: B_PRED luma by pick_luma_predictor, TM_PRED chroma, predicted from the unfiltered reconstruction, with
+ * the quantisers of the segment the inter pass left the macroblock in (MB_segment_id: 3 by default, the caller's map or the AQ
+ * segment in segment modes 1 and 2); the segment id does not change.  What is written is what the fallback writes: coefficients
+ * (blocks 0 .. 23), the unfiltered reconstruction, MB_parts = 2, MB_SSIM = the attempt's value, is_inter = 0, the sixteen sub-block
+ * modes, the non-zero count (sum of |coefficient| over blocks 0 .. 23) and filter mask -1.  Every macroblock that is not forced has
+ * is_inter = 1 and its sixteen modes 0.
+ * Why 2 r: the left, above, above-left and above-right neighbours of a forced macroblock have phases -1, -2, -3 and -1 relative to
+ * it, none of which is 0 modulo P for P >= 4 -- so intra prediction (the above-right samples that sub-block rows 1 to 3 take from the
+ * row above the macroblock included) reads inter-coded reconstruction only, and the forced macroblocks of a frame may be coded in
+ * any order or all at once.  And every macroblock is forced exactly once in any P consecutive phases.
+ * Motion vectors are not constrained to the refreshed area, and GOLDEN / ALTREF may carry damage back in: a receiver's recovery
+ * within a period is not guaranteed: it depends on the motion (measured: profiles/README.md, "Intra refresh").
+ * vp8host_intra_refresh_forced: 1 or 0; -1: period outside 4 .. 1024, or q, r or c negative.
+ * vp8host_intra_refresh_count: the forced macroblocks of a frame of mbw x mbh macroblocks at phase q (the sum of the predicate); -1:
+ * a bad period, q negative, mbw or mbh below 1.  Plain C, no state. */
+#define VP8HOST_INTRA_REFRESH_MIN 4
+#define VP8HOST_INTRA_REFRESH_MAX 1024
+int vp8host_intra_refresh_forced(int period, int q, int r, int c);
+int vp8host_intra_refresh_count(int mbw, int mbh, int period, int q);
+
 /* The key-frame schedule of a whole file with scene detection on, from the chroma differences of its frames alone: nothing but the
  * frame loop's own steps (vp8enc.cpp:364-416, 487), for t = 0 .. nframes - 1:
  *     vp8host_gop_next;

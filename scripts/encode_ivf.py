@@ -106,6 +106,8 @@ def canvas_main(a):
         drv.set_denoise(a.denoise)
     if a.aq:
         drv.set_segment_mode(2, a.aq)
+    if a.intra_refresh:
+        drv.set_intra_refresh(a.intra_refresh)
     for k, (px, ox, oy, opacity) in enumerate(overlays):
         drv.set_overlay(k, px, ox, oy, opacity)
     out = []
@@ -148,6 +150,7 @@ def main():
     ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames made by temporal filtering on the device (vp8drv_set_arf, vp8drv_encode_arf_host): one in front of every group of PERIOD frames of a GOP, centred on the group's last frame, FRAMES frames wide (default 7) at STRENGTH 0..6 (default 3)")
     ap.add_argument("--no-check-ssim", action="store_true", help="cfg.check_ssim = 0, scripts/native/y4m_to_ivf's -no-check-ssim: no check_SSIM behind the inter frames (with --temporal-layers the unreferenced frames are then not loop-filtered)")
     ap.add_argument("--temporal-layers", type=int, choices=(1, 2, 3), default=0, metavar="N", help="a stream of N temporal layers (vp8drv_set_temporal_layers): it still decodes when the frames above a layer are dropped")
+    ap.add_argument("--intra-refresh", type=int, default=0, metavar="N", help="cyclic intra refresh with period N, 4..1024 (vp8drv_set_intra_refresh; scripts/native/y4m_to_ivf's -intra-refresh): a few macroblocks of every inter frame coded as intra, the whole picture every N frames that refresh LAST; the phase restarts with every GOP, so chunks give the serial bytes; not with --ssim-target above -1")
     ap.add_argument("--keep-layers", type=int, choices=(0, 1, 2), default=None, metavar="K", help="with --temporal-layers: write only the frames of temporal_id <= K, with their own timestamps")
     ap.add_argument("--scene-detect", action="store_true", help="key frames where the serial program with scene detection puts them: the sequence is scanned first (gop_shard.scan_differences), api.scene_plan gives the chunks")
     ap.add_argument("--scan-batch", type=int, default=8, metavar="N", help="... members of the scanning batch (1..8)")
@@ -175,6 +178,8 @@ def main():
         sys.exit("--temporal-layers: one process, and not with --arf (layers never search ALTREF)")
     if a.aq and a.segment_map:
         sys.exit("--aq and --segment-map: one of them picks the segments")
+    if a.intra_refresh and (not 4 <= a.intra_refresh <= 1024 or a.ssim_target > -1.0):
+        sys.exit("--intra-refresh: a period of 4..1024, and not with --ssim-target above -1 (the SSIM ladder owns the intra fallback)")
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dist = None
     if world > 1:      # the library's own process group (vp8hip_group_*: RCCL inside libvp8hip.so, the id through a file): no GPU framework in the host
@@ -249,6 +254,8 @@ def main():
             enc.encode = encode_layered
         if arf:      # (the driver refuses the filter's own stream beside hidden frames)
             enc.drv.set_arf(arf[2] + 1)
+        if a.intra_refresh and not scan:      # (a scanning member codes nothing, and a batch refuses a driver with a period)
+            enc.drv.set_intra_refresh(a.intra_refresh)
         if a.denoise:
             enc.drv.set_denoise(a.denoise)
         if a.aq:

@@ -41,6 +41,7 @@ ap.add_argument("--analysis", type=int, choices=(0, 1), default=0, help="1 = the
 ap.add_argument("--aq", type=int, choices=(0, 1, 2, 3), default=0, metavar="N", help="variance-adaptive quantisation at strength N (vp8drv_set_segment_mode, mode 2): what k_aq_map_b + k_aq_seg_b cost, and with one stream the mapped macroblock kernel next to the default's in the same run")
 ap.add_argument("--arf", default="", metavar="PERIOD[:FRAMES[:STRENGTH]]", help="hidden alternate reference frames (vp8drv_set_arf, vp8drv_encode_arf_device): every stream codes one in front of every PERIOD-th frame from a window of FRAMES device-resident frames (default 7) at STRENGTH (default 3); with one stream also what k_arf_filter_b costs by HIP events")
 ap.add_argument("--temporal-layers", type=int, choices=(1, 2, 3), default=1, metavar="N", help="a stream of N temporal layers (vp8drv_set_temporal_layers): with N > 1 scheduled alt-refs are off (--altref-range above the GOP) and the unreferenced frames are loop-filtered only if --check-ssim, --quality-stats or --analysis reads the filter's launch")
+ap.add_argument("--intra-refresh", type=int, default=0, metavar="N", help="cyclic intra refresh with period N, 4..1024 (vp8drv_set_intra_refresh): what k_intra_refresh costs; with one stream also its launch by HIP events (VP8HIP_INTRA_REFRESH_1WAVE=1: the one-wavefront form)")
 ap.add_argument("--altref-range", type=int, default=5, metavar="N", help="vp8drv_config.altref_range (default 5, the driver's); above the GOP size = no scheduled alt-refs, what --temporal-layers 2 and 3 run with: the base to compare them with")
 ap.add_argument("--tiles", choices=("", "letterbox", "grid4", "pip"), default="", metavar="LAYOUT", help="compose every frame of device-resident tiles (vp8drv_set_canvas): letterbox, grid4 or pip; with one stream also what k_compose_b costs by HIP events")
 ap.add_argument("--tiles-precomposed", action="store_true", help="with --tiles: the same pictures composed on the host beforehand and handed over as plain frames")
@@ -173,6 +174,9 @@ if arf:
 if a.temporal_layers > 1:
     for d in drvs:
         d.set_temporal_layers(a.temporal_layers)
+if a.intra_refresh:
+    for d in drvs:
+        d.set_intra_refresh(a.intra_refresh)
 sizes = [0] * a.streams
 hidden_coded = [0] * a.streams
 
@@ -283,6 +287,20 @@ if a.temporal_layers > 1:
     print(f"temporal layers {a.temporal_layers}: of every {period} inter frames {sum(s['refresh'] == api.REFRESH_NONE for s in steps)} refresh no buffer and "
           f"{sum(s['use_golden'] for s in steps)} search GOLDEN beside LAST; stream 0's last frame: temporal_id {info.temporal_id}, tl0_pic_idx {info.tl0_pic_idx}, "
           f"{'loop-filtered' if info.filtered else 'not loop-filtered'}")
+if a.intra_refresh:
+    info = drvs[0].intra_refresh()
+    frames_coded = drvs[0].stats().frame_number
+    print(f"intra refresh, period {info.period}: {info.total_forced} forced macroblocks over {frames_coded} frames of stream 0 "
+          f"({info.total_forced / max(1, frames_coded) / mbs * 100:.2f} % of the macroblocks); its last frame: phase {info.last_q}, {info.last_forced} forced")
+    if a.streams == 1:      # the launch by HIP events (the intra stage of an inter frame is this launch alone)
+        d = drvs[0]
+        d.hip.synchronize()
+        d.hip.profile_enable(["intra"])
+        work(0, 32, False)
+        ms, n = d.hip.profile_read().get("intra", (0.0, 0))
+        d.hip.profile_enable([])
+        print(f"k_intra_refresh ({'one wavefront' if os.environ.get('VP8HIP_INTRA_REFRESH_1WAVE') else 'two wavefronts'} per forced macroblock) by HIP events: "
+              f"{ms / max(n, 1) * 1e3:.1f} us per launch over {n} launches")
 if a.quality_stats:
     q = drvs[0].quality_summary()
     print(f"quality of stream 0 over {q.frames} frames: PSNR overall {q.psnr_all:.3f} dB, avg {q.psnr_avg:.3f} dB, SSIM {q.ssim_all:.5f}")

@@ -3,7 +3,11 @@
 //   y4m_to_ivf <in.y4m> <out.ivf> [-g gop] [-partitions P] [-qmin q] [-qmax q] [-SSIM-target t] [-altref-range n] [-no-scene-detect]
 //              [-no-check-ssim] [-conformant] [-simple-filter] [-psnr] [-resize WxH] [-resize-filter area|lanczos] [-denoise N] [-aq N]
 //              [-input-format NAME] [-input-transfer pq|hlg[:PEAK]] [-overlay FILE:WxH:X:Y[:OPACITY]] [-analysis FILE] [-deinterlace field|adaptive[:top|bottom]] [-crop W:H:X:Y] [-rotate 0|90|180|270] [-mirror]
-//              [-arf PERIOD[:FRAMES[:STRENGTH]]] [-temporal-layers N]
+//              [-arf PERIOD[:FRAMES[:STRENGTH]]] [-temporal-layers N] [-intra-refresh N]
+// -intra-refresh N (4..1024): cyclic intra refresh (vp8drv_set_intra_refresh; the rule: include/vp8hip_host.h,
+// vp8host_intra_refresh_forced): a few macroblocks of every inter frame that refreshes LAST are coded as intra, in a pattern that covers
+// the picture every N such frames, so that a receiver that lost a frame heals without a key frame.  The forced share of all macroblocks
+// is printed next to -psnr's summary.  Not with an -SSIM-target above -1.
 // -temporal-layers N (1..3): a stream of N temporal layers (vp8drv_set_temporal_layers; the rule: include/vp8hip_host.h,
 // vp8host_temporal_step), which still decodes when every frame above a layer is dropped.  The option sets -altref-range to the GOP
 // size + 1 (scheduled alt-refs off), turns the overlapped loop filter off and with it the early hand-over of the next frame: this mode
@@ -92,6 +96,7 @@ int main(int argc, char **argv) {
     const char *analysis_path = nullptr;      // -analysis
     int arf_period = 0, arf_frames = 7, arf_strength = 3;      // -arf
     int layers = 0;          // -temporal-layers (0: the option was not given)
+    int refresh = 0;         // -intra-refresh (0: off)
     static const char *const format_names[VP8HOST_FORMAT_COUNT] = {"i420", "nv12", "i422", "i444", "p010", "i010", "i210", "i410"};
     for (int i = 3; i < argc; ++i) {
         auto val = [&]() { return i + 1 < argc ? argv[++i] : "0"; };
@@ -168,6 +173,10 @@ int main(int argc, char **argv) {
             layers = atoi(val());
             if (layers < 1 || layers > 3) { fprintf(stderr, "-temporal-layers 1..3\n"); return 2; }
         }
+        else if (!strcmp(argv[i], "-intra-refresh")) {
+            refresh = atoi(val());
+            if (refresh < VP8HOST_INTRA_REFRESH_MIN || refresh > VP8HOST_INTRA_REFRESH_MAX) { fprintf(stderr, "-intra-refresh 4..1024\n"); return 2; }
+        }
         else if (!strcmp(argv[i], "-resize")) { if (sscanf(val(), "%dx%d", &rw, &rh) != 2) { fprintf(stderr, "-resize WxH\n"); return 2; } }
         else if (!strcmp(argv[i], "-resize-filter")) {
             const char *f = val();
@@ -188,6 +197,7 @@ int main(int argc, char **argv) {
         cfg.overlap_filter = 0;                   // (the next frame's GOLDEN search would start beside the filter that writes GOLDEN)
         fprintf(stderr, "-temporal-layers: the loop filter runs on the frame's own stream in this mode (no frame is handed over early)\n");
     }
+    if (refresh && cfg.ssim_target > -1.0f) { fprintf(stderr, "-intra-refresh does not go with an -SSIM-target above -1 (the SSIM ladder owns the intra fallback)\n"); return 2; }
     FILE *in = fopen(argv[1], "rb");
     if (!in) { perror(argv[1]); return 1; }
     uint8_t head[256];
@@ -267,6 +277,7 @@ int main(int argc, char **argv) {
     if (crop[0]) CK(vp8drv_set_source_window(drv, pitch, crop[2], crop[3]));
     if (deint) CK(vp8drv_set_deinterlace(drv, deint, field));
     if (layers) CK(vp8drv_set_temporal_layers(drv, layers, 0));
+    if (refresh) CK(vp8drv_set_intra_refresh(drv, refresh));
     uint32_t per_layer[3] = {0, 0, 0}, unfiltered = 0;
     long long dn_filtered = 0, dn_total = 0, di_woven = 0, di_missing = 0;
     FILE *analysis = nullptr;
@@ -539,6 +550,13 @@ int main(int argc, char **argv) {
     if (deint)
         fprintf(stderr, "Deinterlacer %s, %s field kept: %lld of %lld missing luma samples woven (%.1f %%)\n", deint == 1 ? "field" : "adaptive",
                 field ? "bottom" : "top", di_woven, di_missing, di_missing ? 100.0 * (double)di_woven / (double)di_missing : 0.0);
+    if (refresh) {
+        vp8drv_intra_refresh_info ri;
+        CK(vp8drv_get_intra_refresh(drv, &ri));
+        const double all = (double)n * (double)((Wc / 16) * (Hc / 16));
+        fprintf(stderr, "Intra refresh period %d: %lld of %.0f macroblocks forced intra (%.2f %%)\n", refresh, (long long)ri.total_forced, all,
+                all > 0 ? 100.0 * (double)ri.total_forced / all : 0.0);
+    }
     vp8drv_destroy(drv);
     for (int k = 0; k < RING; ++k) vp8hip_host_free(0, buf[k]);
     printf("%s: %u frames %dx%d (coded %dx%d), %u key (%d by scene change, %d recoded), %zu bytes; %d hardware queues\n", argv[2], n, W, H, Wc, Hc, keys,

@@ -107,6 +107,7 @@ int main(int argc, char **argv) {
             else if (!strcmp(f, "lanczos")) cfg.scale_filter = 1;
             else { fprintf(stderr, "-resize-filter area|lanczos\n"); return 2; }
         }
+        else if (!strcmp(argv[i], "-intra-refresh")) { fprintf(stderr, "-intra-refresh: cyclic intra refresh is not batched (y4m_to_ivf codes it)\n"); return 2; }
         else if (!strcmp(argv[i], "-temporal-layers")) { fprintf(stderr, "-temporal-layers: temporal layers are not batched (y4m_to_ivf codes them)\n"); return 2; }
         else if (!strcmp(argv[i], "-arf")) { fprintf(stderr, "-arf: hidden alternate reference frames are not batched (y4m_to_ivf codes them)\n"); return 2; }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }

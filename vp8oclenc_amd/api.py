@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "vp8hip_set_canvas", "vp8hip_canvas_tiles", "vp8hip_compose_current_device", "vp8hip_compose_current_host", "vp8host_tile_valid",
     "vp8host_compose_frame", "vp8drv_set_canvas", "vp8drv_encode_frame_tiles_device", "vp8drv_encode_frame_tiles_host",
     "vp8host_temporal_step", "vp8hip_loop_filter_refresh", "vp8drv_set_temporal_layers", "vp8drv_get_frame_layer",
+    "vp8host_intra_refresh_forced", "vp8host_intra_refresh_count", "vp8hip_intra_refresh", "vp8drv_set_intra_refresh", "vp8drv_get_intra_refresh",
 ]
 
 
@@ -62,6 +63,7 @@ ARF_MAX_FRAMES = 7  # VP8HOST_ARF_MAX_FRAMES, include/vp8hip_host.h
 REFRESH_LAST, REFRESH_GOLDEN, REFRESH_NONE, REFRESH_ALL = range(4)   # VP8HOST_REFRESH_* (the first three also VP8HIP_REFRESH_*)
 GOLDEN_ONLY, REFRESH_NOTHING = 2, 3   # VP8HIP_GOLDEN_ONLY / VP8HIP_REFRESH_NOTHING: is_golden of a temporal layer's inter frame (header params, bitstream.Frame)
 TL_KEEP_RECON = 1   # VP8DRV_TL_KEEP_RECON, include/vp8hip_driver.h
+INTRA_REFRESH_MIN, INTRA_REFRESH_MAX = 4, 1024   # VP8HOST_INTRA_REFRESH_MIN / _MAX, include/vp8hip_host.h
 ERR_OVERFLOW = -7   # VP8HIP_ERR_OVERFLOW, include/vp8hip.h
 ERR_FORMAT = -8     # VP8HIP_ERR_FORMAT
 SHARPNESS_ON_DEVICE = -2 ** 31   # VP8HIP_SHARPNESS_ON_DEVICE
@@ -602,6 +604,31 @@ class Temporal(C.Structure):
 class LayerInfo(C.Structure):
     """vp8drv_layer_info, include/vp8hip_driver.h"""
     _fields_ = [(n, C.c_int32) for n in ("temporal_id", "tl0_pic_idx", "layer_sync", "refresh", "use_golden", "filtered")]
+
+
+class IntraRefreshInfo(C.Structure):
+    """vp8drv_intra_refresh_info, include/vp8hip_driver.h"""
+    _fields_ = [("period", C.c_int32), ("last_q", C.c_int32), ("last_forced", C.c_int32), ("total_forced", C.c_int64)]
+
+
+def intra_refresh_forced(period: int, q: int, r: int, c: int) -> bool:
+    """vp8host_intra_refresh_forced: is macroblock (row r, column c) forced at phase q of the period; ValueError where the rule refuses"""
+    lib = load_library()
+    lib.vp8host_intra_refresh_forced.argtypes = [C.c_int] * 4
+    v = lib.vp8host_intra_refresh_forced(int(period), int(q), int(r), int(c))
+    if v < 0:
+        raise ValueError(f"vp8host_intra_refresh_forced({period}, {q}, {r}, {c}) refused")
+    return bool(v)
+
+
+def intra_refresh_count(mbw: int, mbh: int, period: int, q: int) -> int:
+    """vp8host_intra_refresh_count: the forced macroblocks of a frame of mbw x mbh macroblocks at phase q; ValueError where it refuses"""
+    lib = load_library()
+    lib.vp8host_intra_refresh_count.argtypes = [C.c_int] * 4
+    v = lib.vp8host_intra_refresh_count(int(mbw), int(mbh), int(period), int(q))
+    if v < 0:
+        raise ValueError(f"vp8host_intra_refresh_count({mbw}, {mbh}, {period}, {q}) refused")
+    return v
 
 
 def temporal_step(layers: int, p: int, ref_mask: int = 3):
@@ -1393,6 +1420,22 @@ class NativeDriver:
         if rc != 0:
             raise Vp8HipError(f"vp8drv_set_temporal_layers({layers}, {flags}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
 
+    def set_intra_refresh(self, period: int) -> None:
+        """vp8drv_set_intra_refresh: cyclic intra refresh with the period (4 .. 1024; 0 = off) from the next frame on (include/vp8hip_driver.h)"""
+        self.lib.vp8drv_set_intra_refresh.argtypes = [C.c_void_p, C.c_int]
+        rc = self.lib.vp8drv_set_intra_refresh(self.h, int(period))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_set_intra_refresh({period}): {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+
+    def intra_refresh(self) -> IntraRefreshInfo:
+        """vp8drv_get_intra_refresh: period, last_q, last_forced, total_forced"""
+        info = IntraRefreshInfo()
+        self.lib.vp8drv_get_intra_refresh.argtypes = [C.c_void_p, C.POINTER(IntraRefreshInfo)]
+        rc = self.lib.vp8drv_get_intra_refresh(self.h, C.byref(info))
+        if rc != 0:
+            raise Vp8HipError(f"vp8drv_get_intra_refresh: {self.lib.vp8hip_status_string(rc).decode()} ({rc})", rc)
+        return info
+
     def frame_layer(self) -> LayerInfo:
         """vp8drv_get_frame_layer: temporal_id, tl0_pic_idx, layer_sync, refresh, use_golden and filtered of the frame just made final"""
         info = LayerInfo()
@@ -1779,6 +1822,11 @@ class Vp8Hip:
         filtered reconstruction becomes GOLDEN and LAST stays; REFRESH_NONE: it is dropped (unfiltered with filter = False)"""
         self.lib.vp8hip_loop_filter_refresh.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self._chk(self.lib.vp8hip_loop_filter_refresh(self.h, int(refresh), int(filter)), "loop_filter_refresh")
+
+    def intra_refresh(self, period: int, q: int):
+        """vp8hip_intra_refresh: the forced macroblocks of phase q of the period in the inter reconstruction in flight (asynchronous)"""
+        self.lib.vp8hip_intra_refresh.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._chk(self.lib.vp8hip_intra_refresh(self.h, int(period), int(q)), "intra_refresh")
 
     def refresh_frame(self):
         """(Y, U, V) of the surface the last loop_filter_refresh with REFRESH_GOLDEN or REFRESH_NONE ended (VP8HIP_DBG_REFRESH_FRAME)"""

@@ -35,8 +35,8 @@ bool analysis_src_item(vp8hip_ctx *c, hipStream_t s, AnalysisSrcItem &it) {
 }
 
 bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it) {
-    const bool checked = c->an_checked;
-    c->an_checked = false;
+    const bool checked = c->an_checked, forced = c->an_forced;
+    c->an_checked = c->an_forced = false;
     const int frame = c->cur_count - 1;
     if (!c->in.an_on || frame < 0 || c->an_src_frame[frame & 1] != frame) return false;   // (a frame taken in before analysis was turned on has no record)
     it.parts = c->out.parts;
@@ -51,6 +51,7 @@ bool analysis_mb_item(vp8hip_ctx *c, hipStream_t s, AnalysisMbItem &it) {
     it.frame_number = frame;
     it.is_key = c->lf_key ? 1 : 0;
     it.mbs = c->mbs;
+    it.forced = (forced && !c->lf_key) ? 1 : 0;
     c->an_mb_frame = frame;
     c->an_mb.stream = s;
     return true;

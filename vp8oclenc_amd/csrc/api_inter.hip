@@ -114,6 +114,7 @@ void recon_made(vp8hip_ctx *c, bool key) {
     c->recon_ready = true;
     c->recon_key = key;
     c->an_checked = false;
+    c->an_forced = false;
 }
 // ... and its filter has been launched: it is the LAST reference of the next frame (vp8enc.cpp:395-401); its replicated edges are made
 // with its pyramid, in one launch, when that frame begins (pyramids())
@@ -296,6 +297,7 @@ int vp8hip_check_ssim(vp8hip_ctx *c, int32_t *replaced, float *new_ssim, float *
     JOIN_LF(c);
     if (!c) return VP8HIP_ERR_ARG;
     if (!c->recon_ready || c->recon < 0 || c->cur_count == 0) return VP8HIP_ERR_STATE;
+    if (c->an_forced) return VP8HIP_ERR_STATE;      // (its launch initialises is_inter and modes: the forced macroblocks of vp8hip_intra_refresh would read as inter)
     c->ent_counted_partitions = 0;
     {
         Timed t(c, VP8HIP_K_INTRA);
@@ -329,6 +331,25 @@ int vp8hip_check_ssim_async(vp8hip_ctx *c, const int32_t refqi[4], int qi_min) {
         Timed t(c, VP8HIP_K_INTRA);
         launch_check_fallback(c->stream, &it, 1, c->ssim_target, c->mbw, c->mbh, c->conformant);
     }
+    HIPCHK(c, hipGetLastError());
+    return VP8HIP_OK;
+}
+
+// Cyclic intra refresh (the rule: include/vp8hip_host.h): the forced macroblocks of the inter reconstruction in flight, one launch
+// behind k_mb on the frame's stream, nobody waiting.  It writes every macroblock's is_inter and modes, and the replaced macroblocks'
+// non-zero counts and masks: no vp8hip_prepare_filter_mask afterwards.
+int vp8hip_intra_refresh(vp8hip_ctx *c, int period, int q) {
+    USE_DEVICE(c);
+    if (!c || period < VP8HOST_INTRA_REFRESH_MIN || period > VP8HOST_INTRA_REFRESH_MAX || q < 0) return VP8HIP_ERR_ARG;
+    if (c->ssim_target > -1.0f || c->shard_comm) return VP8HIP_ERR_STATE;      // (the SSIM ladder owns the segment id; a split codes part of a frame)
+    JOIN_LF(c);
+    if (!c->recon_ready || c->recon < 0 || c->recon_key || c->cur_count == 0) return VP8HIP_ERR_STATE;
+    c->ent_counted_partitions = 0;
+    {
+        Timed t(c, VP8HIP_K_INTRA);
+        launch_intra_refresh(c->stream, c->cur, c->frames[c->recon].f, c->out, c->d_sd, c->intra_modes, c->intra_is_inter, period, q, c->mbw, c->mbh);
+    }
+    c->an_forced = true;
     HIPCHK(c, hipGetLastError());
     return VP8HIP_OK;
 }

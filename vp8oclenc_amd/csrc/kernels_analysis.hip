@@ -154,8 +154,9 @@ __device__ __forceinline__ void mb_body(const AnalysisMbItem &it) {
     __shared__ int s_cnt[4][NCNT];
     __shared__ long long s_big[4][NBIG];
     const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
-    // is_inter counts only when check_SSIM ran on this attempt and replaced something (otherwise the array is stale)
-    const bool flags = !it.is_key && it.replaced && __builtin_nontemporal_load(it.replaced) > 0;
+    // is_inter counts only when check_SSIM ran on this attempt and replaced something (otherwise the array is stale), or when the
+    // attempt carries forced intra macroblocks (k_intra_refresh wrote the whole array)
+    const bool flags = !it.is_key && (it.forced || (it.replaced && __builtin_nontemporal_load(it.replaced) > 0));
     int cnt[NCNT] = {};
     long long big[NBIG] = {};
     for (int mb = (int)threadIdx.x; mb < it.mbs; mb += 256) {

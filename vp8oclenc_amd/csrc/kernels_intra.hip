@@ -245,7 +245,8 @@ __device__ __forceinline__ int luma_block(Sh &sh, int lane, const LaneK &k, cons
 }
 
 // the 8 chroma blocks (TM_PRED from the macroblock's edges, :674-739) on lanes 0..31: quad = plane * 4 + block
-__device__ __forceinline__ void chroma_blocks(Sh &sh, int lane, const LaneK &k, int uv_dc, int uv_ac) {
+// tr: the calling wavefront's transpose scratch (nullptr: the tile's own; a second wavefront on the same tile brings its own)
+__device__ __forceinline__ void chroma_blocks(Sh &sh, int lane, const LaneK &k, int uv_dc, int uv_ac, int16_t *tr = nullptr) {
     const int l = lane & 31, pl = l >> 4, bb = (l >> 2) & 3, br = bb >> 1, bc = bb & 1, i = l & 3;
     const uint8_t *t = sh.cimg[pl];
     const uint32_t tdw = *reinterpret_cast<const uint32_t *>(t + 4 + 4 * bc);
@@ -256,7 +257,7 @@ __device__ __forceinline__ void chroma_blocks(Sh &sh, int lane, const LaneK &k, 
     for (int j = 0; j < 4; ++j) p[j] = sat8(byte_of(tdw, j) + dl);
     const LaneQ q = lane_q(uv_dc, uv_ac, lane & 3);
     int qc[4], w;
-    const uint32_t rec = code_unit(sh.tr, lane, p, sdw, q, qc, w);
+    const uint32_t rec = code_unit(tr ? tr : sh.tr, lane, p, sdw, q, qc, w);
     if (lane < 32) {
         *reinterpret_cast<uint32_t *>(&sh.cimg[pl][(4 * br + i + 1) * CIMG_S + 4 + 4 * bc]) = rec;
         int16_t *cf = sh.coef + (16 + 4 * pl + bb) * 16;
@@ -354,6 +355,33 @@ __device__ __forceinline__ int replaced_nz(const Sh &sh, int lane) {
     return wave_sum(s);
 }
 
+// The neighbours of macroblock (r, c) from the unfiltered reconstruction into the work tiles: lanes 0..5 / 6..8 / 9..11 the row above
+// (x = -4 .. 19 / -4 .. 7), lanes 12..27 / 28..35 / 36..43 the column left; the rest of the wavefront idles.  The caller has made sure
+// that whoever writes those samples has finished (k_intra, k_intra_check3: the row above's progress; k_intra_refresh: the launch before).
+__device__ __forceinline__ void fill_neighbours(Sh &sh, const Plane &ry, const Plane &ru, const Plane &rv, int r, int c, int mbw, int lane) {
+    if (lane >= 44) return;
+    const bool top = lane < 12;
+    const int pl = top ? (lane < 6 ? 0 : (lane < 9 ? 1 : 2)) : (lane < 28 ? 0 : (lane < 36 ? 1 : 2));
+    const int j = top ? (pl == 0 ? lane : (pl == 1 ? lane - 6 : lane - 9)) : (pl == 0 ? lane - 12 : (pl == 1 ? lane - 28 : lane - 36));
+    const Plane &P = pl == 0 ? ry : (pl == 1 ? ru : rv);
+    const int msz = pl == 0 ? 16 : 8;
+    const bool last_col_ar = top && pl == 0 && j == 5 && c == mbw - 1;      // no macroblock above-right: repeat top[15] (:596-601)
+    const int x = top ? msz * c - 4 + 4 * (last_col_ar ? 4 : j) : msz * c - 4;
+    const int y = top ? msz * r - 1 : msz * r + j;
+    uint32_t v = ld_agent(P.p + (ptrdiff_t)y * P.stride + x);
+    if (last_col_ar) v = (v >> 24) * 0x01010101u;
+    if (top && r == 0) v = 0x7f7f7f7fu;                                     // 127 above the frame, also in the corner (:575-589)
+    else if (c == 0 && (!top || j == 0)) v = 0x81818181u;                   // 129 left of the frame (:540-551)
+    uint8_t *dst = pl == 0 ? sh.img : sh.cimg[pl - 1];
+    const int S = pl == 0 ? IMG_S : CIMG_S;
+    *reinterpret_cast<uint32_t *>(dst + (top ? 4 * j : (j + 1) * S)) = v;
+    if (top && pl == 0 && j == 5) {   // blocks 7, 11, 15 take T4..T7 from the row above the macroblock too (:630, top_pred_Y[16..19])
+        *reinterpret_cast<uint32_t *>(sh.img + 4 * IMG_S + 20) = v;
+        *reinterpret_cast<uint32_t *>(sh.img + 8 * IMG_S + 20) = v;
+        *reinterpret_cast<uint32_t *>(sh.img + 12 * IMG_S + 20) = v;
+    }
+}
+
 __global__ __launch_bounds__(64) void k_intra(IntraArgs a) {
     __shared__ __attribute__((aligned(16))) Sh sh;
     const int lane = threadIdx.x, r = blockIdx.x, mbw = a.mbw;
@@ -397,29 +425,7 @@ __global__ __launch_bounds__(64) void k_intra(IntraArgs a) {
                 }
             }
         }
-        if (lane < 44) {
-            // lanes 0..5 / 6..8 / 9..11: the row above (x = -4 .. 19 / -4 .. 7); lanes 12..27 / 28..35 / 36..43: the column left
-            const bool top = lane < 12;
-            const int pl = top ? (lane < 6 ? 0 : (lane < 9 ? 1 : 2)) : (lane < 28 ? 0 : (lane < 36 ? 1 : 2));
-            const int j = top ? (pl == 0 ? lane : (pl == 1 ? lane - 6 : lane - 9)) : (pl == 0 ? lane - 12 : (pl == 1 ? lane - 28 : lane - 36));
-            const Plane &P = pl == 0 ? a.ry : (pl == 1 ? a.ru : a.rv);
-            const int msz = pl == 0 ? 16 : 8;
-            const bool last_col_ar = top && pl == 0 && j == 5 && c == mbw - 1;      // no macroblock above-right: repeat top[15] (:596-601)
-            const int x = top ? msz * c - 4 + 4 * (last_col_ar ? 4 : j) : msz * c - 4;
-            const int y = top ? msz * r - 1 : msz * r + j;
-            uint32_t v = ld_agent(P.p + (ptrdiff_t)y * P.stride + x);
-            if (last_col_ar) v = (v >> 24) * 0x01010101u;
-            if (top && r == 0) v = 0x7f7f7f7fu;                                     // 127 above the frame, also in the corner (:575-589)
-            else if (c == 0 && (!top || j == 0)) v = 0x81818181u;                   // 129 left of the frame (:540-551)
-            uint8_t *dst = pl == 0 ? sh.img : sh.cimg[pl - 1];
-            const int S = pl == 0 ? IMG_S : CIMG_S;
-            *reinterpret_cast<uint32_t *>(dst + (top ? 4 * j : (j + 1) * S)) = v;
-            if (top && pl == 0 && j == 5) {   // blocks 7, 11, 15 take T4..T7 from the row above the macroblock too (:630, top_pred_Y[16..19])
-                *reinterpret_cast<uint32_t *>(sh.img + 4 * IMG_S + 20) = v;
-                *reinterpret_cast<uint32_t *>(sh.img + 8 * IMG_S + 20) = v;
-                *reinterpret_cast<uint32_t *>(sh.img + 12 * IMG_S + 20) = v;
-            }
-        }
+        fill_neighbours(sh, a.ry, a.ru, a.rv, r, c, mbw, lane);
         lds_order();
         float cur_ssim = a.key ? 0.0f : a.o.ssim[mb];
         // ---- attempts: key frame = segment 0 once; fallback = AQ (2), HQ (1), UQ (0) while below the target --------
@@ -549,28 +555,7 @@ __device__ __forceinline__ void intra_check3_body(const IntraArgs &a) {
         }
         __syncthreads();
         if (s_abort) return;
-        if (lane < 44) {   // neighbours, as in k_intra (each wave fills its own tile)
-            const bool top = lane < 12;
-            const int pl = top ? (lane < 6 ? 0 : (lane < 9 ? 1 : 2)) : (lane < 28 ? 0 : (lane < 36 ? 1 : 2));
-            const int j = top ? (pl == 0 ? lane : (pl == 1 ? lane - 6 : lane - 9)) : (pl == 0 ? lane - 12 : (pl == 1 ? lane - 28 : lane - 36));
-            const Plane &P = pl == 0 ? a.ry : (pl == 1 ? a.ru : a.rv);
-            const int msz = pl == 0 ? 16 : 8;
-            const bool last_col_ar = top && pl == 0 && j == 5 && c == mbw - 1;
-            const int x = top ? msz * c - 4 + 4 * (last_col_ar ? 4 : j) : msz * c - 4;
-            const int y = top ? msz * r - 1 : msz * r + j;
-            uint32_t v = ld_agent(P.p + (ptrdiff_t)y * P.stride + x);
-            if (last_col_ar) v = (v >> 24) * 0x01010101u;
-            if (top && r == 0) v = 0x7f7f7f7fu;
-            else if (c == 0 && (!top || j == 0)) v = 0x81818181u;
-            uint8_t *dst = pl == 0 ? sh.img : sh.cimg[pl - 1];
-            const int S = pl == 0 ? IMG_S : CIMG_S;
-            *reinterpret_cast<uint32_t *>(dst + (top ? 4 * j : (j + 1) * S)) = v;
-            if (top && pl == 0 && j == 5) {
-                *reinterpret_cast<uint32_t *>(sh.img + 4 * IMG_S + 20) = v;
-                *reinterpret_cast<uint32_t *>(sh.img + 8 * IMG_S + 20) = v;
-                *reinterpret_cast<uint32_t *>(sh.img + 12 * IMG_S + 20) = v;
-            }
-        }
+        fill_neighbours(sh, a.ry, a.ru, a.rv, r, c, mbw, lane);   // (each wave fills its own tile)
         lds_order();
         int mymode = 0;
 #define LUMA(BR, BC)                                                   \
@@ -629,6 +614,108 @@ __device__ __forceinline__ void intra_check3_body(const IntraArgs &a) {
 __global__ __launch_bounds__(192) void k_intra_check3(IntraArgs a) { intra_check3_body(a); }
 // the same for the members of a batch: blockIdx.z = member
 __global__ __launch_bounds__(192) void k_intra_check3_b(BatchOf<IntraArgs> b) { intra_check3_body(b.item[blockIdx.z]); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Cyclic intra refresh (the rule: include/vp8hip_host.h): macroblock (r, c) of an inter frame is forced iff
+// (c + 2 r) mod P == q mod P, and is then replaced by the ONE attempt the fallback above makes, in the segment the inter
+// pass left it in.  No forced macroblock has a forced left, above, above-left or above-right neighbour (their phases are
+// -1, -2, -3, -1: never 0 modulo P >= 4), so every one of them predicts from what k_mb wrote and nothing here waits for
+// anything: no progress counters, no spin waits, one workgroup per forced macroblock on a grid of (ceil(mbw / P) + 1, mbh).
+// Workgroup (x, r), x < ceil(mbw / P), owns column ((q - 2 r) mod P) + P x of row r and leaves if that is past the row; the
+// last workgroup of each row writes is_inter = 1 and modes = 0 for the row's other macroblocks (it knows which they are:
+// nothing is written twice).
+// A launch is as long as ONE macroblock: sixteen dependent luma blocks on one wavefront.  With WAVES = 2 a second
+// wavefront takes what is not on that chain -- the source tiles' loads beside the neighbours' loads, the eight chroma
+// blocks beside the luma blocks -- and wavefront 0 takes the SSIM (mb_ssim's order) and commits after the barrier.
+// ---------------------------------------------------------------------------------------------------------------------
+struct RefreshArgs {
+    Plane cy, cu, cv;       // current frame
+    Plane ry, ru, rv;       // reconstruction (unfiltered), read for the neighbours and written
+    MBOut o;
+    const SegData *sd;
+    int32_t *modes;         // [MBs][16]
+    int32_t *is_inter;      // [MBs]
+    int mbw, period, qm;    // qm = q mod period
+    int nx;                 // ceil(mbw / period): blockIdx.x == nx is the row's housekeeper
+};
+
+template <int WAVES>
+__device__ __forceinline__ void intra_refresh_body(const RefreshArgs &a) {
+    __shared__ __attribute__((aligned(16))) Sh sh;
+    __shared__ __attribute__((aligned(16))) int16_t tr_aux[WAVES == 2 ? 64 * 4 : 4];   // the second wavefront's transposes
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = blockIdx.y, mbw = a.mbw, P = a.period;
+    const int first = ((a.qm - 2 * r) % P + P) % P;   // the row's first forced column
+    const int mb_row0 = r * mbw;
+    if ((int)blockIdx.x == a.nx) {
+        for (int i = threadIdx.x; i < mbw; i += 64 * WAVES)
+            if (i % P != first) a.is_inter[mb_row0 + i] = 1;
+        for (int i = threadIdx.x; i < mbw * 16; i += 64 * WAVES)
+            if ((i >> 4) % P != first) a.modes[(size_t)mb_row0 * 16 + i] = 0;
+        return;
+    }
+    const int c = first + P * (int)blockIdx.x;
+    if (c >= mbw) return;
+    const int mb = mb_row0 + c;
+    const bool luma_wave = wave == 0, aux_wave = wave == WAVES - 1;
+    const LaneK k = lane_consts(lane);
+    const Steps st = steps_of(a.sd, a.o.seg[mb] & 3);   // the segment stays what the inter pass made it
+    const LaneQ ql = lane_q(st.y_dc, st.y_ac, lane & 3);
+    if (aux_wave) {
+        *reinterpret_cast<uint32_t *>(&sh.srcY[lane * 4]) =
+            *reinterpret_cast<const uint32_t *>(a.cy.p + (ptrdiff_t)(16 * r + (lane >> 2)) * a.cy.stride + 16 * c + 4 * (lane & 3));
+        if (lane < 32) {
+            const Plane &Pl = lane < 16 ? a.cu : a.cv;
+            const int l = lane & 15;
+            *reinterpret_cast<uint32_t *>(&sh.srcC[lane >> 4][l * 4]) =
+                *reinterpret_cast<const uint32_t *>(Pl.p + (ptrdiff_t)(8 * r + (l >> 1)) * Pl.stride + 8 * c + 4 * (l & 1));
+        }
+    }
+    if (luma_wave) fill_neighbours(sh, a.ry, a.ru, a.rv, r, c, mbw, lane);   // all of them are k_mb's (see above), final since the launch before
+    if (WAVES == 2) __syncthreads();   // the tiles cross wavefronts: LDS is ordered within one wavefront only
+    else lds_order();
+    int mymode = 0;
+    if (luma_wave) {
+#define LUMA(BR, BC)                                                   \
+        {                                                              \
+            const int m_ = luma_block<BR, BC>(sh, lane, k, ql);        \
+            if (lane == 4 * BR + BC) mymode = m_;                      \
+        }
+        LUMA(0, 0) LUMA(0, 1) LUMA(0, 2) LUMA(0, 3)
+        LUMA(1, 0) LUMA(1, 1) LUMA(1, 2) LUMA(1, 3)
+        LUMA(2, 0) LUMA(2, 1) LUMA(2, 2) LUMA(2, 3)
+        LUMA(3, 0) LUMA(3, 1) LUMA(3, 2) LUMA(3, 3)
+#undef LUMA
+    }
+    if (aux_wave) chroma_blocks(sh, lane, k, st.uv_dc, st.uv_ac, WAVES == 2 ? tr_aux : nullptr);
+    if (WAVES == 2) {
+        __syncthreads();
+        if (!luma_wave) return;
+    }
+    if (lane < 16) a.modes[(size_t)mb * 16 + lane] = mymode;
+    const float s = mb_ssim(sh, lane);
+    const int nz = replaced_nz(sh, lane);
+    st_agent(a.ry.p + (ptrdiff_t)(16 * r + (lane >> 2)) * a.ry.stride + 16 * c + 4 * (lane & 3),
+             *reinterpret_cast<const uint32_t *>(&sh.img[((lane >> 2) + 1) * IMG_S + 4 + 4 * (lane & 3)]));
+    if (lane < 32) {
+        const Plane &Pl = lane < 16 ? a.ru : a.rv;
+        const int l = lane & 15;
+        st_agent(Pl.p + (ptrdiff_t)(8 * r + (l >> 1)) * Pl.stride + 8 * c + 4 * (l & 1),
+                 *reinterpret_cast<const uint32_t *>(&sh.cimg[lane >> 4][((l >> 1) + 1) * CIMG_S + 4 + 4 * (l & 1)]));
+    }
+    uint32_t *gc = reinterpret_cast<uint32_t *>(a.o.coeffs + (size_t)mb * 400);
+    const uint32_t *lc = reinterpret_cast<const uint32_t *>(sh.coef);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) gc[lane + 64 * i] = lc[lane + 64 * i];   // blocks 0..23; block 24 (Y2) stays
+    if (lane == 0) {
+        a.o.parts[mb] = 2;      // are4x4
+        a.o.ssim[mb] = s;
+        a.is_inter[mb] = 0;
+        a.o.nz[mb] = nz;        // prepare_filter_mask of the replaced macroblock: no launch of its own afterwards
+        a.o.mask[mb] = -1;
+    }
+}
+__global__ __launch_bounds__(128) void k_intra_refresh(RefreshArgs a) { intra_refresh_body<2>(a); }
+__global__ __launch_bounds__(64) void k_intra_refresh_1w(RefreshArgs a) { intra_refresh_body<1>(a); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Key frames, pipelined at 4x4-block granularity.  In k_intra one wavefront walks the 16 luma blocks of a macroblock
@@ -981,6 +1068,24 @@ void launch_intra_key_batch(hipStream_t s, const CheckItem *items, int n, int mb
     }
     const size_t shmem = 5 * (size_t)(mbw * 16 + 16) + 3856;
     hipLaunchKernelGGL(k_intra_key4_b, dim3(mbh, 1, n), dim3(64 * K4_WAVES), shmem, s, b);
+}
+
+void launch_intra_refresh(hipStream_t s, const Frame &cur, const Frame &recon, const MBOut &o, const SegData *d_sd, int32_t *modes,
+                          int32_t *is_inter, int period, int q, int mbw, int mbh) {
+    RefreshArgs a;
+    a.cy = cur.Y[0]; a.cu = cur.U; a.cv = cur.V;
+    a.ry = recon.Y[0]; a.ru = recon.U; a.rv = recon.V;
+    a.o = o;
+    a.sd = d_sd;
+    a.modes = modes;
+    a.is_inter = is_inter;
+    a.mbw = mbw;
+    a.period = period;
+    a.qm = q % period;
+    a.nx = (mbw + period - 1) / period;
+    static const bool one_wave = getenv("VP8HIP_INTRA_REFRESH_1WAVE") != nullptr;   // A/B switch: chroma and the source loads on the luma wavefront
+    if (one_wave) hipLaunchKernelGGL(k_intra_refresh_1w, dim3(a.nx + 1, mbh), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_intra_refresh, dim3(a.nx + 1, mbh), dim3(128), 0, s, a);
 }
 
 void launch_ssim_stats(hipStream_t s, const MBOut &o, const int32_t *is_inter, int mbs, const int32_t *err, int32_t *out) {

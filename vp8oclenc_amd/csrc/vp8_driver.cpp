@@ -48,6 +48,10 @@ struct vp8drv {
     // of the next frame (shown frames since the last key frame as finally coded), tid-0 frames made final, the frame just coded
     int tl_layers = 1, tl_next = 1, tl_flags = 0, tl_p = 0, tl0_count = 0;
     vp8drv_layer_info layer{};
+    // vp8drv_set_intra_refresh: the period in force (0 = off), the rule's q of the next inter frame that refreshes LAST (it advances
+    // whether or not a period is set), the forced macroblocks of the frame just coded, the record
+    int ir_period = 0, ir_q = 0, ir_forced = 0;
+    vp8drv_intra_refresh_info ir{};
     // read-back buffers of vp8drv_get_frame
     std::vector<int32_t> seg, nz, ref, parts, is_inter, modes;
     std::vector<int16_t> vectors;
@@ -181,6 +185,8 @@ void key_layer_record(vp8drv *d) {
     d->tl_p = 1;
     d->layer = vp8drv_layer_info{0, 0, 0, VP8HOST_REFRESH_ALL, 0, 1};
     layer_final(d);
+    d->ir_q = d->ir_forced = 0;      // ... and so does the intra refresh's phase; a key frame forces nothing
+    d->ir.last_q = d->ir.last_forced = 0;
 }
 
 // prepare_segments_data() + intra_transform() (vp8enc.cpp:379-383, :411-414, :446-450) and the common tail
@@ -210,6 +216,7 @@ void inter_frame_done(vp8drv *d) {
     d->st.inter_frames++;
     d->st.frame_number = d->gop.frame_number;
     d->tl_p++;
+    if (d->layer.refresh == VP8HOST_REFRESH_LAST) d->ir_q++;      // the intra refresh's phase counts the frames that refreshed LAST
     layer_final(d);
 }
 
@@ -228,8 +235,9 @@ int resolve(vp8drv *d) {
     d->st.last_min_ssim = min1;
     // e_data.is_inter_mb / mode travel to the header coder only when something was replaced: with nothing below the target the
     // fallback's launch left at once and did not even initialise them (all macroblocks inter: the same bits without them)
-    d->checked = replaced > 0;
-    d->replaced = replaced;
+    // ... or when the frame carries forced intra macroblocks (vp8drv_set_intra_refresh: replaced is then 0, the target being -1)
+    d->checked = replaced > 0 || d->ir_forced > 0;
+    d->replaced = replaced > 0 ? replaced : d->ir_forced;
     if (updated) d->sharpness = 7;      // prepare_segments_data(1, 7), :260-261, happened on the device
     if (replaced > d->mbs / 6 || new_ssim < d->cfg.ssim_target) {
         d->st.redone_as_key++;
@@ -284,6 +292,20 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     d->st.last_was_altref = layered ? 0 : d->gop.current_is_altref;
     d->checked = false;
     d->replaced = 0;
+    // vp8drv_set_intra_refresh: the forced macroblocks of a frame that refreshes LAST, behind the transform; the header then takes the
+    // intra information (from either first-partition coder: the host coder's prob_intra is made of d->replaced)
+    d->ir_forced = 0;
+    d->ir.last_q = d->ir_q;
+    if (d->ir_period && tl.refresh == VP8HOST_REFRESH_LAST) {
+        d->ir_forced = vp8host_intra_refresh_count(d->W / 16, d->H / 16, d->ir_period, d->ir_q);
+        if (d->ir_forced > 0) {
+            DRV_CHK(vp8hip_intra_refresh(d->hip, d->ir_period, d->ir_q));
+            d->checked = true;
+            d->replaced = d->ir_forced;
+            d->ir.total_forced += d->ir_forced;
+        }
+    }
+    d->ir.last_forced = d->ir_forced;
     // an unreferenced frame is filtered only if something reads the filter's output or rides in its launch
     const bool filter = tl.refresh != VP8HOST_REFRESH_NONE || d->cfg.check_ssim || d->cfg.quality_stats || d->analysis || (d->tl_flags & VP8DRV_TL_KEEP_RECON);
     d->layer = vp8drv_layer_info{tl.temporal_id, 0, tl.layer_sync, tl.refresh, use_golden, filter ? 1 : 0};
@@ -374,7 +396,8 @@ int intake_restarts(vp8drv *d, bool scheduled_key) {
 
 // a driver with temporal layers whose context has since joined a by-reference split (the context's refresh ending would refuse it in
 // the middle of the frame): refused before the frame is taken in
-bool layers_refused(const vp8drv *d) { return (d->tl_layers > 1 || d->tl_next > 1) && vp8hip_shard_world(d->hip) > 0; }
+// ... and so is a driver with an intra refresh period (vp8hip_intra_refresh would refuse behind the transform)
+bool layers_refused(const vp8drv *d) { return (d->tl_layers > 1 || d->tl_next > 1 || d->ir_period) && vp8hip_shard_world(d->hip) > 0; }
 
 int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     const int P = d->cfg.num_partitions;
@@ -552,8 +575,8 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
         // the batched loop is the device-parameter loop (what bench.py and a file-to-file transcode run); one launch serves all
         // members, so what travels as ONE kernel argument must agree: quantizer range, check_SSIM on or off, partitions, filter type
         if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect || drv[i]->arf || drv[i]->canvas || drv[i]->rotation_consumed || drv[i]->hidden_altref ||
-            drv[i]->tl_layers > 1 || drv[i]->tl_next > 1)
-            return VP8HIP_ERR_ARG;      // (hidden frames are not batched, nor is a driver whose references a hidden frame still shapes; nor are temporal layers)
+            drv[i]->tl_layers > 1 || drv[i]->tl_next > 1 || drv[i]->ir_period)
+            return VP8HIP_ERR_ARG;      // (hidden frames are not batched, nor is a driver whose references a hidden frame still shapes; nor are temporal layers, nor is intra refresh)
         const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
         if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
             a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
@@ -685,6 +708,8 @@ static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *c
         d->st.last_was_altref = d->gop.current_is_altref;
         d->checked = false;
         d->replaced = 0;
+        d->ir_forced = d->ir.last_forced = 0;      // (a member has no period; what its last frame on its own forced is not this frame's)
+        d->ir.last_q = d->ir_q;
         d->layer = vp8drv_layer_info{0, 0, 0, VP8HOST_REFRESH_LAST, ug[i], 1};
         if (check) d->verdict_pending = true;   // counted when the verdict is in (resolve())
         else inter_frame_done(d);
@@ -1026,6 +1051,23 @@ int vp8drv_get_frame_layer(vp8drv *d, vp8drv_layer_info *info) {
     if (!d->have_frame || d->last_hidden) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     *info = d->layer;
+    return VP8HIP_OK;
+}
+
+// ---- cyclic intra refresh ---------------------------------------------------------------------------------------------------------------
+int vp8drv_set_intra_refresh(vp8drv *d, int period) {
+    if (!d || (period != 0 && (period < VP8HOST_INTRA_REFRESH_MIN || period > VP8HOST_INTRA_REFRESH_MAX))) return VP8HIP_ERR_ARG;
+    if (period && (!d->cfg.device_params || d->cfg.ssim_target > -1.0f)) return VP8HIP_ERR_ARG;
+    if (period && (d->in_batch || vp8hip_shard_world(d->hip) > 0)) return VP8HIP_ERR_STATE;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    d->ir_period = d->ir.period = period;
+    return VP8HIP_OK;
+}
+
+int vp8drv_get_intra_refresh(vp8drv *d, vp8drv_intra_refresh_info *info) {
+    if (!d || !info) return VP8HIP_ERR_ARG;
+    { const int rc = resolve(d); if (rc < 0) return rc; }
+    *info = d->ir;
     return VP8HIP_OK;
 }
 

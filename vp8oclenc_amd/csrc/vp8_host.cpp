@@ -599,6 +599,21 @@ int vp8host_temporal_step(int layers, int p, int ref_mask, vp8host_temporal *out
     return 0;
 }
 
+int vp8host_intra_refresh_forced(int period, int q, int r, int c) {  // the rule: include/vp8hip_host.h
+    if (period < VP8HOST_INTRA_REFRESH_MIN || period > VP8HOST_INTRA_REFRESH_MAX || q < 0 || r < 0 || c < 0) return -1;
+    return (int)(((long long)c + 2ll * r) % period == q % period);
+}
+
+int vp8host_intra_refresh_count(int mbw, int mbh, int period, int q) {
+    if (period < VP8HOST_INTRA_REFRESH_MIN || period > VP8HOST_INTRA_REFRESH_MAX || q < 0 || mbw < 1 || mbh < 1) return -1;
+    int n = 0;
+    for (int r = 0; r < mbh; ++r) {
+        const int first = (int)((((long long)q - 2ll * r) % period + period) % period);      // the row's first forced column
+        if (first < mbw) n += (mbw - first + period - 1) / period;
+    }
+    return n;
+}
+
 int vp8host_scene_plan(const int32_t *udiff, const int32_t *vdiff, int nframes, int gop_size, uint8_t *is_key, uint8_t *by_scene) {
     if (!udiff || !vdiff || !is_key || nframes < 0 || gop_size < 1) return -1;
     vp8host_gop g;

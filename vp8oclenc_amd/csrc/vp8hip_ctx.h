@@ -212,6 +212,7 @@ struct vp8hip_ctx {
     // last launched for.  an_checked: check_SSIM ran on the reconstruction in flight (its verdict's device copy says whether the
     // fallback's flags count).
     bool an_have_prev = false, an_checked = false;
+    bool an_forced = false;         // vp8hip_intra_refresh ran on the reconstruction in flight: is_inter is defined, forced macroblocks count as intra
     Record<vp8::AnalysisMirror> an;
     RecordView<vp8::AnalysisSrcMirror> an_src[2];
     RecordView<vp8::AnalysisMbMirror> an_mb;

@@ -192,7 +192,8 @@ void launch_denoise_batch(hipStream_t s, const DenoiseItem *items, int n, int le
 // overwrites with the luma; have_prev 0: measures `spatial` and copies only.  `acc` (five 64-bit words, zero at rest) takes the
 // workgroups' sums and tickets; the workgroup with the last ticket writes the record into `host`, seq last.
 // k_analyse_mb_b: one workgroup per frame over the per-macroblock arrays; `replaced` = the device copy of check_SSIM's verdict (word 0:
-// macroblocks replaced) when the check ran on this attempt, else nullptr (is_inter is then not read).
+// macroblocks replaced) when the check ran on this attempt, else nullptr (is_inter is then not read) -- unless `forced`: the attempt
+// carries forced intra macroblocks (vp8hip_intra_refresh), whose launch wrote every macroblock's is_inter.
 struct AnalysisSrcMirror { uint64_t spatial, sse, sad; int32_t static_mbs, have_prev, frame_number; uint32_t seq; };
 struct AnalysisMbMirror {
     int32_t frame_number, is_key, mbs_total, mbs_intra, mbs_split, mbs_zero_mv, mbs_no_coeffs, mbs_ref[3], segment_mbs[4];
@@ -206,7 +207,7 @@ struct AnalysisMbItem {
     const int16_t *vec;
     AnalysisMbMirror *host;
     uint32_t seq;
-    int32_t frame_number, is_key, mbs;
+    int32_t frame_number, is_key, mbs, forced;
 };
 void launch_analyse_src_batch(hipStream_t s, const AnalysisSrcItem *items, int n);
 void launch_analyse_mb_batch(hipStream_t s, const AnalysisMbItem *items, int n);
@@ -484,6 +485,11 @@ struct CheckItem {
 };
 void launch_check_fallback(hipStream_t s, const CheckItem *items, int n, float target, int mbw, int mbh, int modes_of_kept);
 void launch_intra_key_batch(hipStream_t s, const CheckItem *items, int n, int mbw, int mbh);   // the key frames of n members of a batch, one launch
+// cyclic intra refresh (k_intra_refresh; the rule: include/vp8hip_host.h): the forced macroblocks of an inter frame at phase q of
+// `period`, each by a workgroup of its own on a grid of (ceil(mbw / period) + 1, mbh) -- no list, no ordering, no waits -- and
+// is_inter = 1 / modes = 0 for every other macroblock by the last workgroup of each row
+void launch_intra_refresh(hipStream_t s, const Frame &cur, const Frame &recon, const MBOut &o, const SegData *d_sd, int32_t *modes,
+                          int32_t *is_inter, int period, int q, int mbw, int mbh);
 
 // ---- device helpers ---------------------------------------------------------------------------
 #if defined(__HIPCC__)
