@@ -12,6 +12,7 @@
 #include "../../include/vp8hip_bitstream.h"
 #include "../../include/vp8hip_driver.h"
 #include "../../include/vp8hip_host.h"
+#include "driver_settings.h"
 
 struct vp8drv {
     vp8hip_ctx *hip = nullptr;
@@ -29,28 +30,19 @@ struct vp8drv {
     bool verdict_pending = false;    // check_SSIM's verdict on the frame just coded is still on its way (resolve())
     const uint8_t *staged = nullptr; // vp8drv_stage_frame_host: these planes are the context's current frame already (and, with scene_detect, their scan is under way)
     bool staged_scan = false;
-    int denoise = 0;                 // vp8drv_set_denoise: the level in force
-    int deinterlace = 0, field = 0;  // vp8drv_set_deinterlace: the mode and the field kept
-    int format = 0;                  // vp8drv_set_source_format: the format in force
-    int colour = 0;                  // vp8drv_set_source_colour: the colour matrix in force (read by BGRA / RGBA and a tone-mapped source only)
-    int transfer = 0, peak = 0;      // vp8drv_set_source_transfer: the transfer and peak in force (0, 0: off)
-    bool analysis = false;           // vp8drv_set_analysis
-    bool in_batch = false;           // a member of a live vp8drv_batch
-    bool window = false;             // vp8drv_set_source_window: a window is in force
-    int canvas = 0;                  // vp8drv_set_canvas: tiles of the canvas in force (0 = none)
-    // vp8drv_set_arf: strength + 1 (0 = off).  last_hidden: the frame just coded is a hidden one.  rotation_consumed: a hidden frame's
-    // transform has applied the reference rotation the last shown frame owed; the next shown frame's must not apply it again.
-    // hidden_altref: ALTREF holds a hidden frame's reconstruction (until a key frame or a scheduled shown alt-ref rotates LAST into it).
-    int arf = 0;
+    vp8::DriverSettings s;           // the settings in force: what every refusal reads (driver_settings.h)
+    // last_hidden: the frame just coded is a hidden one.  rotation_consumed: a hidden frame's transform has applied the reference rotation
+    // the last shown frame owed; the next shown frame's must not apply it again.  hidden_altref: ALTREF holds a hidden frame's
+    // reconstruction (until a key frame or a scheduled shown alt-ref rotates LAST into it).
     bool last_hidden = false, rotation_consumed = false, hidden_altref = false;
     vp8drv_arf_stats arf_st{};
-    // vp8drv_set_temporal_layers: layers in force (1 = off) and asked for (in force from the next key frame on), the flags, the rule's p
-    // of the next frame (shown frames since the last key frame as finally coded), tid-0 frames made final, the frame just coded
-    int tl_layers = 1, tl_next = 1, tl_flags = 0, tl_p = 0, tl0_count = 0;
+    // temporal layers: the rule's p of the next frame (shown frames since the last key frame as finally coded), tid-0 frames made final,
+    // the frame just coded
+    int tl_p = 0, tl0_count = 0;
     vp8drv_layer_info layer{};
-    // vp8drv_set_intra_refresh: the period in force (0 = off), the rule's q of the next inter frame that refreshes LAST (it advances
-    // whether or not a period is set), the forced macroblocks of the frame just coded, the record
-    int ir_period = 0, ir_q = 0, ir_forced = 0;
+    // intra refresh: the rule's q of the next inter frame that refreshes LAST (it advances whether or not a period is set), the forced
+    // macroblocks of the frame just coded, the record
+    int ir_q = 0, ir_forced = 0;
     vp8drv_intra_refresh_info ir{};
     // read-back buffers of vp8drv_get_frame
     std::vector<int32_t> seg, nz, ref, parts, is_inter, modes;
@@ -136,6 +128,21 @@ int vp8drv_create(vp8drv **out, int width, int height, int device_ordinal, const
     vp8host_gop_init(&d->gop, cfg->gop_size, cfg->altref_range);
     vp8host_quantizer_ladders(cfg->qi_min, cfg->qi_max, d->lastqi, d->altrefqi);
     d->qi_min = cfg->qi_min < cfg->qi_max ? cfg->qi_min : cfg->qi_max;
+    vp8::DriverSettings &s = d->s;
+    s.device_params = cfg->device_params != 0;
+    s.overlap_filter = cfg->overlap_filter != 0;
+    s.scene_detect = cfg->scene_detect != 0;
+    s.quality_stats = cfg->quality_stats != 0;
+    s.ssim_target = cfg->ssim_target > -1.0f;
+    s.scheduled_altref = cfg->altref_range <= cfg->gop_size;
+    s.qi_min = cfg->qi_min;
+    s.qi_max = cfg->qi_max;
+    s.num_partitions = cfg->num_partitions;
+    s.check_ssim = cfg->check_ssim != 0;
+    s.loop_filter_type = cfg->loop_filter_type;
+    s.in_width = cfg->in_width;
+    s.in_height = cfg->in_height;
+    s.scale_filter = cfg->in_width ? cfg->scale_filter : 0;
     *out = d;
     return VP8HIP_OK;
 }
@@ -162,6 +169,24 @@ namespace {
         if (rc_ != VP8HIP_OK) return rc_; \
     } while (0)
 
+using vp8::refusal;
+
+// the settings with what moves by itself filled in: what refusal() and operator== are asked about
+vp8::DriverSettings settings(const vp8drv *d) {
+    vp8::DriverSettings s = d->s;
+    s.hidden_shapes_refs = d->rotation_consumed || d->hidden_altref;
+    s.shard = vp8hip_shard_world(d->hip) > 0;
+    s.overlays = vp8hip_overlay_count(d->hip) > 0;
+    vp8hip_segment_mode(d->hip, &s.seg_mode, &s.seg_strength);
+    return s;
+}
+
+// planes handed over early under other settings are not these settings' frame
+void drop_staged(vp8drv *d) {
+    d->staged = nullptr;
+    d->staged_scan = false;
+}
+
 // segment data of the current frame: on the device, or from the host mirror on the caller's luma plane
 int segments(vp8drv *d, const uint8_t *host_y, bool key, const int32_t *refqi) {
     d->sharpness = VP8HIP_SHARPNESS_ON_DEVICE;
@@ -181,7 +206,7 @@ void layer_final(vp8drv *d) {
 
 // a key frame is p = 0 of the temporal pattern, whoever asked for it: the pattern restarts, and a layer count asked for takes force
 void key_layer_record(vp8drv *d) {
-    d->tl_layers = d->tl_next;
+    d->s.tl_layers = d->s.tl_next;
     d->tl_p = 1;
     d->layer = vp8drv_layer_info{0, 0, 0, VP8HOST_REFRESH_ALL, 0, 1};
     layer_final(d);
@@ -189,25 +214,53 @@ void key_layer_record(vp8drv *d) {
     d->ir.last_q = d->ir.last_forced = 0;
 }
 
-// prepare_segments_data() + intra_transform() (vp8enc.cpp:379-383, :411-414, :446-450) and the common tail
-// (:472-473): filter mask, loop filter.  The filtered key frame is LAST = GOLDEN = ALTREF (intra_part.h:1091-1098).
-int key_frame(vp8drv *d, const uint8_t *host_y) {
-    DRV_CHK(segments(d, host_y, true, d->altrefqi));
-    DRV_CHK(vp8hip_intra_transform(d->hip));
+// the key frame just coded and filtered is final: GOP state, counters and the record of the frame just coded
+void key_frame_final(vp8drv *d) {
     d->scene.last_key_detect = d->gop.frame_number;       // intra_part.h:1093, for every key frame whoever asked for it
     vp8host_gop_key_coded(&d->gop);
-    DRV_CHK(vp8hip_prepare_filter_mask(d->hip, nullptr));
-    DRV_CHK(vp8hip_loop_filter(d->hip));
     vp8host_gop_frame_done(&d->gop);
     d->st.key_frames++;
     d->st.frame_number = d->gop.frame_number;
     d->have_frame = true;
     d->last_key = d->last_altref = true;
-    d->last_hidden = d->rotation_consumed = d->hidden_altref = false;      // (LAST = GOLDEN = ALTREF = this frame, by the rotation it owes)
+    // (LAST = GOLDEN = ALTREF = this frame, by the rotation it owes.  For a member of a batch a no-op: batch membership refuses a driver
+    // whose references a hidden frame shapes, and a member codes no hidden frame)
+    d->last_hidden = d->rotation_consumed = d->hidden_altref = false;
     d->checked = false;
     d->replaced = 0;
     key_layer_record(d);
+}
+
+// prepare_segments_data() + intra_transform() (vp8enc.cpp:379-383, :411-414, :446-450) and the common tail
+// (:472-473): filter mask, loop filter.  The filtered key frame is LAST = GOLDEN = ALTREF (intra_part.h:1091-1098).
+int key_frame(vp8drv *d, const uint8_t *host_y) {
+    DRV_CHK(segments(d, host_y, true, d->altrefqi));
+    DRV_CHK(vp8hip_intra_transform(d->hip));
+    DRV_CHK(vp8hip_prepare_filter_mask(d->hip, nullptr));
+    DRV_CHK(vp8hip_loop_filter(d->hip));
+    key_frame_final(d);
     return 1;
+}
+
+// the inter frame just coded, shown or hidden: what vp8drv_get_frame needs to know about it
+void inter_frame_coded(vp8drv *d, bool altref, bool hidden) {
+    d->have_frame = true;
+    d->last_key = false;
+    d->last_altref = altref;
+    d->last_hidden = hidden;
+    d->checked = false;
+    d->replaced = 0;
+}
+
+// ... and a shown one's references, for vp8drv_get_stats
+void shown_inter_coded(vp8drv *d, int use_golden, int use_altref, int prev_is_golden, int prev_is_altref, int was_altref) {
+    d->st.last_use_golden = use_golden;
+    d->st.last_use_altref = use_altref;
+    d->st.refs_searched += 1 + use_golden + use_altref;
+    d->st.last_prev_is_golden = prev_is_golden;
+    d->st.last_prev_is_altref = prev_is_altref;
+    d->st.last_was_altref = was_altref;
+    inter_frame_coded(d, was_altref != 0, false);
 }
 
 // the inter frame just coded is final: the counters of main()'s loop tail
@@ -263,9 +316,9 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     if (key) return key_frame(d, host_y);
     // vp8enc.cpp:390, 419: loop-filter strength of the current frame -> segment data
     // vp8drv_set_temporal_layers: references, ending and quantiser ladder from the rule in the place of the GOP state's flags
-    const bool layered = d->tl_layers > 1;
+    const bool layered = d->s.tl_layers > 1;
     vp8host_temporal tl{0, 0, VP8HOST_REFRESH_LAST, 0};
-    if (layered && vp8host_temporal_step(d->tl_layers, d->tl_p, d->cfg.ref_mask, &tl)) return VP8HIP_ERR_STATE;
+    if (layered && vp8host_temporal_step(d->s.tl_layers, d->tl_p, d->cfg.ref_mask, &tl)) return VP8HIP_ERR_STATE;
     const int32_t *refqi = (d->gop.current_is_altref && !layered) ? d->altrefqi : d->lastqi;   // vp8enc.cpp:149-151
     DRV_CHK(segments(d, host_y, false, refqi));
     int32_t use_golden = 0, use_altref = 0;
@@ -280,26 +333,18 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     if (prev_is_altref) d->hidden_altref = false;
     if (d->hidden_altref) use_altref = 1;
     d->rotation_consumed = false;
-    d->last_hidden = false;
     use_golden &= d->cfg.ref_mask & 1;
     use_altref &= (d->cfg.ref_mask >> 1) & 1;
     DRV_CHK(vp8hip_inter_transform(d->hip, prev_is_golden, prev_is_altref, use_golden, use_altref));
-    d->st.last_use_golden = use_golden;
-    d->st.last_use_altref = use_altref;
-    d->st.refs_searched += 1 + use_golden + use_altref;
-    d->st.last_prev_is_golden = prev_is_golden;
-    d->st.last_prev_is_altref = prev_is_altref;
-    d->st.last_was_altref = layered ? 0 : d->gop.current_is_altref;
-    d->checked = false;
-    d->replaced = 0;
+    shown_inter_coded(d, use_golden, use_altref, prev_is_golden, prev_is_altref, layered ? 0 : d->gop.current_is_altref);
     // vp8drv_set_intra_refresh: the forced macroblocks of a frame that refreshes LAST, behind the transform; the header then takes the
     // intra information (from either first-partition coder: the host coder's prob_intra is made of d->replaced)
     d->ir_forced = 0;
     d->ir.last_q = d->ir_q;
-    if (d->ir_period && tl.refresh == VP8HOST_REFRESH_LAST) {
-        d->ir_forced = vp8host_intra_refresh_count(d->W / 16, d->H / 16, d->ir_period, d->ir_q);
+    if (d->s.ir_period && tl.refresh == VP8HOST_REFRESH_LAST) {
+        d->ir_forced = vp8host_intra_refresh_count(d->W / 16, d->H / 16, d->s.ir_period, d->ir_q);
         if (d->ir_forced > 0) {
-            DRV_CHK(vp8hip_intra_refresh(d->hip, d->ir_period, d->ir_q));
+            DRV_CHK(vp8hip_intra_refresh(d->hip, d->s.ir_period, d->ir_q));
             d->checked = true;
             d->replaced = d->ir_forced;
             d->ir.total_forced += d->ir_forced;
@@ -307,7 +352,7 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     }
     d->ir.last_forced = d->ir_forced;
     // an unreferenced frame is filtered only if something reads the filter's output or rides in its launch
-    const bool filter = tl.refresh != VP8HOST_REFRESH_NONE || d->cfg.check_ssim || d->cfg.quality_stats || d->analysis || (d->tl_flags & VP8DRV_TL_KEEP_RECON);
+    const bool filter = tl.refresh != VP8HOST_REFRESH_NONE || d->cfg.check_ssim || d->cfg.quality_stats || d->s.analysis || (d->s.tl_flags & VP8DRV_TL_KEEP_RECON);
     d->layer = vp8drv_layer_info{tl.temporal_id, 0, tl.layer_sync, tl.refresh, use_golden, filter ? 1 : 0};
     if (d->cfg.check_ssim && (d->cfg.device_params || !host_y)) {
         // check_SSIM (vp8enc.cpp:231-263) with nobody waiting for it: fallback, statistics and the filter update on the device,
@@ -316,9 +361,6 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
         DRV_CHK(vp8hip_check_ssim_async(d->hip, refqi, d->qi_min));
         DRV_CHK(vp8hip_loop_filter_refresh(d->hip, tl.refresh, 1));
         d->verdict_pending = true;
-        d->have_frame = true;
-        d->last_key = false;
-        d->last_altref = d->st.last_was_altref != 0;
         return 0;
     }
     if (d->cfg.check_ssim) {
@@ -351,9 +393,6 @@ int frame_body(vp8drv *d, const uint8_t *host_y, bool key) {
     // do_loop_filter (loop_filter.h:185-190) follows directly
     DRV_CHK(vp8hip_loop_filter_refresh(d->hip, tl.refresh, filter ? 1 : 0));
     inter_frame_done(d);
-    d->have_frame = true;
-    d->last_key = false;
-    d->last_altref = d->st.last_was_altref != 0;
     return 0;
 }
 
@@ -382,30 +421,51 @@ vp8hip_header_params header_params(const vp8drv *d) {
 // frames sent back by check_SSIM are not the schedule's.
 // vp8drv_set_analysis: its history restarts at the same frames, for the same reason.
 int intake_restarts(vp8drv *d, bool scheduled_key) {
-    if (d->analysis && scheduled_key) {
+    if (d->s.analysis && scheduled_key) {
         const int rc = vp8hip_analysis_restart(d->hip);
         if (rc != VP8HIP_OK) return rc;
     }
-    if (d->deinterlace && scheduled_key) {      // vp8drv_set_deinterlace: and so does its history
+    if (d->s.deinterlace && scheduled_key) {      // vp8drv_set_deinterlace: and so does its history
         const int rc = vp8hip_deinterlace_restart(d->hip);
         if (rc != VP8HIP_OK) return rc;
     }
-    if (d->denoise && scheduled_key) return vp8hip_denoise_restart(d->hip);
+    if (d->s.denoise && scheduled_key) return vp8hip_denoise_restart(d->hip);
     return VP8HIP_OK;
 }
 
 // a driver with temporal layers whose context has since joined a by-reference split (the context's refresh ending would refuse it in
 // the middle of the frame): refused before the frame is taken in
 // ... and so is a driver with an intra refresh period (vp8hip_intra_refresh would refuse behind the transform)
-bool layers_refused(const vp8drv *d) { return (d->tl_layers > 1 || d->tl_next > 1 || d->ir_period) && vp8hip_shard_world(d->hip) > 0; }
+bool layers_refused(const vp8drv *d) {
+    const vp8::DriverSettings s = settings(d);
+    if (layered(s) && refusal(s, vp8::LAYERS)) return true;
+    return s.ir_period && refusal(s, vp8::INTRA_REFRESH);
+}
+
+// a setter's way in: the table's word on the feature, then the open check_SSIM verdict (a frame sent back is coded again under the
+// settings it was coded under)
+int ask(vp8drv *d, vp8::Feature f, bool on = true) {
+    DRV_CHK(refusal(settings(d), f, on));
+    const int rc = resolve(d);
+    return rc < 0 ? rc : VP8HIP_OK;
+}
+
+// The shape the intake setters share: the arguments, the table, the open verdict, the context's setter (which judges the value against
+// the other intake settings); restage: planes handed over early under the other setting are not this setting's frame.  The caller
+// records the value behind it.
+template <class Set> int intake_setter(vp8drv *d, bool args_ok, bool restage, Set set) {
+    if (!d || !args_ok) return VP8HIP_ERR_ARG;
+    DRV_CHK(ask(d, vp8::INTAKE_SETTER));
+    DRV_CHK(set());
+    if (restage) drop_staged(d);
+    return VP8HIP_OK;
+}
 
 int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     const int P = d->cfg.num_partitions;
     const size_t n = (size_t)d->mbs;
-    if (!d->cfg.host_bitstream) {   // the whole entropy stage on the device, one read-back
-        const vp8hip_header_params hp = header_params(d);
-        return vp8hip_encode_frame(d->hip, P, &hp, out, capacity, size);
-    }
+    const vp8hip_header_params hp = header_params(d);
+    if (!d->cfg.host_bitstream) return vp8hip_encode_frame(d->hip, P, &hp, out, capacity, size);      // the whole entropy stage on the device, one read-back
     uint32_t probs[VP8BS_NUM_COEFF_PROBS], denom[VP8BS_NUM_COEFF_PROBS];
     d->nz.resize(n);
     DRV_CHK(vp8hip_prepare_filter_mask(d->hip, d->nz.data()));                   // counts of the final coefficients (vp8enc.cpp:472)
@@ -444,10 +504,10 @@ int get_frame(vp8drv *d, uint8_t *out, size_t capacity, size_t *size) {
     f.height = d->cfg.display_height > 0 ? d->cfg.display_height : d->H;
     f.mb_width = d->W / 16;
     f.mb_height = d->H / 16;
-    f.is_key = d->last_key;
-    f.is_golden = layer_is_golden(d);           // current_is_golden_frame = current_is_key_frame (vp8enc.cpp:369), or a temporal layer's refresh
-    f.is_altref = d->last_hidden ? VP8HIP_ALTREF_HIDDEN : d->last_altref;
-    f.loop_filter_type = d->cfg.loop_filter_type;    // 0 in the reference (init.h:1583)
+    f.is_key = hp.is_key;
+    f.is_golden = hp.is_golden;
+    f.is_altref = hp.is_altref;
+    f.loop_filter_type = hp.loop_filter_type;
     f.loop_filter_sharpness = sharp;
     f.partitions_log2 = P == 8 ? 3 : (P == 4 ? 2 : (P == 2 ? 1 : 0));
     f.skip_prob = vp8host_skip_prob(d->nz.data(), d->mbs);
@@ -477,7 +537,7 @@ extern "C" {
 
 int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const void *v, int force_key) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
-    if (d->canvas) return VP8HIP_ERR_STATE;      // (frames come in through vp8drv_encode_frame_tiles_*)
+    if (d->s.canvas) return VP8HIP_ERR_STATE;      // (frames come in through vp8drv_encode_frame_tiles_*)
     if (layers_refused(d)) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }                        // the previous frame's check_SSIM verdict, if still open
     vp8host_gop_next(&d->gop);
@@ -488,7 +548,7 @@ int vp8drv_encode_frame_device(vp8drv *d, const void *y, const void *u, const vo
 
 int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v, int force_key) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
-    if (d->canvas || layers_refused(d)) return VP8HIP_ERR_STATE;
+    if (d->s.canvas || layers_refused(d)) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     vp8host_gop_next(&d->gop);
     const bool staged = d->staged == y;
@@ -509,9 +569,9 @@ int vp8drv_encode_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, cons
 // vp8drv_encode_frame_host that names them has returned.
 int vp8drv_stage_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
-    if (d->canvas) return VP8HIP_ERR_STATE;
+    if (d->s.canvas) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
-    if (d->denoise || d->analysis || d->deinterlace) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
+    if (d->s.denoise || d->s.analysis || d->s.deinterlace) {      // the schedule's word on this frame, one call early: the verdict is in, so vp8host_gop_next will say the same
         vp8host_gop g = d->gop;
         vp8host_gop_next(&g);
         DRV_CHK(intake_restarts(d, g.current_is_key != 0));
@@ -528,26 +588,24 @@ int vp8drv_stage_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const
 
 int vp8drv_prefetch_frame_host(vp8drv *d, const uint8_t *y, const uint8_t *u, const uint8_t *v) {
     if (!d || !y || !u || !v) return VP8HIP_ERR_ARG;
-    if (d->canvas) return VP8HIP_ERR_STATE;
+    if (d->s.canvas) return VP8HIP_ERR_STATE;
     return vp8hip_prefetch_current(d->hip, y, u, v);
 }
 
 // vp8drv_set_canvas: frames composed of scaled video tiles from now on (n = 0: one source per frame again)
 int vp8drv_set_canvas(vp8drv *d, const vp8hip_tile *tiles, int n, int bg_y, int bg_u, int bg_v) {
-    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (n && (d->in_batch || d->arf)) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
+    if (!d) return VP8HIP_ERR_ARG;
+    DRV_CHK(ask(d, vp8::CANVAS, n != 0));
     DRV_CHK(vp8hip_set_canvas(d->hip, tiles, n, bg_y, bg_u, bg_v));
-    d->canvas = n;
-    d->staged = nullptr;
-    d->staged_scan = false;
+    d->s.canvas = n;
+    drop_staged(d);
     return VP8HIP_OK;
 }
 
 static int encode_frame_tiles(vp8drv *d, const vp8hip_tile_planes *src, int force_key, bool host) {
     if (!d || !src) return VP8HIP_ERR_ARG;
-    if (!d->canvas) return VP8HIP_ERR_STATE;
-    for (int k = 0; k < d->canvas; ++k)      // (what the context would refuse, before the schedule moves)
+    if (!d->s.canvas) return VP8HIP_ERR_STATE;
+    for (int k = 0; k < d->s.canvas; ++k)      // (what the context would refuse, before the schedule moves)
         if (src[k].y && (!src[k].u || !src[k].v || src[k].pitch_y < 0 || src[k].pitch_u < 0 || src[k].pitch_v < 0)) return VP8HIP_ERR_ARG;
     if (layers_refused(d)) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
@@ -571,24 +629,16 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
     if (!out || !drv || n < 1 || n > VP8HIP_MAX_BATCH) return VP8HIP_ERR_ARG;
     *out = nullptr;
     vp8hip_ctx *ctx[VP8HIP_MAX_BATCH];
+    vp8::DriverSettings first;
     for (int i = 0; i < n; ++i) {
-        // the batched loop is the device-parameter loop (what bench.py and a file-to-file transcode run); one launch serves all
-        // members, so what travels as ONE kernel argument must agree: quantizer range, check_SSIM on or off, partitions, filter type
-        if (!drv[i] || !drv[i]->cfg.device_params || drv[i]->cfg.overlap_filter || drv[i]->cfg.scene_detect || drv[i]->arf || drv[i]->canvas || drv[i]->rotation_consumed || drv[i]->hidden_altref ||
-            drv[i]->tl_layers > 1 || drv[i]->tl_next > 1 || drv[i]->ir_period)
-            return VP8HIP_ERR_ARG;      // (hidden frames are not batched, nor is a driver whose references a hidden frame still shapes; nor are temporal layers, nor is intra refresh)
-        const vp8drv_config &a = drv[i]->cfg, &z = drv[0]->cfg;
-        if (a.qi_min != z.qi_min || a.qi_max != z.qi_max || a.num_partitions != z.num_partitions || (a.check_ssim != 0) != (z.check_ssim != 0) ||
-            a.loop_filter_type != z.loop_filter_type || a.in_width != z.in_width || a.in_height != z.in_height ||
-            (a.in_width && a.scale_filter != z.scale_filter) || drv[i]->denoise != drv[0]->denoise || drv[i]->format != drv[0]->format || drv[i]->colour != drv[0]->colour ||
-            drv[i]->transfer != drv[0]->transfer || drv[i]->peak != drv[0]->peak || drv[i]->analysis != drv[0]->analysis || drv[i]->deinterlace != drv[0]->deinterlace || drv[i]->field != drv[0]->field)
-            return VP8HIP_ERR_ARG;
-        {   // vp8drv_set_segment_mode: one mode and strength (the maps are the members' own)
-            int m0 = 0, s0 = 0, mi = 0, si = 0;
-            vp8hip_segment_mode(drv[0]->hip, &m0, &s0);
-            vp8hip_segment_mode(drv[i]->hip, &mi, &si);
-            if (mi != m0 || si != s0) return VP8HIP_ERR_ARG;
-        }
+        // Every member's settings are judged here, in front of vp8hip_batch_create: the context repeats part of this, but it judges
+        // "already a member" (ERR_STATE) member by member, before a later member's ERR_ARG
+        if (!drv[i]) return VP8HIP_ERR_ARG;
+        const vp8::DriverSettings s = settings(drv[i]);
+        if (i == 0) first = s;
+        DRV_CHK(refusal(s, vp8::BATCH_MEMBER));
+        const vp8::BatchShared &shared = s, &shared0 = first;
+        if (!(shared == shared0)) return VP8HIP_ERR_ARG;
         ctx[i] = drv[i]->hip;
     }
     vp8drv_batch *b = new (std::nothrow) vp8drv_batch();
@@ -601,7 +651,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
     b->n = n;
     for (int i = 0; i < n; ++i) {
         b->d[i] = drv[i];
-        drv[i]->in_batch = true;
+        drv[i]->s.in_batch = true;
     }
     *out = b;
     return VP8HIP_OK;
@@ -609,7 +659,7 @@ int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n) {
 
 void vp8drv_batch_destroy(vp8drv_batch *b) {
     if (!b) return;
-    for (int i = 0; i < b->n; ++i) b->d[i]->in_batch = false;
+    for (int i = 0; i < b->n; ++i) b->d[i]->s.in_batch = false;
     vp8hip_batch_destroy(b->hb);
     delete b;
 }
@@ -657,18 +707,8 @@ static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *c
         DRV_CHK(vp8hip_batch_loop_filter(b->hb, key));
         for (int i = 0; i < b->n; ++i) {
             if (!key[i]) continue;
-            vp8drv *d = b->d[i];
-            d->scene.last_key_detect = d->gop.frame_number;       // intra_part.h:1093
-            vp8host_gop_key_coded(&d->gop);
-            vp8host_gop_frame_done(&d->gop);
-            d->st.key_frames++;
-            d->st.frame_number = d->gop.frame_number;
-            d->have_frame = true;
-            d->last_key = d->last_altref = true;
-            d->checked = false;
-            d->replaced = 0;
-            d->sharpness = VP8HIP_SHARPNESS_ON_DEVICE;
-            key_layer_record(d);
+            b->d[i]->sharpness = VP8HIP_SHARPNESS_ON_DEVICE;
+            key_frame_final(b->d[i]);
         }
     }
     for (int i = 0; i < b->n; ++i) {
@@ -700,22 +740,12 @@ static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *c
     for (int i = 0; i < b->n; ++i) {
         if (!active[i]) continue;
         vp8drv *d = b->d[i];
-        d->st.last_use_golden = ug[i];
-        d->st.last_use_altref = ua[i];
-        d->st.refs_searched += 1 + ug[i] + ua[i];
-        d->st.last_prev_is_golden = pg[i];
-        d->st.last_prev_is_altref = pa[i];
-        d->st.last_was_altref = d->gop.current_is_altref;
-        d->checked = false;
-        d->replaced = 0;
+        shown_inter_coded(d, ug[i], ua[i], pg[i], pa[i], d->gop.current_is_altref);
         d->ir_forced = d->ir.last_forced = 0;      // (a member has no period; what its last frame on its own forced is not this frame's)
         d->ir.last_q = d->ir_q;
         d->layer = vp8drv_layer_info{0, 0, 0, VP8HOST_REFRESH_LAST, ug[i], 1};
         if (check) d->verdict_pending = true;   // counted when the verdict is in (resolve())
         else inter_frame_done(d);
-        d->have_frame = true;
-        d->last_key = false;
-        d->last_altref = d->st.last_was_altref != 0;
     }
     return VP8HIP_OK;
 }
@@ -746,9 +776,8 @@ int vp8drv_batch_prefetch_frame_host(vp8drv_batch *b, const uint8_t *const *y, c
 static int batch_scan_frame(vp8drv_batch *b, const int *members, const void *const *y, const void *const *u, const void *const *v, bool host) {
     if (!b || !y || !u || !v) return VP8HIP_ERR_ARG;
     for (int i = 0; i < b->n; ++i) {
-        const vp8drv *d = b->d[i];
         if (members && !members[i]) continue;
-        if (d->denoise || d->deinterlace == 2 || d->analysis || d->cfg.quality_stats) return VP8HIP_ERR_STATE;
+        DRV_CHK(refusal(b->d[i]->s, vp8::SCAN));      // (it reads no fact that moves by itself)
     }
     for (int i = 0; i < b->n; ++i) {   // an open check_SSIM verdict needs the member's current frame: taken before the frame is replaced
         if (members && !members[i]) continue;
@@ -799,57 +828,35 @@ int vp8drv_get_quality_summary(vp8drv *d, vp8drv_quality_summary *s) {
 }
 
 int vp8drv_set_denoise(vp8drv *d, int level) {
-    if (!d || level < 0 || level > 3 || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_denoise(d->hip, level));
-    d->denoise = level;
+    DRV_CHK(intake_setter(d, level >= 0 && level <= 3, false, [&] { return vp8hip_set_denoise(d->hip, level); }));
+    d->s.denoise = level;
     return VP8HIP_OK;
 }
 
 int vp8drv_set_deinterlace(vp8drv *d, int mode, int keep) {
-    if (!d || mode < 0 || mode > 2 || (keep != 0 && keep != 1) || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_deinterlace(d->hip, mode, keep));
-    d->deinterlace = mode;
-    d->field = mode ? keep : 0;
+    DRV_CHK(intake_setter(d, mode >= 0 && mode <= 2 && (keep == 0 || keep == 1), false, [&] { return vp8hip_set_deinterlace(d->hip, mode, keep); }));
+    d->s.deinterlace = mode;
+    d->s.field = mode ? keep : 0;
     return VP8HIP_OK;
 }
 
 int vp8drv_set_source_format(vp8drv *d, int format) {
-    if (!d || format < 0 || (format >= VP8HOST_FORMAT_COUNT && format < VP8HOST_FORMAT_PACKED_FIRST) || format >= VP8HOST_FORMAT_PACKED_END ||
-        !d->cfg.device_params)
-        return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_source_format(d->hip, format));
-    d->format = format;
-    d->staged = nullptr;             // planes staged in the other format are not this format's frame
-    d->staged_scan = false;
+    const bool known = (format >= 0 && format < VP8HOST_FORMAT_COUNT) || (format >= VP8HOST_FORMAT_PACKED_FIRST && format < VP8HOST_FORMAT_PACKED_END);
+    DRV_CHK(intake_setter(d, known, true, [&] { return vp8hip_set_source_format(d->hip, format); }));
+    d->s.format = format;
     return VP8HIP_OK;
 }
 
 int vp8drv_set_source_colour(vp8drv *d, int matrix) {
-    if (!d || matrix < 0 || matrix >= VP8HOST_COLOUR_COUNT || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_source_colour(d->hip, matrix));
-    d->colour = matrix;
-    d->staged = nullptr;             // planes staged under the other matrix are not this matrix's frame
-    d->staged_scan = false;
+    DRV_CHK(intake_setter(d, matrix >= 0 && matrix < VP8HOST_COLOUR_COUNT, true, [&] { return vp8hip_set_source_colour(d->hip, matrix); }));
+    d->s.colour = matrix;
     return VP8HIP_OK;
 }
 
 int vp8drv_set_source_transfer(vp8drv *d, int transfer, int peak) {
-    if (!d || transfer < VP8HOST_TRANSFER_SDR || transfer > VP8HOST_TRANSFER_HLG || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_source_transfer(d->hip, transfer, peak));
-    d->transfer = transfer;
-    d->peak = transfer ? peak : 0;
-    d->staged = nullptr;             // planes staged under the other transfer are not this transfer's frame
-    d->staged_scan = false;
+    DRV_CHK(intake_setter(d, transfer >= VP8HOST_TRANSFER_SDR && transfer <= VP8HOST_TRANSFER_HLG, true, [&] { return vp8hip_set_source_transfer(d->hip, transfer, peak); }));
+    d->s.transfer = transfer;
+    d->s.peak = transfer ? peak : 0;
     return VP8HIP_OK;
 }
 
@@ -880,39 +887,25 @@ int vp8drv_clear_overlay(vp8drv *d, int slot) {
 }
 
 int vp8drv_set_source_window(vp8drv *d, const int32_t *pitch, int x, int y) {
-    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_source_window(d->hip, pitch, x, y));
-    d->window = pitch != nullptr;
-    d->staged = nullptr;             // planes staged through another window are not this window's frame
-    d->staged_scan = false;
+    DRV_CHK(intake_setter(d, true, true, [&] { return vp8hip_set_source_window(d->hip, pitch, x, y); }));
+    d->s.window = pitch != nullptr;
     return VP8HIP_OK;
 }
 
 int vp8drv_set_source_orientation(vp8drv *d, int turns, int mirror) {
-    if (!d || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_source_orientation(d->hip, turns, mirror));
-    d->staged = nullptr;             // planes staged under another orientation are not this one's frame
-    d->staged_scan = false;
-    return VP8HIP_OK;
+    return intake_setter(d, true, true, [&] { return vp8hip_set_source_orientation(d->hip, turns, mirror); });
 }
 
 int vp8drv_set_analysis(vp8drv *d, int on) {
-    if (!d || (on != 0 && on != 1) || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    DRV_CHK(vp8hip_set_analysis(d->hip, on));
-    d->analysis = on != 0;
+    DRV_CHK(intake_setter(d, on == 0 || on == 1, false, [&] { return vp8hip_set_analysis(d->hip, on); }));
+    d->s.analysis = on != 0;
     return VP8HIP_OK;
 }
 
 // vp8hip_set_segment_mode for the frame loop: inter frames are coded in the mode from the next frame taken in on, key frames as ever
 int vp8drv_set_segment_mode(vp8drv *d, int mode, int strength) {
     if (!d || mode < 0 || mode > 2 || (mode == 2 && (strength < 1 || strength > 3))) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
+    if (d->s.in_batch) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     return vp8hip_set_segment_mode(d->hip, mode, strength);
 }
@@ -927,7 +920,7 @@ int vp8drv_set_segment_map(vp8drv *d, const uint8_t *host_map) {
 // the record of the frame just made final: its verdict first (a frame coded again as a key frame has the key frame's coding side)
 int vp8drv_get_frame_analysis(vp8drv *d, vp8drv_analysis *a) {
     if (!d || !a) return VP8HIP_ERR_ARG;
-    if (!d->analysis || !d->have_frame) return VP8HIP_ERR_STATE;
+    if (!d->s.analysis || !d->have_frame) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }
     return vp8hip_analysis_result(d->hip, a);
 }
@@ -935,10 +928,10 @@ int vp8drv_get_frame_analysis(vp8drv *d, vp8drv_analysis *a) {
 // the two ladders and qi_min as vp8drv_create makes them, from the next frame coded on (every frame takes its quantizers from them)
 int vp8drv_set_quantizer(vp8drv *d, int qi_min, int qi_max) {
     if (!d || qi_min < 0 || qi_min > 127 || qi_max < 0 || qi_max > 127) return VP8HIP_ERR_ARG;
-    if (d->in_batch) return VP8HIP_ERR_STATE;
+    if (d->s.in_batch) return VP8HIP_ERR_STATE;
     { const int rc = resolve(d); if (rc < 0) return rc; }      // (a frame sent back is coded again with the pair it was coded with)
-    d->cfg.qi_min = qi_min;
-    d->cfg.qi_max = qi_max;
+    d->s.qi_min = qi_min;
+    d->s.qi_max = qi_max;
     vp8host_quantizer_ladders(qi_min, qi_max, d->lastqi, d->altrefqi);
     d->qi_min = qi_min < qi_max ? qi_min : qi_max;
     return VP8HIP_OK;
@@ -946,8 +939,8 @@ int vp8drv_set_quantizer(vp8drv *d, int qi_min, int qi_max) {
 
 int vp8drv_get_quantizer(const vp8drv *d, int32_t *qi_min, int32_t *qi_max) {
     if (!d || !qi_min || !qi_max) return VP8HIP_ERR_ARG;
-    *qi_min = d->cfg.qi_min;
-    *qi_max = d->cfg.qi_max;
+    *qi_min = d->s.qi_min;
+    *qi_max = d->s.qi_max;
     return VP8HIP_OK;
 }
 
@@ -964,12 +957,8 @@ int vp8drv_get_deinterlace_stats(vp8drv *d, vp8hip_deinterlace_stats *s) {
 // ---- hidden alternate reference frames ------------------------------------------------------------------------------------------------
 int vp8drv_set_arf(vp8drv *d, int strength_plus_one) {
     if (!d || strength_plus_one < 0 || strength_plus_one > 7) return VP8HIP_ERR_ARG;
-    if (strength_plus_one && (!d->cfg.device_params || d->cfg.overlap_filter || d->format || d->window || d->deinterlace ||
-                              d->denoise || d->analysis))
-        return VP8HIP_ERR_ARG;
-    if (d->in_batch || (strength_plus_one && (d->canvas || d->tl_layers > 1 || d->tl_next > 1))) return VP8HIP_ERR_STATE;      // (a canvas: the window frames bypass the compose launch; temporal layers never search ALTREF)
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    d->arf = strength_plus_one;
+    DRV_CHK(ask(d, vp8::ARF, strength_plus_one != 0));
+    d->s.arf = strength_plus_one;
     if (!strength_plus_one && d->arf_st.hidden_frames) (void)vp8hip_arf_result(d->hip, d->arf_st.last_weight);
     if (!strength_plus_one) return vp8hip_arf_release(d->hip);      // (the staging buffers only: the current frame and ALTREF are surfaces)
     return VP8HIP_OK;
@@ -991,12 +980,7 @@ static int hidden_frame(vp8drv *d) {
     d->rotation_consumed = true;
     DRV_CHK(vp8hip_loop_filter_hidden(d->hip));
     d->hidden_altref = true;
-    d->have_frame = true;
-    d->last_key = false;
-    d->last_altref = true;
-    d->last_hidden = true;
-    d->checked = false;
-    d->replaced = 0;
+    inter_frame_coded(d, true, true);
     d->arf_st.hidden_frames++;
     d->arf_st.last_use_golden = use_golden;
     d->arf_st.last_use_altref = use_altref;
@@ -1005,23 +989,28 @@ static int hidden_frame(vp8drv *d) {
 
 static int arf_check(vp8drv *d, const void *frames, int n, int centre) {
     if (!d || !frames || n < 1 || n > VP8HOST_ARF_MAX_FRAMES || centre < 0 || centre >= n) return VP8HIP_ERR_ARG;
-    if (d->format || d->window || d->deinterlace || d->denoise || d->analysis || !d->cfg.device_params) return VP8HIP_ERR_ARG;
-    if (vp8hip_overlay_count(d->hip)) return VP8HIP_ERR_ARG;      // (the window frames bypass the intake: a layer would miss them)
-    if (!d->arf || d->in_batch || !d->have_frame || d->staged) return VP8HIP_ERR_STATE;      // (off; batched; no reference yet; a frame handed over early is the current frame)
+    // what refuses hidden frames refuses this one, and so do layers burnt in (the window frames bypass the intake: a layer would miss
+    // them) and the states of the moment: off; no reference yet; a frame handed over early is the current frame.  (The overlapped filter
+    // is the setter's word alone: with it hidden frames are never on, and the answer here is "off".)
+    vp8::DriverSettings s = settings(d);
+    s.overlap_filter = false;
+    const int table = refusal(s, vp8::ARF);
+    if (table == VP8HIP_ERR_ARG || s.overlays) return VP8HIP_ERR_ARG;
+    if (table != VP8HIP_OK || !s.arf || !d->have_frame || d->staged) return VP8HIP_ERR_STATE;
     const int rc = resolve(d);                                                                // the open check_SSIM verdict first
     return rc < 0 ? rc : VP8HIP_OK;
 }
 
 int vp8drv_encode_arf_device(vp8drv *d, const void *const (*frames)[3], int n, int centre) {
     DRV_CHK(arf_check(d, frames, n, centre));
-    DRV_CHK(vp8hip_arf_filter_device(d->hip, frames, n, centre, d->arf - 1));
+    DRV_CHK(vp8hip_arf_filter_device(d->hip, frames, n, centre, d->s.arf - 1));
     d->arf_st.last_frames = n;
     return hidden_frame(d);
 }
 
 int vp8drv_encode_arf_host(vp8drv *d, const uint8_t *const (*frames)[3], int n, int centre) {
     DRV_CHK(arf_check(d, frames, n, centre));
-    DRV_CHK(vp8hip_arf_filter_host(d->hip, frames, n, centre, d->arf - 1));
+    DRV_CHK(vp8hip_arf_filter_host(d->hip, frames, n, centre, d->s.arf - 1));
     d->arf_st.last_frames = n;
     return hidden_frame(d);
 }
@@ -1038,11 +1027,9 @@ int vp8drv_get_arf_stats(vp8drv *d, vp8drv_arf_stats *s) {
 // ---- temporal layers --------------------------------------------------------------------------------------------------------------------
 int vp8drv_set_temporal_layers(vp8drv *d, int layers, int flags) {
     if (!d || layers < 1 || layers > 3 || (flags & ~VP8DRV_TL_KEEP_RECON)) return VP8HIP_ERR_ARG;
-    if (layers > 1 && (!d->cfg.device_params || d->cfg.overlap_filter || d->cfg.altref_range <= d->cfg.gop_size)) return VP8HIP_ERR_ARG;
-    if (layers > 1 && (d->in_batch || d->arf || vp8hip_shard_world(d->hip) > 0)) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    d->tl_next = layers;
-    d->tl_flags = layers > 1 ? flags : 0;
+    DRV_CHK(ask(d, vp8::LAYERS, layers > 1));
+    d->s.tl_next = layers;
+    d->s.tl_flags = layers > 1 ? flags : 0;
     return VP8HIP_OK;
 }
 
@@ -1057,10 +1044,8 @@ int vp8drv_get_frame_layer(vp8drv *d, vp8drv_layer_info *info) {
 // ---- cyclic intra refresh ---------------------------------------------------------------------------------------------------------------
 int vp8drv_set_intra_refresh(vp8drv *d, int period) {
     if (!d || (period != 0 && (period < VP8HOST_INTRA_REFRESH_MIN || period > VP8HOST_INTRA_REFRESH_MAX))) return VP8HIP_ERR_ARG;
-    if (period && (!d->cfg.device_params || d->cfg.ssim_target > -1.0f)) return VP8HIP_ERR_ARG;
-    if (period && (d->in_batch || vp8hip_shard_world(d->hip) > 0)) return VP8HIP_ERR_STATE;
-    { const int rc = resolve(d); if (rc < 0) return rc; }
-    d->ir_period = d->ir.period = period;
+    DRV_CHK(ask(d, vp8::INTRA_REFRESH, period != 0));
+    d->s.ir_period = d->ir.period = period;
     return VP8HIP_OK;
 }
 
