@@ -526,7 +526,7 @@ int vp8hip_analysis_result(vp8hip_ctx *ctx, vp8hip_analysis *a);
  *           take the finer segments, busy ones the coarser.  Once per frame TAKEN IN, never per coding attempt.  A frame taken in
  *           before mode 2 was set has no map and is coded in segment 3.
  * In mode 1 or 2 vp8hip_inter_transform, vp8hip_inter_finish and vp8hip_batch_inter_transform launch the mapped form of the
- * macroblock kernel (k_mb_p_map; VP8HIP_MB_PACKED=0 has none, the packed one is launched): each macroblock runs ONE transform pass,
+ * macroblock kernel (k_mb_p_map): each macroblock runs ONE transform pass,
  * in segment map[mb] & 3, and MB_segment_id is that value; MB_SSIM is still computed.  Key frames stay as they are: segment 0, no
  * segmentation in the header.  Everything behind the transform (loop filters, entropy stage, analysis record) reads MB_segment_id.
  * VP8HIP_ERR_ARG and nothing has changed: mode outside 0..2, strength outside 1..3 in mode 2.  VP8HIP_ERR_STATE and nothing has

@@ -2,13 +2,15 @@
 """Compare the instruction streams of kernels in two gfx950 assembly files (hipcc -S --cuda-device-only).
 
     scripts/asm_kernel_diff.py before.s after.s k_loop_filter3_b [k_other ...]
+    scripts/asm_kernel_diff.py before.s after.s k_search2ILb1ELi1E=k_search2E   # a kernel whose symbol changed: before=after
     scripts/asm_kernel_diff.py --all before.s after.s            # every kernel of both files, by its full symbol
     scripts/asm_kernel_diff.py --loop one.s k_loop_filter3_b      # static size of the kernel's largest loop
 
 A kernel is named by a fragment of its symbol that must match exactly one kernel of each file (--all needs no names: it pairs
 the kernels by their mangled symbols, template instantiations included, and fails if the two files' sets differ).  Its stream is what lies
 between its entry label and its s_endpgm-terminated end, without comments, directives and blank lines; labels and mangled
-symbols are renamed in order of first appearance, so streams that differ only in names compare equal.  Prints one line per
+symbols are renamed in order of first appearance, so streams that differ only in names compare equal.  A kernel named by fragments
+is held to its kernel descriptor as well (the .amdhsa_ directives: registers, LDS, scratch and the rest).  Prints one line per
 kernel (instruction counts, identical or not) and a unified diff of the streams that differ; exit status 1 if any does."""
 import difflib
 import re
@@ -35,6 +37,17 @@ def streams(path):
             lines.append(re.sub(r"\.LBB\d+_\d+|_Z\w+", rename, " ".join(ln.split())))
         out[k] = lines
     return out
+
+
+def descriptors(path):
+    """{kernel symbol: [its .amdhsa_ directives]}"""
+    return {m.group(1): m.group(2).split("\n") for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S+)\n(.*?)^\s*\.end_amdhsa_kernel", open(path).read(), re.M | re.S)}
+
+
+def figures(desc):
+    """VGPRs, SGPRs, LDS and scratch bytes of a descriptor, for the report"""
+    d = dict(ln.split()[:2] for ln in desc if ln.strip())
+    return "vgpr %s sgpr %s lds %s scratch %s" % tuple(d[".amdhsa_" + k] for k in ("next_free_vgpr", "next_free_sgpr", "group_segment_fixed_size", "private_segment_fixed_size"))
 
 
 def pick(ks, frag):
@@ -88,10 +101,15 @@ def main(argv):
             print("%s: largest loop %d instructions (of %d)" % (k, len(instructions(s[k][a:b + 1])), len(instructions(s[k]))))
         return 0
     before, after = streams(argv[0]), streams(argv[1])
+    dbefore, dafter = descriptors(argv[0]), descriptors(argv[1])
     differ = 0
     for frag in argv[2:]:
-        kb, ka = pick(before, frag), pick(after, frag)
+        fb, fa = frag.split("=") if "=" in frag else (frag, frag)
+        kb, ka = pick(before, fb), pick(after, fa)
         differ |= report(frag, before[kb], after[ka])
+        same = dbefore[kb] == dafter[ka]
+        print("    %s -> %s  descriptor %s" % (figures(dbefore[kb]), figures(dafter[ka]), "identical" if same else "DIFFERENT"))
+        differ |= not same
     return differ
 
 

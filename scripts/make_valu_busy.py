@@ -34,8 +34,8 @@ def main():
     mfma = table(os.path.join(g, f"{a.tag}_pmc_mfma", "mfma_counter_collection.csv"))
     model = json.load(open(os.path.join(ROOT, "profiles", "pmc_valu.json")))[a.geometry]
     chunks = 6
-    want = {"k_search2_b": ("search2", 3, "frame and reference"), "k_search1_b<false>": ("search1_l0", 3, "frame and reference (level 0)"),
-            "k_mb_b": ("mb", 1, "frame"), "k_loop_filter3_b": ("loop_filter", 1, "frame"), "k_strength_segments_b": ("lf_strength", 1, "frame"),
+    want = {"k_search2_b": ("search2", 3, "frame and reference"), "k_search1_plr_b": ("search1_l0", 3, "frame and reference (level 0)"),
+            "k_mb_p": ("mb", 1, "frame"), "k_loop_filter3_b": ("loop_filter", 1, "frame"), "k_strength_segments_b": ("lf_strength", 1, "frame"),
             "k_pack_b": ("pack", 1, "frame")}
     out = {}
     for short, (key, refs, unit) in want.items():
@@ -65,13 +65,13 @@ def main():
                 e["mfma_busy_cycles_per_launch"] = int(sum(mf["SQ_VALU_MFMA_BUSY_CYCLES"]) / len(mf["SQ_VALU_MFMA_BUSY_CYCLES"]))
         out[short] = e
     # the frame at 2.8 references, by counters and by the model
-    if all(k in out for k in ("k_search2_b", "k_search1_b<false>", "k_mb_b")):
+    if all(k in out for k in ("k_search2_b", "k_search1_plr_b", "k_mb_p")):
         refs = 2.8
         s1_other = sum(model[f"search1_l{l}"]["cycles_per_ref"] for l in (1, 2, 3, 4))
         fixed_model = sum(model[k]["cycles_fixed"] for k in ("mb", "loop_filter", "lf_strength", "pack", "downsample") if k in model)
         by_model = refs * (model["search2"]["cycles_per_ref"] + model["search1_l0"]["cycles_per_ref"] + s1_other) + fixed_model
-        by_counters = refs * (out["k_search2_b"]["per_unit_by_counters"] + out["k_search1_b<false>"]["per_unit_by_counters"] + s1_other) + \
-            sum(out[k]["per_unit_by_counters"] for k in ("k_mb_b", "k_loop_filter3_b", "k_strength_segments_b", "k_pack_b") if k in out) + model["downsample"]["cycles_fixed"]
+        by_counters = refs * (out["k_search2_b"]["per_unit_by_counters"] + out["k_search1_plr_b"]["per_unit_by_counters"] + s1_other) + \
+            sum(out[k]["per_unit_by_counters"] for k in ("k_mb_p", "k_loop_filter3_b", "k_strength_segments_b", "k_pack_b") if k in out) + model["downsample"]["cycles_fixed"]
         frame = {"refs_per_frame": refs, "valu_active_simd_cycles_by_counters": int(by_counters), "issue_cycles_by_the_model": int(by_model),
                  "counters_over_model": round(by_counters / by_model, 3),
                  "note": "search1 levels 1-4, the pyramid and the border taken from the model in both sums (small; their largest-grid launches are not separable by grid size in this pass)"}

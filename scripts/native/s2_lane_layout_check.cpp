@@ -164,13 +164,7 @@ int main() {
             const int want = q >= 0 && q < 26 ? 1 : q >= 29 && q < 32 ? 26 : 0;
             if (n != want) { ++once_bad; if (q >= 18 && q < 26) ++owner_bad; }
         }
-    for (int t = 0; t < S2_THREADS; ++t) {
-        HT.touch(t, s2_cost_q3_read(t), 4, false, s2_slot(t), S2_Q3_WORD * 4, (S2_Q3_WORD + 32) * 4);
-        for (int bb = 0; bb < 4; ++bb) {
-            V.touch(t, s2_cost_src_plain(t) + bb * V_ROW * 4, 16, false, s2_slot(t), 0, S2_V_SLOT_BYTES);
-            PRE.touch(t, s2_cost_pre_plain(t) + 64 * bb, 64, false, s2_slot(t), 0, 64 * 4);
-        }    // the form without the spread
-    }
+    for (int t = 0; t < S2_THREADS; ++t) HT.touch(t, s2_cost_q3_read(t), 4, false, s2_slot(t), S2_Q3_WORD * 4, (S2_Q3_WORD + 32) * 4);
     if (!((S2_Q3_WORD + 32) * 4 <= S2_HT_SLOT_BYTES)) ++overlap_bad;
 
     std::printf("fields_bad %ld\nrange_bad %ld\nalign_bad %ld\nowner_bad %ld\noverlap_bad %ld\nonce_bad %ld\n", fields_bad, range_bad, align_bad, owner_bad, overlap_bad, once_bad);

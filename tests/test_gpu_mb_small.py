@@ -7,17 +7,7 @@ reconstruction before and after the loop filter.  A workgroup takes eight macrob
 The content (mixed, below) is made so that the frame holds split and unsplit macroblocks and winners in all three references (asserted on
 the oracle's own results over the three sizes); it runs at quantiser indices 0 and 127 and under ONE SSIM target on a ladder of indices, at
 which macroblocks leave the segment loop after one, two and four passes (asserted likewise).  flat_up / flat_down of quantiser_cases.py at
-index 0 take the second-order DC to +2040 and -2040, the largest numerator the signed division meets.  The default process runs k_mb_p;
-VP8HIP_MB_PACKED is read once per process, so k_mb_b runs the same function in a child process.  Run with `pytest -m gpu`."""
-import json
-import os
-import subprocess
-import sys
-
-if __name__ == "__main__":      # the child process: no conftest.py has set the path
-    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [_root, os.path.join(_root, "tests")]
-
+index 0 take the second-order DC to +2040 and -2040, the largest numerator the signed division meets.  Run with `pytest -m gpu`."""
 import numpy as np
 import pytest
 
@@ -144,20 +134,3 @@ def test_k_mb_p_on_frames_of_one_six_and_nine_macroblocks(W, H):
 def test_k_mb_p_with_the_second_order_dc_at_both_bounds():
     bad = second_order_differences()
     assert not bad, bad
-
-
-def test_k_mb_b_in_a_child_process():
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, VP8HIP_MB_PACKED="0"), capture_output=True, text=True,
-                       timeout=120)
-    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
-    d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"packed"')][0])
-    assert d["packed"] == "0" and d["frames"] == 3 * len(SIZES) + 2
-    assert d["differences"] == [], d
-
-
-if __name__ == "__main__":
-    bad = []
-    for W, H in SIZES:
-        bad += differences(W, H)
-    bad += second_order_differences()
-    print(json.dumps({"packed": os.environ.get("VP8HIP_MB_PACKED"), "frames": 3 * len(SIZES) + 2, "differences": bad[:20]}))

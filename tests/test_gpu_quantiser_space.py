@@ -1,4 +1,4 @@
-"""The four macroblock kernels (k_mb_p, k_mb_p_conformant, k_mb_b, k_mb_b_conformant: kernels_mb.hip) against the CPU oracle over the whole
+"""The two macroblock kernels (k_mb_p, k_mb_p_conformant: kernels_mb.hip) against the CPU oracle over the whole
 quantiser space, on content that takes their narrow arithmetic to the bounds its comments state (tests/quantiser_cases.py; what the cases
 reach is asserted on the CPU in test_quantiser_space_cpu.py): tdiv's reciprocal multiply with numerators up to 16320 and every quantiser
 the tables and the index deltas can produce, the transform's rotations on packed 16-bit halves with residuals of +-255 everywhere, the
@@ -6,19 +6,9 @@ the tables and the index deltas can produce, the transform's rotations on packed
 the four-pass segment loop leaving at every pass.
 
 One context per content (and SSIM target): between cases only the segment data changes, and LAST is uploaded again because the loop
-filter overwrote it.  Everything the frame leaves is compared bit for bit, MB_SSIM by its bit pattern.  The default process runs the
-packed kernels; VP8HIP_MB_PACKED is read once per process, so the 32-lanes-per-macroblock kernels run the same function in a child
-process.  The conformant kernels differ only in the predictor: they run on the inverse contents, where the last three filtered lines
-leave 0..255.  Run with `pytest -m gpu`."""
+filter overwrote it.  Everything the frame leaves is compared bit for bit, MB_SSIM by its bit pattern.  The conformant kernel differs
+only in the predictor: it runs on the inverse contents, where the last three filtered lines leave 0..255.  Run with `pytest -m gpu`."""
 import ctypes as C
-import json
-import os
-import subprocess
-import sys
-
-if __name__ == "__main__":      # the child process: no conftest.py has set the path
-    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [_root, os.path.join(_root, "tests")]
 
 import numpy as np
 import pytest
@@ -108,52 +98,11 @@ def test_ladders_and_targets(name):
     assert not bad, f"{len(bad)} of {len(cases)} cases differ: {bad[:3]}"
 
 
-def _subset(name=""):
-    """every eighth index, the delta sets and the ladders; on the three-reference contents, where the oracle's frame costs three
-    searches, one delta set per clamp index in rotation (the packed kernels run all of them there, in process)"""
-    deltas = qc.delta_sets()
-    if name.endswith("_3refs"):
-        deltas = [c for j, c in enumerate(deltas) if j % 4 == (j // 4) % 4]
-    return qc.index_sweep(8) + deltas + qc.ladders()
-
-
 @pytest.mark.parametrize("name", qc.INVERSE_CONTENTS)
 def test_conformant_predictor(name):
     cases = qc.index_sweep(8) + qc.delta_sets() + qc.ladders()
     bad = differences(name, cases, conformant=True)
     assert not bad, f"{len(bad)} of {len(cases)} cases differ: {bad[:3]}"
-
-
-# ---- k_mb_b and k_mb_b_conformant: the same function in a process that reads VP8HIP_MB_PACKED=0 -------------------------------------
-CHILD_GROUPS = {      # (two contents to a process: a test stays at a few seconds)
-    "flat": (["flat_up", "flat_down"], False),
-    "second_order": (["hadamard", "flat_pixels"], False),
-    "inverse": (["pixels_inv", "squares_inv"], False),
-    "mid": (["ramp128", "squares128", "one_mb"], False),
-    "3refs": (["pixels_inv_3refs", "squares_inv_3refs"], False),
-    "conformant": (["pixels_inv", "squares_inv"], True),
-    "conformant_3refs": (["pixels_inv_3refs", "squares_inv_3refs"], True),
-}
-
-
-def _child(group):
-    names, conformant = CHILD_GROUPS[group]
-    bad, n = [], 0
-    for name in names:
-        cases = _subset(name)
-        n += len(cases)
-        bad += differences(name, cases, conformant)
-    print(json.dumps({"packed": os.environ.get("VP8HIP_MB_PACKED"), "cases": n, "differences": bad[:20], "differing": len(bad)}))
-
-
-@pytest.mark.parametrize("group", list(CHILD_GROUPS))
-def test_the_unpacked_kernels_in_a_child_process(group):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), group], env=dict(os.environ, VP8HIP_MB_PACKED="0"),
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
-    d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"packed"')][0])
-    assert d["packed"] == "0" and d["cases"] == sum(len(_subset(n)) for n in CHILD_GROUPS[group][0])
-    assert d["differences"] == [] and d["differing"] == 0, d
 
 
 # ---- a batched launch: segment data is a per-member pointer ------------------------------------------------------------------------
@@ -229,6 +178,3 @@ def test_entropy_stage_on_these_frames(name, q):
         check_counts(hip, exp, nz, P, f"{name} q{q} P{P}", parts=parts)
     hip.close()
 
-
-if __name__ == "__main__":
-    _child(sys.argv[1])

@@ -1,15 +1,14 @@
 """The whole-pel search's loop form keeps the current blocks' share of the metric in LDS, a block slot S1_PRE_SLOT = 68 ints apart from the
 next (csrc/s1_pre_layout.h: the skew that takes the bank conflicts out of the C reads).  The slot is addressed in two places -- where
-s1_make_pre stores it (lane = (slot, sub-block)) and where the cost loop reads it (lane = (slot, dy)) -- and in three kernels: k_search1_pl
-(one video), k_search1_plr_b (a batch, every reference in one workgroup) and k_search1_pl_b (a batch with VP8HIP_S1_REF_LOOP=0).  Shapes
-that put the indexing at its edges, each searched all three ways; the level-1 and level-0 nets and the quarter-pel costs that follow from
+s1_make_pre stores it (lane = (slot, sub-block)) and where the cost loop reads it (lane = (slot, dy)) -- and in two kernels: k_search1_pl
+(one video) and k_search1_plr_b (a batch, every reference in one workgroup).  Shapes
+that put the indexing at its edges, each searched both ways; the level-1 and level-0 nets and the quarter-pel costs that follow from
 them must be the CPU oracle's, bit for bit:
     64x48    48 level-0 blocks: exactly one workgroup, every slot of every wave live
     176x144  396 blocks: eight full workgroups and a ninth with one live wave
     208x16   26 blocks: slots 12-15 of s1_make_pre's lane map, dead block slots in the last live wave
-At these sizes a launch picks the short-wave form by itself; VP8HIP_S1_SPLIT=0 forces the loop form on every level.  The switches are
-read once per process, so each of the two settings runs this file in a process of its own, once for all shapes (the cases below read
-what it printed).  Run with `pytest -m gpu`."""
+At these sizes a launch picks the short-wave form by itself; VP8HIP_S1_SPLIT=0 forces the loop form on every level.  The switch is
+read once per process, so this file runs in a process of its own, once for all shapes (the cases below read what it printed).  Run with `pytest -m gpu`."""
 import ctypes as C
 import functools
 import os
@@ -34,7 +33,6 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(64, 48), (176, 144), (208, 16)]
 BATCH_FLAGS = [(0, 0), (1, 1)]      # (use_golden, use_altref) of the batch's two members: one and three enabled references
-SETTINGS = {"ref_loop": {"VP8HIP_S1_SPLIT": "0"}, "wg_per_ref": {"VP8HIP_S1_SPLIT": "0", "VP8HIP_S1_REF_LOOP": "0"}}
 
 
 def _prepare(be, frames):
@@ -109,18 +107,17 @@ def _line(W, H, way):
 
 
 @functools.lru_cache(maxsize=None)
-def _child(setting):
-    """this file as a program under the setting's switches: its output, once per setting"""
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **SETTINGS[setting]), capture_output=True, text=True, timeout=600)
+def _child():
+    """this file as a program with the loop form forced: its output, once"""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, VP8HIP_S1_SPLIT="0"), capture_output=True, text=True, timeout=600)
     assert r.returncode in (0, 1), r.stdout[-2000:] + r.stderr[-3000:]
     return r.stdout
 
 
 @pytest.mark.parametrize("W,H", SHAPES)
-@pytest.mark.parametrize("setting,way", [("ref_loop", "one video"), ("ref_loop", "batch"), ("wg_per_ref", "batch")],
-                         ids=["k_search1_pl", "k_search1_plr_b", "k_search1_pl_b"])
-def test_the_loop_form_with_skewed_block_slots_leaves_the_oracles_nets(setting, way, W, H):
-    out = _child(setting)
+@pytest.mark.parametrize("way", ["one video", "batch"], ids=["k_search1_pl", "k_search1_plr_b"])
+def test_the_loop_form_with_skewed_block_slots_leaves_the_oracles_nets(way, W, H):
+    out = _child()
     assert _line(W, H, way) + "[]" in out, out[-3000:]
 
 

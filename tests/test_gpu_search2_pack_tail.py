@@ -12,7 +12,6 @@ the upper half of the first one's register) and its result written by the winnin
    extremes among them); content: a panned random texture, a noise frame against its inverse, 0 / 255 stripes of period 2 and 3 along x and y
    (two setups per shape, so that every content meets two reference counts).  The references are plain uploads (GOLDEN and ALTREF rotated in
    from LAST), so the oracle's planes are the uploaded ones; the device's planes are read back and compared first.
-   VP8HIP_S2_SPREAD=0 and VP8HIP_S2_ITER=1 are read once per process: each runs this file as a program in a child process.
 3. What the cases reach, from the oracle alone (no GPU: test_the_cases_reach_what_they_are_here_for):
    - blocks won by the zero candidate while a non-zero whole-pel vector stood, and blocks whose 25 offset candidates ALL lie out of the frame
      (only the zero candidate is left);
@@ -29,18 +28,9 @@ the upper half of the first one's register) and its result written by the winnin
 Run with `pytest -m gpu`."""
 import ctypes as C
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if __name__ == "__main__":
-    for p in (ROOT, os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
 
 from oracle_lib import Oracle
 from pipeline import default_segments
@@ -304,31 +294,9 @@ def _differences(W, H):
     return bad
 
 
-def _line(W, H):
-    return f"{W}x{H}: differences: "
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_the_search_over_written_nets_gives_the_oracles_vectors_and_costs(W, H):
     test_the_cases_reach_what_they_are_here_for(W, H)      # (what is compared reaches what it is here for: asserted first)
     bad = _differences(W, H)
     assert not bad, bad[:20]
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("env", [{"VP8HIP_S2_SPREAD": "0"}, {"VP8HIP_S2_ITER": "1"}], ids=lambda e: "-".join(f"{k[7:]}={v}" for k, v in e.items()))
-def test_the_switchable_forms_give_the_oracles_vectors_and_costs(env):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    for W, H in SHAPES:
-        assert _line(W, H) + "[]" in r.stdout, r.stdout[-3000:]
-
-
-if __name__ == "__main__":
-    found = 0
-    for W, H in SHAPES:
-        bad = _differences(W, H)
-        print(_line(W, H) + str(bad), flush=True)
-        found += len(bad)
-    sys.exit(1 if found else 0)

@@ -1,22 +1,11 @@
 """Quarter-pel search of a batch whose members have one, two and three enabled references: in the batched launch a workgroup takes its
 blocks through every enabled reference of ITS context (k_search2_b, k_search2_bs), so members that differ in the number of references
 run loops of different lengths side by side in one launch.  Every member's quarter-pel vectors and costs (net_out / bdiff through the
-debug taps), its whole-pel vectors and its macroblock results must be the CPU oracle's, bit for bit -- in the default form and in the
-forms behind VP8HIP_S2_SPREAD=0 (lane = candidate through four rounds) and VP8HIP_S2_ITER=1 (one group per workgroup), which go
-through the same reference loop; those switches are read once per process, so each runs this file in a process of its own."""
+debug taps), its whole-pel vectors and its macroblock results must be the CPU oracle's, bit for bit."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if __name__ == "__main__":
-    for p in (ROOT, os.path.join(ROOT, "tests")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
 
 from oracle_lib import Oracle
 from pipeline import default_segments
@@ -92,16 +81,3 @@ def _differences(W, H):
 def test_a_batch_whose_members_differ_in_enabled_references_gives_the_oracles_search_results(W, H):
     bad = _differences(W, H)
     assert not bad, f"members with {[1 + sum(f) for f in FLAGS]} references in one batch differ from the oracle: {bad}"
-
-
-@pytest.mark.parametrize("env", [{"VP8HIP_S2_SPREAD": "0"}, {"VP8HIP_S2_ITER": "1"}], ids=lambda e: "-".join(f"{k[7:]}={v}" for k, v in e.items()))
-def test_the_switchable_forms_of_the_search_give_the_oracles_results_for_members_that_differ_in_references(env):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "320", "192"], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    assert "members compared: 4, differences: []" in r.stdout, r.stdout[-2000:]
-
-
-if __name__ == "__main__":
-    found = _differences(int(sys.argv[1]), int(sys.argv[2]))
-    print(f"members compared: {len(FLAGS)}, differences: {found}")
-    sys.exit(1 if found else 0)

@@ -13,18 +13,18 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vp8oclenc_amd", "csrc")
 HOT = {   # file -> {kernel name fragment: max VGPRs}
-    "kernels_mb.hip": {"k_mb_bE": 128, "k_mb_pE": 128, "k_mb_p_conformant": 128},     # both forms (VP8HIP_MB_PACKED): four waves per SIMD
-    "kernels_s2.hip": {"k_search2ILb": 72, "k_search2_bILb": 72, "k_search2_bsILb": 72},      # seven waves per SIMD ... (both forms of the cost phase: SPREAD and lane = candidate; one group of eight blocks per workgroup or four in a loop)
-    "kernels_me.hip": {"k_search1": 128, "k_search1_bILb0": 64, "k_search1_plE": 64, "k_search1_pl_b": 64, "k_search1_plr_b": 72, "k_search1_coarse": 64, "k_pyramid": 128, "k_pack_b": 64},   # the loop form: eight (a form with 7 % fewer instructions and 75 registers was no faster)
+    "kernels_mb.hip": {"k_mb_pE": 128, "k_mb_p_conformant": 128},     # four waves per SIMD
+    "kernels_s2.hip": {"k_search2E": 72, "k_search2_bE": 72, "k_search2_bsE": 72},      # seven waves per SIMD ... (one video: one group of eight blocks per workgroup; batches: two in a loop)
+    "kernels_me.hip": {"k_search1": 128, "k_search1_plE": 64, "k_search1_plr_b": 72, "k_search1_coarse": 64, "k_pyramid": 128, "k_pack_b": 64},   # the loop form: eight (a form with 7 % fewer instructions and 75 registers was no faster)
     "kernels_lf4.hip": {"k_loop_filter4E": 128, "k_loop_filter4_bE": 128,
                         "k_loop_filter4_conformantE": 128, "k_loop_filter4_b_conformantE": 128},   # (87 each, as the default pair: the saturated hand-over shares its clamps with the stores)
     # the banded body of lf_banded.h under its two filter policies: what the shared body must not lose
     "kernels_lf3.hip": {"k_loop_filter3_bE": 90, "k_loop_filter3_b_conformantE": 90},
     "kernels_lf_simple.hip": {"k_loop_filter_simpleE": 80, "k_loop_filter_simple_bE": 80},
 }
-LDS = {"k_search2ILb": 23296, "k_search2_bILb": 23296, "k_search2_bsILb": 23296,   # ... and seven workgroups per CU (163 840 / 7)
+LDS = {"k_search2E": 23296, "k_search2_bE": 23296, "k_search2_bsE": 23296,   # ... and seven workgroups per CU (163 840 / 7)
        "k_loop_filter3_bE": 47424, "k_loop_filter3_b_conformantE": 47424, "k_loop_filter_simpleE": 47384, "k_loop_filter_simple_bE": 47384}
-MFMA = {"k_search2ILb", "k_search2_bILb", "k_search2_bsILb"}   # an MFMA result must land in VGPRs (no AGPRs)
+MFMA = {"k_search2E", "k_search2_bE", "k_search2_bsE"}   # an MFMA result must land in VGPRs (no AGPRs)
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")

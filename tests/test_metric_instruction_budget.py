@@ -4,7 +4,7 @@ emits (no GPU needed).  Both kernels are bound by vector-instruction issue: the 
 test_search2_instruction_budget.py, whose loop_valu() is used here.
 
                                                                               parent    this build
-    k_search2_b<true, 2>   reference loop                                     475       443
+    k_search2_b   reference loop                                     475       443
                            once per group of eight blocks                     53        70     (the producer of the C input: 16 ints per
                                                                                                4x4 block in the new order, half a block per lane)
                            per (group, reference) at three references         492.7     466.3
@@ -36,10 +36,10 @@ def _asm(src, tmp_path):
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")
 def test_the_quarter_pel_search_issues_the_folded_metrics_count(tmp_path):
-    ref_loop, group_loop, mfma = loop_valu(_asm("kernels_s2.hip", tmp_path), "k_search2_bILb1ELi2E")
+    ref_loop, group_loop, mfma = loop_valu(_asm("kernels_s2.hip", tmp_path), "k_search2_bE")
     per_group = group_loop - ref_loop
     per_group_ref = ref_loop + per_group / REFS
-    print(f"k_search2_b<true, 2>: reference loop {ref_loop} (parent 475), once per group {per_group} (parent 53), per (group, reference) at "
+    print(f"k_search2_b: reference loop {ref_loop} (parent 475), once per group {per_group} (parent 53), per (group, reference) at "
           f"{REFS} references {per_group_ref:.1f} (parent 492.7)")
     assert mfma == 8, mfma
     assert ref_loop <= S2_REF_LOOP_MAX, (ref_loop, S2_REF_LOOP_MAX)

@@ -1,7 +1,7 @@
 """What a wave of the batched quarter-pel search issues per (group of eight blocks, reference), counted in the gfx950 code hipcc emits
 (no GPU needed).  The search kernels are bound by vector-instruction issue, so this count is what the kernel costs.
 
-Method: kernels_s2.hip is compiled to assembly with the flags of test_kernel_resources.py.  The basic blocks of k_search2_b<true, 2>
+Method: kernels_s2.hip is compiled to assembly with the flags of test_kernel_resources.py.  The basic blocks of k_search2_b
 (SPREAD, two groups per workgroup: the form batches run) are assigned to loops by the compiler's own annotations (`=>This Loop Header`,
 `Parent Loop`, `in Loop: Header=`), not by their place in the text.  The reference loop is the innermost loop that holds all eight of
 the kernel's matrix instructions (the two passes 4, the metric 3 + the fourth-block round), the group loop the outermost one around it.
@@ -83,7 +83,7 @@ def test_the_batched_search_stays_under_its_vector_instruction_ceiling_per_group
     out = tmp_path / "k.s"
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-x", "hip",
                     "--cuda-device-only", "-S", os.path.join(CSRC, "kernels_s2.hip"), "-o", str(out), "-w"], check=True, timeout=600)
-    ref_loop, group_loop, mfma = loop_valu(out.read_text(), "k_search2_bILb1ELi2E")
+    ref_loop, group_loop, mfma = loop_valu(out.read_text(), "k_search2_bE")
     assert mfma == 8, f"{mfma} matrix instructions in the kernel (the two passes 4, the metric 3 + the fourth-block round)"
     assert group_loop > ref_loop, "no reference loop inside the group loop"
     per_group_ref = ref_loop + (group_loop - ref_loop) / REFS

@@ -3,7 +3,7 @@
 winning lane (kernels_s2.hip), counted in the gfx950 code hipcc emits (no GPU needed).  Recipe and counting rule:
 test_search2_instruction_budget.py, whose loop_valu() is used here -- every `v_*` of a loop's blocks except the MFMAs, counted statically.
 
-    k_search2_b<true, 2> and k_search2_bs<true, 2>      parent    round_pack4 alone    this build
+    k_search2_b and k_search2_bs      parent    round_pack4 alone    this build
     reference loop                                      443       427                  411
       of which v_perm_b32                               92        76                   76
     once per group of eight blocks                      70        70                   69
@@ -28,7 +28,7 @@ REF_LOOP_MAX = 413
 PERM_MAX = 76
 PER_GROUP_MAX = 80
 VGPR_MAX = 72
-KERNELS = ["k_search2_bILb1ELi2E", "k_search2_bsILb1ELi2E"]
+KERNELS = ["k_search2_bE", "k_search2_bsE"]
 
 
 def loop_counts(asm_text, kernel_fragment):

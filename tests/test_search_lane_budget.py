@@ -5,7 +5,7 @@ test_search2_instruction_budget.py (loop_valu) and test_search2_pack_tail_budget
 
 The PARENT commit's code objects, counted with the same functions:
 
-    k_search2_b<true, 2>, k_search2_bs<true, 2>     parent    this build
+    k_search2_b, k_search2_bs     parent    this build
     reference loop                                  411       371
     once per group of eight blocks                  69        75
     VGPRs                                           72        69
@@ -33,12 +33,12 @@ from test_search2_pack_tail_budget import loop_counts, resources
 # loop_counts / loop_valu / resources on the parent commit's kernels_s2.hip and kernels_me.hip
 PARENT_S2_REF_LOOP = 411
 PARENT_S2_VGPRS = 72
-PARENT_S2_LDS = {"k_search2_bILb1ELi2E": 22144, "k_search2_bsILb1ELi2E": 22180}
+PARENT_S2_LDS = {"k_search2_bE": 22144, "k_search2_bsE": 22180}
 PARENT_S1_SUB_LOOP = 351
 PARENT_S1_REF_LOOP = 501
 PARENT_S1_VGPRS = 68
 PARENT_S1_LDS = 15952
-S2_KERNELS = ["k_search2_bILb1ELi2E", "k_search2_bsILb1ELi2E"]
+S2_KERNELS = ["k_search2_bE", "k_search2_bsE"]
 S2_FORBIDDEN = ("v_mad_i64_i32", "v_lshl_add_u64", "v_mul_lo_u32", "v_mov_b64")
 
 

@@ -6,8 +6,8 @@
 // and prepare_filter_mask (loop_filter.h:25-46).  Every step is local to a macroblock (the SSIM
 // that gates the next segment pass is the macroblock's own), so the whole segment loop runs inside
 // the kernel with predictor, residual and coefficients in registers: the predictor/residual planes
-// of the reference never exist in HBM.  Mapping: 32 lanes per macroblock, lane b < 24 owns 4x4
-// block b (0-15 Y raster, 16-19 U, 20-23 V) -- the block index of macroblock_coeffs_t.
+// of the reference never exist in HBM.  Mapping: every lane of a workgroup owns a 4x4 block of one of
+// its eight macroblocks (mb_body_packed below).
 #include <stdlib.h>
 #include <string.h>
 
@@ -202,8 +202,8 @@ __device__ __forceinline__ void idct4x4(int L[16]) {
     }
 }
 
-// WHT_and_quant + dequant_and_iWHT, GPU_kernels.cl:257-401, spread over the sixteen luma lanes of the macroblock: lane
-// L = 4r + c holds element (r, c) of the 4x4 block of luma DCs.  Both transforms are two passes of the same four-point
+// WHT_and_quant + dequant_and_iWHT, GPU_kernels.cl:257-401 (wht_roundtrip_row below), spread over the sixteen luma lanes of the
+// macroblock: lane L = 4r + c holds element (r, c) of the 4x4 block of luma DCs.  Both transforms are two passes of the same four-point
 // pattern -- out[i] = v0 + s1(i) v1 + s2(i) v2 + s3(i) v3 with the signs of row i of {++++, ++--, +--+, +-+-} -- first down
 // the column, then along the row (forward), first along the row, then down the column (inverse): four gathers of four
 // lanes, three multiply-adds each, ONE division per lane.  (Every lane used to gather all sixteen values and run the whole
@@ -213,26 +213,6 @@ __device__ __forceinline__ int had4(int v0, int v1, int v2, int v3, int i) {
     const int s1 = i >= 2 ? -1 : 1, s2 = (i == 1 || i == 2) ? -1 : 1, s3 = (i & 1) ? -1 : 1;
     return v0 + __mul24(s1, v1) + __mul24(s2, v2) + __mul24(s3, v3);
 }
-// (gathers by ds_bpermute with the eight byte addresses made once: __shfl recomputes its lane arithmetic, four instructions,
-// at each of the sixteen calls)
-__device__ __forceinline__ int wht_roundtrip_lane(int x, int lane, int dc_q, int ac_q, TDiv ddc, TDiv dac, int &q) {
-    const int L = lane & 15, r = L >> 2, c = L & 3;
-    const int base = (int)(threadIdx.x & 32u) * 4;             // byte address (in the wave) of the macroblock's lane 0
-    const int col = base + 4 * c, row = base + 4 * (L & 12);   // ... of lane c (top of this lane's column), of lane 4r (head of its row)
-    auto gather_col = [&](int v, int i) { return had4(__builtin_amdgcn_ds_bpermute(col, v), __builtin_amdgcn_ds_bpermute(col + 16, v),
-                                                      __builtin_amdgcn_ds_bpermute(col + 32, v), __builtin_amdgcn_ds_bpermute(col + 48, v), i); };
-    auto gather_row = [&](int v, int i) { return had4(__builtin_amdgcn_ds_bpermute(row, v), __builtin_amdgcn_ds_bpermute(row + 4, v),
-                                                      __builtin_amdgcn_ds_bpermute(row + 8, v), __builtin_amdgcn_ds_bpermute(row + 12, v), i); };
-    // forward: columns (T[4r + c] from X[c], X[4 + c], X[8 + c], X[12 + c]), then rows
-    int o = gather_row(gather_col(x, r), c);
-    o += (o > 0);
-    o >>= 1;
-    q = tdiv(o, L == 0 ? ddc : dac);
-    const int xq = __mul24(q, L == 0 ? dc_q : ac_q);
-    // inverse: rows, then columns with (. + 3) >> 3
-    return (gather_col(gather_row(xq, c), r) + 3) >> 3;
-}
-
 // zig-zag position of raster coefficient k: coeff[inv_zigzag[k]] = L[k], GPU_kernels.cl:1489
 __device__ __forceinline__ constexpr int inv_zigzag(int k) {
     constexpr int t[16] = {0, 1, 5, 6, 2, 4, 7, 12, 3, 8, 11, 13, 9, 10, 14, 15};
@@ -288,294 +268,25 @@ struct MBArgs {
 // plane base (0 / 256 / 320) + component * n/4 + sequence index, so a chain reads consecutive floats.
 struct MBTile { uint8_t cur[384]; uint8_t rec[384]; float fa[384]; float fb[384]; };
 
-// sums of the pixels of a 384-byte tile: Y over the 32 lanes, U in lanes 0-15, V in lanes 16-31 (exact
-// integers, so the means equal the reference's float accumulation, which is exact too: sums < 2^24)
-__device__ __forceinline__ void tile_sums(const uint32_t *t32, int lane, int &sy, int &sc) {
-    sy = (int)__builtin_amdgcn_sad_u8(t32[lane], 0u, __builtin_amdgcn_sad_u8(t32[lane + 32], 0u, 0u));
-    sc = (int)__builtin_amdgcn_sad_u8(t32[64 + lane], 0u, 0u);
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) sy += __shfl_xor(sy, m, 32);
-#pragma unroll
-    for (int m = 8; m >= 1; m >>= 1) sc += __shfl_xor(sc, m, 32);
-}
-// one accumulation chain of n4 terms in the reference's order (first term assigned, then term + acc)
-__device__ __forceinline__ float chain(const float *p, int n4) {
-    float acc = 0.0f;
-    for (int q = 0; q < n4; q += 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(p + q);
-        acc = q == 0 ? v.x : __fadd_rn(v.x, acc);
-        acc = __fadd_rn(v.y, acc);
-        acc = __fadd_rn(v.z, acc);
-        acc = __fadd_rn(v.w, acc);
-    }
-    return acc;
-}
-__device__ __forceinline__ float sum4(float acc, int lane) {   // (((c0 + c1) + c2) + c3) of the four components
-    const float s0 = __shfl(acc, (lane & ~3) + 0, 32), s1 = __shfl(acc, (lane & ~3) + 1, 32);
-    const float s2 = __shfl(acc, (lane & ~3) + 2, 32), s3 = __shfl(acc, (lane & ~3) + 3, 32);
-    return __fadd_rn(__fadd_rn(__fadd_rn(s0, s1), s2), s3);
-}
-
-// SSIM in the reference's float4 order (count_SSIM_luma/_chroma, :1610-2095): lane-component `comp` accumulates
-// pixels (r, 4j+comp), r outer, j inner; n = 16 (luma) or 8 (chroma).  The per-pixel terms (deviation squares and
-// products) are computed by all 32 lanes and parked in LDS in chain order; only the 64- (16-) term accumulation
-// chains, whose order is the result, run on the 12 chain lanes.  All float ops are written so that nothing can
-// be contracted (the reference's mad is a*b+c, unfused).
-// All LDS traffic of a macroblock stays inside its own 32 lanes = half of one wave, so program order is the
-// only synchronisation needed: there is no workgroup barrier in this kernel.
-template <bool CONFORMANT>
-__device__ __forceinline__ void mb_body(const MBArgs &a, MBTile *s_t) {
-    const int g = threadIdx.x >> 5, lane = threadIdx.x & 31;
-    const int mb_raw = xcd_band(blockIdx.x, gridDim.x) * 8 + g;   // an XCD's workgroups on one band of the frame (vp8hip_dev.h)
-    const bool live = mb_raw < a.mbs;
-    const int mb = live ? mb_raw : a.mbs - 1;
-    const int mbx = mb % a.mbw, mby = mb / a.mbw;
-    const int32_t *SD = a.sd->v;
-
-    const bool blk = lane < 24;
-    const int plane = lane < 16 ? 0 : (lane < 20 ? 1 : 2);
-    const int bi = lane < 16 ? lane : (lane - 16) & 3;       // block index inside its plane
-    const int bw = plane == 0 ? 4 : 2;                        // blocks per MB row of the plane
-    const int bx = blk ? bi % bw : 0, by = blk ? bi / bw : 0;
-    const int msz = plane == 0 ? 16 : 8;
-    const int posx = mbx * msz + bx * 4, posy = mby * msz + by * 4;
-    // select_reference (GPU_kernels.cl:1205-1283) + pack_8x8_into_16x16 (:1346-1366), per macroblock:
-    // cheapest of the three references by the sum of its four block costs (ties: LAST over ALTREF, then
-    // that over GOLDEN), its four vectors, 16x16 iff they are equal.  Every lane evaluates it (same
-    // addresses across the 32 lanes: one broadcast load each), lane 0 stores the outputs.
-    const int b8w = a.mbw * 2;
-    const int cell0 = (mby * 2) * b8w + mbx * 2;
-    const int cidx[4] = {cell0, cell0 + 1, cell0 + b8w, cell0 + b8w + 1};
-    int diff1 = a.bdiff0[cidx[0]] + a.bdiff0[cidx[1]] + a.bdiff0[cidx[2]] + a.bdiff0[cidx[3]];
-    int diff2 = 0x7fffffff;
-    if (a.use_altref == 1)
-        diff2 = a.bdiff2[cidx[0]] + a.bdiff2[cidx[1]] + a.bdiff2[cidx[2]] + a.bdiff2[cidx[3]];
-    int ref = diff1 <= diff2 ? 0 : 2;
-    diff1 = diff1 <= diff2 ? diff1 : diff2;
-    diff2 = 0x7fffffff;
-    if (a.use_golden == 1)
-        diff2 = a.bdiff1[cidx[0]] + a.bdiff1[cidx[1]] + a.bdiff1[cidx[2]] + a.bdiff1[cidx[3]];
-    ref = diff1 <= diff2 ? ref : 1;
-    const uint32_t *vnet = reinterpret_cast<const uint32_t *>(ref == 0 ? a.vnet0 : (ref == 1 ? a.vnet1 : a.vnet2));
-    uint32_t mbv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) mbv[k] = vnet[cidx[k]];
-    const int parts = (mbv[1] == mbv[0] && mbv[2] == mbv[0] && mbv[3] == mbv[0]) ? 0 : 1;
-    if (lane == 0 && live) {
-        a.o_ref[mb] = ref;
-        a.o_parts[mb] = parts;
-        *reinterpret_cast<uint4 *>(a.o_vec + 8 * mb) = make_uint4(mbv[0], mbv[1], mbv[2], mbv[3]);
-    }
-    // (pointer by pointer: selecting one of three argument STRUCTS by a per-lane index sends the argument block to scratch memory)
-    uint8_t *const rpy = ref == 0 ? a.ref0.y : (ref == 1 ? a.ref1.y : a.ref2.y);
-    uint8_t *const rpu = ref == 0 ? a.ref0.u : (ref == 1 ? a.ref1.u : a.ref2.u);
-    uint8_t *const rpv = ref == 0 ? a.ref0.v : (ref == 1 ? a.ref1.v : a.ref2.v);
-    const int pstride = plane == 0 ? a.ystride : a.cstride, pw = plane == 0 ? a.yw : a.cw, ph = plane == 0 ? a.yh : a.ch;
-    // the block's first pixel in its plane, in bytes from pixel (0, 0): below 2^31 for any surface, so the rows of the current frame and of the
-    // reconstruction are a plane pointer plus a 32-bit offset (64-bit row products per access were a multiply each)
-    const uint32_t pix0 = (uint32_t)(posy * pstride + posx);
-    const Plane cp{plane == 0 ? a.cur.y : (plane == 1 ? a.cur.u : a.cur.v), pstride, pw, ph};
-    const Plane rc{plane == 0 ? a.recon.y : (plane == 1 ? a.recon.u : a.recon.v), pstride, pw, ph};
-    const Plane rp{plane == 0 ? rpy : (plane == 1 ? rpu : rpv), pstride, pw, ph};
-    const int tile_off = plane == 0 ? 0 : (plane == 1 ? 256 : 320);
-
-    // The predictor stays packed (four dwords of bytes) and the current block lives in the LDS tile: a pass re-forms the
-    // residual from them, and everything a pass produces (coefficients, block 24, reconstruction) is stored as the pass
-    // produces it -- the last pass to run is the one that counts, GPU_kernels.cl:1391 -- so that none of the 16-entry
-    // arrays stays alive across the float SSIM section (193 VGPRs and two waves per SIMD before; see k_mb below).
-    uint32_t predw[4] = {0, 0, 0, 0};
-    if (blk) {
-        // prepare_predictors_and_residual, :1285-1344: vector of the block's 8x8 quadrant
-        const int quad = plane == 0 ? (by >> 1) * 2 + (bx >> 1) : by * 2 + bx;
-        const uint32_t vv = quad == 0 ? mbv[0] : (quad == 1 ? mbv[1] : (quad == 2 ? mbv[2] : mbv[3]));
-        const int vx = (int16_t)(vv & 0xffffu), vy = (int16_t)(vv >> 16);
-        const int gsh = plane == 0 ? 2 : 3, gm = plane == 0 ? 3 : 7;
-        const int fxp = posx * (gm + 1) + vx, fyp = posy * (gm + 1) + vy;  // >= 0 for every in-frame vector
-        const int dx = (fxp & gm) * (plane == 0 ? 2 : 1), dy = (fyp & gm) * (plane == 0 ? 2 : 1);
-        const int ix = iclamp(fxp >> gsh, 2 - EXT, rp.w + EXT - 7), iy = iclamp(fyp >> gsh, 2 - EXT, rp.h + EXT - 7);
-        predict4x4<CONFORMANT>(rp, ix, iy, dx, dy, predw);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t cw = *reinterpret_cast<const uint32_t *>(cp.p + (size_t)(pix0 + (uint32_t)(r * pstride)));
-            *reinterpret_cast<uint32_t *>(&s_t[g].cur[tile_off + (by * 4 + r) * msz + bx * 4]) = cw;
-        }
-    }
-    // ---- SSIM terms of the current frame: mean (exact in float) and variance chain ---------------
-    // chain lanes 0..11: plane sp = lane>>2, float4 component comp = lane&3
-    const int sp = (lane >> 2) < 3 ? (lane >> 2) : 2, comp = lane & 3;
-    const int n4 = sp == 0 ? 64 : 16;                                       // terms per chain
-    const int chain_off = (sp == 0 ? 0 : (sp == 1 ? 256 : 320)) + comp * n4;
-    const float area = sp == 0 ? 256.0f : 64.0f;
-    // term lanes (all 32): Y dwords `lane` and `lane+32` (sequence index = dword index), chroma dword `lane&15`
-    // of U (lanes 0-15) or V (16-31); byte k of a dword belongs to component k
-    const uint32_t *cur32 = reinterpret_cast<const uint32_t *>(s_t[g].cur);
-    const uint32_t *rec32 = reinterpret_cast<const uint32_t *>(s_t[g].rec);
-    const int coff = (lane < 16 ? 256 : 320) + (lane & 15);
-    float *fa = s_t[g].fa, *fb = s_t[g].fb;
-    float M1y, M1c, M1, D1;
-    {
-        int sy, sc;
-        tile_sums(cur32, lane, sy, sc);
-        M1y = __fdiv_rn((float)sy, 256.0f);
-        M1c = __fdiv_rn((float)sc, 64.0f);
-        const float mu = __shfl(M1c, 0, 32), mv = __shfl(M1c, 16, 32);
-        M1 = sp == 0 ? M1y : (sp == 1 ? mu : mv);
-#pragma unroll
-        for (int h = 0; h < 3; ++h) {
-            const uint32_t w = cur32[h < 2 ? lane + 32 * h : 64 + lane];
-            const float m = h < 2 ? M1y : M1c;
-            const int off = h < 2 ? lane + 32 * h : coff, cs = h < 2 ? 64 : 16;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float t = __fsub_rn((float)byte_of(w, k), m);
-                fa[off + k * cs] = __fmul_rn(t, t);
-            }
-        }
-        D1 = __fdiv_rn(sum4(chain(fa + chain_off, n4), lane), area);
-    }
-
-    float ssim = -2.0f;  // pack_8x8_into_16x16, :1352
-    int seg_final = a.o_seg[mb];
-    int nz_blk = 0;            // this lane's share of prepare_filter_mask's count, from the last pass that ran
-    const uint32_t dc_mask = (plane == 0 && parts == 0) ? 0xffff0000u : 0xffffffffu;   // nz_zigzag
-    bool any_pass = false;
-
-    for (int seg = 3; seg >= 0; --seg) {        // inter_part.h:329
-        // dct4x4 gate, :1391 (same value in all 32 lanes of a macroblock; the two macroblocks of a wave may
-        // leave the loop at different passes)
-        if (ssim > a.ssim_target) break;
-        {
-        any_pass = true;
-        seg_final = seg;
-        const int i = SD[seg * SD_INTS + SD_Y_AC_I];
-        int dc_q, ac_q;
-        if (plane == 0) {                        // :1394-1408
-            ac_q = k_ac_q[i];
-            dc_q = parts == 0 ? 1 : k_dc_q[qi(SD[SD_Y_DC_IDELTA] + i)];
-        } else {
-            dc_q = imin(k_dc_q[qi(SD[SD_UV_DC_IDELTA] + i)], 132);
-            ac_q = k_ac_q[qi(SD[SD_UV_AC_IDELTA] + i)];
-        }
-        int coef[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) coef[k] = 0;
-        if (blk) {
-            int res[16];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const uint32_t cw = *reinterpret_cast<const uint32_t *>(&s_t[g].cur[tile_off + (by * 4 + r) * msz + bx * 4]);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) res[4 * r + c] = byte_of(cw, c) - byte_of(predw[r], c);
-            }
-            fdct4x4(res, coef);
-            const TDiv dac = tdiv_make(ac_q);
-            coef[0] = mb_dc_div(coef[0], dc_q);  // truncating, :1478-1481
-#pragma unroll
-            for (int k = 1; k < 16; ++k) coef[k] = tdiv(coef[k], dac);
-        }
-        nz_blk = 0;
-        if (parts == 0) {                        // wht4x4_iwht4x4, :1498-1543 (every lane takes part in the gathers)
-            const int y2dc = k_dc_q[qi(SD[SD_Y2_DC_IDELTA] + i)] * 2;
-            const int y2ac = imax(31 * k_ac_q[qi(SD[SD_Y2_AC_IDELTA] + i)] / 20, 8);
-            int q24 = 0;
-            const int nd = wht_roundtrip_lane((int16_t)coef[0], lane, y2dc, y2ac, tdiv_make(y2dc), tdiv_make(y2ac), q24);
-            if (lane < 16) {
-                coef[0] = (int16_t)nd;           // stored as short, :1537
-                // block 24, element by element, and its share of the non-zero count (CPU_kernels.cl:800-819)
-                if (live) a.o_coeffs[((size_t)mb * 25 + 24) * 16 + inv_zigzag_rt(lane)] = (int16_t)q24;
-                nz_blk += iabs((int16_t)q24);
-            }
-        }
-        if (blk) {                               // idct4x4, :1545-1608
-            uint32_t zw[8];
-            pack_zigzag(coef, zw);
-            if (live) store_zigzag(a.o_coeffs + ((size_t)mb * 25 + lane) * 16, zw);
-            nz_blk = nz_zigzag(zw, dc_mask, nz_blk);
-            int L[16];
-            L[0] = __mul24((int16_t)coef[0], dc_q);
-#pragma unroll
-            for (int k = 1; k < 16; ++k) L[k] = __mul24(coef[k], ac_q);   // (|quotient| <= 2040: an int16 as it stands)
-            idct4x4(L);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int px[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) px[c] = L[4 * r + c] + byte_of(predw[r], c);
-                const uint32_t w = pack_satu4(px);
-                *reinterpret_cast<uint32_t *>(&s_t[g].rec[tile_off + (by * 4 + r) * msz + bx * 4]) = w;
-                if (live) *reinterpret_cast<uint32_t *>(rc.p + (size_t)(pix0 + (uint32_t)(r * pstride))) = w;
-            }
-        }
-        }
-        {
-        // count_SSIM_*, gather_SSIM
-        float M2, D, C;
-        {
-            int sy, sc;
-            tile_sums(rec32, lane, sy, sc);
-            const float M2y = __fdiv_rn((float)sy, 256.0f), M2c = __fdiv_rn((float)sc, 64.0f);
-            const float mu = __shfl(M2c, 0, 32), mv = __shfl(M2c, 16, 32);
-            M2 = sp == 0 ? M2y : (sp == 1 ? mu : mv);
-#pragma unroll
-            for (int h = 0; h < 3; ++h) {
-                const int di = h < 2 ? lane + 32 * h : 64 + lane;
-                const uint32_t wc = cur32[di], wr = rec32[di];
-                const float m1 = h < 2 ? M1y : M1c, m2 = h < 2 ? M2y : M2c;
-                const int off = h < 2 ? lane + 32 * h : coff, cs = h < 2 ? 64 : 16;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float t1 = __fsub_rn((float)byte_of(wc, k), m1);
-                    const float t2 = __fsub_rn((float)byte_of(wr, k), m2);
-                    fa[off + k * cs] = __fmul_rn(t2, t2);
-                    fb[off + k * cs] = __fmul_rn(t1, t2);
-                }
-            }
-            D = __fadd_rn(D1, __fdiv_rn(sum4(chain(fa + chain_off, n4), lane), area));
-            C = __fdiv_rn(sum4(chain(fb + chain_off, n4), lane), area);
-        }
-        const float k1 = 0.01f * 0.01f * 255 * 255, k2 = 0.03f * 0.03f * 255 * 255;
-        const float num = __fmul_rn(__fadd_rn(__fmul_rn(M1, __fmul_rn(M2, 2.0f)), k1), __fadd_rn(__fmul_rn(C, 2.0f), k2));
-        const float den = __fmul_rn(__fadd_rn(__fmul_rn(M1, M1), __fadd_rn(__fmul_rn(M2, M2), k1)), __fadd_rn(D, k2));
-        float metric = __fdiv_rn(num, den);
-        float dm = __fsub_rn(M1, M2);
-        dm = dm < 0 ? -dm : dm;
-        dm = dm > 4 ? __fmul_rn(0.02f, dm) : 0.0f;
-        metric = __fsub_rn(metric, dm);
-        const float m1 = __shfl(metric, 0, 32), m2 = __shfl(metric, 4, 32), m3 = __shfl(metric, 8, 32);
-        ssim = __fdiv_rn(__fadd_rn(__fadd_rn(m1, m2), m3), 3.0f);
-        }
-    }
-
-    // ---- results -------------------------------------------------------------------------------
-    int nz = any_pass ? nz_blk : 0;
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) nz += __shfl_xor(nz, m, 32);
-    if (lane == 0 && live) {
-        if (any_pass) {
-            a.o_seg[mb] = seg_final;
-            a.o_nz[mb] = nz;
-            a.o_mask[mb] = (parts != 0 || nz > 0) ? -1 : 0;
-        }
-        a.o_ssim[mb] = ssim;
-        if (ssim < a.ssim_target) *a.o_flag = 1;   // (vp8enc.cpp:244: what the fallback acts on; rare, so no store otherwise)
-    }
-}
-
-// ---- the same macroblock loop with every lane of the workgroup on a 4x4 block ---------------------------------------------------
-// The kernel is bound by what its waves ISSUE, and in the form above a wave issues the block phase (prediction, transforms,
-// quantisation, reconstruction: two thirds of its instructions) for 2 x 24 blocks on 64 lanes, and each of its three accumulation
-// chains (16 dependent steps of four additions) for 2 x 12 chains.  Here a workgroup of THREE waves takes eight macroblocks:
+// ---- the macroblock loop with every lane of the workgroup on a 4x4 block --------------------------------------------------------
+// SSIM in the reference's float4 order (count_SSIM_luma/_chroma, :1610-2095): float4 component `comp` accumulates pixels (r, 4j+comp),
+// r outer, j inner; n = 16 (luma) or 8 (chroma).  The per-pixel terms (deviation squares and products) are parked in LDS in chain
+// order; only the 64- (16-) term accumulation chains, whose order is the result, run on the chain lanes.  All float ops are written so
+// that nothing can be contracted (the reference's mad is a*b+c, unfused).
+// The kernel is bound by what its waves ISSUE: the block phase (prediction, transforms, quantisation, reconstruction) is two thirds of
+// a macroblock's instructions, and an accumulation chain is 16 dependent steps of four additions whatever the number of lanes that run
+// one.  A workgroup of THREE waves takes eight macroblocks:
 //   waves 0, 1   the luma blocks of macroblocks 0-3 / 4-7 (16 lanes per macroblock = one DPP row: its sums are row reductions);
 //   wave 2       the chroma blocks of all eight (8 lanes per macroblock: U 0-3, V 0-3);
-// every lane owns a block, so eight macroblocks take three block phases where they took four.  A plane's SSIM terms are made by
+// every lane owns a block, so eight macroblocks take three block phases.  A plane's SSIM terms are made by
 // the lanes of its blocks (the pixels they read are their own wave's), and the chains are dealt over the workgroup by LENGTH:
 // the 2 x 32 luma chains (64 terms: `variance' and `covariance' of 8 macroblocks x 4 components) are wave 0, the 2 x 64 chroma
-// chains (16 terms) waves 1 and 2 -- 24 chain steps of a wave per eight macroblocks where there were 128.  The three planes of a
-// macroblock now live in different waves: they meet in LDS (means, variances, the plane's metric, the chroma blocks' share of the
+// chains (16 terms) waves 1 and 2 -- 24 chain steps of a wave per eight macroblocks.  The three planes of a
+// macroblock live in different waves: they meet in LDS (means, variances, the plane's metric, the chroma blocks' share of the
 // non-zero count) behind two workgroup barriers per pass, and the pass loop ends for the whole workgroup when a pass found no
 // macroblock below the target (a word in LDS the active macroblocks set before the first barrier).  A macroblock that has
 // left the loop is masked out of the block phase; its chains are summed again from the terms its last pass left (the same bits).
-// Same operations on the same values in the same order per macroblock: the outputs are the form above's, bit for bit.
+// (Against 32 lanes per macroblock, 24 of them on a block and 12 on a chain: 7.17 -> 4.68 M wave instructions per frame, +3.0 %, DESIGN.md.)
 struct MBShare {
     float M1[8][4], M2[8][4], D1[8][4], metric[8][4];   // [macroblock slot][plane]
     int nzc[8];                                         // the chroma blocks' share of prepare_filter_mask's count
@@ -609,7 +320,8 @@ __device__ __forceinline__ float chain_n(const float *p) {
     }
     return acc;
 }
-// wht_roundtrip_lane for a macroblock whose sixteen luma lanes are lanes base16 .. base16 + 15 of the wave
+// the round trip for a macroblock whose sixteen luma lanes start at byte address base_bytes of the wave's lanes (gathers by ds_bpermute with
+// the eight byte addresses made once: __shfl recomputes its lane arithmetic, four instructions, at each of the sixteen calls)
 __device__ __forceinline__ int wht_roundtrip_row(int x, int L, int base_bytes, int dc_q, int ac_q, TDiv ddc, TDiv dac, int &q) {
     const int r = L >> 2, c = L & 3;
     const int col = base_bytes + 4 * c, row = base_bytes + 4 * (L & 12);
@@ -647,7 +359,9 @@ __device__ __forceinline__ void mb_body_packed(const Args &a, MBTileP *s_t, MBSh
     const int msz = luma ? 16 : 8;
     const int posx = mbx * msz + bx * 4, posy = mby * msz + by * 4;
     if (threadIdx.x == 0) s_x->any[0] = s_x->any[1] = 0;
-    // select_reference + pack_8x8_into_16x16, as in mb_body: every lane evaluates its macroblock's
+    // select_reference (GPU_kernels.cl:1205-1283) + pack_8x8_into_16x16 (:1346-1366), per macroblock: cheapest of the three references by
+    // the sum of its four block costs (ties: LAST over ALTREF, then that over GOLDEN), its four vectors, 16x16 iff they are equal.  Every
+    // lane evaluates its macroblock's (the same addresses across its lanes: one broadcast load each), the head lane stores the outputs.
     const int b8w = a.mbw * 2;
     const int cell0 = (mby * 2) * b8w + mbx * 2;
     const int cidx[4] = {cell0, cell0 + 1, cell0 + b8w, cell0 + b8w + 1};
@@ -672,24 +386,32 @@ __device__ __forceinline__ void mb_body_packed(const Args &a, MBTileP *s_t, MBSh
         a.o_parts[mb] = parts;
         *reinterpret_cast<uint4 *>(a.o_vec + 8 * mb) = make_uint4(mbv[0], mbv[1], mbv[2], mbv[3]);
     }
+    // (pointer by pointer: selecting one of three argument STRUCTS by a per-lane index sends the argument block to scratch memory)
     uint8_t *const rpy = ref == 0 ? a.ref0.y : (ref == 1 ? a.ref1.y : a.ref2.y);
     uint8_t *const rpu = ref == 0 ? a.ref0.u : (ref == 1 ? a.ref1.u : a.ref2.u);
     uint8_t *const rpv = ref == 0 ? a.ref0.v : (ref == 1 ? a.ref1.v : a.ref2.v);
     const int pstride = luma ? a.ystride : a.cstride, pw = luma ? a.yw : a.cw, ph = luma ? a.yh : a.ch;
-    const uint32_t pix0 = (uint32_t)(posy * pstride + posx);   // as in mb_body
+    // the block's first pixel in its plane, in bytes from pixel (0, 0): below 2^31 for any surface, so the rows of the current frame and of the
+    // reconstruction are a plane pointer plus a 32-bit offset (64-bit row products per access were a multiply each)
+    const uint32_t pix0 = (uint32_t)(posy * pstride + posx);
     const Plane cp{plane == 0 ? a.cur.y : (plane == 1 ? a.cur.u : a.cur.v), pstride, pw, ph};
     const Plane rc{plane == 0 ? a.recon.y : (plane == 1 ? a.recon.u : a.recon.v), pstride, pw, ph};
     const Plane rp{plane == 0 ? rpy : (plane == 1 ? rpu : rpv), pstride, pw, ph};
     const int tile_off = plane == 0 ? 0 : (plane == 1 ? 256 : 320);
     MBTile &T = s_t[g].t;
 
+    // The predictor stays packed (four dwords of bytes) and the current block lives in the LDS tile: a pass re-forms the
+    // residual from them, and everything a pass produces (coefficients, block 24, reconstruction) is stored as the pass
+    // produces it -- the last pass to run is the one that counts, GPU_kernels.cl:1391 -- so that none of the 16-entry
+    // arrays stays alive across the float SSIM section.
     uint32_t predw[4];
     {
+        // prepare_predictors_and_residual, :1285-1344: vector of the block's 8x8 quadrant
         const int quad = luma ? (by >> 1) * 2 + (bx >> 1) : by * 2 + bx;
         const uint32_t vv = quad == 0 ? mbv[0] : (quad == 1 ? mbv[1] : (quad == 2 ? mbv[2] : mbv[3]));
         const int vx = (int16_t)(vv & 0xffffu), vy = (int16_t)(vv >> 16);
         const int gsh = luma ? 2 : 3, gm = luma ? 3 : 7;
-        const int fxp = posx * (gm + 1) + vx, fyp = posy * (gm + 1) + vy;
+        const int fxp = posx * (gm + 1) + vx, fyp = posy * (gm + 1) + vy;  // >= 0 for every in-frame vector
         const int dx = (fxp & gm) * (luma ? 2 : 1), dy = (fyp & gm) * (luma ? 2 : 1);
         const int ix = iclamp(fxp >> gsh, 2 - EXT, rp.w + EXT - 7), iy = iclamp(fyp >> gsh, 2 - EXT, rp.h + EXT - 7);
         predict4x4<CONFORMANT>(rp, ix, iy, dx, dy, predw);
@@ -865,38 +587,27 @@ __device__ __forceinline__ void mb_body_packed(const Args &a, MBTileP *s_t, MBSh
             a.o_mask[mb] = (parts != 0 || nz > 0) ? -1 : 0;
         }
         a.o_ssim[mb] = ssim;
-        if (ssim < a.ssim_target) *a.o_flag = 1;
+        if (ssim < a.ssim_target) *a.o_flag = 1;   // (vp8enc.cpp:244: what the fallback acts on; rare, so no store otherwise)
     }
 }
 
 // One kernel for one context and for a batch (blockIdx.z = member; a single context is a batch of one).  The argument block
 // is read through the kernel-argument pointer: a by-value MBArgs whose members are picked by a per-lane index (the reference
 // of the macroblock) is copied to scratch memory by hipcc (296 B per lane, 21 -> 38 us per 1080p frame when it happened).
-// Register budget: 127 VGPRs = four waves per SIMD, nothing spilled (history: 193 VGPRs and two waves; forcing three or
-// four waves on that body by spilling was slower, 42.8-49.5 against 48.7-49.6 M MB/s).
-__global__ __launch_bounds__(256, 2) void k_mb_b(BatchOf<MBArgs> b) {
-    __shared__ __attribute__((aligned(16))) MBTile s_t[8];
-    mb_body<false>(b.item[blockIdx.z], s_t);
-}
-// the same with the format's predictor instead of the reference's (vp8hip_conformant_stream): its own kernel, so that the
-// reference path stays the code that was measured
-__global__ __launch_bounds__(256, 2) void k_mb_b_conformant(BatchOf<MBArgs> b) {
-    __shared__ __attribute__((aligned(16))) MBTile s_t[8];
-    mb_body<true>(b.item[blockIdx.z], s_t);
-}
-
-// the packed form: 192 threads per eight macroblocks (VP8HIP_MB_PACKED=0: the form above, for same-box A/B runs)
+// 192 threads per eight macroblocks.  Register budget: four waves per SIMD, nothing spilled (tests/test_kernel_resources.py).
 __global__ __launch_bounds__(192, 2) void k_mb_p(BatchOf<MBArgs> b) {
     __shared__ __attribute__((aligned(16))) MBTileP s_t[8];
     __shared__ __attribute__((aligned(16))) MBShare s_x;
     mb_body_packed<false>(b.item[blockIdx.z], s_t, &s_x);
 }
+// the same with the format's predictor instead of the reference's (vp8hip_conformant_stream): its own kernel, so that the
+// reference path stays the code that was measured
 __global__ __launch_bounds__(192, 2) void k_mb_p_conformant(BatchOf<MBArgs> b) {
     __shared__ __attribute__((aligned(16))) MBTileP s_t[8];
     __shared__ __attribute__((aligned(16))) MBShare s_x;
     mb_body_packed<true>(b.item[blockIdx.z], s_t, &s_x);
 }
-// the mapped forms (vp8hip_set_segment_mode): the packed form only
+// the mapped forms (vp8hip_set_segment_mode)
 __global__ __launch_bounds__(192, 2) void k_mb_p_map(BatchOf<MBArgsMapped> b) {
     __shared__ __attribute__((aligned(16))) MBTileP s_t[8];
     __shared__ __attribute__((aligned(16))) MBShare s_x;
@@ -907,11 +618,6 @@ __global__ __launch_bounds__(192, 2) void k_mb_p_map_conformant(BatchOf<MBArgsMa
     __shared__ __attribute__((aligned(16))) MBShare s_x;
     mb_body_packed<true, true>(b.item[blockIdx.z], s_t, &s_x);
 }
-static bool mb_packed() {
-    static const bool on = [] { const char *v = getenv("VP8HIP_MB_PACKED"); return !(v && v[0] == '0'); }();
-    return on;
-}
-
 static MBArgs mb_args(const CodingItem &it, float ssim_target, int mbw, int mbh) {
     const Frame &cur = *it.cur, &recon = *it.recon;
     const RefSet &refs = it.refs;
@@ -943,7 +649,7 @@ static bool mb_skip() {
 
 void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_target, int mbw, int mbh, bool conformant, bool mapped) {
     static_assert(sizeof(BatchOf<MBArgs>) <= 4096 && sizeof(BatchOf<MBArgsMapped>) <= 4096, "the batch travels in the kernel arguments");
-    if (mapped) {      // (VP8HIP_MB_PACKED=0 has no mapped form: the packed one)
+    if (mapped) {
         BatchOf<MBArgsMapped> b;
         b.n = n;
         for (int i = 0; i < n; ++i) {
@@ -961,13 +667,8 @@ void launch_mb_batch(hipStream_t s, const CodingItem *items, int n, float ssim_t
     for (int i = 0; i < n; ++i) b.item[i] = mb_args(items[i], ssim_target, mbw, mbh);
     if (mb_skip()) return;
     const dim3 grid((b.item[0].mbs + 7) / 8, 1, n);
-    if (mb_packed()) {
-        if (conformant) VP8_LAUNCH(k_mb_p_conformant, grid, dim3(192), 0, s, b);
-        else VP8_LAUNCH(k_mb_p, grid, dim3(192), 0, s, b);
-        return;
-    }
-    if (conformant) VP8_LAUNCH(k_mb_b_conformant, grid, dim3(256), 0, s, b);
-    else VP8_LAUNCH(k_mb_b, grid, dim3(256), 0, s, b);
+    if (conformant) VP8_LAUNCH(k_mb_p_conformant, grid, dim3(192), 0, s, b);
+    else VP8_LAUNCH(k_mb_p, grid, dim3(192), 0, s, b);
 }
 
 // ------------------------------------------------------------------------------------------------

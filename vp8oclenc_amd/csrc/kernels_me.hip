@@ -372,9 +372,9 @@ __device__ __forceinline__ void s1_make_pre(const Plane &cur, int cx, int cy, in
 // LDS_MIN (the filled loop form, where a block's five lanes may lie in two waves): the minimum over the block's lanes goes through min_lds, one word per
 // lane of the workgroup, this lane's at min_lds[sub] -- one store, a barrier, five reads (so EVERY lane of the workgroup must come here), four v_min_u32
 // where the shuffle tree is three steps of six instructions.  The caller keeps the next call from overwriting words still being read.
-template <bool SPLIT, bool PRE_LDS = false, bool LDS_MIN = false>
+template <bool SPLIT, bool LDS_MIN = false>
 __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, int cx, int cy, uint32_t pv, bool live, int sub, int lane,
-                                                  const int *pre_lds = nullptr /* PRE_LDS (loop form): the workgroup's table from s1_make_pre */,
+                                                  const int *pre_lds = nullptr /* loop form: the workgroup's table from s1_make_pre */,
                                                   int pre_off = 0 /* ... and where this block's [sub-block][16] start in it, in BYTES */,
                                                   uint32_t *min_lds = nullptr /* LDS_MIN: the word of this block's first lane */) {
     const int sb0 = sub / 5, j = sub - 5 * sb0;       // SPLIT: this lane's sub-block; otherwise sb0 = 0
@@ -405,21 +405,13 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
         }
     } else {
         // one sub-block at a time (loop NOT unrolled: the register footprint decides how many waves a SIMD holds)
-        if (PRE_LDS) {
-            const v4i wa = metric_a_rows(lane);
-            int pre_addr = pre_off;     // sub-block 0 of this lane's block; stepped by the loop, in the register the reads take it from
+        const v4i wa = metric_a_rows(lane);
+        int pre_addr = pre_off;     // sub-block 0 of this lane's block; stepped by the loop, in the register the reads take it from
 #pragma unroll 1
-            for (int sb = 0; sb < 4; ++sb) {
-                const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;
-                s1_subblock_pre(wa, pre_lds, pre_addr, rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
-                pre_addr += s1_pre_sub_bytes(1);
-            }
-        } else {
-#pragma unroll 1
-            for (int sb = 0; sb < 4; ++sb) {
-                const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;
-                s1_subblock(cp + (ptrdiff_t)sy * a.cur.stride + sx, a.cur.stride, rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
-            }
+        for (int sb = 0; sb < 4; ++sb) {
+            const int sx = (sb >> 1) * 4, sy = (sb & 1) * 4;
+            s1_subblock_pre(wa, pre_lds, pre_addr, rp + (ptrdiff_t)sy * a.ref[r].stride + sx, a.ref[r].stride, acc);
+            pre_addr += s1_pre_sub_bytes(1);
         }
     }
     const int pen_mask = a.pixel_rate < 4 ? -1 : 0;     // x 32 on the two finest levels, x 0 above (a shift and a mask: `* pen_scale' with a scale the compiler cannot see compiles to a 64-bit multiply-add per candidate)
@@ -501,19 +493,19 @@ __device__ __forceinline__ uint32_t search1_block(const Search1Args &a, int r, i
     return ox16 | (oy16 << 16);
 }
 
-// PRE_LDS (loop form): the current blocks' share of the metric made once per wave into LDS (s1_make_pre) instead of by every lane of a block
+// The loop form (SPLIT = false) keeps the current blocks' share of the metric in LDS, made once per wave (s1_make_pre), not by every lane of a block.
 // REF_LOOP: a workgroup searches its blocks in EVERY enabled reference, one after the other (grid y = 1), instead of a workgroup per reference:
 // the block arithmetic and the current blocks' share of the metric are made once for the two or three of them (batches; one video keeps a
 // workgroup per reference: there a launch is as long as one wave)
-// FILL (with PRE_LDS and REF_LOOP: k_search1_plr_b): blocks numbered across the workgroup, 51 of them in its 256 lanes instead of 4 x 12
+// FILL (the loop form with REF_LOOP: k_search1_plr_b): blocks numbered across the workgroup, 51 of them in its 256 lanes instead of 4 x 12
 // (s1_fill_layout.h): the table is made by the whole workgroup behind one barrier, and the minimum over a block's lanes, three of which blocks lie in
 // two waves, goes through LDS (search1_block, LDS_MIN).  Every lane of the workgroup runs every MFMA and meets every barrier: nrefs is the workgroup's.
 static_assert(s1_fill_c_read_worst() == 4 && s1_fill_c_read_best() == 4, "the C reads of the filled loop form's pre table must be free of LDS bank conflicts: all four waves, every sub-block and quad");
 static_assert(s1_fill_c_read_worst(64) > 4, "the bank model sees the conflicts of unskewed slots");
-template <bool SPLIT, bool PRE_LDS = false, bool REF_LOOP = false, bool FILL = false>
+template <bool SPLIT, bool REF_LOOP = false, bool FILL = false>
 __device__ __forceinline__ void search1_body(const Search1Args &a) {
     using M = S1Map<SPLIT>;
-    static_assert(!FILL || (!SPLIT && PRE_LDS && REF_LOOP), "the filled map is the loop form's, with the table in LDS and the reference loop");
+    static_assert(!FILL || (!SPLIT && REF_LOOP), "the filled map is the loop form's, with the reference loop");
     if (!REF_LOOP && (int)blockIdx.y >= a.nrefs) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = FILL ? s1_fill_slot_of((int)threadIdx.x) : lane / M::LANES_PER_BLOCK;
@@ -547,7 +539,7 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
         // (lane 255 has no block: never live, it searches the frame's last block with slot 50's C input, and of the five words of the minimum it
         // reads, 256..259 are never written -- uninitialised on purpose, its result is never used)
         min_lds = &s_min[0][s1_fill_min_at(t)];
-    } else if (!SPLIT && PRE_LDS) {
+    } else if (!SPLIT) {
         // the current blocks' share of the metric, once per wave into LDS: lane = (block slot, sub-block).  The stages hand over inside the wave
         // (LDS executes a wave's operations in order): no barrier, the compiler is kept from moving the reads up
         __shared__ __attribute__((aligned(16))) int s_pre[4][S1_PRE_INTS];
@@ -567,8 +559,8 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
         const uint32_t pv = parent_written ? reinterpret_cast<const uint32_t *>(a.src[r])[parent] : 0u;
         // (FILL: the minimum's words alternate between two buffers: a wave writes reference ri + 2's only behind the barrier of ri + 1, which every wave
         // passes with its reads of ri done)
-        const uint32_t out = search1_block<SPLIT, !SPLIT && PRE_LDS, FILL>(a, r, cx, cy, pv, live, sub, lane, pre_lds, pre_off,
-                                                                            FILL ? min_lds + (ri & 1) * S1_FILL_MIN_WORDS : nullptr);
+        const uint32_t out = search1_block<SPLIT, FILL>(a, r, cx, cy, pv, live, sub, lane, pre_lds, pre_off,
+                                                             FILL ? min_lds + (ri & 1) * S1_FILL_MIN_WORDS : nullptr);
         if (sub == 0 && live) {
             const int cell = (cy >> 3) * a.net_width + (cx >> 3);
             reinterpret_cast<uint32_t *>(a.dst[r])[cell] = out;
@@ -585,17 +577,13 @@ __device__ __forceinline__ void search1_body(const Search1Args &a) {
 // LDS: 6 block searches on top of 16, no workgroup waits for another, and the chain has one link where it had four.  The same routine on
 // the same inputs (search1_block), so the level-1 net -- the only one the next launch reads -- is the one four launches leave.
 // ------------------------------------------------------------------------------------------------
-// FINEST: level 0 as well -- the 8 x 8 level-0 blocks under the tile, in the loop form (five lanes per block, twelve blocks per wave:
-// the tile's 64 blocks are one pass of the workgroup's six waves), their parents the tile's own level-1 vectors.  The whole hierarchical
-// search of a reference is then ONE link of the chain.
+// (Level 0 in the same launch as well was no faster: the finest level is whole-chip work, profiles/README.md.)
 struct CoarseArgs { Search1Args lv[5]; };   // lv[l] = level l
 constexpr int COARSE_WAVES = 6;             // 18 block slots of 20 lanes: the tile's 16 level-1 blocks in one pass
-// the tile's work: L0..L4 = the five levels' arguments (L0 read only with FINEST), r = the reference's slot in them
-// TOP_ONLY: levels 4, 3 and 2 only (two waves are enough); the level-2 net leaves the workgroup and levels 1 and 0 are launches of their own
-template <bool FINEST, bool TOP_ONLY = false>
-__device__ __forceinline__ void coarse_tile(const Search1Args &L0, const Search1Args &L1, const Search1Args &L2, const Search1Args &L3, const Search1Args &L4, int r) {
+// the tile's work: L1..L4 = the four levels' arguments, r = the reference's slot in them
+__device__ __forceinline__ void coarse_tile(const Search1Args &L1, const Search1Args &L2, const Search1Args &L3, const Search1Args &L4, int r) {
     using M = S1Map<true>;
-    __shared__ uint32_t mv4, mv3, mv2[4], mv1[16];
+    __shared__ uint32_t mv4, mv3, mv2[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / M::LANES_PER_BLOCK, sub = lane - M::LANES_PER_BLOCK * grp;
     const int slot = grp < M::BLOCKS_PER_WAVE ? wave * M::BLOCKS_PER_WAVE + grp : 99;     // block slot of this lane in the workgroup, 0..17
@@ -630,9 +618,7 @@ __device__ __forceinline__ void coarse_tile(const Search1Args &L0, const Search1
         const bool exists = slot < 4 && bx < L2.bw && by * L2.bw + bx < L2.nblk;
         const uint32_t out = search1_block<true>(L2, r, (exists ? bx : 0) * 8, (exists ? by : 0) * 8, mv3, exists, sub, lane);
         if (slot < 4 && sub == 0) mv2[slot] = exists ? out : 0u;
-        if (TOP_ONLY && slot < 4 && sub == 0 && exists) reinterpret_cast<uint32_t *>(L2.dst[r])[by * L2.net_width + bx] = out;
     }
-    if (TOP_ONLY) return;
     __syncthreads();
     // ---- level 1: the tile's 4 x 4 blocks; the only net that leaves the workgroup ----
     {
@@ -642,97 +628,26 @@ __device__ __forceinline__ void coarse_tile(const Search1Args &L0, const Search1
         const uint32_t pv = mv2[(((j >> 1) & 1) << 1) | ((i >> 1) & 1)];
         const uint32_t out = search1_block<true>(L1, r, (live ? bx : 0) * 8, (live ? by : 0) * 8, pv, live, sub, lane);
         if (sub == 0 && live) reinterpret_cast<uint32_t *>(L1.dst[r])[by * L1.net_width + bx] = out;
-        if (FINEST && sub == 0 && slot < 16) mv1[slot] = live ? out : 0u;
-    }
-    if (!FINEST) return;
-    __syncthreads();
-    // ---- level 0: the 8 x 8 blocks under the tile ----
-    {
-        using M0 = S1Map<false>;
-        const int grp0 = lane / M0::LANES_PER_BLOCK, sub0 = lane - M0::LANES_PER_BLOCK * grp0;
-        const int slot0 = grp0 < M0::BLOCKS_PER_WAVE ? wave * M0::BLOCKS_PER_WAVE + grp0 : 99;     // 0..71
-        const int i = slot0 & 7, j = (slot0 >> 3) & 7;
-        const int bx = 8 * tx + i, by = 8 * ty + j;
-        const bool live = slot0 < 64 && bx < L0.bw && by * L0.bw + bx < L0.nblk;
-        const uint32_t pv = mv1[((j >> 1) << 2) | (i >> 1)];
-        const uint32_t out = search1_block<false>(L0, r, (live ? bx : 0) * 8, (live ? by : 0) * 8, pv, live, sub0, lane);
-        if (sub0 == 0 && live) reinterpret_cast<uint32_t *>(L0.dst[r])[by * L0.net_width + bx] = out;
     }
 }
 
-template <bool FINEST>
 __global__ __launch_bounds__(64 * COARSE_WAVES) void k_search1_coarse(CoarseArgs a) {
     if ((int)blockIdx.y >= a.lv[1].nrefs) return;
-    coarse_tile<FINEST>(a.lv[0], a.lv[1], a.lv[2], a.lv[3], a.lv[4], a.lv[1].refmap[blockIdx.y]);
+    coarse_tile(a.lv[1], a.lv[2], a.lv[3], a.lv[4], a.lv[1].refmap[blockIdx.y]);
 }
 
-// The same for the members of a BATCH (blockIdx.z = member): ONE launch where the batched path had four (levels 4-1) or five.  Eight members'
-// Search1Args of four or five levels do not fit the 4 KiB kernel-argument segment, so what all members share -- the levels' geometry: the
-// members are contexts of one size, their surfaces and nets are laid out alike -- travels once and a member brings its addresses only.
-struct CoarseGeom { int w, h, cur_stride, ref_stride; };
-struct CoarseMember {
-    const uint8_t *cur[5];          // pixel (0, 0) of level l of the current frame
-    const uint8_t *ref[3][5];       // ... of reference r
-    int16_t *dst1[3], *dst0[3];     // the level-1 and level-0 nets of reference r (where launch_search1_batch leaves them)
-    int refmap[3], nrefs;
-};
-struct CoarseBatchArgs { CoarseGeom g[5]; int net_width, n; CoarseMember m[MAX_BATCH]; };
-static_assert(sizeof(CoarseBatchArgs) <= 4096, "a batch's argument block travels in the 4 KiB kernel-argument segment");
-__device__ __forceinline__ Search1Args coarse_level(const CoarseBatchArgs &a, const CoarseMember &m, int l, int r) {
-    Search1Args s;
-    const CoarseGeom &g = a.g[l];
-    s.cur = Plane{const_cast<uint8_t *>(m.cur[l]), g.cur_stride, g.w, g.h};
-    s.ref[0] = Plane{const_cast<uint8_t *>(m.ref[r][l]), g.ref_stride, g.w, g.h};
-    s.dst[0] = l == 1 ? m.dst1[r] : m.dst0[r];        // (only levels 1 and 0 leave the workgroup)
-    s.net_width = a.net_width;
-    s.w = g.w;
-    s.h = g.h;
-    s.pixel_rate = 1 << l;
-    s.rate_shift = l;
-    s.bw = g.w / 8;
-    s.nblk = (g.w / 8) * (g.h / 8);
-    return s;
-}
-__global__ __launch_bounds__(128) void k_search1_top_b(CoarseBatchArgs a) {
-    const CoarseMember &m = a.m[blockIdx.z];
-    if ((int)blockIdx.y >= m.nrefs) return;
-    const int r = m.refmap[blockIdx.y];
-    const Search1Args L1 = coarse_level(a, m, 1, r), L2 = coarse_level(a, m, 2, r), L3 = coarse_level(a, m, 3, r), L4 = coarse_level(a, m, 4, r);
-    coarse_tile<false, true>(L1, L1, L2, L3, L4, 0);      // (level 1 gives the tile grid; its blocks are not searched here)
-}
-template <bool FINEST>
-__global__ __launch_bounds__(64 * COARSE_WAVES) void k_search1_coarse_b(CoarseBatchArgs a) {
-    const CoarseMember &m = a.m[blockIdx.z];
-    if ((int)blockIdx.y >= m.nrefs) return;
-    const int r = m.refmap[blockIdx.y];
-    const Search1Args L0 = coarse_level(a, m, 0, r), L1 = coarse_level(a, m, 1, r), L2 = coarse_level(a, m, 2, r), L3 = coarse_level(a, m, 3, r),
-                      L4 = coarse_level(a, m, 4, r);
-    coarse_tile<FINEST>(L0, L1, L2, L3, L4, 0);       // (slot 0 of the locals holds reference r)
-}
-
-template <bool SPLIT>
-__global__ __launch_bounds__(256) void k_search1(Search1Args a) { search1_body<SPLIT>(a); }
+// The short-wave form, what a small launch takes (search1_split) ...
+__global__ __launch_bounds__(256) void k_search1(Search1Args a) { search1_body<true>(a); }
 static_assert(sizeof(BatchOf<Search1Args>) <= 4096 && sizeof(PyrArgs) <= 4096 && sizeof(BatchOf<PackItem>) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
-template <bool SPLIT>
-__global__ __launch_bounds__(256) void k_search1_b(BatchOf<Search1Args> b) { search1_body<SPLIT>(b.item[blockIdx.z]); }
+__global__ __launch_bounds__(256) void k_search1_b(BatchOf<Search1Args> b) { search1_body<true>(b.item[blockIdx.z]); }
+// ... and the loop form: one video a workgroup per reference, batches the filled map with the reference loop.
 // (the loop form's register budgets pinned, eight waves per SIMD and seven: under a bare launch bound hipcc gives the MFMA results of the metric
 // AGPRs and pays a v_accvgpr_read per value)
-__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_search1_pl(Search1Args a) { search1_body<false, true>(a); }
-__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_search1_pl_b(BatchOf<Search1Args> b) { search1_body<false, true>(b.item[blockIdx.z]); }
-__global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search1_plr_b(BatchOf<Search1Args> b) { search1_body<false, true, true, true>(b.item[blockIdx.z]); }
+__global__ __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(256) void k_search1_pl(Search1Args a) { search1_body<false>(a); }
+__global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search1_plr_b(BatchOf<Search1Args> b) { search1_body<false, true, true>(b.item[blockIdx.z]); }
 // (the filled map pays where the part is full, the headline's regime.  Alone on the part -- a batch of one 1080p member, three references -- a launch is
 // as long as one wave and the barrier per reference costs more than the lanes save: 28.4 us a launch where the twelve-slot map took 27.3, -0.8 % of
 // that one-chunk rate; profiles/s1_fill_parent_vs_this.txt, section 4.  Not branched on: a launch cannot see what else runs on the part.)
-// VP8HIP_S1_REF_LOOP=0: a workgroup per reference in batches too (same-box A/B runs)
-static bool search1_ref_loop() {
-    static const bool on = [] { const char *v = getenv("VP8HIP_S1_REF_LOOP"); return !(v && v[0] == '0'); }();
-    return on;
-}
-// VP8HIP_S1_PRE_LDS=0: the loop form as it was (every lane makes the current block's share itself); same-box A/B runs
-static bool search1_pre_lds() {
-    static const bool on = [] { const char *v = getenv("VP8HIP_S1_PRE_LDS"); return !(v && v[0] == '0'); }();
-    return on;
-}
 
 static Search1Args search1_args(const CodingItem &it, int level, int src_idx, int net_width) {
     const Frame &cur = *it.cur;
@@ -762,89 +677,37 @@ static Search1Args search1_args(const CodingItem &it, int level, int src_idx, in
     return a;
 }
 
-int persistent_workgroups() {
-    static const int n = [] { const char *v = getenv("VP8HIP_PERSIST"); return v && v[0] ? atoi(v) : 0; }();
-    return n;
-}
-
 static bool search1_skip() {
     static const bool skip = experiment_skip("s1");
     return skip;   // timing experiment only
 }
 // fewer waves than the chip has SIMDs: the launch is as long as one wave whatever else runs -> the short-wave form.
-// VP8HIP_S1_SPLIT=0/1 forces one form (same-box A/B runs)
-static bool search1_split(size_t blocks_times_refs, bool latency) {
+// VP8HIP_S1_SPLIT=0/1 forces one form (the tests' tap: at their shapes every launch is a small one)
+static bool search1_split(size_t blocks_times_refs) {
     static const int forced = [] { const char *v = getenv("VP8HIP_S1_SPLIT"); return v && v[0] ? (v[0] == '1' ? 1 : 0) : -1; }();
-    return forced >= 0 ? forced == 1 : (latency || blocks_times_refs < (size_t)12 * 1024);
+    return forced >= 0 ? forced == 1 : blocks_times_refs < (size_t)12 * 1024;
 }
 
-void launch_search1(hipStream_t s, const CodingItem &it, int level, int src_idx, int net_width, bool latency) {
+void launch_search1(hipStream_t s, const CodingItem &it, int level, int src_idx, int net_width) {
     const Search1Args a = search1_args(it, level, src_idx, net_width);
     const int n = a.nrefs;
     if (a.nblk <= 0 || n == 0 || search1_skip()) return;
-    if (search1_split((size_t)a.nblk * n, latency))
-        VP8_LAUNCH(k_search1<true>, dim3((a.nblk + S1Map<true>::BLOCKS_PER_WG - 1) / S1Map<true>::BLOCKS_PER_WG, n), dim3(256), 0, s, a);
-    else if (search1_pre_lds())
-        VP8_LAUNCH(k_search1_pl, dim3((a.nblk + S1Map<false>::BLOCKS_PER_WG - 1) / S1Map<false>::BLOCKS_PER_WG, n), dim3(256), 0, s, a);
+    if (search1_split((size_t)a.nblk * n))
+        VP8_LAUNCH(k_search1, dim3((a.nblk + S1Map<true>::BLOCKS_PER_WG - 1) / S1Map<true>::BLOCKS_PER_WG, n), dim3(256), 0, s, a);
     else
-        VP8_LAUNCH(k_search1<false>, dim3((a.nblk + S1Map<false>::BLOCKS_PER_WG - 1) / S1Map<false>::BLOCKS_PER_WG, n), dim3(256), 0, s, a);
+        VP8_LAUNCH(k_search1_pl, dim3((a.nblk + S1Map<false>::BLOCKS_PER_WG - 1) / S1Map<false>::BLOCKS_PER_WG, n), dim3(256), 0, s, a);
 }
 
-// levels 4..1 (finest = false) or 4..0 in one launch (k_search1_coarse); the level-1 and level-0 nets land where launch_search1 leaves them
-void launch_search1_coarse(hipStream_t s, const CodingItem &it, int net_width, bool finest) {
+// levels 4..1 in one launch (k_search1_coarse); the level-1 net lands where launch_search1 leaves it
+void launch_search1_coarse(hipStream_t s, const CodingItem &it, int net_width) {
     CoarseArgs a;
     for (int l = 0; l <= 4; ++l) a.lv[l] = search1_args(it, l, l & 1, net_width);   // src of level l: 0 for 4, 2 and 0; 1 for 3 and 1
     const Search1Args &L0 = a.lv[0], &L1 = a.lv[1];
     if (L0.nblk <= 0 || L0.nrefs == 0 || search1_skip()) return;
-    // tiles of 4 x 4 level-1 blocks = 8 x 8 level-0 blocks; a frame of one macroblock row or column has level-0 blocks without a level-1 block above them
-    const int tiles_x = finest ? (L0.bw + 7) / 8 : (L1.bw + 3) / 4, tiles_y = finest ? (L0.h / 8 + 7) / 8 : (L1.h / 8 + 3) / 4;
+    // tiles of 4 x 4 level-1 blocks (a frame of one macroblock row or column has none)
+    const int tiles_x = (L1.bw + 3) / 4, tiles_y = (L1.h / 8 + 3) / 4;
     if (tiles_x * tiles_y <= 0) return;
-    if (finest) VP8_LAUNCH(k_search1_coarse<true>, dim3(tiles_x * tiles_y, L0.nrefs), dim3(64 * COARSE_WAVES), 0, s, a);
-    else VP8_LAUNCH(k_search1_coarse<false>, dim3(tiles_x * tiles_y, L0.nrefs), dim3(64 * COARSE_WAVES), 0, s, a);
-}
-
-// levels 4..1 (finest = false) or 4..0 of every member of a batch in ONE launch; false = the members' surfaces are not laid out alike
-// (never so for contexts of one size: the caller then launches level by level)
-bool launch_search1_coarse_batch(hipStream_t s, const CodingItem *items, int n, int net_width, bool finest, bool top_only) {
-    CoarseBatchArgs a;
-    a.net_width = net_width;
-    a.n = n;
-    int maxrefs = 0;
-    for (int l = 0; l <= 4; ++l) {
-        const Plane &c = items[0].cur->Y[l];
-        a.g[l] = CoarseGeom{c.w, c.h, c.stride, items[0].refs.ref[0].Y[l].stride};
-    }
-    for (int i = 0; i < n; ++i) {
-        CoarseMember &m = a.m[i];
-        const RefSet &refs = items[i].refs;
-        const NetSet &nets = *items[i].nets;
-        int k = 0;
-        for (int r = 0; r < 3; ++r) {
-            for (int l = 0; l <= 4; ++l) {
-                const Plane &rp = refs.ref[r].Y[l], &cp = items[i].cur->Y[l];
-                if (rp.stride != a.g[l].ref_stride || cp.stride != a.g[l].cur_stride || cp.w != a.g[l].w || cp.h != a.g[l].h || rp.w != cp.w || rp.h != cp.h) return false;
-                m.ref[r][l] = rp.p;
-                if (r == 0) m.cur[l] = cp.p;
-            }
-            m.dst1[r] = nets.net[r][0];       // launch_search1_batch's ping-pong: level 4 reads net 0 ... level 1 writes net 0, level 0 writes net 1
-            m.dst0[r] = nets.net[r][1];
-            if (refs.use[r]) m.refmap[k++] = r;
-        }
-        m.nrefs = k;
-        for (int j = k; j < 3; ++j) m.refmap[j] = 0;
-        maxrefs = k > maxrefs ? k : maxrefs;
-    }
-    const int bw0 = a.g[0].w / 8, bh0 = a.g[0].h / 8, bw1 = a.g[1].w / 8, bh1 = a.g[1].h / 8;
-    if (bw0 * bh0 <= 0 || maxrefs == 0 || search1_skip()) return true;
-    const int tiles_x = finest ? (bw0 + 7) / 8 : (bw1 + 3) / 4, tiles_y = finest ? (bh0 + 7) / 8 : (bh1 + 3) / 4;
-    if (tiles_x * tiles_y <= 0) return !finest ? true : false;
-    if (top_only) {     // tiles of 2 x 2 level-2 blocks = one level-3 block (the tile grid is the same: 4 x 4 level-1 blocks)
-        VP8_LAUNCH(k_search1_top_b, dim3(tiles_x * tiles_y, maxrefs, n), dim3(128), 0, s, a);
-        return true;
-    }
-    if (finest) VP8_LAUNCH(k_search1_coarse_b<true>, dim3(tiles_x * tiles_y, maxrefs, n), dim3(64 * COARSE_WAVES), 0, s, a);
-    else VP8_LAUNCH(k_search1_coarse_b<false>, dim3(tiles_x * tiles_y, maxrefs, n), dim3(64 * COARSE_WAVES), 0, s, a);
-    return true;
+    VP8_LAUNCH(k_search1_coarse, dim3(tiles_x * tiles_y, L0.nrefs), dim3(64 * COARSE_WAVES), 0, s, a);
 }
 
 void launch_search1_batch(hipStream_t s, const CodingItem *items, int n, int level, int src_idx, int net_width) {
@@ -858,14 +721,10 @@ void launch_search1_batch(hipStream_t s, const CodingItem *items, int n, int lev
     }
     const int nblk = b.item[0].nblk;
     if (nblk <= 0 || maxrefs == 0 || search1_skip()) return;
-    if (search1_split((size_t)nblk * totrefs, false))
-        VP8_LAUNCH(k_search1_b<true>, dim3((nblk + S1Map<true>::BLOCKS_PER_WG - 1) / S1Map<true>::BLOCKS_PER_WG, maxrefs, n), dim3(256), 0, s, b);
-    else if (search1_pre_lds() && search1_ref_loop())     // (68 registers, seven waves per SIMD.  Its twelve-slot predecessor, 70 registers, held to 64 spilled six and was no faster: 73.4-73.6 either way)
+    if (search1_split((size_t)nblk * totrefs))
+        VP8_LAUNCH(k_search1_b, dim3((nblk + S1Map<true>::BLOCKS_PER_WG - 1) / S1Map<true>::BLOCKS_PER_WG, maxrefs, n), dim3(256), 0, s, b);
+    else      // (68 registers, seven waves per SIMD.  Its twelve-slot predecessor, 70 registers, held to 64 spilled six and was no faster: 73.4-73.6 either way)
         VP8_LAUNCH(k_search1_plr_b, dim3(s1_fill_grid(nblk), 1, n), dim3(256), 0, s, b);      // the filled map: 51 blocks per workgroup (s1_fill_layout.h)
-    else if (search1_pre_lds())
-        VP8_LAUNCH(k_search1_pl_b, dim3((nblk + S1Map<false>::BLOCKS_PER_WG - 1) / S1Map<false>::BLOCKS_PER_WG, maxrefs, n), dim3(256), 0, s, b);
-    else
-        VP8_LAUNCH(k_search1_b<false>, dim3((nblk + S1Map<false>::BLOCKS_PER_WG - 1) / S1Map<false>::BLOCKS_PER_WG, maxrefs, n), dim3(256), 0, s, b);
 }
 
 // test tap: the block-match metric on caller-supplied difference blocks (n x 16 ints)

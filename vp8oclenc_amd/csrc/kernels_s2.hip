@@ -159,27 +159,25 @@ __device__ __forceinline__ v16i mfma_round(v4i a, v4i b) {
     return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
 }
 
-// SPREAD: the cost phase's 26 x 4 (candidate, 4x4 block) tasks of a block spread over ALL 32 lanes of its half-wave and, for what is left, over
-// one wave of the workgroup.  With lane = candidate, 6 of a block's 32 lanes idle through four rounds of the metric (the wave issues them all the
-// same); here the idle lanes take the FOURTH 4x4 block of candidates 0..17 during the first three rounds, and the fourth 4x4 block of candidates
-// 18..25 of all eight blocks -- 64 tasks -- is one round of wave 0 alone: 3.25 rounds per wave on average instead of 4.  The costs meet in LDS
-// (in the H array's dead bytes), two workgroup barriers around wave 0's extra round.  Same integer sums in another order: the same result.
+// The cost phase's 26 x 4 (candidate, 4x4 block) tasks of a block are spread over ALL 32 lanes of its half-wave and, for what is left, over
+// one wave of the workgroup.  A lane takes its own candidate's 4x4 blocks 0..2 in three rounds; the six lanes of a block's 32 that have no
+// candidate take the FOURTH 4x4 block of candidates 0..17 during those rounds, and the fourth 4x4 block of candidates 18..25 of all eight
+// blocks -- 64 tasks -- is one round of one wave alone: 3.25 rounds per wave on average where lane = candidate throughout would issue 4.  The
+// costs meet in LDS (in the H array's dead bytes), two workgroup barriers around the one wave's extra round.
 // ALLREFS: the workgroup takes its eight blocks through EVERY enabled reference of its context, one after the other (the batched forms, grid
 // y = 1); what does not depend on the reference is made once, ahead of the loop: the blocks' coordinates, the current block's load, its byte
 // scatter and its share of the metric (the pre table, which therefore has an array of its own: the H array's bytes are the next reference's).
 // Otherwise one reference, ref_idx (the one-video form: one reference per blockIdx.y).
 // Lane arithmetic: every LDS address and every small integer of a global address is a function of the thread's number alone, stated once in
 // s2_lane_layout.h.  A register of it kept across the loops is one a wave of the SIMD cannot have, so only what the later stages use is kept (the H
-// store, the vertical pass and the cost phase: made from threadIdx.x, the compiler holds them); what the head of a reference uses -- the window,
-// the zero-vector block, the operands' rows and the whole-pel column -- used to be computed again per reference (37 vector instructions) and is
-// now READ: the lane's row of K_S2_LANE -- its first two dwords, which the window's load and store hang on, once per group and kept where the
-// registers allow (KEEP), the rest per reference in one load beside the net vector's -- a field taken out where it is used.
-// tn: the thread's number again, as a value the compiler cannot follow (search2_groups), for the once-per-group part, which is made again per group.
-// READ false: the fields are computed from tn by the functions the table was made from, not read -- the one-group, one-reference form, whose
-// workgroup comes here once: nothing is made twice there, and the row's registers would only add to its count.
-// KEEP: the first two dwords of the lane's row are read once per group and kept across the reference loop; otherwise per reference with the rest
-// (the one-group batched forms, which have no register to spare: kept there, the two dwords cost 8 bytes of scratch).
-template <bool SPREAD, bool ALLREFS, bool READ = true, bool KEEP = false>
+// store, the vertical pass and the cost phase: made from threadIdx.x, the compiler holds them).  What the head of a reference uses -- the window,
+// the zero-vector block, the operands' rows and the whole-pel column, 37 vector instructions to compute -- the ALLREFS form reads: the lane's row
+// of K_S2_LANE, its first two dwords, which the window's load and store hang on, once per group and kept across the reference loop, the rest per
+// reference in one load beside the net vector's -- a field taken out where it is used.  The one-reference form computes the fields from tn by the
+// functions the table was made from: its workgroup comes here once, nothing is made twice, and the row's registers would only add to its count.
+// tn: the thread's number -- in the ALLREFS form as a value the compiler cannot follow (search2_two_groups), for the once-per-group part, which is made
+// again per group.
+template <bool ALLREFS>
 __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_idx, int tn) {
     if (ALLREFS ? a.nrefs == 0 : ref_idx >= a.nrefs) return;
     __shared__ __attribute__((aligned(16))) uint32_t s_HT[8][5 * HT_XC];
@@ -206,7 +204,7 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
     uint32_t trow = (uint32_t)tn * (uint32_t)(S2_LANE_DWORDS * 4);
     // the first two dwords of that row, what the head of a reference needs first: read here, once per group, and kept across the reference loop
     v2i lk = {0, 0};
-    if (READ && KEEP) lk = *reinterpret_cast<const v2i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow);
+    if (ALLREFS) lk = *reinterpret_cast<const v2i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow);
     {   // current block: lanes 0-15 one dword each, scattered as column bytes [row half][column] (16 dwords, in the table's last 64 bytes): the four
         // columns of 4x4 block (m*2 + n) -- the order the cost loop below walks them: row half m, column half n -- are four consecutive dwords.  Then
         // its share of the metric (vp8hip_dev.h, weight_pre_half), half a 4x4 block per lane: lane = (copy, half): the 4x4 blocks 0, 1, 2, 3 and the two
@@ -255,10 +253,9 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         // The rest of the lane's row, at the top with the net vector's load; its first two dwords were read once per group (lk, above) and are
         // kept: nothing the window's load and store hang on is waited for, and the zero-vector block's load comes behind the window's.
         v4i lb = {0, 0, 0, 0};
-        if (READ && !KEEP) lk = *reinterpret_cast<const v2i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow);
-        if (READ) lb = *reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow + 4 * S2_LANE_KEPT_DWORDS);
+        if (ALLREFS) lb = *reinterpret_cast<const v4i *>(reinterpret_cast<const char *>(K_S2_LANE.w) + trow + 4 * S2_LANE_KEPT_DWORDS);
         auto fld = [&](int f) -> uint32_t {      // (f is a constant wherever this is called: a register and one v_and_b32 or v_lshrrev_b32)
-            if (!READ) return s2_field(tn, f);
+            if (!ALLREFS) return s2_field(tn, f);
             const uint32_t w = (uint32_t)(f < 2 * S2_LANE_KEPT_DWORDS ? lk[(f >> 1) & 1] : lb[((f >> 1) - S2_LANE_KEPT_DWORDS) & 3]);
             return (f & 1) ? w >> 16 : w & 0xffffu;
         };
@@ -293,8 +290,8 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         const uint32_t zoff = __umul24((uint32_t)cy + fld(S2F_ZERO_ROW), (uint32_t)rf.stride) + ((uint32_t)cx + fld(S2F_ZERO_HALF));
         const uint32_t zv = *reinterpret_cast<const uint32_t *>(rf.p + zoff) ^ 0x80808080u;
         lds_fence();
-        const uint32_t k_row = !READ ? (uint32_t)s2_k_row(tn) : (uint32_t)lb[(S2F_K_ROW >> 1) - S2_LANE_KEPT_DWORDS];                     // the lane's row of K_BH and of K_AV: S2F_K_ROW, alone in its dword
-        const uint32_t k31_keep = !READ ? s2_k31_keep(tn) : (uint32_t)lk[S2F_K31_KEEP_HI >> 1] | 0xffffu;        // one_at_k31's mask, all of the operand's last dword or all but its last byte: S2F_K31_KEEP_HI above 0xffff
+        const uint32_t k_row = !ALLREFS ? (uint32_t)s2_k_row(tn) : (uint32_t)lb[(S2F_K_ROW >> 1) - S2_LANE_KEPT_DWORDS];                     // the lane's row of K_BH and of K_AV: S2F_K_ROW, alone in its dword
+        const uint32_t k31_keep = !ALLREFS ? s2_k31_keep(tn) : (uint32_t)lk[S2F_K31_KEEP_HI >> 1] | 0xffffu;        // one_at_k31's mask, all of the operand's last dword or all but its last byte: S2F_K31_KEEP_HI above 0xffff
 
         // ---- horizontal pass: ONE MFMA for the wave's two blocks ------------------------------------------------------------
         // A = the windows (row m = 16 * block + window row; rows 14, 15 and bytes 20..31 of a row hold whatever the LDS held: they
@@ -356,30 +353,23 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
         int diff = 0;
         // a task = 16 bytes of the V array (the B operand: one ds_read_b128) and 16 ints of the pre table (the C input)
         auto metric = [&](int src, int pre16) { return weight_mfma(wa, load_pre16(lds_at<const int>(PRE, pre16)), *lds_at<const v4i>(V, src)); };
-        if (SPREAD) {
-            // (branch-free: a lane's own candidate, 4x4 block j in round j, or, for the idle lanes, 4x4 block 3 of candidate 3 (lane - 26) + j: one
-            // base address and one stride per lane, the table's copies of block 3 one block apart like the others; the idle lanes' costs go to q3,
-            // everybody else's to the table's unused words 29..31, and an idle lane's own sum is never looked at: `valid` is false there)
-            const int src = s2_cost_src(t), step = s2_cost_step(t), pre = s2_cost_pre(t);
-            int *dst = lds_at<int>(HT, s2_cost_dst(t));
+        // (branch-free: a lane's own candidate, 4x4 block j in round j, or, for the idle lanes, 4x4 block 3 of candidate 3 (lane - 26) + j: one
+        // base address and one stride per lane, the table's copies of block 3 one block apart like the others; the idle lanes' costs go to q3,
+        // everybody else's to the table's unused words 29..31, and an idle lane's own sum is never looked at: `valid` is false there)
+        const int src = s2_cost_src(t), step = s2_cost_step(t), pre = s2_cost_pre(t);
+        int *dst = lds_at<int>(HT, s2_cost_dst(t));
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {       // rounds 0..2: a candidate's own lane its 4x4 blocks 0..2, the idle lanes block 3 of candidates 0..17
-                const int c = metric(src + j * step, pre + 64 * j);
-                dst[j] = c;
-                diff += c;
-            }
-            __syncthreads();                    // every wave's V and pre arrays (and the idle lanes' costs) are in LDS
-            if (s2_wave(t) == (wg_x & 3)) {      // ONE wave (taking turns from workgroup to workgroup: the waves of a workgroup sit on different SIMDs): block 3 of candidates 18..25 of all eight block slots
-                *lds_at<int>(HT, s2_extra_dst(t)) = metric(s2_extra_src(t), s2_extra_pre(t));
-            }
-            __syncthreads();
-            diff += *lds_at<const int>(HT, s2_cost_q3_read(t));
-        } else {
-            // lane 25: the zero-MV block (whole-pel: both passes are the identity); the idle lanes read it too
-            const int src = s2_cost_src_plain(t), pre = s2_cost_pre_plain(t);
-#pragma unroll
-            for (int bb = 0; bb < 4; ++bb) diff += metric(src + bb * V_ROW * 4, pre + bb * 64);
+        for (int j = 0; j < 3; ++j) {       // rounds 0..2: a candidate's own lane its 4x4 blocks 0..2, the idle lanes block 3 of candidates 0..17
+            const int c = metric(src + j * step, pre + 64 * j);
+            dst[j] = c;
+            diff += c;
         }
+        __syncthreads();                    // every wave's V and pre arrays (and the idle lanes' costs) are in LDS
+        if (s2_wave(t) == (wg_x & 3)) {      // ONE wave (taking turns from workgroup to workgroup: the waves of a workgroup sit on different SIMDs): block 3 of candidates 18..25 of all eight block slots
+            *lds_at<int>(HT, s2_extra_dst(t)) = metric(s2_extra_src(t), s2_extra_pre(t));
+        }
+        __syncthreads();
+        diff += *lds_at<const int>(HT, s2_cost_q3_read(t));
         uint32_t key = ((uint32_t)diff << 8) + kcode;     // (diff + penalty) << 8 | number
         const bool ok = valid && key < (0x7fffu << 8);
         key = ok ? key : 0xffffffffu;
@@ -419,43 +409,42 @@ __device__ __forceinline__ void search2_body(const S2Args &a, int wg_x, int ref_
     }
 }
 
-// ITER: a workgroup takes ITER consecutive groups of eight blocks, one after the other.  A third of what a wave issues for a group does not
-// depend on the group -- the lane's place in the operand tables of the two passes and the tables themselves, its LDS addresses in every stage, its
-// candidate's offset and penalty -- and the compiler keeps in registers across the loop what search2_body makes from threadIdx.x (the price:
-// registers, i.e. waves per SIMD).  What it makes from tn -- the once-per-group part's addresses, and the byte offset of the lane's row of
-// K_S2_LANE -- starts anew with every group: the empty asm below is the one place the thread's number is hidden at; per reference the body hides
-// the row's offset again, in place.  (The form that comes here once, ITER = 1 with one reference per workgroup, computes the fields: READ = false.)
-template <bool SPREAD, int ITER, bool ALLREFS>
-__device__ __forceinline__ void search2_groups(const S2Args &a, int grp, int ref_idx) {
-    if (ITER == 1 && !ALLREFS) { search2_body<SPREAD, ALLREFS, false>(a, grp, ref_idx, (int)threadIdx.x); return; }
+// The batched forms: a workgroup takes two consecutive groups of eight blocks, one after the other, each through every enabled reference -- up to
+// six passes of the body per workgroup (four groups took the registers past seven waves per SIMD, and a workgroup of twelve passes makes the
+// launch's end ragged).  A third of what a wave issues for a group does not depend on the group -- the lane's place in the operand tables of
+// the two passes and the tables themselves, its LDS addresses in every stage, its candidate's offset and penalty -- and the compiler keeps in
+// registers across the loop what search2_body makes from threadIdx.x (the price: registers, i.e. waves per SIMD).  What it makes from tn --
+// the once-per-group part's addresses, and the byte offset of the lane's row of K_S2_LANE -- starts anew with every group: the empty asm below
+// is the one place the thread's number is hidden at; per reference the body hides the row's offset again, in place.
+__device__ __forceinline__ void search2_two_groups(const S2Args &a, int grp) {
 #pragma unroll 1
-    for (int it = 0; it < ITER; ++it) {
+    for (int it = 0; it < 2; ++it) {
         int tn = (int)threadIdx.x;
         asm volatile("" : "+v"(tn));     // (the same number, as far as the compiler can tell a new one per group)
-        search2_body<SPREAD, ALLREFS, true, (ITER > 1 && ALLREFS)>(a, grp * ITER + it, ref_idx, tn);
+        search2_body<true>(a, grp * 2 + it, 0, tn);
     }
 }
+// One video: grid (groups, references), one group and one reference per workgroup -- its launch is a few rounds of workgroups long, and
+// longer workgroups make its end ragged (53.0 against 54.3 us with two groups each).
 // (waves_per_eu, here as on the batched forms: left to __launch_bounds__(256, 4) the register allocator takes 74 registers for the two-group
-// form -- six waves per SIMD -- where it fits the same code into 72 when told to; the one-group form, the default for one video, has 57
-// either way.  The MFMAs' results still land in VGPRs, no v_accvgpr_read per result: tests/test_kernel_resources.py pins zero AGPRs.)
-template <bool SPREAD, int ITER>
+// form -- six waves per SIMD -- where it fits the same code into 72 when told to; this form has 57 either way.  The MFMAs' results still
+// land in VGPRs, no v_accvgpr_read per result: tests/test_kernel_resources.py pins zero AGPRs.)
 __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2(S2Args a) {
     const unsigned long long first = launch_clock_first_thread();
     launch_clock_begin(a.clk);
-    search2_groups<SPREAD, ITER, false>(a, xcd_band(blockIdx.x, gridDim.x), blockIdx.y);
+    search2_body<false>(a, xcd_band(blockIdx.x, gridDim.x), blockIdx.y, (int)threadIdx.x);
     launch_clock_end(a.clk, first);
 }
 static_assert(sizeof(BatchOf<S2Args>) <= 4096, "a batch's argument blocks travel in the 4 KiB kernel-argument segment");
-// The batched forms: grid (groups, 1, contexts), every enabled reference of the context inside the workgroup (ALLREFS)
-template <bool SPREAD, int ITER>
+// The batched forms: grid (pairs of groups, 1, contexts), every enabled reference of the context inside the workgroup
 __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2_b(BatchOf<S2Args> b) {
     const unsigned long long first = launch_clock_first_thread();
     launch_clock_begin(b.item[0].clk);
-    search2_groups<SPREAD, ITER, true>(b.item[blockIdx.z], xcd_band(blockIdx.x, gridDim.x), 0);
+    search2_two_groups(b.item[blockIdx.z], xcd_band(blockIdx.x, gridDim.x));
     launch_clock_end(b.item[0].clk, first);
 }
 // The same launch carrying the loop-filter strength scans of its members' NEW frames (kernels_rc_dev.h): the workgroups behind the
-// nbx block groups.  With the part full a launch of the scan's own holds the batch's stream for 0.4-0.7 ms where its
+// nbx searching workgroups.  With the part full a launch of the scan's own holds the batch's stream for 0.4-0.7 ms where its
 // work is 15 us (every workgroup waits for a place) -- the headline without that launch: +4 %, scripts/ab_flags_experiments.sh -- and
 // the shorter launches of the chain cannot absorb it either (in the pyramid's launch it made THAT link the long one: -2 %).  This is
 // the frame's longest launch, the scan's result is wanted by k_mb, which comes next, and the scan's 136 workgroups per frame ride
@@ -463,7 +452,6 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) voi
 struct S2Scans { rc::ScanCore item[MAX_BATCH]; uint32_t mask; int nbx, wgs; };
 static_assert(sizeof(BatchOf<S2Args>) + sizeof(S2Scans) <= 4096, "the kernel-argument segment");
 // (waves_per_eu: with the scans' body in the same function the register allocator otherwise settles at 76 -- six waves per SIMD; told to, it fits the same code into 70)
-template <bool SPREAD, int ITER>
 __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) void k_search2_bs(BatchOf<S2Args> b, S2Scans sc) {
     if ((int)blockIdx.x >= sc.nbx) {
         const int wg = (int)blockIdx.x - sc.nbx;
@@ -472,23 +460,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(256) voi
     }
     const unsigned long long first = launch_clock_first_thread();
     launch_clock_begin(b.item[0].clk);
-    search2_groups<SPREAD, ITER, true>(b.item[blockIdx.z], xcd_band(blockIdx.x, sc.nbx), 0);
+    search2_two_groups(b.item[blockIdx.z], xcd_band(blockIdx.x, sc.nbx));
     launch_clock_end(b.item[0].clk, first);
-}
-// Persistent form: a grid no larger than what the part holds at once, every workgroup walking the (context, reference,
-// block group) space with a stride.  A command-processor pipe stays busy with a launch until its last workgroup is
-// placed -- for a grid of tens of thousands of workgroups on a full chip that is the kernel's whole duration, and the
-// pipe's other queues wait (the kernel trace of eight busy streams shows 3.6 kernels running and every stream idle half of
-// the time, ~0.26 ms between a kernel's end and its successor's start).  A grid that fits is placed at once.
-__global__ __launch_bounds__(256, 4) void k_search2_p(BatchOf<S2Args> b, int nbx, int maxrefs, int total) {
-    for (int w = blockIdx.x; w < total; w += gridDim.x) {
-        const int item = w / (nbx * maxrefs), rem = w - item * (nbx * maxrefs);
-        const int ref_idx = rem / nbx, wg_x = rem - ref_idx * nbx;
-        // (the table form, READ: this loop is the group loop and the reference loop in one, and with the fields read the form takes 66 registers
-        // where computing them across the loop took 79)
-        search2_body<false, false>(b.item[item], wg_x, ref_idx, (int)threadIdx.x);
-        lds_fence();   // the next round reuses this workgroup's LDS: every read of this round has returned
-    }
 }
 
 // test tap: round_pack4 over caller-supplied values, a lane four quadruples (its "sixteen results" of an MFMA: q = 0..3 as the passes call it)
@@ -535,19 +508,6 @@ static S2Args search2_args(const CodingItem &it, unsigned long long *clk) {
     a.nblk = a.w * a.h / 64;
     return a;
 }
-// VP8HIP_S2_SPREAD=0: lane = candidate through all four rounds, as it was (same-box A/B runs)
-static bool search2_spread() {
-    static const bool on = [] { const char *v = getenv("VP8HIP_S2_SPREAD"); return !(v && v[0] == '0'); }();
-    return on;
-}
-// VP8HIP_S2_ITER=1/2: groups of eight blocks a workgroup takes one after the other (same-box A/B runs).  Batches: two, each through every
-// enabled reference -- up to six passes of the body per workgroup (four took the registers past seven waves per SIMD, and a workgroup of
-// twelve passes makes the launch's end ragged).  One video: one -- its launch is a few rounds of workgroups long, and longer workgroups make
-// its end ragged (53.0 against 54.3 us)
-static int search2_iter(bool batch) {
-    static const int forced = [] { const char *v = getenv("VP8HIP_S2_ITER"); const int k = v && v[0] ? atoi(v) : 0; return k == 1 || k == 2 ? k : 0; }();
-    return forced ? forced : (batch ? 2 : 1);
-}
 static bool search2_skip() {
     static const bool skip = experiment_skip("s2");
     return skip;   // timing experiment only
@@ -556,10 +516,7 @@ static bool search2_skip() {
 void launch_search2(hipStream_t s, const CodingItem &it, unsigned long long *clk) {
     const S2Args a = search2_args(it, clk);
     if (a.nrefs == 0 || search2_skip()) return;
-    const int nbx = (a.nblk + 7) / 8;
-    if (!search2_spread()) VP8_LAUNCH((k_search2<false, 1>), dim3(nbx, a.nrefs), dim3(256), 0, s, a);
-    else if (search2_iter(false) == 2) VP8_LAUNCH((k_search2<true, 2>), dim3((nbx + 1) / 2, a.nrefs), dim3(256), 0, s, a);
-    else VP8_LAUNCH((k_search2<true, 1>), dim3(nbx, a.nrefs), dim3(256), 0, s, a);
+    VP8_LAUNCH(k_search2, dim3((a.nblk + 7) / 8, a.nrefs), dim3(256), 0, s, a);
 }
 
 bool launch_search2_batch(hipStream_t s, const CodingItem *items, int n, unsigned long long *clk) {
@@ -571,12 +528,6 @@ bool launch_search2_batch(hipStream_t s, const CodingItem *items, int n, unsigne
         maxrefs = b.item[i].nrefs > maxrefs ? b.item[i].nrefs : maxrefs;
     }
     if (maxrefs == 0 || search2_skip()) return false;
-    const int nbx = (b.item[0].nblk + 7) / 8;
-    const int persist = persistent_workgroups();
-    if (persist > 0 && nbx * maxrefs * n > persist) {
-        VP8_LAUNCH(k_search2_p, dim3(persist), dim3(256), 0, s, b, nbx, maxrefs, nbx * maxrefs * n);
-        return false;
-    }
     S2Scans sc;
     sc.mask = 0;
     for (int i = 0; i < n; ++i) {      // (a request's plane is the member's current luma: what the kernel reads as b.item[i].cur)
@@ -584,18 +535,14 @@ bool launch_search2_batch(hipStream_t s, const CodingItem *items, int n, unsigne
         sc.mask |= 1u << i;
         sc.item[i] = rc::scan_core(*items[i].scan);
     }
-    const int iter = search2_spread() ? search2_iter(true) : 1, ngrp = (nbx + iter - 1) / iter;     // workgroups that search: each takes `iter` groups of eight blocks
+    const int ngrp = ((b.item[0].nblk + 7) / 8 + 1) / 2;     // workgroups that search: each takes two groups of eight blocks
     if (!sc.mask) {
-        if (!search2_spread()) VP8_LAUNCH((k_search2_b<false, 1>), dim3(nbx, 1, n), dim3(256), 0, s, b);
-        else if (iter == 2) VP8_LAUNCH((k_search2_b<true, 2>), dim3(ngrp, 1, n), dim3(256), 0, s, b);
-        else VP8_LAUNCH((k_search2_b<true, 1>), dim3(nbx, 1, n), dim3(256), 0, s, b);
+        VP8_LAUNCH(k_search2_b, dim3(ngrp, 1, n), dim3(256), 0, s, b);
         return false;
     }
     sc.nbx = ngrp;
     sc.wgs = (b.item[0].h + rc::ROWS_PER_BLOCK - 1) / rc::ROWS_PER_BLOCK;
-    if (!search2_spread()) VP8_LAUNCH((k_search2_bs<false, 1>), dim3(nbx + sc.wgs, 1, n), dim3(256), 0, s, b, sc);
-    else if (iter == 2) VP8_LAUNCH((k_search2_bs<true, 2>), dim3(ngrp + sc.wgs, 1, n), dim3(256), 0, s, b, sc);
-    else VP8_LAUNCH((k_search2_bs<true, 1>), dim3(nbx + sc.wgs, 1, n), dim3(256), 0, s, b, sc);
+    VP8_LAUNCH(k_search2_bs, dim3(ngrp + sc.wgs, 1, n), dim3(256), 0, s, b, sc);
     return true;
 }
 

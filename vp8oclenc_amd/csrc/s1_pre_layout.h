@@ -1,4 +1,4 @@
-// Where the whole-pel search's loop form (kernels_me.hip: k_search1_pl, k_search1_pl_b, k_search1_plr_b) keeps the current blocks' share of the metric
+// Where the whole-pel search's loop form (kernels_me.hip: k_search1_pl, k_search1_plr_b) keeps the current blocks' share of the metric
 // in LDS: s_pre[wave][block slot][sub-block][16 ints], twelve block slots per wave, made by s1_make_pre and read back as the C input of the
 // metric's MFMA, 16 ints = four ds_read_b128 per candidate.  Lane l of a wave reads block slot l / 5 (five lanes per block; lanes 60-63 have no block
 // and read slot 0), while the sub-block sb and the quad j are the same for the whole wave: the lanes of one read differ ONLY in their slot.

@@ -103,9 +103,6 @@ S2_LANE_HD constexpr int s2_cost_dst(int t) {                                   
 S2_LANE_HD constexpr int s2_cost_q3_read(int t) {                                      // s_HT (q3): the candidate's fourth-block cost
     return s2_slot(t) * S2_HT_SLOT_BYTES + (S2_Q3_WORD + (s2_lane(t) < 26 ? s2_lane(t) : 31)) * 4;
 }
-// without the spread: lane = candidate through all four 4x4 blocks (+ V_ROW * 4 each), the idle lanes on the zero-vector block with lane 25
-S2_LANE_HD constexpr int s2_cost_src_plain(int t) { return s2_slot(t) * S2_V_SLOT_BYTES + (s2_lane(t) < V_ZERO ? s2_lane(t) : V_ZERO) * V_CAND * 4; }
-S2_LANE_HD constexpr int s2_cost_pre_plain(int t) { return s2_slot(t) * S2_PRE_SLOT_BYTES; }     // s_pre: 4x4 block bb at + 64 bb
 // the one wave of the fourth-block round: 4x4 block 3 of candidates 18..25 of all eight slots, lane = (slot, candidate)
 S2_LANE_HD constexpr int s2_extra_slot(int t) { return s2_wave_lane(t) >> 3; }
 S2_LANE_HD constexpr int s2_extra_cand(int t) { return 18 + (t & 7); }
@@ -188,7 +185,7 @@ constexpr bool s2_table_unpacks() {
 }
 constexpr bool s2_aligned16() {      // the 16-byte reads and stores
     for (int t = 0; t < S2_THREADS; ++t) {
-        if ((s2_win_store(t) | s2_aw_read(t) | s2_cost_src(t) | s2_cost_step(t) | s2_cost_pre(t) | s2_cost_src_plain(t) | s2_cost_pre_plain(t) | s2_extra_src(t) | s2_extra_pre(t) |
+        if ((s2_win_store(t) | s2_aw_read(t) | s2_cost_src(t) | s2_cost_step(t) | s2_cost_pre(t) | s2_extra_src(t) | s2_extra_pre(t) |
              s2_pre_cols(t) | s2_pre_store(t) | s2_k_row(t)) & 15) return false;
         for (int i = 0; i < 3; ++i)
             if (s2_hv_read(t, i) & 15) return false;

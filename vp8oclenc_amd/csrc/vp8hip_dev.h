@@ -143,8 +143,6 @@ inline const char *experiment_env(const char *name) { return getenv(name); }
 inline bool experiment_skip(const char *) { return false; }
 inline const char *experiment_env(const char *) { return nullptr; }
 #endif
-// workgroups of a persistent launch (0 = launch the full grid); VP8HIP_PERSIST overrides (same-box A/B runs)
-int persistent_workgroups();
 
 // ---- launchers (kernels_*.hip) ---------------------------------------------------------------
 void launch_border(hipStream_t s, const Frame &f);
@@ -310,7 +308,6 @@ struct FilterItem {
     unsigned launch_no;
     LfCheck chk;
 };
-bool launch_search1_coarse_batch(hipStream_t s, const CodingItem *items, int n, int net_width, bool finest, bool top_only = false);
 void launch_search1_batch(hipStream_t s, const CodingItem *items, int n, int level, int src_idx, int net_width);
 // Members with a scan get their loop-filter strength scan + segment data in this launch.  Returns false if the scans were NOT
 // carried (nothing to search, or the persistent form): the caller launches them on their own.
@@ -322,9 +319,9 @@ void launch_loop_filter3_batch(hipStream_t s, const FilterItem *items, int n, in
 void launch_loop_filter4_batch(hipStream_t s, const FilterItem *items, int n, int mbw, int mbh, bool conformant = false);
 void launch_auto_segments_batch(hipStream_t s, const ScanRequest *q, int n);
 // The forms of ONE video (kernels of their own; the argument blocks are made as the batched forms make them).
-// levels 4, 3, 2, 1 (and, finest, 0) in ONE launch (kernels_me.hip, k_search1_coarse); leaves the level-1 / level-0 nets where the per-level launches leave them
-void launch_search1_coarse(hipStream_t s, const CodingItem &it, int net_width, bool finest);
-void launch_search1(hipStream_t s, const CodingItem &it, int level, int src_idx, int net_width, bool latency = false);   // latency: the short-wave mapping whatever the size
+// levels 4, 3, 2, 1 in ONE launch (kernels_me.hip, k_search1_coarse); leaves the level-1 net where the per-level launches leave it
+void launch_search1_coarse(hipStream_t s, const CodingItem &it, int net_width);
+void launch_search1(hipStream_t s, const CodingItem &it, int level, int src_idx, int net_width);
 void launch_search2(hipStream_t s, const CodingItem &it, unsigned long long *clk = nullptr);
 void launch_weight_tap(hipStream_t s, const int32_t *d, int n, int32_t *out);
 void launch_weight_tap_mfma(hipStream_t s, const int32_t *d, int n, int32_t *out);
