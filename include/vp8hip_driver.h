@@ -136,6 +136,7 @@ int vp8drv_get_frame_end(vp8drv *d, uint8_t *out, size_t capacity, size_t *size)
 typedef struct vp8drv_batch vp8drv_batch;
 int vp8drv_batch_create(vp8drv_batch **out, vp8drv *const *drv, int n);
 void vp8drv_batch_destroy(vp8drv_batch *b);      /* the drivers stay */
+int vp8drv_batch_lane(const vp8drv_batch *b);    /* vp8hip_batch_lane of the batch underneath: the chain stream it shares, -1 = its own */
 int vp8drv_batch_encode_frame_device(vp8drv_batch *b, const int *members /* NULL = all; 0 = this member sits the call out */,
                                      const void *const *y, const void *const *u, const void *const *v, const int *force_key, int *was_key);
 /* ... with the members' frames in host memory (vp8hip_batch_upload_current: tight planes of the source size, page-locked for the copies

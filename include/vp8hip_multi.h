@@ -114,6 +114,13 @@ int vp8hip_group_last_hip_error(const vp8hip_group *g);
 typedef struct vp8hip_batch vp8hip_batch;
 int vp8hip_batch_create(vp8hip_batch **out, vp8hip_ctx *const *ctxs, int n);
 void vp8hip_batch_destroy(vp8hip_batch *b);      /* the contexts stay, each back on its own stream; destroy a batch before its members */
+/* The batch's stream is a LANE: one of L = min(vp8hip_hw_queues(), 8) streams per device that the library makes at the device's first
+ * vp8hip_batch_create and destroys with its last batch.  A new batch takes the lowest-numbered lane with the fewest batches (batch i
+ * lane i mod L while none has been destroyed), so with more batches than hardware queues the chains share the queues evenly instead of
+ * as the runtime's stream bookkeeping happens to place them.  Batches on one lane are independent work in one in-order stream: advance
+ * each from its own host thread, as before.  Returns the lane's index, or -1 for a batch with a stream to itself
+ * (VP8HIP_BATCH_LANES=0 in the environment, read once: a stream per batch, for A/B runs) and for NULL. */
+int vp8hip_batch_lane(const vp8hip_batch *b);
 int vp8hip_batch_set_current_device(vp8hip_batch *b, const int *active, const void *const *y, const void *const *u, const void *const *v);
 /* The same from HOST memory -- the reference's own hand-over (clEnqueueWriteBuffer of the frame it has read, vp8enc.cpp:386-388) for a
  * batch: tight planes of the source size, copied on a stream of the batch's own into staging buffers (two per member, made on the first

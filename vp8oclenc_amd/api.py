@@ -22,7 +22,7 @@ DBG_NET1, DBG_NET2, DBG_BDIFF, DBG_PYRAMID, DBG_MB_MASK, DBG_MB_NZ, DBG_THIRD_CO
 # every symbol include/vp8hip.h and include/vp8hip_host.h declare
 ABI_SYMBOLS = [
     "vp8hip_hw_queues", "vp8hip_profile_read_clock", "vp8hip_inter_search", "vp8hip_inter_finish", "vp8hip_export_search",
-    "vp8hip_import_search", "vp8hip_export_last", "vp8hip_import_last", "vp8hip_group_rendezvous", "vp8hip_group_create", "vp8hip_group_destroy", "vp8hip_group_rank", "vp8hip_group_world", "vp8hip_group_count", "vp8hip_group_barrier", "vp8hip_group_max", "vp8hip_group_all_gather", "vp8hip_group_broadcast", "vp8hip_group_gather_bytes", "vp8hip_group_last_hip_error", "vp8hip_batch_create", "vp8hip_batch_destroy", "vp8hip_batch_set_current_device",
+    "vp8hip_import_search", "vp8hip_export_last", "vp8hip_import_last", "vp8hip_group_rendezvous", "vp8hip_group_create", "vp8hip_group_destroy", "vp8hip_group_rank", "vp8hip_group_world", "vp8hip_group_count", "vp8hip_group_barrier", "vp8hip_group_max", "vp8hip_group_all_gather", "vp8hip_group_broadcast", "vp8hip_group_gather_bytes", "vp8hip_group_last_hip_error", "vp8hip_batch_create", "vp8hip_batch_destroy", "vp8hip_batch_lane", "vp8drv_batch_lane", "vp8hip_batch_set_current_device",
     "vp8hip_batch_auto_segments", "vp8hip_batch_inter_transform", "vp8hip_batch_loop_filter", "vp8drv_batch_create", "vp8drv_batch_destroy",
     "vp8drv_batch_encode_frame_device", "vp8hip_batch_encode_frame_begin", "vp8drv_batch_get_frame_begin", "vp8hip_profile_context_switches", "vp8hip_profile_read_search2_clock", "vp8hip_profile_search2_clock",
     "vp8hip_create", "vp8hip_destroy", "vp8hip_upload_current", "vp8hip_set_current_device", "vp8hip_upload_last",
@@ -1569,6 +1569,11 @@ class NativeBatch:
         if rc != 0:
             raise Vp8HipError(f"vp8drv_batch_scan_result: {self.lib.vp8hip_status_string(rc).decode()} ({rc})")
         return [(ud[i], vd[i]) if self._members[i] else None for i in range(self.n)]
+
+    def lane(self) -> int:
+        """the chain stream (lane) this batch shares with other batches of its device, -1 = a stream of its own (vp8drv_batch_lane)"""
+        self.lib.vp8drv_batch_lane.argtypes = [C.c_void_p]
+        return int(self.lib.vp8drv_batch_lane(self.h))
 
     def ready(self) -> bool:
         """no member's check_SSIM verdict is still on its way: the next encode_frame_device would not wait (vp8drv_batch_ready)"""

@@ -9,7 +9,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvp8hip.so")
 SOURCES = ["api_context.hip", "api_intake.hip", "api_inter.hip", "api_entropy.hip", "api_batch.hip", "api_shard.hip", "api_profile.hip", "kernels_me.hip", "kernels_scale.hip", "kernels_compose.hip", "kernels_denoise.hip", "api_denoise.hip", "kernels_analysis.hip", "api_analysis.hip", "kernels_aq.hip", "api_segment.hip", "kernels_arf.hip", "api_arf.hip", "kernels_convert.hip", "kernels_deinterlace.hip", "api_deinterlace.hip", "kernels_geometry.hip", "api_geometry.hip", "kernels_overlay.hip", "api_overlay.hip", "kernels_s2.hip", "kernels_mb.hip", "kernels_lf3.hip", "kernels_lf4.hip", "kernels_lf_simple.hip", "kernels_quality.hip", "api_quality.hip", "kernels_entropy_stage.hip", "kernels_rc.hip", "kernels_intra.hip", "vp8_host.cpp", "vp8_driver.cpp", "vp8_bitstream.cpp"]
-HEADERS = ["vp8hip_ctx.h", "vp8hip_dev.h", "intake_settings.h", "driver_settings.h", "kernels_rc_dev.h", "lf_shared.h", "lf_banded.h", "lds_bank_model.h", "s1_pre_layout.h", "s1_fill_layout.h", "s2_lane_layout.h", "vp8_rfc6386_tables.inc", "vp8_mbhdr.h", "kernels_ent.hip", "kernels_hdr.hip"]   # the two .hip files are included by kernels_entropy_stage.hip
+HEADERS = ["vp8hip_ctx.h", "vp8hip_dev.h", "intake_settings.h", "driver_settings.h", "batch_lanes.h", "kernels_rc_dev.h", "lf_shared.h", "lf_banded.h", "lds_bank_model.h", "s1_pre_layout.h", "s1_fill_layout.h", "s2_lane_layout.h", "vp8_rfc6386_tables.inc", "vp8_mbhdr.h", "kernels_ent.hip", "kernels_hdr.hip"]   # the two .hip files are included by kernels_entropy_stage.hip
 HEADERS = HEADERS + [os.path.join("..", "..", "include", h) for h in ("vp8hip.h", "vp8hip_multi.h", "vp8hip_taps.h", "vp8hip_host.h", "vp8hip_driver.h", "vp8hip_bitstream.h")]
 
 

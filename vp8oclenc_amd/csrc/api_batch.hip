@@ -1,10 +1,82 @@
 // api_batch.hip -- batched contexts: up to MAX_BATCH contexts of one geometry advance one frame together, every stage ONE launch (vp8hip_batch_*).
 // The stages are those of api_inter.hip / api_entropy.hip; what a host with many GOP chunks in flight uses instead of a stream per chunk.
 #include "vp8hip_ctx.h"
+#include "batch_lanes.h"
+
+#include <mutex>
 
 using namespace vp8;
 
 namespace vp8 {
+
+// ---- lanes: the chain streams of a device's batches ------------------------------------------------------------------------
+// Which hardware queue a stream lands on is the runtime's bookkeeping (it counts the streams on each queue and gives a new stream
+// the queue with the fewest; idle streams count).  A stream per batch, made when the batch is -- between the members' own streams
+// going, six at a time -- left it to that sequence which chains shared a queue, and with fewer queues than batches some queues got
+// three chains and others one.  The library owns the mapping instead: L = lane_count(vp8hip_hw_queues()) streams per device, made
+// TOGETHER at the device's first vp8hip_batch_create BEFORE any member's own stream is retired (the runtime's counts are then as
+// even as the host's streams left them, and L streams made in a row go to L different queues), handed to the batches by pick_lane
+// (batch_lanes.h), reference-counted and destroyed with the device's last batch.  Two batches on one lane are independent work in
+// one in-order queue: each batch's own order is its host thread's, and what one of them waits for on the lane (an event of a side
+// stream) the other waits for too -- as it did when their streams shared a hardware queue.
+// VP8HIP_BATCH_LANES=0 (read once): a stream per batch as before, for A/B runs.
+struct LanePool {
+    hipStream_t s[MAX_LANES] = {};
+    int load[MAX_LANES] = {};
+    int lanes = 0;       // 0: not made
+    int batches = 0;
+};
+static std::mutex g_lane_mu;
+static LanePool g_lane_pool[64];      // by device ordinal (a device beyond them gets a stream per batch)
+
+static bool lanes_enabled() {
+    static const bool on = [] { const char *v = getenv("VP8HIP_BATCH_LANES"); return !(v && v[0] == '0'); }();
+    return on;
+}
+// The batch's chain stream: a lane (b->lane >= 0) or a stream of its own.  The device is current.
+static bool batch_take_stream(vp8hip_batch *b, int device) {
+    if (!lanes_enabled() || device < 0 || device >= 64) {
+        if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) return false;
+        ++g_live_contexts;
+        return true;
+    }
+    std::lock_guard<std::mutex> lock(g_lane_mu);
+    LanePool &p = g_lane_pool[device];
+    if (!p.lanes) {
+        const int want = lane_count(vp8hip_hw_queues());
+        for (int l = 0; l < want; ++l)
+            if (hipStreamCreateWithFlags(&p.s[l], hipStreamNonBlocking) != hipSuccess) {
+                while (l-- > 0) { hipStreamDestroy(p.s[l]); p.s[l] = nullptr; }
+                return false;
+            }
+        p.lanes = want;
+    }
+    const int l = pick_lane(p.load, p.lanes);
+    if (p.load[l]++ == 0) ++g_live_contexts;
+    ++p.batches;
+    b->lane = l;
+    b->stream = p.s[l];
+    return true;
+}
+// ... given back: everything of this batch on it is over; a lane stays while any batch of the device lives.
+static void batch_release_stream(vp8hip_batch *b, int device) {
+    if (!b->stream) return;
+    hipStreamSynchronize(b->stream);
+    if (b->lane < 0) {
+        hipStreamDestroy(b->stream);
+        --g_live_contexts;
+    } else {
+        std::lock_guard<std::mutex> lock(g_lane_mu);
+        LanePool &p = g_lane_pool[device];
+        if (--p.load[b->lane] == 0) --g_live_contexts;
+        if (--p.batches == 0) {
+            for (int l = 0; l < p.lanes; ++l) { hipStreamDestroy(p.s[l]); p.s[l] = nullptr; }
+            p.lanes = 0;
+        }
+    }
+    b->stream = nullptr;
+    b->lane = -1;
+}
 
 // A batch's second stream for the entropy stage, made when the first frame is asked for as bytes (a batch that only runs the
 // inter path never has one: idle streams still take part in the runtime's stream -> hardware queue assignment).
@@ -68,31 +140,30 @@ int vp8hip_batch_create(vp8hip_batch **out, vp8hip_ctx *const *ctxs, int n) {
     if (!b) return VP8HIP_ERR_ARG;
     USE_DEVICE(ctxs[0]);
     b->n = n;
-    // Idle streams still take part in the runtime's stream -> hardware queue assignment: with 32 contexts' own streams
-    // alive, two of eight batch streams could land on one queue and serialise (a slow mode of 0.21 instead of 0.16 ms per
-    // frame in one run out of four).  The members' own streams go, the batch gets a new one -- batches made one after the
-    // other then sit on consecutive queues -- and vp8hip_batch_destroy gives every member a stream of its own again.
+    // The chain's stream is a lane of the device's pool (above): batch number i of the device on lane i mod L, so eight batches at
+    // four hardware queues are two per lane, and at sixteen queues eight lanes carry one batch each -- the streams of before in
+    // effect.  The lanes are made (first batch of the device) while the members' own streams are all still alive.  TRACED in
+    // bench.py's order -- six contexts, then their batch, eight times: four lanes on four different queues, two chains each
+    // (profiles/queue_lanes_parent_vs_this.txt).  NOT traced, an argument from the runtime's least-used rule only: a host that
+    // makes all its contexts first (48: twelve per queue) gets distinct queues too, which it would not if the first batch's six
+    // streams went before the lanes came (10 / 10 / 12 / 12).  Idle streams still take part in the runtime's assignment, so the
+    // members' own streams go once the batch has its lane, and vp8hip_batch_destroy gives every member a stream of its own again.
+    if (!batch_take_stream(b, ctxs[0]->device)) {      // (nothing of the members has changed)
+        delete b;
+        return VP8HIP_ERR_HIP;
+    }
     for (int i = 0; i < n; ++i) {
         hipStreamSynchronize(ctxs[i]->stream);
         if (ctxs[i]->own_stream) hipStreamDestroy(ctxs[i]->own_stream);
         ctxs[i]->own_stream = nullptr;
     }
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) {
-        for (int i = 0; i < n; ++i) {
-            hipStreamCreateWithFlags(&ctxs[i]->own_stream, hipStreamNonBlocking);
-            ctxs[i]->stream = ctxs[i]->own_stream;
-        }
-        delete b;
-        return VP8HIP_ERR_HIP;
-    }
     for (int i = 0; i < n; ++i) {
         ctxs[i]->stream = b->stream;
         ctxs[i]->batch = b;
         b->c[i] = ctxs[i];
-        if (ctxs[i]->counted) --g_live_contexts;   // the batch's one stream is counted in their place
+        if (ctxs[i]->counted) --g_live_contexts;   // the batch's lane is counted in their place (batch_take_stream)
         ctxs[i]->counted = false;
     }
-    ++g_live_contexts;
     // the head-of-frame stream (VP8HIP_BATCH_PREP): 0 (default) = none, the head of the frame stays at the head of the chain;
     // 1 = one per batch, in the lowest priority class; 2 = one for all batches of the process.  Measured on MI355X, 48 chunks
     // in 8 batches, same box: 62.2 M MB/s without, 59.5 with one per batch (59.9 in the default priority class), 60.9 with one
@@ -129,8 +200,9 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
     if (!b) return;
     hipSetDevice(b->c[0]->device);
     if (b->prep) hipStreamSynchronize(b->prep);
-    hipStreamSynchronize(b->stream);
-    hipStreamDestroy(b->stream);
+    // the chain's stream is synchronised and, where it is a lane, only given back: a lane other batches still use stays (whatever
+    // of theirs was enqueued by now is waited for too, nothing more)
+    batch_release_stream(b, b->c[0]->device);
     if (b->prep && !b->prep_shared) hipStreamDestroy(b->prep);
     if (b->ev_gate) hipEventDestroy(b->ev_gate);
     if (b->ev_gate2) hipEventDestroy(b->ev_gate2);
@@ -151,7 +223,6 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
     if (b->ev_ent) hipEventDestroy(b->ev_ent);
     if (b->ev_chroma) hipEventDestroy(b->ev_chroma);      // (the stream has been synchronised: a member's pending scan has its sums)
     for (int i = 0; i < b->n; ++i) b->c[i]->frame_event = nullptr;
-    --g_live_contexts;
     for (int i = 0; i < b->n; ++i) {
         b->c[i]->batch = nullptr;
         if (!b->c[i]->own_stream) hipStreamCreateWithFlags(&b->c[i]->own_stream, hipStreamNonBlocking);
@@ -161,6 +232,8 @@ void vp8hip_batch_destroy(vp8hip_batch *b) {   // the contexts stay (destroy the
     }
     delete b;
 }
+
+int vp8hip_batch_lane(const vp8hip_batch *b) { return b ? b->lane : -1; }
 
 // the copy stream, its events and the members' staging buffers (two each), made on first use and again when the source size has changed
 static int batch_stage_ready(vp8hip_batch *b) {

@@ -106,7 +106,9 @@ int make_last(vp8hip_ctx *c, const void *y, const void *u, const void *v, hipMem
     return VP8HIP_OK;
 }
 
-std::atomic<int> g_live_contexts{0};   // contexts that launch on a stream of their own (members of a batch share one)
+// chain streams in use: a context on a stream of its own counts one; the members of a batch do not, their batch's LANE does, once,
+// however many batches share it (api_batch.hip: a lane is one in-order stream; a batch with a stream to itself counts one)
+std::atomic<int> g_live_contexts{0};
 
 // Contexts overlap only if their streams sit on different hardware queues, and the HIP runtime multiplexes all streams of a process
 // onto GPU_MAX_HW_QUEUES queues (default 4), read once when the runtime initialises at the process's first HIP call.  The reference
@@ -245,7 +247,8 @@ void batch_join_prep(vp8hip_batch *b) {
     (void)hipStreamWaitEvent(b->stream, b->ev_prep, 0);
 }
 // (NOT wait_for_seq: this is no result somebody asked for -- it gives up silently as soon as the filter's stream is idle and sets no
-// error; the entry point that follows reports a stream that failed)
+// error; the entry point that follows reports a stream that failed.  The filter's stream may be a shared lane, as for wait_for_seq:
+// idle still means it has run, busy with another batch's work only delays the giving up)
 void side_stream_ordered(vp8hip_ctx *c) {
     if (!c->lf_pending || !c->fork_by_verdict) return;
     const uint32_t want = c->verdict_seq;
@@ -285,6 +288,10 @@ int check_device_timeout(vp8hip_ctx *c) {
 // A launch writes its record into host memory the device sees and the sequence number last, at system scope: the host polls that word
 // and needs no event.  Every few thousand polls it looks whether the stream is still alive: a stream that is idle (or has failed)
 // while the word -- looked at once more -- is still not there never ran the launch's last workgroup.
+// The stream may be a LANE that the batch shares with other batches (api_batch.hip).  An idle lane proves the same: the launch was
+// enqueued on it before this wait began, and a lane with nothing left to run has run it.  A busy lane may be busy with the OTHER
+// batch's launches only, which proves nothing and is taken as "not yet": the time-out verdict then comes when the lane drains,
+// later than on a stream of the batch's own, never wrongly, and the wait stays bounded by the work enqueued on the lane.
 int wait_for_seq(vp8hip_ctx *c, const uint32_t *word, uint32_t want, hipStream_t s) {
     for (unsigned spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != want; ++spins) {
         if ((spins & 0xfff) == 0xfff) {

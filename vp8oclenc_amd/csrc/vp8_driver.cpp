@@ -664,6 +664,8 @@ void vp8drv_batch_destroy(vp8drv_batch *b) {
     delete b;
 }
 
+int vp8drv_batch_lane(const vp8drv_batch *b) { return b ? vp8hip_batch_lane(b->hb) : -1; }
+
 static int batch_encode_frame(vp8drv_batch *b, const int *members, const void *const *y, const void *const *u, const void *const *v,
                               const int *force_key, int *was_key, bool host) {
     if (!b || !y || !u || !v) return VP8HIP_ERR_ARG;
@@ -1124,6 +1126,10 @@ static int batches_encode_frames(vp8drv_batch *const *batches, int nbatches, int
     // arrives at the same moment, every next frame is enqueued at the same moment -- and then all the latency-bound loop filters run
     // at once with nothing wide beside them: 55.3-59.0 M MB/s from run to run on one box; with the starts a fraction of a frame
     // apart the batches stay staggered: 60.2-60.6 (800 us apart: 60.1-60.4).  VP8DRV_STAGGER_US overrides (experiments).
+    // A thread per batch also where two batches share a chain stream (a lane, vp8hip_batch_lane): the two are independent work in one
+    // in-order stream, each batch's own order is its thread's, and nothing here waits on a batch's stream being empty of OTHER work
+    // (finish() below synchronises the lane, which then includes what the other batch had enqueued by then -- it ends, since that
+    // batch's thread never waits for this one).
     static const int stagger_us = [] { const char *v = getenv("VP8DRV_STAGGER_US"); return v ? atoi(v) : 200; }();
     for (int k = 0; k < nbatches; ++k)
         th.emplace_back([&, k] {

@@ -318,7 +318,8 @@ struct vp8hip_ctx {
 struct vp8hip_batch {
     int n = 0;
     vp8hip_ctx *c[vp8::MAX_BATCH] = {};
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;        // the chain's stream: a lane of the device's pool (shared with other batches), or the batch's own
+    int lane = -1;                       // which lane of the pool (api_batch.hip, batch_lanes.h); -1: `stream` is this batch's alone
     hipStream_t prep = nullptr;          // nullptr: everything on `stream` (VP8HIP_BATCH_PREP=0)
     bool prep_shared = false;            // prep is the process-wide one (VP8HIP_BATCH_PREP=2), not this batch's to destroy
     hipEvent_t ev_gate = nullptr;        // on `stream`, at the start of a frame call: everything of the earlier frames
@@ -389,6 +390,10 @@ static constexpr unsigned FRAME_EVENT_FLAGS = hipEventDisableTiming | hipEventRe
 // ---- per-kernel event timing --------------------------------------------------------------------
 // Stages that are ONE kernel launch get their two events recorded by the dispatch itself (VP8_LAUNCH, vp8hip_dev.h): the
 // kernel's own begin and end.  Stages made of several launches (entropy stage, intra) are bracketed with hipEventRecord.
+// On a LANE that batches share (api_batch.hip) the two kinds differ: a dispatch's own events time that kernel whatever else is on
+// the lane, and so does k_search2's launch clock (s2_clock: stamped by the launch's own workgroups into its context's words), but a
+// bracket spans whatever the other batch's thread enqueued between the two records -- the bracketed stages' times of a batch that
+// shares its lane are upper bounds.  bench.py's roofline kernels are all single-launch stages.
 constexpr uint32_t SINGLE_LAUNCH_STAGES = (1u << VP8HIP_K_PACK) | (1u << VP8HIP_K_DOWNSAMPLE) | (1u << VP8HIP_K_SEARCH1_L4) | (1u << VP8HIP_K_SEARCH1_L3) |
                                           (1u << VP8HIP_K_SEARCH1_L2) | (1u << VP8HIP_K_SEARCH1_L1) | (1u << VP8HIP_K_SEARCH1_L0) | (1u << VP8HIP_K_SEARCH2) |
                                           (1u << VP8HIP_K_MB) | (1u << VP8HIP_K_LOOP_FILTER) | (1u << VP8HIP_K_BORDER);
@@ -430,7 +435,7 @@ struct Timed {
 };
 
 // ---- api_context.hip: surfaces, parameters, stream ordering ----
-extern std::atomic<int> g_live_contexts;   // contexts that launch on a stream of their own (members of a batch share one)
+extern std::atomic<int> g_live_contexts;   // chain streams in use: contexts on a stream of their own, lanes with a batch, batches with a stream of their own
 void note_queue_oversubscription();
 int pick_free_frame(const vp8hip_ctx *c);
 int copy_in(vp8hip_ctx *c, const Plane &dst, const void *src, hipMemcpyKind kind);
